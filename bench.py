@@ -16,12 +16,16 @@ configuration the metric is quoted on.  For N > 1 the same job is sharded over t
 Both produce the same maps bit for bit (each record carries verified_vs_single_gpu and oracle_maps_equal); the row axis is
 the headline because it is the faster way to run the same job (no 33 MB collective, two-phase selection at full efficiency).
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the contract fields (metric,
+value, unit, higher_is_better, dtype, ms_per_step, ...) and nothing else; --dump-outputs DIR also writes what the last timed
+step computed (DIR/<name>.npy, float32).  With --full (implied by --pp, --box-bench and --verify) the line also carries
   roofline     - dominant kernel (k_cvf_pc): algorithmic HBM bytes per launch / its mean duration over the launches OF THE
                  TIMED REGION (time stamps the kernel takes itself, PSM_OPT_PROFILE 2 - no events, no separate pass)
   cpu_baseline - the CPU oracle (restatement of the reference pthreads path) timed on a bounded
                  sample on this box's host cores (rank 0, N=1 only); a reported baseline
   oracle_maps_equal - the maps the TIMED path left on the device == the oracle's maps of the same pair (whole D)
+and the per-step median, the PCIe legs and frame loop, per-kernel times, the single-GPU check and (N > 1) the per-rank figures
+and the other sharding axis.
 """
 import argparse
 import json
@@ -49,6 +53,8 @@ CONFIGS = {
 ALG = {"f32": {"cvf_fused": 40.0, "cvf_a": 20.0, "cvc": 4.0, "wta": 4.0, "box8": 8.0, "pipeline": 48.0},
        "u8": {"cvf_fused": 34.0, "cvf_a": 17.0, "cvc": 1.0, "wta": 1.0, "box8": 8.0, "pipeline": 36.0}}
 FORM_NAME = {0: "store", 1: "planes", 2: "keys"}
+DUMP_LIMIT = 64 * 10**6   # bytes of --dump-outputs in all; above it every array is sampled at the same seeded positions
+DUMP_SEED = 0
 
 
 def spawn_ranks(n, args):
@@ -125,6 +131,14 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: per-step median, PCIe legs and frame loop, "
+                         "per-kernel times and roofline, CPU baseline and oracle check of the maps, single-GPU check, and for N > 1 the "
+                         "per-rank figures and the other sharding axis (--pp, --box-bench and --verify imply it)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed - both disparity maps (and the validity "
+                         "masks when the step runs the left-right check; a batch stacks its pairs) - as DIR/<name>.npy in float32; "
+                         "above 64 MB in all, every array is a fixed, seeded sample of the same flat positions")
     ap.add_argument("--config", default="c4", choices=sorted(CONFIGS))
     ap.add_argument("--dtype", default="", choices=["", "f32", "u8"], help="volume element type (default: f32, u8 for the c1 configs)")
     ap.add_argument("--seg-rows", type=int, default=-1, help="marching-kernel y segment (-1: library default)")
@@ -183,8 +197,8 @@ def parse_args():
                     help="(0 = default: 1 at N = 1; 2 per rank for row stripes from N = 4 and for disparity shards from N = 2)  F contexts of the configuration, each on its own stream, take the steps in turn - frame i + 1 is queued while "
                          "frame i runs, so a frame's short kernels (prep, guidance, reduction) and the half-empty last round of its fused "
                          "launch run beside the next frame's fused kernel.  The reference's use is a frame loop (src/main.cpp:64-73); this is "
-                         "that loop with two frames in the device's queues.  Measured: -9 % at 720p x 128, -19 % at 450 x 375 x 64, nothing at "
-                         "1080p x 256 (profiles/r05/exp_frames_in_flight.txt); a rank's 1/8 share of 1080p x 256: -6 %")
+                         "that loop with two frames in the device's queues.  Measured: -9 %% at 720p x 128, -19 %% at 450 x 375 x 64, nothing at "
+                         "1080p x 256 (profiles/r05/exp_frames_in_flight.txt); a rank's 1/8 share of 1080p x 256: -6 %%")
     ap.add_argument("--shard-sim", type=int, default=0,
                     help="diagnostic: time only rank 0's share of a G-rank job on this GPU (no exchange); "
                          "the JSON line is then NOT the headline metric")
@@ -199,6 +213,12 @@ def main():
     N = args.gpus
     if N < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.shard_sim > 1:
+        raise SystemExit("bench.py: --dump-outputs: a --shard-sim run computes one share of the job, not its outputs")
+    # what the headline figure does not need runs only in a full run; the opt-in extras are parts of it
+    full = args.full or args.pp or args.box_bench or args.verify
     Wc, Hc, Dc, _ = CONFIGS[args.config]
     if args.shard == "disp" and N > Dc:
         raise SystemExit(f"bench.py: --gpus {N} exceeds the {Dc} disparity slices of config {args.config} (one shard per rank)")
@@ -306,8 +326,38 @@ def main():
                 out += [ref.lValid.copy(), ref.rValid.copy()]
         return out
 
-    def measure(shard, exchange):
-        """One timed measurement of the step under a sharding axis; returns the record (with the live context in it)."""
+    def timed_outputs(ctxs):
+        """What a caller of the timed path receives from its last step (downloaded after the timed region): both disparity maps
+        of every pair, and the validity masks when the step runs the left-right check; a batch stacks its pairs."""
+        outs = {}
+        with_valid = lrc and not use_batch and not args.fgf        # (the steps that run the check)
+        for o_ in ctxs:
+            o_.set_option(capi.PSM_OPT_ASYNC, 0)
+            got_ = [m.copy() for m in o_.download_maps()]
+            if with_valid:
+                got_ += [m.copy() for m in o_.download_valid()]
+            o_.set_option(capi.PSM_OPT_ASYNC, 1)
+            for nm, m in zip(("ldisp", "rdisp", "lvalid", "rvalid"), got_):
+                outs.setdefault(nm, []).append(m)
+        return {nm: (np.stack(v) if len(v) > 1 else v[0]) for nm, v in outs.items()}
+
+    def write_outputs(outs, out_dir):
+        arrs = {nm: np.ascontiguousarray(a, dtype=np.float32) for nm, a in outs.items()}
+        if sum(a.nbytes for a in arrs.values()) > DUMP_LIMIT:
+            # a fixed, seeded sample: the same flat positions in every array of a shape, the same from run to run
+            k = (DUMP_LIMIT - 4096) // (4 * len(arrs))
+            for nm, a in arrs.items():
+                idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=min(k, a.size), replace=False))
+                arrs[nm] = a.reshape(-1)[idx]
+            print(f"bench.py: --dump-outputs: {k} seeded sample positions per array (the whole outputs exceed {DUMP_LIMIT} bytes)",
+                  file=sys.stderr)
+        os.makedirs(out_dir, exist_ok=True)
+        for nm, a in arrs.items():
+            np.save(os.path.join(out_dir, nm + ".npy"), a)
+
+    def measure(shard, exchange, outputs=False):
+        """One timed measurement of the step under a sharding axis; returns the record (with the live context in it).
+        outputs: rank 0 keeps what the last timed step computed (rec["outputs"])."""
         rows_mode = shard == "rows" and not args.fgf and (use_dist or args.shard_sim > 1)
         parts = world if use_dist else max(args.shard_sim, 1)
         rows_max, y0, y1 = H, 0, H
@@ -500,38 +550,45 @@ def main():
 
         for _ in range(args.warmup):
             step()
-        # the fused filter kernel stamps its own start / end from here on: two atomics per workgroup, no events between the
-        # kernels - the launches of the timed region itself are what roofline reports
-        for o_ in ring:
-            o_.set_option(capi.PSM_OPT_PROFILE, 2)
-        sync()
-        for o_ in ring:
-            o_.filter_launch_times()
+        if full:
+            # the fused filter kernel stamps its own start / end from here on: two atomics per workgroup, no events between the
+            # kernels - the launches of the timed region itself are what roofline reports
+            for o_ in ring:
+                o_.set_option(capi.PSM_OPT_PROFILE, 2)
+            sync()
+            for o_ in ring:
+                o_.filter_launch_times()
         sync(); barrier(); sync()
         t0 = time.perf_counter()
         for _ in range(args.steps):
             step()
         sync(); barrier(); sync()
         elapsed = time.perf_counter() - t0
-        launch_times = [lt for o_ in ring for lt in o_.filter_launch_times()]
-        for o_ in ring:
-            o_.set_option(capi.PSM_OPT_PROFILE, 0)
+        launch_times = []
+        if full:
+            launch_times = [lt for o_ in ring for lt in o_.filter_launch_times()]
+            for o_ in ring:
+                o_.set_option(capi.PSM_OPT_PROFILE, 0)
         if use_dist:
             elapsed = ex.max_float(elapsed)
         rec = {"shard": shard if (use_dist or args.shard_sim > 1) else None,
                "exchange": (("all_gather of map rows" if rows_mode else exchange) if use_dist else None),
                "ms_per_step": 1e3 * elapsed / args.steps, "value": voxels_per_step / (elapsed / args.steps)}
-        # ---- per-step times (SURVEY.md 8d asks for the median): each step bracketed by its own synchronisation; the
-        # frame-pipelined N>1 path finishes a frame's exchange one step later, so its steps are only meaningful in bulk ----
-        step_ms = []
-        for _ in range(max(3, min(args.steps, 20))):
-            sync()
-            ts = time.perf_counter()
-            step()
-            sync()
-            step_ms.append(1e3 * (time.perf_counter() - ts))
-        step_ms.sort()
-        rec["median_ms_per_step"] = round(step_ms[len(step_ms) // 2], 4)
+        if outputs and rank == 0:
+            # the context that took the last timed step (frames in flight: step i ran on context i % F)
+            rec["outputs"] = timed_outputs(batch_all if use_batch else [ring[(frame[0] - 1) % FIF]])
+        if full:
+            # ---- per-step times (SURVEY.md 8d asks for the median): each step bracketed by its own synchronisation; the
+            # frame-pipelined N>1 path finishes a frame's exchange one step later, so its steps are only meaningful in bulk ----
+            step_ms = []
+            for _ in range(max(3, min(args.steps, 20))):
+                sync()
+                ts = time.perf_counter()
+                step()
+                sync()
+                step_ms.append(1e3 * (time.perf_counter() - ts))
+            step_ms.sort()
+            rec["median_ms_per_step"] = round(step_ms[len(step_ms) // 2], 4)
         # ---- the launches of the fused kernel inside the timed region, by form ----
         by_form = {}
         for ms, f in launch_times:
@@ -542,7 +599,7 @@ def main():
         rec["filter_ms_per_step"] = sum(ms for ms, _ in launch_times) / args.steps if launch_times else None
         # ---- N > 1: what a step is made of on every rank - the rank-local kernels alone and the frame's ONE collective alone (each
         # bracketed by its own synchronisation: their sum exceeds a pipelined step, which overlaps the two) ----
-        if use_dist and not args.fgf:
+        if use_dist and not args.fgf and full:
             s0 = slots[0]
 
             def local_only():
@@ -615,7 +672,7 @@ def main():
 
     # ================= headline measurement =================
     exchange = args.exchange or ("allreduce" if args.shard == "disp" else "allgather")
-    head = measure(args.shard, exchange)
+    head = measure(args.shard, exchange, outputs=bool(args.dump_outputs))
     de, sync, step, batch_all = head["de"], head["sync"], head["step"], head["batch_all"]
 
     def step_all():      # one step on every context of the frame ring (one step when there is no ring): every context holds current maps
@@ -624,6 +681,58 @@ def main():
     geo = head["geometry"]
     (y0, y1), (d0, d1), rows_mode, n_slices = geo["rows"], geo["slices"], geo["rows_mode"], geo["n_slices"]
     ms_per_step, value = head["ms_per_step"], head["value"]
+
+    def result_line():
+        """The fields of the headline figure: all a plain run prints."""
+        out = {
+            "metric": "cost-volume voxels/s (CVC+CVF+WTA)" if not args.fgf else f"cost-volume voxels/s (CVC+CVF_FGF s={args.fgf}+WTA)",
+            "value": value, "unit": "voxels/s",
+            "n_gpus": N, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": dtype,
+            "data": data_note,
+            "config": {"workload": desc, "W": W, "H": H, "D": D, "voxels_per_step": voxels_per_step,
+                       "parallelism": "1 GPU" if world == 1 and not use_dist else
+                                      (f"{world} row stripes of {geo['rows_max']} rows (all {D} slices each) + 1 {xname} all_gather of the map rows per frame"
+                                       if rows_mode else f"D sharded over {world} ranks + 1 {xname} {exchange} of packed minima"),
+                       "kernel_variant": args.variant, "shard_sim": args.shard_sim, "lr_check_on_gpu": bool(lrc),
+                       "shard": head["shard"], "batch": B, "ranks": world, "same_device": bool(args.same_device),
+                       "frames_in_flight": len(head["ring"]), "strided_disparity_shards": bool(geo["strided"]),
+                       "exchange_backend": (backend if use_dist else None)},
+        }
+        if B > 1:
+            out["ms_per_pair"] = ms_per_step / B
+            out["config"]["workload"] = f"{B} x " + desc + " per step (psm_compute_batch: one set of launches for all pairs)"
+        if args.same_device and use_dist:
+            out["same_device_note"] = (f"{world} ranks share GPU 0: the N > 1 protocol (alternating buffers, pending exchange, gather / merge at world "
+                                       f"{world}) run for correctness - value is NOT a scaling measurement"
+                                       + (f"; {args.backend_note}" if args.backend_note else ""))
+        if use_dist:
+            out["ranks"] = world
+            out["exchange_backend"] = backend
+            out["shard"] = head["shard"]
+            out["exchange"] = head["exchange"]
+            out["frame_pipeline"] = bool(not args.no_frame_pipeline)
+        return out
+
+    def emit(out):
+        if json_fd is not None:
+            os.write(json_fd, (json.dumps(out) + "\n").encode())
+        else:
+            print(json.dumps(out))
+            sys.stdout.flush()
+
+    if args.dump_outputs and rank == 0:
+        write_outputs(head["outputs"], args.dump_outputs)
+    if not full:
+        # a plain run: the headline figure and nothing else
+        for o_ in batch_all:
+            o_.close()
+        if rank == 0:
+            emit(result_line())
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return 0
 
     # ---- the maps the timed region left on the device (before anything else runs on this context) ----
     timed_maps = None
@@ -1071,50 +1180,20 @@ def main():
                 o_.close()
 
     if rank == 0:
-        out = {
-            "metric": "cost-volume voxels/s (CVC+CVF+WTA)" if not args.fgf else f"cost-volume voxels/s (CVC+CVF_FGF s={args.fgf}+WTA)",
-            "value": value, "unit": "voxels/s",
-            "n_gpus": N, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": dtype,
-            "data": data_note,
-            "config": {"workload": desc, "W": W, "H": H, "D": D, "voxels_per_step": voxels_per_step,
-                       "parallelism": "1 GPU" if world == 1 and not use_dist else
-                                      (f"{world} row stripes of {geo['rows_max']} rows (all {D} slices each) + 1 {xname} all_gather of the map rows per frame"
-                                       if rows_mode else f"D sharded over {world} ranks + 1 {xname} {exchange} of packed minima"),
-                       "kernel_variant": args.variant, "shard_sim": args.shard_sim, "lr_check_on_gpu": bool(lrc),
-                       "shard": head["shard"], "batch": B, "ranks": world, "same_device": bool(args.same_device),
-                       "frames_in_flight": len(head["ring"]), "strided_disparity_shards": bool(geo["strided"]),
-                       "exchange_backend": (backend if use_dist else None)},
-            "roofline": roofline, "cpu_baseline": cpu, "kernels": kern,
-            "kernels_sum_ms_per_step": round(kernels_sum, 4), "kernels_sum_le_step": bool(kernels_sum <= ms_per_step * 1.005),
-            "median_ms_per_step": head["median_ms_per_step"], "pcie": pcie,
-        }
-        if B > 1:
-            out["ms_per_pair"] = ms_per_step / B
-            out["config"]["workload"] = f"{B} x " + desc + " per step (psm_compute_batch: one set of launches for all pairs)"
+        out = result_line()
+        out.update({"roofline": roofline, "cpu_baseline": cpu, "kernels": kern,
+                    "kernels_sum_ms_per_step": round(kernels_sum, 4), "kernels_sum_le_step": bool(kernels_sum <= ms_per_step * 1.005),
+                    "median_ms_per_step": head["median_ms_per_step"], "pcie": pcie})
         out.update(checks)
-        if args.same_device and use_dist:
-            out["same_device_note"] = (f"{world} ranks share GPU 0: the N > 1 protocol (alternating buffers, pending exchange, gather / merge at world "
-                                       f"{world}) run for correctness - value is NOT a scaling measurement"
-                                       + (f"; {args.backend_note}" if args.backend_note else ""))
         if use_dist:
-            out["ranks"] = world
-            out["exchange_backend"] = backend
-            out["shard"] = head["shard"]
-            out["exchange"] = head["exchange"]
             out["per_rank"] = head.get("per_rank")
-            out["frame_pipeline"] = bool(not args.no_frame_pipeline)
         if alt:
             out["alt_shard"] = alt
         if pp:
             out["pp"] = pp
         if box:
             out["box_filter_pass"] = box
-        if json_fd is not None:
-            os.write(json_fd, (json.dumps(out) + "\n").encode())
-        else:
-            print(json.dumps(out))
-            sys.stdout.flush()
+        emit(out)
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()

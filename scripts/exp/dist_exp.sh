@@ -17,7 +17,7 @@ for l in sys.stdin:
     if l.startswith('{'):
         j=json.loads(l); print('plain N=1', '%.3f ms'%j['ms_per_step'])"
 for g in 2 4 8; do
-timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --shard-sim $g 2>/dev/null | python -c "
+timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --shard-sim $g 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -4,10 +4,10 @@ TAG=${1:-distov}
 O=gpurun_out/$TAG
 mkdir -p $O
 for cfg in c3 c2; do
-  python bench.py --config $cfg --steps 60 --warmup 10 --no-cpu-baseline --frame-loop 0 > $O/${cfg}_plain.json 2>> $O/err.txt
+  python bench.py --full --config $cfg --steps 60 --warmup 10 --no-cpu-baseline --frame-loop 0 > $O/${cfg}_plain.json 2>> $O/err.txt
   for f in 1 2; do
-    python bench.py --config $cfg --gpus 1 --force-dist --frames-in-flight $f --steps 60 --warmup 10 --no-cpu-baseline > $O/${cfg}_dist_fif$f.json 2>> $O/err.txt
-    python bench.py --config $cfg --gpus 1 --force-dist --shard disp --frames-in-flight $f --steps 60 --warmup 10 --no-cpu-baseline > $O/${cfg}_dist_disp_fif$f.json 2>> $O/err.txt
+    python bench.py --full --config $cfg --gpus 1 --force-dist --frames-in-flight $f --steps 60 --warmup 10 --no-cpu-baseline > $O/${cfg}_dist_fif$f.json 2>> $O/err.txt
+    python bench.py --full --config $cfg --gpus 1 --force-dist --shard disp --frames-in-flight $f --steps 60 --warmup 10 --no-cpu-baseline > $O/${cfg}_dist_disp_fif$f.json 2>> $O/err.txt
   done
 done
 python - <<PY

@@ -3,7 +3,7 @@
 TAG=${1:-fix}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-B="timeout 600 python bench.py"
+B="timeout 600 python bench.py --full"
 $B --shard-sim 8 --frames-in-flight 2 --steps 40 > $OUT/bench_c4_shardsim_1of8_fif2.json 2>> $OUT/err.txt
 $B --shard-sim 8 --shard disp --frames-in-flight 2 --steps 40 > $OUT/bench_c4_shardsim_disp_1of8_fif2.json 2>> $OUT/err.txt
 timeout 1500 python -m pytest tests/test_gpu_bench.py -m gpu -x -q 2>&1 | tail -3

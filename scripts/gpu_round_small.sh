@@ -21,7 +21,7 @@ done
 cd $GRAFT_REPO_ROOT
 python scripts/make_traffic.py $OUT $TAG > $OUT/traffic_small.log 2>&1; grep -c "keeping the committed" $OUT/traffic_small.log
 cp profiles/traffic.json $OUT/traffic.json
-B="timeout 600 python bench.py"
+B="timeout 600 python bench.py --full"
 $B --config c2 --steps 30 --verify --pp > $OUT/bench_c2_n1.json 2>> $OUT/bench_small.err
 $B --config c1 --steps 30 --verify > $OUT/bench_c1_u8_n1.json 2>> $OUT/bench_small.err
 $B --config c1x --steps 30 --verify > $OUT/bench_c1x_u8_n1.json 2>> $OUT/bench_small.err

@@ -10,16 +10,16 @@ echo "== smoke"; timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 
 echo "== tests"
 timeout 1500 python -m pytest tests/test_gpu_fma.py tests/test_gpu_api.py tests/test_gpu_stripes.py tests/test_gpu_bench.py tests/test_capi_host.py -m gpu -q -x -p no:cacheprovider --timeout=900 > $OUT/pytest_sel.log 2>&1
 tail -5 $OUT/pytest_sel.log
-B="timeout 600 python bench.py"
+B="timeout 600 python bench.py --full"
 $B --no-cpu-wide > $OUT/bench_c4_n1.json 2> $OUT/bench.err
 $B --shard-sim 8 --steps 40 --no-oracle-check > $OUT/bench_c4_shardsim_1of8.json 2>> $OUT/bench.err
 $B --shard-sim 8 --steps 40 --frames-in-flight 2 --no-oracle-check > $OUT/bench_c4_shardsim_1of8_fif2.json 2>> $OUT/bench.err
 $B --shard-sim 8 --shard disp --steps 40 --no-oracle-check > $OUT/bench_c4_shardsim_disp_1of8.json 2>> $OUT/bench.err
 $B --config c2 --pair fixture --steps 30 --no-cpu-wide > $OUT/bench_c2_teddy_n1.json 2>> $OUT/bench.err
-D="timeout 600 python bench.py --gpus 1 --force-dist --steps 10 --warmup 3 --no-cpu-baseline"
+D="timeout 600 python bench.py --full --gpus 1 --force-dist --steps 10 --warmup 3 --no-cpu-baseline"
 $D > $OUT/bench_c4_dist_world1.json 2> $OUT/bench_dist1.err
 $D --frames-in-flight 1 > $OUT/bench_c4_dist_world1_fif1.json 2>> $OUT/bench_dist1.err
-W2="timeout 900 python bench.py --gpus 2 --same-device --steps 10 --warmup 3"
+W2="timeout 900 python bench.py --full --gpus 2 --same-device --steps 10 --warmup 3"
 $W2 > $OUT/bench_c4_world2_same_device.json 2> $OUT/bench_world2.err
 python - <<PY
 import json,glob

@@ -9,7 +9,7 @@ cd $GRAFT_REPO_ROOT
 L=$GRAFT_REPO_ROOT/primestereomatch_amd/lib
 echo "$TAG $(date -u +%Y-%m-%dT%H:%MZ) box $(hostname)" > $OUT/device.txt
 timeout 900 python -m pytest tests/test_gpu_fuse.py -m gpu -q -x -p no:cacheprovider --timeout=600 -k "strided" > $OUT/pytest_strided.log 2>&1; tail -4 $OUT/pytest_strided.log
-B="timeout 600 python bench.py --no-cpu-baseline --frame-loop 0"
+B="timeout 600 python bench.py --full --no-cpu-baseline --frame-loop 0"
 $B --steps 20 --warmup 5 > $OUT/c4_ref.json 2>> $OUT/err.txt
 for rep in 1 2; do
   $B --shard-sim 8 --shard disp --steps 40 > $OUT/disp8_contig_$rep.json 2>> $OUT/err.txt

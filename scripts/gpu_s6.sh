@@ -7,7 +7,7 @@ cd $GRAFT_REPO_ROOT
 echo "$TAG $(date -u +%Y-%m-%dT%H:%MZ) box $(hostname)" > $OUT/device.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
 timeout 2400 python -m pytest tests -m gpu -q -p no:cacheprovider --timeout=1200 -x > $OUT/pytest_gpu.log 2>&1; tail -4 $OUT/pytest_gpu.log
-B="timeout 600 python bench.py --no-cpu-wide --frame-loop 0"
+B="timeout 600 python bench.py --full --no-cpu-wide --frame-loop 0"
 $B > $OUT/c4.json 2>> $OUT/err.txt
 $B --config c3 --steps 30 > $OUT/c3.json 2>> $OUT/err.txt
 $B --config c5 --steps 4 --warmup 1 > $OUT/c5.json 2>> $OUT/err.txt

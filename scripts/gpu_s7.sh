@@ -8,7 +8,7 @@ cd $GRAFT_REPO_ROOT
 L=$GRAFT_REPO_ROOT/primestereomatch_amd/lib
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
 timeout 2400 python -m pytest tests -m gpu -q -x -p no:cacheprovider --timeout=1200 --deselect tests/test_gpu_bench.py > $OUT/pytest_gpu.log 2>&1; tail -4 $OUT/pytest_gpu.log
-B="timeout 600 python bench.py --no-cpu-baseline --frame-loop 0"
+B="timeout 600 python bench.py --full --no-cpu-baseline --frame-loop 0"
 for rep in 1 2; do
 for v in new prev; do
   lib=$L/libprimesm_hip.so; [ $v = prev ] && lib=$L/libprimesm_hip_prev.so

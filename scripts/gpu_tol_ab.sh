@@ -7,7 +7,7 @@ python - <<PY > $OUT/device.txt
 import subprocess,datetime
 print("$TAG", datetime.datetime.utcnow().strftime("%Y-%m-%dT%H:%MZ"))
 PY
-B="python bench.py"
+B="python bench.py --full"
 for rep in 1 2; do
   $B --steps 20 --warmup 5 --no-cpu-baseline --frame-loop 0 > $OUT/bench_c4_exact_ab$rep.json 2>> $OUT/err.txt
   $B --steps 20 --warmup 5 --flags 33554432 --no-cpu-wide --frame-loop 0 > $OUT/bench_c4_tol_ab$rep.json 2>> $OUT/err.txt

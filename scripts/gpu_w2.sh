@@ -6,7 +6,7 @@ mkdir -p $OUT
 python -c "
 import datetime,subprocess
 print('$TAG', datetime.datetime.utcnow().strftime('%Y-%m-%dT%H:%MZ'))" > $OUT/device.txt
-W2="timeout 900 python bench.py --gpus 2 --same-device --frames-in-flight 2 --steps 10 --warmup 3"
+W2="timeout 900 python bench.py --full --gpus 2 --same-device --frames-in-flight 2 --steps 10 --warmup 3"
 $W2 > $OUT/bench_c4_world2_same_device.json 2> $OUT/bench_world2.err
 python - <<PY
 import json

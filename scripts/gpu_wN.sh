@@ -5,8 +5,8 @@ TAG=${1:-wN}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for n in 4 8; do
-  timeout 1200 python bench.py --gpus $n --same-device --steps 6 --warmup 2 > $OUT/bench_c4_world${n}_same_device.json 2> $OUT/bench_world$n.err
-  timeout 1200 python bench.py --gpus $n --same-device --shard disp --steps 6 --warmup 2 > $OUT/bench_c4_world${n}_same_device_disp.json 2>> $OUT/bench_world$n.err
+  timeout 1200 python bench.py --full --gpus $n --same-device --steps 6 --warmup 2 > $OUT/bench_c4_world${n}_same_device.json 2> $OUT/bench_world$n.err
+  timeout 1200 python bench.py --full --gpus $n --same-device --shard disp --steps 6 --warmup 2 > $OUT/bench_c4_world${n}_same_device_disp.json 2>> $OUT/bench_world$n.err
 done
 python - <<PY
 import json,glob,os

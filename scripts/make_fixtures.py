@@ -5,7 +5,9 @@ re-encoded as numpy arrays in cv::imread order (BGR), plus outputs of the CPU or
 
   python scripts/make_fixtures.py
 """
+import glob
 import hashlib
+import io
 import json
 import os
 import sys
@@ -33,6 +35,38 @@ def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
+PART_LIMIT = 1000000    # bytes: no committed file reaches 1 MiB
+
+
+def savez_parts(path, **arrays):
+    """np.savez_compressed; a fixture that would exceed PART_LIMIT is written as <stem>.1.npz, <stem>.2.npz, ... instead, the
+    arrays packed first-fit in their order (the `golden` fixture of tests/conftest.py joins the parts)."""
+    stem = path[:-len(".npz")]
+    for old in glob.glob(stem + ".*.npz") + ([path] if os.path.exists(path) else []):
+        os.remove(old)
+    buf = io.BytesIO()
+    np.savez_compressed(buf, **arrays)
+    if buf.tell() <= PART_LIMIT:
+        np.savez_compressed(path, **arrays)
+        return [path]
+    parts, sizes = [], []
+    for k, a in arrays.items():
+        one = io.BytesIO()
+        np.savez_compressed(one, **{k: a})
+        n = one.tell()
+        i = next((i for i, s in enumerate(sizes) if s + n <= PART_LIMIT), len(parts))
+        if i == len(parts):
+            parts.append({})
+            sizes.append(0)
+        parts[i][k] = a
+        sizes[i] += n
+    out = [f"{stem}.{i + 1}.npz" for i in range(len(parts))]
+    for p, arrs in zip(out, parts):
+        np.savez_compressed(p, **arrs)
+        assert os.path.getsize(p) < 1 << 20, p
+    return out
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     O.build(force=True)
@@ -51,7 +85,7 @@ def main():
         res8 = O.pipeline_u8(l, r, D, threads=8, want_volumes=True, want_raw=True)
         # full outputs are large; keep maps + a few filtered slices / crops + SHA-256 of the rest
         ys, xs = slice(100, 132), slice(200, 248)
-        np.savez_compressed(
+        savez_parts(
             os.path.join(OUT, f"{name.lower()}_oracle_d64.npz"),
             ldisp=res["ldisp"], rdisp=res["rdisp"], ldisp_u8mode=res8["ldisp"],
             rdisp_u8mode=res8["rdisp"],
