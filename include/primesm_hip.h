@@ -48,7 +48,7 @@ enum { PSM_STAGE_CVC = 0, PSM_STAGE_CVF = 1, PSM_STAGE_DISPSEL = 2, PSM_STAGE_PP
 /* kernels whose device time can be queried with psm_kernel_time_ms() */
 enum { PSM_K_PREP = 0, PSM_K_CVC = 1, PSM_K_GUIDE = 2, PSM_K_CVF_A = 3, PSM_K_CVF_B = 4,
        PSM_K_WTA = 5, PSM_K_MERGE = 6, PSM_K_BOX = 7, PSM_K_LRC = 8, PSM_K_CVF_F = 9, PSM_K_FGF = 10, PSM_K_WMF = 11,
-       PSM_K_COUNT = 12 };
+       PSM_K_JWMF = 12, PSM_K_COUNT = 13 };
 /* options for psm_set_option */
 enum {
     PSM_OPT_ASYNC = 0,          /* 1: stage calls only enqueue; use psm_synchronize()        */
@@ -273,6 +273,32 @@ int psm_wgt_median(psm_ctx *ctx, uint8_t *lmap, uint8_t *rmap, size_t stride);
  * in-place recursion); these two numbers are not - a changed pixel is visible to evaluations still running in its sweep, so how
  * many evaluations (and, on dense maps, sweeps) a call needs can differ from run to run. */
 int psm_wgt_median_stats(psm_ctx *ctx, int sweeps[2], long long evals[2]);
+
+/* The live post-filter of the reference: PP::processDM runs JointWMF::filter on both maps with the 8-bit colour image as
+ * the feature (src/PP.cpp:402-424, include/JointWMF.h), which is what PostProcess_GPU / PostProcess_CPU compute
+ * (src/DispEst.cpp:330-344).  Filters the context's device maps in place (lDisMap = JointWMF::filter(...)), the left map
+ * with the left image and the right map with the right image; the valid masks are untouched.  Per pixel: the smallest
+ * disparity c with W(<=c) >= W(>c) over the clipped (2*radius+1)^2 window, W summing w[F(p)][F(q)] for the colour clusters
+ * F of the centre and the tap; the sums are exact integers rint(w * 2^48) (equal to the reference's float
+ * walk except where its own rounding decides, |W(<=c) - W(>c)| ~ 1e-4).  Clusters of a side: those psm_joint_wmf_set_clusters
+ * gave for the current pair; otherwise every distinct 6-bit colour key is its own cluster when there are at most n_clusters
+ * of them (the reference's result for any RNG state), else a deterministic k-means (k-means++ seeding from a fixed
+ * splitmix64 stream, Lloyd iterations in fp32 until no label changes or max_iter).
+ * radius 1..16, sigma > 0, n_clusters 1..256, max_iter >= 1; 0 or a negative value selects the reference's value
+ * (9 = MED_SZ/2, 25.5, 256, 10000).  Refuses stripe-only maps.  lmap/rmap (optional) receive the filtered maps.
+ * Synchronises with the host when the device k-means runs (the host reads the sample count and the convergence counter);
+ * it runs once per pair and (n_clusters, max_iter).  With clusters set for both sides, or on a later call for the same pair,
+ * it is asynchronous under PSM_OPT_ASYNC (the weight tables are formed once per clustering and sigma and copied from
+ * page-locked memory).  Kernel time: PSM_K_JWMF; stage PSM_STAGE_PP. */
+int psm_joint_wmf(psm_ctx *ctx, int radius, float sigma, int n_clusters, int max_iter, uint8_t *lmap, uint8_t *rmap, size_t stride);
+/* Bring-your-own clustering for one side (PSM_LEFT / PSM_RIGHT) of the current pair: n_clusters (1..256) centres
+ * [n][3] (B, G, R order of the 6-bit keys) and label_of_key[64*64*64] (index (B>>2)*4096 + (G>>2)*64 + (R>>2), values
+ * < n_clusters).  Holds until the next pair is adopted; psm_joint_wmf then ignores its n_clusters / max_iter for that side. */
+int psm_joint_wmf_set_clusters(psm_ctx *ctx, int side, int n_clusters, const float *centres, const uint8_t *label_of_key);
+/* The clustering the last psm_joint_wmf used for a side (or the one set for it): *n_clusters, centres [n][3] (room for
+ * 256 x 3), label_of_key [64^3] (keys absent from the image: 0 unless set), *iterations (Lloyd assignments; 0: identity or
+ * set by the host).  Any output pointer may be NULL. */
+int psm_joint_wmf_clusters(psm_ctx *ctx, int side, int *n_clusters, float *centres, uint8_t *label_of_key, int *iterations);
 
 /* ---- second sharding axis: row stripes (SURVEY.md 8e asks for shards of the path; the filter's vertical support is
  * bounded - 8 rows of costs either side - so a stripe of output rows needs nothing from another stripe) ----

@@ -18,7 +18,7 @@ PSM_IMG_U8, PSM_IMG_F32 = 0, 1
 PSM_LEFT, PSM_RIGHT = 0, 1
 PSM_STAGE_CVC, PSM_STAGE_CVF, PSM_STAGE_DISPSEL, PSM_STAGE_PP = 0, 1, 2, 3
 (PSM_K_PREP, PSM_K_CVC, PSM_K_GUIDE, PSM_K_CVF_A, PSM_K_CVF_B, PSM_K_WTA, PSM_K_MERGE, PSM_K_BOX,
- PSM_K_LRC, PSM_K_CVF_F, PSM_K_FGF, PSM_K_WMF) = range(12)
+ PSM_K_LRC, PSM_K_CVF_F, PSM_K_FGF, PSM_K_WMF, PSM_K_JWMF) = range(13)
 (PSM_OPT_ASYNC, PSM_OPT_KERNEL_VARIANT, PSM_OPT_PROFILE, PSM_OPT_SEG_ROWS, PSM_OPT_WAVES, PSM_OPT_FLAGS, PSM_OPT_GRAPH,
  PSM_OPT_GATHER_STAGED, PSM_OPT_FRAMES_IN_FLIGHT) = range(9)
 # enum psm_flag (PSM_OPT_FLAGS bits)
@@ -64,6 +64,9 @@ SYMBOLS = [
     ("psm_fill_invalid", _i, [_vp, _vp, _vp, _sz]),
     ("psm_wgt_median", _i, [_vp, _vp, _vp, _sz]),
     ("psm_wgt_median_stats", _i, [_vp, _vp, _vp]),
+    ("psm_joint_wmf", _i, [_vp, _i, C.c_float, _i, _i, _vp, _vp, _sz]),
+    ("psm_joint_wmf_set_clusters", _i, [_vp, _i, _i, _vp, _vp]),
+    ("psm_joint_wmf_clusters", _i, [_vp, _i, _pi, _vp, _vp, _pi]),
     ("psm_set_rows", _i, [_vp, _i, _i]),
     ("psm_set_map_buffer", _i, [_vp, _vp, _i]),
     ("psm_gather_rows_ctx", _i, [_vp, _vp, _i, _vp, _vp, _sz]),

@@ -88,6 +88,8 @@ void adopt_new_pair(psm_ctx *c, int depth)
     c->fgf_virtual[0] = c->fgf_virtual[1] = 0;
     c->gf_virtual[0] = c->gf_virtual[1] = false;
     c->maps_early = nullptr;
+    c->jw_have[0] = c->jw_have[1] = c->jw_user[0] = c->jw_user[1] = false;   // clusters belong to the images
+    c->jw_tab_ok[0] = c->jw_tab_ok[1] = false;
 }
 
 }  // namespace psm
@@ -127,6 +129,10 @@ void free_all(psm_ctx *c)
     (void)hipFree(c->wm);
     (void)hipFree(c->wm_par);
     (void)hipFree(c->wm_wts);
+    (void)hipFree(c->jw);
+    if (c->jw_pin) (void)hipHostFree(c->jw_pin);
+    for (hipEvent_t e : c->ev_jw)
+        if (e) (void)hipEventDestroy(e);
     if (c->wm_pin) (void)hipHostFree(c->wm_pin);
     for (hipEvent_t e : {c->ev_wm[0], c->ev_wm[1]})
         if (e) (void)hipEventDestroy(e);

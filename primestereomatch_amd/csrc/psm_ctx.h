@@ -5,6 +5,7 @@
 //   psm_api_select.cpp  DispSelect: maps, packed minima, row stripes and disparity shards
 //   psm_api_pp.cpp      post-processing: L-R check, invalid fill, weighted median
 //   psm_api_batch.cpp   several Middlebury-size pairs per launch (psm_compute_batch)
+//   psm_api_jwmf.cpp    JointWMF: the joint weighted median of the reference's live post-filter (psm_joint_wmf)
 // Takes the place of the reference's oclUtil + CVC_cl / CVF_cl / DispSel_cl host wrappers
 // (src/oclUtil.cpp, src/CVC_cl.cpp, src/CVF_cl.cpp, src/DispSel_cl.cpp).
 #pragma once
@@ -93,6 +94,17 @@ struct psm_ctx {
     hipEvent_t ev_wm[2] = {nullptr, nullptr};
     int wm_sweeps[2] = {0, 0};          // last call: sweeps until the fixed point (-1: dataflow form), evaluations
     long long wm_evals[2] = {0, 0};
+    // psm_joint_wmf (psm_api_jwmf.cpp): one device block for both sides (psm::JwScratch), allocated on first use
+    uint8_t *jw = nullptr;
+    bool jw_have[2] = {false, false};   // a clustering of the current pair exists for the side (run or set)
+    bool jw_user[2] = {false, false};   // ... and the host set it (psm_joint_wmf_set_clusters)
+    int jw_nf[2] = {0, 0}, jw_iters[2] = {0, 0};
+    int jw_params[2][2] = {{0, 0}, {0, 0}};   // {n_clusters, max_iter} of the device k-means that made the side's clustering
+    std::vector<float> jw_centres[2];
+    bool jw_tab_ok[2] = {false, false};  // the device weight table of the side is that of its clustering with sigma jw_tab_sigma
+    float jw_tab_sigma[2] = {0.f, 0.f};
+    unsigned long long *jw_pin = nullptr;  // page-locked staging of the two integer tables (on first use)
+    hipEvent_t ev_jw[2] = {nullptr, nullptr};   // ... the copy out of a side's staging has executed
     uint8_t *p4[2] = {nullptr, nullptr};  // PSM_U8 only: {c0,c1,c2,grad} words
     // After psm_cost_filter_fgf the filtered volume of a side may stay virtual (fgf_virtual[side] = subsample rate):
     // it is fully described by the smoothed low-resolution models fgf_mab[side]; the WTA consumes them directly

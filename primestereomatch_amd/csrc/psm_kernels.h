@@ -175,4 +175,28 @@ void launch_f32_to_u8(hipStream_t s, const float *src, uint8_t *dst, size_t n);
 void launch_wta_u8(hipStream_t s, const uint8_t *vol, int W, int H, int d_begin, int Dloc, long long *keys,
                    uint8_t *map);
 
+// psm_jwmf.hip: the joint weighted median (psm_joint_wmf, psm_api_jwmf.cpp)
+constexpr int JW_KEYS = 1 << 18;       // 6-bit B, G, R colour keys
+constexpr int JW_NF_MAX = 256;         // clusters at most; the integer weight table of a side is [JW_NF_MAX][JW_NF_MAX]
+constexpr int JW_RMAX = 16;            // window radius at most: (2r+1)^2 <= 1089 taps, every integer sum < 2^59
+struct JwSide {
+    const void *img;                   // staged interleaved B,G,R image (PSM_IMG_U8 bytes or PSM_IMG_F32 floats)
+    const uint8_t *lok;                // cluster of every key [JW_KEYS]
+    uint8_t *F;                        // cluster plane [H][W]
+    const uint8_t *din;                // input map [H][W]
+    const unsigned long long *wq;      // rint(w * 2^48) [JW_NF_MAX][JW_NF_MAX]
+    uint8_t *out;                      // filtered map [H][W]
+};
+struct JwPair { JwSide s[2]; };
+void launch_jw_keys(hipStream_t s, const void *img, int depth, size_t HW, unsigned *bits);
+void launch_jw_compact(hipStream_t s, const unsigned *bits, unsigned *samples, int *n_out);
+void launch_jw_identity(hipStream_t s, const unsigned *samples, int n, float *centres, int *labels);
+void launch_jw_seed(hipStream_t s, const unsigned *samples, int n, int nf, unsigned long long seed, float *centres,
+                    unsigned *kt, unsigned *d2t);
+// one Lloyd iteration (assignment + update); state {changed, converged, iterations}
+void launch_jw_lloyd(hipStream_t s, const unsigned *samples, int n, int nf, float *centres, int *labels, int *sums, int *state, int it);
+void launch_jw_lok(hipStream_t s, const unsigned *samples, int n, const int *labels, uint8_t *lok);
+void launch_jw_plane(hipStream_t s, const JwPair &pr, int depth, size_t HW);
+void launch_jw_median(hipStream_t s, const JwPair &pr, int W, int H, int r);
+
 }  // namespace psm

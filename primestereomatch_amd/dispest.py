@@ -164,6 +164,33 @@ class DispEst:
         self._ck(self._lib.psm_wgt_median(self._h, _ptr(self.lDisMap), _ptr(self.rDisMap), self.wid), "WgtMedian_GPU")
         return 0
 
+    def JointWMF_GPU(self, radius: int = 0, sigma: float = 0.0, n_clusters: int = 0, max_iter: int = 0) -> int:
+        """The reference's live post-filter: PP::processDM = JointWMF::filter on both maps with the 8-bit colour images
+        (src/PP.cpp:402-424) on the device; updates lDisMap / rDisMap, the valid masks stay as they are.  0: the
+        reference's radius 9, sigma 25.5, 256 clusters, 10000 k-means iterations.  PostProcess_GPU is unchanged."""
+        self._ck(self._lib.psm_joint_wmf(self._h, int(radius), float(sigma), int(n_clusters), int(max_iter),
+                                         _ptr(self.lDisMap), _ptr(self.rDisMap), self.wid), "JointWMF_GPU")
+        return 0
+
+    def set_jwmf_clusters(self, side: int, centres, label_of_key):
+        """Bring-your-own clustering of one side for JointWMF_GPU: centres [n, 3] (6-bit B, G, R), label_of_key [64**3]."""
+        cen = np.ascontiguousarray(centres, dtype=np.float32).reshape(-1, 3)
+        lok = np.ascontiguousarray(label_of_key, dtype=np.uint8).reshape(-1)
+        if lok.size != 64 ** 3:
+            raise ValueError("label_of_key must hold 64**3 entries")
+        self._ck(self._lib.psm_joint_wmf_set_clusters(self._h, int(side), int(cen.shape[0]), _ptr(cen), _ptr(lok)),
+                 "set_jwmf_clusters")
+
+    def jwmf_clusters(self, side: int):
+        """-> (centres [n, 3] float32, label_of_key [64**3] uint8, iterations) of the clustering JointWMF_GPU used."""
+        import ctypes as C
+        n, it = C.c_int(), C.c_int()
+        cen = np.zeros((256, 3), np.float32)
+        lok = np.zeros(64 ** 3, np.uint8)
+        self._ck(self._lib.psm_joint_wmf_clusters(self._h, int(side), C.byref(n), _ptr(cen), _ptr(lok), C.byref(it)),
+                 "jwmf_clusters")
+        return cen[:n.value].copy(), lok, it.value
+
     def wgt_median_stats(self):
         """(sweeps, evaluations) of the last WgtMedian_GPU per map [left, right]; sweeps = -1: the dataflow form ran."""
         import ctypes as C

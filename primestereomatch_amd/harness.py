@@ -30,13 +30,16 @@ def error_vs_ground_truth(lDisMap, gt, mask, maxDis, scale_factor, error_thresho
 
 
 def compute(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, error_threshold=4, threads=8,
-            dtype="f32", post_process=True, verbose=False, subsample_rate=0, process_dm=False):
+            dtype="f32", post_process=True, verbose=False, subsample_rate=0, process_dm=False, joint_wmf=False):
     """One frame of STEREO_GIF on the accelerator path.  l_bgr/r_bgr: H x W x 3 uint8 (imread order).
     subsample_rate 0: full guided filter (CostFilter_GPU, the reference's 'm' branch); 2/4/8: the Fast Guided
     Filter variant (CostFilter_FGF, the snapshot's live branch, src/StereoMatch.cpp:213) on the device.
     process_dm: after the L-R check run the rest of PP::processDM's plain sequence on the device - fillInv, then wgtMedian
     on the pixels the check rejected (src/PP.cpp:405-410; lrCheck and fillInv are commented out in the snapshot's live
-    processDM, wgtMedian is its dead-code predecessor of JointWMF) - the maps before it stay in lDisMap_raw / rDisMap_raw."""
+    processDM, wgtMedian is its dead-code predecessor of JointWMF) - the maps before it stay in lDisMap_raw / rDisMap_raw.
+    joint_wmf: then run the snapshot's live processDM body, JointWMF::filter on both maps (src/PP.cpp:417-422), on the device
+    (DispEst.JointWMF_GPU) and score the filtered left map, as StereoMatch::compute does after PostProcess
+    (src/StereoMatch.cpp:225-311); the selected maps stay in lDisMap_raw / rDisMap_raw."""
     out = {}
     lFrame = np.ascontiguousarray(l_bgr)
     rFrame = np.ascontiguousarray(r_bgr)
@@ -61,6 +64,10 @@ def compute(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, error_t
             out["lDisMap_raw"], out["rDisMap_raw"] = SMDE.lDisMap.copy(), SMDE.rDisMap.copy()
             SMDE.FillInv_GPU()
             SMDE.WgtMedian_GPU()
+        if joint_wmf:
+            out.setdefault("lDisMap_raw", SMDE.lDisMap.copy())
+            out.setdefault("rDisMap_raw", SMDE.rDisMap.copy())
+            SMDE.JointWMF_GPU()
         out["cvc_ms"] = SMDE.stage_time_us(capi.PSM_STAGE_CVC) / 1000
         out["cvf_ms"] = SMDE.stage_time_us(capi.PSM_STAGE_CVF) / 1000
         out["dispsel_ms"] = SMDE.stage_time_us(capi.PSM_STAGE_DISPSEL) / 1000

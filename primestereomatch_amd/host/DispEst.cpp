@@ -170,6 +170,12 @@ int DispEst::WgtMedian_GPU()
     return hipUtil::api().wgt_median(ctx[0], lDisMap.data, rDisMap.data, lDisMap.step);
 }
 
+int DispEst::JointWMF_GPU()
+{
+    if (ctx.empty()) return 1;
+    return hipUtil::api().joint_wmf(ctx[0], 0, 0.f, 0, 0, lDisMap.data, rDisMap.data, lDisMap.step);
+}
+
 int DispEst::computeFrame(const Mat *nextL, const Mat *nextR, bool have_prev)
 {
     if (ctx.size() != 1) return 1;           // (a multi-device host gathers stripes: use the stage calls)

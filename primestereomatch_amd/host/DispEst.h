@@ -80,6 +80,9 @@ public:
     // wgtMedian (src/PP.cpp:145-247) for the pixels the last L-R check marked invalid; same result as the reference's sequential
     // in-place form
     int WgtMedian_GPU();
+    // The live body of PP::processDM (src/PP.cpp:417-422): JointWMF::filter on both maps, on the device (psm_joint_wmf with the
+    // reference's radius, sigma and cluster count); lDisMap / rDisMap receive the filtered maps.  PostProcess_GPU is unchanged.
+    int JointWMF_GPU();
 
     // Frame loop (src/main.cpp:64-73) with the PCIe legs next to the kernels (single-device hosts): one call per frame -
     // CostConst (adopts the pair staged by the previous call), stages `next` pair (may be NULL at the end of the stream: its

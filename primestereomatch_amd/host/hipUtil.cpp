@@ -47,7 +47,8 @@ bool hipUtil::load(const char *path)
               bind(g_api.disp_select, "psm_disp_select") && bind(g_api.disp_select_partial, "psm_disp_select_partial") &&
               bind(g_api.disp_merge_ctx, "psm_disp_merge_ctx") && bind(g_api.set_rows, "psm_set_rows") && bind(g_api.gather_rows_ctx, "psm_gather_rows_ctx") &&
               bind(g_api.lr_check, "psm_lr_check") && bind(g_api.fill_invalid, "psm_fill_invalid") &&
-              bind(g_api.wgt_median, "psm_wgt_median") &&
+              bind(g_api.wgt_median, "psm_wgt_median") && bind(g_api.joint_wmf, "psm_joint_wmf") &&
+              bind(g_api.joint_wmf_set_clusters, "psm_joint_wmf_set_clusters") &&
               bind(g_api.stage_time_us, "psm_stage_time_us") && bind(g_api.compute_batch, "psm_compute_batch") &&
               bind(g_api.download_maps, "psm_download_maps");
     if (!ok) {

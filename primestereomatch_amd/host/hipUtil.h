@@ -33,6 +33,8 @@ struct HipApi {
     int (*lr_check)(psm_ctx *, uint8_t *, uint8_t *, size_t) = nullptr;
     int (*fill_invalid)(psm_ctx *, uint8_t *, uint8_t *, size_t) = nullptr;
     int (*wgt_median)(psm_ctx *, uint8_t *, uint8_t *, size_t) = nullptr;
+    int (*joint_wmf)(psm_ctx *, int, float, int, int, uint8_t *, uint8_t *, size_t) = nullptr;
+    int (*joint_wmf_set_clusters)(psm_ctx *, int, int, const float *, const uint8_t *) = nullptr;
     int (*stage_time_us)(psm_ctx *, int, double *) = nullptr;
     int (*compute_batch)(psm_ctx *const *, int) = nullptr;
     int (*download_maps)(psm_ctx *, uint8_t *, uint8_t *, size_t) = nullptr;

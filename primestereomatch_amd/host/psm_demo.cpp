@@ -11,6 +11,7 @@
 // fgf_rate 0 (default): CostFilter_GPU; 2/4/8: CostFilter_FGF_GPU with that subsample rate
 // pp 1: after the left-right check also fillInv + wgtMedian (the stages of PP::processDM, src/PP.cpp:405-410); the
 //       post-processed maps go to <out_prefix>_ldisp_pp.raw / _rdisp_pp.raw
+// pp 2: instead JointWMF on the device (JointWMF_GPU: the live body of processDM, src/PP.cpp:417-422), same output files
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -49,7 +50,7 @@ int main(int argc, char **argv)
     const int dtype = (argc > 8 && !strcmp(argv[8], "u8")) ? PSM_U8 : PSM_F32;
     const bool float_input = argc > 9 && atoi(argv[9]) != 0;
     const int fgf_rate = argc > 10 ? atoi(argv[10]) : 0;
-    const bool pp = argc > 11 && atoi(argv[11]) != 0;
+    const int pp = argc > 11 ? atoi(argv[11]) : 0;
     const int frames = argc > 12 ? atoi(argv[12]) : 0;
     const int batch = argc > 13 ? atoi(argv[13]) : 0;
     const int nring = argc > 14 ? atoi(argv[14]) : 0;
@@ -93,7 +94,8 @@ int main(int argc, char **argv)
     bool ok = dump(out + "_ldisp.raw", SMDE.lDisMap.data, (size_t)W * H) && dump(out + "_rdisp.raw", SMDE.rDisMap.data, (size_t)W * H) &&
               dump(out + "_lvalid.raw", SMDE.lValid.data, (size_t)W * H) && dump(out + "_rvalid.raw", SMDE.rValid.data, (size_t)W * H);
     if (ok && pp) {
-        if (SMDE.ProcessDM_GPU()) return 5;        // lrCheck + fillInv + wgtMedian (src/PP.cpp:405-410, commented out in the reference)
+        if (pp == 2 ? SMDE.JointWMF_GPU() : SMDE.ProcessDM_GPU()) return 5;   // pp 1: lrCheck + fillInv + wgtMedian (src/PP.cpp:405-410,
+                                                                              // commented out in the reference); pp 2: JointWMF
         ok = dump(out + "_ldisp_pp.raw", SMDE.lDisMap.data, (size_t)W * H) && dump(out + "_rdisp_pp.raw", SMDE.rDisMap.data, (size_t)W * H);
     }
     if (ok && frames > 0 && ndev == 1 && !fgf_rate) {
