@@ -39,6 +39,7 @@
 #include "../../include/primesm_hip.h"
 
 #include <mutex>
+#include <type_traits>
 
 #include "psm_pc_debug.inc"   // PSM_PC_TIMING per-workgroup traces and the PSM_EXPERIMENTS knobs: all compiled out of the product
 
@@ -783,24 +784,98 @@ int pc_seed_stride(int W, int rows, bool u8)
 
 static int pc_blocks(const PcPlan &pl, int chunks) { return pl.nxcd * ((pl.ngroups * pl.nsegs * chunks + pl.nxcd - 1) / pl.nxcd); }
 
+// The arguments of one k_cvf_pc launch, gathered by its launcher (pc_launch passes them on).
+struct PcArgs {
+    const float *vin;                // CVC 0: the cost volume; 8-bit mode: byte planes of the left image (read by the right volume)
+    float *vout;                     // MODE 0: the filtered volume; 8-bit mode: byte planes of the right image (read by the left volume)
+    int W, H, Dloc, ybeg, yend, d_begin;
+    PcSide side[2];                  // side[0]: the launch's (left) volume; side[1]: the right one of a two-volume launch
+    PcSel sel;
+    unsigned long long *ts;
+    const PcPair *batch;             // BATCH: the pairs' table (the sides' planes come from it)
+};
+
+// Which k_cvf_pc runs a launch: its template arguments as runtime values.
+struct PcForm {
+    int mode, cvc;
+    bool u8;
+    int var;
+    bool batch, narrow, vec4;
+};
+
+template <int V> using pc_int = std::integral_constant<int, V>;
+// fn(pc_int<V>{}) for the V of Vs that equals v (callers pass only values of Vs)
+template <int... Vs, class Fn> static void pc_pick(int v, Fn &&fn) { (void)((v == Vs && (fn(pc_int<Vs>{}), true)) || ...); }
+template <class Fn> static void pc_pick_bool(bool b, Fn &&fn) { if (b) fn(std::true_type{}); else fn(std::false_type{}); }
+
+// The one launch of k_cvf_pc: the runtime form -> one of the 44 instantiations that exist, and no other -
+//   storing form:            VEC4 x CVC 0-2 x {canon, FMA solve}
+//   one-volume plane form:   CVC 0-2 x {canon, FMA solve}, CVC 1-2 x 8-bit
+//   two-volume select forms: planes / keys x wide / narrow x {8-bit, canon, tolerance, FMA solve}; batched: {8-bit, canon}
+static void pc_launch(hipStream_t s, const PcPlan &pl, dim3 grid, const PcArgs &a, const PcForm &f)
+{
+    using F = std::false_type;
+    using T = std::true_type;
+    const bool planes = f.mode == PC_PLANES;     // (DC and nbmax mean something to the plane form only)
+    const PcSide &s0 = a.side[0];
+    auto go = [&](auto V4, auto CV, auto MD, auto U, auto BT, auto VR, auto NW) {
+        using L = PcLayout<MD, NW>;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cvf_pc<V4, CV, MD, U, BT, VR, NW>), grid, dim3(64 * (L::NA + L::NB)), 0, s, a.vin, a.vout,
+                           s0.G1, s0.G2, s0.G3, s0.G4, a.W, a.H, a.Dloc, pl.ngroups, pl.nsegs, pl.seg_rows, a.ybeg, a.yend, s0.Gother,
+                           a.d_begin, planes ? pl.DC : 1, s0.kcost, s0.kdisp, planes ? pl.nbmax : 0, a.side[1], a.sel, a.ts, a.batch);
+    };
+    if (f.mode == PC_STORE)
+        pc_pick_bool(f.vec4, [&](auto V4) { pc_pick<0, 1, 2>(f.cvc, [&](auto CV) {
+            pc_pick<0, 2>(f.var, [&](auto VR) { go(V4, CV, pc_int<0>{}, F{}, F{}, VR, F{}); }); }); });
+    else if (f.cvc != 3)
+        pc_pick<0, 1, 2>(f.cvc, [&](auto CV) {
+            if constexpr (CV != 0) if (f.u8) return go(F{}, CV, pc_int<1>{}, T{}, F{}, pc_int<0>{}, F{});
+            pc_pick<0, 2>(f.var, [&](auto VR) { go(F{}, CV, pc_int<1>{}, F{}, F{}, VR, F{}); });
+        });
+    else
+        pc_pick<1, 2>(f.mode, [&](auto MD) { pc_pick_bool(f.narrow, [&](auto NW) {
+            if (f.u8) pc_pick_bool(f.batch, [&](auto BT) { go(F{}, pc_int<3>{}, MD, T{}, BT, pc_int<0>{}, NW); });
+            else if (f.batch) go(F{}, pc_int<3>{}, MD, F{}, T{}, pc_int<0>{}, NW);
+            else pc_pick<0, 1, 2>(f.var, [&](auto VR) { go(F{}, pc_int<3>{}, MD, F{}, F{}, VR, NW); });
+        }); });
+}
+
+// Chunk planes of volume v in `scratch` (pl.scratch_bytes() per volume): float4 cost records, then uchar4 disparity records.
+static PcSide pc_planes(const PcPlan &pl, void *scratch, int v)
+{
+    PcSide p = {};
+    p.kcost = (float *)((char *)scratch + v * pl.scratch_bytes());
+    p.kdisp = (unsigned *)(p.kcost + 4 * pl.rec_per_chunk * pl.nchunks);
+    return p;
+}
+
+// float mode's arithmetic variant of a two-volume launch (8-bit mode: the canon)
+static int pc_var(March m, bool u8)
+{
+    return u8 ? 0 : (m.flags & PSM_FLAG_FMA_SOLVE) ? 2 : (m.flags & PSM_FLAG_F32_TOL) ? 1 : 0;
+}
+
+// The one launch of k_chunk_min: `sides` volumes (chunk planes in `scratch`, or from the table `tab`) of `npairs` pairs.
+static void pc_chunk_min(hipStream_t s, March m, const PcPlan &pl, int W, int H, int sides, int npairs, void *scratch,
+                         long long *keys, uint8_t *map, const PcPair *tab = nullptr, bool to_maps = false)
+{
+    const PcSide p0 = scratch ? pc_planes(pl, scratch, 0) : PcSide{}, p1 = scratch && sides == 2 ? pc_planes(pl, scratch, 1) : PcSide{};
+    hipLaunchKernelGGL(k_chunk_min, dim3((unsigned)((pl.rec_per_chunk + 255) / 256), sides, npairs), dim3(256), 0, s,
+                       (const float4 *)p0.kcost, (const unsigned *)p0.kdisp, pl.nchunks, pl.ngroups * pl.nsegs, pl.nbmax, pl.ngroups,
+                       pl.seg_rows, W, H, keys, map, (const float4 *)p1.kcost, (const unsigned *)p1.kdisp, m.y0(H), m.y1(H), tab,
+                       to_maps ? 1 : 0, pl.cols);
+}
+
 // Storing form (MODE 0): vin (or, cvc_mode 1 / 2, the costs built on the fly) -> vout, one slice per workgroup.
 void launch_cvf_fused(hipStream_t s, March m, const float *vin, float *vout, Guidance gd, int W, int H, int Dloc,
                       int ybeg, int yend, const float4 *g1_other, int d_begin, int cvc_mode, unsigned long long *ts)
 {
     if (yend <= ybeg) return;
     const PcPlan pl = pc_plan(W, yend - ybeg, Dloc, m.seg_rows, PC_STORE);
-    const dim3 grid(pc_blocks(pl, Dloc)), blk(64 * (PcLayout<0>::NA + PcLayout<0>::NB));
-#define PSM_LAUNCH_PC(V4, CV, VR)                                                                                          \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cvf_pc<V4, CV, 0, false, false, VR>), grid, blk, 0, s, vin, vout, (const float4 *)gd.g1, \
-                       (const float4 *)gd.g2, (const float4 *)gd.g3, (const float2 *)gd.g4, W, H, Dloc, pl.ngroups, pl.nsegs, \
-                       pl.seg_rows, ybeg, yend, g1_other, d_begin, 1, (float *)nullptr, (unsigned *)nullptr, 0, PcSide{}, PcSel{0, 1, pl.nxcd, 0, Dloc, 0, 1}, ts, (const PcPair *)nullptr)
-#define PSM_LAUNCH_PCV(V4, CV) { if (m.flags & PSM_FLAG_FMA_SOLVE) PSM_LAUNCH_PC(V4, CV, 2); else PSM_LAUNCH_PC(V4, CV, 0); }
-    const bool v4 = (W & 3) == 0;
-    if (cvc_mode == 1) { if (v4) PSM_LAUNCH_PCV(true, 1) else PSM_LAUNCH_PCV(false, 1) }
-    else if (cvc_mode == 2) { if (v4) PSM_LAUNCH_PCV(true, 2) else PSM_LAUNCH_PCV(false, 2) }
-    else { if (v4) PSM_LAUNCH_PCV(true, 0) else PSM_LAUNCH_PCV(false, 0) }
-#undef PSM_LAUNCH_PCV
-#undef PSM_LAUNCH_PC
+    PcArgs a = {vin, vout, W, H, Dloc, ybeg, yend, d_begin, {}, PcSel{0, 1, pl.nxcd, 0, Dloc, 0, 1}, ts, nullptr};
+    a.side[0] = PcSide{gd.g1, gd.g2, gd.g3, gd.g4, g1_other, nullptr, nullptr};
+    const int cvc = cvc_mode == 1 || cvc_mode == 2 ? cvc_mode : 0;
+    pc_launch(s, pl, dim3(pc_blocks(pl, Dloc)), a, {PC_STORE, cvc, false, (m.flags & PSM_FLAG_FMA_SOLVE) ? 2 : 0, false, false, (W & 3) == 0});
 }
 
 // Select form with chunk planes (MODE 1), one volume: costs read from vin (cvc_mode 0) or built on the fly (1 / 2; p4_own !=
@@ -809,32 +884,19 @@ void launch_cvf_select(hipStream_t s, March m, const float *vin, Guidance gd, in
                        int d_begin, int cvc_mode, void *scratch, unsigned long long *ts, const uint8_t *p4_own, const uint8_t *p4_other)
 {
     const PcPlan pl = pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_PLANES);
-    const PcSel sel = {0, 1, pl.nxcd, 0, Dloc, 0, 1};
-    float *kcost = (float *)scratch;                                           // nchunks * rec_per_chunk float4
-    unsigned *kdisp = (unsigned *)(kcost + 4 * pl.rec_per_chunk * pl.nchunks);  // nchunks * rec_per_chunk uchar4
-    const dim3 grid(pc_blocks(pl, pl.nchunks)), blk(64 * (PcLayout<1>::NA + PcLayout<1>::NB));
-#define PSM_LAUNCH_PC(CV, U8V, VR, A0, A1)                                                                                  \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cvf_pc<false, CV, 1, U8V, false, VR>), grid, blk, 0, s, A0, A1, (const float4 *)gd.g1, \
-                       (const float4 *)gd.g2, (const float4 *)gd.g3, (const float2 *)gd.g4, W, H, Dloc, pl.ngroups, pl.nsegs, \
-                       pl.seg_rows, m.y0(H), m.y1(H), g1_other, d_begin, pl.DC, kcost, kdisp, pl.nbmax, PcSide{}, sel, ts, (const PcPair *)nullptr)
-    const bool fma = (m.flags & PSM_FLAG_FMA_SOLVE) != 0;      // (one volume per launch: the canon and the FMA reading; no tolerance form)
-    if (p4_own && cvc_mode != 0) {
-        if (cvc_mode == 1) PSM_LAUNCH_PC(1, true, 0, (const float *)p4_own, (float *)const_cast<uint8_t *>(p4_other));
-        else PSM_LAUNCH_PC(2, true, 0, (const float *)p4_own, (float *)const_cast<uint8_t *>(p4_other));
-    } else if (cvc_mode == 1) { if (fma) PSM_LAUNCH_PC(1, false, 2, vin, (float *)nullptr); else PSM_LAUNCH_PC(1, false, 0, vin, (float *)nullptr); }
-    else if (cvc_mode == 2) { if (fma) PSM_LAUNCH_PC(2, false, 2, vin, (float *)nullptr); else PSM_LAUNCH_PC(2, false, 0, vin, (float *)nullptr); }
-    else { if (fma) PSM_LAUNCH_PC(0, false, 2, vin, (float *)nullptr); else PSM_LAUNCH_PC(0, false, 0, vin, (float *)nullptr); }
-#undef PSM_LAUNCH_PC
+    const int cvc = cvc_mode == 1 || cvc_mode == 2 ? cvc_mode : 0;
+    const bool u8 = p4_own && cvc != 0;
+    PcArgs a = {u8 ? (const float *)p4_own : vin, u8 ? (float *)const_cast<uint8_t *>(p4_other) : nullptr, W, H, Dloc, m.y0(H), m.y1(H),
+                d_begin, {}, PcSel{0, 1, pl.nxcd, 0, Dloc, 0, 1}, ts, nullptr};
+    const PcSide k = pc_planes(pl, scratch, 0);
+    a.side[0] = PcSide{gd.g1, gd.g2, gd.g3, gd.g4, g1_other, k.kcost, k.kdisp};
+    // (one volume per launch: the canon and the FMA reading; no tolerance form)
+    pc_launch(s, pl, dim3(pc_blocks(pl, pl.nchunks)), a, {PC_PLANES, cvc, u8, (m.flags & PSM_FLAG_FMA_SOLVE) ? 2 : 0, false, false, false});
 }
 
 void launch_chunk_min(hipStream_t s, March m, int W, int H, int Dloc, void *scratch, long long *keys, uint8_t *map)
 {
-    const PcPlan pl = pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_PLANES);
-    const float *kcost = (const float *)scratch;
-    const unsigned *kdisp = (const unsigned *)(kcost + 4 * pl.rec_per_chunk * pl.nchunks);
-    hipLaunchKernelGGL(k_chunk_min, dim3((unsigned)((pl.rec_per_chunk + 255) / 256)), dim3(256), 0, s, (const float4 *)kcost, (const unsigned *)kdisp,
-                       pl.nchunks, pl.ngroups * pl.nsegs, pl.nbmax, pl.ngroups, pl.seg_rows, W, H, keys, map, (const float4 *)nullptr,
-                       (const unsigned *)nullptr, m.y0(H), m.y1(H), (const PcPair *)nullptr, 0, pl.cols);
+    pc_chunk_min(s, m, pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_PLANES), W, H, 1, 1, scratch, keys, map);
 }
 
 // Both volumes in one launch each (costs built on the fly): left volume = (g[0], other g[1].g1), right = (g[1], other g[0].g1).
@@ -844,38 +906,19 @@ void launch_chunk_min(hipStream_t s, March m, int W, int H, int Dloc, void *scra
 void launch_cvf_select2(hipStream_t s, March m, const Guidance *g, int W, int H, int Dloc, int d_begin, void *scratch,
                         unsigned long long *ts, const uint8_t *const *p4, int sel, int step)
 {
-    const bool tol = !p4 && (m.flags & PSM_FLAG_F32_TOL), fma = !p4 && (m.flags & PSM_FLAG_FMA_SOLVE);
     const PcPlan pl = pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_PLANES | PC_BOTH, 1, m.inflight);
-    const PcSel ps = {sel, step, pl.nxcd, 0, Dloc, 0, m.dstep};
-    float *kcost0 = (float *)scratch;
-    unsigned *kdisp0 = (unsigned *)(kcost0 + 4 * pl.rec_per_chunk * pl.nchunks);
-    float *kcost1 = (float *)((char *)scratch + pl.scratch_bytes());
-    unsigned *kdisp1 = (unsigned *)(kcost1 + 4 * pl.rec_per_chunk * pl.nchunks);
-    const dim3 grid(pc_blocks(pl, pl.nchunks), 2), blk(pl.narrow ? 64 * (PcLayout<1, true>::NA + PcLayout<1, true>::NB) : 64 * (PcLayout<1>::NA + PcLayout<1>::NB));
-    const PcSide s1 = {(const float4 *)g[1].g1, (const float4 *)g[1].g2, (const float4 *)g[1].g3, (const float2 *)g[1].g4, (const float4 *)g[0].g1, kcost1, kdisp1};
-#define PSM_LAUNCH_PC(U8V, VR, NW, A0, A1)                                                                                   \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cvf_pc<false, 3, 1, U8V, false, VR, NW>), grid, blk, 0, s, A0, A1, (const float4 *)g[0].g1, \
-                       (const float4 *)g[0].g2, (const float4 *)g[0].g3, (const float2 *)g[0].g4, W, H, Dloc, pl.ngroups, pl.nsegs, pl.seg_rows, m.y0(H), m.y1(H), \
-                       (const float4 *)g[1].g1, d_begin, pl.DC, kcost0, kdisp0, pl.nbmax, s1, ps, ts, (const PcPair *)nullptr)
-#define PSM_LAUNCH_PCN(U8V, VR, A0, A1) { if (pl.narrow) PSM_LAUNCH_PC(U8V, VR, true, A0, A1); else PSM_LAUNCH_PC(U8V, VR, false, A0, A1); }
-    if (p4) PSM_LAUNCH_PCN(true, 0, (const float *)p4[0], (float *)const_cast<uint8_t *>(p4[1]))
-    else if (fma) PSM_LAUNCH_PCN(false, 2, (const float *)nullptr, (float *)nullptr)
-    else if (tol) PSM_LAUNCH_PCN(false, 1, (const float *)nullptr, (float *)nullptr)
-    else PSM_LAUNCH_PCN(false, 0, (const float *)nullptr, (float *)nullptr)
-#undef PSM_LAUNCH_PCN
-#undef PSM_LAUNCH_PC
+    PcArgs a = {p4 ? (const float *)p4[0] : nullptr, p4 ? (float *)const_cast<uint8_t *>(p4[1]) : nullptr, W, H, Dloc, m.y0(H), m.y1(H),
+                d_begin, {}, PcSel{sel, step, pl.nxcd, 0, Dloc, 0, m.dstep}, ts, nullptr};
+    for (int v = 0; v < 2; ++v) {
+        const PcSide k = pc_planes(pl, scratch, v);
+        a.side[v] = PcSide{g[v].g1, g[v].g2, g[v].g3, g[v].g4, g[v ^ 1].g1, k.kcost, k.kdisp};
+    }
+    pc_launch(s, pl, dim3(pc_blocks(pl, pl.nchunks), 2), a, {PC_PLANES, 3, p4 != nullptr, pc_var(m, p4 != nullptr), false, pl.narrow, false});
 }
 
 void launch_chunk_min2sides(hipStream_t s, March m, int W, int H, int Dloc, void *scratch, long long *keys, uint8_t *map)
 {
-    const PcPlan pl = pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_PLANES | PC_BOTH, 1, m.inflight);
-    const float *kcost0 = (const float *)scratch;
-    const unsigned *kdisp0 = (const unsigned *)(kcost0 + 4 * pl.rec_per_chunk * pl.nchunks);
-    const float *kcost1 = (const float *)((const char *)scratch + pl.scratch_bytes());
-    const unsigned *kdisp1 = (const unsigned *)(kcost1 + 4 * pl.rec_per_chunk * pl.nchunks);
-    hipLaunchKernelGGL(k_chunk_min, dim3((unsigned)((pl.rec_per_chunk + 255) / 256), 2), dim3(256), 0, s, (const float4 *)kcost0, kdisp0,
-                       pl.nchunks, pl.ngroups * pl.nsegs, pl.nbmax, pl.ngroups, pl.seg_rows, W, H, keys, map, (const float4 *)kcost1, kdisp1, m.y0(H), m.y1(H),
-                       (const PcPair *)nullptr, 0, pl.cols);
+    pc_chunk_min(s, m, pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_PLANES | PC_BOTH, 1, m.inflight), W, H, 2, 1, scratch, keys, map);
 }
 
 // ... key form (MODE 2): keys[2][H][W] receives the packed minima (init: start from key(+inf, 0); otherwise continue from what
@@ -884,23 +927,13 @@ void launch_cvf_select_keys2(hipStream_t s, March m, const Guidance *g, int W, i
                              unsigned long long *ts, const uint8_t *const *p4, int init, int sel, int step)
 {
     const PcPlan pl = pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_KEYS | PC_BOTH, 1, m.inflight);
-    const PcSel ps = {sel, step, pl.nxcd, PSM_KNOB("PSM_PC_SPREAD", PC_KEY_SPREAD), Dloc, 0, m.dstep};
     const size_t HW = (size_t)W * H;
     if (init) hipLaunchKernelGGL(k_fill_keys, dim3((unsigned)((2 * HW + 255) / 256)), dim3(256), 0, s, keys, 2 * HW);
-    const dim3 grid(pc_blocks(pl, Dloc), 2), blk(pl.narrow ? 64 * (PcLayout<2, true>::NA + PcLayout<2, true>::NB) : 64 * (PcLayout<2>::NA + PcLayout<2>::NB));
-    const PcSide s1 = {(const float4 *)g[1].g1, (const float4 *)g[1].g2, (const float4 *)g[1].g3, (const float2 *)g[1].g4, (const float4 *)g[0].g1,
-                       (float *)(keys + HW), nullptr};
-#define PSM_LAUNCH_PC(U8V, VR, NW, A0, A1)                                                                                   \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cvf_pc<false, 3, 2, U8V, false, VR, NW>), grid, blk, 0, s, A0, A1,                     \
-                       (const float4 *)g[0].g1, (const float4 *)g[0].g2, (const float4 *)g[0].g3, (const float2 *)g[0].g4, W, H, Dloc, pl.ngroups, \
-                       pl.nsegs, pl.seg_rows, m.y0(H), m.y1(H), (const float4 *)g[1].g1, d_begin, 1, (float *)keys, (unsigned *)nullptr, 0, s1, ps, ts, (const PcPair *)nullptr)
-#define PSM_LAUNCH_PCN(U8V, VR, A0, A1) { if (pl.narrow) PSM_LAUNCH_PC(U8V, VR, true, A0, A1); else PSM_LAUNCH_PC(U8V, VR, false, A0, A1); }
-    if (p4) PSM_LAUNCH_PCN(true, 0, (const float *)p4[0], (float *)const_cast<uint8_t *>(p4[1]))
-    else if (m.flags & PSM_FLAG_FMA_SOLVE) PSM_LAUNCH_PCN(false, 2, (const float *)nullptr, (float *)nullptr)
-    else if (m.flags & PSM_FLAG_F32_TOL) PSM_LAUNCH_PCN(false, 1, (const float *)nullptr, (float *)nullptr)
-    else PSM_LAUNCH_PCN(false, 0, (const float *)nullptr, (float *)nullptr)
-#undef PSM_LAUNCH_PCN
-#undef PSM_LAUNCH_PC
+    PcArgs a = {p4 ? (const float *)p4[0] : nullptr, p4 ? (float *)const_cast<uint8_t *>(p4[1]) : nullptr, W, H, Dloc, m.y0(H), m.y1(H),
+                d_begin, {}, PcSel{sel, step, pl.nxcd, PSM_KNOB("PSM_PC_SPREAD", PC_KEY_SPREAD), Dloc, 0, m.dstep}, ts, nullptr};
+    for (int v = 0; v < 2; ++v)
+        a.side[v] = PcSide{g[v].g1, g[v].g2, g[v].g3, g[v].g4, g[v ^ 1].g1, (float *)(keys + v * HW), nullptr};
+    pc_launch(s, pl, dim3(pc_blocks(pl, Dloc), 2), a, {PC_KEYS, 3, p4 != nullptr, pc_var(m, p4 != nullptr), false, pl.narrow, false});
 }
 
 // ---- the same launches for `npairs` stereo pairs at once (psm_compute_batch): blockIdx.z = pair, pointers from the table ----
@@ -908,42 +941,24 @@ void launch_cvf_select2_batch(hipStream_t s, March m, const PcPair *tab, int npa
                               unsigned long long *ts, bool u8, int sel, int step)
 {
     const PcPlan pl = pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_PLANES | PC_BOTH, npairs);
-    const PcSel ps = {sel, step, pl.nxcd, 0, Dloc, (unsigned long long)pl.rec_per_chunk * pl.nchunks, m.dstep};
-    const dim3 grid(pc_blocks(pl, pl.nchunks), 2, npairs), blk(pl.narrow ? 64 * (PcLayout<1, true>::NA + PcLayout<1, true>::NB) : 64 * (PcLayout<1>::NA + PcLayout<1>::NB));
-#define PSM_LAUNCH_PCB(U8V) { if (pl.narrow) PSM_LAUNCH_PCBN(U8V, true); else PSM_LAUNCH_PCBN(U8V, false); }
-#define PSM_LAUNCH_PCBN(U8V, NW)                                                                                              \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cvf_pc<false, 3, 1, U8V, true, 0, NW>), grid, blk, 0, s, (const float *)nullptr, (float *)nullptr,  \
-                       (const float4 *)nullptr, (const float4 *)nullptr, (const float4 *)nullptr, (const float2 *)nullptr, W, H, Dloc, \
-                       pl.ngroups, pl.nsegs, pl.seg_rows, m.y0(H), m.y1(H), (const float4 *)nullptr, d_begin, pl.DC, (float *)nullptr, \
-                       (unsigned *)nullptr, pl.nbmax, PcSide{}, ps, ts, tab)
-    if (u8) PSM_LAUNCH_PCB(true) else PSM_LAUNCH_PCB(false)
-#undef PSM_LAUNCH_PCB
-#undef PSM_LAUNCH_PCBN
+    const PcArgs a = {nullptr, nullptr, W, H, Dloc, m.y0(H), m.y1(H), d_begin, {},
+                      PcSel{sel, step, pl.nxcd, 0, Dloc, (unsigned long long)pl.rec_per_chunk * pl.nchunks, m.dstep}, ts, tab};
+    pc_launch(s, pl, dim3(pc_blocks(pl, pl.nchunks), 2, npairs), a, {PC_PLANES, 3, u8, 0, true, pl.narrow, false});
 }
 
 void launch_chunk_min2sides_batch(hipStream_t s, March m, const PcPair *tab, int npairs, int W, int H, int Dloc, bool to_maps)
 {
-    const PcPlan pl = pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_PLANES | PC_BOTH, npairs);
-    hipLaunchKernelGGL(k_chunk_min, dim3((unsigned)((pl.rec_per_chunk + 255) / 256), 2, npairs), dim3(256), 0, s, (const float4 *)nullptr,
-                       (const unsigned *)nullptr, pl.nchunks, pl.ngroups * pl.nsegs, pl.nbmax, pl.ngroups, pl.seg_rows, W, H, (long long *)nullptr,
-                       (uint8_t *)nullptr, (const float4 *)nullptr, (const unsigned *)nullptr, m.y0(H), m.y1(H), tab, to_maps ? 1 : 0, pl.cols);
+    pc_chunk_min(s, m, pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_PLANES | PC_BOTH, npairs), W, H, 2, npairs, nullptr, nullptr, nullptr,
+                 tab, to_maps);
 }
 
 void launch_cvf_select_keys2_batch(hipStream_t s, March m, const PcPair *tab, int npairs, int W, int H, int Dloc, int d_begin,
                                    unsigned long long *ts, bool u8, int sel, int step)
 {
     const PcPlan pl = pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_KEYS | PC_BOTH, npairs);
-    const PcSel ps = {sel, step, pl.nxcd, PC_KEY_SPREAD, Dloc, 0, m.dstep};
-    const dim3 grid(pc_blocks(pl, Dloc), 2, npairs), blk(pl.narrow ? 64 * (PcLayout<2, true>::NA + PcLayout<2, true>::NB) : 64 * (PcLayout<2>::NA + PcLayout<2>::NB));
-#define PSM_LAUNCH_PCB(U8V) { if (pl.narrow) PSM_LAUNCH_PCBN(U8V, true); else PSM_LAUNCH_PCBN(U8V, false); }
-#define PSM_LAUNCH_PCBN(U8V, NW)                                                                                              \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cvf_pc<false, 3, 2, U8V, true, 0, NW>), grid, blk, 0, s, (const float *)nullptr, (float *)nullptr,  \
-                       (const float4 *)nullptr, (const float4 *)nullptr, (const float4 *)nullptr, (const float2 *)nullptr, W, H, Dloc, \
-                       pl.ngroups, pl.nsegs, pl.seg_rows, m.y0(H), m.y1(H), (const float4 *)nullptr, d_begin, 1, (float *)nullptr,      \
-                       (unsigned *)nullptr, 0, PcSide{}, ps, ts, tab)
-    if (u8) PSM_LAUNCH_PCB(true) else PSM_LAUNCH_PCB(false)
-#undef PSM_LAUNCH_PCB
-#undef PSM_LAUNCH_PCBN
+    const PcArgs a = {nullptr, nullptr, W, H, Dloc, m.y0(H), m.y1(H), d_begin, {}, PcSel{sel, step, pl.nxcd, PC_KEY_SPREAD, Dloc, 0, m.dstep},
+                      ts, tab};
+    pc_launch(s, pl, dim3(pc_blocks(pl, Dloc), 2, npairs), a, {PC_KEYS, 3, u8, 0, true, pl.narrow, false});
 }
 
 }  // namespace psm
