@@ -52,12 +52,9 @@ extern "C" int psm_compute_batch(psm_ctx *const *ctxs, int n)
     if (!c0->ev_batch) PSM_HIP(c0, hipEventCreateWithFlags(&c0->ev_batch, hipEventDisableTiming));
 
     // ---- plan and scratch (before any launch: growing a scratch buffer synchronises its context's stream) ----
-    const bool two_phase = !(c0->march.flags & PSM_FLAG_TWO_PHASE_OFF) && Dloc >= 2 && (Dloc >= 112 || (c0->march.flags & PSM_FLAG_TWO_PHASE_ON));
-    const int S = pc_seed_stride(W, H, c0->dtype == PSM_U8);
-    const int n1 = two_phase ? (Dloc + S - 1) / S : Dloc, n2 = Dloc - n1;
-    const PcPlan pl = pc_plan(W, H, n1, c0->march.seg_rows, PC_PLANES | PC_BOTH, n);
+    const SelPlan sp = select_plan(c0, n, true);
     for (int i = 0; i < n; ++i)
-        if (ensure_gf_scratch(ctxs[i], 2 * pl.scratch_bytes())) return fail(c0, "psm_compute_batch: %s", ctxs[i]->err.c_str());
+        if (ensure_gf_scratch(ctxs[i], sp.scratch_bytes)) return fail(c0, "psm_compute_batch: %s", ctxs[i]->err.c_str());
 
     // ---- every context's earlier work (uploads, downloads of its maps) is ordered before the shared launches ----
     for (int i = 0; i < n; ++i) {
@@ -76,15 +73,7 @@ extern "C" int psm_compute_batch(psm_ctx *const *ctxs, int n)
 
     // ---- the table of the pairs' pointers (device copy refreshed only when an entry changed) ----
     std::vector<PcPair> tab((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        const psm_ctx *c = ctxs[i];
-        PcPair &p = tab[i];
-        memset(&p, 0, sizeof p);
-        for (int k = 0; k < 2; ++k) { p.raw[k] = c->raw[k]; p.g[k] = c->g[k]; p.p4[k] = c->p4[k]; }
-        p.scratch = c->gf_scratch;
-        p.keys = c->keys_cur;
-        p.maps = c->maps;
-    }
+    for (int i = 0; i < n; ++i) tab[i] = pc_pair(ctxs[i]);
     if (c0->batch_host.size() != tab.size() || memcmp(c0->batch_host.data(), tab.data(), tab.size() * sizeof(PcPair)) != 0) {
         if (c0->batch_cap < tab.size()) {
             PSM_HIP(c0, hipStreamSynchronize(s));
@@ -111,6 +100,7 @@ extern "C" int psm_compute_batch(psm_ctx *const *ctxs, int n)
         PSM_HIP(c0, hipEventRecord(c0->ev_tab[slot], s));
     }
     const PcPair *dt = c0->batch_tab;
+    const PcPairs P = {dt, n, {}};
 
     const int depth = c0->raw_depth;
     const size_t row = (size_t)W * 3 * (depth == PSM_IMG_F32 ? 4 : 1);
@@ -127,25 +117,12 @@ extern "C" int psm_compute_batch(psm_ctx *const *ctxs, int n)
         // ---- CostFilter: guidance of every image, the fused select kernel over every pair, the reduction ----
         {
             Prof p(c0, PSM_K_GUIDE);
-            launch_guidance_batch(s, dt, n, W, H, row, u8 ? 0 : (depth == PSM_IMG_F32 ? 2 : 1));
+            launch_guidance(s, P, W, H, 0, H, false, u8 ? 0 : (depth == PSM_IMG_F32 ? 2 : 1), row);
         }
-        {
-            Prof p(c0, PSM_K_CVF_F);
-            launch_cvf_select2_batch(s, c0->march, dt, n, W, H, n1, c0->d0, next_pc_stamp(c0), u8, two_phase ? 1 : 0, two_phase ? S : 1);
-        }
-        {
-            Prof p(c0, PSM_K_WTA);
-            launch_chunk_min2sides_batch(s, c0->march, dt, n, W, H, n1, whole && !(two_phase && n2 > 0));
-        }
-        if (two_phase && n2 > 0) {
-            {
-                Prof p(c0, PSM_K_CVF_F);
-                launch_cvf_select_keys2_batch(s, c0->march, dt, n, W, H, n2, c0->d0, next_pc_stamp(c0), u8, 2, S);
-            }
-            if (whole) {
-                Prof p(c0, PSM_K_MERGE);
-                launch_merge_batch(s, dt, n, W, H);
-            }
+        if (enqueue_select(c0, P, sp)) return 1;
+        if (sp.two_phase && whole) {
+            Prof p(c0, PSM_K_MERGE);
+            launch_merge_batch(s, dt, n, W, H);
         }
         return check_launch(c0, "batch (prep, guidance, fused select filter, reduction)");
     };

@@ -5,6 +5,7 @@
 // (src/DispEst.cpp:272-276,299-308); the FGF entry follows DispEst::CostFilter_FGF (src/DispEst.cpp:281-296).
 #include "psm_ctx.h"
 
+#include <cstring>
 #include <utility>
 
 using namespace psm;
@@ -115,6 +116,62 @@ int ensure_gf_scratch(psm_ctx *c, size_t bytes)
     return 0;
 }
 
+PcPair pc_pair(const psm_ctx *c)
+{
+    PcPair p;
+    memset(&p, 0, sizeof p);             // (psm_compute_batch compares table entries bytewise)
+    for (int k = 0; k < 2; ++k) { p.raw[k] = c->raw[k]; p.g[k] = c->g[k]; p.p4[k] = c->p4[k]; }
+    p.scratch = c->gf_scratch;
+    p.keys = c->keys_cur;
+    p.maps = c->maps;
+    return p;
+}
+
+// npairs / batch: see pc_plan_select.  The geometry, options and slices are the context's (a batch: those of its first context).
+SelPlan select_plan(const psm_ctx *c, int npairs, bool batch)
+{
+    const March &m = c->march;
+    SelPlan sp;
+    // Two-phase selection (default from 112 local slices up - measured: -10 % at 1080p x 256, -13 % at 4K x 256, -4 % at
+    // 720p x 128, worse at 64 slices and below; PSM_FLAG_TWO_PHASE_ON / _OFF force it for any Dloc >= 2 / disable it): every
+    // S-th slice goes through the minima planes -> k_chunk_min -> keys; the other slices then run against that seeded key
+    // plane (key form: one key load per voxel, an atomic only where a slice beats the current minimum - rare after the
+    // seeding), so they write no planes and need no reduction.  S = pc_seed_stride: 8 since round 6 (5, and 4 from 4 Mpixel up,
+    // while the key loads came from the memory side).
+    sp.two_phase = !(m.flags & PSM_FLAG_TWO_PHASE_OFF) && c->Dloc >= 2 && (c->Dloc >= 112 || (m.flags & PSM_FLAG_TWO_PHASE_ON));
+    sp.S = sp.two_phase ? pc_seed_stride(c->W, m.rows(c->H), c->dtype == PSM_U8) : 1;
+    sp.n1 = (c->Dloc + sp.S - 1) / sp.S;
+    sp.n2 = c->Dloc - sp.n1;
+    // The reduction is the last thing that touches the keys: when the pair holds every slice and one phase runs, it writes the maps
+    // (the low byte of each key) in the same pass.  After two phases a batch merges its maps itself (k_merge_batch), a single
+    // context leaves them to psm_disp_select.
+    sp.maps = c->Dloc == c->D && !sp.two_phase;
+    sp.scratch_bytes = 2 * pc_plan_select(m, c->W, c->H, sp.n1, PC_PLANES, npairs, batch).scratch_bytes();
+    return sp;
+}
+
+// Plane form (all slices, or every S-th) -> reduction -> key form (the others) for the pairs P on c's stream, with c's brackets
+// and launch stamps.  Every pair's scratch holds sp.scratch_bytes.
+int enqueue_select(psm_ctx *c, const PcPairs &P, const SelPlan &sp)
+{
+    const bool u8 = c->dtype == PSM_U8;
+    {
+        Prof p(c, PSM_K_CVF_F);
+        launch_cvf_select2(c->stream, c->march, P, u8, c->W, c->H, sp.n1, c->d0, next_pc_stamp(c), sp.two_phase ? 1 : 0, sp.S);
+    }
+    // (a single context's maps may still be the source of the last frame's download; a batch waited for its contexts' before the table)
+    if (sp.maps && !P.tab && maps_writable(c)) return 1;
+    {
+        Prof p(c, PSM_K_WTA);
+        launch_chunk_min2sides(c->stream, c->march, P, c->W, c->H, sp.n1, sp.maps);
+    }
+    if (sp.n2 > 0) {
+        Prof p(c, PSM_K_CVF_F);
+        launch_cvf_select_keys2(c->stream, c->march, P, u8, c->W, c->H, sp.n2, c->d0, next_pc_stamp(c), 2, sp.S);
+    }
+    return 0;
+}
+
 // the pair psm_upload_pair_async staged becomes the current one: the kernels wait for its copy on the device
 int adopt_staged_pair(psm_ctx *c)
 {
@@ -153,7 +210,7 @@ int ensure_whole_planes(psm_ctx *c)
     if (!(c->have_guid[0] && c->have_guid[1])) {
         {
             Prof p(c, PSM_K_GUIDE);
-            launch_guidance(c->stream, c->g[0], c->W, c->H, &c->g[1], 0, 0, fma_solve(c));
+            launch_guidance(c->stream, PcPairs{nullptr, 1, pc_pair(c)}, c->W, c->H, 0, 0, fma_solve(c));
         }
         c->have_guid[0] = c->have_guid[1] = true;
         c->guid_y0 = 0;
@@ -243,7 +300,7 @@ int filter_side(psm_ctx *c, int side, bool stage_b)
     if (!c->have_guid[side]) {
         // the guidance of BOTH images in one launch the first time either side asks (the other side's call then finds it)
         Prof p(c, PSM_K_GUIDE);
-        launch_guidance(c->stream, c->g[0], W, H, &c->g[1], 0, 0, fma_solve(c));
+        launch_guidance(c->stream, PcPairs{nullptr, 1, pc_pair(c)}, W, H, 0, 0, fma_solve(c));
         c->have_guid[0] = c->have_guid[1] = true;
     }
     // Default: the fused kernel in "select" mode - the WTA over the local slices runs inside the filter, the filtered
@@ -346,7 +403,7 @@ int filter_both(psm_ctx *c)
             const size_t row = (size_t)c->W * 3 * (c->raw_depth == PSM_IMG_F32 ? 4 : 1);
             {
                 Prof p(c, PSM_K_GUIDE);
-                launch_guidance(c->stream, c->g[0], c->W, c->H, &c->g[1], ya, yb, fma_solve(c), c->raw[0], c->raw[1], row, c->raw_depth == PSM_IMG_F32);
+                launch_guidance(c->stream, PcPairs{nullptr, 1, pc_pair(c)}, c->W, c->H, ya, yb, fma_solve(c), c->raw_depth == PSM_IMG_F32 ? 2 : 1, row);
             }
             if (check_launch(c, "prep + guidance")) return 1;
             if (c->ev_free) PSM_HIP(c, hipEventRecord(c->ev_free, c->stream));   // the staged images have been read: their slot may be refilled
@@ -361,58 +418,19 @@ int filter_both(psm_ctx *c)
             // consumer recomputes them; guid_y0/1 remember what is there for the next frame's check)
             if (!(c->have_guid[0] && c->have_guid[1]) && !(c->guid_y1 > c->guid_y0 && c->guid_y0 <= gy0 && c->guid_y1 >= gy1)) {
                 Prof p(c, PSM_K_GUIDE);
-                launch_guidance(c->stream, c->g[0], c->W, c->H, &c->g[1], gy0, gy1, fma_solve(c));
+                launch_guidance(c->stream, PcPairs{nullptr, 1, pc_pair(c)}, c->W, c->H, gy0, gy1, fma_solve(c));
                 c->guid_y0 = gy0;
                 c->guid_y1 = gy1;
                 if (gy0 == 0 && gy1 == c->H) c->have_guid[0] = c->have_guid[1] = true;
             }
         }
     }
-    const uint8_t *const *p4 = c->dtype == PSM_U8 ? c->p4 : nullptr;
-    // Two-phase selection (default from 112 local slices up - measured: -10 % at 1080p x 256, -13 % at 4K x 256, -4 % at
-    // 720p x 128, worse at 64 slices and below; PSM_FLAG_TWO_PHASE_ON / _OFF force it for any Dloc >= 2 / disable it): every
-    // S-th slice goes through the minima planes -> k_chunk_min -> keys; the other slices then run against that seeded key
-    // plane (key form: one key load per voxel, an atomic only where a slice beats the current minimum - rare after the
-    // seeding), so they write no planes and need no reduction.  S = pc_seed_stride: 8 since round 6 (5, and 4 from 4 Mpixel up,
-    // while the key loads came from the memory side).
-    const bool two_phase = !(c->march.flags & PSM_FLAG_TWO_PHASE_OFF) && c->Dloc >= 2 && (c->Dloc >= 112 || (c->march.flags & PSM_FLAG_TWO_PHASE_ON));
-    if (two_phase) {
-        const int S = pc_seed_stride(c->W, c->march.rows(c->H), c->dtype == PSM_U8);
-        const int n1 = (c->Dloc + S - 1) / S, n2 = c->Dloc - n1;
-        const PcPlan pl1 = pc_plan(c->W, c->march.rows(c->H), n1, c->march.seg_rows, PC_PLANES | PC_BOTH, 1, c->march.inflight);
-        if (ensure_gf_scratch(c, 2 * pl1.scratch_bytes())) return 1;
-        {
-            Prof p(c, PSM_K_CVF_F);
-            launch_cvf_select2(c->stream, c->march, c->g, c->W, c->H, n1, c->d0, c->gf_scratch, next_pc_stamp(c), p4, 1, S);
-        }
-        {
-            Prof p(c, PSM_K_WTA);
-            launch_chunk_min2sides(c->stream, c->march, c->W, c->H, n1, c->gf_scratch, c->keys_cur, nullptr);
-        }
-        if (n2 > 0) {
-            Prof p(c, PSM_K_CVF_F);
-            launch_cvf_select_keys2(c->stream, c->march, c->g, c->W, c->H, n2, c->d0, c->keys_cur, next_pc_stamp(c), p4, 0, 2, S);
-        }
-        c->gf_virtual[0] = c->gf_virtual[1] = true;
-        return check_launch(c, "cvf (fused, select mode, two phases, both volumes)");
-    }
-    const PcPlan pl = pc_plan(c->W, c->march.rows(c->H), c->Dloc, c->march.seg_rows, PC_PLANES | PC_BOTH, 1, c->march.inflight);
-    if (ensure_gf_scratch(c, 2 * pl.scratch_bytes())) return 1;
-    {
-        Prof p(c, PSM_K_CVF_F);
-        launch_cvf_select2(c->stream, c->march, c->g, c->W, c->H, c->Dloc, c->d0, c->gf_scratch, next_pc_stamp(c), p4);
-    }
-    {
-        // The reduction of the planes is the last thing that touches the keys: when the context holds every slice it writes the
-        // maps (the low byte of each key) in the same pass, and psm_disp_select has no kernel left to launch.
-        uint8_t *const early = c->Dloc == c->D ? c->maps : nullptr;
-        if (early && maps_writable(c)) return 1;   // (still the source of the last frame's download?)
-        Prof p(c, PSM_K_WTA);
-        launch_chunk_min2sides(c->stream, c->march, c->W, c->H, c->Dloc, c->gf_scratch, c->keys_cur, early);
-        c->maps_early = early;
-    }
+    const SelPlan sp = select_plan(c, 1, false);
+    if (ensure_gf_scratch(c, sp.scratch_bytes)) return 1;
+    if (enqueue_select(c, PcPairs{nullptr, 1, pc_pair(c)}, sp)) return 1;
+    c->maps_early = sp.maps ? c->maps : nullptr;      // (psm_disp_select has no kernel left to launch)
     c->gf_virtual[0] = c->gf_virtual[1] = true;
-    return check_launch(c, "cvf (fused, select mode, both volumes)");
+    return check_launch(c, sp.two_phase ? "cvf (fused, select mode, two phases, both volumes)" : "cvf (fused, select mode, both volumes)");
 }
 
 }  // namespace

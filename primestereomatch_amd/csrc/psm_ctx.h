@@ -225,6 +225,17 @@ int fgf_flush(psm_ctx *c, int side);
 int materialize(psm_ctx *c, int side);
 int adopt_staged_pair(psm_ctx *c);               // the pair psm_upload_pair_async staged becomes the current one
 int ensure_gf_scratch(psm_ctx *c, size_t bytes);
+// The select path of the default product path - fused select filter of both volumes, reduction - for one pair (psm_cost_filter)
+// or the pairs of a batch (psm_compute_batch)
+PcPair pc_pair(const psm_ctx *c);                // the context's pair as the launchers see it (an entry of the batch table)
+struct SelPlan {
+    bool two_phase;
+    int S, n1, n2;          // the plane form runs n1 slices (every S-th; one phase: all, S = 1), the key form the other n2
+    bool maps;              // the reduction writes the maps
+    size_t scratch_bytes;   // chunk planes per pair (both volumes)
+};
+SelPlan select_plan(const psm_ctx *c, int npairs, bool batch);
+int enqueue_select(psm_ctx *c, const PcPairs &P, const SelPlan &sp);
 // psm_api_core.cpp: measure the exponent range of n floats on `stream` into slot (0..3) of the context's range buffers
 int range_enqueue(psm_ctx *c, hipStream_t stream, int slot, const float *p0, size_t n0, const float *p1, size_t n1);
 bool range_inside(const psm_ctx *c, int slot, int lo_exp, int hi_exp);     // after the stream has been synchronised

@@ -33,7 +33,7 @@ struct March {       // geometry of the marching kernels
 
 // ---- batched launches: B stereo pairs of one geometry share every launch of the default path (psm_compute_batch; the
 // reference's use on Middlebury-size data is a loop over pairs, src/main.cpp:64-73) ----
-struct PcPair {                  // one pair of the batch: an entry of a device table the kernels index with the pair number
+struct PcPair {                  // one pair's buffers: an entry of a batch's device table the kernels index with the pair number
     const void *raw[2];          // staged interleaved images (left, right)
     Guidance g[2];
     uint8_t *p4[2];              // 8-bit char mode: {c0,c1,c2,grad} byte planes (else null)
@@ -41,8 +41,14 @@ struct PcPair {                  // one pair of the batch: an entry of a device 
     long long *keys;             // [2][H][W] packed minima
     uint8_t *maps;               // [2][H][W]
 };
+// The pairs one launch of the select path covers: the single pair `one` (tab == nullptr, n == 1; its pointers go into the
+// kernels' arguments), or the n pairs of the device table `tab` (psm_compute_batch; blockIdx.z = pair, `one` unused)
+struct PcPairs {
+    const PcPair *tab;
+    int n;
+    PcPair one;
+};
 void launch_prep_batch(hipStream_t s, const PcPair *tab, int npairs, size_t pitch, int depth_f32, int W, int H, bool u8_planes);
-void launch_guidance_batch(hipStream_t s, const PcPair *tab, int npairs, int W, int H, size_t pitch = 0, int src = 0);   // src 1 / 2: + image preparation (8-bit / float staged images)
 void launch_merge_batch(hipStream_t s, const PcPair *tab, int npairs, int W, int H);   // keys -> maps of every pair
 
 // device <-> page-locked host copy as a kernel (both pointers 16-byte aligned)
@@ -52,12 +58,10 @@ void launch_range_f32(hipStream_t s, const float *p, size_t n, unsigned *out);
 // image -> g1 (planarise, scale, gray, x-gradient).  src: device copy of the interleaved image.
 void launch_prep(hipStream_t s, const void *src, size_t pitch, int depth_f32, int W, int H, float4 *g1, const void *src1 = nullptr,
                  float4 *g11 = nullptr);
-// g1 -> g2,g3,g4 (second != NULL: both images in one launch; [ybeg, yend): rows of g2..g4 to produce, default all)
-void launch_guidance(hipStream_t s, Guidance g, int W, int H, const Guidance *second = nullptr, int ybeg = 0, int yend = 0,
-                     bool fma = false,    // fma: PSM_FLAG_FMA_SOLVE - minors and DET in their fused forms
-                     const void *raw0 = nullptr, const void *raw1 = nullptr, size_t pitch = 0, int raw_f32 = 0);
-// raw0 / raw1 (device copies of the interleaved images, row pitch `pitch`): image preparation (launch_prep) in the same launch -
-// the g1 rows [ybeg, yend) of both images are written from them
+// g1 -> g2,g3,g4 of both images of every pair in P, one launch ([ybeg, yend): rows of g2..g4 to produce, yend <= ybeg: all).
+// fma: PSM_FLAG_FMA_SOLVE - minors and DET in their fused forms.  src 1 / 2: image preparation (launch_prep) in the same launch
+// from the pairs' staged 8-bit / float images (raw, row pitch `pitch`) - the g1 rows [ybeg, yend) are written from them
+void launch_guidance(hipStream_t s, const PcPairs &P, int W, int H, int ybeg, int yend, bool fma, int src = 0, size_t pitch = 0);
 // cost volume slices [d_begin, d_begin+Dloc) of one side.  base: g1 of the side's own image.
 void launch_cvc(hipStream_t s, const float4 *g1_base, const float4 *g1_other, float *vol, int W, int H,
                 int d_begin, int Dloc, int right, int ybeg, int yend);
@@ -86,6 +90,8 @@ struct PcPlan {
     size_t scratch_bytes() const { return rec_per_chunk * (size_t)nchunks * rec_bytes; }
 };
 PcPlan pc_plan(int W, int rows, int Dloc, int seg_rows_opt, int form, int batch = 1, int inflight = 1);   // batch: pairs per launch (psm_compute_batch); inflight: March::inflight
+// pc_plan of the two-volume select launches (form PC_PLANES / PC_KEYS) of npairs pairs; batch: the pairs of psm_compute_batch
+PcPlan pc_plan_select(March m, int W, int H, int Dloc, int form, int npairs, bool batch);
 int pc_seed_stride(int W, int rows, bool u8);                     // S of the two-phase selection: every S-th slice seeds the key plane (rows: of the stripe being filtered)
 // ts (may be NULL): slot of this launch in a buffer of 3 x PC_TS_SLOTS 64-bit words {first workgroup start | last workgroup
 // end | form} in ticks of the device's constant-rate clock (PSM_OPT_PROFILE 2, psm_filter_launch_times)
@@ -95,20 +101,17 @@ void launch_cvf_select(hipStream_t s, March m, const float *vin, Guidance g, int
                        int d_begin, int cvc_mode, void *scratch, unsigned long long *ts = nullptr, const uint8_t *p4_own = nullptr,
                        const uint8_t *p4_other = nullptr);
 void launch_chunk_min(hipStream_t s, March m, int W, int H, int Dloc, void *scratch, long long *keys, uint8_t *map);
-// both volumes per launch (costs on the fly): g[0] / g[1] = guidance of the left / right image; keys / map: [2][H][W];
-// Dloc slices, which ones: (sel, step) - 0: all, 1: every step-th, 2: the others
-void launch_cvf_select2(hipStream_t s, March m, const Guidance *g, int W, int H, int Dloc, int d_begin, void *scratch,
-                        unsigned long long *ts = nullptr, const uint8_t *const *p4 = nullptr, int sel = 0, int step = 1);
-void launch_chunk_min2sides(hipStream_t s, March m, int W, int H, int Dloc, void *scratch, long long *keys, uint8_t *map);
-void launch_cvf_select_keys2(hipStream_t s, March m, const Guidance *g, int W, int H, int Dloc, int d_begin, long long *keys,
-                             unsigned long long *ts = nullptr, const uint8_t *const *p4 = nullptr, int init = 1, int sel = 0, int step = 1);
-// the three launches above for `npairs` pairs at once (blockIdx.z = pair, pointers from the device table `tab`; every pair's
-// scratch holds 2 x pc_plan(..., PC_PLANES | PC_BOTH, npairs).scratch_bytes()); to_maps: the reduction also writes the maps
-void launch_cvf_select2_batch(hipStream_t s, March m, const PcPair *tab, int npairs, int W, int H, int Dloc, int d_begin,
-                              unsigned long long *ts, bool u8, int sel = 0, int step = 1);
-void launch_chunk_min2sides_batch(hipStream_t s, March m, const PcPair *tab, int npairs, int W, int H, int Dloc, bool to_maps);
-void launch_cvf_select_keys2_batch(hipStream_t s, March m, const PcPair *tab, int npairs, int W, int H, int Dloc, int d_begin,
-                                   unsigned long long *ts, bool u8, int sel, int step);
+// both volumes of every pair in P per launch (costs on the fly; u8: 8-bit char mode): the left volume is filtered with the guidance
+// g[0] of the left image, the right one with g[1]; keys / maps: [2][H][W] per pair; grid z = pair (a single pair: 1).  Dloc slices,
+// which ones: (sel, step) - 0: all, 1: every step-th, 2: the others.
+// ... plane form: chunk planes in each pair's scratch (2 x pc_plan_select(..., PC_PLANES, ...).scratch_bytes())
+void launch_cvf_select2(hipStream_t s, March m, const PcPairs &P, bool u8, int W, int H, int Dloc, int d_begin, unsigned long long *ts,
+                        int sel, int step);
+// ... their reduction to each pair's keys; to_maps: the maps as well
+void launch_chunk_min2sides(hipStream_t s, March m, const PcPairs &P, int W, int H, int Dloc, bool to_maps);
+// ... key form: continues from the minima each pair's keys hold (the second phase of the two-phase selection)
+void launch_cvf_select_keys2(hipStream_t s, March m, const PcPairs &P, bool u8, int W, int H, int Dloc, int d_begin,
+                             unsigned long long *ts, int sel, int step);
 // plain 8x8 box filter of every slice (the north-star kernel in isolation)
 void launch_box8(hipStream_t s, int variant, March m, const float *vol, float *out, int W, int H, int Dloc);
 // WTA over local slices -> packed keys (keys != NULL) and/or final map (map != NULL)

@@ -23,6 +23,8 @@
 #include "psm_cost.h"
 #include "psm_dev.h"
 
+#include <algorithm>
+
 namespace psm {
 
 // ------------------------------------------------------------------------------------------
@@ -262,43 +264,25 @@ __global__ __launch_bounds__(192) void k_guide_march(const float4 *g1, int W, in
     }
 }
 
-void launch_guidance(hipStream_t s, Guidance g, int W, int H, const Guidance *second, int ybeg, int yend, bool fma,
-                     const void *raw0, const void *raw1, size_t pitch, int raw_f32)
-{   // second != NULL: the guidance of both images in one launch; [ybeg, yend) (yend <= ybeg: all rows): the rows of g2..g4
-    // to produce - a row stripe of the filter needs its own rows + 4 either side.  raw0 / raw1 != NULL: CVC::preprocess in the
-    // same launch - the images are read from the staged interleaved copies, and the g1 rows [ybeg, yend) are WRITTEN
+void launch_guidance(hipStream_t s, const PcPairs &P, int W, int H, int ybeg, int yend, bool fma, int src, size_t pitch)
+{   // [ybeg, yend): the rows of g2..g4 to produce - a row stripe of the filter needs its own rows + 4 either side.  src != 0:
+    // CVC::preprocess in the same launch - the images are read from the staged interleaved copies, and the g1 rows [ybeg, yend)
+    // are WRITTEN.  A single pair passes its planes and images in the arguments; a table is read by the kernel (blockIdx.y = image)
     if (yend <= ybeg) { ybeg = 0; yend = H; }
     const int rows = yend - ybeg;
     // one workgroup of three waves per (strip, segment); segments as short as still fill ~2 workgroups per SIMD-quad of the
     // chip in one resident round (8..64 rows each: 7 halo rows per segment)
     const int nstrips = (W + 55) / 56;
     const PcDev dev = pc_dev();
-    const int wgs = 6 * dev.nxcd * dev.cus_per_xcd / (second ? 2 : 1);   // per image (87 VGPRs, 18 KB of LDS: ~6 resident workgroups per CU)
+    const int wgs = std::max(1, 6 * dev.nxcd * dev.cus_per_xcd / (2 * P.n));   // per image (87 VGPRs, 18 KB of LDS: ~6 resident workgroups per CU)
     int seg_rows = 8;
     while (seg_rows < 64 && nstrips * ((rows + seg_rows - 1) / seg_rows) > wgs) ++seg_rows;
     const int nsegs = (rows + seg_rows - 1) / seg_rows;
-#define PSM_LAUNCH_G(SRC)                                                                                                            \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_guide_march<SRC>), dim3(nstrips * nsegs, second ? 2 : 1), dim3(192), 0, s, (const float4 *)g.g1, W, H, nstrips, \
-                       seg_rows, g.g2, g.g3, g.g4, second ? *second : Guidance{}, ybeg, yend, (const PcPair *)nullptr, fma ? 1 : 0, raw0, raw1, pitch)
-    if (!raw0) PSM_LAUNCH_G(0); else if (raw_f32) PSM_LAUNCH_G(2); else PSM_LAUNCH_G(1);
-#undef PSM_LAUNCH_G
-}
-
-// ---- the same two kernels for every pair of a batch (psm_compute_batch): one launch each, images indexed through the table ----
-void launch_guidance_batch(hipStream_t s, const PcPair *tab, int npairs, int W, int H, size_t pitch, int src)
-{   // src 0: g1 of every image exists (launch_prep_batch); 1 / 2: image preparation in the same launch, from the table's staged 8-bit /
-    // float images (row pitch `pitch`), as launch_guidance does for one pair
-    const int nstrips = (W + 55) / 56;
-    const PcDev dev = pc_dev();
-    const int wgs = 6 * dev.nxcd * dev.cus_per_xcd / (2 * npairs) > 0 ? 6 * dev.nxcd * dev.cus_per_xcd / (2 * npairs) : 1;
-    int seg_rows = 8;
-    while (seg_rows < 64 && nstrips * ((H + seg_rows - 1) / seg_rows) > wgs) ++seg_rows;
-    const int nsegs = (H + seg_rows - 1) / seg_rows;
-#define PSM_LAUNCH_GB(SRC)                                                                                                          \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_guide_march<SRC>), dim3(nstrips * nsegs, 2 * npairs), dim3(192), 0, s, (const float4 *)nullptr, W, H, nstrips, seg_rows, \
-                       (float4 *)nullptr, (float4 *)nullptr, (float2 *)nullptr, Guidance{}, 0, H, tab, 0, (const void *)nullptr, (const void *)nullptr, pitch)
-    if (src == 1) PSM_LAUNCH_GB(1); else if (src == 2) PSM_LAUNCH_GB(2); else PSM_LAUNCH_GB(0);
-#undef PSM_LAUNCH_GB
+    const Guidance gl = P.tab ? Guidance{} : P.one.g[0], gr = P.tab ? Guidance{} : P.one.g[1];
+    const bool raw = !P.tab && src != 0;
+    hipLaunchKernelGGL(src == 1 ? k_guide_march<1> : (src == 2 ? k_guide_march<2> : k_guide_march<0>), dim3(nstrips * nsegs, 2 * P.n),
+                       dim3(192), 0, s, (const float4 *)gl.g1, W, H, nstrips, seg_rows, gl.g2, gl.g3, gl.g4, gr, ybeg, yend, P.tab,
+                       fma ? 1 : 0, raw ? P.one.raw[0] : nullptr, raw ? P.one.raw[1] : nullptr, pitch);
 }
 
 // ------------------------------------------------------------------------------------------

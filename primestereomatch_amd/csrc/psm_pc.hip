@@ -899,66 +899,56 @@ void launch_chunk_min(hipStream_t s, March m, int W, int H, int Dloc, void *scra
     pc_chunk_min(s, m, pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_PLANES), W, H, 1, 1, scratch, keys, map);
 }
 
-// Both volumes in one launch each (costs built on the fly): left volume = (g[0], other g[1].g1), right = (g[1], other g[0].g1).
-// Dloc = number of slices of this launch, (sel, step) = which ones (PcSel).  p4 != NULL: 8-bit char mode, p4[0] / p4[1] = byte
-// planes {c0,c1,c2,grad} of the left / right image.
-// ... plane form: scratch = 2 x pc_plan(..., PC_PLANES | PC_BOTH).scratch_bytes()
-void launch_cvf_select2(hipStream_t s, March m, const Guidance *g, int W, int H, int Dloc, int d_begin, void *scratch,
-                        unsigned long long *ts, const uint8_t *const *p4, int sel, int step)
+// pc_plan of the two-volume select launches.  A single context plans the rows of its stripe together with the frames other contexts
+// have in flight (March::inflight); a batch plans its pairs without that hint, a batch of one too (psm_compute_batch rejects
+// stripes: its rows are the whole image).
+PcPlan pc_plan_select(March m, int W, int H, int Dloc, int form, int npairs, bool batch)
 {
-    const PcPlan pl = pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_PLANES | PC_BOTH, 1, m.inflight);
-    PcArgs a = {p4 ? (const float *)p4[0] : nullptr, p4 ? (float *)const_cast<uint8_t *>(p4[1]) : nullptr, W, H, Dloc, m.y0(H), m.y1(H),
-                d_begin, {}, PcSel{sel, step, pl.nxcd, 0, Dloc, 0, m.dstep}, ts, nullptr};
+    return pc_plan(W, m.rows(H), Dloc, m.seg_rows, form | PC_BOTH, npairs, batch ? 1 : m.inflight);
+}
+
+// The arguments of a two-volume select launch (form PC_PLANES / PC_KEYS) for the pairs P, costs built on the fly: left volume =
+// (g[0], other g[1].g1), right = (g[1], other g[0].g1).  A single pair passes its planes here - 8-bit mode: the byte planes
+// {c0,c1,c2,grad} of the left / right image as vin / vout; the minima: chunk planes in its scratch, or its keys -, the batched forms
+// read every pointer of a pair from the table.
+static PcArgs pc_args2(March m, const PcPlan &pl, int form, const PcPairs &P, bool u8, int W, int H, int Dloc, int d_begin, PcSel sel,
+                       unsigned long long *ts)
+{
+    PcArgs a = {nullptr, nullptr, W, H, Dloc, m.y0(H), m.y1(H), d_begin, {}, sel, ts, P.tab};
+    if (P.tab) return a;
+    const PcPair &p = P.one;
+    if (u8) { a.vin = (const float *)p.p4[0]; a.vout = (float *)p.p4[1]; }
     for (int v = 0; v < 2; ++v) {
-        const PcSide k = pc_planes(pl, scratch, v);
-        a.side[v] = PcSide{g[v].g1, g[v].g2, g[v].g3, g[v].g4, g[v ^ 1].g1, k.kcost, k.kdisp};
+        const PcSide k = form == PC_PLANES ? pc_planes(pl, p.scratch, v) : PcSide{};
+        a.side[v] = PcSide{p.g[v].g1, p.g[v].g2, p.g[v].g3, p.g[v].g4, p.g[v ^ 1].g1, k.kcost, k.kdisp};
+        if (form == PC_KEYS) a.side[v].kcost = (float *)(p.keys + v * (size_t)W * H);
     }
-    pc_launch(s, pl, dim3(pc_blocks(pl, pl.nchunks), 2), a, {PC_PLANES, 3, p4 != nullptr, pc_var(m, p4 != nullptr), false, pl.narrow, false});
+    return a;
 }
 
-void launch_chunk_min2sides(hipStream_t s, March m, int W, int H, int Dloc, void *scratch, long long *keys, uint8_t *map)
+void launch_cvf_select2(hipStream_t s, March m, const PcPairs &P, bool u8, int W, int H, int Dloc, int d_begin, unsigned long long *ts,
+                        int sel, int step)
 {
-    pc_chunk_min(s, m, pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_PLANES | PC_BOTH, 1, m.inflight), W, H, 2, 1, scratch, keys, map);
+    const PcPlan pl = pc_plan_select(m, W, H, Dloc, PC_PLANES, P.n, P.tab != nullptr);
+    const unsigned long long rec_total = P.tab ? (unsigned long long)pl.rec_per_chunk * pl.nchunks : 0;   // (read by the batched form only)
+    const PcArgs a = pc_args2(m, pl, PC_PLANES, P, u8, W, H, Dloc, d_begin, PcSel{sel, step, pl.nxcd, 0, Dloc, rec_total, m.dstep}, ts);
+    pc_launch(s, pl, dim3(pc_blocks(pl, pl.nchunks), 2, P.n), a, {PC_PLANES, 3, u8, pc_var(m, u8), P.tab != nullptr, pl.narrow, false});
 }
 
-// ... key form (MODE 2): keys[2][H][W] receives the packed minima (init: start from key(+inf, 0); otherwise continue from what
-// `keys` holds - the second phase of the two-phase selection)
-void launch_cvf_select_keys2(hipStream_t s, March m, const Guidance *g, int W, int H, int Dloc, int d_begin, long long *keys,
-                             unsigned long long *ts, const uint8_t *const *p4, int init, int sel, int step)
+void launch_chunk_min2sides(hipStream_t s, March m, const PcPairs &P, int W, int H, int Dloc, bool to_maps)
 {
-    const PcPlan pl = pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_KEYS | PC_BOTH, 1, m.inflight);
-    const size_t HW = (size_t)W * H;
-    if (init) hipLaunchKernelGGL(k_fill_keys, dim3((unsigned)((2 * HW + 255) / 256)), dim3(256), 0, s, keys, 2 * HW);
-    PcArgs a = {p4 ? (const float *)p4[0] : nullptr, p4 ? (float *)const_cast<uint8_t *>(p4[1]) : nullptr, W, H, Dloc, m.y0(H), m.y1(H),
-                d_begin, {}, PcSel{sel, step, pl.nxcd, PSM_KNOB("PSM_PC_SPREAD", PC_KEY_SPREAD), Dloc, 0, m.dstep}, ts, nullptr};
-    for (int v = 0; v < 2; ++v)
-        a.side[v] = PcSide{g[v].g1, g[v].g2, g[v].g3, g[v].g4, g[v ^ 1].g1, (float *)(keys + v * HW), nullptr};
-    pc_launch(s, pl, dim3(pc_blocks(pl, Dloc), 2), a, {PC_KEYS, 3, p4 != nullptr, pc_var(m, p4 != nullptr), false, pl.narrow, false});
+    const PcPlan pl = pc_plan_select(m, W, H, Dloc, PC_PLANES, P.n, P.tab != nullptr);
+    if (P.tab) pc_chunk_min(s, m, pl, W, H, 2, P.n, nullptr, nullptr, nullptr, P.tab, to_maps);
+    else pc_chunk_min(s, m, pl, W, H, 2, 1, P.one.scratch, P.one.keys, to_maps ? P.one.maps : nullptr);
 }
 
-// ---- the same launches for `npairs` stereo pairs at once (psm_compute_batch): blockIdx.z = pair, pointers from the table ----
-void launch_cvf_select2_batch(hipStream_t s, March m, const PcPair *tab, int npairs, int W, int H, int Dloc, int d_begin,
-                              unsigned long long *ts, bool u8, int sel, int step)
+void launch_cvf_select_keys2(hipStream_t s, March m, const PcPairs &P, bool u8, int W, int H, int Dloc, int d_begin,
+                             unsigned long long *ts, int sel, int step)
 {
-    const PcPlan pl = pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_PLANES | PC_BOTH, npairs);
-    const PcArgs a = {nullptr, nullptr, W, H, Dloc, m.y0(H), m.y1(H), d_begin, {},
-                      PcSel{sel, step, pl.nxcd, 0, Dloc, (unsigned long long)pl.rec_per_chunk * pl.nchunks, m.dstep}, ts, tab};
-    pc_launch(s, pl, dim3(pc_blocks(pl, pl.nchunks), 2, npairs), a, {PC_PLANES, 3, u8, 0, true, pl.narrow, false});
-}
-
-void launch_chunk_min2sides_batch(hipStream_t s, March m, const PcPair *tab, int npairs, int W, int H, int Dloc, bool to_maps)
-{
-    pc_chunk_min(s, m, pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_PLANES | PC_BOTH, npairs), W, H, 2, npairs, nullptr, nullptr, nullptr,
-                 tab, to_maps);
-}
-
-void launch_cvf_select_keys2_batch(hipStream_t s, March m, const PcPair *tab, int npairs, int W, int H, int Dloc, int d_begin,
-                                   unsigned long long *ts, bool u8, int sel, int step)
-{
-    const PcPlan pl = pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_KEYS | PC_BOTH, npairs);
-    const PcArgs a = {nullptr, nullptr, W, H, Dloc, m.y0(H), m.y1(H), d_begin, {}, PcSel{sel, step, pl.nxcd, PC_KEY_SPREAD, Dloc, 0, m.dstep},
-                      ts, tab};
-    pc_launch(s, pl, dim3(pc_blocks(pl, Dloc), 2, npairs), a, {PC_KEYS, 3, u8, 0, true, pl.narrow, false});
+    const PcPlan pl = pc_plan_select(m, W, H, Dloc, PC_KEYS, P.n, P.tab != nullptr);
+    const PcArgs a = pc_args2(m, pl, PC_KEYS, P, u8, W, H, Dloc, d_begin,
+                              PcSel{sel, step, pl.nxcd, PSM_KNOB("PSM_PC_SPREAD", PC_KEY_SPREAD), Dloc, 0, m.dstep}, ts);
+    pc_launch(s, pl, dim3(pc_blocks(pl, Dloc), 2, P.n), a, {PC_KEYS, 3, u8, pc_var(m, u8), P.tab != nullptr, pl.narrow, false});
 }
 
 }  // namespace psm
