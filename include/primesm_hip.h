@@ -241,6 +241,44 @@ int psm_upload_pair_async(psm_ctx *ctx, const void *l, const void *r, int channe
 int psm_download_maps_async(psm_ctx *ctx);
 int psm_download_maps_wait(psm_ctx *ctx, uint8_t *lmap, uint8_t *rmap, size_t stride);
 
+/* ---- video mode (the DE_VIDEO branch of StereoMatch::compute, src/StereoMatch.cpp:138-153): the camera frame is rectified and
+ * cropped on the device.  The arithmetic is that of cv::remap(src, dst, map1, map2, INTER_LINEAR) with CV_16SC2 / CV_16UC1 maps,
+ * the default BORDER_CONSTANT with value 0, 8-bit 3-channel images, followed by dst(cropBox) - stated exactly:
+ * for an output pixel (x, y) of a side, (mx, my) = map_xy[crop_y + y][crop_x + x], f = map_frac[crop_y + y][crop_x + x],
+ * fx = f & 31, fy = f >> 5: w00 = (32-fx)(32-fy)*32, w01 = fx(32-fy)*32, w10 = (32-fx)fy*32, w11 = fx*fy*32 (their sum is 2^15),
+ * out = (w00*S(my, mx) + w01*S(my, mx+1) + w10*S(my+1, mx) + w11*S(my+1, mx+1) + 2^14) >> 15 per channel, where a tap outside the
+ * src_w x src_h eye image reads 0, each tap on its own.
+ *
+ * psm_rectify_build_maps: host only, needs no device and no context (ctx-less errors: psm_last_error(NULL)) -
+ * initUndistortRectifyMap(M, D, R, P, Size(map_w, map_h), CV_16SC2, map1, map2) (src/StereoMatch.cpp:464-466) restated in double,
+ * every pixel from its own (u, v): iR = inv(P[:, :3] * R) by cofactors over the determinant, [X Y Z] = iR * [u v 1], x = X/Z,
+ * y = Y/Z, the rational radial + tangential + thin-prism model (dist: k1 k2 p1 p2 [k3 [k4 k5 k6 [s1 s2 s3 s4 [tx ty]]]], n_dist 0,
+ * 4, 5, 8, 12 or 14; tx, ty != 0 refused), u' = fx * xd + cx, iu = rint(32 u') (ties to even), map_xy = saturate_int16(iu >> 5),
+ * map_frac = (iv & 31) * 32 + (iu & 31); a non-finite coordinate gives map_xy = (-32768, -32768), map_frac = 0 (every tap outside).
+ * map_xy: [map_h][map_w][2], map_frac: [map_h][map_w]. */
+int psm_rectify_build_maps(const double M[9], const double *dist, int n_dist, const double R[9], const double P[12],
+                           int map_w, int map_h, int16_t *map_xy, uint16_t *map_frac);
+/* The maps of one side (dense, as above; every map_frac < 1024) for the following rectified uploads.  The eye images they index are
+ * src_w x src_h (2 <= src_w, 1 <= src_h, both <= 32767; the same for both sides); the context's W x H window of the maps starts
+ * at (crop_x, crop_y) - lFrame_rec(cropBox).  The window is copied to the device once; the host arrays are free on return. */
+int psm_rectify_set_maps(psm_ctx *ctx, int side, const int16_t *map_xy, const uint16_t *map_frac, int map_w, int map_h,
+                         int src_w, int src_h, int crop_x, int crop_y);
+/* Forget the maps of both sides and free everything the rectified uploads allocated. */
+int psm_rectify_clear(psm_ctx *ctx);
+/* As psm_upload_pair / psm_upload_pair_async with depth PSM_IMG_U8, but l / r are the UNRECTIFIED eye images: src_h rows of src_w
+ * B,G,R pixels, pitch stride_bytes (0: packed).  The two halves of a side-by-side frame are l = frame, r = frame + 3 * src_w with
+ * the frame's pitch (the cv::Mat ROIs of src/StereoMatch.cpp:138-139: no copy).  The pair the context adopts is the rectified,
+ * cropped one - contexts of either dtype, shards, row stripes and psm_compute_batch see an ordinary 8-bit pair.  One kernel launch
+ * per frame, timed under PSM_K_PREP, outside the four stage timers (remap sits before cvc_time in the reference).  The asynchronous
+ * form keeps the contract of psm_upload_pair_async: the caller's buffers are free on return, two staging slots, one upload in
+ * flight, adopted by the next psm_cost_construct. */
+int psm_upload_pair_rectified(psm_ctx *ctx, const void *l, const void *r, int channels, size_t stride_bytes);
+int psm_upload_pair_rectified_async(psm_ctx *ctx, const void *l, const void *r, int channels, size_t stride_bytes);
+/* The context's CURRENT 8-bit pair as it is staged on the device (what the reference shows as leftInputImg / rightInputImg):
+ * H rows of W B,G,R pixels each, pitch stride_bytes (0: packed).  A pair staged by an asynchronous upload becomes current in
+ * psm_cost_construct.  Float pairs are refused. */
+int psm_download_images(psm_ctx *ctx, uint8_t *l, uint8_t *r, size_t stride_bytes);
+
 /* "next" row: PP lrCheck on the device (src/PP.cpp:17-50) on the maps of the last
  * psm_disp_select/psm_disp_merge.  lvalid/rvalid: H x W bytes (0/1), pitch `stride`; either
  * may be NULL (results stay on the device). */

@@ -83,6 +83,12 @@ SYMBOLS = [
     ("psm_reset_kernel_times", _i, [_vp]),
     ("psm_filter_launch_times", _i, [_vp, _pd, _pi, _i, _pi]),
     ("psm_get_info", _i, [_vp, _pi, _pi, _pi, _pi, _pi, _pi, _pi]),
+    ("psm_rectify_build_maps", _i, [_pd, _pd, _i, _pd, _pd, _i, _i, _vp, _vp]),
+    ("psm_rectify_set_maps", _i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i]),
+    ("psm_rectify_clear", _i, [_vp]),
+    ("psm_upload_pair_rectified", _i, [_vp, _vp, _vp, _i, _sz]),
+    ("psm_upload_pair_rectified_async", _i, [_vp, _vp, _vp, _i, _sz]),
+    ("psm_download_images", _i, [_vp, _vp, _vp, _sz]),
 ]
 
 _lib = None

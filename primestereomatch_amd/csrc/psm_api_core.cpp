@@ -112,6 +112,7 @@ void free_all(psm_ctx *c)
         (void)hipFree(c->vol[s]);
         (void)hipFree(c->p4[s]);
     }
+    rectify_free(c, true);
     (void)hipFree(c->fvol);
     (void)hipFree(c->spare);
     (void)hipFree(c->ab);
@@ -166,6 +167,7 @@ void free_all(psm_ctx *c)
 int flush_timers(psm_ctx *c)
 {
     PSM_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->copy_stream) PSM_HIP(c, hipStreamSynchronize(c->copy_stream));    // (k_rectify of a staged pair is timed there)
     for (auto &t : c->timers) {
         for (auto &p : t.pending) {
             float ms = 0.f;
@@ -427,6 +429,7 @@ int psm_release_scratch(psm_ctx *c)
     (void)hipFree(c->gf_scratch); c->gf_scratch = nullptr; c->gf_scratch_bytes = 0;
     (void)hipFree(c->gather); c->gather = nullptr; c->gather_ranks = 0;
     (void)hipFree(c->fvol); c->fvol = nullptr;
+    rectify_free(c, false);
     for (int k = 0; k < 2; ++k)
         if (c->xfer_pin[k]) { (void)hipHostFree(c->xfer_pin[k]); c->xfer_pin[k] = nullptr; c->xfer_pin_bytes[k] = 0; }
     (void)hipGetLastError();

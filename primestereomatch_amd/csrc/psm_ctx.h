@@ -6,6 +6,7 @@
 //   psm_api_pp.cpp      post-processing: L-R check, invalid fill, weighted median
 //   psm_api_batch.cpp   several Middlebury-size pairs per launch (psm_compute_batch)
 //   psm_api_jwmf.cpp    JointWMF: the joint weighted median of the reference's live post-filter (psm_joint_wmf)
+//   psm_api_rectify.cpp video mode: remap + crop of the camera frame into the staged image slot (psm_upload_pair_rectified)
 // Takes the place of the reference's oclUtil + CVC_cl / CVF_cl / DispSel_cl host wrappers
 // (src/oclUtil.cpp, src/CVC_cl.cpp, src/CVF_cl.cpp, src/DispSel_cl.cpp).
 #pragma once
@@ -105,6 +106,15 @@ struct psm_ctx {
     float jw_tab_sigma[2] = {0.f, 0.f};
     unsigned long long *jw_pin = nullptr;  // page-locked staging of the two integer tables (on first use)
     hipEvent_t ev_jw[2] = {nullptr, nullptr};   // ... the copy out of a side's staging has executed
+    // psm_upload_pair_rectified (psm_api_rectify.cpp): the W x H crop window of a side's CV_16SC2 maps, uploaded once by
+    // psm_rectify_set_maps; the unrectified source frames (both eyes, packed rows) per staging slot and their page-locked staging,
+    // allocated on first use
+    uint32_t *rect_xy[2] = {nullptr, nullptr};   // [H][W] {int16 x, int16 y}
+    uint16_t *rect_fr[2] = {nullptr, nullptr};   // [H][W] fy * 32 + fx
+    int rect_src_w[2] = {0, 0}, rect_src_h[2] = {0, 0};
+    uint8_t *rect_src[2] = {nullptr, nullptr};
+    uint8_t *rect_pin = nullptr;
+    size_t rect_src_bytes = 0;                   // bytes of one eye in a slot (16-byte multiple) the buffers were allocated for
     uint8_t *p4[2] = {nullptr, nullptr};  // PSM_U8 only: {c0,c1,c2,grad} words
     // After psm_cost_filter_fgf the filtered volume of a side may stay virtual (fgf_virtual[side] = subsample rate):
     // it is fully described by the smoothed low-resolution models fgf_mab[side]; the WTA consumes them directly
@@ -191,24 +201,26 @@ inline int maps_writable(psm_ctx *c)
     return 0;
 }
 
-// RAII bracket of one kernel launch with hipEvents on the launch stream (PSM_OPT_PROFILE 1)
+// RAII bracket of one kernel launch with hipEvents on the launch stream (PSM_OPT_PROFILE 1); s: that stream if it is not the
+// context's (the rectification of a pair staged on the copy stream)
 struct Prof {
     psm_ctx *c;
     int k;
+    hipStream_t s;
     hipEvent_t a = nullptr, b = nullptr;
-    Prof(psm_ctx *c_, int k_) : c(c_), k(k_)
+    Prof(psm_ctx *c_, int k_, hipStream_t s_ = nullptr) : c(c_), k(k_), s(s_ ? s_ : c_->stream)
     {
         if (c->opt_profile == 1) {
             a = get_event(c);
             b = a ? get_event(c) : nullptr;
             if (a && !b) { c->event_pool.push_back(a); a = nullptr; }
-            if (a) (void)hipEventRecord(a, c->stream);
+            if (a) (void)hipEventRecord(a, s);
         }
     }
     ~Prof()
     {
         if (a) {
-            (void)hipEventRecord(b, c->stream);
+            (void)hipEventRecord(b, s);
             c->timers[k].pending.emplace_back(a, b);
         }
     }
@@ -252,6 +264,8 @@ constexpr int PSM_IMG_EXP = 10, PSM_VOL_EXP = 60;
 constexpr size_t PSM_COPY_KERNEL_MAX = (size_t)2 << 20;     // asynchronous PCIe legs up to this size go through k_copy16 instead of the copy engines
 unsigned long long *next_pc_stamp(psm_ctx *c);   // slot of the next k_cvf_pc launch (NULL unless PSM_OPT_PROFILE 2)
 
+// psm_api_rectify.cpp
+void rectify_free(psm_ctx *c, bool maps);        // the source slots and their staging; maps: the device maps too
 // psm_api_select.cpp
 int copy_maps_out(psm_ctx *c, const uint8_t *dev, uint8_t *lmap, uint8_t *rmap, size_t stride);
 

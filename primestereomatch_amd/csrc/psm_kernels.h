@@ -202,4 +202,19 @@ void launch_jw_lok(hipStream_t s, const unsigned *samples, int n, const int *lab
 void launch_jw_plane(hipStream_t s, const JwPair &pr, int depth, size_t HW);
 void launch_jw_median(hipStream_t s, const JwPair &pr, int W, int H, int r);
 
+// psm_rectify.hip: remap (CV_16SC2 maps, INTER_LINEAR, constant border 0) + crop of both eyes (psm_api_rectify.cpp)
+struct RectSide {
+    const uint8_t *src;                // unrectified eye image, interleaved B,G,R rows of `pitch` bytes (8 readable bytes behind the last)
+    const uint32_t *xy;                // crop window of the map: {int16 x, int16 y} per output pixel, [npix]
+    const uint16_t *fr;                // ... fy * 32 + fx
+    uint32_t *out;                     // staged image slot: npix interleaved B,G,R pixels, written as ndw whole dwords
+};
+struct RectArgs {
+    RectSide s[2];
+    int npix, ndw;                     // W * H of the context; (3 * npix + 3) / 4
+    int src_w, src_h;
+    unsigned pitch;
+};
+void launch_rectify(hipStream_t s, const RectArgs &a);
+
 }  // namespace psm

@@ -291,6 +291,62 @@ class DispEst:
         self._ck(self._lib.psm_upload_pair_async(self._h, _ptr(l), _ptr(r), 3, l.strides[0], depth), "setInputImages_async")
         return 0
 
+    # ---- video mode: the camera frame is rectified and cropped on the device (src/StereoMatch.cpp:138-153) ----
+    def setRectification(self, rect) -> int:
+        """rect: rectify.Rectification whose crop has this object's size.  The maps go to the device once."""
+        x, y, w, h = rect.crop
+        if (w, h) != (self.wid, self.hei):
+            raise ValueError("setRectification: the crop's size differs from the one DispEst was built for")
+        for side in (capi.PSM_LEFT, capi.PSM_RIGHT):
+            xy = np.ascontiguousarray(rect.map_xy[side], dtype=np.int16)
+            fr = np.ascontiguousarray(rect.map_frac[side], dtype=np.uint16)
+            if xy.ndim != 3 or xy.shape[2] != 2 or fr.shape != xy.shape[:2]:
+                raise ValueError("setRectification: maps must be [h, w, 2] int16 and [h, w] uint16")
+            self._ck(self._lib.psm_rectify_set_maps(self._h, side, _ptr(xy), _ptr(fr), xy.shape[1], xy.shape[0], int(rect.src_w),
+                                                    int(rect.src_h), int(x), int(y)), "setRectification")
+        self._rect_src = (int(rect.src_h), int(rect.src_w))
+        return 0
+
+    def clearRectification(self):
+        self._ck(self._lib.psm_rectify_clear(self._h), "clearRectification")
+        self._rect_src = None
+
+    def _eyes(self, vFrame, who):
+        """The two halves of a side-by-side frame as pointers into it (the cv::Mat ROIs of src/StereoMatch.cpp:138-139: no copy)."""
+        src = getattr(self, "_rect_src", None)
+        if src is None:
+            raise capi.PsmError(f"{who}: no rectification set (setRectification)")
+        v = np.asarray(vFrame)
+        if v.dtype != np.uint8:
+            raise ValueError(f"{who}: the frame must be uint8 (float frames are not remapped)")
+        if v.ndim != 3 or v.shape != (src[0], 2 * src[1], 3):
+            raise ValueError(f"{who}: the frame must be {src[0]} x {2 * src[1]} x 3 (two eyes side by side)")
+        if v.strides[2] != 1 or v.strides[1] != 3:
+            v = np.ascontiguousarray(v)
+        base = v.ctypes.data
+        return v, C.c_void_p(base), C.c_void_p(base + 3 * src[1]), v.strides[0]
+
+    def setInputFrame(self, vFrame) -> int:
+        """vFrame: the camera's side-by-side frame, src_h x 2 src_w x 3 uint8, unrectified; the pair the object holds afterwards is
+        remap(eye, maps, INTER_LINEAR)(cropBox) of both eyes."""
+        v, l, r, stride = self._eyes(vFrame, "setInputFrame")
+        self._ck(self._lib.psm_upload_pair_rectified(self._h, l, r, 3, stride), "setInputFrame")
+        return 0
+
+    def setInputFrame_async(self, vFrame) -> int:
+        """setInputFrame for the NEXT frame (as setInputImages_async): copy and remap run on the copy stream while the current
+        frame computes; the next CostConst_GPU adopts the pair."""
+        v, l, r, stride = self._eyes(vFrame, "setInputFrame_async")
+        self._ck(self._lib.psm_upload_pair_rectified_async(self._h, l, r, 3, stride), "setInputFrame_async")
+        return 0
+
+    def download_images(self):
+        """The current 8-bit pair as staged on the device -> (l, r) H x W x 3 uint8 (the reference's leftInputImg / rightInputImg)."""
+        l = np.empty((self.hei, self.wid, 3), np.uint8)
+        r = np.empty((self.hei, self.wid, 3), np.uint8)
+        self._ck(self._lib.psm_download_images(self._h, _ptr(l), _ptr(r), l.strides[0]), "download_images")
+        return l, r
+
     def download_maps_async(self):
         self._ck(self._lib.psm_download_maps_async(self._h), "download_maps_async")
 
@@ -412,14 +468,26 @@ class FrameRing:
         self._busy = [False] * frames
         self._lrc = lr_check
 
+    def setRectification(self, rect):
+        """Every context of the ring rectifies the frames push_frame gives it (DispEst.setRectification)."""
+        for c in self.ctx:
+            c.setRectification(rect)
+
     def push(self, l, r):
+        return self._push(lambda c: c.setInputImages(l, r))
+
+    def push_frame(self, vFrame):
+        """push for a side-by-side camera frame: rectified and cropped on the device (DispEst.setInputFrame)."""
+        return self._push(lambda c: c.setInputFrame(vFrame))
+
+    def _push(self, set_input):
         i = self._n % len(self.ctx)
         self._n += 1
         c = self.ctx[i]
         out = None
         if self._busy[i]:
             out = tuple(m.copy() for m in c.download_maps_wait())
-        c.setInputImages(l, r)
+        set_input(c)
         c.CostConst_GPU()
         c.CostFilter_GPU()
         c.DispSelect_device()

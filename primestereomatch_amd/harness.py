@@ -49,30 +49,56 @@ def compute(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, error_t
         rFrame = rFrame.astype(np.float32) * np.float32(1 / 255.0)
     with DispEst(lFrame, rFrame, maxDis, threads, True, dtype=dtype) as SMDE:
         SMDE.setInputImages(lFrame, rFrame)
-        SMDE.setThreads(threads)
-        SMDE.setSubsampleRate(subsample_rate or 4)
-        SMDE.CostConst_GPU()
-        if subsample_rate:
-            SMDE.CostFilter_FGF_GPU()
-        else:
-            SMDE.CostFilter_GPU()
-        SMDE.DispSelect_GPU()
-        if post_process or process_dm:
-            SMDE.LRCheck_GPU()
-            out["lValid"], out["rValid"] = SMDE.lValid.copy(), SMDE.rValid.copy()
-        if process_dm:
-            out["lDisMap_raw"], out["rDisMap_raw"] = SMDE.lDisMap.copy(), SMDE.rDisMap.copy()
-            SMDE.FillInv_GPU()
-            SMDE.WgtMedian_GPU()
-        if joint_wmf:
-            out.setdefault("lDisMap_raw", SMDE.lDisMap.copy())
-            out.setdefault("rDisMap_raw", SMDE.rDisMap.copy())
-            SMDE.JointWMF_GPU()
-        out["cvc_ms"] = SMDE.stage_time_us(capi.PSM_STAGE_CVC) / 1000
-        out["cvf_ms"] = SMDE.stage_time_us(capi.PSM_STAGE_CVF) / 1000
-        out["dispsel_ms"] = SMDE.stage_time_us(capi.PSM_STAGE_DISPSEL) / 1000
-        out["pp_ms"] = SMDE.stage_time_us(capi.PSM_STAGE_PP) / 1000
-        out["lDisMap"], out["rDisMap"] = SMDE.lDisMap.copy(), SMDE.rDisMap.copy()
+        _run_stages(SMDE, out, threads, subsample_rate, post_process, process_dm, joint_wmf)
+    return _finish(out, maxDis, gt, mask, scale_factor, error_threshold, verbose)
+
+
+def compute_video(vFrame, rectification, maxDis=64, gt=None, mask=None, scale_factor=4, error_threshold=4, threads=8,
+                  dtype="f32", post_process=True, verbose=False, subsample_rate=0, process_dm=False, joint_wmf=False):
+    """One frame of the DE_VIDEO branch of StereoMatch::compute (src/StereoMatch.cpp:138-153) followed by the stages of compute():
+    vFrame is the camera's side-by-side frame (src_h x 2 src_w x 3 uint8), split into its eyes without a copy, rectified with
+    `rectification` (rectify.Rectification) and cropped on the device.  The rectified pair comes back as lFrame / rFrame.
+    The device keeps the pair 8-bit (float contexts scale it by 1/255 themselves), where the reference converts to float on
+    the host (src/StereoMatch.cpp:193-198) - the same values."""
+    out = {}
+    w, h = rectification.crop[2], rectification.crop[3]
+    blank = np.zeros((h, w, 3), np.uint8)
+    with DispEst(blank, blank, maxDis, threads, True, dtype=dtype) as SMDE:
+        SMDE.setRectification(rectification)
+        SMDE.setInputFrame(vFrame)
+        out["lFrame"], out["rFrame"] = SMDE.download_images()
+        _run_stages(SMDE, out, threads, subsample_rate, post_process, process_dm, joint_wmf)
+    return _finish(out, maxDis, gt, mask, scale_factor, error_threshold, verbose)
+
+
+def _run_stages(SMDE, out, threads, subsample_rate, post_process, process_dm, joint_wmf):
+    SMDE.setThreads(threads)
+    SMDE.setSubsampleRate(subsample_rate or 4)
+    SMDE.CostConst_GPU()
+    if subsample_rate:
+        SMDE.CostFilter_FGF_GPU()
+    else:
+        SMDE.CostFilter_GPU()
+    SMDE.DispSelect_GPU()
+    if post_process or process_dm:
+        SMDE.LRCheck_GPU()
+        out["lValid"], out["rValid"] = SMDE.lValid.copy(), SMDE.rValid.copy()
+    if process_dm:
+        out["lDisMap_raw"], out["rDisMap_raw"] = SMDE.lDisMap.copy(), SMDE.rDisMap.copy()
+        SMDE.FillInv_GPU()
+        SMDE.WgtMedian_GPU()
+    if joint_wmf:
+        out.setdefault("lDisMap_raw", SMDE.lDisMap.copy())
+        out.setdefault("rDisMap_raw", SMDE.rDisMap.copy())
+        SMDE.JointWMF_GPU()
+    out["cvc_ms"] = SMDE.stage_time_us(capi.PSM_STAGE_CVC) / 1000
+    out["cvf_ms"] = SMDE.stage_time_us(capi.PSM_STAGE_CVF) / 1000
+    out["dispsel_ms"] = SMDE.stage_time_us(capi.PSM_STAGE_DISPSEL) / 1000
+    out["pp_ms"] = SMDE.stage_time_us(capi.PSM_STAGE_PP) / 1000
+    out["lDisMap"], out["rDisMap"] = SMDE.lDisMap.copy(), SMDE.rDisMap.copy()
+
+
+def _finish(out, maxDis, gt, mask, scale_factor, error_threshold, verbose):
     out["lDispMap"] = np.clip(out["lDisMap"].astype(np.int32) * scale_factor, 0, 255).astype(np.uint8)
     if gt is not None:
         bp, avg, bad, emap = error_vs_ground_truth(out["lDisMap"], gt, mask, maxDis, scale_factor, error_threshold)

@@ -77,6 +77,45 @@ int DispEst::setInputImages(Mat leftImg, Mat rightImg)
     return rc;
 }
 
+int DispEst::setRectification(const Rectification &rect)
+{
+    if (ctx.empty()) return 1;
+    int rc = 0;
+    for (psm_ctx *c : ctx)
+        for (int s = 0; s < 2 && !rc; ++s) {
+            rc = hipUtil::api().rectify_set_maps(c, s, rect.map_xy[s], rect.map_frac[s], rect.map_w, rect.map_h, rect.src_w, rect.src_h,
+                                                 rect.crop_x, rect.crop_y);
+            if (rc) fprintf(stderr, "DispEst: %s\n", hipUtil::api().last_error(c));
+        }
+    rect_src_w = rc ? 0 : rect.src_w;
+    rect_src_h = rc ? 0 : rect.src_h;
+    return rc;
+}
+
+bool DispEst::frameOk(const Mat &v) const
+{
+    if (rect_src_w > 0 && v.data && v.depth == PSM_8U && v.channels == 3 && v.rows == rect_src_h && v.cols == 2 * rect_src_w) return true;
+    fprintf(stderr, "DispEst: setInputFrame needs setRectification first and a %d x %d CV_8UC3 side-by-side frame\n", 2 * rect_src_w, rect_src_h);
+    return false;
+}
+
+int DispEst::setInputFrame(const Mat &vFrame)
+{
+    if (ctx.empty() || !frameOk(vFrame)) return 1;
+    int rc = 0;       // the two eyes: ROIs of the frame (same pitch, the right one 3 * src_w bytes further)
+    for (psm_ctx *c : ctx) rc |= hipUtil::api().upload_pair_rectified(c, vFrame.data, vFrame.data + 3 * (size_t)rect_src_w, 3, vFrame.step);
+    return rc;
+}
+
+int DispEst::downloadImages(Mat *l, Mat *r)
+{
+    if (ctx.empty() || !l || !r) return 1;
+    for (Mat *m : {l, r})
+        if (!m->data || m->rows != hei || m->cols != wid || m->channels != 3 || m->depth != PSM_8U) *m = Mat::zeros(hei, wid, 3, PSM_8U);
+    if (l->step != r->step) return 1;
+    return hipUtil::api().download_images(ctx[0], l->data, r->data, l->step);
+}
+
 int DispEst::setThreads(unsigned int newThreads)
 {
     if (newThreads > MAX_CPU_THREADS) return -1;  // src/DispEst.cpp:172-179
@@ -192,6 +231,20 @@ int DispEst::computeFrame(const Mat *nextL, const Mat *nextR, bool have_prev)
     return rc;
 }
 
+int DispEst::computeVideoFrame(const Mat *next, bool have_prev)
+{
+    if (ctx.size() != 1 || (next && !frameOk(*next))) return 1;
+    const HipApi &api = hipUtil::api();
+    psm_ctx *c = ctx[0];
+    int rc = api.cost_construct(c);
+    if (next) rc |= api.upload_pair_rectified_async(c, next->data, next->data + 3 * (size_t)rect_src_w, 3, next->step);
+    rc |= api.cost_filter(c);
+    rc |= api.disp_select(c, nullptr, nullptr, 0);
+    if (have_prev) rc |= api.download_maps_wait(c, lDisMap.data, rDisMap.data, lDisMap.step);
+    rc |= api.download_maps_async(c);
+    return rc;
+}
+
 int DispEst::finishFrames()
 {
     if (ctx.size() != 1) return 1;
@@ -262,7 +315,18 @@ int FrameRing::deliver(int i, Mat *outL, Mat *outR)
     return 1;
 }
 
-int FrameRing::push(const Mat &l, const Mat &r, Mat *outL, Mat *outR)
+int FrameRing::setRectification(const Rectification &rect)
+{
+    if (ring.empty()) return -1;
+    int rc = 0;
+    for (DispEst *o : ring) rc |= o->setRectification(rect);
+    return rc;
+}
+
+int FrameRing::push(const Mat &l, const Mat &r, Mat *outL, Mat *outR) { return push_any(&l, &r, nullptr, outL, outR); }
+int FrameRing::push_frame(const Mat &vFrame, Mat *outL, Mat *outR) { return push_any(nullptr, nullptr, &vFrame, outL, outR); }
+
+int FrameRing::push_any(const Mat *l, const Mat *r, const Mat *vFrame, Mat *outL, Mat *outR)
 {
     if (ring.empty()) return -1;
     const HipApi &api = hipUtil::api();
@@ -275,7 +339,10 @@ int FrameRing::push(const Mat &l, const Mat &r, Mat *outL, Mat *outR)
     }
     DispEst *de = ring[i];
     psm_ctx *c = de->ctx[0];
-    if (api.upload_pair_async(c, l.data, r.data, l.channels, l.step, l.depth == PSM_32F ? PSM_IMG_F32 : PSM_IMG_U8)) return -1;
+    if (vFrame) {
+        if (!de->frameOk(*vFrame)) return -1;
+        if (api.upload_pair_rectified_async(c, vFrame->data, vFrame->data + 3 * (size_t)de->rect_src_w, 3, vFrame->step)) return -1;
+    } else if (api.upload_pair_async(c, l->data, r->data, l->channels, l->step, l->depth == PSM_32F ? PSM_IMG_F32 : PSM_IMG_U8)) return -1;
     if (api.cost_construct(c) || api.cost_filter(c) || api.disp_select(c, nullptr, nullptr, 0) || api.download_maps_async(c)) return -1;
     busy[i] = 1;
     ++pushed;

@@ -45,6 +45,16 @@ struct Mat {
 
 #define MAX_CPU_THREADS 8  // include/ComFunc.h:52
 
+// Video mode (src/StereoMatch.cpp:138-153,464-466): the CV_16SC2 maps of both cameras (mapl / mapr: dense map_h x map_w, [..][2]
+// int16 and uint16; from initUndistortRectifyMap or psm_rectify_build_maps), the size of the eye images they index and the
+// origin of cropBox in the rectified image (its size is the DispEst object's).  The maps are copied to the device by
+// setRectification; the host arrays need not outlive the call.
+struct Rectification {
+    const int16_t *map_xy[2] = {nullptr, nullptr};
+    const uint16_t *map_frac[2] = {nullptr, nullptr};
+    int map_w = 0, map_h = 0, src_w = 0, src_h = 0, crop_x = 0, crop_y = 0;
+};
+
 class DispEst {
 public:
     // l, r: H x W x 3 images, cv::imread channel order, CV_8U or CV_32F (already scaled by
@@ -61,6 +71,13 @@ public:
     Mat rValid;
 
     int setInputImages(Mat l, Mat r);
+    // Video mode: after setRectification, setInputFrame takes the camera's side-by-side frame (src_h x 2 src_w, CV_8UC3), splits
+    // it by pointer arithmetic - lFrame = vFrame(Rect(0, 0, cols/2, rows)), rFrame = vFrame(Rect(cols/2, ...)), no copy - and the
+    // device remaps (INTER_LINEAR) and crops both eyes; the pair the object then holds is the rectified, cropped one
+    // (downloadImages: H x W CV_8UC3 Mats).  Replaces src/StereoMatch.cpp:138-153.
+    int setRectification(const Rectification &rect);
+    int setInputFrame(const Mat &vFrame);
+    int downloadImages(Mat *l, Mat *r);
     int setThreads(unsigned int newThreads);
     void setSubsampleRate(unsigned int newRate) { subsample_rate = newRate; }
 
@@ -89,6 +106,9 @@ public:
     // Mats are free again on return), CostFilter, DispSelect on the device, hands over the PREVIOUS frame's maps in
     // lDisMap / rDisMap (have_prev: there was one) and starts this frame's download.  finishFrames() returns the last maps.
     int computeFrame(const Mat *nextL, const Mat *nextR, bool have_prev);
+    // ... the same loop in video mode: `next` is the next side-by-side camera frame (setInputFrame's argument), rectified on the
+    // copy stream behind its H2D copy
+    int computeVideoFrame(const Mat *next, bool have_prev);
     int finishFrames();
 
     // Several pairs of one geometry per launch (the reference loops over pairs / datasets, src/main.cpp:64-73,
@@ -111,6 +131,8 @@ private:
     unsigned int subsample_rate = 4;
     std::vector<psm_ctx *> ctx;  // one per device (row stripes of ceil(H / ndev) rows)
     std::vector<int> y0s, y1s;   // their stripes
+    int rect_src_w = 0, rect_src_h = 0;   // setRectification: the eye images' size
+    bool frameOk(const Mat &vFrame) const;
     bool whole_on_first = false; // the last filter ran on ctx[0] over the whole image (Fast Guided Filter path: no stripes)
 };
 
@@ -128,12 +150,16 @@ public:
     // Queues the pair (l, r).  Once the ring is full this first hands over the maps of the frame pushed frames() calls earlier:
     // outL / outR (H x W, 8-bit, may be NULL to drop them) are filled and 1 is returned; 0 = no maps yet; < 0 = a device call failed.
     int push(const Mat &l, const Mat &r, Mat *outL, Mat *outR);
+    // Video mode: setRectification on every object of the ring, then push_frame instead of push with the side-by-side frame.
+    int setRectification(const Rectification &rect);
+    int push_frame(const Mat &vFrame, Mat *outL, Mat *outR);
     // The frames still in flight, oldest first, one per call: 1 = maps delivered, 0 = none left, < 0 = error.
     int flush(Mat *outL, Mat *outR);
     int setOption(int option, int value);      // on every object of the ring
 
 private:
     int deliver(int i, Mat *outL, Mat *outR);
+    int push_any(const Mat *l, const Mat *r, const Mat *vFrame, Mat *outL, Mat *outR);
     std::vector<DispEst *> ring;
     std::vector<char> busy;
     long long pushed = 0, flushed = 0;

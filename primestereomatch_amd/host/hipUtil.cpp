@@ -50,7 +50,10 @@ bool hipUtil::load(const char *path)
               bind(g_api.wgt_median, "psm_wgt_median") && bind(g_api.joint_wmf, "psm_joint_wmf") &&
               bind(g_api.joint_wmf_set_clusters, "psm_joint_wmf_set_clusters") &&
               bind(g_api.stage_time_us, "psm_stage_time_us") && bind(g_api.compute_batch, "psm_compute_batch") &&
-              bind(g_api.download_maps, "psm_download_maps");
+              bind(g_api.download_maps, "psm_download_maps") && bind(g_api.rectify_build_maps, "psm_rectify_build_maps") &&
+              bind(g_api.rectify_set_maps, "psm_rectify_set_maps") && bind(g_api.rectify_clear, "psm_rectify_clear") &&
+              bind(g_api.upload_pair_rectified, "psm_upload_pair_rectified") &&
+              bind(g_api.upload_pair_rectified_async, "psm_upload_pair_rectified_async") && bind(g_api.download_images, "psm_download_images");
     if (!ok) {
         fprintf(stderr, "%s\n", g_error.c_str());
         dlclose(g_handle);

@@ -38,6 +38,13 @@ struct HipApi {
     int (*stage_time_us)(psm_ctx *, int, double *) = nullptr;
     int (*compute_batch)(psm_ctx *const *, int) = nullptr;
     int (*download_maps)(psm_ctx *, uint8_t *, uint8_t *, size_t) = nullptr;
+    // video mode: rectification on the device
+    int (*rectify_build_maps)(const double *, const double *, int, const double *, const double *, int, int, int16_t *, uint16_t *) = nullptr;
+    int (*rectify_set_maps)(psm_ctx *, int, const int16_t *, const uint16_t *, int, int, int, int, int, int) = nullptr;
+    int (*rectify_clear)(psm_ctx *) = nullptr;
+    int (*upload_pair_rectified)(psm_ctx *, const void *, const void *, int, size_t) = nullptr;
+    int (*upload_pair_rectified_async)(psm_ctx *, const void *, const void *, int, size_t) = nullptr;
+    int (*download_images)(psm_ctx *, uint8_t *, uint8_t *, size_t) = nullptr;
 };
 
 class hipUtil {
