@@ -159,8 +159,7 @@ extern "C" int psm_compute_batch(psm_ctx *const *ctxs, int n)
     PSM_HIP(c0, hipEventRecord(c0->ev_batch, s));
     for (int i = 0; i < n; ++i) {
         psm_ctx *c = ctxs[i];
-        c->have_g1 = true; c->g1_y0 = 0; c->g1_y1 = H;
-        c->have_guid[0] = c->have_guid[1] = true; c->guid_y0 = 0; c->guid_y1 = H;
+        c->g1_rows = c->guid_rows = whole_image(c);
         c->fgf_virtual[0] = c->fgf_virtual[1] = 0;
         c->raw_rows[0] = c->raw_rows[1] = psm_ctx::RAW_NONE;
         c->gf_virtual[0] = c->gf_virtual[1] = true;

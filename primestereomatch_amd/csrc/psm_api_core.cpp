@@ -76,10 +76,7 @@ void adopt_new_pair(psm_ctx *c, int depth)
 {
     c->raw_depth = depth;
     c->have_images = true;
-    c->have_g1 = false;
-    c->g1_y0 = c->g1_y1 = 0;
-    c->have_guid[0] = c->have_guid[1] = false;
-    c->guid_y0 = c->guid_y1 = 0;
+    c->g1_rows = c->guid_rows = Rows{};
     c->have_cost = false;
     c->have_maps = false;
     c->have_valid = false;
@@ -377,10 +374,7 @@ int psm_set_option(psm_ctx *c, int option, int value)
         if (c->dtype == PSM_U8) value &= ~(PSM_FLAG_FMA_SOLVE | PSM_FLAG_F32_TOL);
         if ((value & PSM_FLAG_F32_TOL) && (value & PSM_FLAG_FMA_SOLVE))
             return fail(c, "psm_set_option: PSM_FLAG_F32_TOL and PSM_FLAG_FMA_SOLVE exclude each other (one arithmetic variant at a time)");
-        if ((value ^ c->march.flags) & PSM_FLAG_FMA_SOLVE) {       // the minors and 1/DET in the guidance planes are those of the other reading
-            c->have_guid[0] = c->have_guid[1] = false;
-            c->guid_y0 = c->guid_y1 = 0;
-        }
+        if ((value ^ c->march.flags) & PSM_FLAG_FMA_SOLVE) c->guid_rows = Rows{};   // the minors and 1/DET in the guidance planes are those of the other reading
         c->march.flags = value; return 0;
     case PSM_OPT_GRAPH:
 #ifdef PSM_EXPERIMENTS
@@ -567,7 +561,7 @@ int psm_upload_volume(psm_ctx *c, int side, int d0, int d1, const void *host)
     PSM_NOT_STRIDED(c, "psm_upload_volume");
     if (bind(c)) return 1;
     // a partial upload must not leave virtual slices behind: whatever of this side exists only as a recipe (lazy costs - also
-    // after a striped psm_cost_construct, which leaves have_g1 false -, packed minima, FGF models) becomes real data first
+    // after a striped psm_cost_construct, which prepares the stripe's image rows only -, packed minima, FGF models) becomes real data first
     if (c->have_cost && (c->raw_rows[side] != psm_ctx::RAW_ALL || c->gf_virtual[side] || c->fgf_virtual[side]) && materialize(c, side)) return 1;
     c->gf_virtual[side] = false;
     c->maps_early = nullptr;
@@ -606,7 +600,7 @@ int psm_download_guidance(psm_ctx *c, int side, float *host)
     const size_t HW = (size_t)c->W * c->H;
     std::vector<float4> b1(HW), b2(HW), b3(HW);
     std::vector<float2> b4(HW);
-    if (c->have_images && !c->have_g1 && run_prep(c)) return 1;     // (image preparation is lazy: psm_cost_construct may have left it to the filter)
+    if (c->have_images && ensure_planes(c, whole_image(c), Rows{})) return 1;     // g1 alone (image preparation is lazy: psm_cost_construct may have left it to the filter)
     PSM_HIP(c, hipStreamSynchronize(c->stream));
     PSM_HIP(c, hipMemcpy(b1.data(), c->g[side].g1, HW * sizeof(float4), hipMemcpyDeviceToHost));
     PSM_HIP(c, hipMemcpy(b2.data(), c->g[side].g2, HW * sizeof(float4), hipMemcpyDeviceToHost));

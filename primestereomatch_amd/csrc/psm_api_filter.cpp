@@ -12,36 +12,6 @@ using namespace psm;
 
 namespace psm {
 
-// planarise + scale + gray + x-gradient of both staged images -> g1 (and the 8-bit planes)
-// (rows [ya, yb) only - the kernels are row-independent - when a row stripe is all the following filter will read: have_g1
-// then stays false and g1_y0/1 say what is there; every other consumer finds have_g1 false and prepares the whole image)
-int run_prep(psm_ctx *c, int ya, int yb)
-{
-    const bool whole = yb <= ya || (ya <= 0 && yb >= c->H);
-    if (whole) { ya = 0; yb = c->H; }
-    ya = ya < 0 ? 0 : ya;
-    yb = yb > c->H ? c->H : yb;
-    const size_t row = (size_t)c->W * 3 * (c->raw_depth == PSM_IMG_F32 ? 4 : 1);
-    const size_t o = (size_t)ya * c->W;
-    {   // both images in one launch
-        Prof p(c, PSM_K_PREP);
-        launch_prep(c->stream, (const char *)c->raw[0] + ya * row, row, c->raw_depth == PSM_IMG_F32, c->W, yb - ya, c->g[0].g1 + o,
-                    (const char *)c->raw[1] + ya * row, c->g[1].g1 + o);
-    }
-    for (int s = 0; s < 2 && c->dtype == PSM_U8; ++s) {
-        Prof p(c, PSM_K_PREP);
-        launch_prep_u8(c->stream, (const uint8_t *)c->raw[s] + ya * row, row, c->W, yb - ya, c->p4[s] + 4 * o, c->g[s].g1 + o);
-    }
-    if (check_launch(c, "prep")) return 1;
-    if (c->ev_free) PSM_HIP(c, hipEventRecord(c->ev_free, c->stream));   // the staged images have been read: their slot may be refilled
-    c->have_guid[0] = c->have_guid[1] = false;
-    c->guid_y0 = c->guid_y1 = 0;
-    c->have_g1 = whole;
-    c->g1_y0 = ya;
-    c->g1_y1 = yb;
-    return 0;
-}
-
 // The float volumes are allocated on first use: the default path (lazy costs + select-mode filter) never touches them.
 int ensure_vol(psm_ctx *c, int side)
 {
@@ -127,6 +97,62 @@ PcPair pc_pair(const psm_ctx *c)
     return p;
 }
 
+// the launch just made has read the staged images: their slot may be refilled
+static int staged_images_read(psm_ctx *c, const char *what)
+{
+    if (check_launch(c, what)) return 1;
+    if (c->ev_free) PSM_HIP(c, hipEventRecord(c->ev_free, c->stream));
+    return 0;
+}
+
+// Bring g1 (and the 8-bit planes) of the rows g1_need and the guidance g2..g4 of the rows guid_need up to date with the current
+// pair - an empty need asks for nothing; guid_need lies inside g1_need.  The one place that compares need with record, picks
+// the launches and updates the record: float contexts that miss both take ONE launch, k_guide_march forming the image planes
+// itself from the staged images (planarise + scale + gray + x-gradient, then the guidance of the same rows - a stripe: 4 rows
+// more either side than it needs); everything else takes k_prep (+ k_prep_u8) and / or the guidance kernel on the g1 planes.
+// The kernels are row-independent, so a row stripe prepares its own rows only and every later need they do not cover
+// prepares again.
+int ensure_planes(psm_ctx *c, Rows g1_need, Rows guid_need)
+{
+    const bool need_g1 = !c->g1_rows.covers(g1_need), need_guid = !c->guid_rows.covers(guid_need);
+    if (!need_g1 && !need_guid) return 0;
+    const bool f32_img = c->raw_depth == PSM_IMG_F32;
+    const size_t row = (size_t)c->W * 3 * (f32_img ? 4 : 1);
+    if (need_g1 && need_guid && c->dtype == PSM_F32) {
+        {
+            Prof p(c, PSM_K_GUIDE);
+            launch_guidance(c->stream, PcPairs{nullptr, 1, pc_pair(c)}, c->W, c->H, g1_need.y0, g1_need.y1, fma_solve(c), f32_img ? 2 : 1, row);
+        }
+        if (staged_images_read(c, "prep + guidance")) return 1;
+        guid_need = g1_need;
+    } else {
+        if (need_g1) {
+            const int ya = g1_need.y0, rows = g1_need.y1 - ya;
+            const size_t o = (size_t)ya * c->W;
+            {   // both images in one launch
+                Prof p(c, PSM_K_PREP);
+                launch_prep(c->stream, (const char *)c->raw[0] + ya * row, row, f32_img, c->W, rows, c->g[0].g1 + o,
+                            (const char *)c->raw[1] + ya * row, c->g[1].g1 + o);
+            }
+            for (int s = 0; s < 2 && c->dtype == PSM_U8; ++s) {
+                Prof p(c, PSM_K_PREP);
+                launch_prep_u8(c->stream, (const uint8_t *)c->raw[s] + ya * row, row, c->W, rows, c->p4[s] + 4 * o, c->g[s].g1 + o);
+            }
+            if (staged_images_read(c, "prep")) return 1;
+        }
+        if (need_guid) {
+            {
+                Prof p(c, PSM_K_GUIDE);
+                launch_guidance(c->stream, PcPairs{nullptr, 1, pc_pair(c)}, c->W, c->H, guid_need.y0, guid_need.y1, fma_solve(c));
+            }
+            if (check_launch(c, "guidance")) return 1;
+        }
+    }
+    if (need_g1) c->g1_rows = g1_need;
+    if (need_guid) c->guid_rows = guid_need;
+    return 0;
+}
+
 // npairs / batch: see pc_plan_select.  The geometry, options and slices are the context's (a batch: those of its first context).
 SelPlan select_plan(const psm_ctx *c, int npairs, bool batch)
 {
@@ -203,37 +229,47 @@ void launch_cvc_rows(psm_ctx *c, int side, int ybeg, int yend)
     launch_cvc(c->stream, c->g[side].g1, c->g[1 - side].g1, (float *)c->vol[side], c->W, c->H, c->d0, c->Dloc, side, ybeg, yend);
 }
 
-// g1 (and the 8-bit planes) and the guidance of the whole image: a row-stripe filter leaves only its own rows behind
-int ensure_whole_planes(psm_ctx *c)
-{
-    if (!c->have_g1 && run_prep(c)) return 1;
-    if (!(c->have_guid[0] && c->have_guid[1])) {
-        {
-            Prof p(c, PSM_K_GUIDE);
-            launch_guidance(c->stream, PcPairs{nullptr, 1, pc_pair(c)}, c->W, c->H, 0, 0, fma_solve(c));
-        }
-        c->have_guid[0] = c->have_guid[1] = true;
-        c->guid_y0 = 0;
-        c->guid_y1 = c->H;
-        return check_launch(c, "guidance");
-    }
-    return 0;
-}
-
-// 8-bit mode, storing form: float copy of the 8-bit cost volume -> fused filter (store mode, out of place) -> re-quantise
-// (what psm_download_volume etc. see; the default path never runs it).  Needs the guidance of `side`.
-int filter_u8_stored(psm_ctx *c, int side)
+// 8-bit mode: the float copy of the 8-bit volume of `side` that the storing kernels work on (re-quantised afterwards)
+int u8_to_fvol(psm_ctx *c, int side)
 {
     const size_t V = (size_t)c->W * c->H * c->Dloc;
     if (!c->fvol) PSM_HIP(c, hipMalloc((void **)&c->fvol, V * sizeof(float)));
-    if (ensure_spare(c)) return 1;
     launch_u8_to_f32(c->stream, (const uint8_t *)c->vol[side], c->fvol, V);
+    return 0;
+}
+
+void launch_cvc_u8_side(psm_ctx *c, int side)
+{
+    Prof p(c, PSM_K_CVC);
+    launch_cvc_u8(c->stream, c->p4[side], c->p4[1 - side], (uint8_t *)c->vol[side], c->W, c->H, c->d0, c->Dloc, side);
+    c->raw_rows[side] = psm_ctx::RAW_ALL;
+}
+
+// The storing form of the fused filter: `side` filtered into a real volume, from whatever its costs currently are (what
+// psm_download_volume etc. see; the default path never runs it).  Needs the planes of the whole image.
+//   float, costs virtual:  built on the fly inside the kernel; nothing is read from vol[side], so the result goes straight into it
+//   float, costs in vol[side]:  out of place into `spare`, which then becomes vol[side] (ping-pong)
+//   8-bit:  costs built if they are virtual; float copy -> kernel (out of place) -> re-quantised into vol[side]
+int filter_stored(psm_ctx *c, int side)
+{
+    const bool u8 = c->dtype == PSM_U8;
+    if (ensure_vol(c, side)) return 1;
+    if (u8 && c->raw_rows[side] != psm_ctx::RAW_ALL) launch_cvc_u8_side(c, side);
+    const bool lazy = c->raw_rows[side] != psm_ctx::RAW_ALL;
+    if (u8 && u8_to_fvol(c, side)) return 1;
+    if (!lazy && ensure_spare(c)) return 1;
+    const float *in = lazy ? nullptr : u8 ? c->fvol : (const float *)c->vol[side];
+    float *out = lazy ? (float *)c->vol[side] : c->spare;
     {
         Prof p(c, PSM_K_CVF_F);
-        launch_cvf_fused(c->stream, c->march, c->fvol, c->spare, c->g[side], c->W, c->H, c->Dloc, 0, c->H, c->g[1 - side].g1, c->d0, 0, next_pc_stamp(c));
+        launch_cvf_fused(c->stream, c->march, in, out, c->g[side], c->W, c->H, c->Dloc, 0, c->H, c->g[1 - side].g1, c->d0, lazy ? 1 + side : 0,
+                         next_pc_stamp(c));
     }
-    launch_f32_to_u8(c->stream, c->spare, (uint8_t *)c->vol[side], V);   // q8 = sat_u8(rintf(q * 255))
-    return check_launch(c, "cvf (8-bit, storing form)");
+    if (u8) launch_f32_to_u8(c->stream, out, (uint8_t *)c->vol[side], (size_t)c->W * c->H * c->Dloc);   // q8 = sat_u8(rintf(q * 255))
+    else if (!lazy) std::swap(*(float **)&c->vol[side], c->spare);
+    c->gf_virtual[side] = false;
+    c->raw_rows[side] = psm_ctx::RAW_ALL;                 // vol[side] now holds real (filtered) data
+    return check_launch(c, "cvf (fused, storing form)");
 }
 
 }  // namespace
@@ -245,40 +281,19 @@ int materialize(psm_ctx *c, int side)
 {
     PSM_NOT_STRIDED(c, "materialising a cost volume");
     if (fgf_flush(c, side)) return 1;
-    if ((c->gf_virtual[side] || c->raw_rows[side] != psm_ctx::RAW_ALL) && ensure_whole_planes(c)) return 1;
+    if (!c->gf_virtual[side] && c->raw_rows[side] == psm_ctx::RAW_ALL) return 0;
+    // (a row-stripe filter leaves only its own rows of the planes behind)
+    if (ensure_planes(c, whole_image(c), whole_image(c))) return 1;
+    // the guided-filter result exists only as WTA keys: run the same fused kernel again, this time storing q
+    if (c->gf_virtual[side]) return filter_stored(c, side);
+    // the costs exist only as a recipe: build them
     if (c->dtype == PSM_U8) {
-        if (c->raw_rows[side] != psm_ctx::RAW_ALL) {      // the 8-bit costs exist only as a recipe: build them
-            Prof p(c, PSM_K_CVC);
-            launch_cvc_u8(c->stream, c->p4[side], c->p4[1 - side], (uint8_t *)c->vol[side], c->W, c->H, c->d0, c->Dloc, side);
-            c->raw_rows[side] = psm_ctx::RAW_ALL;
-        }
-        if (c->gf_virtual[side]) {                         // ... and the filtered volume only as WTA keys: filter in the storing form
-            if (filter_u8_stored(c, side)) return 1;
-            c->gf_virtual[side] = false;
-        }
-        return check_launch(c, "8-bit volume (materialize)");
-    }
-    if (c->gf_virtual[side]) {
-        // the guided-filter result exists only as WTA keys: run the same fused kernel again, this time storing q
+        launch_cvc_u8_side(c, side);
+    } else {
         if (ensure_vol(c, side)) return 1;
-        Prof p(c, PSM_K_CVF_F);
-        if (c->raw_rows[side] == psm_ctx::RAW_ALL) {          // materialised costs in vol[side]: out of place
-            if (ensure_spare(c)) return 1;
-            launch_cvf_fused(c->stream, c->march, (const float *)c->vol[side], c->spare, c->g[side], c->W, c->H, c->Dloc, 0, c->H,
-                             c->g[1 - side].g1, c->d0, 0, next_pc_stamp(c));
-            std::swap(*(float **)&c->vol[side], c->spare);
-        } else {
-            launch_cvf_fused(c->stream, c->march, nullptr, (float *)c->vol[side], c->g[side], c->W, c->H, c->Dloc, 0, c->H,
-                             c->g[1 - side].g1, c->d0, 1 + side, next_pc_stamp(c));
-        }
-        c->gf_virtual[side] = false;
-        c->raw_rows[side] = psm_ctx::RAW_ALL;                 // vol[side] now holds real (filtered) data
-        return check_launch(c, "cvf (materialize)");
+        launch_cvc_rows(c, side, 0, c->H);
+        c->raw_rows[side] = psm_ctx::RAW_ALL;
     }
-    if (c->raw_rows[side] == psm_ctx::RAW_ALL) return 0;
-    if (ensure_vol(c, side)) return 1;
-    launch_cvc_rows(c, side, 0, c->H);
-    c->raw_rows[side] = psm_ctx::RAW_ALL;
     return check_launch(c, "cvc (materialize)");
 }
 
@@ -286,95 +301,64 @@ int materialize(psm_ctx *c, int side)
 
 namespace {
 
-// One volume: the path for cost volumes that exist in memory (psm_upload_volume, PSM_FLAG_MATERIALISE_COSTS), for the storing
-// form, the direct variant and for stage A alone.
-int filter_side(psm_ctx *c, int side, bool stage_b)
+// One volume, select form: the fused kernel in "select" mode - the WTA over the local slices runs inside the filter, the filtered
+// volume stays virtual (8-bit mode: with costs built on the fly only)
+int filter_side_select(psm_ctx *c, int side)
 {
-    PSM_NOT_STRIDED(c, "filtering one side / a materialised volume / the storing form");
-    c->maps_early = nullptr;
-    const size_t V = (size_t)c->W * c->H * c->Dloc;
     const int W = c->W, H = c->H;
-    if (!c->have_g1 && run_prep(c)) return 1;  // volume came from psm_upload_volume
-    if (fgf_flush(c, side)) return 1;
-    if (c->gf_virtual[side] && materialize(c, side)) return 1;   // filtering an already filtered (virtual) volume: make it real first
-    if (!c->have_guid[side]) {
-        // the guidance of BOTH images in one launch the first time either side asks (the other side's call then finds it)
-        Prof p(c, PSM_K_GUIDE);
-        launch_guidance(c->stream, PcPairs{nullptr, 1, pc_pair(c)}, W, H, 0, 0, fma_solve(c));
-        c->have_guid[0] = c->have_guid[1] = true;
+    const bool lazy = c->raw_rows[side] != psm_ctx::RAW_ALL, sel8 = c->dtype == PSM_U8;
+    const PcPlan pl = pc_plan(W, c->march.rows(H), c->Dloc, c->march.seg_rows, PC_PLANES);
+    if (ensure_gf_scratch(c, pl.scratch_bytes())) return 1;
+    {
+        Prof p(c, PSM_K_CVF_F);
+        launch_cvf_select(c->stream, c->march, lazy ? nullptr : (const float *)c->vol[side], c->g[side], W, H, c->Dloc, c->g[1 - side].g1,
+                          c->d0, lazy ? 1 + side : 0, c->gf_scratch, next_pc_stamp(c), sel8 ? c->p4[side] : nullptr, sel8 ? c->p4[1 - side] : nullptr);
     }
-    // Default: the fused kernel in "select" mode - the WTA over the local slices runs inside the filter, the filtered
-    // volume stays virtual (PSM_FLAG_STORE_FILTERED forces the storing form; the direct variant is its own filter)
-    const bool sel8 = c->dtype == PSM_U8 && c->raw_rows[side] != psm_ctx::RAW_ALL;   // 8-bit mode: select form only with costs on the fly
-    if (stage_b && (c->dtype == PSM_F32 || sel8) && c->opt_variant == 0 && !(c->march.flags & PSM_FLAG_STORE_FILTERED) && scaled_forms_ok(c)) {
-        const bool lazy = c->raw_rows[side] != psm_ctx::RAW_ALL;
-        const PcPlan pl = pc_plan(W, c->march.rows(H), c->Dloc, c->march.seg_rows, PC_PLANES);
-        if (ensure_gf_scratch(c, pl.scratch_bytes())) return 1;
-        const size_t HW = (size_t)W * H;
-        {
-            Prof p(c, PSM_K_CVF_F);
-            launch_cvf_select(c->stream, c->march, lazy ? nullptr : (const float *)c->vol[side], c->g[side], W, H, c->Dloc, c->g[1 - side].g1,
-                              c->d0, lazy ? 1 + side : 0, c->gf_scratch, next_pc_stamp(c), sel8 ? c->p4[side] : nullptr, sel8 ? c->p4[1 - side] : nullptr);
-        }
-        {
-            Prof p(c, PSM_K_WTA);
-            launch_chunk_min(c->stream, c->march, W, H, c->Dloc, c->gf_scratch, c->keys_cur + side * HW, nullptr);
-        }
-        c->gf_virtual[side] = true;
-        return check_launch(c, "cvf (fused, select mode)");
+    {
+        Prof p(c, PSM_K_WTA);
+        launch_chunk_min(c->stream, c->march, W, H, c->Dloc, c->gf_scratch, c->keys_cur + side * (size_t)W * H, nullptr);
     }
-    if (c->dtype == PSM_F32 && ensure_vol(c, side)) return 1;
-    if (c->dtype == PSM_U8 && stage_b && c->raw_rows[side] != psm_ctx::RAW_ALL && materialize(c, side)) return 1;   // storing forms read the 8-bit volume
-    float *fv = (float *)c->vol[side];
-    if (c->dtype == PSM_U8) {
-        // (8-bit mode: a float copy of the volume goes through the same kernels and is re-quantised afterwards)
-        if (!c->fvol) PSM_HIP(c, hipMalloc((void **)&c->fvol, V * sizeof(float)));
-        fv = c->fvol;
-        launch_u8_to_f32(c->stream, (const uint8_t *)c->vol[side], fv, V);
-    }
-    const bool fused = stage_b && c->opt_variant == 0;
-    if (!fused && fma_solve(c))
+    c->gf_virtual[side] = true;
+    return check_launch(c, "cvf (fused, select mode)");
+}
+
+// One volume, stage A alone (psm_filter_stage_a) or the direct variant: they read a real cost volume (8-bit mode: its float copy,
+// re-quantised after stage B)
+int filter_side_direct(psm_ctx *c, int side, bool stage_b)
+{
+    if (fma_solve(c))
         return fail(c, "PSM_FLAG_FMA_SOLVE: stage A alone (psm_filter_stage_a) and the direct kernel variant exist in the canonical arithmetic only");
-    if (!fused && materialize(c, side)) return 1;   // stage A alone / the direct variant read a real cost volume
-    if (fused) {
-        if (c->raw_rows[side] != psm_ctx::RAW_ALL) {
-            // producer/consumer kernel on a virtual cost volume: nothing is read from vol[side], so the
-            // filtered volume is written straight into it
-            {
-                Prof p(c, PSM_K_CVF_F);
-                launch_cvf_fused(c->stream, c->march, nullptr, fv, c->g[side], W, H, c->Dloc, 0, H, c->g[1 - side].g1, c->d0, 1 + side, next_pc_stamp(c));
-            }
-            c->raw_rows[side] = psm_ctx::RAW_ALL;   // vol[side] now holds real (filtered) data
-            return check_launch(c, "cvf (fused, lazy costs)");
-        }
-        // producer/consumer kernel reading a materialised cost volume: out of place, all rows in one launch
-        if (ensure_spare(c)) return 1;
-        float *out = c->spare;
-        {
-            Prof p(c, PSM_K_CVF_F);
-            launch_cvf_fused(c->stream, c->march, fv, out, c->g[side], W, H, c->Dloc, 0, H, c->g[1 - side].g1, c->d0, 0, next_pc_stamp(c));
-        }
-        if (c->dtype == PSM_U8) {
-            launch_f32_to_u8(c->stream, out, (uint8_t *)c->vol[side], V);   // q8 = sat_u8(rintf(q * 255))
-        } else {
-            c->spare = fv;          // ping-pong: the filtered volume becomes vol[side]
-            c->vol[side] = out;
-        }
-        return check_launch(c, "cvf (fused)");
-    }
-    if (ensure_ab(c)) return 1;
+    if (materialize(c, side) || ensure_ab(c)) return 1;
+    const bool u8 = c->dtype == PSM_U8;
+    if (u8 && u8_to_fvol(c, side)) return 1;
+    float *fv = u8 ? c->fvol : (float *)c->vol[side];
     {
         Prof p(c, PSM_K_CVF_A);
-        launch_cvf_a(c->stream, c->opt_variant, c->march, fv, c->ab, c->g[side], W, H, c->Dloc, 0, H);
+        launch_cvf_a(c->stream, c->opt_variant, c->march, fv, c->ab, c->g[side], c->W, c->H, c->Dloc, 0, c->H);
     }
     if (stage_b) {          // (direct variant only: the marching stage B lives in the fused kernel)
         {
             Prof p(c, PSM_K_CVF_B);
-            launch_cvf_b_direct(c->stream, c->ab, fv, c->g[side], W, H, c->Dloc);
+            launch_cvf_b_direct(c->stream, c->ab, fv, c->g[side], c->W, c->H, c->Dloc);
         }
-        if (c->dtype == PSM_U8) launch_f32_to_u8(c->stream, fv, (uint8_t *)c->vol[side], V);
+        if (u8) launch_f32_to_u8(c->stream, fv, (uint8_t *)c->vol[side], (size_t)c->W * c->H * c->Dloc);
     }
     return check_launch(c, "cvf");
+}
+
+// One volume: the path for cost volumes that exist in memory (psm_upload_volume, PSM_FLAG_MATERIALISE_COSTS), for the storing
+// form (PSM_FLAG_STORE_FILTERED, or images / volumes outside the select forms' domain), the direct variant and for stage A alone.
+int filter_side(psm_ctx *c, int side, bool stage_b)
+{
+    PSM_NOT_STRIDED(c, "filtering one side / a materialised volume / the storing form");
+    c->maps_early = nullptr;
+    // (the guidance of BOTH images the first time either side asks: the other side's call then finds it)
+    if (ensure_planes(c, whole_image(c), whole_image(c))) return 1;
+    if (fgf_flush(c, side)) return 1;
+    if (c->gf_virtual[side] && materialize(c, side)) return 1;   // filtering an already filtered (virtual) volume: make it real first
+    if (!stage_b || c->opt_variant != 0) return filter_side_direct(c, side, stage_b);
+    const bool select_form = (c->dtype == PSM_F32 || c->raw_rows[side] != psm_ctx::RAW_ALL) && !(c->march.flags & PSM_FLAG_STORE_FILTERED) && scaled_forms_ok(c);
+    return select_form ? filter_side_select(c, side) : filter_stored(c, side);
 }
 
 // Both volumes per launch: guidance of both images, select-mode fused filter of both volumes, chunk reduction of both - five
@@ -389,42 +373,9 @@ bool can_filter_both(const psm_ctx *c)
 int filter_both(psm_ctx *c)
 {
     c->maps_early = nullptr;
-    const bool striped = c->march.yend > c->march.ybeg;
-    {   // g1 rows this launch reads: everything, or the stripe's rows - 8 .. + 8; guidance rows: the model rows y0 - 4 .. y1 + 2
-        const int ya = striped ? (c->march.ybeg - 8 > 0 ? c->march.ybeg - 8 : 0) : 0;
-        const int yb = striped ? (c->march.yend + 8 < c->H ? c->march.yend + 8 : c->H) : c->H;
-        const int gy0 = striped ? (c->march.ybeg - 4 > 0 ? c->march.ybeg - 4 : 0) : 0;
-        const int gy1 = striped ? (c->march.yend + 4 < c->H ? c->march.yend + 4 : c->H) : c->H;
-        const bool need_g1 = !c->have_g1 && !(c->g1_y1 > c->g1_y0 && c->g1_y0 <= ya && c->g1_y1 >= yb);
-        const bool need_guid = !(c->have_guid[0] && c->have_guid[1]) && !(c->guid_y1 > c->guid_y0 && c->guid_y0 <= gy0 && c->guid_y1 >= gy1);
-        if (need_g1 && need_guid && c->dtype == PSM_F32) {
-            // image planes AND guidance in one launch, straight from the staged images (psm_cost_construct left the preparation to
-            // us): rows [ya, yb) of g1 are written, and the guidance of the same rows (a stripe: 4 rows more either side than it needs)
-            const size_t row = (size_t)c->W * 3 * (c->raw_depth == PSM_IMG_F32 ? 4 : 1);
-            {
-                Prof p(c, PSM_K_GUIDE);
-                launch_guidance(c->stream, PcPairs{nullptr, 1, pc_pair(c)}, c->W, c->H, ya, yb, fma_solve(c), c->raw_depth == PSM_IMG_F32 ? 2 : 1, row);
-            }
-            if (check_launch(c, "prep + guidance")) return 1;
-            if (c->ev_free) PSM_HIP(c, hipEventRecord(c->ev_free, c->stream));   // the staged images have been read: their slot may be refilled
-            const bool whole = ya == 0 && yb == c->H;
-            c->have_g1 = whole;
-            c->g1_y0 = c->guid_y0 = ya;
-            c->g1_y1 = c->guid_y1 = yb;
-            c->have_guid[0] = c->have_guid[1] = whole;
-        } else {
-            if (need_g1 && (striped ? run_prep(c, c->march.ybeg - 8, c->march.yend + 8) : run_prep(c))) return 1;
-            // a row stripe needs the guidance of its model rows only (have_guid stays false: the planes are not whole, any other
-            // consumer recomputes them; guid_y0/1 remember what is there for the next frame's check)
-            if (!(c->have_guid[0] && c->have_guid[1]) && !(c->guid_y1 > c->guid_y0 && c->guid_y0 <= gy0 && c->guid_y1 >= gy1)) {
-                Prof p(c, PSM_K_GUIDE);
-                launch_guidance(c->stream, PcPairs{nullptr, 1, pc_pair(c)}, c->W, c->H, gy0, gy1, fma_solve(c));
-                c->guid_y0 = gy0;
-                c->guid_y1 = gy1;
-                if (gy0 == 0 && gy1 == c->H) c->have_guid[0] = c->have_guid[1] = true;
-            }
-        }
-    }
+    // (after a lazy psm_cost_construct in a float context: image planes AND guidance in one launch, straight from the staged images)
+    const PlaneRows need = stripe_planes(c);
+    if (ensure_planes(c, need.g1, need.guid)) return 1;
     const SelPlan sp = select_plan(c, 1, false);
     if (ensure_gf_scratch(c, sp.scratch_bytes)) return 1;
     if (enqueue_select(c, PcPairs{nullptr, 1, pc_pair(c)}, sp)) return 1;
@@ -449,22 +400,17 @@ int psm_cost_construct(psm_ctx *c)
     // (8-bit mode: lazy only when the select-mode kernel will consume the costs - its storing form reads a float copy)
     const bool lazy = c->opt_variant == 0 && !(c->march.flags & PSM_FLAG_MATERIALISE_COSTS) &&
                       (c->dtype == PSM_F32 || !(c->march.flags & PSM_FLAG_STORE_FILTERED));
-    // CVC::preprocess belongs to this stage (src/DispEst.cpp:232-233).  A row stripe [y0, y1) with lazy costs reads the image
-    // planes of rows y0 - 8 .. y1 + 7 only (costs of the model rows y0 - 4 .. y1 + 2, +- 4 for their box sums, and the guidance)
     if (!lazy) PSM_NOT_STRIDED(c, "psm_cost_construct with materialised costs");
-    const bool striped = c->march.yend > c->march.ybeg;
-    if (lazy && c->dtype == PSM_F32 && c->march.inflight <= 1) {
-        // CVC::preprocess is lazy too (round 6): with the cost volume virtual, the first thing that needs the image planes is the
-        // guidance precompute of psm_cost_filter - and k_guide_march forms them itself from the staged images (one launch instead of
-        // k_prep + k_guide_march; launch_guidance with raw images).  Everything else that reads g1 finds have_g1 false and runs
-        // run_prep first, as after a striped frame.  (Not with frames in flight on other streams - PSM_OPT_FRAMES_IN_FLIGHT: the merged
-        // launch carries the conversions in all three waves of its workgroups and stretches beside another frame's VALU-bound fused
-        // kernel - 450 x 375 x 64, two frames in flight: 0.226 ms against 0.211 with k_prep + k_guide_march; alone it is 0.270 vs 0.279.)
-        c->have_g1 = false;
-        c->g1_y0 = c->g1_y1 = 0;
-        c->have_guid[0] = c->have_guid[1] = false;
-        c->guid_y0 = c->guid_y1 = 0;
-    } else if (striped && lazy ? run_prep(c, c->march.ybeg - 8, c->march.yend + 8) : run_prep(c)) return 1;
+    // Every call starts the planes afresh, also when the pair has not changed: a frame does all of its work.
+    c->g1_rows = c->guid_rows = Rows{};
+    // CVC::preprocess belongs to this stage (src/DispEst.cpp:232-233): the rows a stripe with lazy costs reads, else the whole image.
+    // In a float context it is lazy too (round 6): with the cost volume virtual, the first thing that needs the image planes is the
+    // guidance precompute of psm_cost_filter - and k_guide_march forms them itself from the staged images (one launch instead of
+    // k_prep + k_guide_march: ensure_planes).  (Not with frames in flight on other streams - PSM_OPT_FRAMES_IN_FLIGHT: the merged
+    // launch carries the conversions in all three waves of its workgroups and stretches beside another frame's VALU-bound fused
+    // kernel - 450 x 375 x 64, two frames in flight: 0.226 ms against 0.211 with k_prep + k_guide_march; alone it is 0.270 vs 0.279.)
+    const bool lazy_prep = lazy && c->dtype == PSM_F32 && c->march.inflight <= 1;
+    if (!lazy_prep && ensure_planes(c, lazy ? stripe_planes(c).g1 : whole_image(c), Rows{})) return 1;
     c->fgf_virtual[0] = c->fgf_virtual[1] = 0;   // a new cost volume replaces whatever was pending
     c->gf_virtual[0] = c->gf_virtual[1] = false;
     c->vol_domain_ok[0] = c->vol_domain_ok[1] = true;   // (uploaded volumes are gone; the costs now follow from the images)
@@ -473,9 +419,7 @@ int psm_cost_construct(psm_ctx *c)
         if (lazy) {
             c->raw_rows[s] = psm_ctx::RAW_NONE;
         } else if (c->dtype == PSM_U8) {
-            Prof p(c, PSM_K_CVC);
-            launch_cvc_u8(c->stream, c->p4[s], c->p4[1 - s], (uint8_t *)c->vol[s], c->W, c->H, c->d0, c->Dloc, s);
-            c->raw_rows[s] = psm_ctx::RAW_ALL;
+            launch_cvc_u8_side(c, s);
         } else {
             if (ensure_vol(c, s)) return 1;
             launch_cvc_rows(c, s, 0, c->H);
@@ -548,7 +492,7 @@ int psm_cost_filter_fgf(psm_ctx *c, int sub)
     if (bind(c)) return 1;
     c->maps_early = nullptr;
     const double t0 = now_us();
-    if (!c->have_g1 && run_prep(c)) return 1;
+    if (ensure_planes(c, whole_image(c), Rows{})) return 1;
     // small planes: ism, msm, v1 (float4), v2 (float2) per pixel; ab (scratch) and one mab per side (float4) per small voxel
     const size_t n = (size_t)ws * hs, need = n * (3 * sizeof(float4) + sizeof(float2)) + 3 * n * c->Dloc * sizeof(float4);
     if (fgf_flush(c, 0) || fgf_flush(c, 1)) return 1;   // filtering an already FGF-filtered volume: make it real first

@@ -79,7 +79,7 @@ int psm_wgt_median(psm_ctx *c, uint8_t *lmap, uint8_t *rmap, size_t stride)
     if (c->W < 9 || c->H < 9) return fail(c, "psm_wgt_median: image %dx%d smaller than the 19x19 window's wrap allows", c->W, c->H);
     if (bind(c) || maps_writable(c)) return 1;
     const double t0 = now_us();
-    if (!c->have_g1 && run_prep(c)) return 1;
+    if (ensure_planes(c, whole_image(c), Rows{})) return 1;
     const size_t HW = (size_t)c->W * c->H;
     // PSM_FLAG_WMF_DATAFLOW: dataflow form only; PSM_FLAG_WMF_TWO_SWEEPS: at most 2 sweeps (test hook for the fall-back)
     const bool dataflow_only = (c->march.flags & PSM_FLAG_WMF_DATAFLOW) != 0;

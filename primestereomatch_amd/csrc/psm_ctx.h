@@ -1,7 +1,8 @@
 // psm_ctx.h - the context behind the C ABI of libprimesm_hip.so (include/primesm_hip.h) and the helpers its
 // translation units share.  Internal to the library:
 //   psm_api_core.cpp    context life cycle, options, uploads / downloads, timers
-//   psm_api_filter.cpp  CostConst / CostFilter: what is built lazily, which form of the fused kernel runs, materialisation
+//   psm_api_filter.cpp  CostConst / CostFilter: which plane rows are current (ensure_planes), what is built lazily, which form
+//                       of the fused kernel runs, materialisation
 //   psm_api_select.cpp  DispSelect: maps, packed minima, row stripes and disparity shards
 //   psm_api_pp.cpp      post-processing: L-R check, invalid fill, weighted median
 //   psm_api_batch.cpp   several Middlebury-size pairs per launch (psm_compute_batch)
@@ -34,6 +35,13 @@ namespace psm {
 struct StreamSet {
     hipStream_t main = nullptr, up = nullptr, down = nullptr;
     int refs = 0;
+};
+
+// A range of image rows [y0, y1); empty (y1 <= y0): no row.
+struct Rows {
+    int y0 = 0, y1 = 0;
+    bool empty() const { return y1 <= y0; }
+    bool covers(Rows need) const { return need.empty() || (y0 <= need.y0 && y1 >= need.y1); }
 };
 }  // namespace psm
 
@@ -125,9 +133,10 @@ struct psm_ctx {
     // the packed per-pixel minima in keys[side].  vol[side] is then untouched (raw_rows[side] still describes the
     // UNFILTERED volume); any reader of the filtered volume re-runs the filter in "store" mode first (materialize()).
     bool gf_virtual[2] = {false, false};
-    bool have_guid[2] = {false, false};   // g2..g4 of a side are those of the current image pair
-    int guid_y0 = 0, guid_y1 = 0;         // ... or, while have_guid is false, only their rows [guid_y0, guid_y1) of both sides are (row stripes)
-    int g1_y0 = 0, g1_y1 = 0;             // likewise for g1 (and the 8-bit planes) while have_g1 is false
+    // The rows of the planes that are those of the current image pair (empty: none; [0, H): the whole image; a row stripe
+    // leaves its own rows behind).  Brought up to date by ensure_planes alone.
+    psm::Rows g1_rows;                    // g1 (and the 8-bit planes p4) of both images
+    psm::Rows guid_rows;                  // g2..g4 of both images
     void *gf_scratch = nullptr;         // chunk planes of the select-mode kernel (PcPlan::scratch_bytes)
     size_t gf_scratch_bytes = 0;
     unsigned long long *pc_ts = nullptr;  // PSM_OPT_PROFILE 2: {first start, last end} device time stamps per k_cvf_pc launch
@@ -148,7 +157,7 @@ struct psm_ctx {
     void *fgf = nullptr;                // psm_cost_filter_fgf scratch (small planes), fgf_bytes long
     size_t fgf_bytes = 0;
 
-    bool have_images = false, have_g1 = false, have_cost = false, have_maps = false, have_valid = false;
+    bool have_images = false, have_cost = false, have_maps = false, have_valid = false;
     bool have_keys = false;             // keys_cur holds the packed minima of the current frame's local slices (both sides)
     bool have_keys_side[2] = {false, false};
     // raw_rows[side]: which rows of the unfiltered cost volume exist in memory.  psm_cost_construct may
@@ -228,8 +237,20 @@ struct Prof {
 
 // psm_api_core.cpp
 int h2d_rows(psm_ctx *c, void *dst, const void *src, size_t row, size_t stride, int rows);   // host rows -> packed device rows
+
+// The plane rows a filter reads: the whole image, or - a psm_set_rows stripe [y0, y1) being in force - what the select form of
+// the fused kernel touches for it: the guidance of the model rows y0 - 4 .. y1 + 2 (rounded to +- 4), and the image planes of
+// the rows y0 - 8 .. y1 + 7 (the costs of those model rows, +- 4 for their box sums, and their guidance).
+struct PlaneRows { Rows g1, guid; };
+inline Rows whole_image(const psm_ctx *c) { return Rows{0, c->H}; }
+inline PlaneRows stripe_planes(const psm_ctx *c)
+{
+    const int H = c->H, a = c->march.ybeg, b = c->march.yend;
+    if (b <= a) return {whole_image(c), whole_image(c)};
+    return {Rows{a > 8 ? a - 8 : 0, b + 8 < H ? b + 8 : H}, Rows{a > 4 ? a - 4 : 0, b + 4 < H ? b + 4 : H}};
+}
 // psm_api_filter.cpp
-int run_prep(psm_ctx *c, int ya = 0, int yb = 0);
+int ensure_planes(psm_ctx *c, Rows g1_need, Rows guid_need);   // an empty need: those planes are not asked for
 int ensure_vol(psm_ctx *c, int side);
 int ensure_ab(psm_ctx *c);
 int ensure_spare(psm_ctx *c);

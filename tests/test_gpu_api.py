@@ -18,7 +18,7 @@ def psm():
 
 
 def test_partial_volume_upload_after_striped_cost_construct(psm, oracle):
-    """psm_set_rows + lazy CostConst leaves only a stripe of g1 prepared (have_g1 false): a partial psm_upload_volume must
+    """psm_set_rows + lazy CostConst leaves only a stripe of g1 prepared (the g1 record is that stripe): a partial psm_upload_volume must
     still materialise every other slice from the WHOLE image first (round-2 advisor finding: it skipped that and left
     uninitialised slices marked as real costs)."""
     from primestereomatch_amd import synth
