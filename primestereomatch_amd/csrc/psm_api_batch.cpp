@@ -160,16 +160,14 @@ extern "C" int psm_compute_batch(psm_ctx *const *ctxs, int n)
     for (int i = 0; i < n; ++i) {
         psm_ctx *c = ctxs[i];
         c->g1_rows = c->guid_rows = whole_image(c);
-        c->fgf_virtual[0] = c->fgf_virtual[1] = 0;
-        c->raw_rows[0] = c->raw_rows[1] = psm_ctx::RAW_NONE;
-        c->gf_virtual[0] = c->gf_virtual[1] = true;
         c->have_cost = true;
         c->vol_domain_ok[0] = c->vol_domain_ok[1] = true;      // (the costs are those of the images again, as after psm_cost_construct)
-        c->have_keys = c->have_keys_side[0] = c->have_keys_side[1] = !whole;   // (a disparity shard: its minima are what psm_disp_merge_ctx takes)
-        c->have_maps = whole;
-        c->have_valid = false;
-        c->maps_early = nullptr;
-        c->have_rows = false; c->rows_y0 = 0; c->rows_y1 = H;
+        for (VolSide &v : c->vside) { new_costs(v, true); filtered_to_keys(v); }
+        stale(c->res);
+        keys_gone(c->res);
+        filtered(c->res, whole_image(c), nullptr);             // (the batch wrote the maps itself: no early map to take)
+        if (whole) maps_written(c->res);
+        else { keys_complete(c->res, 0); keys_complete(c->res, 1); }   // (a disparity shard: its minima are what psm_disp_merge_ctx takes)
         if (c->stream != s) PSM_HIP(c0, hipStreamWaitEvent(c->stream, c0->ev_batch, 0));
     }
     if (!c0->opt_async) PSM_HIP(c0, hipStreamSynchronize(s));

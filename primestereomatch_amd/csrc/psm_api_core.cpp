@@ -78,13 +78,9 @@ void adopt_new_pair(psm_ctx *c, int depth)
     c->have_images = true;
     c->g1_rows = c->guid_rows = Rows{};
     c->have_cost = false;
-    c->have_maps = false;
-    c->have_valid = false;
-    c->have_keys = c->have_keys_side[0] = c->have_keys_side[1] = false;
-    c->raw_rows[0] = c->raw_rows[1] = psm_ctx::RAW_ALL;   // nothing virtual survives a new pair
-    c->fgf_virtual[0] = c->fgf_virtual[1] = 0;
-    c->gf_virtual[0] = c->gf_virtual[1] = false;
-    c->maps_early = nullptr;
+    for (VolSide &v : c->vside) new_costs(v, false);       // nothing virtual survives a new pair
+    stale(c->res);
+    keys_gone(c->res);
     c->jw_have[0] = c->jw_have[1] = c->jw_user[0] = c->jw_user[1] = false;   // clusters belong to the images
     c->jw_tab_ok[0] = c->jw_tab_ok[1] = false;
 }
@@ -278,6 +274,7 @@ int psm_create_shard(psm_ctx **out, int width, int height, int max_disp, int d_b
     psm_ctx *c = new psm_ctx();
     c->W = width; c->H = height; c->D = max_disp; c->d0 = d_begin; c->d1 = d_end; c->Dloc = d_end - d_begin;
     c->dtype = dtype; c->device = device;
+    cover(c->res, whole_image(c));
     const size_t HW = (size_t)width * height;
     const size_t V = HW * (size_t)c->Dloc;
     hipError_t e = hipSetDevice(device);
@@ -562,9 +559,7 @@ int psm_upload_volume(psm_ctx *c, int side, int d0, int d1, const void *host)
     if (bind(c)) return 1;
     // a partial upload must not leave virtual slices behind: whatever of this side exists only as a recipe (lazy costs - also
     // after a striped psm_cost_construct, which prepares the stripe's image rows only -, packed minima, FGF models) becomes real data first
-    if (c->have_cost && (c->raw_rows[side] != psm_ctx::RAW_ALL || c->gf_virtual[side] || c->fgf_virtual[side]) && materialize(c, side)) return 1;
-    c->gf_virtual[side] = false;
-    c->maps_early = nullptr;
+    if (c->have_cost && !all_real(c->vside[side]) && materialize(c, side)) return 1;
     if (ensure_vol(c, side)) return 1;
     const size_t S = (size_t)c->W * c->H * velem(c);
     PSM_HIP(c, hipMemcpyAsync((char *)c->vol[side] + (size_t)(d0 - c->d0) * S, host, (size_t)(d1 - d0) * S, hipMemcpyHostToDevice, c->stream));
@@ -575,8 +570,8 @@ int psm_upload_volume(psm_ctx *c, int side, int d0, int d1, const void *host)
     // psm_cost_construct replaces the volume)
     if (c->dtype == PSM_F32 && !range_inside(c, 2 + side, -PSM_VOL_EXP, PSM_VOL_EXP)) c->vol_domain_ok[side] = false;
     c->have_cost = true;
-    c->have_maps = false;
-    c->raw_rows[side] = psm_ctx::RAW_ALL;
+    in_memory(c->vside[side]);
+    stale(c->res);
     return 0;
 }
 

@@ -59,19 +59,16 @@ unsigned long long *next_pc_stamp(psm_ctx *c)
 // a virtual Fast-Guided-Filter result becomes a real volume
 int fgf_flush(psm_ctx *c, int side)
 {
-    if (!c->fgf_virtual[side]) return 0;
+    const int sub = pending_fgf(c->vside[side]);
+    if (!sub) return 0;
     if (ensure_vol(c, side)) return 1;
     {
         Prof p(c, PSM_K_FGF);
-        launch_fgf_apply(c->stream, (float *)c->vol[side], c->g[side].g1, c->W, c->H, c->Dloc, c->fgf_virtual[side], c->fgf_mab[side]);
+        launch_fgf_apply(c->stream, (float *)c->vol[side], c->g[side].g1, c->W, c->H, c->Dloc, sub, c->fgf_mab[side]);
     }
-    c->fgf_virtual[side] = 0;
+    in_memory(c->vside[side]);
     return check_launch(c, "fgf (upsample)");
 }
-
-}  // namespace psm
-
-namespace psm {
 
 // chunk planes of the select-mode fused kernel
 int ensure_gf_scratch(psm_ctx *c, size_t bytes)
@@ -221,12 +218,16 @@ int adopt_staged_pair(psm_ctx *c)
 
 namespace {
 
-// build the (float) cost slices of `side` for rows [ybeg, yend)
-void launch_cvc_rows(psm_ctx *c, int side, int ybeg, int yend)
+// the recipe carried out: the unfiltered costs of `side` written to vol[side]
+int build_costs(psm_ctx *c, int side)
 {
+    if (ensure_vol(c, side)) return 1;
     Prof p(c, PSM_K_CVC);
     // buildCV_right is called with the images swapped (src/DispEst.cpp:217,260)
-    launch_cvc(c->stream, c->g[side].g1, c->g[1 - side].g1, (float *)c->vol[side], c->W, c->H, c->d0, c->Dloc, side, ybeg, yend);
+    if (c->dtype == PSM_U8) launch_cvc_u8(c->stream, c->p4[side], c->p4[1 - side], (uint8_t *)c->vol[side], c->W, c->H, c->d0, c->Dloc, side);
+    else launch_cvc(c->stream, c->g[side].g1, c->g[1 - side].g1, (float *)c->vol[side], c->W, c->H, c->d0, c->Dloc, side, 0, c->H);
+    costs_built(c->vside[side]);
+    return 0;
 }
 
 // 8-bit mode: the float copy of the 8-bit volume of `side` that the storing kernels work on (re-quantised afterwards)
@@ -238,13 +239,6 @@ int u8_to_fvol(psm_ctx *c, int side)
     return 0;
 }
 
-void launch_cvc_u8_side(psm_ctx *c, int side)
-{
-    Prof p(c, PSM_K_CVC);
-    launch_cvc_u8(c->stream, c->p4[side], c->p4[1 - side], (uint8_t *)c->vol[side], c->W, c->H, c->d0, c->Dloc, side);
-    c->raw_rows[side] = psm_ctx::RAW_ALL;
-}
-
 // The storing form of the fused filter: `side` filtered into a real volume, from whatever its costs currently are (what
 // psm_download_volume etc. see; the default path never runs it).  Needs the planes of the whole image.
 //   float, costs virtual:  built on the fly inside the kernel; nothing is read from vol[side], so the result goes straight into it
@@ -254,8 +248,8 @@ int filter_stored(psm_ctx *c, int side)
 {
     const bool u8 = c->dtype == PSM_U8;
     if (ensure_vol(c, side)) return 1;
-    if (u8 && c->raw_rows[side] != psm_ctx::RAW_ALL) launch_cvc_u8_side(c, side);
-    const bool lazy = c->raw_rows[side] != psm_ctx::RAW_ALL;
+    if (u8 && costs_lazy(c->vside[side]) && build_costs(c, side)) return 1;
+    const bool lazy = costs_lazy(c->vside[side]);
     if (u8 && u8_to_fvol(c, side)) return 1;
     if (!lazy && ensure_spare(c)) return 1;
     const float *in = lazy ? nullptr : u8 ? c->fvol : (const float *)c->vol[side];
@@ -267,8 +261,7 @@ int filter_stored(psm_ctx *c, int side)
     }
     if (u8) launch_f32_to_u8(c->stream, out, (uint8_t *)c->vol[side], (size_t)c->W * c->H * c->Dloc);   // q8 = sat_u8(rintf(q * 255))
     else if (!lazy) std::swap(*(float **)&c->vol[side], c->spare);
-    c->gf_virtual[side] = false;
-    c->raw_rows[side] = psm_ctx::RAW_ALL;                 // vol[side] now holds real (filtered) data
+    in_memory(c->vside[side]);                   // vol[side] now holds real (filtered) data
     return check_launch(c, "cvf (fused, storing form)");
 }
 
@@ -281,20 +274,13 @@ int materialize(psm_ctx *c, int side)
 {
     PSM_NOT_STRIDED(c, "materialising a cost volume");
     if (fgf_flush(c, side)) return 1;
-    if (!c->gf_virtual[side] && c->raw_rows[side] == psm_ctx::RAW_ALL) return 0;
+    if (all_real(c->vside[side])) return 0;
     // (a row-stripe filter leaves only its own rows of the planes behind)
     if (ensure_planes(c, whole_image(c), whole_image(c))) return 1;
     // the guided-filter result exists only as WTA keys: run the same fused kernel again, this time storing q
-    if (c->gf_virtual[side]) return filter_stored(c, side);
+    if (pending_keys(c->vside[side])) return filter_stored(c, side);
     // the costs exist only as a recipe: build them
-    if (c->dtype == PSM_U8) {
-        launch_cvc_u8_side(c, side);
-    } else {
-        if (ensure_vol(c, side)) return 1;
-        launch_cvc_rows(c, side, 0, c->H);
-        c->raw_rows[side] = psm_ctx::RAW_ALL;
-    }
-    return check_launch(c, "cvc (materialize)");
+    return build_costs(c, side) || check_launch(c, "cvc (materialize)");
 }
 
 }  // namespace psm
@@ -306,7 +292,7 @@ namespace {
 int filter_side_select(psm_ctx *c, int side)
 {
     const int W = c->W, H = c->H;
-    const bool lazy = c->raw_rows[side] != psm_ctx::RAW_ALL, sel8 = c->dtype == PSM_U8;
+    const bool lazy = costs_lazy(c->vside[side]), sel8 = c->dtype == PSM_U8;
     const PcPlan pl = pc_plan(W, c->march.rows(H), c->Dloc, c->march.seg_rows, PC_PLANES);
     if (ensure_gf_scratch(c, pl.scratch_bytes())) return 1;
     {
@@ -318,7 +304,7 @@ int filter_side_select(psm_ctx *c, int side)
         Prof p(c, PSM_K_WTA);
         launch_chunk_min(c->stream, c->march, W, H, c->Dloc, c->gf_scratch, c->keys_cur + side * (size_t)W * H, nullptr);
     }
-    c->gf_virtual[side] = true;
+    filtered_to_keys(c->vside[side]);
     return check_launch(c, "cvf (fused, select mode)");
 }
 
@@ -351,13 +337,13 @@ int filter_side_direct(psm_ctx *c, int side, bool stage_b)
 int filter_side(psm_ctx *c, int side, bool stage_b)
 {
     PSM_NOT_STRIDED(c, "filtering one side / a materialised volume / the storing form");
-    c->maps_early = nullptr;
+    forget_early(c->res);                // (the keys under an early map are about to change)
     // (the guidance of BOTH images the first time either side asks: the other side's call then finds it)
     if (ensure_planes(c, whole_image(c), whole_image(c))) return 1;
     if (fgf_flush(c, side)) return 1;
-    if (c->gf_virtual[side] && materialize(c, side)) return 1;   // filtering an already filtered (virtual) volume: make it real first
+    if (pending_keys(c->vside[side]) && materialize(c, side)) return 1;   // filtering an already filtered (virtual) volume: make it real first
     if (!stage_b || c->opt_variant != 0) return filter_side_direct(c, side, stage_b);
-    const bool select_form = (c->dtype == PSM_F32 || c->raw_rows[side] != psm_ctx::RAW_ALL) && !(c->march.flags & PSM_FLAG_STORE_FILTERED) && scaled_forms_ok(c);
+    const bool select_form = (c->dtype == PSM_F32 || costs_lazy(c->vside[side])) && !(c->march.flags & PSM_FLAG_STORE_FILTERED) && scaled_forms_ok(c);
     return select_form ? filter_side_select(c, side) : filter_stored(c, side);
 }
 
@@ -365,22 +351,20 @@ int filter_side(psm_ctx *c, int side, bool stage_b)
 // launches per frame instead of twelve.  The default path (costs built on the fly, both sides fresh).
 bool can_filter_both(const psm_ctx *c)
 {
-    return c->opt_variant == 0 && !(c->march.flags & PSM_FLAG_STORE_FILTERED) && scaled_forms_ok(c) &&
-           c->raw_rows[0] != psm_ctx::RAW_ALL && c->raw_rows[1] != psm_ctx::RAW_ALL && !c->gf_virtual[0] && !c->gf_virtual[1] &&
-           !c->fgf_virtual[0] && !c->fgf_virtual[1];
+    return c->opt_variant == 0 && !(c->march.flags & PSM_FLAG_STORE_FILTERED) && scaled_forms_ok(c) && fresh_lazy(c->vside[0]) && fresh_lazy(c->vside[1]);
 }
 
+// The results are those of the stripe in force NOW, whatever psm_set_rows says later; sp.maps: psm_disp_select has no kernel left to launch.
 int filter_both(psm_ctx *c)
 {
-    c->maps_early = nullptr;
     // (after a lazy psm_cost_construct in a float context: image planes AND guidance in one launch, straight from the staged images)
     const PlaneRows need = stripe_planes(c);
     if (ensure_planes(c, need.g1, need.guid)) return 1;
     const SelPlan sp = select_plan(c, 1, false);
     if (ensure_gf_scratch(c, sp.scratch_bytes)) return 1;
     if (enqueue_select(c, PcPairs{nullptr, 1, pc_pair(c)}, sp)) return 1;
-    c->maps_early = sp.maps ? c->maps : nullptr;      // (psm_disp_select has no kernel left to launch)
-    c->gf_virtual[0] = c->gf_virtual[1] = true;
+    for (VolSide &v : c->vside) filtered_to_keys(v);
+    filtered(c->res, stripe_rows(c), sp.maps ? c->maps : nullptr);
     return check_launch(c, sp.two_phase ? "cvf (fused, select mode, two phases, both volumes)" : "cvf (fused, select mode, both volumes)");
 }
 
@@ -411,25 +395,15 @@ int psm_cost_construct(psm_ctx *c)
     // kernel - 450 x 375 x 64, two frames in flight: 0.226 ms against 0.211 with k_prep + k_guide_march; alone it is 0.270 vs 0.279.)
     const bool lazy_prep = lazy && c->dtype == PSM_F32 && c->march.inflight <= 1;
     if (!lazy_prep && ensure_planes(c, lazy ? stripe_planes(c).g1 : whole_image(c), Rows{})) return 1;
-    c->fgf_virtual[0] = c->fgf_virtual[1] = 0;   // a new cost volume replaces whatever was pending
-    c->gf_virtual[0] = c->gf_virtual[1] = false;
     c->vol_domain_ok[0] = c->vol_domain_ok[1] = true;   // (uploaded volumes are gone; the costs now follow from the images)
-    c->maps_early = nullptr;
     for (int s = 0; s < 2; ++s) {
-        if (lazy) {
-            c->raw_rows[s] = psm_ctx::RAW_NONE;
-        } else if (c->dtype == PSM_U8) {
-            launch_cvc_u8_side(c, s);
-        } else {
-            if (ensure_vol(c, s)) return 1;
-            launch_cvc_rows(c, s, 0, c->H);
-            c->raw_rows[s] = psm_ctx::RAW_ALL;
-        }
+        if (!lazy && build_costs(c, s)) return 1;
+        new_costs(c->vside[s], lazy);                   // a new cost volume replaces whatever was pending
     }
     if (check_launch(c, "cvc")) return 1;
     c->have_cost = true;
-    c->have_maps = false;
-    c->have_keys = c->have_keys_side[0] = c->have_keys_side[1] = false;
+    stale(c->res);
+    keys_gone(c->res);
     return end_stage(c, PSM_STAGE_CVC, t0);
 }
 
@@ -449,12 +423,8 @@ int psm_cost_filter(psm_ctx *c)
                                     "(no variant / storing flag, cost volumes not materialised, images / volumes inside the select forms' domain)");
         for (int s = 0; s < 2; ++s)
             if (filter_side(c, s, true)) return 1;
+        filtered(c->res, whole_image(c), nullptr);
     }
-    c->have_maps = false;
-    // the minima (and the maps made from them) describe the stripe that is in force NOW, whatever psm_set_rows says later
-    c->have_rows = striped;
-    c->rows_y0 = striped ? c->march.ybeg : 0;
-    c->rows_y1 = striped ? c->march.yend : c->H;
     return end_stage(c, PSM_STAGE_CVF, t0);
 }
 
@@ -468,10 +438,7 @@ int psm_cost_filter_side(psm_ctx *c, int side)
     if (bind(c)) return 1;
     const double t0 = now_us();
     if (filter_side(c, side, true)) return 1;
-    c->have_maps = false;
-    c->have_rows = false;
-    c->rows_y0 = 0;
-    c->rows_y1 = c->H;
+    filtered(c->res, whole_image(c), nullptr);
     if (!c->opt_async) PSM_HIP(c, hipStreamSynchronize(c->stream));
     c->stage_us[PSM_STAGE_CVF] = (side == PSM_LEFT ? 0.0 : c->stage_us[PSM_STAGE_CVF]) + (now_us() - t0);
     return 0;
@@ -490,14 +457,13 @@ int psm_cost_filter_fgf(psm_ctx *c, int sub)
     const int ws = c->W / sub, hs = c->H / sub, rad = 8 / sub;
     if (ws <= rad || hs <= rad) return fail(c, "psm_cost_filter_fgf: %dx%d too small for subsample_rate %d", c->W, c->H, sub);
     if (bind(c)) return 1;
-    c->maps_early = nullptr;
     const double t0 = now_us();
     if (ensure_planes(c, whole_image(c), Rows{})) return 1;
     // small planes: ism, msm, v1 (float4), v2 (float2) per pixel; ab (scratch) and one mab per side (float4) per small voxel
     const size_t n = (size_t)ws * hs, need = n * (3 * sizeof(float4) + sizeof(float2)) + 3 * n * c->Dloc * sizeof(float4);
     if (fgf_flush(c, 0) || fgf_flush(c, 1)) return 1;   // filtering an already FGF-filtered volume: make it real first
     for (int side = 0; side < 2; ++side)
-        if (c->gf_virtual[side] && materialize(c, side)) return 1;
+        if (pending_keys(c->vside[side]) && materialize(c, side)) return 1;
     if (c->fgf_bytes < need) {
         PSM_HIP(c, hipStreamSynchronize(c->stream));
         (void)hipFree(c->fgf);
@@ -515,21 +481,18 @@ int psm_cost_filter_fgf(psm_ctx *c, int sub)
     // left volume with the left image as guidance, then the right one (src/DispEst.cpp:283-295)
     for (int side = 0; side < 2; ++side) {
         // a virtual (lazy) cost volume stays virtual: the filter samples 1/sub^2 of it straight from the g1 planes
-        const int mode = c->raw_rows[side] == psm_ctx::RAW_ALL ? 0 : 1 + side;
+        const int mode = costs_lazy(c->vside[side]) ? 1 + side : 0;
         Prof p(c, PSM_K_FGF);
         launch_fgf_setup(c->stream, c->g[side].g1, c->W, c->H, sub, ism, msm, v1, v2);
         launch_fgf_model(c->stream, (const float *)c->vol[side], c->g[side].g1, c->g[1 - side].g1, c->W, c->H, c->Dloc, c->d0, sub, mode,
                          msm, v1, v2, ab, c->fgf_mab[side]);
-        if (keep_virtual) c->fgf_virtual[side] = sub;
-        else if (ensure_vol(c, side)) return 1;
-        else launch_fgf_apply(c->stream, (float *)c->vol[side], c->g[side].g1, c->W, c->H, c->Dloc, sub, c->fgf_mab[side]);
-        c->raw_rows[side] = psm_ctx::RAW_ALL;   // vol[side] holds (or, while virtual, stands for) filtered data
+        if (keep_virtual) { filtered_to_fgf(c->vside[side], sub); continue; }   // (vol[side] stands for it, allocated or not: VolSide)
+        if (ensure_vol(c, side)) return 1;
+        launch_fgf_apply(c->stream, (float *)c->vol[side], c->g[side].g1, c->W, c->H, c->Dloc, sub, c->fgf_mab[side]);
+        in_memory(c->vside[side]);
     }
     if (check_launch(c, "cvf (fast guided filter)")) return 1;
-    c->have_maps = false;
-    c->have_rows = false;                       // whole-image results
-    c->rows_y0 = 0;
-    c->rows_y1 = c->H;
+    filtered(c->res, whole_image(c), nullptr);
     return end_stage(c, PSM_STAGE_CVF, t0);
 }
 
@@ -539,7 +502,6 @@ int psm_filter_stage_a(psm_ctx *c, int side)
     if (side != PSM_LEFT && side != PSM_RIGHT) return fail(c, "psm_filter_stage_a: bad side %d", side);
     if (!c->have_cost || !c->have_images) return fail(c, "psm_filter_stage_a: needs images and a cost volume");
     if (bind(c)) return 1;
-    c->maps_early = nullptr;
     if (filter_side(c, side, false)) return 1;
     PSM_HIP(c, hipStreamSynchronize(c->stream));
     return 0;

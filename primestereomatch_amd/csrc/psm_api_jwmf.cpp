@@ -146,8 +146,8 @@ int psm_joint_wmf(psm_ctx *c, int radius, float sigma, int n_clusters, int max_i
     if (max_iter <= 0) max_iter = 10000;       // TermCriteria(..., 10000) (JointWMF.h:590)
     if (radius > JW_RMAX) return fail(c, "psm_joint_wmf: radius %d outside 1..%d", radius, JW_RMAX);
     if (n_clusters > JW_NF_MAX) return fail(c, "psm_joint_wmf: n_clusters %d outside 1..%d", n_clusters, JW_NF_MAX);
-    if (!c->have_maps) return fail(c, "psm_joint_wmf: no disparity maps computed");
-    if (c->have_rows) return fail(c, "psm_joint_wmf: the maps hold this context's row stripe only (gather the stripes first)");
+    if (!c->res.maps) return fail(c, "psm_joint_wmf: no disparity maps computed");
+    if (stripe_only(c)) return fail(c, "psm_joint_wmf: the maps hold this context's row stripe only (gather the stripes first)");
     if (!c->have_images) return fail(c, "psm_joint_wmf: no image pair uploaded (the feature images)");
     if (bind(c) || maps_writable(c)) return 1;
     const double t0 = now_us();
@@ -187,7 +187,7 @@ int psm_joint_wmf(psm_ctx *c, int radius, float sigma, int n_clusters, int max_i
     if (check_launch(c, "joint_wmf (median)")) return 1;
     for (int s = 0; s < 2; ++s)
         PSM_HIP(c, hipMemcpyAsync(c->maps + s * HW, sc[s].out, HW, hipMemcpyDeviceToDevice, c->stream));
-    c->maps_early = nullptr;
+    forget_early(c->res);        // (rewritten in place)
     if (copy_maps_out(c, c->maps, lmap, rmap, stride)) return 1;
     if (!c->opt_async) PSM_HIP(c, hipStreamSynchronize(c->stream));
     c->stage_us[PSM_STAGE_PP] += now_us() - t0;

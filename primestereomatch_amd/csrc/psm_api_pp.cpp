@@ -10,8 +10,8 @@ extern "C" {
 int psm_lr_check(psm_ctx *c, uint8_t *lvalid, uint8_t *rvalid, size_t stride)
 {
     if (!c) return 1;
-    if (!c->have_maps) return fail(c, "psm_lr_check: no disparity maps computed");
-    if (c->have_rows) return fail(c, "psm_lr_check: the maps hold this context's row stripe only (gather the stripes first)");
+    if (!c->res.maps) return fail(c, "psm_lr_check: no disparity maps computed");
+    if (stripe_only(c)) return fail(c, "psm_lr_check: the maps hold this context's row stripe only (gather the stripes first)");
     if (bind(c)) return 1;
     const double t0 = now_us();
     const size_t HW = (size_t)c->W * c->H;
@@ -20,7 +20,7 @@ int psm_lr_check(psm_ctx *c, uint8_t *lvalid, uint8_t *rvalid, size_t stride)
         launch_lr_check(c->stream, c->maps, c->maps + HW, c->W, c->H, c->valid, c->valid + HW);
     }
     if (check_launch(c, "lr_check")) return 1;
-    c->have_valid = true;
+    mask_written(c->res);
     if (copy_maps_out(c, c->valid, lvalid, rvalid, stride)) return 1;
     return end_stage(c, PSM_STAGE_PP, t0);
 }
@@ -28,7 +28,7 @@ int psm_lr_check(psm_ctx *c, uint8_t *lvalid, uint8_t *rvalid, size_t stride)
 int psm_fill_invalid(psm_ctx *c, uint8_t *lmap, uint8_t *rmap, size_t stride)
 {
     if (!c) return 1;
-    if (!c->have_maps || !c->have_valid) return fail(c, "psm_fill_invalid: needs disparity maps and psm_lr_check");
+    if (!c->res.mask) return fail(c, "psm_fill_invalid: needs disparity maps and psm_lr_check");
     if (bind(c) || maps_writable(c)) return 1;
     const double t0 = now_us();
     const size_t HW = (size_t)c->W * c->H;
@@ -37,7 +37,7 @@ int psm_fill_invalid(psm_ctx *c, uint8_t *lmap, uint8_t *rmap, size_t stride)
         launch_fill_inv(c->stream, c->maps, c->valid, HW, c->W, c->H);
     }
     if (check_launch(c, "fill_inv")) return 1;
-    // have_valid stays set: the mask still says which pixels the L-R check rejected, which is what the next stage of
+    // the mask stays current: it still says which pixels the L-R check rejected, which is what the next stage of
     // PP::processDM (wgtMedian, src/PP.cpp:405-410) filters
     if (copy_maps_out(c, c->maps, lmap, rmap, stride)) return 1;
     if (!c->opt_async) PSM_HIP(c, hipStreamSynchronize(c->stream));
@@ -62,8 +62,7 @@ static int wgt_median_dataflow(psm_ctx *c, int side)
     PSM_HIP(c, hipStreamSynchronize(c->stream));
     if (herr) {
         // the kernel gave up on unfinished rows: the in-place maps are partially filtered - not results
-        c->have_maps = false;
-        c->have_valid = false;
+        maps_gone(c->res);
         return fail(c, "psm_wgt_median: row pipeline stalled (watchdog); the device maps are no longer valid - select again");
     }
     c->wm_sweeps[side] = -1;
@@ -74,7 +73,7 @@ static int wgt_median_dataflow(psm_ctx *c, int side)
 int psm_wgt_median(psm_ctx *c, uint8_t *lmap, uint8_t *rmap, size_t stride)
 {
     if (!c) return 1;
-    if (!c->have_maps || !c->have_valid) return fail(c, "psm_wgt_median: needs disparity maps and psm_lr_check");
+    if (!c->res.mask) return fail(c, "psm_wgt_median: needs disparity maps and psm_lr_check");
     if (!c->have_images) return fail(c, "psm_wgt_median: no image pair uploaded (colour weights)");
     if (c->W < 9 || c->H < 9) return fail(c, "psm_wgt_median: image %dx%d smaller than the 19x19 window's wrap allows", c->W, c->H);
     if (bind(c) || maps_writable(c)) return 1;
@@ -239,15 +238,15 @@ int psm_upload_maps(psm_ctx *c, const uint8_t *lmap, const uint8_t *rmap, const 
     if (stride == 0) stride = c->W;
     if (stride < (size_t)c->W) return fail(c, "psm_upload_maps: stride %zu < width %d", stride, c->W);
     if (bind(c) || maps_writable(c)) return 1;
-    c->maps_early = nullptr;
+    forget_early(c->res);
     const size_t HW = (size_t)c->W * c->H;
     const uint8_t *src[4] = {lmap, rmap, lvalid, rvalid};
     uint8_t *dst[4] = {c->maps, c->maps + HW, c->valid, c->valid + HW};
     for (int i = 0; i < 4; ++i)
         if (src[i] && h2d_rows(c, dst[i], src[i], (size_t)c->W, stride, c->H)) return 1;
     PSM_HIP(c, hipStreamSynchronize(c->stream));
-    if (lmap && rmap) { c->have_maps = true; c->have_valid = false; c->have_rows = false; c->rows_y0 = 0; c->rows_y1 = c->H; }   // whole maps
-    if (lvalid && rvalid && c->have_maps) c->have_valid = true;
+    if (lmap && rmap) { cover(c->res, whole_image(c)); maps_written(c->res); }   // whole maps
+    if (lvalid && rvalid) mask_written(c->res);                                  // (of the maps in the buffer: none without them)
     return 0;
 }
 

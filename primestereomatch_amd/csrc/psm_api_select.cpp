@@ -10,11 +10,27 @@ using namespace psm;
 
 namespace psm {
 
+// Two [H][W] planes in a page-locked buffer into the caller's (pageable, possibly strided) rows: the row stride the caller
+// means (0: packed rows), refused when it is shorter than a row, and the copy
+static int rows_out(psm_ctx *c, size_t &stride, const uint8_t *pin = nullptr, uint8_t *lmap = nullptr, uint8_t *rmap = nullptr)
+{
+    const size_t W = (size_t)c->W, HW = W * c->H;
+    if (stride == 0) stride = W;
+    if (stride < W) return fail(c, "map stride %zu < width %d", stride, c->W);
+    uint8_t *dst[2] = {lmap, rmap};
+    for (int s = 0; s < 2 && pin; ++s) {
+        if (!dst[s]) continue;
+        const uint8_t *src = pin + s * HW;
+        if (stride == W) memcpy(dst[s], src, HW);
+        else for (int y = 0; y < c->H; ++y) memcpy(dst[s] + (size_t)y * stride, src + (size_t)y * W, W);
+    }
+    return 0;
+}
+
 int copy_maps_out(psm_ctx *c, const uint8_t *dev, uint8_t *lmap, uint8_t *rmap, size_t stride)
 {
     const size_t HW = (size_t)c->W * c->H;
-    if (stride == 0) stride = c->W;
-    if (stride < (size_t)c->W) return fail(c, "map stride %zu < width %d", stride, c->W);
+    if (rows_out(c, stride)) return 1;          // (the stride alone: nothing is started for one that is refused)
     if (!lmap && !rmap) return 0;
     // device -> page-locked bounce buffer (one DMA at link speed) -> the caller's (pageable, possibly strided) rows.
     // A direct copy into pageable memory took 6-16 ms for two 1080p maps; this way it is ~0.5 ms.
@@ -32,14 +48,7 @@ int copy_maps_out(psm_ctx *c, const uint8_t *dev, uint8_t *lmap, uint8_t *rmap, 
     else if (lmap) PSM_HIP(c, hipMemcpyAsync(c->pinned, dev, HW, hipMemcpyDeviceToHost, c->stream));
     else PSM_HIP(c, hipMemcpyAsync(c->pinned + HW, dev + HW, HW, hipMemcpyDeviceToHost, c->stream));
     PSM_HIP(c, hipStreamSynchronize(c->stream));
-    uint8_t *dst[2] = {lmap, rmap};
-    for (int s2 = 0; s2 < 2; ++s2) {
-        if (!dst[s2]) continue;
-        const uint8_t *src = c->pinned + s2 * HW;
-        if (stride == (size_t)c->W) memcpy(dst[s2], src, HW);
-        else for (int y = 0; y < c->H; ++y) memcpy(dst[s2] + (size_t)y * stride, src + (size_t)y * c->W, (size_t)c->W);
-    }
-    return 0;
+    return rows_out(c, stride, c->pinned, lmap, rmap);
 }
 
 }  // namespace psm
@@ -52,19 +61,20 @@ int wta_side(psm_ctx *c, int s, long long *keys_s, uint8_t *map_s)
 {
     const size_t HW = (size_t)c->W * c->H;
     Prof p(c, PSM_K_WTA);
-    if (c->gf_virtual[s]) {
-        // the select-mode filter already reduced this side: keys[s] holds the packed minima over the local slices
-        const long long *src = c->keys_cur + s * HW;
-        if (keys_s && keys_s != src) PSM_HIP(c, hipMemcpyAsync(keys_s, src, HW * sizeof(long long), hipMemcpyDeviceToDevice, c->stream));
-        if (map_s) launch_merge(c->stream, src, HW, 1, (int)HW, map_s);
-    } else if (c->fgf_virtual[s]) {
-        long long *k = keys_s ? keys_s : c->keys_cur + s * HW;
-        launch_fgf_apply_wta(c->stream, c->g[s].g1, c->W, c->H, c->Dloc, c->d0, c->fgf_virtual[s], c->fgf_mab[s], k);
+    long long *const cur = c->keys_cur + s * HW, *const k = keys_s ? keys_s : cur;
+    switch (c->vside[s].pending) {
+    case VolSide::KEYS:         // the select-mode filter already reduced this side: `cur` holds the packed minima over the local slices
+        if (k != cur) PSM_HIP(c, hipMemcpyAsync(k, cur, HW * sizeof(long long), hipMemcpyDeviceToDevice, c->stream));
+        if (map_s) launch_merge(c->stream, cur, HW, 1, (int)HW, map_s);
+        break;
+    case VolSide::FGF:
+        launch_fgf_apply_wta(c->stream, c->g[s].g1, c->W, c->H, c->Dloc, c->d0, pending_fgf(c->vside[s]), c->fgf_mab[s], k);
         if (map_s) launch_merge(c->stream, k, HW, 1, (int)HW, map_s);
-    } else if (c->dtype == PSM_U8) {
-        launch_wta_u8(c->stream, (const uint8_t *)c->vol[s], c->W, c->H, c->d0, c->Dloc, keys_s, map_s);
-    } else {
-        launch_wta(c->stream, (const float *)c->vol[s], c->W, c->H, c->d0, c->Dloc, keys_s, map_s);
+        break;
+    case VolSide::NOTHING:      // (real memory: wta_ready)
+        if (c->dtype == PSM_U8) launch_wta_u8(c->stream, (const uint8_t *)c->vol[s], c->W, c->H, c->d0, c->Dloc, keys_s, map_s);
+        else launch_wta(c->stream, (const float *)c->vol[s], c->W, c->H, c->d0, c->Dloc, keys_s, map_s);
+        break;
     }
     return 0;
 }
@@ -75,11 +85,10 @@ int wta_launch(psm_ctx *c, long long *keys, uint8_t *maps)
     // the map buffer may still be the source of an asynchronous download of the previous frame
     if (maps && maps_writable(c)) return 1;
     // a side that is not the select filter's packed minima was selected from a whole volume: its map is whole
-    if (!(c->gf_virtual[0] && c->gf_virtual[1])) { c->have_rows = false; c->rows_y0 = 0; c->rows_y1 = c->H; }
-    if (c->gf_virtual[0] && c->gf_virtual[1] && !keys && maps) {   // both sides already reduced to keys: one launch for both maps
-        const bool done = c->maps_early == maps;                    // ... unless the filter's reduction wrote them already
-        c->maps_early = nullptr;                                    // (once: post-processing rewrites the maps in place)
-        if (done) return 0;
+    const bool both_keys = pending_keys(c->vside[0]) && pending_keys(c->vside[1]);
+    if (!both_keys) cover(c->res, whole_image(c));
+    if (both_keys && !keys && maps) {             // both sides already reduced to keys: one launch for both maps
+        if (take_early(c->res, maps)) return 0;   // ... unless the filter's reduction wrote them already (once: post-processing rewrites the maps in place)
         Prof p(c, PSM_K_WTA);
         launch_merge(c->stream, c->keys_cur, 2 * HW, 1, (int)(2 * HW), maps);
         return check_launch(c, "wta");
@@ -92,7 +101,7 @@ int wta_launch(psm_ctx *c, long long *keys, uint8_t *maps)
 // the volume a WTA is about to read: real data, or a virtual result (consumed without materialising it)
 int wta_ready(psm_ctx *c, int side)
 {
-    return (c->fgf_virtual[side] || c->gf_virtual[side]) ? 0 : materialize(c, side);
+    return c->vside[side].pending != VolSide::NOTHING ? 0 : materialize(c, side);
 }
 
 }  // namespace
@@ -108,8 +117,7 @@ int psm_disp_select(psm_ctx *c, uint8_t *lmap, uint8_t *rmap, size_t stride)
     const double t0 = now_us();
     if (wta_ready(c, 0) || wta_ready(c, 1)) return 1;
     if (wta_launch(c, nullptr, c->maps)) return 1;
-    c->have_maps = true;
-    c->have_valid = false;
+    maps_written(c->res);
     if (copy_maps_out(c, c->maps, lmap, rmap, stride)) return 1;
     return end_stage(c, PSM_STAGE_DISPSEL, t0);
 }
@@ -122,7 +130,7 @@ int psm_disp_select_partial(psm_ctx *c, void *dev_keys)
     const double t0 = now_us();
     if (wta_ready(c, 0) || wta_ready(c, 1)) return 1;
     if (wta_launch(c, dev_keys ? (long long *)dev_keys : c->keys_cur, nullptr)) return 1;
-    if (!dev_keys) c->have_keys = c->have_keys_side[0] = c->have_keys_side[1] = true;
+    if (!dev_keys) { keys_complete(c->res, 0); keys_complete(c->res, 1); }
     return end_stage(c, PSM_STAGE_DISPSEL, t0);
 }
 
@@ -138,10 +146,7 @@ int psm_disp_select_partial_side(psm_ctx *c, int side, void *dev_keys_side)
     long long *keys = dev_keys_side ? (long long *)dev_keys_side : c->keys_cur + side * HW;
     if (wta_side(c, side, keys, nullptr)) return 1;
     if (check_launch(c, "wta")) return 1;
-    if (!dev_keys_side) {
-        c->have_keys_side[side] = true;
-        c->have_keys = c->have_keys_side[0] && c->have_keys_side[1];
-    }
+    if (!dev_keys_side) keys_complete(c->res, side);
     if (!c->opt_async) PSM_HIP(c, hipStreamSynchronize(c->stream));
     c->stage_us[PSM_STAGE_DISPSEL] = (side == PSM_LEFT ? 0.0 : c->stage_us[PSM_STAGE_DISPSEL]) + (now_us() - t0);
     return 0;
@@ -151,7 +156,7 @@ int psm_set_rows(psm_ctx *c, int y_begin, int y_end)
 {
     if (!c) return 1;
     // (takes effect with the next psm_cost_filter; minima / maps already computed keep describing the stripe they were made
-    // for - rows_y0 / rows_y1, recorded when they were filtered)
+    // for - Results::rows, recorded when they were filtered)
     if (y_begin == 0 && (y_end == 0 || y_end == c->H)) {   // whole image
         c->march.ybeg = c->march.yend = 0;
         return 0;
@@ -166,15 +171,12 @@ int psm_set_map_buffer(psm_ctx *c, void *dev_maps, int whole)
 {
     if (!c) return 1;
     uint8_t *m = dev_maps ? (uint8_t *)dev_maps : c->maps_own;
-    if (m != c->maps) { c->have_maps = false; c->have_valid = false; }
-    c->maps_early = nullptr;
+    if (m != c->maps) maps_gone(c->res);
+    forget_early(c->res);
     c->maps = m;
     if (whole) {    // the caller filled the buffer with both complete maps of the current frame (e.g. gathered row stripes)
-        c->have_maps = true;
-        c->have_rows = false;
-        c->rows_y0 = 0;
-        c->rows_y1 = c->H;
-        c->have_valid = false;
+        cover(c->res, whole_image(c));
+        maps_written(c->res);
     }
     return 0;
 }
@@ -223,20 +225,27 @@ static int gather_leg(psm_ctx *root, void *dst, psm_ctx *s, const void *src, siz
     return 0;
 }
 
+// ... first: everything context s has enqueued on its stream (on its device) has executed
+static int sync_other(psm_ctx *root, psm_ctx *s)
+{
+    (void)hipSetDevice(s->device);
+    PSM_HIP(root, hipStreamSynchronize(s->stream));
+    (void)hipSetDevice(root->device);
+    return 0;
+}
+
 int psm_gather_rows_ctx(psm_ctx *root, psm_ctx *const *stripes, int nstripes, uint8_t *lmap, uint8_t *rmap, size_t stride)
 {
     if (!root) return 1;
     if (!stripes || nstripes < 1) return fail(root, "psm_gather_rows_ctx: bad arguments");
     std::vector<char> covered((size_t)root->H, 0);
-    // which rows a context's maps hold: the stripe they were FILTERED with (not what psm_set_rows says now)
-    auto y0_of = [](const psm_ctx *s) { return s->have_rows ? s->rows_y0 : 0; };
-    auto y1_of = [](const psm_ctx *s) { return s->have_rows ? s->rows_y1 : s->H; };
+    // (which rows a context's maps hold: the stripe they were FILTERED with - Results::rows -, not what psm_set_rows says now)
     for (int i = 0; i < nstripes; ++i) {
         const psm_ctx *s = stripes[i];
         if (!s || s->W != root->W || s->H != root->H || s->D != root->D || s->dtype != root->dtype)
             return fail(root, "psm_gather_rows_ctx: stripe %d does not belong to this job", i);
-        if (!s->have_maps) return fail(root, "psm_gather_rows_ctx: stripe %d has no maps for this frame (call psm_disp_select first)", i);
-        for (int y = y0_of(s); y < y1_of(s); ++y) {
+        if (!s->res.maps) return fail(root, "psm_gather_rows_ctx: stripe %d has no maps for this frame (call psm_disp_select first)", i);
+        for (int y = s->res.rows.y0; y < s->res.rows.y1; ++y) {
             if (covered[y]) return fail(root, "psm_gather_rows_ctx: row %d is held by more than one stripe", y);
             covered[y] = 1;
         }
@@ -248,18 +257,13 @@ int psm_gather_rows_ctx(psm_ctx *root, psm_ctx *const *stripes, int nstripes, ui
     for (int i = 0; i < nstripes; ++i) {
         psm_ctx *s = stripes[i];
         if (s == root) continue;
-        (void)hipSetDevice(s->device);
-        PSM_HIP(root, hipStreamSynchronize(s->stream));     // the stripe's maps must be complete before they are read
-        (void)hipSetDevice(root->device);
-        const size_t o = (size_t)y0_of(s) * root->W, n = (size_t)(y1_of(s) - y0_of(s)) * root->W;
+        if (sync_other(root, s)) return 1;                  // the stripe's maps must be complete before they are read
+        const size_t o = (size_t)s->res.rows.y0 * root->W, n = (size_t)(s->res.rows.y1 - s->res.rows.y0) * root->W;
         for (int side = 0; side < 2; ++side)
             if (gather_leg(root, root->maps + side * HW + o, s, s->maps + side * HW + o, n)) return 1;
     }
-    root->have_maps = true;
-    root->have_rows = false;      // the root's maps are whole now
-    root->rows_y0 = 0;
-    root->rows_y1 = root->H;
-    root->have_valid = false;
+    cover(root->res, whole_image(root));      // the root's maps are whole now
+    maps_written(root->res);
     if (copy_maps_out(root, root->maps, lmap, rmap, stride)) return 1;
     if (!root->opt_async) PSM_HIP(root, hipStreamSynchronize(root->stream));
     return 0;
@@ -271,7 +275,7 @@ int psm_set_key_buffer(psm_ctx *c, void *dev_keys)
 {
     if (!c) return 1;
     long long *k = dev_keys ? (long long *)dev_keys : c->keys;
-    if (k != c->keys_cur && (c->gf_virtual[0] || c->gf_virtual[1]))
+    if (k != c->keys_cur && (pending_keys(c->vside[0]) || pending_keys(c->vside[1])))
         return fail(c, "psm_set_key_buffer: the current minima are still pending in the previous buffer (call before psm_cost_filter)");
     c->keys_cur = k;
     return 0;
@@ -298,10 +302,9 @@ int psm_disp_merge(psm_ctx *c, const void *dev_keys_all, int nranks, uint8_t *lm
         launch_merge(c->stream, (const long long *)dev_keys_all, n, nranks, (int)n, c->maps);
     }
     if (check_launch(c, "merge")) return 1;
-    // (the merged keys are those of this job's shards, filtered under the stripe this context recorded - rows_y0 / rows_y1
+    // (the merged keys are those of this job's shards, filtered under the stripe this context recorded - Results::rows
     // stay as psm_cost_filter left them: stripes of disparity shards merge to a stripe)
-    c->have_maps = true;
-    c->have_valid = false;   // new maps: a validity mask of an earlier frame does not describe them
+    maps_written(c->res);
     if (copy_maps_out(c, c->maps, lmap, rmap, stride)) return 1;
     if (!c->opt_async) PSM_HIP(c, hipStreamSynchronize(c->stream));
     c->stage_us[PSM_STAGE_DISPSEL] += now_us() - t0;
@@ -318,9 +321,9 @@ int psm_disp_merge_ctx(psm_ctx *root, psm_ctx *const *shards, int nshards, uint8
         const psm_ctx *s = shards[i];
         if (!s || s->W != root->W || s->H != root->H || s->D != root->D || s->dtype != root->dtype)
             return fail(root, "psm_disp_merge_ctx: shard %d does not belong to this job", i);
-        if (!s->have_keys)
+        if (!(s->res.keys[0] && s->res.keys[1]))
             return fail(root, "psm_disp_merge_ctx: shard %d has no partial minima for this frame (call psm_disp_select_partial(ctx, NULL) first)", i);
-        if (s->have_rows != shards[0]->have_rows || (s->have_rows && (s->rows_y0 != shards[0]->rows_y0 || s->rows_y1 != shards[0]->rows_y1)))
+        if (!(s->res.rows == shards[0]->res.rows))
             return fail(root, "psm_disp_merge_ctx: shard %d was filtered under another row stripe than shard 0", i);
         for (int d = s->d0; d < s->d1; d += s->march.dstep) {       // (a strided shard holds d0, d0 + dstep, ...)
             if (covered[d]) return fail(root, "psm_disp_merge_ctx: slice %d is held by more than one shard", d);
@@ -340,23 +343,18 @@ int psm_disp_merge_ctx(psm_ctx *root, psm_ctx *const *shards, int nshards, uint8
     }
     for (int i = 0; i < nshards; ++i) {
         psm_ctx *s = shards[i];
-        // the shard's partial WTA must have finished before its keys are read
-        (void)hipSetDevice(s->device);
-        PSM_HIP(root, hipStreamSynchronize(s->stream));
-        (void)hipSetDevice(root->device);
+        if (sync_other(root, s)) return 1;      // the shard's partial WTA must have finished before its keys are read
         if (gather_leg(root, (char *)root->gather + bytes * i, s, s->keys_cur, bytes)) return 1;
     }
     // the merged maps cover what the shards' minima cover
-    root->have_rows = shards[0]->have_rows;
-    root->rows_y0 = shards[0]->have_rows ? shards[0]->rows_y0 : 0;
-    root->rows_y1 = shards[0]->have_rows ? shards[0]->rows_y1 : root->H;
+    cover(root->res, shards[0]->res.rows);
     return psm_disp_merge(root, root->gather, nshards, lmap, rmap, stride);
 }
 
 int psm_download_maps(psm_ctx *c, uint8_t *lmap, uint8_t *rmap, size_t stride)
 {
     if (!c) return 1;
-    if (!c->have_maps) return fail(c, "psm_download_maps: no disparity maps computed");
+    if (!c->res.maps) return fail(c, "psm_download_maps: no disparity maps computed");
     if (bind(c)) return 1;
     return copy_maps_out(c, c->maps, lmap, rmap, stride);
 }
@@ -367,7 +365,7 @@ int psm_download_maps(psm_ctx *c, uint8_t *lmap, uint8_t *rmap, size_t stride)
 int psm_download_maps_async(psm_ctx *c)
 {
     if (!c) return 1;
-    if (!c->have_maps) return fail(c, "psm_download_maps_async: no disparity maps computed");
+    if (!c->res.maps) return fail(c, "psm_download_maps_async: no disparity maps computed");
     if (bind(c)) return 1;
     const size_t HW = (size_t)c->W * c->H;
     if (!c->copy_stream) PSM_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
@@ -389,19 +387,10 @@ int psm_download_maps_wait(psm_ctx *c, uint8_t *lmap, uint8_t *rmap, size_t stri
 {
     if (!c) return 1;
     if (!c->ev_down || !c->pinned2) return fail(c, "psm_download_maps_wait: no asynchronous download started");
-    if (stride == 0) stride = c->W;
-    if (stride < (size_t)c->W) return fail(c, "map stride %zu < width %d", stride, c->W);
+    if (rows_out(c, stride)) return 1;
     if (bind(c)) return 1;
     PSM_HIP(c, hipEventSynchronize(c->ev_down));
-    const size_t HW = (size_t)c->W * c->H;
-    uint8_t *dst[2] = {lmap, rmap};
-    for (int s = 0; s < 2; ++s) {
-        if (!dst[s]) continue;
-        const uint8_t *src = c->pinned2 + s * HW;
-        if (stride == (size_t)c->W) memcpy(dst[s], src, HW);
-        else for (int y = 0; y < c->H; ++y) memcpy(dst[s] + (size_t)y * stride, src + (size_t)y * c->W, (size_t)c->W);
-    }
-    return 0;
+    return rows_out(c, stride, c->pinned2, lmap, rmap);
 }
 
 }  // extern "C"

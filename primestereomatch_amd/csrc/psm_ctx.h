@@ -10,9 +10,12 @@
 //   psm_api_rectify.cpp video mode: remap + crop of the camera frame into the staged image slot (psm_upload_pair_rectified)
 // Takes the place of the reference's oclUtil + CVC_cl / CVF_cl / DispSel_cl host wrappers
 // (src/oclUtil.cpp, src/CVC_cl.cpp, src/CVF_cl.cpp, src/DispSel_cl.cpp).
+// What a context knows about its volumes and results between calls - psm::VolSide per side, psm::Results - lives in psm_state.h
+// with the only functions that change it.
 #pragma once
 #include "../../include/primesm_hip.h"
 #include "psm_kernels.h"
+#include "psm_state.h"
 
 #include <string>
 #include <utility>
@@ -26,22 +29,12 @@ struct KernelTimer {
     int launches = 0;
 };
 
-}  // namespace psm
-
-namespace psm {
 // psm_share_streams: the contexts of a batch run on ONE main stream and ONE copy stream each way instead of three streams per
 // context (the runtime multiplexes streams onto a few hardware queues; with 8 contexts' 24 streams every asynchronous copy cost
 // 0.2 ms of host time).  Owned jointly: the last context to go destroys the streams.
 struct StreamSet {
     hipStream_t main = nullptr, up = nullptr, down = nullptr;
     int refs = 0;
-};
-
-// A range of image rows [y0, y1); empty (y1 <= y0): no row.
-struct Rows {
-    int y0 = 0, y1 = 0;
-    bool empty() const { return y1 <= y0; }
-    bool covers(Rows need) const { return need.empty() || (y0 <= need.y0 && y1 >= need.y1); }
 };
 }  // namespace psm
 
@@ -84,12 +77,7 @@ struct psm_ctx {
     int gather_staged_legs = 0;         // legs that went through the bounce buffers since the context was created (psm_gather_staged_legs: tests)
     uint8_t *maps = nullptr;            // [2][H][W]: maps_own, or the caller's buffer (psm_set_map_buffer)
     uint8_t *maps_own = nullptr;
-    uint8_t *maps_early = nullptr;      // the map buffer the single-phase filter already filled from its final keys (k_chunk_min), or null
-    // The maps / minima of the current frame cover the rows [rows_y0, rows_y1) only (a psm_set_rows stripe was in force when
-    // psm_cost_filter produced them); have_rows false: whole image.  Recorded at filter time - psm_set_rows itself only
-    // affects the NEXT filter - and cleared by everything that writes whole maps.
-    bool have_rows = false;
-    int rows_y0 = 0, rows_y1 = 0;
+    psm::Results res;                   // which of maps / valid / keys_cur are the current frame's, and for which rows (psm_state.h)
     uint8_t *valid = nullptr;           // [2][H][W]
     uint8_t *pinned = nullptr;          // [2][H][W] page-locked bounce buffer for map / mask downloads (on first use)
     uint8_t *pinned2 = nullptr;         // second bounce buffer: psm_download_maps_async of frame i while frame i-1 is being read
@@ -124,15 +112,9 @@ struct psm_ctx {
     uint8_t *rect_pin = nullptr;
     size_t rect_src_bytes = 0;                   // bytes of one eye in a slot (16-byte multiple) the buffers were allocated for
     uint8_t *p4[2] = {nullptr, nullptr};  // PSM_U8 only: {c0,c1,c2,grad} words
-    // After psm_cost_filter_fgf the filtered volume of a side may stay virtual (fgf_virtual[side] = subsample rate):
-    // it is fully described by the smoothed low-resolution models fgf_mab[side]; the WTA consumes them directly
-    // (upsample + model + argmin in one pass), any other reader of vol[side] materialises it first (materialize()).
-    int fgf_virtual[2] = {0, 0};
-    // After psm_cost_filter (default path) the filtered volume of a side is virtual as well (gf_virtual[side]): the fused
-    // kernel ran in "select" mode - cost build, guided filter and the WTA over the local slices in one pass - and left
-    // the packed per-pixel minima in keys[side].  vol[side] is then untouched (raw_rows[side] still describes the
-    // UNFILTERED volume); any reader of the filtered volume re-runs the filter in "store" mode first (materialize()).
-    bool gf_virtual[2] = {false, false};
+    // What stands for vol[side] (psm_state.h): costs that are a recipe, a filtered volume pending as packed minima or as FGF models.
+    // The WTA consumes either form directly; any other reader makes the volume real first (materialize()).
+    psm::VolSide vside[2];
     // The rows of the planes that are those of the current image pair (empty: none; [0, H): the whole image; a row stripe
     // leaves its own rows behind).  Brought up to date by ensure_planes alone.
     psm::Rows g1_rows;                    // g1 (and the 8-bit planes p4) of both images
@@ -157,14 +139,7 @@ struct psm_ctx {
     void *fgf = nullptr;                // psm_cost_filter_fgf scratch (small planes), fgf_bytes long
     size_t fgf_bytes = 0;
 
-    bool have_images = false, have_cost = false, have_maps = false, have_valid = false;
-    bool have_keys = false;             // keys_cur holds the packed minima of the current frame's local slices (both sides)
-    bool have_keys_side[2] = {false, false};
-    // raw_rows[side]: which rows of the unfiltered cost volume exist in memory.  psm_cost_construct may
-    // leave the volume virtual (RAW_NONE): the fused filter builds the costs on the fly from the g1
-    // planes.  Anything else that reads the volume materialises it first (materialize()).
-    enum { RAW_ALL = 0, RAW_NONE = 1 };
-    int raw_rows[2] = {RAW_ALL, RAW_ALL};
+    bool have_images = false, have_cost = false;
 
     // Domain of the scaled window sums (select forms of the fused kernel carry the 1/64 of both box filters as one 2^-12 at the
     // end: bit-identical to the per-sum scaling only while no intermediate under- or overflows).  8-bit images are always
@@ -242,7 +217,9 @@ int h2d_rows(psm_ctx *c, void *dst, const void *src, size_t row, size_t stride, 
 // the fused kernel touches for it: the guidance of the model rows y0 - 4 .. y1 + 2 (rounded to +- 4), and the image planes of
 // the rows y0 - 8 .. y1 + 7 (the costs of those model rows, +- 4 for their box sums, and their guidance).
 struct PlaneRows { Rows g1, guid; };
-inline Rows whole_image(const psm_ctx *c) { return Rows{0, c->H}; }
+inline Rows whole_image(const psm_ctx *c) { return whole_image(c->H); }
+inline bool stripe_only(const psm_ctx *c) { return !(c->res.rows == whole_image(c)); }   // the current minima / maps cover a row stripe
+inline Rows stripe_rows(const psm_ctx *c) { return c->march.yend > c->march.ybeg ? Rows{c->march.ybeg, c->march.yend} : whole_image(c); }   // psm_set_rows
 inline PlaneRows stripe_planes(const psm_ctx *c)
 {
     const int H = c->H, a = c->march.ybeg, b = c->march.yend;
@@ -287,7 +264,7 @@ unsigned long long *next_pc_stamp(psm_ctx *c);   // slot of the next k_cvf_pc la
 
 // psm_api_rectify.cpp
 void rectify_free(psm_ctx *c, bool maps);        // the source slots and their staging; maps: the device maps too
-// psm_api_select.cpp
+// psm_api_select.cpp: copy_maps_out - two [H][W] planes on the device to the caller's rows
 int copy_maps_out(psm_ctx *c, const uint8_t *dev, uint8_t *lmap, uint8_t *rmap, size_t stride);
 
 }  // namespace psm

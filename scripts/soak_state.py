@@ -1,7 +1,8 @@
 """Randomised soak of the CONTEXT STATE MACHINE (not part of the test suite): one context lives through a random sequence of
 new image pairs, row stripes, tuning flags and readers of intermediate results; after every filter + select the maps of the
 current stripe must equal the oracle's for the current pair.
-    python scripts/soak_state.py [seconds] [seed]"""
+    python scripts/soak_state.py [seconds] [seed]
+    python scripts/soak_state.py --episodes N [seed]     (the same N episodes for a seed on every build: for comparing two)"""
 import os
 import sys
 import time
@@ -25,13 +26,17 @@ def episode(rng, idx):
     dtype = "u8" if rng.random() < 0.25 else "f32"
     pairs = [synth.make_pair(W, H, D, seed=int(rng.integers(0, 1 << 16)))[:2] for _ in range(3)]
     pipe = O.pipeline_u8 if dtype == "u8" else O.pipeline_f32
-    refs = [pipe(l, r, D, threads=8, want_volumes=(dtype == "f32" and D <= 16)) for l, r in pairs]
+    small = D <= 16                              # volumes are held (and compared) for few slices only
+    refs = [pipe(l, r, D, threads=8, want_volumes=(dtype == "f32" and small), want_raw=small) for l, r in pairs]
+    fgf_rates = [s for s in (2, 4, 8) if W // s > 8 // s and H // s > 8 // s] if dtype == "f32" else []
+    fgf_refs = {}
     log = [f"episode {idx}: {W}x{H} D={D} {dtype}"]
     cur, pend = 0, None
     y0, y1 = 0, H
     with P.DispEst(pairs[0][0], pairs[0][1], D, dtype=dtype) as de:
         for step in range(int(rng.integers(4, 12))):
-            op = rng.choice(["frame", "frame", "frame", "images", "images_async", "rows", "flags", "volume", "pp", "frame_async"])
+            op = rng.choice(["frame", "frame", "frame", "images", "images_async", "rows", "flags", "volume", "pp", "frame_async",
+                             "fgf", "upvol", "sides"])
             if op == "images":
                 cur = int(rng.integers(0, 3))
                 pend = None                     # a blocking upload supersedes a staged pair
@@ -58,12 +63,44 @@ def episode(rng, idx):
                 continue
             if pend is not None:                # CostConst adopts the staged pair
                 cur, pend = pend, None
+            ref = refs[cur]
+            if op == "fgf" and fgf_rates and (y0, y1) == (0, H):      # Fast Guided Filter (+ select, + a slice of its volume)
+                s = int(rng.choice(fgf_rates))
+                if (cur, s) not in fgf_refs:
+                    fgf_refs[cur, s] = O.pipeline_fgf(*pairs[cur], D, s=s, threads=8, want_volumes=small)
+                fref = fgf_refs[cur, s]
+                de.setSubsampleRate(s)
+                de.CostConst_GPU(); de.CostFilter_FGF_GPU(); de.DispSelect_GPU()
+                log.append(f"fgf s={s} pair {cur}")
+                if not (np.array_equal(de.lDisMap, fref["ldisp"]) and np.array_equal(de.rDisMap, fref["rdisp"])):
+                    return False, " | ".join(log)
+                if small:
+                    d, side = int(rng.integers(0, D)), int(rng.integers(0, 2))
+                    log.append(f"fgf volume side {side} slice {d}")
+                    if not np.array_equal(de.download_volume(side, d, d + 1)[0], fref["rvol" if side else "lvol"][d]):
+                        return False, " | ".join(log)
+                continue
+            if op == "upvol" and small:         # some slices uploaded over fresh costs: the others must be the real costs
+                side, d0 = int(rng.integers(0, 2)), int(rng.integers(0, D))
+                n = int(rng.integers(1, D - d0 + 1))
+                patch = np.full((n, H, W), 64, np.uint8) if dtype == "u8" else np.full((n, H, W), 0.25, np.float32)
+                de.CostConst_GPU()
+                de.upload_volume(side, patch, d0=d0)
+                log.append(f"upvol pair {cur} side {side} slices {d0}..{d0 + n}")
+                exp = ref["raw_r" if side else "raw_l"].copy()
+                exp[d0:d0 + n] = patch
+                if not (np.array_equal(de.download_volume(side), exp) and
+                        np.array_equal(de.download_volume(1 - side), ref["raw_l" if side else "raw_r"])):
+                    return False, " | ".join(log)
+                continue
             if op == "frame_async":             # maps through psm_download_maps_async / _wait
                 de.CostConst_GPU(); de.CostFilter_GPU(); de.DispSelect_device()
                 de.download_maps_async(); de.download_maps_wait()
+            elif op == "sides" and (y0, y1) == (0, H):      # one side at a time in place of CostFilter_GPU
+                de.CostConst_GPU(); de.CostFilter_side(0); de.CostFilter_side(1); de.DispSelect_GPU()
+                log.append("sides")
             else:
                 de.CostConst_GPU(); de.CostFilter_GPU(); de.DispSelect_GPU()
-            ref = refs[cur]
             log.append(f"frame pair {cur} rows {y0},{y1}")
             if not (np.array_equal(de.lDisMap[y0:y1], ref["ldisp"][y0:y1]) and np.array_equal(de.rDisMap[y0:y1], ref["rdisp"][y0:y1])):
                 return False, " | ".join(log)
@@ -83,12 +120,16 @@ def episode(rng, idx):
 
 
 def main():
-    secs = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    args = sys.argv[1:]
+    episodes = None
+    if args and args[0] == "--episodes":
+        episodes, args = int(args[1]), [0] + args[2:]
+    secs = float(args[0]) if args else 60.0
+    seed = int(args[1]) if len(args) > 1 else 1
     O.build()
     rng = np.random.default_rng(seed)
     t0 = time.time(); n = bad = 0
-    while time.time() - t0 < secs:
+    while (n < episodes) if episodes is not None else (time.time() - t0 < secs):
         try:
             ok, desc = episode(rng, n)
         except Exception as e:

@@ -1,0 +1,53 @@
+// ctx_state_probe.cpp - test infrastructure (tests/test_ctx_state.py): the records of primestereomatch_amd/csrc/psm_state.h and
+// their transitions behind a C ABI for ctypes, built with the host compiler alone - no context, no device.
+#include "../primestereomatch_amd/csrc/psm_state.h"
+
+using namespace psm;
+
+extern "C" {
+
+// One transition of a volume side.  st = {lazy, pending, sub} in and out; returns the answers to the five questions as bits.
+int side_step(int *st, int op, int arg)
+{
+    VolSide v{st[0] != 0, (VolSide::Pending)st[1], st[2]};
+    switch (op) {
+    case 0: new_costs(v, arg != 0); break;
+    case 1: costs_built(v); break;
+    case 2: filtered_to_keys(v); break;
+    case 3: filtered_to_fgf(v, arg); break;
+    case 4: in_memory(v); break;
+    default: break;                       // (the questions of the state as it is)
+    }
+    st[0] = v.lazy; st[1] = v.pending; st[2] = v.sub;
+    return costs_lazy(v) | pending_keys(v) << 1 | (pending_fgf(v) != 0) << 2 | all_real(v) << 3 | fresh_lazy(v) << 4 |
+           (pending_fgf(v) == (v.pending == VolSide::FGF ? v.sub : 0)) << 5;
+}
+
+// One transition of the results.  st = {maps, mask, keys L, keys R, y0, y1, early} in and out, early: 0 = none, n = map buffer n.
+int res_step(int *st, int op, int a, int b, int e)
+{
+    static const uint8_t buf[8] = {};
+    Results r;
+    r.maps = st[0]; r.mask = st[1]; r.keys[0] = st[2]; r.keys[1] = st[3]; r.rows = Rows{st[4], st[5]}; r.early = st[6] ? buf + st[6] : nullptr;
+    int ret = 0;
+    switch (op) {
+    case 0: stale(r); break;
+    case 1: filtered(r, Rows{a, b}, e ? buf + e : nullptr); break;
+    case 2: cover(r, Rows{a, b}); break;
+    case 3: maps_written(r); break;
+    case 4: mask_written(r); break;
+    case 5: ret = take_early(r, buf + e); break;
+    case 6: forget_early(r); break;
+    case 7: maps_gone(r); break;
+    case 8: keys_complete(r, a); break;
+    case 9: keys_gone(r); break;
+    default: r = Results{}; break;        // a new record
+    }
+    st[0] = r.maps; st[1] = r.mask; st[2] = r.keys[0]; st[3] = r.keys[1]; st[4] = r.rows.y0; st[5] = r.rows.y1;
+    st[6] = r.early ? (int)(r.early - buf) : 0;
+    return ret;
+}
+
+int rows_whole(int H, int y0, int y1) { return Rows{y0, y1} == whole_image(H); }
+
+}  // extern "C"

@@ -1,0 +1,111 @@
+"""The two records a context keeps between calls of the C ABI (primestereomatch_amd/csrc/psm_state.h: what stands for a volume
+side, what the current results are) walked without a context or a device: tests/ctx_state_probe.cpp puts their transitions behind
+ctypes and is built here with the host compiler - the header includes nothing of HIP."""
+import ctypes
+import itertools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+NOTHING, KEYS, FGF = 0, 1, 2
+# the five states of a side: (lazy, pending, subsample rate)
+RECIPE, REAL, RECIPE_KEYS, REAL_KEYS, MODELS = (1, NOTHING, 0), (0, NOTHING, 0), (1, KEYS, 0), (0, KEYS, 0), (0, FGF, 4)
+FIVE = [RECIPE, REAL, RECIPE_KEYS, REAL_KEYS, MODELS]
+NEW_COSTS, COSTS_BUILT, TO_KEYS, TO_FGF, TO_MEMORY, ASK = range(6)
+STALE, FILTERED, COVER, MAPS_WRITTEN, MASK_WRITTEN, TAKE_EARLY, FORGET_EARLY, MAPS_GONE, KEYS_COMPLETE, KEYS_GONE, NEW = range(11)
+
+
+@pytest.fixture(scope="module")
+def probe(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("ctx_state") / "ctx_state_probe.so")
+    subprocess.run(["c++", "-std=c++17", "-O1", "-Wall", "-Werror", "-fPIC", "-shared", os.path.join(HERE, "ctx_state_probe.cpp"), "-o", so],
+                   check=True)
+    return ctypes.CDLL(so)
+
+
+def side(probe, state, op, arg=0):
+    st = (ctypes.c_int * 3)(*state)
+    return tuple(st), probe.side_step(st, op, arg), tuple(st)
+
+
+def res(probe, st, op, a=0, b=0, e=0):
+    buf = (ctypes.c_int * 7)(*st)
+    ret = probe.res_step(buf, op, a, b, e)
+    return list(buf), ret
+
+
+def test_side_transitions_stay_inside_the_table(probe):
+    # what each move makes of each state: new costs replace everything; built costs keep what is pending; keys keep whatever the
+    # costs were and replace models; models and memory leave no recipe and nothing else pending
+    want = {
+        (NEW_COSTS, 1): lambda s: RECIPE,
+        (NEW_COSTS, 0): lambda s: REAL,
+        (COSTS_BUILT, 0): lambda s: (0, s[1], s[2]),
+        (TO_KEYS, 0): lambda s: (s[0], KEYS, 0),
+        (TO_FGF, 2): lambda s: (0, FGF, 2),
+        (TO_FGF, 8): lambda s: (0, FGF, 8),
+        (TO_MEMORY, 0): lambda s: REAL,
+    }
+    for state, ((op, arg), f) in itertools.product(FIVE, want.items()):
+        _, q, got = side(probe, state, op, arg)
+        assert got == f(state), (state, op, arg)
+        assert (got[0], got[1], 4 if got[1] == FGF else got[2]) in FIVE, (state, op, arg)     # no sixth state
+        lazy, keys, fgf, real, fresh = (bool(q >> i & 1) for i in range(5))
+        assert not (keys and fgf)                                  # keys and models are never pending together
+        assert (lazy, keys, fgf) == (bool(got[0]), got[1] == KEYS, got[1] == FGF) and q >> 5 & 1
+        assert real == (got == REAL) and fresh == (got == RECIPE)
+        assert not (fgf and lazy)                                  # models stand for the volume: nothing of it is a recipe
+    assert side(probe, (0, NOTHING, 0), ASK)[2] == REAL            # (what VolSide{} and a new image pair give)
+
+
+def test_results_mask_rows_and_early_map(probe):
+    H = 60
+    new, _ = res(probe, [0] * 7, NEW)
+    assert new == [0, 0, 0, 0, 0, 0, 0]
+    # a mask never outlives its maps, whatever happens in whatever order
+    rng = np.random.default_rng(3)
+    st = new
+    for _ in range(4000):
+        op = int(rng.integers(0, 10))
+        y0 = int(rng.integers(0, H)); y1 = int(rng.integers(y0 + 1, H + 1))
+        before = st
+        st, ret = res(probe, st, op, y0 if op != KEYS_COMPLETE else int(rng.integers(0, 2)), y1, int(rng.integers(0, 3)))
+        assert not (st[1] and not st[0]), (op, st)
+        if op == MAPS_WRITTEN:
+            assert st[:2] == [1, 0]                                # new maps: the old mask does not describe them
+        if op in (STALE, FILTERED, MAPS_GONE):
+            assert st[:2] == [0, 0]
+        if op == MASK_WRITTEN:
+            assert st[1] == before[0]
+        if op in (STALE, FORGET_EARLY, TAKE_EARLY):
+            assert st[6] == 0
+        if op not in (FILTERED, COVER):
+            assert st[4:6] == before[4:6]                          # only a filter and `cover` say which rows
+        if op not in (KEYS_COMPLETE, KEYS_GONE):
+            assert st[2:4] == before[2:4]
+    # maps written for the whole image after a stripe
+    st, _ = res(probe, new, FILTERED, 20, 40, 1)
+    assert st[4:6] == [20, 40] and not probe.rows_whole(H, *st[4:6])
+    st, _ = res(probe, st, COVER, 0, H)
+    st, _ = res(probe, st, MAPS_WRITTEN)
+    assert st[:2] == [1, 0] and st[4:6] == [0, H] and probe.rows_whole(H, *st[4:6])
+    # the early map: recorded by the filter call whose reduction filled it, taken once, and only for that buffer
+    st, _ = res(probe, new, FILTERED, 0, H, 1)
+    assert st[6] == 1
+    st, hit = res(probe, st, TAKE_EARLY, e=1)
+    assert hit == 1 and st[6] == 0
+    assert res(probe, st, TAKE_EARLY, e=1)[1] == 0                 # once
+    st, _ = res(probe, new, FILTERED, 0, H, 1)
+    assert res(probe, st, TAKE_EARLY, e=2) == (st[:6] + [0], 0)    # another buffer: no hit, and forgotten
+    for op, args in ((STALE, ()), (FILTERED, (0, H, 0)), (FORGET_EARLY, ())):      # a later filter without one, new costs, an upload
+        assert res(probe, st, op, *args)[0][6] == 0
+    for op in (MAPS_WRITTEN, MASK_WRITTEN, COVER, KEYS_COMPLETE, KEYS_GONE, MAPS_GONE):
+        assert res(probe, st, op, 0, H)[0][6] == 1                 # (nothing else touches it)
+    # keys: per side, gone together
+    st, _ = res(probe, new, KEYS_COMPLETE, 1)
+    assert st[2:4] == [0, 1]
+    st, _ = res(probe, st, KEYS_COMPLETE, 0)
+    assert st[2:4] == [1, 1] and res(probe, st, KEYS_GONE)[0][2:4] == [0, 0]
