@@ -279,6 +279,46 @@ int psm_upload_pair_rectified_async(psm_ctx *ctx, const void *l, const void *r, 
  * psm_cost_construct.  Float pairs are refused. */
 int psm_download_images(psm_ctx *ctx, uint8_t *l, uint8_t *r, size_t stride_bytes);
 
+/* ---- semi-global matching: the reference's second algorithm, the STEREO_SGBM branch of StereoMatch::compute
+ * (ssgbm->compute(lFrame, rFrame, imgDisparity16S), src/StereoMatch.cpp:169-187) with the configuration of setupOpenCVSGBM
+ * (:639-660): minDisparity 0, numDisparities = the context's max_disp (any value in [2, 256]), blockSize 5, P1 = 8 ch bs^2,
+ * P2 = 32 ch bs^2, disp12MaxDiff 1, uniquenessRatio 10, eight paths (MODE_HH).  All integer; the definition (DESIGN.md section 10,
+ * tests/sgm_model.py) is Hirschmueller's recurrence under OpenCV's parameter names, and the device equals it element for element:
+ *   pixel cost  c(x,y,d) = sum_ch |L[y][x][ch] - R[y][max(x-d, 0)][ch]|
+ *   block cost  C = the bs x bs box sum of c(.,.,d), the plane replicated at the image edge (u16)
+ *   paths       L_r(p,d) = C(p,d) + min(L_r(p-r,d), L_r(p-r,d-1)+P1, L_r(p-r,d+1)+P1, m+P2) - m, m = min_k L_r(p-r,k); L_r = C where
+ *               p-r is outside; r = (dy,dx) in (0,+-1), (+-1,0), (+-1,+-1); S = sum_r L_r (u32, exact)
+ *   select      best = argmin_d S (lowest d on ties); not unique if some d, |d-best| > 1, has S(d)(100-u) < minS 100;
+ *               0 < best < D-1: den = max(S(best-1)+S(best+1)-2 minS, 1), d16 = 16 best + floor(((S(best-1)-S(best+1)) 16 + den) / (2 den))
+ *   consistency disp2[y][x-best] = best of the smallest (minS, best) among the unique pixels landing there; with m >= 0 a pixel is
+ *               rejected if the probes (x-da, da), da = d16 >> 4, and (x-db, db), db = (d16+15) >> 4, both find a disp2 that
+ *               differs from the probe's disparity by more than m
+ *   output      int16, d16 (disparity * 16) or -16 where not unique or rejected (OpenCV's (minDisparity - 1) * 16)
+ * A float pair (PSM_IMG_F32) is quantised as lFrame.convertTo(lFrame, CV_8U, 255) does (:174-177): saturate(rint(f * 255.0f)).
+ * OPEN, not part of this stage: the speckle filter (speckleWindowSize 100, speckleRange 32) and OpenCV's Sobel-prefiltered
+ * Birchfield-Tomasi pixel cost (preFilterCap 63) - the pixel cost here is plain SAD; agreement with a live cv::StereoSGBM is not
+ * pinned (neither OpenCV nor its source was available).
+ *
+ * psm_sgm_set_params: block_size in {1, 3, 5, 7}; 0 < P1 <= P2; block_size^2 * channels * 255 + P2 <= 65535; uniqueness_ratio in
+ * [0, 100); disp12_max_diff < 0 turns the consistency test off.  0 for any of the first three: the default above. */
+int psm_sgm_set_params(psm_ctx *ctx, int block_size, int p1, int p2, int uniqueness_ratio, int disp12_max_diff);
+/* Runs the stage on the context's stream over the pair psm_upload_pair* staged (either depth); synchronous on return unless
+ * PSM_OPT_ASYNC.  An independent stage: it reads the staged images only and writes its own buffers - 6 * W * H * Dp bytes of
+ * volumes (Dp = max_disp rounded up to 4) and 8 * W * H of planes, allocated on first use, reused from frame to frame, given back
+ * by psm_release_scratch and psm_destroy.  Volumes, maps, masks and minima of the other entry points are untouched: it may be
+ * called anywhere between them.  Refused on disparity shards, under a row stripe, and when nothing has been uploaded. */
+int psm_sgm_compute(psm_ctx *ctx);
+/* The same for a 1-channel 8-bit pair (CV_8UC1 frames): H rows of W bytes, pitch stride_bytes (0: packed).  The pair is copied to
+ * buffers of the stage and used by this call only (the caller's memory is free on return); the staged colour pair is untouched. */
+int psm_sgm_compute_gray(psm_ctx *ctx, const uint8_t *l, const uint8_t *r, size_t stride_bytes);
+/* The left map of the last compute (imgDisparity16S): H rows of W int16, pitch stride_bytes (0: packed).  Synchronises. */
+int psm_sgm_download_disparity(psm_ctx *ctx, int16_t *disp, size_t stride_bytes);
+/* Test hook: the volumes of the last compute as dense host arrays [H][W][max_disp] - which 0: C as uint16, 1: S as uint32. */
+int psm_sgm_download_costs(psm_ctx *ctx, int which, void *host);
+/* With PSM_OPT_PROFILE set during the last compute: device time in ms of its block-cost launch, its eight path launches and its
+ * select + check launches (a getter of its own: the PSM_K_* and PSM_STAGE_* tables stay as they are). */
+int psm_sgm_times(psm_ctx *ctx, double ms[3]);
+
 /* "next" row: PP lrCheck on the device (src/PP.cpp:17-50) on the maps of the last
  * psm_disp_select/psm_disp_merge.  lvalid/rvalid: H x W bytes (0/1), pitch `stride`; either
  * may be NULL (results stay on the device). */

@@ -89,6 +89,12 @@ SYMBOLS = [
     ("psm_upload_pair_rectified", _i, [_vp, _vp, _vp, _i, _sz]),
     ("psm_upload_pair_rectified_async", _i, [_vp, _vp, _vp, _i, _sz]),
     ("psm_download_images", _i, [_vp, _vp, _vp, _sz]),
+    ("psm_sgm_set_params", _i, [_vp, _i, _i, _i, _i, _i]),
+    ("psm_sgm_compute", _i, [_vp]),
+    ("psm_sgm_compute_gray", _i, [_vp, _vp, _vp, _sz]),
+    ("psm_sgm_download_disparity", _i, [_vp, _vp, _sz]),
+    ("psm_sgm_download_costs", _i, [_vp, _i, _vp]),
+    ("psm_sgm_times", _i, [_vp, _pd]),
 ]
 
 _lib = None

@@ -106,6 +106,7 @@ void free_all(psm_ctx *c)
         (void)hipFree(c->p4[s]);
     }
     rectify_free(c, true);
+    sgm_free(c);
     (void)hipFree(c->fvol);
     (void)hipFree(c->spare);
     (void)hipFree(c->ab);
@@ -421,6 +422,7 @@ int psm_release_scratch(psm_ctx *c)
     (void)hipFree(c->gather); c->gather = nullptr; c->gather_ranks = 0;
     (void)hipFree(c->fvol); c->fvol = nullptr;
     rectify_free(c, false);
+    sgm_free(c);
     for (int k = 0; k < 2; ++k)
         if (c->xfer_pin[k]) { (void)hipHostFree(c->xfer_pin[k]); c->xfer_pin[k] = nullptr; c->xfer_pin_bytes[k] = 0; }
     (void)hipGetLastError();

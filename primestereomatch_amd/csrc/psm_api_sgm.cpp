@@ -1,0 +1,196 @@
+// psm_api_sgm.cpp - semi-global matching behind the C ABI: the STEREO_SGBM branch of StereoMatch::compute (ssgbm->compute(lFrame,
+// rFrame, imgDisparity16S), src/StereoMatch.cpp:169-187) with the parameters of setupOpenCVSGBM (:639-660), on the device
+// (psm_sgm.hip).  An independent stage: it reads the staged images and writes its own buffers (psm::SgmState) - volumes, maps,
+// masks, keys and the records of psm_state.h never see it.  The definition is tests/sgm_model.py / DESIGN.md 10; open there and
+// here: the speckle filter and OpenCV's prefiltered Birchfield-Tomasi cost.
+#include "psm_ctx.h"
+
+#include <cstring>
+
+using namespace psm;
+
+namespace psm {
+
+void sgm_free(psm_ctx *c)
+{
+    SgmState &g = c->sgm;
+    (void)hipFree(g.C); g.C = nullptr;
+    (void)hipFree(g.S); g.S = nullptr;
+    (void)hipFree(g.disp2); g.disp2 = nullptr;
+    (void)hipFree(g.pre); g.pre = nullptr;
+    (void)hipFree(g.out); g.out = nullptr;
+    for (uint8_t *&p : g.gray) { (void)hipFree(p); p = nullptr; }
+    for (hipEvent_t &e : g.ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    g.have = g.timed = false;
+}
+
+}  // namespace psm
+
+namespace {
+
+inline int sgm_dp(const psm_ctx *c) { return (c->D + 3) & ~3; }
+
+// the conditions on the parameters for a pair of `ch` channels; *p1 / *p2: 0 resolved to the default
+int check_params(psm_ctx *c, const char *who, int ch, int bs, int *p1, int *p2, int u)
+{
+    if (bs != 1 && bs != 3 && bs != 5 && bs != 7) return fail(c, "%s: block_size %d not in {1, 3, 5, 7}", who, bs);
+    if (*p1 < 0 || *p2 < 0) return fail(c, "%s: P1 %d, P2 %d: 0 < P1 <= P2 required (0: the default)", who, *p1, *p2);
+    if (*p1 == 0) *p1 = 8 * ch * bs * bs;
+    if (*p2 == 0) *p2 = 32 * ch * bs * bs;
+    if (*p1 > *p2) return fail(c, "%s: P1 %d > P2 %d (0 < P1 <= P2 required)", who, *p1, *p2);
+    if ((long long)bs * bs * ch * 255 + *p2 > 65535)
+        return fail(c, "%s: block_size^2 * channels * 255 + P2 = %lld > 65535 (a path cost must fit 16 bits)", who, (long long)bs * bs * ch * 255 + *p2);
+    if (u < 0 || u >= 100) return fail(c, "%s: uniqueness_ratio %d outside [0, 100)", who, u);
+    return 0;
+}
+
+int check_ctx(psm_ctx *c, const char *who)
+{
+    if (c->Dloc != c->D || strided(c)) return fail(c, "%s: a disparity shard holds part of the range (the paths need every disparity of a pixel)", who);
+    if (c->march.yend > c->march.ybeg) return fail(c, "%s: a row stripe is in force (psm_set_rows): the paths cross the whole image", who);
+    if (c->D < 2) return fail(c, "%s: max_disp %d < 2", who, c->D);
+    return 0;
+}
+
+int ensure_buffers(psm_ctx *c)
+{
+    SgmState &g = c->sgm;
+    const size_t HW = (size_t)c->W * c->H, V = HW * sgm_dp(c);
+    if (!g.C) PSM_HIP(c, hipMalloc((void **)&g.C, V * sizeof(uint16_t)));
+    if (!g.S) PSM_HIP(c, hipMalloc((void **)&g.S, V * sizeof(uint32_t)));
+    if (!g.disp2) PSM_HIP(c, hipMalloc((void **)&g.disp2, HW * sizeof(uint32_t)));
+    if (!g.pre) PSM_HIP(c, hipMalloc((void **)&g.pre, HW * sizeof(int16_t)));
+    if (!g.out) PSM_HIP(c, hipMalloc((void **)&g.out, HW * sizeof(int16_t)));
+    if (c->opt_profile)
+        for (hipEvent_t &e : g.ev)
+            if (!e) PSM_HIP(c, hipEventCreate(&e));
+    return 0;
+}
+
+// cost, the eight directions, select + check on the context's stream
+int enqueue(psm_ctx *c, const char *who, const void *l, const void *r, int depth, int ch)
+{
+    SgmState &g = c->sgm;
+    int p1 = g.p1, p2 = g.p2;
+    if (check_params(c, who, ch, g.bs, &p1, &p2, g.u)) return 1;
+    if (ensure_buffers(c)) return 1;
+    SgmArgs a;
+    a.img[0] = l; a.img[1] = r; a.depth = depth; a.ch = ch;
+    a.C = g.C; a.S = g.S; a.disp2 = g.disp2; a.pre = g.pre; a.out = g.out;
+    a.W = c->W; a.H = c->H; a.D = c->D; a.Dp = sgm_dp(c);
+    a.bs = g.bs; a.P1 = p1; a.P2 = p2; a.u = g.u; a.m = g.m;
+    const bool timed = c->opt_profile != 0;
+    g.have = g.timed = false;
+    // disp2 starts every frame as "nothing lands here", on the stream
+    PSM_HIP(c, hipMemsetAsync(g.disp2, 0xff, (size_t)c->W * c->H * sizeof(uint32_t), c->stream));
+    if (timed) PSM_HIP(c, hipEventRecord(g.ev[0], c->stream));
+    launch_sgm_cost(c->stream, a);
+    if (check_launch(c, "k_sgm_cost")) return 1;
+    if (timed) PSM_HIP(c, hipEventRecord(g.ev[1], c->stream));
+    for (int i = 0; i < 8; ++i) launch_sgm_path(c->stream, a, SGM_DIRS[i][0], SGM_DIRS[i][1], i == 0);
+    if (check_launch(c, "k_sgm_path")) return 1;
+    if (timed) PSM_HIP(c, hipEventRecord(g.ev[2], c->stream));
+    launch_sgm_select(c->stream, a);
+    if (check_launch(c, "k_sgm_select")) return 1;
+    if (timed) PSM_HIP(c, hipEventRecord(g.ev[3], c->stream));
+    g.have = true;
+    g.timed = timed;
+    if (!c->opt_async) PSM_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int psm_sgm_set_params(psm_ctx *c, int block_size, int p1, int p2, int uniqueness_ratio, int disp12_max_diff)
+{
+    if (!c) return 1;
+    const int bs = block_size ? block_size : 5;
+    int q1 = p1, q2 = p2;
+    if (check_params(c, "psm_sgm_set_params", 3, bs, &q1, &q2, uniqueness_ratio)) return 1;      // (the staged pair has 3 channels)
+    SgmState &g = c->sgm;
+    g.bs = bs; g.p1 = p1; g.p2 = p2; g.u = uniqueness_ratio; g.m = disp12_max_diff;
+    return 0;
+}
+
+int psm_sgm_compute(psm_ctx *c)
+{
+    if (!c) return 1;
+    if (check_ctx(c, "psm_sgm_compute")) return 1;
+    if (c->raw_depth < 0) return fail(c, "psm_sgm_compute: no image pair (psm_upload_pair)");
+    if (bind(c)) return 1;
+    return enqueue(c, "psm_sgm_compute", c->raw[0], c->raw[1], c->raw_depth, 3);
+}
+
+int psm_sgm_compute_gray(psm_ctx *c, const uint8_t *l, const uint8_t *r, size_t stride_bytes)
+{
+    if (!c) return 1;
+    if (check_ctx(c, "psm_sgm_compute_gray")) return 1;
+    if (!l || !r) return fail(c, "psm_sgm_compute_gray: NULL image");
+    const size_t row = (size_t)c->W;
+    if (stride_bytes == 0) stride_bytes = row;
+    if (stride_bytes < row) return fail(c, "psm_sgm_compute_gray: stride %zu < row size %zu", stride_bytes, row);
+    if (bind(c)) return 1;
+    SgmState &g = c->sgm;
+    const uint8_t *src[2] = {l, r};
+    for (int s = 0; s < 2; ++s) {
+        if (!g.gray[s]) PSM_HIP(c, hipMalloc((void **)&g.gray[s], row * c->H));
+        if (h2d_rows(c, g.gray[s], src[s], row, stride_bytes, c->H)) return 1;
+    }
+    PSM_HIP(c, hipStreamSynchronize(c->stream));      // the copy reads caller memory (psm_upload_pair)
+    return enqueue(c, "psm_sgm_compute_gray", g.gray[0], g.gray[1], PSM_IMG_U8, 1);
+}
+
+int psm_sgm_download_disparity(psm_ctx *c, int16_t *disp, size_t stride_bytes)
+{
+    if (!c) return 1;
+    if (!disp) return fail(c, "psm_sgm_download_disparity: NULL map");
+    if (!c->sgm.have) return fail(c, "psm_sgm_download_disparity: no result (psm_sgm_compute)");
+    const size_t row = (size_t)c->W * sizeof(int16_t);
+    if (stride_bytes == 0) stride_bytes = row;
+    if (stride_bytes < row) return fail(c, "psm_sgm_download_disparity: stride %zu < row size %zu", stride_bytes, row);
+    if (bind(c)) return 1;
+    if (stride_bytes == row) {
+        PSM_HIP(c, hipMemcpyAsync(disp, c->sgm.out, row * c->H, hipMemcpyDeviceToHost, c->stream));
+        PSM_HIP(c, hipStreamSynchronize(c->stream));
+    } else {
+        std::vector<int16_t> packed((size_t)c->W * c->H);
+        PSM_HIP(c, hipMemcpyAsync(packed.data(), c->sgm.out, row * c->H, hipMemcpyDeviceToHost, c->stream));
+        PSM_HIP(c, hipStreamSynchronize(c->stream));
+        for (int y = 0; y < c->H; ++y) memcpy((uint8_t *)disp + (size_t)y * stride_bytes, packed.data() + (size_t)y * c->W, row);
+    }
+    return 0;
+}
+
+int psm_sgm_download_costs(psm_ctx *c, int which, void *host)
+{
+    if (!c) return 1;
+    if (!host) return fail(c, "psm_sgm_download_costs: NULL buffer");
+    if (which != 0 && which != 1) return fail(c, "psm_sgm_download_costs: which %d (0: C as u16, 1: S as u32)", which);
+    if (!c->sgm.have) return fail(c, "psm_sgm_download_costs: no result (psm_sgm_compute)");
+    if (bind(c)) return 1;
+    const size_t HW = (size_t)c->W * c->H, Dp = sgm_dp(c), D = c->D, el = which ? sizeof(uint32_t) : sizeof(uint16_t);
+    std::vector<uint8_t> dev(HW * Dp * el);
+    PSM_HIP(c, hipMemcpyAsync(dev.data(), which ? (const void *)c->sgm.S : (const void *)c->sgm.C, dev.size(), hipMemcpyDeviceToHost, c->stream));
+    PSM_HIP(c, hipStreamSynchronize(c->stream));
+    for (size_t p = 0; p < HW; ++p) memcpy((uint8_t *)host + p * D * el, dev.data() + p * Dp * el, D * el);      // the host layout has no padding
+    return 0;
+}
+
+int psm_sgm_times(psm_ctx *c, double ms[3])
+{
+    if (!c) return 1;
+    if (!ms) return fail(c, "psm_sgm_times: NULL array");
+    if (!c->sgm.have || !c->sgm.timed) return fail(c, "psm_sgm_times: the last psm_sgm_compute was not timed (PSM_OPT_PROFILE)");
+    if (bind(c)) return 1;
+    PSM_HIP(c, hipEventSynchronize(c->sgm.ev[3]));
+    for (int i = 0; i < 3; ++i) {
+        float t = 0.f;
+        PSM_HIP(c, hipEventElapsedTime(&t, c->sgm.ev[i], c->sgm.ev[i + 1]));
+        ms[i] = t;
+    }
+    return 0;
+}
+
+}  // extern "C"

@@ -8,6 +8,7 @@
 //   psm_api_batch.cpp   several Middlebury-size pairs per launch (psm_compute_batch)
 //   psm_api_jwmf.cpp    JointWMF: the joint weighted median of the reference's live post-filter (psm_joint_wmf)
 //   psm_api_rectify.cpp video mode: remap + crop of the camera frame into the staged image slot (psm_upload_pair_rectified)
+//   psm_api_sgm.cpp     semi-global matching over the staged pair, the reference's STEREO_SGBM branch (psm_sgm_compute)
 // Takes the place of the reference's oclUtil + CVC_cl / CVF_cl / DispSel_cl host wrappers
 // (src/oclUtil.cpp, src/CVC_cl.cpp, src/CVF_cl.cpp, src/DispSel_cl.cpp).
 // What a context knows about its volumes and results between calls - psm::VolSide per side, psm::Results - lives in psm_state.h
@@ -35,6 +36,20 @@ struct KernelTimer {
 struct StreamSet {
     hipStream_t main = nullptr, up = nullptr, down = nullptr;
     int refs = 0;
+};
+
+// psm_sgm_compute (psm_api_sgm.cpp): parameters, the stage's own device buffers (allocated on first use, reused from frame to
+// frame) and the events of psm_sgm_times.  Nothing else in the context reads or writes any of it.
+struct SgmState {
+    int bs = 5, p1 = 0, p2 = 0, u = 10, m = 1;     // p1 / p2 0: the default for the pair's channel count
+    uint16_t *C = nullptr;
+    uint32_t *S = nullptr;
+    uint32_t *disp2 = nullptr;
+    int16_t *pre = nullptr, *out = nullptr;
+    uint8_t *gray[2] = {nullptr, nullptr};         // psm_sgm_compute_gray: its 1-channel pair
+    bool have = false;                             // a map and volumes of a compute exist
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool timed = false;                            // ... and its launches were bracketed (PSM_OPT_PROFILE)
 };
 }  // namespace psm
 
@@ -111,6 +126,7 @@ struct psm_ctx {
     uint8_t *rect_src[2] = {nullptr, nullptr};
     uint8_t *rect_pin = nullptr;
     size_t rect_src_bytes = 0;                   // bytes of one eye in a slot (16-byte multiple) the buffers were allocated for
+    psm::SgmState sgm;
     uint8_t *p4[2] = {nullptr, nullptr};  // PSM_U8 only: {c0,c1,c2,grad} words
     // What stands for vol[side] (psm_state.h): costs that are a recipe, a filtered volume pending as packed minima or as FGF models.
     // The WTA consumes either form directly; any other reader makes the volume real first (materialize()).
@@ -264,6 +280,8 @@ unsigned long long *next_pc_stamp(psm_ctx *c);   // slot of the next k_cvf_pc la
 
 // psm_api_rectify.cpp
 void rectify_free(psm_ctx *c, bool maps);        // the source slots and their staging; maps: the device maps too
+// psm_api_sgm.cpp
+void sgm_free(psm_ctx *c);                       // the stage's buffers and events (its parameters stay)
 // psm_api_select.cpp: copy_maps_out - two [H][W] planes on the device to the caller's rows
 int copy_maps_out(psm_ctx *c, const uint8_t *dev, uint8_t *lmap, uint8_t *rmap, size_t stride);
 

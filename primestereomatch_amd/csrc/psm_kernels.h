@@ -217,4 +217,20 @@ struct RectArgs {
 };
 void launch_rectify(hipStream_t s, const RectArgs &a);
 
+// psm_sgm.hip: semi-global matching over the staged pair (psm_sgm_compute, psm_api_sgm.cpp)
+struct SgmArgs {
+    const void *img[2];                // staged images: interleaved `ch` channels, PSM_IMG_U8 bytes or PSM_IMG_F32 floats
+    int depth, ch;
+    uint16_t *C;                       // block costs [H][W][Dp]
+    uint32_t *S;                       // summed path costs [H][W][Dp]
+    uint32_t *disp2;                   // [H][W] packed minima (minS << 8 | best) landing on the right image's pixel; all ones: none
+    int16_t *pre, *out;                // [H][W] d16 (or -16: not unique) before the consistency test / the final map
+    int W, H, D, Dp;                   // Dp: elements per pixel, D rounded up to a multiple of 4
+    int bs, P1, P2, u, m;
+};
+constexpr int SGM_DIRS[8][2] = {{0, 1}, {0, -1}, {1, 0}, {-1, 0}, {1, 1}, {1, -1}, {-1, 1}, {-1, -1}};   // (dy, dx)
+void launch_sgm_cost(hipStream_t s, const SgmArgs &a);
+void launch_sgm_path(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first);     // S = L_r (first) or S += L_r
+void launch_sgm_select(hipStream_t s, const SgmArgs &a);                               // k_sgm_select + k_sgm_check (disp2 all ones before)
+
 }  // namespace psm

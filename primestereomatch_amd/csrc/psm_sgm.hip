@@ -1,0 +1,314 @@
+// psm_sgm.hip - semi-global matching, the reference's second algorithm (STEREO_SGBM: ssgbm->compute, src/StereoMatch.cpp:169-187,
+// configured by setupOpenCVSGBM, :639-660) as four kernels over the staged 8-bit pair.  All arithmetic is integer; the definition
+// is tests/sgm_model.py, the device equals it element for element:
+//   k_sgm_cost    C(x,y,d) = sum over the bs x bs block (replicated edge) of sum_ch |L[y][x] - R[y][max(x-d,0)]|        u16 [y][x][d]
+//   k_sgm_path    one scan direction r: L_r(p,d) = C(p,d) + min(L_r(p-r,d), L_r(p-r,d+-1)+P1, m+P2) - m, m = min_k L_r(p-r,k);
+//                 S += L_r (the first direction stores)                                                                   u32 [y][x][d]
+//   k_sgm_select  argmin_d S (lowest d), uniqueness, sub-pixel d16, disp2[y][x-best] = min (minS << 8 | best)
+//   k_sgm_check   the disp12MaxDiff test of every pixel against disp2 of its row -> int16 map, -16 where invalid
+// d is innermost in both volumes (Dp = D rounded up to 4 elements per pixel): the disparities of a pixel are one contiguous read
+// whatever the walking direction.  Not here, and open: the speckle filter and the Sobel-prefiltered Birchfield-Tomasi cost.
+#include "psm_kernels.h"
+
+#include <type_traits>
+
+namespace psm {
+
+constexpr int SGM_INF = 1 << 28;
+constexpr int SGM_TX = 32;         // k_sgm_cost: output pixels of a row per workgroup
+constexpr int SGM_U = 8;           // k_sgm_path: steps whose loads are issued together, ahead of the dependent chain
+
+// DPP moves with `old` for the lanes that have no source (bound_ctrl off): row_shr:n 0x110 + n, wave_shl:1 0x130 (lane l <- l + 1),
+// wave_shr:1 0x138 (lane l <- l - 1)
+template <int CTRL>
+__device__ __forceinline__ int sgm_dpp(int old, int v) { return __builtin_amdgcn_update_dpp(old, v, CTRL, 0xf, 0xf, false); }
+
+// minimum over the wave, in every lane: four row_shr steps leave a row's minimum in its lane 15, the four rows meet in SGPRs
+__device__ __forceinline__ int sgm_wave_min(int v)
+{
+    v = min(v, sgm_dpp<0x111>(0x7fffffff, v));
+    v = min(v, sgm_dpp<0x112>(0x7fffffff, v));
+    v = min(v, sgm_dpp<0x114>(0x7fffffff, v));
+    v = min(v, sgm_dpp<0x118>(0x7fffffff, v));
+    return min(min(__builtin_amdgcn_readlane(v, 15), __builtin_amdgcn_readlane(v, 31)),
+               min(__builtin_amdgcn_readlane(v, 47), __builtin_amdgcn_readlane(v, 63)));
+}
+
+// one pixel of a staged image as a dword of `ch` bytes (depth 0: bytes, PSM_IMG_U8); float images are quantised as lFrame.convertTo(lFrame, CV_8U, 255) does
+// (src/StereoMatch.cpp:174-177): saturate(rint(f * 255.0f)), ties to even
+__device__ __forceinline__ unsigned sgm_px(const void *img, int depth, int ch, size_t idx)
+{
+    unsigned v = 0;
+    for (int k = 0; k < ch; ++k) {
+        unsigned b;
+        if (depth == 0) b = ((const uint8_t *)img)[idx * ch + k];
+        else b = (unsigned)fminf(fmaxf(rintf(__fmul_rn(((const float *)img)[idx * ch + k], 255.0f)), 0.0f), 255.0f);
+        v |= b << (8 * k);
+    }
+    return v;
+}
+
+__device__ __forceinline__ int sgm_clamp(int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); }
+
+// One workgroup per SGM_TX pixels of one row, one thread per disparity.  The BS rows of both images the block needs go to LDS as
+// one dword per pixel (v_sad_u8 then takes the 1 or 3 channels of a tap in one instruction); a thread walks x with its d fixed:
+// the left tap is a broadcast, the right taps of neighbouring lanes are neighbouring dwords, the stores of a wave are 128
+// contiguous bytes.  Column sums of the last BS columns stay in registers.
+template <int BS>
+__global__ __launch_bounds__(256) void k_sgm_cost(SgmArgs a)
+{
+    constexpr int HALF = BS / 2, NL = SGM_TX + BS - 1, NR = NL + 255;
+    __shared__ unsigned sl[BS][NL], sr[BS][NR];
+    const int y = blockIdx.y, x0 = blockIdx.x * SGM_TX, d = threadIdx.x;
+    const int cx_min = sgm_clamp(x0 - HALF, a.W);
+    const int rbase = cx_min - (a.D - 1);                 // image column of sr[.][0]
+    const int nr = NL + a.D - 1;
+    for (int i = threadIdx.x; i < BS * NL; i += blockDim.x) {
+        const int j = i / NL, s = i - j * NL;
+        sl[j][s] = sgm_px(a.img[0], a.depth, a.ch, (size_t)sgm_clamp(y + j - HALF, a.H) * a.W + sgm_clamp(x0 - HALF + s, a.W));
+    }
+    for (int i = threadIdx.x; i < BS * nr; i += blockDim.x) {
+        const int j = i / nr, k = i - j * nr;
+        sr[j][k] = sgm_px(a.img[1], a.depth, a.ch, (size_t)sgm_clamp(y + j - HALF, a.H) * a.W + sgm_clamp(rbase + k, a.W));
+    }
+    __syncthreads();
+    if (d >= a.Dp) return;
+    const bool real = d < a.D;
+    unsigned v[BS];
+#pragma unroll
+    for (int i = 0; i < BS; ++i) v[i] = 0;
+    for (int s = 0; s < NL; ++s) {
+        const int cx = sgm_clamp(x0 - HALF + s, a.W);
+        const int k = max(cx - (real ? d : 0), 0) - rbase;
+        unsigned col = 0;
+#pragma unroll
+        for (int j = 0; j < BS; ++j) col = __builtin_amdgcn_sad_u8(sl[j][s], sr[j][k], col);
+#pragma unroll
+        for (int i = 0; i + 1 < BS; ++i) v[i] = v[i + 1];
+        v[BS - 1] = col;
+        const int x = x0 + s - (BS - 1);
+        if (s >= BS - 1 && x < a.W) {
+            unsigned sum = 0;
+#pragma unroll
+            for (int i = 0; i < BS; ++i) sum += v[i];
+            a.C[((size_t)y * a.W + x) * a.Dp + d] = (uint16_t)(real ? sum : 0u);
+        }
+    }
+}
+
+// NV adjacent disparities per lane: what a lane moves per pixel
+template <int NV> struct SgmVec;
+template <> struct SgmVec<1> { using C = unsigned short; using S = unsigned; };
+template <> struct SgmVec<2> { using C = unsigned; using S = uint2; };
+template <> struct SgmVec<4> { using C = uint2; using S = uint4; };
+__device__ __forceinline__ void sgm_unpack(unsigned short v, int *o) { o[0] = v; }
+__device__ __forceinline__ void sgm_unpack(unsigned v, int *o) { o[0] = v & 0xffffu; o[1] = v >> 16; }
+__device__ __forceinline__ void sgm_unpack(uint2 v, int *o) { o[0] = v.x & 0xffffu; o[1] = v.x >> 16; o[2] = v.y & 0xffffu; o[3] = v.y >> 16; }
+__device__ __forceinline__ void sgm_unpack_s(unsigned v, unsigned *o) { o[0] = v; }
+__device__ __forceinline__ void sgm_unpack_s(uint2 v, unsigned *o) { o[0] = v.x; o[1] = v.y; }
+__device__ __forceinline__ void sgm_unpack_s(uint4 v, unsigned *o) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
+__device__ __forceinline__ void sgm_pack_s(const unsigned *o, unsigned &v) { v = o[0]; }
+__device__ __forceinline__ void sgm_pack_s(const unsigned *o, uint2 &v) { v = make_uint2(o[0], o[1]); }
+__device__ __forceinline__ void sgm_pack_s(const unsigned *o, uint4 &v) { v = make_uint4(o[0], o[1], o[2], o[3]); }
+
+// the paths of direction (dy, dx): one per pixel whose predecessor lies outside the image
+__host__ __device__ inline int sgm_npaths(int W, int H, int dy, int dx) { return dy == 0 ? H : (dx == 0 ? W : W + H - 1); }
+
+// One wave per path, lane l holds the disparities l * NV .. l * NV + NV - 1 of the previous pixel, normalised (L - m: their
+// minimum is 0), so a step is L = C + min(Lq(d), Lq(d-1) + P1, Lq(d+1) + P1, P2); d+-1 is a register except at the lane's edges
+// (two DPP moves), m the DPP minimum over the wave.  The recurrence is one dependent chain; C and S do not depend on it, so the
+// loads of SGM_U steps are issued together, one batch ahead of the one the chain is walking.  The body of the main loop has no
+// branch: the compiler then waits for exactly the loads a step needs (s_waitcnt vmcnt(n)) - with a branch per step it waited for
+// everything in flight, the previous step's store included, and a step cost a store round trip (measured: 1080p x 256, 13.6 ms for
+// the eight directions in that form).  Loads past the end of a path read its last pixel again; FIRST: the first direction of a
+// frame stores S instead of adding to it; ALL: every lane holds disparities below Dp (Dp = 64 NV) and stores without a predicate.
+// Within a direction every voxel lies on exactly one path and the launches of a frame follow each other on one stream: S is
+// updated with plain loads and stores, no atomics.
+template <int NV, bool FIRST, bool ALL>
+__global__ __launch_bounds__(256) void k_sgm_path(SgmArgs a, int dy, int dx)
+{
+    using CV = typename SgmVec<NV>::C;
+    using SV = typename SgmVec<NV>::S;
+    const int lane = threadIdx.x & 63;
+    const int path = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (path >= sgm_npaths(a.W, a.H, dy, dx)) return;             // (wave-uniform)
+    const int xs = dx > 0 ? 0 : a.W - 1, ys = dy > 0 ? 0 : a.H - 1;        // where a path enters the image
+    int x, y;
+    if (dy == 0) { x = xs; y = path; }
+    else if (dx == 0 || path < a.W) { x = path; y = ys; }
+    else { x = xs; y = ys + dy * (path - a.W + 1); }
+    const int lx = dx == 0 ? a.H : (dx > 0 ? a.W - x : x + 1), ly = dy == 0 ? a.W : (dy > 0 ? a.H - y : y + 1);
+    const int len = min(lx, ly);
+    const int d0 = lane * NV;
+    const bool act = ALL || d0 < a.Dp;
+    const long long step = ((long long)dy * a.W + dx) * a.Dp;
+    const long long off = ((long long)y * a.W + x) * a.Dp + (act ? d0 : 0);      // the path's first pixel (lanes past Dp: lane 0's
+                                                                                 // address - they load what they never use)
+    int lq[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) lq[k] = d0 + k < a.D ? 0 : SGM_INF;
+    CV cv[2][SGM_U];
+    SV sv[2][SGM_U];
+    auto load = [&](CV (&cb)[SGM_U], SV (&sb)[SGM_U], int i) {             // the loads of steps i .. i + SGM_U - 1
+#pragma unroll
+        for (int u = 0; u < SGM_U; ++u) {
+            const long long o = off + min(i + u, len - 1) * step;
+            cb[u] = *(const CV *)(a.C + o);
+            if (!FIRST) sb[u] = *(const SV *)(a.S + o);
+        }
+    };
+    auto run = [&](const CV (&cb)[SGM_U], const SV (&sb)[SGM_U], int i, auto full) {      // ... and their part of the chain
+#pragma unroll
+        for (int u = 0; u < SGM_U; ++u) {
+            if (decltype(full)::value || i + u < len) {
+                int c[NV], l[NV];
+                unsigned s[NV] = {};
+                sgm_unpack(cb[u], c);
+                if (!FIRST) sgm_unpack_s(sb[u], s);
+                const int left = sgm_dpp<0x138>(SGM_INF, lq[NV - 1]), right = sgm_dpp<0x130>(SGM_INF, lq[0]);
+                int lmin = SGM_INF;
+#pragma unroll
+                for (int k = 0; k < NV; ++k) {
+                    const int lo = (k ? lq[k - 1] : left) + a.P1, hi = (k + 1 < NV ? lq[k + 1] : right) + a.P1;
+                    const int t = min(min(lq[k], lo), min(hi, a.P2));
+                    l[k] = d0 + k < a.D ? c[k] + t : SGM_INF;
+                    lmin = min(lmin, l[k]);
+                }
+                const int m = sgm_wave_min(lmin);
+#pragma unroll
+                for (int k = 0; k < NV; ++k) {
+                    const bool real = d0 + k < a.D;
+                    s[k] += real ? (unsigned)l[k] : 0u;
+                    lq[k] = real ? l[k] - m : SGM_INF;
+                }
+                if (act) {
+                    SV o;
+                    sgm_pack_s(s, o);
+                    *(SV *)(a.S + off + (i + u) * step) = o;
+                }
+            }
+        }
+    };
+    load(cv[0], sv[0], 0);
+    int i = 0;
+    for (; i + 2 * SGM_U <= len; i += 2 * SGM_U) {
+        load(cv[1], sv[1], i + SGM_U);
+        run(cv[0], sv[0], i, std::true_type{});
+        load(cv[0], sv[0], i + 2 * SGM_U);
+        run(cv[1], sv[1], i + SGM_U, std::true_type{});
+    }
+    load(cv[1], sv[1], i + SGM_U);                                        // fewer than 2 SGM_U steps are left
+    run(cv[0], sv[0], i, std::false_type{});
+    run(cv[1], sv[1], i + SGM_U, std::false_type{});
+}
+
+// One wave per pixel: the packed (S << 8 | d) minimum over the wave is argmin with the lowest d on ties (S < 2^19).
+template <int NV>
+__global__ __launch_bounds__(256) void k_sgm_select(SgmArgs a)
+{
+    using SV = typename SgmVec<NV>::S;
+    const int lane = threadIdx.x & 63;
+    const int pix = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pix >= a.W * a.H) return;                                 // (wave-uniform)
+    const int d0 = lane * NV;
+    const unsigned *Sp = a.S + (size_t)pix * a.Dp;
+    unsigned s[NV] = {};
+    if (d0 < a.Dp) sgm_unpack_s(*(const SV *)(Sp + d0), s);
+    int key = 0x7fffffff;
+#pragma unroll
+    for (int k = 0; k < NV; ++k)
+        if (d0 + k < a.D) key = min(key, (int)((s[k] << 8) | (unsigned)(d0 + k)));
+    const int kmin = sgm_wave_min(key);
+    const int best = kmin & 255, minS = kmin >> 8;
+    bool rival = false;                                            // a disparity further than 1 from best within the uniqueness margin
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const int d = d0 + k;
+        rival |= d < a.D && (d < best - 1 || d > best + 1) && (int)s[k] * (100 - a.u) < minS * 100;
+    }
+    const bool unique = !__any(rival);
+    if (lane != 0) return;
+    int d16 = best * 16;
+    if (best > 0 && best < a.D - 1) {
+        const int sm = (int)Sp[best - 1], sp = (int)Sp[best + 1];
+        const int den = max(sm + sp - 2 * minS, 1);
+        const int num = (sm - sp) * 16 + den, dd = 2 * den;
+        int q = num / dd;
+        if (num % dd != 0 && num < 0) --q;                         // floor
+        d16 += q;
+    }
+    a.pre[pix] = (int16_t)(unique ? d16 : -16);
+    const int y = pix / a.W, x = pix - y * a.W;
+    if (unique && x - best >= 0) atomicMin(a.disp2 + (size_t)y * a.W + (x - best), (unsigned)kmin);
+}
+
+__device__ __forceinline__ bool sgm_bad_probe(const unsigned *row, int W, int xq, int dq, int m)
+{
+    if (xq < 0 || xq >= W) return false;
+    const unsigned k = row[xq];
+    if (k == 0xffffffffu) return false;
+    const int t = (int)(k & 255u) - dq;
+    return (t < 0 ? -t : t) > m;
+}
+
+__global__ __launch_bounds__(256) void k_sgm_check(SgmArgs a)
+{
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= a.W * a.H) return;
+    int v = a.pre[pix];
+    if (v >= 0 && a.m >= 0) {
+        const int y = pix / a.W, x = pix - y * a.W;
+        const unsigned *row = a.disp2 + (size_t)y * a.W;
+        const int da = v >> 4, db = (v + 15) >> 4;
+        if (sgm_bad_probe(row, a.W, x - da, da, a.m) && sgm_bad_probe(row, a.W, x - db, db, a.m)) v = -16;
+    }
+    a.out[pix] = (int16_t)v;
+}
+
+void launch_sgm_cost(hipStream_t s, const SgmArgs &a)
+{
+    const dim3 grid((a.W + SGM_TX - 1) / SGM_TX, a.H), block((a.D + 63) / 64 * 64);
+    switch (a.bs) {
+    case 1: hipLaunchKernelGGL(k_sgm_cost<1>, grid, block, 0, s, a); break;
+    case 3: hipLaunchKernelGGL(k_sgm_cost<3>, grid, block, 0, s, a); break;
+    case 5: hipLaunchKernelGGL(k_sgm_cost<5>, grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL(k_sgm_cost<7>, grid, block, 0, s, a); break;
+    }
+}
+
+// lanes hold 1, 2 or 4 disparities: the smallest count that covers Dp with 64 lanes
+static int sgm_nv(int Dp) { return Dp <= 64 ? 1 : (Dp <= 128 ? 2 : 4); }
+
+template <int NV>
+static void launch_path_nv(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first)
+{
+    const dim3 grid((sgm_npaths(a.W, a.H, dy, dx) + 3) / 4), block(256);
+    const bool all = a.Dp == 64 * NV;
+    if (first && all) hipLaunchKernelGGL((k_sgm_path<NV, true, true>), grid, block, 0, s, a, dy, dx);
+    else if (first) hipLaunchKernelGGL((k_sgm_path<NV, true, false>), grid, block, 0, s, a, dy, dx);
+    else if (all) hipLaunchKernelGGL((k_sgm_path<NV, false, true>), grid, block, 0, s, a, dy, dx);
+    else hipLaunchKernelGGL((k_sgm_path<NV, false, false>), grid, block, 0, s, a, dy, dx);
+}
+
+void launch_sgm_path(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first)
+{
+    switch (sgm_nv(a.Dp)) {
+    case 1: launch_path_nv<1>(s, a, dy, dx, first); break;
+    case 2: launch_path_nv<2>(s, a, dy, dx, first); break;
+    default: launch_path_nv<4>(s, a, dy, dx, first); break;
+    }
+}
+
+void launch_sgm_select(hipStream_t s, const SgmArgs &a)
+{
+    const int HW = a.W * a.H;
+    const dim3 grid((HW + 3) / 4), block(256);
+    switch (sgm_nv(a.Dp)) {
+    case 1: hipLaunchKernelGGL(k_sgm_select<1>, grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL(k_sgm_select<2>, grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL(k_sgm_select<4>, grid, block, 0, s, a); break;
+    }
+    hipLaunchKernelGGL(k_sgm_check, dim3((HW + 255) / 256), dim3(256), 0, s, a);
+}
+
+}  // namespace psm

@@ -136,6 +136,44 @@ class DispEst:
                  "DispSelect_GPU")
         return 0
 
+    # ---- the second algorithm: STEREO_SGBM (src/StereoMatch.cpp:169-187) ----------------------
+    def SGBM_GPU(self, block_size: int = 0, P1: int = 0, P2: int = 0, uniqueness_ratio: int = 10, disp12_max_diff: int = 1,
+                 gray=None):
+        """ssgbm->compute(lFrame, rFrame, imgDisparity16S) on the device over the pair setInputImages staged, with the
+        parameters of setupOpenCVSGBM (src/StereoMatch.cpp:639-660) as defaults (0: blockSize 5, P1 = 8 ch bs^2, P2 = 32 ch bs^2).
+        -> H x W int16: disparity * 16, -16 where invalid.  An independent stage (psm_sgm_compute): the maps, masks and volumes
+        of the other methods are untouched.  gray = (l, r): run on that H x W uint8 pair instead (CV_8UC1 frames)."""
+        self._ck(self._lib.psm_sgm_set_params(self._h, int(block_size), int(P1), int(P2), int(uniqueness_ratio),
+                                              int(disp12_max_diff)), "SGBM_GPU")
+        if gray is None:
+            self._ck(self._lib.psm_sgm_compute(self._h), "SGBM_GPU")
+        else:
+            l, r = (np.ascontiguousarray(a) for a in gray)
+            if l.shape != (self.hei, self.wid) or r.shape != l.shape or l.dtype != np.uint8 or r.dtype != np.uint8:
+                raise ValueError("SGBM_GPU: gray must be two H x W uint8 images of the size DispEst was built for")
+            self._ck(self._lib.psm_sgm_compute_gray(self._h, _ptr(l), _ptr(r), l.strides[0]), "SGBM_GPU")
+        return self.sgm_disparity()
+
+    def sgm_disparity(self):
+        """The int16 map of the last SGBM_GPU (synchronises)."""
+        disp = np.empty((self.hei, self.wid), np.int16)
+        self._ck(self._lib.psm_sgm_download_disparity(self._h, _ptr(disp), disp.strides[0]), "sgm_disparity")
+        return disp
+
+    def sgm_costs(self):
+        """Test hook: (C uint16, S uint32), both [H][W][maxDis], of the last SGBM_GPU."""
+        Cv = np.empty((self.hei, self.wid, self.maxDis), np.uint16)
+        Sv = np.empty((self.hei, self.wid, self.maxDis), np.uint32)
+        self._ck(self._lib.psm_sgm_download_costs(self._h, 0, _ptr(Cv)), "sgm_costs")
+        self._ck(self._lib.psm_sgm_download_costs(self._h, 1, _ptr(Sv)), "sgm_costs")
+        return Cv, Sv
+
+    def sgm_times(self):
+        """(cost, paths, select + check) device ms of the last SGBM_GPU; needs PSM_OPT_PROFILE."""
+        ms = (C.c_double * 3)()
+        self._ck(self._lib.psm_sgm_times(self._h, ms), "sgm_times")
+        return tuple(ms)
+
     # ---- extensions beyond the reference surface --------------------------------------------
     def LRCheck_GPU(self) -> int:
         """PP lrCheck (src/PP.cpp:17-50) on the device -> lValid / rValid."""

@@ -71,6 +71,42 @@ def compute_video(vFrame, rectification, maxDis=64, gt=None, mask=None, scale_fa
     return _finish(out, maxDis, gt, mask, scale_factor, error_threshold, verbose)
 
 
+def compute_sgbm(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, error_threshold=4, verbose=False, **params):
+    """One frame of STEREO_SGBM (src/StereoMatch.cpp:169-187, 275-309) on the device: l_bgr / r_bgr H x W x 3, uint8 or float32
+    scaled by 1/255 (quantised on the device as lFrame.convertTo(lFrame, CV_8U, 255) does); params: DispEst.SGBM_GPU's.
+    -> disp16 (imgDisparity16S), lDispMap (the display map), the reference's error metric on it, and bp_percent_int."""
+    out = {}
+    lFrame, rFrame = np.ascontiguousarray(l_bgr), np.ascontiguousarray(r_bgr)
+    with DispEst(lFrame, rFrame, maxDis, 8, True) as SMDE:
+        SMDE.set_option(capi.PSM_OPT_PROFILE, 1)
+        d16 = out["disp16"] = SMDE.SGBM_GPU(**params)
+        out["cost_ms"], out["paths_ms"], out["select_ms"] = SMDE.sgm_times()
+    # minMaxLoc(imgDisparity16S, &minVal, &maxVal); imgDisparity16S.convertTo(lDispMap, CV_8U, 255/(maxVal - minVal));
+    # lDispMap = (lDispMap/4) * scale_factor.  OpenCV's rounding of both steps: the factor is formed in double, but convertTo of a
+    # 16-bit source multiplies in fp32 - saturate_cast<uchar>(cvRound((float)v * (float)alpha)), cvRound = ties to even, negative
+    # products (the invalid -16) saturate to 0; Mat / 4 on CV_8U is convertTo(CV_8U, 0.25): cvRound(v * 0.25f), ties to even
+    # again (10 / 4 -> 2, 14 / 4 -> 4); * scale_factor saturates at 255.  There is no offset: minVal is not subtracted.
+    v = d16.astype(np.float32)
+    alpha = np.float32(255.0 / (float(d16.max()) - float(d16.min())))
+    m8 = np.clip(np.rint(v * alpha), 0, 255).astype(np.float32)
+    m8 = np.clip(np.rint(m8 * np.float32(0.25)), 0, 255)
+    out["lDispMap"] = np.clip(m8 * scale_factor, 0, 255).astype(np.uint8)
+    if gt is not None:
+        # the metric of :275-309 on the display map as it is (it already carries scale_factor)
+        bp, avg, bad, _ = error_vs_ground_truth(out["lDispMap"], gt, mask, maxDis, 1, error_threshold)
+        out.update({"bp_percent": bp, "avg_err": avg, "bad_pixels": bad})
+        # The figure to compare with the GIF path: the same metric on the integer disparity max(d16, 0) >> 4 scaled like the GIF
+        # maps.  bp_percent above is NOT comparable - the reference stretches the SGBM map by 255 / (maxVal - minVal) of the
+        # frame at hand (min-max scaling, then / 4), so its grey levels are not disparity * scale_factor.
+        out["bp_percent_int"] = error_vs_ground_truth(np.maximum(d16, 0) >> 4, gt, mask, maxDis, scale_factor, error_threshold)[0]
+    if verbose:
+        print("STEREO SGBM Times:")
+        print("Cost Time:\t %4.3f ms\nPaths Time:\t %4.3f ms\nSelect Time:\t %4.3f ms" % (out["cost_ms"], out["paths_ms"], out["select_ms"]))
+        if gt is not None:
+            print("%%BP = %.2f%% \t Avg Err = %.2f" % (out["bp_percent"], out["avg_err"]))
+    return out
+
+
 def _run_stages(SMDE, out, threads, subsample_rate, post_process, process_dm, joint_wmf):
     SMDE.setThreads(threads)
     SMDE.setSubsampleRate(subsample_rate or 4)

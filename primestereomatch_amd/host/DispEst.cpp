@@ -215,6 +215,28 @@ int DispEst::JointWMF_GPU()
     return hipUtil::api().joint_wmf(ctx[0], 0, 0.f, 0, 0, lDisMap.data, rDisMap.data, lDisMap.step);
 }
 
+int DispEst::setSGBMParams(int blockSize, int P1, int P2, int uniquenessRatio, int disp12MaxDiff)
+{
+    if (ctx.empty()) return 1;
+    return hipUtil::api().sgm_set_params(ctx[0], blockSize, P1, P2, uniquenessRatio, disp12MaxDiff);
+}
+
+int DispEst::SGBM_GPU(std::vector<int16_t> &disp16)
+{
+    if (ctx.size() != 1) {
+        fprintf(stderr, "DispEst: SGBM_GPU runs on single-device objects only\n");
+        return 1;
+    }
+    disp16.resize((size_t)hei * wid);
+    return hipUtil::api().sgm_compute(ctx[0]) || hipUtil::api().sgm_download_disparity(ctx[0], disp16.data(), 0);
+}
+
+int DispEst::sgbmTimes(double ms[3])
+{
+    if (ctx.empty()) return 1;
+    return hipUtil::api().sgm_times(ctx[0], ms);
+}
+
 int DispEst::computeFrame(const Mat *nextL, const Mat *nextR, bool have_prev)
 {
     if (ctx.size() != 1) return 1;           // (a multi-device host gathers stripes: use the stage calls)

@@ -101,6 +101,16 @@ public:
     // reference's radius, sigma and cluster count); lDisMap / rDisMap receive the filtered maps.  PostProcess_GPU is unchanged.
     int JointWMF_GPU();
 
+    // The second algorithm, STEREO_SGBM: ssgbm->compute(lFrame, rFrame, imgDisparity16S) (src/StereoMatch.cpp:169-187) on the device
+    // over the pair setInputImages gave, CV_8U or CV_32F (quantised on the device as convertTo(CV_8U, 255) does); the parameters
+    // are those of setupOpenCVSGBM (:639-660) unless setSGBMParams changed them (0: the default of the first three).  disp16:
+    // H x W int16 (imgDisparity16S, packed rows) - disparity * 16, -16 where invalid; resized by the call.  Independent of the GIF stages: lDisMap / rDisMap and
+    // the masks stay as they are.  Single-device objects only (the paths cross the whole image).  sgbmTimes: device ms of the
+    // block costs, the paths and select + check of the last call, if setOption(PSM_OPT_PROFILE, 1) was in force.
+    int setSGBMParams(int blockSize, int P1, int P2, int uniquenessRatio, int disp12MaxDiff);
+    int SGBM_GPU(std::vector<int16_t> &disp16);
+    int sgbmTimes(double ms[3]);
+
     // Frame loop (src/main.cpp:64-73) with the PCIe legs next to the kernels (single-device hosts): one call per frame -
     // CostConst (adopts the pair staged by the previous call), stages `next` pair (may be NULL at the end of the stream: its
     // Mats are free again on return), CostFilter, DispSelect on the device, hands over the PREVIOUS frame's maps in

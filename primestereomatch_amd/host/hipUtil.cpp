@@ -53,7 +53,10 @@ bool hipUtil::load(const char *path)
               bind(g_api.download_maps, "psm_download_maps") && bind(g_api.rectify_build_maps, "psm_rectify_build_maps") &&
               bind(g_api.rectify_set_maps, "psm_rectify_set_maps") && bind(g_api.rectify_clear, "psm_rectify_clear") &&
               bind(g_api.upload_pair_rectified, "psm_upload_pair_rectified") &&
-              bind(g_api.upload_pair_rectified_async, "psm_upload_pair_rectified_async") && bind(g_api.download_images, "psm_download_images");
+              bind(g_api.upload_pair_rectified_async, "psm_upload_pair_rectified_async") && bind(g_api.download_images, "psm_download_images") &&
+              bind(g_api.sgm_set_params, "psm_sgm_set_params") && bind(g_api.sgm_compute, "psm_sgm_compute") &&
+              bind(g_api.sgm_compute_gray, "psm_sgm_compute_gray") && bind(g_api.sgm_download_disparity, "psm_sgm_download_disparity") &&
+              bind(g_api.sgm_times, "psm_sgm_times");
     if (!ok) {
         fprintf(stderr, "%s\n", g_error.c_str());
         dlclose(g_handle);

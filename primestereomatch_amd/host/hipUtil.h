@@ -45,6 +45,12 @@ struct HipApi {
     int (*upload_pair_rectified)(psm_ctx *, const void *, const void *, int, size_t) = nullptr;
     int (*upload_pair_rectified_async)(psm_ctx *, const void *, const void *, int, size_t) = nullptr;
     int (*download_images)(psm_ctx *, uint8_t *, uint8_t *, size_t) = nullptr;
+    // the second algorithm: semi-global matching
+    int (*sgm_set_params)(psm_ctx *, int, int, int, int, int) = nullptr;
+    int (*sgm_compute)(psm_ctx *) = nullptr;
+    int (*sgm_compute_gray)(psm_ctx *, const uint8_t *, const uint8_t *, size_t) = nullptr;
+    int (*sgm_download_disparity)(psm_ctx *, int16_t *, size_t) = nullptr;
+    int (*sgm_times)(psm_ctx *, double *) = nullptr;
 };
 
 class hipUtil {

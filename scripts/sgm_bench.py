@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""Timing of the semi-global matching stage (psm_sgm_compute: k_sgm_cost, 8 x k_sgm_path, k_sgm_select + k_sgm_check).
+One JSON line per configuration on stdout and, with --out, appended to that file (profiles/sgm_bench.txt).
+
+Configurations: 450 x 375 x 64 (the Cones pair, tests/golden), 1280 x 720 x 128 and 1920 x 1080 x 256 (synth.make_pair).
+Per configuration, in one process: --warmup computes, then --runs computes under PSM_OPT_PROFILE 1; reported are the medians of
+the three kernel-group times of psm_sgm_times (hipEvents on the stream) and of their sum, the bytes the design moves by its own
+accounting (per element of the padded volumes, Dp = D rounded up to 4: C written once, 2 B; per direction C read, 2 B, S read
+and written, 8 B - the first direction only writes; S read once by the selection, 4 B: 82 B; plus the images and the planes),
+those bytes over the total as a fraction of the part's measured copy ceiling (6.29 TB/s, float4 copy), and the device memory
+the stage holds.  --model: also time the numpy model (tests/sgm_model.py) on the same pair, for scale; --model-only does just
+that and needs no GPU (the large pairs take minutes and gigabytes)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+COPY_CEILING = 6.29e12          # B/s
+CONFIGS = {"cones": (450, 375, 64), "720p": (1280, 720, 128), "1080p": (1920, 1080, 256)}
+
+
+def the_pair(name):
+    W, H, D = CONFIGS[name]
+    if name == "cones":
+        z = np.load(os.path.join(ROOT, "tests", "golden", "cones_pair.npz"))
+        return z["l_bgr"], z["r_bgr"]
+    from primestereomatch_amd import synth
+    return synth.make_pair(W, H, D, seed=0)[:2]
+
+
+def accounting(W, H, D):
+    Dp = (D + 3) // 4 * 4
+    vox = W * H * Dp
+    moved = vox * (2 + 8 * 10 - 4 + 4) + W * H * (2 * 3 + 4 + 4 + 2 + 4 + 4 + 2 + 2)   # images; disp2 fill, atomics, probes; pre, out
+    held = vox * 6 + W * H * (4 + 2 + 2)
+    return Dp, moved, held
+
+
+def model_seconds(l, r, D):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import sgm_model as M
+    t0 = time.perf_counter()
+    M.sgm(l, r, D)
+    return time.perf_counter() - t0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", default="cones,720p,1080p")
+    ap.add_argument("--runs", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--model", action="store_true")
+    ap.add_argument("--model-only", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    assert a.runs >= 1
+    for name in a.configs.split(","):
+        W, H, D = CONFIGS[name]
+        l, r = the_pair(name)
+        Dp, moved, held = accounting(W, H, D)
+        rec = {"bench": "sgm", "config": name, "W": W, "H": H, "D": D, "Dp": Dp}
+        if not a.model_only:
+            import primestereomatch_amd as P
+            from primestereomatch_amd import capi
+            if capi.device_count() < 1:
+                raise SystemExit("sgm_bench: no HIP device visible")
+            with P.DispEst(l, r, D) as de:
+                de.set_option(capi.PSM_OPT_PROFILE, 1)
+                for _ in range(a.warmup):
+                    de.SGBM_GPU()
+                t, wall = [], []
+                for _ in range(a.runs):
+                    w0 = time.perf_counter()
+                    de._ck(de._lib.psm_sgm_compute(de._h), "psm_sgm_compute")
+                    wall.append((time.perf_counter() - w0) * 1e3)
+                    t.append(de.sgm_times())
+                disp = de.sgm_disparity()
+            t = np.array(t)
+            med = np.median(t, axis=0)
+            total = float(np.median(t.sum(axis=1)))
+            rec.update({"runs": a.runs, "warmup": a.warmup, "cost_ms": round(float(med[0]), 4), "paths_ms": round(float(med[1]), 4),
+                        "select_ms": round(float(med[2]), 4), "total_ms": round(total, 4), "total_ms_min_max": [round(float(t.sum(axis=1).min()), 4), round(float(t.sum(axis=1).max()), 4)],
+                        "wall_ms_median": round(float(np.median(wall)), 4), "bytes_moved": int(moved),
+                        "fraction_of_copy_ceiling": round(moved / COPY_CEILING * 1e3 / total, 4), "copy_ceiling_TBps": COPY_CEILING / 1e12,
+                        "device_bytes_held": int(held), "valid_fraction": round(float((disp >= 0).mean()), 4)})
+        if a.model or a.model_only:
+            rec["numpy_model_s"] = round(model_seconds(l, r, D), 2)
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
