@@ -294,10 +294,10 @@ int psm_download_images(psm_ctx *ctx, uint8_t *l, uint8_t *r, size_t stride_byte
  *               rejected if the probes (x-da, da), da = d16 >> 4, and (x-db, db), db = (d16+15) >> 4, both find a disp2 that
  *               differs from the probe's disparity by more than m
  *   output      int16, d16 (disparity * 16) or -16 where not unique or rejected (OpenCV's (minDisparity - 1) * 16)
+ *   speckles    optional (psm_sgm_set_speckle), StereoSGBM's last step: cv::filterSpeckles on the output map - below
  * A float pair (PSM_IMG_F32) is quantised as lFrame.convertTo(lFrame, CV_8U, 255) does (:174-177): saturate(rint(f * 255.0f)).
- * OPEN, not part of this stage: the speckle filter (speckleWindowSize 100, speckleRange 32) and OpenCV's Sobel-prefiltered
- * Birchfield-Tomasi pixel cost (preFilterCap 63) - the pixel cost here is plain SAD; agreement with a live cv::StereoSGBM is not
- * pinned (neither OpenCV nor its source was available).
+ * OPEN, not part of this stage: OpenCV's Sobel-prefiltered Birchfield-Tomasi pixel cost (preFilterCap 63) - the pixel cost here
+ * is plain SAD; agreement with a live cv::StereoSGBM is not pinned (neither OpenCV nor its source was available).
  *
  * psm_sgm_set_params: block_size in {1, 3, 5, 7}; 0 < P1 <= P2; block_size^2 * channels * 255 + P2 <= 65535; uniqueness_ratio in
  * [0, 100); disp12_max_diff < 0 turns the consistency test off.  0 for any of the first three: the default above. */
@@ -318,6 +318,35 @@ int psm_sgm_download_costs(psm_ctx *ctx, int which, void *host);
 /* With PSM_OPT_PROFILE set during the last compute: device time in ms of its block-cost launch, its eight path launches and its
  * select + check launches (a getter of its own: the PSM_K_* and PSM_STAGE_* tables stay as they are). */
 int psm_sgm_times(psm_ctx *ctx, double ms[3]);
+
+/* The speckle filter, the step StereoSGBM ends with when speckleWindowSize > 0 (the reference: 100, with speckleRange 32):
+ * cv::filterSpeckles(img, newVal, maxSpeckleSize, maxDiff) on a CV_16SC1 map.  Its definition (tests/speckle_model.py) is free of
+ * any visiting order:
+ *   vertices  the pixels with img != newVal
+ *   edges     4-neighbours p, q, both vertices, |img[p] - img[q]| <= maxDiff (the difference taken in 32 bits; chains connect:
+ *             0, 512, 1024 side by side are one component at maxDiff 512)
+ *   result    every pixel of a connected component of AT MOST maxSpeckleSize pixels becomes newVal, every other pixel is unchanged
+ * On the device: union-find over the pixel grid in four launches whatever the data (psm_speckle.hip), all integer, the result
+ * equals the definition element for element.  It holds 8 * W * H bytes, allocated when first used, given back by
+ * psm_release_scratch and psm_destroy.
+ *
+ * psm_sgm_set_speckle: window 0 (a new context's setting): off - psm_sgm_compute / psm_sgm_compute_gray are what they are without
+ * this function.  window > 0: every following compute ends with filterSpeckles(map, -16, window, 16 * range) on its output map,
+ * after the disp12_max_diff test, on the stream (asynchronous computes stay asynchronous); C and S are not touched.  Negative
+ * values are refused.  The setting holds until changed; psm_sgm_set_params does not reset it. */
+int psm_sgm_set_speckle(psm_ctx *ctx, int speckle_window_size, int speckle_range);
+/* cv::filterSpeckles on the caller's map, in place: H rows of W int16, pitch stride_bytes (0: packed).  new_val: any int16 value;
+ * max_speckle_size >= 0 (0 changes nothing); max_diff >= 0.  The map goes through a device plane of this call; the last compute's
+ * map, C and S are untouched.  Synchronises on return.  Needs no staged pair and reads nothing else of the context: valid on
+ * disparity shards and under a row stripe too. */
+int psm_sgm_filter_speckles(psm_ctx *ctx, int16_t *disp, size_t stride_bytes, int new_val, int max_speckle_size, int max_diff);
+/* Test hook: for the last filter run (a compute with the filter on, or psm_sgm_filter_speckles) the size of every pixel's
+ * component, 0 where the pixel was new_val on input: H rows of W int32, pitch stride_bytes (0: packed).  Synchronises. */
+int psm_sgm_download_speckle_sizes(psm_ctx *ctx, int32_t *sizes, size_t stride_bytes);
+/* Device time in ms of the filter's four launches in the last compute, which must have been timed (PSM_OPT_PROFILE) and have run
+ * the filter; psm_sgm_times keeps its three numbers.  A psm_sgm_filter_speckles under PSM_OPT_PROFILE is timed the same way
+ * (the copies of the map excluded) and then is what this reports. */
+int psm_sgm_speckle_time(psm_ctx *ctx, double *ms);
 
 /* "next" row: PP lrCheck on the device (src/PP.cpp:17-50) on the maps of the last
  * psm_disp_select/psm_disp_merge.  lvalid/rvalid: H x W bytes (0/1), pitch `stride`; either

@@ -95,6 +95,10 @@ SYMBOLS = [
     ("psm_sgm_download_disparity", _i, [_vp, _vp, _sz]),
     ("psm_sgm_download_costs", _i, [_vp, _i, _vp]),
     ("psm_sgm_times", _i, [_vp, _pd]),
+    ("psm_sgm_set_speckle", _i, [_vp, _i, _i]),
+    ("psm_sgm_filter_speckles", _i, [_vp, _vp, _sz, _i, _i, _i]),
+    ("psm_sgm_download_speckle_sizes", _i, [_vp, _vp, _sz]),
+    ("psm_sgm_speckle_time", _i, [_vp, _pd]),
 ]
 
 _lib = None

@@ -1,8 +1,10 @@
 // psm_api_sgm.cpp - semi-global matching behind the C ABI: the STEREO_SGBM branch of StereoMatch::compute (ssgbm->compute(lFrame,
 // rFrame, imgDisparity16S), src/StereoMatch.cpp:169-187) with the parameters of setupOpenCVSGBM (:639-660), on the device
 // (psm_sgm.hip).  An independent stage: it reads the staged images and writes its own buffers (psm::SgmState) - volumes, maps,
-// masks, keys and the records of psm_state.h never see it.  The definition is tests/sgm_model.py / DESIGN.md 10; open there and
-// here: the speckle filter and OpenCV's prefiltered Birchfield-Tomasi cost.
+// masks, keys and the records of psm_state.h never see it.  The definition is tests/sgm_model.py / DESIGN.md 10.  The last step
+// of ssgbm->compute, the speckle filter (speckleWindowSize 100, speckleRange 32 there), is psm_speckle.hip: on the stage's map when
+// psm_sgm_set_speckle turned it on, on a caller's map in psm_sgm_filter_speckles (tests/speckle_model.py).  Open there and here:
+// OpenCV's prefiltered Birchfield-Tomasi cost.
 #include "psm_ctx.h"
 
 #include <cstring>
@@ -19,9 +21,12 @@ void sgm_free(psm_ctx *c)
     (void)hipFree(g.disp2); g.disp2 = nullptr;
     (void)hipFree(g.pre); g.pre = nullptr;
     (void)hipFree(g.out); g.out = nullptr;
+    (void)hipFree(g.spk_label); g.spk_label = nullptr;
+    (void)hipFree(g.spk_size); g.spk_size = nullptr;
     for (uint8_t *&p : g.gray) { (void)hipFree(p); p = nullptr; }
     for (hipEvent_t &e : g.ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    g.have = g.timed = false;
+    g.have = g.timed = g.spk_have = false;
+    g.spk_t0 = -1;
 }
 
 }  // namespace psm
@@ -67,7 +72,30 @@ int ensure_buffers(psm_ctx *c)
     return 0;
 }
 
-// cost, the eight directions, select + check on the context's stream
+// The speckle filter on `map` (a device plane of the context's size) in place, on the context's stream: four launches, nothing
+// read back.  t0 / ev[4]: the events that bracket it when the run is timed (t0 is already recorded).
+int enqueue_speckle(psm_ctx *c, int16_t *map, int new_val, int max_size, long long max_diff, int t0)
+{
+    SgmState &g = c->sgm;
+    const size_t HW = (size_t)c->W * c->H;
+    if (!g.spk_label) PSM_HIP(c, hipMalloc((void **)&g.spk_label, HW * sizeof(unsigned)));
+    if (!g.spk_size) PSM_HIP(c, hipMalloc((void **)&g.spk_size, HW * sizeof(unsigned)));
+    SpkArgs a;
+    a.map = map; a.label = g.spk_label; a.size = g.spk_size;
+    a.W = c->W; a.H = c->H;
+    a.new_val = new_val; a.max_size = max_size;
+    a.max_diff = (int)(max_diff > 65535 ? 65535 : max_diff);      // (two int16 values differ by 65535 at most)
+    g.spk_have = false;
+    g.spk_t0 = -1;
+    launch_speckle(c->stream, a);
+    if (check_launch(c, "k_spk_*")) return 1;
+    if (t0 >= 0) PSM_HIP(c, hipEventRecord(g.ev[4], c->stream));
+    g.spk_have = true;
+    g.spk_t0 = t0;
+    return 0;
+}
+
+// cost, the eight directions, select + check, the speckle filter if it is on, on the context's stream
 int enqueue(psm_ctx *c, const char *who, const void *l, const void *r, int depth, int ch)
 {
     SgmState &g = c->sgm;
@@ -81,6 +109,7 @@ int enqueue(psm_ctx *c, const char *who, const void *l, const void *r, int depth
     a.bs = g.bs; a.P1 = p1; a.P2 = p2; a.u = g.u; a.m = g.m;
     const bool timed = c->opt_profile != 0;
     g.have = g.timed = false;
+    g.spk_t0 = -1;
     // disp2 starts every frame as "nothing lands here", on the stream
     PSM_HIP(c, hipMemsetAsync(g.disp2, 0xff, (size_t)c->W * c->H * sizeof(uint32_t), c->stream));
     if (timed) PSM_HIP(c, hipEventRecord(g.ev[0], c->stream));
@@ -93,6 +122,8 @@ int enqueue(psm_ctx *c, const char *who, const void *l, const void *r, int depth
     launch_sgm_select(c->stream, a);
     if (check_launch(c, "k_sgm_select")) return 1;
     if (timed) PSM_HIP(c, hipEventRecord(g.ev[3], c->stream));
+    // filterSpeckles(disp, (minDisparity - 1) * 16, speckleWindowSize, 16 * speckleRange), as StereoSGBM ends
+    if (g.spk_window > 0 && enqueue_speckle(c, g.out, -16, g.spk_window, 16ll * g.spk_range, timed ? 3 : -1)) return 1;
     g.have = true;
     g.timed = timed;
     if (!c->opt_async) PSM_HIP(c, hipStreamSynchronize(c->stream));
@@ -111,6 +142,16 @@ int psm_sgm_set_params(psm_ctx *c, int block_size, int p1, int p2, int uniquenes
     if (check_params(c, "psm_sgm_set_params", 3, bs, &q1, &q2, uniqueness_ratio)) return 1;      // (the staged pair has 3 channels)
     SgmState &g = c->sgm;
     g.bs = bs; g.p1 = p1; g.p2 = p2; g.u = uniqueness_ratio; g.m = disp12_max_diff;
+    return 0;
+}
+
+int psm_sgm_set_speckle(psm_ctx *c, int speckle_window_size, int speckle_range)
+{
+    if (!c) return 1;
+    if (speckle_window_size < 0 || speckle_range < 0)
+        return fail(c, "psm_sgm_set_speckle: speckle_window_size %d, speckle_range %d: negative", speckle_window_size, speckle_range);
+    c->sgm.spk_window = speckle_window_size;
+    c->sgm.spk_range = speckle_range;
     return 0;
 }
 
@@ -190,6 +231,71 @@ int psm_sgm_times(psm_ctx *c, double ms[3])
         PSM_HIP(c, hipEventElapsedTime(&t, c->sgm.ev[i], c->sgm.ev[i + 1]));
         ms[i] = t;
     }
+    return 0;
+}
+
+int psm_sgm_filter_speckles(psm_ctx *c, int16_t *disp, size_t stride_bytes, int new_val, int max_speckle_size, int max_diff)
+{
+    if (!c) return 1;
+    if (!disp) return fail(c, "psm_sgm_filter_speckles: NULL map");
+    if (new_val < -32768 || new_val > 32767) return fail(c, "psm_sgm_filter_speckles: new_val %d is no int16 value", new_val);
+    if (max_speckle_size < 0) return fail(c, "psm_sgm_filter_speckles: max_speckle_size %d negative", max_speckle_size);
+    if (max_diff < 0) return fail(c, "psm_sgm_filter_speckles: max_diff %d negative", max_diff);
+    const size_t row = (size_t)c->W * sizeof(int16_t);
+    if (stride_bytes == 0) stride_bytes = row;
+    if (stride_bytes < row) return fail(c, "psm_sgm_filter_speckles: stride %zu < row size %zu", stride_bytes, row);
+    if (bind(c)) return 1;
+    SgmState &g = c->sgm;
+    const bool timed = c->opt_profile != 0;
+    if (timed)
+        for (int i = 4; i < 6; ++i)
+            if (!g.ev[i]) PSM_HIP(c, hipEventCreate(&g.ev[i]));
+    // the map lives in a plane of this call: the stage's own map and volumes are not touched, and the filter holds no more than
+    // its 8 W H bytes between calls
+    int16_t *map = nullptr;
+    PSM_HIP(c, hipMalloc((void **)&map, row * c->H));
+    int rc = h2d_rows(c, map, disp, row, stride_bytes, c->H);
+    if (!rc && timed) rc = hipEventRecord(g.ev[5], c->stream) != hipSuccess ? fail(c, "psm_sgm_filter_speckles: hipEventRecord") : 0;
+    if (!rc) rc = enqueue_speckle(c, map, new_val, max_speckle_size, max_diff, timed ? 5 : -1);
+    std::vector<int16_t> packed;
+    if (!rc) {
+        packed.resize((size_t)c->W * c->H);
+        if (hipMemcpyAsync(packed.data(), map, row * c->H, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = fail(c, "psm_sgm_filter_speckles: copy back");
+    }
+    if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(c, "psm_sgm_filter_speckles: hipStreamSynchronize");
+    (void)hipFree(map);
+    if (rc) return 1;
+    for (int y = 0; y < c->H; ++y) memcpy((uint8_t *)disp + (size_t)y * stride_bytes, packed.data() + (size_t)y * c->W, row);
+    return 0;
+}
+
+int psm_sgm_download_speckle_sizes(psm_ctx *c, int32_t *sizes, size_t stride_bytes)
+{
+    if (!c) return 1;
+    if (!sizes) return fail(c, "psm_sgm_download_speckle_sizes: NULL plane");
+    if (!c->sgm.spk_have) return fail(c, "psm_sgm_download_speckle_sizes: no filter run (psm_sgm_set_speckle + psm_sgm_compute, psm_sgm_filter_speckles)");
+    const size_t row = (size_t)c->W * sizeof(int32_t);
+    if (stride_bytes == 0) stride_bytes = row;
+    if (stride_bytes < row) return fail(c, "psm_sgm_download_speckle_sizes: stride %zu < row size %zu", stride_bytes, row);
+    if (bind(c)) return 1;
+    std::vector<int32_t> packed((size_t)c->W * c->H);
+    PSM_HIP(c, hipMemcpyAsync(packed.data(), c->sgm.spk_size, row * c->H, hipMemcpyDeviceToHost, c->stream));
+    PSM_HIP(c, hipStreamSynchronize(c->stream));
+    for (int y = 0; y < c->H; ++y) memcpy((uint8_t *)sizes + (size_t)y * stride_bytes, packed.data() + (size_t)y * c->W, row);
+    return 0;
+}
+
+int psm_sgm_speckle_time(psm_ctx *c, double *ms)
+{
+    if (!c) return 1;
+    if (!ms) return fail(c, "psm_sgm_speckle_time: NULL pointer");
+    if (!c->sgm.spk_have || c->sgm.spk_t0 < 0)
+        return fail(c, "psm_sgm_speckle_time: the last compute did not run the speckle filter, or was not timed (psm_sgm_set_speckle, PSM_OPT_PROFILE)");
+    if (bind(c)) return 1;
+    PSM_HIP(c, hipEventSynchronize(c->sgm.ev[4]));
+    float t = 0.f;
+    PSM_HIP(c, hipEventElapsedTime(&t, c->sgm.ev[c->sgm.spk_t0], c->sgm.ev[4]));
+    *ms = t;
     return 0;
 }
 

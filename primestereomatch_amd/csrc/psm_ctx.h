@@ -48,8 +48,13 @@ struct SgmState {
     int16_t *pre = nullptr, *out = nullptr;
     uint8_t *gray[2] = {nullptr, nullptr};         // psm_sgm_compute_gray: its 1-channel pair
     bool have = false;                             // a map and volumes of a compute exist
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [0..3]: psm_sgm_times; [4]: behind the speckle filter; [5]: ahead of a psm_sgm_filter_speckles
     bool timed = false;                            // ... and its launches were bracketed (PSM_OPT_PROFILE)
+    // the speckle filter (psm_sgm_set_speckle, psm_sgm_filter_speckles; psm_speckle.hip): 8 W H bytes, allocated when first used
+    int spk_window = 0, spk_range = 0;             // window 0: off
+    unsigned *spk_label = nullptr, *spk_size = nullptr;
+    bool spk_have = false;                         // spk_size holds the component sizes of a filter run
+    int spk_t0 = -1;                               // the event ahead of the last filter run's launches (3 or 5); -1: it was not timed
 };
 }  // namespace psm
 

@@ -233,4 +233,14 @@ void launch_sgm_cost(hipStream_t s, const SgmArgs &a);
 void launch_sgm_path(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first);     // S = L_r (first) or S += L_r
 void launch_sgm_select(hipStream_t s, const SgmArgs &a);                               // k_sgm_select + k_sgm_check (disp2 all ones before)
 
+// psm_speckle.hip: cv::filterSpeckles on an int16 map, in place (psm_sgm_set_speckle, psm_sgm_filter_speckles)
+struct SpkArgs {
+    int16_t *map;                      // [H][W], filtered in place
+    unsigned *label;                   // [H][W] union-find parents: a pixel index of the same component, <= the pixel's own; all ones: a new_val pixel
+    unsigned *size;                    // [H][W] run lengths at run heads, then component sizes at roots, in the end every pixel's component size
+    int W, H;
+    int new_val, max_size, max_diff;   // max_diff <= 65535
+};
+void launch_speckle(hipStream_t s, const SpkArgs &a);                                  // k_spk_runs, k_spk_merge, k_spk_count, k_spk_apply
+
 }  // namespace psm

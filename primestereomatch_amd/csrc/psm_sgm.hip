@@ -7,7 +7,8 @@
 //   k_sgm_select  argmin_d S (lowest d), uniqueness, sub-pixel d16, disp2[y][x-best] = min (minS << 8 | best)
 //   k_sgm_check   the disp12MaxDiff test of every pixel against disp2 of its row -> int16 map, -16 where invalid
 // d is innermost in both volumes (Dp = D rounded up to 4 elements per pixel): the disparities of a pixel are one contiguous read
-// whatever the walking direction.  Not here, and open: the speckle filter and the Sobel-prefiltered Birchfield-Tomasi cost.
+// whatever the walking direction.  The speckle filter StereoSGBM ends with is psm_speckle.hip (psm_sgm_set_speckle).  Not here,
+// and open: the Sobel-prefiltered Birchfield-Tomasi cost.
 #include "psm_kernels.h"
 
 #include <type_traits>

@@ -138,11 +138,14 @@ class DispEst:
 
     # ---- the second algorithm: STEREO_SGBM (src/StereoMatch.cpp:169-187) ----------------------
     def SGBM_GPU(self, block_size: int = 0, P1: int = 0, P2: int = 0, uniqueness_ratio: int = 10, disp12_max_diff: int = 1,
-                 gray=None):
+                 gray=None, speckle_window_size: int = 0, speckle_range: int = 0):
         """ssgbm->compute(lFrame, rFrame, imgDisparity16S) on the device over the pair setInputImages staged, with the
         parameters of setupOpenCVSGBM (src/StereoMatch.cpp:639-660) as defaults (0: blockSize 5, P1 = 8 ch bs^2, P2 = 32 ch bs^2).
         -> H x W int16: disparity * 16, -16 where invalid.  An independent stage (psm_sgm_compute): the maps, masks and volumes
-        of the other methods are untouched.  gray = (l, r): run on that H x W uint8 pair instead (CV_8UC1 frames)."""
+        of the other methods are untouched.  gray = (l, r): run on that H x W uint8 pair instead (CV_8UC1 frames).
+        speckle_window_size > 0: the map goes through StereoSGBM's last step, filterSpeckles(map, -16, speckle_window_size,
+        16 * speckle_range) (the reference: 100, 32); 0, the default: off - the setting is this call's, not the object's."""
+        self._ck(self._lib.psm_sgm_set_speckle(self._h, int(speckle_window_size), int(speckle_range)), "SGBM_GPU")
         self._ck(self._lib.psm_sgm_set_params(self._h, int(block_size), int(P1), int(P2), int(uniqueness_ratio),
                                               int(disp12_max_diff)), "SGBM_GPU")
         if gray is None:
@@ -173,6 +176,31 @@ class DispEst:
         ms = (C.c_double * 3)()
         self._ck(self._lib.psm_sgm_times(self._h, ms), "sgm_times")
         return tuple(ms)
+
+    def filter_speckles(self, disp, new_val: int, max_speckle_size: int, max_diff: int):
+        """cv::filterSpeckles(disp, newVal, maxSpeckleSize, maxDiff) on the device (psm_sgm_filter_speckles): disp H x W int16 of
+        the size DispEst was built for -> the filtered copy.  Components of at most max_speckle_size pixels (4-neighbours, values
+        != new_val, |difference| <= max_diff) become new_val.  The results of SGBM_GPU are untouched."""
+        disp = np.asarray(disp)
+        if disp.shape != (self.hei, self.wid) or disp.dtype != np.int16:
+            raise ValueError("filter_speckles: disp must be an H x W int16 map of the size DispEst was built for")
+        out = np.array(disp, order="C", copy=True)
+        self._ck(self._lib.psm_sgm_filter_speckles(self._h, _ptr(out), out.strides[0], int(new_val), int(max_speckle_size),
+                                                   int(max_diff)), "filter_speckles")
+        return out
+
+    def sgm_speckle_sizes(self):
+        """Test hook: H x W int32, the size of every pixel's component in the last speckle filter run (SGBM_GPU with the filter
+        on, or filter_speckles); 0 where the pixel was new_val on input."""
+        sizes = np.empty((self.hei, self.wid), np.int32)
+        self._ck(self._lib.psm_sgm_download_speckle_sizes(self._h, _ptr(sizes), sizes.strides[0]), "sgm_speckle_sizes")
+        return sizes
+
+    def sgm_speckle_time(self):
+        """Device ms of the speckle filter's launches in the last SGBM_GPU (or filter_speckles); needs PSM_OPT_PROFILE."""
+        ms = C.c_double()
+        self._ck(self._lib.psm_sgm_speckle_time(self._h, C.byref(ms)), "sgm_speckle_time")
+        return ms.value
 
     # ---- extensions beyond the reference surface --------------------------------------------
     def LRCheck_GPU(self) -> int:

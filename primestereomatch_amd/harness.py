@@ -81,6 +81,8 @@ def compute_sgbm(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, er
         SMDE.set_option(capi.PSM_OPT_PROFILE, 1)
         d16 = out["disp16"] = SMDE.SGBM_GPU(**params)
         out["cost_ms"], out["paths_ms"], out["select_ms"] = SMDE.sgm_times()
+        if params.get("speckle_window_size", 0) > 0:
+            out["speckle_ms"] = SMDE.sgm_speckle_time()
     # minMaxLoc(imgDisparity16S, &minVal, &maxVal); imgDisparity16S.convertTo(lDispMap, CV_8U, 255/(maxVal - minVal));
     # lDispMap = (lDispMap/4) * scale_factor.  OpenCV's rounding of both steps: the factor is formed in double, but convertTo of a
     # 16-bit source multiplies in fp32 - saturate_cast<uchar>(cvRound((float)v * (float)alpha)), cvRound = ties to even, negative
@@ -102,6 +104,8 @@ def compute_sgbm(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, er
     if verbose:
         print("STEREO SGBM Times:")
         print("Cost Time:\t %4.3f ms\nPaths Time:\t %4.3f ms\nSelect Time:\t %4.3f ms" % (out["cost_ms"], out["paths_ms"], out["select_ms"]))
+        if "speckle_ms" in out:
+            print("Speckle Time:\t %4.3f ms" % out["speckle_ms"])
         if gt is not None:
             print("%%BP = %.2f%% \t Avg Err = %.2f" % (out["bp_percent"], out["avg_err"]))
     return out

@@ -231,6 +231,18 @@ int DispEst::SGBM_GPU(std::vector<int16_t> &disp16)
     return hipUtil::api().sgm_compute(ctx[0]) || hipUtil::api().sgm_download_disparity(ctx[0], disp16.data(), 0);
 }
 
+int DispEst::setSGBMSpeckle(int speckleWindowSize, int speckleRange)
+{
+    if (ctx.empty()) return 1;
+    return hipUtil::api().sgm_set_speckle(ctx[0], speckleWindowSize, speckleRange);
+}
+
+int DispEst::sgbmSpeckleTime(double *ms)
+{
+    if (ctx.empty()) return 1;
+    return hipUtil::api().sgm_speckle_time(ctx[0], ms);
+}
+
 int DispEst::sgbmTimes(double ms[3])
 {
     if (ctx.empty()) return 1;

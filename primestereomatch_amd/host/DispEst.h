@@ -110,6 +110,11 @@ public:
     int setSGBMParams(int blockSize, int P1, int P2, int uniquenessRatio, int disp12MaxDiff);
     int SGBM_GPU(std::vector<int16_t> &disp16);
     int sgbmTimes(double ms[3]);
+    // The step StereoSGBM ends with: filterSpeckles(disp16, -16, speckleWindowSize, 16 * speckleRange) on the map of every following
+    // SGBM_GPU (setupOpenCVSGBM: 100, 32).  Window 0, the setting of a new object: off.  sgbmSpeckleTime: device ms of the filter in
+    // the last timed SGBM_GPU.
+    int setSGBMSpeckle(int speckleWindowSize, int speckleRange);
+    int sgbmSpeckleTime(double *ms);
 
     // Frame loop (src/main.cpp:64-73) with the PCIe legs next to the kernels (single-device hosts): one call per frame -
     // CostConst (adopts the pair staged by the previous call), stages `next` pair (may be NULL at the end of the stream: its

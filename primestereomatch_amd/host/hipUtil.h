@@ -51,6 +51,10 @@ struct HipApi {
     int (*sgm_compute_gray)(psm_ctx *, const uint8_t *, const uint8_t *, size_t) = nullptr;
     int (*sgm_download_disparity)(psm_ctx *, int16_t *, size_t) = nullptr;
     int (*sgm_times)(psm_ctx *, double *) = nullptr;
+    int (*sgm_set_speckle)(psm_ctx *, int, int) = nullptr;
+    int (*sgm_filter_speckles)(psm_ctx *, int16_t *, size_t, int, int, int) = nullptr;
+    int (*sgm_download_speckle_sizes)(psm_ctx *, int32_t *, size_t) = nullptr;
+    int (*sgm_speckle_time)(psm_ctx *, double *) = nullptr;
 };
 
 class hipUtil {

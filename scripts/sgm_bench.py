@@ -9,7 +9,12 @@ accounting (per element of the padded volumes, Dp = D rounded up to 4: C written
 and written, 8 B - the first direction only writes; S read once by the selection, 4 B: 82 B; plus the images and the planes),
 those bytes over the total as a fraction of the part's measured copy ceiling (6.29 TB/s, float4 copy), and the device memory
 the stage holds.  --model: also time the numpy model (tests/sgm_model.py) on the same pair, for scale; --model-only does just
-that and needs no GPU (the large pairs take minutes and gigabytes)."""
+that and needs no GPU (the large pairs take minutes and gigabytes).
+
+The speckle filter (psm_sgm_set_speckle; k_spk_runs, k_spk_merge, k_spk_count, k_spk_apply): every configuration is timed twice in
+the same process, with the filter off (the record above, unchanged) and on at the reference's (100, 32) - "speckle_ms", the median
+of psm_sgm_speckle_time, and the three group times of those runs as "*_ms_speckle_on".  --speckle-maps: also two 1920 x 1080
+maps through psm_sgm_filter_speckles at (-16, 100, 512): a serpentine (the whole image one path) and a constant map."""
 import argparse
 import json
 import os
@@ -50,6 +55,34 @@ def model_seconds(l, r, D):
     return time.perf_counter() - t0
 
 
+def speckle_maps(runs, warmup, out):
+    """The filter alone on 1080p maps an SGM run never produces: device ms of its four launches, median of `runs`."""
+    import primestereomatch_amd as P
+    from primestereomatch_amd import capi
+    W, H = 1920, 1080
+    serp = np.full((H, W), 2000, np.int16)
+    serp[0::2] = 160
+    serp[1::4, W - 1] = 160
+    serp[3::4, 0] = 160
+    blank = np.zeros((H, W, 3), np.uint8)
+    with P.DispEst(blank, blank, 2) as de:
+        de.set_option(capi.PSM_OPT_PROFILE, 1)
+        for name, m in (("serpentine", serp), ("constant", np.full((H, W), 160, np.int16))):
+            t = []
+            for i in range(warmup + runs):
+                de.filter_speckles(m, -16, 100, 512)
+                if i >= warmup:
+                    t.append(de.sgm_speckle_time())
+            rec = {"bench": "speckle", "map": name, "W": W, "H": H, "args": [-16, 100, 512], "runs": runs, "warmup": warmup,
+                   "speckle_ms": round(float(np.median(t)), 4), "speckle_ms_min_max": [round(min(t), 4), round(max(t), 4)],
+                   "largest_component": int(de.sgm_speckle_sizes().max())}
+            line = json.dumps(rec)
+            print(line, flush=True)
+            if out:
+                with open(out, "a") as f:
+                    f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="cones,720p,1080p")
@@ -57,6 +90,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--model", action="store_true")
     ap.add_argument("--model-only", action="store_true")
+    ap.add_argument("--speckle-maps", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert a.runs >= 1
@@ -81,14 +115,26 @@ def main():
                     wall.append((time.perf_counter() - w0) * 1e3)
                     t.append(de.sgm_times())
                 disp = de.sgm_disparity()
+                for _ in range(a.warmup):
+                    de.SGBM_GPU(speckle_window_size=100, speckle_range=32)
+                ts, tk = [], []
+                for _ in range(a.runs):
+                    de._ck(de._lib.psm_sgm_compute(de._h), "psm_sgm_compute")      # (the setting holds)
+                    ts.append(de.sgm_times())
+                    tk.append(de.sgm_speckle_time())
+                removed = int(np.count_nonzero(de.sgm_disparity() != disp))
             t = np.array(t)
+            meds = np.median(np.array(ts), axis=0)
             med = np.median(t, axis=0)
             total = float(np.median(t.sum(axis=1)))
             rec.update({"runs": a.runs, "warmup": a.warmup, "cost_ms": round(float(med[0]), 4), "paths_ms": round(float(med[1]), 4),
                         "select_ms": round(float(med[2]), 4), "total_ms": round(total, 4), "total_ms_min_max": [round(float(t.sum(axis=1).min()), 4), round(float(t.sum(axis=1).max()), 4)],
                         "wall_ms_median": round(float(np.median(wall)), 4), "bytes_moved": int(moved),
                         "fraction_of_copy_ceiling": round(moved / COPY_CEILING * 1e3 / total, 4), "copy_ceiling_TBps": COPY_CEILING / 1e12,
-                        "device_bytes_held": int(held), "valid_fraction": round(float((disp >= 0).mean()), 4)})
+                        "device_bytes_held": int(held), "valid_fraction": round(float((disp >= 0).mean()), 4),
+                        "speckle_ms": round(float(np.median(tk)), 4), "speckle_ms_min_max": [round(min(tk), 4), round(max(tk), 4)],
+                        "cost_ms_speckle_on": round(float(meds[0]), 4), "paths_ms_speckle_on": round(float(meds[1]), 4),
+                        "select_ms_speckle_on": round(float(meds[2]), 4), "speckle_pixels_removed": removed})
         if a.model or a.model_only:
             rec["numpy_model_s"] = round(model_seconds(l, r, D), 2)
         line = json.dumps(rec)
@@ -96,6 +142,8 @@ def main():
         if a.out:
             with open(a.out, "a") as f:
                 f.write(line + "\n")
+    if a.speckle_maps and not a.model_only:
+        speckle_maps(a.runs, a.warmup, a.out)
 
 
 if __name__ == "__main__":
