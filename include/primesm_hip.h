@@ -284,7 +284,7 @@ int psm_download_images(psm_ctx *ctx, uint8_t *l, uint8_t *r, size_t stride_byte
  * (:639-660): minDisparity 0, numDisparities = the context's max_disp (any value in [2, 256]), blockSize 5, P1 = 8 ch bs^2,
  * P2 = 32 ch bs^2, disp12MaxDiff 1, uniquenessRatio 10, eight paths (MODE_HH).  All integer; the definition (DESIGN.md section 10,
  * tests/sgm_model.py) is Hirschmueller's recurrence under OpenCV's parameter names, and the device equals it element for element:
- *   pixel cost  c(x,y,d) = sum_ch |L[y][x][ch] - R[y][max(x-d, 0)][ch]|
+ *   pixel cost  c(x,y,d) = sum_ch |L[y][x][ch] - R[y][max(x-d, 0)][ch]|, or the prefiltered Birchfield-Tomasi cost - below
  *   block cost  C = the bs x bs box sum of c(.,.,d), the plane replicated at the image edge (u16)
  *   paths       L_r(p,d) = C(p,d) + min(L_r(p-r,d), L_r(p-r,d-1)+P1, L_r(p-r,d+1)+P1, m+P2) - m, m = min_k L_r(p-r,k); L_r = C where
  *               p-r is outside; r = (dy,dx) in (0,+-1), (+-1,0), (+-1,+-1); S = sum_r L_r (u32, exact)
@@ -296,16 +296,17 @@ int psm_download_images(psm_ctx *ctx, uint8_t *l, uint8_t *r, size_t stride_byte
  *   output      int16, d16 (disparity * 16) or -16 where not unique or rejected (OpenCV's (minDisparity - 1) * 16)
  *   speckles    optional (psm_sgm_set_speckle), StereoSGBM's last step: cv::filterSpeckles on the output map - below
  * A float pair (PSM_IMG_F32) is quantised as lFrame.convertTo(lFrame, CV_8U, 255) does (:174-177): saturate(rint(f * 255.0f)).
- * OPEN, not part of this stage: OpenCV's Sobel-prefiltered Birchfield-Tomasi pixel cost (preFilterCap 63) - the pixel cost here
- * is plain SAD; agreement with a live cv::StereoSGBM is not pinned (neither OpenCV nor its source was available).
+ * Every field of setupOpenCVSGBM is built; the pixel cost of a new context is SAD, StereoSGBM's own cost (preFilterCap 63 in the
+ * reference) is selected by psm_sgm_set_prefilter.  Unpinned: agreement with a live cv::StereoSGBM (neither OpenCV nor its
+ * source was available) - what is built is the definition stated here and in the models under tests/.
  *
  * psm_sgm_set_params: block_size in {1, 3, 5, 7}; 0 < P1 <= P2; block_size^2 * channels * 255 + P2 <= 65535; uniqueness_ratio in
  * [0, 100); disp12_max_diff < 0 turns the consistency test off.  0 for any of the first three: the default above. */
 int psm_sgm_set_params(psm_ctx *ctx, int block_size, int p1, int p2, int uniqueness_ratio, int disp12_max_diff);
 /* Runs the stage on the context's stream over the pair psm_upload_pair* staged (either depth); synchronous on return unless
  * PSM_OPT_ASYNC.  An independent stage: it reads the staged images only and writes its own buffers - 6 * W * H * Dp bytes of
- * volumes (Dp = max_disp rounded up to 4) and 8 * W * H of planes, allocated on first use, reused from frame to frame, given back
- * by psm_release_scratch and psm_destroy.  Volumes, maps, masks and minima of the other entry points are untouched: it may be
+ * volumes (Dp = max_disp rounded up to 4) and 8 * W * H of planes, plus 12 * W * H of prefiltered planes once a compute ran with
+ * pre_filter_cap > 0, allocated on first use, reused from frame to frame, given back by psm_release_scratch and psm_destroy.  Volumes, maps, masks and minima of the other entry points are untouched: it may be
  * called anywhere between them.  Refused on disparity shards, under a row stripe, and when nothing has been uploaded. */
 int psm_sgm_compute(psm_ctx *ctx);
 /* The same for a 1-channel 8-bit pair (CV_8UC1 frames): H rows of W bytes, pitch stride_bytes (0: packed).  The pair is copied to
@@ -315,9 +316,34 @@ int psm_sgm_compute_gray(psm_ctx *ctx, const uint8_t *l, const uint8_t *r, size_
 int psm_sgm_download_disparity(psm_ctx *ctx, int16_t *disp, size_t stride_bytes);
 /* Test hook: the volumes of the last compute as dense host arrays [H][W][max_disp] - which 0: C as uint16, 1: S as uint32. */
 int psm_sgm_download_costs(psm_ctx *ctx, int which, void *host);
-/* With PSM_OPT_PROFILE set during the last compute: device time in ms of its block-cost launch, its eight path launches and its
- * select + check launches (a getter of its own: the PSM_K_* and PSM_STAGE_* tables stay as they are). */
+/* With PSM_OPT_PROFILE set during the last compute: device time in ms of its block-cost launches (everything up to C, the
+ * prefilter included), its eight path launches and its select + check launches (a getter of its own: the PSM_K_* and PSM_STAGE_* tables stay as they are). */
 int psm_sgm_times(psm_ctx *ctx, double ms[3]);
+
+/* StereoSGBM's pixel cost: the Birchfield-Tomasi cost over Sobel-prefiltered images (tests/sgm_bt_model.py; all integer, the
+ * device equals it element for element).  pre_filter_cap = cap, 1 <= cap <= 63, ft = max(cap, 15) | 1; images are the 8-bit pair
+ * (a float pair is quantised first), ch in {1, 3}:
+ *   planes   2 ch per image, [H][W] bytes each, over the whole image; yn = max(y-1, 0), ys = min(y+1, H-1); for 1 <= x <= W-2:
+ *              g = 2 (I[y][x+1] - I[y][x-1]) + (I[yn][x+1] - I[yn][x-1]) + (I[ys][x+1] - I[ys][x-1])   on channel k
+ *              P_k[y][x] = min(max(g, -ft), ft) + ft,  Q_k[y][x] = I[y][x][k]
+ *            for x = 0 and x = W-1 BOTH P_k and Q_k are ft (OpenCV presets the border columns of all its row buffers).
+ *            Order P_0 .. P_{ch-1}, Q_0 .. Q_{ch-1}; P planes have shift 0, Q planes shift 2.
+ *   bounds   of a plane row a: al = x > 0 ? (a[x] + a[x-1]) / 2 : a[x], ar = x < W-1 ? (a[x] + a[x+1]) / 2 : a[x] (floor),
+ *            lo(a, x) = min(a[x], al, ar), hi(a, x) = max(a[x], al, ar)
+ *   cost     xr = max(x - d, 0); per plane, U of the left image, V of the right: u = U[y][x], v = V[y][xr],
+ *            c0 = max(0, u - hi(V, xr), lo(V, xr) - u), c1 = max(0, v - hi(U, x), lo(U, x) - v),
+ *            c(x,y,d) = sum over the planes of min(c0, c1) >> shift
+ * Per channel c is at most 2 ft + 63 <= 189 < 255: the conditions of psm_sgm_set_params hold as they are.  Block cost, paths,
+ * selection, consistency test and speckle filter are unchanged.  Not OpenCV's: the stage keeps all columns and xr = max(x-d, 0)
+ * where OpenCV leaves the leftmost numDisparities columns invalid.
+ *
+ * psm_sgm_set_prefilter: 0 (a new context's setting): SAD - psm_sgm_compute / psm_sgm_compute_gray are what they are without this
+ * function.  1 .. 63: every following compute uses the cost above.  Other values are refused.  The setting holds until changed;
+ * psm_sgm_set_params and psm_sgm_set_speckle do not reset it. */
+int psm_sgm_set_prefilter(psm_ctx *ctx, int pre_filter_cap);
+/* Test hook: the prefiltered planes of the last compute, side 0: left, 1: right, as [H][W][2 ch] bytes in the plane order above.
+ * Refused when the last compute ran with pre_filter_cap 0, or there is none.  Synchronises. */
+int psm_sgm_download_prefiltered(psm_ctx *ctx, int side, uint8_t *planes);
 
 /* The speckle filter, the step StereoSGBM ends with when speckleWindowSize > 0 (the reference: 100, with speckleRange 32):
  * cv::filterSpeckles(img, newVal, maxSpeckleSize, maxDiff) on a CV_16SC1 map.  Its definition (tests/speckle_model.py) is free of

@@ -99,6 +99,8 @@ SYMBOLS = [
     ("psm_sgm_filter_speckles", _i, [_vp, _vp, _sz, _i, _i, _i]),
     ("psm_sgm_download_speckle_sizes", _i, [_vp, _vp, _sz]),
     ("psm_sgm_speckle_time", _i, [_vp, _pd]),
+    ("psm_sgm_set_prefilter", _i, [_vp, _i]),
+    ("psm_sgm_download_prefiltered", _i, [_vp, _i, _vp]),
 ]
 
 _lib = None

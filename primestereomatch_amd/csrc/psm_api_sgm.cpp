@@ -3,8 +3,9 @@
 // (psm_sgm.hip).  An independent stage: it reads the staged images and writes its own buffers (psm::SgmState) - volumes, maps,
 // masks, keys and the records of psm_state.h never see it.  The definition is tests/sgm_model.py / DESIGN.md 10.  The last step
 // of ssgbm->compute, the speckle filter (speckleWindowSize 100, speckleRange 32 there), is psm_speckle.hip: on the stage's map when
-// psm_sgm_set_speckle turned it on, on a caller's map in psm_sgm_filter_speckles (tests/speckle_model.py).  Open there and here:
-// OpenCV's prefiltered Birchfield-Tomasi cost.
+// psm_sgm_set_speckle turned it on, on a caller's map in psm_sgm_filter_speckles (tests/speckle_model.py).  The pixel cost is SAD
+// (pre_filter_cap 0, a new context's setting) or, after psm_sgm_set_prefilter, StereoSGBM's Sobel-prefiltered Birchfield-Tomasi
+// cost as tests/sgm_bt_model.py defines it (the reference: preFilterCap 63).  Unpinned in all of it: a live cv::StereoSGBM.
 #include "psm_ctx.h"
 
 #include <cstring>
@@ -24,6 +25,8 @@ void sgm_free(psm_ctx *c)
     (void)hipFree(g.spk_label); g.spk_label = nullptr;
     (void)hipFree(g.spk_size); g.spk_size = nullptr;
     for (uint8_t *&p : g.gray) { (void)hipFree(p); p = nullptr; }
+    for (uint8_t *&p : g.pf) { (void)hipFree(p); p = nullptr; }
+    g.pf_ch = 0;
     for (hipEvent_t &e : g.ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     g.have = g.timed = g.spk_have = false;
     g.spk_t0 = -1;
@@ -107,14 +110,29 @@ int enqueue(psm_ctx *c, const char *who, const void *l, const void *r, int depth
     a.C = g.C; a.S = g.S; a.disp2 = g.disp2; a.pre = g.pre; a.out = g.out;
     a.W = c->W; a.H = c->H; a.D = c->D; a.Dp = sgm_dp(c);
     a.bs = g.bs; a.P1 = p1; a.P2 = p2; a.u = g.u; a.m = g.m;
+    a.pf[0] = a.pf[1] = nullptr; a.Hs = nullptr; a.ft = 0;
+    if (g.cap > 0) {
+        for (uint8_t *&p : g.pf)
+            if (!p) PSM_HIP(c, hipMalloc((void **)&p, (size_t)c->W * c->H * 6));
+        a.pf[0] = g.pf[0]; a.pf[1] = g.pf[1];
+        a.Hs = (uint16_t *)g.S;                           // S is free until the first direction stores it
+        a.ft = (g.cap > 15 ? g.cap : 15) | 1;
+    }
     const bool timed = c->opt_profile != 0;
     g.have = g.timed = false;
     g.spk_t0 = -1;
+    g.pf_ch = 0;
     // disp2 starts every frame as "nothing lands here", on the stream
     PSM_HIP(c, hipMemsetAsync(g.disp2, 0xff, (size_t)c->W * c->H * sizeof(uint32_t), c->stream));
     if (timed) PSM_HIP(c, hipEventRecord(g.ev[0], c->stream));
-    launch_sgm_cost(c->stream, a);
-    if (check_launch(c, "k_sgm_cost")) return 1;
+    if (g.cap > 0) {
+        launch_sgm_cost_bt(c->stream, a);
+        if (check_launch(c, "k_sgm_prefilter, k_sgm_bt_*")) return 1;
+        g.pf_ch = ch;
+    } else {
+        launch_sgm_cost(c->stream, a);
+        if (check_launch(c, "k_sgm_cost")) return 1;
+    }
     if (timed) PSM_HIP(c, hipEventRecord(g.ev[1], c->stream));
     for (int i = 0; i < 8; ++i) launch_sgm_path(c->stream, a, SGM_DIRS[i][0], SGM_DIRS[i][1], i == 0);
     if (check_launch(c, "k_sgm_path")) return 1;
@@ -152,6 +170,15 @@ int psm_sgm_set_speckle(psm_ctx *c, int speckle_window_size, int speckle_range)
         return fail(c, "psm_sgm_set_speckle: speckle_window_size %d, speckle_range %d: negative", speckle_window_size, speckle_range);
     c->sgm.spk_window = speckle_window_size;
     c->sgm.spk_range = speckle_range;
+    return 0;
+}
+
+int psm_sgm_set_prefilter(psm_ctx *c, int pre_filter_cap)
+{
+    if (!c) return 1;
+    if (pre_filter_cap < 0 || pre_filter_cap > 63)
+        return fail(c, "psm_sgm_set_prefilter: pre_filter_cap %d outside [0, 63] (0: the SAD cost)", pre_filter_cap);
+    c->sgm.cap = pre_filter_cap;
     return 0;
 }
 
@@ -216,6 +243,19 @@ int psm_sgm_download_costs(psm_ctx *c, int which, void *host)
     PSM_HIP(c, hipMemcpyAsync(dev.data(), which ? (const void *)c->sgm.S : (const void *)c->sgm.C, dev.size(), hipMemcpyDeviceToHost, c->stream));
     PSM_HIP(c, hipStreamSynchronize(c->stream));
     for (size_t p = 0; p < HW; ++p) memcpy((uint8_t *)host + p * D * el, dev.data() + p * Dp * el, D * el);      // the host layout has no padding
+    return 0;
+}
+
+int psm_sgm_download_prefiltered(psm_ctx *c, int side, uint8_t *planes)
+{
+    if (!c) return 1;
+    if (!planes) return fail(c, "psm_sgm_download_prefiltered: NULL buffer");
+    if (side != 0 && side != 1) return fail(c, "psm_sgm_download_prefiltered: side %d (0: left, 1: right)", side);
+    if (!c->sgm.have || c->sgm.pf_ch == 0)
+        return fail(c, "psm_sgm_download_prefiltered: the last psm_sgm_compute prefiltered nothing (psm_sgm_set_prefilter), or there is none");
+    if (bind(c)) return 1;
+    PSM_HIP(c, hipMemcpyAsync(planes, c->sgm.pf[side], (size_t)c->W * c->H * 2 * c->sgm.pf_ch, hipMemcpyDeviceToHost, c->stream));
+    PSM_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 

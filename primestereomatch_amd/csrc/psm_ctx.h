@@ -55,6 +55,10 @@ struct SgmState {
     unsigned *spk_label = nullptr, *spk_size = nullptr;
     bool spk_have = false;                         // spk_size holds the component sizes of a filter run
     int spk_t0 = -1;                               // the event ahead of the last filter run's launches (3 or 5); -1: it was not timed
+    // the prefiltered Birchfield-Tomasi cost (psm_sgm_set_prefilter): 12 W H bytes, allocated when first used
+    int cap = 0;                                   // pre_filter_cap; 0: the SAD cost
+    uint8_t *pf[2] = {nullptr, nullptr};           // the planes of both images, [H][W][2 ch] bytes (room for ch 3)
+    int pf_ch = 0;                                 // the channels of the planes the last compute wrote; 0: it wrote none
 };
 }  // namespace psm
 

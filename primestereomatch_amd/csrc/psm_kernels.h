@@ -227,9 +227,16 @@ struct SgmArgs {
     int16_t *pre, *out;                // [H][W] d16 (or -16: not unique) before the consistency test / the final map
     int W, H, D, Dp;                   // Dp: elements per pixel, D rounded up to a multiple of 4
     int bs, P1, P2, u, m;
+    // the prefiltered Birchfield-Tomasi cost (launch_sgm_cost_bt only; psm_sgm_set_prefilter)
+    uint8_t *pf[2];                    // prefiltered planes of both images, [H][W][2 ch] bytes: P_0 .. P_{ch-1}, Q_0 .. Q_{ch-1}
+    uint16_t *Hs;                      // horizontal block sums [H][W][Dp], in the memory of S (free until the first direction stores it)
+    int ft;                            // max(pre_filter_cap, 15) | 1
 };
 constexpr int SGM_DIRS[8][2] = {{0, 1}, {0, -1}, {1, 0}, {-1, 0}, {1, 1}, {1, -1}, {-1, 1}, {-1, -1}};   // (dy, dx)
+constexpr int SGM_BT_TX = 128;         // k_sgm_bt_rows: output pixels of a row per workgroup
+constexpr int SGM_BT_YS = 32;          // k_sgm_bt_cols: output rows per thread
 void launch_sgm_cost(hipStream_t s, const SgmArgs &a);
+void launch_sgm_cost_bt(hipStream_t s, const SgmArgs &a);                              // k_sgm_prefilter, k_sgm_bt_rows, k_sgm_bt_cols: the same C
 void launch_sgm_path(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first);     // S = L_r (first) or S += L_r
 void launch_sgm_select(hipStream_t s, const SgmArgs &a);                               // k_sgm_select + k_sgm_check (disp2 all ones before)
 

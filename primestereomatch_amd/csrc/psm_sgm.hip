@@ -7,8 +7,9 @@
 //   k_sgm_select  argmin_d S (lowest d), uniqueness, sub-pixel d16, disp2[y][x-best] = min (minS << 8 | best)
 //   k_sgm_check   the disp12MaxDiff test of every pixel against disp2 of its row -> int16 map, -16 where invalid
 // d is innermost in both volumes (Dp = D rounded up to 4 elements per pixel): the disparities of a pixel are one contiguous read
-// whatever the walking direction.  The speckle filter StereoSGBM ends with is psm_speckle.hip (psm_sgm_set_speckle).  Not here,
-// and open: the Sobel-prefiltered Birchfield-Tomasi cost.
+// whatever the walking direction.  The speckle filter StereoSGBM ends with is psm_speckle.hip (psm_sgm_set_speckle).  StereoSGBM's
+// own pixel cost, Birchfield-Tomasi over Sobel-prefiltered images (psm_sgm_set_prefilter, tests/sgm_bt_model.py), writes the same
+// C through k_sgm_prefilter, k_sgm_bt_rows and k_sgm_bt_cols below.  Unpinned: agreement with a live cv::StereoSGBM.
 #include "psm_kernels.h"
 
 #include <type_traits>
@@ -93,6 +94,152 @@ __global__ __launch_bounds__(256) void k_sgm_cost(SgmArgs a)
 #pragma unroll
             for (int i = 0; i < BS; ++i) sum += v[i];
             a.C[((size_t)y * a.W + x) * a.Dp + d] = (uint16_t)(real ? sum : 0u);
+        }
+    }
+}
+
+// ---- the prefiltered Birchfield-Tomasi cost (psm_sgm_set_prefilter, tests/sgm_bt_model.py): the same C by three kernels -------
+//   k_sgm_prefilter  both images -> their 2 ch planes per pixel (x-Sobel clipped to [0, 2 ft], the intensity; ft in the border columns)
+//   k_sgm_bt_rows    c(x,y,d) and its horizontal sum over the block's columns (replicated edge) -> Hs u16 [y][x][d], in S's memory
+//   k_sgm_bt_cols    the vertical sum of Hs over the block's rows (replicated edge), marching down the rows -> C
+// Every c is evaluated once (the bs - 1 columns two neighbouring tiles of SGM_BT_TX columns share: twice): a Birchfield-Tomasi
+// tap is ~13 packed operations per pair of planes, not the one v_sad_u8 k_sgm_cost repeats per block row.
+
+// k_sgm_prefilter: one thread per pixel of one image (blockIdx.z); a float image is quantised here, once
+__global__ __launch_bounds__(256) void k_sgm_prefilter(SgmArgs a)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, side = blockIdx.z;
+    if (x >= a.W) return;
+    const void *img = a.img[side];
+    const int ch = a.ch, ft = a.ft;
+    uint8_t *out = a.pf[side] + ((size_t)y * a.W + x) * (2 * ch);
+    if (x == 0 || x == a.W - 1) {
+        for (int i = 0; i < 2 * ch; ++i) out[i] = (uint8_t)ft;
+        return;
+    }
+    const int rows[3] = {max(y - 1, 0), y, min(y + 1, a.H - 1)};
+    unsigned w[3], e[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        w[j] = sgm_px(img, a.depth, ch, (size_t)rows[j] * a.W + x - 1);
+        e[j] = sgm_px(img, a.depth, ch, (size_t)rows[j] * a.W + x + 1);
+    }
+    const unsigned centre = sgm_px(img, a.depth, ch, (size_t)y * a.W + x);
+    for (int k = 0; k < ch; ++k) {
+        int g = 0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) g += (j == 1 ? 2 : 1) * ((int)((e[j] >> (8 * k)) & 255u) - (int)((w[j] >> (8 * k)) & 255u));
+        out[k] = (uint8_t)(min(max(g, -ft), ft) + ft);
+        out[ch + k] = (uint8_t)((centre >> (8 * k)) & 255u);
+    }
+}
+
+// Two adjacent planes of a pixel travel as the two 16-bit lanes of a dword (planes 2p, 2p + 1: pair p), so that one packed
+// instruction (v_pk_sub_i16, v_pk_max_i16, v_pk_min_i16) serves both; every value is in [-255, 255].
+typedef short sgm_s2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ sgm_s2 sgm_as_s2(unsigned v) { return __builtin_bit_cast(sgm_s2, v); }
+__device__ __forceinline__ unsigned sgm_as_u(sgm_s2 v) { return __builtin_bit_cast(unsigned, v); }
+__device__ __forceinline__ unsigned sgm_bt_pair(const uint8_t *p) { return (unsigned)p[0] | ((unsigned)p[1] << 16); }
+
+// pixel cx of a plane row ([W][2 NP] bytes) -> dst[(3 p + q) * stride], q = 0: the values, 1: lo, 2: hi (the half-sample bounds)
+template <int NP>
+__device__ __forceinline__ void sgm_bt_stage(const uint8_t *row, int W, int cx, unsigned *dst, int stride)
+{
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const uint8_t *q = row + ((size_t)cx * NP + p) * 2;
+        const unsigned v = sgm_bt_pair(q);
+        const unsigned vl = cx > 0 ? ((v + sgm_bt_pair(q - 2 * NP)) >> 1) & 0x00ff00ffu : v;          // (a lane's sum <= 510: no carry)
+        const unsigned vr = cx < W - 1 ? ((v + sgm_bt_pair(q + 2 * NP)) >> 1) & 0x00ff00ffu : v;
+        const sgm_s2 s = sgm_as_s2(v), sl = sgm_as_s2(vl), sr = sgm_as_s2(vr);
+        dst[(3 * p) * stride] = v;
+        dst[(3 * p + 1) * stride] = sgm_as_u(__builtin_elementwise_min(s, __builtin_elementwise_min(sl, sr)));
+        dst[(3 * p + 2) * stride] = sgm_as_u(__builtin_elementwise_max(s, __builtin_elementwise_max(sl, sr)));
+    }
+}
+
+// One workgroup per SGM_BT_TX pixels of one row, one thread per disparity, as k_sgm_cost - but one image row only: a thread walks
+// x with its d fixed, evaluates c(x, y, d) once and keeps the last BS of them in registers.  LDS holds, per pixel and pair of
+// planes, the values and both bounds of the left tile and of the part of the right row the tile's disparities reach; the left
+// operands are broadcasts, the right ones of neighbouring lanes neighbouring dwords.  NP pairs of planes: ch = NP (1 or 3); plane
+// i has shift 0 below ch (P), 2 from ch on (Q).  out: Hs, or C itself when BS is 1.
+template <int BS, int NP>
+__global__ __launch_bounds__(256) void k_sgm_bt_rows(SgmArgs a, uint16_t *out)
+{
+    constexpr int HALF = BS / 2, NL = SGM_BT_TX + BS - 1, NR = NL + 255, NQ = 3 * NP;
+    __shared__ unsigned sl[NQ][NL], sr[NQ][NR];
+    const int y = blockIdx.y, x0 = blockIdx.x * SGM_BT_TX, d = threadIdx.x;
+    const int cx_min = sgm_clamp(x0 - HALF, a.W);
+    const int rbase = cx_min - (a.D - 1);                 // image column of sr[.][0]
+    const int nr = NL + a.D - 1;
+    const uint8_t *rowl = a.pf[0] + (size_t)y * a.W * (2 * NP), *rowr = a.pf[1] + (size_t)y * a.W * (2 * NP);
+    for (int i = threadIdx.x; i < NL; i += blockDim.x) sgm_bt_stage<NP>(rowl, a.W, sgm_clamp(x0 - HALF + i, a.W), &sl[0][i], NL);
+    for (int i = threadIdx.x; i < nr; i += blockDim.x) sgm_bt_stage<NP>(rowr, a.W, sgm_clamp(rbase + i, a.W), &sr[0][i], NR);
+    __syncthreads();
+    if (d >= a.Dp) return;
+    const bool real = d < a.D;
+    const int ns = min(NL, a.W - x0 + BS - 1);            // the steps up to the row's last pixel
+    const sgm_s2 zero = {0, 0};
+    unsigned v[BS];
+#pragma unroll
+    for (int i = 0; i < BS; ++i) v[i] = 0;
+    for (int s = 0; s < ns; ++s) {
+        const int cx = sgm_clamp(x0 - HALF + s, a.W);
+        const int k = max(cx - (real ? d : 0), 0) - rbase;
+        unsigned col = 0;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const sgm_s2 u = sgm_as_s2(sl[3 * p][s]), lu = sgm_as_s2(sl[3 * p + 1][s]), hu = sgm_as_s2(sl[3 * p + 2][s]);
+            const sgm_s2 w = sgm_as_s2(sr[3 * p][k]), lw = sgm_as_s2(sr[3 * p + 1][k]), hw = sgm_as_s2(sr[3 * p + 2][k]);
+            const sgm_s2 c0 = __builtin_elementwise_max(__builtin_elementwise_max(u - hw, lw - u), zero);
+            const sgm_s2 c1 = __builtin_elementwise_max(__builtin_elementwise_max(w - hu, lu - w), zero);
+            const unsigned m = sgm_as_u(__builtin_elementwise_min(c0, c1));
+            constexpr int CH = NP;
+            const int s0 = 2 * p >= CH ? 2 : 0, s1 = 2 * p + 1 >= CH ? 2 : 0;
+            col += ((m & 0xffffu) >> s0) + (m >> (16 + s1));
+        }
+#pragma unroll
+        for (int i = 0; i + 1 < BS; ++i) v[i] = v[i + 1];
+        v[BS - 1] = col;
+        if (s >= BS - 1) {
+            unsigned sum = 0;
+#pragma unroll
+            for (int i = 0; i < BS; ++i) sum += v[i];
+            out[((size_t)y * a.W + (x0 + s - (BS - 1))) * a.Dp + d] = (uint16_t)(real ? sum : 0u);
+        }
+    }
+}
+
+// The vertical sum: a thread holds four adjacent disparities of one pixel column (8 bytes: Dp is a multiple of 4) and marches
+// down SGM_BT_YS rows; the last BS rows of Hs stay in registers, a step is one load, one add, one subtract and one store.  Two
+// 16-bit sums share a dword: every result is at most 65535 (psm_sgm_set_params), and the 32-bit arithmetic is exact modulo 2^32,
+// so no carry survives between the halves.  Only the BS - 1 rows two segments share are loaded twice.
+template <int BS>
+__global__ __launch_bounds__(256) void k_sgm_bt_cols(SgmArgs a)
+{
+    constexpr int HALF = BS / 2;
+    const size_t rowq = (size_t)a.W * a.Dp / 4;           // uint2 per row
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= rowq) return;
+    const int y0 = blockIdx.y * SGM_BT_YS, y1 = min(y0 + SGM_BT_YS, a.H);
+    const uint2 *src = (const uint2 *)a.Hs + e;
+    uint2 *dst = (uint2 *)a.C + e;
+    uint2 ring[BS], sum = make_uint2(0u, 0u);
+#pragma unroll
+    for (int j = 0; j < BS; ++j) {
+        ring[j] = src[(size_t)sgm_clamp(y0 - HALF + j, a.H) * rowq];
+        sum.x += ring[j].x; sum.y += ring[j].y;
+    }
+    dst[(size_t)y0 * rowq] = sum;
+    for (int y = y0 + 1; y < y1; y += BS) {
+#pragma unroll
+        for (int r = 0; r < BS; ++r) {
+            if (y + r < y1) {
+                const uint2 n = src[(size_t)sgm_clamp(y + r + HALF, a.H) * rowq];
+                sum.x += n.x - ring[r].x; sum.y += n.y - ring[r].y;
+                ring[r] = n;
+                dst[(size_t)(y + r) * rowq] = sum;
+            }
         }
     }
 }
@@ -274,6 +421,30 @@ void launch_sgm_cost(hipStream_t s, const SgmArgs &a)
     case 3: hipLaunchKernelGGL(k_sgm_cost<3>, grid, block, 0, s, a); break;
     case 5: hipLaunchKernelGGL(k_sgm_cost<5>, grid, block, 0, s, a); break;
     default: hipLaunchKernelGGL(k_sgm_cost<7>, grid, block, 0, s, a); break;
+    }
+}
+
+template <int BS>
+static void launch_bt_bs(hipStream_t s, const SgmArgs &a)
+{
+    const dim3 grid((a.W + SGM_BT_TX - 1) / SGM_BT_TX, a.H), block((a.D + 63) / 64 * 64);
+    uint16_t *out = BS == 1 ? a.C : a.Hs;                 // (a 1 x 1 block has no vertical sum)
+    if (a.ch == 1) hipLaunchKernelGGL((k_sgm_bt_rows<BS, 1>), grid, block, 0, s, a, out);
+    else hipLaunchKernelGGL((k_sgm_bt_rows<BS, 3>), grid, block, 0, s, a, out);
+    if constexpr (BS > 1) {
+        const size_t rowq = (size_t)a.W * a.Dp / 4;
+        hipLaunchKernelGGL(k_sgm_bt_cols<BS>, dim3((unsigned)((rowq + 255) / 256), (a.H + SGM_BT_YS - 1) / SGM_BT_YS), dim3(256), 0, s, a);
+    }
+}
+
+void launch_sgm_cost_bt(hipStream_t s, const SgmArgs &a)
+{
+    hipLaunchKernelGGL(k_sgm_prefilter, dim3((a.W + 255) / 256, a.H, 2), dim3(256), 0, s, a);
+    switch (a.bs) {
+    case 1: launch_bt_bs<1>(s, a); break;
+    case 3: launch_bt_bs<3>(s, a); break;
+    case 5: launch_bt_bs<5>(s, a); break;
+    default: launch_bt_bs<7>(s, a); break;
     }
 }
 

@@ -26,6 +26,8 @@ def _ptr(a):
 
 
 class DispEst:
+    _sgm_ch = 3                                  # the channels of the pair the last SGBM_GPU ran on (1: its gray= pair)
+
     def __init__(self, l, r, d: int, t: int = 8, ocl: bool = True, *, dtype: str = "f32",
                  device: int = 0, d_range=None, d_stride=None):
         """l, r: H x W x 3 images (uint8 as loaded by imread, or float32 scaled by 1/255 as
@@ -138,16 +140,20 @@ class DispEst:
 
     # ---- the second algorithm: STEREO_SGBM (src/StereoMatch.cpp:169-187) ----------------------
     def SGBM_GPU(self, block_size: int = 0, P1: int = 0, P2: int = 0, uniqueness_ratio: int = 10, disp12_max_diff: int = 1,
-                 gray=None, speckle_window_size: int = 0, speckle_range: int = 0):
+                 gray=None, speckle_window_size: int = 0, speckle_range: int = 0, pre_filter_cap: int = 0):
         """ssgbm->compute(lFrame, rFrame, imgDisparity16S) on the device over the pair setInputImages staged, with the
         parameters of setupOpenCVSGBM (src/StereoMatch.cpp:639-660) as defaults (0: blockSize 5, P1 = 8 ch bs^2, P2 = 32 ch bs^2).
         -> H x W int16: disparity * 16, -16 where invalid.  An independent stage (psm_sgm_compute): the maps, masks and volumes
         of the other methods are untouched.  gray = (l, r): run on that H x W uint8 pair instead (CV_8UC1 frames).
         speckle_window_size > 0: the map goes through StereoSGBM's last step, filterSpeckles(map, -16, speckle_window_size,
-        16 * speckle_range) (the reference: 100, 32); 0, the default: off - the setting is this call's, not the object's."""
+        16 * speckle_range) (the reference: 100, 32); 0, the default: off - the setting is this call's, not the object's.
+        pre_filter_cap in 1 .. 63: StereoSGBM's pixel cost, Birchfield-Tomasi over Sobel-prefiltered images (psm_sgm_set_prefilter;
+        the reference: 63); 0, the default: SAD - this call's setting too."""
+        self._ck(self._lib.psm_sgm_set_prefilter(self._h, int(pre_filter_cap)), "SGBM_GPU")
         self._ck(self._lib.psm_sgm_set_speckle(self._h, int(speckle_window_size), int(speckle_range)), "SGBM_GPU")
         self._ck(self._lib.psm_sgm_set_params(self._h, int(block_size), int(P1), int(P2), int(uniqueness_ratio),
                                               int(disp12_max_diff)), "SGBM_GPU")
+        self._sgm_ch = 3 if gray is None else 1
         if gray is None:
             self._ck(self._lib.psm_sgm_compute(self._h), "SGBM_GPU")
         else:
@@ -170,6 +176,14 @@ class DispEst:
         self._ck(self._lib.psm_sgm_download_costs(self._h, 0, _ptr(Cv)), "sgm_costs")
         self._ck(self._lib.psm_sgm_download_costs(self._h, 1, _ptr(Sv)), "sgm_costs")
         return Cv, Sv
+
+    def sgm_prefiltered(self, side: int):
+        """Test hook: the prefiltered planes [H][W][2 ch] uint8 (P_0 .. P_{ch-1}, Q_0 .. Q_{ch-1}) of the left (side 0) or right
+        (1) image in the last SGBM_GPU, which must have run with pre_filter_cap > 0; ch: 3, or 1 for a gray pair."""
+        planes = np.empty((self.hei, self.wid, 6), np.uint8)           # (room for either channel count)
+        self._ck(self._lib.psm_sgm_download_prefiltered(self._h, int(side), _ptr(planes)), "sgm_prefiltered")
+        ch = self._sgm_ch
+        return planes.reshape(-1)[:self.hei * self.wid * 2 * ch].reshape(self.hei, self.wid, 2 * ch).copy()
 
     def sgm_times(self):
         """(cost, paths, select + check) device ms of the last SGBM_GPU; needs PSM_OPT_PROFILE."""

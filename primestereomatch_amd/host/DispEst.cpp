@@ -237,6 +237,12 @@ int DispEst::setSGBMSpeckle(int speckleWindowSize, int speckleRange)
     return hipUtil::api().sgm_set_speckle(ctx[0], speckleWindowSize, speckleRange);
 }
 
+int DispEst::setSGBMPreFilterCap(int preFilterCap)
+{
+    if (ctx.empty()) return 1;
+    return hipUtil::api().sgm_set_prefilter(ctx[0], preFilterCap);
+}
+
 int DispEst::sgbmSpeckleTime(double *ms)
 {
     if (ctx.empty()) return 1;

@@ -115,6 +115,9 @@ public:
     // the last timed SGBM_GPU.
     int setSGBMSpeckle(int speckleWindowSize, int speckleRange);
     int sgbmSpeckleTime(double *ms);
+    // StereoSGBM's pixel cost for every following SGBM_GPU: Birchfield-Tomasi over Sobel-prefiltered images, preFilterCap in 1 .. 63
+    // (setupOpenCVSGBM: 63).  0, the setting of a new object: the SAD cost.
+    int setSGBMPreFilterCap(int preFilterCap);
 
     // Frame loop (src/main.cpp:64-73) with the PCIe legs next to the kernels (single-device hosts): one call per frame -
     // CostConst (adopts the pair staged by the previous call), stages `next` pair (may be NULL at the end of the stream: its

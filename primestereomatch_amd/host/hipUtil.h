@@ -55,6 +55,7 @@ struct HipApi {
     int (*sgm_filter_speckles)(psm_ctx *, int16_t *, size_t, int, int, int) = nullptr;
     int (*sgm_download_speckle_sizes)(psm_ctx *, int32_t *, size_t) = nullptr;
     int (*sgm_speckle_time)(psm_ctx *, double *) = nullptr;
+    int (*sgm_set_prefilter)(psm_ctx *, int) = nullptr;
 };
 
 class hipUtil {

@@ -1,8 +1,10 @@
 // psm_demo - headless counterpart of the reference's StereoMatch::compute accelerator branch
 // (src/StereoMatch.cpp:193-262): raw B,G,R uint8 pair in, four timed stages, raw uint8 maps out.
-//   psm_demo <left.raw> <right.raw> <W> <H> <maxDis> <out_prefix> [ndev] [f32|u8] [float_input] [fgf_rate] [pp] [frames] [batch] [ring] [sgbm]
+//   psm_demo <left.raw> <right.raw> <W> <H> <maxDis> <out_prefix> [ndev] [f32|u8] [float_input] [fgf_rate] [pp] [frames] [batch] [ring] [sgbm|sgbm_ref]
 // sgbm: the 15th argument, the word "sgbm": additionally run the second algorithm (DispEst::SGBM_GPU: the STEREO_SGBM branch,
-// src/StereoMatch.cpp:169-187) on the pair, print its three device times and dump the int16 map as <out>_sgbm16.raw
+// src/StereoMatch.cpp:169-187) on the pair, print its three device times and dump the int16 map as <out>_sgbm16.raw (the SAD
+// cost, no speckle filter); the word "sgbm_ref": the same with the whole configuration of setupOpenCVSGBM (:639-660) -
+// preFilterCap 63, speckleWindowSize 100, speckleRange 32 - and the filter's time as a fourth line
 // ring > 0: additionally push that many frames of the pair through a psm::FrameRing of two objects (two frames in flight, each
 // object told PSM_OPT_FRAMES_IN_FLIGHT = 2), check every delivered frame's maps against the single-pair run, dump <out>_ldisp_ring.raw
 // batch > 1: additionally run that many copies of the pair as ONE batch (DispEst::computeBatch -> psm_compute_batch: the
@@ -43,7 +45,7 @@ static bool dump(const std::string &path, const unsigned char *p, size_t n)
 int main(int argc, char **argv)
 {
     if (argc < 7) {
-        fprintf(stderr, "usage: %s left.raw right.raw W H maxDis out_prefix [ndev] [f32|u8] [float_input] [fgf_rate] [pp] [frames] [batch] [ring] [sgbm]\n", argv[0]);
+        fprintf(stderr, "usage: %s left.raw right.raw W H maxDis out_prefix [ndev] [f32|u8] [float_input] [fgf_rate] [pp] [frames] [batch] [ring] [sgbm|sgbm_ref]\n", argv[0]);
         return 2;
     }
     const int W = atoi(argv[3]), H = atoi(argv[4]), D = atoi(argv[5]);
@@ -56,7 +58,8 @@ int main(int argc, char **argv)
     const int frames = argc > 12 ? atoi(argv[12]) : 0;
     const int batch = argc > 13 ? atoi(argv[13]) : 0;
     const int nring = argc > 14 ? atoi(argv[14]) : 0;
-    const bool sgbm = argc > 15 && !strcmp(argv[15], "sgbm");
+    const bool sgbm_ref = argc > 15 && !strcmp(argv[15], "sgbm_ref");
+    const bool sgbm = sgbm_ref || (argc > 15 && !strcmp(argv[15], "sgbm"));
     std::vector<unsigned char> lraw, rraw;
     if (!slurp(argv[1], lraw, (size_t)W * H * 3) || !slurp(argv[2], rraw, (size_t)W * H * 3)) {
         fprintf(stderr, "psm_demo: cannot read the input pair\n");
@@ -153,8 +156,14 @@ int main(int argc, char **argv)
         std::vector<int16_t> d16;
         double ms[3] = {0, 0, 0};
         SMDE.setInputImages(l, r);
+        if (sgbm_ref && (SMDE.setSGBMPreFilterCap(63) || SMDE.setSGBMSpeckle(100, 32))) return 5;
         if (SMDE.setOption(PSM_OPT_PROFILE, 1) || SMDE.SGBM_GPU(d16) || SMDE.sgbmTimes(ms)) return 5;
         printf("STEREO SGBM Times:\nCost Time:\t %4.3f ms\nPaths Time:\t %4.3f ms\nSelect Time:\t %4.3f ms\n", ms[0], ms[1], ms[2]);
+        if (sgbm_ref) {
+            double spk = 0;
+            if (SMDE.sgbmSpeckleTime(&spk)) return 5;
+            printf("Speckle Time:\t %4.3f ms\n", spk);
+        }
         ok = dump(out + "_sgbm16.raw", (const unsigned char *)d16.data(), d16.size() * sizeof(int16_t));
     }
     return ok ? 0 : 6;

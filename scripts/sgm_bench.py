@@ -14,7 +14,11 @@ that and needs no GPU (the large pairs take minutes and gigabytes).
 The speckle filter (psm_sgm_set_speckle; k_spk_runs, k_spk_merge, k_spk_count, k_spk_apply): every configuration is timed twice in
 the same process, with the filter off (the record above, unchanged) and on at the reference's (100, 32) - "speckle_ms", the median
 of psm_sgm_speckle_time, and the three group times of those runs as "*_ms_speckle_on".  --speckle-maps: also two 1920 x 1080
-maps through psm_sgm_filter_speckles at (-16, 100, 512): a serpentine (the whole image one path) and a constant map."""
+maps through psm_sgm_filter_speckles at (-16, 100, 512): a serpentine (the whole image one path) and a constant map.
+
+The prefiltered Birchfield-Tomasi cost (psm_sgm_set_prefilter; k_sgm_prefilter, k_sgm_bt_rows, k_sgm_bt_cols): every configuration
+is timed a third time in the same process at pre_filter_cap 63 with the filter off - the three group times as "*_ms_cap63" (the
+cost group holds the prefilter), their ratio to the SAD cost group, and the 12 W H bytes of planes the stage then holds."""
 import argparse
 import json
 import os
@@ -123,8 +127,16 @@ def main():
                     ts.append(de.sgm_times())
                     tk.append(de.sgm_speckle_time())
                 removed = int(np.count_nonzero(de.sgm_disparity() != disp))
+                for _ in range(a.warmup):
+                    de.SGBM_GPU(pre_filter_cap=63)
+                tb = []
+                for _ in range(a.runs):
+                    de._ck(de._lib.psm_sgm_compute(de._h), "psm_sgm_compute")      # (the setting holds)
+                    tb.append(de.sgm_times())
+                valid_bt = float((de.sgm_disparity() >= 0).mean())
             t = np.array(t)
             meds = np.median(np.array(ts), axis=0)
+            medb = np.median(np.array(tb), axis=0)
             med = np.median(t, axis=0)
             total = float(np.median(t.sum(axis=1)))
             rec.update({"runs": a.runs, "warmup": a.warmup, "cost_ms": round(float(med[0]), 4), "paths_ms": round(float(med[1]), 4),
@@ -134,7 +146,11 @@ def main():
                         "device_bytes_held": int(held), "valid_fraction": round(float((disp >= 0).mean()), 4),
                         "speckle_ms": round(float(np.median(tk)), 4), "speckle_ms_min_max": [round(min(tk), 4), round(max(tk), 4)],
                         "cost_ms_speckle_on": round(float(meds[0]), 4), "paths_ms_speckle_on": round(float(meds[1]), 4),
-                        "select_ms_speckle_on": round(float(meds[2]), 4), "speckle_pixels_removed": removed})
+                        "select_ms_speckle_on": round(float(meds[2]), 4), "speckle_pixels_removed": removed,
+                        "cost_ms_cap63": round(float(medb[0]), 4), "paths_ms_cap63": round(float(medb[1]), 4),
+                        "select_ms_cap63": round(float(medb[2]), 4), "cost_cap63_over_sad": round(float(medb[0] / med[0]), 2),
+                        "cost_cap63_over_paths": round(float(medb[0] / medb[1]), 3), "prefiltered_bytes_held": 12 * W * H,
+                        "valid_fraction_cap63": round(valid_bt, 4)})
         if a.model or a.model_only:
             rec["numpy_model_s"] = round(model_seconds(l, r, D), 2)
         line = json.dumps(rec)
