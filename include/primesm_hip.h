@@ -374,6 +374,30 @@ int psm_sgm_download_speckle_sizes(psm_ctx *ctx, int32_t *sizes, size_t stride_b
  * (the copies of the map excluded) and then is what this reports. */
 int psm_sgm_speckle_time(psm_ctx *ctx, double *ms);
 
+/* psm_sgm_compute of the n contexts ctxs[0..n) in shared launches: every kernel of the stage - cost or prefilter + Birchfield-Tomasi
+ * cost, the eight paths, select, check, the four of the speckle filter - runs once with the pair on a grid axis of its own, so a
+ * path launch has n x (H, W or W + H - 1) one-wave paths instead of one pair's.  The reference's use on Middlebury-size data is a
+ * loop over pairs and datasets (src/main.cpp:64-73, src/StereoMatch.cpp:528-609); there the stage is bound by the waves it has in
+ * flight, not by bytes.  Measured at 450 x 375 x 64 with the reference's configuration
+ * (cap 63, speckle 100 / 32): 0.569 ms per pair one context after the other, 0.276 ms per pair in a batch of 8 (0.356 in a batch
+ * of 2); at 1280 x 720 x 128 0.98 of the singles in a batch of 8, at 1920 x 1080 x 256 0.96 in a batch of 4.
+ * Each context holds its own pair, exactly the one its own psm_sgm_compute would read at that moment, and afterwards is exactly
+ * where that call would have left it: psm_sgm_download_disparity / _costs / _prefiltered / _speckle_sizes, a later single
+ * psm_sgm_compute and psm_sgm_filter_speckles work per context and return the same bits.  Volumes, maps, masks and minima of the
+ * other entry points are untouched; the call may stand anywhere between them.
+ * The contexts must agree on width, height, max_disp and device, on the depth of the staged pair (a float pair is quantised on the
+ * device, as ever) and on every setting of psm_sgm_set_params, psm_sgm_set_prefilter and psm_sgm_set_speckle.  Refused otherwise,
+ * and for NULL or repeated contexts, n < 1 or n > 4096, a context without a pair, a disparity shard, a row stripe in force and
+ * parameters psm_sgm_set_params would refuse: psm_last_error(ctxs[0]) names the offending index, nothing has been enqueued, and
+ * every context's previous result is still readable.
+ * The launches run on ctxs[0]'s stream, after everything already queued on the other contexts' streams and before anything queued
+ * on them later; synchronous on return unless ctxs[0] has PSM_OPT_ASYNC.  Contexts under psm_share_streams work as they are.
+ * Buffers stay per context (allocated on first use, given back by psm_release_scratch / psm_destroy); the kernels reach them
+ * through a device table of n * 88 bytes that ctxs[0] owns and uploads again only when an entry changed.  With PSM_OPT_PROFILE on
+ * ctxs[0], psm_sgm_times(ctxs[0]) and psm_sgm_speckle_time(ctxs[0]) report the batch's launches; the other contexts count as not
+ * timed.  psm_sgm_compute_gray has no batch form: it takes host pointers and stages them itself. */
+int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n);
+
 /* "next" row: PP lrCheck on the device (src/PP.cpp:17-50) on the maps of the last
  * psm_disp_select/psm_disp_merge.  lvalid/rvalid: H x W bytes (0/1), pitch `stride`; either
  * may be NULL (results stay on the device). */

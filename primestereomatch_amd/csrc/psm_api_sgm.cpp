@@ -6,8 +6,10 @@
 // psm_sgm_set_speckle turned it on, on a caller's map in psm_sgm_filter_speckles (tests/speckle_model.py).  The pixel cost is SAD
 // (pre_filter_cap 0, a new context's setting) or, after psm_sgm_set_prefilter, StereoSGBM's Sobel-prefiltered Birchfield-Tomasi
 // cost as tests/sgm_bt_model.py defines it (the reference: preFilterCap 63).  Unpinned in all of it: a live cv::StereoSGBM.
+// psm_sgm_compute_batch: the same launches for the pairs of several contexts at once, the pair on a grid axis of its own.
 #include "psm_ctx.h"
 
+#include <cstdio>
 #include <cstring>
 
 using namespace psm;
@@ -28,6 +30,12 @@ void sgm_free(psm_ctx *c)
     for (uint8_t *&p : g.pf) { (void)hipFree(p); p = nullptr; }
     g.pf_ch = 0;
     for (hipEvent_t &e : g.ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    (void)hipFree(g.tab); g.tab = nullptr;
+    if (g.tab_pin) (void)hipHostFree(g.tab_pin);
+    g.tab_pin = nullptr;
+    g.tab_cap = 0;
+    g.tab_host.clear();
+    for (hipEvent_t &e : g.ev_tab) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     g.have = g.timed = g.spk_have = false;
     g.spk_t0 = -1;
 }
@@ -52,11 +60,12 @@ int check_params(psm_ctx *c, const char *who, int ch, int bs, int *p1, int *p2, 
     return 0;
 }
 
-int check_ctx(psm_ctx *c, const char *who)
+// e: the context that receives the message (a batch: its first; who then names the member)
+int check_ctx(psm_ctx *e, const psm_ctx *c, const char *who)
 {
-    if (c->Dloc != c->D || strided(c)) return fail(c, "%s: a disparity shard holds part of the range (the paths need every disparity of a pixel)", who);
-    if (c->march.yend > c->march.ybeg) return fail(c, "%s: a row stripe is in force (psm_set_rows): the paths cross the whole image", who);
-    if (c->D < 2) return fail(c, "%s: max_disp %d < 2", who, c->D);
+    if (c->Dloc != c->D || strided(c)) return fail(e, "%s: a disparity shard holds part of the range (the paths need every disparity of a pixel)", who);
+    if (c->march.yend > c->march.ybeg) return fail(e, "%s: a row stripe is in force (psm_set_rows): the paths cross the whole image", who);
+    if (c->D < 2) return fail(e, "%s: max_disp %d < 2", who, c->D);
     return 0;
 }
 
@@ -69,10 +78,51 @@ int ensure_buffers(psm_ctx *c)
     if (!g.disp2) PSM_HIP(c, hipMalloc((void **)&g.disp2, HW * sizeof(uint32_t)));
     if (!g.pre) PSM_HIP(c, hipMalloc((void **)&g.pre, HW * sizeof(int16_t)));
     if (!g.out) PSM_HIP(c, hipMalloc((void **)&g.out, HW * sizeof(int16_t)));
+    if (g.cap > 0)
+        for (uint8_t *&p : g.pf)
+            if (!p) PSM_HIP(c, hipMalloc((void **)&p, HW * 6));
     if (c->opt_profile)
         for (hipEvent_t &e : g.ev)
             if (!e) PSM_HIP(c, hipEventCreate(&e));
     return 0;
+}
+
+// the context's buffers (ensure_buffers) and settings as the kernels take them
+SgmArgs sgm_args(const psm_ctx *c, const void *l, const void *r, int depth, int ch, int p1, int p2)
+{
+    const SgmState &g = c->sgm;
+    SgmArgs a;
+    a.img[0] = l; a.img[1] = r; a.depth = depth; a.ch = ch;
+    a.C = g.C; a.S = g.S; a.disp2 = g.disp2; a.pre = g.pre; a.out = g.out;
+    a.W = c->W; a.H = c->H; a.D = c->D; a.Dp = sgm_dp(c);
+    a.bs = g.bs; a.P1 = p1; a.P2 = p2; a.u = g.u; a.m = g.m;
+    a.pf[0] = a.pf[1] = nullptr; a.Hs = nullptr; a.ft = 0;
+    if (g.cap > 0) {
+        a.pf[0] = g.pf[0]; a.pf[1] = g.pf[1];
+        a.Hs = (uint16_t *)g.S;                           // S is free until the first direction stores it
+        a.ft = (g.cap > 15 ? g.cap : 15) | 1;
+    }
+    return a;
+}
+
+int ensure_speckle_planes(psm_ctx *c)
+{
+    SgmState &g = c->sgm;
+    const size_t HW = (size_t)c->W * c->H;
+    if (!g.spk_label) PSM_HIP(c, hipMalloc((void **)&g.spk_label, HW * sizeof(unsigned)));
+    if (!g.spk_size) PSM_HIP(c, hipMalloc((void **)&g.spk_size, HW * sizeof(unsigned)));
+    return 0;
+}
+
+// the filter's settings as the kernels take them (the planes: the caller's)
+SpkArgs speckle_args(const psm_ctx *c, int new_val, int max_size, long long max_diff)
+{
+    SpkArgs a;
+    a.map = nullptr; a.label = nullptr; a.size = nullptr;
+    a.W = c->W; a.H = c->H;
+    a.new_val = new_val; a.max_size = max_size;
+    a.max_diff = (int)(max_diff > 65535 ? 65535 : max_diff);      // (two int16 values differ by 65535 at most)
+    return a;
 }
 
 // The speckle filter on `map` (a device plane of the context's size) in place, on the context's stream: four launches, nothing
@@ -80,14 +130,9 @@ int ensure_buffers(psm_ctx *c)
 int enqueue_speckle(psm_ctx *c, int16_t *map, int new_val, int max_size, long long max_diff, int t0)
 {
     SgmState &g = c->sgm;
-    const size_t HW = (size_t)c->W * c->H;
-    if (!g.spk_label) PSM_HIP(c, hipMalloc((void **)&g.spk_label, HW * sizeof(unsigned)));
-    if (!g.spk_size) PSM_HIP(c, hipMalloc((void **)&g.spk_size, HW * sizeof(unsigned)));
-    SpkArgs a;
+    if (ensure_speckle_planes(c)) return 1;
+    SpkArgs a = speckle_args(c, new_val, max_size, max_diff);
     a.map = map; a.label = g.spk_label; a.size = g.spk_size;
-    a.W = c->W; a.H = c->H;
-    a.new_val = new_val; a.max_size = max_size;
-    a.max_diff = (int)(max_diff > 65535 ? 65535 : max_diff);      // (two int16 values differ by 65535 at most)
     g.spk_have = false;
     g.spk_t0 = -1;
     launch_speckle(c->stream, a);
@@ -105,19 +150,7 @@ int enqueue(psm_ctx *c, const char *who, const void *l, const void *r, int depth
     int p1 = g.p1, p2 = g.p2;
     if (check_params(c, who, ch, g.bs, &p1, &p2, g.u)) return 1;
     if (ensure_buffers(c)) return 1;
-    SgmArgs a;
-    a.img[0] = l; a.img[1] = r; a.depth = depth; a.ch = ch;
-    a.C = g.C; a.S = g.S; a.disp2 = g.disp2; a.pre = g.pre; a.out = g.out;
-    a.W = c->W; a.H = c->H; a.D = c->D; a.Dp = sgm_dp(c);
-    a.bs = g.bs; a.P1 = p1; a.P2 = p2; a.u = g.u; a.m = g.m;
-    a.pf[0] = a.pf[1] = nullptr; a.Hs = nullptr; a.ft = 0;
-    if (g.cap > 0) {
-        for (uint8_t *&p : g.pf)
-            if (!p) PSM_HIP(c, hipMalloc((void **)&p, (size_t)c->W * c->H * 6));
-        a.pf[0] = g.pf[0]; a.pf[1] = g.pf[1];
-        a.Hs = (uint16_t *)g.S;                           // S is free until the first direction stores it
-        a.ft = (g.cap > 15 ? g.cap : 15) | 1;
-    }
+    const SgmArgs a = sgm_args(c, l, r, depth, ch, p1, p2);
     const bool timed = c->opt_profile != 0;
     g.have = g.timed = false;
     g.spk_t0 = -1;
@@ -185,7 +218,7 @@ int psm_sgm_set_prefilter(psm_ctx *c, int pre_filter_cap)
 int psm_sgm_compute(psm_ctx *c)
 {
     if (!c) return 1;
-    if (check_ctx(c, "psm_sgm_compute")) return 1;
+    if (check_ctx(c, c, "psm_sgm_compute")) return 1;
     if (c->raw_depth < 0) return fail(c, "psm_sgm_compute: no image pair (psm_upload_pair)");
     if (bind(c)) return 1;
     return enqueue(c, "psm_sgm_compute", c->raw[0], c->raw[1], c->raw_depth, 3);
@@ -194,7 +227,7 @@ int psm_sgm_compute(psm_ctx *c)
 int psm_sgm_compute_gray(psm_ctx *c, const uint8_t *l, const uint8_t *r, size_t stride_bytes)
 {
     if (!c) return 1;
-    if (check_ctx(c, "psm_sgm_compute_gray")) return 1;
+    if (check_ctx(c, c, "psm_sgm_compute_gray")) return 1;
     if (!l || !r) return fail(c, "psm_sgm_compute_gray: NULL image");
     const size_t row = (size_t)c->W;
     if (stride_bytes == 0) stride_bytes = row;
@@ -208,6 +241,137 @@ int psm_sgm_compute_gray(psm_ctx *c, const uint8_t *l, const uint8_t *r, size_t 
     }
     PSM_HIP(c, hipStreamSynchronize(c->stream));      // the copy reads caller memory (psm_upload_pair)
     return enqueue(c, "psm_sgm_compute_gray", g.gray[0], g.gray[1], PSM_IMG_U8, 1);
+}
+
+// The launches of psm_sgm_compute with the pair on a grid axis of its own: n x (H, W or W + H - 1) one-wave paths per path launch
+// instead of one pair's 375 to 824 on 1024 SIMDs ("several pairs per launch").  Buffers stay per context; the kernels
+// reach them through a device table ctxs[0] owns.  Every context ends where its own psm_sgm_compute would have left it.
+int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
+{
+    const char *who = "psm_sgm_compute_batch";
+    if (!ctxs || n < 1 || !ctxs[0]) return fail(nullptr, "%s: bad arguments", who);
+    psm_ctx *c0 = ctxs[0];
+    if (n > 4096) return fail(c0, "%s: %d pairs (at most 4096 per call)", who, n);
+    const SgmState &g0 = c0->sgm;
+    for (int i = 0; i < n; ++i) {
+        psm_ctx *c = ctxs[i];
+        if (!c) return fail(c0, "%s: context %d is NULL", who, i);
+        for (int j = 0; j < i; ++j)
+            if (ctxs[j] == c) return fail(c0, "%s: context %d appears twice", who, i);
+        if (c->W != c0->W || c->H != c0->H || c->D != c0->D || c->device != c0->device)
+            return fail(c0, "%s: context %d has another width / height / max_disp / device than context 0", who, i);
+        char member[64];
+        snprintf(member, sizeof member, "%s: context %d", who, i);
+        if (check_ctx(c0, c, member)) return 1;
+        if (c->raw_depth < 0) return fail(c0, "%s: context %d has no image pair (psm_upload_pair)", who, i);
+        if (c->raw_depth != c0->raw_depth) return fail(c0, "%s: context %d holds images of another depth than context 0", who, i);
+        const SgmState &g = c->sgm;
+        if (g.bs != g0.bs || g.p1 != g0.p1 || g.p2 != g0.p2 || g.u != g0.u || g.m != g0.m)
+            return fail(c0, "%s: context %d has other parameters (psm_sgm_set_params) than context 0", who, i);
+        if (g.cap != g0.cap) return fail(c0, "%s: context %d has another pre_filter_cap (%d) than context 0 (%d)", who, i, g.cap, g0.cap);
+        if (g.spk_window != g0.spk_window || g.spk_range != g0.spk_range)
+            return fail(c0, "%s: context %d has another speckle window / range (%d, %d) than context 0 (%d, %d)", who, i, g.spk_window,
+                        g.spk_range, g0.spk_window, g0.spk_range);
+    }
+    int p1 = g0.p1, p2 = g0.p2;
+    if (check_params(c0, who, 3, g0.bs, &p1, &p2, g0.u)) return 1;      // (every context's: they are context 0's)
+    if (bind(c0)) return 1;
+    hipStream_t s = c0->stream;
+    const bool timed = c0->opt_profile != 0, spk = g0.spk_window > 0;
+
+    // ---- buffers, events and the table's memory: before any launch, and before any context forgets its previous result ----
+    for (int i = 0; i < n; ++i) {
+        psm_ctx *c = ctxs[i];
+        if (ensure_buffers(c) || (spk && ensure_speckle_planes(c))) return c == c0 ? 1 : fail(c0, "%s: context %d: %s", who, i, c->err.c_str());
+        if (c->stream != s && !c->ev_batch) PSM_HIP(c0, hipEventCreateWithFlags(&c->ev_batch, hipEventDisableTiming));
+    }
+    if (!c0->ev_batch) PSM_HIP(c0, hipEventCreateWithFlags(&c0->ev_batch, hipEventDisableTiming));
+    SgmState &t = c0->sgm;
+    std::vector<SgmPair> tab((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const psm_ctx *c = ctxs[i];
+        const SgmState &g = c->sgm;
+        tab[i] = SgmPair{{c->raw[0], c->raw[1]}, g.C, g.S, g.disp2, g.pre, g.out, {g.cap > 0 ? g.pf[0] : nullptr, g.cap > 0 ? g.pf[1] : nullptr},
+                         spk ? g.spk_label : nullptr, spk ? g.spk_size : nullptr};
+    }
+    const bool fresh = t.tab_host.size() != tab.size() || memcmp(t.tab_host.data(), tab.data(), tab.size() * sizeof(SgmPair)) != 0;
+    if (fresh && t.tab_cap < tab.size()) {
+        PSM_HIP(c0, hipStreamSynchronize(s));
+        (void)hipFree(t.tab);
+        if (t.tab_pin) (void)hipHostFree(t.tab_pin);
+        t.tab = nullptr;
+        t.tab_pin = nullptr;
+        t.tab_cap = 0;
+        t.tab_host.clear();                  // (should an allocation below fail, the next call must not take the old table for current)
+        PSM_HIP(c0, hipMalloc((void **)&t.tab, tab.size() * sizeof(SgmPair)));
+        PSM_HIP(c0, hipHostMalloc((void **)&t.tab_pin, 2 * tab.size() * sizeof(SgmPair), hipHostMallocDefault));
+        t.tab_cap = tab.size();
+    }
+    for (hipEvent_t &e : t.ev_tab)
+        if (!e) PSM_HIP(c0, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+
+    // ---- every context's earlier work (uploads, a single compute, downloads) is ordered before the shared launches ----
+    for (int i = 0; i < n; ++i) {
+        psm_ctx *c = ctxs[i];
+        if (c->stream == s) continue;
+        PSM_HIP(c0, hipEventRecord(c->ev_batch, c->stream));
+        PSM_HIP(c0, hipStreamWaitEvent(s, c->ev_batch, 0));
+    }
+    if (fresh) {
+        // (the table changes with every frame of a loop whose image slots alternate; the copy is stream-ordered behind the previous
+        // batch's kernels, which still read the old table, and reads one of two page-locked slots: a slot is rewritten only after
+        // the copy that read it has executed)
+        const int slot = t.tab_slot ^= 1;
+        PSM_HIP(c0, hipEventSynchronize(t.ev_tab[slot]));
+        SgmPair *pin = t.tab_pin + (size_t)slot * t.tab_cap;
+        memcpy(pin, tab.data(), tab.size() * sizeof(SgmPair));
+        t.tab_host = tab;
+        PSM_HIP(c0, hipMemcpyAsync(t.tab, pin, tab.size() * sizeof(SgmPair), hipMemcpyHostToDevice, s));
+        PSM_HIP(c0, hipEventRecord(t.ev_tab[slot], s));
+    }
+
+    for (int i = 0; i < n; ++i) {
+        SgmState &g = ctxs[i]->sgm;
+        g.have = g.timed = false;
+        g.spk_t0 = -1;
+        g.pf_ch = 0;
+        if (spk) g.spk_have = false;
+    }
+    const SgmArgs a = sgm_args(c0, nullptr, nullptr, c0->raw_depth, 3, p1, p2);      // (the scalars; the pointers are the table's)
+    launch_sgm_fill_batch(s, a, t.tab, n);
+    if (timed) PSM_HIP(c0, hipEventRecord(t.ev[0], s));
+    if (g0.cap > 0) launch_sgm_cost_bt(s, a, t.tab, n);
+    else launch_sgm_cost(s, a, t.tab, n);
+    if (check_launch(c0, g0.cap > 0 ? "k_sgm_fill_b, k_sgm_prefilter_b, k_sgm_bt_*_b" : "k_sgm_fill_b, k_sgm_cost_b")) return 1;
+    if (timed) PSM_HIP(c0, hipEventRecord(t.ev[1], s));
+    for (int i = 0; i < 8; ++i) launch_sgm_path(s, a, SGM_DIRS[i][0], SGM_DIRS[i][1], i == 0, t.tab, n);
+    if (check_launch(c0, "k_sgm_path_b")) return 1;
+    if (timed) PSM_HIP(c0, hipEventRecord(t.ev[2], s));
+    launch_sgm_select(s, a, t.tab, n);
+    if (check_launch(c0, "k_sgm_select_b")) return 1;
+    if (timed) PSM_HIP(c0, hipEventRecord(t.ev[3], s));
+    if (spk) {
+        launch_speckle(s, speckle_args(c0, -16, g0.spk_window, 16ll * g0.spk_range), t.tab, n);
+        if (check_launch(c0, "k_spk_*_b")) return 1;
+        if (timed) PSM_HIP(c0, hipEventRecord(t.ev[4], s));
+    }
+
+    // ---- every context is now where its own psm_sgm_compute would have left it; only context 0 counts as timed ----
+    PSM_HIP(c0, hipEventRecord(c0->ev_batch, s));
+    for (int i = 0; i < n; ++i) {
+        psm_ctx *c = ctxs[i];
+        SgmState &g = c->sgm;
+        g.have = true;
+        g.timed = timed && i == 0;
+        g.pf_ch = g0.cap > 0 ? 3 : 0;
+        if (spk) {
+            g.spk_have = true;
+            g.spk_t0 = timed && i == 0 ? 3 : -1;
+        }
+        if (c->stream != s) PSM_HIP(c0, hipStreamWaitEvent(c->stream, c0->ev_batch, 0));
+    }
+    if (!c0->opt_async) PSM_HIP(c0, hipStreamSynchronize(s));
+    return 0;
 }
 
 int psm_sgm_download_disparity(psm_ctx *c, int16_t *disp, size_t stride_bytes)

@@ -8,7 +8,8 @@
 //   psm_api_batch.cpp   several Middlebury-size pairs per launch (psm_compute_batch)
 //   psm_api_jwmf.cpp    JointWMF: the joint weighted median of the reference's live post-filter (psm_joint_wmf)
 //   psm_api_rectify.cpp video mode: remap + crop of the camera frame into the staged image slot (psm_upload_pair_rectified)
-//   psm_api_sgm.cpp     semi-global matching over the staged pair, the reference's STEREO_SGBM branch (psm_sgm_compute)
+//   psm_api_sgm.cpp     semi-global matching over the staged pair, the reference's STEREO_SGBM branch (psm_sgm_compute), and
+//                       over the pairs of several contexts in shared launches (psm_sgm_compute_batch)
 // Takes the place of the reference's oclUtil + CVC_cl / CVF_cl / DispSel_cl host wrappers
 // (src/oclUtil.cpp, src/CVC_cl.cpp, src/CVF_cl.cpp, src/DispSel_cl.cpp).
 // What a context knows about its volumes and results between calls - psm::VolSide per side, psm::Results - lives in psm_state.h
@@ -59,6 +60,14 @@ struct SgmState {
     int cap = 0;                                   // pre_filter_cap; 0: the SAD cost
     uint8_t *pf[2] = {nullptr, nullptr};           // the planes of both images, [H][W][2 ch] bytes (room for ch 3)
     int pf_ch = 0;                                 // the channels of the planes the last compute wrote; 0: it wrote none
+    // psm_sgm_compute_batch (this context as the first of a batch): the device table of the pairs' buffers, its host copy (the
+    // table is uploaded again only when an entry changed) and its page-locked staging, two slots used alternately as
+    // psm_compute_batch's (psm_ctx::batch_pin); ev_tab: the copy out of a slot has executed
+    SgmPair *tab = nullptr, *tab_pin = nullptr;
+    std::vector<SgmPair> tab_host;
+    size_t tab_cap = 0;
+    int tab_slot = 0;
+    hipEvent_t ev_tab[2] = {nullptr, nullptr};
 };
 }  // namespace psm
 

@@ -232,13 +232,33 @@ struct SgmArgs {
     uint16_t *Hs;                      // horizontal block sums [H][W][Dp], in the memory of S (free until the first direction stores it)
     int ft;                            // max(pre_filter_cap, 15) | 1
 };
+// Several pairs of one geometry per launch (psm_sgm_compute_batch): one pair's buffers, an entry of the device table the batched
+// entries index with the pair number (blockIdx.z).  The scalars of SgmArgs / SpkArgs are the batch's; the pointers come from here.
+struct SgmPair {
+    const void *img[2];
+    uint16_t *C;
+    uint32_t *S;
+    uint32_t *disp2;
+    int16_t *pre, *out;
+    uint8_t *pf[2];                    // null with the SAD cost
+    unsigned *spk_label, *spk_size;    // null with the speckle filter off
+};
+// A pointer a kernel reads from the table is a flat pointer to the compiler (one that arrives as a kernel argument is known to be
+// global): every access through it would become a flat_* instruction, which counts on vmcnt and lgkmcnt at once and makes the
+// body wait for everything in flight (k_sgm_path_b with flat accesses: 0.44 ms for a batch of one Cones pair against 0.38 ms).
+// Reading the table's slot as one that holds a global pointer gives the batched entries the global_* instructions of the
+// single-pair ones (a cast of the loaded value to global and back is folded away before it can tell anyone).
+template <typename T>
+__device__ __forceinline__ T *sgm_global(T *const &slot) { return (T *)*(__attribute__((address_space(1))) T *const *)(const void *)&slot; }
 constexpr int SGM_DIRS[8][2] = {{0, 1}, {0, -1}, {1, 0}, {-1, 0}, {1, 1}, {1, -1}, {-1, 1}, {-1, -1}};   // (dy, dx)
 constexpr int SGM_BT_TX = 128;         // k_sgm_bt_rows: output pixels of a row per workgroup
 constexpr int SGM_BT_YS = 32;          // k_sgm_bt_cols: output rows per thread
-void launch_sgm_cost(hipStream_t s, const SgmArgs &a);
-void launch_sgm_cost_bt(hipStream_t s, const SgmArgs &a);                              // k_sgm_prefilter, k_sgm_bt_rows, k_sgm_bt_cols: the same C
-void launch_sgm_path(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first);     // S = L_r (first) or S += L_r
-void launch_sgm_select(hipStream_t s, const SgmArgs &a);                               // k_sgm_select + k_sgm_check (disp2 all ones before)
+// tab == nullptr: the pair whose pointers `a` holds; else the n pairs of the device table (the pointers of `a` unused, grid z = pair)
+void launch_sgm_cost(hipStream_t s, const SgmArgs &a, const SgmPair *tab = nullptr, int n = 1);
+void launch_sgm_cost_bt(hipStream_t s, const SgmArgs &a, const SgmPair *tab = nullptr, int n = 1);   // k_sgm_prefilter, k_sgm_bt_rows, k_sgm_bt_cols: the same C
+void launch_sgm_path(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first, const SgmPair *tab = nullptr, int n = 1);   // S = L_r (first) or S += L_r
+void launch_sgm_select(hipStream_t s, const SgmArgs &a, const SgmPair *tab = nullptr, int n = 1);   // k_sgm_select + k_sgm_check (disp2 all ones before)
+void launch_sgm_fill_batch(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n);   // disp2 of every pair all ones
 
 // psm_speckle.hip: cv::filterSpeckles on an int16 map, in place (psm_sgm_set_speckle, psm_sgm_filter_speckles)
 struct SpkArgs {
@@ -248,6 +268,7 @@ struct SpkArgs {
     int W, H;
     int new_val, max_size, max_diff;   // max_diff <= 65535
 };
-void launch_speckle(hipStream_t s, const SpkArgs &a);                                  // k_spk_runs, k_spk_merge, k_spk_count, k_spk_apply
+// k_spk_runs, k_spk_merge, k_spk_count, k_spk_apply; tab: as above - the maps are the pairs' `out`
+void launch_speckle(hipStream_t s, const SpkArgs &a, const SgmPair *tab = nullptr, int n = 1);
 
 }  // namespace psm

@@ -52,12 +52,26 @@ __device__ __forceinline__ unsigned sgm_px(const void *img, int depth, int ch, s
 
 __device__ __forceinline__ int sgm_clamp(int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); }
 
+// Several pairs per launch (psm_sgm_compute_batch): every kernel below is one body (sgm_*) behind two entries.  k_sgm_* takes its
+// pair's pointers in SgmArgs, as ever; k_sgm_*_b has the pair on grid axis z and reads its pointers from the device table into
+// the same SgmArgs - the pair number is uniform per workgroup, so these are scalar loads ahead of an unchanged body.  All index
+// arithmetic stays inside a pair.
+__device__ __forceinline__ SgmArgs sgm_pair_args(SgmArgs a, const SgmPair *tab, unsigned pair)
+{
+    const SgmPair &p = tab[pair];
+    a.img[0] = sgm_global(p.img[0]); a.img[1] = sgm_global(p.img[1]);
+    a.C = sgm_global(p.C); a.S = sgm_global(p.S); a.disp2 = sgm_global(p.disp2); a.pre = sgm_global(p.pre); a.out = sgm_global(p.out);
+    a.pf[0] = sgm_global(p.pf[0]); a.pf[1] = sgm_global(p.pf[1]);
+    a.Hs = (uint16_t *)a.S;
+    return a;
+}
+
 // One workgroup per SGM_TX pixels of one row, one thread per disparity.  The BS rows of both images the block needs go to LDS as
 // one dword per pixel (v_sad_u8 then takes the 1 or 3 channels of a tap in one instruction); a thread walks x with its d fixed:
 // the left tap is a broadcast, the right taps of neighbouring lanes are neighbouring dwords, the stores of a wave are 128
 // contiguous bytes.  Column sums of the last BS columns stay in registers.
 template <int BS>
-__global__ __launch_bounds__(256) void k_sgm_cost(SgmArgs a)
+__device__ __forceinline__ void sgm_cost(const SgmArgs &a)
 {
     constexpr int HALF = BS / 2, NL = SGM_TX + BS - 1, NR = NL + 255;
     __shared__ unsigned sl[BS][NL], sr[BS][NR];
@@ -98,6 +112,9 @@ __global__ __launch_bounds__(256) void k_sgm_cost(SgmArgs a)
     }
 }
 
+template <int BS> __global__ __launch_bounds__(256) void k_sgm_cost(SgmArgs a) { sgm_cost<BS>(a); }
+template <int BS> __global__ __launch_bounds__(256) void k_sgm_cost_b(SgmArgs a, const SgmPair *tab) { sgm_cost<BS>(sgm_pair_args(a, tab, blockIdx.z)); }
+
 // ---- the prefiltered Birchfield-Tomasi cost (psm_sgm_set_prefilter, tests/sgm_bt_model.py): the same C by three kernels -------
 //   k_sgm_prefilter  both images -> their 2 ch planes per pixel (x-Sobel clipped to [0, 2 ft], the intensity; ft in the border columns)
 //   k_sgm_bt_rows    c(x,y,d) and its horizontal sum over the block's columns (replicated edge) -> Hs u16 [y][x][d], in S's memory
@@ -105,10 +122,10 @@ __global__ __launch_bounds__(256) void k_sgm_cost(SgmArgs a)
 // Every c is evaluated once (the bs - 1 columns two neighbouring tiles of SGM_BT_TX columns share: twice): a Birchfield-Tomasi
 // tap is ~13 packed operations per pair of planes, not the one v_sad_u8 k_sgm_cost repeats per block row.
 
-// k_sgm_prefilter: one thread per pixel of one image (blockIdx.z); a float image is quantised here, once
-__global__ __launch_bounds__(256) void k_sgm_prefilter(SgmArgs a)
+// k_sgm_prefilter: one thread per pixel of one image (blockIdx.z; batched: z = 2 pair + side); a float image is quantised here, once
+__device__ __forceinline__ void sgm_prefilter(const SgmArgs &a, int side)
 {
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, side = blockIdx.z;
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= a.W) return;
     const void *img = a.img[side];
     const int ch = a.ch, ft = a.ft;
@@ -133,6 +150,9 @@ __global__ __launch_bounds__(256) void k_sgm_prefilter(SgmArgs a)
         out[ch + k] = (uint8_t)((centre >> (8 * k)) & 255u);
     }
 }
+
+__global__ __launch_bounds__(256) void k_sgm_prefilter(SgmArgs a) { sgm_prefilter(a, blockIdx.z); }
+__global__ __launch_bounds__(256) void k_sgm_prefilter_b(SgmArgs a, const SgmPair *tab) { sgm_prefilter(sgm_pair_args(a, tab, blockIdx.z >> 1), blockIdx.z & 1); }
 
 // Two adjacent planes of a pixel travel as the two 16-bit lanes of a dword (planes 2p, 2p + 1: pair p), so that one packed
 // instruction (v_pk_sub_i16, v_pk_max_i16, v_pk_min_i16) serves both; every value is in [-255, 255].
@@ -164,7 +184,7 @@ __device__ __forceinline__ void sgm_bt_stage(const uint8_t *row, int W, int cx, 
 // operands are broadcasts, the right ones of neighbouring lanes neighbouring dwords.  NP pairs of planes: ch = NP (1 or 3); plane
 // i has shift 0 below ch (P), 2 from ch on (Q).  out: Hs, or C itself when BS is 1.
 template <int BS, int NP>
-__global__ __launch_bounds__(256) void k_sgm_bt_rows(SgmArgs a, uint16_t *out)
+__device__ __forceinline__ void sgm_bt_rows(const SgmArgs &a, uint16_t *out)
 {
     constexpr int HALF = BS / 2, NL = SGM_BT_TX + BS - 1, NR = NL + 255, NQ = 3 * NP;
     __shared__ unsigned sl[NQ][NL], sr[NQ][NR];
@@ -210,12 +230,20 @@ __global__ __launch_bounds__(256) void k_sgm_bt_rows(SgmArgs a, uint16_t *out)
     }
 }
 
+template <int BS, int NP> __global__ __launch_bounds__(256) void k_sgm_bt_rows(SgmArgs a, uint16_t *out) { sgm_bt_rows<BS, NP>(a, out); }
+template <int BS, int NP>
+__global__ __launch_bounds__(256) void k_sgm_bt_rows_b(SgmArgs a, const SgmPair *tab)
+{
+    a = sgm_pair_args(a, tab, blockIdx.z);
+    sgm_bt_rows<BS, NP>(a, BS == 1 ? a.C : a.Hs);
+}
+
 // The vertical sum: a thread holds four adjacent disparities of one pixel column (8 bytes: Dp is a multiple of 4) and marches
 // down SGM_BT_YS rows; the last BS rows of Hs stay in registers, a step is one load, one add, one subtract and one store.  Two
 // 16-bit sums share a dword: every result is at most 65535 (psm_sgm_set_params), and the 32-bit arithmetic is exact modulo 2^32,
 // so no carry survives between the halves.  Only the BS - 1 rows two segments share are loaded twice.
 template <int BS>
-__global__ __launch_bounds__(256) void k_sgm_bt_cols(SgmArgs a)
+__device__ __forceinline__ void sgm_bt_cols(const SgmArgs &a)
 {
     constexpr int HALF = BS / 2;
     const size_t rowq = (size_t)a.W * a.Dp / 4;           // uint2 per row
@@ -243,6 +271,9 @@ __global__ __launch_bounds__(256) void k_sgm_bt_cols(SgmArgs a)
         }
     }
 }
+
+template <int BS> __global__ __launch_bounds__(256) void k_sgm_bt_cols(SgmArgs a) { sgm_bt_cols<BS>(a); }
+template <int BS> __global__ __launch_bounds__(256) void k_sgm_bt_cols_b(SgmArgs a, const SgmPair *tab) { sgm_bt_cols<BS>(sgm_pair_args(a, tab, blockIdx.z)); }
 
 // NV adjacent disparities per lane: what a lane moves per pixel
 template <int NV> struct SgmVec;
@@ -273,7 +304,7 @@ __host__ __device__ inline int sgm_npaths(int W, int H, int dy, int dx) { return
 // Within a direction every voxel lies on exactly one path and the launches of a frame follow each other on one stream: S is
 // updated with plain loads and stores, no atomics.
 template <int NV, bool FIRST, bool ALL>
-__global__ __launch_bounds__(256) void k_sgm_path(SgmArgs a, int dy, int dx)
+__device__ __forceinline__ void sgm_path(const SgmArgs &a, int dy, int dx)
 {
     using CV = typename SgmVec<NV>::C;
     using SV = typename SgmVec<NV>::S;
@@ -350,9 +381,15 @@ __global__ __launch_bounds__(256) void k_sgm_path(SgmArgs a, int dy, int dx)
     run(cv[1], sv[1], i + SGM_U, std::false_type{});
 }
 
+template <int NV, bool FIRST, bool ALL>
+__global__ __launch_bounds__(256) void k_sgm_path(SgmArgs a, int dy, int dx) { sgm_path<NV, FIRST, ALL>(a, dy, dx); }
+// n x (H, W or W + H - 1) one-wave paths per launch: what hides a path's dependent chain is other pairs' waves on the same SIMD
+template <int NV, bool FIRST, bool ALL>
+__global__ __launch_bounds__(256) void k_sgm_path_b(SgmArgs a, const SgmPair *tab, int dy, int dx) { sgm_path<NV, FIRST, ALL>(sgm_pair_args(a, tab, blockIdx.z), dy, dx); }
+
 // One wave per pixel: the packed (S << 8 | d) minimum over the wave is argmin with the lowest d on ties (S < 2^19).
 template <int NV>
-__global__ __launch_bounds__(256) void k_sgm_select(SgmArgs a)
+__device__ __forceinline__ void sgm_select(const SgmArgs &a)
 {
     using SV = typename SgmVec<NV>::S;
     const int lane = threadIdx.x & 63;
@@ -390,6 +427,9 @@ __global__ __launch_bounds__(256) void k_sgm_select(SgmArgs a)
     if (unique && x - best >= 0) atomicMin(a.disp2 + (size_t)y * a.W + (x - best), (unsigned)kmin);
 }
 
+template <int NV> __global__ __launch_bounds__(256) void k_sgm_select(SgmArgs a) { sgm_select<NV>(a); }
+template <int NV> __global__ __launch_bounds__(256) void k_sgm_select_b(SgmArgs a, const SgmPair *tab) { sgm_select<NV>(sgm_pair_args(a, tab, blockIdx.z)); }
+
 __device__ __forceinline__ bool sgm_bad_probe(const unsigned *row, int W, int xq, int dq, int m)
 {
     if (xq < 0 || xq >= W) return false;
@@ -399,7 +439,7 @@ __device__ __forceinline__ bool sgm_bad_probe(const unsigned *row, int W, int xq
     return (t < 0 ? -t : t) > m;
 }
 
-__global__ __launch_bounds__(256) void k_sgm_check(SgmArgs a)
+__device__ __forceinline__ void sgm_check(const SgmArgs &a)
 {
     const int pix = blockIdx.x * 256 + threadIdx.x;
     if (pix >= a.W * a.H) return;
@@ -413,38 +453,65 @@ __global__ __launch_bounds__(256) void k_sgm_check(SgmArgs a)
     a.out[pix] = (int16_t)v;
 }
 
-void launch_sgm_cost(hipStream_t s, const SgmArgs &a)
+__global__ __launch_bounds__(256) void k_sgm_check(SgmArgs a) { sgm_check(a); }
+__global__ __launch_bounds__(256) void k_sgm_check_b(SgmArgs a, const SgmPair *tab) { sgm_check(sgm_pair_args(a, tab, blockIdx.z)); }
+
+// disp2 of every pair of a batch: "nothing lands here" (the single pair's is a hipMemsetAsync)
+__global__ __launch_bounds__(256) void k_sgm_fill_b(SgmArgs a, const SgmPair *tab)
+{
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix < a.W * a.H) sgm_global(tab[blockIdx.z].disp2)[pix] = 0xffffffffu;
+}
+
+// One launch: the single-pair entry k with the pair in `a`, or the batched entry kb over the table with gz as the grid's z extent
+template <typename... A>
+static void sgm_launch(hipStream_t s, void (*k)(SgmArgs, A...), void (*kb)(SgmArgs, const SgmPair *, A...), dim3 grid, dim3 block,
+                       const SgmArgs &a, const SgmPair *tab, int gz, A... rest)
+{
+    if (tab) hipLaunchKernelGGL(kb, dim3(grid.x, grid.y, (unsigned)gz), block, 0, s, a, tab, rest...);
+    else hipLaunchKernelGGL(k, grid, block, 0, s, a, rest...);
+}
+
+void launch_sgm_fill_batch(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
+{
+    hipLaunchKernelGGL(k_sgm_fill_b, dim3((a.W * a.H + 255) / 256, 1, n), dim3(256), 0, s, a, tab);
+}
+
+void launch_sgm_cost(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
 {
     const dim3 grid((a.W + SGM_TX - 1) / SGM_TX, a.H), block((a.D + 63) / 64 * 64);
     switch (a.bs) {
-    case 1: hipLaunchKernelGGL(k_sgm_cost<1>, grid, block, 0, s, a); break;
-    case 3: hipLaunchKernelGGL(k_sgm_cost<3>, grid, block, 0, s, a); break;
-    case 5: hipLaunchKernelGGL(k_sgm_cost<5>, grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL(k_sgm_cost<7>, grid, block, 0, s, a); break;
+    case 1: sgm_launch(s, k_sgm_cost<1>, k_sgm_cost_b<1>, grid, block, a, tab, n); break;
+    case 3: sgm_launch(s, k_sgm_cost<3>, k_sgm_cost_b<3>, grid, block, a, tab, n); break;
+    case 5: sgm_launch(s, k_sgm_cost<5>, k_sgm_cost_b<5>, grid, block, a, tab, n); break;
+    default: sgm_launch(s, k_sgm_cost<7>, k_sgm_cost_b<7>, grid, block, a, tab, n); break;
     }
 }
 
 template <int BS>
-static void launch_bt_bs(hipStream_t s, const SgmArgs &a)
+static void launch_bt_bs(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
 {
-    const dim3 grid((a.W + SGM_BT_TX - 1) / SGM_BT_TX, a.H), block((a.D + 63) / 64 * 64);
+    const dim3 grid((a.W + SGM_BT_TX - 1) / SGM_BT_TX, a.H, tab ? n : 1), block((a.D + 63) / 64 * 64);
     uint16_t *out = BS == 1 ? a.C : a.Hs;                 // (a 1 x 1 block has no vertical sum)
-    if (a.ch == 1) hipLaunchKernelGGL((k_sgm_bt_rows<BS, 1>), grid, block, 0, s, a, out);
+    if (tab) {
+        if (a.ch == 1) hipLaunchKernelGGL((k_sgm_bt_rows_b<BS, 1>), grid, block, 0, s, a, tab);
+        else hipLaunchKernelGGL((k_sgm_bt_rows_b<BS, 3>), grid, block, 0, s, a, tab);
+    } else if (a.ch == 1) hipLaunchKernelGGL((k_sgm_bt_rows<BS, 1>), grid, block, 0, s, a, out);
     else hipLaunchKernelGGL((k_sgm_bt_rows<BS, 3>), grid, block, 0, s, a, out);
     if constexpr (BS > 1) {
         const size_t rowq = (size_t)a.W * a.Dp / 4;
-        hipLaunchKernelGGL(k_sgm_bt_cols<BS>, dim3((unsigned)((rowq + 255) / 256), (a.H + SGM_BT_YS - 1) / SGM_BT_YS), dim3(256), 0, s, a);
+        sgm_launch(s, k_sgm_bt_cols<BS>, k_sgm_bt_cols_b<BS>, dim3((unsigned)((rowq + 255) / 256), (a.H + SGM_BT_YS - 1) / SGM_BT_YS), dim3(256), a, tab, n);
     }
 }
 
-void launch_sgm_cost_bt(hipStream_t s, const SgmArgs &a)
+void launch_sgm_cost_bt(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
 {
-    hipLaunchKernelGGL(k_sgm_prefilter, dim3((a.W + 255) / 256, a.H, 2), dim3(256), 0, s, a);
+    sgm_launch(s, k_sgm_prefilter, k_sgm_prefilter_b, dim3((a.W + 255) / 256, a.H, 2), dim3(256), a, tab, 2 * n);
     switch (a.bs) {
-    case 1: launch_bt_bs<1>(s, a); break;
-    case 3: launch_bt_bs<3>(s, a); break;
-    case 5: launch_bt_bs<5>(s, a); break;
-    default: launch_bt_bs<7>(s, a); break;
+    case 1: launch_bt_bs<1>(s, a, tab, n); break;
+    case 3: launch_bt_bs<3>(s, a, tab, n); break;
+    case 5: launch_bt_bs<5>(s, a, tab, n); break;
+    default: launch_bt_bs<7>(s, a, tab, n); break;
     }
 }
 
@@ -452,35 +519,35 @@ void launch_sgm_cost_bt(hipStream_t s, const SgmArgs &a)
 static int sgm_nv(int Dp) { return Dp <= 64 ? 1 : (Dp <= 128 ? 2 : 4); }
 
 template <int NV>
-static void launch_path_nv(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first)
+static void launch_path_nv(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first, const SgmPair *tab, int n)
 {
     const dim3 grid((sgm_npaths(a.W, a.H, dy, dx) + 3) / 4), block(256);
     const bool all = a.Dp == 64 * NV;
-    if (first && all) hipLaunchKernelGGL((k_sgm_path<NV, true, true>), grid, block, 0, s, a, dy, dx);
-    else if (first) hipLaunchKernelGGL((k_sgm_path<NV, true, false>), grid, block, 0, s, a, dy, dx);
-    else if (all) hipLaunchKernelGGL((k_sgm_path<NV, false, true>), grid, block, 0, s, a, dy, dx);
-    else hipLaunchKernelGGL((k_sgm_path<NV, false, false>), grid, block, 0, s, a, dy, dx);
+    if (first && all) sgm_launch(s, k_sgm_path<NV, true, true>, k_sgm_path_b<NV, true, true>, grid, block, a, tab, n, dy, dx);
+    else if (first) sgm_launch(s, k_sgm_path<NV, true, false>, k_sgm_path_b<NV, true, false>, grid, block, a, tab, n, dy, dx);
+    else if (all) sgm_launch(s, k_sgm_path<NV, false, true>, k_sgm_path_b<NV, false, true>, grid, block, a, tab, n, dy, dx);
+    else sgm_launch(s, k_sgm_path<NV, false, false>, k_sgm_path_b<NV, false, false>, grid, block, a, tab, n, dy, dx);
 }
 
-void launch_sgm_path(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first)
+void launch_sgm_path(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first, const SgmPair *tab, int n)
 {
     switch (sgm_nv(a.Dp)) {
-    case 1: launch_path_nv<1>(s, a, dy, dx, first); break;
-    case 2: launch_path_nv<2>(s, a, dy, dx, first); break;
-    default: launch_path_nv<4>(s, a, dy, dx, first); break;
+    case 1: launch_path_nv<1>(s, a, dy, dx, first, tab, n); break;
+    case 2: launch_path_nv<2>(s, a, dy, dx, first, tab, n); break;
+    default: launch_path_nv<4>(s, a, dy, dx, first, tab, n); break;
     }
 }
 
-void launch_sgm_select(hipStream_t s, const SgmArgs &a)
+void launch_sgm_select(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
 {
     const int HW = a.W * a.H;
     const dim3 grid((HW + 3) / 4), block(256);
     switch (sgm_nv(a.Dp)) {
-    case 1: hipLaunchKernelGGL(k_sgm_select<1>, grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL(k_sgm_select<2>, grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL(k_sgm_select<4>, grid, block, 0, s, a); break;
+    case 1: sgm_launch(s, k_sgm_select<1>, k_sgm_select_b<1>, grid, block, a, tab, n); break;
+    case 2: sgm_launch(s, k_sgm_select<2>, k_sgm_select_b<2>, grid, block, a, tab, n); break;
+    default: sgm_launch(s, k_sgm_select<4>, k_sgm_select_b<4>, grid, block, a, tab, n); break;
     }
-    hipLaunchKernelGGL(k_sgm_check, dim3((HW + 255) / 256), dim3(256), 0, s, a);
+    sgm_launch(s, k_sgm_check, k_sgm_check_b, dim3((HW + 255) / 256), dim3(256), a, tab, n);
 }
 
 }  // namespace psm

@@ -56,7 +56,7 @@ __device__ __forceinline__ void spk_union(unsigned *label, unsigned a, unsigned 
 // ballot of the starts and a bit scan give every lane its run's first pixel, a run that began in an earlier piece is carried in
 // `carry`.  The last pixel of a run writes the run's length to size[head].  All horizontal structure is flat before the first
 // atomic is issued.
-__global__ __launch_bounds__(256) void k_spk_runs(SpkArgs a)
+__device__ __forceinline__ void spk_runs(const SpkArgs &a)
 {
     const int lane = threadIdx.x & 63;
     const int y = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void k_spk_runs(SpkArgs a)
 
 // One thread per pixel below the first row: its edge to the pixel above.  Skipped when the left neighbour is in the same run, has
 // an edge of its own to the pixel above it and that pixel is in the same run as ours above: the edge would join the same two runs.
-__global__ __launch_bounds__(256) void k_spk_merge(SpkArgs a)
+__device__ __forceinline__ void spk_merge(const SpkArgs &a)
 {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y + 1;
     if (x >= a.W) return;
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void k_spk_merge(SpkArgs a)
 // One thread per pixel, run heads act.  After k_spk_merge the labels are final (a launch of its own on the same stream), so find
 // gives the true root; writing it back only shortens chains other threads walk (either value leads to the same root).  Only roots
 // receive adds and only heads that are no roots read their own size: a size is an exact integer sum, whatever the arrival order.
-__global__ __launch_bounds__(256) void k_spk_count(SpkArgs a)
+__device__ __forceinline__ void spk_count(const SpkArgs &a)
 {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= a.W) return;
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void k_spk_count(SpkArgs a)
 
 // One thread per pixel.  size[p] is rewritten in place with the size of p's component: the only entries other threads read here
 // are those of roots, and a root writes the value it already holds.
-__global__ __launch_bounds__(256) void k_spk_apply(SpkArgs a)
+__device__ __forceinline__ void spk_apply(const SpkArgs &a)
 {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= a.W) return;
@@ -134,9 +134,34 @@ __global__ __launch_bounds__(256) void k_spk_apply(SpkArgs a)
     a.size[p] = s;
 }
 
-void launch_speckle(hipStream_t s, const SpkArgs &a)
+// Every kernel is its body behind two entries: the map of `a`, or - several maps of one size per launch (psm_sgm_compute_batch) -
+// the planes of pair blockIdx.z of the device table, read into the same SpkArgs (uniform per workgroup).  Labels and sizes are
+// pixel indices within a pair's own planes.
+__device__ __forceinline__ SpkArgs spk_pair_args(SpkArgs a, const SgmPair *tab, unsigned pair)
+{
+    const SgmPair &p = tab[pair];
+    a.map = sgm_global(p.out); a.label = sgm_global(p.spk_label); a.size = sgm_global(p.spk_size);
+    return a;
+}
+__global__ __launch_bounds__(256) void k_spk_runs(SpkArgs a) { spk_runs(a); }
+__global__ __launch_bounds__(256) void k_spk_merge(SpkArgs a) { spk_merge(a); }
+__global__ __launch_bounds__(256) void k_spk_count(SpkArgs a) { spk_count(a); }
+__global__ __launch_bounds__(256) void k_spk_apply(SpkArgs a) { spk_apply(a); }
+__global__ __launch_bounds__(256) void k_spk_runs_b(SpkArgs a, const SgmPair *tab) { spk_runs(spk_pair_args(a, tab, blockIdx.z)); }
+__global__ __launch_bounds__(256) void k_spk_merge_b(SpkArgs a, const SgmPair *tab) { spk_merge(spk_pair_args(a, tab, blockIdx.z)); }
+__global__ __launch_bounds__(256) void k_spk_count_b(SpkArgs a, const SgmPair *tab) { spk_count(spk_pair_args(a, tab, blockIdx.z)); }
+__global__ __launch_bounds__(256) void k_spk_apply_b(SpkArgs a, const SgmPair *tab) { spk_apply(spk_pair_args(a, tab, blockIdx.z)); }
+
+void launch_speckle(hipStream_t s, const SpkArgs &a, const SgmPair *tab, int n)
 {
     const dim3 block(256), rows((a.W + 255) / 256, a.H);
+    if (tab) {
+        hipLaunchKernelGGL(k_spk_runs_b, dim3((a.H + 3) / 4, 1, n), block, 0, s, a, tab);
+        if (a.H > 1) hipLaunchKernelGGL(k_spk_merge_b, dim3(rows.x, a.H - 1, n), block, 0, s, a, tab);
+        hipLaunchKernelGGL(k_spk_count_b, dim3(rows.x, rows.y, n), block, 0, s, a, tab);
+        hipLaunchKernelGGL(k_spk_apply_b, dim3(rows.x, rows.y, n), block, 0, s, a, tab);
+        return;
+    }
     hipLaunchKernelGGL(k_spk_runs, dim3((a.H + 3) / 4), block, 0, s, a);
     if (a.H > 1) hipLaunchKernelGGL(k_spk_merge, dim3(rows.x, a.H - 1), block, 0, s, a);
     hipLaunchKernelGGL(k_spk_count, rows, block, 0, s, a);

@@ -506,6 +506,32 @@ def compute_batch(des):
     capi.check(des[0]._lib.psm_compute_batch(arr, len(des)), des[0]._h, "compute_batch")
 
 
+def sgbm_batch(des, block_size: int = 0, P1: int = 0, P2: int = 0, uniqueness_ratio: int = 10, disp12_max_diff: int = 1,
+               speckle_window_size: int = 0, speckle_range: int = 0, pre_filter_cap: int = 0):
+    """SGBM_GPU of several DispEst objects of one geometry in shared launches (psm_sgm_compute_batch): the parameters (SGBM_GPU's,
+    without gray=) are set on every object, each object's own staged pair goes through the stage, -> the list of H x W int16 maps.
+    Every object afterwards behaves as after its own SGBM_GPU (sgm_costs(), sgm_prefiltered(), sgm_speckle_sizes(), ...); the
+    times of the batch are des[0]'s (sgm_times(), sgm_speckle_time() under PSM_OPT_PROFILE)."""
+    des = list(des)
+    if not des:
+        return []
+    for d in des:
+        d._ck(d._lib.psm_sgm_set_prefilter(d._h, int(pre_filter_cap)), "sgbm_batch")
+        d._ck(d._lib.psm_sgm_set_speckle(d._h, int(speckle_window_size), int(speckle_range)), "sgbm_batch")
+        d._ck(d._lib.psm_sgm_set_params(d._h, int(block_size), int(P1), int(P2), int(uniqueness_ratio), int(disp12_max_diff)),
+              "sgbm_batch")
+        d._sgm_ch = 3
+    sgm_compute_batch(des)
+    return [d.sgm_disparity() for d in des]
+
+
+def sgm_compute_batch(des):
+    """psm_sgm_compute_batch with the objects' parameters as they are (sgbm_batch sets them first)."""
+    des = list(des)
+    arr = (C.c_void_p * len(des))(*[d._h for d in des])
+    capi.check(des[0]._lib.psm_sgm_compute_batch(arr, len(des)), des[0]._h, "sgm_compute_batch")
+
+
 def share_streams(des):
     """The DispEst objects of a batch run on one compute stream and one copy stream each way (psm_share_streams) - call once
     before a frame loop over batches."""

@@ -7,7 +7,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import capi
-from .dispest import DispEst
+from .dispest import DispEst, sgbm_batch
 
 MASK_NONE, MASK_NONOCC, MASK_DISC = 0, 1, 2   # include/StereoMatch.h
 
@@ -85,6 +85,37 @@ def compute_sgbm(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, er
         out["cost_ms"], out["paths_ms"], out["select_ms"] = SMDE.sgm_times()
         if params.get("speckle_window_size", 0) > 0:
             out["speckle_ms"] = SMDE.sgm_speckle_time()
+    return _finish_sgbm(out, maxDis, gt, mask, scale_factor, error_threshold, verbose)
+
+
+def compute_sgbm_batch(pairs, maxDis=64, gts=None, masks=None, scale_factor=4, error_threshold=4, verbose=False, **params):
+    """compute_sgbm for a list of (l_bgr, r_bgr) pairs of one size and depth in shared launches (dispest.sgbm_batch): the
+    reference's loop over pairs and datasets (src/main.cpp:64-73, src/StereoMatch.cpp:528-609).  gts / masks: one per pair (or
+    None).  -> a list of compute_sgbm's records; the times are the batch's divided by the number of pairs."""
+    pairs = [(np.ascontiguousarray(l), np.ascontiguousarray(r)) for l, r in pairs]
+    if not pairs:
+        return []
+    des = [DispEst(l, r, maxDis, 8, True) for l, r in pairs]
+    try:
+        des[0].set_option(capi.PSM_OPT_PROFILE, 1)
+        maps = sgbm_batch(des, **params)
+        times = [t / len(des) for t in des[0].sgm_times()]
+        spk = des[0].sgm_speckle_time() / len(des) if params.get("speckle_window_size", 0) > 0 else None
+    finally:
+        for d in des:
+            d.close()
+    outs = []
+    for i, d16 in enumerate(maps):
+        out = {"disp16": d16, "cost_ms": times[0], "paths_ms": times[1], "select_ms": times[2]}
+        if spk is not None:
+            out["speckle_ms"] = spk
+        outs.append(_finish_sgbm(out, maxDis, gts[i] if gts else None, masks[i] if masks else None, scale_factor, error_threshold,
+                                 verbose))
+    return outs
+
+
+def _finish_sgbm(out, maxDis, gt, mask, scale_factor, error_threshold, verbose):
+    d16 = out["disp16"]
     # minMaxLoc(imgDisparity16S, &minVal, &maxVal); imgDisparity16S.convertTo(lDispMap, CV_8U, 255/(maxVal - minVal));
     # lDispMap = (lDispMap/4) * scale_factor.  OpenCV's rounding of both steps: the factor is formed in double, but convertTo of a
     # 16-bit source multiplies in fp32 - saturate_cast<uchar>(cvRound((float)v * (float)alpha)), cvRound = ties to even, negative

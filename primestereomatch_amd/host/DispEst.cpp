@@ -306,6 +306,27 @@ int DispEst::computeBatch(DispEst *const *des, int n)
     return rc;
 }
 
+int DispEst::SGBMBatch(DispEst *const *des, int n, std::vector<std::vector<int16_t>> &disp16)
+{
+    if (!des || n < 1) return 1;
+    std::vector<psm_ctx *> cs;
+    for (int i = 0; i < n; ++i) {
+        if (!des[i] || des[i]->ctx.size() != 1) {
+            fprintf(stderr, "DispEst: SGBMBatch runs on single-device objects only\n");
+            return 1;
+        }
+        cs.push_back(des[i]->ctx[0]);
+    }
+    const HipApi &api = hipUtil::api();
+    int rc = api.sgm_compute_batch(cs.data(), n);
+    disp16.resize(rc ? 0 : (size_t)n);
+    for (int i = 0; i < n && !rc; ++i) {
+        disp16[i].resize((size_t)des[i]->wid * des[i]->hei);
+        rc |= api.sgm_download_disparity(cs[i], disp16[i].data(), 0);
+    }
+    return rc;
+}
+
 double DispEst::stageTimeUs(int stage) const
 {
     double us = 0;

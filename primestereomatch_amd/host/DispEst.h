@@ -133,6 +133,10 @@ public:
     // src/StereoMatch.cpp:556-607): CostConst_GPU + CostFilter_GPU + DispSelect_GPU of n single-device DispEst objects in shared
     // launches (psm_compute_batch); every object's lDisMap / rDisMap receive its maps.
     static int computeBatch(DispEst *const *des, int n);
+    // ... and the second algorithm: SGBM_GPU of n single-device objects of one geometry and one set of SGBM settings in shared
+    // launches (psm_sgm_compute_batch); disp16[i]: object i's H x W int16 map, as SGBM_GPU returns it.  Every object is afterwards
+    // where its own SGBM_GPU would have left it; sgbmTimes / sgbmSpeckleTime of des[0] report the batch.
+    static int SGBMBatch(DispEst *const *des, int n, std::vector<std::vector<int16_t>> &disp16);
 
     // psm_set_option on every device's context (PSM_OPT_FLAGS: e.g. PSM_FLAG_FMA_SOLVE - the maps of a reference binary built for an
     // FMA target -, PSM_OPT_SEG_ROWS, PSM_OPT_GATHER_STAGED, PSM_OPT_FRAMES_IN_FLIGHT ...; include/primesm_hip.h).  0 = ok.

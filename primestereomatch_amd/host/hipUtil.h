@@ -56,6 +56,7 @@ struct HipApi {
     int (*sgm_download_speckle_sizes)(psm_ctx *, int32_t *, size_t) = nullptr;
     int (*sgm_speckle_time)(psm_ctx *, double *) = nullptr;
     int (*sgm_set_prefilter)(psm_ctx *, int) = nullptr;
+    int (*sgm_compute_batch)(psm_ctx *const *, int) = nullptr;
 };
 
 class hipUtil {

@@ -8,7 +8,9 @@
 // ring > 0: additionally push that many frames of the pair through a psm::FrameRing of two objects (two frames in flight, each
 // object told PSM_OPT_FRAMES_IN_FLIGHT = 2), check every delivered frame's maps against the single-pair run, dump <out>_ldisp_ring.raw
 // batch > 1: additionally run that many copies of the pair as ONE batch (DispEst::computeBatch -> psm_compute_batch: the
-// reference's loop over pairs as shared launches), check every copy's maps against the single-pair run, dump <out>_ldisp_batch.raw
+// reference's loop over pairs as shared launches), check every copy's maps against the single-pair run, dump <out>_ldisp_batch.raw;
+// together with sgbm / sgbm_ref: also that many copies through DispEst::SGBMBatch (psm_sgm_compute_batch), every copy's int16
+// map checked against the single run's
 // frames > 0: additionally run that many frames of the pair through DispEst::computeFrame (asynchronous upload of the next
 // pair / download of the previous maps: the frame loop of src/main.cpp:64-73), dump its last maps as <out>_ldisp_loop.raw and
 // print the time per frame
@@ -165,6 +167,23 @@ int main(int argc, char **argv)
             printf("Speckle Time:\t %4.3f ms\n", spk);
         }
         ok = dump(out + "_sgbm16.raw", (const unsigned char *)d16.data(), d16.size() * sizeof(int16_t));
+        if (ok && batch > 1 && ndev == 1) {
+            std::vector<psm::DispEst *> des;
+            bool set = true;
+            for (int b = 0; b < batch; ++b) {
+                des.push_back(new psm::DispEst(l, r, D, 8, true, 1, dtype));
+                set = set && des[b]->ok() && !(sgbm_ref && (des[b]->setSGBMPreFilterCap(63) || des[b]->setSGBMSpeckle(100, 32)));
+            }
+            std::vector<std::vector<int16_t>> maps;
+            double bms[3] = {0, 0, 0};
+            const int rcb = !set || des[0]->setOption(PSM_OPT_PROFILE, 1) || psm::DispEst::SGBMBatch(des.data(), batch, maps) || des[0]->sgbmTimes(bms);
+            bool same = rcb == 0;
+            for (int b = 0; b < batch && same; ++b) same = maps[b] == d16;
+            printf("SGBM batch:\t %d pairs in one set of launches, per pair %4.3f ms cost, %4.3f ms paths, %4.3f ms select, maps %s\n", batch,
+                   bms[0] / batch, bms[1] / batch, bms[2] / batch, same ? "equal the single run's" : "DIFFER");
+            ok = same;
+            for (auto *d : des) delete d;
+        }
     }
     return ok ? 0 : 6;
 }

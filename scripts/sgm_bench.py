@@ -18,7 +18,15 @@ maps through psm_sgm_filter_speckles at (-16, 100, 512): a serpentine (the whole
 
 The prefiltered Birchfield-Tomasi cost (psm_sgm_set_prefilter; k_sgm_prefilter, k_sgm_bt_rows, k_sgm_bt_cols): every configuration
 is timed a third time in the same process at pre_filter_cap 63 with the filter off - the three group times as "*_ms_cap63" (the
-cost group holds the prefilter), their ratio to the SAD cost group, and the 12 W H bytes of planes the stage then holds."""
+cost group holds the prefilter), their ratio to the SAD cost group, and the 12 W H bytes of planes the stage then holds.
+
+--batch N[,N...]: instead of the above, several pairs per launch (psm_sgm_compute_batch).  Per configuration (450 x 375 x 64 and
+1280 x 720 x 128 at the batch sizes given; 1920 x 1080 x 256, 3.2 GB per context, at those of them that are 2 or 4), at
+pre_filter_cap 0 and 63 with the speckle filter on at (100, 32): per-pair ms of the three groups and of the filter for the batch
+(psm_sgm_times / psm_sgm_speckle_time of its first context over N), beside the same N contexts run one after another through
+psm_sgm_compute in the same process (the mean of their own times), hipEvents, median of --runs after --warmup, and the wall time
+per pair of both.  --reps R: the whole pair of measurements R times, singles and batch alternating - the spread between the
+repetitions is what a difference has to exceed."""
 import argparse
 import json
 import os
@@ -87,6 +95,80 @@ def speckle_maps(runs, warmup, out):
                     f.write(line + "\n")
 
 
+def batch_pairs(name, n):
+    """n pairs of the configuration's size: Cones and Teddy alternating at their size, synth pairs of n seeds elsewhere."""
+    W, H, D = CONFIGS[name]
+    if name == "cones":
+        zs = [np.load(os.path.join(ROOT, "tests", "golden", f"{k}_pair.npz")) for k in ("cones", "teddy")]
+        return [(zs[i % 2]["l_bgr"], zs[i % 2]["r_bgr"]) for i in range(n)]
+    from primestereomatch_amd import synth
+    return [synth.make_pair(W, H, D, seed=i)[:2] for i in range(n)]
+
+
+def batch_bench(a):
+    import primestereomatch_amd as P
+    from primestereomatch_amd import capi, dispest
+    if capi.device_count() < 1:
+        raise SystemExit("sgm_bench: no HIP device visible")
+    sizes = sorted({int(v) for v in a.batch.split(",")})
+    for name in a.configs.split(","):
+        W, H, D = CONFIGS[name]
+        ns = [n for n in sizes if name != "1080p" or n in (2, 4)]
+        if not ns:
+            continue
+        des = [P.DispEst(l, r, D) for l, r in batch_pairs(name, max(ns))]
+        try:
+            for de in des:
+                de.set_option(capi.PSM_OPT_PROFILE, 1)
+            for cap in (0, 63):
+                kw = dict(pre_filter_cap=cap, speckle_window_size=100, speckle_range=32)
+                for n in ns:
+                    sub = des[:n]
+
+                    def singles():
+                        t, wall = [], []
+                        for i in range(a.warmup + a.runs):
+                            w0 = time.perf_counter()
+                            for de in sub:
+                                de._ck(de._lib.psm_sgm_compute(de._h), "psm_sgm_compute")
+                            w = (time.perf_counter() - w0) * 1e3 / n
+                            if i >= a.warmup:
+                                wall.append(w)
+                                t.append(np.mean([list(de.sgm_times()) + [de.sgm_speckle_time()] for de in sub], axis=0))
+                        return np.median(np.array(t), axis=0), float(np.median(wall))
+
+                    def batch():
+                        t, wall = [], []
+                        for i in range(a.warmup + a.runs):
+                            w0 = time.perf_counter()
+                            dispest.sgm_compute_batch(sub)
+                            w = (time.perf_counter() - w0) * 1e3 / n
+                            if i >= a.warmup:
+                                wall.append(w)
+                                t.append(np.array(list(sub[0].sgm_times()) + [sub[0].sgm_speckle_time()]) / n)
+                        return np.median(np.array(t), axis=0), float(np.median(wall))
+
+                    maps1 = [de.SGBM_GPU(**kw) for de in sub]                      # (sets the parameters of every context)
+                    same = all(np.array_equal(x, y) for x, y in zip(maps1, dispest.sgbm_batch(sub, **kw)))
+                    for rep_i in range(a.reps):
+                        s_t, s_w = singles()
+                        b_t, b_w = batch()
+                        rec = {"bench": "sgm_batch", "config": name, "W": W, "H": H, "D": D, "pre_filter_cap": cap, "speckle": [100, 32],
+                               "batch": n, "rep": rep_i, "runs": a.runs, "warmup": a.warmup, "maps_equal_singles": bool(same)}
+                        for tag, t, w in (("singles", s_t, s_w), ("batch", b_t, b_w)):
+                            rec[tag + "_per_pair_ms"] = {"cost": round(float(t[0]), 4), "paths": round(float(t[1]), 4), "select": round(float(t[2]), 4),
+                                                         "speckle": round(float(t[3]), 4), "total": round(float(t.sum()), 4), "wall": round(w, 4)}
+                        rec["batch_over_singles_total"] = round(float(b_t.sum() / s_t.sum()), 3)
+                        line = json.dumps(rec)
+                        print(line, flush=True)
+                        if a.out:
+                            with open(a.out, "a") as f:
+                                f.write(line + "\n")
+        finally:
+            for de in des:
+                de.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="cones,720p,1080p")
@@ -95,9 +177,13 @@ def main():
     ap.add_argument("--model", action="store_true")
     ap.add_argument("--model-only", action="store_true")
     ap.add_argument("--speckle-maps", action="store_true")
+    ap.add_argument("--batch", default=None, help="N[,N...]: time psm_sgm_compute_batch at these batch sizes beside the singles")
+    ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert a.runs >= 1
+    if a.batch:
+        return batch_bench(a)
     for name in a.configs.split(","):
         W, H, D = CONFIGS[name]
         l, r = the_pair(name)
