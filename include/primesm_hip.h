@@ -457,6 +457,37 @@ int psm_joint_wmf_set_clusters(psm_ctx *ctx, int side, int n_clusters, const flo
  * set by the host).  Any output pointer may be NULL. */
 int psm_joint_wmf_clusters(psm_ctx *ctx, int side, int *n_clusters, float *centres, uint8_t *label_of_key, int *iterations);
 
+/* psm_joint_wmf of the n contexts ctxs[0..n) in shared launches: every kernel of the stage runs once with the image to cluster or
+ * the map side on a grid axis of its own.  The reference's use on Middlebury-size data is a loop over pairs and datasets
+ * (src/main.cpp:64-73, src/StereoMatch.cpp:528-609), and in a single call nearly all the time is one image's clustering chain - one
+ * seeding workgroup, two small launches per Lloyd iteration - with the rest of the device idle; the chains of different images are
+ * independent, so here they run side by side (one seeding workgroup per image in one launch, one pair of launches per Lloyd
+ * iteration for all images, one look at all convergence flags per 16 iterations; an image that has converged is frozen by its
+ * own flag while the others go on), and the median is one grid over the 2 n map sides.  Measured: DESIGN.md 9.
+ * The parameters are psm_joint_wmf's, with the same "0 selects the reference's value" rule and the same ranges.  The filtered maps
+ * stay on the device: psm_download_maps[_async] per context reads them, as after psm_compute_batch.
+ * Each context uses its own state - its own current pair (the feature images) and its own device maps (from psm_disp_select,
+ * psm_compute_batch, psm_disp_merge, psm_upload_maps, or after psm_lr_check / psm_fill_invalid) - and afterwards is exactly where
+ * its own psm_joint_wmf(ctx, ..., NULL, NULL, 0) would have left it: the same maps bit for bit (every sum of the stage is an exact
+ * integer, so no result depends on the grid's shape), the same clustering - psm_joint_wmf_clusters answers per context, a later
+ * single psm_joint_wmf on the same pair reuses clustering and tables - and the same weight tables.
+ * A side whose clustering the host set (psm_joint_wmf_set_clusters), or that an earlier call made with the same (n_clusters,
+ * max_iter), takes no part in the k-means, exactly as in psm_joint_wmf: the images to cluster are m <= 2 n.  With m = 0 the call
+ * never synchronises with the host and is asynchronous under PSM_OPT_ASYNC on ctxs[0]; with m > 0 it synchronises as the single
+ * call does (the sample counts, the convergence flags of all images once per 16 iterations, the centres).
+ * The contexts must agree on width, height, device and the depth of the staged pair.  Refused otherwise, and for NULL or repeated
+ * contexts, n < 1 or n > 4096, a context without maps or without an image pair, stripe-only maps, and radius or n_clusters out of
+ * range: psm_last_error(ctxs[0]) names the offending index, nothing has been enqueued, and every context's maps and clustering
+ * are as before.
+ * The launches run on ctxs[0]'s stream, after everything already queued on the other contexts' streams (a pending
+ * psm_download_maps_async of their maps included) and before anything queued on them later; synchronous on return unless ctxs[0]
+ * has PSM_OPT_ASYNC.  Contexts under psm_share_streams work as they are.
+ * Buffers stay per context (allocated on first use); the kernels reach them through a device table of n * 272 bytes that ctxs[0]
+ * owns and uploads from page-locked memory only when an entry changed, and the Lloyd states and centres of the m images lie in a
+ * block of ctxs[0] (n * 6176 bytes, and as much page-locked memory), so one copy reads all of them.  PSM_STAGE_PP of every
+ * context receives the batch's wall time; with PSM_OPT_PROFILE 1 on ctxs[0], PSM_K_JWMF of ctxs[0] counts the batch's launches. */
+int psm_joint_wmf_batch(psm_ctx *const *ctxs, int n, int radius, float sigma, int n_clusters, int max_iter);
+
 /* ---- second sharding axis: row stripes (SURVEY.md 8e asks for shards of the path; the filter's vertical support is
  * bounded - 8 rows of costs either side - so a stripe of output rows needs nothing from another stripe) ----
  * psm_set_rows restricts psm_cost_filter (select form) and psm_disp_select* of this context to the output rows

@@ -67,6 +67,7 @@ SYMBOLS = [
     ("psm_joint_wmf", _i, [_vp, _i, C.c_float, _i, _i, _vp, _vp, _sz]),
     ("psm_joint_wmf_set_clusters", _i, [_vp, _i, _i, _vp, _vp]),
     ("psm_joint_wmf_clusters", _i, [_vp, _i, _pi, _vp, _vp, _pi]),
+    ("psm_joint_wmf_batch", _i, [C.POINTER(_vp), _i, _i, C.c_float, _i, _i]),
     ("psm_set_rows", _i, [_vp, _i, _i]),
     ("psm_set_map_buffer", _i, [_vp, _vp, _i]),
     ("psm_gather_rows_ctx", _i, [_vp, _vp, _i, _vp, _vp, _sz]),

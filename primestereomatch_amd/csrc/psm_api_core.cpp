@@ -128,6 +128,7 @@ void free_all(psm_ctx *c)
     if (c->jw_pin) (void)hipHostFree(c->jw_pin);
     for (hipEvent_t e : c->ev_jw)
         if (e) (void)hipEventDestroy(e);
+    jwmf_batch_free(c);
     if (c->wm_pin) (void)hipHostFree(c->wm_pin);
     for (hipEvent_t e : {c->ev_wm[0], c->ev_wm[1]})
         if (e) (void)hipEventDestroy(e);

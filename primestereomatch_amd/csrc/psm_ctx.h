@@ -6,7 +6,8 @@
 //   psm_api_select.cpp  DispSelect: maps, packed minima, row stripes and disparity shards
 //   psm_api_pp.cpp      post-processing: L-R check, invalid fill, weighted median
 //   psm_api_batch.cpp   several Middlebury-size pairs per launch (psm_compute_batch)
-//   psm_api_jwmf.cpp    JointWMF: the joint weighted median of the reference's live post-filter (psm_joint_wmf)
+//   psm_api_jwmf.cpp    JointWMF: the joint weighted median of the reference's live post-filter (psm_joint_wmf), and of the
+//                       maps of several contexts in shared launches (psm_joint_wmf_batch)
 //   psm_api_rectify.cpp video mode: remap + crop of the camera frame into the staged image slot (psm_upload_pair_rectified)
 //   psm_api_sgm.cpp     semi-global matching over the staged pair, the reference's STEREO_SGBM branch (psm_sgm_compute), and
 //                       over the pairs of several contexts in shared launches (psm_sgm_compute_batch)
@@ -68,6 +69,20 @@ struct SgmState {
     size_t tab_cap = 0;
     int tab_slot = 0;
     hipEvent_t ev_tab[2] = {nullptr, nullptr};
+};
+
+// psm_joint_wmf_batch (psm_api_jwmf.cpp; this context as the first of a batch): the device table - JwImg records of the images to
+// cluster, behind them the JwSide records of the map sides - with its host copy (uploaded again only when an entry changed) and
+// its page-locked staging, two slots used alternately as SgmState's; `block`: the Lloyd states and centres of the images side by
+// side, `pin` the page-locked memory the host reads them in.
+struct JwBatch {
+    uint8_t *tab = nullptr, *tab_pin = nullptr;
+    std::vector<uint8_t> tab_host;
+    size_t tab_cap = 0;                            // bytes
+    int tab_slot = 0;
+    hipEvent_t ev_tab[2] = {nullptr, nullptr};
+    uint8_t *block = nullptr, *pin = nullptr;      // [cap] x {int state[4]}, then [cap] x {float centres[JW_NF_MAX][3]}
+    size_t cap = 0;                                // images
 };
 }  // namespace psm
 
@@ -135,6 +150,7 @@ struct psm_ctx {
     float jw_tab_sigma[2] = {0.f, 0.f};
     unsigned long long *jw_pin = nullptr;  // page-locked staging of the two integer tables (on first use)
     hipEvent_t ev_jw[2] = {nullptr, nullptr};   // ... the copy out of a side's staging has executed
+    psm::JwBatch jwb;
     // psm_upload_pair_rectified (psm_api_rectify.cpp): the W x H crop window of a side's CV_16SC2 maps, uploaded once by
     // psm_rectify_set_maps; the unrectified source frames (both eyes, packed rows) per staging slot and their page-locked staging,
     // allocated on first use
@@ -298,6 +314,8 @@ unsigned long long *next_pc_stamp(psm_ctx *c);   // slot of the next k_cvf_pc la
 
 // psm_api_rectify.cpp
 void rectify_free(psm_ctx *c, bool maps);        // the source slots and their staging; maps: the device maps too
+// psm_api_jwmf.cpp
+void jwmf_batch_free(psm_ctx *c);                // what the context holds as the first of a psm_joint_wmf_batch
 // psm_api_sgm.cpp
 void sgm_free(psm_ctx *c);                       // the stage's buffers and events (its parameters stay)
 // psm_api_select.cpp: copy_maps_out - two [H][W] planes on the device to the caller's rows

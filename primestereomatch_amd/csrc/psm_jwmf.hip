@@ -11,6 +11,11 @@
 // The reference's column scan with its joint histogram and necklace tables (filterCore, JointWMF.h:173-410) is a serial
 // speed-up of that definition; nothing of it is used here.  The weight table itself is formed on the host with libm expf
 // (psm_api_jwmf.cpp), so it is the reference's float table bit for bit.
+//
+// Several pairs per launch (psm_joint_wmf_batch): every kernel is one body (jw_*) behind two entries.  k_jw_* takes its buffers
+// as arguments, as ever; k_jw_*_b has the image to cluster (JwImg) or the map side (JwSide) on a grid axis of its own and reads
+// the buffers from the device table - the index is uniform per workgroup, so these are scalar loads ahead of an unchanged body.
+// All sums are exact integers: a body's result does not depend on the grid it runs in.
 #include "psm_kernels.h"
 
 namespace psm {
@@ -43,13 +48,29 @@ __device__ __forceinline__ unsigned key_at(const void *img, int depth, size_t p)
 __device__ __forceinline__ void key_xyz(unsigned k, int &x, int &y, int &z) { x = (int)(k >> 12); y = (int)((k >> 6) & 63); z = (int)(k & 63); }
 
 // presence of every key of one image: one bit per key in a 2^18-bit map
-__global__ void k_jw_keys(const void *img, int depth, size_t HW, unsigned *bits)
+__device__ __forceinline__ void jw_keys(const void *img, int depth, size_t HW, unsigned *bits)
 {
     for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += (size_t)gridDim.x * blockDim.x) {
         const unsigned k = key_at(img, depth, p);
         const unsigned m = 1u << (k & 31);
         if (!(bits[k >> 5] & m)) atomicOr(&bits[k >> 5], m);
     }
+}
+
+__global__ void k_jw_keys(const void *img, int depth, size_t HW, unsigned *bits) { jw_keys(img, depth, HW, bits); }
+__global__ void k_jw_keys_b(const JwImg *tab, int depth, size_t HW)
+{
+    const JwImg &r = tab[blockIdx.y];
+    jw_keys(sgm_global(r.img), depth, HW, sgm_global(r.bits));
+}
+
+// batch: the key bitmap (what 0) or the key -> cluster table (what 1) of every image to zero, 16 bytes per lane
+__global__ void k_jw_clear_b(const JwImg *tab, int what)
+{
+    const JwImg &r = tab[blockIdx.y];
+    uint4 *p = what ? (uint4 *)sgm_global(r.lok) : (uint4 *)sgm_global(r.bits);
+    const size_t n = (what ? (size_t)JW_KEYS : (size_t)JW_KEYS / 8) / 16;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = make_uint4(0, 0, 0, 0);
 }
 
 // inclusive block scan of one 64-bit value per thread (blockDim.x = 64 * waves <= 1024)
@@ -73,7 +94,7 @@ __device__ unsigned long long block_scan_u64(unsigned long long v, unsigned long
 }
 
 // ordered compaction of the key bitmap into the ascending sample list (one workgroup of 1024 threads, 8 words each)
-__global__ void __launch_bounds__(1024) k_jw_compact(const unsigned *bits, unsigned *samples, int *n_out)
+__device__ __forceinline__ void jw_compact(const unsigned *bits, unsigned *samples, int *n_out)
 {
     __shared__ unsigned long long wsum[17];
     const int w0 = threadIdx.x * (JW_KEYS / 32 / 1024);
@@ -92,8 +113,15 @@ __global__ void __launch_bounds__(1024) k_jw_compact(const unsigned *bits, unsig
     if (threadIdx.x == blockDim.x - 1) *n_out = (int)incl;
 }
 
+__global__ void __launch_bounds__(1024) k_jw_compact(const unsigned *bits, unsigned *samples, int *n_out) { jw_compact(bits, samples, n_out); }
+__global__ void __launch_bounds__(1024) k_jw_compact_b(const JwImg *tab)
+{
+    const JwImg &r = tab[blockIdx.x];
+    jw_compact(sgm_global(r.bits), sgm_global(r.samples), sgm_global(r.state) + 3);
+}
+
 // every sample its own cluster
-__global__ void k_jw_identity(const unsigned *samples, int n, float *centres, int *labels)
+__device__ __forceinline__ void jw_identity(const unsigned *samples, int n, float *centres, int *labels)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -101,6 +129,16 @@ __global__ void k_jw_identity(const unsigned *samples, int n, float *centres, in
     key_xyz(samples[i], x, y, z);
     centres[3 * i] = (float)x; centres[3 * i + 1] = (float)y; centres[3 * i + 2] = (float)z;
     labels[i] = i;
+}
+
+__global__ void k_jw_identity(const unsigned *samples, int n, float *centres, int *labels) { jw_identity(samples, n, centres, labels); }
+// batch: the images with at most n_clusters samples; such an image counts as converged from the start (the Lloyd entries skip it)
+__global__ void k_jw_identity_b(const JwImg *tab, int n_clusters)
+{
+    const JwImg &r = tab[blockIdx.y];
+    if (r.n > n_clusters) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) sgm_global(r.state)[1] = 1;
+    jw_identity(sgm_global(r.samples), r.n, sgm_global(r.centres), sgm_global(r.labels));
 }
 
 __device__ __forceinline__ unsigned long long splitmix64(unsigned long long &s)
@@ -115,8 +153,8 @@ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long &s)
 // k-means++ seeding in one workgroup: thread t owns the samples [t*chunk, (t+1)*chunk) (kept transposed in kt / d2t so the
 // rounds read coalesced); per round a block scan of the owners' D^2 sums finds the owner of the draw, which walks its chunk.
 // Seeds are samples: D^2 and all prefix sums are integers, so the choice is exact.
-__global__ void __launch_bounds__(JW_SEED_THREADS) k_jw_seed(const unsigned *samples, int n, int nf, unsigned long long seed,
-                                                             float *centres, unsigned *kt, unsigned *d2t)
+__device__ __forceinline__ void jw_seed(const unsigned *samples, int n, int nf, unsigned long long seed, float *centres, unsigned *kt,
+                                        unsigned *d2t)
 {
     __shared__ unsigned long long wsum[17];
     __shared__ unsigned long long s_r;
@@ -165,10 +203,27 @@ __global__ void __launch_bounds__(JW_SEED_THREADS) k_jw_seed(const unsigned *sam
     }
 }
 
+__global__ void __launch_bounds__(JW_SEED_THREADS) k_jw_seed(const unsigned *samples, int n, int nf, unsigned long long seed,
+                                                             float *centres, unsigned *kt, unsigned *d2t)
+{
+    jw_seed(samples, n, nf, seed, centres, kt, d2t);
+}
+// batch: one workgroup per image with more than n_clusters samples, every image from the same seed; behind the seeding the
+// workgroup puts the image's Lloyd state where the single call's three fills put it (labels -1, sums 0; the state block is
+// zero from the start of the call)
+__global__ void __launch_bounds__(JW_SEED_THREADS) k_jw_seed_b(const JwImg *tab, int n_clusters, unsigned long long seed)
+{
+    const JwImg &r = tab[blockIdx.x];
+    if (r.n <= n_clusters) return;
+    jw_seed(sgm_global(r.samples), r.n, r.nf, seed, sgm_global(r.centres), sgm_global(r.kt), sgm_global(r.d2t));
+    int *labels = sgm_global(r.labels), *sums = sgm_global(r.sums);
+    for (int i = threadIdx.x; i < r.n; i += JW_SEED_THREADS) labels[i] = -1;
+    for (int i = threadIdx.x; i < JW_NF_MAX * 4; i += JW_SEED_THREADS) sums[i] = 0;
+}
+
 // Lloyd assignment: nearest centre in fp32 ((t0*t0 + t1*t1) + t2*t2, no contraction), ties to the lower index; integer
 // sums and counts of the new clusters; st[0] counts the samples whose label changed.  st[1] != 0: converged, nothing to do.
-__global__ void __launch_bounds__(256) k_jw_assign(const unsigned *samples, int n, int nf, const float *centres, int *labels,
-                                                   int *sums, int *st)
+__device__ __forceinline__ void jw_assign(const unsigned *samples, int n, int nf, const float *centres, int *labels, int *sums, int *st)
 {
     __shared__ float c[JW_NF_MAX * 3];
     __shared__ int acc[JW_NF_MAX * 4];
@@ -202,9 +257,21 @@ __global__ void __launch_bounds__(256) k_jw_assign(const unsigned *samples, int 
     if ((threadIdx.x & 63) == 0 && changed) atomicAdd(&st[0], changed);
 }
 
+__global__ void __launch_bounds__(256) k_jw_assign(const unsigned *samples, int n, int nf, const float *centres, int *labels,
+                                                   int *sums, int *st)
+{
+    jw_assign(samples, n, nf, centres, labels, sums, st);
+}
+// batch: the image on grid axis y, x sized for the largest image (an image's workgroups beyond its samples add nothing)
+__global__ void __launch_bounds__(256) k_jw_assign_b(const JwImg *tab)
+{
+    const JwImg &r = tab[blockIdx.y];
+    jw_assign(sgm_global(r.samples), r.n, r.nf, sgm_global(r.centres), sgm_global(r.labels), sgm_global(r.sums), sgm_global(r.state));
+}
+
 // Lloyd update (one workgroup): no label changed in iteration `it` -> converged after it + 1 assignments (st[1], st[2]);
 // otherwise every non-empty cluster moves to its integer sums / count (fp32, exact operands, correctly rounded).
-__global__ void __launch_bounds__(256) k_jw_update(int nf, float *centres, int *sums, int *st, int it)
+__device__ __forceinline__ void jw_update(int nf, float *centres, int *sums, int *st, int it)
 {
     if (st[1]) return;
     const int changed = st[0];
@@ -224,29 +291,51 @@ __global__ void __launch_bounds__(256) k_jw_update(int nf, float *centres, int *
     }
 }
 
-__global__ void k_jw_lok(const unsigned *samples, int n, const int *labels, uint8_t *lok)
+__global__ void __launch_bounds__(256) k_jw_update(int nf, float *centres, int *sums, int *st, int it) { jw_update(nf, centres, sums, st, it); }
+__global__ void __launch_bounds__(256) k_jw_update_b(const JwImg *tab, int it)
+{
+    const JwImg &r = tab[blockIdx.x];
+    jw_update(r.nf, sgm_global(r.centres), sgm_global(r.sums), sgm_global(r.state), it);
+}
+
+__device__ __forceinline__ void jw_lok(const unsigned *samples, int n, const int *labels, uint8_t *lok)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) lok[samples[i]] = (uint8_t)labels[i];
 }
 
-// per-pixel cluster plane of both sides: F = label_of_key[key]
-__global__ void k_jw_plane(JwPair pr, int depth, size_t HW)
+__global__ void k_jw_lok(const unsigned *samples, int n, const int *labels, uint8_t *lok) { jw_lok(samples, n, labels, lok); }
+__global__ void k_jw_lok_b(const JwImg *tab)
 {
-    const JwSide &s = pr.s[blockIdx.y];
+    const JwImg &r = tab[blockIdx.y];
+    jw_lok(sgm_global(r.samples), r.n, sgm_global(r.labels), sgm_global(r.lok));
+}
+
+// per-pixel cluster plane of both sides: F = label_of_key[key]
+__device__ __forceinline__ void jw_plane(const JwSide &s, int depth, size_t HW)
+{
     for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += (size_t)gridDim.x * blockDim.x)
         s.F[p] = s.lok[key_at(s.img, depth, p)];
 }
+
+// a map side's record of the device table, its pointers read as global ones (sgm_global, psm_kernels.h)
+__device__ __forceinline__ JwSide jw_side(const JwSide *tab, unsigned i)
+{
+    const JwSide &t = tab[i];
+    return JwSide{sgm_global(t.img), sgm_global(t.lok), sgm_global(t.F), sgm_global(t.din), sgm_global(t.wq), sgm_global(t.out)};
+}
+
+__global__ void k_jw_plane(JwPair pr, int depth, size_t HW) { jw_plane(pr.s[blockIdx.y], depth, HW); }
+__global__ void k_jw_plane_b(const JwSide *tab, int depth, size_t HW) { jw_plane(jw_side(tab, blockIdx.y), depth, HW); }
 
 // The weighted median of both maps: one lane per output pixel of a 16 x 16 tile, the (disparity, cluster) pairs of the tile
 // and its halo staged in LDS.  Two radix passes over 16 bins each (high nibble, then the low nibble inside the chosen high
 // bin), every lane with its own 64-bit bins in LDS (bin-major, lane-minor: a lane's bins never share a bank with another
 // lane's).  The sums are exact integers: the result does not depend on their order.
-__global__ void __launch_bounds__(256) k_jw_median(JwPair pr, int W, int H, int r)
+__device__ __forceinline__ void jw_median(const JwSide &s, int W, int H, int r)
 {
     __shared__ unsigned short tile[JW_HALO_MAX * JW_HALO_MAX];
     __shared__ unsigned long long bins[16][256];
-    const JwSide &s = pr.s[blockIdx.z];
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * JW_TILE, y0 = blockIdx.y * JW_TILE;
     const int tw = JW_TILE + 2 * r;
@@ -296,6 +385,9 @@ __global__ void __launch_bounds__(256) k_jw_median(JwPair pr, int W, int H, int 
     s.out[(size_t)y * W + x] = (uint8_t)(16 * h + l);
 }
 
+__global__ void __launch_bounds__(256) k_jw_median(JwPair pr, int W, int H, int r) { jw_median(pr.s[blockIdx.z], W, H, r); }
+__global__ void __launch_bounds__(256) k_jw_median_b(const JwSide *tab, int W, int H, int r) { jw_median(jw_side(tab, blockIdx.z), W, H, r); }
+
 }  // namespace
 
 void launch_jw_keys(hipStream_t st, const void *img, int depth, size_t HW, unsigned *bits)
@@ -342,6 +434,55 @@ void launch_jw_plane(hipStream_t st, const JwPair &pr, int depth, size_t HW)
 void launch_jw_median(hipStream_t st, const JwPair &pr, int W, int H, int r)
 {
     hipLaunchKernelGGL(k_jw_median, dim3((W + JW_TILE - 1) / JW_TILE, (H + JW_TILE - 1) / JW_TILE, 2), dim3(256), 0, st, pr, W, H, r);
+}
+
+// ---- several pairs per launch: m images to cluster (img), n_sides map sides (sides) ----
+
+void launch_jw_keys_b(hipStream_t st, const JwImg *img, int m, int depth, size_t HW)
+{
+    const unsigned blocks = (unsigned)((HW + 255) / 256 < 2048 ? (HW + 255) / 256 : 2048);
+    hipLaunchKernelGGL(k_jw_clear_b, dim3(JW_KEYS / 8 / 16 / 256, m), dim3(256), 0, st, img, 0);
+    hipLaunchKernelGGL(k_jw_keys_b, dim3(blocks ? blocks : 1, m), dim3(256), 0, st, img, depth, HW);
+}
+
+void launch_jw_compact_b(hipStream_t st, const JwImg *img, int m)
+{
+    hipLaunchKernelGGL(k_jw_compact_b, dim3(m), dim3(1024), 0, st, img);
+}
+
+void launch_jw_identity_b(hipStream_t st, const JwImg *img, int m, int n_clusters)
+{
+    hipLaunchKernelGGL(k_jw_identity_b, dim3((n_clusters + 255) / 256, m), dim3(256), 0, st, img, n_clusters);
+}
+
+void launch_jw_seed_b(hipStream_t st, const JwImg *img, int m, int n_clusters, unsigned long long seed)
+{
+    hipLaunchKernelGGL(k_jw_seed_b, dim3(m), dim3(JW_SEED_THREADS), 0, st, img, n_clusters, seed);
+}
+
+void launch_jw_lloyd_b(hipStream_t st, const JwImg *img, int m, int n_max, int it)
+{
+    int blocks = (n_max + 255) / 256;
+    blocks = blocks > 512 ? 512 : blocks;
+    hipLaunchKernelGGL(k_jw_assign_b, dim3(blocks, m), dim3(256), 0, st, img);
+    hipLaunchKernelGGL(k_jw_update_b, dim3(m), dim3(256), 0, st, img, it);
+}
+
+void launch_jw_lok_b(hipStream_t st, const JwImg *img, int m, int n_max)
+{
+    hipLaunchKernelGGL(k_jw_clear_b, dim3(64, m), dim3(256), 0, st, img, 1);
+    hipLaunchKernelGGL(k_jw_lok_b, dim3((n_max + 255) / 256, m), dim3(256), 0, st, img);
+}
+
+void launch_jw_plane_b(hipStream_t st, const JwSide *sides, int n_sides, int depth, size_t HW)
+{
+    const unsigned blocks = (unsigned)((HW + 255) / 256 < 2048 ? (HW + 255) / 256 : 2048);
+    hipLaunchKernelGGL(k_jw_plane_b, dim3(blocks ? blocks : 1, n_sides), dim3(256), 0, st, sides, depth, HW);
+}
+
+void launch_jw_median_b(hipStream_t st, const JwSide *sides, int n_sides, int W, int H, int r)
+{
+    hipLaunchKernelGGL(k_jw_median_b, dim3((W + JW_TILE - 1) / JW_TILE, (H + JW_TILE - 1) / JW_TILE, n_sides), dim3(256), 0, st, sides, W, H, r);
 }
 
 }  // namespace psm

@@ -201,6 +201,27 @@ void launch_jw_lloyd(hipStream_t s, const unsigned *samples, int n, int nf, floa
 void launch_jw_lok(hipStream_t s, const unsigned *samples, int n, const int *labels, uint8_t *lok);
 void launch_jw_plane(hipStream_t s, const JwPair &pr, int depth, size_t HW);
 void launch_jw_median(hipStream_t s, const JwPair &pr, int W, int H, int r);
+// Several pairs of one geometry per launch (psm_joint_wmf_batch): the device table holds one JwImg per image to cluster and one
+// JwSide per map side; the batched entries k_jw_*_b index it with a grid axis and read the pointers as global ones (sgm_global
+// below).  Buffers are the contexts' own (JwScratch), but for state and centres: those lie side by side in a block of the batch,
+// so the host reads all of them in one copy.
+struct JwImg {
+    const void *img;
+    unsigned *bits, *samples, *kt, *d2t;
+    int *labels, *sums;
+    int *state;                        // {changed, converged, iterations, sample count} in the batch's block
+    float *centres;                    // [JW_NF_MAX][3] in the batch's block
+    uint8_t *lok;
+    int n, nf;                         // sample count and clusters: known (and uploaded) once the samples have been counted
+};
+void launch_jw_keys_b(hipStream_t s, const JwImg *img, int m, int depth, size_t HW);     // clears the bitmaps first
+void launch_jw_compact_b(hipStream_t s, const JwImg *img, int m);
+void launch_jw_identity_b(hipStream_t s, const JwImg *img, int m, int n_clusters);      // the images with n <= n_clusters
+void launch_jw_seed_b(hipStream_t s, const JwImg *img, int m, int n_clusters, unsigned long long seed);   // ... the others
+void launch_jw_lloyd_b(hipStream_t s, const JwImg *img, int m, int n_max, int it);
+void launch_jw_lok_b(hipStream_t s, const JwImg *img, int m, int n_max);                 // clears the tables first
+void launch_jw_plane_b(hipStream_t s, const JwSide *sides, int n_sides, int depth, size_t HW);
+void launch_jw_median_b(hipStream_t s, const JwSide *sides, int n_sides, int W, int H, int r);
 
 // psm_rectify.hip: remap (CV_16SC2 maps, INTER_LINEAR, constant border 0) + crop of both eyes (psm_api_rectify.cpp)
 struct RectSide {

@@ -532,6 +532,28 @@ def sgm_compute_batch(des):
     capi.check(des[0]._lib.psm_sgm_compute_batch(arr, len(des)), des[0]._h, "sgm_compute_batch")
 
 
+def joint_wmf_batch(des, radius: int = 0, sigma: float = 0.0, n_clusters: int = 0, max_iter: int = 0):
+    """JointWMF_GPU of several DispEst objects of one geometry in shared launches (psm_joint_wmf_batch): each object's device maps
+    are filtered with its own pair (the parameters: JointWMF_GPU's), the clustering chains of all images side by side; then every
+    object's lDisMap / rDisMap are refreshed (download_maps).  Every object afterwards behaves as after its own JointWMF_GPU
+    (jwmf_clusters(), a later JointWMF_GPU on the same pair reuses the clustering)."""
+    des = list(des)
+    if not des:
+        return
+    joint_wmf_batch_device(des, radius, sigma, n_clusters, max_iter)
+    for d in des:
+        d.download_maps()
+
+
+def joint_wmf_batch_device(des, radius: int = 0, sigma: float = 0.0, n_clusters: int = 0, max_iter: int = 0):
+    """psm_joint_wmf_batch alone: the filtered maps stay on the device (asynchronous under PSM_OPT_ASYNC on des[0] when no image
+    needs the device k-means)."""
+    des = list(des)
+    arr = (C.c_void_p * len(des))(*[d._h for d in des])
+    capi.check(des[0]._lib.psm_joint_wmf_batch(arr, len(des), int(radius), float(sigma), int(n_clusters), int(max_iter)),
+               des[0]._h, "joint_wmf_batch")
+
+
 def share_streams(des):
     """The DispEst objects of a batch run on one compute stream and one copy stream each way (psm_share_streams) - call once
     before a frame loop over batches."""

@@ -7,6 +7,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import capi
+from . import dispest
 from .dispest import DispEst, sgbm_batch
 
 MASK_NONE, MASK_NONOCC, MASK_DISC = 0, 1, 2   # include/StereoMatch.h
@@ -51,6 +52,48 @@ def compute(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, error_t
         SMDE.setInputImages(lFrame, rFrame)
         _run_stages(SMDE, out, threads, subsample_rate, post_process, process_dm, joint_wmf)
     return _finish(out, maxDis, gt, mask, scale_factor, error_threshold, verbose)
+
+
+def compute_batch(pairs, maxDis=64, gts=None, masks=None, scale_factor=4, error_threshold=4, dtype="f32", post_process=True,
+                  joint_wmf=False, verbose=False):
+    """compute() for a list of (l_bgr, r_bgr) uint8 pairs of one size in shared launches: the reference's loop over pairs and
+    datasets (src/main.cpp:64-73, src/StereoMatch.cpp:528-609) on the live STEREO_GIF branch.  dispest.compute_batch (CostConst +
+    CostFilter + DispSelect of all pairs), then per object the L-R check when post_process, then dispest.joint_wmf_batch when
+    joint_wmf (the live processDM body on every pair's maps, the clustering chains of all images side by side).  gts / masks: one
+    per pair (or None).  -> a list of compute's records; the stage times are each object's (a batch's wall time is charged to
+    every member)."""
+    if not pairs:
+        return []
+    frames = []
+    for l, r in pairs:
+        l, r = np.ascontiguousarray(l), np.ascontiguousarray(r)
+        if dtype == "f32":
+            l, r = l.astype(np.float32) * np.float32(1 / 255.0), r.astype(np.float32) * np.float32(1 / 255.0)
+        frames.append((l, r))
+    des = [DispEst(l, r, maxDis, 8, True, dtype=dtype) for l, r in frames]
+    outs = [{} for _ in des]
+    try:
+        dispest.compute_batch(des)
+        for d, out in zip(des, outs):
+            d.download_maps()
+            if post_process:
+                d.LRCheck_GPU()
+                out["lValid"], out["rValid"] = d.lValid.copy(), d.rValid.copy()
+            if joint_wmf:
+                out["lDisMap_raw"], out["rDisMap_raw"] = d.lDisMap.copy(), d.rDisMap.copy()
+        if joint_wmf:
+            dispest.joint_wmf_batch(des)
+        for d, out in zip(des, outs):
+            out["cvc_ms"] = d.stage_time_us(capi.PSM_STAGE_CVC) / 1000
+            out["cvf_ms"] = d.stage_time_us(capi.PSM_STAGE_CVF) / 1000
+            out["dispsel_ms"] = d.stage_time_us(capi.PSM_STAGE_DISPSEL) / 1000
+            out["pp_ms"] = d.stage_time_us(capi.PSM_STAGE_PP) / 1000
+            out["lDisMap"], out["rDisMap"] = d.lDisMap.copy(), d.rDisMap.copy()
+    finally:
+        for d in des:
+            d.close()
+    return [_finish(out, maxDis, gts[i] if gts else None, masks[i] if masks else None, scale_factor, error_threshold, verbose)
+            for i, out in enumerate(outs)]
 
 
 def compute_video(vFrame, rectification, maxDis=64, gt=None, mask=None, scale_factor=4, error_threshold=4, threads=8,

@@ -327,6 +327,24 @@ int DispEst::SGBMBatch(DispEst *const *des, int n, std::vector<std::vector<int16
     return rc;
 }
 
+int DispEst::JointWMFBatch(DispEst *const *des, int n, int radius, float sigma, int n_clusters, int max_iter)
+{
+    if (!des || n < 1) return 1;
+    std::vector<psm_ctx *> cs;
+    for (int i = 0; i < n; ++i) {
+        if (!des[i] || des[i]->ctx.size() != 1) {
+            fprintf(stderr, "DispEst: JointWMFBatch runs on single-device objects only\n");
+            return 1;
+        }
+        cs.push_back(des[i]->ctx[0]);
+    }
+    const HipApi &api = hipUtil::api();
+    int rc = api.joint_wmf_batch(cs.data(), n, radius, sigma, n_clusters, max_iter);
+    for (int i = 0; i < n && !rc; ++i)
+        rc |= api.download_maps(cs[i], des[i]->lDisMap.data, des[i]->rDisMap.data, des[i]->lDisMap.step);
+    return rc;
+}
+
 double DispEst::stageTimeUs(int stage) const
 {
     double us = 0;

@@ -137,6 +137,10 @@ public:
     // launches (psm_sgm_compute_batch); disp16[i]: object i's H x W int16 map, as SGBM_GPU returns it.  Every object is afterwards
     // where its own SGBM_GPU would have left it; sgbmTimes / sgbmSpeckleTime of des[0] report the batch.
     static int SGBMBatch(DispEst *const *des, int n, std::vector<std::vector<int16_t>> &disp16);
+    // ... and the live post-filter: JointWMF_GPU of n single-device objects of one geometry in shared launches (psm_joint_wmf_batch;
+    // 0: the reference's radius, sigma, cluster count and iteration limit), each object's device maps with its own pair - after
+    // computeBatch, say, with or without the L-R check between; every object's lDisMap / rDisMap receive its filtered maps.
+    static int JointWMFBatch(DispEst *const *des, int n, int radius = 0, float sigma = 0, int n_clusters = 0, int max_iter = 0);
 
     // psm_set_option on every device's context (PSM_OPT_FLAGS: e.g. PSM_FLAG_FMA_SOLVE - the maps of a reference binary built for an
     // FMA target -, PSM_OPT_SEG_ROWS, PSM_OPT_GATHER_STAGED, PSM_OPT_FRAMES_IN_FLIGHT ...; include/primesm_hip.h).  0 = ok.
