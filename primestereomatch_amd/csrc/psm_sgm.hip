@@ -387,7 +387,8 @@ __global__ __launch_bounds__(256) void k_sgm_path(SgmArgs a, int dy, int dx) { s
 template <int NV, bool FIRST, bool ALL>
 __global__ __launch_bounds__(256) void k_sgm_path_b(SgmArgs a, const SgmPair *tab, int dy, int dx) { sgm_path<NV, FIRST, ALL>(sgm_pair_args(a, tab, blockIdx.z), dy, dx); }
 
-// One wave per pixel: the packed (S << 8 | d) minimum over the wave is argmin with the lowest d on ties (S < 2^19).
+// One wave per pixel: the packed (S << 8 | d) minimum over the wave is argmin with the lowest d on ties (S < 2^19: at most
+// 8 * 65535 = 524280, which tests/test_gpu_sgm_fuzz.py::test_saturating_pairs_reach_the_packing_bound reaches).
 template <int NV>
 __device__ __forceinline__ void sgm_select(const SgmArgs &a)
 {

@@ -34,12 +34,14 @@ _INF = 1 << 28
 
 
 def quantise(img):
-    """convertTo(CV_8U, 255) of a float image: saturate_cast<uchar>(cvRound(f * 255.0f)), the product in fp32, ties to even."""
+    """convertTo(CV_8U, 255) of a float image: saturate_cast<uchar>(cvRound(f * 255.0f)), the product in fp32, ties to even.
+    NaN -> 0: the device's fminf(fmaxf(rintf(f * 255.0f), 0.0f), 255.0f), where fmaxf(NaN, 0) is 0 (jwmf_model.feature_u8 alike)."""
     img = np.asarray(img)
     if img.dtype == np.uint8:
         return img
-    v = np.rint(img.astype(np.float32) * np.float32(255.0))
-    return np.clip(v, 0, 255).astype(np.uint8)
+    with np.errstate(invalid="ignore"):                      # inf * 255, comparisons with NaN
+        v = np.rint(img.astype(np.float32) * np.float32(255.0))
+        return np.where(v > 0, np.minimum(v, np.float32(255)), np.float32(0)).astype(np.uint8)
 
 
 def resolve_params(ch, block_size=0, P1=0, P2=0, uniqueness_ratio=10, disp12_max_diff=1):

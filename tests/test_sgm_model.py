@@ -215,6 +215,17 @@ def test_quantise_is_convert_to_8u_255():
     assert np.array_equal(M.quantise(f), want) and want[-2] == 0 and want[-1] == 255
 
 
+def test_quantise_sends_nan_to_0_and_infinities_to_the_ends():
+    """The device's fminf(fmaxf(rintf(f * 255.0f), 0.0f), 255.0f): fmaxf(NaN, 0) is 0.  The model says so itself instead of leaving
+    NaN to a float -> uint8 cast, as jwmf_model.feature_u8 does for its feature image."""
+    f = np.array([np.nan, -np.nan, np.inf, -np.inf, -0.0, 1.0, np.nan], np.float32)
+    with np.errstate(all="raise"):                           # no invalid cast on the way
+        got = M.quantise(f)
+    assert got.dtype == np.uint8 and got.tolist() == [0, 0, 255, 0, 0, 255, 0]
+    img = np.full((3, 4, 3), np.nan, np.float32)
+    assert not M.quantise(img).any() and not M._as3(img[:, :, 0]).any()
+
+
 def test_display_map_rounds_as_opencv_does():
     d16 = np.array([[-16, 0, 160, 1008]], np.int16)          # alpha = 255 / 1024
     out = M.display_map(d16, 4)
