@@ -320,6 +320,21 @@ int psm_sgm_download_costs(psm_ctx *ctx, int which, void *host);
  * prefilter included), its eight path launches and its select + check launches (a getter of its own: the PSM_K_* and PSM_STAGE_* tables stay as they are). */
 int psm_sgm_times(psm_ctx *ctx, double ms[3]);
 
+/* StereoSGBM's modes (ssgbm->setMode, the reference's `m` key: src/main.cpp:22,114-168): the set of directions step "paths" sums.
+ * Everything else above is untouched.  (dy, dx) is the step from the predecessor p-r to p; the values are OpenCV's enum:
+ *   PSM_SGM_MODE_SGBM       (0, 1), (0, -1), (1, 0), (1, 1), (1, -1): OpenCV's single top-down pass plus the right-to-left row path
+ *                           it forms during selection
+ *   PSM_SGM_MODE_HH         all eight - a new context's setting: psm_sgm_compute is what it is without this function
+ *   PSM_SGM_MODE_SGBM_3WAY  (0, 1), (0, -1), (1, 0)
+ *   PSM_SGM_MODE_HH4        (0, 1), (0, -1), (1, 0), (-1, 0)   (the reference's key does not reach it; OpenCV's enum has it)
+ * The paths cross the whole image in every mode: OpenCV cuts the 3-way image into stripes by thread count and restarts its paths
+ * in each, which is not built.  The definition is tests/sgm_mode_model.py; agreement with a live cv::StereoSGBM stays unpinned in
+ * every mode.  S is at most (directions) * 65535 < 2^19 as before.  Any other value is refused.  The setting holds until changed;
+ * psm_sgm_compute, _compute_gray and _compute_batch launch the mode's directions in the order above, the first one stores S;
+ * psm_sgm_times' second number covers the mode's path launches.  psm_sgm_compute_batch refuses contexts whose modes differ. */
+enum { PSM_SGM_MODE_SGBM = 0, PSM_SGM_MODE_HH = 1, PSM_SGM_MODE_SGBM_3WAY = 2, PSM_SGM_MODE_HH4 = 3 };
+int psm_sgm_set_mode(psm_ctx *ctx, int mode);
+
 /* StereoSGBM's pixel cost: the Birchfield-Tomasi cost over Sobel-prefiltered images (tests/sgm_bt_model.py; all integer, the
  * device equals it element for element).  pre_filter_cap = cap, 1 <= cap <= 63, ft = max(cap, 15) | 1; images are the 8-bit pair
  * (a float pair is quantised first), ch in {1, 3}:
@@ -386,7 +401,7 @@ int psm_sgm_speckle_time(psm_ctx *ctx, double *ms);
  * psm_sgm_compute and psm_sgm_filter_speckles work per context and return the same bits.  Volumes, maps, masks and minima of the
  * other entry points are untouched; the call may stand anywhere between them.
  * The contexts must agree on width, height, max_disp and device, on the depth of the staged pair (a float pair is quantised on the
- * device, as ever) and on every setting of psm_sgm_set_params, psm_sgm_set_prefilter and psm_sgm_set_speckle.  Refused otherwise,
+ * device, as ever) and on every setting of psm_sgm_set_params, psm_sgm_set_prefilter, psm_sgm_set_speckle and psm_sgm_set_mode.  Refused otherwise,
  * and for NULL or repeated contexts, n < 1 or n > 4096, a context without a pair, a disparity shard, a row stripe in force and
  * parameters psm_sgm_set_params would refuse: psm_last_error(ctxs[0]) names the offending index, nothing has been enqueued, and
  * every context's previous result is still readable.

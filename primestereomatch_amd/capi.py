@@ -103,6 +103,7 @@ SYMBOLS = [
     ("psm_sgm_set_prefilter", _i, [_vp, _i]),
     ("psm_sgm_download_prefiltered", _i, [_vp, _i, _vp]),
     ("psm_sgm_compute_batch", _i, [C.POINTER(_vp), _i]),
+    ("psm_sgm_set_mode", _i, [_vp, _i]),
 ]
 
 _lib = None

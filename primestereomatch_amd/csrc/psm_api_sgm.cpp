@@ -143,7 +143,17 @@ int enqueue_speckle(psm_ctx *c, int16_t *map, int new_val, int max_size, long lo
     return 0;
 }
 
-// cost, the eight directions, select + check, the speckle filter if it is on, on the context's stream
+// the directions of the context's mode in table order; the first launch stores S, so no sum of an earlier frame or mode survives
+void launch_paths(const psm_ctx *c, hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
+{
+    const int mode = c->sgm.mode;
+    for (int i = 0; i < SGM_MODE_NDIR[mode]; ++i) {
+        const int *r = SGM_DIRS[SGM_MODE_DIRS[mode][i]];
+        launch_sgm_path(s, a, r[0], r[1], i == 0, tab, n);
+    }
+}
+
+// cost, the mode's directions, select + check, the speckle filter if it is on, on the context's stream
 int enqueue(psm_ctx *c, const char *who, const void *l, const void *r, int depth, int ch)
 {
     SgmState &g = c->sgm;
@@ -167,7 +177,7 @@ int enqueue(psm_ctx *c, const char *who, const void *l, const void *r, int depth
         if (check_launch(c, "k_sgm_cost")) return 1;
     }
     if (timed) PSM_HIP(c, hipEventRecord(g.ev[1], c->stream));
-    for (int i = 0; i < 8; ++i) launch_sgm_path(c->stream, a, SGM_DIRS[i][0], SGM_DIRS[i][1], i == 0);
+    launch_paths(c, c->stream, a, nullptr, 1);
     if (check_launch(c, "k_sgm_path")) return 1;
     if (timed) PSM_HIP(c, hipEventRecord(g.ev[2], c->stream));
     launch_sgm_select(c->stream, a);
@@ -212,6 +222,15 @@ int psm_sgm_set_prefilter(psm_ctx *c, int pre_filter_cap)
     if (pre_filter_cap < 0 || pre_filter_cap > 63)
         return fail(c, "psm_sgm_set_prefilter: pre_filter_cap %d outside [0, 63] (0: the SAD cost)", pre_filter_cap);
     c->sgm.cap = pre_filter_cap;
+    return 0;
+}
+
+int psm_sgm_set_mode(psm_ctx *c, int mode)
+{
+    if (mode < 0 || mode > 3)                  // (without a context the message is psm_last_error(NULL)'s)
+        return fail(c, "psm_sgm_set_mode: mode %d not in {0: MODE_SGBM, 1: MODE_HH, 2: MODE_SGBM_3WAY, 3: MODE_HH4}", mode);
+    if (!c) return fail(nullptr, "psm_sgm_set_mode: NULL context");
+    c->sgm.mode = mode;
     return 0;
 }
 
@@ -269,6 +288,7 @@ int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
         if (g.bs != g0.bs || g.p1 != g0.p1 || g.p2 != g0.p2 || g.u != g0.u || g.m != g0.m)
             return fail(c0, "%s: context %d has other parameters (psm_sgm_set_params) than context 0", who, i);
         if (g.cap != g0.cap) return fail(c0, "%s: context %d has another pre_filter_cap (%d) than context 0 (%d)", who, i, g.cap, g0.cap);
+        if (g.mode != g0.mode) return fail(c0, "%s: context %d has another mode (%d) than context 0 (%d)", who, i, g.mode, g0.mode);
         if (g.spk_window != g0.spk_window || g.spk_range != g0.spk_range)
             return fail(c0, "%s: context %d has another speckle window / range (%d, %d) than context 0 (%d, %d)", who, i, g.spk_window,
                         g.spk_range, g0.spk_window, g0.spk_range);
@@ -344,7 +364,7 @@ int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
     else launch_sgm_cost(s, a, t.tab, n);
     if (check_launch(c0, g0.cap > 0 ? "k_sgm_fill_b, k_sgm_prefilter_b, k_sgm_bt_*_b" : "k_sgm_fill_b, k_sgm_cost_b")) return 1;
     if (timed) PSM_HIP(c0, hipEventRecord(t.ev[1], s));
-    for (int i = 0; i < 8; ++i) launch_sgm_path(s, a, SGM_DIRS[i][0], SGM_DIRS[i][1], i == 0, t.tab, n);
+    launch_paths(c0, s, a, t.tab, n);
     if (check_launch(c0, "k_sgm_path_b")) return 1;
     if (timed) PSM_HIP(c0, hipEventRecord(t.ev[2], s));
     launch_sgm_select(s, a, t.tab, n);

@@ -44,6 +44,7 @@ struct StreamSet {
 // frame) and the events of psm_sgm_times.  Nothing else in the context reads or writes any of it.
 struct SgmState {
     int bs = 5, p1 = 0, p2 = 0, u = 10, m = 1;     // p1 / p2 0: the default for the pair's channel count
+    int mode = 1;                                  // psm_sgm_set_mode: the row of SGM_MODE_DIRS; 1: MODE_HH, all eight directions
     uint16_t *C = nullptr;
     uint32_t *S = nullptr;
     uint32_t *disp2 = nullptr;

@@ -272,6 +272,10 @@ struct SgmPair {
 template <typename T>
 __device__ __forceinline__ T *sgm_global(T *const &slot) { return (T *)*(__attribute__((address_space(1))) T *const *)(const void *)&slot; }
 constexpr int SGM_DIRS[8][2] = {{0, 1}, {0, -1}, {1, 0}, {-1, 0}, {1, 1}, {1, -1}, {-1, 1}, {-1, -1}};   // (dy, dx)
+// the directions a mode sums (psm_sgm_set_mode; the values are OpenCV's enum): the first SGM_MODE_NDIR[mode] entries of its row, as
+// indices into SGM_DIRS, launched in this order - the first one stores S.  Every reduced mode begins with the two row directions.
+constexpr int SGM_MODE_NDIR[4] = {5, 8, 3, 4};
+constexpr int SGM_MODE_DIRS[4][8] = {{0, 1, 2, 4, 5}, {0, 1, 2, 3, 4, 5, 6, 7}, {0, 1, 2}, {0, 1, 2, 3}};   // SGBM, HH, SGBM_3WAY, HH4
 constexpr int SGM_BT_TX = 128;         // k_sgm_bt_rows: output pixels of a row per workgroup
 constexpr int SGM_BT_YS = 32;          // k_sgm_bt_cols: output rows per thread
 // tab == nullptr: the pair whose pointers `a` holds; else the n pairs of the device table (the pointers of `a` unused, grid z = pair)

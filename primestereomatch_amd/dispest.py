@@ -140,7 +140,7 @@ class DispEst:
 
     # ---- the second algorithm: STEREO_SGBM (src/StereoMatch.cpp:169-187) ----------------------
     def SGBM_GPU(self, block_size: int = 0, P1: int = 0, P2: int = 0, uniqueness_ratio: int = 10, disp12_max_diff: int = 1,
-                 gray=None, speckle_window_size: int = 0, speckle_range: int = 0, pre_filter_cap: int = 0):
+                 gray=None, speckle_window_size: int = 0, speckle_range: int = 0, pre_filter_cap: int = 0, mode="hh"):
         """ssgbm->compute(lFrame, rFrame, imgDisparity16S) on the device over the pair setInputImages staged, with the
         parameters of setupOpenCVSGBM (src/StereoMatch.cpp:639-660) as defaults (0: blockSize 5, P1 = 8 ch bs^2, P2 = 32 ch bs^2).
         -> H x W int16: disparity * 16, -16 where invalid.  An independent stage (psm_sgm_compute): the maps, masks and volumes
@@ -148,7 +148,10 @@ class DispEst:
         speckle_window_size > 0: the map goes through StereoSGBM's last step, filterSpeckles(map, -16, speckle_window_size,
         16 * speckle_range) (the reference: 100, 32); 0, the default: off - the setting is this call's, not the object's.
         pre_filter_cap in 1 .. 63: StereoSGBM's pixel cost, Birchfield-Tomasi over Sobel-prefiltered images (psm_sgm_set_prefilter;
-        the reference: 63); 0, the default: SAD - this call's setting too."""
+        the reference: 63); 0, the default: SAD - this call's setting too.
+        mode: ssgbm->setMode, "sgbm", "hh" (the default: all eight directions), "3way", "hh4" or OpenCV's integer
+        (psm_sgm_set_mode) - this call's setting as well."""
+        self._ck(self._lib.psm_sgm_set_mode(self._h, sgm_mode(mode)), "SGBM_GPU")
         self._ck(self._lib.psm_sgm_set_prefilter(self._h, int(pre_filter_cap)), "SGBM_GPU")
         self._ck(self._lib.psm_sgm_set_speckle(self._h, int(speckle_window_size), int(speckle_range)), "SGBM_GPU")
         self._ck(self._lib.psm_sgm_set_params(self._h, int(block_size), int(P1), int(P2), int(uniqueness_ratio),
@@ -506,8 +509,20 @@ def compute_batch(des):
     capi.check(des[0]._lib.psm_compute_batch(arr, len(des)), des[0]._h, "compute_batch")
 
 
+SGM_MODES = {"sgbm": 0, "hh": 1, "3way": 2, "hh4": 3}       # ssgbm->setMode: OpenCV's enum values
+
+
+def sgm_mode(mode):
+    """A mode name of SGM_MODES, or its integer (passed on as it is: psm_sgm_set_mode refuses what it does not know)."""
+    if isinstance(mode, str):
+        if mode not in SGM_MODES:
+            raise ValueError(f"mode {mode!r} not in {sorted(SGM_MODES)}")
+        return SGM_MODES[mode]
+    return int(mode)
+
+
 def sgbm_batch(des, block_size: int = 0, P1: int = 0, P2: int = 0, uniqueness_ratio: int = 10, disp12_max_diff: int = 1,
-               speckle_window_size: int = 0, speckle_range: int = 0, pre_filter_cap: int = 0):
+               speckle_window_size: int = 0, speckle_range: int = 0, pre_filter_cap: int = 0, mode="hh"):
     """SGBM_GPU of several DispEst objects of one geometry in shared launches (psm_sgm_compute_batch): the parameters (SGBM_GPU's,
     without gray=) are set on every object, each object's own staged pair goes through the stage, -> the list of H x W int16 maps.
     Every object afterwards behaves as after its own SGBM_GPU (sgm_costs(), sgm_prefiltered(), sgm_speckle_sizes(), ...); the
@@ -516,6 +531,7 @@ def sgbm_batch(des, block_size: int = 0, P1: int = 0, P2: int = 0, uniqueness_ra
     if not des:
         return []
     for d in des:
+        d._ck(d._lib.psm_sgm_set_mode(d._h, sgm_mode(mode)), "sgbm_batch")
         d._ck(d._lib.psm_sgm_set_prefilter(d._h, int(pre_filter_cap)), "sgbm_batch")
         d._ck(d._lib.psm_sgm_set_speckle(d._h, int(speckle_window_size), int(speckle_range)), "sgbm_batch")
         d._ck(d._lib.psm_sgm_set_params(d._h, int(block_size), int(P1), int(P2), int(uniqueness_ratio), int(disp12_max_diff)),

@@ -243,6 +243,12 @@ int DispEst::setSGBMPreFilterCap(int preFilterCap)
     return hipUtil::api().sgm_set_prefilter(ctx[0], preFilterCap);
 }
 
+int DispEst::setSGBMMode(int mode)
+{
+    if (ctx.empty()) return 1;
+    return hipUtil::api().sgm_set_mode(ctx[0], mode);
+}
+
 int DispEst::sgbmSpeckleTime(double *ms)
 {
     if (ctx.empty()) return 1;

@@ -118,6 +118,10 @@ public:
     // StereoSGBM's pixel cost for every following SGBM_GPU: Birchfield-Tomasi over Sobel-prefiltered images, preFilterCap in 1 .. 63
     // (setupOpenCVSGBM: 63).  0, the setting of a new object: the SAD cost.
     int setSGBMPreFilterCap(int preFilterCap);
+    // ssgbm->setMode for every following SGBM_GPU (the reference's `m` key, src/main.cpp:114-168): PSM_SGM_MODE_SGBM (0),
+    // PSM_SGM_MODE_HH (1, the setting of a new object: all eight directions), PSM_SGM_MODE_SGBM_3WAY (2), PSM_SGM_MODE_HH4 (3) -
+    // OpenCV's enum values.  SGBMBatch wants one mode on all its objects.
+    int setSGBMMode(int mode);
 
     // Frame loop (src/main.cpp:64-73) with the PCIe legs next to the kernels (single-device hosts): one call per frame -
     // CostConst (adopts the pair staged by the previous call), stages `next` pair (may be NULL at the end of the stream: its

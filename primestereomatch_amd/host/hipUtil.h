@@ -57,6 +57,7 @@ struct HipApi {
     int (*sgm_speckle_time)(psm_ctx *, double *) = nullptr;
     int (*sgm_set_prefilter)(psm_ctx *, int) = nullptr;
     int (*sgm_compute_batch)(psm_ctx *const *, int) = nullptr;
+    int (*sgm_set_mode)(psm_ctx *, int) = nullptr;
     int (*joint_wmf_batch)(psm_ctx *const *, int, int, float, int, int) = nullptr;
 };
 

@@ -11,6 +11,8 @@ those bytes over the total as a fraction of the part's measured copy ceiling (6.
 the stage holds.  --model: also time the numpy model (tests/sgm_model.py) on the same pair, for scale; --model-only does just
 that and needs no GPU (the large pairs take minutes and gigabytes).
 
+--mode: StereoSGBM's reduced modes beside hh - modes_bench below.
+
 The speckle filter (psm_sgm_set_speckle; k_spk_runs, k_spk_merge, k_spk_count, k_spk_apply): every configuration is timed twice in
 the same process, with the filter off (the record above, unchanged) and on at the reference's (100, 32) - "speckle_ms", the median
 of psm_sgm_speckle_time, and the three group times of those runs as "*_ms_speckle_on".  --speckle-maps: also two 1920 x 1080
@@ -169,6 +171,63 @@ def batch_bench(a):
                 de.close()
 
 
+def modes_bench(a):
+    """--mode M[,M...] [--batch N]: the reduced modes (psm_sgm_set_mode) on one context per configuration, in one process.  Per
+    repetition (--reps) the sequence hh, then every mode in turn; per entry --warmup computes, then the medians of psm_sgm_times
+    over --runs computes.  One record per (configuration, rep, mode) with the three groups, the paths group over hh's of the same
+    repetition and, at the Cones size, bp_percent_int of Cones / Teddy.  With --batch N the same for a batch of N pairs, per
+    pair."""
+    import primestereomatch_amd as P
+    from primestereomatch_amd import capi, dispest, harness
+    if capi.device_count() < 1:
+        raise SystemExit("sgm_bench: no HIP device visible")
+    modes = a.mode.split(",")
+    n = int(a.batch) if a.batch else 1
+    for name in a.configs.split(","):
+        W, H, D = CONFIGS[name]
+        des = [P.DispEst(l, r, D) for l, r in batch_pairs(name, max(n, 2 if name == "cones" else 1))]
+        try:
+            sub = des[:n]
+            sub[0].set_option(capi.PSM_OPT_PROFILE, 1)
+            bp = {}
+            if name == "cones":                                     # des[0]: Cones, des[1]: Teddy
+                for k, de in zip(("cones", "teddy"), des):
+                    z = np.load(os.path.join(ROOT, "tests", "golden", f"{k}_pair.npz"))
+                    for mode in ["hh"] + modes:
+                        d16 = de.SGBM_GPU(mode=mode)
+                        bp[k, mode] = round(float(harness.error_vs_ground_truth(np.maximum(d16, 0) >> 4, z["gt_l"], z["occl"], D, 4)[0]), 2)
+
+            def timed(mode):
+                dispest.sgbm_batch(sub, mode=mode)                                     # (sets every context; the first warm-up)
+                t = []
+                for i in range(a.warmup + a.runs):
+                    if n == 1:
+                        sub[0]._ck(sub[0]._lib.psm_sgm_compute(sub[0]._h), "psm_sgm_compute")
+                    else:
+                        dispest.sgm_compute_batch(sub)
+                    if i >= a.warmup:
+                        t.append(np.array(sub[0].sgm_times()) / n)
+                return np.median(np.array(t), axis=0)
+
+            for rep_i in range(a.reps):
+                hh = timed("hh")
+                for mode, t in [("hh", hh)] + [(mode, timed(mode)) for mode in modes]:
+                    rec = {"bench": "sgm_modes", "config": name, "W": W, "H": H, "D": D, "batch": n, "rep": rep_i, "runs": a.runs,
+                           "warmup": a.warmup, "mode": mode, "cost_ms": round(float(t[0]), 4),
+                           "paths_ms": round(float(t[1]), 4), "select_ms": round(float(t[2]), 4),
+                           "paths_over_hh": round(float(t[1] / hh[1]), 3), "total_over_hh": round(float(t.sum() / hh.sum()), 3)}
+                    if bp:
+                        rec["bp_percent_int"] = {k: bp[k, mode] for k in ("cones", "teddy")}
+                    line = json.dumps(rec)
+                    print(line, flush=True)
+                    if a.out:
+                        with open(a.out, "a") as f:
+                            f.write(line + "\n")
+        finally:
+            for de in des:
+                de.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="cones,720p,1080p")
@@ -179,9 +238,12 @@ def main():
     ap.add_argument("--speckle-maps", action="store_true")
     ap.add_argument("--batch", default=None, help="N[,N...]: time psm_sgm_compute_batch at these batch sizes beside the singles")
     ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--mode", default=None, help="M[,M...] of sgbm, 3way, hh4: time these modes beside hh (modes_bench)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert a.runs >= 1
+    if a.mode:
+        return modes_bench(a)
     if a.batch:
         return batch_bench(a)
     for name in a.configs.split(","):
