@@ -281,7 +281,8 @@ int psm_download_images(psm_ctx *ctx, uint8_t *l, uint8_t *r, size_t stride_byte
 
 /* ---- semi-global matching: the reference's second algorithm, the STEREO_SGBM branch of StereoMatch::compute
  * (ssgbm->compute(lFrame, rFrame, imgDisparity16S), src/StereoMatch.cpp:169-187) with the configuration of setupOpenCVSGBM
- * (:639-660): minDisparity 0, numDisparities = the context's max_disp (any value in [2, 256]), blockSize 5, P1 = 8 ch bs^2,
+ * (:639-660): minDisparity 0, numDisparities = the context's max_disp (any value in [2, 256]; psm_sgm_set_range: another minimum,
+ * up to 1024 disparities), blockSize 5, P1 = 8 ch bs^2,
  * P2 = 32 ch bs^2, disp12MaxDiff 1, uniquenessRatio 10, eight paths (MODE_HH).  All integer; the definition (DESIGN.md section 10,
  * tests/sgm_model.py) is Hirschmueller's recurrence under OpenCV's parameter names, and the device equals it element for element:
  *   pixel cost  c(x,y,d) = sum_ch |L[y][x][ch] - R[y][max(x-d, 0)][ch]|, or the prefiltered Birchfield-Tomasi cost - below
@@ -305,7 +306,8 @@ int psm_download_images(psm_ctx *ctx, uint8_t *l, uint8_t *r, size_t stride_byte
 int psm_sgm_set_params(psm_ctx *ctx, int block_size, int p1, int p2, int uniqueness_ratio, int disp12_max_diff);
 /* Runs the stage on the context's stream over the pair psm_upload_pair* staged (either depth); synchronous on return unless
  * PSM_OPT_ASYNC.  An independent stage: it reads the staged images only and writes its own buffers - 6 * W * H * Dp bytes of
- * volumes (Dp = max_disp rounded up to 4) and 8 * W * H of planes, plus 12 * W * H of prefiltered planes once a compute ran with
+ * volumes (Dp = the number of disparities D rounded up to 4; above 256 to 8, above 512 to 16 - D is max_disp or psm_sgm_set_range's)
+ * and 8 * W * H of planes, plus 12 * W * H of prefiltered planes once a compute ran with
  * pre_filter_cap > 0, allocated on first use, reused from frame to frame, given back by psm_release_scratch and psm_destroy.  Volumes, maps, masks and minima of the other entry points are untouched: it may be
  * called anywhere between them.  Refused on disparity shards, under a row stripe, and when nothing has been uploaded. */
 int psm_sgm_compute(psm_ctx *ctx);
@@ -314,7 +316,8 @@ int psm_sgm_compute(psm_ctx *ctx);
 int psm_sgm_compute_gray(psm_ctx *ctx, const uint8_t *l, const uint8_t *r, size_t stride_bytes);
 /* The left map of the last compute (imgDisparity16S): H rows of W int16, pitch stride_bytes (0: packed).  Synchronises. */
 int psm_sgm_download_disparity(psm_ctx *ctx, int16_t *disp, size_t stride_bytes);
-/* Test hook: the volumes of the last compute as dense host arrays [H][W][max_disp] - which 0: C as uint16, 1: S as uint32. */
+/* Test hook: the volumes of the last compute as dense host arrays [H][W][D], D the number of disparities that compute ran with
+ * (max_disp, or psm_sgm_set_range's) - which 0: C as uint16, 1: S as uint32. */
 int psm_sgm_download_costs(psm_ctx *ctx, int which, void *host);
 /* With PSM_OPT_PROFILE set during the last compute: device time in ms of its block-cost launches (everything up to C, the
  * prefilter included), its eight path launches and its select + check launches (a getter of its own: the PSM_K_* and PSM_STAGE_* tables stay as they are). */
@@ -334,6 +337,30 @@ int psm_sgm_times(psm_ctx *ctx, double ms[3]);
  * psm_sgm_times' second number covers the mode's path launches.  psm_sgm_compute_batch refuses contexts whose modes differ. */
 enum { PSM_SGM_MODE_SGBM = 0, PSM_SGM_MODE_HH = 1, PSM_SGM_MODE_SGBM_3WAY = 2, PSM_SGM_MODE_HH4 = 3 };
 int psm_sgm_set_mode(psm_ctx *ctx, int mode);
+
+/* The first two arguments of StereoSGBM::create, minDisparity and numDisparities (the reference passes mindisparity, ndisparities):
+ * the stage's D = num_disparities indices k in [0, D) stand for the disparities min_disparity + k.  min_disparity in [-1024, 1024];
+ * num_disparities 0: the context's max_disp (a new context's setting), else any value in [2, 1024] - independent of max_disp and
+ * of the width, because every case is defined by the clamp below.  With (0, 0), or without this function, psm_sgm_compute,
+ * _compute_gray and _compute_batch are bit for bit what they are above.  The definition is tests/sgm_range_model.py:
+ *   pixel cost   the right column is xr = clamp(x - (min_disparity + k), 0, W - 1), on BOTH sides (a negative disparity reaches past
+ *                the right edge), in the SAD cost and in step "cost" of the Birchfield-Tomasi cost; planes, bounds and border
+ *                columns are unchanged
+ *   block cost, paths, sum, select   over k as above; d16 = 16 (min_disparity + best_k) + sub, sub only for 0 < best_k < D - 1
+ *   consistency  a unique pixel lands at column x - (min_disparity + best_k) if that is inside [0, W); disp2 holds the disparity
+ *                min_disparity + best_k of the smallest (minS, best_k) landing there, "nothing landed" is a state of its own
+ *                (-1 can be a disparity); the probes da = d16 >> 4, db = (d16 + 15) >> 4 are floors, also of a negative d16
+ *   output       d16, or invalid = (min_disparity - 1) * 16 where not unique or rejected; the speckle filter, when on, runs with
+ *                newVal = invalid.  |sub| <= 8: a valid value never equals invalid.  16 (min_disparity + D - 1) + 8 <= 32767 and
+ *                invalid >= -32768 hold inside the ranges above; S <= 8 * 65535 as before.
+ * Not OpenCV's convention: OpenCV leaves the columns outside [max(maxD, 0), W + min(minD, 0)) invalid, the stage keeps all columns,
+ * as it does without a range.  Agreement with a live cv::StereoSGBM stays unpinned.
+ * The setting holds until changed.  The volumes follow it: a compute whose D needs another Dp than the volumes have frees and
+ * allocates C and S again (6 * W * H * Dp bytes: 1920 x 1080 x 512 is 6.4 GB, 3840 x 2160 x 512 25.5 GB) and the previous result
+ * is gone from that moment; psm_release_scratch and psm_destroy work as ever.  psm_sgm_compute_batch refuses contexts whose ranges
+ * differ.  Values outside the ranges are refused; with a NULL context the message is psm_last_error(NULL)'s.  The guided-filter path
+ * (psm_cost_construct ... psm_post_process) keeps max_disp <= 256: its maps are 8-bit. */
+int psm_sgm_set_range(psm_ctx *ctx, int min_disparity, int num_disparities);
 
 /* StereoSGBM's pixel cost: the Birchfield-Tomasi cost over Sobel-prefiltered images (tests/sgm_bt_model.py; all integer, the
  * device equals it element for element).  pre_filter_cap = cap, 1 <= cap <= 63, ft = max(cap, 15) | 1; images are the 8-bit pair
@@ -401,7 +428,8 @@ int psm_sgm_speckle_time(psm_ctx *ctx, double *ms);
  * psm_sgm_compute and psm_sgm_filter_speckles work per context and return the same bits.  Volumes, maps, masks and minima of the
  * other entry points are untouched; the call may stand anywhere between them.
  * The contexts must agree on width, height, max_disp and device, on the depth of the staged pair (a float pair is quantised on the
- * device, as ever) and on every setting of psm_sgm_set_params, psm_sgm_set_prefilter, psm_sgm_set_speckle and psm_sgm_set_mode.  Refused otherwise,
+ * device, as ever) and on every setting of psm_sgm_set_params, psm_sgm_set_prefilter, psm_sgm_set_speckle, psm_sgm_set_mode
+ * and psm_sgm_set_range.  Refused otherwise,
  * and for NULL or repeated contexts, n < 1 or n > 4096, a context without a pair, a disparity shard, a row stripe in force and
  * parameters psm_sgm_set_params would refuse: psm_last_error(ctxs[0]) names the offending index, nothing has been enqueued, and
  * every context's previous result is still readable.

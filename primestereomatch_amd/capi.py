@@ -104,6 +104,7 @@ SYMBOLS = [
     ("psm_sgm_download_prefiltered", _i, [_vp, _i, _vp]),
     ("psm_sgm_compute_batch", _i, [C.POINTER(_vp), _i]),
     ("psm_sgm_set_mode", _i, [_vp, _i]),
+    ("psm_sgm_set_range", _i, [_vp, _i, _i]),
 ]
 
 _lib = None

@@ -38,13 +38,17 @@ void sgm_free(psm_ctx *c)
     for (hipEvent_t &e : g.ev_tab) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     g.have = g.timed = g.spk_have = false;
     g.spk_t0 = -1;
+    g.vol_dp = g.res_d = 0;
 }
 
 }  // namespace psm
 
 namespace {
 
-inline int sgm_dp(const psm_ctx *c) { return (c->D + 3) & ~3; }
+// the disparities of the stage: psm_sgm_set_range's, or the context's max_disp; index k stands for the disparity dmin + k
+inline int sgm_d(const psm_ctx *c) { return c->sgm.nd ? c->sgm.nd : c->D; }
+inline int sgm_dp(const psm_ctx *c) { return psm::sgm_dp(sgm_d(c)); }
+inline int sgm_invalid(const psm_ctx *c) { return (c->sgm.dmin - 1) * 16; }
 
 // the conditions on the parameters for a pair of `ch` channels; *p1 / *p2: 0 resolved to the default
 int check_params(psm_ctx *c, const char *who, int ch, int bs, int *p1, int *p2, int u)
@@ -65,7 +69,7 @@ int check_ctx(psm_ctx *e, const psm_ctx *c, const char *who)
 {
     if (c->Dloc != c->D || strided(c)) return fail(e, "%s: a disparity shard holds part of the range (the paths need every disparity of a pixel)", who);
     if (c->march.yend > c->march.ybeg) return fail(e, "%s: a row stripe is in force (psm_set_rows): the paths cross the whole image", who);
-    if (c->D < 2) return fail(e, "%s: max_disp %d < 2", who, c->D);
+    if (sgm_d(c) < 2) return fail(e, "%s: max_disp %d < 2", who, sgm_d(c));
     return 0;
 }
 
@@ -73,6 +77,15 @@ int ensure_buffers(psm_ctx *c)
 {
     SgmState &g = c->sgm;
     const size_t HW = (size_t)c->W * c->H, V = HW * sgm_dp(c);
+    if ((g.C || g.S) && g.vol_dp != sgm_dp(c)) {
+        // another range's volumes: nothing may still read them (a batch runs on its first context's stream), and the result in
+        // them is gone; a table that names them is compared against the new pointers by psm_sgm_compute_batch
+        PSM_HIP(c, hipDeviceSynchronize());
+        (void)hipFree(g.C); g.C = nullptr;
+        (void)hipFree(g.S); g.S = nullptr;
+        g.have = g.timed = false;
+    }
+    g.vol_dp = sgm_dp(c);
     if (!g.C) PSM_HIP(c, hipMalloc((void **)&g.C, V * sizeof(uint16_t)));
     if (!g.S) PSM_HIP(c, hipMalloc((void **)&g.S, V * sizeof(uint32_t)));
     if (!g.disp2) PSM_HIP(c, hipMalloc((void **)&g.disp2, HW * sizeof(uint32_t)));
@@ -94,7 +107,8 @@ SgmArgs sgm_args(const psm_ctx *c, const void *l, const void *r, int depth, int 
     SgmArgs a;
     a.img[0] = l; a.img[1] = r; a.depth = depth; a.ch = ch;
     a.C = g.C; a.S = g.S; a.disp2 = g.disp2; a.pre = g.pre; a.out = g.out;
-    a.W = c->W; a.H = c->H; a.D = c->D; a.Dp = sgm_dp(c);
+    a.W = c->W; a.H = c->H; a.D = sgm_d(c); a.Dp = sgm_dp(c);
+    a.dmin = g.dmin; a.invalid = sgm_invalid(c);
     a.bs = g.bs; a.P1 = p1; a.P2 = p2; a.u = g.u; a.m = g.m;
     a.pf[0] = a.pf[1] = nullptr; a.Hs = nullptr; a.ft = 0;
     if (g.cap > 0) {
@@ -184,8 +198,9 @@ int enqueue(psm_ctx *c, const char *who, const void *l, const void *r, int depth
     if (check_launch(c, "k_sgm_select")) return 1;
     if (timed) PSM_HIP(c, hipEventRecord(g.ev[3], c->stream));
     // filterSpeckles(disp, (minDisparity - 1) * 16, speckleWindowSize, 16 * speckleRange), as StereoSGBM ends
-    if (g.spk_window > 0 && enqueue_speckle(c, g.out, -16, g.spk_window, 16ll * g.spk_range, timed ? 3 : -1)) return 1;
+    if (g.spk_window > 0 && enqueue_speckle(c, g.out, a.invalid, g.spk_window, 16ll * g.spk_range, timed ? 3 : -1)) return 1;
     g.have = true;
+    g.res_d = a.D;
     g.timed = timed;
     if (!c->opt_async) PSM_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
@@ -231,6 +246,18 @@ int psm_sgm_set_mode(psm_ctx *c, int mode)
         return fail(c, "psm_sgm_set_mode: mode %d not in {0: MODE_SGBM, 1: MODE_HH, 2: MODE_SGBM_3WAY, 3: MODE_HH4}", mode);
     if (!c) return fail(nullptr, "psm_sgm_set_mode: NULL context");
     c->sgm.mode = mode;
+    return 0;
+}
+
+int psm_sgm_set_range(psm_ctx *c, int min_disparity, int num_disparities)
+{
+    if (min_disparity < -1024 || min_disparity > 1024)      // (without a context the message is psm_last_error(NULL)'s)
+        return fail(c, "psm_sgm_set_range: min_disparity %d outside [-1024, 1024]", min_disparity);
+    if (num_disparities != 0 && (num_disparities < 2 || num_disparities > SGM_DMAX))
+        return fail(c, "psm_sgm_set_range: num_disparities %d neither 0 (the context's max_disp) nor in [2, %d]", num_disparities, SGM_DMAX);
+    if (!c) return fail(nullptr, "psm_sgm_set_range: NULL context");
+    c->sgm.dmin = min_disparity;
+    c->sgm.nd = num_disparities;
     return 0;
 }
 
@@ -289,6 +316,9 @@ int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
             return fail(c0, "%s: context %d has other parameters (psm_sgm_set_params) than context 0", who, i);
         if (g.cap != g0.cap) return fail(c0, "%s: context %d has another pre_filter_cap (%d) than context 0 (%d)", who, i, g.cap, g0.cap);
         if (g.mode != g0.mode) return fail(c0, "%s: context %d has another mode (%d) than context 0 (%d)", who, i, g.mode, g0.mode);
+        if (g.dmin != g0.dmin || sgm_d(c) != sgm_d(c0))
+            return fail(c0, "%s: context %d has another disparity range (min %d, %d disparities) than context 0 (min %d, %d)", who, i, g.dmin,
+                        sgm_d(c), g0.dmin, sgm_d(c0));
         if (g.spk_window != g0.spk_window || g.spk_range != g0.spk_range)
             return fail(c0, "%s: context %d has another speckle window / range (%d, %d) than context 0 (%d, %d)", who, i, g.spk_window,
                         g.spk_range, g0.spk_window, g0.spk_range);
@@ -371,7 +401,7 @@ int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
     if (check_launch(c0, "k_sgm_select_b")) return 1;
     if (timed) PSM_HIP(c0, hipEventRecord(t.ev[3], s));
     if (spk) {
-        launch_speckle(s, speckle_args(c0, -16, g0.spk_window, 16ll * g0.spk_range), t.tab, n);
+        launch_speckle(s, speckle_args(c0, a.invalid, g0.spk_window, 16ll * g0.spk_range), t.tab, n);
         if (check_launch(c0, "k_spk_*_b")) return 1;
         if (timed) PSM_HIP(c0, hipEventRecord(t.ev[4], s));
     }
@@ -382,6 +412,7 @@ int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
         psm_ctx *c = ctxs[i];
         SgmState &g = c->sgm;
         g.have = true;
+        g.res_d = a.D;
         g.timed = timed && i == 0;
         g.pf_ch = g0.cap > 0 ? 3 : 0;
         if (spk) {
@@ -422,7 +453,7 @@ int psm_sgm_download_costs(psm_ctx *c, int which, void *host)
     if (which != 0 && which != 1) return fail(c, "psm_sgm_download_costs: which %d (0: C as u16, 1: S as u32)", which);
     if (!c->sgm.have) return fail(c, "psm_sgm_download_costs: no result (psm_sgm_compute)");
     if (bind(c)) return 1;
-    const size_t HW = (size_t)c->W * c->H, Dp = sgm_dp(c), D = c->D, el = which ? sizeof(uint32_t) : sizeof(uint16_t);
+    const size_t HW = (size_t)c->W * c->H, Dp = psm::sgm_dp(c->sgm.res_d), D = c->sgm.res_d, el = which ? sizeof(uint32_t) : sizeof(uint16_t);
     std::vector<uint8_t> dev(HW * Dp * el);
     PSM_HIP(c, hipMemcpyAsync(dev.data(), which ? (const void *)c->sgm.S : (const void *)c->sgm.C, dev.size(), hipMemcpyDeviceToHost, c->stream));
     PSM_HIP(c, hipStreamSynchronize(c->stream));

@@ -45,6 +45,9 @@ struct StreamSet {
 struct SgmState {
     int bs = 5, p1 = 0, p2 = 0, u = 10, m = 1;     // p1 / p2 0: the default for the pair's channel count
     int mode = 1;                                  // psm_sgm_set_mode: the row of SGM_MODE_DIRS; 1: MODE_HH, all eight directions
+    int dmin = 0, nd = 0;                          // psm_sgm_set_range: minDisparity, numDisparities; nd 0: the context's max_disp
+    int vol_dp = 0;                                // the Dp C and S are allocated for (another range's: freed and allocated again)
+    int res_d = 0;                                 // the D of the result in them (psm_sgm_download_costs)
     uint16_t *C = nullptr;
     uint32_t *S = nullptr;
     uint32_t *disp2 = nullptr;

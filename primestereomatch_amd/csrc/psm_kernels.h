@@ -244,9 +244,10 @@ struct SgmArgs {
     int depth, ch;
     uint16_t *C;                       // block costs [H][W][Dp]
     uint32_t *S;                       // summed path costs [H][W][Dp]
-    uint32_t *disp2;                   // [H][W] packed minima (minS << 8 | best) landing on the right image's pixel; all ones: none
-    int16_t *pre, *out;                // [H][W] d16 (or -16: not unique) before the consistency test / the final map
-    int W, H, D, Dp;                   // Dp: elements per pixel, D rounded up to a multiple of 4
+    uint32_t *disp2;                   // [H][W] packed minima (minS << KB | best index) landing on the right image's pixel, KB = sgm_kb(Dp); all ones: none
+    int16_t *pre, *out;                // [H][W] d16 (or `invalid`: not unique) before the consistency test / the final map
+    int W, H, D, Dp;                   // Dp: elements per pixel, sgm_dp(D)
+    int dmin, invalid;                 // psm_sgm_set_range: index k in [0, D) is the disparity dmin + k; invalid = (dmin - 1) * 16
     int bs, P1, P2, u, m;
     // the prefiltered Birchfield-Tomasi cost (launch_sgm_cost_bt only; psm_sgm_set_prefilter)
     uint8_t *pf[2];                    // prefiltered planes of both images, [H][W][2 ch] bytes: P_0 .. P_{ch-1}, Q_0 .. Q_{ch-1}
@@ -276,6 +277,12 @@ constexpr int SGM_DIRS[8][2] = {{0, 1}, {0, -1}, {1, 0}, {-1, 0}, {1, 1}, {1, -1
 // indices into SGM_DIRS, launched in this order - the first one stores S.  Every reduced mode begins with the two row directions.
 constexpr int SGM_MODE_NDIR[4] = {5, 8, 3, 4};
 constexpr int SGM_MODE_DIRS[4][8] = {{0, 1, 2, 4, 5}, {0, 1, 2, 3, 4, 5, 6, 7}, {0, 1, 2}, {0, 1, 2, 3}};   // SGBM, HH, SGBM_3WAY, HH4
+// The widest range (psm_sgm_set_range).  Up to 256 disparities a pixel's Dp is D rounded up to 4 elements, as ever; above, to the
+// 8 or 16 disparities a lane of k_sgm_path holds, so that a lane's vector is whole and 16-byte aligned in both volumes.
+constexpr int SGM_DMAX = 1024;
+inline int sgm_dp(int D) { return D <= 256 ? (D + 3) & ~3 : (D <= 512 ? (D + 7) & ~7 : (D + 15) & ~15); }
+// bits of the disparity index below S in the packed minima of k_sgm_select: 8 as ever up to Dp 256, 10 above (S < 2^19: 29 bits)
+__host__ __device__ inline int sgm_kb(int Dp) { return Dp > 256 ? 10 : 8; }
 constexpr int SGM_BT_TX = 128;         // k_sgm_bt_rows: output pixels of a row per workgroup
 constexpr int SGM_BT_YS = 32;          // k_sgm_bt_cols: output rows per thread
 // tab == nullptr: the pair whose pointers `a` holds; else the n pairs of the device table (the pointers of `a` unused, grid z = pair)

@@ -6,6 +6,9 @@
 //                 S += L_r (the first direction stores)                                                                   u32 [y][x][d]
 //   k_sgm_select  argmin_d S (lowest d), uniqueness, sub-pixel d16, disp2[y][x-best] = min (minS << 8 | best)
 //   k_sgm_check   the disp12MaxDiff test of every pixel against disp2 of its row -> int16 map, -16 where invalid
+// psm_sgm_set_range (tests/sgm_range_model.py): index k in [0, D), D <= 1024, stands for the disparity dmin + k - the right column
+// is clamp(x - dmin - k, 0, W - 1), d16, the landing column and the probes carry dmin, invalid is (dmin - 1) * 16.  Above 256
+// disparities the cost kernels walk their tile once per 256 of them, a lane of k_sgm_path / k_sgm_select holds 8 or 16.
 // d is innermost in both volumes (Dp = D rounded up to 4 elements per pixel): the disparities of a pixel are one contiguous read
 // whatever the walking direction.  The speckle filter StereoSGBM ends with is psm_speckle.hip (psm_sgm_set_speckle).  StereoSGBM's
 // own pixel cost, Birchfield-Tomasi over Sobel-prefiltered images (psm_sgm_set_prefilter, tests/sgm_bt_model.py), writes the same
@@ -70,14 +73,17 @@ __device__ __forceinline__ SgmArgs sgm_pair_args(SgmArgs a, const SgmPair *tab, 
 // one dword per pixel (v_sad_u8 then takes the 1 or 3 channels of a tap in one instruction); a thread walks x with its d fixed:
 // the left tap is a broadcast, the right taps of neighbouring lanes are neighbouring dwords, the stores of a wave are 128
 // contiguous bytes.  Column sums of the last BS columns stay in registers.
-template <int BS>
+// WIDE (D > 256): 256 threads, a thread takes the disparities d, d + 256, ... in turn; the staged right span is NL + D - 1 columns
+// either way (static LDS: 29.7 KB at BS 7 when WIDE), and holds the clamped columns: a tap's index needs no clamp of its own.
+template <int BS, bool WIDE>
 __device__ __forceinline__ void sgm_cost(const SgmArgs &a)
 {
-    constexpr int HALF = BS / 2, NL = SGM_TX + BS - 1, NR = NL + 255;
+    constexpr int HALF = BS / 2, NL = SGM_TX + BS - 1, NR = NL + (WIDE ? SGM_DMAX : 256) - 1;
     __shared__ unsigned sl[BS][NL], sr[BS][NR];
-    const int y = blockIdx.y, x0 = blockIdx.x * SGM_TX, d = threadIdx.x;
+    const int y = blockIdx.y, x0 = blockIdx.x * SGM_TX;
+    int d = threadIdx.x;
     const int cx_min = sgm_clamp(x0 - HALF, a.W);
-    const int rbase = cx_min - (a.D - 1);                 // image column of sr[.][0]
+    const int rbase = cx_min - a.dmin - (a.D - 1);        // image column of sr[.][0] (before the clamp)
     const int nr = NL + a.D - 1;
     for (int i = threadIdx.x; i < BS * NL; i += blockDim.x) {
         const int j = i / NL, s = i - j * NL;
@@ -89,31 +95,34 @@ __device__ __forceinline__ void sgm_cost(const SgmArgs &a)
     }
     __syncthreads();
     if (d >= a.Dp) return;
-    const bool real = d < a.D;
-    unsigned v[BS];
+    do {
+        const bool real = d < a.D;
+        const int kd = a.D - 1 - (real ? d : 0) - cx_min;     // column cx, index d: sr[.][cx - cx_min + D - 1 - d], inside [0, nr)
+        unsigned v[BS];
 #pragma unroll
-    for (int i = 0; i < BS; ++i) v[i] = 0;
-    for (int s = 0; s < NL; ++s) {
-        const int cx = sgm_clamp(x0 - HALF + s, a.W);
-        const int k = max(cx - (real ? d : 0), 0) - rbase;
-        unsigned col = 0;
+        for (int i = 0; i < BS; ++i) v[i] = 0;
+        for (int s = 0; s < NL; ++s) {
+            const int k = sgm_clamp(x0 - HALF + s, a.W) + kd;
+            unsigned col = 0;
 #pragma unroll
-        for (int j = 0; j < BS; ++j) col = __builtin_amdgcn_sad_u8(sl[j][s], sr[j][k], col);
+            for (int j = 0; j < BS; ++j) col = __builtin_amdgcn_sad_u8(sl[j][s], sr[j][k], col);
 #pragma unroll
-        for (int i = 0; i + 1 < BS; ++i) v[i] = v[i + 1];
-        v[BS - 1] = col;
-        const int x = x0 + s - (BS - 1);
-        if (s >= BS - 1 && x < a.W) {
-            unsigned sum = 0;
+            for (int i = 0; i + 1 < BS; ++i) v[i] = v[i + 1];
+            v[BS - 1] = col;
+            const int x = x0 + s - (BS - 1);
+            if (s >= BS - 1 && x < a.W) {
+                unsigned sum = 0;
 #pragma unroll
-            for (int i = 0; i < BS; ++i) sum += v[i];
-            a.C[((size_t)y * a.W + x) * a.Dp + d] = (uint16_t)(real ? sum : 0u);
+                for (int i = 0; i < BS; ++i) sum += v[i];
+                a.C[((size_t)y * a.W + x) * a.Dp + d] = (uint16_t)(real ? sum : 0u);
+            }
         }
-    }
+    } while (WIDE && (d += 256) < a.Dp);
 }
 
-template <int BS> __global__ __launch_bounds__(256) void k_sgm_cost(SgmArgs a) { sgm_cost<BS>(a); }
-template <int BS> __global__ __launch_bounds__(256) void k_sgm_cost_b(SgmArgs a, const SgmPair *tab) { sgm_cost<BS>(sgm_pair_args(a, tab, blockIdx.z)); }
+template <int BS, bool WIDE> __global__ __launch_bounds__(256) void k_sgm_cost(SgmArgs a) { sgm_cost<BS, WIDE>(a); }
+template <int BS, bool WIDE>
+__global__ __launch_bounds__(256) void k_sgm_cost_b(SgmArgs a, const SgmPair *tab) { sgm_cost<BS, WIDE>(sgm_pair_args(a, tab, blockIdx.z)); }
 
 // ---- the prefiltered Birchfield-Tomasi cost (psm_sgm_set_prefilter, tests/sgm_bt_model.py): the same C by three kernels -------
 //   k_sgm_prefilter  both images -> their 2 ch planes per pixel (x-Sobel clipped to [0, 2 ft], the intensity; ft in the border columns)
@@ -183,59 +192,64 @@ __device__ __forceinline__ void sgm_bt_stage(const uint8_t *row, int W, int cx, 
 // planes, the values and both bounds of the left tile and of the part of the right row the tile's disparities reach; the left
 // operands are broadcasts, the right ones of neighbouring lanes neighbouring dwords.  NP pairs of planes: ch = NP (1 or 3); plane
 // i has shift 0 below ch (P), 2 from ch on (Q).  out: Hs, or C itself when BS is 1.
-template <int BS, int NP>
+// WIDE: as k_sgm_cost (static LDS: 46.5 KB at BS 7, NP 3).
+template <int BS, int NP, bool WIDE>
 __device__ __forceinline__ void sgm_bt_rows(const SgmArgs &a, uint16_t *out)
 {
-    constexpr int HALF = BS / 2, NL = SGM_BT_TX + BS - 1, NR = NL + 255, NQ = 3 * NP;
+    constexpr int HALF = BS / 2, NL = SGM_BT_TX + BS - 1, NR = NL + (WIDE ? SGM_DMAX : 256) - 1, NQ = 3 * NP;
     __shared__ unsigned sl[NQ][NL], sr[NQ][NR];
-    const int y = blockIdx.y, x0 = blockIdx.x * SGM_BT_TX, d = threadIdx.x;
+    const int y = blockIdx.y, x0 = blockIdx.x * SGM_BT_TX;
+    int d = threadIdx.x;
     const int cx_min = sgm_clamp(x0 - HALF, a.W);
-    const int rbase = cx_min - (a.D - 1);                 // image column of sr[.][0]
+    const int rbase = cx_min - a.dmin - (a.D - 1);        // image column of sr[.][0] (before the clamp)
     const int nr = NL + a.D - 1;
     const uint8_t *rowl = a.pf[0] + (size_t)y * a.W * (2 * NP), *rowr = a.pf[1] + (size_t)y * a.W * (2 * NP);
     for (int i = threadIdx.x; i < NL; i += blockDim.x) sgm_bt_stage<NP>(rowl, a.W, sgm_clamp(x0 - HALF + i, a.W), &sl[0][i], NL);
     for (int i = threadIdx.x; i < nr; i += blockDim.x) sgm_bt_stage<NP>(rowr, a.W, sgm_clamp(rbase + i, a.W), &sr[0][i], NR);
     __syncthreads();
     if (d >= a.Dp) return;
-    const bool real = d < a.D;
     const int ns = min(NL, a.W - x0 + BS - 1);            // the steps up to the row's last pixel
     const sgm_s2 zero = {0, 0};
-    unsigned v[BS];
+    do {
+        const bool real = d < a.D;
+        const int kd = a.D - 1 - (real ? d : 0) - cx_min;     // column cx, index d: sr[.][cx - cx_min + D - 1 - d], inside [0, nr)
+        unsigned v[BS];
 #pragma unroll
-    for (int i = 0; i < BS; ++i) v[i] = 0;
-    for (int s = 0; s < ns; ++s) {
-        const int cx = sgm_clamp(x0 - HALF + s, a.W);
-        const int k = max(cx - (real ? d : 0), 0) - rbase;
-        unsigned col = 0;
+        for (int i = 0; i < BS; ++i) v[i] = 0;
+        for (int s = 0; s < ns; ++s) {
+            const int k = sgm_clamp(x0 - HALF + s, a.W) + kd;
+            unsigned col = 0;
 #pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            const sgm_s2 u = sgm_as_s2(sl[3 * p][s]), lu = sgm_as_s2(sl[3 * p + 1][s]), hu = sgm_as_s2(sl[3 * p + 2][s]);
-            const sgm_s2 w = sgm_as_s2(sr[3 * p][k]), lw = sgm_as_s2(sr[3 * p + 1][k]), hw = sgm_as_s2(sr[3 * p + 2][k]);
-            const sgm_s2 c0 = __builtin_elementwise_max(__builtin_elementwise_max(u - hw, lw - u), zero);
-            const sgm_s2 c1 = __builtin_elementwise_max(__builtin_elementwise_max(w - hu, lu - w), zero);
-            const unsigned m = sgm_as_u(__builtin_elementwise_min(c0, c1));
-            constexpr int CH = NP;
-            const int s0 = 2 * p >= CH ? 2 : 0, s1 = 2 * p + 1 >= CH ? 2 : 0;
-            col += ((m & 0xffffu) >> s0) + (m >> (16 + s1));
+            for (int p = 0; p < NP; ++p) {
+                const sgm_s2 u = sgm_as_s2(sl[3 * p][s]), lu = sgm_as_s2(sl[3 * p + 1][s]), hu = sgm_as_s2(sl[3 * p + 2][s]);
+                const sgm_s2 w = sgm_as_s2(sr[3 * p][k]), lw = sgm_as_s2(sr[3 * p + 1][k]), hw = sgm_as_s2(sr[3 * p + 2][k]);
+                const sgm_s2 c0 = __builtin_elementwise_max(__builtin_elementwise_max(u - hw, lw - u), zero);
+                const sgm_s2 c1 = __builtin_elementwise_max(__builtin_elementwise_max(w - hu, lu - w), zero);
+                const unsigned m = sgm_as_u(__builtin_elementwise_min(c0, c1));
+                constexpr int CH = NP;
+                const int s0 = 2 * p >= CH ? 2 : 0, s1 = 2 * p + 1 >= CH ? 2 : 0;
+                col += ((m & 0xffffu) >> s0) + (m >> (16 + s1));
+            }
+#pragma unroll
+            for (int i = 0; i + 1 < BS; ++i) v[i] = v[i + 1];
+            v[BS - 1] = col;
+            if (s >= BS - 1) {
+                unsigned sum = 0;
+#pragma unroll
+                for (int i = 0; i < BS; ++i) sum += v[i];
+                out[((size_t)y * a.W + (x0 + s - (BS - 1))) * a.Dp + d] = (uint16_t)(real ? sum : 0u);
+            }
         }
-#pragma unroll
-        for (int i = 0; i + 1 < BS; ++i) v[i] = v[i + 1];
-        v[BS - 1] = col;
-        if (s >= BS - 1) {
-            unsigned sum = 0;
-#pragma unroll
-            for (int i = 0; i < BS; ++i) sum += v[i];
-            out[((size_t)y * a.W + (x0 + s - (BS - 1))) * a.Dp + d] = (uint16_t)(real ? sum : 0u);
-        }
-    }
+    } while (WIDE && (d += 256) < a.Dp);
 }
 
-template <int BS, int NP> __global__ __launch_bounds__(256) void k_sgm_bt_rows(SgmArgs a, uint16_t *out) { sgm_bt_rows<BS, NP>(a, out); }
-template <int BS, int NP>
+template <int BS, int NP, bool WIDE>
+__global__ __launch_bounds__(256) void k_sgm_bt_rows(SgmArgs a, uint16_t *out) { sgm_bt_rows<BS, NP, WIDE>(a, out); }
+template <int BS, int NP, bool WIDE>
 __global__ __launch_bounds__(256) void k_sgm_bt_rows_b(SgmArgs a, const SgmPair *tab)
 {
     a = sgm_pair_args(a, tab, blockIdx.z);
-    sgm_bt_rows<BS, NP>(a, BS == 1 ? a.C : a.Hs);
+    sgm_bt_rows<BS, NP, WIDE>(a, BS == 1 ? a.C : a.Hs);
 }
 
 // The vertical sum: a thread holds four adjacent disparities of one pixel column (8 bytes: Dp is a multiple of 4) and marches
@@ -275,20 +289,37 @@ __device__ __forceinline__ void sgm_bt_cols(const SgmArgs &a)
 template <int BS> __global__ __launch_bounds__(256) void k_sgm_bt_cols(SgmArgs a) { sgm_bt_cols<BS>(a); }
 template <int BS> __global__ __launch_bounds__(256) void k_sgm_bt_cols_b(SgmArgs a, const SgmPair *tab) { sgm_bt_cols<BS>(sgm_pair_args(a, tab, blockIdx.z)); }
 
-// NV adjacent disparities per lane: what a lane moves per pixel
+// NV adjacent disparities per lane: what a lane moves per pixel, and U, the steps of k_sgm_path whose loads are issued together.
+// NV U is constant from NV 4 on: the look-ahead of the wide forms (NV 8, 16: Dp up to 512, 1024) holds the 2 U (NV / 2 + NV) = 96
+// dwords of NV 4, not 192 or 384 - the registers the longer vectors need go to lq, c, l and s instead.
+template <int N> struct alignas(16) SgmQ { uint4 q[N]; };
 template <int NV> struct SgmVec;
-template <> struct SgmVec<1> { using C = unsigned short; using S = unsigned; };
-template <> struct SgmVec<2> { using C = unsigned; using S = uint2; };
-template <> struct SgmVec<4> { using C = uint2; using S = uint4; };
+template <> struct SgmVec<1> { using C = unsigned short; using S = unsigned; static constexpr int U = SGM_U; };
+template <> struct SgmVec<2> { using C = unsigned; using S = uint2; static constexpr int U = SGM_U; };
+template <> struct SgmVec<4> { using C = uint2; using S = uint4; static constexpr int U = SGM_U; };
+template <> struct SgmVec<8> { using C = uint4; using S = SgmQ<2>; static constexpr int U = SGM_U / 2; };
+template <> struct SgmVec<16> { using C = SgmQ<2>; using S = SgmQ<4>; static constexpr int U = SGM_U / 4; };
 __device__ __forceinline__ void sgm_unpack(unsigned short v, int *o) { o[0] = v; }
 __device__ __forceinline__ void sgm_unpack(unsigned v, int *o) { o[0] = v & 0xffffu; o[1] = v >> 16; }
 __device__ __forceinline__ void sgm_unpack(uint2 v, int *o) { o[0] = v.x & 0xffffu; o[1] = v.x >> 16; o[2] = v.y & 0xffffu; o[3] = v.y >> 16; }
+__device__ __forceinline__ void sgm_unpack(uint4 v, int *o) { sgm_unpack(make_uint2(v.x, v.y), o); sgm_unpack(make_uint2(v.z, v.w), o + 4); }
+__device__ __forceinline__ void sgm_unpack(const SgmQ<2> &v, int *o) { sgm_unpack(v.q[0], o); sgm_unpack(v.q[1], o + 8); }
 __device__ __forceinline__ void sgm_unpack_s(unsigned v, unsigned *o) { o[0] = v; }
 __device__ __forceinline__ void sgm_unpack_s(uint2 v, unsigned *o) { o[0] = v.x; o[1] = v.y; }
 __device__ __forceinline__ void sgm_unpack_s(uint4 v, unsigned *o) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
+template <int N> __device__ __forceinline__ void sgm_unpack_s(const SgmQ<N> &v, unsigned *o)
+{
+#pragma unroll
+    for (int i = 0; i < N; ++i) sgm_unpack_s(v.q[i], o + 4 * i);
+}
 __device__ __forceinline__ void sgm_pack_s(const unsigned *o, unsigned &v) { v = o[0]; }
 __device__ __forceinline__ void sgm_pack_s(const unsigned *o, uint2 &v) { v = make_uint2(o[0], o[1]); }
 __device__ __forceinline__ void sgm_pack_s(const unsigned *o, uint4 &v) { v = make_uint4(o[0], o[1], o[2], o[3]); }
+template <int N> __device__ __forceinline__ void sgm_pack_s(const unsigned *o, SgmQ<N> &v)
+{
+#pragma unroll
+    for (int i = 0; i < N; ++i) sgm_pack_s(o + 4 * i, v.q[i]);
+}
 
 // the paths of direction (dy, dx): one per pixel whose predecessor lies outside the image
 __host__ __device__ inline int sgm_npaths(int W, int H, int dy, int dx) { return dy == 0 ? H : (dx == 0 ? W : W + H - 1); }
@@ -308,6 +339,7 @@ __device__ __forceinline__ void sgm_path(const SgmArgs &a, int dy, int dx)
 {
     using CV = typename SgmVec<NV>::C;
     using SV = typename SgmVec<NV>::S;
+    constexpr int U = SgmVec<NV>::U;
     const int lane = threadIdx.x & 63;
     const int path = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (path >= sgm_npaths(a.W, a.H, dy, dx)) return;             // (wave-uniform)
@@ -326,19 +358,19 @@ __device__ __forceinline__ void sgm_path(const SgmArgs &a, int dy, int dx)
     int lq[NV];
 #pragma unroll
     for (int k = 0; k < NV; ++k) lq[k] = d0 + k < a.D ? 0 : SGM_INF;
-    CV cv[2][SGM_U];
-    SV sv[2][SGM_U];
-    auto load = [&](CV (&cb)[SGM_U], SV (&sb)[SGM_U], int i) {             // the loads of steps i .. i + SGM_U - 1
+    CV cv[2][U];
+    SV sv[2][U];
+    auto load = [&](CV (&cb)[U], SV (&sb)[U], int i) {             // the loads of steps i .. i + U - 1
 #pragma unroll
-        for (int u = 0; u < SGM_U; ++u) {
+        for (int u = 0; u < U; ++u) {
             const long long o = off + min(i + u, len - 1) * step;
             cb[u] = *(const CV *)(a.C + o);
             if (!FIRST) sb[u] = *(const SV *)(a.S + o);
         }
     };
-    auto run = [&](const CV (&cb)[SGM_U], const SV (&sb)[SGM_U], int i, auto full) {      // ... and their part of the chain
+    auto run = [&](const CV (&cb)[U], const SV (&sb)[U], int i, auto full) {      // ... and their part of the chain
 #pragma unroll
-        for (int u = 0; u < SGM_U; ++u) {
+        for (int u = 0; u < U; ++u) {
             if (decltype(full)::value || i + u < len) {
                 int c[NV], l[NV];
                 unsigned s[NV] = {};
@@ -370,15 +402,15 @@ __device__ __forceinline__ void sgm_path(const SgmArgs &a, int dy, int dx)
     };
     load(cv[0], sv[0], 0);
     int i = 0;
-    for (; i + 2 * SGM_U <= len; i += 2 * SGM_U) {
-        load(cv[1], sv[1], i + SGM_U);
+    for (; i + 2 * U <= len; i += 2 * U) {
+        load(cv[1], sv[1], i + U);
         run(cv[0], sv[0], i, std::true_type{});
-        load(cv[0], sv[0], i + 2 * SGM_U);
-        run(cv[1], sv[1], i + SGM_U, std::true_type{});
+        load(cv[0], sv[0], i + 2 * U);
+        run(cv[1], sv[1], i + U, std::true_type{});
     }
-    load(cv[1], sv[1], i + SGM_U);                                        // fewer than 2 SGM_U steps are left
+    load(cv[1], sv[1], i + U);                                        // fewer than 2 U steps are left
     run(cv[0], sv[0], i, std::false_type{});
-    run(cv[1], sv[1], i + SGM_U, std::false_type{});
+    run(cv[1], sv[1], i + U, std::false_type{});
 }
 
 template <int NV, bool FIRST, bool ALL>
@@ -387,12 +419,14 @@ __global__ __launch_bounds__(256) void k_sgm_path(SgmArgs a, int dy, int dx) { s
 template <int NV, bool FIRST, bool ALL>
 __global__ __launch_bounds__(256) void k_sgm_path_b(SgmArgs a, const SgmPair *tab, int dy, int dx) { sgm_path<NV, FIRST, ALL>(sgm_pair_args(a, tab, blockIdx.z), dy, dx); }
 
-// One wave per pixel: the packed (S << 8 | d) minimum over the wave is argmin with the lowest d on ties (S < 2^19: at most
-// 8 * 65535 = 524280, which tests/test_gpu_sgm_fuzz.py::test_saturating_pairs_reach_the_packing_bound reaches).
+// One wave per pixel: the packed (S << KB | d) minimum over the wave is argmin with the lowest d on ties (S < 2^19: at most
+// 8 * 65535 = 524280, which tests/test_gpu_sgm_fuzz.py::test_saturating_pairs_reach_the_packing_bound reaches).  KB is 8 up to 256
+// disparities, 10 above (29 bits).  d is the index; the disparity is dmin + d in d16 and in the landing column.
 template <int NV>
 __device__ __forceinline__ void sgm_select(const SgmArgs &a)
 {
     using SV = typename SgmVec<NV>::S;
+    constexpr int KB = NV > 4 ? 10 : 8;                            // = sgm_kb(Dp): NV > 4 is Dp > 256
     const int lane = threadIdx.x & 63;
     const int pix = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (pix >= a.W * a.H) return;                                 // (wave-uniform)
@@ -403,9 +437,9 @@ __device__ __forceinline__ void sgm_select(const SgmArgs &a)
     int key = 0x7fffffff;
 #pragma unroll
     for (int k = 0; k < NV; ++k)
-        if (d0 + k < a.D) key = min(key, (int)((s[k] << 8) | (unsigned)(d0 + k)));
+        if (d0 + k < a.D) key = min(key, (int)((s[k] << KB) | (unsigned)(d0 + k)));
     const int kmin = sgm_wave_min(key);
-    const int best = kmin & 255, minS = kmin >> 8;
+    const int best = kmin & ((1 << KB) - 1), minS = kmin >> KB;
     bool rival = false;                                            // a disparity further than 1 from best within the uniqueness margin
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
@@ -414,7 +448,7 @@ __device__ __forceinline__ void sgm_select(const SgmArgs &a)
     }
     const bool unique = !__any(rival);
     if (lane != 0) return;
-    int d16 = best * 16;
+    int d16 = (a.dmin + best) * 16;
     if (best > 0 && best < a.D - 1) {
         const int sm = (int)Sp[best - 1], sp = (int)Sp[best + 1];
         const int den = max(sm + sp - 2 * minS, 1);
@@ -423,20 +457,21 @@ __device__ __forceinline__ void sgm_select(const SgmArgs &a)
         if (num % dd != 0 && num < 0) --q;                         // floor
         d16 += q;
     }
-    a.pre[pix] = (int16_t)(unique ? d16 : -16);
-    const int y = pix / a.W, x = pix - y * a.W;
-    if (unique && x - best >= 0) atomicMin(a.disp2 + (size_t)y * a.W + (x - best), (unsigned)kmin);
+    a.pre[pix] = (int16_t)(unique ? d16 : a.invalid);
+    const int y = pix / a.W, x = pix - y * a.W, xl = x - (a.dmin + best);
+    if (unique && xl >= 0 && xl < a.W) atomicMin(a.disp2 + (size_t)y * a.W + xl, (unsigned)kmin);
 }
 
 template <int NV> __global__ __launch_bounds__(256) void k_sgm_select(SgmArgs a) { sgm_select<NV>(a); }
 template <int NV> __global__ __launch_bounds__(256) void k_sgm_select_b(SgmArgs a, const SgmPair *tab) { sgm_select<NV>(sgm_pair_args(a, tab, blockIdx.z)); }
 
-__device__ __forceinline__ bool sgm_bad_probe(const unsigned *row, int W, int xq, int dq, int m)
+// a packed minimum's disparity: dmin + its index bits (mask)
+__device__ __forceinline__ bool sgm_bad_probe(const unsigned *row, int W, int xq, int dq, int m, int dmin, unsigned mask)
 {
     if (xq < 0 || xq >= W) return false;
     const unsigned k = row[xq];
     if (k == 0xffffffffu) return false;
-    const int t = (int)(k & 255u) - dq;
+    const int t = dmin + (int)(k & mask) - dq;
     return (t < 0 ? -t : t) > m;
 }
 
@@ -445,11 +480,12 @@ __device__ __forceinline__ void sgm_check(const SgmArgs &a)
     const int pix = blockIdx.x * 256 + threadIdx.x;
     if (pix >= a.W * a.H) return;
     int v = a.pre[pix];
-    if (v >= 0 && a.m >= 0) {
+    if (v != a.invalid && a.m >= 0) {
         const int y = pix / a.W, x = pix - y * a.W;
         const unsigned *row = a.disp2 + (size_t)y * a.W;
-        const int da = v >> 4, db = (v + 15) >> 4;
-        if (sgm_bad_probe(row, a.W, x - da, da, a.m) && sgm_bad_probe(row, a.W, x - db, db, a.m)) v = -16;
+        const unsigned mask = (1u << sgm_kb(a.Dp)) - 1u;
+        const int da = v >> 4, db = (v + 15) >> 4;                 // (arithmetic shifts: floor, also of a negative d16)
+        if (sgm_bad_probe(row, a.W, x - da, da, a.m, a.dmin, mask) && sgm_bad_probe(row, a.W, x - db, db, a.m, a.dmin, mask)) v = a.invalid;
     }
     a.out[pix] = (int16_t)v;
 }
@@ -478,27 +514,35 @@ void launch_sgm_fill_batch(hipStream_t s, const SgmArgs &a, const SgmPair *tab, 
     hipLaunchKernelGGL(k_sgm_fill_b, dim3((a.W * a.H + 255) / 256, 1, n), dim3(256), 0, s, a, tab);
 }
 
+// one thread per disparity up to 256 of them; above, 256 threads that each take every 256th (the WIDE forms)
+static unsigned sgm_cost_threads(int D) { return D > 256 ? 256u : (unsigned)((D + 63) / 64 * 64); }
+
 void launch_sgm_cost(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
 {
-    const dim3 grid((a.W + SGM_TX - 1) / SGM_TX, a.H), block((a.D + 63) / 64 * 64);
-    switch (a.bs) {
-    case 1: sgm_launch(s, k_sgm_cost<1>, k_sgm_cost_b<1>, grid, block, a, tab, n); break;
-    case 3: sgm_launch(s, k_sgm_cost<3>, k_sgm_cost_b<3>, grid, block, a, tab, n); break;
-    case 5: sgm_launch(s, k_sgm_cost<5>, k_sgm_cost_b<5>, grid, block, a, tab, n); break;
-    default: sgm_launch(s, k_sgm_cost<7>, k_sgm_cost_b<7>, grid, block, a, tab, n); break;
+    const dim3 grid((a.W + SGM_TX - 1) / SGM_TX, a.H), block(sgm_cost_threads(a.D));
+    const int wide = a.D > 256;
+    switch (a.bs * 2 + wide) {
+    case 2: sgm_launch(s, k_sgm_cost<1, false>, k_sgm_cost_b<1, false>, grid, block, a, tab, n); break;
+    case 3: sgm_launch(s, k_sgm_cost<1, true>, k_sgm_cost_b<1, true>, grid, block, a, tab, n); break;
+    case 6: sgm_launch(s, k_sgm_cost<3, false>, k_sgm_cost_b<3, false>, grid, block, a, tab, n); break;
+    case 7: sgm_launch(s, k_sgm_cost<3, true>, k_sgm_cost_b<3, true>, grid, block, a, tab, n); break;
+    case 10: sgm_launch(s, k_sgm_cost<5, false>, k_sgm_cost_b<5, false>, grid, block, a, tab, n); break;
+    case 11: sgm_launch(s, k_sgm_cost<5, true>, k_sgm_cost_b<5, true>, grid, block, a, tab, n); break;
+    case 14: sgm_launch(s, k_sgm_cost<7, false>, k_sgm_cost_b<7, false>, grid, block, a, tab, n); break;
+    default: sgm_launch(s, k_sgm_cost<7, true>, k_sgm_cost_b<7, true>, grid, block, a, tab, n); break;
     }
 }
 
-template <int BS>
+template <int BS, bool WIDE>
 static void launch_bt_bs(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
 {
-    const dim3 grid((a.W + SGM_BT_TX - 1) / SGM_BT_TX, a.H, tab ? n : 1), block((a.D + 63) / 64 * 64);
+    const dim3 grid((a.W + SGM_BT_TX - 1) / SGM_BT_TX, a.H, tab ? n : 1), block(sgm_cost_threads(a.D));
     uint16_t *out = BS == 1 ? a.C : a.Hs;                 // (a 1 x 1 block has no vertical sum)
     if (tab) {
-        if (a.ch == 1) hipLaunchKernelGGL((k_sgm_bt_rows_b<BS, 1>), grid, block, 0, s, a, tab);
-        else hipLaunchKernelGGL((k_sgm_bt_rows_b<BS, 3>), grid, block, 0, s, a, tab);
-    } else if (a.ch == 1) hipLaunchKernelGGL((k_sgm_bt_rows<BS, 1>), grid, block, 0, s, a, out);
-    else hipLaunchKernelGGL((k_sgm_bt_rows<BS, 3>), grid, block, 0, s, a, out);
+        if (a.ch == 1) hipLaunchKernelGGL((k_sgm_bt_rows_b<BS, 1, WIDE>), grid, block, 0, s, a, tab);
+        else hipLaunchKernelGGL((k_sgm_bt_rows_b<BS, 3, WIDE>), grid, block, 0, s, a, tab);
+    } else if (a.ch == 1) hipLaunchKernelGGL((k_sgm_bt_rows<BS, 1, WIDE>), grid, block, 0, s, a, out);
+    else hipLaunchKernelGGL((k_sgm_bt_rows<BS, 3, WIDE>), grid, block, 0, s, a, out);
     if constexpr (BS > 1) {
         const size_t rowq = (size_t)a.W * a.Dp / 4;
         sgm_launch(s, k_sgm_bt_cols<BS>, k_sgm_bt_cols_b<BS>, dim3((unsigned)((rowq + 255) / 256), (a.H + SGM_BT_YS - 1) / SGM_BT_YS), dim3(256), a, tab, n);
@@ -508,16 +552,21 @@ static void launch_bt_bs(hipStream_t s, const SgmArgs &a, const SgmPair *tab, in
 void launch_sgm_cost_bt(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
 {
     sgm_launch(s, k_sgm_prefilter, k_sgm_prefilter_b, dim3((a.W + 255) / 256, a.H, 2), dim3(256), a, tab, 2 * n);
-    switch (a.bs) {
-    case 1: launch_bt_bs<1>(s, a, tab, n); break;
-    case 3: launch_bt_bs<3>(s, a, tab, n); break;
-    case 5: launch_bt_bs<5>(s, a, tab, n); break;
-    default: launch_bt_bs<7>(s, a, tab, n); break;
+    const int wide = a.D > 256;
+    switch (a.bs * 2 + wide) {
+    case 2: launch_bt_bs<1, false>(s, a, tab, n); break;
+    case 3: launch_bt_bs<1, true>(s, a, tab, n); break;
+    case 6: launch_bt_bs<3, false>(s, a, tab, n); break;
+    case 7: launch_bt_bs<3, true>(s, a, tab, n); break;
+    case 10: launch_bt_bs<5, false>(s, a, tab, n); break;
+    case 11: launch_bt_bs<5, true>(s, a, tab, n); break;
+    case 14: launch_bt_bs<7, false>(s, a, tab, n); break;
+    default: launch_bt_bs<7, true>(s, a, tab, n); break;
     }
 }
 
-// lanes hold 1, 2 or 4 disparities: the smallest count that covers Dp with 64 lanes
-static int sgm_nv(int Dp) { return Dp <= 64 ? 1 : (Dp <= 128 ? 2 : 4); }
+// lanes hold 1, 2, 4, 8 or 16 disparities: the smallest count that covers Dp with 64 lanes
+static int sgm_nv(int Dp) { return Dp <= 64 ? 1 : (Dp <= 128 ? 2 : (Dp <= 256 ? 4 : (Dp <= 512 ? 8 : 16))); }
 
 template <int NV>
 static void launch_path_nv(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first, const SgmPair *tab, int n)
@@ -535,7 +584,9 @@ void launch_sgm_path(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first
     switch (sgm_nv(a.Dp)) {
     case 1: launch_path_nv<1>(s, a, dy, dx, first, tab, n); break;
     case 2: launch_path_nv<2>(s, a, dy, dx, first, tab, n); break;
-    default: launch_path_nv<4>(s, a, dy, dx, first, tab, n); break;
+    case 4: launch_path_nv<4>(s, a, dy, dx, first, tab, n); break;
+    case 8: launch_path_nv<8>(s, a, dy, dx, first, tab, n); break;
+    default: launch_path_nv<16>(s, a, dy, dx, first, tab, n); break;
     }
 }
 
@@ -546,7 +597,9 @@ void launch_sgm_select(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int 
     switch (sgm_nv(a.Dp)) {
     case 1: sgm_launch(s, k_sgm_select<1>, k_sgm_select_b<1>, grid, block, a, tab, n); break;
     case 2: sgm_launch(s, k_sgm_select<2>, k_sgm_select_b<2>, grid, block, a, tab, n); break;
-    default: sgm_launch(s, k_sgm_select<4>, k_sgm_select_b<4>, grid, block, a, tab, n); break;
+    case 4: sgm_launch(s, k_sgm_select<4>, k_sgm_select_b<4>, grid, block, a, tab, n); break;
+    case 8: sgm_launch(s, k_sgm_select<8>, k_sgm_select_b<8>, grid, block, a, tab, n); break;
+    default: sgm_launch(s, k_sgm_select<16>, k_sgm_select_b<16>, grid, block, a, tab, n); break;
     }
     sgm_launch(s, k_sgm_check, k_sgm_check_b, dim3((HW + 255) / 256), dim3(256), a, tab, n);
 }

@@ -26,6 +26,7 @@ def _ptr(a):
 
 
 class DispEst:
+    _sgm_d = 0                               # the disparities of the last SGBM_GPU (0: none yet - maxDis)
     _sgm_ch = 3                                  # the channels of the pair the last SGBM_GPU ran on (1: its gray= pair)
 
     def __init__(self, l, r, d: int, t: int = 8, ocl: bool = True, *, dtype: str = "f32",
@@ -140,7 +141,8 @@ class DispEst:
 
     # ---- the second algorithm: STEREO_SGBM (src/StereoMatch.cpp:169-187) ----------------------
     def SGBM_GPU(self, block_size: int = 0, P1: int = 0, P2: int = 0, uniqueness_ratio: int = 10, disp12_max_diff: int = 1,
-                 gray=None, speckle_window_size: int = 0, speckle_range: int = 0, pre_filter_cap: int = 0, mode="hh"):
+                 gray=None, speckle_window_size: int = 0, speckle_range: int = 0, pre_filter_cap: int = 0, mode="hh",
+                 min_disparity: int = 0, num_disparities: int = 0):
         """ssgbm->compute(lFrame, rFrame, imgDisparity16S) on the device over the pair setInputImages staged, with the
         parameters of setupOpenCVSGBM (src/StereoMatch.cpp:639-660) as defaults (0: blockSize 5, P1 = 8 ch bs^2, P2 = 32 ch bs^2).
         -> H x W int16: disparity * 16, -16 where invalid.  An independent stage (psm_sgm_compute): the maps, masks and volumes
@@ -150,8 +152,13 @@ class DispEst:
         pre_filter_cap in 1 .. 63: StereoSGBM's pixel cost, Birchfield-Tomasi over Sobel-prefiltered images (psm_sgm_set_prefilter;
         the reference: 63); 0, the default: SAD - this call's setting too.
         mode: ssgbm->setMode, "sgbm", "hh" (the default: all eight directions), "3way", "hh4" or OpenCV's integer
-        (psm_sgm_set_mode) - this call's setting as well."""
+        (psm_sgm_set_mode) - this call's setting as well.
+        min_disparity, num_disparities: StereoSGBM::create's first two arguments (psm_sgm_set_range) - the disparities
+        min_disparity .. min_disparity + num_disparities - 1, num_disparities in 2 .. 1024 whatever maxDis is, or 0, the default:
+        maxDis; invalid pixels are then (min_disparity - 1) * 16.  This call's setting as well."""
         self._ck(self._lib.psm_sgm_set_mode(self._h, sgm_mode(mode)), "SGBM_GPU")
+        self._ck(self._lib.psm_sgm_set_range(self._h, int(min_disparity), int(num_disparities)), "SGBM_GPU")
+        self._sgm_d = int(num_disparities) or self.maxDis
         self._ck(self._lib.psm_sgm_set_prefilter(self._h, int(pre_filter_cap)), "SGBM_GPU")
         self._ck(self._lib.psm_sgm_set_speckle(self._h, int(speckle_window_size), int(speckle_range)), "SGBM_GPU")
         self._ck(self._lib.psm_sgm_set_params(self._h, int(block_size), int(P1), int(P2), int(uniqueness_ratio),
@@ -173,9 +180,10 @@ class DispEst:
         return disp
 
     def sgm_costs(self):
-        """Test hook: (C uint16, S uint32), both [H][W][maxDis], of the last SGBM_GPU."""
-        Cv = np.empty((self.hei, self.wid, self.maxDis), np.uint16)
-        Sv = np.empty((self.hei, self.wid, self.maxDis), np.uint32)
+        """Test hook: (C uint16, S uint32), both [H][W][D], of the last SGBM_GPU - D its num_disparities, or maxDis."""
+        D = self._sgm_d or self.maxDis
+        Cv = np.empty((self.hei, self.wid, D), np.uint16)
+        Sv = np.empty((self.hei, self.wid, D), np.uint32)
         self._ck(self._lib.psm_sgm_download_costs(self._h, 0, _ptr(Cv)), "sgm_costs")
         self._ck(self._lib.psm_sgm_download_costs(self._h, 1, _ptr(Sv)), "sgm_costs")
         return Cv, Sv
@@ -522,7 +530,8 @@ def sgm_mode(mode):
 
 
 def sgbm_batch(des, block_size: int = 0, P1: int = 0, P2: int = 0, uniqueness_ratio: int = 10, disp12_max_diff: int = 1,
-               speckle_window_size: int = 0, speckle_range: int = 0, pre_filter_cap: int = 0, mode="hh"):
+               speckle_window_size: int = 0, speckle_range: int = 0, pre_filter_cap: int = 0, mode="hh", min_disparity: int = 0,
+               num_disparities: int = 0):
     """SGBM_GPU of several DispEst objects of one geometry in shared launches (psm_sgm_compute_batch): the parameters (SGBM_GPU's,
     without gray=) are set on every object, each object's own staged pair goes through the stage, -> the list of H x W int16 maps.
     Every object afterwards behaves as after its own SGBM_GPU (sgm_costs(), sgm_prefiltered(), sgm_speckle_sizes(), ...); the
@@ -532,6 +541,8 @@ def sgbm_batch(des, block_size: int = 0, P1: int = 0, P2: int = 0, uniqueness_ra
         return []
     for d in des:
         d._ck(d._lib.psm_sgm_set_mode(d._h, sgm_mode(mode)), "sgbm_batch")
+        d._ck(d._lib.psm_sgm_set_range(d._h, int(min_disparity), int(num_disparities)), "sgbm_batch")
+        d._sgm_d = int(num_disparities) or d.maxDis
         d._ck(d._lib.psm_sgm_set_prefilter(d._h, int(pre_filter_cap)), "sgbm_batch")
         d._ck(d._lib.psm_sgm_set_speckle(d._h, int(speckle_window_size), int(speckle_range)), "sgbm_batch")
         d._ck(d._lib.psm_sgm_set_params(d._h, int(block_size), int(P1), int(P2), int(uniqueness_ratio), int(disp12_max_diff)),

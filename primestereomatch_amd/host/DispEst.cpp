@@ -249,6 +249,12 @@ int DispEst::setSGBMMode(int mode)
     return hipUtil::api().sgm_set_mode(ctx[0], mode);
 }
 
+int DispEst::setSGBMRange(int minDisparity, int numDisparities)
+{
+    if (ctx.empty()) return 1;
+    return hipUtil::api().sgm_set_range(ctx[0], minDisparity, numDisparities);
+}
+
 int DispEst::sgbmSpeckleTime(double *ms)
 {
     if (ctx.empty()) return 1;

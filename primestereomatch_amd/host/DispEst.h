@@ -122,6 +122,11 @@ public:
     // PSM_SGM_MODE_HH (1, the setting of a new object: all eight directions), PSM_SGM_MODE_SGBM_3WAY (2), PSM_SGM_MODE_HH4 (3) -
     // OpenCV's enum values.  SGBMBatch wants one mode on all its objects.
     int setSGBMMode(int mode);
+    // StereoSGBM::create's minDisparity and numDisparities for every following SGBM_GPU (psm_sgm_set_range): the disparities
+    // minDisparity .. minDisparity + numDisparities - 1, minDisparity in [-1024, 1024], numDisparities in [2, 1024] or 0, the
+    // setting of a new object: maxDis.  Invalid pixels of the map are (minDisparity - 1) * 16.  SGBMBatch wants one range on all
+    // its objects.
+    int setSGBMRange(int minDisparity, int numDisparities);
 
     // Frame loop (src/main.cpp:64-73) with the PCIe legs next to the kernels (single-device hosts): one call per frame -
     // CostConst (adopts the pair staged by the previous call), stages `next` pair (may be NULL at the end of the stream: its

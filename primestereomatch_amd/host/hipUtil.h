@@ -58,6 +58,7 @@ struct HipApi {
     int (*sgm_set_prefilter)(psm_ctx *, int) = nullptr;
     int (*sgm_compute_batch)(psm_ctx *const *, int) = nullptr;
     int (*sgm_set_mode)(psm_ctx *, int) = nullptr;
+    int (*sgm_set_range)(psm_ctx *, int, int) = nullptr;
     int (*joint_wmf_batch)(psm_ctx *const *, int, int, float, int, int) = nullptr;
 };
 

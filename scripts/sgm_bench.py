@@ -11,6 +11,11 @@ those bytes over the total as a fraction of the part's measured copy ceiling (6.
 the stage holds.  --model: also time the numpy model (tests/sgm_model.py) on the same pair, for scale; --model-only does just
 that and needs no GPU (the large pairs take minutes and gigabytes).
 
+--min-disparity M, --num-disparities N (psm_sgm_set_range): the same record over the disparities M .. M + N - 1 instead of
+0 .. D - 1, N up to 1024 whatever the configuration's D (the context keeps max_disp = min(D, 256)); the configurations 1080p512,
+1080p1024 and 4k512 (1920 x 1080 x 512 / x 1024, 3840 x 2160 x 512) set N themselves.  Dp is then N rounded up to 8 (N > 256) or
+16 (N > 512), and "valid" means != (M - 1) * 16.
+
 --mode: StereoSGBM's reduced modes beside hh - modes_bench below.
 
 The speckle filter (psm_sgm_set_speckle; k_spk_runs, k_spk_merge, k_spk_count, k_spk_apply): every configuration is timed twice in
@@ -41,7 +46,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 COPY_CEILING = 6.29e12          # B/s
-CONFIGS = {"cones": (450, 375, 64), "720p": (1280, 720, 128), "1080p": (1920, 1080, 256)}
+CONFIGS = {"cones": (450, 375, 64), "720p": (1280, 720, 128), "1080p": (1920, 1080, 256),
+           "1080p512": (1920, 1080, 512), "1080p1024": (1920, 1080, 1024), "4k512": (3840, 2160, 512)}       # above 256: through the range
 
 
 def the_pair(name):
@@ -54,7 +60,7 @@ def the_pair(name):
 
 
 def accounting(W, H, D):
-    Dp = (D + 3) // 4 * 4
+    Dp = (D + 3) // 4 * 4 if D <= 256 else ((D + 7) // 8 * 8 if D <= 512 else (D + 15) // 16 * 16)
     vox = W * H * Dp
     moved = vox * (2 + 8 * 10 - 4 + 4) + W * H * (2 * 3 + 4 + 4 + 2 + 4 + 4 + 2 + 2)   # images; disp2 fill, atomics, probes; pre, out
     held = vox * 6 + W * H * (4 + 2 + 2)
@@ -239,9 +245,13 @@ def main():
     ap.add_argument("--batch", default=None, help="N[,N...]: time psm_sgm_compute_batch at these batch sizes beside the singles")
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--mode", default=None, help="M[,M...] of sgbm, 3way, hh4: time these modes beside hh (modes_bench)")
+    ap.add_argument("--min-disparity", type=int, default=0, help="psm_sgm_set_range: the first disparity")
+    ap.add_argument("--num-disparities", type=int, default=0, help="psm_sgm_set_range: their number, up to 1024 (0: the configuration's D)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert a.runs >= 1
+    if (a.mode or a.batch) and (a.min_disparity or a.num_disparities):
+        raise SystemExit("sgm_bench: --min-disparity / --num-disparities go with the plain record only")
     if a.mode:
         return modes_bench(a)
     if a.batch:
@@ -249,17 +259,24 @@ def main():
     for name in a.configs.split(","):
         W, H, D = CONFIGS[name]
         l, r = the_pair(name)
+        maxdis = min(D, 256)
+        nd = a.num_disparities or (D if D > 256 else 0)
+        D = nd or D
+        rng = dict(min_disparity=a.min_disparity, num_disparities=nd) if nd or a.min_disparity else {}
+        invalid = (a.min_disparity - 1) * 16
         Dp, moved, held = accounting(W, H, D)
         rec = {"bench": "sgm", "config": name, "W": W, "H": H, "D": D, "Dp": Dp}
+        if rng:
+            rec["range"] = [a.min_disparity, nd]
         if not a.model_only:
             import primestereomatch_amd as P
             from primestereomatch_amd import capi
             if capi.device_count() < 1:
                 raise SystemExit("sgm_bench: no HIP device visible")
-            with P.DispEst(l, r, D) as de:
+            with P.DispEst(l, r, maxdis) as de:
                 de.set_option(capi.PSM_OPT_PROFILE, 1)
                 for _ in range(a.warmup):
-                    de.SGBM_GPU()
+                    de.SGBM_GPU(**rng)
                 t, wall = [], []
                 for _ in range(a.runs):
                     w0 = time.perf_counter()
@@ -268,7 +285,7 @@ def main():
                     t.append(de.sgm_times())
                 disp = de.sgm_disparity()
                 for _ in range(a.warmup):
-                    de.SGBM_GPU(speckle_window_size=100, speckle_range=32)
+                    de.SGBM_GPU(speckle_window_size=100, speckle_range=32, **rng)
                 ts, tk = [], []
                 for _ in range(a.runs):
                     de._ck(de._lib.psm_sgm_compute(de._h), "psm_sgm_compute")      # (the setting holds)
@@ -276,12 +293,12 @@ def main():
                     tk.append(de.sgm_speckle_time())
                 removed = int(np.count_nonzero(de.sgm_disparity() != disp))
                 for _ in range(a.warmup):
-                    de.SGBM_GPU(pre_filter_cap=63)
+                    de.SGBM_GPU(pre_filter_cap=63, **rng)
                 tb = []
                 for _ in range(a.runs):
                     de._ck(de._lib.psm_sgm_compute(de._h), "psm_sgm_compute")      # (the setting holds)
                     tb.append(de.sgm_times())
-                valid_bt = float((de.sgm_disparity() >= 0).mean())
+                valid_bt = float((de.sgm_disparity() != invalid).mean())
             t = np.array(t)
             meds = np.median(np.array(ts), axis=0)
             medb = np.median(np.array(tb), axis=0)
@@ -291,7 +308,7 @@ def main():
                         "select_ms": round(float(med[2]), 4), "total_ms": round(total, 4), "total_ms_min_max": [round(float(t.sum(axis=1).min()), 4), round(float(t.sum(axis=1).max()), 4)],
                         "wall_ms_median": round(float(np.median(wall)), 4), "bytes_moved": int(moved),
                         "fraction_of_copy_ceiling": round(moved / COPY_CEILING * 1e3 / total, 4), "copy_ceiling_TBps": COPY_CEILING / 1e12,
-                        "device_bytes_held": int(held), "valid_fraction": round(float((disp >= 0).mean()), 4),
+                        "device_bytes_held": int(held), "valid_fraction": round(float((disp != invalid).mean()), 4),
                         "speckle_ms": round(float(np.median(tk)), 4), "speckle_ms_min_max": [round(min(tk), 4), round(max(tk), 4)],
                         "cost_ms_speckle_on": round(float(meds[0]), 4), "paths_ms_speckle_on": round(float(meds[1]), 4),
                         "select_ms_speckle_on": round(float(meds[2]), 4), "speckle_pixels_removed": removed,
