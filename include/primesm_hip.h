@@ -573,7 +573,65 @@ int psm_compute_batch(psm_ctx *const *ctxs, int n);
  * the streams live until the last of the contexts is destroyed.  psm_set_stream is refused afterwards. */
 int psm_share_streams(psm_ctx *const *ctxs, int n);
 
+/* ---- score: the display maps and the error metric of StereoMatch::compute on the device (src/StereoMatch.cpp:181-185,
+ * 248-249, 275-309).  The definition is tests/score_model.py; the device equals it in every element and counter.
+ * An independent stage: it reads the context's current result and writes its own planes - maps, masks, volumes and the SGM
+ * stage's buffers are untouched. ----
+ * Sources.  PSM_SCORE_GIF: the current 8-bit maps, as psm_download_maps would return them (after whichever of psm_disp_select,
+ * psm_lr_check, psm_fill_invalid, psm_wgt_median, psm_joint_wmf, psm_upload_maps ran last); display of both sides =
+ * min(v * scale_factor, 255) (convertTo(CV_8U, scale_factor)); the left one is scored.  The right display is the right map (the
+ * reference's rightDispMap = lDispMap, :252, is not mirrored).
+ * PSM_SCORE_SGM: the int16 map of the last psm_sgm_compute*; minVal / maxVal over the whole map, the invalid value included
+ * (minMaxLoc); alpha = (float)(255.0 / ((double)maxVal - (double)minVal)); m = sat_u8(rne((float)v * alpha)) - one fp32 multiply,
+ * negative products saturate to 0; m = sat_u8(rne((float)m * 0.25f)); display = min(m * scale_factor, 255); the metric runs on
+ * the display with scale 1.  maxVal == minVal (the reference divides by zero): alpha = 0, an all-zero display, PSM_SCORE_FLAT.
+ * PSM_SCORE_SGM_INT: min(max(d16, 0) >> 4, 255) of that map, then as a PSM_SCORE_GIF left map (the figure comparable with the
+ * GIF path's).
+ * Metric on the 8-bit display p, ground truth g, mask k: e = |p - g|; e = 0 for columns x <= max_disp; unit = 127 / max_disp
+ * (integer; 0 from max_disp 128 up); e = 0 where e <= error_threshold * unit (THRESH_TOZERO); with a mask, after k = (k > 254 ?
+ * k : 0) under PSM_MASK_DISC, e = sat_u8(rne((double)(e * k) * (double)(1 / 255.f))); bad = #(e != 0), err_sum = sum of e.
+ * %BP = 100.0 * bad / pixels; Avg Err = unit ? ((double)err_sum / pixels) / unit : 0.0 - both exact on the host in double. */
+enum { PSM_SCORE_GIF = 0, PSM_SCORE_SGM = 1, PSM_SCORE_SGM_INT = 2 };
+enum { PSM_MASK_NONE = 0, PSM_MASK_NONOCC = 1, PSM_MASK_DISC = 2 };      /* include/StereoMatch.h */
+enum { PSM_SCORE_FLAT = 1 };                                             /* psm_score.flags */
+struct psm_score {
+    int32_t min_val, max_val;   /* PSM_SCORE_SGM: minMaxLoc of the int16 map; the other sources: 0 */
+    uint32_t pixels, bad;       /* W * H; pixels whose error survived (0 without a truth) */
+    uint64_t err_sum;           /* the sum of the surviving errors */
+    int32_t unit;               /* 127 / max_disp */
+    uint32_t flags;             /* PSM_SCORE_FLAT */
+};
+/* The ground truth and (mask != NULL) the error mask of this context's dataset, H rows of W bytes, pitch stride_bytes (0: W),
+ * copied to the device once; they stay until replaced or cleared and survive psm_release_scratch.  mask NULL: no mask. */
+int psm_score_set_truth(psm_ctx *ctx, const uint8_t *gt, const uint8_t *mask, size_t stride_bytes);
+int psm_score_clear_truth(psm_ctx *ctx);
+/* scale_factor in 1..255, error_threshold in 0..255, mask_mode PSM_MASK_NONE (an uploaded mask is ignored) | PSM_MASK_NONOCC (the
+ * mask as it is) | PSM_MASK_DISC.  A new context has (4, 4, PSM_MASK_NONOCC), the reference's settings for Cones and Teddy. */
+int psm_score_set_params(psm_ctx *ctx, int scale_factor, int error_threshold, int mask_mode);
+/* Display map(s), error plane and record of `source`, in one launch (two for PSM_SCORE_SGM), the counters zeroed on the stream
+ * ahead of them.  Synchronous, the record in *out, unless PSM_OPT_ASYNC: then the record travels to a page-locked slot and
+ * psm_score_wait collects it (one record in flight; out is not written).  Without a truth the display maps and min_val / max_val
+ * are written all the same, bad = err_sum = 0 and the error plane is zero.  Refused with nothing enqueued: a GIF source without
+ * current maps or with maps that cover a row stripe only, an SGM source without a compute, an unknown source. */
+int psm_score(psm_ctx *ctx, int source, struct psm_score *out);
+int psm_score_wait(psm_ctx *ctx, struct psm_score *out);
+/* The planes of the last psm_score / psm_score_batch: left display, right display (PSM_SCORE_GIF only), error plane; any pointer
+ * may be NULL; H rows of W bytes, pitch stride (0: W).  Synchronises. */
+int psm_score_download(psm_ctx *ctx, uint8_t *ldisp, uint8_t *rdisp, uint8_t *emap, size_t stride);
+/* psm_score of the n contexts ctxs[0..n) in one set of launches, the context on a grid axis of its own; each context scores its
+ * own result against its own truth.  Same width, height, max_disp, device and score parameters on all; a truth (and a mask) on
+ * all or on none - anything else is refused naming the context, with nothing enqueued.  The launches run on ctxs[0]'s stream,
+ * ordered as psm_sgm_compute_batch's; synchronous with the records in outs[0..n) unless ctxs[0] has PSM_OPT_ASYNC (then every
+ * context's psm_score_wait collects its own).  Afterwards every context is exactly where its own psm_score would have left it. */
+int psm_score_batch(psm_ctx *const *ctxs, int n, int source, struct psm_score *outs);
+/* Device ms of the launches of the last psm_score (a batch: on ctxs[0], for all pairs); needs PSM_OPT_PROFILE. */
+int psm_score_time(psm_ctx *ctx, double *ms);
+
 /* ---- debug / bench entry points (no counterpart in the reference) ---- */
+/* Test hook of the score stage: an int16 map (H rows of W values, pitch stride_bytes; 0: packed) that the SGM sources of
+ * psm_score read from now on instead of the map of the last psm_sgm_compute - maps no compute would produce.  Kept in a plane
+ * of its own: the SGM stage and its readers never see it.  disp NULL: the hook map is dropped again. */
+int psm_score_upload_sgm_map(psm_ctx *ctx, const int16_t *disp, size_t stride_bytes);
 /* Replace the device maps and validity masks (any may be NULL = keep) - lets the post-processing stages run on maps
  * that did not come from this context's WTA.  H rows of W bytes, pitch `stride`; map values must be < max_disp. */
 int psm_upload_maps(psm_ctx *ctx, const uint8_t *lmap, const uint8_t *rmap, const uint8_t *lvalid, const uint8_t *rvalid,

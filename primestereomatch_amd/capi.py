@@ -27,6 +27,23 @@ PSM_FLAG_TWO_PHASE_ON, PSM_FLAG_TWO_PHASE_OFF = 1048576, 2097152
 PSM_FLAG_WMF_DATAFLOW, PSM_FLAG_WMF_TWO_SWEEPS, PSM_FLAG_WMF_NO_CACHE = 4194304, 8388608, 16777216
 PSM_FLAG_F32_TOL = 33554432
 PSM_FLAG_FMA_SOLVE = 67108864
+# the score stage: sources, mask modes (include/StereoMatch.h), record flags
+PSM_SCORE_GIF, PSM_SCORE_SGM, PSM_SCORE_SGM_INT = 0, 1, 2
+PSM_MASK_NONE, PSM_MASK_NONOCC, PSM_MASK_DISC = 0, 1, 2
+PSM_SCORE_FLAT = 1
+
+
+class Score(C.Structure):
+    """struct psm_score: the integers of the error record; the two figures are derived from them in double."""
+    _fields_ = [("min_val", C.c_int32), ("max_val", C.c_int32), ("pixels", C.c_uint32), ("bad", C.c_uint32),
+                ("err_sum", C.c_uint64), ("unit", C.c_int32), ("flags", C.c_uint32)]
+
+    def as_dict(self):
+        d = {name: int(getattr(self, name)) for name, _ in self._fields_}
+        d["bp_percent"] = 100.0 * d["bad"] / d["pixels"]
+        d["avg_err"] = (d["err_sum"] / d["pixels"]) / d["unit"] if d["unit"] else 0.0
+        return d
+
 
 # every symbol include/primesm_hip.h declares: (name, restype, argtypes)
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
@@ -105,6 +122,15 @@ SYMBOLS = [
     ("psm_sgm_compute_batch", _i, [C.POINTER(_vp), _i]),
     ("psm_sgm_set_mode", _i, [_vp, _i]),
     ("psm_sgm_set_range", _i, [_vp, _i, _i]),
+    ("psm_score_set_truth", _i, [_vp, _vp, _vp, _sz]),
+    ("psm_score_clear_truth", _i, [_vp]),
+    ("psm_score_set_params", _i, [_vp, _i, _i, _i]),
+    ("psm_score", _i, [_vp, _i, C.POINTER(Score)]),
+    ("psm_score_wait", _i, [_vp, C.POINTER(Score)]),
+    ("psm_score_download", _i, [_vp, _vp, _vp, _vp, _sz]),
+    ("psm_score_batch", _i, [C.POINTER(_vp), _i, _i, C.POINTER(Score)]),
+    ("psm_score_time", _i, [_vp, _pd]),
+    ("psm_score_upload_sgm_map", _i, [_vp, _vp, _sz]),
 ]
 
 _lib = None

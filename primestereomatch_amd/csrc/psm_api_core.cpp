@@ -107,6 +107,7 @@ void free_all(psm_ctx *c)
     }
     rectify_free(c, true);
     sgm_free(c);
+    score_free(c, true);
     (void)hipFree(c->fvol);
     (void)hipFree(c->spare);
     (void)hipFree(c->ab);
@@ -424,6 +425,7 @@ int psm_release_scratch(psm_ctx *c)
     (void)hipFree(c->fvol); c->fvol = nullptr;
     rectify_free(c, false);
     sgm_free(c);
+    score_free(c, false);
     for (int k = 0; k < 2; ++k)
         if (c->xfer_pin[k]) { (void)hipHostFree(c->xfer_pin[k]); c->xfer_pin[k] = nullptr; c->xfer_pin_bytes[k] = 0; }
     (void)hipGetLastError();

@@ -11,6 +11,8 @@
 //   psm_api_rectify.cpp video mode: remap + crop of the camera frame into the staged image slot (psm_upload_pair_rectified)
 //   psm_api_sgm.cpp     semi-global matching over the staged pair, the reference's STEREO_SGBM branch (psm_sgm_compute), and
 //                       over the pairs of several contexts in shared launches (psm_sgm_compute_batch)
+//   psm_api_score.cpp   display maps and the error metric against ground truth of the current result (psm_score), and of the
+//                       results of several contexts in shared launches (psm_score_batch)
 // Takes the place of the reference's oclUtil + CVC_cl / CVF_cl / DispSel_cl host wrappers
 // (src/oclUtil.cpp, src/CVC_cl.cpp, src/CVF_cl.cpp, src/DispSel_cl.cpp).
 // What a context knows about its volumes and results between calls - psm::VolSide per side, psm::Results - lives in psm_state.h
@@ -87,6 +89,30 @@ struct JwBatch {
     hipEvent_t ev_tab[2] = {nullptr, nullptr};
     uint8_t *block = nullptr, *pin = nullptr;      // [cap] x {int state[4]}, then [cap] x {float centres[JW_NF_MAX][3]}
     size_t cap = 0;                                // images
+};
+
+// psm_score (psm_api_score.cpp): parameters, the dataset's truth (kept until replaced or cleared), and the stage's scratch -
+// display and error planes, counters, their page-locked slot - allocated on first use and given back by psm_release_scratch.
+struct ScoreState {
+    int scale = 4, thr = 4, mask_mode = PSM_MASK_NONOCC;
+    uint8_t *gt = nullptr, *mask = nullptr;        // [H][W] each; have_mask: the last psm_score_set_truth brought one
+    bool have_truth = false, have_mask = false;
+    int16_t *hook = nullptr;                       // psm_score_upload_sgm_map: the plane; hook_on: the SGM sources read it
+    bool hook_on = false;
+    uint8_t *planes = nullptr;                     // [3][H][W]: left display, right display, error plane
+    ScCnt *cnt = nullptr, *pin = nullptr;          // the counters and the page-locked slot their copy lands in
+    hipEvent_t ev_done = nullptr;                  // ... that copy has executed
+    hipEvent_t ev[2] = {nullptr, nullptr};         // PSM_OPT_PROFILE: around the launches
+    int source = -1;                               // of the last psm_score (-1: none: the planes hold nothing)
+    int unit = 0;                                  // ... and its 127 / max_disp
+    bool pending = false;                          // a record is on its way to `pin` (psm_score_wait)
+    bool timed = false;
+    // psm_score_batch (this context as the first of a batch): the device table, its host copy and page-locked staging, as SgmState's
+    ScPair *tab = nullptr, *tab_pin = nullptr;
+    std::vector<ScPair> tab_host;
+    size_t tab_cap = 0;
+    int tab_slot = 0;
+    hipEvent_t ev_tab[2] = {nullptr, nullptr};
 };
 }  // namespace psm
 
@@ -165,6 +191,7 @@ struct psm_ctx {
     uint8_t *rect_pin = nullptr;
     size_t rect_src_bytes = 0;                   // bytes of one eye in a slot (16-byte multiple) the buffers were allocated for
     psm::SgmState sgm;
+    psm::ScoreState score;
     uint8_t *p4[2] = {nullptr, nullptr};  // PSM_U8 only: {c0,c1,c2,grad} words
     // What stands for vol[side] (psm_state.h): costs that are a recipe, a filtered volume pending as packed minima or as FGF models.
     // The WTA consumes either form directly; any other reader makes the volume real first (materialize()).
@@ -322,6 +349,8 @@ void rectify_free(psm_ctx *c, bool maps);        // the source slots and their s
 void jwmf_batch_free(psm_ctx *c);                // what the context holds as the first of a psm_joint_wmf_batch
 // psm_api_sgm.cpp
 void sgm_free(psm_ctx *c);                       // the stage's buffers and events (its parameters stay)
+// psm_api_score.cpp
+void score_free(psm_ctx *c, bool truth);         // the stage's scratch and events; truth: the uploaded truth, mask and hook map too
 // psm_api_select.cpp: copy_maps_out - two [H][W] planes on the device to the caller's rows
 int copy_maps_out(psm_ctx *c, const uint8_t *dev, uint8_t *lmap, uint8_t *rmap, size_t stride);
 

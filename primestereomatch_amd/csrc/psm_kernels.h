@@ -303,4 +303,36 @@ struct SpkArgs {
 // k_spk_runs, k_spk_merge, k_spk_count, k_spk_apply; tab: as above - the maps are the pairs' `out`
 void launch_speckle(hipStream_t s, const SpkArgs &a, const SgmPair *tab = nullptr, int n = 1);
 
+// psm_score.hip: the display maps and the reference's error record of the current result (psm_score, psm_api_score.cpp)
+// The counters of one pair, zeroed on the stream ahead of the launches.  mn / mx hold the int16 map's minimum - 32767 (<= 0) and
+// maximum + 32768 (>= 0): zero is then the identity of both atomics, and one memset prepares all of it.
+struct ScCnt {
+    int mn, mx;
+    unsigned bad, pad;
+    unsigned long long sum;
+};
+constexpr int SC_MN_BIAS = 32767, SC_MX_BIAS = 32768;
+enum { SC_GIF = 0, SC_SGM = 1, SC_SGM_INT = 2 };       // PSM_SCORE_* (include/primesm_hip.h)
+struct ScArgs {
+    const uint8_t *maps;               // SC_GIF: [2][H][W], the context's current maps
+    const int16_t *d16;                // SC_SGM, SC_SGM_INT: [H][W], the map of the last compute
+    const uint8_t *gt, *mask;          // [H][W] each; gt null: nothing is scored; mask null: step 5 of the metric is left out
+    uint8_t *planes;                   // [3][H][W]: left display, right display (SC_GIF only), error plane
+    ScCnt *cnt;
+    int W, H, D;
+    int scale, thr;                    // scale_factor; error_threshold * unit: errors up to it count as none
+    int disc;                          // PSM_MASK_DISC: mask values up to 254 count as 0
+};
+// Several pairs per launch (psm_score_batch): one pair's pointers, an entry of the device table the batched entries index with the
+// pair number (blockIdx.y); the scalars of ScArgs are the batch's.
+struct ScPair {
+    const uint8_t *maps;
+    const int16_t *d16;
+    const uint8_t *gt, *mask;
+    uint8_t *planes;
+    ScCnt *cnt;
+};
+void launch_sc_minmax(hipStream_t s, const ScArgs &a, const ScPair *tab = nullptr, int n = 1);   // k_sc_minmax: cnt->mn, cnt->mx of d16
+void launch_sc_score(hipStream_t s, int source, const ScArgs &a, const ScPair *tab = nullptr, int n = 1);   // k_sc_score<source>: planes, cnt->bad, cnt->sum
+
 }  // namespace psm

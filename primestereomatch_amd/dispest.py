@@ -227,6 +227,71 @@ class DispEst:
         self._ck(self._lib.psm_sgm_speckle_time(self._h, C.byref(ms)), "sgm_speckle_time")
         return ms.value
 
+    # ---- score: display maps and the error metric on the device (src/StereoMatch.cpp:181-185, 248-249, 275-309) ----
+    def set_truth(self, gt, mask=None):
+        """The dataset's ground truth and (optional) error mask, H x W uint8 each: uploaded once, kept until replaced or
+        clear_truth() (psm_score_set_truth)."""
+        gt = np.asarray(gt)
+        mask = None if mask is None else np.asarray(mask)
+        for a in (gt, mask):
+            if a is not None and (a.shape != (self.hei, self.wid) or a.dtype != np.uint8):
+                raise ValueError("set_truth: gt and mask must be H x W uint8 planes of the size DispEst was built for")
+        if mask is not None and (mask.strides != gt.strides or gt.strides[1] != 1):
+            gt, mask = np.ascontiguousarray(gt), np.ascontiguousarray(mask)
+        elif gt.strides[1] != 1:
+            gt = np.ascontiguousarray(gt)
+        self._ck(self._lib.psm_score_set_truth(self._h, _ptr(gt), _ptr(mask), gt.strides[0]), "set_truth")
+
+    def clear_truth(self):
+        self._ck(self._lib.psm_score_clear_truth(self._h), "clear_truth")
+
+    def set_score_params(self, scale_factor: int = 4, error_threshold: int = 4, mask_mode: int = capi.PSM_MASK_NONOCC):
+        """scale_factor 1..255, error_threshold 0..255, mask_mode capi.PSM_MASK_NONE | PSM_MASK_NONOCC | PSM_MASK_DISC
+        (psm_score_set_params; a new object: 4, 4, NONOCC)."""
+        self._ck(self._lib.psm_score_set_params(self._h, int(scale_factor), int(error_threshold), int(mask_mode)),
+                 "set_score_params")
+
+    def Score_GPU(self, source: int = capi.PSM_SCORE_GIF):
+        """psm_score: the display map(s) and the reference's error record of the current result, on the device.  source:
+        capi.PSM_SCORE_GIF (the current 8-bit maps), PSM_SCORE_SGM (the int16 map of the last SGBM_GPU through the reference's
+        min-max display conversion) or PSM_SCORE_SGM_INT (its integer disparities scaled like the GIF maps).
+        -> dict: the record's integers (min_val, max_val, pixels, bad, err_sum, unit, flags) and bp_percent / avg_err derived from
+        them; under PSM_OPT_ASYNC None - score_wait() collects the record."""
+        rec = capi.Score()
+        self._ck(self._lib.psm_score(self._h, int(source), C.byref(rec)), "Score_GPU")
+        return None if self.options.get(capi.PSM_OPT_ASYNC) else rec.as_dict()
+
+    def score_wait(self):
+        """The record of the Score_GPU enqueued under PSM_OPT_ASYNC."""
+        rec = capi.Score()
+        self._ck(self._lib.psm_score_wait(self._h, C.byref(rec)), "score_wait")
+        return rec.as_dict()
+
+    def score_maps(self, right: bool = False):
+        """(left display, error plane) of the last Score_GPU, H x W uint8 each; right=True: (left, right, error) - the right
+        display exists for PSM_SCORE_GIF only."""
+        l, e = np.empty((self.hei, self.wid), np.uint8), np.empty((self.hei, self.wid), np.uint8)
+        r = np.empty((self.hei, self.wid), np.uint8) if right else None
+        self._ck(self._lib.psm_score_download(self._h, _ptr(l), _ptr(r), _ptr(e), self.wid), "score_maps")
+        return (l, r, e) if right else (l, e)
+
+    def score_time(self):
+        """Device ms of the launches of the last Score_GPU (score_batch: of all pairs, on its first object); needs PSM_OPT_PROFILE."""
+        ms = C.c_double()
+        self._ck(self._lib.psm_score_time(self._h, C.byref(ms)), "score_time")
+        return ms.value
+
+    def upload_sgm_map(self, disp):
+        """Test hook (psm_score_upload_sgm_map): the SGM sources of Score_GPU read this H x W int16 map from now on; None: the
+        map of the last SGBM_GPU again."""
+        if disp is None:
+            self._ck(self._lib.psm_score_upload_sgm_map(self._h, None, 0), "upload_sgm_map")
+            return
+        disp = np.ascontiguousarray(disp)
+        if disp.shape != (self.hei, self.wid) or disp.dtype != np.int16:
+            raise ValueError("upload_sgm_map: disp must be an H x W int16 map of the size DispEst was built for")
+        self._ck(self._lib.psm_score_upload_sgm_map(self._h, _ptr(disp), disp.strides[0]), "upload_sgm_map")
+
     # ---- extensions beyond the reference surface --------------------------------------------
     def LRCheck_GPU(self) -> int:
         """PP lrCheck (src/PP.cpp:17-50) on the device -> lValid / rValid."""
@@ -581,6 +646,19 @@ def joint_wmf_batch_device(des, radius: int = 0, sigma: float = 0.0, n_clusters:
                des[0]._h, "joint_wmf_batch")
 
 
+def score_batch(des, source: int = capi.PSM_SCORE_GIF):
+    """Score_GPU of several DispEst objects of one geometry in one set of launches (psm_score_batch): each object's current result
+    against its own truth -> the list of Score_GPU's dicts.  Every object afterwards behaves as after its own Score_GPU
+    (score_maps()); under PSM_OPT_ASYNC on des[0]: None, every object's score_wait() collects its record."""
+    des = list(des)
+    if not des:
+        return []
+    arr = (C.c_void_p * len(des))(*[d._h for d in des])
+    recs = (capi.Score * len(des))()
+    capi.check(des[0]._lib.psm_score_batch(arr, len(des), int(source), recs), des[0]._h, "score_batch")
+    return None if des[0].options.get(capi.PSM_OPT_ASYNC) else [r.as_dict() for r in recs]
+
+
 def share_streams(des):
     """The DispEst objects of a batch run on one compute stream and one copy stream each way (psm_share_streams) - call once
     before a frame loop over batches."""
@@ -606,11 +684,13 @@ class FrameRing:
     """
 
     def __init__(self, l, r, d: int, frames: int = 2, *, dtype: str = "f32", device: int = 0, lr_check: bool = False,
-                 seg_rows: int = 0):
+                 seg_rows: int = 0, truth=None, scale_factor: int = 4, error_threshold: int = 4):
         """Every context is told PSM_OPT_FRAMES_IN_FLIGHT = frames: the planner of the fused launches then cuts them for a shared
         device (450 x 375 x 64: 0.207 ms per frame against 0.22-0.23 without the hint; no result changes).  seg_rows > 0:
         PSM_OPT_SEG_ROWS of every context on top of that (round 5's first finding - one segment per launch, seg_rows = image height
-        - is what the hint replaced: profiles/r05/exp_plan_model.txt)."""
+        - is what the hint replaced: profiles/r05/exp_plan_model.txt).
+        truth = (gt, mask or None): every frame's left map is scored against it on the device behind its last stage (Score_GPU,
+        PSM_SCORE_GIF, with scale_factor / error_threshold); push / flush then return (lmap, rmap, score) instead of (lmap, rmap)."""
         if frames < 1:
             raise ValueError("FrameRing: frames must be >= 1")
         self.ctx = [DispEst(l, r, d, dtype=dtype, device=device) for _ in range(frames)]
@@ -622,6 +702,12 @@ class FrameRing:
         self._n = 0
         self._busy = [False] * frames
         self._lrc = lr_check
+        self._score = truth is not None
+        if self._score:
+            for c in self.ctx:
+                c.set_truth(truth[0], truth[1])
+                c.set_score_params(scale_factor, error_threshold,
+                                   capi.PSM_MASK_NONOCC if truth[1] is not None else capi.PSM_MASK_NONE)
 
     def setRectification(self, rect):
         """Every context of the ring rectifies the frames push_frame gives it (DispEst.setRectification)."""
@@ -641,7 +727,7 @@ class FrameRing:
         c = self.ctx[i]
         out = None
         if self._busy[i]:
-            out = tuple(m.copy() for m in c.download_maps_wait())
+            out = self._collect(c)
         set_input(c)
         c.CostConst_GPU()
         c.CostFilter_GPU()
@@ -649,8 +735,14 @@ class FrameRing:
         if self._lrc:
             c.LRCheck_device()
         c.download_maps_async()
+        if self._score:
+            c.Score_GPU(capi.PSM_SCORE_GIF)      # (behind the download's start: the copy of the maps does not wait for the score)
         self._busy[i] = True
         return out
+
+    def _collect(self, c):
+        maps = tuple(m.copy() for m in c.download_maps_wait())
+        return maps + (c.score_wait(),) if self._score else maps
 
     def flush(self):
         out = []
@@ -658,7 +750,7 @@ class FrameRing:
         for k in range(F):
             i = (self._n + k) % F
             if self._busy[i]:
-                out.append(tuple(m.copy() for m in self.ctx[i].download_maps_wait()))
+                out.append(self._collect(self.ctx[i]))
                 self._busy[i] = False
         return out
 

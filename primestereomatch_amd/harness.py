@@ -8,7 +8,7 @@ import numpy as np
 
 from . import capi
 from . import dispest
-from .dispest import DispEst, sgbm_batch
+from .dispest import DispEst, sgbm_batch, score_batch
 
 MASK_NONE, MASK_NONOCC, MASK_DISC = 0, 1, 2   # include/StereoMatch.h
 
@@ -31,7 +31,7 @@ def error_vs_ground_truth(lDisMap, gt, mask, maxDis, scale_factor, error_thresho
 
 
 def compute(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, error_threshold=4, threads=8,
-            dtype="f32", post_process=True, verbose=False, subsample_rate=0, process_dm=False, joint_wmf=False):
+            dtype="f32", post_process=True, verbose=False, subsample_rate=0, process_dm=False, joint_wmf=False, device_tail=False):
     """One frame of STEREO_GIF on the accelerator path.  l_bgr/r_bgr: H x W x 3 uint8 (imread order).
     subsample_rate 0: full guided filter (CostFilter_GPU, the reference's 'm' branch); 2/4/8: the Fast Guided
     Filter variant (CostFilter_FGF, the snapshot's live branch, src/StereoMatch.cpp:213) on the device.
@@ -40,7 +40,9 @@ def compute(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, error_t
     processDM, wgtMedian is its dead-code predecessor of JointWMF) - the maps before it stay in lDisMap_raw / rDisMap_raw.
     joint_wmf: then run the snapshot's live processDM body, JointWMF::filter on both maps (src/PP.cpp:417-422), on the device
     (DispEst.JointWMF_GPU) and score the filtered left map, as StereoMatch::compute does after PostProcess
-    (src/StereoMatch.cpp:225-311); the selected maps stay in lDisMap_raw / rDisMap_raw."""
+    (src/StereoMatch.cpp:225-311); the selected maps stay in lDisMap_raw / rDisMap_raw.
+    device_tail: the display map and the error metric come from the device (DispEst.Score_GPU) instead of the numpy tail below -
+    the same record, key for key."""
     out = {}
     lFrame = np.ascontiguousarray(l_bgr)
     rFrame = np.ascontiguousarray(r_bgr)
@@ -51,17 +53,18 @@ def compute(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, error_t
     with DispEst(lFrame, rFrame, maxDis, threads, True, dtype=dtype) as SMDE:
         SMDE.setInputImages(lFrame, rFrame)
         _run_stages(SMDE, out, threads, subsample_rate, post_process, process_dm, joint_wmf)
-    return _finish(out, maxDis, gt, mask, scale_factor, error_threshold, verbose)
+        tail = _device_tail([SMDE], [gt], [mask], scale_factor, error_threshold, capi.PSM_SCORE_GIF)[0] if device_tail else None
+    return _finish(out, maxDis, gt, mask, scale_factor, error_threshold, verbose, tail)
 
 
 def compute_batch(pairs, maxDis=64, gts=None, masks=None, scale_factor=4, error_threshold=4, dtype="f32", post_process=True,
-                  joint_wmf=False, verbose=False):
+                  joint_wmf=False, verbose=False, device_tail=False):
     """compute() for a list of (l_bgr, r_bgr) uint8 pairs of one size in shared launches: the reference's loop over pairs and
     datasets (src/main.cpp:64-73, src/StereoMatch.cpp:528-609) on the live STEREO_GIF branch.  dispest.compute_batch (CostConst +
     CostFilter + DispSelect of all pairs), then per object the L-R check when post_process, then dispest.joint_wmf_batch when
     joint_wmf (the live processDM body on every pair's maps, the clustering chains of all images side by side).  gts / masks: one
     per pair (or None).  -> a list of compute's records; the stage times are each object's (a batch's wall time is charged to
-    every member)."""
+    every member).  device_tail: display maps and metric of all pairs from the device in one set of launches (dispest.score_batch)."""
     if not pairs:
         return []
     frames = []
@@ -89,10 +92,11 @@ def compute_batch(pairs, maxDis=64, gts=None, masks=None, scale_factor=4, error_
             out["dispsel_ms"] = d.stage_time_us(capi.PSM_STAGE_DISPSEL) / 1000
             out["pp_ms"] = d.stage_time_us(capi.PSM_STAGE_PP) / 1000
             out["lDisMap"], out["rDisMap"] = d.lDisMap.copy(), d.rDisMap.copy()
+        tails = _device_tail(des, gts, masks, scale_factor, error_threshold, capi.PSM_SCORE_GIF) if device_tail else [None] * len(des)
     finally:
         for d in des:
             d.close()
-    return [_finish(out, maxDis, gts[i] if gts else None, masks[i] if masks else None, scale_factor, error_threshold, verbose)
+    return [_finish(out, maxDis, gts[i] if gts else None, masks[i] if masks else None, scale_factor, error_threshold, verbose, tails[i])
             for i, out in enumerate(outs)]
 
 
@@ -114,13 +118,15 @@ def compute_video(vFrame, rectification, maxDis=64, gt=None, mask=None, scale_fa
     return _finish(out, maxDis, gt, mask, scale_factor, error_threshold, verbose)
 
 
-def compute_sgbm(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, error_threshold=4, verbose=False, **params):
+def compute_sgbm(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, error_threshold=4, verbose=False, device_tail=False,
+                 **params):
     """One frame of STEREO_SGBM (src/StereoMatch.cpp:169-187, 275-309) on the device: l_bgr / r_bgr H x W x 3, uint8 or float32
     scaled by 1/255 (quantised on the device as lFrame.convertTo(lFrame, CV_8U, 255) does); params: DispEst.SGBM_GPU's, forwarded
     as they are - the reference's whole configuration is pre_filter_cap=63, speckle_window_size=100, speckle_range=32 (the
     defaults: SAD cost, no speckle filter); min_disparity / num_disparities choose another range than [0, maxDis), up to 1024
     disparities (the display conversion works from the map's own minimum and maximum).
-    -> disp16 (imgDisparity16S), lDispMap (the display map), the reference's error metric on it, and bp_percent_int."""
+    -> disp16 (imgDisparity16S), lDispMap (the display map), the reference's error metric on it, and bp_percent_int.
+    device_tail: display map and both metrics from the device (DispEst.Score_GPU, PSM_SCORE_SGM and PSM_SCORE_SGM_INT)."""
     out = {}
     lFrame, rFrame = np.ascontiguousarray(l_bgr), np.ascontiguousarray(r_bgr)
     with DispEst(lFrame, rFrame, maxDis, 8, True) as SMDE:
@@ -129,13 +135,16 @@ def compute_sgbm(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, er
         out["cost_ms"], out["paths_ms"], out["select_ms"] = SMDE.sgm_times()
         if params.get("speckle_window_size", 0) > 0:
             out["speckle_ms"] = SMDE.sgm_speckle_time()
-    return _finish_sgbm(out, maxDis, gt, mask, scale_factor, error_threshold, verbose)
+        tail = _device_tail_sgbm([SMDE], [gt], [mask], scale_factor, error_threshold)[0] if device_tail else None
+    return _finish_sgbm(out, maxDis, gt, mask, scale_factor, error_threshold, verbose, tail)
 
 
-def compute_sgbm_batch(pairs, maxDis=64, gts=None, masks=None, scale_factor=4, error_threshold=4, verbose=False, **params):
+def compute_sgbm_batch(pairs, maxDis=64, gts=None, masks=None, scale_factor=4, error_threshold=4, verbose=False, device_tail=False,
+                       **params):
     """compute_sgbm for a list of (l_bgr, r_bgr) pairs of one size and depth in shared launches (dispest.sgbm_batch): the
     reference's loop over pairs and datasets (src/main.cpp:64-73, src/StereoMatch.cpp:528-609).  gts / masks: one per pair (or
-    None).  -> a list of compute_sgbm's records; the times are the batch's divided by the number of pairs."""
+    None).  -> a list of compute_sgbm's records; the times are the batch's divided by the number of pairs.  device_tail: display
+    maps and both metrics of all pairs from the device (dispest.score_batch)."""
     pairs = [(np.ascontiguousarray(l), np.ascontiguousarray(r)) for l, r in pairs]
     if not pairs:
         return []
@@ -145,6 +154,7 @@ def compute_sgbm_batch(pairs, maxDis=64, gts=None, masks=None, scale_factor=4, e
         maps = sgbm_batch(des, **params)
         times = [t / len(des) for t in des[0].sgm_times()]
         spk = des[0].sgm_speckle_time() / len(des) if params.get("speckle_window_size", 0) > 0 else None
+        tails = _device_tail_sgbm(des, gts, masks, scale_factor, error_threshold) if device_tail else [None] * len(des)
     finally:
         for d in des:
             d.close()
@@ -154,11 +164,42 @@ def compute_sgbm_batch(pairs, maxDis=64, gts=None, masks=None, scale_factor=4, e
         if spk is not None:
             out["speckle_ms"] = spk
         outs.append(_finish_sgbm(out, maxDis, gts[i] if gts else None, masks[i] if masks else None, scale_factor, error_threshold,
-                                 verbose))
+                                 verbose, tails[i]))
     return outs
 
 
-def _finish_sgbm(out, maxDis, gt, mask, scale_factor, error_threshold, verbose):
+def _device_tail(des, gts, masks, scale_factor, error_threshold, source):
+    """The display map and the error record of every object's current result from the device: truth and parameters to each
+    object, one score_batch -> [(display map, record)]."""
+    for i, d in enumerate(des):
+        gt, mask = (gts[i] if gts else None), (masks[i] if masks else None)
+        d.set_score_params(scale_factor, error_threshold, MASK_NONOCC if mask is not None else MASK_NONE)
+        if gt is not None:
+            d.set_truth(np.asarray(gt, np.uint8), None if mask is None else np.asarray(mask, np.uint8))
+        else:
+            d.clear_truth()
+    recs = score_batch(des, source)
+    return [(d.score_maps()[0], rec) for d, rec in zip(des, recs)]
+
+
+def _device_tail_sgbm(des, gts, masks, scale_factor, error_threshold):
+    """... of STEREO_SGBM: the reference's min-max display conversion and its metric, then the integer-disparity figure."""
+    tails = _device_tail(des, gts, masks, scale_factor, error_threshold, capi.PSM_SCORE_SGM)
+    ints = score_batch(des, capi.PSM_SCORE_SGM_INT)
+    return [(disp, rec, rint) for (disp, rec), rint in zip(tails, ints)]
+
+
+def _from_record(out, rec):
+    out.update({"bp_percent": rec["bp_percent"], "avg_err": rec["avg_err"], "bad_pixels": rec["bad"]})
+
+
+def _finish_sgbm(out, maxDis, gt, mask, scale_factor, error_threshold, verbose, tail=None):
+    if tail is not None:
+        out["lDispMap"] = tail[0]
+        if gt is not None:
+            _from_record(out, tail[1])
+            out["bp_percent_int"] = tail[2]["bp_percent"]
+        return _report_sgbm(out, gt, verbose)
     d16 = out["disp16"]
     # minMaxLoc(imgDisparity16S, &minVal, &maxVal); imgDisparity16S.convertTo(lDispMap, CV_8U, 255/(maxVal - minVal));
     # lDispMap = (lDispMap/4) * scale_factor.  OpenCV's rounding of both steps: the factor is formed in double, but convertTo of a
@@ -178,6 +219,10 @@ def _finish_sgbm(out, maxDis, gt, mask, scale_factor, error_threshold, verbose):
         # maps.  bp_percent above is NOT comparable - the reference stretches the SGBM map by 255 / (maxVal - minVal) of the
         # frame at hand (min-max scaling, then / 4), so its grey levels are not disparity * scale_factor.
         out["bp_percent_int"] = error_vs_ground_truth(np.maximum(d16, 0) >> 4, gt, mask, maxDis, scale_factor, error_threshold)[0]
+    return _report_sgbm(out, gt, verbose)
+
+
+def _report_sgbm(out, gt, verbose):
     if verbose:
         print("STEREO SGBM Times:")
         print("Cost Time:\t %4.3f ms\nPaths Time:\t %4.3f ms\nSelect Time:\t %4.3f ms" % (out["cost_ms"], out["paths_ms"], out["select_ms"]))
@@ -215,11 +260,16 @@ def _run_stages(SMDE, out, threads, subsample_rate, post_process, process_dm, jo
     out["lDisMap"], out["rDisMap"] = SMDE.lDisMap.copy(), SMDE.rDisMap.copy()
 
 
-def _finish(out, maxDis, gt, mask, scale_factor, error_threshold, verbose):
-    out["lDispMap"] = np.clip(out["lDisMap"].astype(np.int32) * scale_factor, 0, 255).astype(np.uint8)
-    if gt is not None:
-        bp, avg, bad, emap = error_vs_ground_truth(out["lDisMap"], gt, mask, maxDis, scale_factor, error_threshold)
-        out.update({"bp_percent": bp, "avg_err": avg, "bad_pixels": bad})
+def _finish(out, maxDis, gt, mask, scale_factor, error_threshold, verbose, tail=None):
+    if tail is not None:
+        out["lDispMap"] = tail[0]
+        if gt is not None:
+            _from_record(out, tail[1])
+    else:
+        out["lDispMap"] = np.clip(out["lDisMap"].astype(np.int32) * scale_factor, 0, 255).astype(np.uint8)
+        if gt is not None:
+            bp, avg, bad, emap = error_vs_ground_truth(out["lDisMap"], gt, mask, maxDis, scale_factor, error_threshold)
+            out.update({"bp_percent": bp, "avg_err": avg, "bad_pixels": bad})
     if verbose:
         print("STEREO GIF Module Times:")
         print("CVC Time:\t %4.2f ms" % out["cvc_ms"])

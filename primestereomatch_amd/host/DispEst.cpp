@@ -215,6 +215,34 @@ int DispEst::JointWMF_GPU()
     return hipUtil::api().joint_wmf(ctx[0], 0, 0.f, 0, 0, lDisMap.data, rDisMap.data, lDisMap.step);
 }
 
+int DispEst::setGroundTruth(const Mat &gt, const Mat *mask)
+{
+    if (ctx.empty()) return 1;
+    if (gt.rows != hei || gt.cols != wid || gt.channels != 1 || gt.depth != PSM_8U ||
+        (mask && (mask->rows != hei || mask->cols != wid || mask->channels != 1 || mask->depth != PSM_8U || mask->step != gt.step))) {
+        fprintf(stderr, "DE: setGroundTruth wants H x W CV_8UC1 planes of one step\n");
+        return 1;
+    }
+    return hipUtil::api().score_set_truth(ctx[0], gt.data, mask ? mask->data : nullptr, gt.step);
+}
+
+int DispEst::setScoreParams(int scaleFactor, int errorThreshold, int maskMode)
+{
+    if (ctx.empty()) return 1;
+    return hipUtil::api().score_set_params(ctx[0], scaleFactor, errorThreshold, maskMode);
+}
+
+int DispEst::Score(int source, struct psm_score *rec, Mat *lDisp, Mat *eDisp)
+{
+    if (ctx.empty() || !rec) return 1;
+    if (hipUtil::api().score(ctx[0], source, rec)) return 1;      // (several devices: ctx[0] holds the gathered maps)
+    for (Mat *m : {lDisp, eDisp})
+        if (m && (m->rows != hei || m->cols != wid || m->channels != 1 || m->depth != PSM_8U)) *m = Mat::zeros(hei, wid, 1, PSM_8U);
+    if (!lDisp && !eDisp) return 0;
+    return hipUtil::api().score_download(ctx[0], lDisp ? lDisp->data : nullptr, nullptr, eDisp ? eDisp->data : nullptr,
+                                         lDisp ? lDisp->step : eDisp->step);
+}
+
 int DispEst::setSGBMParams(int blockSize, int P1, int P2, int uniquenessRatio, int disp12MaxDiff)
 {
     if (ctx.empty()) return 1;

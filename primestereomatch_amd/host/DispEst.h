@@ -128,6 +128,19 @@ public:
     // its objects.
     int setSGBMRange(int minDisparity, int numDisparities);
 
+    // The steps of StereoMatch::compute behind the maps, on the device (psm_score): setGroundTruth uploads the dataset's ground truth
+    // and (mask non-NULL) error mask once, H x W CV_8UC1 each; setScoreParams: scale_factor, error_threshold, PSM_MASK_NONE / NONOCC /
+    // DISC (a new object: 4, 4, NONOCC).  Score writes the display map of `source` - PSM_SCORE_GIF: the current lDisMap as
+    // convertTo(CV_8U, scale_factor) makes it (src/StereoMatch.cpp:248); PSM_SCORE_SGM: the map of the last SGBM_GPU through minMaxLoc,
+    // convertTo, / 4, * scale_factor (:181-185); PSM_SCORE_SGM_INT: its integer disparities scaled like the GIF maps - and the error
+    // record of :275-309 against the truth; lDisp / eDisp (may be NULL; resized) receive the display map and the error plane.
+    // scoreBP / scoreAvgErr: the two figures of the reference's "%BP = ... Avg Err = ..." line from the record's integers.
+    int setGroundTruth(const Mat &gt, const Mat *mask);
+    int setScoreParams(int scaleFactor, int errorThreshold, int maskMode);
+    int Score(int source, struct psm_score *rec, Mat *lDisp = nullptr, Mat *eDisp = nullptr);
+    static double scoreBP(const struct psm_score &r) { return 100.0 * r.bad / r.pixels; }
+    static double scoreAvgErr(const struct psm_score &r) { return r.unit ? ((double)r.err_sum / r.pixels) / r.unit : 0.0; }
+
     // Frame loop (src/main.cpp:64-73) with the PCIe legs next to the kernels (single-device hosts): one call per frame -
     // CostConst (adopts the pair staged by the previous call), stages `next` pair (may be NULL at the end of the stream: its
     // Mats are free again on return), CostFilter, DispSelect on the device, hands over the PREVIOUS frame's maps in

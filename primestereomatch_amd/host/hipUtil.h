@@ -60,6 +60,11 @@ struct HipApi {
     int (*sgm_set_mode)(psm_ctx *, int) = nullptr;
     int (*sgm_set_range)(psm_ctx *, int, int) = nullptr;
     int (*joint_wmf_batch)(psm_ctx *const *, int, int, float, int, int) = nullptr;
+    // score: display maps and the error metric against ground truth
+    int (*score_set_truth)(psm_ctx *, const uint8_t *, const uint8_t *, size_t) = nullptr;
+    int (*score_set_params)(psm_ctx *, int, int, int) = nullptr;
+    int (*score)(psm_ctx *, int, struct psm_score *) = nullptr;
+    int (*score_download)(psm_ctx *, uint8_t *, uint8_t *, uint8_t *, size_t) = nullptr;
 };
 
 class hipUtil {

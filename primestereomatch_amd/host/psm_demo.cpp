@@ -1,6 +1,10 @@
 // psm_demo - headless counterpart of the reference's StereoMatch::compute accelerator branch
 // (src/StereoMatch.cpp:193-262): raw B,G,R uint8 pair in, four timed stages, raw uint8 maps out.
-//   psm_demo <left.raw> <right.raw> <W> <H> <maxDis> <out_prefix> [ndev] [f32|u8] [float_input] [fgf_rate] [pp] [frames] [batch] [ring] [sgbm|sgbm_ref]
+//   psm_demo <left.raw> <right.raw> <W> <H> <maxDis> <out_prefix> [ndev] [f32|u8] [float_input] [fgf_rate] [pp] [frames] [batch] [ring] [sgbm|sgbm_ref|-] [gt.raw] [mask.raw|-]
+// gt.raw (the 16th argument; W x H bytes, mask.raw likewise): the left map - after pp, if given - is scored on the device
+// (DispEst::Score: scale_factor 4, error_threshold 4, the non-occluded mask if one is given) and the reference's line
+// "%BP = ... Avg Err = ..." (src/StereoMatch.cpp:306) is printed from the device record; the display map and the error plane go to
+// <out>_ldisp_disp.raw / <out>_edisp.raw; together with sgbm / sgbm_ref the same for the SGBM map (<out>_sgbm_disp.raw)
 // sgbm: the 15th argument, the word "sgbm": additionally run the second algorithm (DispEst::SGBM_GPU: the STEREO_SGBM branch,
 // src/StereoMatch.cpp:169-187) on the pair, print its three device times and dump the int16 map as <out>_sgbm16.raw (the SAD
 // cost, no speckle filter); the word "sgbm_ref": the same with the whole configuration of setupOpenCVSGBM (:639-660) -
@@ -47,7 +51,7 @@ static bool dump(const std::string &path, const unsigned char *p, size_t n)
 int main(int argc, char **argv)
 {
     if (argc < 7) {
-        fprintf(stderr, "usage: %s left.raw right.raw W H maxDis out_prefix [ndev] [f32|u8] [float_input] [fgf_rate] [pp] [frames] [batch] [ring] [sgbm|sgbm_ref]\n", argv[0]);
+        fprintf(stderr, "usage: %s left.raw right.raw W H maxDis out_prefix [ndev] [f32|u8] [float_input] [fgf_rate] [pp] [frames] [batch] [ring] [sgbm|sgbm_ref|-] [gt.raw] [mask.raw|-]\n", argv[0]);
         return 2;
     }
     const int W = atoi(argv[3]), H = atoi(argv[4]), D = atoi(argv[5]);
@@ -62,7 +66,13 @@ int main(int argc, char **argv)
     const int nring = argc > 14 ? atoi(argv[14]) : 0;
     const bool sgbm_ref = argc > 15 && !strcmp(argv[15], "sgbm_ref");
     const bool sgbm = sgbm_ref || (argc > 15 && !strcmp(argv[15], "sgbm"));
-    std::vector<unsigned char> lraw, rraw;
+    const char *gt_path = argc > 16 ? argv[16] : nullptr;
+    const char *mask_path = argc > 17 && strcmp(argv[17], "-") ? argv[17] : nullptr;
+    std::vector<unsigned char> lraw, rraw, gtraw, maskraw;
+    if (gt_path && (!slurp(gt_path, gtraw, (size_t)W * H) || (mask_path && !slurp(mask_path, maskraw, (size_t)W * H)))) {
+        fprintf(stderr, "psm_demo: cannot read the ground truth / mask\n");
+        return 2;
+    }
     if (!slurp(argv[1], lraw, (size_t)W * H * 3) || !slurp(argv[2], rraw, (size_t)W * H * 3)) {
         fprintf(stderr, "psm_demo: cannot read the input pair\n");
         return 2;
@@ -105,6 +115,15 @@ int main(int argc, char **argv)
         if (pp == 2 ? SMDE.JointWMF_GPU() : SMDE.ProcessDM_GPU()) return 5;   // pp 1: lrCheck + fillInv + wgtMedian (src/PP.cpp:405-410,
                                                                               // commented out in the reference); pp 2: JointWMF
         ok = dump(out + "_ldisp_pp.raw", SMDE.lDisMap.data, (size_t)W * H) && dump(out + "_rdisp_pp.raw", SMDE.rDisMap.data, (size_t)W * H);
+    }
+    if (ok && gt_path) {
+        psm::Mat gt(H, W, 1, psm::PSM_8U, gtraw.data()), mask(H, W, 1, psm::PSM_8U, maskraw.data()), disp, emap;
+        struct psm_score rec;
+        if (SMDE.setGroundTruth(gt, mask_path ? &mask : nullptr) || SMDE.setScoreParams(4, 4, mask_path ? PSM_MASK_NONOCC : PSM_MASK_NONE) ||
+            SMDE.Score(PSM_SCORE_GIF, &rec, &disp, &emap))
+            return 5;
+        printf("%%BP = %.2f%% \t Avg Err = %.2f\n", psm::DispEst::scoreBP(rec), psm::DispEst::scoreAvgErr(rec));
+        ok = dump(out + "_ldisp_disp.raw", disp.data, (size_t)W * H) && dump(out + "_edisp.raw", emap.data, (size_t)W * H);
     }
     if (ok && frames > 0 && ndev == 1 && !fgf_rate) {
         SMDE.setInputImages(l, r);
@@ -167,6 +186,13 @@ int main(int argc, char **argv)
             printf("Speckle Time:\t %4.3f ms\n", spk);
         }
         ok = dump(out + "_sgbm16.raw", (const unsigned char *)d16.data(), d16.size() * sizeof(int16_t));
+        if (ok && gt_path) {      // (the truth is already on the device)
+            psm::Mat disp;
+            struct psm_score rec;
+            if (SMDE.Score(PSM_SCORE_SGM, &rec, &disp, nullptr)) return 5;
+            printf("%%BP = %.2f%% \t Avg Err = %.2f\n", psm::DispEst::scoreBP(rec), psm::DispEst::scoreAvgErr(rec));
+            ok = dump(out + "_sgbm_disp.raw", disp.data, (size_t)W * H);
+        }
         if (ok && batch > 1 && ndev == 1) {
             std::vector<psm::DispEst *> des;
             bool set = true;
