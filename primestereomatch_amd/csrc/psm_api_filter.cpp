@@ -186,7 +186,7 @@ int enqueue_select(psm_ctx *c, const PcPairs &P, const SelPlan &sp)
     if (sp.maps && !P.tab && maps_writable(c)) return 1;
     {
         Prof p(c, PSM_K_WTA);
-        launch_chunk_min2sides(c->stream, c->march, P, c->W, c->H, sp.n1, sp.maps);
+        launch_chunk_min2sides(c->stream, c->march, P, c->W, c->H, sp.n1, sp.maps, c->d0, sp.two_phase ? 1 : 0, sp.S);
     }
     if (sp.n2 > 0) {
         Prof p(c, PSM_K_CVF_F);

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "psm_live.h"
 
 namespace psm {
 
@@ -108,7 +109,8 @@ void launch_chunk_min(hipStream_t s, March m, int W, int H, int Dloc, void *scra
 void launch_cvf_select2(hipStream_t s, March m, const PcPairs &P, bool u8, int W, int H, int Dloc, int d_begin, unsigned long long *ts,
                         int sel, int step);
 // ... their reduction to each pair's keys; to_maps: the maps as well
-void launch_chunk_min2sides(hipStream_t s, March m, const PcPairs &P, int W, int H, int Dloc, bool to_maps);
+// d_begin, (sel, step): as given to launch_cvf_select2 - chunks it did not walk (psm_live.h) are not read
+void launch_chunk_min2sides(hipStream_t s, March m, const PcPairs &P, int W, int H, int Dloc, bool to_maps, int d_begin, int sel, int step);
 // ... key form: continues from the minima each pair's keys hold (the second phase of the two-phase selection)
 void launch_cvf_select_keys2(hipStream_t s, March m, const PcPairs &P, bool u8, int W, int H, int Dloc, int d_begin,
                              unsigned long long *ts, int sel, int step);

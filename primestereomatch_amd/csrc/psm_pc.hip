@@ -36,6 +36,7 @@
 #include "psm_kernels.h"
 #include "psm_cost.h"
 #include "psm_dev.h"
+#include "psm_live.h"
 #include "../../include/primesm_hip.h"
 
 #include <mutex>
@@ -121,15 +122,38 @@ struct PcSide {
 // (i -> i * step); sel 2 the others (i -> (i / (step-1)) * step + i % (step-1) + 1).  Two-phase selection: a first launch
 // reduces every step-th slice to the key plane, a MODE 2 launch then runs the rest against that plane - its consumer lanes
 // find a tight bound there and issue an atomic only a few times per pixel.
+// Select forms: the work items of a launch are its LIVE (column group, slice) combinations only (psm_live.h; plane form: chunks
+// with a live slice).  A group's items are indices lo .. lo + count - 1 in launch order (slices, or chunks); count = `full` except
+// for a run of `nshort` groups starting at group `pre` (left volume: the first groups, right volume: the last ones), whose counts
+// are in `cnt`.  Per volume ([0]: blockIdx.y == 0).  Built by pc_live.  k_cvf_pc enumerates from this table and k_chunk_min reads
+// the chunks this table names (pc_live_count), so the plane form's table must name exactly the chunks that hold a live slice:
+// tests/test_border_skip.py compares it with the predicate group by group.
+constexpr int PC_LIVE_MAX = 6;     // D <= 256 and groups of 50+ columns: at most 5 groups have dead slices (pc_live falls back to "all" beyond)
+struct PcLive {
+    int on;                        // 0: every item enumerated, nothing skipped
+    int lo, full;
+    int pre[2], nshort[2], tot[2]; // tot: items of one segment's groups together
+    int cnt[2][PC_LIVE_MAX];
+};
+// items of column group g of volume `side`: indices lo .. lo + count - 1
+__host__ __device__ __forceinline__ int pc_live_count(const PcLive &lv, int side, int g)
+{
+    const int k = g - (side ? lv.pre[1] : lv.pre[0]), ns = side ? lv.nshort[1] : lv.nshort[0];
+    int c = lv.full;
+#pragma unroll
+    for (int i = 0; i < PC_LIVE_MAX; ++i)
+        if (i == k && i < ns) c = side ? lv.cnt[1][i] : lv.cnt[0][i];
+    return c;
+}
 struct PcSel {
     int sel, step;
     int nxcd;      // XCDs of the device (blocks are dispatched round-robin over them)
-    int spread;    // key form: dispatch the slices of a pair in `spread` interleaved passes (0 / 1: ascending)
-    int n;         // ... over n slices
+    int spread;    // key form: dispatch a group's live slices in `spread` interleaved passes (0 / 1: ascending; pc_spread)
     unsigned long long rec_total;   // BATCH launches: float4 cost records per side in a pair's scratch (the disparities follow them)
     int dstep;     // global disparity of local slice i: d_begin + i * dstep (1: a contiguous range; psm_create_shard_strided: the rank count)
+    PcLive live;
 };
-__device__ __forceinline__ int pc_slice(const PcSel &o, int i)
+__device__ __forceinline__ int pc_spread(const PcSel &o, int n, int i)      // dispatch position i of a group's n (live) slices -> index in ascending order
 {
     // Key form: the workgroups of one (column group, segment) pair that run at the same time would be CONSECUTIVE slices - the
     // ones most likely to tie or nearly tie for a pixel's minimum, each deciding on a snapshot of the key that predates the
@@ -139,13 +163,13 @@ __device__ __forceinline__ int pc_slice(const PcSel &o, int i)
     if (o.spread > 1) {
         int r = 0, base = 0;
         for (; r < o.spread; ++r) {
-            const int cnt = (o.n - r + o.spread - 1) / o.spread;     // slices with index % spread == r
+            const int cnt = (n - r + o.spread - 1) / o.spread;       // slices with index % spread == r
             if (i < base + cnt) break;
             base += cnt;
         }
         i = (i - base) * o.spread + r;
     }
-    return o.sel == 1 ? i * o.step : (o.sel == 2 ? (i / (o.step - 1)) * o.step + i % (o.step - 1) + 1 : i);
+    return i;
 }
 
 // CVC = 0: the cost slice is read from `vin`.  CVC = 1 (left volume) / 2 (right volume): the cost volume is never
@@ -220,12 +244,13 @@ void k_cvf_pc(
     // (block b -> XCD b % nxcd): every XCD owns a contiguous range of (group, segment) pairs and walks the
     // chunks of one pair back to back, so the guidance rows its resident workgroups are reading (few
     // pairs, neighbouring rows, many slices) fit its 4 MB L2 instead of coming from the MALL.  Speed only.
-    const int nchunks = (Dloc + DC - 1) / DC;
     int id = blockIdx.x;
     const int npairs = ngroups * nsegs;               // (column group, segment) pairs
-    // work items (pair, chunk), pair-major; XCD x takes the x-th share of them: a contiguous range of pairs whose chunks
-    // run back to back, and equal work per XCD whatever the pair count
-    const int nitems = npairs * nchunks;
+    // live work items (pair, chunk), pair-major; XCD x takes the x-th share of them: a contiguous range of pairs whose chunks
+    // run back to back, and equal work per XCD whatever the pair count and however many items a pair has left (PcLive)
+    const PcLive &lv = dyn.live;
+    const int ltot = s1 ? lv.tot[1] : lv.tot[0];
+    const int nitems = nsegs * ltot;
     const int ipx = (nitems + dyn.nxcd - 1) / dyn.nxcd;
     const int xcd = id % dyn.nxcd, jj = id / dyn.nxcd;
     const int item = xcd * ipx + jj;
@@ -234,8 +259,31 @@ void k_cvf_pc(
         (void)__hip_atomic_fetch_min(ts, (unsigned long long)wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (blockIdx.x == 0 && blockIdx.y == 0) ts[2 * PC_TS_SLOTS] = (unsigned long long)MODE;
     }
-    const int pair = item / nchunks, ch = item % nchunks;
-    const int g = pair % ngroups, seg = pair / ngroups;
+    const int seg = item / ltot;
+    int g, gi = item - seg * ltot, gn = lv.full;      // column group, index among its items, their number
+    {
+        const int pre = s1 ? lv.pre[1] : lv.pre[0], ns = s1 ? lv.nshort[1] : lv.nshort[0];
+        if (gi < pre * lv.full) { g = gi / lv.full; gi -= g * lv.full; }
+        else {
+            gi -= pre * lv.full;
+            g = pre;
+            bool found = false;
+#pragma unroll
+            for (int k = 0; k < PC_LIVE_MAX; ++k) {
+                const int c = s1 ? lv.cnt[1][k] : lv.cnt[0][k];
+                if (!found && k < ns) {
+                    if (gi < c) { found = true; gn = c; }
+                    else { gi -= c; ++g; }
+                }
+            }
+            if (!found) { const int q = gi / lv.full; g += q; gi -= q * lv.full; }
+        }
+    }
+    const int pair = seg * ngroups + g;
+    // key form: the item is the group's live slice `sl0` (local slice of the context), dispatched in PC_KEY_SPREAD passes over the
+    // live ones; plane / storing form: its chunk `ch`
+    const int ch = lv.lo + gi;
+    const int sl0 = pc_sel_index(dyn.sel, dyn.step, MODE == 2 ? lv.lo + pc_spread(dyn, gn, gi) : ch);
     // (which hardware wave takes which role does not matter: swapping / interleaving the producer and consumer
     // waves, per workgroup or pseudo-randomly, changed nothing - the CU balances the SIMDs itself)
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;   // wave index in an SGPR: everything derived from it is scalar
@@ -261,12 +309,22 @@ void k_cvf_pc(
     // after the last slice.  The ring keeps counting batches across slices (rb): the producers are never more than two batches ahead
     // of what the consumers still read, within a slice as before and across the seam (slots rb+nbA, rb+nbA+1 are written while
     // rb+nbA-2, rb+nbA-1 are read).
-    const int nds = MODE == 1 ? min(DC, Dloc - ch * DC) : 1;
+    // Plane form: of the chunk's slices only [ds_lo, ds_hi) are walked - d = 0 (never a candidate) is skipped at the low end, the
+    // slices that repeat the border cost in every column of the group (psm_live.h) at the high end.  PcLive names only chunks
+    // that keep a slice, and k_chunk_min reads the chunks it names, so the return below is never taken (it guards the barriers
+    // against an empty loop, nothing else).  (Scalar, before the first barrier.)
+    int ds_lo = 0, ds_hi = MODE == 1 ? min(DC, Dloc - ch * DC) : 1;
+    if (MODE == 1 && lv.on) {
+        const PcOwn own = {1, d_begin, dyn.dstep, dyn.sel, dyn.step};
+        while (ds_lo < ds_hi && pc_dead_at(own, right, xg, xg + PC_COLS - 1, W, ch * DC + ds_lo)) ++ds_lo;
+        while (ds_hi > ds_lo && pc_dead_at(own, right, xg, xg + PC_COLS - 1, W, ch * DC + ds_hi - 1)) --ds_hi;
+        if (ds_lo >= ds_hi) return;
+    }
     bool first = true;                                // no slice processed yet: the plane holds nothing
     int rb = 0;                                       // ring slot of this slice's model batch 0
-    for (int ds = 0; ds < nds; ++ds) {                // ascending d
-    const int d = ch * DC + ds;
-    const bool last_slice = ds == nds - 1;
+    for (int ds = ds_lo; ds < ds_hi; ++ds) {          // ascending d
+    const int sl = MODE == 1 ? pc_sel_index(dyn.sel, dyn.step, ch * DC + ds) : sl0;   // local slice of the context
+    const bool last_slice = ds == ds_hi - 1;
     if (is_a) {
         // ---------------- producer: stage A ----------------
         // step s reads input row mstart-5+s; from step 8 on it yields model row mstart+(s-8)
@@ -275,8 +333,8 @@ void k_cvf_pc(
         const int xa = xa0 + lane;                    // model column of this lane
         const int xac = xa < 0 ? 0 : (xa > W - 1 ? W - 1 : xa);
         const bool mvalid = lane < PC_OUT_A;
-        const float *vd = vin + (size_t)pc_slice(dyn, d) * HW;
-        const int dg = d_begin + dyn.dstep * pc_slice(dyn, d);    // global disparity of this slice
+        const float *vd = vin + (size_t)sl * HW;
+        const int dg = d_begin + dyn.dstep * sl;      // global disparity of this slice
         // buildCV_left: partner x-d while x >= d; buildCV_right: partner x+d while x < W-d (src/CVC.cpp:135-146,165-176)
         const bool inb = right ? (ci < W - dg) : (ci >= dg);
         const int cpart = right ? min(ci + dg, W - 1) : max(ci - dg, 0);
@@ -415,7 +473,7 @@ void k_cvf_pc(
         mc = mc < 0 ? 0 : (mc > PC_MCOLS - 1 ? PC_MCOLS - 1 : mc);
         const int xb = xb0 + lane;                    // output column of this lane
         const int xbc = min(xb, W - 1);
-        float *od = vout + (MODE == 0 ? (size_t)pc_slice(dyn, d) * HW : 0);
+        float *od = vout + (MODE == 0 ? (size_t)sl * HW : 0);
         const int amax = 4 * nbA - 1;
         VTree t0 = {}, t1 = {}, t2 = {}, t3 = {};
         float o1x[4], o1y[4], o1z[4];                 // g1.xyz at (output row, output column), one batch ahead
@@ -447,7 +505,7 @@ void k_cvf_pc(
     }
         const __amdgpu_buffer_rsrc_t rG1 = pc_rsrc(G1, (unsigned)HW * 16u);
         const int vxb = xbc * 16;
-        const int dg = d_begin + dyn.dstep * pc_slice(dyn, d);
+        const int dg = d_begin + dyn.dstep * sl;
         const bool lane_out = lane < bwidth && xb < W;   // this lane owns an output pixel
 #define PSM_ISSUE_PB(SLOT, J)                                                           \
     {                                                                                   \
@@ -496,7 +554,7 @@ void k_cvf_pc(
             }
         }
         if constexpr (MODE == 2) { PSM_KEY_LOAD1(0, 0) PSM_KEY_LOAD1(1, 1) }
-        if (ds == 0) {                           // (two batches behind the producers: once per chunk - later slices stay in step)
+        if (ds == ds_lo) {                       // (two batches behind the producers: once per chunk - later slices stay in step)
             PC_SYNC();                           // iteration 0
             PC_SYNC();                           // iteration 1
         }
@@ -591,8 +649,11 @@ void k_cvf_pc(
 __global__ __launch_bounds__(256) void k_chunk_min(const float4 *kcost, const unsigned *kdisp, int nchunks, int npairs,
                                                   int nbmax, int ngroups, int seg_rows, int W, int H, long long *keys,
                                                   uint8_t *map, const float4 *__restrict__ kcost1, const unsigned *__restrict__ kdisp1,
-                                                  int ybeg, int yend, const PcPair *__restrict__ batch, int to_maps, int cols)
+                                                  int ybeg, int yend, const PcPair *__restrict__ batch, int to_maps, int cols,
+                                                  PcLive lv)
 {   // cols: output columns per (column group) of the layout the select kernel ran with (107 / 50)
+    // lv: the select launch's item table - the chunks it walked for each column group; the others' records were never written
+    // (blockIdx.y = side, as in the select kernel)
     if (batch) {             // batched launch: blockIdx.z = pair, planes / keys / maps from the table
         const PcPair pp = batch[blockIdx.z];
         const size_t rec_total = (size_t)npairs * nbmax * cols * nchunks;
@@ -626,13 +687,14 @@ __global__ __launch_bounds__(256) void k_chunk_min(const float4 *kcost, const un
     // kernel got faster - 17.8 -> 13.7 us at 450 x 375 x 64 -, but with two frames in flight the frame rose from 0.211 to 0.229 ms:
     // beside three resident workgroups of the fused kernel a SIMD has 32 vector registers left, and only this small form still fits
     // there; the wider ones wait for a fused workgroup to leave.  profiles/r06/exp_chunk_min_unroll.txt)
-    float4 kc = kcost[idx];
-    unsigned kd = kdisp[idx];
-    long long best[4] = {pack_key_f32(kc.x, kd & 0xff), pack_key_f32(kc.y, (kd >> 8) & 0xff), pack_key_f32(kc.z, (kd >> 16) & 0xff),
-                         pack_key_f32(kc.w, kd >> 24)};
-    for (int ch = 1; ch < nchunks; ++ch) {
-        kc = kcost[(size_t)ch * nrec + idx];
-        kd = kdisp[(size_t)ch * nrec + idx];
+    // (starts from key(+inf, 0), "no candidate": what a record holds before a slice improves it)
+    // The chunks the select launch walked for this column group: [c_lo, c_hi), from its own table.
+    const int c_lo = lv.lo, c_hi = min(nchunks, lv.lo + pc_live_count(lv, blockIdx.y == 1, g));
+    const long long none = pack_key_f32(__builtin_inff(), 0);
+    long long best[4] = {none, none, none, none};
+    for (int ch = c_lo; ch < c_hi; ++ch) {
+        const float4 kc = kcost[(size_t)ch * nrec + idx];
+        const unsigned kd = kdisp[(size_t)ch * nrec + idx];
         const long long k0 = pack_key_f32(kc.x, kd & 0xff), k1 = pack_key_f32(kc.y, (kd >> 8) & 0xff),
                         k2 = pack_key_f32(kc.z, (kd >> 16) & 0xff), k3 = pack_key_f32(kc.w, kd >> 24);
         best[0] = k0 < best[0] ? k0 : best[0];
@@ -683,6 +745,47 @@ PcDev pc_dev()
 }
 
 
+// The live work items of a launch of n slices (chunks: in chunks of DC slices - the plane form) over ngroups column groups of
+// `cols` columns: PcLive.  Counts come from pc_live_end and are checked against the predicate at their boundary; whenever the
+// table's shape does not hold (it always does for D <= 256 and groups of 50+ columns) the launch skips nothing at all (on = 0):
+// every slice of every group is run, as before the table existed.
+PcLive pc_live(int W, int cols, int ngroups, int n, int DC, bool chunks, const PcOwn &own)
+{
+    const int nu = chunks ? (n + DC - 1) / DC : n;
+    PcLive all = {};
+    all.full = nu;
+    all.tot[0] = all.tot[1] = ngroups * nu;
+    if (!own.on || n < 1 || ngroups < 1) return all;
+    PcLive lv = {};
+    lv.on = 1;
+    const int skip0 = own.d_begin == 0 && own.sel != 2 ? 1 : 0;      // the launch's slice 0 is d = 0
+    lv.lo = skip0 && (!chunks || DC == 1 || n == 1) ? 1 : 0;
+    lv.full = nu - lv.lo;
+    for (int side = 0; side < 2; ++side) {
+        int gs = -1, ge = -1;
+        for (int g = 0; g < ngroups; ++g) {
+            const int xf = g * cols, xl = xf + cols - 1;
+            const int L = pc_live_end(own, side, xf, xl, W, n);
+            if ((L < n && !pc_dead_at(own, side, xf, xl, W, L)) || (L - 1 >= skip0 && pc_dead_at(own, side, xf, xl, W, L - 1))) return all;
+            // live slices: skip0 .. L - 1; the items that hold one
+            const int end = chunks ? (L + DC - 1) / DC : L, c = L > skip0 && end > lv.lo ? end - lv.lo : 0;
+            lv.tot[side] += c;
+            if (c == lv.full) continue;
+            if (gs < 0) gs = g;
+            ge = g;
+        }
+        if (gs < 0) continue;
+        if (ge - gs + 1 > PC_LIVE_MAX) return all;
+        lv.pre[side] = gs;
+        lv.nshort[side] = ge - gs + 1;
+        for (int g = gs; g <= ge; ++g) {
+            const int L = pc_live_end(own, side, g * cols, g * cols + cols - 1, W, n), end = chunks ? (L + DC - 1) / DC : L;
+            lv.cnt[side][g - gs] = L > skip0 && end > lv.lo ? end - lv.lo : 0;
+        }
+    }
+    return lv;
+}
+
 // Segment count k (and, for the plane form, slices per chunk DC): every segment re-walks 14 halo rows, and the launch runs in
 // rounds of resident workgroups - per XCD ceil(pairs / nxcd) (column group, segment) pairs x chunks over cus_per_xcd CUs x 3
 // workgroups (key form: x 4).  Cost model, fitted to measurements at 1080p (DC = 1, 2, 4, 8, 16: 4.39, 4.41, 4.46, 4.71,
@@ -690,6 +793,10 @@ PcDev pc_dev()
 // which is what makes long-running workgroups (large DC) expensive - plus two row-steps per chunk plane for the reduction.
 // Round 5 added the choice of the column-group layout (wide / narrow) and, for several small pairs at a time, a flow model
 // in place of the rounds (both below).
+// The cut is chosen over ALL items of the launch, dead ones included: the two cost models below were fitted that way, and with the
+// live counts in their place the cut moved (1080p x 256: planes 8 segments x DC 2 -> 5 x DC 1; 4K x 256: keys 4 segments -> 2; 720p x
+// 128: keys 3 -> 5) and lost against the old cut on the same box in every alternating run - 6.54 against 6.45 ms at 1080p, 26.63
+// against 25.84 at 4K, 1.804 against 1.794 at 720p (profiles/border_skip/moved_cut_experiment).  The live items size the grid and the XCDs' shares (pc_live).
 PcPlan pc_plan(int W, int rows, int Dloc, int seg_rows_opt, int form, int batch, int inflight)
 {   // form: PC_STORE; PC_PLANES (select with chunk planes) / PC_KEYS (select against a shared key plane, one slice per
     // workgroup, no reduction afterwards), each + PC_BOTH when one launch covers both volumes (twice the work items)
@@ -767,7 +874,7 @@ PcPlan pc_plan(int W, int rows, int Dloc, int seg_rows_opt, int form, int batch,
     return pl;
 }
 
-constexpr int PC_KEY_SPREAD = 4;    // passes of the key form's slice order (pc_slice; measured 1 / 2 / 4 / 8 / 16: f32 5.12 / 5.07 / 5.06 / 5.08 / 5.10 ms, 8-bit 5.94 / 5.82 / 5.80 / 5.81 / 5.83)
+constexpr int PC_KEY_SPREAD = 4;    // passes of the key form's slice order (pc_spread; measured 1 / 2 / 4 / 8 / 16: f32 5.12 / 5.07 / 5.06 / 5.08 / 5.10 ms, 8-bit 5.94 / 5.82 / 5.80 / 5.81 / 5.83)
 
 int pc_seed_stride(int W, int rows, bool u8)
 {   // every S-th slice goes through the minima planes and seeds the key plane.  Rounds 3-5: 5, and 4 from 4 Mpixel up (flat from 5 to
@@ -782,7 +889,12 @@ int pc_seed_stride(int W, int rows, bool u8)
     return 8;
 }
 
-static int pc_blocks(const PcPlan &pl, int chunks) { return pl.nxcd * ((pl.ngroups * pl.nsegs * chunks + pl.nxcd - 1) / pl.nxcd); }
+// blocks per volume of a launch: every XCD its share of the live items of the volume that has more of them
+static int pc_blocks(const PcPlan &pl, const PcLive &lv)
+{
+    const int items = pl.nsegs * (lv.tot[0] > lv.tot[1] ? lv.tot[0] : lv.tot[1]);
+    return pl.nxcd * ((items + pl.nxcd - 1) / pl.nxcd);
+}
 
 // The arguments of one k_cvf_pc launch, gathered by its launcher (pc_launch passes them on).
 struct PcArgs {
@@ -818,6 +930,7 @@ static void pc_launch(hipStream_t s, const PcPlan &pl, dim3 grid, const PcArgs &
     using T = std::true_type;
     const bool planes = f.mode == PC_PLANES;     // (DC and nbmax mean something to the plane form only)
     const PcSide &s0 = a.side[0];
+    if (grid.x == 0) return;                     // (no live item: a launch of d = 0 alone)
     auto go = [&](auto V4, auto CV, auto MD, auto U, auto BT, auto VR, auto NW) {
         using L = PcLayout<MD, NW>;
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cvf_pc<V4, CV, MD, U, BT, VR, NW>), grid, dim3(64 * (L::NA + L::NB)), 0, s, a.vin, a.vout,
@@ -857,13 +970,13 @@ static int pc_var(March m, bool u8)
 
 // The one launch of k_chunk_min: `sides` volumes (chunk planes in `scratch`, or from the table `tab`) of `npairs` pairs.
 static void pc_chunk_min(hipStream_t s, March m, const PcPlan &pl, int W, int H, int sides, int npairs, void *scratch,
-                         long long *keys, uint8_t *map, const PcPair *tab = nullptr, bool to_maps = false)
+                         long long *keys, uint8_t *map, const PcLive &lv, const PcPair *tab = nullptr, bool to_maps = false)
 {
     const PcSide p0 = scratch ? pc_planes(pl, scratch, 0) : PcSide{}, p1 = scratch && sides == 2 ? pc_planes(pl, scratch, 1) : PcSide{};
     hipLaunchKernelGGL(k_chunk_min, dim3((unsigned)((pl.rec_per_chunk + 255) / 256), sides, npairs), dim3(256), 0, s,
                        (const float4 *)p0.kcost, (const unsigned *)p0.kdisp, pl.nchunks, pl.ngroups * pl.nsegs, pl.nbmax, pl.ngroups,
                        pl.seg_rows, W, H, keys, map, (const float4 *)p1.kcost, (const unsigned *)p1.kdisp, m.y0(H), m.y1(H), tab,
-                       to_maps ? 1 : 0, pl.cols);
+                       to_maps ? 1 : 0, pl.cols, lv);
 }
 
 // Storing form (MODE 0): vin (or, cvc_mode 1 / 2, the costs built on the fly) -> vout, one slice per workgroup.
@@ -872,10 +985,11 @@ void launch_cvf_fused(hipStream_t s, March m, const float *vin, float *vout, Gui
 {
     if (yend <= ybeg) return;
     const PcPlan pl = pc_plan(W, yend - ybeg, Dloc, m.seg_rows, PC_STORE);
-    PcArgs a = {vin, vout, W, H, Dloc, ybeg, yend, d_begin, {}, PcSel{0, 1, pl.nxcd, 0, Dloc, 0, 1}, ts, nullptr};
+    const PcLive lv = pc_live(W, pl.cols, pl.ngroups, Dloc, 1, false, PcOwn{});      // (the stored volume is complete)
+    PcArgs a = {vin, vout, W, H, Dloc, ybeg, yend, d_begin, {}, PcSel{0, 1, pl.nxcd, 0, 0, 1, lv}, ts, nullptr};
     a.side[0] = PcSide{gd.g1, gd.g2, gd.g3, gd.g4, g1_other, nullptr, nullptr};
     const int cvc = cvc_mode == 1 || cvc_mode == 2 ? cvc_mode : 0;
-    pc_launch(s, pl, dim3(pc_blocks(pl, Dloc)), a, {PC_STORE, cvc, false, (m.flags & PSM_FLAG_FMA_SOLVE) ? 2 : 0, false, false, (W & 3) == 0});
+    pc_launch(s, pl, dim3(pc_blocks(pl, lv)), a, {PC_STORE, cvc, false, (m.flags & PSM_FLAG_FMA_SOLVE) ? 2 : 0, false, false, (W & 3) == 0});
 }
 
 // Select form with chunk planes (MODE 1), one volume: costs read from vin (cvc_mode 0) or built on the fly (1 / 2; p4_own !=
@@ -886,22 +1000,26 @@ void launch_cvf_select(hipStream_t s, March m, const float *vin, Guidance gd, in
     const PcPlan pl = pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_PLANES);
     const int cvc = cvc_mode == 1 || cvc_mode == 2 ? cvc_mode : 0;
     const bool u8 = p4_own && cvc != 0;
+    const PcLive lv = pc_live(W, pl.cols, pl.ngroups, Dloc, pl.DC, true, PcOwn{});    // (one volume per launch: every chunk walked, as before)
     PcArgs a = {u8 ? (const float *)p4_own : vin, u8 ? (float *)const_cast<uint8_t *>(p4_other) : nullptr, W, H, Dloc, m.y0(H), m.y1(H),
-                d_begin, {}, PcSel{0, 1, pl.nxcd, 0, Dloc, 0, 1}, ts, nullptr};
+                d_begin, {}, PcSel{0, 1, pl.nxcd, 0, 0, 1, lv}, ts, nullptr};
     const PcSide k = pc_planes(pl, scratch, 0);
     a.side[0] = PcSide{gd.g1, gd.g2, gd.g3, gd.g4, g1_other, k.kcost, k.kdisp};
     // (one volume per launch: the canon and the FMA reading; no tolerance form)
-    pc_launch(s, pl, dim3(pc_blocks(pl, pl.nchunks)), a, {PC_PLANES, cvc, u8, (m.flags & PSM_FLAG_FMA_SOLVE) ? 2 : 0, false, false, false});
+    pc_launch(s, pl, dim3(pc_blocks(pl, lv)), a, {PC_PLANES, cvc, u8, (m.flags & PSM_FLAG_FMA_SOLVE) ? 2 : 0, false, false, false});
 }
 
 void launch_chunk_min(hipStream_t s, March m, int W, int H, int Dloc, void *scratch, long long *keys, uint8_t *map)
 {
-    pc_chunk_min(s, m, pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_PLANES), W, H, 1, 1, scratch, keys, map);
+    const PcPlan pl = pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_PLANES);
+    pc_chunk_min(s, m, pl, W, H, 1, 1, scratch, keys, map, pc_live(W, pl.cols, pl.ngroups, Dloc, pl.DC, true, PcOwn{}));
 }
 
 // pc_plan of the two-volume select launches.  A single context plans the rows of its stripe together with the frames other contexts
 // have in flight (March::inflight); a batch plans its pairs without that hint, a batch of one too (psm_compute_batch rejects
 // stripes: its rows are the whole image).
+// The launch covers Dloc of the slices the context owns from d_begin on (stride m.dstep): which ones, (sel, step) as in PcSel.
+static PcOwn pc_own(March m, int d_begin, int sel, int step) { return PcOwn{1, d_begin, m.dstep, sel, step}; }
 PcPlan pc_plan_select(March m, int W, int H, int Dloc, int form, int npairs, bool batch)
 {
     return pc_plan(W, m.rows(H), Dloc, m.seg_rows, form | PC_BOTH, npairs, batch ? 1 : m.inflight);
@@ -930,25 +1048,80 @@ void launch_cvf_select2(hipStream_t s, March m, const PcPairs &P, bool u8, int W
                         int sel, int step)
 {
     const PcPlan pl = pc_plan_select(m, W, H, Dloc, PC_PLANES, P.n, P.tab != nullptr);
+    const PcLive lv = pc_live(W, pl.cols, pl.ngroups, Dloc, pl.DC, true, pc_own(m, d_begin, sel, step));
     const unsigned long long rec_total = P.tab ? (unsigned long long)pl.rec_per_chunk * pl.nchunks : 0;   // (read by the batched form only)
-    const PcArgs a = pc_args2(m, pl, PC_PLANES, P, u8, W, H, Dloc, d_begin, PcSel{sel, step, pl.nxcd, 0, Dloc, rec_total, m.dstep}, ts);
-    pc_launch(s, pl, dim3(pc_blocks(pl, pl.nchunks), 2, P.n), a, {PC_PLANES, 3, u8, pc_var(m, u8), P.tab != nullptr, pl.narrow, false});
+    const PcArgs a = pc_args2(m, pl, PC_PLANES, P, u8, W, H, Dloc, d_begin, PcSel{sel, step, pl.nxcd, 0, rec_total, m.dstep, lv}, ts);
+    pc_launch(s, pl, dim3(pc_blocks(pl, lv), 2, P.n), a, {PC_PLANES, 3, u8, pc_var(m, u8), P.tab != nullptr, pl.narrow, false});
 }
 
-void launch_chunk_min2sides(hipStream_t s, March m, const PcPairs &P, int W, int H, int Dloc, bool to_maps)
+void launch_chunk_min2sides(hipStream_t s, March m, const PcPairs &P, int W, int H, int Dloc, bool to_maps, int d_begin, int sel, int step)
 {
     const PcPlan pl = pc_plan_select(m, W, H, Dloc, PC_PLANES, P.n, P.tab != nullptr);
-    if (P.tab) pc_chunk_min(s, m, pl, W, H, 2, P.n, nullptr, nullptr, nullptr, P.tab, to_maps);
-    else pc_chunk_min(s, m, pl, W, H, 2, 1, P.one.scratch, P.one.keys, to_maps ? P.one.maps : nullptr);
+    const PcLive lv = pc_live(W, pl.cols, pl.ngroups, Dloc, pl.DC, true, pc_own(m, d_begin, sel, step));    // the select launch's own table
+    if (P.tab) pc_chunk_min(s, m, pl, W, H, 2, P.n, nullptr, nullptr, nullptr, lv, P.tab, to_maps);
+    else pc_chunk_min(s, m, pl, W, H, 2, 1, P.one.scratch, P.one.keys, to_maps ? P.one.maps : nullptr, lv);
 }
 
 void launch_cvf_select_keys2(hipStream_t s, March m, const PcPairs &P, bool u8, int W, int H, int Dloc, int d_begin,
                              unsigned long long *ts, int sel, int step)
 {
     const PcPlan pl = pc_plan_select(m, W, H, Dloc, PC_KEYS, P.n, P.tab != nullptr);
+    const PcLive lv = pc_live(W, pl.cols, pl.ngroups, Dloc, 1, false, pc_own(m, d_begin, sel, step));
     const PcArgs a = pc_args2(m, pl, PC_KEYS, P, u8, W, H, Dloc, d_begin,
-                              PcSel{sel, step, pl.nxcd, PSM_KNOB("PSM_PC_SPREAD", PC_KEY_SPREAD), Dloc, 0, m.dstep}, ts);
-    pc_launch(s, pl, dim3(pc_blocks(pl, Dloc), 2, P.n), a, {PC_KEYS, 3, u8, pc_var(m, u8), P.tab != nullptr, pl.narrow, false});
+                              PcSel{sel, step, pl.nxcd, PSM_KNOB("PSM_PC_SPREAD", PC_KEY_SPREAD), 0, m.dstep, lv}, ts);
+    pc_launch(s, pl, dim3(pc_blocks(pl, lv), 2, P.n), a, {PC_KEYS, 3, u8, pc_var(m, u8), P.tab != nullptr, pl.narrow, false});
 }
 
 }  // namespace psm
+
+// debug / tests (no device needed): the liveness predicate of psm_live.h as the library was built with it
+extern "C" int psm_debug_pc_dead(int right, int xfirst, int xlast, int W, int dg, int dprev)
+{
+    return psm::pc_dead(right, xfirst, xlast, W, dg, dprev) ? 1 : 0;
+}
+
+// debug / tests (no device needed): the work items of one launch as the planner cuts it.  form PC_PLANES / PC_KEYS: the two-volume
+// select launch over nsl slices (sel, step) of a context that owns d_begin, d_begin + dstep, ...; PC_STORE: the storing form.
+// out[12] = {column groups, segments, DC, columns per group, live items per segment set left / right, all items per segment set
+// and volume, live slices (group, slice) left / right as the predicate counts them one by one, blocks per volume, first item, 0}
+extern "C" int psm_debug_pc_items(int W, int rows, int nsl, int form, int d_begin, int dstep, int sel, int step, int *out)
+{
+    using namespace psm;
+    if (!out || W < 1 || rows < 1 || nsl < 1 || dstep < 1 || form < PC_STORE || form > PC_KEYS) return 1;
+    March m = {};
+    m.dstep = dstep;
+    m.yend = rows;
+    PcOwn own = pc_own(m, d_begin, sel, step);
+    if (form == PC_STORE) own.on = 0;
+    const PcPlan pl = form == PC_STORE ? pc_plan(W, rows, nsl, 0, PC_STORE) : pc_plan_select(m, W, rows, nsl, form, 1, false);
+    const bool chunks = form == PC_PLANES;
+    const PcLive lv = pc_live(W, pl.cols, pl.ngroups, nsl, chunks ? pl.DC : 1, chunks, own);
+    int slices[2] = {0, 0};
+    for (int side = 0; side < 2; ++side)
+        for (int g = 0; g < pl.ngroups; ++g)
+            for (int j = 0; j < nsl; ++j)
+                slices[side] += pc_dead_at(own, side, g * pl.cols, g * pl.cols + pl.cols - 1, W, j) ? 0 : 1;
+    const int v[12] = {pl.ngroups, pl.nsegs, pl.DC, pl.cols, lv.tot[0], lv.tot[1], pl.ngroups * (chunks ? pl.nchunks : nsl),
+                       slices[0], slices[1], pc_blocks(pl, lv), lv.lo, 0};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return 0;
+}
+
+// debug / tests (no device needed): the items of column group g of volume `side` in the same launch's table, as k_cvf_pc
+// enumerates them and k_chunk_min reads them.  out[2] = {first item (slice of the launch, or chunk), their number}
+extern "C" int psm_debug_pc_group_items(int W, int rows, int nsl, int form, int d_begin, int dstep, int sel, int step, int side, int g,
+                                        int *out)
+{
+    using namespace psm;
+    if (!out || W < 1 || rows < 1 || nsl < 1 || dstep < 1 || form < PC_PLANES || form > PC_KEYS || side < 0 || side > 1 || g < 0) return 1;
+    March m = {};
+    m.dstep = dstep;
+    m.yend = rows;
+    const PcPlan pl = pc_plan_select(m, W, rows, nsl, form, 1, false);
+    if (g >= pl.ngroups) return 1;
+    const bool chunks = form == PC_PLANES;
+    const PcLive lv = pc_live(W, pl.cols, pl.ngroups, nsl, chunks ? pl.DC : 1, chunks, pc_own(m, d_begin, sel, step));
+    out[0] = lv.lo;
+    out[1] = pc_live_count(lv, side, g);
+    return 0;
+}
