@@ -285,7 +285,8 @@ int psm_download_images(psm_ctx *ctx, uint8_t *l, uint8_t *r, size_t stride_byte
  * up to 1024 disparities), blockSize 5, P1 = 8 ch bs^2,
  * P2 = 32 ch bs^2, disp12MaxDiff 1, uniquenessRatio 10, eight paths (MODE_HH).  All integer; the definition (DESIGN.md section 10,
  * tests/sgm_model.py) is Hirschmueller's recurrence under OpenCV's parameter names, and the device equals it element for element:
- *   pixel cost  c(x,y,d) = sum_ch |L[y][x][ch] - R[y][max(x-d, 0)][ch]|, or the prefiltered Birchfield-Tomasi cost - below
+ *   pixel cost  c(x,y,d) = sum_ch |L[y][x][ch] - R[y][max(x-d, 0)][ch]|, or the prefiltered Birchfield-Tomasi cost, or the
+ *               census cost - below
  *   block cost  C = the bs x bs box sum of c(.,.,d), the plane replicated at the image edge (u16)
  *   paths       L_r(p,d) = C(p,d) + min(L_r(p-r,d), L_r(p-r,d-1)+P1, L_r(p-r,d+1)+P1, m+P2) - m, m = min_k L_r(p-r,k); L_r = C where
  *               p-r is outside; r = (dy,dx) in (0,+-1), (+-1,0), (+-1,+-1); S = sum_r L_r (u32, exact)
@@ -308,7 +309,7 @@ int psm_sgm_set_params(psm_ctx *ctx, int block_size, int p1, int p2, int uniquen
  * PSM_OPT_ASYNC.  An independent stage: it reads the staged images only and writes its own buffers - 6 * W * H * Dp bytes of
  * volumes (Dp = the number of disparities D rounded up to 4; above 256 to 8, above 512 to 16 - D is max_disp or psm_sgm_set_range's)
  * and 8 * W * H of planes, plus 12 * W * H of prefiltered planes once a compute ran with
- * pre_filter_cap > 0, allocated on first use, reused from frame to frame, given back by psm_release_scratch and psm_destroy.  Volumes, maps, masks and minima of the other entry points are untouched: it may be
+ * pre_filter_cap > 0 and 16 * W * H of census codes once one ran with a census window, allocated on first use, reused from frame to frame, given back by psm_release_scratch and psm_destroy.  Volumes, maps, masks and minima of the other entry points are untouched: it may be
  * called anywhere between them.  Refused on disparity shards, under a row stripe, and when nothing has been uploaded. */
 int psm_sgm_compute(psm_ctx *ctx);
 /* The same for a 1-channel 8-bit pair (CV_8UC1 frames): H rows of W bytes, pitch stride_bytes (0: packed).  The pair is copied to
@@ -320,7 +321,7 @@ int psm_sgm_download_disparity(psm_ctx *ctx, int16_t *disp, size_t stride_bytes)
  * (max_disp, or psm_sgm_set_range's) - which 0: C as uint16, 1: S as uint32. */
 int psm_sgm_download_costs(psm_ctx *ctx, int which, void *host);
 /* With PSM_OPT_PROFILE set during the last compute: device time in ms of its block-cost launches (everything up to C, the
- * prefilter included), its eight path launches and its select + check launches (a getter of its own: the PSM_K_* and PSM_STAGE_* tables stay as they are). */
+ * prefilter or the census transform included), its eight path launches and its select + check launches (a getter of its own: the PSM_K_* and PSM_STAGE_* tables stay as they are). */
 int psm_sgm_times(psm_ctx *ctx, double ms[3]);
 
 /* StereoSGBM's modes (ssgbm->setMode, the reference's `m` key: src/main.cpp:22,114-168): the set of directions step "paths" sums.
@@ -387,6 +388,36 @@ int psm_sgm_set_prefilter(psm_ctx *ctx, int pre_filter_cap);
  * Refused when the last compute ran with pre_filter_cap 0, or there is none.  Synchronises. */
 int psm_sgm_download_prefiltered(psm_ctx *ctx, int side, uint8_t *planes);
 
+/* A third pixel cost: the Hamming distance of census transforms (tests/sgm_census_model.py; all integer, the device equals it
+ * element for element).  SAD and Birchfield-Tomasi compare intensities and break when the two cameras differ in gain, exposure or
+ * vignetting; a census code keeps only the order of a pixel's neighbourhood, which any increasing map of the intensities leaves
+ * as it is.  Window win_w x win_h, both odd, 3 <= win_w <= 9, 3 <= win_h <= 7 (win_w win_h - 1 <= 62 bits: one uint64 per pixel);
+ * images are the 8-bit pair (a float pair is quantised first), ch in {1, 3}:
+ *   gray     g [H][W]: ch 1: the byte; ch 3, staged order B, G, R: g = (1868 B + 9617 G + 4899 R + 8192) >> 14 (the stage's own
+ *            definition; the coefficients sum to 16384, so g <= 255)
+ *   code     T [H][W] uint64: the taps (dy, dx) in raster order, dy from -(win_h / 2) up, dx from -(win_w / 2) up, the centre
+ *            skipped, tap i = 0, 1, ...: bit i (bit 0 the least significant) is 1 iff
+ *            g[clamp(y + dy, 0, H - 1)][clamp(x + dx, 0, W - 1)] < g[y][x], strictly (a tap equal to the centre gives 0); the
+ *            plane is replicated at the image edge; the bits above win_w win_h - 2 are 0
+ *   cost     c(x,y,k) = popcount(T_L[y][x] ^ T_R[y][xr]), xr = clamp(x - (min_disparity + k), 0, W - 1): the range's right column,
+ *            max(x - d, 0) with the default range, as for the other two costs
+ * c <= win_w win_h - 1 <= 62, C <= 49 * 62 = 3038: the conditions of psm_sgm_set_params hold as they are, and P1 / P2 default to
+ * 8 ch bs^2 / 32 ch bs^2 with ch the pair's channels whatever the cost.  Block cost, paths, selection, consistency test and
+ * speckle filter are unchanged.  No library's convention, like the other two costs.
+ *
+ * psm_sgm_set_census: (0, 0) (a new context's setting): off - psm_sgm_compute, _compute_gray and _compute_batch are bit for bit
+ * what they are without this function.  A window as above: every following compute uses the cost above.  Anything else is
+ * refused; with a NULL context the message is psm_last_error(NULL)'s.  The setting holds until changed; no other setter resets
+ * it, it resets none, and no setter depends on call order.  A compute that finds a window and pre_filter_cap > 0 both set is
+ * refused (the message names both; in a batch also the index): nothing is enqueued, the previous result stays readable.
+ * psm_sgm_compute_batch refuses contexts whose windows differ.  The two code planes are 16 * W * H bytes per context, allocated
+ * by the first census compute, given back by psm_release_scratch and psm_destroy; psm_sgm_times counts the census launches in
+ * its first number. */
+int psm_sgm_set_census(psm_ctx *ctx, int win_w, int win_h);
+/* Test hook: the codes of the last compute, side 0: left, 1: right, as [H][W] uint64.  Refused when the last compute ran another
+ * cost, or there is none.  Synchronises. */
+int psm_sgm_download_census(psm_ctx *ctx, int side, uint64_t *codes);
+
 /* The speckle filter, the step StereoSGBM ends with when speckleWindowSize > 0 (the reference: 100, with speckleRange 32):
  * cv::filterSpeckles(img, newVal, maxSpeckleSize, maxDiff) on a CV_16SC1 map.  Its definition (tests/speckle_model.py) is free of
  * any visiting order:
@@ -416,27 +447,28 @@ int psm_sgm_download_speckle_sizes(psm_ctx *ctx, int32_t *sizes, size_t stride_b
  * (the copies of the map excluded) and then is what this reports. */
 int psm_sgm_speckle_time(psm_ctx *ctx, double *ms);
 
-/* psm_sgm_compute of the n contexts ctxs[0..n) in shared launches: every kernel of the stage - cost or prefilter + Birchfield-Tomasi
- * cost, the eight paths, select, check, the four of the speckle filter - runs once with the pair on a grid axis of its own, so a
+/* psm_sgm_compute of the n contexts ctxs[0..n) in shared launches: every kernel of the stage - cost, prefilter + Birchfield-Tomasi
+ * cost or census + census cost, the eight paths, select, check, the four of the speckle filter - runs once with the pair on a grid axis of its own, so a
  * path launch has n x (H, W or W + H - 1) one-wave paths instead of one pair's.  The reference's use on Middlebury-size data is a
  * loop over pairs and datasets (src/main.cpp:64-73, src/StereoMatch.cpp:528-609); there the stage is bound by the waves it has in
  * flight, not by bytes.  Measured at 450 x 375 x 64 with the reference's configuration
  * (cap 63, speckle 100 / 32): 0.569 ms per pair one context after the other, 0.276 ms per pair in a batch of 8 (0.356 in a batch
  * of 2); at 1280 x 720 x 128 0.98 of the singles in a batch of 8, at 1920 x 1080 x 256 0.96 in a batch of 4.
  * Each context holds its own pair, exactly the one its own psm_sgm_compute would read at that moment, and afterwards is exactly
- * where that call would have left it: psm_sgm_download_disparity / _costs / _prefiltered / _speckle_sizes, a later single
+ * where that call would have left it: psm_sgm_download_disparity / _costs / _prefiltered / _census / _speckle_sizes, a later single
  * psm_sgm_compute and psm_sgm_filter_speckles work per context and return the same bits.  Volumes, maps, masks and minima of the
  * other entry points are untouched; the call may stand anywhere between them.
  * The contexts must agree on width, height, max_disp and device, on the depth of the staged pair (a float pair is quantised on the
- * device, as ever) and on every setting of psm_sgm_set_params, psm_sgm_set_prefilter, psm_sgm_set_speckle, psm_sgm_set_mode
- * and psm_sgm_set_range.  Refused otherwise,
+ * device, as ever) and on every setting of psm_sgm_set_params, psm_sgm_set_prefilter, psm_sgm_set_census, psm_sgm_set_speckle,
+ * psm_sgm_set_mode and psm_sgm_set_range.  Refused otherwise,
  * and for NULL or repeated contexts, n < 1 or n > 4096, a context without a pair, a disparity shard, a row stripe in force and
  * parameters psm_sgm_set_params would refuse: psm_last_error(ctxs[0]) names the offending index, nothing has been enqueued, and
  * every context's previous result is still readable.
  * The launches run on ctxs[0]'s stream, after everything already queued on the other contexts' streams and before anything queued
  * on them later; synchronous on return unless ctxs[0] has PSM_OPT_ASYNC.  Contexts under psm_share_streams work as they are.
  * Buffers stay per context (allocated on first use, given back by psm_release_scratch / psm_destroy); the kernels reach them
- * through a device table of n * 88 bytes that ctxs[0] owns and uploads again only when an entry changed.  With PSM_OPT_PROFILE on
+ * through a device table of n * 88 bytes (the census code planes take the slots of the prefiltered planes: a batch has one cost)
+ * that ctxs[0] owns and uploads again only when an entry changed.  With PSM_OPT_PROFILE on
  * ctxs[0], psm_sgm_times(ctxs[0]) and psm_sgm_speckle_time(ctxs[0]) report the batch's launches; the other contexts count as not
  * timed.  psm_sgm_compute_gray has no batch form: it takes host pointers and stages them itself. */
 int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n);

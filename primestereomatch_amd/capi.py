@@ -122,6 +122,8 @@ SYMBOLS = [
     ("psm_sgm_compute_batch", _i, [C.POINTER(_vp), _i]),
     ("psm_sgm_set_mode", _i, [_vp, _i]),
     ("psm_sgm_set_range", _i, [_vp, _i, _i]),
+    ("psm_sgm_set_census", _i, [_vp, _i, _i]),
+    ("psm_sgm_download_census", _i, [_vp, _i, _vp]),
     ("psm_score_set_truth", _i, [_vp, _vp, _vp, _sz]),
     ("psm_score_clear_truth", _i, [_vp]),
     ("psm_score_set_params", _i, [_vp, _i, _i, _i]),

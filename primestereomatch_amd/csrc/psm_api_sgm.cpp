@@ -5,7 +5,8 @@
 // of ssgbm->compute, the speckle filter (speckleWindowSize 100, speckleRange 32 there), is psm_speckle.hip: on the stage's map when
 // psm_sgm_set_speckle turned it on, on a caller's map in psm_sgm_filter_speckles (tests/speckle_model.py).  The pixel cost is SAD
 // (pre_filter_cap 0, a new context's setting) or, after psm_sgm_set_prefilter, StereoSGBM's Sobel-prefiltered Birchfield-Tomasi
-// cost as tests/sgm_bt_model.py defines it (the reference: preFilterCap 63).  Unpinned in all of it: a live cv::StereoSGBM.
+// cost as tests/sgm_bt_model.py defines it (the reference: preFilterCap 63), or, after psm_sgm_set_census, the Hamming distance
+// of census codes (tests/sgm_census_model.py).  Unpinned in all of it: a live cv::StereoSGBM.
 // psm_sgm_compute_batch: the same launches for the pairs of several contexts at once, the pair on a grid axis of its own.
 #include "psm_ctx.h"
 
@@ -29,6 +30,8 @@ void sgm_free(psm_ctx *c)
     for (uint8_t *&p : g.gray) { (void)hipFree(p); p = nullptr; }
     for (uint8_t *&p : g.pf) { (void)hipFree(p); p = nullptr; }
     g.pf_ch = 0;
+    for (uint64_t *&p : g.cen) { (void)hipFree(p); p = nullptr; }
+    g.cen_have = false;
     for (hipEvent_t &e : g.ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     (void)hipFree(g.tab); g.tab = nullptr;
     if (g.tab_pin) (void)hipHostFree(g.tab_pin);
@@ -73,6 +76,16 @@ int check_ctx(psm_ctx *e, const psm_ctx *c, const char *who)
     return 0;
 }
 
+// the census cost and the prefilter exclude each other: a compute that finds both set is refused before it touches anything
+int check_cost(psm_ctx *e, const psm_ctx *c, const char *who)
+{
+    const SgmState &g = c->sgm;
+    if (g.cen_w > 0 && g.cap > 0)
+        return fail(e, "%s: census window %d x %d (psm_sgm_set_census) and pre_filter_cap %d (psm_sgm_set_prefilter) are both set: one pixel cost at a time",
+                    who, g.cen_w, g.cen_h, g.cap);
+    return 0;
+}
+
 int ensure_buffers(psm_ctx *c)
 {
     SgmState &g = c->sgm;
@@ -94,6 +107,9 @@ int ensure_buffers(psm_ctx *c)
     if (g.cap > 0)
         for (uint8_t *&p : g.pf)
             if (!p) PSM_HIP(c, hipMalloc((void **)&p, HW * 6));
+    if (g.cen_w > 0)
+        for (uint64_t *&p : g.cen)
+            if (!p) PSM_HIP(c, hipMalloc((void **)&p, HW * sizeof(uint64_t)));
     if (c->opt_profile)
         for (hipEvent_t &e : g.ev)
             if (!e) PSM_HIP(c, hipEventCreate(&e));
@@ -116,6 +132,8 @@ SgmArgs sgm_args(const psm_ctx *c, const void *l, const void *r, int depth, int 
         a.Hs = (uint16_t *)g.S;                           // S is free until the first direction stores it
         a.ft = (g.cap > 15 ? g.cap : 15) | 1;
     }
+    a.cw = g.cen_w; a.chh = g.cen_h;
+    if (g.cen_w > 0) { a.pf[0] = (uint8_t *)g.cen[0]; a.pf[1] = (uint8_t *)g.cen[1]; }      // (the code planes travel in the pf slots)
     return a;
 }
 
@@ -179,10 +197,15 @@ int enqueue(psm_ctx *c, const char *who, const void *l, const void *r, int depth
     g.have = g.timed = false;
     g.spk_t0 = -1;
     g.pf_ch = 0;
+    g.cen_have = false;
     // disp2 starts every frame as "nothing lands here", on the stream
     PSM_HIP(c, hipMemsetAsync(g.disp2, 0xff, (size_t)c->W * c->H * sizeof(uint32_t), c->stream));
     if (timed) PSM_HIP(c, hipEventRecord(g.ev[0], c->stream));
-    if (g.cap > 0) {
+    if (g.cen_w > 0) {
+        launch_sgm_cost_census(c->stream, a);
+        if (check_launch(c, "k_sgm_census, k_sgm_census_cost")) return 1;
+        g.cen_have = true;
+    } else if (g.cap > 0) {
         launch_sgm_cost_bt(c->stream, a);
         if (check_launch(c, "k_sgm_prefilter, k_sgm_bt_*")) return 1;
         g.pf_ch = ch;
@@ -240,6 +263,18 @@ int psm_sgm_set_prefilter(psm_ctx *c, int pre_filter_cap)
     return 0;
 }
 
+int psm_sgm_set_census(psm_ctx *c, int win_w, int win_h)
+{
+    const bool off = win_w == 0 && win_h == 0;             // (without a context the message is psm_last_error(NULL)'s)
+    if (!off && (win_w < 3 || win_w > SGM_CEN_MAXW || win_h < 3 || win_h > SGM_CEN_MAXH || win_w % 2 == 0 || win_h % 2 == 0))
+        return fail(c, "psm_sgm_set_census: window %d x %d: both odd, width in [3, %d], height in [3, %d], or (0, 0) for off", win_w, win_h,
+                    SGM_CEN_MAXW, SGM_CEN_MAXH);
+    if (!c) return fail(nullptr, "psm_sgm_set_census: NULL context");
+    c->sgm.cen_w = win_w;
+    c->sgm.cen_h = win_h;
+    return 0;
+}
+
 int psm_sgm_set_mode(psm_ctx *c, int mode)
 {
     if (mode < 0 || mode > 3)                  // (without a context the message is psm_last_error(NULL)'s)
@@ -264,7 +299,7 @@ int psm_sgm_set_range(psm_ctx *c, int min_disparity, int num_disparities)
 int psm_sgm_compute(psm_ctx *c)
 {
     if (!c) return 1;
-    if (check_ctx(c, c, "psm_sgm_compute")) return 1;
+    if (check_ctx(c, c, "psm_sgm_compute") || check_cost(c, c, "psm_sgm_compute")) return 1;
     if (c->raw_depth < 0) return fail(c, "psm_sgm_compute: no image pair (psm_upload_pair)");
     if (bind(c)) return 1;
     return enqueue(c, "psm_sgm_compute", c->raw[0], c->raw[1], c->raw_depth, 3);
@@ -273,7 +308,7 @@ int psm_sgm_compute(psm_ctx *c)
 int psm_sgm_compute_gray(psm_ctx *c, const uint8_t *l, const uint8_t *r, size_t stride_bytes)
 {
     if (!c) return 1;
-    if (check_ctx(c, c, "psm_sgm_compute_gray")) return 1;
+    if (check_ctx(c, c, "psm_sgm_compute_gray") || check_cost(c, c, "psm_sgm_compute_gray")) return 1;
     if (!l || !r) return fail(c, "psm_sgm_compute_gray: NULL image");
     const size_t row = (size_t)c->W;
     if (stride_bytes == 0) stride_bytes = row;
@@ -308,13 +343,15 @@ int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
             return fail(c0, "%s: context %d has another width / height / max_disp / device than context 0", who, i);
         char member[64];
         snprintf(member, sizeof member, "%s: context %d", who, i);
-        if (check_ctx(c0, c, member)) return 1;
+        if (check_ctx(c0, c, member) || check_cost(c0, c, member)) return 1;
         if (c->raw_depth < 0) return fail(c0, "%s: context %d has no image pair (psm_upload_pair)", who, i);
         if (c->raw_depth != c0->raw_depth) return fail(c0, "%s: context %d holds images of another depth than context 0", who, i);
         const SgmState &g = c->sgm;
         if (g.bs != g0.bs || g.p1 != g0.p1 || g.p2 != g0.p2 || g.u != g0.u || g.m != g0.m)
             return fail(c0, "%s: context %d has other parameters (psm_sgm_set_params) than context 0", who, i);
         if (g.cap != g0.cap) return fail(c0, "%s: context %d has another pre_filter_cap (%d) than context 0 (%d)", who, i, g.cap, g0.cap);
+        if (g.cen_w != g0.cen_w || g.cen_h != g0.cen_h)
+            return fail(c0, "%s: context %d has another census window (%d x %d) than context 0 (%d x %d)", who, i, g.cen_w, g.cen_h, g0.cen_w, g0.cen_h);
         if (g.mode != g0.mode) return fail(c0, "%s: context %d has another mode (%d) than context 0 (%d)", who, i, g.mode, g0.mode);
         if (g.dmin != g0.dmin || sgm_d(c) != sgm_d(c0))
             return fail(c0, "%s: context %d has another disparity range (min %d, %d disparities) than context 0 (min %d, %d)", who, i, g.dmin,
@@ -327,7 +364,7 @@ int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
     if (check_params(c0, who, 3, g0.bs, &p1, &p2, g0.u)) return 1;      // (every context's: they are context 0's)
     if (bind(c0)) return 1;
     hipStream_t s = c0->stream;
-    const bool timed = c0->opt_profile != 0, spk = g0.spk_window > 0;
+    const bool timed = c0->opt_profile != 0, spk = g0.spk_window > 0, census = g0.cen_w > 0;
 
     // ---- buffers, events and the table's memory: before any launch, and before any context forgets its previous result ----
     for (int i = 0; i < n; ++i) {
@@ -341,8 +378,9 @@ int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
     for (int i = 0; i < n; ++i) {
         const psm_ctx *c = ctxs[i];
         const SgmState &g = c->sgm;
-        tab[i] = SgmPair{{c->raw[0], c->raw[1]}, g.C, g.S, g.disp2, g.pre, g.out, {g.cap > 0 ? g.pf[0] : nullptr, g.cap > 0 ? g.pf[1] : nullptr},
-                         spk ? g.spk_label : nullptr, spk ? g.spk_size : nullptr};
+        uint8_t *const p0 = census ? (uint8_t *)g.cen[0] : (g.cap > 0 ? g.pf[0] : nullptr);      // (the code planes travel in the pf slots)
+        uint8_t *const p1 = census ? (uint8_t *)g.cen[1] : (g.cap > 0 ? g.pf[1] : nullptr);
+        tab[i] = SgmPair{{c->raw[0], c->raw[1]}, g.C, g.S, g.disp2, g.pre, g.out, {p0, p1}, spk ? g.spk_label : nullptr, spk ? g.spk_size : nullptr};
     }
     const bool fresh = t.tab_host.size() != tab.size() || memcmp(t.tab_host.data(), tab.data(), tab.size() * sizeof(SgmPair)) != 0;
     if (fresh && t.tab_cap < tab.size()) {
@@ -385,14 +423,17 @@ int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
         g.have = g.timed = false;
         g.spk_t0 = -1;
         g.pf_ch = 0;
+        g.cen_have = false;
         if (spk) g.spk_have = false;
     }
     const SgmArgs a = sgm_args(c0, nullptr, nullptr, c0->raw_depth, 3, p1, p2);      // (the scalars; the pointers are the table's)
     launch_sgm_fill_batch(s, a, t.tab, n);
     if (timed) PSM_HIP(c0, hipEventRecord(t.ev[0], s));
-    if (g0.cap > 0) launch_sgm_cost_bt(s, a, t.tab, n);
+    if (census) launch_sgm_cost_census(s, a, t.tab, n);
+    else if (g0.cap > 0) launch_sgm_cost_bt(s, a, t.tab, n);
     else launch_sgm_cost(s, a, t.tab, n);
-    if (check_launch(c0, g0.cap > 0 ? "k_sgm_fill_b, k_sgm_prefilter_b, k_sgm_bt_*_b" : "k_sgm_fill_b, k_sgm_cost_b")) return 1;
+    if (check_launch(c0, census ? "k_sgm_fill_b, k_sgm_census_b, k_sgm_census_cost_b"
+                                : (g0.cap > 0 ? "k_sgm_fill_b, k_sgm_prefilter_b, k_sgm_bt_*_b" : "k_sgm_fill_b, k_sgm_cost_b"))) return 1;
     if (timed) PSM_HIP(c0, hipEventRecord(t.ev[1], s));
     launch_paths(c0, s, a, t.tab, n);
     if (check_launch(c0, "k_sgm_path_b")) return 1;
@@ -415,6 +456,7 @@ int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
         g.res_d = a.D;
         g.timed = timed && i == 0;
         g.pf_ch = g0.cap > 0 ? 3 : 0;
+        g.cen_have = census;
         if (spk) {
             g.spk_have = true;
             g.spk_t0 = timed && i == 0 ? 3 : -1;
@@ -470,6 +512,19 @@ int psm_sgm_download_prefiltered(psm_ctx *c, int side, uint8_t *planes)
         return fail(c, "psm_sgm_download_prefiltered: the last psm_sgm_compute prefiltered nothing (psm_sgm_set_prefilter), or there is none");
     if (bind(c)) return 1;
     PSM_HIP(c, hipMemcpyAsync(planes, c->sgm.pf[side], (size_t)c->W * c->H * 2 * c->sgm.pf_ch, hipMemcpyDeviceToHost, c->stream));
+    PSM_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int psm_sgm_download_census(psm_ctx *c, int side, uint64_t *codes)
+{
+    if (!c) return 1;
+    if (!codes) return fail(c, "psm_sgm_download_census: NULL buffer");
+    if (side != 0 && side != 1) return fail(c, "psm_sgm_download_census: side %d (0: left, 1: right)", side);
+    if (!c->sgm.have || !c->sgm.cen_have)
+        return fail(c, "psm_sgm_download_census: the last psm_sgm_compute ran another pixel cost (psm_sgm_set_census), or there is none");
+    if (bind(c)) return 1;
+    PSM_HIP(c, hipMemcpyAsync(codes, c->sgm.cen[side], (size_t)c->W * c->H * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     PSM_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }

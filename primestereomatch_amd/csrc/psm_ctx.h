@@ -67,6 +67,10 @@ struct SgmState {
     int cap = 0;                                   // pre_filter_cap; 0: the SAD cost
     uint8_t *pf[2] = {nullptr, nullptr};           // the planes of both images, [H][W][2 ch] bytes (room for ch 3)
     int pf_ch = 0;                                 // the channels of the planes the last compute wrote; 0: it wrote none
+    // the census cost (psm_sgm_set_census): 16 W H bytes, allocated when first used
+    int cen_w = 0, cen_h = 0;                      // the window; (0, 0): off
+    uint64_t *cen[2] = {nullptr, nullptr};         // the code planes of both images, [H][W]
+    bool cen_have = false;                         // the last compute wrote them
     // psm_sgm_compute_batch (this context as the first of a batch): the device table of the pairs' buffers, its host copy (the
     // table is uploaded again only when an entry changed) and its page-locked staging, two slots used alternately as
     // psm_compute_batch's (psm_ctx::batch_pin); ev_tab: the copy out of a slot has executed

@@ -255,6 +255,9 @@ struct SgmArgs {
     uint8_t *pf[2];                    // prefiltered planes of both images, [H][W][2 ch] bytes: P_0 .. P_{ch-1}, Q_0 .. Q_{ch-1}
     uint16_t *Hs;                      // horizontal block sums [H][W][Dp], in the memory of S (free until the first direction stores it)
     int ft;                            // max(pre_filter_cap, 15) | 1
+    // the census cost (launch_sgm_cost_census only; psm_sgm_set_census): the window, and in the two pf slots the code planes of both
+    // images, [H][W] uint64 (the two costs exclude each other)
+    int cw, chh;
 };
 // Several pairs of one geometry per launch (psm_sgm_compute_batch): one pair's buffers, an entry of the device table the batched
 // entries index with the pair number (blockIdx.z).  The scalars of SgmArgs / SpkArgs are the batch's; the pointers come from here.
@@ -264,7 +267,7 @@ struct SgmPair {
     uint32_t *S;
     uint32_t *disp2;
     int16_t *pre, *out;
-    uint8_t *pf[2];                    // null with the SAD cost
+    uint8_t *pf[2];                    // null with the SAD cost; with the census cost the two code planes
     unsigned *spk_label, *spk_size;    // null with the speckle filter off
 };
 // A pointer a kernel reads from the table is a flat pointer to the compiler (one that arrives as a kernel argument is known to be
@@ -287,9 +290,14 @@ inline int sgm_dp(int D) { return D <= 256 ? (D + 3) & ~3 : (D <= 512 ? (D + 7) 
 __host__ __device__ inline int sgm_kb(int Dp) { return Dp > 256 ? 10 : 8; }
 constexpr int SGM_BT_TX = 128;         // k_sgm_bt_rows: output pixels of a row per workgroup
 constexpr int SGM_BT_YS = 32;          // k_sgm_bt_cols: output rows per thread
+constexpr int SGM_CEN_TX = 32;         // k_sgm_census: the pixels of a workgroup's tile, columns ...
+constexpr int SGM_CEN_TY = 8;          // ... and rows
+constexpr int SGM_CEN_MAXW = 9;        // the widest census window (psm_sgm_set_census): 9 x 7 - 1 = 62 bits
+constexpr int SGM_CEN_MAXH = 7;
 // tab == nullptr: the pair whose pointers `a` holds; else the n pairs of the device table (the pointers of `a` unused, grid z = pair)
 void launch_sgm_cost(hipStream_t s, const SgmArgs &a, const SgmPair *tab = nullptr, int n = 1);
 void launch_sgm_cost_bt(hipStream_t s, const SgmArgs &a, const SgmPair *tab = nullptr, int n = 1);   // k_sgm_prefilter, k_sgm_bt_rows, k_sgm_bt_cols: the same C
+void launch_sgm_cost_census(hipStream_t s, const SgmArgs &a, const SgmPair *tab = nullptr, int n = 1);   // k_sgm_census, k_sgm_census_cost: the same C
 void launch_sgm_path(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first, const SgmPair *tab = nullptr, int n = 1);   // S = L_r (first) or S += L_r
 void launch_sgm_select(hipStream_t s, const SgmArgs &a, const SgmPair *tab = nullptr, int n = 1);   // k_sgm_select + k_sgm_check (disp2 all ones before)
 void launch_sgm_fill_batch(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n);   // disp2 of every pair all ones

@@ -12,7 +12,8 @@
 // d is innermost in both volumes (Dp = D rounded up to 4 elements per pixel): the disparities of a pixel are one contiguous read
 // whatever the walking direction.  The speckle filter StereoSGBM ends with is psm_speckle.hip (psm_sgm_set_speckle).  StereoSGBM's
 // own pixel cost, Birchfield-Tomasi over Sobel-prefiltered images (psm_sgm_set_prefilter, tests/sgm_bt_model.py), writes the same
-// C through k_sgm_prefilter, k_sgm_bt_rows and k_sgm_bt_cols below.  Unpinned: agreement with a live cv::StereoSGBM.
+// C through k_sgm_prefilter, k_sgm_bt_rows and k_sgm_bt_cols below; the census cost (psm_sgm_set_census, tests/sgm_census_model.py)
+// through k_sgm_census and k_sgm_census_cost.  Unpinned: agreement with a live cv::StereoSGBM.
 #include "psm_kernels.h"
 
 #include <type_traits>
@@ -289,6 +290,117 @@ __device__ __forceinline__ void sgm_bt_cols(const SgmArgs &a)
 template <int BS> __global__ __launch_bounds__(256) void k_sgm_bt_cols(SgmArgs a) { sgm_bt_cols<BS>(a); }
 template <int BS> __global__ __launch_bounds__(256) void k_sgm_bt_cols_b(SgmArgs a, const SgmPair *tab) { sgm_bt_cols<BS>(sgm_pair_args(a, tab, blockIdx.z)); }
 
+// ---- the census cost (psm_sgm_set_census, tests/sgm_census_model.py): the same C by two kernels ---------------------------------
+//   k_sgm_census       both images -> their code planes T [H][W] uint64: bit i is "tap i of the win_w x win_h window is darker than
+//                      the centre" on the gray plane, the taps in raster order with the centre skipped, the plane replicated
+//   k_sgm_census_cost  C(x,y,k) = the bs x bs box sum (replicated edge) of popcount(T_L[y][x] ^ T_R[y][xr])
+
+// the gray value of one staged pixel: the byte, or (1868 B + 9617 G + 4899 R + 8192) >> 14 of the staged order B, G, R
+__device__ __forceinline__ unsigned sgm_gray(const void *img, int depth, int ch, size_t idx)
+{
+    const unsigned v = sgm_px(img, depth, ch, idx);
+    return ch == 1 ? v : (1868u * (v & 255u) + 9617u * ((v >> 8) & 255u) + 4899u * (v >> 16) + 8192u) >> 14;
+}
+
+// One workgroup per tile of SGM_CEN_TX x SGM_CEN_TY pixels of one image (blockIdx.z; batched: z = 2 pair + side), one pixel per
+// thread.  The tile's gray values with the window's halo go to LDS as bytes (a float image is quantised here, once); the clamp of
+// a tap is done there.  The two dwords of a code are built separately - a tap sets a bit of one of them - and leave as one 8-byte
+// store.
+__device__ __forceinline__ void sgm_census(const SgmArgs &a, int side)
+{
+    constexpr int LW = SGM_CEN_TX + SGM_CEN_MAXW - 1, LH = SGM_CEN_TY + SGM_CEN_MAXH - 1;
+    __shared__ uint8_t sg[LH * LW];
+    const int hx = a.cw / 2, hy = a.chh / 2, lw = SGM_CEN_TX + 2 * hx, lh = SGM_CEN_TY + 2 * hy;      // lw <= LW, lh <= LH
+    const int x0 = blockIdx.x * SGM_CEN_TX, y0 = blockIdx.y * SGM_CEN_TY;
+    const void *img = side ? a.img[1] : a.img[0];             // (no index: the argument record stays in registers)
+    for (int i = threadIdx.x; i < lh * lw; i += blockDim.x) {
+        const int j = i / lw, s = i - j * lw;
+        sg[i] = (uint8_t)sgm_gray(img, a.depth, a.ch, (size_t)sgm_clamp(y0 - hy + j, a.H) * a.W + sgm_clamp(x0 - hx + s, a.W));
+    }
+    __syncthreads();
+    const int tx = threadIdx.x % SGM_CEN_TX, ty = threadIdx.x / SGM_CEN_TX;
+    const int x = x0 + tx, y = y0 + ty;
+    if (x >= a.W || y >= a.H) return;
+    const unsigned centre = sg[(ty + hy) * lw + tx + hx];
+    unsigned lo = 0, hi = 0;
+    int i = 0;
+    for (int dy = 0; dy <= 2 * hy; ++dy) {
+        const uint8_t *row = sg + (ty + dy) * lw + tx;
+        for (int dx = 0; dx <= 2 * hx; ++dx) {
+            if (dy == hy && dx == hx) continue;
+            const unsigned bit = row[dx] < centre;
+            if (i < 32) lo |= bit << i;
+            else hi |= bit << (i - 32);
+            ++i;
+        }
+    }
+    ((uint2 *)(side ? a.pf[1] : a.pf[0]))[(size_t)y * a.W + x] = make_uint2(lo, hi);
+}
+
+__global__ __launch_bounds__(256) void k_sgm_census(SgmArgs a) { sgm_census(a, blockIdx.z); }
+__global__ __launch_bounds__(256) void k_sgm_census_b(SgmArgs a, const SgmPair *tab) { sgm_census(sgm_pair_args(a, tab, blockIdx.z >> 1), blockIdx.z & 1); }
+
+// k_sgm_cost's shape: one workgroup per SGM_TX pixels of one row, one thread per disparity; the BS rows of both code planes go to
+// LDS as 8-byte words, the left tap is a broadcast, the right taps of neighbouring lanes are neighbouring words; where k_sgm_cost
+// has one v_sad_u8 with its accumulator this has two XORs and two v_bcnt_u32_b32, whose second operand takes the running sum.
+// Column sums of the last BS columns stay in registers.  Above 256 disparities the 256 threads take the disparities in passes of
+// 256 and the right span is staged again for every pass: NL + 255 columns whatever D is (static LDS: 18.1 KB at BS 7, where one
+// span for all 1024 disparities would be 61.5 KB and leave a CU one workgroup).
+template <int BS>
+__device__ __forceinline__ void sgm_census_cost(const SgmArgs &a)
+{
+    constexpr int HALF = BS / 2, NL = SGM_TX + BS - 1, NR = NL + 255;
+    __shared__ uint2 sl[BS][NL], sr[BS][NR];
+    const uint2 *tl = (const uint2 *)a.pf[0], *tr = (const uint2 *)a.pf[1];
+    const int y = blockIdx.y, x0 = blockIdx.x * SGM_TX;
+    const int cx_min = sgm_clamp(x0 - HALF, a.W);
+    for (int i = threadIdx.x; i < BS * NL; i += blockDim.x) {
+        const int j = i / NL, s = i - j * NL;
+        sl[j][s] = tl[(size_t)sgm_clamp(y + j - HALF, a.H) * a.W + sgm_clamp(x0 - HALF + s, a.W)];
+    }
+    for (int db = 0; db < a.Dp; db += 256) {                  // the pass over the indices db .. de - 1 (db < D: Dp - D < 16)
+        const int de = min(a.D, db + 256);
+        const int rbase = cx_min - a.dmin - (de - 1);         // image column of sr[.][0] (before the clamp)
+        const int nr = NL + (de - db) - 1;
+        if (db) __syncthreads();                              // the previous pass has read its span
+        for (int i = threadIdx.x; i < BS * nr; i += blockDim.x) {
+            const int j = i / nr, k = i - j * nr;
+            sr[j][k] = tr[(size_t)sgm_clamp(y + j - HALF, a.H) * a.W + sgm_clamp(rbase + k, a.W)];
+        }
+        __syncthreads();
+        const int d = db + threadIdx.x;
+        if (d >= a.Dp) continue;
+        const bool real = d < a.D;
+        const int kd = de - 1 - (real ? d : db) - cx_min;     // column cx, index d: sr[.][cx - cx_min + de - 1 - d], inside [0, nr)
+        unsigned v[BS];
+#pragma unroll
+        for (int i = 0; i < BS; ++i) v[i] = 0;
+        for (int s = 0; s < NL; ++s) {
+            const int k = sgm_clamp(x0 - HALF + s, a.W) + kd;
+            unsigned col = 0;
+#pragma unroll
+            for (int j = 0; j < BS; ++j) {
+                const uint2 l = sl[j][s], r = sr[j][k];
+                col = __builtin_popcount(l.x ^ r.x) + col;
+                col = __builtin_popcount(l.y ^ r.y) + col;
+            }
+#pragma unroll
+            for (int i = 0; i + 1 < BS; ++i) v[i] = v[i + 1];
+            v[BS - 1] = col;
+            const int x = x0 + s - (BS - 1);
+            if (s >= BS - 1 && x < a.W) {
+                unsigned sum = 0;
+#pragma unroll
+                for (int i = 0; i < BS; ++i) sum += v[i];
+                a.C[((size_t)y * a.W + x) * a.Dp + d] = (uint16_t)(real ? sum : 0u);
+            }
+        }
+    }
+}
+
+template <int BS> __global__ __launch_bounds__(256) void k_sgm_census_cost(SgmArgs a) { sgm_census_cost<BS>(a); }
+template <int BS> __global__ __launch_bounds__(256) void k_sgm_census_cost_b(SgmArgs a, const SgmPair *tab) { sgm_census_cost<BS>(sgm_pair_args(a, tab, blockIdx.z)); }
+
 // NV adjacent disparities per lane: what a lane moves per pixel, and U, the steps of k_sgm_path whose loads are issued together.
 // NV U is constant from NV 4 on: the look-ahead of the wide forms (NV 8, 16: Dp up to 512, 1024) holds the 2 U (NV / 2 + NV) = 96
 // dwords of NV 4, not 192 or 384 - the registers the longer vectors need go to lq, c, l and s instead.
@@ -562,6 +674,19 @@ void launch_sgm_cost_bt(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int
     case 11: launch_bt_bs<5, true>(s, a, tab, n); break;
     case 14: launch_bt_bs<7, false>(s, a, tab, n); break;
     default: launch_bt_bs<7, true>(s, a, tab, n); break;
+    }
+}
+
+void launch_sgm_cost_census(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
+{
+    sgm_launch(s, k_sgm_census, k_sgm_census_b, dim3((a.W + SGM_CEN_TX - 1) / SGM_CEN_TX, (a.H + SGM_CEN_TY - 1) / SGM_CEN_TY, 2),
+               dim3(SGM_CEN_TX * SGM_CEN_TY), a, tab, 2 * n);
+    const dim3 grid((a.W + SGM_TX - 1) / SGM_TX, a.H), block(sgm_cost_threads(a.D));
+    switch (a.bs) {
+    case 1: sgm_launch(s, k_sgm_census_cost<1>, k_sgm_census_cost_b<1>, grid, block, a, tab, n); break;
+    case 3: sgm_launch(s, k_sgm_census_cost<3>, k_sgm_census_cost_b<3>, grid, block, a, tab, n); break;
+    case 5: sgm_launch(s, k_sgm_census_cost<5>, k_sgm_census_cost_b<5>, grid, block, a, tab, n); break;
+    default: sgm_launch(s, k_sgm_census_cost<7>, k_sgm_census_cost_b<7>, grid, block, a, tab, n); break;
     }
 }
 

@@ -142,7 +142,7 @@ class DispEst:
     # ---- the second algorithm: STEREO_SGBM (src/StereoMatch.cpp:169-187) ----------------------
     def SGBM_GPU(self, block_size: int = 0, P1: int = 0, P2: int = 0, uniqueness_ratio: int = 10, disp12_max_diff: int = 1,
                  gray=None, speckle_window_size: int = 0, speckle_range: int = 0, pre_filter_cap: int = 0, mode="hh",
-                 min_disparity: int = 0, num_disparities: int = 0):
+                 min_disparity: int = 0, num_disparities: int = 0, census=None):
         """ssgbm->compute(lFrame, rFrame, imgDisparity16S) on the device over the pair setInputImages staged, with the
         parameters of setupOpenCVSGBM (src/StereoMatch.cpp:639-660) as defaults (0: blockSize 5, P1 = 8 ch bs^2, P2 = 32 ch bs^2).
         -> H x W int16: disparity * 16, -16 where invalid.  An independent stage (psm_sgm_compute): the maps, masks and volumes
@@ -155,7 +155,11 @@ class DispEst:
         (psm_sgm_set_mode) - this call's setting as well.
         min_disparity, num_disparities: StereoSGBM::create's first two arguments (psm_sgm_set_range) - the disparities
         min_disparity .. min_disparity + num_disparities - 1, num_disparities in 2 .. 1024 whatever maxDis is, or 0, the default:
-        maxDis; invalid pixels are then (min_disparity - 1) * 16.  This call's setting as well."""
+        maxDis; invalid pixels are then (min_disparity - 1) * 16.  This call's setting as well.
+        census = (win_w, win_h), both odd, 3 .. 9 by 3 .. 7: the pixel cost is the Hamming distance of census codes
+        (psm_sgm_set_census), which does not change when the two cameras differ in gain or exposure; None or (0, 0), the default:
+        off - this call's setting too.  Refused together with pre_filter_cap > 0."""
+        self._ck(self._lib.psm_sgm_set_census(self._h, *census_window(census)), "SGBM_GPU")
         self._ck(self._lib.psm_sgm_set_mode(self._h, sgm_mode(mode)), "SGBM_GPU")
         self._ck(self._lib.psm_sgm_set_range(self._h, int(min_disparity), int(num_disparities)), "SGBM_GPU")
         self._sgm_d = int(num_disparities) or self.maxDis
@@ -195,6 +199,13 @@ class DispEst:
         self._ck(self._lib.psm_sgm_download_prefiltered(self._h, int(side), _ptr(planes)), "sgm_prefiltered")
         ch = self._sgm_ch
         return planes.reshape(-1)[:self.hei * self.wid * 2 * ch].reshape(self.hei, self.wid, 2 * ch).copy()
+
+    def sgm_census(self, side: int):
+        """Test hook: the census codes [H][W] uint64 of the left (side 0) or right (1) image in the last SGBM_GPU, which must have
+        run with census=(win_w, win_h)."""
+        codes = np.empty((self.hei, self.wid), np.uint64)
+        self._ck(self._lib.psm_sgm_download_census(self._h, int(side), _ptr(codes)), "sgm_census")
+        return codes
 
     def sgm_times(self):
         """(cost, paths, select + check) device ms of the last SGBM_GPU; needs PSM_OPT_PROFILE."""
@@ -594,17 +605,26 @@ def sgm_mode(mode):
     return int(mode)
 
 
+def census_window(census):
+    """SGBM_GPU's census=: None is (0, 0), off; a pair is passed on as it is (psm_sgm_set_census refuses what it does not know)."""
+    if census is None:
+        return 0, 0
+    win_w, win_h = census
+    return int(win_w), int(win_h)
+
+
 def sgbm_batch(des, block_size: int = 0, P1: int = 0, P2: int = 0, uniqueness_ratio: int = 10, disp12_max_diff: int = 1,
                speckle_window_size: int = 0, speckle_range: int = 0, pre_filter_cap: int = 0, mode="hh", min_disparity: int = 0,
-               num_disparities: int = 0):
+               num_disparities: int = 0, census=None):
     """SGBM_GPU of several DispEst objects of one geometry in shared launches (psm_sgm_compute_batch): the parameters (SGBM_GPU's,
     without gray=) are set on every object, each object's own staged pair goes through the stage, -> the list of H x W int16 maps.
-    Every object afterwards behaves as after its own SGBM_GPU (sgm_costs(), sgm_prefiltered(), sgm_speckle_sizes(), ...); the
+    Every object afterwards behaves as after its own SGBM_GPU (sgm_costs(), sgm_prefiltered(), sgm_census(), sgm_speckle_sizes(), ...); the
     times of the batch are des[0]'s (sgm_times(), sgm_speckle_time() under PSM_OPT_PROFILE)."""
     des = list(des)
     if not des:
         return []
     for d in des:
+        d._ck(d._lib.psm_sgm_set_census(d._h, *census_window(census)), "sgbm_batch")
         d._ck(d._lib.psm_sgm_set_mode(d._h, sgm_mode(mode)), "sgbm_batch")
         d._ck(d._lib.psm_sgm_set_range(d._h, int(min_disparity), int(num_disparities)), "sgbm_batch")
         d._sgm_d = int(num_disparities) or d.maxDis

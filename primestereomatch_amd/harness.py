@@ -123,7 +123,7 @@ def compute_sgbm(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, er
     """One frame of STEREO_SGBM (src/StereoMatch.cpp:169-187, 275-309) on the device: l_bgr / r_bgr H x W x 3, uint8 or float32
     scaled by 1/255 (quantised on the device as lFrame.convertTo(lFrame, CV_8U, 255) does); params: DispEst.SGBM_GPU's, forwarded
     as they are - the reference's whole configuration is pre_filter_cap=63, speckle_window_size=100, speckle_range=32 (the
-    defaults: SAD cost, no speckle filter); min_disparity / num_disparities choose another range than [0, maxDis), up to 1024
+    defaults: SAD cost, no speckle filter), census=(win_w, win_h) selects the census cost; min_disparity / num_disparities choose another range than [0, maxDis), up to 1024
     disparities (the display conversion works from the map's own minimum and maximum).
     -> disp16 (imgDisparity16S), lDispMap (the display map), the reference's error metric on it, and bp_percent_int.
     device_tail: display map and both metrics from the device (DispEst.Score_GPU, PSM_SCORE_SGM and PSM_SCORE_SGM_INT)."""

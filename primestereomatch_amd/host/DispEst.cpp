@@ -283,6 +283,12 @@ int DispEst::setSGBMRange(int minDisparity, int numDisparities)
     return hipUtil::api().sgm_set_range(ctx[0], minDisparity, numDisparities);
 }
 
+int DispEst::setSGBMCensus(int winW, int winH)
+{
+    if (ctx.empty()) return 1;
+    return hipUtil::api().sgm_set_census(ctx[0], winW, winH);
+}
+
 int DispEst::sgbmSpeckleTime(double *ms)
 {
     if (ctx.empty()) return 1;

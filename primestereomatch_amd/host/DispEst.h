@@ -127,6 +127,10 @@ public:
     // setting of a new object: maxDis.  Invalid pixels of the map are (minDisparity - 1) * 16.  SGBMBatch wants one range on all
     // its objects.
     int setSGBMRange(int minDisparity, int numDisparities);
+    // The census cost for every following SGBM_GPU (psm_sgm_set_census): the Hamming distance of census codes over a winW x winH
+    // window, both odd, 3 .. 9 by 3 .. 7 - unchanged when the two cameras differ in gain or exposure.  (0, 0), the setting of a new
+    // object: off.  Refused by SGBM_GPU together with a preFilterCap > 0.  SGBMBatch wants one window on all its objects.
+    int setSGBMCensus(int winW, int winH);
 
     // The steps of StereoMatch::compute behind the maps, on the device (psm_score): setGroundTruth uploads the dataset's ground truth
     // and (mask non-NULL) error mask once, H x W CV_8UC1 each; setScoreParams: scale_factor, error_threshold, PSM_MASK_NONE / NONOCC /

@@ -1,6 +1,6 @@
 // psm_demo - headless counterpart of the reference's StereoMatch::compute accelerator branch
 // (src/StereoMatch.cpp:193-262): raw B,G,R uint8 pair in, four timed stages, raw uint8 maps out.
-//   psm_demo <left.raw> <right.raw> <W> <H> <maxDis> <out_prefix> [ndev] [f32|u8] [float_input] [fgf_rate] [pp] [frames] [batch] [ring] [sgbm|sgbm_ref|-] [gt.raw] [mask.raw|-]
+//   psm_demo <left.raw> <right.raw> <W> <H> <maxDis> <out_prefix> [ndev] [f32|u8] [float_input] [fgf_rate] [pp] [frames] [batch] [ring] [sgbm|sgbm_ref|sgbm_census|-] [gt.raw] [mask.raw|-]
 // gt.raw (the 16th argument; W x H bytes, mask.raw likewise): the left map - after pp, if given - is scored on the device
 // (DispEst::Score: scale_factor 4, error_threshold 4, the non-occluded mask if one is given) and the reference's line
 // "%BP = ... Avg Err = ..." (src/StereoMatch.cpp:306) is printed from the device record; the display map and the error plane go to
@@ -8,7 +8,8 @@
 // sgbm: the 15th argument, the word "sgbm": additionally run the second algorithm (DispEst::SGBM_GPU: the STEREO_SGBM branch,
 // src/StereoMatch.cpp:169-187) on the pair, print its three device times and dump the int16 map as <out>_sgbm16.raw (the SAD
 // cost, no speckle filter); the word "sgbm_ref": the same with the whole configuration of setupOpenCVSGBM (:639-660) -
-// preFilterCap 63, speckleWindowSize 100, speckleRange 32 - and the filter's time as a fourth line
+// preFilterCap 63, speckleWindowSize 100, speckleRange 32 - and the filter's time as a fourth line; the word "sgbm_census": the
+// settings of sgbm with the census cost over a 9 x 7 window (DispEst::setSGBMCensus), nothing else changed
 // ring > 0: additionally push that many frames of the pair through a psm::FrameRing of two objects (two frames in flight, each
 // object told PSM_OPT_FRAMES_IN_FLIGHT = 2), check every delivered frame's maps against the single-pair run, dump <out>_ldisp_ring.raw
 // batch > 1: additionally run that many copies of the pair as ONE batch (DispEst::computeBatch -> psm_compute_batch: the
@@ -51,7 +52,7 @@ static bool dump(const std::string &path, const unsigned char *p, size_t n)
 int main(int argc, char **argv)
 {
     if (argc < 7) {
-        fprintf(stderr, "usage: %s left.raw right.raw W H maxDis out_prefix [ndev] [f32|u8] [float_input] [fgf_rate] [pp] [frames] [batch] [ring] [sgbm|sgbm_ref|-] [gt.raw] [mask.raw|-]\n", argv[0]);
+        fprintf(stderr, "usage: %s left.raw right.raw W H maxDis out_prefix [ndev] [f32|u8] [float_input] [fgf_rate] [pp] [frames] [batch] [ring] [sgbm|sgbm_ref|sgbm_census|-] [gt.raw] [mask.raw|-]\n", argv[0]);
         return 2;
     }
     const int W = atoi(argv[3]), H = atoi(argv[4]), D = atoi(argv[5]);
@@ -65,7 +66,8 @@ int main(int argc, char **argv)
     const int batch = argc > 13 ? atoi(argv[13]) : 0;
     const int nring = argc > 14 ? atoi(argv[14]) : 0;
     const bool sgbm_ref = argc > 15 && !strcmp(argv[15], "sgbm_ref");
-    const bool sgbm = sgbm_ref || (argc > 15 && !strcmp(argv[15], "sgbm"));
+    const bool sgbm_census = argc > 15 && !strcmp(argv[15], "sgbm_census");
+    const bool sgbm = sgbm_ref || sgbm_census || (argc > 15 && !strcmp(argv[15], "sgbm"));
     const char *gt_path = argc > 16 ? argv[16] : nullptr;
     const char *mask_path = argc > 17 && strcmp(argv[17], "-") ? argv[17] : nullptr;
     std::vector<unsigned char> lraw, rraw, gtraw, maskraw;
@@ -178,6 +180,7 @@ int main(int argc, char **argv)
         double ms[3] = {0, 0, 0};
         SMDE.setInputImages(l, r);
         if (sgbm_ref && (SMDE.setSGBMPreFilterCap(63) || SMDE.setSGBMSpeckle(100, 32))) return 5;
+        if (sgbm_census && SMDE.setSGBMCensus(9, 7)) return 5;
         if (SMDE.setOption(PSM_OPT_PROFILE, 1) || SMDE.SGBM_GPU(d16) || SMDE.sgbmTimes(ms)) return 5;
         printf("STEREO SGBM Times:\nCost Time:\t %4.3f ms\nPaths Time:\t %4.3f ms\nSelect Time:\t %4.3f ms\n", ms[0], ms[1], ms[2]);
         if (sgbm_ref) {
@@ -198,7 +201,8 @@ int main(int argc, char **argv)
             bool set = true;
             for (int b = 0; b < batch; ++b) {
                 des.push_back(new psm::DispEst(l, r, D, 8, true, 1, dtype));
-                set = set && des[b]->ok() && !(sgbm_ref && (des[b]->setSGBMPreFilterCap(63) || des[b]->setSGBMSpeckle(100, 32)));
+                set = set && des[b]->ok() && !(sgbm_ref && (des[b]->setSGBMPreFilterCap(63) || des[b]->setSGBMSpeckle(100, 32))) &&
+                      !(sgbm_census && des[b]->setSGBMCensus(9, 7));
             }
             std::vector<std::vector<int16_t>> maps;
             double bms[3] = {0, 0, 0};

@@ -27,6 +27,12 @@ The prefiltered Birchfield-Tomasi cost (psm_sgm_set_prefilter; k_sgm_prefilter, 
 is timed a third time in the same process at pre_filter_cap 63 with the filter off - the three group times as "*_ms_cap63" (the
 cost group holds the prefilter), their ratio to the SAD cost group, and the 12 W H bytes of planes the stage then holds.
 
+--census W,H: the census cost (psm_sgm_set_census; k_sgm_census, k_sgm_census_cost): every configuration is timed once more in the
+same process with that window, at pre_filter_cap 0 with the filter off - the three group times as "*_ms_census" (the cost group
+holds the census transform), the cost group over the SAD and the Birchfield-Tomasi cost groups of the same process, the 16 W H
+bytes of codes the stage then holds, and the floor of the cost group - C written once, 2 W H Dp bytes at the copy ceiling - over
+its time.  With --batch the census cost is a third setting beside pre_filter_cap 0 and 63; --num-disparities works as ever.
+
 --batch N[,N...]: instead of the above, several pairs per launch (psm_sgm_compute_batch).  Per configuration (450 x 375 x 64 and
 1280 x 720 x 128 at the batch sizes given; 1920 x 1080 x 256, 3.2 GB per context, at those of them that are 2 or 4), at
 pre_filter_cap 0 and 63 with the speckle filter on at (100, 32): per-pair ms of the three groups and of the filter for the batch
@@ -128,8 +134,8 @@ def batch_bench(a):
         try:
             for de in des:
                 de.set_option(capi.PSM_OPT_PROFILE, 1)
-            for cap in (0, 63):
-                kw = dict(pre_filter_cap=cap, speckle_window_size=100, speckle_range=32)
+            for cap, census in [(0, None), (63, None)] + ([(0, a.census)] if a.census else []):
+                kw = dict(pre_filter_cap=cap, census=census, speckle_window_size=100, speckle_range=32)
                 for n in ns:
                     sub = des[:n]
 
@@ -163,6 +169,8 @@ def batch_bench(a):
                         b_t, b_w = batch()
                         rec = {"bench": "sgm_batch", "config": name, "W": W, "H": H, "D": D, "pre_filter_cap": cap, "speckle": [100, 32],
                                "batch": n, "rep": rep_i, "runs": a.runs, "warmup": a.warmup, "maps_equal_singles": bool(same)}
+                        if census:
+                            rec["census"] = list(census)
                         for tag, t, w in (("singles", s_t, s_w), ("batch", b_t, b_w)):
                             rec[tag + "_per_pair_ms"] = {"cost": round(float(t[0]), 4), "paths": round(float(t[1]), 4), "select": round(float(t[2]), 4),
                                                          "speckle": round(float(t[3]), 4), "total": round(float(t.sum()), 4), "wall": round(w, 4)}
@@ -247,9 +255,13 @@ def main():
     ap.add_argument("--mode", default=None, help="M[,M...] of sgbm, 3way, hh4: time these modes beside hh (modes_bench)")
     ap.add_argument("--min-disparity", type=int, default=0, help="psm_sgm_set_range: the first disparity")
     ap.add_argument("--num-disparities", type=int, default=0, help="psm_sgm_set_range: their number, up to 1024 (0: the configuration's D)")
+    ap.add_argument("--census", default=None, help="W,H: also time the census cost with this window (psm_sgm_set_census)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert a.runs >= 1
+    a.census = tuple(int(v) for v in a.census.split(",")) if a.census else None
+    if a.census and a.mode:
+        raise SystemExit("sgm_bench: --census goes with the plain record and with --batch")
     if (a.mode or a.batch) and (a.min_disparity or a.num_disparities):
         raise SystemExit("sgm_bench: --min-disparity / --num-disparities go with the plain record only")
     if a.mode:
@@ -299,6 +311,14 @@ def main():
                     de._ck(de._lib.psm_sgm_compute(de._h), "psm_sgm_compute")      # (the setting holds)
                     tb.append(de.sgm_times())
                 valid_bt = float((de.sgm_disparity() != invalid).mean())
+                tc = []
+                if a.census:
+                    for _ in range(a.warmup):
+                        de.SGBM_GPU(census=a.census, **rng)
+                    for _ in range(a.runs):
+                        de._ck(de._lib.psm_sgm_compute(de._h), "psm_sgm_compute")      # (the setting holds)
+                        tc.append(de.sgm_times())
+                    valid_census = float((de.sgm_disparity() != invalid).mean())
             t = np.array(t)
             meds = np.median(np.array(ts), axis=0)
             medb = np.median(np.array(tb), axis=0)
@@ -316,6 +336,14 @@ def main():
                         "select_ms_cap63": round(float(medb[2]), 4), "cost_cap63_over_sad": round(float(medb[0] / med[0]), 2),
                         "cost_cap63_over_paths": round(float(medb[0] / medb[1]), 3), "prefiltered_bytes_held": 12 * W * H,
                         "valid_fraction_cap63": round(valid_bt, 4)})
+            if tc:
+                medc = np.median(np.array(tc), axis=0)
+                floor_ms = 2 * W * H * Dp / COPY_CEILING * 1e3
+                rec.update({"census": list(a.census), "cost_ms_census": round(float(medc[0]), 4), "paths_ms_census": round(float(medc[1]), 4),
+                            "select_ms_census": round(float(medc[2]), 4), "cost_census_over_sad": round(float(medc[0] / med[0]), 2),
+                            "cost_census_over_cap63": round(float(medc[0] / medb[0]), 2), "census_bytes_held": 16 * W * H,
+                            "cost_census_floor_ms": round(floor_ms, 4), "cost_census_fraction_of_floor": round(float(floor_ms / medc[0]), 3),
+                            "valid_fraction_census": round(valid_census, 4)})
         if a.model or a.model_only:
             rec["numpy_model_s"] = round(model_seconds(l, r, D), 2)
         line = json.dumps(rec)
