@@ -8,6 +8,9 @@
 // cost as tests/sgm_bt_model.py defines it (the reference: preFilterCap 63), or, after psm_sgm_set_census, the Hamming distance
 // of census codes (tests/sgm_census_model.py).  Unpinned in all of it: a live cv::StereoSGBM.
 // psm_sgm_compute_batch: the same launches for the pairs of several contexts at once, the pair on a grid axis of its own.
+// Single pairs and batches share the launch sequence (enqueue), the record of a pair's buffers (pair_of), the name of the pixel
+// cost (cost_kind) and what a context forgets ahead of the launches and holds behind them (forget, mark); the entry points keep
+// what differs - argument checks, the gray upload, a batch's cross-context checks, stream ordering and table.
 #include "psm_ctx.h"
 
 #include <cstdio>
@@ -86,6 +89,21 @@ int check_cost(psm_ctx *e, const psm_ctx *c, const char *who)
     return 0;
 }
 
+// ... and which one a context that passed is set to: the only place that reads the two settings for it.  Buffers, arguments,
+// launchers, the kernel names of check_launch and the marks of a result all go by this.
+enum class SgmCost { SAD, BT, CENSUS };
+SgmCost cost_kind(const SgmState &g) { return g.cen_w > 0 ? SgmCost::CENSUS : (g.cap > 0 ? SgmCost::BT : SgmCost::SAD); }
+
+int ensure_speckle_planes(psm_ctx *c)
+{
+    SgmState &g = c->sgm;
+    const size_t HW = (size_t)c->W * c->H;
+    if (!g.spk_label) PSM_HIP(c, hipMalloc((void **)&g.spk_label, HW * sizeof(unsigned)));
+    if (!g.spk_size) PSM_HIP(c, hipMalloc((void **)&g.spk_size, HW * sizeof(unsigned)));
+    return 0;
+}
+
+// everything a compute of this context's settings touches, the events of a timed one included
 int ensure_buffers(psm_ctx *c)
 {
     SgmState &g = c->sgm;
@@ -104,46 +122,51 @@ int ensure_buffers(psm_ctx *c)
     if (!g.disp2) PSM_HIP(c, hipMalloc((void **)&g.disp2, HW * sizeof(uint32_t)));
     if (!g.pre) PSM_HIP(c, hipMalloc((void **)&g.pre, HW * sizeof(int16_t)));
     if (!g.out) PSM_HIP(c, hipMalloc((void **)&g.out, HW * sizeof(int16_t)));
-    if (g.cap > 0)
+    switch (cost_kind(g)) {
+    case SgmCost::BT:
         for (uint8_t *&p : g.pf)
             if (!p) PSM_HIP(c, hipMalloc((void **)&p, HW * 6));
-    if (g.cen_w > 0)
+        break;
+    case SgmCost::CENSUS:
         for (uint64_t *&p : g.cen)
             if (!p) PSM_HIP(c, hipMalloc((void **)&p, HW * sizeof(uint64_t)));
+        break;
+    case SgmCost::SAD: break;
+    }
+    if (g.spk_window > 0 && ensure_speckle_planes(c)) return 1;
     if (c->opt_profile)
         for (hipEvent_t &e : g.ev)
             if (!e) PSM_HIP(c, hipEventCreate(&e));
     return 0;
 }
 
-// the context's buffers (ensure_buffers) and settings as the kernels take them
-SgmArgs sgm_args(const psm_ctx *c, const void *l, const void *r, int depth, int ch, int p1, int p2)
+// One pair's buffers (ensure_buffers) as the kernels take them: the record of a batch's device table, and what a single pair's
+// SgmArgs point to.  l, r: the staged pair, or psm_sgm_compute_gray's.
+SgmPair pair_of(const psm_ctx *c, const void *l, const void *r)
 {
     const SgmState &g = c->sgm;
-    SgmArgs a;
-    a.img[0] = l; a.img[1] = r; a.depth = depth; a.ch = ch;
-    a.C = g.C; a.S = g.S; a.disp2 = g.disp2; a.pre = g.pre; a.out = g.out;
+    SgmPair p{{l, r}, g.C, g.S, g.disp2, g.pre, g.out, {nullptr, nullptr}, nullptr, nullptr};
+    switch (cost_kind(g)) {
+    case SgmCost::BT: p.pf[0] = g.pf[0]; p.pf[1] = g.pf[1]; break;
+    case SgmCost::CENSUS: p.pf[0] = (uint8_t *)g.cen[0]; p.pf[1] = (uint8_t *)g.cen[1]; break;      // the code planes travel in the pf slots
+    case SgmCost::SAD: break;
+    }
+    if (g.spk_window > 0) { p.spk_label = g.spk_label; p.spk_size = g.spk_size; }
+    return p;
+}
+
+// the context's settings as the kernels take them; the pointers stay null: a single pair's are set by enqueue, a batch's are the table's
+SgmArgs sgm_args(const psm_ctx *c, int depth, int ch, int p1, int p2)
+{
+    const SgmState &g = c->sgm;
+    SgmArgs a = {};
+    a.depth = depth; a.ch = ch;
     a.W = c->W; a.H = c->H; a.D = sgm_d(c); a.Dp = sgm_dp(c);
     a.dmin = g.dmin; a.invalid = sgm_invalid(c);
     a.bs = g.bs; a.P1 = p1; a.P2 = p2; a.u = g.u; a.m = g.m;
-    a.pf[0] = a.pf[1] = nullptr; a.Hs = nullptr; a.ft = 0;
-    if (g.cap > 0) {
-        a.pf[0] = g.pf[0]; a.pf[1] = g.pf[1];
-        a.Hs = (uint16_t *)g.S;                           // S is free until the first direction stores it
-        a.ft = (g.cap > 15 ? g.cap : 15) | 1;
-    }
+    if (cost_kind(g) == SgmCost::BT) a.ft = (g.cap > 15 ? g.cap : 15) | 1;
     a.cw = g.cen_w; a.chh = g.cen_h;
-    if (g.cen_w > 0) { a.pf[0] = (uint8_t *)g.cen[0]; a.pf[1] = (uint8_t *)g.cen[1]; }      // (the code planes travel in the pf slots)
     return a;
-}
-
-int ensure_speckle_planes(psm_ctx *c)
-{
-    SgmState &g = c->sgm;
-    const size_t HW = (size_t)c->W * c->H;
-    if (!g.spk_label) PSM_HIP(c, hipMalloc((void **)&g.spk_label, HW * sizeof(unsigned)));
-    if (!g.spk_size) PSM_HIP(c, hipMalloc((void **)&g.spk_size, HW * sizeof(unsigned)));
-    return 0;
 }
 
 // the filter's settings as the kernels take them (the planes: the caller's)
@@ -157,74 +180,105 @@ SpkArgs speckle_args(const psm_ctx *c, int new_val, int max_size, long long max_
     return a;
 }
 
-// The speckle filter on `map` (a device plane of the context's size) in place, on the context's stream: four launches, nothing
-// read back.  t0 / ev[4]: the events that bracket it when the run is timed (t0 is already recorded).
-int enqueue_speckle(psm_ctx *c, int16_t *map, int new_val, int max_size, long long max_diff, int t0)
+// The speckle filter in place on stream s - on the map of `a`, or on the `out` maps of the table's n pairs: four launches, nothing
+// read back.  timed: the event behind them is c's ev[4] (the one ahead is already recorded).
+int enqueue_speckle(psm_ctx *c, hipStream_t s, const SpkArgs &a, const SgmPair *tab, int n, bool timed)
 {
-    SgmState &g = c->sgm;
-    if (ensure_speckle_planes(c)) return 1;
-    SpkArgs a = speckle_args(c, new_val, max_size, max_diff);
-    a.map = map; a.label = g.spk_label; a.size = g.spk_size;
-    g.spk_have = false;
-    g.spk_t0 = -1;
-    launch_speckle(c->stream, a);
-    if (check_launch(c, "k_spk_*")) return 1;
-    if (t0 >= 0) PSM_HIP(c, hipEventRecord(g.ev[4], c->stream));
-    g.spk_have = true;
-    g.spk_t0 = t0;
+    launch_speckle(s, a, tab, n);
+    if (check_launch(c, tab ? "k_spk_*_b" : "k_spk_*")) return 1;
+    if (timed) PSM_HIP(c, hipEventRecord(c->sgm.ev[4], s));
     return 0;
 }
 
-// the directions of the context's mode in table order; the first launch stores S, so no sum of an earlier frame or mode survives
-void launch_paths(const psm_ctx *c, hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
+// ahead of a compute's launches a context forgets its previous result (every check and allocation lies before this) ...
+void forget(SgmState &g)
 {
-    const int mode = c->sgm.mode;
-    for (int i = 0; i < SGM_MODE_NDIR[mode]; ++i) {
-        const int *r = SGM_DIRS[SGM_MODE_DIRS[mode][i]];
-        launch_sgm_path(s, a, r[0], r[1], i == 0, tab, n);
+    g.have = g.timed = false;
+    g.spk_t0 = -1;
+    g.pf_ch = 0;
+    g.cen_have = false;
+    if (g.spk_window > 0) g.spk_have = false;             // (with the filter off, the sizes of an earlier run stay readable)
+}
+
+// ... and behind them it holds the result of this cost on `ch` channels over D disparities; timed: its own events bracketed them
+void mark(SgmState &g, SgmCost kind, int ch, int D, bool timed)
+{
+    g.have = true;
+    g.res_d = D;
+    g.timed = timed;
+    g.pf_ch = kind == SgmCost::BT ? ch : 0;
+    g.cen_have = kind == SgmCost::CENSUS;
+    if (g.spk_window > 0) {
+        g.spk_have = true;
+        g.spk_t0 = timed ? 3 : -1;
     }
 }
 
-// cost, the mode's directions, select + check, the speckle filter if it is on, on the context's stream
-int enqueue(psm_ctx *c, const char *who, const void *l, const void *r, int depth, int ch)
+// The launches of a compute, for a single pair and for a batch alike: disp2 reset, the cost group, the mode's directions, select
+// and check, the speckle filter if it is on - on stream s, with c's settings, events (PSM_OPT_PROFILE) and error slot.  `one`:
+// the single pair's record; else the device table `tab` of n pairs, c being the batch's first context.  `a` brings the scalars.
+// What the two deliberately do differently:
+//   - a single pair resets disp2 with hipMemsetAsync, a batch with k_sgm_fill_b (one launch for the n planes);
+//   - a batch is bracketed by its first context's events only: that context alone counts as timed (psm_sgm_compute_batch);
+//   - psm_sgm_compute_gray comes with ch 1 in `a`, which has also resolved its P1 / P2 defaults (check_params);
+//   - a batch reports a member's allocation failure on its first context, as "...: context i: <the member's message>" - by its
+//     caller, as every check and allocation: nothing here can fail but a launch or an event.
+int enqueue(psm_ctx *c, hipStream_t s, SgmArgs a, const SgmPair *one, const SgmPair *tab, int n)
+{
+    static const char *const cost_kernels[3][2] = {{"k_sgm_cost", "k_sgm_fill_b, k_sgm_cost_b"},
+                                                   {"k_sgm_prefilter, k_sgm_bt_*", "k_sgm_fill_b, k_sgm_prefilter_b, k_sgm_bt_*_b"},
+                                                   {"k_sgm_census, k_sgm_census_cost", "k_sgm_fill_b, k_sgm_census_b, k_sgm_census_cost_b"}};
+    SgmState &g = c->sgm;
+    const SgmCost kind = cost_kind(g);
+    const bool timed = c->opt_profile != 0, batch = tab != nullptr;
+    if (one) {
+        a.img[0] = one->img[0]; a.img[1] = one->img[1];
+        a.C = one->C; a.S = one->S; a.disp2 = one->disp2; a.pre = one->pre; a.out = one->out;
+        a.pf[0] = one->pf[0]; a.pf[1] = one->pf[1];
+        a.Hs = (uint16_t *)a.S;                           // S is free until the first direction stores it (a batch: sgm_pair_args)
+    }
+    // disp2 starts every frame as "nothing lands here"
+    if (batch) launch_sgm_fill_batch(s, a, tab, n);
+    else PSM_HIP(c, hipMemsetAsync(a.disp2, 0xff, (size_t)a.W * a.H * sizeof(uint32_t), s));
+    if (timed) PSM_HIP(c, hipEventRecord(g.ev[0], s));
+    switch (kind) {
+    case SgmCost::SAD: launch_sgm_cost(s, a, tab, n); break;
+    case SgmCost::BT: launch_sgm_cost_bt(s, a, tab, n); break;
+    case SgmCost::CENSUS: launch_sgm_cost_census(s, a, tab, n); break;
+    }
+    if (check_launch(c, cost_kernels[(int)kind][batch])) return 1;
+    if (timed) PSM_HIP(c, hipEventRecord(g.ev[1], s));
+    // the directions of the mode in table order; the first launch stores S, so no sum of an earlier frame or mode survives
+    for (int i = 0; i < SGM_MODE_NDIR[g.mode]; ++i) {
+        const int *r = SGM_DIRS[SGM_MODE_DIRS[g.mode][i]];
+        launch_sgm_path(s, a, r[0], r[1], i == 0, tab, n);
+    }
+    if (check_launch(c, batch ? "k_sgm_path_b" : "k_sgm_path")) return 1;
+    if (timed) PSM_HIP(c, hipEventRecord(g.ev[2], s));
+    launch_sgm_select(s, a, tab, n);
+    if (check_launch(c, batch ? "k_sgm_select_b" : "k_sgm_select")) return 1;
+    if (timed) PSM_HIP(c, hipEventRecord(g.ev[3], s));
+    if (g.spk_window > 0) {
+        // filterSpeckles(disp, (minDisparity - 1) * 16, speckleWindowSize, 16 * speckleRange), as StereoSGBM ends
+        SpkArgs k = speckle_args(c, a.invalid, g.spk_window, 16ll * g.spk_range);
+        if (one) { k.map = one->out; k.label = one->spk_label; k.size = one->spk_size; }
+        if (enqueue_speckle(c, s, k, tab, n, timed)) return 1;
+    }
+    return 0;
+}
+
+// a single pair of `ch` channels through the stage on the context's stream (psm_sgm_compute, psm_sgm_compute_gray)
+int compute_one(psm_ctx *c, const char *who, const void *l, const void *r, int depth, int ch)
 {
     SgmState &g = c->sgm;
     int p1 = g.p1, p2 = g.p2;
     if (check_params(c, who, ch, g.bs, &p1, &p2, g.u)) return 1;
     if (ensure_buffers(c)) return 1;
-    const SgmArgs a = sgm_args(c, l, r, depth, ch, p1, p2);
-    const bool timed = c->opt_profile != 0;
-    g.have = g.timed = false;
-    g.spk_t0 = -1;
-    g.pf_ch = 0;
-    g.cen_have = false;
-    // disp2 starts every frame as "nothing lands here", on the stream
-    PSM_HIP(c, hipMemsetAsync(g.disp2, 0xff, (size_t)c->W * c->H * sizeof(uint32_t), c->stream));
-    if (timed) PSM_HIP(c, hipEventRecord(g.ev[0], c->stream));
-    if (g.cen_w > 0) {
-        launch_sgm_cost_census(c->stream, a);
-        if (check_launch(c, "k_sgm_census, k_sgm_census_cost")) return 1;
-        g.cen_have = true;
-    } else if (g.cap > 0) {
-        launch_sgm_cost_bt(c->stream, a);
-        if (check_launch(c, "k_sgm_prefilter, k_sgm_bt_*")) return 1;
-        g.pf_ch = ch;
-    } else {
-        launch_sgm_cost(c->stream, a);
-        if (check_launch(c, "k_sgm_cost")) return 1;
-    }
-    if (timed) PSM_HIP(c, hipEventRecord(g.ev[1], c->stream));
-    launch_paths(c, c->stream, a, nullptr, 1);
-    if (check_launch(c, "k_sgm_path")) return 1;
-    if (timed) PSM_HIP(c, hipEventRecord(g.ev[2], c->stream));
-    launch_sgm_select(c->stream, a);
-    if (check_launch(c, "k_sgm_select")) return 1;
-    if (timed) PSM_HIP(c, hipEventRecord(g.ev[3], c->stream));
-    // filterSpeckles(disp, (minDisparity - 1) * 16, speckleWindowSize, 16 * speckleRange), as StereoSGBM ends
-    if (g.spk_window > 0 && enqueue_speckle(c, g.out, a.invalid, g.spk_window, 16ll * g.spk_range, timed ? 3 : -1)) return 1;
-    g.have = true;
-    g.res_d = a.D;
-    g.timed = timed;
+    const SgmArgs a = sgm_args(c, depth, ch, p1, p2);
+    const SgmPair p = pair_of(c, l, r);
+    forget(g);
+    if (enqueue(c, c->stream, a, &p, nullptr, 1)) return 1;
+    mark(g, cost_kind(g), ch, a.D, c->opt_profile != 0);
     if (!c->opt_async) PSM_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -302,7 +356,7 @@ int psm_sgm_compute(psm_ctx *c)
     if (check_ctx(c, c, "psm_sgm_compute") || check_cost(c, c, "psm_sgm_compute")) return 1;
     if (c->raw_depth < 0) return fail(c, "psm_sgm_compute: no image pair (psm_upload_pair)");
     if (bind(c)) return 1;
-    return enqueue(c, "psm_sgm_compute", c->raw[0], c->raw[1], c->raw_depth, 3);
+    return compute_one(c, "psm_sgm_compute", c->raw[0], c->raw[1], c->raw_depth, 3);
 }
 
 int psm_sgm_compute_gray(psm_ctx *c, const uint8_t *l, const uint8_t *r, size_t stride_bytes)
@@ -321,7 +375,7 @@ int psm_sgm_compute_gray(psm_ctx *c, const uint8_t *l, const uint8_t *r, size_t 
         if (h2d_rows(c, g.gray[s], src[s], row, stride_bytes, c->H)) return 1;
     }
     PSM_HIP(c, hipStreamSynchronize(c->stream));      // the copy reads caller memory (psm_upload_pair)
-    return enqueue(c, "psm_sgm_compute_gray", g.gray[0], g.gray[1], PSM_IMG_U8, 1);
+    return compute_one(c, "psm_sgm_compute_gray", g.gray[0], g.gray[1], PSM_IMG_U8, 1);
 }
 
 // The launches of psm_sgm_compute with the pair on a grid axis of its own: n x (H, W or W + H - 1) one-wave paths per path launch
@@ -364,24 +418,17 @@ int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
     if (check_params(c0, who, 3, g0.bs, &p1, &p2, g0.u)) return 1;      // (every context's: they are context 0's)
     if (bind(c0)) return 1;
     hipStream_t s = c0->stream;
-    const bool timed = c0->opt_profile != 0, spk = g0.spk_window > 0, census = g0.cen_w > 0;
 
     // ---- buffers, events and the table's memory: before any launch, and before any context forgets its previous result ----
     for (int i = 0; i < n; ++i) {
         psm_ctx *c = ctxs[i];
-        if (ensure_buffers(c) || (spk && ensure_speckle_planes(c))) return c == c0 ? 1 : fail(c0, "%s: context %d: %s", who, i, c->err.c_str());
+        if (ensure_buffers(c)) return c == c0 ? 1 : fail(c0, "%s: context %d: %s", who, i, c->err.c_str());
         if (c->stream != s && !c->ev_batch) PSM_HIP(c0, hipEventCreateWithFlags(&c->ev_batch, hipEventDisableTiming));
     }
     if (!c0->ev_batch) PSM_HIP(c0, hipEventCreateWithFlags(&c0->ev_batch, hipEventDisableTiming));
     SgmState &t = c0->sgm;
     std::vector<SgmPair> tab((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        const psm_ctx *c = ctxs[i];
-        const SgmState &g = c->sgm;
-        uint8_t *const p0 = census ? (uint8_t *)g.cen[0] : (g.cap > 0 ? g.pf[0] : nullptr);      // (the code planes travel in the pf slots)
-        uint8_t *const p1 = census ? (uint8_t *)g.cen[1] : (g.cap > 0 ? g.pf[1] : nullptr);
-        tab[i] = SgmPair{{c->raw[0], c->raw[1]}, g.C, g.S, g.disp2, g.pre, g.out, {p0, p1}, spk ? g.spk_label : nullptr, spk ? g.spk_size : nullptr};
-    }
+    for (int i = 0; i < n; ++i) tab[i] = pair_of(ctxs[i], ctxs[i]->raw[0], ctxs[i]->raw[1]);
     const bool fresh = t.tab_host.size() != tab.size() || memcmp(t.tab_host.data(), tab.data(), tab.size() * sizeof(SgmPair)) != 0;
     if (fresh && t.tab_cap < tab.size()) {
         PSM_HIP(c0, hipStreamSynchronize(s));
@@ -418,49 +465,14 @@ int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
         PSM_HIP(c0, hipEventRecord(t.ev_tab[slot], s));
     }
 
-    for (int i = 0; i < n; ++i) {
-        SgmState &g = ctxs[i]->sgm;
-        g.have = g.timed = false;
-        g.spk_t0 = -1;
-        g.pf_ch = 0;
-        g.cen_have = false;
-        if (spk) g.spk_have = false;
-    }
-    const SgmArgs a = sgm_args(c0, nullptr, nullptr, c0->raw_depth, 3, p1, p2);      // (the scalars; the pointers are the table's)
-    launch_sgm_fill_batch(s, a, t.tab, n);
-    if (timed) PSM_HIP(c0, hipEventRecord(t.ev[0], s));
-    if (census) launch_sgm_cost_census(s, a, t.tab, n);
-    else if (g0.cap > 0) launch_sgm_cost_bt(s, a, t.tab, n);
-    else launch_sgm_cost(s, a, t.tab, n);
-    if (check_launch(c0, census ? "k_sgm_fill_b, k_sgm_census_b, k_sgm_census_cost_b"
-                                : (g0.cap > 0 ? "k_sgm_fill_b, k_sgm_prefilter_b, k_sgm_bt_*_b" : "k_sgm_fill_b, k_sgm_cost_b"))) return 1;
-    if (timed) PSM_HIP(c0, hipEventRecord(t.ev[1], s));
-    launch_paths(c0, s, a, t.tab, n);
-    if (check_launch(c0, "k_sgm_path_b")) return 1;
-    if (timed) PSM_HIP(c0, hipEventRecord(t.ev[2], s));
-    launch_sgm_select(s, a, t.tab, n);
-    if (check_launch(c0, "k_sgm_select_b")) return 1;
-    if (timed) PSM_HIP(c0, hipEventRecord(t.ev[3], s));
-    if (spk) {
-        launch_speckle(s, speckle_args(c0, a.invalid, g0.spk_window, 16ll * g0.spk_range), t.tab, n);
-        if (check_launch(c0, "k_spk_*_b")) return 1;
-        if (timed) PSM_HIP(c0, hipEventRecord(t.ev[4], s));
-    }
-
-    // ---- every context is now where its own psm_sgm_compute would have left it; only context 0 counts as timed ----
+    // ---- the launches; then every context is where its own psm_sgm_compute would have left it - only context 0 counts as timed ----
+    const SgmArgs a = sgm_args(c0, c0->raw_depth, 3, p1, p2);
+    for (int i = 0; i < n; ++i) forget(ctxs[i]->sgm);
+    if (enqueue(c0, s, a, nullptr, t.tab, n)) return 1;
     PSM_HIP(c0, hipEventRecord(c0->ev_batch, s));
     for (int i = 0; i < n; ++i) {
         psm_ctx *c = ctxs[i];
-        SgmState &g = c->sgm;
-        g.have = true;
-        g.res_d = a.D;
-        g.timed = timed && i == 0;
-        g.pf_ch = g0.cap > 0 ? 3 : 0;
-        g.cen_have = census;
-        if (spk) {
-            g.spk_have = true;
-            g.spk_t0 = timed && i == 0 ? 3 : -1;
-        }
+        mark(c->sgm, cost_kind(g0), 3, a.D, i == 0 && c0->opt_profile != 0);
         if (c->stream != s) PSM_HIP(c0, hipStreamWaitEvent(c->stream, c0->ev_batch, 0));
     }
     if (!c0->opt_async) PSM_HIP(c0, hipStreamSynchronize(s));
@@ -476,16 +488,7 @@ int psm_sgm_download_disparity(psm_ctx *c, int16_t *disp, size_t stride_bytes)
     if (stride_bytes == 0) stride_bytes = row;
     if (stride_bytes < row) return fail(c, "psm_sgm_download_disparity: stride %zu < row size %zu", stride_bytes, row);
     if (bind(c)) return 1;
-    if (stride_bytes == row) {
-        PSM_HIP(c, hipMemcpyAsync(disp, c->sgm.out, row * c->H, hipMemcpyDeviceToHost, c->stream));
-        PSM_HIP(c, hipStreamSynchronize(c->stream));
-    } else {
-        std::vector<int16_t> packed((size_t)c->W * c->H);
-        PSM_HIP(c, hipMemcpyAsync(packed.data(), c->sgm.out, row * c->H, hipMemcpyDeviceToHost, c->stream));
-        PSM_HIP(c, hipStreamSynchronize(c->stream));
-        for (int y = 0; y < c->H; ++y) memcpy((uint8_t *)disp + (size_t)y * stride_bytes, packed.data() + (size_t)y * c->W, row);
-    }
-    return 0;
+    return d2h_rows(c, disp, c->sgm.out, row, stride_bytes, c->H);
 }
 
 int psm_sgm_download_costs(psm_ctx *c, int which, void *host)
@@ -566,17 +569,23 @@ int psm_sgm_filter_speckles(psm_ctx *c, int16_t *disp, size_t stride_bytes, int 
     PSM_HIP(c, hipMalloc((void **)&map, row * c->H));
     int rc = h2d_rows(c, map, disp, row, stride_bytes, c->H);
     if (!rc && timed) rc = hipEventRecord(g.ev[5], c->stream) != hipSuccess ? fail(c, "psm_sgm_filter_speckles: hipEventRecord") : 0;
-    if (!rc) rc = enqueue_speckle(c, map, new_val, max_speckle_size, max_diff, timed ? 5 : -1);
-    std::vector<int16_t> packed;
+    if (!rc) rc = ensure_speckle_planes(c);
     if (!rc) {
-        packed.resize((size_t)c->W * c->H);
-        if (hipMemcpyAsync(packed.data(), map, row * c->H, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = fail(c, "psm_sgm_filter_speckles: copy back");
+        SpkArgs a = speckle_args(c, new_val, max_speckle_size, max_diff);
+        a.map = map; a.label = g.spk_label; a.size = g.spk_size;
+        g.spk_have = false;
+        g.spk_t0 = -1;
+        rc = enqueue_speckle(c, c->stream, a, nullptr, 1, timed);
+        if (!rc) {
+            g.spk_have = true;
+            g.spk_t0 = timed ? 5 : -1;
+        }
     }
+    // the filter has run before anything is written to the caller's map: a failure up to here leaves it untouched
     if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(c, "psm_sgm_filter_speckles: hipStreamSynchronize");
+    if (!rc) rc = d2h_rows(c, disp, map, row, stride_bytes, c->H);
     (void)hipFree(map);
-    if (rc) return 1;
-    for (int y = 0; y < c->H; ++y) memcpy((uint8_t *)disp + (size_t)y * stride_bytes, packed.data() + (size_t)y * c->W, row);
-    return 0;
+    return rc;
 }
 
 int psm_sgm_download_speckle_sizes(psm_ctx *c, int32_t *sizes, size_t stride_bytes)
@@ -588,11 +597,7 @@ int psm_sgm_download_speckle_sizes(psm_ctx *c, int32_t *sizes, size_t stride_byt
     if (stride_bytes == 0) stride_bytes = row;
     if (stride_bytes < row) return fail(c, "psm_sgm_download_speckle_sizes: stride %zu < row size %zu", stride_bytes, row);
     if (bind(c)) return 1;
-    std::vector<int32_t> packed((size_t)c->W * c->H);
-    PSM_HIP(c, hipMemcpyAsync(packed.data(), c->sgm.spk_size, row * c->H, hipMemcpyDeviceToHost, c->stream));
-    PSM_HIP(c, hipStreamSynchronize(c->stream));
-    for (int y = 0; y < c->H; ++y) memcpy((uint8_t *)sizes + (size_t)y * stride_bytes, packed.data() + (size_t)y * c->W, row);
-    return 0;
+    return d2h_rows(c, sizes, c->sgm.spk_size, row, stride_bytes, c->H);
 }
 
 int psm_sgm_speckle_time(psm_ctx *c, double *ms)

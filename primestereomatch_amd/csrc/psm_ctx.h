@@ -22,6 +22,7 @@
 #include "psm_kernels.h"
 #include "psm_state.h"
 
+#include <cstring>
 #include <string>
 #include <utility>
 #include <vector>
@@ -297,6 +298,17 @@ struct Prof {
 
 // psm_api_core.cpp
 int h2d_rows(psm_ctx *c, void *dst, const void *src, size_t row, size_t stride, int rows);   // host rows -> packed device rows
+// packed device rows -> host rows `stride` bytes apart, on the context's stream and complete on return; rows that are packed on
+// the host as well (stride == row) are the copy's own destination
+inline int d2h_rows(psm_ctx *c, void *dst, const void *src, size_t row, size_t stride, int rows)
+{
+    std::vector<uint8_t> packed(stride == row ? 0 : row * rows);
+    PSM_HIP(c, hipMemcpyAsync(stride == row ? dst : packed.data(), src, row * rows, hipMemcpyDeviceToHost, c->stream));
+    PSM_HIP(c, hipStreamSynchronize(c->stream));
+    if (stride != row)
+        for (int y = 0; y < rows; ++y) memcpy((uint8_t *)dst + (size_t)y * stride, packed.data() + (size_t)y * row, row);
+    return 0;
+}
 
 // The plane rows a filter reads: the whole image, or - a psm_set_rows stripe [y0, y1) being in force - what the select form of
 // the fused kernel touches for it: the guidance of the model rows y0 - 4 .. y1 + 2 (rounded to +- 4), and the image planes of

@@ -294,6 +294,15 @@ constexpr int SGM_CEN_TX = 32;         // k_sgm_census: the pixels of a workgrou
 constexpr int SGM_CEN_TY = 8;          // ... and rows
 constexpr int SGM_CEN_MAXW = 9;        // the widest census window (psm_sgm_set_census): 9 x 7 - 1 = 62 bits
 constexpr int SGM_CEN_MAXH = 7;
+// One launch of a kernel with its two entries, over either argument record R (SgmArgs, SpkArgs): the single-pair entry k with the
+// pair in `a`, or - tab given - the batched entry kb over the device table with gz as the grid's z extent
+template <typename R, typename... A>
+static void sgm_launch(hipStream_t s, void (*k)(R, A...), void (*kb)(R, const SgmPair *, A...), dim3 grid, dim3 block, const R &a,
+                       const SgmPair *tab, int gz, A... rest)
+{
+    if (tab) hipLaunchKernelGGL(kb, dim3(grid.x, grid.y, (unsigned)gz), block, 0, s, a, tab, rest...);
+    else hipLaunchKernelGGL(k, grid, block, 0, s, a, rest...);
+}
 // tab == nullptr: the pair whose pointers `a` holds; else the n pairs of the device table (the pointers of `a` unused, grid z = pair)
 void launch_sgm_cost(hipStream_t s, const SgmArgs &a, const SgmPair *tab = nullptr, int n = 1);
 void launch_sgm_cost_bt(hipStream_t s, const SgmArgs &a, const SgmPair *tab = nullptr, int n = 1);   // k_sgm_prefilter, k_sgm_bt_rows, k_sgm_bt_cols: the same C

@@ -192,11 +192,12 @@ __device__ __forceinline__ void sgm_bt_stage(const uint8_t *row, int W, int cx, 
 // x with its d fixed, evaluates c(x, y, d) once and keeps the last BS of them in registers.  LDS holds, per pixel and pair of
 // planes, the values and both bounds of the left tile and of the part of the right row the tile's disparities reach; the left
 // operands are broadcasts, the right ones of neighbouring lanes neighbouring dwords.  NP pairs of planes: ch = NP (1 or 3); plane
-// i has shift 0 below ch (P), 2 from ch on (Q).  out: Hs, or C itself when BS is 1.
+// i has shift 0 below ch (P), 2 from ch on (Q).  The sums go to Hs, or to C itself when BS is 1 (a 1 x 1 block has no vertical sum).
 // WIDE: as k_sgm_cost (static LDS: 46.5 KB at BS 7, NP 3).
 template <int BS, int NP, bool WIDE>
-__device__ __forceinline__ void sgm_bt_rows(const SgmArgs &a, uint16_t *out)
+__device__ __forceinline__ void sgm_bt_rows(const SgmArgs &a)
 {
+    uint16_t *const out = BS == 1 ? a.C : a.Hs;
     constexpr int HALF = BS / 2, NL = SGM_BT_TX + BS - 1, NR = NL + (WIDE ? SGM_DMAX : 256) - 1, NQ = 3 * NP;
     __shared__ unsigned sl[NQ][NL], sr[NQ][NR];
     const int y = blockIdx.y, x0 = blockIdx.x * SGM_BT_TX;
@@ -244,14 +245,9 @@ __device__ __forceinline__ void sgm_bt_rows(const SgmArgs &a, uint16_t *out)
     } while (WIDE && (d += 256) < a.Dp);
 }
 
+template <int BS, int NP, bool WIDE> __global__ __launch_bounds__(256) void k_sgm_bt_rows(SgmArgs a) { sgm_bt_rows<BS, NP, WIDE>(a); }
 template <int BS, int NP, bool WIDE>
-__global__ __launch_bounds__(256) void k_sgm_bt_rows(SgmArgs a, uint16_t *out) { sgm_bt_rows<BS, NP, WIDE>(a, out); }
-template <int BS, int NP, bool WIDE>
-__global__ __launch_bounds__(256) void k_sgm_bt_rows_b(SgmArgs a, const SgmPair *tab)
-{
-    a = sgm_pair_args(a, tab, blockIdx.z);
-    sgm_bt_rows<BS, NP, WIDE>(a, BS == 1 ? a.C : a.Hs);
-}
+__global__ __launch_bounds__(256) void k_sgm_bt_rows_b(SgmArgs a, const SgmPair *tab) { sgm_bt_rows<BS, NP, WIDE>(sgm_pair_args(a, tab, blockIdx.z)); }
 
 // The vertical sum: a thread holds four adjacent disparities of one pixel column (8 bytes: Dp is a multiple of 4) and marches
 // down SGM_BT_YS rows; the last BS rows of Hs stay in registers, a step is one load, one add, one subtract and one store.  Two
@@ -612,15 +608,6 @@ __global__ __launch_bounds__(256) void k_sgm_fill_b(SgmArgs a, const SgmPair *ta
     if (pix < a.W * a.H) sgm_global(tab[blockIdx.z].disp2)[pix] = 0xffffffffu;
 }
 
-// One launch: the single-pair entry k with the pair in `a`, or the batched entry kb over the table with gz as the grid's z extent
-template <typename... A>
-static void sgm_launch(hipStream_t s, void (*k)(SgmArgs, A...), void (*kb)(SgmArgs, const SgmPair *, A...), dim3 grid, dim3 block,
-                       const SgmArgs &a, const SgmPair *tab, int gz, A... rest)
-{
-    if (tab) hipLaunchKernelGGL(kb, dim3(grid.x, grid.y, (unsigned)gz), block, 0, s, a, tab, rest...);
-    else hipLaunchKernelGGL(k, grid, block, 0, s, a, rest...);
-}
-
 void launch_sgm_fill_batch(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
 {
     hipLaunchKernelGGL(k_sgm_fill_b, dim3((a.W * a.H + 255) / 256, 1, n), dim3(256), 0, s, a, tab);
@@ -629,52 +616,47 @@ void launch_sgm_fill_batch(hipStream_t s, const SgmArgs &a, const SgmPair *tab, 
 // one thread per disparity up to 256 of them; above, 256 threads that each take every 256th (the WIDE forms)
 static unsigned sgm_cost_threads(int D) { return D > 256 ? 256u : (unsigned)((D + 63) / 64 * 64); }
 
-void launch_sgm_cost(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
+// The run-time block size (1, 3, 5 or 7: psm_sgm_set_params) and `wide` as the kernels' template arguments: f(BS, WIDE) with two
+// std::integral_constant values
+template <typename F>
+static void sgm_with_bs(int bs, bool wide, F f)
 {
-    const dim3 grid((a.W + SGM_TX - 1) / SGM_TX, a.H), block(sgm_cost_threads(a.D));
-    const int wide = a.D > 256;
-    switch (a.bs * 2 + wide) {
-    case 2: sgm_launch(s, k_sgm_cost<1, false>, k_sgm_cost_b<1, false>, grid, block, a, tab, n); break;
-    case 3: sgm_launch(s, k_sgm_cost<1, true>, k_sgm_cost_b<1, true>, grid, block, a, tab, n); break;
-    case 6: sgm_launch(s, k_sgm_cost<3, false>, k_sgm_cost_b<3, false>, grid, block, a, tab, n); break;
-    case 7: sgm_launch(s, k_sgm_cost<3, true>, k_sgm_cost_b<3, true>, grid, block, a, tab, n); break;
-    case 10: sgm_launch(s, k_sgm_cost<5, false>, k_sgm_cost_b<5, false>, grid, block, a, tab, n); break;
-    case 11: sgm_launch(s, k_sgm_cost<5, true>, k_sgm_cost_b<5, true>, grid, block, a, tab, n); break;
-    case 14: sgm_launch(s, k_sgm_cost<7, false>, k_sgm_cost_b<7, false>, grid, block, a, tab, n); break;
-    default: sgm_launch(s, k_sgm_cost<7, true>, k_sgm_cost_b<7, true>, grid, block, a, tab, n); break;
+    auto g = [&](auto b) {
+        if (wide) f(b, std::true_type{});
+        else f(b, std::false_type{});
+    };
+    switch (bs) {
+    case 1: g(std::integral_constant<int, 1>{}); break;
+    case 3: g(std::integral_constant<int, 3>{}); break;
+    case 5: g(std::integral_constant<int, 5>{}); break;
+    default: g(std::integral_constant<int, 7>{}); break;
     }
 }
 
-template <int BS, bool WIDE>
-static void launch_bt_bs(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
+void launch_sgm_cost(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
 {
-    const dim3 grid((a.W + SGM_BT_TX - 1) / SGM_BT_TX, a.H, tab ? n : 1), block(sgm_cost_threads(a.D));
-    uint16_t *out = BS == 1 ? a.C : a.Hs;                 // (a 1 x 1 block has no vertical sum)
-    if (tab) {
-        if (a.ch == 1) hipLaunchKernelGGL((k_sgm_bt_rows_b<BS, 1, WIDE>), grid, block, 0, s, a, tab);
-        else hipLaunchKernelGGL((k_sgm_bt_rows_b<BS, 3, WIDE>), grid, block, 0, s, a, tab);
-    } else if (a.ch == 1) hipLaunchKernelGGL((k_sgm_bt_rows<BS, 1, WIDE>), grid, block, 0, s, a, out);
-    else hipLaunchKernelGGL((k_sgm_bt_rows<BS, 3, WIDE>), grid, block, 0, s, a, out);
-    if constexpr (BS > 1) {
-        const size_t rowq = (size_t)a.W * a.Dp / 4;
-        sgm_launch(s, k_sgm_bt_cols<BS>, k_sgm_bt_cols_b<BS>, dim3((unsigned)((rowq + 255) / 256), (a.H + SGM_BT_YS - 1) / SGM_BT_YS), dim3(256), a, tab, n);
-    }
+    const dim3 grid((a.W + SGM_TX - 1) / SGM_TX, a.H), block(sgm_cost_threads(a.D));
+    sgm_with_bs(a.bs, a.D > 256, [&](auto bs, auto wide) {
+        constexpr int BS = decltype(bs)::value;
+        constexpr bool WIDE = decltype(wide)::value;
+        sgm_launch(s, k_sgm_cost<BS, WIDE>, k_sgm_cost_b<BS, WIDE>, grid, block, a, tab, n);
+    });
 }
 
 void launch_sgm_cost_bt(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
 {
     sgm_launch(s, k_sgm_prefilter, k_sgm_prefilter_b, dim3((a.W + 255) / 256, a.H, 2), dim3(256), a, tab, 2 * n);
-    const int wide = a.D > 256;
-    switch (a.bs * 2 + wide) {
-    case 2: launch_bt_bs<1, false>(s, a, tab, n); break;
-    case 3: launch_bt_bs<1, true>(s, a, tab, n); break;
-    case 6: launch_bt_bs<3, false>(s, a, tab, n); break;
-    case 7: launch_bt_bs<3, true>(s, a, tab, n); break;
-    case 10: launch_bt_bs<5, false>(s, a, tab, n); break;
-    case 11: launch_bt_bs<5, true>(s, a, tab, n); break;
-    case 14: launch_bt_bs<7, false>(s, a, tab, n); break;
-    default: launch_bt_bs<7, true>(s, a, tab, n); break;
-    }
+    const dim3 grid((a.W + SGM_BT_TX - 1) / SGM_BT_TX, a.H), block(sgm_cost_threads(a.D));
+    sgm_with_bs(a.bs, a.D > 256, [&](auto bs, auto wide) {
+        constexpr int BS = decltype(bs)::value;
+        constexpr bool WIDE = decltype(wide)::value;
+        if (a.ch == 1) sgm_launch(s, k_sgm_bt_rows<BS, 1, WIDE>, k_sgm_bt_rows_b<BS, 1, WIDE>, grid, block, a, tab, n);
+        else sgm_launch(s, k_sgm_bt_rows<BS, 3, WIDE>, k_sgm_bt_rows_b<BS, 3, WIDE>, grid, block, a, tab, n);
+        if constexpr (BS > 1) {
+            const size_t rowq = (size_t)a.W * a.Dp / 4;
+            sgm_launch(s, k_sgm_bt_cols<BS>, k_sgm_bt_cols_b<BS>, dim3((unsigned)((rowq + 255) / 256), (a.H + SGM_BT_YS - 1) / SGM_BT_YS), dim3(256), a, tab, n);
+        }
+    });
 }
 
 void launch_sgm_cost_census(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
@@ -682,50 +664,43 @@ void launch_sgm_cost_census(hipStream_t s, const SgmArgs &a, const SgmPair *tab,
     sgm_launch(s, k_sgm_census, k_sgm_census_b, dim3((a.W + SGM_CEN_TX - 1) / SGM_CEN_TX, (a.H + SGM_CEN_TY - 1) / SGM_CEN_TY, 2),
                dim3(SGM_CEN_TX * SGM_CEN_TY), a, tab, 2 * n);
     const dim3 grid((a.W + SGM_TX - 1) / SGM_TX, a.H), block(sgm_cost_threads(a.D));
-    switch (a.bs) {
-    case 1: sgm_launch(s, k_sgm_census_cost<1>, k_sgm_census_cost_b<1>, grid, block, a, tab, n); break;
-    case 3: sgm_launch(s, k_sgm_census_cost<3>, k_sgm_census_cost_b<3>, grid, block, a, tab, n); break;
-    case 5: sgm_launch(s, k_sgm_census_cost<5>, k_sgm_census_cost_b<5>, grid, block, a, tab, n); break;
-    default: sgm_launch(s, k_sgm_census_cost<7>, k_sgm_census_cost_b<7>, grid, block, a, tab, n); break;
-    }
+    sgm_with_bs(a.bs, false, [&](auto bs, auto) {              // (one form whatever D is: the passes are the kernel's own)
+        constexpr int BS = decltype(bs)::value;
+        sgm_launch(s, k_sgm_census_cost<BS>, k_sgm_census_cost_b<BS>, grid, block, a, tab, n);
+    });
 }
 
-// lanes hold 1, 2, 4, 8 or 16 disparities: the smallest count that covers Dp with 64 lanes
-static int sgm_nv(int Dp) { return Dp <= 64 ? 1 : (Dp <= 128 ? 2 : (Dp <= 256 ? 4 : (Dp <= 512 ? 8 : 16))); }
-
-template <int NV>
-static void launch_path_nv(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first, const SgmPair *tab, int n)
+// lanes hold 1, 2, 4, 8 or 16 disparities, the smallest count that covers Dp with 64 lanes: f(NV) with a std::integral_constant
+template <typename F>
+static void sgm_with_nv(int Dp, F f)
 {
-    const dim3 grid((sgm_npaths(a.W, a.H, dy, dx) + 3) / 4), block(256);
-    const bool all = a.Dp == 64 * NV;
-    if (first && all) sgm_launch(s, k_sgm_path<NV, true, true>, k_sgm_path_b<NV, true, true>, grid, block, a, tab, n, dy, dx);
-    else if (first) sgm_launch(s, k_sgm_path<NV, true, false>, k_sgm_path_b<NV, true, false>, grid, block, a, tab, n, dy, dx);
-    else if (all) sgm_launch(s, k_sgm_path<NV, false, true>, k_sgm_path_b<NV, false, true>, grid, block, a, tab, n, dy, dx);
-    else sgm_launch(s, k_sgm_path<NV, false, false>, k_sgm_path_b<NV, false, false>, grid, block, a, tab, n, dy, dx);
+    if (Dp <= 64) f(std::integral_constant<int, 1>{});
+    else if (Dp <= 128) f(std::integral_constant<int, 2>{});
+    else if (Dp <= 256) f(std::integral_constant<int, 4>{});
+    else if (Dp <= 512) f(std::integral_constant<int, 8>{});
+    else f(std::integral_constant<int, 16>{});
 }
 
 void launch_sgm_path(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first, const SgmPair *tab, int n)
 {
-    switch (sgm_nv(a.Dp)) {
-    case 1: launch_path_nv<1>(s, a, dy, dx, first, tab, n); break;
-    case 2: launch_path_nv<2>(s, a, dy, dx, first, tab, n); break;
-    case 4: launch_path_nv<4>(s, a, dy, dx, first, tab, n); break;
-    case 8: launch_path_nv<8>(s, a, dy, dx, first, tab, n); break;
-    default: launch_path_nv<16>(s, a, dy, dx, first, tab, n); break;
-    }
+    const dim3 grid((sgm_npaths(a.W, a.H, dy, dx) + 3) / 4), block(256);
+    sgm_with_nv(a.Dp, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        const bool all = a.Dp == 64 * NV;
+        if (first && all) sgm_launch(s, k_sgm_path<NV, true, true>, k_sgm_path_b<NV, true, true>, grid, block, a, tab, n, dy, dx);
+        else if (first) sgm_launch(s, k_sgm_path<NV, true, false>, k_sgm_path_b<NV, true, false>, grid, block, a, tab, n, dy, dx);
+        else if (all) sgm_launch(s, k_sgm_path<NV, false, true>, k_sgm_path_b<NV, false, true>, grid, block, a, tab, n, dy, dx);
+        else sgm_launch(s, k_sgm_path<NV, false, false>, k_sgm_path_b<NV, false, false>, grid, block, a, tab, n, dy, dx);
+    });
 }
 
 void launch_sgm_select(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
 {
     const int HW = a.W * a.H;
-    const dim3 grid((HW + 3) / 4), block(256);
-    switch (sgm_nv(a.Dp)) {
-    case 1: sgm_launch(s, k_sgm_select<1>, k_sgm_select_b<1>, grid, block, a, tab, n); break;
-    case 2: sgm_launch(s, k_sgm_select<2>, k_sgm_select_b<2>, grid, block, a, tab, n); break;
-    case 4: sgm_launch(s, k_sgm_select<4>, k_sgm_select_b<4>, grid, block, a, tab, n); break;
-    case 8: sgm_launch(s, k_sgm_select<8>, k_sgm_select_b<8>, grid, block, a, tab, n); break;
-    default: sgm_launch(s, k_sgm_select<16>, k_sgm_select_b<16>, grid, block, a, tab, n); break;
-    }
+    sgm_with_nv(a.Dp, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        sgm_launch(s, k_sgm_select<NV>, k_sgm_select_b<NV>, dim3((HW + 3) / 4), dim3(256), a, tab, n);
+    });
     sgm_launch(s, k_sgm_check, k_sgm_check_b, dim3((HW + 255) / 256), dim3(256), a, tab, n);
 }
 

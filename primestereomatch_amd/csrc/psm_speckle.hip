@@ -155,17 +155,10 @@ __global__ __launch_bounds__(256) void k_spk_apply_b(SpkArgs a, const SgmPair *t
 void launch_speckle(hipStream_t s, const SpkArgs &a, const SgmPair *tab, int n)
 {
     const dim3 block(256), rows((a.W + 255) / 256, a.H);
-    if (tab) {
-        hipLaunchKernelGGL(k_spk_runs_b, dim3((a.H + 3) / 4, 1, n), block, 0, s, a, tab);
-        if (a.H > 1) hipLaunchKernelGGL(k_spk_merge_b, dim3(rows.x, a.H - 1, n), block, 0, s, a, tab);
-        hipLaunchKernelGGL(k_spk_count_b, dim3(rows.x, rows.y, n), block, 0, s, a, tab);
-        hipLaunchKernelGGL(k_spk_apply_b, dim3(rows.x, rows.y, n), block, 0, s, a, tab);
-        return;
-    }
-    hipLaunchKernelGGL(k_spk_runs, dim3((a.H + 3) / 4), block, 0, s, a);
-    if (a.H > 1) hipLaunchKernelGGL(k_spk_merge, dim3(rows.x, a.H - 1), block, 0, s, a);
-    hipLaunchKernelGGL(k_spk_count, rows, block, 0, s, a);
-    hipLaunchKernelGGL(k_spk_apply, rows, block, 0, s, a);
+    sgm_launch(s, k_spk_runs, k_spk_runs_b, dim3((a.H + 3) / 4), block, a, tab, n);
+    if (a.H > 1) sgm_launch(s, k_spk_merge, k_spk_merge_b, dim3(rows.x, a.H - 1), block, a, tab, n);
+    sgm_launch(s, k_spk_count, k_spk_count_b, rows, block, a, tab, n);
+    sgm_launch(s, k_spk_apply, k_spk_apply_b, rows, block, a, tab, n);
 }
 
 }  // namespace psm
