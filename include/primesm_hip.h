@@ -467,11 +467,49 @@ int psm_sgm_speckle_time(psm_ctx *ctx, double *ms);
  * The launches run on ctxs[0]'s stream, after everything already queued on the other contexts' streams and before anything queued
  * on them later; synchronous on return unless ctxs[0] has PSM_OPT_ASYNC.  Contexts under psm_share_streams work as they are.
  * Buffers stay per context (allocated on first use, given back by psm_release_scratch / psm_destroy); the kernels reach them
- * through a device table of n * 88 bytes (the census code planes take the slots of the prefiltered planes: a batch has one cost)
+ * through a device table of n * 96 bytes (the census code planes take the slots of the prefiltered planes: a batch has one cost)
  * that ctxs[0] owns and uploads again only when an entry changed.  With PSM_OPT_PROFILE on
  * ctxs[0], psm_sgm_times(ctxs[0]) and psm_sgm_speckle_time(ctxs[0]) report the batch's launches; the other contexts count as not
  * timed.  psm_sgm_compute_gray has no batch form: it takes host pointers and stages them itself. */
 int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n);
+
+/* The 8-bit maps of both views from the SGM stage, so that everything that works on the context's current maps - psm_lr_check,
+ * psm_fill_invalid, psm_wgt_median, psm_joint_wmf, psm_score(PSM_SCORE_GIF), psm_download_maps* - runs behind the stage as it runs
+ * behind psm_disp_select.  The definition is tests/sgm_maps_model.py, all integer; the device equals it element for element.  For
+ * the summed path costs S [H][W][D] of the last psm_sgm_compute / _compute_gray / _compute_batch of the context, computed with
+ * the range (dmin, D) - index k stands for the disparity dmin + k:
+ *   left   lmap[y][x]  = dmin + argmin_k S[y][x][k], the lowest k on ties: the winner-takes-all disparity.  The uniqueness test,
+ *                        the sub-pixel step and the disp12_max_diff test play no part: psm_lr_check validates these maps.
+ *   right  rmap[y][xr] = dmin + k of the smallest (S[y][xr + dmin + k][k], k) over the k in [0, D) with xr + dmin + k < W, the
+ *                        lowest k on ties - Hirschmueller's D_m(q) = argmin_d S(q.x + d, q.y, d), the search along the epipolar
+ *                        line in the same S; 0 in a column without a candidate (the last dmin columns).
+ * Range condition: the call is defined for 0 <= dmin and dmin + D <= max_disp (<= 256) only - the maps are bytes and index the
+ * max_disp bins of the weighted medians.  The range is the one the RESULT was computed with, whatever psm_sgm_set_range has been
+ * told since.  One launch (k_sgm_maps) that reads S once; no global atomics.
+ * Both maps go to the context's map buffer (psm_disp_select's, or the caller's after psm_set_map_buffer).  Afterwards the context
+ * is exactly where psm_upload_maps(ctx, l, r, NULL, NULL, 0) leaves it: whole-image maps are current, there is no mask
+ * (psm_fill_invalid and the medians are refused until a new psm_lr_check), and the guided-filter path keeps what it had - volumes,
+ * packed minima and anything pending are untouched, a later psm_disp_select yields the guided-filter maps again.  Untouched as
+ * well, bit for bit: the int16 map, C, S, the consistency plane, the speckle planes and everything psm_sgm_download_* returns.
+ * lmap / rmap: H rows of W bytes, pitch `stride` (0: packed); either may be NULL (the results stay on the device).  On the
+ * context's stream; synchronous on return unless PSM_OPT_ASYNC is set.
+ * Refused - psm_last_error names the call and the numbers, nothing has been enqueued, the previous maps are still current - for a
+ * NULL context (psm_last_error(NULL)), a context without an SGM result (never computed, or given back by psm_release_scratch), a
+ * result whose range violates the range condition (so every result with more disparities than the image has columns: psm_create
+ * wants max_disp <= width), a disparity shard, a row stripe in force and stride < W. */
+int psm_sgm_select_maps(psm_ctx *ctx, uint8_t *lmap, uint8_t *rmap, size_t stride);
+/* psm_sgm_select_maps of the n contexts ctxs[0..n) in one launch, the pair on a grid axis of its own; the maps stay on the device
+ * (psm_download_maps).  On ctxs[0]'s stream, ordered as psm_sgm_compute_batch's launches: after everything already queued on the
+ * other contexts' streams, before anything queued on them later; synchronous on return unless ctxs[0] has PSM_OPT_ASYNC.  The
+ * contexts must agree on width, height, max_disp and device and on the range (dmin, D) of their results; every context must pass
+ * the single call's conditions.  Refused otherwise and for NULL or repeated contexts, n < 1 or n > 4096: psm_last_error(ctxs[0])
+ * names the offending index, nothing has been enqueued.  Every context ends where its own psm_sgm_select_maps would have left
+ * it, with the same bits.  The kernels reach the buffers through psm_sgm_compute_batch's device table, which for this carries
+ * every context's map buffer. */
+int psm_sgm_select_maps_batch(psm_ctx *const *ctxs, int n);
+/* Device time in ms of the launch of the last psm_sgm_select_maps, which must have run under PSM_OPT_PROFILE (a batch: of all
+ * pairs, on its first context; the other contexts count as not timed). */
+int psm_sgm_maps_time(psm_ctx *ctx, double *ms);
 
 /* "next" row: PP lrCheck on the device (src/PP.cpp:17-50) on the maps of the last
  * psm_disp_select/psm_disp_merge.  lvalid/rvalid: H x W bytes (0/1), pitch `stride`; either

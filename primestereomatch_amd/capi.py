@@ -124,6 +124,9 @@ SYMBOLS = [
     ("psm_sgm_set_range", _i, [_vp, _i, _i]),
     ("psm_sgm_set_census", _i, [_vp, _i, _i]),
     ("psm_sgm_download_census", _i, [_vp, _i, _vp]),
+    ("psm_sgm_select_maps", _i, [_vp, _vp, _vp, _sz]),
+    ("psm_sgm_select_maps_batch", _i, [C.POINTER(_vp), _i]),
+    ("psm_sgm_maps_time", _i, [_vp, _pd]),
     ("psm_score_set_truth", _i, [_vp, _vp, _vp, _sz]),
     ("psm_score_clear_truth", _i, [_vp]),
     ("psm_score_set_params", _i, [_vp, _i, _i, _i]),

@@ -8,6 +8,8 @@
 // cost as tests/sgm_bt_model.py defines it (the reference: preFilterCap 63), or, after psm_sgm_set_census, the Hamming distance
 // of census codes (tests/sgm_census_model.py).  Unpinned in all of it: a live cv::StereoSGBM.
 // psm_sgm_compute_batch: the same launches for the pairs of several contexts at once, the pair on a grid axis of its own.
+// psm_sgm_select_maps / _batch: the one place where the stage meets the rest - the context's two current 8-bit maps (psm::Results)
+// from S, so that the post-processing and score stages run behind it (tests/sgm_maps_model.py).
 // Single pairs and batches share the launch sequence (enqueue), the record of a pair's buffers (pair_of), the name of the pixel
 // cost (cost_kind) and what a context forgets ahead of the launches and holds behind them (forget, mark); the entry points keep
 // what differs - argument checks, the gray upload, a batch's cross-context checks, stream ordering and table.
@@ -42,9 +44,10 @@ void sgm_free(psm_ctx *c)
     g.tab_cap = 0;
     g.tab_host.clear();
     for (hipEvent_t &e : g.ev_tab) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    g.have = g.timed = g.spk_have = false;
+    for (hipEvent_t &e : g.ev_maps) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    g.have = g.timed = g.spk_have = g.maps_timed = false;
     g.spk_t0 = -1;
-    g.vol_dp = g.res_d = 0;
+    g.vol_dp = g.res_d = g.res_dmin = 0;
 }
 
 }  // namespace psm
@@ -145,7 +148,7 @@ int ensure_buffers(psm_ctx *c)
 SgmPair pair_of(const psm_ctx *c, const void *l, const void *r)
 {
     const SgmState &g = c->sgm;
-    SgmPair p{{l, r}, g.C, g.S, g.disp2, g.pre, g.out, {nullptr, nullptr}, nullptr, nullptr};
+    SgmPair p{{l, r}, g.C, g.S, g.disp2, g.pre, g.out, {nullptr, nullptr}, nullptr, nullptr, c->maps};
     switch (cost_kind(g)) {
     case SgmCost::BT: p.pf[0] = g.pf[0]; p.pf[1] = g.pf[1]; break;
     case SgmCost::CENSUS: p.pf[0] = (uint8_t *)g.cen[0]; p.pf[1] = (uint8_t *)g.cen[1]; break;      // the code planes travel in the pf slots
@@ -200,11 +203,13 @@ void forget(SgmState &g)
     if (g.spk_window > 0) g.spk_have = false;             // (with the filter off, the sizes of an earlier run stay readable)
 }
 
-// ... and behind them it holds the result of this cost on `ch` channels over D disparities; timed: its own events bracketed them
-void mark(SgmState &g, SgmCost kind, int ch, int D, bool timed)
+// ... and behind them it holds the result of this cost on `ch` channels over the D disparities from dmin on; timed: its own events
+// bracketed them
+void mark(SgmState &g, SgmCost kind, int ch, int dmin, int D, bool timed)
 {
     g.have = true;
     g.res_d = D;
+    g.res_dmin = dmin;
     g.timed = timed;
     g.pf_ch = kind == SgmCost::BT ? ch : 0;
     g.cen_have = kind == SgmCost::CENSUS;
@@ -267,6 +272,86 @@ int enqueue(psm_ctx *c, hipStream_t s, SgmArgs a, const SgmPair *one, const SgmP
     return 0;
 }
 
+// The device table of a batch's pairs (psm_sgm_compute_batch, psm_sgm_select_maps_batch), owned by the batch's first context c0 and
+// uploaded again only when an entry changed.  table_memory: the records of ctxs[0..n) and, if they differ from the uploaded ones
+// (*fresh), room for them - before anything is ordered or launched; table_upload: the copy, on c0's stream.
+int table_memory(psm_ctx *c0, psm_ctx *const *ctxs, int n, std::vector<SgmPair> &tab, bool *fresh)
+{
+    SgmState &t = c0->sgm;
+    hipStream_t s = c0->stream;
+    tab.resize((size_t)n);
+    for (int i = 0; i < n; ++i) tab[i] = pair_of(ctxs[i], ctxs[i]->raw[0], ctxs[i]->raw[1]);
+    *fresh = t.tab_host.size() != tab.size() || memcmp(t.tab_host.data(), tab.data(), tab.size() * sizeof(SgmPair)) != 0;
+    if (*fresh && t.tab_cap < tab.size()) {
+        PSM_HIP(c0, hipStreamSynchronize(s));
+        (void)hipFree(t.tab);
+        if (t.tab_pin) (void)hipHostFree(t.tab_pin);
+        t.tab = nullptr;
+        t.tab_pin = nullptr;
+        t.tab_cap = 0;
+        t.tab_host.clear();                  // (should an allocation below fail, the next call must not take the old table for current)
+        PSM_HIP(c0, hipMalloc((void **)&t.tab, tab.size() * sizeof(SgmPair)));
+        PSM_HIP(c0, hipHostMalloc((void **)&t.tab_pin, 2 * tab.size() * sizeof(SgmPair), hipHostMallocDefault));
+        t.tab_cap = tab.size();
+    }
+    for (hipEvent_t &e : t.ev_tab)
+        if (!e) PSM_HIP(c0, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return 0;
+}
+
+int table_upload(psm_ctx *c0, const std::vector<SgmPair> &tab)
+{
+    // (the table changes with every frame of a loop whose image slots alternate; the copy is stream-ordered behind the previous
+    // batch's kernels, which still read the old table, and reads one of two page-locked slots: a slot is rewritten only after
+    // the copy that read it has executed)
+    SgmState &t = c0->sgm;
+    hipStream_t s = c0->stream;
+    const int slot = t.tab_slot ^= 1;
+    PSM_HIP(c0, hipEventSynchronize(t.ev_tab[slot]));
+    SgmPair *pin = t.tab_pin + (size_t)slot * t.tab_cap;
+    memcpy(pin, tab.data(), tab.size() * sizeof(SgmPair));
+    t.tab_host = tab;
+    PSM_HIP(c0, hipMemcpyAsync(t.tab, pin, tab.size() * sizeof(SgmPair), hipMemcpyHostToDevice, s));
+    PSM_HIP(c0, hipEventRecord(t.ev_tab[slot], s));
+    return 0;
+}
+
+// psm_sgm_select_maps / _batch: what context c must be for the call `who`; e: the context that receives the message
+int check_maps(psm_ctx *e, const psm_ctx *c, const char *who)
+{
+    const SgmState &g = c->sgm;
+    if (c->Dloc != c->D || strided(c)) return fail(e, "%s: a disparity shard holds part of the range (the SGM stage does not run on it)", who);
+    if (c->march.yend > c->march.ybeg) return fail(e, "%s: a row stripe is in force (psm_set_rows): the maps are whole-image maps", who);
+    if (!g.have) return fail(e, "%s: no SGM result (psm_sgm_compute; psm_release_scratch gives it back)", who);
+    if (g.res_dmin < 0 || g.res_dmin + g.res_d > c->D || g.res_dmin + g.res_d > 256)
+        return fail(e, "%s: the result's range (min_disparity %d, %d disparities) is not inside [0, max_disp %d): the 8-bit maps hold the disparities 0 .. max_disp - 1, at most 256",
+                    who, g.res_dmin, g.res_d, c->D);
+    if (sgm_maps_lds_bytes(c->W) > SGM_MAPS_LDS_MAX)
+        return fail(e, "%s: width %d: a row's keys and bytes (%zu bytes) exceed the %zu bytes of LDS a workgroup takes", who, c->W,
+                    sgm_maps_lds_bytes(c->W), SGM_MAPS_LDS_MAX);
+    return 0;
+}
+
+// the result of a context as k_sgm_maps takes it: its own range (mark), not the current setting's
+SgmArgs maps_args(const psm_ctx *c)
+{
+    const SgmState &g = c->sgm;
+    SgmArgs a = {};
+    a.S = g.S;
+    a.W = c->W; a.H = c->H; a.D = g.res_d; a.Dp = psm::sgm_dp(g.res_d);
+    a.dmin = g.res_dmin;
+    return a;
+}
+
+// behind the launch a context is where psm_upload_maps(l, r, NULL, NULL) leaves it: whole-image maps, no mask, no early map; the
+// volume sides, the packed minima and whatever the guided-filter path has pending are not touched
+void maps_selected(psm_ctx *c)
+{
+    forget_early(c->res);
+    cover(c->res, whole_image(c));
+    maps_written(c->res);
+}
+
 // a single pair of `ch` channels through the stage on the context's stream (psm_sgm_compute, psm_sgm_compute_gray)
 int compute_one(psm_ctx *c, const char *who, const void *l, const void *r, int depth, int ch)
 {
@@ -278,7 +363,7 @@ int compute_one(psm_ctx *c, const char *who, const void *l, const void *r, int d
     const SgmPair p = pair_of(c, l, r);
     forget(g);
     if (enqueue(c, c->stream, a, &p, nullptr, 1)) return 1;
-    mark(g, cost_kind(g), ch, a.D, c->opt_profile != 0);
+    mark(g, cost_kind(g), ch, a.dmin, a.D, c->opt_profile != 0);
     if (!c->opt_async) PSM_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -427,23 +512,9 @@ int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
     }
     if (!c0->ev_batch) PSM_HIP(c0, hipEventCreateWithFlags(&c0->ev_batch, hipEventDisableTiming));
     SgmState &t = c0->sgm;
-    std::vector<SgmPair> tab((size_t)n);
-    for (int i = 0; i < n; ++i) tab[i] = pair_of(ctxs[i], ctxs[i]->raw[0], ctxs[i]->raw[1]);
-    const bool fresh = t.tab_host.size() != tab.size() || memcmp(t.tab_host.data(), tab.data(), tab.size() * sizeof(SgmPair)) != 0;
-    if (fresh && t.tab_cap < tab.size()) {
-        PSM_HIP(c0, hipStreamSynchronize(s));
-        (void)hipFree(t.tab);
-        if (t.tab_pin) (void)hipHostFree(t.tab_pin);
-        t.tab = nullptr;
-        t.tab_pin = nullptr;
-        t.tab_cap = 0;
-        t.tab_host.clear();                  // (should an allocation below fail, the next call must not take the old table for current)
-        PSM_HIP(c0, hipMalloc((void **)&t.tab, tab.size() * sizeof(SgmPair)));
-        PSM_HIP(c0, hipHostMalloc((void **)&t.tab_pin, 2 * tab.size() * sizeof(SgmPair), hipHostMallocDefault));
-        t.tab_cap = tab.size();
-    }
-    for (hipEvent_t &e : t.ev_tab)
-        if (!e) PSM_HIP(c0, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    std::vector<SgmPair> tab;
+    bool fresh = false;
+    if (table_memory(c0, ctxs, n, tab, &fresh)) return 1;
 
     // ---- every context's earlier work (uploads, a single compute, downloads) is ordered before the shared launches ----
     for (int i = 0; i < n; ++i) {
@@ -452,18 +523,7 @@ int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
         PSM_HIP(c0, hipEventRecord(c->ev_batch, c->stream));
         PSM_HIP(c0, hipStreamWaitEvent(s, c->ev_batch, 0));
     }
-    if (fresh) {
-        // (the table changes with every frame of a loop whose image slots alternate; the copy is stream-ordered behind the previous
-        // batch's kernels, which still read the old table, and reads one of two page-locked slots: a slot is rewritten only after
-        // the copy that read it has executed)
-        const int slot = t.tab_slot ^= 1;
-        PSM_HIP(c0, hipEventSynchronize(t.ev_tab[slot]));
-        SgmPair *pin = t.tab_pin + (size_t)slot * t.tab_cap;
-        memcpy(pin, tab.data(), tab.size() * sizeof(SgmPair));
-        t.tab_host = tab;
-        PSM_HIP(c0, hipMemcpyAsync(t.tab, pin, tab.size() * sizeof(SgmPair), hipMemcpyHostToDevice, s));
-        PSM_HIP(c0, hipEventRecord(t.ev_tab[slot], s));
-    }
+    if (fresh && table_upload(c0, tab)) return 1;
 
     // ---- the launches; then every context is where its own psm_sgm_compute would have left it - only context 0 counts as timed ----
     const SgmArgs a = sgm_args(c0, c0->raw_depth, 3, p1, p2);
@@ -472,10 +532,114 @@ int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
     PSM_HIP(c0, hipEventRecord(c0->ev_batch, s));
     for (int i = 0; i < n; ++i) {
         psm_ctx *c = ctxs[i];
-        mark(c->sgm, cost_kind(g0), 3, a.D, i == 0 && c0->opt_profile != 0);
+        mark(c->sgm, cost_kind(g0), 3, a.dmin, a.D, i == 0 && c0->opt_profile != 0);
         if (c->stream != s) PSM_HIP(c0, hipStreamWaitEvent(c->stream, c0->ev_batch, 0));
     }
     if (!c0->opt_async) PSM_HIP(c0, hipStreamSynchronize(s));
+    return 0;
+}
+
+// The 8-bit maps of both views from the S of the last compute, into the context's map buffer (k_sgm_maps, tests/sgm_maps_model.py):
+// one launch; the int16 map, C, S, disp2 and the speckle planes are read-only or untouched.
+int psm_sgm_select_maps(psm_ctx *c, uint8_t *lmap, uint8_t *rmap, size_t stride)
+{
+    const char *who = "psm_sgm_select_maps";
+    if (!c) return fail(nullptr, "%s: NULL context", who);
+    if (check_maps(c, c, who)) return 1;
+    if (stride != 0 && stride < (size_t)c->W) return fail(c, "%s: stride %zu < width %d", who, stride, c->W);
+    if (bind(c)) return 1;
+    SgmState &g = c->sgm;
+    const bool timed = c->opt_profile != 0;
+    if (timed)
+        for (hipEvent_t &e : g.ev_maps)
+            if (!e) PSM_HIP(c, hipEventCreate(&e));
+    if (maps_writable(c)) return 1;
+    g.maps_timed = false;
+    if (timed) PSM_HIP(c, hipEventRecord(g.ev_maps[0], c->stream));
+    launch_sgm_maps(c->stream, maps_args(c), c->maps);
+    if (check_launch(c, "k_sgm_maps")) return 1;
+    if (timed) PSM_HIP(c, hipEventRecord(g.ev_maps[1], c->stream));
+    g.maps_timed = timed;
+    maps_selected(c);
+    if (copy_maps_out(c, c->maps, lmap, rmap, stride)) return 1;
+    if (!c->opt_async) PSM_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ... of the n contexts ctxs[0..n) in one launch on ctxs[0]'s stream, ordered as psm_sgm_compute_batch's
+int psm_sgm_select_maps_batch(psm_ctx *const *ctxs, int n)
+{
+    const char *who = "psm_sgm_select_maps_batch";
+    if (!ctxs || n < 1 || !ctxs[0]) return fail(nullptr, "%s: bad arguments", who);
+    psm_ctx *c0 = ctxs[0];
+    if (n > 4096) return fail(c0, "%s: %d pairs (at most 4096 per call)", who, n);
+    for (int i = 0; i < n; ++i) {
+        psm_ctx *c = ctxs[i];
+        if (!c) return fail(c0, "%s: context %d is NULL", who, i);
+        for (int j = 0; j < i; ++j)
+            if (ctxs[j] == c) return fail(c0, "%s: context %d appears twice", who, i);
+        if (c->W != c0->W || c->H != c0->H || c->D != c0->D || c->device != c0->device)
+            return fail(c0, "%s: context %d has another width / height / max_disp / device than context 0", who, i);
+        char member[64];
+        snprintf(member, sizeof member, "%s: context %d", who, i);
+        if (check_maps(c0, c, member)) return 1;
+        if (c->sgm.res_dmin != c0->sgm.res_dmin || c->sgm.res_d != c0->sgm.res_d)
+            return fail(c0, "%s: the result of context %d has another disparity range (min %d, %d disparities) than context 0's (min %d, %d)", who, i,
+                        c->sgm.res_dmin, c->sgm.res_d, c0->sgm.res_dmin, c0->sgm.res_d);
+    }
+    if (bind(c0)) return 1;
+    hipStream_t s = c0->stream;
+    SgmState &t = c0->sgm;
+    const bool timed = c0->opt_profile != 0;
+
+    // ---- events and the table's memory: before anything is ordered or launched ----
+    for (int i = 0; i < n; ++i)
+        if (ctxs[i]->stream != s && !ctxs[i]->ev_batch) PSM_HIP(c0, hipEventCreateWithFlags(&ctxs[i]->ev_batch, hipEventDisableTiming));
+    if (!c0->ev_batch) PSM_HIP(c0, hipEventCreateWithFlags(&c0->ev_batch, hipEventDisableTiming));
+    if (timed)
+        for (hipEvent_t &e : t.ev_maps)
+            if (!e) PSM_HIP(c0, hipEventCreate(&e));
+    std::vector<SgmPair> tab;
+    bool fresh = false;
+    if (table_memory(c0, ctxs, n, tab, &fresh)) return 1;
+
+    // ---- every context's earlier work (its compute, downloads of its maps) is ordered before the shared launch ----
+    for (int i = 0; i < n; ++i) {
+        psm_ctx *c = ctxs[i];
+        if (c->ev_down) PSM_HIP(c0, hipStreamWaitEvent(s, c->ev_down, 0));       // (maps_writable, for the stream that writes)
+        if (c->stream == s) continue;
+        PSM_HIP(c0, hipEventRecord(c->ev_batch, c->stream));
+        PSM_HIP(c0, hipStreamWaitEvent(s, c->ev_batch, 0));
+    }
+    if (fresh && table_upload(c0, tab)) return 1;
+
+    // ---- the launch; then every context is where its own psm_sgm_select_maps would have left it - only context 0 counts as timed ----
+    for (int i = 0; i < n; ++i) ctxs[i]->sgm.maps_timed = false;
+    if (timed) PSM_HIP(c0, hipEventRecord(t.ev_maps[0], s));
+    launch_sgm_maps(s, maps_args(c0), nullptr, t.tab, n);
+    if (check_launch(c0, "k_sgm_maps_b")) return 1;
+    if (timed) PSM_HIP(c0, hipEventRecord(t.ev_maps[1], s));
+    t.maps_timed = timed;
+    PSM_HIP(c0, hipEventRecord(c0->ev_batch, s));
+    for (int i = 0; i < n; ++i) {
+        psm_ctx *c = ctxs[i];
+        maps_selected(c);
+        if (c->stream != s) PSM_HIP(c0, hipStreamWaitEvent(c->stream, c0->ev_batch, 0));
+    }
+    if (!c0->opt_async) PSM_HIP(c0, hipStreamSynchronize(s));
+    return 0;
+}
+
+int psm_sgm_maps_time(psm_ctx *c, double *ms)
+{
+    if (!c) return fail(nullptr, "psm_sgm_maps_time: NULL context");
+    if (!ms) return fail(c, "psm_sgm_maps_time: NULL pointer");
+    if (!c->sgm.maps_timed) return fail(c, "psm_sgm_maps_time: the last psm_sgm_select_maps was not timed (PSM_OPT_PROFILE), or there is none");
+    if (bind(c)) return 1;
+    PSM_HIP(c, hipEventSynchronize(c->sgm.ev_maps[1]));
+    float t = 0.f;
+    PSM_HIP(c, hipEventElapsedTime(&t, c->sgm.ev_maps[0], c->sgm.ev_maps[1]));
+    *ms = t;
     return 0;
 }
 

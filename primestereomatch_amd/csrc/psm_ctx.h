@@ -51,6 +51,7 @@ struct SgmState {
     int dmin = 0, nd = 0;                          // psm_sgm_set_range: minDisparity, numDisparities; nd 0: the context's max_disp
     int vol_dp = 0;                                // the Dp C and S are allocated for (another range's: freed and allocated again)
     int res_d = 0;                                 // the D of the result in them (psm_sgm_download_costs)
+    int res_dmin = 0;                              // ... and its minDisparity (psm_sgm_select_maps: psm_sgm_set_range may have been called since)
     uint16_t *C = nullptr;
     uint32_t *S = nullptr;
     uint32_t *disp2 = nullptr;
@@ -80,6 +81,9 @@ struct SgmState {
     size_t tab_cap = 0;
     int tab_slot = 0;
     hipEvent_t ev_tab[2] = {nullptr, nullptr};
+    // psm_sgm_select_maps: the events around its launch (PSM_OPT_PROFILE), and whether the last call recorded them (psm_sgm_maps_time)
+    hipEvent_t ev_maps[2] = {nullptr, nullptr};
+    bool maps_timed = false;
 };
 
 // psm_joint_wmf_batch (psm_api_jwmf.cpp; this context as the first of a batch): the device table - JwImg records of the images to

@@ -269,6 +269,7 @@ struct SgmPair {
     int16_t *pre, *out;
     uint8_t *pf[2];                    // null with the SAD cost; with the census cost the two code planes
     unsigned *spk_label, *spk_size;    // null with the speckle filter off
+    uint8_t *maps;                     // the context's map buffer [2][H][W] (k_sgm_maps_b alone writes it: psm_sgm_select_maps_batch)
 };
 // A pointer a kernel reads from the table is a flat pointer to the compiler (one that arrives as a kernel argument is known to be
 // global): every access through it would become a flat_* instruction, which counts on vmcnt and lgkmcnt at once and makes the
@@ -310,6 +311,11 @@ void launch_sgm_cost_census(hipStream_t s, const SgmArgs &a, const SgmPair *tab 
 void launch_sgm_path(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first, const SgmPair *tab = nullptr, int n = 1);   // S = L_r (first) or S += L_r
 void launch_sgm_select(hipStream_t s, const SgmArgs &a, const SgmPair *tab = nullptr, int n = 1);   // k_sgm_select + k_sgm_check (disp2 all ones before)
 void launch_sgm_fill_batch(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n);   // disp2 of every pair all ones
+// k_sgm_maps: the 8-bit maps of both views from S into `maps` [2][H][W] (tab: into the pairs' `maps`); of `a` it reads S, W, H, D, Dp
+// and dmin >= 0, D <= 256.  One workgroup per row with sgm_maps_lds_bytes(W) of dynamic LDS, which must not exceed SGM_MAPS_LDS_MAX.
+constexpr size_t SGM_MAPS_LDS_MAX = 65536;
+size_t sgm_maps_lds_bytes(int W);
+void launch_sgm_maps(hipStream_t s, const SgmArgs &a, uint8_t *maps, const SgmPair *tab = nullptr, int n = 1);
 
 // psm_speckle.hip: cv::filterSpeckles on an int16 map, in place (psm_sgm_set_speckle, psm_sgm_filter_speckles)
 struct SpkArgs {

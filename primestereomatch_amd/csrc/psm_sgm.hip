@@ -6,6 +6,7 @@
 //                 S += L_r (the first direction stores)                                                                   u32 [y][x][d]
 //   k_sgm_select  argmin_d S (lowest d), uniqueness, sub-pixel d16, disp2[y][x-best] = min (minS << 8 | best)
 //   k_sgm_check   the disp12MaxDiff test of every pixel against disp2 of its row -> int16 map, -16 where invalid
+//   k_sgm_maps    (psm_sgm_select_maps, its own launch) the 8-bit maps of both views from S: argmin_d S(x, d) and argmin_d S(xr + d, d)
 // psm_sgm_set_range (tests/sgm_range_model.py): index k in [0, D), D <= 1024, stands for the disparity dmin + k - the right column
 // is clamp(x - dmin - k, 0, W - 1), d16, the landing column and the probes carry dmin, invalid is (dmin - 1) * 16.  Above 256
 // disparities the cost kernels walk their tile once per 256 of them, a lane of k_sgm_path / k_sgm_select holds 8 or 16.
@@ -702,6 +703,96 @@ void launch_sgm_select(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int 
         sgm_launch(s, k_sgm_select<NV>, k_sgm_select_b<NV>, dim3((HW + 3) / 4), dim3(256), a, tab, n);
     });
     sgm_launch(s, k_sgm_check, k_sgm_check_b, dim3((HW + 255) / 256), dim3(256), a, tab, n);
+}
+
+// ---- the 8-bit maps of both views from S (psm_sgm_select_maps, tests/sgm_maps_model.py) -----------------------------------------
+//   left   lmap[y][x]  = dmin + argmin_k S[y][x][k], lowest k: k_sgm_select's `best`, nothing else of it
+//   right  rmap[y][xr] = dmin + k of the smallest (S[y][xr + dmin + k][k], k) over the k with xr + dmin + k < W; 0 where there is none
+// The right view's candidates lie on a diagonal of S (stride Dp + 1 elements): gathered, a wave would touch 64 cache lines for 64
+// values.  S is read as k_sgm_select reads it instead - a pixel's disparities across the lanes of a wave - and the minimum is
+// SCATTERED: a workgroup owns one image row, holds the row's right keys in LDS (4 W bytes, all ones to begin with), and for
+// every left pixel x each lane takes the LDS minimum (ds_min_u32, no return value) of (S << 8 | k) into slot x - dmin - k.
+// Minima commute: the keys do not depend on the order the waves arrive in.  The wave minimum of the same keys is the left map's
+// entry; it waits in LDS too (W bytes), and after a barrier the workgroup writes both rows of bytes coalesced.  S is read once.
+// Lane l holds the NV indices l, l + 64, .. (NV dword loads of 256 contiguous bytes each), not NV adjacent ones: the 64 lanes of
+// one LDS instruction then go to 64 consecutive slots, and the 32 lanes the LDS serves together to 32 different banks (bank =
+// dword address mod 32).  With adjacent indices per lane the lanes of an instruction would lie NV slots apart - 2 or 4 lanes
+// per bank.  KB is 8: the call exists up to 256 disparities (S < 2^19: a key has 27 bits and never equals the all-ones start).
+// The waves of a workgroup take every SGM_MAPS_WAVES-th pixel of the row, U pixels' loads issued ahead of their minima.
+constexpr int SGM_MAPS_WAVES = 8, SGM_MAPS_U = 4;
+
+template <int NV>
+__device__ __forceinline__ void sgm_maps(const SgmArgs &a, uint8_t *maps)
+{
+    extern __shared__ unsigned sgm_maps_lds[];
+    unsigned *rkey = sgm_maps_lds;                                 // [W] the right view's packed minima
+    uint8_t *lrow = (uint8_t *)(rkey + a.W);                       // [W] the left map's row
+    const int y = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = threadIdx.x; i < a.W; i += SGM_MAPS_WAVES * 64) rkey[i] = 0xffffffffu;
+    __syncthreads();
+    const unsigned *Srow = a.S + (size_t)y * a.W * a.Dp;
+    for (int x0 = wave; x0 < a.W; x0 += SGM_MAPS_WAVES * SGM_MAPS_U) {      // (wave-uniform)
+        // The body has no branch, so that the compiler waits for exactly the loads a pixel needs (k_sgm_path above): what takes no
+        // part - a lane past D, a landing column left of the image, a pixel past the row's end - loads a clamped address and
+        // brings the all-ones key, which changes no minimum, to a slot inside the row.
+        unsigned s[SGM_MAPS_U][NV];
+#pragma unroll
+        for (int u = 0; u < SGM_MAPS_U; ++u) {
+            const unsigned *Sp = Srow + (size_t)min(x0 + u * SGM_MAPS_WAVES, a.W - 1) * a.Dp;
+#pragma unroll
+            for (int j = 0; j < NV; ++j) s[u][j] = Sp[min(j * 64 + lane, a.Dp - 1)];
+        }
+        int lv = 0;                                                // lane u: the left map's entry of pixel u
+#pragma unroll
+        for (int u = 0; u < SGM_MAPS_U; ++u) {
+            const int x = x0 + u * SGM_MAPS_WAVES;
+            int lkey = 0x7fffffff;
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                const int k = j * 64 + lane;
+                const bool real = k < a.D && x < a.W;              // (the padding elements of Dp take no part)
+                const unsigned key = (s[u][j] << 8) | (unsigned)k;
+                lkey = min(lkey, real ? (int)key : 0x7fffffff);
+                const int xr = x - a.dmin - k;                     // the landing column: < W for a real key, as dmin, k >= 0
+                atomicMin(rkey + min(xr >= 0 ? xr : -xr - 1, a.W - 1), real && xr >= 0 ? key : 0xffffffffu);
+            }
+            const int kmin = sgm_wave_min(lkey);
+            lv = lane == u ? a.dmin + (kmin & 255) : lv;
+        }
+        const int xl = x0 + lane * SGM_MAPS_WAVES;
+        if (lane < SGM_MAPS_U && xl < a.W) lrow[xl] = (uint8_t)lv;
+    }
+    __syncthreads();
+    uint8_t *lo = maps + (size_t)y * a.W, *ro = lo + (size_t)a.W * a.H;
+    for (int i = threadIdx.x; i < a.W; i += SGM_MAPS_WAVES * 64) {
+        const unsigned k = rkey[i];
+        lo[i] = lrow[i];
+        ro[i] = k == 0xffffffffu ? (uint8_t)0 : (uint8_t)(a.dmin + (int)(k & 255u));
+    }
+}
+
+template <int NV> __global__ __launch_bounds__(SGM_MAPS_WAVES * 64) void k_sgm_maps(SgmArgs a, uint8_t *maps) { sgm_maps<NV>(a, maps); }
+template <int NV>
+__global__ __launch_bounds__(SGM_MAPS_WAVES * 64) void k_sgm_maps_b(SgmArgs a, const SgmPair *tab)
+{
+    sgm_maps<NV>(sgm_pair_args(a, tab, blockIdx.z), sgm_global(tab[blockIdx.z].maps));
+}
+
+size_t sgm_maps_lds_bytes(int W) { return (size_t)W * 5; }
+
+// one workgroup per image row (a batch: the pair on grid axis z)
+void launch_sgm_maps(hipStream_t s, const SgmArgs &a, uint8_t *maps, const SgmPair *tab, int n)
+{
+    const dim3 block(SGM_MAPS_WAVES * 64);
+    const size_t lds = sgm_maps_lds_bytes(a.W);
+    auto go = [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        if (tab) hipLaunchKernelGGL(k_sgm_maps_b<NV>, dim3(a.H, 1, n), block, lds, s, a, tab);
+        else hipLaunchKernelGGL(k_sgm_maps<NV>, dim3(a.H), block, lds, s, a, maps);
+    };
+    if (a.Dp <= 64) go(std::integral_constant<int, 1>{});
+    else if (a.Dp <= 128) go(std::integral_constant<int, 2>{});
+    else go(std::integral_constant<int, 4>{});
 }
 
 }  // namespace psm

@@ -238,6 +238,26 @@ class DispEst:
         self._ck(self._lib.psm_sgm_speckle_time(self._h, C.byref(ms)), "sgm_speckle_time")
         return ms.value
 
+    def SGBMSelect_GPU(self, download: bool = True):
+        """psm_sgm_select_maps: the 8-bit maps of both views from the S of the last SGBM_GPU (sgbm_batch) into the object's device
+        maps, where LRCheck_GPU, FillInv_GPU, WgtMedian_GPU, JointWMF_GPU, Score_GPU(PSM_SCORE_GIF) and download_maps() find
+        them: the left map is the winner-takes-all disparity of S, the right map Hirschmueller's search along the epipolar line
+        in the same S (tests/sgm_maps_model.py).  The range is the one that SGBM_GPU ran with; it must lie inside [0, maxDis).
+        The int16 map, sgm_costs() and the guided-filter path's volumes are untouched.  -> (lDisMap, rDisMap); download=False:
+        the maps stay on the device, None."""
+        if download:
+            self._ck(self._lib.psm_sgm_select_maps(self._h, _ptr(self.lDisMap), _ptr(self.rDisMap), self.wid), "SGBMSelect_GPU")
+            return self.lDisMap, self.rDisMap
+        self._ck(self._lib.psm_sgm_select_maps(self._h, None, None, 0), "SGBMSelect_GPU")
+        return None
+
+    def sgm_maps_time(self):
+        """Device ms of the launch of the last SGBMSelect_GPU (sgbm_select_batch: of all pairs, on its first object); needs
+        PSM_OPT_PROFILE."""
+        ms = C.c_double()
+        self._ck(self._lib.psm_sgm_maps_time(self._h, C.byref(ms)), "sgm_maps_time")
+        return ms.value
+
     # ---- score: display maps and the error metric on the device (src/StereoMatch.cpp:181-185, 248-249, 275-309) ----
     def set_truth(self, gt, mask=None):
         """The dataset's ground truth and (optional) error mask, H x W uint8 each: uploaded once, kept until replaced or
@@ -642,6 +662,17 @@ def sgm_compute_batch(des):
     des = list(des)
     arr = (C.c_void_p * len(des))(*[d._h for d in des])
     capi.check(des[0]._lib.psm_sgm_compute_batch(arr, len(des)), des[0]._h, "sgm_compute_batch")
+
+
+def sgbm_select_batch(des):
+    """SGBMSelect_GPU(download=False) of several DispEst objects of one geometry in one launch (psm_sgm_select_maps_batch): each
+    object's S becomes its own device maps; every object afterwards behaves as after its own call (download_maps(),
+    LRCheck_GPU(), ...).  The results must share one disparity range."""
+    des = list(des)
+    if not des:
+        return
+    arr = (C.c_void_p * len(des))(*[d._h for d in des])
+    capi.check(des[0]._lib.psm_sgm_select_maps_batch(arr, len(des)), des[0]._h, "sgbm_select_batch")
 
 
 def joint_wmf_batch(des, radius: int = 0, sigma: float = 0.0, n_clusters: int = 0, max_iter: int = 0):

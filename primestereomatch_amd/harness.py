@@ -8,7 +8,7 @@ import numpy as np
 
 from . import capi
 from . import dispest
-from .dispest import DispEst, sgbm_batch, score_batch
+from .dispest import DispEst, sgbm_batch, score_batch, sgbm_select_batch
 
 MASK_NONE, MASK_NONOCC, MASK_DISC = 0, 1, 2   # include/StereoMatch.h
 
@@ -119,14 +119,18 @@ def compute_video(vFrame, rectification, maxDis=64, gt=None, mask=None, scale_fa
 
 
 def compute_sgbm(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, error_threshold=4, verbose=False, device_tail=False,
-                 **params):
+                 post_process=False, joint_wmf=False, **params):
     """One frame of STEREO_SGBM (src/StereoMatch.cpp:169-187, 275-309) on the device: l_bgr / r_bgr H x W x 3, uint8 or float32
     scaled by 1/255 (quantised on the device as lFrame.convertTo(lFrame, CV_8U, 255) does); params: DispEst.SGBM_GPU's, forwarded
     as they are - the reference's whole configuration is pre_filter_cap=63, speckle_window_size=100, speckle_range=32 (the
     defaults: SAD cost, no speckle filter), census=(win_w, win_h) selects the census cost; min_disparity / num_disparities choose another range than [0, maxDis), up to 1024
     disparities (the display conversion works from the map's own minimum and maximum).
     -> disp16 (imgDisparity16S), lDispMap (the display map), the reference's error metric on it, and bp_percent_int.
-    device_tail: display map and both metrics from the device (DispEst.Score_GPU, PSM_SCORE_SGM and PSM_SCORE_SGM_INT)."""
+    device_tail: display map and both metrics from the device (DispEst.Score_GPU, PSM_SCORE_SGM and PSM_SCORE_SGM_INT).
+    post_process: afterwards the stage's 8-bit maps of both views (DispEst.SGBMSelect_GPU) go through the post-processing chain of
+    the GIF path on the device - LRCheck, FillInv, WgtMedian; joint_wmf: JointWMF in place of the latter two - and the record
+    gains lDisMap_pp, the filtered left map, and (with gt) bp_percent_pp / avg_err_pp, the metric of compute() on it - from
+    Score_GPU(PSM_SCORE_GIF) under device_tail.  The range must lie inside [0, maxDis).  Off, the default: no key is added."""
     out = {}
     lFrame, rFrame = np.ascontiguousarray(l_bgr), np.ascontiguousarray(r_bgr)
     with DispEst(lFrame, rFrame, maxDis, 8, True) as SMDE:
@@ -136,15 +140,43 @@ def compute_sgbm(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, er
         if params.get("speckle_window_size", 0) > 0:
             out["speckle_ms"] = SMDE.sgm_speckle_time()
         tail = _device_tail_sgbm([SMDE], [gt], [mask], scale_factor, error_threshold)[0] if device_tail else None
+        if post_process or joint_wmf:
+            SMDE.SGBMSelect_GPU()
+            _post_process_sgbm([SMDE], [out], [gt], [mask], scale_factor, error_threshold, joint_wmf, device_tail)
     return _finish_sgbm(out, maxDis, gt, mask, scale_factor, error_threshold, verbose, tail)
 
 
+def _post_process_sgbm(des, outs, gts, masks, scale_factor, error_threshold, joint_wmf, device_tail):
+    """The chain behind SGBMSelect_GPU on every object's device maps, and its keys of the record: lDisMap_pp and the metric on it."""
+    for d in des:
+        d.LRCheck_GPU()
+        if not joint_wmf:
+            d.FillInv_GPU()
+            d.WgtMedian_GPU()
+    if joint_wmf and len(des) == 1:
+        des[0].JointWMF_GPU()
+    elif joint_wmf:
+        dispest.joint_wmf_batch(des)
+    tails = _device_tail(des, gts, masks, scale_factor, error_threshold, capi.PSM_SCORE_GIF) if device_tail else [None] * len(des)
+    for i, (d, out) in enumerate(zip(des, outs)):
+        out["lDisMap_pp"] = d.lDisMap.copy()
+        gt, mask = (gts[i] if gts else None), (masks[i] if masks else None)
+        if gt is None:
+            continue
+        if tails[i] is not None:
+            out["bp_percent_pp"], out["avg_err_pp"] = tails[i][1]["bp_percent"], tails[i][1]["avg_err"]
+        else:
+            out["bp_percent_pp"], out["avg_err_pp"] = error_vs_ground_truth(out["lDisMap_pp"], gt, mask, d.maxDis, scale_factor,
+                                                                             error_threshold)[:2]
+
+
 def compute_sgbm_batch(pairs, maxDis=64, gts=None, masks=None, scale_factor=4, error_threshold=4, verbose=False, device_tail=False,
-                       **params):
+                       post_process=False, joint_wmf=False, **params):
     """compute_sgbm for a list of (l_bgr, r_bgr) pairs of one size and depth in shared launches (dispest.sgbm_batch): the
     reference's loop over pairs and datasets (src/main.cpp:64-73, src/StereoMatch.cpp:528-609).  gts / masks: one per pair (or
     None).  -> a list of compute_sgbm's records; the times are the batch's divided by the number of pairs.  device_tail: display
-    maps and both metrics of all pairs from the device (dispest.score_batch)."""
+    maps and both metrics of all pairs from the device (dispest.score_batch).  post_process / joint_wmf: compute_sgbm's, the maps of
+    all pairs from one launch (dispest.sgbm_select_batch)."""
     pairs = [(np.ascontiguousarray(l), np.ascontiguousarray(r)) for l, r in pairs]
     if not pairs:
         return []
@@ -155,12 +187,17 @@ def compute_sgbm_batch(pairs, maxDis=64, gts=None, masks=None, scale_factor=4, e
         times = [t / len(des) for t in des[0].sgm_times()]
         spk = des[0].sgm_speckle_time() / len(des) if params.get("speckle_window_size", 0) > 0 else None
         tails = _device_tail_sgbm(des, gts, masks, scale_factor, error_threshold) if device_tail else [None] * len(des)
+        pps = [{} for _ in des]
+        if post_process or joint_wmf:
+            sgbm_select_batch(des)
+            _post_process_sgbm(des, pps, gts, masks, scale_factor, error_threshold, joint_wmf, device_tail)
     finally:
         for d in des:
             d.close()
     outs = []
     for i, d16 in enumerate(maps):
         out = {"disp16": d16, "cost_ms": times[0], "paths_ms": times[1], "select_ms": times[2]}
+        out.update(pps[i])
         if spk is not None:
             out["speckle_ms"] = spk
         outs.append(_finish_sgbm(out, maxDis, gts[i] if gts else None, masks[i] if masks else None, scale_factor, error_threshold,

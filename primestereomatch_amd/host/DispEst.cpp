@@ -259,6 +259,21 @@ int DispEst::SGBM_GPU(std::vector<int16_t> &disp16)
     return hipUtil::api().sgm_compute(ctx[0]) || hipUtil::api().sgm_download_disparity(ctx[0], disp16.data(), 0);
 }
 
+int DispEst::SGBMSelect()
+{
+    if (ctx.size() != 1) {
+        fprintf(stderr, "DispEst: SGBMSelect runs on single-device objects only\n");
+        return 1;
+    }
+    return hipUtil::api().sgm_select_maps(ctx[0], lDisMap.data, rDisMap.data, lDisMap.step);
+}
+
+int DispEst::sgbmMapsTime(double *ms)
+{
+    if (ctx.empty()) return 1;
+    return hipUtil::api().sgm_maps_time(ctx[0], ms);
+}
+
 int DispEst::setSGBMSpeckle(int speckleWindowSize, int speckleRange)
 {
     if (ctx.empty()) return 1;
@@ -370,6 +385,23 @@ int DispEst::SGBMBatch(DispEst *const *des, int n, std::vector<std::vector<int16
         disp16[i].resize((size_t)des[i]->wid * des[i]->hei);
         rc |= api.sgm_download_disparity(cs[i], disp16[i].data(), 0);
     }
+    return rc;
+}
+
+int DispEst::SGBMSelectBatch(DispEst *const *des, int n)
+{
+    if (!des || n < 1) return 1;
+    std::vector<psm_ctx *> cs;
+    for (int i = 0; i < n; ++i) {
+        if (!des[i] || des[i]->ctx.size() != 1) {
+            fprintf(stderr, "DispEst: SGBMSelectBatch runs on single-device objects only\n");
+            return 1;
+        }
+        cs.push_back(des[i]->ctx[0]);
+    }
+    const HipApi &api = hipUtil::api();
+    int rc = api.sgm_select_maps_batch(cs.data(), n);
+    for (int i = 0; i < n && !rc; ++i) rc |= api.download_maps(cs[i], des[i]->lDisMap.data, des[i]->rDisMap.data, des[i]->lDisMap.step);
     return rc;
 }
 

@@ -131,6 +131,13 @@ public:
     // window, both odd, 3 .. 9 by 3 .. 7 - unchanged when the two cameras differ in gain or exposure.  (0, 0), the setting of a new
     // object: off.  Refused by SGBM_GPU together with a preFilterCap > 0.  SGBMBatch wants one window on all its objects.
     int setSGBMCensus(int winW, int winH);
+    // The 8-bit maps of both views from the summed path costs of the last SGBM_GPU (psm_sgm_select_maps): lDisMap - the
+    // winner-takes-all disparity - and rDisMap - the search along the epipolar line in the same costs - are filled and become the
+    // object's device maps, so LRCheck_GPU, FillInvalid_GPU, WgtMedian_GPU, JointWMF_GPU and Score(PSM_SCORE_GIF) run behind the
+    // SGBM stage as behind DispSelect_GPU.  The range of that SGBM_GPU must lie inside [0, maxDis); the int16 map and the GIF
+    // stages' volumes are untouched.  sgbmMapsTime: device ms of the launch under PSM_OPT_PROFILE.
+    int SGBMSelect();
+    int sgbmMapsTime(double *ms);
 
     // The steps of StereoMatch::compute behind the maps, on the device (psm_score): setGroundTruth uploads the dataset's ground truth
     // and (mask non-NULL) error mask once, H x W CV_8UC1 each; setScoreParams: scale_factor, error_threshold, PSM_MASK_NONE / NONOCC /
@@ -163,6 +170,8 @@ public:
     // launches (psm_sgm_compute_batch); disp16[i]: object i's H x W int16 map, as SGBM_GPU returns it.  Every object is afterwards
     // where its own SGBM_GPU would have left it; sgbmTimes / sgbmSpeckleTime of des[0] report the batch.
     static int SGBMBatch(DispEst *const *des, int n, std::vector<std::vector<int16_t>> &disp16);
+    // SGBMSelect of n such objects in one launch (psm_sgm_select_maps_batch); every object's lDisMap / rDisMap receive its maps.
+    static int SGBMSelectBatch(DispEst *const *des, int n);
     // ... and the live post-filter: JointWMF_GPU of n single-device objects of one geometry in shared launches (psm_joint_wmf_batch;
     // 0: the reference's radius, sigma, cluster count and iteration limit), each object's device maps with its own pair - after
     // computeBatch, say, with or without the L-R check between; every object's lDisMap / rDisMap receive its filtered maps.

@@ -61,7 +61,8 @@ bool hipUtil::load(const char *path)
               bind(g_api.sgm_download_speckle_sizes, "psm_sgm_download_speckle_sizes") && bind(g_api.sgm_speckle_time, "psm_sgm_speckle_time") &&
               bind(g_api.sgm_set_prefilter, "psm_sgm_set_prefilter") && bind(g_api.sgm_compute_batch, "psm_sgm_compute_batch") &&
               bind(g_api.sgm_set_mode, "psm_sgm_set_mode") && bind(g_api.sgm_set_range, "psm_sgm_set_range") &&
-              bind(g_api.sgm_set_census, "psm_sgm_set_census") &&
+              bind(g_api.sgm_set_census, "psm_sgm_set_census") && bind(g_api.sgm_select_maps, "psm_sgm_select_maps") &&
+              bind(g_api.sgm_select_maps_batch, "psm_sgm_select_maps_batch") && bind(g_api.sgm_maps_time, "psm_sgm_maps_time") &&
               bind(g_api.joint_wmf_batch, "psm_joint_wmf_batch") && bind(g_api.score_set_truth, "psm_score_set_truth") &&
               bind(g_api.score_set_params, "psm_score_set_params") && bind(g_api.score, "psm_score") &&
               bind(g_api.score_download, "psm_score_download");

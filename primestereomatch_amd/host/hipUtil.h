@@ -60,6 +60,9 @@ struct HipApi {
     int (*sgm_set_mode)(psm_ctx *, int) = nullptr;
     int (*sgm_set_range)(psm_ctx *, int, int) = nullptr;
     int (*sgm_set_census)(psm_ctx *, int, int) = nullptr;
+    int (*sgm_select_maps)(psm_ctx *, uint8_t *, uint8_t *, size_t) = nullptr;
+    int (*sgm_select_maps_batch)(psm_ctx *const *, int) = nullptr;
+    int (*sgm_maps_time)(psm_ctx *, double *) = nullptr;
     int (*joint_wmf_batch)(psm_ctx *const *, int, int, float, int, int) = nullptr;
     // score: display maps and the error metric against ground truth
     int (*score_set_truth)(psm_ctx *, const uint8_t *, const uint8_t *, size_t) = nullptr;

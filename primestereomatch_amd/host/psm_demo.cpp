@@ -1,6 +1,6 @@
 // psm_demo - headless counterpart of the reference's StereoMatch::compute accelerator branch
 // (src/StereoMatch.cpp:193-262): raw B,G,R uint8 pair in, four timed stages, raw uint8 maps out.
-//   psm_demo <left.raw> <right.raw> <W> <H> <maxDis> <out_prefix> [ndev] [f32|u8] [float_input] [fgf_rate] [pp] [frames] [batch] [ring] [sgbm|sgbm_ref|sgbm_census|-] [gt.raw] [mask.raw|-]
+//   psm_demo <left.raw> <right.raw> <W> <H> <maxDis> <out_prefix> [ndev] [f32|u8] [float_input] [fgf_rate] [pp] [frames] [batch] [ring] [sgbm|sgbm_ref|sgbm_census|-] [gt.raw] [mask.raw|-] [pp]
 // gt.raw (the 16th argument; W x H bytes, mask.raw likewise): the left map - after pp, if given - is scored on the device
 // (DispEst::Score: scale_factor 4, error_threshold 4, the non-occluded mask if one is given) and the reference's line
 // "%BP = ... Avg Err = ..." (src/StereoMatch.cpp:306) is printed from the device record; the display map and the error plane go to
@@ -10,6 +10,9 @@
 // cost, no speckle filter); the word "sgbm_ref": the same with the whole configuration of setupOpenCVSGBM (:639-660) -
 // preFilterCap 63, speckleWindowSize 100, speckleRange 32 - and the filter's time as a fourth line; the word "sgbm_census": the
 // settings of sgbm with the census cost over a 9 x 7 window (DispEst::setSGBMCensus), nothing else changed
+// pp: the 19th argument, the word "pp", with one of the sgbm words: the stage's 8-bit maps (DispEst::SGBMSelect) then go through
+// lrCheck, fillInv and wgtMedian on the device; the filtered left map is dumped as <out>_sgbm_pp_ldisp.raw and, with gt.raw, scored
+// like a GIF map (its %BP line)
 // ring > 0: additionally push that many frames of the pair through a psm::FrameRing of two objects (two frames in flight, each
 // object told PSM_OPT_FRAMES_IN_FLIGHT = 2), check every delivered frame's maps against the single-pair run, dump <out>_ldisp_ring.raw
 // batch > 1: additionally run that many copies of the pair as ONE batch (DispEst::computeBatch -> psm_compute_batch: the
@@ -52,7 +55,7 @@ static bool dump(const std::string &path, const unsigned char *p, size_t n)
 int main(int argc, char **argv)
 {
     if (argc < 7) {
-        fprintf(stderr, "usage: %s left.raw right.raw W H maxDis out_prefix [ndev] [f32|u8] [float_input] [fgf_rate] [pp] [frames] [batch] [ring] [sgbm|sgbm_ref|sgbm_census|-] [gt.raw] [mask.raw|-]\n", argv[0]);
+        fprintf(stderr, "usage: %s left.raw right.raw W H maxDis out_prefix [ndev] [f32|u8] [float_input] [fgf_rate] [pp] [frames] [batch] [ring] [sgbm|sgbm_ref|sgbm_census|-] [gt.raw] [mask.raw|-] [pp]\n", argv[0]);
         return 2;
     }
     const int W = atoi(argv[3]), H = atoi(argv[4]), D = atoi(argv[5]);
@@ -70,6 +73,7 @@ int main(int argc, char **argv)
     const bool sgbm = sgbm_ref || sgbm_census || (argc > 15 && !strcmp(argv[15], "sgbm"));
     const char *gt_path = argc > 16 ? argv[16] : nullptr;
     const char *mask_path = argc > 17 && strcmp(argv[17], "-") ? argv[17] : nullptr;
+    const bool sgbm_pp = sgbm && argc > 18 && !strcmp(argv[18], "pp");
     std::vector<unsigned char> lraw, rraw, gtraw, maskraw;
     if (gt_path && (!slurp(gt_path, gtraw, (size_t)W * H) || (mask_path && !slurp(mask_path, maskraw, (size_t)W * H)))) {
         fprintf(stderr, "psm_demo: cannot read the ground truth / mask\n");
@@ -195,6 +199,16 @@ int main(int argc, char **argv)
             if (SMDE.Score(PSM_SCORE_SGM, &rec, &disp, nullptr)) return 5;
             printf("%%BP = %.2f%% \t Avg Err = %.2f\n", psm::DispEst::scoreBP(rec), psm::DispEst::scoreAvgErr(rec));
             ok = dump(out + "_sgbm_disp.raw", disp.data, (size_t)W * H);
+        }
+        if (ok && sgbm_pp) {      // the stage's 8-bit maps through the post-processing chain of the GIF path, scored like its maps
+            if (SMDE.SGBMSelect() || SMDE.LRCheck_GPU() || SMDE.FillInvalid_GPU() || SMDE.WgtMedian_GPU()) return 5;
+            ok = dump(out + "_sgbm_pp_ldisp.raw", SMDE.lDisMap.data, (size_t)W * H);
+            if (ok && gt_path) {
+                struct psm_score rec;
+                if (SMDE.Score(PSM_SCORE_GIF, &rec, nullptr, nullptr)) return 5;
+                printf("SGBM post-processed (lrCheck, fillInv, wgtMedian): %%BP = %.2f%% \t Avg Err = %.2f\n", psm::DispEst::scoreBP(rec),
+                       psm::DispEst::scoreAvgErr(rec));
+            }
         }
         if (ok && batch > 1 && ndev == 1) {
             std::vector<psm::DispEst *> des;

@@ -39,7 +39,15 @@ pre_filter_cap 0 and 63 with the speckle filter on at (100, 32): per-pair ms of 
 (psm_sgm_times / psm_sgm_speckle_time of its first context over N), beside the same N contexts run one after another through
 psm_sgm_compute in the same process (the mean of their own times), hipEvents, median of --runs after --warmup, and the wall time
 per pair of both.  --reps R: the whole pair of measurements R times, singles and batch alternating - the spread between the
-repetitions is what a difference has to exceed."""
+repetitions is what a difference has to exceed.
+
+--maps: instead of the above, the 8-bit maps of both views (psm_sgm_select_maps; k_sgm_maps) beside the group it is measured
+against.  Per configuration (SAD cost, the configuration's D, filter off), --reps times over: --warmup rounds, then --runs rounds
+of psm_sgm_compute, psm_sgm_select_maps with the maps left on the device, and the post-processing chain behind them (psm_lr_check,
+psm_fill_invalid, psm_wgt_median, maps left on the device).  Reported per repetition: the medians of psm_sgm_times' third number
+(select + check: the same S read once, one wave per pixel), of psm_sgm_maps_time and of the chain's wall time; over the
+repetitions their medians and, as "*_spread", the smallest and largest - what a difference has to exceed - and the bytes the
+launch moves (S once, 4 B per element of the padded volume, 2 B per pixel written) over its time."""
 import argparse
 import json
 import os
@@ -242,6 +250,53 @@ def modes_bench(a):
                 de.close()
 
 
+def maps_bench(a):
+    import primestereomatch_amd as P
+    from primestereomatch_amd import capi
+    if capi.device_count() < 1:
+        raise SystemExit("sgm_bench: no HIP device visible")
+    for name in a.configs.split(","):
+        W, H, D = CONFIGS[name]
+        if D > 256:
+            continue                                               # (the maps are 8-bit)
+        l, r = the_pair(name)
+        Dp = (D + 3) & ~3
+        sel, maps, chain = [], [], []
+        with P.DispEst(l, r, D) as de:
+            de.set_option(capi.PSM_OPT_PROFILE, 1)
+            lib, h = de._lib, de._h
+
+            def round_():
+                de._ck(lib.psm_sgm_compute(h), "psm_sgm_compute")
+                de._ck(lib.psm_sgm_select_maps(h, None, None, 0), "psm_sgm_select_maps")
+                w0 = time.perf_counter()
+                de._ck(lib.psm_lr_check(h, None, None, 0), "psm_lr_check")
+                de._ck(lib.psm_fill_invalid(h, None, None, 0), "psm_fill_invalid")
+                de._ck(lib.psm_wgt_median(h, None, None, 0), "psm_wgt_median")
+                de.synchronize()
+                return de.sgm_times()[2], de.sgm_maps_time(), (time.perf_counter() - w0) * 1e3
+
+            de.SGBM_GPU()
+            for _ in range(a.reps):
+                for _ in range(a.warmup):
+                    round_()
+                t = np.array([round_() for _ in range(a.runs)])
+                m = np.median(t, axis=0)
+                sel.append(float(m[0])); maps.append(float(m[1])); chain.append(float(m[2]))
+        moved = 4 * W * H * Dp + 2 * W * H
+        rec = {"bench": "sgm_maps", "config": name, "W": W, "H": H, "D": D, "runs": a.runs, "warmup": a.warmup, "reps": a.reps}
+        for key, v in (("select_ms", sel), ("maps_ms", maps), ("chain_wall_ms", chain)):
+            rec[key] = round(float(np.median(v)), 4)
+            rec[key + "_spread"] = [round(min(v), 4), round(max(v), 4)]
+        rec.update({"maps_over_select": round(rec["maps_ms"] / rec["select_ms"], 3), "maps_bytes_moved": int(moved),
+                    "maps_fraction_of_copy_ceiling": round(moved / COPY_CEILING * 1e3 / rec["maps_ms"], 4)})
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="cones,720p,1080p")
@@ -256,6 +311,7 @@ def main():
     ap.add_argument("--min-disparity", type=int, default=0, help="psm_sgm_set_range: the first disparity")
     ap.add_argument("--num-disparities", type=int, default=0, help="psm_sgm_set_range: their number, up to 1024 (0: the configuration's D)")
     ap.add_argument("--census", default=None, help="W,H: also time the census cost with this window (psm_sgm_set_census)")
+    ap.add_argument("--maps", action="store_true", help="time psm_sgm_select_maps beside the select group and the chain behind it (maps_bench)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert a.runs >= 1
@@ -264,6 +320,8 @@ def main():
         raise SystemExit("sgm_bench: --census goes with the plain record and with --batch")
     if (a.mode or a.batch) and (a.min_disparity or a.num_disparities):
         raise SystemExit("sgm_bench: --min-disparity / --num-disparities go with the plain record only")
+    if a.maps:
+        return maps_bench(a)
     if a.mode:
         return modes_bench(a)
     if a.batch:
