@@ -87,6 +87,7 @@ int wta_launch(psm_ctx *c, long long *keys, uint8_t *maps)
     // a side that is not the select filter's packed minima was selected from a whole volume: its map is whole
     const bool both_keys = pending_keys(c->vside[0]) && pending_keys(c->vside[1]);
     if (!both_keys) cover(c->res, whole_image(c));
+    else cover_filtered(c->res);                  // (maps uploaded, gathered or selected by the SGM stage in between covered the whole image)
     if (both_keys && !keys && maps) {             // both sides already reduced to keys: one launch for both maps
         if (take_early(c->res, maps)) return 0;   // ... unless the filter's reduction wrote them already (once: post-processing rewrites the maps in place)
         Prof p(c, PSM_K_WTA);
@@ -263,6 +264,7 @@ int psm_gather_rows_ctx(psm_ctx *root, psm_ctx *const *stripes, int nstripes, ui
             if (gather_leg(root, root->maps + side * HW + o, s, s->maps + side * HW + o, n)) return 1;
     }
     cover(root->res, whole_image(root));      // the root's maps are whole now
+    forget_early(root->res);                  // (a single-phase filter of the root's own, not selected yet, no longer finds its maps there)
     maps_written(root->res);
     if (copy_maps_out(root, root->maps, lmap, rmap, stride)) return 1;
     if (!root->opt_async) PSM_HIP(root, hipStreamSynchronize(root->stream));
@@ -304,6 +306,7 @@ int psm_disp_merge(psm_ctx *c, const void *dev_keys_all, int nranks, uint8_t *lm
     if (check_launch(c, "merge")) return 1;
     // (the merged keys are those of this job's shards, filtered under the stripe this context recorded - Results::rows
     // stay as psm_cost_filter left them: stripes of disparity shards merge to a stripe)
+    forget_early(c->res);                     // (as above: the merged maps replaced what the context's own filter had put there)
     maps_written(c->res);
     if (copy_maps_out(c, c->maps, lmap, rmap, stride)) return 1;
     if (!c->opt_async) PSM_HIP(c, hipStreamSynchronize(c->stream));

@@ -49,14 +49,18 @@ struct Results {
     // The rows the minima and the maps cover: the psm_set_rows stripe in force when psm_cost_filter produced them - recorded at
     // filter time, psm_set_rows itself only affects the NEXT filter - else the whole image ([0, H) from psm_create* on).
     Rows rows;
+    // The rows the last filter covered, as it recorded them: `rows` follows whoever wrote the maps last (an upload, the SGM stage, a
+    // gather cover the whole image), the pending minima go on covering these - a select of them brings `rows` back here.
+    Rows filt;
     const uint8_t *early = nullptr;     // the map buffer the single-phase filter's reduction (k_chunk_min) already filled, or null
 };
 inline void maps_gone(Results &r) { r.maps = r.mask = false; }
 inline void forget_early(Results &r) { r.early = nullptr; }
 inline void stale(Results &r) { maps_gone(r); forget_early(r); }            // new costs, a volume uploaded
 // ... or a filter ran, for `rows`; early: the map buffer its own reduction filled on the way (null: none)
-inline void filtered(Results &r, Rows rows, const uint8_t *early) { maps_gone(r); r.rows = rows; r.early = early; }
+inline void filtered(Results &r, Rows rows, const uint8_t *early) { maps_gone(r); r.rows = r.filt = rows; r.early = early; }
 inline void cover(Results &r, Rows rows) { r.rows = rows; }
+inline void cover_filtered(Results &r) { r.rows = r.filt; }               // what is selected from the pending minima covers what they cover
 inline void maps_written(Results &r) { r.maps = true; r.mask = false; }     // new maps: a mask of earlier ones does not describe them
 inline void mask_written(Results &r) { r.mask = r.maps; }
 // psm_disp_select, both sides pending as keys: true when `maps` is what the filter's reduction filled - once

@@ -1,6 +1,8 @@
 """Randomised soak of the CONTEXT STATE MACHINE (not part of the test suite): one context lives through a random sequence of
 new image pairs, row stripes, tuning flags and readers of intermediate results; after every filter + select the maps of the
-current stripe must equal the oracle's for the current pair.
+current stripe must equal the oracle's for the current pair.  The suite's version is tests/test_gpu_sequences.py with the shadow
+of tests/seq_model.py: every stage, three contexts, every reader against the models; this script stays as the open-ended soak of
+the guided-filter path at random geometries.
     python scripts/soak_state.py [seconds] [seed]
     python scripts/soak_state.py --episodes N [seed]     (the same N episodes for a seed on every build: for comparing two)"""
 import os

@@ -48,6 +48,20 @@ int res_step(int *st, int op, int a, int b, int e)
     return ret;
 }
 
+// A filter under the stripe [fy0, fy1), then maps from elsewhere that cover [cy0, cy1) (an upload, a gather, the SGM stage), then the
+// select of the minima still pending: y = the rows the results cover after the foreign maps and after the select.
+void rows_across_foreign_maps(int fy0, int fy1, int cy0, int cy1, int *y)
+{
+    Results r;
+    filtered(r, Rows{fy0, fy1}, nullptr);
+    cover(r, Rows{cy0, cy1});
+    maps_written(r);
+    y[0] = r.rows.y0; y[1] = r.rows.y1;
+    cover_filtered(r);
+    maps_written(r);
+    y[2] = r.rows.y0; y[3] = r.rows.y1;
+}
+
 int rows_whole(int H, int y0, int y1) { return Rows{y0, y1} == whole_image(H); }
 
 }  // extern "C"

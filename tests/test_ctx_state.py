@@ -109,3 +109,15 @@ def test_results_mask_rows_and_early_map(probe):
     assert st[2:4] == [0, 1]
     st, _ = res(probe, st, KEYS_COMPLETE, 0)
     assert st[2:4] == [1, 1] and res(probe, st, KEYS_GONE)[0][2:4] == [0, 0]
+
+
+def test_pending_minima_keep_their_rows_across_foreign_maps(probe):
+    """Maps written by someone else than the select (psm_upload_maps, psm_gather_rows_ctx, the SGM stage) cover the whole image; the
+    minima a striped filter left pending still cover the stripe, and so do the maps a later select makes of them."""
+    H = 60
+    for stripe in ((20, 40), (0, 7), (0, H)):
+        y = (ctypes.c_int * 4)()
+        probe.rows_across_foreign_maps(*stripe, 0, H, y)
+        assert tuple(y) == (0, H, *stripe)
+        assert probe.rows_whole(H, y[2], y[3]) == (stripe == (0, H))
+
