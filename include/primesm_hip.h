@@ -556,8 +556,9 @@ int psm_wgt_median_stats(psm_ctx *ctx, int sweeps[2], long long evals[2]);
  * splitmix64 stream, Lloyd iterations in fp32 until no label changes or max_iter).
  * radius 1..16, sigma > 0, n_clusters 1..256, max_iter >= 1; 0 or a negative value selects the reference's value
  * (9 = MED_SZ/2, 25.5, 256, 10000).  Refuses stripe-only maps.  lmap/rmap (optional) receive the filtered maps.
- * Synchronises with the host when the device k-means runs (the host reads the sample count and the convergence counter);
- * it runs once per pair and (n_clusters, max_iter).  With clusters set for both sides, or on a later call for the same pair,
+ * Synchronises with the host when the device k-means runs (the host reads the sample counts and the convergence flags);
+ * it runs once per pair and (n_clusters, max_iter), the images of both sides in the same launches, as a psm_joint_wmf_batch of
+ * this one context would run them.  With clusters set for both sides, or on a later call for the same pair,
  * it is asynchronous under PSM_OPT_ASYNC (the weight tables are formed once per clustering and sigma and copied from
  * page-locked memory).  Kernel time: PSM_K_JWMF; stage PSM_STAGE_PP. */
 int psm_joint_wmf(psm_ctx *ctx, int radius, float sigma, int n_clusters, int max_iter, uint8_t *lmap, uint8_t *rmap, size_t stride);
@@ -595,8 +596,8 @@ int psm_joint_wmf_clusters(psm_ctx *ctx, int side, int *n_clusters, float *centr
  * The launches run on ctxs[0]'s stream, after everything already queued on the other contexts' streams (a pending
  * psm_download_maps_async of their maps included) and before anything queued on them later; synchronous on return unless ctxs[0]
  * has PSM_OPT_ASYNC.  Contexts under psm_share_streams work as they are.
- * Buffers stay per context (allocated on first use); the kernels reach them through a device table of n * 272 bytes that ctxs[0]
- * owns and uploads from page-locked memory only when an entry changed, and the Lloyd states and centres of the m images lie in a
+ * Buffers stay per context (allocated on first use); with n > 1 the kernels reach them through a device table of n * 272 bytes that
+ * ctxs[0] owns and uploads from page-locked memory only when an entry changed (n = 1: in the kernel arguments), and the Lloyd states and centres of the m images lie in a
  * block of ctxs[0] (n * 6176 bytes, and as much page-locked memory), so one copy reads all of them.  PSM_STAGE_PP of every
  * context receives the batch's wall time; with PSM_OPT_PROFILE 1 on ctxs[0], PSM_K_JWMF of ctxs[0] counts the batch's launches. */
 int psm_joint_wmf_batch(psm_ctx *const *ctxs, int n, int radius, float sigma, int n_clusters, int max_iter);

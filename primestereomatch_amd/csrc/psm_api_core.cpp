@@ -81,8 +81,7 @@ void adopt_new_pair(psm_ctx *c, int depth)
     for (VolSide &v : c->vside) new_costs(v, false);       // nothing virtual survives a new pair
     stale(c->res);
     keys_gone(c->res);
-    c->jw_have[0] = c->jw_have[1] = c->jw_user[0] = c->jw_user[1] = false;   // clusters belong to the images
-    c->jw_tab_ok[0] = c->jw_tab_ok[1] = false;
+    for (JwClust &q : c->jw_cl) q.gone();                  // clusters belong to the images
 }
 
 }  // namespace psm

@@ -86,10 +86,26 @@ struct SgmState {
     bool maps_timed = false;
 };
 
-// psm_joint_wmf_batch (psm_api_jwmf.cpp; this context as the first of a batch): the device table - JwImg records of the images to
-// cluster, behind them the JwSide records of the map sides - with its host copy (uploaded again only when an entry changed) and
-// its page-locked staging, two slots used alternately as SgmState's; `block`: the Lloyd states and centres of the images side by
-// side, `pin` the page-locked memory the host reads them in.
+// JointWMF (psm_api_jwmf.cpp): what a side's clustering of the current pair is.  Written by its three transitions alone; each makes
+// the whole record anew, so none can leave the device weight table of an earlier clustering standing as current.
+struct JwClust {
+    bool have = false, user = false;               // a clustering exists (run or set) / ... and the host set it (psm_joint_wmf_set_clusters)
+    int nf = 0, iters = 0;
+    int n_clusters = 0, max_iter = 0;              // the parameters of the device k-means that made it
+    std::vector<float> centres;
+    bool tab_ok = false;                           // the device weight table is that of this clustering with sigma tab_sigma
+    float tab_sigma = 0.f;
+    // clustering adopted from the device k-means / clustering set by host / clustering gone: with the image pair, or because the
+    // side's lok, labels or centres buffers are about to be rewritten
+    void adopted(int nf_, int it, int nc, int mi, const float *cen) { *this = JwClust{true, false, nf_, it, nc, mi, {cen, cen + 3 * (size_t)nf_}}; }
+    void set_by_host(int nf_, const float *cen) { *this = JwClust{true, true, nf_, 0, 0, 0, {cen, cen + 3 * (size_t)nf_}}; }
+    void gone() { *this = JwClust{}; }
+};
+
+// psm_joint_wmf, psm_joint_wmf_batch (psm_api_jwmf.cpp; this context as the first of the call): `block`: the Lloyd states and centres
+// of the images to cluster side by side, `pin` the page-locked memory the host reads them in.  A call of several contexts also has
+// the device table - JwImg records of the images to cluster, behind them the JwSide records of the map sides - with its host copy
+// (uploaded again only when an entry changed) and its page-locked staging, two slots used alternately as SgmState's.
 struct JwBatch {
     uint8_t *tab = nullptr, *tab_pin = nullptr;
     std::vector<uint8_t> tab_host;
@@ -180,13 +196,7 @@ struct psm_ctx {
     long long wm_evals[2] = {0, 0};
     // psm_joint_wmf (psm_api_jwmf.cpp): one device block for both sides (psm::JwScratch), allocated on first use
     uint8_t *jw = nullptr;
-    bool jw_have[2] = {false, false};   // a clustering of the current pair exists for the side (run or set)
-    bool jw_user[2] = {false, false};   // ... and the host set it (psm_joint_wmf_set_clusters)
-    int jw_nf[2] = {0, 0}, jw_iters[2] = {0, 0};
-    int jw_params[2][2] = {{0, 0}, {0, 0}};   // {n_clusters, max_iter} of the device k-means that made the side's clustering
-    std::vector<float> jw_centres[2];
-    bool jw_tab_ok[2] = {false, false};  // the device weight table of the side is that of its clustering with sigma jw_tab_sigma
-    float jw_tab_sigma[2] = {0.f, 0.f};
+    psm::JwClust jw_cl[2];
     unsigned long long *jw_pin = nullptr;  // page-locked staging of the two integer tables (on first use)
     hipEvent_t ev_jw[2] = {nullptr, nullptr};   // ... the copy out of a side's staging has executed
     psm::JwBatch jwb;

@@ -12,11 +12,14 @@
 // speed-up of that definition; nothing of it is used here.  The weight table itself is formed on the host with libm expf
 // (psm_api_jwmf.cpp), so it is the reference's float table bit for bit.
 //
-// Several pairs per launch (psm_joint_wmf_batch): every kernel is one body (jw_*) behind two entries.  k_jw_* takes its buffers
-// as arguments, as ever; k_jw_*_b has the image to cluster (JwImg) or the map side (JwSide) on a grid axis of its own and reads
-// the buffers from the device table - the index is uniform per workgroup, so these are scalar loads ahead of an unchanged body.
-// All sums are exact integers: a body's result does not depend on the grid it runs in.
+// One launch sequence for a single pair and for several (psm_joint_wmf, psm_joint_wmf_batch): every kernel is one body (jw_*)
+// behind one entry k_jw_*<S>, which has the image to cluster (JwImg) or the map side (JwSide) on a grid axis of its own and is
+// templated over where the records come from - S = JwVal<R>: the at most two records of a single pair by value in the kernarg;
+// S = const R *: the device table of a batch.  The index is uniform per workgroup, so either way these are scalar loads ahead of
+// the same body.  All sums are exact integers: a body's result does not depend on the grid it runs in.
 #include "psm_kernels.h"
+
+#include <algorithm>
 
 namespace psm {
 
@@ -47,6 +50,14 @@ __device__ __forceinline__ unsigned key_at(const void *img, int depth, size_t p)
 
 __device__ __forceinline__ void key_xyz(unsigned k, int &x, int &y, int &z) { x = (int)(k >> 12); y = (int)((k >> 6) & 63); z = (int)(k & 63); }
 
+// record i of either source (psm_kernels.h, JwRecs); its pointers are read as global ones (sgm_global)
+template <typename R> __device__ __forceinline__ const R &jw_rec(const R *tab, unsigned i) { return tab[i]; }
+template <typename R> __device__ __forceinline__ const R &jw_rec(const JwVal<R> &v, unsigned i) { return v.r[i]; }
+using ImgV = JwVal<JwImg>;
+using ImgT = const JwImg *;
+using SideV = JwVal<JwSide>;
+using SideT = const JwSide *;
+
 // presence of every key of one image: one bit per key in a 2^18-bit map
 __device__ __forceinline__ void jw_keys(const void *img, int depth, size_t HW, unsigned *bits)
 {
@@ -57,17 +68,16 @@ __device__ __forceinline__ void jw_keys(const void *img, int depth, size_t HW, u
     }
 }
 
-__global__ void k_jw_keys(const void *img, int depth, size_t HW, unsigned *bits) { jw_keys(img, depth, HW, bits); }
-__global__ void k_jw_keys_b(const JwImg *tab, int depth, size_t HW)
+template <typename S> __global__ void k_jw_keys(S src, int depth, size_t HW)
 {
-    const JwImg &r = tab[blockIdx.y];
+    const JwImg &r = jw_rec(src, blockIdx.y);
     jw_keys(sgm_global(r.img), depth, HW, sgm_global(r.bits));
 }
 
-// batch: the key bitmap (what 0) or the key -> cluster table (what 1) of every image to zero, 16 bytes per lane
-__global__ void k_jw_clear_b(const JwImg *tab, int what)
+// the key bitmap (what 0) or the key -> cluster table (what 1) of every image to zero, 16 bytes per lane
+template <typename S> __global__ void k_jw_clear(S src, int what)
 {
-    const JwImg &r = tab[blockIdx.y];
+    const JwImg &r = jw_rec(src, blockIdx.y);
     uint4 *p = what ? (uint4 *)sgm_global(r.lok) : (uint4 *)sgm_global(r.bits);
     const size_t n = (what ? (size_t)JW_KEYS : (size_t)JW_KEYS / 8) / 16;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = make_uint4(0, 0, 0, 0);
@@ -113,10 +123,9 @@ __device__ __forceinline__ void jw_compact(const unsigned *bits, unsigned *sampl
     if (threadIdx.x == blockDim.x - 1) *n_out = (int)incl;
 }
 
-__global__ void __launch_bounds__(1024) k_jw_compact(const unsigned *bits, unsigned *samples, int *n_out) { jw_compact(bits, samples, n_out); }
-__global__ void __launch_bounds__(1024) k_jw_compact_b(const JwImg *tab)
+template <typename S> __global__ void __launch_bounds__(1024) k_jw_compact(S src)
 {
-    const JwImg &r = tab[blockIdx.x];
+    const JwImg &r = jw_rec(src, blockIdx.x);
     jw_compact(sgm_global(r.bits), sgm_global(r.samples), sgm_global(r.state) + 3);
 }
 
@@ -131,11 +140,10 @@ __device__ __forceinline__ void jw_identity(const unsigned *samples, int n, floa
     labels[i] = i;
 }
 
-__global__ void k_jw_identity(const unsigned *samples, int n, float *centres, int *labels) { jw_identity(samples, n, centres, labels); }
-// batch: the images with at most n_clusters samples; such an image counts as converged from the start (the Lloyd entries skip it)
-__global__ void k_jw_identity_b(const JwImg *tab, int n_clusters)
+// the images with at most n_clusters samples; such an image counts as converged from the start (the Lloyd entries skip it)
+template <typename S> __global__ void k_jw_identity(S src, int n_clusters)
 {
-    const JwImg &r = tab[blockIdx.y];
+    const JwImg &r = jw_rec(src, blockIdx.y);
     if (r.n > n_clusters) return;
     if (blockIdx.x == 0 && threadIdx.x == 0) sgm_global(r.state)[1] = 1;
     jw_identity(sgm_global(r.samples), r.n, sgm_global(r.centres), sgm_global(r.labels));
@@ -203,17 +211,12 @@ __device__ __forceinline__ void jw_seed(const unsigned *samples, int n, int nf, 
     }
 }
 
-__global__ void __launch_bounds__(JW_SEED_THREADS) k_jw_seed(const unsigned *samples, int n, int nf, unsigned long long seed,
-                                                             float *centres, unsigned *kt, unsigned *d2t)
+// one workgroup per image with more than n_clusters samples, every image from the same seed; behind the seeding the workgroup
+// makes the image's Lloyd state ready: labels -1 (the first assignment changes every label), sums 0 (the state block is zero from
+// the start of the call)
+template <typename S> __global__ void __launch_bounds__(JW_SEED_THREADS) k_jw_seed(S src, int n_clusters, unsigned long long seed)
 {
-    jw_seed(samples, n, nf, seed, centres, kt, d2t);
-}
-// batch: one workgroup per image with more than n_clusters samples, every image from the same seed; behind the seeding the
-// workgroup puts the image's Lloyd state where the single call's three fills put it (labels -1, sums 0; the state block is
-// zero from the start of the call)
-__global__ void __launch_bounds__(JW_SEED_THREADS) k_jw_seed_b(const JwImg *tab, int n_clusters, unsigned long long seed)
-{
-    const JwImg &r = tab[blockIdx.x];
+    const JwImg &r = jw_rec(src, blockIdx.x);
     if (r.n <= n_clusters) return;
     jw_seed(sgm_global(r.samples), r.n, r.nf, seed, sgm_global(r.centres), sgm_global(r.kt), sgm_global(r.d2t));
     int *labels = sgm_global(r.labels), *sums = sgm_global(r.sums);
@@ -257,15 +260,10 @@ __device__ __forceinline__ void jw_assign(const unsigned *samples, int n, int nf
     if ((threadIdx.x & 63) == 0 && changed) atomicAdd(&st[0], changed);
 }
 
-__global__ void __launch_bounds__(256) k_jw_assign(const unsigned *samples, int n, int nf, const float *centres, int *labels,
-                                                   int *sums, int *st)
+// the image on grid axis y, x sized for the largest image (an image's workgroups beyond its samples add nothing)
+template <typename S> __global__ void __launch_bounds__(256) k_jw_assign(S src)
 {
-    jw_assign(samples, n, nf, centres, labels, sums, st);
-}
-// batch: the image on grid axis y, x sized for the largest image (an image's workgroups beyond its samples add nothing)
-__global__ void __launch_bounds__(256) k_jw_assign_b(const JwImg *tab)
-{
-    const JwImg &r = tab[blockIdx.y];
+    const JwImg &r = jw_rec(src, blockIdx.y);
     jw_assign(sgm_global(r.samples), r.n, r.nf, sgm_global(r.centres), sgm_global(r.labels), sgm_global(r.sums), sgm_global(r.state));
 }
 
@@ -291,10 +289,9 @@ __device__ __forceinline__ void jw_update(int nf, float *centres, int *sums, int
     }
 }
 
-__global__ void __launch_bounds__(256) k_jw_update(int nf, float *centres, int *sums, int *st, int it) { jw_update(nf, centres, sums, st, it); }
-__global__ void __launch_bounds__(256) k_jw_update_b(const JwImg *tab, int it)
+template <typename S> __global__ void __launch_bounds__(256) k_jw_update(S src, int it)
 {
-    const JwImg &r = tab[blockIdx.x];
+    const JwImg &r = jw_rec(src, blockIdx.x);
     jw_update(r.nf, sgm_global(r.centres), sgm_global(r.sums), sgm_global(r.state), it);
 }
 
@@ -304,10 +301,9 @@ __device__ __forceinline__ void jw_lok(const unsigned *samples, int n, const int
     if (i < n) lok[samples[i]] = (uint8_t)labels[i];
 }
 
-__global__ void k_jw_lok(const unsigned *samples, int n, const int *labels, uint8_t *lok) { jw_lok(samples, n, labels, lok); }
-__global__ void k_jw_lok_b(const JwImg *tab)
+template <typename S> __global__ void k_jw_lok(S src)
 {
-    const JwImg &r = tab[blockIdx.y];
+    const JwImg &r = jw_rec(src, blockIdx.y);
     jw_lok(sgm_global(r.samples), r.n, sgm_global(r.labels), sgm_global(r.lok));
 }
 
@@ -318,15 +314,15 @@ __device__ __forceinline__ void jw_plane(const JwSide &s, int depth, size_t HW)
         s.F[p] = s.lok[key_at(s.img, depth, p)];
 }
 
-// a map side's record of the device table, its pointers read as global ones (sgm_global, psm_kernels.h)
+// a map side's record: of the device table, its pointers read as global ones (sgm_global, psm_kernels.h); of the kernarg, as it is
 __device__ __forceinline__ JwSide jw_side(const JwSide *tab, unsigned i)
 {
     const JwSide &t = tab[i];
     return JwSide{sgm_global(t.img), sgm_global(t.lok), sgm_global(t.F), sgm_global(t.din), sgm_global(t.wq), sgm_global(t.out)};
 }
+__device__ __forceinline__ const JwSide &jw_side(const SideV &v, unsigned i) { return v.r[i]; }
 
-__global__ void k_jw_plane(JwPair pr, int depth, size_t HW) { jw_plane(pr.s[blockIdx.y], depth, HW); }
-__global__ void k_jw_plane_b(const JwSide *tab, int depth, size_t HW) { jw_plane(jw_side(tab, blockIdx.y), depth, HW); }
+template <typename S> __global__ void k_jw_plane(S src, int depth, size_t HW) { jw_plane(jw_side(src, blockIdx.y), depth, HW); }
 
 // The weighted median of both maps: one lane per output pixel of a 16 x 16 tile, the (disparity, cluster) pairs of the tile
 // and its halo staged in LDS.  Two radix passes over 16 bins each (high nibble, then the low nibble inside the chosen high
@@ -385,104 +381,64 @@ __device__ __forceinline__ void jw_median(const JwSide &s, int W, int H, int r)
     s.out[(size_t)y * W + x] = (uint8_t)(16 * h + l);
 }
 
-__global__ void __launch_bounds__(256) k_jw_median(JwPair pr, int W, int H, int r) { jw_median(pr.s[blockIdx.z], W, H, r); }
-__global__ void __launch_bounds__(256) k_jw_median_b(const JwSide *tab, int W, int H, int r) { jw_median(jw_side(tab, blockIdx.z), W, H, r); }
+template <typename S> __global__ void __launch_bounds__(256) k_jw_median(S src, int W, int H, int r) { jw_median(jw_side(src, blockIdx.z), W, H, r); }
+
+// One launch of an entry over either record source (the caller sizes the record's grid axis with q.n): the device table, or - a
+// single pair - its records by value
+template <typename R, typename... A>
+void jw_launch(hipStream_t st, void (*kv)(JwVal<R>, A...), void (*kt)(const R *, A...), dim3 grid, dim3 block, const JwRecs<R> &q, A... rest)
+{
+    if (q.dev) hipLaunchKernelGGL(kt, grid, block, 0, st, q.dev, rest...);
+    else hipLaunchKernelGGL(kv, grid, block, 0, st, JwVal<R>{{q.host[0], q.host[q.n > 1]}}, rest...);
+}
+
+// grid x of the kernels that stride over the pixels of an image (keys, planes)
+unsigned pixel_blocks(size_t HW) { return (unsigned)std::min<size_t>(std::max<size_t>((HW + 255) / 256, 1), 2048); }
 
 }  // namespace
 
-void launch_jw_keys(hipStream_t st, const void *img, int depth, size_t HW, unsigned *bits)
+void launch_jw_keys(hipStream_t st, const JwRecs<JwImg> &im, int depth, size_t HW)
 {
-    const unsigned blocks = (unsigned)((HW + 255) / 256 < 2048 ? (HW + 255) / 256 : 2048);
-    hipLaunchKernelGGL(k_jw_keys, dim3(blocks ? blocks : 1), dim3(256), 0, st, img, depth, HW, bits);
+    jw_launch(st, k_jw_clear<ImgV>, k_jw_clear<ImgT>, dim3(JW_KEYS / 8 / 16 / 256, im.n), dim3(256), im, 0);
+    jw_launch(st, k_jw_keys<ImgV>, k_jw_keys<ImgT>, dim3(pixel_blocks(HW), im.n), dim3(256), im, depth, HW);
 }
 
-void launch_jw_compact(hipStream_t st, const unsigned *bits, unsigned *samples, int *n_out)
+void launch_jw_compact(hipStream_t st, const JwRecs<JwImg> &im)
 {
-    hipLaunchKernelGGL(k_jw_compact, dim3(1), dim3(1024), 0, st, bits, samples, n_out);
+    jw_launch(st, k_jw_compact<ImgV>, k_jw_compact<ImgT>, dim3(im.n), dim3(1024), im);
 }
 
-void launch_jw_identity(hipStream_t st, const unsigned *samples, int n, float *centres, int *labels)
+void launch_jw_identity(hipStream_t st, const JwRecs<JwImg> &im, int n_clusters)
 {
-    hipLaunchKernelGGL(k_jw_identity, dim3((n + 255) / 256), dim3(256), 0, st, samples, n, centres, labels);
+    jw_launch(st, k_jw_identity<ImgV>, k_jw_identity<ImgT>, dim3((n_clusters + 255) / 256, im.n), dim3(256), im, n_clusters);
 }
 
-void launch_jw_seed(hipStream_t st, const unsigned *samples, int n, int nf, unsigned long long seed, float *centres,
-                    unsigned *kt, unsigned *d2t)
+void launch_jw_seed(hipStream_t st, const JwRecs<JwImg> &im, int n_clusters, unsigned long long seed)
 {
-    hipLaunchKernelGGL(k_jw_seed, dim3(1), dim3(JW_SEED_THREADS), 0, st, samples, n, nf, seed, centres, kt, d2t);
+    jw_launch(st, k_jw_seed<ImgV>, k_jw_seed<ImgT>, dim3(im.n), dim3(JW_SEED_THREADS), im, n_clusters, seed);
 }
 
-void launch_jw_lloyd(hipStream_t st, const unsigned *samples, int n, int nf, float *centres, int *labels, int *sums, int *state, int it)
+void launch_jw_lloyd(hipStream_t st, const JwRecs<JwImg> &im, int n_max, int it)
 {
-    int blocks = (n + 255) / 256;
-    blocks = blocks > 512 ? 512 : blocks;
-    hipLaunchKernelGGL(k_jw_assign, dim3(blocks), dim3(256), 0, st, samples, n, nf, (const float *)centres, labels, sums, state);
-    hipLaunchKernelGGL(k_jw_update, dim3(1), dim3(256), 0, st, nf, centres, sums, state, it);
+    jw_launch(st, k_jw_assign<ImgV>, k_jw_assign<ImgT>, dim3(std::min((n_max + 255) / 256, 512), im.n), dim3(256), im);
+    jw_launch(st, k_jw_update<ImgV>, k_jw_update<ImgT>, dim3(im.n), dim3(256), im, it);
 }
 
-void launch_jw_lok(hipStream_t st, const unsigned *samples, int n, const int *labels, uint8_t *lok)
+void launch_jw_lok(hipStream_t st, const JwRecs<JwImg> &im, int n_max)
 {
-    hipLaunchKernelGGL(k_jw_lok, dim3((n + 255) / 256), dim3(256), 0, st, samples, n, labels, lok);
+    jw_launch(st, k_jw_clear<ImgV>, k_jw_clear<ImgT>, dim3(64, im.n), dim3(256), im, 1);
+    jw_launch(st, k_jw_lok<ImgV>, k_jw_lok<ImgT>, dim3((n_max + 255) / 256, im.n), dim3(256), im);
 }
 
-void launch_jw_plane(hipStream_t st, const JwPair &pr, int depth, size_t HW)
+void launch_jw_plane(hipStream_t st, const JwRecs<JwSide> &sides, int depth, size_t HW)
 {
-    const unsigned blocks = (unsigned)((HW + 255) / 256 < 2048 ? (HW + 255) / 256 : 2048);
-    hipLaunchKernelGGL(k_jw_plane, dim3(blocks ? blocks : 1, 2), dim3(256), 0, st, pr, depth, HW);
+    jw_launch(st, k_jw_plane<SideV>, k_jw_plane<SideT>, dim3(pixel_blocks(HW), sides.n), dim3(256), sides, depth, HW);
 }
 
-void launch_jw_median(hipStream_t st, const JwPair &pr, int W, int H, int r)
+void launch_jw_median(hipStream_t st, const JwRecs<JwSide> &sides, int W, int H, int r)
 {
-    hipLaunchKernelGGL(k_jw_median, dim3((W + JW_TILE - 1) / JW_TILE, (H + JW_TILE - 1) / JW_TILE, 2), dim3(256), 0, st, pr, W, H, r);
-}
-
-// ---- several pairs per launch: m images to cluster (img), n_sides map sides (sides) ----
-
-void launch_jw_keys_b(hipStream_t st, const JwImg *img, int m, int depth, size_t HW)
-{
-    const unsigned blocks = (unsigned)((HW + 255) / 256 < 2048 ? (HW + 255) / 256 : 2048);
-    hipLaunchKernelGGL(k_jw_clear_b, dim3(JW_KEYS / 8 / 16 / 256, m), dim3(256), 0, st, img, 0);
-    hipLaunchKernelGGL(k_jw_keys_b, dim3(blocks ? blocks : 1, m), dim3(256), 0, st, img, depth, HW);
-}
-
-void launch_jw_compact_b(hipStream_t st, const JwImg *img, int m)
-{
-    hipLaunchKernelGGL(k_jw_compact_b, dim3(m), dim3(1024), 0, st, img);
-}
-
-void launch_jw_identity_b(hipStream_t st, const JwImg *img, int m, int n_clusters)
-{
-    hipLaunchKernelGGL(k_jw_identity_b, dim3((n_clusters + 255) / 256, m), dim3(256), 0, st, img, n_clusters);
-}
-
-void launch_jw_seed_b(hipStream_t st, const JwImg *img, int m, int n_clusters, unsigned long long seed)
-{
-    hipLaunchKernelGGL(k_jw_seed_b, dim3(m), dim3(JW_SEED_THREADS), 0, st, img, n_clusters, seed);
-}
-
-void launch_jw_lloyd_b(hipStream_t st, const JwImg *img, int m, int n_max, int it)
-{
-    int blocks = (n_max + 255) / 256;
-    blocks = blocks > 512 ? 512 : blocks;
-    hipLaunchKernelGGL(k_jw_assign_b, dim3(blocks, m), dim3(256), 0, st, img);
-    hipLaunchKernelGGL(k_jw_update_b, dim3(m), dim3(256), 0, st, img, it);
-}
-
-void launch_jw_lok_b(hipStream_t st, const JwImg *img, int m, int n_max)
-{
-    hipLaunchKernelGGL(k_jw_clear_b, dim3(64, m), dim3(256), 0, st, img, 1);
-    hipLaunchKernelGGL(k_jw_lok_b, dim3((n_max + 255) / 256, m), dim3(256), 0, st, img);
-}
-
-void launch_jw_plane_b(hipStream_t st, const JwSide *sides, int n_sides, int depth, size_t HW)
-{
-    const unsigned blocks = (unsigned)((HW + 255) / 256 < 2048 ? (HW + 255) / 256 : 2048);
-    hipLaunchKernelGGL(k_jw_plane_b, dim3(blocks ? blocks : 1, n_sides), dim3(256), 0, st, sides, depth, HW);
-}
-
-void launch_jw_median_b(hipStream_t st, const JwSide *sides, int n_sides, int W, int H, int r)
-{
-    hipLaunchKernelGGL(k_jw_median_b, dim3((W + JW_TILE - 1) / JW_TILE, (H + JW_TILE - 1) / JW_TILE, n_sides), dim3(256), 0, st, sides, W, H, r);
+    jw_launch(st, k_jw_median<SideV>, k_jw_median<SideT>, dim3((W + JW_TILE - 1) / JW_TILE, (H + JW_TILE - 1) / JW_TILE, sides.n), dim3(256), sides, W, H, r);
 }
 
 }  // namespace psm
+

@@ -192,38 +192,30 @@ struct JwSide {
     const unsigned long long *wq;      // rint(w * 2^48) [JW_NF_MAX][JW_NF_MAX]
     uint8_t *out;                      // filtered map [H][W]
 };
-struct JwPair { JwSide s[2]; };
-void launch_jw_keys(hipStream_t s, const void *img, int depth, size_t HW, unsigned *bits);
-void launch_jw_compact(hipStream_t s, const unsigned *bits, unsigned *samples, int *n_out);
-void launch_jw_identity(hipStream_t s, const unsigned *samples, int n, float *centres, int *labels);
-void launch_jw_seed(hipStream_t s, const unsigned *samples, int n, int nf, unsigned long long seed, float *centres,
-                    unsigned *kt, unsigned *d2t);
-// one Lloyd iteration (assignment + update); state {changed, converged, iterations}
-void launch_jw_lloyd(hipStream_t s, const unsigned *samples, int n, int nf, float *centres, int *labels, int *sums, int *state, int it);
-void launch_jw_lok(hipStream_t s, const unsigned *samples, int n, const int *labels, uint8_t *lok);
-void launch_jw_plane(hipStream_t s, const JwPair &pr, int depth, size_t HW);
-void launch_jw_median(hipStream_t s, const JwPair &pr, int W, int H, int r);
-// Several pairs of one geometry per launch (psm_joint_wmf_batch): the device table holds one JwImg per image to cluster and one
-// JwSide per map side; the batched entries k_jw_*_b index it with a grid axis and read the pointers as global ones (sgm_global
-// below).  Buffers are the contexts' own (JwScratch), but for state and centres: those lie side by side in a block of the batch,
-// so the host reads all of them in one copy.
+// One image to cluster.  Buffers are the context's own (JwScratch), but for state and centres: those lie side by side in a block of
+// the call's first context (JwBatch), so the host reads all of them in one copy.
 struct JwImg {
     const void *img;
     unsigned *bits, *samples, *kt, *d2t;
     int *labels, *sums;
-    int *state;                        // {changed, converged, iterations, sample count} in the batch's block
-    float *centres;                    // [JW_NF_MAX][3] in the batch's block
+    int *state;                        // {changed, converged, iterations, sample count}
+    float *centres;                    // [JW_NF_MAX][3]
     uint8_t *lok;
-    int n, nf;                         // sample count and clusters: known (and uploaded) once the samples have been counted
+    int n, nf;                         // sample count and clusters: known once the samples have been counted
 };
-void launch_jw_keys_b(hipStream_t s, const JwImg *img, int m, int depth, size_t HW);     // clears the bitmaps first
-void launch_jw_compact_b(hipStream_t s, const JwImg *img, int m);
-void launch_jw_identity_b(hipStream_t s, const JwImg *img, int m, int n_clusters);      // the images with n <= n_clusters
-void launch_jw_seed_b(hipStream_t s, const JwImg *img, int m, int n_clusters, unsigned long long seed);   // ... the others
-void launch_jw_lloyd_b(hipStream_t s, const JwImg *img, int m, int n_max, int it);
-void launch_jw_lok_b(hipStream_t s, const JwImg *img, int m, int n_max);                 // clears the tables first
-void launch_jw_plane_b(hipStream_t s, const JwSide *sides, int n_sides, int depth, size_t HW);
-void launch_jw_median_b(hipStream_t s, const JwSide *sides, int n_sides, int W, int H, int r);
+// The records (R: JwImg, JwSide) of one launch as the host filled them, the record on a grid axis.  dev == nullptr: the n <= 2 records
+// of a single pair travel by value in the kernarg (JwVal); else the kernels read the n records of the device table at dev and the
+// pointers in them as global ones (sgm_global below).  Either way the index is uniform per workgroup: scalar loads ahead of one body.
+template <typename R> struct JwRecs { const R *host, *dev; int n; };
+template <typename R> struct JwVal { R r[2]; };
+void launch_jw_keys(hipStream_t s, const JwRecs<JwImg> &im, int depth, size_t HW);           // clears the bitmaps first
+void launch_jw_compact(hipStream_t s, const JwRecs<JwImg> &im);
+void launch_jw_identity(hipStream_t s, const JwRecs<JwImg> &im, int n_clusters);             // the images with n <= n_clusters
+void launch_jw_seed(hipStream_t s, const JwRecs<JwImg> &im, int n_clusters, unsigned long long seed);   // ... the others; leaves the Lloyd state ready
+void launch_jw_lloyd(hipStream_t s, const JwRecs<JwImg> &im, int n_max, int it);             // one Lloyd iteration (assignment + update) of every image
+void launch_jw_lok(hipStream_t s, const JwRecs<JwImg> &im, int n_max);                       // clears the tables first
+void launch_jw_plane(hipStream_t s, const JwRecs<JwSide> &sides, int depth, size_t HW);
+void launch_jw_median(hipStream_t s, const JwRecs<JwSide> &sides, int W, int H, int r);
 
 // psm_rectify.hip: remap (CV_16SC2 maps, INTER_LINEAR, constant border 0) + crop of both eyes (psm_api_rectify.cpp)
 struct RectSide {

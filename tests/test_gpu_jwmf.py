@@ -256,3 +256,69 @@ def test_merged_root(psm, oracle):
     finally:
         for s in shards:
             s.close()
+
+
+def _chain_img(W, H, k):
+    """Image k of the generator tests/test_gpu_jwmf_batch.py uses (its model chains at 33 x 17, 4 clusters: k = 7: 11 Lloyd
+    iterations, k = 22: 51)."""
+    return np.random.default_rng(1000 + k).integers(0, 256, (H, W, 3), dtype=np.uint8)
+
+
+def test_single_call_bracket_count(psm):
+    """PSM_K_JWMF brackets of a single call that clusters, the batch's formula: keys, seeding, one per group of 16 Lloyd
+    iterations until every image has converged, clusters, median - both images of the call in the same launches."""
+    from primestereomatch_amd import capi
+    W, H, nc, radius = 33, 17, 4, 4
+    short, long_ = _chain_img(W, H, 7), _chain_img(W, H, 22)
+    rng = np.random.default_rng(5)
+    pal = rng.integers(0, 256, (3, 3), dtype=np.uint8)
+    ident = pal[rng.integers(0, 3, (H, W))], pal[rng.integers(0, 3, (H, W))]
+    lm, rm = rng.integers(0, 256, (2, H, W), dtype=np.uint8)
+    host = (rng.random((7, 3)) * 63).astype(np.float32), rng.integers(0, 7, 64 ** 3).astype(np.uint8)
+
+    def run(l, r, clusters=()):
+        with psm.DispEst(l, r, 8) as de:
+            de.upload_maps(lm, rm)
+            for s, cl in enumerate(clusters):
+                if cl is not None:
+                    de.set_jwmf_clusters(s, *cl)
+            de.set_option(capi.PSM_OPT_PROFILE, 1)
+            de.reset_kernel_times()
+            de.JointWMF_GPU(radius, 0.0, nc, 0)
+            return de.kernel_time_ms(capi.PSM_K_JWMF)[1], [de.jwmf_clusters(s)[2] for s in (0, 1)]
+
+    its = [M.clustering_of(im, nc)["iterations"] for im in (short, long_)]
+    assert 0 < its[0] <= 16 and its[1] > 32, its
+    for l, r in ((short, long_), (long_, short)):
+        n, got = run(l, r)
+        assert sorted(got) == its
+        print("two k-means images:", n, got)
+        assert n == 2 + -(-max(its) // 16) + 2
+    n, got = run(*ident)
+    print("two identity images:", n, got)
+    assert got == [0, 0] and n == 2 + 0 + 2
+    n, got = run(short, long_, (None, host))
+    print("host clusters on the long side:", n, got)
+    assert got == [its[0], 0] and n == 2 + 1 + 2
+
+
+def test_reclustering_after_a_parameter_change(psm):
+    """Another n_clusters on a clustered pair clusters both sides again, and the first parameters after that once more: a
+    kept clustering is one made with the call's own parameters."""
+    from primestereomatch_amd import capi
+    W, H, radius = 33, 17, 4
+    l, r, lm, rm = _random_pair(W, H, 31, "u8")
+    with psm.DispEst(l, r, 8) as de:
+        de.set_option(capi.PSM_OPT_PROFILE, 1)
+        seen = []
+        for nc in (16, 5, 16):
+            de.upload_maps(lm, rm)
+            de.reset_kernel_times()
+            de.JointWMF_GPU(radius, 0.0, nc, 0)
+            assert de.kernel_time_ms(capi.PSM_K_JWMF)[1] > 1          # (1: planes + median alone, a clustering kept)
+            for s, img, dmap, out in ((0, l, lm, de.lDisMap), (1, r, rm, de.rDisMap)):
+                m = _check_clusters(de.jwmf_clusters(s), img, nc)
+                assert m["iterations"] > 0 and len(m["centres"]) == nc
+                assert np.array_equal(out, M.median(dmap, m["F"], M.quantise(M.weight_table(m["centres"])), radius))
+            seen.append(de.jwmf_clusters(0)[0].copy())
+        assert np.array_equal(seen[0], seen[2]) and seen[0].shape != seen[1].shape

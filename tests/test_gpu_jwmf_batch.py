@@ -122,6 +122,32 @@ def test_several_groups_apart(psm):
     _batch_equals_model_and_singles(psm, W, H, [0, 1], [2, 3], nc, 9)
 
 
+@pytest.mark.parametrize("depth", ["u8", "f32"])
+@pytest.mark.parametrize("order", ["short-left", "short-right"])
+@pytest.mark.parametrize("W,H,nc,k_short,k_long", [(33, 17, 4, 7, 22), (70, 45, 8, 20, 9)])
+def test_unequal_chains_in_one_single_call(psm, W, H, nc, k_short, k_long, order, depth):
+    """One image of a single call converges inside the first group of iterations, the other needs more than two groups;
+    max_iter 1, 16 and 17 cut one or both chains at and next to the group's end (a cut image reports max_iter)."""
+    full = [_model(W, H, k, nc)["iterations"] for k in (k_short, k_long)]
+    print("iterations", full)
+    assert 0 < full[0] <= JW_GROUP and full[1] > 2 * JW_GROUP, full
+    ks = (k_short, k_long) if order == "short-left" else (k_long, k_short)
+    pair = tuple(_img(W, H, k) for k in ks)
+    if depth == "f32":
+        pair = tuple(_as_f32(im) for im in pair)
+    maps, radius = _maps(W, H, 50), 4
+    for max_iter in (0, 1, 16, 17):
+        (de,) = _objects(psm, [pair], [maps])
+        try:
+            de.JointWMF_GPU(radius, 0.0, nc, max_iter)
+            for s, k in enumerate(ks):
+                m = _model(W, H, k, nc, max_iter or 10000)
+                assert m["iterations"] == min(_model(W, H, k, nc)["iterations"], max_iter or 10000)
+                _check_side(de, s, m, maps[s], radius, (de.lDisMap, de.rDisMap)[s])
+        finally:
+            _close([de])
+
+
 def test_max_iter_cuts_some_images(psm):
     W, H, nc, cap = 33, 17, 4, 18
     its = [_model(W, H, k, nc)["iterations"] for k in range(8)]
