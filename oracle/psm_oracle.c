@@ -925,7 +925,10 @@ int psmo_pipeline_fgf(const uint8_t *l_bgr, const uint8_t *r_bgr, int H, int W, 
                       uint8_t *ldisp, uint8_t *rdisp, float *lvol, float *rvol, psmo_times *times)
 {
     if (!l_bgr || !r_bgr || H < 8 || W < 8 || D < 1 || D > 256 || threads < 1 || (s != 2 && s != 4 && s != 8)) return -1;
-    if (H / s < 2 * (8 / s) + 1 || W / s < 2 * (8 / s) + 1) return -1;
+    /* the library's bound (psm_cost_filter_fgf): a subsampled axis longer than the blur radius 8/s.  blur_k reflects through r101,
+       which folds once: taps reach from -r to n-1+r, -k <= r <= n-1 and 2(n-1)-k >= n-1-r >= 0 for n >= r+1, so one
+       BORDER_REFLECT_101 fold is exact down to that size (a window then reflects at both ends of the axis) */
+    if (H / s <= 8 / s || W / s <= 8 / s) return -1;
     const size_t N = (size_t)H * W, n = (size_t)(H / s) * (W / s);
     int rc = -1;
     float *lImg = (float *)malloc(N * 3 * sizeof(float)), *rImg = (float *)malloc(N * 3 * sizeof(float));

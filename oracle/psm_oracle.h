@@ -145,7 +145,8 @@ int psmo_pipeline_f32_maps(const uint8_t *l_bgr, const uint8_t *r_bgr, int H, in
                            uint8_t *ldisp, uint8_t *rdisp);
 
 /* CostConst() -> CostFilter_FGF() -> DispSelect_CPU(): the snapshot's live CPU branch
- * (src/StereoMatch.cpp:207-224), s = subsample_rate in {2,4,8}. */
+ * (src/StereoMatch.cpp:207-224), s = subsample_rate in {2,4,8}.  Accepts what psm_cost_filter_fgf accepts: H/s and W/s
+ * above the blur radius 8/s (one REFLECT_101 fold is exact down to there); -1 below. */
 int psmo_pipeline_fgf(const uint8_t *l_bgr, const uint8_t *r_bgr, int H, int W, int D, int threads, int s,
                       uint8_t *ldisp, uint8_t *rdisp, float *lvol, float *rvol, psmo_times *times);
 

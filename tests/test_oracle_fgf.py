@@ -71,11 +71,23 @@ def np_fgf(img, p, s):
     return sum(np_upsample(ma[c], H, W) * img[:, :, c] for c in range(3)) + np_upsample(mb, H, W)
 
 
+def small_shape(axes, j, s):
+    """(H, W) with the subsampled size of the named axes in [R + 1, 2 R], R = 8 / s the blur radius: there a window reflects at
+    both ends of the axis and one REFLECT_101 fold is still exact (below R + 1 it is not, and library and oracle refuse).  j picks
+    the size within the range (s = 8 has the one size 2) and the remainder: j = 0 is a multiple of s, the others are not.  The
+    other axis keeps 45 (subsampled 22, 11, 5).  No rate admits an 8: 8 / s is never above the radius."""
+    R = 8 // s
+    W = (R + 1 + j % R) * s + j % s if "W" in axes else 45
+    H = (R + 1 + (R - 1 - j) % R) * s + (j + 1) % s if "H" in axes else 45
+    assert all(R + 1 <= n // s <= 2 * R for n, a in ((W, "W"), (H, "H")) if a in axes)
+    return H, W
+
+
 @pytest.mark.parametrize("s", [2, 4, 8])
-@pytest.mark.parametrize("shape", [(48, 64), (45, 70)])
+@pytest.mark.parametrize("shape", [(48, 64), (45, 70)] + [(axes, j) for axes in ("W", "H", "WH") for j in range(4)])
 def test_fgf_vs_numpy(oracle, s, shape):
     rng = np.random.default_rng(11 + s)
-    H, W = shape
+    H, W = small_shape(*shape, s) if isinstance(shape[0], str) else shape
     img = rng.random((H, W, 3), dtype=np.float32)
     p = (rng.random((H, W), dtype=np.float32) * 2.0).astype(np.float32)
     setup = oracle.fgf_setup(img, s)
@@ -91,6 +103,26 @@ def test_fgf_vs_numpy(oracle, s, shape):
     # a constant cost slice is a fixed point (a = 0, b = p)
     qc = oracle.fgf_filter(img, setup, np.full((H, W), 0.25, np.float32), s)
     assert np.allclose(qc, 0.25, atol=2e-5)
+
+
+@pytest.mark.parametrize("s", [2, 4, 8])
+def test_pipeline_fgf_accepts_what_the_library_accepts(oracle, s):
+    """psm_cost_filter_fgf wants W / s and H / s above the radius 8 / s; psmo_pipeline_fgf refuses exactly what it refuses, and
+    what it takes is fgf_setup + fgf_filter of the costs it built (the volumes are the per-slice filter's bits)."""
+    from primestereomatch_amd import synth
+    R = 8 // s
+    big, least, under = 5 * s, (R + 1) * s, max((R + 1) * s - 1, 8)       # subsampled sizes 5, R + 1, R
+    for W, H, ok in ((least, big, True), (big, least, True), (least, least, True), (under, big, False), (big, under, False)):
+        l, r, _ = synth.make_pair(W, H, 3, seed=W + H)
+        if not ok:
+            with pytest.raises(ValueError):
+                oracle.pipeline_fgf(l, r, 3, s=s, threads=2)
+            continue
+        res = oracle.pipeline_fgf(l, r, 3, s=s, threads=2, want_volumes=True)
+        lf, rf = oracle.u8_to_f32(l), oracle.u8_to_f32(r)
+        raw = oracle.cvc_build(lf, rf, oracle.cvc_preprocess(lf), oracle.cvc_preprocess(rf), 2)
+        assert np.array_equal(res["lvol"][2], oracle.fgf_filter(lf, oracle.fgf_setup(lf, s), raw, s)), (W, H)
+        assert np.array_equal(res["ldisp"], oracle.wta(res["lvol"]))
 
 
 def test_fgf_constant_guidance_is_blur_then_upsample(oracle):
