@@ -11,16 +11,122 @@
 
 using namespace psm;
 
+// What the batch entry points share - psm_compute_batch, psm_sgm_compute_batch, psm_sgm_select_maps_batch,
+// psm_joint_wmf_batch, psm_score_batch.  c0 is the batch's first context: it owns the table, the shared launches run on its
+// stream, and it receives every message.
+namespace psm {
+
+int batch_member(psm_ctx *c0, const char *who, psm_ctx *const *ctxs, int i)
+{
+    if (!ctxs[i]) return fail(c0, "%s: context %d is NULL", who, i);
+    for (int j = 0; j < i; ++j)
+        if (ctxs[j] == ctxs[i]) return fail(c0, "%s: context %d appears twice", who, i);
+    return 0;
+}
+
+int member_failed(psm_ctx *c0, const char *who, int i, const psm_ctx *c)
+{
+    return c == c0 ? 1 : fail(c0, "%s: context %d: %s", who, i, c->err.c_str());
+}
+
+// The device table of the members' records is uploaded again only when a record changed (*fresh: `recs` differ from the host
+// copy; the comparison is bytewise, so a record's padding can report a change that is none - one upload too many, never one too
+// few).  table_reserve makes room for a fresh table and is the part to call before anything is ordered or launched: growing
+// synchronises c0's stream, whose kernels may still read the old table.
+int table_reserve(psm_ctx *c0, DevTable &t, const void *recs, size_t bytes, bool *fresh)
+{
+    *fresh = t.host.size() != bytes || memcmp(t.host.data(), recs, bytes) != 0;
+    if (*fresh && t.cap < bytes) {
+        PSM_HIP(c0, hipStreamSynchronize(c0->stream));
+        (void)hipFree(t.dev);
+        if (t.pin) (void)hipHostFree(t.pin);
+        t.dev = t.pin = nullptr;
+        t.cap = 0;
+        t.host.clear();                      // (should an allocation below fail, the next call must not take the old table for current)
+        PSM_HIP(c0, hipMalloc((void **)&t.dev, bytes));
+        PSM_HIP(c0, hipHostMalloc((void **)&t.pin, 2 * bytes, hipHostMallocDefault));
+        t.cap = bytes;
+    }
+    for (hipEvent_t &e : t.ev)
+        if (!e) PSM_HIP(c0, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return 0;
+}
+
+// The copy of a fresh table, on c0's stream: stream-ordered behind the previous call's kernels, which still read the old table (it
+// changes with every frame of a loop whose image slots alternate), and out of one of two page-locked slots (a pageable source
+// would make the "asynchronous" copy wait for the stream to drain) - a slot is rewritten only after the copy that read it has
+// executed.  The host copy is adopted last: a table that did not get under way is not taken for current by the next call.
+int table_upload(psm_ctx *c0, DevTable &t, const void *recs, size_t bytes)
+{
+    const int slot = t.slot ^= 1;
+    PSM_HIP(c0, hipEventSynchronize(t.ev[slot]));
+    uint8_t *pin = t.pin + (size_t)slot * t.cap;
+    memcpy(pin, recs, bytes);
+    t.host.clear();                          // (from here to the end the device copy is neither the old table for certain nor the new one)
+    PSM_HIP(c0, hipMemcpyAsync(t.dev, pin, bytes, hipMemcpyHostToDevice, c0->stream));
+    PSM_HIP(c0, hipEventRecord(t.ev[slot], c0->stream));
+    t.host.assign((const uint8_t *)recs, (const uint8_t *)recs + bytes);
+    return 0;
+}
+
+void table_free(DevTable &t)
+{
+    (void)hipFree(t.dev);
+    if (t.pin) (void)hipHostFree(t.pin);
+    for (hipEvent_t &e : t.ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    t.dev = t.pin = nullptr;
+    t.cap = 0;
+    t.host.clear();
+}
+
+// The stream ordering around the shared launches.  batch_events: the events of the two below, before any launch; batch_join:
+// every member's earlier work on a stream of its own is ordered before what follows on c0's; batch_fork: what was enqueued on c0's
+// stream is ordered before every such member's later work.  Members on c0's stream (shared streams, a batch of one) need neither.
+int batch_events(psm_ctx *c0, psm_ctx *const *ctxs, int n)
+{
+    for (int i = 0; i < n; ++i) {
+        psm_ctx *c = ctxs[i];
+        if (c->stream == c0->stream) continue;
+        if (!c->ev_batch) PSM_HIP(c0, hipEventCreateWithFlags(&c->ev_batch, hipEventDisableTiming));
+        if (!c0->ev_batch) PSM_HIP(c0, hipEventCreateWithFlags(&c0->ev_batch, hipEventDisableTiming));
+    }
+    return 0;
+}
+
+int batch_join(psm_ctx *c0, psm_ctx *const *ctxs, int n)
+{
+    for (int i = 0; i < n; ++i) {
+        psm_ctx *c = ctxs[i];
+        if (c->stream == c0->stream) continue;
+        PSM_HIP(c0, hipEventRecord(c->ev_batch, c->stream));
+        PSM_HIP(c0, hipStreamWaitEvent(c0->stream, c->ev_batch, 0));
+    }
+    return 0;
+}
+
+int batch_fork(psm_ctx *c0, psm_ctx *const *ctxs, int n)
+{
+    bool recorded = false;
+    for (int i = 0; i < n; ++i) {
+        psm_ctx *c = ctxs[i];
+        if (c->stream == c0->stream) continue;
+        if (!recorded) PSM_HIP(c0, hipEventRecord(c0->ev_batch, c0->stream));
+        recorded = true;
+        PSM_HIP(c0, hipStreamWaitEvent(c->stream, c0->ev_batch, 0));
+    }
+    return 0;
+}
+
+}  // namespace psm
+
 extern "C" int psm_compute_batch(psm_ctx *const *ctxs, int n)
 {
     if (!ctxs || n < 1 || !ctxs[0]) return fail(nullptr, "psm_compute_batch: bad arguments");
     psm_ctx *c0 = ctxs[0];
     if (n > 4096) return fail(c0, "psm_compute_batch: %d pairs (at most 4096 per call)", n);
     for (int i = 0; i < n; ++i) {
+        if (batch_member(c0, "psm_compute_batch", ctxs, i)) return 1;
         psm_ctx *c = ctxs[i];
-        if (!c) return fail(c0, "psm_compute_batch: context %d is NULL", i);
-        for (int j = 0; j < i; ++j)
-            if (ctxs[j] == c) return fail(c0, "psm_compute_batch: context %d appears twice", i);
         if (c->W != c0->W || c->H != c0->H || c->D != c0->D || c->d0 != c0->d0 || c->d1 != c0->d1 || c->dtype != c0->dtype || c->device != c0->device)
             return fail(c0, "psm_compute_batch: context %d has another geometry / type / device than context 0", i);
         if (c->opt_variant != 0 || (c->march.flags & (PSM_FLAG_STORE_FILTERED | PSM_FLAG_MATERIALISE_COSTS)))
@@ -49,12 +155,12 @@ extern "C" int psm_compute_batch(psm_ctx *const *ctxs, int n)
     }                                                           //  as psm_cost_construct does before it forgets an uploaded volume's range)
     const int W = c0->W, H = c0->H, Dloc = c0->Dloc;
     hipStream_t s = c0->stream;
-    if (!c0->ev_batch) PSM_HIP(c0, hipEventCreateWithFlags(&c0->ev_batch, hipEventDisableTiming));
 
-    // ---- plan and scratch (before any launch: growing a scratch buffer synchronises its context's stream) ----
+    // ---- plan, scratch and events (before any launch: growing a scratch buffer synchronises its context's stream) ----
     const SelPlan sp = select_plan(c0, n, true);
     for (int i = 0; i < n; ++i)
         if (ensure_gf_scratch(ctxs[i], sp.scratch_bytes)) return fail(c0, "psm_compute_batch: %s", ctxs[i]->err.c_str());
+    if (batch_events(c0, ctxs, n)) return 1;
 
     // ---- every context's earlier work (uploads, downloads of its maps) is ordered before the shared launches ----
     for (int i = 0; i < n; ++i) {
@@ -64,42 +170,16 @@ extern "C" int psm_compute_batch(psm_ctx *const *ctxs, int n)
         const int bad = adopt_staged_pair(c) || maps_writable(c);
         c->stream = own;
         if (bad) return fail(c0, "psm_compute_batch: %s", c->err.c_str());
-        if (own != s) {
-            if (!c->ev_batch) PSM_HIP(c0, hipEventCreateWithFlags(&c->ev_batch, hipEventDisableTiming));
-            PSM_HIP(c0, hipEventRecord(c->ev_batch, own));
-            PSM_HIP(c0, hipStreamWaitEvent(s, c->ev_batch, 0));
-        }
     }
+    if (batch_join(c0, ctxs, n)) return 1;
 
-    // ---- the table of the pairs' pointers (device copy refreshed only when an entry changed) ----
+    // ---- the table of the pairs' pointers: built here, since adopt_staged_pair swapped the image slots ----
     std::vector<PcPair> tab((size_t)n);
     for (int i = 0; i < n; ++i) tab[i] = pc_pair(ctxs[i]);
-    if (c0->batch_host.size() != tab.size() || memcmp(c0->batch_host.data(), tab.data(), tab.size() * sizeof(PcPair)) != 0) {
-        if (c0->batch_cap < tab.size()) {
-            PSM_HIP(c0, hipStreamSynchronize(s));
-            (void)hipFree(c0->batch_tab);
-            if (c0->batch_pin) (void)hipHostFree(c0->batch_pin);
-            c0->batch_tab = nullptr;
-            c0->batch_pin = nullptr;
-            c0->batch_cap = 0;
-            c0->batch_host.clear();          // (should an allocation below fail, the next call must not take the old table for current)
-            PSM_HIP(c0, hipMalloc((void **)&c0->batch_tab, tab.size() * sizeof(PcPair)));
-            PSM_HIP(c0, hipHostMalloc((void **)&c0->batch_pin, 2 * tab.size() * sizeof(PcPair), hipHostMallocDefault));
-            c0->batch_cap = tab.size();
-        }
-        // (the table changes with every frame of a frame loop - the image slots alternate; the copy is stream-ordered behind the
-        // previous frame's kernels, which still read the old table, and reads one of two page-locked slots: a slot is rewritten
-        // only after the copy that read it has executed)
-        const int slot = c0->batch_slot ^= 1;
-        if (!c0->ev_tab[slot]) PSM_HIP(c0, hipEventCreateWithFlags(&c0->ev_tab[slot], hipEventDisableTiming));
-        else PSM_HIP(c0, hipEventSynchronize(c0->ev_tab[slot]));
-        PcPair *pin = c0->batch_pin + (size_t)slot * c0->batch_cap;
-        memcpy(pin, tab.data(), tab.size() * sizeof(PcPair));
-        c0->batch_host = tab;
-        PSM_HIP(c0, hipMemcpyAsync(c0->batch_tab, pin, tab.size() * sizeof(PcPair), hipMemcpyHostToDevice, s));
-        PSM_HIP(c0, hipEventRecord(c0->ev_tab[slot], s));
-    }
-    const PcPair *dt = c0->batch_tab;
+    bool fresh = false;
+    if (table_reserve(c0, c0->batch_tab, tab.data(), tab.size() * sizeof(PcPair), &fresh)) return 1;
+    if (fresh && table_upload(c0, c0->batch_tab, tab.data(), tab.size() * sizeof(PcPair))) return 1;
+    const PcPair *dt = (const PcPair *)c0->batch_tab.dev;
     const PcPairs P = {dt, n, {}};
 
     const int depth = c0->raw_depth;
@@ -156,7 +236,7 @@ extern "C" int psm_compute_batch(psm_ctx *const *ctxs, int n)
     const double t2 = now_us();
 
     // ---- every context is now where psm_cost_construct + psm_cost_filter + psm_disp_select(ctx, NULL, NULL, 0) leave it ----
-    PSM_HIP(c0, hipEventRecord(c0->ev_batch, s));
+    if (batch_fork(c0, ctxs, n)) return 1;
     for (int i = 0; i < n; ++i) {
         psm_ctx *c = ctxs[i];
         c->g1_rows = c->guid_rows = whole_image(c);
@@ -168,7 +248,6 @@ extern "C" int psm_compute_batch(psm_ctx *const *ctxs, int n)
         filtered(c->res, whole_image(c), nullptr);             // (the batch wrote the maps itself: no early map to take)
         if (whole) maps_written(c->res);
         else { keys_complete(c->res, 0); keys_complete(c->res, 1); }   // (a disparity shard: its minima are what psm_disp_merge_ctx takes)
-        if (c->stream != s) PSM_HIP(c0, hipStreamWaitEvent(c->stream, c0->ev_batch, 0));
     }
     if (!c0->opt_async) PSM_HIP(c0, hipStreamSynchronize(s));
     const double t3 = now_us();

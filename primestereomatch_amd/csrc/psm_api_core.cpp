@@ -138,10 +138,8 @@ void free_all(psm_ctx *c)
     if (c->batch_graph) (void)hipGraphExecDestroy(c->batch_graph);
     (void)hipFree(c->range_dev);
     if (c->range_pin) (void)hipHostFree(c->range_pin);
-    (void)hipFree(c->batch_tab);
-    if (c->batch_pin) (void)hipHostFree(c->batch_pin);
-    for (hipEvent_t e : {c->ev_batch, c->ev_tab[0], c->ev_tab[1]})
-        if (e) (void)hipEventDestroy(e);
+    table_free(c->batch_tab);
+    if (c->ev_batch) (void)hipEventDestroy(c->ev_batch);
     for (auto &t : c->timers)
         for (auto &p : t.pending) {
             (void)hipEventDestroy(p.first);

@@ -15,12 +15,7 @@ namespace psm {
 void jwmf_batch_free(psm_ctx *c)
 {
     JwBatch &b = c->jwb;
-    (void)hipFree(b.tab); b.tab = nullptr;
-    if (b.tab_pin) (void)hipHostFree(b.tab_pin);
-    b.tab_pin = nullptr;
-    b.tab_cap = 0;
-    b.tab_host.clear();
-    for (hipEvent_t &e : b.ev_tab) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    table_free(b.tab);
     (void)hipFree(b.block); b.block = nullptr;
     if (b.pin) (void)hipHostFree(b.pin);
     b.pin = nullptr;
@@ -111,25 +106,14 @@ int upload_tables(psm_ctx *e, psm_ctx *c, const JwScratch sc[2], float sigma, hi
     return 0;
 }
 
-// The device table of a batch of several contexts - the images to cluster in front, the map sides from a fixed offset (the
-// capacity's: it does not move with n) - to the device if it differs from the one there (t.tab_host), through one of two page-locked
-// slots: the copy is stream-ordered behind the kernels that still read the old table, and a slot is rewritten only after the copy
-// that read it has executed
-int upload_table(psm_ctx *c0, const std::vector<JwImg> &img, const std::vector<JwSide> &sides)
+// The records of a call of several contexts as its device table holds them (c0->jwb.tab): the images to cluster in
+// front, the 2 n map sides behind the room for 2 n images - an offset that is the call's, whatever m is
+std::vector<uint8_t> table_records(const std::vector<JwImg> &img, const std::vector<JwSide> &sides)
 {
-    JwBatch &t = c0->jwb;
-    std::vector<uint8_t> tab(t.tab_cap, 0);
-    if (!img.empty()) memcpy(tab.data(), img.data(), img.size() * sizeof(JwImg));
-    memcpy(tab.data() + t.cap * sizeof(JwImg), sides.data(), sides.size() * sizeof(JwSide));
-    if (t.tab_host == tab) return 0;
-    const int slot = t.tab_slot ^= 1;
-    PSM_HIP(c0, hipEventSynchronize(t.ev_tab[slot]));
-    uint8_t *pin = t.tab_pin + (size_t)slot * t.tab_cap;
-    memcpy(pin, tab.data(), tab.size());
-    PSM_HIP(c0, hipMemcpyAsync(t.tab, pin, tab.size(), hipMemcpyHostToDevice, c0->stream));
-    PSM_HIP(c0, hipEventRecord(t.ev_tab[slot], c0->stream));
-    t.tab_host.swap(tab);
-    return 0;
+    std::vector<uint8_t> recs(sides.size() * (sizeof(JwImg) + sizeof(JwSide)), 0);
+    if (!img.empty()) memcpy(recs.data(), img.data(), img.size() * sizeof(JwImg));
+    memcpy(recs.data() + sides.size() * sizeof(JwImg), sides.data(), sides.size() * sizeof(JwSide));
+    return recs;
 }
 
 // The stage for the maps of the n contexts of one call: the only statement of its defaults, limits and preconditions,
@@ -142,7 +126,7 @@ int upload_table(psm_ctx *c0, const std::vector<JwImg> &img, const std::vector<J
 // synchronises with the host.  Every context of a batch ends where its own psm_joint_wmf(ctx, ..., NULL, NULL, 0) would have left it.
 // What differs between a single call and a batch, and nothing else:
 //   - n == 1 (either entry): the at most two JwImg / two JwSide records go to the kernels by value in the kernarg, so such a call
-//     neither allocates nor uploads a device table; n > 1: the records are uploaded as ctxs[0]'s table (upload_table);
+//     neither allocates nor uploads a device table; n > 1: the records are uploaded as ctxs[0]'s table (table_records);
 //   - n > 1 only: the other contexts' streams are ordered before and behind the shared launches by events;
 //   - psm_joint_wmf only: copy_maps_out behind this function, by the entry itself (which is why the closing synchronisation and
 //     the stage time are the entries').
@@ -156,11 +140,9 @@ int jw_enqueue(const char *who, bool single, psm_ctx *const *ctxs, int n, int ra
     if (radius > JW_RMAX) return fail(c0, "%s: radius %d outside 1..%d", who, radius, JW_RMAX);
     if (n_clusters > JW_NF_MAX) return fail(c0, "%s: n_clusters %d outside 1..%d", who, n_clusters, JW_NF_MAX);
     for (int i = 0; i < n; ++i) {
+        if (batch_member(c0, who, ctxs, i)) return 1;
         psm_ctx *c = ctxs[i];
-        if (!c) return fail(c0, "%s: context %d is NULL", who, i);
         const std::string at = single ? "this context" : "context " + std::to_string(i);
-        for (int j = 0; j < i; ++j)
-            if (ctxs[j] == c) return fail(c0, "%s: %s appears twice", who, at.c_str());
         if (c->W != c0->W || c->H != c0->H || c->device != c0->device)
             return fail(c0, "%s: %s has another width / height / device than context 0", who, at.c_str());
         if (!c->res.maps) return fail(c0, "%s: %s has no disparity maps", who, at.c_str());
@@ -179,28 +161,19 @@ int jw_enqueue(const char *who, bool single, psm_ctx *const *ctxs, int n, int ra
 
     // ---- buffers, events, the block's and the table's memory: before any launch ----
     std::vector<JwScratch> sc(NS);
-    for (int i = 0; i < n; ++i) {
-        psm_ctx *c = ctxs[i];
-        if (ensure_jw(c, &sc[2 * (size_t)i])) return c == c0 ? 1 : fail(c0, "%s: context %d: %s", who, i, c->err.c_str());
-        if (c->stream != s && !c->ev_batch) PSM_HIP(c0, hipEventCreateWithFlags(&c->ev_batch, hipEventDisableTiming));
-    }
-    if (table && !c0->ev_batch) PSM_HIP(c0, hipEventCreateWithFlags(&c0->ev_batch, hipEventDisableTiming));
-    const size_t tab_bytes = NS * (sizeof(JwImg) + sizeof(JwSide));
-    if (t.cap < NS || (table && t.tab_cap < tab_bytes)) {
+    for (int i = 0; i < n; ++i)
+        if (ensure_jw(ctxs[i], &sc[2 * (size_t)i])) return member_failed(c0, who, i, ctxs[i]);
+    if (batch_events(c0, ctxs, n)) return 1;
+    if (t.cap < NS) {
         PSM_HIP(c0, hipStreamSynchronize(s));
-        jwmf_batch_free(c0);                 // (should an allocation below fail, the next call must not take the old table for current)
+        (void)hipFree(t.block);
+        if (t.pin) (void)hipHostFree(t.pin);
+        t.block = t.pin = nullptr;
+        t.cap = 0;
         PSM_HIP(c0, hipMalloc((void **)&t.block, NS * (ST + CEN)));
         PSM_HIP(c0, hipHostMalloc((void **)&t.pin, NS * (ST + CEN), hipHostMallocDefault));
         t.cap = NS;
-        if (table) {
-            PSM_HIP(c0, hipMalloc((void **)&t.tab, tab_bytes));
-            PSM_HIP(c0, hipHostMalloc((void **)&t.tab_pin, 2 * tab_bytes, hipHostMallocDefault));
-            t.tab_cap = tab_bytes;
-        }
     }
-    if (table)
-        for (hipEvent_t &e : t.ev_tab)
-            if (!e) PSM_HIP(c0, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     int *const st_dev = (int *)t.block, *const st_pin = (int *)t.pin;
     float *const cen_dev = (float *)(t.block + t.cap * ST), *const cen_pin = (float *)(t.pin + t.cap * ST);
 
@@ -221,18 +194,20 @@ int jw_enqueue(const char *who, bool single, psm_ctx *const *ctxs, int n, int ra
             img.push_back(JwImg{c->raw[k], q.bits, q.samples, q.kt, q.d2t, q.labels, q.sums, st_dev + 4 * j, cen_dev + j * JW_NF_MAX * 3, q.lok, 0, 0});
         }
     const int m = (int)mem.size();
-    const JwRecs<JwImg> im{img.data(), table ? (const JwImg *)t.tab : nullptr, m};
-    const JwRecs<JwSide> sd{sides.data(), table ? (const JwSide *)(t.tab + t.cap * sizeof(JwImg)) : nullptr, (int)NS};
+    std::vector<uint8_t> recs;
+    bool fresh = false;
+    if (table) {
+        recs = table_records(img, sides);
+        if (table_reserve(c0, t.tab, recs.data(), recs.size(), &fresh)) return 1;
+    }
+    const JwRecs<JwImg> im{img.data(), table ? (const JwImg *)t.tab.dev : nullptr, m};
+    const JwRecs<JwSide> sd{sides.data(), table ? (const JwSide *)(t.tab.dev + NS * sizeof(JwImg)) : nullptr, (int)NS};
 
     // ---- every context's earlier work (uploads, downloads of its maps, a call of its own) is ordered before the shared launches ----
-    for (int i = 0; i < n; ++i) {
-        psm_ctx *c = ctxs[i];
-        if (maps_writable(c)) return c == c0 ? 1 : fail(c0, "%s: context %d: %s", who, i, c->err.c_str());
-        if (c->stream == s) continue;
-        PSM_HIP(c0, hipEventRecord(c->ev_batch, c->stream));
-        PSM_HIP(c0, hipStreamWaitEvent(s, c->ev_batch, 0));
-    }
-    if (table && upload_table(c0, img, sides)) return 1;
+    for (int i = 0; i < n; ++i)
+        if (maps_writable(ctxs[i])) return member_failed(c0, who, i, ctxs[i]);
+    if (batch_join(c0, ctxs, n)) return 1;
+    if (fresh && table_upload(c0, t.tab, recs.data(), recs.size())) return 1;
 
     // ---- the default clustering of the m images (tests/jwmf_model.py cluster): keys, ordered samples, identity or k-means++ +
     // Lloyd; leaves label_of_key in the side's lok.  Synchronises with the host. ----
@@ -257,7 +232,10 @@ int jw_enqueue(const char *who, bool single, psm_ctx *const *ctxs, int n, int ra
             if (ns <= n_clusters) any_id = true;
             else n_km = std::max(n_km, ns);
         }
-        if (table && upload_table(c0, img, sides)) return 1;                    // (n, nf; by value they are the next launch's argument)
+        if (table) {                            // (n, nf; by value they are the next launch's argument)
+            recs = table_records(img, sides);
+            if (table_upload(c0, t.tab, recs.data(), recs.size())) return 1;
+        }
         {
             Prof p(c0, PSM_K_JWMF);
             if (any_id) launch_jw_identity(s, im, n_clusters);
@@ -304,13 +282,8 @@ int jw_enqueue(const char *who, bool single, psm_ctx *const *ctxs, int n, int ra
     if (launched("median")) return 1;
     for (size_t q = 0; q < NS; ++q)
         PSM_HIP(c0, hipMemcpyAsync(ctxs[q / 2]->maps + (q & 1) * HW, sc[q].out, HW, hipMemcpyDeviceToDevice, s));
-    if (table) PSM_HIP(c0, hipEventRecord(c0->ev_batch, s));
-    for (int i = 0; i < n; ++i) {
-        psm_ctx *c = ctxs[i];
-        forget_early(c->res);        // (rewritten in place)
-        if (c->stream != s) PSM_HIP(c0, hipStreamWaitEvent(c->stream, c0->ev_batch, 0));
-    }
-    return 0;
+    for (int i = 0; i < n; ++i) forget_early(ctxs[i]->res);        // (rewritten in place)
+    return batch_fork(c0, ctxs, n);
 }
 
 }  // namespace

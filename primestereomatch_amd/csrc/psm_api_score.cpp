@@ -19,15 +19,11 @@ void score_free(psm_ctx *c, bool truth)
     (void)hipFree(q.cnt); q.cnt = nullptr;
     if (q.pin) (void)hipHostFree(q.pin);
     q.pin = nullptr;
-    for (hipEvent_t *e : {&q.ev_done, &q.ev[0], &q.ev[1], &q.ev_tab[0], &q.ev_tab[1]}) {
+    for (hipEvent_t *e : {&q.ev_done, &q.ev[0], &q.ev[1]}) {
         if (*e) (void)hipEventDestroy(*e);
         *e = nullptr;
     }
-    (void)hipFree(q.tab); q.tab = nullptr;
-    if (q.tab_pin) (void)hipHostFree(q.tab_pin);
-    q.tab_pin = nullptr;
-    q.tab_cap = 0;
-    q.tab_host.clear();
+    table_free(q.tab);
     q.source = -1;
     q.pending = q.timed = false;
     if (truth) {
@@ -225,10 +221,8 @@ int psm_score_batch(psm_ctx *const *ctxs, int n, int source, struct psm_score *o
     if (!outs && !c0->opt_async) return fail(c0, "%s: NULL records (only PSM_OPT_ASYNC leaves them to psm_score_wait)", who);
     const ScoreState &q0 = c0->score;
     for (int i = 0; i < n; ++i) {
+        if (batch_member(c0, who, ctxs, i)) return 1;
         psm_ctx *c = ctxs[i];
-        if (!c) return fail(c0, "%s: context %d is NULL", who, i);
-        for (int j = 0; j < i; ++j)
-            if (ctxs[j] == c) return fail(c0, "%s: context %d appears twice", who, i);
         if (c->W != c0->W || c->H != c0->H || c->D != c0->D || c->device != c0->device)
             return fail(c0, "%s: context %d has another width / height / max_disp / device than context 0", who, i);
         char member[64];
@@ -249,49 +243,19 @@ int psm_score_batch(psm_ctx *const *ctxs, int n, int source, struct psm_score *o
     const bool timed = c0->opt_profile != 0;
 
     // ---- buffers, events and the table's memory: before any launch ----
-    for (int i = 0; i < n; ++i) {
-        psm_ctx *c = ctxs[i];
-        if (ensure_scratch(c)) return c == c0 ? 1 : fail(c0, "%s: context %d: %s", who, i, c->err.c_str());
-        if (c->stream != s && !c->ev_batch) PSM_HIP(c0, hipEventCreateWithFlags(&c->ev_batch, hipEventDisableTiming));
-    }
-    if (!c0->ev_batch) PSM_HIP(c0, hipEventCreateWithFlags(&c0->ev_batch, hipEventDisableTiming));
+    for (int i = 0; i < n; ++i)
+        if (ensure_scratch(ctxs[i])) return member_failed(c0, who, i, ctxs[i]);
+    if (batch_events(c0, ctxs, n)) return 1;
     ScoreState &t = c0->score;
     std::vector<ScPair> tab((size_t)n);
     for (int i = 0; i < n; ++i) tab[i] = score_pair(ctxs[i]);
-    const bool fresh = t.tab_host.size() != tab.size() || memcmp(t.tab_host.data(), tab.data(), tab.size() * sizeof(ScPair)) != 0;
-    if (fresh && t.tab_cap < tab.size()) {
-        PSM_HIP(c0, hipStreamSynchronize(s));
-        (void)hipFree(t.tab);
-        if (t.tab_pin) (void)hipHostFree(t.tab_pin);
-        t.tab = nullptr;
-        t.tab_pin = nullptr;
-        t.tab_cap = 0;
-        t.tab_host.clear();                  // (should an allocation below fail, the next call must not take the old table for current)
-        PSM_HIP(c0, hipMalloc((void **)&t.tab, tab.size() * sizeof(ScPair)));
-        PSM_HIP(c0, hipHostMalloc((void **)&t.tab_pin, 2 * tab.size() * sizeof(ScPair), hipHostMallocDefault));
-        t.tab_cap = tab.size();
-    }
-    for (hipEvent_t &e : t.ev_tab)
-        if (!e) PSM_HIP(c0, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    bool fresh = false;
+    if (table_reserve(c0, t.tab, tab.data(), tab.size() * sizeof(ScPair), &fresh)) return 1;
+    const ScPair *dt = (const ScPair *)t.tab.dev;
 
     // ---- every context's earlier work (the result to score, a single psm_score) is ordered before the shared launches ----
-    for (int i = 0; i < n; ++i) {
-        psm_ctx *c = ctxs[i];
-        if (c->stream == s) continue;
-        PSM_HIP(c0, hipEventRecord(c->ev_batch, c->stream));
-        PSM_HIP(c0, hipStreamWaitEvent(s, c->ev_batch, 0));
-    }
-    if (fresh) {
-        // (stream-ordered behind the previous batch's kernels, which still read the old table, out of one of two page-locked slots:
-        // a slot is rewritten only after the copy that read it has executed)
-        const int slot = t.tab_slot ^= 1;
-        PSM_HIP(c0, hipEventSynchronize(t.ev_tab[slot]));
-        ScPair *pin = t.tab_pin + (size_t)slot * t.tab_cap;
-        memcpy(pin, tab.data(), tab.size() * sizeof(ScPair));
-        t.tab_host = tab;
-        PSM_HIP(c0, hipMemcpyAsync(t.tab, pin, tab.size() * sizeof(ScPair), hipMemcpyHostToDevice, s));
-        PSM_HIP(c0, hipEventRecord(t.ev_tab[slot], s));
-    }
+    if (batch_join(c0, ctxs, n)) return 1;
+    if (fresh && table_upload(c0, t.tab, tab.data(), tab.size() * sizeof(ScPair))) return 1;
 
     for (int i = 0; i < n; ++i) {
         ScoreState &q = ctxs[i]->score;
@@ -301,8 +265,8 @@ int psm_score_batch(psm_ctx *const *ctxs, int n, int source, struct psm_score *o
     }
     const ScArgs a = score_args(c0, ScPair{nullptr, nullptr, q0.have_truth ? q0.gt : nullptr, use_mask(q0) ? q0.mask : nullptr, nullptr, nullptr});      // (the scalars; the pointers are the table's)
     if (timed) PSM_HIP(c0, hipEventRecord(t.ev[0], s));
-    if (source == PSM_SCORE_SGM) launch_sc_minmax(s, a, t.tab, n);
-    launch_sc_score(s, source, a, t.tab, n);
+    if (source == PSM_SCORE_SGM) launch_sc_minmax(s, a, dt, n);
+    launch_sc_score(s, source, a, dt, n);
     if (check_launch(c0, "k_sc_minmax_b, k_sc_score_b")) return 1;
     if (timed) PSM_HIP(c0, hipEventRecord(t.ev[1], s));
 
@@ -312,12 +276,8 @@ int psm_score_batch(psm_ctx *const *ctxs, int n, int source, struct psm_score *o
         PSM_HIP(c0, hipMemcpyAsync(q.pin, q.cnt, sizeof(ScCnt), hipMemcpyDeviceToHost, s));
         PSM_HIP(c0, hipEventRecord(q.ev_done, s));
     }
-    PSM_HIP(c0, hipEventRecord(c0->ev_batch, s));
-    for (int i = 0; i < n; ++i) {
-        psm_ctx *c = ctxs[i];
-        scored(c, source, timed && i == 0, c0->opt_async != 0);
-        if (c->stream != s) PSM_HIP(c0, hipStreamWaitEvent(c->stream, c0->ev_batch, 0));
-    }
+    if (batch_fork(c0, ctxs, n)) return 1;
+    for (int i = 0; i < n; ++i) scored(ctxs[i], source, timed && i == 0, c0->opt_async != 0);
     if (c0->opt_async) return 0;
     PSM_HIP(c0, hipStreamSynchronize(s));
     for (int i = 0; i < n; ++i) fill_record(ctxs[i], &outs[i]);

@@ -38,12 +38,7 @@ void sgm_free(psm_ctx *c)
     for (uint64_t *&p : g.cen) { (void)hipFree(p); p = nullptr; }
     g.cen_have = false;
     for (hipEvent_t &e : g.ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    (void)hipFree(g.tab); g.tab = nullptr;
-    if (g.tab_pin) (void)hipHostFree(g.tab_pin);
-    g.tab_pin = nullptr;
-    g.tab_cap = 0;
-    g.tab_host.clear();
-    for (hipEvent_t &e : g.ev_tab) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    table_free(g.tab);
     for (hipEvent_t &e : g.ev_maps) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     g.have = g.timed = g.spk_have = g.maps_timed = false;
     g.spk_t0 = -1;
@@ -272,48 +267,12 @@ int enqueue(psm_ctx *c, hipStream_t s, SgmArgs a, const SgmPair *one, const SgmP
     return 0;
 }
 
-// The device table of a batch's pairs (psm_sgm_compute_batch, psm_sgm_select_maps_batch), owned by the batch's first context c0 and
-// uploaded again only when an entry changed.  table_memory: the records of ctxs[0..n) and, if they differ from the uploaded ones
-// (*fresh), room for them - before anything is ordered or launched; table_upload: the copy, on c0's stream.
-int table_memory(psm_ctx *c0, psm_ctx *const *ctxs, int n, std::vector<SgmPair> &tab, bool *fresh)
+// The records of a batch's device table (psm_sgm_compute_batch, psm_sgm_select_maps_batch): c0->sgm.tab, DESIGN.md 4.7
+std::vector<SgmPair> pairs_of(psm_ctx *const *ctxs, int n)
 {
-    SgmState &t = c0->sgm;
-    hipStream_t s = c0->stream;
-    tab.resize((size_t)n);
+    std::vector<SgmPair> tab((size_t)n);
     for (int i = 0; i < n; ++i) tab[i] = pair_of(ctxs[i], ctxs[i]->raw[0], ctxs[i]->raw[1]);
-    *fresh = t.tab_host.size() != tab.size() || memcmp(t.tab_host.data(), tab.data(), tab.size() * sizeof(SgmPair)) != 0;
-    if (*fresh && t.tab_cap < tab.size()) {
-        PSM_HIP(c0, hipStreamSynchronize(s));
-        (void)hipFree(t.tab);
-        if (t.tab_pin) (void)hipHostFree(t.tab_pin);
-        t.tab = nullptr;
-        t.tab_pin = nullptr;
-        t.tab_cap = 0;
-        t.tab_host.clear();                  // (should an allocation below fail, the next call must not take the old table for current)
-        PSM_HIP(c0, hipMalloc((void **)&t.tab, tab.size() * sizeof(SgmPair)));
-        PSM_HIP(c0, hipHostMalloc((void **)&t.tab_pin, 2 * tab.size() * sizeof(SgmPair), hipHostMallocDefault));
-        t.tab_cap = tab.size();
-    }
-    for (hipEvent_t &e : t.ev_tab)
-        if (!e) PSM_HIP(c0, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    return 0;
-}
-
-int table_upload(psm_ctx *c0, const std::vector<SgmPair> &tab)
-{
-    // (the table changes with every frame of a loop whose image slots alternate; the copy is stream-ordered behind the previous
-    // batch's kernels, which still read the old table, and reads one of two page-locked slots: a slot is rewritten only after
-    // the copy that read it has executed)
-    SgmState &t = c0->sgm;
-    hipStream_t s = c0->stream;
-    const int slot = t.tab_slot ^= 1;
-    PSM_HIP(c0, hipEventSynchronize(t.ev_tab[slot]));
-    SgmPair *pin = t.tab_pin + (size_t)slot * t.tab_cap;
-    memcpy(pin, tab.data(), tab.size() * sizeof(SgmPair));
-    t.tab_host = tab;
-    PSM_HIP(c0, hipMemcpyAsync(t.tab, pin, tab.size() * sizeof(SgmPair), hipMemcpyHostToDevice, s));
-    PSM_HIP(c0, hipEventRecord(t.ev_tab[slot], s));
-    return 0;
+    return tab;
 }
 
 // psm_sgm_select_maps / _batch: what context c must be for the call `who`; e: the context that receives the message
@@ -474,10 +433,8 @@ int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
     if (n > 4096) return fail(c0, "%s: %d pairs (at most 4096 per call)", who, n);
     const SgmState &g0 = c0->sgm;
     for (int i = 0; i < n; ++i) {
+        if (batch_member(c0, who, ctxs, i)) return 1;
         psm_ctx *c = ctxs[i];
-        if (!c) return fail(c0, "%s: context %d is NULL", who, i);
-        for (int j = 0; j < i; ++j)
-            if (ctxs[j] == c) return fail(c0, "%s: context %d appears twice", who, i);
         if (c->W != c0->W || c->H != c0->H || c->D != c0->D || c->device != c0->device)
             return fail(c0, "%s: context %d has another width / height / max_disp / device than context 0", who, i);
         char member[64];
@@ -505,36 +462,24 @@ int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
     hipStream_t s = c0->stream;
 
     // ---- buffers, events and the table's memory: before any launch, and before any context forgets its previous result ----
-    for (int i = 0; i < n; ++i) {
-        psm_ctx *c = ctxs[i];
-        if (ensure_buffers(c)) return c == c0 ? 1 : fail(c0, "%s: context %d: %s", who, i, c->err.c_str());
-        if (c->stream != s && !c->ev_batch) PSM_HIP(c0, hipEventCreateWithFlags(&c->ev_batch, hipEventDisableTiming));
-    }
-    if (!c0->ev_batch) PSM_HIP(c0, hipEventCreateWithFlags(&c0->ev_batch, hipEventDisableTiming));
-    SgmState &t = c0->sgm;
-    std::vector<SgmPair> tab;
+    for (int i = 0; i < n; ++i)
+        if (ensure_buffers(ctxs[i])) return member_failed(c0, who, i, ctxs[i]);
+    if (batch_events(c0, ctxs, n)) return 1;
+    DevTable &t = c0->sgm.tab;
+    const std::vector<SgmPair> tab = pairs_of(ctxs, n);
     bool fresh = false;
-    if (table_memory(c0, ctxs, n, tab, &fresh)) return 1;
+    if (table_reserve(c0, t, tab.data(), tab.size() * sizeof(SgmPair), &fresh)) return 1;
 
     // ---- every context's earlier work (uploads, a single compute, downloads) is ordered before the shared launches ----
-    for (int i = 0; i < n; ++i) {
-        psm_ctx *c = ctxs[i];
-        if (c->stream == s) continue;
-        PSM_HIP(c0, hipEventRecord(c->ev_batch, c->stream));
-        PSM_HIP(c0, hipStreamWaitEvent(s, c->ev_batch, 0));
-    }
-    if (fresh && table_upload(c0, tab)) return 1;
+    if (batch_join(c0, ctxs, n)) return 1;
+    if (fresh && table_upload(c0, t, tab.data(), tab.size() * sizeof(SgmPair))) return 1;
 
     // ---- the launches; then every context is where its own psm_sgm_compute would have left it - only context 0 counts as timed ----
     const SgmArgs a = sgm_args(c0, c0->raw_depth, 3, p1, p2);
     for (int i = 0; i < n; ++i) forget(ctxs[i]->sgm);
-    if (enqueue(c0, s, a, nullptr, t.tab, n)) return 1;
-    PSM_HIP(c0, hipEventRecord(c0->ev_batch, s));
-    for (int i = 0; i < n; ++i) {
-        psm_ctx *c = ctxs[i];
-        mark(c->sgm, cost_kind(g0), 3, a.dmin, a.D, i == 0 && c0->opt_profile != 0);
-        if (c->stream != s) PSM_HIP(c0, hipStreamWaitEvent(c->stream, c0->ev_batch, 0));
-    }
+    if (enqueue(c0, s, a, nullptr, (const SgmPair *)t.dev, n)) return 1;
+    if (batch_fork(c0, ctxs, n)) return 1;
+    for (int i = 0; i < n; ++i) mark(ctxs[i]->sgm, cost_kind(g0), 3, a.dmin, a.D, i == 0 && c0->opt_profile != 0);
     if (!c0->opt_async) PSM_HIP(c0, hipStreamSynchronize(s));
     return 0;
 }
@@ -574,10 +519,8 @@ int psm_sgm_select_maps_batch(psm_ctx *const *ctxs, int n)
     psm_ctx *c0 = ctxs[0];
     if (n > 4096) return fail(c0, "%s: %d pairs (at most 4096 per call)", who, n);
     for (int i = 0; i < n; ++i) {
+        if (batch_member(c0, who, ctxs, i)) return 1;
         psm_ctx *c = ctxs[i];
-        if (!c) return fail(c0, "%s: context %d is NULL", who, i);
-        for (int j = 0; j < i; ++j)
-            if (ctxs[j] == c) return fail(c0, "%s: context %d appears twice", who, i);
         if (c->W != c0->W || c->H != c0->H || c->D != c0->D || c->device != c0->device)
             return fail(c0, "%s: context %d has another width / height / max_disp / device than context 0", who, i);
         char member[64];
@@ -589,43 +532,34 @@ int psm_sgm_select_maps_batch(psm_ctx *const *ctxs, int n)
     }
     if (bind(c0)) return 1;
     hipStream_t s = c0->stream;
-    SgmState &t = c0->sgm;
+    SgmState &g0 = c0->sgm;
+    DevTable &t = g0.tab;
     const bool timed = c0->opt_profile != 0;
 
     // ---- events and the table's memory: before anything is ordered or launched ----
-    for (int i = 0; i < n; ++i)
-        if (ctxs[i]->stream != s && !ctxs[i]->ev_batch) PSM_HIP(c0, hipEventCreateWithFlags(&ctxs[i]->ev_batch, hipEventDisableTiming));
-    if (!c0->ev_batch) PSM_HIP(c0, hipEventCreateWithFlags(&c0->ev_batch, hipEventDisableTiming));
+    if (batch_events(c0, ctxs, n)) return 1;
     if (timed)
-        for (hipEvent_t &e : t.ev_maps)
+        for (hipEvent_t &e : g0.ev_maps)
             if (!e) PSM_HIP(c0, hipEventCreate(&e));
-    std::vector<SgmPair> tab;
+    const std::vector<SgmPair> tab = pairs_of(ctxs, n);
     bool fresh = false;
-    if (table_memory(c0, ctxs, n, tab, &fresh)) return 1;
+    if (table_reserve(c0, t, tab.data(), tab.size() * sizeof(SgmPair), &fresh)) return 1;
 
     // ---- every context's earlier work (its compute, downloads of its maps) is ordered before the shared launch ----
-    for (int i = 0; i < n; ++i) {
-        psm_ctx *c = ctxs[i];
-        if (c->ev_down) PSM_HIP(c0, hipStreamWaitEvent(s, c->ev_down, 0));       // (maps_writable, for the stream that writes)
-        if (c->stream == s) continue;
-        PSM_HIP(c0, hipEventRecord(c->ev_batch, c->stream));
-        PSM_HIP(c0, hipStreamWaitEvent(s, c->ev_batch, 0));
-    }
-    if (fresh && table_upload(c0, tab)) return 1;
+    for (int i = 0; i < n; ++i)
+        if (ctxs[i]->ev_down) PSM_HIP(c0, hipStreamWaitEvent(s, ctxs[i]->ev_down, 0));       // (maps_writable, for the stream that writes)
+    if (batch_join(c0, ctxs, n)) return 1;
+    if (fresh && table_upload(c0, t, tab.data(), tab.size() * sizeof(SgmPair))) return 1;
 
     // ---- the launch; then every context is where its own psm_sgm_select_maps would have left it - only context 0 counts as timed ----
     for (int i = 0; i < n; ++i) ctxs[i]->sgm.maps_timed = false;
-    if (timed) PSM_HIP(c0, hipEventRecord(t.ev_maps[0], s));
-    launch_sgm_maps(s, maps_args(c0), nullptr, t.tab, n);
+    if (timed) PSM_HIP(c0, hipEventRecord(g0.ev_maps[0], s));
+    launch_sgm_maps(s, maps_args(c0), nullptr, (const SgmPair *)t.dev, n);
     if (check_launch(c0, "k_sgm_maps_b")) return 1;
-    if (timed) PSM_HIP(c0, hipEventRecord(t.ev_maps[1], s));
-    t.maps_timed = timed;
-    PSM_HIP(c0, hipEventRecord(c0->ev_batch, s));
-    for (int i = 0; i < n; ++i) {
-        psm_ctx *c = ctxs[i];
-        maps_selected(c);
-        if (c->stream != s) PSM_HIP(c0, hipStreamWaitEvent(c->stream, c0->ev_batch, 0));
-    }
+    if (timed) PSM_HIP(c0, hipEventRecord(g0.ev_maps[1], s));
+    g0.maps_timed = timed;
+    if (batch_fork(c0, ctxs, n)) return 1;
+    for (int i = 0; i < n; ++i) maps_selected(ctxs[i]);
     if (!c0->opt_async) PSM_HIP(c0, hipStreamSynchronize(s));
     return 0;
 }

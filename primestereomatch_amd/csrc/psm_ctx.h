@@ -5,7 +5,9 @@
 //                       of the fused kernel runs, materialisation
 //   psm_api_select.cpp  DispSelect: maps, packed minima, row stripes and disparity shards
 //   psm_api_pp.cpp      post-processing: L-R check, invalid fill, weighted median
-//   psm_api_batch.cpp   several Middlebury-size pairs per launch (psm_compute_batch)
+//   psm_api_batch.cpp   several Middlebury-size pairs per launch (psm_compute_batch); what every batch entry point shares: the
+//                       device table of the members' records (psm::DevTable), the join and fork of the members' streams, the
+//                       member checks
 //   psm_api_jwmf.cpp    JointWMF: the joint weighted median of the reference's live post-filter (psm_joint_wmf), and of the
 //                       maps of several contexts in shared launches (psm_joint_wmf_batch)
 //   psm_api_rectify.cpp video mode: remap + crop of the camera frame into the staged image slot (psm_upload_pair_rectified)
@@ -43,6 +45,17 @@ struct StreamSet {
     int refs = 0;
 };
 
+// The device table of the members' records of a batch entry point, owned by the batch's first context and written
+// by table_reserve / table_upload / table_free (psm_api_batch.cpp) alone.  Bytes: the records' type is the launch site's cast.
+struct DevTable {
+    uint8_t *dev = nullptr;
+    uint8_t *pin = nullptr;                        // page-locked staging: two slots of `cap` bytes, used alternately
+    std::vector<uint8_t> host;                     // the records the device copy holds (empty: none)
+    size_t cap = 0;                                // bytes
+    int slot = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};         // the copy out of a slot has executed (the host may refill it)
+};
+
 // psm_sgm_compute (psm_api_sgm.cpp): parameters, the stage's own device buffers (allocated on first use, reused from frame to
 // frame) and the events of psm_sgm_times.  Nothing else in the context reads or writes any of it.
 struct SgmState {
@@ -73,14 +86,7 @@ struct SgmState {
     int cen_w = 0, cen_h = 0;                      // the window; (0, 0): off
     uint64_t *cen[2] = {nullptr, nullptr};         // the code planes of both images, [H][W]
     bool cen_have = false;                         // the last compute wrote them
-    // psm_sgm_compute_batch (this context as the first of a batch): the device table of the pairs' buffers, its host copy (the
-    // table is uploaded again only when an entry changed) and its page-locked staging, two slots used alternately as
-    // psm_compute_batch's (psm_ctx::batch_pin); ev_tab: the copy out of a slot has executed
-    SgmPair *tab = nullptr, *tab_pin = nullptr;
-    std::vector<SgmPair> tab_host;
-    size_t tab_cap = 0;
-    int tab_slot = 0;
-    hipEvent_t ev_tab[2] = {nullptr, nullptr};
+    DevTable tab;                                  // psm_sgm_compute_batch, psm_sgm_select_maps_batch (this context as the first): SgmPair records
     // psm_sgm_select_maps: the events around its launch (PSM_OPT_PROFILE), and whether the last call recorded them (psm_sgm_maps_time)
     hipEvent_t ev_maps[2] = {nullptr, nullptr};
     bool maps_timed = false;
@@ -104,14 +110,9 @@ struct JwClust {
 
 // psm_joint_wmf, psm_joint_wmf_batch (psm_api_jwmf.cpp; this context as the first of the call): `block`: the Lloyd states and centres
 // of the images to cluster side by side, `pin` the page-locked memory the host reads them in.  A call of several contexts also has
-// the device table - JwImg records of the images to cluster, behind them the JwSide records of the map sides - with its host copy
-// (uploaded again only when an entry changed) and its page-locked staging, two slots used alternately as SgmState's.
+// the device table: room for 2 n JwImg records (the images to cluster), behind them the 2 n JwSide records of the map sides.
 struct JwBatch {
-    uint8_t *tab = nullptr, *tab_pin = nullptr;
-    std::vector<uint8_t> tab_host;
-    size_t tab_cap = 0;                            // bytes
-    int tab_slot = 0;
-    hipEvent_t ev_tab[2] = {nullptr, nullptr};
+    DevTable tab;
     uint8_t *block = nullptr, *pin = nullptr;      // [cap] x {int state[4]}, then [cap] x {float centres[JW_NF_MAX][3]}
     size_t cap = 0;                                // images
 };
@@ -132,12 +133,7 @@ struct ScoreState {
     int unit = 0;                                  // ... and its 127 / max_disp
     bool pending = false;                          // a record is on its way to `pin` (psm_score_wait)
     bool timed = false;
-    // psm_score_batch (this context as the first of a batch): the device table, its host copy and page-locked staging, as SgmState's
-    ScPair *tab = nullptr, *tab_pin = nullptr;
-    std::vector<ScPair> tab_host;
-    size_t tab_cap = 0;
-    int tab_slot = 0;
-    hipEvent_t ev_tab[2] = {nullptr, nullptr};
+    DevTable tab;                                  // psm_score_batch (this context as the first of a batch): ScPair records
 };
 }  // namespace psm
 
@@ -223,15 +219,8 @@ struct psm_ctx {
     size_t gf_scratch_bytes = 0;
     unsigned long long *pc_ts = nullptr;  // PSM_OPT_PROFILE 2: {first start, last end} device time stamps per k_cvf_pc launch
     int pc_ts_n = 0;                      // launches stamped since the last reset (slots: PC_TS_SLOTS)
-    // psm_compute_batch (this context as the first of a batch): device table of the pairs' plane pointers, its host copy
-    // (re-uploaded only when an entry changed) and the event the other contexts' streams wait for
-    psm::PcPair *batch_tab = nullptr;
-    std::vector<psm::PcPair> batch_host;
-    psm::PcPair *batch_pin = nullptr;    // page-locked staging of the table, two slots used alternately (a pageable source would make
-    size_t batch_cap = 0;                // the "asynchronous" copy wait for the stream to drain: one frame could not follow the other)
-    int batch_slot = 0;
-    hipEvent_t ev_tab[2] = {nullptr, nullptr};
-    hipEvent_t ev_batch = nullptr;
+    psm::DevTable batch_tab;            // psm_compute_batch (this context as the first of a batch): PcPair records
+    hipEvent_t ev_batch = nullptr;      // a batch entry point's join and fork (batch_join, batch_fork)
     // PSM_OPT_GRAPH: the launches of a batch captured once as a hipGraph and replayed while nothing they depend on changes
     hipGraphExec_t batch_graph = nullptr;
     long long graph_sig[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -373,6 +362,16 @@ constexpr int PSM_IMG_EXP = 10, PSM_VOL_EXP = 60;
 constexpr size_t PSM_COPY_KERNEL_MAX = (size_t)2 << 20;     // asynchronous PCIe legs up to this size go through k_copy16 instead of the copy engines
 unsigned long long *next_pc_stamp(psm_ctx *c);   // slot of the next k_cvf_pc launch (NULL unless PSM_OPT_PROFILE 2)
 
+// psm_api_batch.cpp: what the batch entry points share.  c0: the batch's first context, which owns the table,
+// whose stream the shared launches run on and which receives every message.
+int batch_member(psm_ctx *c0, const char *who, psm_ctx *const *ctxs, int i);    // ctxs[i] is a context, and none of ctxs[0..i)
+int member_failed(psm_ctx *c0, const char *who, int i, const psm_ctx *c);        // the error of member i as the batch's: returns 1
+int table_reserve(psm_ctx *c0, DevTable &t, const void *recs, size_t bytes, bool *fresh);
+int table_upload(psm_ctx *c0, DevTable &t, const void *recs, size_t bytes);
+void table_free(DevTable &t);
+int batch_events(psm_ctx *c0, psm_ctx *const *ctxs, int n);
+int batch_join(psm_ctx *c0, psm_ctx *const *ctxs, int n);
+int batch_fork(psm_ctx *c0, psm_ctx *const *ctxs, int n);
 // psm_api_rectify.cpp
 void rectify_free(psm_ctx *c, bool maps);        // the source slots and their staging; maps: the device maps too
 // psm_api_jwmf.cpp
