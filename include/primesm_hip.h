@@ -738,7 +738,8 @@ int psm_kernel_time_ms(psm_ctx *ctx, int kernel, double *total_ms, int *launches
 int psm_reset_kernel_times(psm_ctx *ctx);
 /* With PSM_OPT_PROFILE=2: duration in ms (first workgroup start to last workgroup end, device constant-rate clock) and form
  * (1 = minima planes, 2 = key plane, 0 = storing) of every launch of the fused filter kernel since the last call, in launch
- * order; at most max_launches (the library keeps 4096).  Costs two 64-bit atomics per workgroup and no events or
+ * order; at most max_launches (the library keeps 4096).  A phase without a live work item (the minima planes of a forced
+ * two-phase selection whose only seed slice is d = 0) starts no kernel and leaves no record.  Costs two 64-bit atomics per workgroup and no events or
  * synchronisation between kernels, so it can stay on inside a timed region.  Resets the record. */
 int psm_filter_launch_times(psm_ctx *ctx, double *ms, int *form, int max_launches, int *n_launches);
 

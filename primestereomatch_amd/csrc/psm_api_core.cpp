@@ -681,12 +681,17 @@ int psm_filter_launch_times(psm_ctx *c, double *ms, int *form, int max_launches,
         PSM_HIP(c, hipMemcpy(h.data(), c->pc_ts, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         int khz = 0;
         if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device) != hipSuccess || khz <= 0) khz = 100000;
-        for (int i = 0; i < n && i < max_launches; ++i) {
+        int k = 0;
+        for (int i = 0; i < n && k < max_launches; ++i) {
             const unsigned long long a = h[i], b = h[PC_TS_SLOTS + i];
-            if (ms) ms[i] = b > a ? (double)(b - a) / (double)khz : 0.0;
-            if (form) form[i] = (int)h[2 * PC_TS_SLOTS + i];
+            // a slot nobody stamped belongs to a launch without a live item (the plane phase of d = 0 alone: pc_launch starts
+            // nothing) - no launch, no record; it used to read as 0 ms of form 0, the storing form
+            if (a == ~0ull) continue;
+            if (ms) ms[k] = b > a ? (double)(b - a) / (double)khz : 0.0;
+            if (form) form[k] = (int)h[2 * PC_TS_SLOTS + i];
+            ++k;
         }
-        *n_launches = n < max_launches ? n : max_launches;
+        *n_launches = k;
     }
     // start over: starts <- all ones, ends / forms <- 0
     if (c->pc_ts) {
