@@ -121,17 +121,12 @@ void free_all(psm_ctx *c)
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->pinned2) (void)hipHostFree(c->pinned2);
     if (c->pin_up) (void)hipHostFree(c->pin_up);
-    (void)hipFree(c->wm);
-    (void)hipFree(c->wm_par);
-    (void)hipFree(c->wm_wts);
+    wm_free(c, true);
     (void)hipFree(c->jw);
     if (c->jw_pin) (void)hipHostFree(c->jw_pin);
     for (hipEvent_t e : c->ev_jw)
         if (e) (void)hipEventDestroy(e);
     jwmf_batch_free(c);
-    if (c->wm_pin) (void)hipHostFree(c->wm_pin);
-    for (hipEvent_t e : {c->ev_wm[0], c->ev_wm[1]})
-        if (e) (void)hipEventDestroy(e);
     (void)hipFree(c->gf_scratch);
     (void)hipFree(c->pc_ts);
     (void)hipFree(c->fgf);
@@ -414,9 +409,7 @@ int psm_release_scratch(psm_ctx *c)
 {
     if (!c) return 1;
     if (psm_synchronize(c)) return 1;
-    (void)hipFree(c->wm_wts); c->wm_wts = nullptr; c->wm_wts_n = 0;
-    (void)hipFree(c->wm_par); c->wm_par = nullptr;
-    (void)hipFree(c->wm); c->wm = nullptr;
+    wm_free(c, false);
     (void)hipFree(c->gf_scratch); c->gf_scratch = nullptr; c->gf_scratch_bytes = 0;
     (void)hipFree(c->gather); c->gather = nullptr; c->gather_ranks = 0;
     (void)hipFree(c->fvol); c->fvol = nullptr;

@@ -4,7 +4,8 @@
 //   psm_api_filter.cpp  CostConst / CostFilter: which plane rows are current (ensure_planes), what is built lazily, which form
 //                       of the fused kernel runs, materialisation
 //   psm_api_select.cpp  DispSelect: maps, packed minima, row stripes and disparity shards
-//   psm_api_pp.cpp      post-processing: L-R check, invalid fill, weighted median
+//   psm_api_pp.cpp      post-processing: L-R check, invalid fill, weighted median (psm::WmState; its sweep schedule, block
+//                       layout and cache decision are the host-only psm_wm_sched.h)
 //   psm_api_batch.cpp   several Middlebury-size pairs per launch (psm_compute_batch); what every batch entry point shares: the
 //                       device table of the members' records (psm::DevTable), the join and fork of the members' streams, the
 //                       member checks
@@ -117,6 +118,19 @@ struct JwBatch {
     size_t cap = 0;                                // images
 };
 
+// psm_wgt_median (psm_api_pp.cpp): the scratch of its two forms, allocated on first use, and what the last call reports.  Freed by
+// wm_free alone.
+struct WmState {
+    int *flow = nullptr;                           // the dataflow form: nxt[H][W+1], prog[H], err[1]
+    uint8_t *block = nullptr;                      // the sweep form: both sides' state and the per-sweep counters of both maps (wm_layout, psm_wm_sched.h)
+    float *wts = nullptr;                          // ... the 19 x 19 window weights of every invalid pixel (formed once per call, read by every evaluation)
+    size_t wts_n = 0;                              // floats
+    int *pin = nullptr;                            // page-locked snapshots of the counters (two slots: a group's counters are read while the next group runs)
+    hipEvent_t ev[2] = {nullptr, nullptr};         // ... the snapshot into a slot has executed
+    int sweeps[2] = {0, 0};                        // last call: sweeps until the fixed point (-1: dataflow form), evaluations
+    long long evals[2] = {0, 0};
+};
+
 // psm_score (psm_api_score.cpp): parameters, the dataset's truth (kept until replaced or cleared), and the stage's scratch -
 // display and error planes, counters, their page-locked slot - allocated on first use and given back by psm_release_scratch.
 struct ScoreState {
@@ -180,16 +194,7 @@ struct psm_ctx {
     uint8_t *valid = nullptr;           // [2][H][W]
     uint8_t *pinned = nullptr;          // [2][H][W] page-locked bounce buffer for map / mask downloads (on first use)
     uint8_t *pinned2 = nullptr;         // second bounce buffer: psm_download_maps_async of frame i while frame i-1 is being read
-    int *wm = nullptr;                  // psm_wgt_median scratch: nxt[H][W+1], prog[H], err[1]; allocated on first use
-    uint8_t *wm_par = nullptr;          // scratch of its parallel (sweep) form, per side: orig, newv, chgb, rowany (bytes), stamp, 2 active lists, changed list,
-                                        // slot_of, the list of all invalid pixels; behind the two sides the per-sweep counters of both maps (one block:
-                                        // one fill, one snapshot) - the layout WmPair points into (psm_kernels.h)
-    float *wm_wts = nullptr;            // ... the 19 x 19 window weights of every invalid pixel (formed once per call, read by every evaluation)
-    size_t wm_wts_n = 0;
-    int *wm_pin = nullptr;              // page-locked snapshots of the sweep counters (two slots: a group's counters are read while the next group runs)
-    hipEvent_t ev_wm[2] = {nullptr, nullptr};
-    int wm_sweeps[2] = {0, 0};          // last call: sweeps until the fixed point (-1: dataflow form), evaluations
-    long long wm_evals[2] = {0, 0};
+    psm::WmState wm;
     // psm_joint_wmf (psm_api_jwmf.cpp): one device block for both sides (psm::JwScratch), allocated on first use
     uint8_t *jw = nullptr;
     psm::JwClust jw_cl[2];
@@ -378,6 +383,8 @@ void rectify_free(psm_ctx *c, bool maps);        // the source slots and their s
 void jwmf_batch_free(psm_ctx *c);                // what the context holds as the first of a psm_joint_wmf_batch
 // psm_api_sgm.cpp
 void sgm_free(psm_ctx *c);                       // the stage's buffers and events (its parameters stay)
+// psm_api_pp.cpp
+void wm_free(psm_ctx *c, bool all);              // the weighted median's device scratch; all: its page-locked snapshots and events too
 // psm_api_score.cpp
 void score_free(psm_ctx *c, bool truth);         // the stage's scratch and events; truth: the uploaded truth, mask and hook map too
 // psm_api_select.cpp: copy_maps_out - two [H][W] planes on the device to the caller's rows

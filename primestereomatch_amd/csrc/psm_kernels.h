@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "psm_live.h"
+#include "psm_wm_sched.h"
 
 namespace psm {
 
@@ -134,9 +135,7 @@ void launch_fill_inv(hipStream_t s, uint8_t *dis, const uint8_t *valid, size_t s
 void launch_wgt_median(hipStream_t s, uint8_t *dis, const uint8_t *valid, const float4 *g1, int W, int H, int maxDis, int right,
                        int *nxt, int *prog, int *err);
 // parallel form (sweeps to the fixed point of the in-place recursion; psm_pp.hip)
-constexpr int WM_LANE_MIN = 8192;       // active pixels from which a sweep evaluates one pixel per LANE (k_wm_eval) instead of per wave
-constexpr int WM_WROW = 20;             // floats per window row of the weight cache (19 weights + 1 pad: five float4)
-constexpr int WM_WPIX = 19 * WM_WROW;   // floats per cached pixel
+// (WM_LANE_MIN, WM_WROW, WM_WPIX, the sweep cap and the counters' accessors: psm_wm_sched.h)
 // One map's share of the sweep state.  Sweep k (0-based) evaluates the list act = k ? list[(k + 1) & 1] : inv, whose length is
 // cnt[2k]; it leaves the number of changed pixels in cnt[2k + 1], the changed pixels in chg, and the next sweep's list in
 // list[k & 1] / cnt[2k + 2]; cnt[0] is the number of invalid pixels (inv).  Both maps go through every launch side by side

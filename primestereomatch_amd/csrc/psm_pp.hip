@@ -833,6 +833,16 @@ __global__ __launch_bounds__(64) void k_wm_apply(WmPair pr, int sw, int W, int H
              blockIdx.x, gridDim.x, a.cnt + 2 * sw);
 }
 
+// f(std::integral_constant<int, NB>) for nb = ceil(maxDis / 64) histogram bins per lane: the instantiations are NB 1..4 (D <= 256)
+template <class F>
+static void wm_with_nb(int nb, F f)
+{
+    if (nb <= 1) f(std::integral_constant<int, 1>{});
+    else if (nb == 2) f(std::integral_constant<int, 2>{});
+    else if (nb == 3) f(std::integral_constant<int, 3>{});
+    else f(std::integral_constant<int, 4>{});
+}
+
 // the 19 x 19 weights of the n_inv invalid pixels of `inv` (n = an upper bound of *n_inv, for the grid) -> wts, slot_of
 void launch_wm_weights(hipStream_t s, const float4 *g1, int W, int H, int right, const int *inv, const int *n_inv, int n, float *wts, int *slot_of)
 {
@@ -867,11 +877,11 @@ void launch_wm_sweep(hipStream_t s, const WmPair &p, int W, int H, int maxDis, i
     // ... and the one-wave-per-pixel form for short lists (either kernel returns at once when a list is not its size)
     const int nb = (maxDis + 63) / 64;
     const dim3 gw(8192, 2);
-#define PSM_LAUNCH_WE(NBV, CA) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wm_eval_w<NBV, CA>), gw, dim3(64), 0, s, p, sw, W, H, maxDis, force)
-#define PSM_LAUNCH_WE2(NBV) { if (cached) PSM_LAUNCH_WE(NBV, true); else PSM_LAUNCH_WE(NBV, false); }
-    if (nb <= 1) PSM_LAUNCH_WE2(1) else if (nb == 2) PSM_LAUNCH_WE2(2) else if (nb == 3) PSM_LAUNCH_WE2(3) else PSM_LAUNCH_WE2(4)
-#undef PSM_LAUNCH_WE2
-#undef PSM_LAUNCH_WE
+    wm_with_nb(nb, [&](auto nbv) {
+        constexpr int NB = decltype(nbv)::value;
+        if (cached) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wm_eval_w<NB, true>), gw, dim3(64), 0, s, p, sw, W, H, maxDis, force);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wm_eval_w<NB, false>), gw, dim3(64), 0, s, p, sw, W, H, maxDis, force);
+    });
     if (tail) return;               // (the forced wave form applied its changes and queued their dependents itself)
     hipLaunchKernelGGL(k_wm_apply, ga, dim3(64), 0, s, p, sw, W, H, force);
     hipLaunchKernelGGL(k_wm_gather, dim3(2048, 2), dim3(256), 0, s, p, sw, W, H);
@@ -882,14 +892,10 @@ void launch_wgt_median(hipStream_t s, uint8_t *dis, const uint8_t *valid, const 
 {
     hipLaunchKernelGGL(k_wm_next, dim3(H), dim3(64), 0, s, valid, W, nxt, prog);
     const int nb = (maxDis + 63) / 64;
-#define PSM_LAUNCH_WM(R, NBV) \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wgt_median<R, NBV>), dim3(H), dim3(64), 0, s, dis, g1, (const int *)nxt, prog, W, H, maxDis, err)
-    if (right) {
-        if (nb <= 1) PSM_LAUNCH_WM(true, 1); else if (nb == 2) PSM_LAUNCH_WM(true, 2); else if (nb == 3) PSM_LAUNCH_WM(true, 3); else PSM_LAUNCH_WM(true, 4);
-    } else {
-        if (nb <= 1) PSM_LAUNCH_WM(false, 1); else if (nb == 2) PSM_LAUNCH_WM(false, 2); else if (nb == 3) PSM_LAUNCH_WM(false, 3); else PSM_LAUNCH_WM(false, 4);
-    }
-#undef PSM_LAUNCH_WM
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(H), dim3(64), 0, s, dis, g1, (const int *)nxt, prog, W, H, maxDis, err); };
+    // (the side outside: the kernels stay in the object in the order they have had, all right ones first)
+    if (right) wm_with_nb(nb, [&](auto nbv) { launch(k_wgt_median<true, decltype(nbv)::value>); });
+    else wm_with_nb(nb, [&](auto nbv) { launch(k_wgt_median<false, decltype(nbv)::value>); });
 }
 
 }  // namespace psm

@@ -96,6 +96,36 @@ def test_wgt_median_long_lists_with_and_without_the_weight_cache(psm, oracle, fl
     assert np.array_equal(gl, el) and np.array_equal(gr, er)
 
 
+def test_wgt_median_forms_in_turn_on_one_context(psm, oracle):
+    """One context through every form of the driver in turn - sweeps with the cache, without it, the dataflow form, two sweeps and
+    the fall-back, then the first two again - on the inputs of the long-list test, uploaded anew for every run, with
+    psm_release_scratch between each run and the next: every run allocates its scratch again (wm_free gave it back), lays the
+    sweep block out again and meets the page-locked snapshots, the events and the statistics another form left behind.  Both maps
+    are the oracle's every time."""
+    from primestereomatch_amd import capi
+    H, W, D = 110, 230, 96
+    l, lm, rm, lv, rv = _wm_inputs(H, W, D, seed=77, frac_invalid=0.55)
+    assert (lv == 0).sum() >= 8192 and (rv == 0).sum() >= 8192
+    r = np.roll(l, 5, axis=1)
+    el = oracle.wgt_median(oracle.u8_to_f32(l), lm, lv, D, right=False)
+    er = oracle.wgt_median(oracle.u8_to_f32(r), rm, rv, D, right=True)
+    NO_CACHE, DATAFLOW, TWO_SWEEPS = 16777216, 4194304, 8388608
+    with psm.DispEst(l, r, D) as de:
+        for run, flags in enumerate((0, NO_CACHE, DATAFLOW, TWO_SWEEPS, 0, NO_CACHE)):
+            if run:
+                de.release_scratch()
+            de.set_option(capi.PSM_OPT_FLAGS, flags)
+            de.upload_maps(lm, rm, lv, rv)
+            de.WgtMedian_GPU()
+            sweeps, evals = de.wgt_median_stats()
+            print(f"[wmf] run {run} flags {flags}: sweeps {sweeps}, evaluations {evals}")
+            assert np.array_equal(de.lDisMap, el) and np.array_equal(de.rDisMap, er), run
+            if flags == DATAFLOW:
+                assert sweeps == [-1, -1]
+            elif flags in (0, NO_CACHE):
+                assert min(sweeps) >= 2, run
+
+
 def test_wgt_median_repeats_give_one_map(psm, oracle):
     """Round 6: a changed pixel is written the moment it is found, so which evaluations of a sweep see it depends on timing - the
     number of evaluations may differ between runs, the maps may not (the fixed point is unique).  The same dense input twelve times,
