@@ -138,21 +138,21 @@ extern "C" int psm_compute_batch(psm_ctx *const *ctxs, int n)
         if (c->march.flags & (PSM_FLAG_F32_TOL | PSM_FLAG_FMA_SOLVE))
             return fail(c0, "psm_compute_batch: context %d asks for PSM_FLAG_F32_TOL / PSM_FLAG_FMA_SOLVE (single-pair entry points only)", i);
         if (c->march.yend > c->march.ybeg) return fail(c0, "psm_compute_batch: context %d is restricted to a row stripe", i);
-        if (!c->have_images && c->next_depth < 0) return fail(c0, "psm_compute_batch: context %d has no image pair", i);
-        if (c->next_depth >= 0 ? c->next_depth != (c0->next_depth >= 0 ? c0->next_depth : c0->raw_depth)
-                               : c->raw_depth != (c0->next_depth >= 0 ? c0->next_depth : c0->raw_depth))
+        if (!c->have_images && !pair_staged(c->pair.st)) return fail(c0, "psm_compute_batch: context %d has no image pair", i);
+        if (depth_at_construct(c->pair.st) != depth_at_construct(c0->pair.st))      // (a staged pair is adopted below)
             return fail(c0, "psm_compute_batch: context %d holds images of another depth than context 0", i);
     }
     if (bind(c0)) return 1;
     const double t0 = now_us();
-    for (int i = 0; i < n; ++i) {        // (float images staged asynchronously bring their range with them)
+    // Refused before any context has changed.  Float images staged asynchronously bring their range with them; only the IMAGES
+    // matter: the batch rebuilds the costs from them, as psm_cost_construct does before it forgets an uploaded volume's range.
+    for (int i = 0; i < n; ++i) {
         psm_ctx *c = ctxs[i];
-        if (c->next_depth >= 0 && c->range_next_pending) {
-            PSM_HIP(c0, hipEventSynchronize(c->ev_up));
-            if (!range_inside(c, 1, -PSM_IMG_EXP, PSM_IMG_EXP)) return fail(c0, "psm_compute_batch: the float images of context %d are outside the select forms' domain (2^-10 .. 2^10)", i);
-        } else if (c->next_depth < 0 && !c->img_domain_ok)      // (only the IMAGES matter: the batch rebuilds the costs from them,
-            return fail(c0, "psm_compute_batch: the float images of context %d are outside the select forms' domain (2^-10 .. 2^10); use the single-pair entry points", i);
-    }                                                           //  as psm_cost_construct does before it forgets an uploaded volume's range)
+        bool ok = true;
+        if (next_pair_inside(c, &ok)) return member_failed(c0, "psm_compute_batch", i, c);
+        if (!ok) return fail(c0, "psm_compute_batch: the float images of context %d are outside the select forms' domain (2^-10 .. 2^10)%s", i,
+                             pair_staged(c->pair.st) ? "" : "; use the single-pair entry points");
+    }
     const int W = c0->W, H = c0->H, Dloc = c0->Dloc;
     hipStream_t s = c0->stream;
 
@@ -182,7 +182,7 @@ extern "C" int psm_compute_batch(psm_ctx *const *ctxs, int n)
     const PcPair *dt = (const PcPair *)c0->batch_tab.dev;
     const PcPairs P = {dt, n, {}};
 
-    const int depth = c0->raw_depth;
+    const int depth = c0->pair.st.depth;
     const size_t row = (size_t)W * 3 * (depth == PSM_IMG_F32 ? 4 : 1);
     const bool u8 = c0->dtype == PSM_U8;
     const bool whole = Dloc == c0->D;        // every slice here: the maps are final (else: packed minima for psm_disp_merge)
@@ -232,7 +232,7 @@ extern "C" int psm_compute_batch(psm_ctx *const *ctxs, int n)
 #endif
     if (enqueue()) return 1;
     for (int i = 0; i < n; ++i)
-        if (ctxs[i]->ev_free) PSM_HIP(c0, hipEventRecord(ctxs[i]->ev_free, s));     // the staged images have been read
+        if (images_read(ctxs[i], s)) return member_failed(c0, "psm_compute_batch", i, ctxs[i]);
     const double t2 = now_us();
 
     // ---- every context is now where psm_cost_construct + psm_cost_filter + psm_disp_select(ctx, NULL, NULL, 0) leave it ----

@@ -70,11 +70,9 @@ int bind(psm_ctx *c)
     return 0;
 }
 
-
 // a new image pair is current: nothing derived from the previous one survives
-void adopt_new_pair(psm_ctx *c, int depth)
+void adopt_new_pair(psm_ctx *c)
 {
-    c->raw_depth = depth;
     c->have_images = true;
     c->g1_rows = c->guid_rows = Rows{};
     c->have_cost = false;
@@ -82,6 +80,15 @@ void adopt_new_pair(psm_ctx *c, int depth)
     stale(c->res);
     keys_gone(c->res);
     for (JwClust &q : c->jw_cl) q.gone();                  // clusters belong to the images
+}
+
+void pair_slots_free(psm_ctx *c)
+{
+    PairSlots &p = c->pair;
+    for (void *d : {p.raw[0], p.raw[1], p.raw_next[0], p.raw_next[1]}) (void)hipFree(d);
+    if (p.pin_up) (void)hipHostFree(p.pin_up);
+    for (hipEvent_t e : {p.ev_up, p.ev_free, p.ev_stage[0], p.ev_stage[1]})
+        if (e) (void)hipEventDestroy(e);
 }
 
 }  // namespace psm
@@ -94,9 +101,8 @@ void free_all(psm_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->down_stream) (void)hipStreamSynchronize(c->down_stream);
+    pair_slots_free(c);
     for (int s = 0; s < 2; ++s) {
-        (void)hipFree(c->raw[s]);
-        (void)hipFree(c->raw_next[s]);
         (void)hipFree(c->g[s].g1);
         (void)hipFree(c->g[s].g2);
         (void)hipFree(c->g[s].g3);
@@ -120,7 +126,6 @@ void free_all(psm_ctx *c)
     }
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->pinned2) (void)hipHostFree(c->pinned2);
-    if (c->pin_up) (void)hipHostFree(c->pin_up);
     wm_free(c, true);
     (void)hipFree(c->jw);
     if (c->jw_pin) (void)hipHostFree(c->jw_pin);
@@ -141,7 +146,7 @@ void free_all(psm_ctx *c)
             (void)hipEventDestroy(p.second);
         }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {c->ev_up, c->ev_maps, c->ev_down, c->ev_free, c->ev_stage[0], c->ev_stage[1]})
+    for (hipEvent_t e : {c->ev_maps, c->ev_down})
         if (e) (void)hipEventDestroy(e);
     if (c->shared) {
         if (--c->shared->refs == 0) {
@@ -234,6 +239,75 @@ int h2d_rows(psm_ctx *c, void *dst, const void *src, size_t row, size_t stride, 
     return 0;
 }
 
+// (image slots of the page-locked staging: 16-byte aligned for the copy kernel)
+static size_t pin_stride(const PairSlots &p) { return (p.raw_bytes + 15) & ~(size_t)15; }
+
+int stage_begin(psm_ctx *c, bool pin, int *slot)
+{
+    PairSlots &p = c->pair;
+    if (!c->copy_stream) PSM_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    for (hipEvent_t *e : {&p.ev_up, &p.ev_free})
+        if (!*e) PSM_HIP(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    if (pin && !p.pin_up) PSM_HIP(c, hipHostMalloc((void **)&p.pin_up, 4 * pin_stride(p), hipHostMallocDefault));
+    for (int s = 0; s < 2; ++s)
+        if (!p.raw_next[s]) PSM_HIP(c, hipMalloc(&p.raw_next[s], p.raw_bytes));
+    staged(p.st, -1, false);            // (a pair staged before is given up: raw_next and range slot 1 are about to be overwritten)
+    // two staging slots, used alternately: the host only waits for the copy issued TWO uploads ago (the previous one may still
+    // be queued behind the current frame's kernels - waiting for it would tie the host to the device's pace)
+    *slot = next_slot(p.st);
+    if (!p.ev_stage[*slot]) PSM_HIP(c, hipEventCreateWithFlags(&p.ev_stage[*slot], hipEventDisableTiming));
+    else PSM_HIP(c, hipEventSynchronize(p.ev_stage[*slot]));
+    return 0;
+}
+
+void stage_pack(void *dst, const void *src, size_t row, size_t stride, int rows)
+{
+    if (stride == row) memcpy(dst, src, row * rows);
+    else for (int y = 0; y < rows; ++y) memcpy((uint8_t *)dst + (size_t)y * row, (const uint8_t *)src + (size_t)y * stride, row);
+}
+
+// Small images (Middlebury size: 0.5 MB) travel through a kernel that reads the page-locked slot - submitting a copy-engine
+// transfer behind a stream wait costs 0.2 - 0.4 ms of HOST time on this stack, more than such a pair takes to compute; large
+// ones keep the copy engines, which overlap a 12 MB pair with the filter without taking CU slots (1080p: +0.10 vs +0.27 ms).
+void stage_send(psm_ctx *c, void *dst, const void *pinned, size_t bytes)
+{
+    if (bytes <= PSM_COPY_KERNEL_MAX) launch_copy_bytes(c->copy_stream, dst, pinned, bytes);
+    else (void)hipMemcpyAsync(dst, pinned, bytes, hipMemcpyHostToDevice, c->copy_stream);      // (a failure is the last error the form's check_launch reads)
+}
+
+int stage_commit(psm_ctx *c, int depth, bool range_pending)
+{
+    PSM_HIP(c, hipEventRecord(c->pair.ev_up, c->copy_stream));
+    staged(c->pair.st, depth, range_pending);
+    return 0;
+}
+
+int next_pair_inside(psm_ctx *c, bool *inside)
+{
+    PairState &st = c->pair.st;
+    if (st.range_pending) {             // float images: their range arrived with the copy (long done in a running frame loop)
+        PSM_HIP(c, hipEventSynchronize(c->pair.ev_up));
+        staged(st, st.next_depth, false);
+    }
+    // (range slot 1 is that of the last FLOAT pair staged; 8-bit pairs are always inside)
+    *inside = pair_staged(st) ? st.next_depth != PSM_IMG_F32 || range_inside(c, 1, -PSM_IMG_EXP, PSM_IMG_EXP) : st.inside;
+    return 0;
+}
+
+// the kernels wait for the staged pair's copy on the device
+int adopt_staged_pair(psm_ctx *c)
+{
+    PairSlots &p = c->pair;
+    if (!pair_staged(p.st)) return 0;
+    bool ok = true;
+    if (next_pair_inside(c, &ok)) return 1;
+    PSM_HIP(c, hipStreamWaitEvent(c->stream, p.ev_up, 0));
+    std::swap(p.raw, p.raw_next);
+    adopted(p.st, ok);
+    adopt_new_pair(c);
+    return 0;
+}
+
 }  // namespace psm
 
 extern "C" {
@@ -275,9 +349,9 @@ int psm_create_shard(psm_ctx **out, int width, int height, int max_disp, int d_b
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
     c->stream = c->own_stream;
-    c->raw_bytes = HW * 3 * sizeof(float);
+    c->pair.raw_bytes = HW * 3 * sizeof(float);
     for (int s = 0; s < 2 && e == hipSuccess; ++s) {
-        e = hipMalloc(&c->raw[s], c->raw_bytes);
+        e = hipMalloc(&c->pair.raw[s], c->pair.raw_bytes);
         if (e == hipSuccess) e = hipMalloc((void **)&c->g[s].g1, HW * sizeof(float4));
         if (e == hipSuccess) e = hipMalloc((void **)&c->g[s].g2, HW * sizeof(float4));
         if (e == hipSuccess) e = hipMalloc((void **)&c->g[s].g3, HW * sizeof(float4));
@@ -465,17 +539,14 @@ int psm_upload_pair(psm_ctx *c, const void *l, const void *r, int channels, size
     if (bind(c)) return 1;
     const void *src[2] = {l, r};
     for (int s = 0; s < 2; ++s)
-        if (h2d_rows(c, c->raw[s], src[s], row, stride_bytes, c->H)) return 1;
+        if (h2d_rows(c, c->pair.raw[s], src[s], row, stride_bytes, c->H)) return 1;
     // float images are used as they are: their range decides whether the select forms' scaled window sums apply
     const size_t nf = (size_t)c->W * c->H * 3;
-    if (depth == PSM_IMG_F32 && range_enqueue(c, c->stream, 0, (const float *)c->raw[0], nf, (const float *)c->raw[1], nf)) return 1;
+    if (depth == PSM_IMG_F32 && range_enqueue(c, c->stream, 0, (const float *)c->pair.raw[0], nf, (const float *)c->pair.raw[1], nf)) return 1;
     // the copy reads caller memory: always complete it before returning (CVC_cl::buildCV copies
     // out of the cv::Mats synchronously, src/CVC_cl.cpp:113-160)
     PSM_HIP(c, hipStreamSynchronize(c->stream));
-    c->next_depth = -1;                 // a pair staged by psm_upload_pair_async is superseded
-    c->range_next_pending = false;
-    adopt_new_pair(c, depth);
-    c->img_domain_ok = depth != PSM_IMG_F32 || range_inside(c, 0, -PSM_IMG_EXP, PSM_IMG_EXP);
+    pair_uploaded(c, depth, depth != PSM_IMG_F32 || range_inside(c, 0, -PSM_IMG_EXP, PSM_IMG_EXP));
     return 0;
 }
 
@@ -490,46 +561,21 @@ int psm_upload_pair_async(psm_ctx *c, const void *l, const void *r, int channels
     size_t row = 0;
     if (check_pair_args(c, "psm_upload_pair_async", l, r, channels, &stride_bytes, depth, &row)) return 1;
     if (bind(c)) return 1;
-    const size_t img = row * c->H;
-    if (!c->copy_stream) PSM_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    for (hipEvent_t *e : {&c->ev_up, &c->ev_free})
-        if (!*e) PSM_HIP(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
-    const size_t sstride = (c->raw_bytes + 15) & ~(size_t)15;      // (image slots of the staging memory: 16-byte aligned for the copy kernel)
-    if (!c->pin_up) PSM_HIP(c, hipHostMalloc((void **)&c->pin_up, 4 * sstride, hipHostMallocDefault));
-    for (int s = 0; s < 2; ++s)
-        if (!c->raw_next[s]) PSM_HIP(c, hipMalloc(&c->raw_next[s], c->raw_bytes));
-    // two staging slots, used alternately: the host only waits for the copy issued TWO uploads ago (the previous one may still
-    // be queued behind the current frame's kernels - waiting for it would tie the host to the device's pace)
-    const int slot = c->stage_slot ^= 1;
-    if (!c->ev_stage[slot]) PSM_HIP(c, hipEventCreateWithFlags(&c->ev_stage[slot], hipEventDisableTiming));
-    else PSM_HIP(c, hipEventSynchronize(c->ev_stage[slot]));
-    uint8_t *stage = c->pin_up + (size_t)slot * 2 * sstride;
+    PairSlots &p = c->pair;
+    int slot = 0;
+    if (stage_begin(c, true, &slot)) return 1;
+    const size_t img = row * c->H, sstride = pin_stride(p), nf = (size_t)c->W * c->H * 3;
+    uint8_t *stage = p.pin_up + (size_t)slot * 2 * sstride;
     const void *src[2] = {l, r};
-    for (int s = 0; s < 2; ++s) {
-        uint8_t *dst = stage + s * sstride;
-        if (stride_bytes == row) memcpy(dst, src[s], img);
-        else for (int y = 0; y < c->H; ++y) memcpy(dst + (size_t)y * row, (const uint8_t *)src[s] + (size_t)y * stride_bytes, row);
-    }
-    // raw_next was the current pair two frames ago: its k_prep (recorded as ev_free by psm_cost_construct) must be over
-    PSM_HIP(c, hipStreamWaitEvent(c->copy_stream, c->ev_free, 0));
-    // Small images (Middlebury size: 0.5 MB) travel through a kernel that reads the page-locked slot - submitting a copy-engine
-    // transfer behind a stream wait costs 0.2 - 0.4 ms of HOST time on this stack, more than such a pair takes to compute; large
-    // ones keep the copy engines, which overlap a 12 MB pair with the filter without taking CU slots (1080p: +0.10 vs +0.27 ms).
-    for (int s = 0; s < 2; ++s) {
-        if (img <= PSM_COPY_KERNEL_MAX) launch_copy_bytes(c->copy_stream, c->raw_next[s], stage + s * sstride, img);
-        else PSM_HIP(c, hipMemcpyAsync(c->raw_next[s], stage + s * sstride, img, hipMemcpyHostToDevice, c->copy_stream));
-    }
+    for (int s = 0; s < 2; ++s) stage_pack(stage + s * sstride, src[s], row, stride_bytes, c->H);
+    // raw_next was the current pair two frames ago: the launches that read it (images_read records ev_free behind them) must be over
+    PSM_HIP(c, hipStreamWaitEvent(c->copy_stream, p.ev_free, 0));
+    for (int s = 0; s < 2; ++s) stage_send(c, p.raw_next[s], stage + s * sstride, img);
     if (check_launch(c, "upload (copy kernel)")) return 1;
-    c->range_next_pending = false;
-    if (depth == PSM_IMG_F32) {         // (measured behind the copy on the copy stream; read when the pair is adopted)
-        const size_t nf = (size_t)c->W * c->H * 3;
-        if (range_enqueue(c, c->copy_stream, 1, (const float *)c->raw_next[0], nf, (const float *)c->raw_next[1], nf)) return 1;
-        c->range_next_pending = true;
-    }
-    PSM_HIP(c, hipEventRecord(c->ev_up, c->copy_stream));
-    PSM_HIP(c, hipEventRecord(c->ev_stage[slot], c->copy_stream));
-    c->up_recorded = true;
-    c->next_depth = depth;
+    const bool f32 = depth == PSM_IMG_F32;      // (the range: measured behind the copy on the copy stream; read when the pair is adopted)
+    if (f32 && range_enqueue(c, c->copy_stream, 1, (const float *)p.raw_next[0], nf, (const float *)p.raw_next[1], nf)) return 1;
+    if (stage_commit(c, depth, f32)) return 1;
+    PSM_HIP(c, hipEventRecord(p.ev_stage[slot], c->copy_stream));      // the staging slot is free again once the stream gets here
     return 0;
 }
 

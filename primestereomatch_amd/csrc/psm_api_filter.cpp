@@ -87,19 +87,11 @@ PcPair pc_pair(const psm_ctx *c)
 {
     PcPair p;
     memset(&p, 0, sizeof p);             // (psm_compute_batch compares table entries bytewise)
-    for (int k = 0; k < 2; ++k) { p.raw[k] = c->raw[k]; p.g[k] = c->g[k]; p.p4[k] = c->p4[k]; }
+    for (int k = 0; k < 2; ++k) { p.raw[k] = c->pair.raw[k]; p.g[k] = c->g[k]; p.p4[k] = c->p4[k]; }
     p.scratch = c->gf_scratch;
     p.keys = c->keys_cur;
     p.maps = c->maps;
     return p;
-}
-
-// the launch just made has read the staged images: their slot may be refilled
-static int staged_images_read(psm_ctx *c, const char *what)
-{
-    if (check_launch(c, what)) return 1;
-    if (c->ev_free) PSM_HIP(c, hipEventRecord(c->ev_free, c->stream));
-    return 0;
 }
 
 // Bring g1 (and the 8-bit planes) of the rows g1_need and the guidance g2..g4 of the rows guid_need up to date with the current
@@ -113,14 +105,14 @@ int ensure_planes(psm_ctx *c, Rows g1_need, Rows guid_need)
 {
     const bool need_g1 = !c->g1_rows.covers(g1_need), need_guid = !c->guid_rows.covers(guid_need);
     if (!need_g1 && !need_guid) return 0;
-    const bool f32_img = c->raw_depth == PSM_IMG_F32;
+    const bool f32_img = c->pair.st.depth == PSM_IMG_F32;
     const size_t row = (size_t)c->W * 3 * (f32_img ? 4 : 1);
     if (need_g1 && need_guid && c->dtype == PSM_F32) {
         {
             Prof p(c, PSM_K_GUIDE);
             launch_guidance(c->stream, PcPairs{nullptr, 1, pc_pair(c)}, c->W, c->H, g1_need.y0, g1_need.y1, fma_solve(c), f32_img ? 2 : 1, row);
         }
-        if (staged_images_read(c, "prep + guidance")) return 1;
+        if (check_launch(c, "prep + guidance") || images_read(c, c->stream)) return 1;
         guid_need = g1_need;
     } else {
         if (need_g1) {
@@ -128,14 +120,14 @@ int ensure_planes(psm_ctx *c, Rows g1_need, Rows guid_need)
             const size_t o = (size_t)ya * c->W;
             {   // both images in one launch
                 Prof p(c, PSM_K_PREP);
-                launch_prep(c->stream, (const char *)c->raw[0] + ya * row, row, f32_img, c->W, rows, c->g[0].g1 + o,
-                            (const char *)c->raw[1] + ya * row, c->g[1].g1 + o);
+                launch_prep(c->stream, (const char *)c->pair.raw[0] + ya * row, row, f32_img, c->W, rows, c->g[0].g1 + o,
+                            (const char *)c->pair.raw[1] + ya * row, c->g[1].g1 + o);
             }
             for (int s = 0; s < 2 && c->dtype == PSM_U8; ++s) {
                 Prof p(c, PSM_K_PREP);
-                launch_prep_u8(c->stream, (const uint8_t *)c->raw[s] + ya * row, row, c->W, rows, c->p4[s] + 4 * o, c->g[s].g1 + o);
+                launch_prep_u8(c->stream, (const uint8_t *)c->pair.raw[s] + ya * row, row, c->W, rows, c->p4[s] + 4 * o, c->g[s].g1 + o);
             }
-            if (staged_images_read(c, "prep")) return 1;
+            if (check_launch(c, "prep") || images_read(c, c->stream)) return 1;
         }
         if (need_guid) {
             {
@@ -192,25 +184,6 @@ int enqueue_select(psm_ctx *c, const PcPairs &P, const SelPlan &sp)
         Prof p(c, PSM_K_CVF_F);
         launch_cvf_select_keys2(c->stream, c->march, P, u8, c->W, c->H, sp.n2, c->d0, next_pc_stamp(c), 2, sp.S);
     }
-    return 0;
-}
-
-// the pair psm_upload_pair_async staged becomes the current one: the kernels wait for its copy on the device
-int adopt_staged_pair(psm_ctx *c)
-{
-    if (c->next_depth < 0) return 0;
-    bool ok = true;
-    if (c->range_next_pending) {        // float images: their range arrived with the copy (long done in a running frame loop)
-        PSM_HIP(c, hipEventSynchronize(c->ev_up));
-        ok = range_inside(c, 1, -PSM_IMG_EXP, PSM_IMG_EXP);
-        c->range_next_pending = false;
-    }
-    PSM_HIP(c, hipStreamWaitEvent(c->stream, c->ev_up, 0));
-    std::swap(c->raw[0], c->raw_next[0]);
-    std::swap(c->raw[1], c->raw_next[1]);
-    adopt_new_pair(c, c->next_depth);
-    c->img_domain_ok = ok;
-    c->next_depth = -1;
     return 0;
 }
 

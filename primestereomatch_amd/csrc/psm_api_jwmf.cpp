@@ -147,8 +147,8 @@ int jw_enqueue(const char *who, bool single, psm_ctx *const *ctxs, int n, int ra
             return fail(c0, "%s: %s has another width / height / device than context 0", who, at.c_str());
         if (!c->res.maps) return fail(c0, "%s: %s has no disparity maps", who, at.c_str());
         if (stripe_only(c)) return fail(c0, "%s: the maps of %s hold its row stripe only (gather the stripes first)", who, at.c_str());
-        if (!c->have_images || c->raw_depth < 0) return fail(c0, "%s: %s has no image pair uploaded (the feature images)", who, at.c_str());
-        if (c->raw_depth != c0->raw_depth) return fail(c0, "%s: %s holds images of another depth than context 0", who, at.c_str());
+        if (!c->have_images || c->pair.st.depth < 0) return fail(c0, "%s: %s has no image pair uploaded (the feature images)", who, at.c_str());
+        if (c->pair.st.depth != c0->pair.st.depth) return fail(c0, "%s: %s holds images of another depth than context 0", who, at.c_str());
     }
     if (bind(c0)) return 1;
     hipStream_t s = c0->stream;
@@ -187,11 +187,11 @@ int jw_enqueue(const char *who, bool single, psm_ctx *const *ctxs, int n, int ra
             psm_ctx *c = ctxs[i];
             const JwClust &cl = c->jw_cl[k];
             const JwScratch &q = sc[2 * (size_t)i + k];
-            sides.push_back(JwSide{c->raw[k], q.lok, q.F, c->maps + k * HW, q.wq, q.out});
+            sides.push_back(JwSide{c->pair.raw[k], q.lok, q.F, c->maps + k * HW, q.wq, q.out});
             if (cl.user || (cl.have && cl.n_clusters == n_clusters && cl.max_iter == max_iter)) continue;
             const size_t j = mem.size();
             mem.push_back(Member{c, k});
-            img.push_back(JwImg{c->raw[k], q.bits, q.samples, q.kt, q.d2t, q.labels, q.sums, st_dev + 4 * j, cen_dev + j * JW_NF_MAX * 3, q.lok, 0, 0});
+            img.push_back(JwImg{c->pair.raw[k], q.bits, q.samples, q.kt, q.d2t, q.labels, q.sums, st_dev + 4 * j, cen_dev + j * JW_NF_MAX * 3, q.lok, 0, 0});
         }
     const int m = (int)mem.size();
     std::vector<uint8_t> recs;
@@ -216,7 +216,7 @@ int jw_enqueue(const char *who, bool single, psm_ctx *const *ctxs, int n, int ra
         {
             Prof p(c0, PSM_K_JWMF);
             PSM_HIP(c0, hipMemsetAsync(st_dev, 0, (size_t)m * ST, s));
-            launch_jw_keys(s, im, c0->raw_depth, HW);
+            launch_jw_keys(s, im, c0->pair.st.depth, HW);
             launch_jw_compact(s, im);
         }
         if (launched("keys")) return 1;
@@ -276,10 +276,13 @@ int jw_enqueue(const char *who, bool single, psm_ctx *const *ctxs, int n, int ra
         if (upload_tables(c0, ctxs[i], &sc[2 * (size_t)i], sigma, s)) return 1;
     {
         Prof p(c0, PSM_K_JWMF);
-        launch_jw_plane(s, sd, c0->raw_depth, HW);
+        launch_jw_plane(s, sd, c0->pair.st.depth, HW);
         launch_jw_median(s, sd, c0->W, c0->H, radius);
     }
     if (launched("median")) return 1;
+    // (the feature images are the image slots: the keys and the cluster planes are formed from them, the median reads the planes)
+    for (int i = 0; i < n; ++i)
+        if (images_read(ctxs[i], s)) return member_failed(c0, who, i, ctxs[i]);
     for (size_t q = 0; q < NS; ++q)
         PSM_HIP(c0, hipMemcpyAsync(ctxs[q / 2]->maps + (q & 1) * HW, sc[q].out, HW, hipMemcpyDeviceToDevice, s));
     for (int i = 0; i < n; ++i) forget_early(ctxs[i]->res);        // (rewritten in place)

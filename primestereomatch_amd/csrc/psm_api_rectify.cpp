@@ -195,12 +195,9 @@ int psm_upload_pair_rectified(psm_ctx *c, const void *l, const void *r, int chan
     const void *src[2] = {l, r};
     for (int s = 0; s < 2; ++s)
         if (h2d_rows(c, c->rect_src[0] + s * eye, src[s], row, stride_bytes, c->rect_src_h[0])) return 1;
-    if (enqueue_rectify(c, c->stream, c->rect_src[0], eye, c->raw)) return 1;
+    if (enqueue_rectify(c, c->stream, c->rect_src[0], eye, c->pair.raw)) return 1;
     PSM_HIP(c, hipStreamSynchronize(c->stream));      // the copy reads caller memory (psm_upload_pair)
-    c->next_depth = -1;
-    c->range_next_pending = false;
-    adopt_new_pair(c, PSM_IMG_U8);
-    c->img_domain_ok = true;
+    pair_uploaded(c, PSM_IMG_U8, true);
     return 0;
 }
 
@@ -214,35 +211,19 @@ int psm_upload_pair_rectified_async(psm_ctx *c, const void *l, const void *r, in
     if (check_rect_args(c, "psm_upload_pair_rectified_async", l, r, channels, &stride_bytes, &row, &eye)) return 1;
     if (bind(c)) return 1;
     if (ensure_src(c, eye, true)) return 1;
-    if (!c->copy_stream) PSM_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    for (hipEvent_t *e : {&c->ev_up, &c->ev_free})
-        if (!*e) PSM_HIP(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
-    for (int s = 0; s < 2; ++s)
-        if (!c->raw_next[s]) PSM_HIP(c, hipMalloc(&c->raw_next[s], c->raw_bytes));
-    const int slot = c->stage_slot ^= 1;              // (the slots and their events are those of psm_upload_pair_async)
-    if (!c->ev_stage[slot]) PSM_HIP(c, hipEventCreateWithFlags(&c->ev_stage[slot], hipEventDisableTiming));
-    else PSM_HIP(c, hipEventSynchronize(c->ev_stage[slot]));
+    int slot = 0;
+    if (stage_begin(c, false, &slot)) return 1;
     uint8_t *stage = c->rect_pin + (size_t)slot * 2 * eye;
     const void *src[2] = {l, r};
-    const int src_h = c->rect_src_h[0];
-    for (int s = 0; s < 2; ++s) {
-        uint8_t *dst = stage + s * eye;
-        if (stride_bytes == row) memcpy(dst, src[s], row * src_h);
-        else for (int y = 0; y < src_h; ++y) memcpy(dst + (size_t)y * row, (const uint8_t *)src[s] + (size_t)y * stride_bytes, row);
-    }
-    if (2 * eye <= PSM_COPY_KERNEL_MAX) launch_copy_bytes(c->copy_stream, c->rect_src[slot], stage, 2 * eye);      // both eyes, one copy
-    else PSM_HIP(c, hipMemcpyAsync(c->rect_src[slot], stage, 2 * eye, hipMemcpyHostToDevice, c->copy_stream));
+    for (int s = 0; s < 2; ++s) stage_pack(stage + s * eye, src[s], row, stride_bytes, c->rect_src_h[0]);
+    stage_send(c, c->rect_src[slot], stage, 2 * eye);                        // both eyes, one copy
     if (check_launch(c, "upload (copy kernel)")) return 1;
-    PSM_HIP(c, hipEventRecord(c->ev_stage[slot], c->copy_stream));           // the staging slot is free again once the copy is over
-    // raw_next was the current pair two frames ago: its k_prep (recorded as ev_free by psm_cost_construct) must be over before the
-    // kernel writes there (the copy above touches the source slot only and need not wait)
-    PSM_HIP(c, hipStreamWaitEvent(c->copy_stream, c->ev_free, 0));
-    if (enqueue_rectify(c, c->copy_stream, c->rect_src[slot], eye, c->raw_next)) return 1;
-    c->range_next_pending = false;
-    PSM_HIP(c, hipEventRecord(c->ev_up, c->copy_stream));
-    c->up_recorded = true;
-    c->next_depth = PSM_IMG_U8;
-    return 0;
+    PSM_HIP(c, hipEventRecord(c->pair.ev_stage[slot], c->copy_stream));            // the staging slot is free again once the copy is over
+    // raw_next was the current pair two frames ago: the launches that read it (images_read records ev_free behind them) must be over
+    // before the kernel writes there (the copy above touches the source slot only and need not wait)
+    PSM_HIP(c, hipStreamWaitEvent(c->copy_stream, c->pair.ev_free, 0));
+    if (enqueue_rectify(c, c->copy_stream, c->rect_src[slot], eye, c->pair.raw_next)) return 1;
+    return stage_commit(c, PSM_IMG_U8, false);
 }
 
 int psm_download_images(psm_ctx *c, uint8_t *l, uint8_t *r, size_t stride_bytes)
@@ -250,25 +231,12 @@ int psm_download_images(psm_ctx *c, uint8_t *l, uint8_t *r, size_t stride_bytes)
     if (!c) return 1;
     if (!l || !r) return fail(c, "psm_download_images: NULL image");
     if (!c->have_images) return fail(c, "psm_download_images: no current image pair (a staged pair becomes current in psm_cost_construct)");
-    if (c->raw_depth != PSM_IMG_U8) return fail(c, "psm_download_images: the current pair is a float pair (8-bit pairs only)");
+    if (c->pair.st.depth != PSM_IMG_U8) return fail(c, "psm_download_images: the current pair is a float pair (8-bit pairs only)");
     const size_t row = (size_t)c->W * 3;
     if (stride_bytes == 0) stride_bytes = row;
     if (stride_bytes < row) return fail(c, "psm_download_images: stride %zu < row size %zu", stride_bytes, row);
     if (bind(c)) return 1;
-    uint8_t *dst[2] = {l, r};
-    std::vector<uint8_t> packed;
-    for (int s = 0; s < 2; ++s) {
-        if (stride_bytes == row) {
-            PSM_HIP(c, hipMemcpyAsync(dst[s], c->raw[s], row * c->H, hipMemcpyDeviceToHost, c->stream));
-            PSM_HIP(c, hipStreamSynchronize(c->stream));
-        } else {
-            packed.resize(row * c->H);
-            PSM_HIP(c, hipMemcpyAsync(packed.data(), c->raw[s], row * c->H, hipMemcpyDeviceToHost, c->stream));
-            PSM_HIP(c, hipStreamSynchronize(c->stream));
-            for (int y = 0; y < c->H; ++y) memcpy(dst[s] + (size_t)y * stride_bytes, packed.data() + (size_t)y * row, row);
-        }
-    }
-    return 0;
+    return d2h_rows(c, l, c->pair.raw[0], row, stride_bytes, c->H) || d2h_rows(c, r, c->pair.raw[1], row, stride_bytes, c->H);
 }
 
 }  // extern "C"

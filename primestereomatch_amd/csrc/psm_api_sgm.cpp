@@ -223,7 +223,10 @@ void mark(SgmState &g, SgmCost kind, int ch, int dmin, int D, bool timed)
 //   - psm_sgm_compute_gray comes with ch 1 in `a`, which has also resolved its P1 / P2 defaults (check_params);
 //   - a batch reports a member's allocation failure on its first context, as "...: context i: <the member's message>" - by its
 //     caller, as every check and allocation: nothing here can fail but a launch or an event.
-int enqueue(psm_ctx *c, hipStream_t s, SgmArgs a, const SgmPair *one, const SgmPair *tab, int n)
+// readers: the n contexts whose image slots the pairs are (null: psm_sgm_compute_gray's own planes) - behind the launches, outside
+// the brackets of psm_sgm_times, each records that its images have been read (the cost group reads them; the paths, the select
+// and the speckle filter read C, S and the maps).
+int enqueue(psm_ctx *c, hipStream_t s, SgmArgs a, const SgmPair *one, const SgmPair *tab, int n, psm_ctx *const *readers)
 {
     static const char *const cost_kernels[3][2] = {{"k_sgm_cost", "k_sgm_fill_b, k_sgm_cost_b"},
                                                    {"k_sgm_prefilter, k_sgm_bt_*", "k_sgm_fill_b, k_sgm_prefilter_b, k_sgm_bt_*_b"},
@@ -264,6 +267,8 @@ int enqueue(psm_ctx *c, hipStream_t s, SgmArgs a, const SgmPair *one, const SgmP
         if (one) { k.map = one->out; k.label = one->spk_label; k.size = one->spk_size; }
         if (enqueue_speckle(c, s, k, tab, n, timed)) return 1;
     }
+    for (int i = 0; readers && i < n; ++i)
+        if (images_read(readers[i], s)) return member_failed(c, "the SGM stage", i, readers[i]);
     return 0;
 }
 
@@ -271,7 +276,7 @@ int enqueue(psm_ctx *c, hipStream_t s, SgmArgs a, const SgmPair *one, const SgmP
 std::vector<SgmPair> pairs_of(psm_ctx *const *ctxs, int n)
 {
     std::vector<SgmPair> tab((size_t)n);
-    for (int i = 0; i < n; ++i) tab[i] = pair_of(ctxs[i], ctxs[i]->raw[0], ctxs[i]->raw[1]);
+    for (int i = 0; i < n; ++i) tab[i] = pair_of(ctxs[i], ctxs[i]->pair.raw[0], ctxs[i]->pair.raw[1]);
     return tab;
 }
 
@@ -311,8 +316,9 @@ void maps_selected(psm_ctx *c)
     maps_written(c->res);
 }
 
-// a single pair of `ch` channels through the stage on the context's stream (psm_sgm_compute, psm_sgm_compute_gray)
-int compute_one(psm_ctx *c, const char *who, const void *l, const void *r, int depth, int ch)
+// a single pair of `ch` channels through the stage on the context's stream (psm_sgm_compute: the context's image slots;
+// psm_sgm_compute_gray: planes of its own)
+int compute_one(psm_ctx *c, const char *who, const void *l, const void *r, int depth, int ch, bool slots)
 {
     SgmState &g = c->sgm;
     int p1 = g.p1, p2 = g.p2;
@@ -321,7 +327,7 @@ int compute_one(psm_ctx *c, const char *who, const void *l, const void *r, int d
     const SgmArgs a = sgm_args(c, depth, ch, p1, p2);
     const SgmPair p = pair_of(c, l, r);
     forget(g);
-    if (enqueue(c, c->stream, a, &p, nullptr, 1)) return 1;
+    if (enqueue(c, c->stream, a, &p, nullptr, 1, slots ? &c : nullptr)) return 1;
     mark(g, cost_kind(g), ch, a.dmin, a.D, c->opt_profile != 0);
     if (!c->opt_async) PSM_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
@@ -398,9 +404,10 @@ int psm_sgm_compute(psm_ctx *c)
 {
     if (!c) return 1;
     if (check_ctx(c, c, "psm_sgm_compute") || check_cost(c, c, "psm_sgm_compute")) return 1;
-    if (c->raw_depth < 0) return fail(c, "psm_sgm_compute: no image pair (psm_upload_pair)");
+    const PairSlots &p = c->pair;
+    if (p.st.depth < 0) return fail(c, "psm_sgm_compute: no image pair (psm_upload_pair)");
     if (bind(c)) return 1;
-    return compute_one(c, "psm_sgm_compute", c->raw[0], c->raw[1], c->raw_depth, 3);
+    return compute_one(c, "psm_sgm_compute", p.raw[0], p.raw[1], p.st.depth, 3, true);
 }
 
 int psm_sgm_compute_gray(psm_ctx *c, const uint8_t *l, const uint8_t *r, size_t stride_bytes)
@@ -419,7 +426,7 @@ int psm_sgm_compute_gray(psm_ctx *c, const uint8_t *l, const uint8_t *r, size_t 
         if (h2d_rows(c, g.gray[s], src[s], row, stride_bytes, c->H)) return 1;
     }
     PSM_HIP(c, hipStreamSynchronize(c->stream));      // the copy reads caller memory (psm_upload_pair)
-    return compute_one(c, "psm_sgm_compute_gray", g.gray[0], g.gray[1], PSM_IMG_U8, 1);
+    return compute_one(c, "psm_sgm_compute_gray", g.gray[0], g.gray[1], PSM_IMG_U8, 1, false);
 }
 
 // The launches of psm_sgm_compute with the pair on a grid axis of its own: n x (H, W or W + H - 1) one-wave paths per path launch
@@ -440,8 +447,8 @@ int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
         char member[64];
         snprintf(member, sizeof member, "%s: context %d", who, i);
         if (check_ctx(c0, c, member) || check_cost(c0, c, member)) return 1;
-        if (c->raw_depth < 0) return fail(c0, "%s: context %d has no image pair (psm_upload_pair)", who, i);
-        if (c->raw_depth != c0->raw_depth) return fail(c0, "%s: context %d holds images of another depth than context 0", who, i);
+        if (c->pair.st.depth < 0) return fail(c0, "%s: context %d has no image pair (psm_upload_pair)", who, i);
+        if (c->pair.st.depth != c0->pair.st.depth) return fail(c0, "%s: context %d holds images of another depth than context 0", who, i);
         const SgmState &g = c->sgm;
         if (g.bs != g0.bs || g.p1 != g0.p1 || g.p2 != g0.p2 || g.u != g0.u || g.m != g0.m)
             return fail(c0, "%s: context %d has other parameters (psm_sgm_set_params) than context 0", who, i);
@@ -475,9 +482,9 @@ int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
     if (fresh && table_upload(c0, t, tab.data(), tab.size() * sizeof(SgmPair))) return 1;
 
     // ---- the launches; then every context is where its own psm_sgm_compute would have left it - only context 0 counts as timed ----
-    const SgmArgs a = sgm_args(c0, c0->raw_depth, 3, p1, p2);
+    const SgmArgs a = sgm_args(c0, c0->pair.st.depth, 3, p1, p2);
     for (int i = 0; i < n; ++i) forget(ctxs[i]->sgm);
-    if (enqueue(c0, s, a, nullptr, (const SgmPair *)t.dev, n)) return 1;
+    if (enqueue(c0, s, a, nullptr, (const SgmPair *)t.dev, n, ctxs)) return 1;
     if (batch_fork(c0, ctxs, n)) return 1;
     for (int i = 0; i < n; ++i) mark(ctxs[i]->sgm, cost_kind(g0), 3, a.dmin, a.D, i == 0 && c0->opt_profile != 0);
     if (!c0->opt_async) PSM_HIP(c0, hipStreamSynchronize(s));

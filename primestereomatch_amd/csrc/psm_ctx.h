@@ -1,6 +1,7 @@
 // psm_ctx.h - the context behind the C ABI of libprimesm_hip.so (include/primesm_hip.h) and the helpers its
 // translation units share.  Internal to the library:
-//   psm_api_core.cpp    context life cycle, options, uploads / downloads, timers
+//   psm_api_core.cpp    context life cycle, options, uploads / downloads, timers; the image pair slots (psm::PairSlots): the
+//                       staging steps of the asynchronous uploads, adoption of the staged pair, the mark that the images were read
 //   psm_api_filter.cpp  CostConst / CostFilter: which plane rows are current (ensure_planes), what is built lazily, which form
 //                       of the fused kernel runs, materialisation
 //   psm_api_select.cpp  DispSelect: maps, packed minima, row stripes and disparity shards
@@ -18,8 +19,8 @@
 //                       results of several contexts in shared launches (psm_score_batch)
 // Takes the place of the reference's oclUtil + CVC_cl / CVF_cl / DispSel_cl host wrappers
 // (src/oclUtil.cpp, src/CVC_cl.cpp, src/CVF_cl.cpp, src/DispSel_cl.cpp).
-// What a context knows about its volumes and results between calls - psm::VolSide per side, psm::Results - lives in psm_state.h
-// with the only functions that change it.
+// What a context knows about its volumes, results and image pairs between calls - psm::VolSide per side, psm::Results,
+// psm::PairState - lives in psm_state.h with the only functions that change it.
 #pragma once
 #include "../../include/primesm_hip.h"
 #include "psm_kernels.h"
@@ -149,6 +150,21 @@ struct ScoreState {
     bool timed = false;
     DevTable tab;                                  // psm_score_batch (this context as the first of a batch): ScPair records
 };
+
+// The image pair every frame starts with, and the second slot the next frame travels into (psm_upload_pair_async,
+// psm_upload_pair_rectified_async).  `st` is changed by its transitions (psm_state.h) alone, the rest by the functions declared
+// under "the image pair slots" below.
+struct PairSlots {
+    PairState st;
+    void *raw[2] = {nullptr, nullptr};             // the current pair: the interleaved host images, raw_bytes each
+    void *raw_next[2] = {nullptr, nullptr};        // the slot a staged pair travels into (swapped with raw when adopted), on first use
+    size_t raw_bytes = 0;
+    uint8_t *pin_up = nullptr;                     // page-locked staging of the plain asynchronous form (2 slots x 2 images, used alternately), on first use
+    hipEvent_t ev_stage[2] = {nullptr, nullptr};   // the copy out of staging slot st.slot (pin_up's or rect_pin's) has executed: the host may refill it
+    // ev_up: the staged pair is complete in raw_next; ev_free: recorded behind every launch sequence that reads raw (images_read) -
+    // what the copy stream waits for before it overwrites raw_next, the current pair of two frames ago
+    hipEvent_t ev_up = nullptr, ev_free = nullptr;
+};
 }  // namespace psm
 
 struct psm_ctx {
@@ -158,18 +174,10 @@ struct psm_ctx {
     hipStream_t copy_stream = nullptr;  // psm_upload_pair_async / psm_download_maps_async: PCIe legs next to the kernels
     hipStream_t down_stream = nullptr;  // ... the D2H leg's stream: copy_stream unless the context shares a StreamSet
     psm::StreamSet *shared = nullptr;   // psm_share_streams
-    hipEvent_t ev_up = nullptr, ev_maps = nullptr, ev_down = nullptr, ev_free = nullptr;
+    hipEvent_t ev_maps = nullptr, ev_down = nullptr;
 
     // device memory (DESIGN.md "HBM layout")
-    void *raw[2] = {nullptr, nullptr};  // staged copy of the interleaved host images
-    void *raw_next[2] = {nullptr, nullptr};   // second image slot (psm_upload_pair_async), allocated on first use
-    uint8_t *pin_up = nullptr;          // page-locked staging of the next pair (2 slots x 2 images, used alternately), on first use
-    hipEvent_t ev_stage[2] = {nullptr, nullptr};   // ... the H2D copy out of a slot has executed (the host may refill it)
-    int stage_slot = 0;
-    int next_depth = -1;                // PSM_IMG_* of the pair in raw_next (-1: none pending)
-    bool up_recorded = false;           // ev_up has been recorded at least once
-    size_t raw_bytes = 0;
-    int raw_depth = -1;                 // PSM_IMG_* of the staged pair, -1 = nothing uploaded
+    psm::PairSlots pair;                // the staged image pair, the slot of the next one and their events
     psm::Guidance g[2] = {};
     void *vol[2] = {nullptr, nullptr};  // [Dloc][H][W] float (PSM_F32) or uint8 (PSM_U8)
     float *fvol = nullptr;              // PSM_U8 only: float work volume of one side
@@ -239,10 +247,10 @@ struct psm_ctx {
     // end: bit-identical to the per-sum scaling only while no intermediate under- or overflows).  8-bit images are always
     // inside; float images (non-zero |I| within 2^-10 .. 2^10) and uploaded cost volumes (2^-60 .. 2^60) are measured on the
     // device when they arrive; outside, psm_cost_filter runs the storing form (the oracle's arithmetic op for op) + k_wta.
-    bool img_domain_ok = true, img_next_domain_ok = true, vol_domain_ok[2] = {true, true};
+    // (The images' answer is pair.st.inside.)
+    bool vol_domain_ok[2] = {true, true};
     unsigned *range_dev = nullptr;      // [4][2] exponent ranges (current pair, staged pair, volume L, volume R), on first use
     unsigned *range_pin = nullptr;      // page-locked copy
-    bool range_next_pending = false;    // the staged pair's range is still on its way (read when the pair is adopted)
 
     // options
     int opt_async = 0, opt_variant = 0, opt_profile = 0, opt_graph = 0, opt_gather_staged = 0;
@@ -269,7 +277,6 @@ hipEvent_t get_event(psm_ctx *c);
 int check_launch(psm_ctx *c, const char *what);
 int end_stage(psm_ctx *c, int stage, double t0);
 int bind(psm_ctx *c);
-void adopt_new_pair(psm_ctx *c, int depth);   // a new image pair is current: nothing derived from the previous one survives
 inline size_t velem(const psm_ctx *c) { return c->dtype == PSM_U8 ? 1 : 4; }
 // Call before anything on c->stream writes c->maps: the buffer may still be the source of an asynchronous download
 // (psm_download_maps_async on the copy stream) - the writer waits for that copy on the device, the host never blocks.
@@ -318,6 +325,36 @@ inline int d2h_rows(psm_ctx *c, void *dst, const void *src, size_t row, size_t s
     return 0;
 }
 
+// psm_api_core.cpp: the image pair slots (psm::PairSlots)
+void pair_slots_free(psm_ctx *c);
+void adopt_new_pair(psm_ctx *c);                 // a new image pair is current: nothing derived from the previous one survives
+// a blocking upload has filled raw: it supersedes a staged pair, adopts the new one and sets the domain flag
+inline void pair_uploaded(psm_ctx *c, int depth, bool inside) { uploaded(c->pair.st, depth, inside); adopt_new_pair(c); }
+// The staging sequence of the two asynchronous forms, all on the copy stream.  They differ in where they record ev_stage[slot]
+// relative to their wait for ev_free, and in what runs between send and commit.
+//   begin:  a pair staged before is given up (raw_next is about to be overwritten); copy stream, ev_up, ev_free, (pin: pin_up,)
+//           raw_next - each on first use; the next staging slot; its event is created, or waited for on the host: the copy out of
+//           the slot issued TWO uploads ago is over
+//   pack:   the caller's rows into a page-locked destination
+//   send:   `bytes` from a page-locked source to the device - up to PSM_COPY_KERNEL_MAX by the copy kernel, else by a copy engine
+//           (the form checks the launch)
+//   commit: ev_up behind what the form enqueued; the pair is staged
+int stage_begin(psm_ctx *c, bool pin, int *slot);
+void stage_pack(void *dst, const void *src, size_t row, size_t stride, int rows);
+void stage_send(psm_ctx *c, void *dst, const void *pinned, size_t bytes);
+int stage_commit(psm_ctx *c, int depth, bool range_pending);
+// Is the pair the next psm_cost_construct will find - the staged one, else the current one - inside the select forms' domain?  Waits
+// on the host for a range still on its way; asking again is free.
+int next_pair_inside(psm_ctx *c, bool *inside);
+int adopt_staged_pair(psm_ctx *c);               // the staged pair becomes the current one (psm_cost_construct, psm_compute_batch)
+// Behind the last launch of a sequence on stream s that reads c's raw: the slot may be overwritten once the stream gets here.  A
+// context that never uploaded asynchronously has no ev_free and records nothing.
+inline int images_read(psm_ctx *c, hipStream_t s)
+{
+    if (c->pair.ev_free) PSM_HIP(c, hipEventRecord(c->pair.ev_free, s));
+    return 0;
+}
+
 // The plane rows a filter reads: the whole image, or - a psm_set_rows stripe [y0, y1) being in force - what the select form of
 // the fused kernel touches for it: the guidance of the model rows y0 - 4 .. y1 + 2 (rounded to +- 4), and the image planes of
 // the rows y0 - 8 .. y1 + 7 (the costs of those model rows, +- 4 for their box sums, and their guidance).
@@ -338,7 +375,6 @@ int ensure_ab(psm_ctx *c);
 int ensure_spare(psm_ctx *c);
 int fgf_flush(psm_ctx *c, int side);
 int materialize(psm_ctx *c, int side);
-int adopt_staged_pair(psm_ctx *c);               // the pair psm_upload_pair_async staged becomes the current one
 int ensure_gf_scratch(psm_ctx *c, size_t bytes);
 // The select path of the default product path - fused select filter of both volumes, reduction - for one pair (psm_cost_filter)
 // or the pairs of a batch (psm_compute_batch)
@@ -351,9 +387,6 @@ struct SelPlan {
 };
 SelPlan select_plan(const psm_ctx *c, int npairs, bool batch);
 int enqueue_select(psm_ctx *c, const PcPairs &P, const SelPlan &sp);
-// psm_api_core.cpp: measure the exponent range of n floats on `stream` into slot (0..3) of the context's range buffers
-int range_enqueue(psm_ctx *c, hipStream_t stream, int slot, const float *p0, size_t n0, const float *p1, size_t n1);
-bool range_inside(const psm_ctx *c, int slot, int lo_exp, int hi_exp);     // after the stream has been synchronised
 // PSM_FLAG_FMA_SOLVE applies to float mode only (8-bit contexts never carry the bit: psm_set_option)
 inline bool fma_solve(const psm_ctx *c) { return c->dtype == PSM_F32 && (c->march.flags & PSM_FLAG_FMA_SOLVE) != 0; }
 // psm_create_shard_strided: the slices of such a context exist in the select forms of the fused kernel only
@@ -362,7 +395,7 @@ inline bool strided(const psm_ctx *c) { return c->march.dstep != 1; }
     do {                                                                                                                        \
         if (psm::strided(c)) return psm::fail((c), "%s: a strided disparity shard (psm_create_shard_strided) runs the default select path only", (what)); \
     } while (0)
-inline bool scaled_forms_ok(const psm_ctx *c) { return c->img_domain_ok && c->vol_domain_ok[0] && c->vol_domain_ok[1]; }
+inline bool scaled_forms_ok(const psm_ctx *c) { return c->pair.st.inside && c->vol_domain_ok[0] && c->vol_domain_ok[1]; }
 constexpr int PSM_IMG_EXP = 10, PSM_VOL_EXP = 60;
 constexpr size_t PSM_COPY_KERNEL_MAX = (size_t)2 << 20;     // asynchronous PCIe legs up to this size go through k_copy16 instead of the copy engines
 unsigned long long *next_pc_stamp(psm_ctx *c);   // slot of the next k_cvf_pc launch (NULL unless PSM_OPT_PROFILE 2)

@@ -1,5 +1,5 @@
-// psm_state.h - what a context (psm_ctx.h) remembers between two calls of the C ABI about its cost volumes and its results: two
-// plain records, the questions the entry points ask of them and the only functions that change them.  Nothing of HIP in here: it
+// psm_state.h - what a context (psm_ctx.h) remembers between two calls of the C ABI about its cost volumes, its results and its image
+// pairs: plain records, the questions the entry points ask of them and the only functions that change them.  Nothing of HIP in here: it
 // compiles with the host compiler alone (tests/test_ctx_state.py walks the transitions that way).
 #pragma once
 #include <cstdint>
@@ -67,5 +67,22 @@ inline void mask_written(Results &r) { r.mask = r.maps; }
 inline bool take_early(Results &r, const uint8_t *maps) { const bool hit = r.early == maps; r.early = nullptr; return hit; }
 inline void keys_complete(Results &r, int side) { r.keys[side] = true; }
 inline void keys_gone(Results &r) { r.keys[0] = r.keys[1] = false; }
+
+// ---- The image pair and the one on its way ----
+// The bookkeeping of psm::PairSlots (psm_ctx.h) that needs no device.  Depths are PSM_IMG_* (-1: no such pair).  The staged pair
+// lies in the second image slot until the next psm_cost_construct adopts it; a blocking upload in between supersedes it.
+// depth, next_depth: of the current pair / of the staged one; slot: the page-locked staging slot the last asynchronous upload filled;
+// range_pending: the staged pair's measured range is still on its way (float pairs); inside: the current pair lies inside the select
+// forms' domain (psm_ctx.h: scaled_forms_ok).
+struct PairState {
+    int depth = -1, next_depth = -1, slot = 0;
+    bool range_pending = false, inside = true;
+};
+inline bool pair_staged(const PairState &p) { return p.next_depth >= 0; }
+inline int depth_at_construct(const PairState &p) { return pair_staged(p) ? p.next_depth : p.depth; }   // ... the next psm_cost_construct will find
+inline int next_slot(PairState &p) { return p.slot ^= 1; }                                              // 1, 0, 1, ...
+inline void uploaded(PairState &p, int depth, bool inside) { p.depth = depth; p.inside = inside; p.next_depth = -1; p.range_pending = false; }   // blocking
+inline void staged(PairState &p, int depth, bool range_pending) { p.next_depth = depth; p.range_pending = range_pending; }   // replaces a pair staged before; (-1, false): gives it up; (its depth, false): its range has arrived
+inline void adopted(PairState &p, bool inside) { if (pair_staged(p)) uploaded(p, p.next_depth, inside); }   // nothing staged: nothing happens
 
 }  // namespace psm

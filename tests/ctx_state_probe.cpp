@@ -64,4 +64,47 @@ void rows_across_foreign_maps(int fy0, int fy1, int cy0, int cy1, int *y)
 
 int rows_whole(int H, int y0, int y1) { return Rows{y0, y1} == whole_image(H); }
 
+// One transition of the image pair's bookkeeping.  st = {depth, next depth, slot, range pending, inside} in and out; returns the
+// slot (op 3), else the answers: bit 0 a pair is staged, from bit 1 on the depth at the next construct + 1.
+int pair_step(int *st, int op, int a, int b)
+{
+    PairState p;
+    p.depth = st[0]; p.next_depth = st[1]; p.slot = st[2]; p.range_pending = st[3] != 0; p.inside = st[4] != 0;
+    int slot = -1;
+    switch (op) {
+    case 0: uploaded(p, a, b != 0); break;
+    case 1: staged(p, a, b != 0); break;
+    case 2: adopted(p, a != 0); break;
+    case 3: slot = next_slot(p); break;
+    case 4: staged(p, p.next_depth, false); break;       // its range has arrived
+    case 5: p = PairState{}; break;       // a new record
+    default: break;                       // (the questions of the state as it is)
+    }
+    st[0] = p.depth; st[1] = p.next_depth; st[2] = p.slot; st[3] = p.range_pending; st[4] = p.inside;
+    return op == 3 ? slot : (int)pair_staged(p) | (depth_at_construct(p) + 1) << 1;
+}
+
 }  // extern "C"
+
+#ifdef PROBE_MAIN
+// The same records walked natively, for a build under -fsanitize=address,undefined (tests/test_ctx_state.py runs it): every move of
+// every record from every state a short random walk reaches.  Prints the number of steps; a sanitizer report fails the run.
+#include <cstdio>
+
+int main()
+{
+    unsigned seed = 12345u, steps = 0;
+    auto rnd = [&](unsigned n) { seed = seed * 1664525u + 1013904223u; return (int)((seed >> 8) % n); };
+    int side[3] = {0, 0, 0}, res[7] = {0, 0, 0, 0, 0, 0, 0}, pair[5] = {-1, -1, 0, 0, 1}, y[4];
+    for (int i = 0; i < 20000; ++i, steps += 3) {
+        side_step(side, rnd(6), 2 << rnd(3));
+        const int y0 = rnd(60), op = rnd(11);
+        res_step(res, op, op == 8 ? rnd(2) : y0, y0 + 1 + rnd(60 - y0), rnd(3));
+        pair_step(pair, rnd(7), rnd(2), rnd(2));
+        if (pair[2] != 0 && pair[2] != 1) return 1;       // (the slot indexes two events and two halves of the staging memory)
+    }
+    rows_across_foreign_maps(20, 40, 0, 60, y);
+    printf("%u steps, rows %d %d %d %d, whole %d\n", steps, y[0], y[1], y[2], y[3], rows_whole(60, 0, 60));
+    return 0;
+}
+#endif

@@ -1,6 +1,8 @@
-"""The two records a context keeps between calls of the C ABI (primestereomatch_amd/csrc/psm_state.h: what stands for a volume
-side, what the current results are) walked without a context or a device: tests/ctx_state_probe.cpp puts their transitions behind
-ctypes and is built here with the host compiler - the header includes nothing of HIP."""
+"""The records a context keeps between calls of the C ABI (primestereomatch_amd/csrc/psm_state.h: what stands for a volume side,
+what the current results are, which image pair is current and which is on its way) walked without a context or a device:
+tests/ctx_state_probe.cpp puts their transitions behind ctypes and is built here with the host compiler - the header includes nothing
+of HIP.  The same file with its own main is also built as a stand-alone program under AddressSanitizer and
+UndefinedBehaviorSanitizer and run."""
 import ctypes
 import itertools
 import os
@@ -120,4 +122,93 @@ def test_pending_minima_keep_their_rows_across_foreign_maps(probe):
         probe.rows_across_foreign_maps(*stripe, 0, H, y)
         assert tuple(y) == (0, H, *stripe)
         assert probe.rows_whole(H, y[2], y[3]) == (stripe == (0, H))
+
+
+# ---- the image pair and the staged one (psm::PairState): st = (depth, next depth, slot, range pending, inside) ----
+UPLOADED, STAGED, ADOPTED, NEXT_SLOT, RANGE_ARRIVED, NEW_PAIR, ASK_PAIR = range(7)
+NONE, U8, F32 = -1, 0, 1
+
+
+def pair(probe, st, op, a=0, b=0):
+    buf = (ctypes.c_int * 5)(*st)
+    ret = probe.pair_step(buf, op, a, b)
+    return tuple(buf), ret
+
+
+def reachable_pairs(probe):
+    fresh, _ = pair(probe, (0,) * 5, NEW_PAIR)
+    moves = [(UPLOADED, d, i) for d in (U8, F32) for i in (0, 1)] + [(STAGED, U8, 0), (STAGED, F32, 1)] + \
+            [(ADOPTED, i, 0) for i in (0, 1)] + [(NEXT_SLOT, 0, 0), (RANGE_ARRIVED, 0, 0)]
+    seen, todo = {fresh}, [fresh]
+    while todo:
+        st = todo.pop()
+        for m in moves:
+            nxt, _ = pair(probe, st, *m)
+            if nxt not in seen:
+                seen.add(nxt)
+                todo.append(nxt)
+    return fresh, sorted(seen)
+
+
+def test_pair_transitions_from_every_reachable_state(probe):
+    fresh, states = reachable_pairs(probe)
+    assert fresh == (NONE, NONE, 0, 0, 1)
+    assert len(states) > 20 and all(s[2] in (0, 1) for s in states)
+    for st in states:
+        staged_before = st[1] >= 0
+        assert pair(probe, st, ASK_PAIR) == (st, int(staged_before) | ((st[1] if staged_before else st[0]) + 1) << 1)
+        # a blocking upload leaves no staged pair and no pending range
+        for depth, inside in itertools.product((U8, F32), (0, 1)):
+            got, q = pair(probe, st, UPLOADED, depth, inside)
+            assert got == (depth, NONE, st[2], 0, inside) and q == (depth + 1) << 1
+        # staging twice without adopting keeps the second pair's depth and its pending mark only
+        for (d1, p1), (d2, p2) in itertools.product(((U8, 0), (F32, 1)), repeat=2):
+            once, _ = pair(probe, st, STAGED, d1, p1)
+            twice, q = pair(probe, once, STAGED, d2, p2)
+            assert twice == (st[0], d2, st[2], p2, st[4]) and q == 1 | (d2 + 1) << 1
+            # ... which the adoption makes current, with the answer it is given
+            for inside in (0, 1):
+                assert pair(probe, twice, ADOPTED, inside)[0] == (d2, NONE, st[2], 0, inside)
+        # adopt with nothing staged changes nothing
+        if not staged_before:
+            for inside in (0, 1):
+                assert pair(probe, st, ADOPTED, inside)[0] == st
+        # a staged pair given up (the next one is about to overwrite its slot) leaves none; the range arriving changes the pending
+        # mark alone; the slot flips and nothing else moves
+        assert pair(probe, st, STAGED, NONE, 0)[0] == (st[0], NONE, st[2], 0, st[4])
+        assert pair(probe, st, RANGE_ARRIVED)[0] == st[:3] + (0,) + st[4:]
+        assert pair(probe, st, NEXT_SLOT) == (st[:2] + (st[2] ^ 1,) + st[3:], st[2] ^ 1)
+
+
+def test_pair_slot_alternates_from_a_fresh_record(probe):
+    st, _ = pair(probe, (0,) * 5, NEW_PAIR)
+    slots = []
+    for _ in range(6):
+        st, slot = pair(probe, st, NEXT_SLOT)
+        slots.append(slot)
+    assert slots == [1, 0, 1, 0, 1, 0]                             # as `stage_slot ^= 1` gave them
+
+
+def test_depth_at_the_next_construct_is_the_batch_rule(probe):
+    """psm_compute_batch compared its members' depths with a nested conditional over the staged and the current depth of the member
+    and of context 0; the accessor answers the same on all 3 x 3 combinations of (none, 8-bit, float), for both contexts."""
+    def at_construct(depth, nxt):
+        return (pair(probe, (depth, nxt, 0, 0, 1), ASK_PAIR)[1] >> 1) - 1
+
+    depths = (NONE, U8, F32)
+    for raw, nxt, raw0, nxt0 in itertools.product(depths, repeat=4):
+        ref0 = nxt0 if nxt0 >= 0 else raw0
+        refused = (nxt != ref0) if nxt >= 0 else (raw != ref0)     # the conditional as it stood
+        assert (at_construct(raw, nxt) != at_construct(raw0, nxt0)) == refused, (raw, nxt, raw0, nxt0)
+
+
+def test_probe_runs_clean_under_sanitizers(tmp_path):
+    """The probe as a stand-alone program with its own main, built with AddressSanitizer and UndefinedBehaviorSanitizer: it walks
+    the records' transitions natively and must report nothing."""
+    exe = str(tmp_path / "ctx_state_probe_san")
+    subprocess.run(["c++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-DPROBE_MAIN", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", os.path.join(HERE, "ctx_state_probe.cpp"), "-o", exe], check=True)
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stderr == "", run.stderr
+    assert run.stdout.startswith("60000 steps, rows 0 60 20 40, whole 1")
 

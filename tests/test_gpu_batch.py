@@ -178,3 +178,44 @@ def test_batch_after_an_out_of_range_volume_upload(psm, oracle):
         assert forms and 0 not in forms, forms
         assert np.array_equal(de.lDisMap, ref["ldisp"])
 
+
+
+def test_batch_refuses_a_staged_float_pair_outside_the_domain_before_anything_changes(psm, oracle):
+    """Two float contexts, each with a float pair staged asynchronously; one of the staged pairs is scaled by 2^14, outside the
+    select forms' domain.  The batch refuses with the domain message before either context has adopted anything: the other
+    member's current 8-bit pair and its maps are what they were.  The refused member's own psm_cost_construct then adopts the pair
+    and runs the storing form."""
+    from primestereomatch_amd import capi, synth
+    from primestereomatch_amd.dispest import compute_batch
+    W, H, D = 150, 70, 12
+    l, r, _ = synth.make_pair(W, H, D, seed=8)
+    l2, r2, _ = synth.make_pair(W, H, D, seed=9)
+    lf, rf, l2f, r2f = (oracle.u8_to_f32(a) for a in (l, r, l2, r2))
+    big = np.float32(2.0 ** 14)
+
+    def forms(de):
+        return sorted({f for _, f in de.filter_launch_times()})
+
+    with psm.DispEst(l, r, D) as other, psm.DispEst(lf, rf, D) as refused, psm.DispEst(l2f * big, r2f * big, D) as blocking:
+        other.CostConst_GPU(); other.CostFilter_GPU(); other.DispSelect_GPU()
+        maps = other.lDisMap.copy(), other.rDisMap.copy()
+        other.setInputImages_async(l2f, r2f)                           # 8-bit-derived, inside the domain
+        refused.set_option(capi.PSM_OPT_PROFILE, 2)
+        refused.setInputImages_async(l2f * big, r2f * big)
+        for _ in range(2):                                             # (asking again changes nothing)
+            with pytest.raises(capi.PsmError, match=r"float images of context 1 are outside the select forms' domain"):
+                compute_batch([other, refused])
+            gl, gr = other.download_images()                           # still the 8-bit pair: nothing was adopted
+            assert np.array_equal(gl, l) and np.array_equal(gr, r)
+            lm, rm = other.download_maps()
+            assert np.array_equal(lm, maps[0]) and np.array_equal(rm, maps[1])
+        refused.filter_launch_times()
+        refused.CostConst_GPU(); refused.CostFilter_GPU(); refused.DispSelect_GPU()
+        assert forms(refused) == [0]                                   # 0 = storing form
+        blocking.CostConst_GPU(); blocking.CostFilter_GPU(); blocking.DispSelect_GPU()
+        assert np.array_equal(refused.lDisMap, blocking.lDisMap) and np.array_equal(refused.rDisMap, blocking.rDisMap)
+        # the pair is now the current one: the batch goes on refusing it, and sends the caller to the single-pair entry points
+        with pytest.raises(capi.PsmError, match="use the single-pair entry points"):
+            compute_batch([other, refused])
+        gl, _ = other.download_images()
+        assert np.array_equal(gl, l)

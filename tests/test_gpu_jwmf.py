@@ -302,6 +302,31 @@ def test_single_call_bracket_count(psm):
     assert got == [its[0], 0] and n == 2 + 1 + 2
 
 
+def test_jwmf_only_async_frame_loop(psm):
+    """construct(i) (adopts pair i); setInputImages_async(pair i + 1); JointWMF of uploaded maps with pair i as the feature images -
+    no guided filter in between, PSM_OPT_ASYNC on.  The stage forms its keys and cluster planes from the image slots and records that
+    it has read them (images_read), so the copy into the slot of two frames ago is ordered behind it.  Every frame's maps must be the
+    model's for THAT frame's pair.  This guards the mark and the bookkeeping around it; it cannot see a missing ordering even by
+    chance: psm_upload_maps blocks, and clustering a new pair synchronises the host several times inside psm_joint_wmf, so the host
+    has caught up with the device well before the next upload is issued.  The proof is the code: one function, called by every
+    reader."""
+    from primestereomatch_amd import capi
+    W, H, D, radius, nc, frames = 67, 45, 16, 4, 16, 5
+    data = [_random_pair(W, H, 300 + i, "u8") for i in range(frames)]
+    with psm.DispEst(data[0][0], data[0][1], D) as de:
+        de.set_option(capi.PSM_OPT_ASYNC, 1)
+        de.setInputImages_async(*data[0][:2])
+        for i, (l, r, lm, rm) in enumerate(data):
+            de.CostConst_GPU()
+            if i + 1 < frames:
+                de.setInputImages_async(*data[i + 1][:2])
+            de.upload_maps(lm, rm)
+            de.JointWMF_GPU(radius, 0.0, nc, 0)
+            de.synchronize()
+            assert np.array_equal(de.lDisMap, M.joint_wmf(lm, l, radius, n_clusters=nc)), i
+            assert np.array_equal(de.rDisMap, M.joint_wmf(rm, r, radius, n_clusters=nc)), i
+
+
 def test_reclustering_after_a_parameter_change(psm):
     """Another n_clusters on a clustered pair clusters both sides again, and the first parameters after that once more: a
     kept clustering is one made with the call's own parameters."""

@@ -232,6 +232,64 @@ def test_frame_loop_async_equals_blocking(psm, zed, dtype):
             assert np.array_equal(gl, el) and np.array_equal(gr, er), i
 
 
+@pytest.mark.parametrize("pad", [0, 5], ids=["contiguous", "padded"])
+def test_mixed_async_frame_loop(psm, pad):
+    """One context, frames staged in turn by setInputImages_async and setInputFrame_async (the two forms share the staging slots and
+    their events), at the random-map geometry: 53 x 41 pairs, 37 x 29 eyes - rows of 159 and 111 bytes, no multiple of 4, so with
+    `pad` bytes behind every row both forms pack row by row.  Strict alternation gives each form one slot of its page-locked
+    buffer only; the pair staged and then superseded by a blocking setInputImages in the middle shifts the parity, so both slots of
+    both buffers are filled twice.  Every frame's staged bytes equal the CPU model's and its maps those of the same pair uploaded the
+    blocking way."""
+    from primestereomatch_amd.rectify import Rectification
+    sw, sh, mw, mh, crop, D = 37, 29, 61, 47, (3, 2, 53, 41), 8
+    W, H = crop[2], crop[3]
+    rng = np.random.default_rng(77)
+    mxy = [np.stack([rng.integers(-3, sw + 3, size=(mh, mw)), rng.integers(-3, sh + 3, size=(mh, mw))], -1).astype(np.int16) for _ in range(2)]
+    mfr = [rng.integers(0, 1024, size=(mh, mw)).astype(np.uint16) for _ in range(2)]
+    rect = Rectification(tuple(mxy), tuple(mfr), sw, sh, crop)
+    vp = C.c_void_p
+
+    def padded(a):                                   # the same rows, `pad` bytes apart from the next
+        buf = np.zeros((a.shape[0], a.shape[1] * 3 + pad), np.uint8)
+        buf[:, :a.shape[1] * 3] = a.reshape(a.shape[0], -1)
+        return buf
+
+    def stage(de, kind, l, r):
+        lp, rp = padded(l), padded(r)
+        if kind == "pair":
+            rc = de._lib.psm_upload_pair_async(de._h, vp(lp.ctypes.data), vp(rp.ctypes.data), 3, lp.strides[0], psm.capi.PSM_IMG_U8)
+        else:
+            rc = de._lib.psm_upload_pair_rectified_async(de._h, vp(lp.ctypes.data), vp(rp.ctypes.data), 3, lp.strides[0])
+        assert rc == 0, psm.capi.last_error(de._h)
+
+    kinds = ["pair", "eyes", "pair", "eyes", "blocking", "pair", "eyes", "pair", "eyes"]
+    src = [tuple(rng.integers(0, 256, size=(sh, sw, 3) if k == "eyes" else (H, W, 3), dtype=np.uint8) for _ in range(2)) for k in kinds]
+    want = [model_pair(*s, rect) if k == "eyes" else s for k, s in zip(kinds, src)]
+    ghost = tuple(rng.integers(0, 256, size=(H, W, 3), dtype=np.uint8) for _ in range(2))
+    with blank_de(psm, rect, D=D) as de, blank_de(psm, rect, D=D) as plain:
+        de.set_option(psm.capi.PSM_OPT_ASYNC, 1)
+        de.setRectification(rect)
+        stage(de, kinds[0], *src[0])
+        for i, (el, er) in enumerate(want):
+            de.CostConst_GPU()
+            if i + 1 < len(kinds):                   # the next frame travels; ahead of the blocking one, a pair nobody will see
+                stage(de, *((kinds[i + 1],) + src[i + 1] if kinds[i + 1] != "blocking" else ("pair",) + ghost))
+            de.CostFilter_GPU()
+            de.DispSelect_device()
+            lm, rm = (m.copy() for m in de.download_maps())
+            gl, gr = de.download_images()
+            assert_same_bytes(gl, el, f"frame {i} ({kinds[i]}) left")
+            assert_same_bytes(gr, er, f"frame {i} ({kinds[i]}) right")
+            plain.setInputImages(el, er)
+            plain.CostConst_GPU()
+            plain.CostFilter_GPU()
+            plain.DispSelect_GPU()
+            assert np.array_equal(lm, plain.lDisMap) and np.array_equal(rm, plain.rDisMap), i
+            if i + 1 < len(kinds) and kinds[i + 1] == "blocking":
+                de.setInputImages(*src[i + 1])       # supersedes the staged pair: the next CostConst_GPU adopts nothing
+    assert not np.array_equal(want[4][0], ghost[0])
+
+
 def test_frame_ring_push_frame(psm, zed):
     from primestereomatch_amd.dispest import FrameRing
     rect = rect_of(zed, LOOP_CROP)

@@ -325,6 +325,54 @@ def test_refusals_repeated_and_without_a_pair(psm):
         close_all(des)
 
 
+def test_sgm_only_async_frame_loop(psm):
+    """construct(i) (adopts pair i); setInputImages_async(pair i + 1); SGBM(i) - no guided filter in between, PSM_OPT_ASYNC on, the
+    host synchronises only in each frame's read-back.  The SGM stage reads the image slots and records that it has (images_read),
+    so the copy into the slot of two frames ago is ordered behind it.  Every frame's map must be the model's for THAT frame's pair.
+    This guards the mark; it cannot prove an ordering, and passes without the mark too unless the copy happens to overtake the
+    stage - the proof is the code: one function, called by every reader."""
+    W, H, D, frames = 67, 45, 16, 5
+    with psm.DispEst(*pair(W, H, D, 0), D) as de:
+        de.set_option(psm.capi.PSM_OPT_ASYNC, 1)
+        de.setInputImages_async(*pair(W, H, D, 0))
+        for i in range(frames):
+            de.CostConst_GPU()
+            if i + 1 < frames:
+                de.setInputImages_async(*pair(W, H, D, i + 1))
+            disp = de.SGBM_GPU()
+            n = int(np.count_nonzero(disp != model(W, H, D, i)["disp"]))
+            print(f"[sgm-loop] frame {i}: differing map elements {n}")
+            assert n == 0, i
+
+
+def test_sgm_only_async_frame_loop_of_a_batch(psm):
+    """The same loop through psm_sgm_compute_batch with three contexts on shared streams, each with a pair sequence of its own: the
+    mark is recorded for every member on the shared stream.  A guard like the one above, not a proof."""
+    from primestereomatch_amd import dispest
+    W, H, D, frames, n = 67, 45, 16, 5, 3
+
+    def seed(i, k):                                      # frame i of context k
+        return (i + 2 * k) % 7
+
+    des = open_all(psm, [pair(W, H, D, seed(0, k)) for k in range(n)], D)
+    try:
+        dispest.share_streams(des)
+        for k, de in enumerate(des):
+            de.set_option(psm.capi.PSM_OPT_ASYNC, 1)
+            de.setInputImages_async(*pair(W, H, D, seed(0, k)))
+        for i in range(frames):
+            for de in des:
+                de.CostConst_GPU()
+            for k, de in enumerate(des):
+                if i + 1 < frames:
+                    de.setInputImages_async(*pair(W, H, D, seed(i + 1, k)))
+            maps = dispest.sgbm_batch(des)
+            for k, disp in enumerate(maps):
+                assert np.array_equal(disp, model(W, H, D, seed(i, k))["disp"]), (i, k)
+    finally:
+        close_all(des)
+
+
 def test_harness_batch(psm, golden):
     from primestereomatch_amd import harness
     ps = [golden(f"{n}_pair.npz") for n in ("cones", "teddy")]
