@@ -698,6 +698,61 @@ int psm_score_batch(psm_ctx *const *ctxs, int n, int source, struct psm_score *o
 /* Device ms of the launches of the last psm_score (a batch: on ctxs[0], for all pairs); needs PSM_OPT_PROFILE. */
 int psm_score_time(psm_ctx *ctx, double *ms);
 
+/* ---- reproject: from disparity to depth on the device - cv::reprojectImageTo3D of the current result with the Q of
+ * cv::stereoRectify (the reference computes it at src/StereoMatch.cpp:456-458 and drops it), and the ordered, compacted,
+ * coloured point cloud.  The definition is tests/depth_model.py; the device equals it in every bit.  An
+ * independent stage like psm_score: it reads the context's current result and writes planes of its own. ----
+ * For pixel (x, y) of the W x H map: xf = (double)(x + crop_x), yf = (double)(y + crop_y) - the maps are those of the cropped
+ * image, Q speaks of the uncropped rectified one (the cropBox of src/StereoMatch.cpp:474-481).
+ * Disparity d (double) and "missing".  PSM_DEPTH_GIF: d = the byte of the current LEFT 8-bit map, as psm_download_maps would
+ * return it; missing only under PSM_DEPTH_USE_MASK: the left validity byte of the current L-R mask is 0.  PSM_DEPTH_SGM:
+ * d = (double)v * 0.0625 of the int16 map the SGM sources of psm_score read (the plane of psm_score_upload_sgm_map while it is on,
+ * else the last psm_sgm_compute*'s); missing: v == (min_disparity - 1) * 16, the invalid value of the range that map was
+ * computed with (the hook plane: of the current psm_sgm_set_range setting).
+ * Arithmetic: fp64, every product and sum rounded on its own (no FMA), the terms added left to right, for i = 0..3:
+ *   s_i = ((Q[i][0]*xf + Q[i][1]*yf) + Q[i][2]*d) + Q[i][3];   r = 1.0 / s_3;   p_i = s_i * r (i = 0..2)
+ * - the reciprocal-then-multiply reading of OpenCV's Vec3d /= double.  Agreement with a live OpenCV is unpinned.
+ * A point is void if it is missing or any p_i is not finite (s_3 == 0: with a CALIB_ZERO_DISPARITY Q every pixel of disparity
+ * 0).  Void pixels hold the bit pattern 0x7FC00000 in every component of the dense planes - stored, never computed; every other
+ * pixel holds (float)p_i, round to nearest even, +-inf and subnormal floats kept.
+ * Kept for the cloud: not void and z_min < zf <= z_max on the stored float zf.  The cloud is the 16-byte records
+ *   struct { float x, y, z; uint8_t b, g, r, a; }     a = 255
+ * of the kept pixels in raster order, without gaps.  The colour is the left image of the current pair at (x, y), float pairs
+ * quantised as the SGM stage reads them (saturate(rint(f * 255.0f))); under PSM_DEPTH_SGM with a result of psm_sgm_compute_gray
+ * it is that call's left plane, the byte three times. */
+enum { PSM_DEPTH_GIF = 0, PSM_DEPTH_SGM = 1 };                            /* sources */
+enum { PSM_DEPTH_XYZ = 1, PSM_DEPTH_Z = 2, PSM_DEPTH_CLOUD = 4 };         /* outputs */
+enum { PSM_DEPTH_USE_MASK = 1 };                                          /* flags */
+/* Q: 16 finite doubles, row-major; crop_x, crop_y in [-32768, 32767].  No Q is set in a new context; it survives
+ * psm_release_scratch. */
+int psm_reproject_set_q(psm_ctx *ctx, const double Q[16], int crop_x, int crop_y);
+/* z_min < z_max, neither NaN (infinities are allowed).  A new context has (0, FLT_MAX). */
+int psm_reproject_set_range(psm_ctx *ctx, float z_min, float z_max);
+/* The outputs asked for (a non-empty set of PSM_DEPTH_*: the [H][W][3] float plane, the [H][W] float plane of z alone, the
+ * cloud) of `source`, in three launches whatever the data (two without the cloud): the points, the dense planes and one count
+ * of kept pixels per tile; the tiles' offsets; the records.  *count: the number of kept pixels (with or without the cloud).
+ * Synchronous unless PSM_OPT_ASYNC: then the count travels to a page-locked slot and psm_reproject_wait collects it (count may
+ * be NULL).  Buffers are allocated on first use, for the outputs asked for only (12, 4 and 16 bytes per pixel), and given back
+ * by psm_release_scratch.  Refused with nothing enqueued and the previous result intact: no Q set, an unknown source, output
+ * or flag bit, outputs == 0, a GIF source without current maps or with maps that cover a row stripe only, PSM_DEPTH_USE_MASK
+ * without a current mask or with an SGM source, an SGM source with neither a compute nor the hook plane, PSM_DEPTH_CLOUD
+ * without a current pair. */
+int psm_reproject(psm_ctx *ctx, int source, int outputs, int flags, uint32_t *count);
+int psm_reproject_wait(psm_ctx *ctx, uint32_t *count);
+/* The dense planes of the last psm_reproject / psm_reproject_batch (either pointer may be NULL; one that is not must have been
+ * among its outputs): z as H rows of W floats stride_bytes apart, xyz as H rows of 3 W floats 3 * stride_bytes apart;
+ * stride_bytes 0: packed, else a multiple of 4 that is >= 4 W.  Synchronises. */
+int psm_reproject_download(psm_ctx *ctx, float *xyz, float *z, size_t stride_bytes);
+/* The records of the last run (which had PSM_DEPTH_CLOUD), *written of them; max_records below the count is refused. */
+int psm_reproject_download_cloud(psm_ctx *ctx, void *records, uint32_t max_records, uint32_t *written);
+/* psm_reproject of the n contexts ctxs[0..n) in one set of launches, the context on a grid axis of its own.  Same width,
+ * height and device on all; each context uses its own Q, crop, range and result.  The launches run on ctxs[0]'s stream,
+ * ordered as psm_score_batch's; synchronous with the counts in counts[0..n) unless ctxs[0] has PSM_OPT_ASYNC.  Afterwards
+ * every context is exactly where its own psm_reproject would have left it. */
+int psm_reproject_batch(psm_ctx *const *ctxs, int n, int source, int outputs, int flags, uint32_t *counts);
+/* Device ms of the launches of the last psm_reproject (a batch: on ctxs[0], for all pairs); needs PSM_OPT_PROFILE. */
+int psm_reproject_time(psm_ctx *ctx, double *ms);
+
 /* ---- debug / bench entry points (no counterpart in the reference) ---- */
 /* Test hook of the score stage: an int16 map (H rows of W values, pitch stride_bytes; 0: packed) that the SGM sources of
  * psm_score read from now on instead of the map of the last psm_sgm_compute - maps no compute would produce.  Kept in a plane

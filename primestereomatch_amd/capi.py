@@ -31,6 +31,11 @@ PSM_FLAG_FMA_SOLVE = 67108864
 PSM_SCORE_GIF, PSM_SCORE_SGM, PSM_SCORE_SGM_INT = 0, 1, 2
 PSM_MASK_NONE, PSM_MASK_NONOCC, PSM_MASK_DISC = 0, 1, 2
 PSM_SCORE_FLAT = 1
+# the reprojection stage: sources, outputs, flags
+PSM_DEPTH_GIF, PSM_DEPTH_SGM = 0, 1
+PSM_DEPTH_XYZ, PSM_DEPTH_Z, PSM_DEPTH_CLOUD = 1, 2, 4
+PSM_DEPTH_USE_MASK = 1
+PSM_DEPTH_VOID = 0x7FC00000          # the bit pattern of a void pixel in the dense planes
 
 
 class Score(C.Structure):
@@ -45,9 +50,22 @@ class Score(C.Structure):
         return d
 
 
+def point_dtype():
+    """The 16-byte record of the point cloud (psm_reproject_download_cloud): float x, y, z; uint8 b, g, r, a (a = 255)."""
+    import numpy as np
+    return np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("b", "u1"), ("g", "u1"), ("r", "u1"), ("a", "u1")])
+
+
+class Point(C.Structure):
+    """The same record for ctypes callers."""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("b", C.c_uint8), ("g", C.c_uint8), ("r", C.c_uint8),
+                ("a", C.c_uint8)]
+
+
 # every symbol include/primesm_hip.h declares: (name, restype, argtypes)
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 _pi, _pd = C.POINTER(C.c_int), C.POINTER(C.c_double)
+_pu = C.POINTER(C.c_uint32)
 SYMBOLS = [
     ("psm_device_count", _i, []),
     ("psm_create", _i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),
@@ -136,6 +154,14 @@ SYMBOLS = [
     ("psm_score_batch", _i, [C.POINTER(_vp), _i, _i, C.POINTER(Score)]),
     ("psm_score_time", _i, [_vp, _pd]),
     ("psm_score_upload_sgm_map", _i, [_vp, _vp, _sz]),
+    ("psm_reproject_set_q", _i, [_vp, _pd, _i, _i]),
+    ("psm_reproject_set_range", _i, [_vp, C.c_float, C.c_float]),
+    ("psm_reproject", _i, [_vp, _i, _i, _i, _pu]),
+    ("psm_reproject_wait", _i, [_vp, _pu]),
+    ("psm_reproject_download", _i, [_vp, _vp, _vp, _sz]),
+    ("psm_reproject_download_cloud", _i, [_vp, _vp, C.c_uint32, _pu]),
+    ("psm_reproject_batch", _i, [C.POINTER(_vp), _i, _i, _i, _i, _pu]),
+    ("psm_reproject_time", _i, [_vp, _pd]),
 ]
 
 _lib = None

@@ -49,7 +49,7 @@ int check_source(psm_ctx *e, const psm_ctx *c, const char *who, int source)
     if (source == PSM_SCORE_GIF) {
         if (!c->res.maps) return fail(e, "%s: no disparity maps computed (PSM_SCORE_GIF)", who);
         if (stripe_only(c)) return fail(e, "%s: the maps hold this context's row stripe only (gather the stripes first)", who);
-    } else if (!c->sgm.have && !c->score.hook_on) {
+    } else if (!sgm_source_exists(c)) {
         return fail(e, "%s: no SGM result (psm_sgm_compute) for an SGM source", who);
     }
     return 0;
@@ -73,7 +73,7 @@ int ensure_scratch(psm_ctx *c)
 ScPair score_pair(const psm_ctx *c)
 {
     const ScoreState &q = c->score;
-    return ScPair{c->maps, q.hook_on ? q.hook : c->sgm.out, q.have_truth ? q.gt : nullptr, use_mask(q) ? q.mask : nullptr, q.planes, q.cnt};
+    return ScPair{c->maps, sgm_source_map(c), q.have_truth ? q.gt : nullptr, use_mask(q) ? q.mask : nullptr, q.planes, q.cnt};
 }
 
 ScArgs score_args(const psm_ctx *c, const ScPair &p)

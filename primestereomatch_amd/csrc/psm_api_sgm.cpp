@@ -42,7 +42,7 @@ void sgm_free(psm_ctx *c)
     for (hipEvent_t &e : g.ev_maps) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     g.have = g.timed = g.spk_have = g.maps_timed = false;
     g.spk_t0 = -1;
-    g.vol_dp = g.res_d = g.res_dmin = 0;
+    g.vol_dp = g.res_d = g.res_dmin = g.res_ch = 0;
 }
 
 }  // namespace psm
@@ -205,6 +205,7 @@ void mark(SgmState &g, SgmCost kind, int ch, int dmin, int D, bool timed)
     g.have = true;
     g.res_d = D;
     g.res_dmin = dmin;
+    g.res_ch = ch;
     g.timed = timed;
     g.pf_ch = kind == SgmCost::BT ? ch : 0;
     g.cen_have = kind == SgmCost::CENSUS;

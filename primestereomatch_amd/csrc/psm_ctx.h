@@ -17,6 +17,8 @@
 //                       over the pairs of several contexts in shared launches (psm_sgm_compute_batch)
 //   psm_api_score.cpp   display maps and the error metric against ground truth of the current result (psm_score), and of the
 //                       results of several contexts in shared launches (psm_score_batch)
+//   psm_api_depth.cpp   from disparity to depth: cv::reprojectImageTo3D of the current result and the compacted point cloud
+//                       (psm_reproject), and of the results of several contexts in shared launches (psm_reproject_batch)
 // Takes the place of the reference's oclUtil + CVC_cl / CVF_cl / DispSel_cl host wrappers
 // (src/oclUtil.cpp, src/CVC_cl.cpp, src/CVF_cl.cpp, src/DispSel_cl.cpp).
 // What a context knows about its volumes, results and image pairs between calls - psm::VolSide per side, psm::Results,
@@ -67,6 +69,7 @@ struct SgmState {
     int vol_dp = 0;                                // the Dp C and S are allocated for (another range's: freed and allocated again)
     int res_d = 0;                                 // the D of the result in them (psm_sgm_download_costs)
     int res_dmin = 0;                              // ... and its minDisparity (psm_sgm_select_maps: psm_sgm_set_range may have been called since)
+    int res_ch = 0;                                // ... and the channels of the pair it ran on (1: psm_sgm_compute_gray's planes `gray`)
     uint16_t *C = nullptr;
     uint32_t *S = nullptr;
     uint32_t *disp2 = nullptr;
@@ -151,6 +154,25 @@ struct ScoreState {
     DevTable tab;                                  // psm_score_batch (this context as the first of a batch): ScPair records
 };
 
+// psm_reproject (psm_api_depth.cpp): parameters (they survive psm_release_scratch) and the stage's scratch - the dense planes and
+// the cloud (each allocated when first asked for), the tiles' counts and offsets, the count and its page-locked slot.
+struct DepthState {
+    double Q[16] = {};
+    bool have_q = false;
+    int crop_x = 0, crop_y = 0;
+    float z_min = 0.0f, z_max = 3.402823466e+38f;  // FLT_MAX
+    unsigned *xyz = nullptr, *z = nullptr;         // [H][W][3], [H][W] float bit patterns
+    uint4 *cloud = nullptr;                        // [H W] records
+    unsigned *tiles = nullptr;                     // [2][dp_tiles]: counts, offsets
+    unsigned *cnt = nullptr, *pin = nullptr;       // the count and the page-locked slot its copy lands in
+    hipEvent_t ev_done = nullptr;                  // ... that copy has executed
+    hipEvent_t ev[2] = {nullptr, nullptr};         // PSM_OPT_PROFILE: around the launches
+    int outputs = 0;                               // of the last psm_reproject (0: none: the planes hold nothing)
+    bool pending = false;                          // a count is on its way to `pin` (psm_reproject_wait)
+    bool timed = false;
+    DevTable tab;                                  // psm_reproject_batch (this context as the first of a batch): DpArgs records
+};
+
 // The image pair every frame starts with, and the second slot the next frame travels into (psm_upload_pair_async,
 // psm_upload_pair_rectified_async).  `st` is changed by its transitions (psm_state.h) alone, the rest by the functions declared
 // under "the image pair slots" below.
@@ -220,6 +242,7 @@ struct psm_ctx {
     size_t rect_src_bytes = 0;                   // bytes of one eye in a slot (16-byte multiple) the buffers were allocated for
     psm::SgmState sgm;
     psm::ScoreState score;
+    psm::DepthState depth;
     uint8_t *p4[2] = {nullptr, nullptr};  // PSM_U8 only: {c0,c1,c2,grad} words
     // What stands for vol[side] (psm_state.h): costs that are a recipe, a filtered volume pending as packed minima or as FGF models.
     // The WTA consumes either form directly; any other reader makes the volume real first (materialize()).
@@ -420,6 +443,13 @@ void sgm_free(psm_ctx *c);                       // the stage's buffers and even
 void wm_free(psm_ctx *c, bool all);              // the weighted median's device scratch; all: its page-locked snapshots and events too
 // psm_api_score.cpp
 void score_free(psm_ctx *c, bool truth);         // the stage's scratch and events; truth: the uploaded truth, mask and hook map too
+// The int16 map the SGM sources of psm_score and psm_reproject read - the plane of psm_score_upload_sgm_map while it is on, else
+// the last psm_sgm_compute*'s - and the invalid value of the range it belongs to (the hook plane: the current setting's)
+inline const int16_t *sgm_source_map(const psm_ctx *c) { return c->score.hook_on ? c->score.hook : c->sgm.out; }
+inline int sgm_source_invalid(const psm_ctx *c) { return ((c->score.hook_on ? c->sgm.dmin : c->sgm.res_dmin) - 1) * 16; }
+inline bool sgm_source_exists(const psm_ctx *c) { return c->sgm.have || c->score.hook_on; }
+// psm_api_depth.cpp
+void depth_free(psm_ctx *c);                     // the stage's scratch and events (its parameters stay)
 // psm_api_select.cpp: copy_maps_out - two [H][W] planes on the device to the caller's rows
 int copy_maps_out(psm_ctx *c, const uint8_t *dev, uint8_t *lmap, uint8_t *rmap, size_t stride);
 

@@ -269,6 +269,19 @@ struct SgmPair {
 // single-pair ones (a cast of the loaded value to global and back is folded away before it can tell anyone).
 template <typename T>
 __device__ __forceinline__ T *sgm_global(T *const &slot) { return (T *)*(__attribute__((address_space(1))) T *const *)(const void *)&slot; }
+// one pixel of a staged image as a dword of `ch` bytes (depth 0: bytes, PSM_IMG_U8); float images are quantised as lFrame.convertTo(lFrame, CV_8U, 255) does
+// (src/StereoMatch.cpp:174-177): saturate(rint(f * 255.0f)), ties to even
+__device__ __forceinline__ unsigned sgm_px(const void *img, int depth, int ch, size_t idx)
+{
+    unsigned v = 0;
+    for (int k = 0; k < ch; ++k) {
+        unsigned b;
+        if (depth == 0) b = ((const uint8_t *)img)[idx * ch + k];
+        else b = (unsigned)fminf(fmaxf(rintf(__fmul_rn(((const float *)img)[idx * ch + k], 255.0f)), 0.0f), 255.0f);
+        v |= b << (8 * k);
+    }
+    return v;
+}
 constexpr int SGM_DIRS[8][2] = {{0, 1}, {0, -1}, {1, 0}, {-1, 0}, {1, 1}, {1, -1}, {-1, 1}, {-1, -1}};   // (dy, dx)
 // the directions a mode sums (psm_sgm_set_mode; the values are OpenCV's enum): the first SGM_MODE_NDIR[mode] entries of its row, as
 // indices into SGM_DIRS, launched in this order - the first one stores S.  Every reduced mode begins with the two row directions.
@@ -350,5 +363,33 @@ struct ScPair {
 };
 void launch_sc_minmax(hipStream_t s, const ScArgs &a, const ScPair *tab = nullptr, int n = 1);   // k_sc_minmax: cnt->mn, cnt->mx of d16
 void launch_sc_score(hipStream_t s, int source, const ScArgs &a, const ScPair *tab = nullptr, int n = 1);   // k_sc_score<source>: planes, cnt->bad, cnt->sum
+
+// psm_depth.hip: cv::reprojectImageTo3D of the current result and the compacted point cloud (psm_reproject, psm_api_depth.cpp)
+enum { DP_GIF = 0, DP_SGM = 1 };                       // PSM_DEPTH_* (include/primesm_hip.h)
+constexpr int DP_TILE = 256;                           // pixels (in raster order) of a workgroup: one count per tile
+constexpr int DP_SCAN = 256;                           // threads of the scan's single workgroup; thread t takes ceil(tiles / DP_SCAN) consecutive tiles
+__host__ __device__ inline int dp_tiles(int W, int H) { return (int)(((size_t)W * H + DP_TILE - 1) / DP_TILE); }
+// One pair: its pointers and its own parameters.  A single call passes the record as the kernel argument; a batch's device table
+// holds one per pair, indexed with the pair number (blockIdx.y).  What a batch shares travels in DpGeom.
+struct DpArgs {
+    const uint8_t *map;                // DP_GIF: [H][W], the left 8-bit map
+    const uint8_t *valid;              // PSM_DEPTH_USE_MASK: [H][W], the left validity bytes; else null
+    const int16_t *d16;                // DP_SGM: [H][W]
+    const void *img;                   // the left image of the colour pair (k_dp_pack only)
+    unsigned *xyz, *z;                 // [H][W][3], [H][W] float bit patterns; null: not asked for
+    uint4 *cloud;                      // [H W] records; null: not asked for
+    unsigned *tile_cnt, *tile_off;     // [dp_tiles]: kept pixels per tile, and their exclusive sums
+    unsigned *total;                   // the count
+    double Q[16];
+    int crop_x, crop_y;
+    float z_min, z_max;
+    int invalid;                       // DP_SGM: the map's invalid value
+    int depth, ch;                     // of img: PSM_IMG_*, 3 or 1 channels
+};
+struct DpGeom { int W, H, source; };
+// tab == nullptr: the pair of `a`; else the n pairs of the device table (`a` unused, grid y = pair)
+void launch_dp_count(hipStream_t s, const DpArgs &a, const DpGeom &g, const DpArgs *tab = nullptr, int n = 1);   // k_dp_count: dense planes, tile_cnt
+void launch_dp_scan(hipStream_t s, const DpArgs &a, const DpGeom &g, const DpArgs *tab = nullptr, int n = 1);    // k_dp_scan: tile_off, total
+void launch_dp_pack(hipStream_t s, const DpArgs &a, const DpGeom &g, const DpArgs *tab = nullptr, int n = 1);    // k_dp_pack: cloud
 
 }  // namespace psm

@@ -41,20 +41,7 @@ __device__ __forceinline__ int sgm_wave_min(int v)
                min(__builtin_amdgcn_readlane(v, 47), __builtin_amdgcn_readlane(v, 63)));
 }
 
-// one pixel of a staged image as a dword of `ch` bytes (depth 0: bytes, PSM_IMG_U8); float images are quantised as lFrame.convertTo(lFrame, CV_8U, 255) does
-// (src/StereoMatch.cpp:174-177): saturate(rint(f * 255.0f)), ties to even
-__device__ __forceinline__ unsigned sgm_px(const void *img, int depth, int ch, size_t idx)
-{
-    unsigned v = 0;
-    for (int k = 0; k < ch; ++k) {
-        unsigned b;
-        if (depth == 0) b = ((const uint8_t *)img)[idx * ch + k];
-        else b = (unsigned)fminf(fmaxf(rintf(__fmul_rn(((const float *)img)[idx * ch + k], 255.0f)), 0.0f), 255.0f);
-        v |= b << (8 * k);
-    }
-    return v;
-}
-
+// (sgm_px, one pixel of a staged image as a dword of its bytes: psm_kernels.h - the reprojection stage's colours read it too)
 __device__ __forceinline__ int sgm_clamp(int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); }
 
 // Several pairs per launch (psm_sgm_compute_batch): every kernel below is one body (sgm_*) behind two entries.  k_sgm_* takes its

@@ -323,6 +323,62 @@ class DispEst:
             raise ValueError("upload_sgm_map: disp must be an H x W int16 map of the size DispEst was built for")
         self._ck(self._lib.psm_score_upload_sgm_map(self._h, _ptr(disp), disp.strides[0]), "upload_sgm_map")
 
+    # ---- reproject: from disparity to depth on the device (cv::reprojectImageTo3D with the Q of src/StereoMatch.cpp:456-458) ----
+    _depth_outputs = 0                           # the outputs of the last Reproject_GPU (reproject_batch)
+
+    def setReprojection(self, Q, crop=(0, 0), z_range=None):
+        """Q: the 4 x 4 matrix of cv::stereoRectify (rectify.load_calibration(...)["Q"], or rectify.q_from_projections); crop: the
+        (x, y) of this object's image inside the rectified one (the cropBox of src/StereoMatch.cpp:474-481; an (x, y, w, h) box
+        is taken by its first two); z_range = (z_min, z_max): the cloud keeps z_min < z <= z_max (None: unchanged; a new
+        object: (0, FLT_MAX)).  psm_reproject_set_q / psm_reproject_set_range."""
+        q = np.ascontiguousarray(Q, dtype=np.float64)
+        if q.size != 16:
+            raise ValueError("setReprojection: Q must hold 4 x 4 values")
+        self._ck(self._lib.psm_reproject_set_q(self._h, q.ctypes.data_as(C.POINTER(C.c_double)), int(crop[0]), int(crop[1])),
+                 "setReprojection")
+        if z_range is not None:
+            self._ck(self._lib.psm_reproject_set_range(self._h, float(z_range[0]), float(z_range[1])), "setReprojection")
+
+    def Reproject_GPU(self, source: int = capi.PSM_DEPTH_GIF, outputs: int = capi.PSM_DEPTH_CLOUD, use_mask: bool = False):
+        """psm_reproject: the points of the current result, on the device.  source: capi.PSM_DEPTH_GIF (the current left 8-bit
+        map; use_mask: pixels the current L-R mask marks invalid are missing) or PSM_DEPTH_SGM (the int16 map of the last
+        SGBM_GPU); outputs: any of capi.PSM_DEPTH_XYZ | PSM_DEPTH_Z | PSM_DEPTH_CLOUD.  -> the number of kept pixels; under
+        PSM_OPT_ASYNC None - reproject_wait() collects it.  reprojected() and cloud() download the results."""
+        n = C.c_uint32()
+        flags = capi.PSM_DEPTH_USE_MASK if use_mask else 0
+        self._ck(self._lib.psm_reproject(self._h, int(source), int(outputs), flags, C.byref(n)), "Reproject_GPU")
+        self._depth_outputs = int(outputs)
+        return None if self.options.get(capi.PSM_OPT_ASYNC) else int(n.value)
+
+    def reproject_wait(self):
+        """The count of the Reproject_GPU enqueued under PSM_OPT_ASYNC."""
+        n = C.c_uint32()
+        self._ck(self._lib.psm_reproject_wait(self._h, C.byref(n)), "reproject_wait")
+        return int(n.value)
+
+    def reprojected(self):
+        """The dense planes of the last Reproject_GPU: (xyz H x W x 3 float32 or None, z H x W float32 or None) - what its
+        outputs named.  Void pixels hold the bit pattern capi.PSM_DEPTH_VOID (a NaN)."""
+        xyz = np.empty((self.hei, self.wid, 3), np.float32) if self._depth_outputs & capi.PSM_DEPTH_XYZ else None
+        z = np.empty((self.hei, self.wid), np.float32) if self._depth_outputs & capi.PSM_DEPTH_Z else None
+        self._ck(self._lib.psm_reproject_download(self._h, _ptr(xyz), _ptr(z), 0), "reprojected")
+        return xyz, z
+
+    def cloud(self):
+        """The point cloud of the last Reproject_GPU (with PSM_DEPTH_CLOUD): a structured array of capi.point_dtype() - x, y,
+        z, b, g, r, a - the kept pixels in raster order."""
+        rec = np.empty(self.hei * self.wid, capi.point_dtype())
+        n = C.c_uint32()
+        self._ck(self._lib.psm_reproject_download_cloud(self._h, _ptr(rec), rec.size, C.byref(n)), "cloud")
+        return rec[:n.value].copy()
+
+    def reproject_time(self):
+        """Device ms of the launches of the last Reproject_GPU (reproject_batch: of all pairs, on its first object); needs
+        PSM_OPT_PROFILE."""
+        ms = C.c_double()
+        self._ck(self._lib.psm_reproject_time(self._h, C.byref(ms)), "reproject_time")
+        return ms.value
+
     # ---- extensions beyond the reference surface --------------------------------------------
     def LRCheck_GPU(self) -> int:
         """PP lrCheck (src/PP.cpp:17-50) on the device -> lValid / rValid."""
@@ -492,6 +548,8 @@ class DispEst:
             self._ck(self._lib.psm_rectify_set_maps(self._h, side, _ptr(xy), _ptr(fr), xy.shape[1], xy.shape[0], int(rect.src_w),
                                                     int(rect.src_h), int(x), int(y)), "setRectification")
         self._rect_src = (int(rect.src_h), int(rect.src_w))
+        if getattr(rect, "Q", None) is not None:             # the calibration's Q came along: the object can reproject as well
+            self.setReprojection(rect.Q, crop=(x, y))
         return 0
 
     def clearRectification(self):
@@ -710,6 +768,22 @@ def score_batch(des, source: int = capi.PSM_SCORE_GIF):
     return None if des[0].options.get(capi.PSM_OPT_ASYNC) else [r.as_dict() for r in recs]
 
 
+def reproject_batch(des, source: int = capi.PSM_DEPTH_GIF, outputs: int = capi.PSM_DEPTH_CLOUD, use_mask: bool = False):
+    """Reproject_GPU of several DispEst objects of one geometry in one set of launches (psm_reproject_batch): each object's current
+    result with its own Q, crop and range -> the list of counts.  Every object afterwards behaves as after its own Reproject_GPU
+    (reprojected(), cloud()); under PSM_OPT_ASYNC on des[0]: None, every object's reproject_wait() collects its count."""
+    des = list(des)
+    if not des:
+        return []
+    arr = (C.c_void_p * len(des))(*[d._h for d in des])
+    counts = (C.c_uint32 * len(des))()
+    flags = capi.PSM_DEPTH_USE_MASK if use_mask else 0
+    capi.check(des[0]._lib.psm_reproject_batch(arr, len(des), int(source), int(outputs), flags, counts), des[0]._h, "reproject_batch")
+    for d in des:
+        d._depth_outputs = int(outputs)
+    return None if des[0].options.get(capi.PSM_OPT_ASYNC) else [int(v) for v in counts]
+
+
 def share_streams(des):
     """The DispEst objects of a batch run on one compute stream and one copy stream each way (psm_share_streams) - call once
     before a frame loop over batches."""
@@ -735,13 +809,17 @@ class FrameRing:
     """
 
     def __init__(self, l, r, d: int, frames: int = 2, *, dtype: str = "f32", device: int = 0, lr_check: bool = False,
-                 seg_rows: int = 0, truth=None, scale_factor: int = 4, error_threshold: int = 4):
+                 seg_rows: int = 0, truth=None, scale_factor: int = 4, error_threshold: int = 4, reproject: int = 0):
         """Every context is told PSM_OPT_FRAMES_IN_FLIGHT = frames: the planner of the fused launches then cuts them for a shared
         device (450 x 375 x 64: 0.207 ms per frame against 0.22-0.23 without the hint; no result changes).  seg_rows > 0:
         PSM_OPT_SEG_ROWS of every context on top of that (round 5's first finding - one segment per launch, seg_rows = image height
         - is what the hint replaced: profiles/r05/exp_plan_model.txt).
         truth = (gt, mask or None): every frame's left map is scored against it on the device behind its last stage (Score_GPU,
-        PSM_SCORE_GIF, with scale_factor / error_threshold); push / flush then return (lmap, rmap, score) instead of (lmap, rmap)."""
+        PSM_SCORE_GIF, with scale_factor / error_threshold); push / flush then return (lmap, rmap, score) instead of (lmap, rmap).
+        reproject = outputs (capi.PSM_DEPTH_*): every frame's left map is reprojected on the device behind its last stage
+        (Reproject_GPU, PSM_DEPTH_GIF; under lr_check with its mask) once setReprojection - or setRectification with a
+        rectification that carries Q - has told the ring its Q; push / flush then return one more element: the cloud if the
+        outputs name it alone, else the dict {"xyz", "z", "cloud"} of what they name."""
         if frames < 1:
             raise ValueError("FrameRing: frames must be >= 1")
         self.ctx = [DispEst(l, r, d, dtype=dtype, device=device) for _ in range(frames)]
@@ -754,6 +832,7 @@ class FrameRing:
         self._busy = [False] * frames
         self._lrc = lr_check
         self._score = truth is not None
+        self._depth = int(reproject)
         if self._score:
             for c in self.ctx:
                 c.set_truth(truth[0], truth[1])
@@ -765,8 +844,18 @@ class FrameRing:
         for c in self.ctx:
             c.setRectification(rect)
 
+    def setReprojection(self, Q, crop=(0, 0), z_range=None):
+        """Every context of the ring reprojects with this Q, crop and range (DispEst.setReprojection)."""
+        for c in self.ctx:
+            c.setReprojection(Q, crop, z_range)
+
     def push(self, l, r):
         return self._push(lambda c: c.setInputImages(l, r))
+
+    def push_async(self, l, r):
+        """push with the pair travelling on the context's copy stream (DispEst.setInputImages_async): the call returns once the
+        images are in page-locked staging memory, and the frame's first kernel waits for the copy on the device."""
+        return self._push(lambda c: c.setInputImages_async(l, r))
 
     def push_frame(self, vFrame):
         """push for a side-by-side camera frame: rectified and cropped on the device (DispEst.setInputFrame)."""
@@ -788,12 +877,23 @@ class FrameRing:
         c.download_maps_async()
         if self._score:
             c.Score_GPU(capi.PSM_SCORE_GIF)      # (behind the download's start: the copy of the maps does not wait for the score)
+        if self._depth:
+            c.Reproject_GPU(capi.PSM_DEPTH_GIF, self._depth, use_mask=self._lrc)
         self._busy[i] = True
         return out
 
     def _collect(self, c):
-        maps = tuple(m.copy() for m in c.download_maps_wait())
-        return maps + (c.score_wait(),) if self._score else maps
+        out = tuple(m.copy() for m in c.download_maps_wait())
+        if self._score:
+            out += (c.score_wait(),)
+        if self._depth:
+            c.reproject_wait()
+            if self._depth == capi.PSM_DEPTH_CLOUD:
+                out += (c.cloud(),)
+            else:
+                xyz, z = c.reprojected()
+                out += ({"xyz": xyz, "z": z, "cloud": c.cloud() if self._depth & capi.PSM_DEPTH_CLOUD else None},)
+        return out
 
     def flush(self):
         out = []

@@ -31,7 +31,8 @@ def error_vs_ground_truth(lDisMap, gt, mask, maxDis, scale_factor, error_thresho
 
 
 def compute(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, error_threshold=4, threads=8,
-            dtype="f32", post_process=True, verbose=False, subsample_rate=0, process_dm=False, joint_wmf=False, device_tail=False):
+            dtype="f32", post_process=True, verbose=False, subsample_rate=0, process_dm=False, joint_wmf=False, device_tail=False,
+            depth=False):
     """One frame of STEREO_GIF on the accelerator path.  l_bgr/r_bgr: H x W x 3 uint8 (imread order).
     subsample_rate 0: full guided filter (CostFilter_GPU, the reference's 'm' branch); 2/4/8: the Fast Guided
     Filter variant (CostFilter_FGF, the snapshot's live branch, src/StereoMatch.cpp:213) on the device.
@@ -42,7 +43,10 @@ def compute(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, error_t
     (DispEst.JointWMF_GPU) and score the filtered left map, as StereoMatch::compute does after PostProcess
     (src/StereoMatch.cpp:225-311); the selected maps stay in lDisMap_raw / rDisMap_raw.
     device_tail: the display map and the error metric come from the device (DispEst.Score_GPU) instead of the numpy tail below -
-    the same record, key for key."""
+    the same record, key for key.
+    depth: False, the default: nothing is added.  Else the Q of cv::stereoRectify (4 x 4), or a dict {"Q", "crop": (x, y),
+    "z_range": (z_min, z_max), "use_mask": bool}: the final left map is reprojected on the device (DispEst.Reproject_GPU) and the
+    record gains xyz (H x W x 3 float32), z (H x W float32) and cloud (capi.point_dtype() records)."""
     out = {}
     lFrame = np.ascontiguousarray(l_bgr)
     rFrame = np.ascontiguousarray(r_bgr)
@@ -54,6 +58,7 @@ def compute(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, error_t
         SMDE.setInputImages(lFrame, rFrame)
         _run_stages(SMDE, out, threads, subsample_rate, post_process, process_dm, joint_wmf)
         tail = _device_tail([SMDE], [gt], [mask], scale_factor, error_threshold, capi.PSM_SCORE_GIF)[0] if device_tail else None
+        _reproject(SMDE, out, depth, capi.PSM_DEPTH_GIF)
     return _finish(out, maxDis, gt, mask, scale_factor, error_threshold, verbose, tail)
 
 
@@ -119,7 +124,7 @@ def compute_video(vFrame, rectification, maxDis=64, gt=None, mask=None, scale_fa
 
 
 def compute_sgbm(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, error_threshold=4, verbose=False, device_tail=False,
-                 post_process=False, joint_wmf=False, **params):
+                 post_process=False, joint_wmf=False, depth=False, **params):
     """One frame of STEREO_SGBM (src/StereoMatch.cpp:169-187, 275-309) on the device: l_bgr / r_bgr H x W x 3, uint8 or float32
     scaled by 1/255 (quantised on the device as lFrame.convertTo(lFrame, CV_8U, 255) does); params: DispEst.SGBM_GPU's, forwarded
     as they are - the reference's whole configuration is pre_filter_cap=63, speckle_window_size=100, speckle_range=32 (the
@@ -130,7 +135,8 @@ def compute_sgbm(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, er
     post_process: afterwards the stage's 8-bit maps of both views (DispEst.SGBMSelect_GPU) go through the post-processing chain of
     the GIF path on the device - LRCheck, FillInv, WgtMedian; joint_wmf: JointWMF in place of the latter two - and the record
     gains lDisMap_pp, the filtered left map, and (with gt) bp_percent_pp / avg_err_pp, the metric of compute() on it - from
-    Score_GPU(PSM_SCORE_GIF) under device_tail.  The range must lie inside [0, maxDis).  Off, the default: no key is added."""
+    Score_GPU(PSM_SCORE_GIF) under device_tail.  The range must lie inside [0, maxDis).  Off, the default: no key is added.
+    depth: compute()'s, on the int16 map (PSM_DEPTH_SGM: sixteenths of a disparity, the invalid pixels missing)."""
     out = {}
     lFrame, rFrame = np.ascontiguousarray(l_bgr), np.ascontiguousarray(r_bgr)
     with DispEst(lFrame, rFrame, maxDis, 8, True) as SMDE:
@@ -140,10 +146,38 @@ def compute_sgbm(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, er
         if params.get("speckle_window_size", 0) > 0:
             out["speckle_ms"] = SMDE.sgm_speckle_time()
         tail = _device_tail_sgbm([SMDE], [gt], [mask], scale_factor, error_threshold)[0] if device_tail else None
+        _reproject(SMDE, out, depth, capi.PSM_DEPTH_SGM)
         if post_process or joint_wmf:
             SMDE.SGBMSelect_GPU()
             _post_process_sgbm([SMDE], [out], [gt], [mask], scale_factor, error_threshold, joint_wmf, device_tail)
     return _finish_sgbm(out, maxDis, gt, mask, scale_factor, error_threshold, verbose, tail)
+
+
+def _reproject(SMDE, out, depth, source):
+    """compute's depth= option: the planes and the cloud of the object's current result into the record."""
+    if depth is False or depth is None:
+        return
+    opt = depth if isinstance(depth, dict) else {"Q": depth}
+    SMDE.setReprojection(opt["Q"], opt.get("crop", (0, 0)), opt.get("z_range"))
+    outputs = capi.PSM_DEPTH_XYZ | capi.PSM_DEPTH_Z | capi.PSM_DEPTH_CLOUD
+    SMDE.Reproject_GPU(source, outputs, use_mask=bool(opt.get("use_mask", False)) and source == capi.PSM_DEPTH_GIF)
+    out["xyz"], out["z"] = SMDE.reprojected()
+    out["cloud"] = SMDE.cloud()
+
+
+def write_ply(path, cloud):
+    """A point cloud (capi.point_dtype() records: DispEst.cloud()) as a binary little-endian PLY file, vertices only: x, y, z as
+    float, red, green, blue as uchar."""
+    cloud = np.asarray(cloud)
+    rec = np.empty(cloud.shape[0], np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")]))
+    for k in ("x", "y", "z"):
+        rec[k] = cloud[k]
+    rec["red"], rec["green"], rec["blue"] = cloud["r"], cloud["g"], cloud["b"]
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % rec.shape[0])
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(rec.tobytes())
 
 
 def _post_process_sgbm(des, outs, gts, masks, scale_factor, error_threshold, joint_wmf, device_tail):

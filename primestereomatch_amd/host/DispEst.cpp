@@ -243,6 +243,30 @@ int DispEst::Score(int source, struct psm_score *rec, Mat *lDisp, Mat *eDisp)
                                          lDisp ? lDisp->step : eDisp->step);
 }
 
+int DispEst::setReprojection(const double Q[16], int cropX, int cropY, float zMin, float zMax)
+{
+    if (ctx.empty()) return 1;
+    if (hipUtil::api().reproject_set_q(ctx[0], Q, cropX, cropY)) return 1;
+    return zMin < zMax ? hipUtil::api().reproject_set_range(ctx[0], zMin, zMax) : 0;
+}
+
+int DispEst::Reproject(int source, uint32_t *count, bool useMask, Mat *xyz, Mat *z)
+{
+    if (ctx.empty() || !count) return 1;
+    const int outputs = PSM_DEPTH_CLOUD | (xyz ? PSM_DEPTH_XYZ : 0) | (z ? PSM_DEPTH_Z : 0);
+    if (hipUtil::api().reproject(ctx[0], source, outputs, useMask ? PSM_DEPTH_USE_MASK : 0, count)) return 1;      // (several devices: ctx[0] holds the gathered maps)
+    if (xyz && (xyz->rows != hei || xyz->cols != wid || xyz->channels != 3 || xyz->depth != PSM_32F)) *xyz = Mat::zeros(hei, wid, 3, PSM_32F);
+    if (z && (z->rows != hei || z->cols != wid || z->channels != 1 || z->depth != PSM_32F)) *z = Mat::zeros(hei, wid, 1, PSM_32F);
+    // (the planes of Mat::zeros are packed; psm_reproject_download takes one stride for both: that of z)
+    if (xyz && hipUtil::api().reproject_download(ctx[0], (float *)xyz->data, nullptr, xyz->step / 3)) return 1;
+    if (z && hipUtil::api().reproject_download(ctx[0], nullptr, (float *)z->data, z->step)) return 1;
+    cloud_.resize(*count);
+    uint32_t written = 0;
+    static_assert(sizeof(Point) == 16, "the cloud's record is 16 bytes");
+    if (hipUtil::api().reproject_download_cloud(ctx[0], cloud_.data(), *count, &written) || written != *count) return 1;
+    return 0;
+}
+
 int DispEst::setSGBMParams(int blockSize, int P1, int P2, int uniquenessRatio, int disp12MaxDiff)
 {
     if (ctx.empty()) return 1;

@@ -151,6 +151,17 @@ public:
     int Score(int source, struct psm_score *rec, Mat *lDisp = nullptr, Mat *eDisp = nullptr);
     static double scoreBP(const struct psm_score &r) { return 100.0 * r.bad / r.pixels; }
     static double scoreAvgErr(const struct psm_score &r) { return r.unit ? ((double)r.err_sum / r.pixels) / r.unit : 0.0; }
+    // From disparity to depth on the device (psm_reproject): cv::reprojectImageTo3D with the Q of cv::stereoRectify - the
+    // reference's camProps.Q (src/StereoMatch.cpp:456-458) - and the compacted, coloured point cloud.  setReprojection: Q (16
+    // doubles, row-major), the (x, y) of this object's image inside the rectified one (the cropBox of :474-481), and the range
+    // z_min < z <= z_max the cloud keeps (zMin >= zMax: the range stays as it is; a new object: (0, FLT_MAX)).  Reproject: `source`
+    // PSM_DEPTH_GIF (the current lDisMap; useMask: without the pixels the L-R check rejected) or PSM_DEPTH_SGM (the map of the
+    // last SGBM_GPU); *count: the kept pixels; xyz (H x W CV_32FC3) / z (H x W CV_32FC1) receive the dense planes if given;
+    // cloud() then holds the records of the kept pixels in raster order.
+    struct Point { float x, y, z; uint8_t b, g, r, a; };
+    int setReprojection(const double Q[16], int cropX = 0, int cropY = 0, float zMin = 0.f, float zMax = 0.f);
+    int Reproject(int source, uint32_t *count, bool useMask = false, Mat *xyz = nullptr, Mat *z = nullptr);
+    const std::vector<Point> &cloud() const { return cloud_; }
 
     // Frame loop (src/main.cpp:64-73) with the PCIe legs next to the kernels (single-device hosts): one call per frame -
     // CostConst (adopts the pair staged by the previous call), stages `next` pair (may be NULL at the end of the stream: its
@@ -193,6 +204,7 @@ private:
     std::vector<psm_ctx *> ctx;  // one per device (row stripes of ceil(H / ndev) rows)
     std::vector<int> y0s, y1s;   // their stripes
     int rect_src_w = 0, rect_src_h = 0;   // setRectification: the eye images' size
+    std::vector<Point> cloud_;            // Reproject: the records of the last call
     bool frameOk(const Mat &vFrame) const;
     bool whole_on_first = false; // the last filter ran on ctx[0] over the whole image (Fast Guided Filter path: no stripes)
 };

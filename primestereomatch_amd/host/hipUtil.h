@@ -69,6 +69,12 @@ struct HipApi {
     int (*score_set_params)(psm_ctx *, int, int, int) = nullptr;
     int (*score)(psm_ctx *, int, struct psm_score *) = nullptr;
     int (*score_download)(psm_ctx *, uint8_t *, uint8_t *, uint8_t *, size_t) = nullptr;
+    // reproject: from disparity to depth, the point cloud
+    int (*reproject_set_q)(psm_ctx *, const double *, int, int) = nullptr;
+    int (*reproject_set_range)(psm_ctx *, float, float) = nullptr;
+    int (*reproject)(psm_ctx *, int, int, int, uint32_t *) = nullptr;
+    int (*reproject_download)(psm_ctx *, float *, float *, size_t) = nullptr;
+    int (*reproject_download_cloud)(psm_ctx *, void *, uint32_t, uint32_t *) = nullptr;
 };
 
 class hipUtil {

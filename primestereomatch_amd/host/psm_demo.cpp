@@ -26,6 +26,10 @@
 // pp 1: after the left-right check also fillInv + wgtMedian (the stages of PP::processDM, src/PP.cpp:405-410); the
 //       post-processed maps go to <out_prefix>_ldisp_pp.raw / _rdisp_pp.raw
 // pp 2: instead JointWMF on the device (JointWMF_GPU: the live body of processDM, src/PP.cpp:417-422), same output files
+// --ply FILE (anywhere on the line; optionally --q q00,q01,...,q33: the 16 entries of cv::stereoRectify's Q, row-major): the left
+// map - without the pixels the L-R check rejected; after pp, if given, all of it - is reprojected on the device (DispEst::Reproject) and the
+// coloured point cloud written to FILE as a binary little-endian PLY.  Without --q: a pinhole camera of focal length W pixels with the
+// principal point in the image centre and baseline 1 (depths in baselines)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -52,8 +56,33 @@ static bool dump(const std::string &path, const unsigned char *p, size_t n)
     return put == n;
 }
 
+static bool write_ply(const char *path, const std::vector<psm::DispEst::Point> &cloud)
+{
+    FILE *f = fopen(path, "wb");
+    if (!f) return false;
+    fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n"
+               "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n", cloud.size());
+    bool ok = true;
+    for (const psm::DispEst::Point &p : cloud) {
+        const float xyz[3] = {p.x, p.y, p.z};
+        const unsigned char rgb[3] = {p.r, p.g, p.b};
+        ok = ok && fwrite(xyz, sizeof xyz, 1, f) == 1 && fwrite(rgb, sizeof rgb, 1, f) == 1;
+    }
+    return fclose(f) == 0 && ok;
+}
+
 int main(int argc, char **argv)
 {
+    // the two named options are taken off the line first; the positional arguments keep their places
+    const char *ply_path = nullptr, *q_text = nullptr;
+    std::vector<char *> args;
+    for (int i = 0; i < argc; ++i) {
+        if (!strcmp(argv[i], "--ply") && i + 1 < argc) ply_path = argv[++i];
+        else if (!strcmp(argv[i], "--q") && i + 1 < argc) q_text = argv[++i];
+        else args.push_back(argv[i]);
+    }
+    argc = (int)args.size();
+    argv = args.data();
     if (argc < 7) {
         fprintf(stderr, "usage: %s left.raw right.raw W H maxDis out_prefix [ndev] [f32|u8] [float_input] [fgf_rate] [pp] [frames] [batch] [ring] [sgbm|sgbm_ref|sgbm_census|-] [gt.raw] [mask.raw|-] [pp]\n", argv[0]);
         return 2;
@@ -130,6 +159,22 @@ int main(int argc, char **argv)
             return 5;
         printf("%%BP = %.2f%% \t Avg Err = %.2f\n", psm::DispEst::scoreBP(rec), psm::DispEst::scoreAvgErr(rec));
         ok = dump(out + "_ldisp_disp.raw", disp.data, (size_t)W * H) && dump(out + "_edisp.raw", emap.data, (size_t)W * H);
+    }
+    if (ok && ply_path) {
+        double Q[16] = {1, 0, 0, -0.5 * W, 0, 1, 0, -0.5 * H, 0, 0, 0, (double)W, 0, 0, 1, 0};
+        if (q_text) {
+            const char *p = q_text;
+            for (int i = 0; i < 16; ++i) {
+                char *end = nullptr;
+                Q[i] = strtod(p, &end);
+                if (end == p || (i < 15 && *end != ',')) { fprintf(stderr, "psm_demo: --q wants 16 numbers separated by commas\n"); return 2; }
+                p = end + 1;
+            }
+        }
+        uint32_t count = 0;
+        if (SMDE.setReprojection(Q) || SMDE.Reproject(PSM_DEPTH_GIF, &count, pp == 0)) return 5;
+        printf("Point cloud:\t %u of %d pixels kept -> %s\n", count, W * H, ply_path);
+        ok = write_ply(ply_path, SMDE.cloud());
     }
     if (ok && frames > 0 && ndev == 1 && !fgf_rate) {
         SMDE.setInputImages(l, r);

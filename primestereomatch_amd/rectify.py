@@ -56,6 +56,27 @@ def scale_calibration(cal: dict, s: float) -> dict:
     return out
 
 
+def scale_q(Q, s: float):
+    """The Q of the same cameras at s times the resolution (next to scale_calibration): -cx, -cy, f and (cx - cx2) / Tx - the last
+    column - scale; 1 / Tx, the baseline's reciprocal, does not."""
+    out = np.array(Q, np.float64).reshape(4, 4).copy()
+    out[0, 3] *= s
+    out[1, 3] *= s
+    out[2, 3] *= s
+    out[3, 3] *= s
+    return out
+
+
+def q_from_projections(P1, P2):
+    """The Q of cv::stereoRectify (horizontal stereo) from its two projection matrices, for calibration files that do not carry
+    it.  Reproduces the Q of tests/golden/zed_extrinsics.yml - a value a real OpenCV wrote - from that file's P1 and P2 bit for
+    bit (tests/test_depth_model.py)."""
+    P1, P2 = np.asarray(P1, np.float64), np.asarray(P2, np.float64)
+    f, cx, cy, cx2 = P1[0, 0], P1[0, 2], P1[1, 2], P2[0, 2]
+    tx = P2[0, 3] / f
+    return np.array([[1.0, 0.0, 0.0, -cx], [0.0, 1.0, 0.0, -cy], [0.0, 0.0, 0.0, f], [0.0, 0.0, -1.0 / tx, (cx - cx2) / tx]], np.float64)
+
+
 def build_maps(M, D, R, P, map_w: int, map_h: int):
     """initUndistortRectifyMap(M, D, R, P, Size(map_w, map_h), CV_16SC2) through psm_rectify_build_maps.
     -> (map_xy [map_h, map_w, 2] int16, map_frac [map_h, map_w] uint16)"""
@@ -81,11 +102,17 @@ class Rectification:
     map_frac: tuple        # (left, right) uint16 [map_h, map_w]
     src_w: int
     src_h: int
-    crop: tuple            # (x, y, w, h)
+    crop: tuple = None     # (x, y, w, h); None: the whole src_w x src_h image
+    Q: object = None       # the 4 x 4 Q of cv::stereoRectify (None: unknown) - DispEst.setRectification then sets the reprojection too
+
+    def __post_init__(self):
+        if self.crop is None:
+            self.crop = (0, 0, int(self.src_w), int(self.src_h))
 
     @classmethod
     def from_calibration(cls, cal: dict, width: int, height: int, crop=None):
         """Both cameras' maps at width x height (the calibration's imgSize: maps and eye images have that size)."""
         l = build_maps(cal["M1"], cal["D1"], cal["R1"], cal["P1"], width, height)
         r = build_maps(cal["M2"], cal["D2"], cal["R2"], cal["P2"], width, height)
-        return cls((l[0], r[0]), (l[1], r[1]), int(width), int(height), tuple(crop) if crop else (0, 0, int(width), int(height)))
+        Q = np.array(cal["Q"], np.float64).reshape(4, 4) if "Q" in cal else q_from_projections(cal["P1"], cal["P2"])
+        return cls((l[0], r[0]), (l[1], r[1]), int(width), int(height), tuple(crop) if crop else (0, 0, int(width), int(height)), Q)
