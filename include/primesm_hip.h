@@ -544,6 +544,47 @@ int psm_wgt_median(psm_ctx *ctx, uint8_t *lmap, uint8_t *rmap, size_t stride);
  * many evaluations (and, on dense maps, sweeps) a call needs can differ from run to run. */
 int psm_wgt_median_stats(psm_ctx *ctx, int sweeps[2], long long evals[2]);
 
+/* PP::processDM's own sequence - lrCheck, fillInv, wgtMedian (src/PP.cpp:17-247,405-410) - of the n contexts ctxs[0..n) in shared
+ * launches: the stages named in `stages` run in the reference's order, every launch once with the pair on a grid axis of its own.
+ * The reference's use on Middlebury-size data is a loop over pairs and datasets (src/main.cpp:64-73, src/StereoMatch.cpp:528-609),
+ * and a single psm_wgt_median is a chain of 20 - 40 small sweeps, each one to four launches near the launch floor, with the device
+ * nearly idle; the chains of different maps are independent, so here the sweeps of all 2 n maps run side by side: one seed launch,
+ * one weights launch, one set of launches per sweep and one look at the counters of all maps per group of sweeps.  A map that has
+ * reached its fixed point has empty lists while the others go on; a group takes the one-launch wave form only when every map's list
+ * is short or finished; maps that leave the sweeps at the cap of 96 are restored and take the dataflow form one by one.
+ * Measured: DESIGN.md 4.5.
+ * Each context uses its own device maps (from psm_disp_select, psm_compute_batch, psm_disp_merge, psm_upload_maps), its own mask
+ * and its own current pair, and afterwards is exactly where its own psm_lr_check(ctx, NULL, NULL, 0), psm_fill_invalid(ctx, NULL,
+ * NULL, 0) and psm_wgt_median(ctx, NULL, NULL, 0) - those of the named stages - would have left it: the same maps and masks bit for
+ * bit (no result depends on a grid's shape: the kernels stride over their lists, and the median's map is the unique fixed point of
+ * the in-place recursion), the same result state, and psm_wgt_median_stats answering per context (-1 for a map that went to the
+ * dataflow form; sweeps and evaluations may differ from run to run as they may in the single call).  The maps stay on the device:
+ * psm_download_maps[_async] per context reads them.
+ * The contexts must agree on width, height, max_disp, device, the depth of the image pair and the weighted-median bits of
+ * PSM_OPT_FLAGS (4194304 dataflow only, 16777216 no cache, 8388608 two sweeps).  Refused otherwise, and for NULL or repeated
+ * contexts, n < 1 or n > 4096, stages naming none or an unknown stage, a context without maps or with stripe-only maps, without a
+ * current mask when PSM_PP_LR_CHECK is not among the stages, and - the median being asked for - without an image pair or with W or
+ * H below 9: psm_last_error(ctxs[0]) names the offending index, nothing has been enqueued, and every context is as before.
+ * The weight cache is decided for the batch as a whole, since a launch takes every map one way: cached when at least one of the
+ * 2 n maps has 8192 invalid pixels, the needs of all maps together stay within psm_wgt_median's bound and no flag forbids it; then
+ * every map's weights are formed, in its own context's buffer.  The maps are the same either way.
+ * The launches run on ctxs[0]'s stream, after everything already queued on the other contexts' streams (a pending
+ * psm_download_maps_async of their maps included) and before anything queued on them later.  Without the median the call never
+ * synchronises with the host under PSM_OPT_ASYNC on ctxs[0]; with it, it synchronises as psm_wgt_median does.  Contexts under
+ * psm_share_streams work as they are.
+ * Buffers stay per context (allocated on first use); the kernels reach them through a device table of n * 256 bytes that ctxs[0]
+ * owns and uploads from page-locked memory only when an entry changed, and the per-sweep counters of all 2 n maps lie in one block of
+ * ctxs[0] (n * 1568 bytes, and twice as much page-locked memory), so one small copy kernel snapshots all of them.  PSM_STAGE_PP
+ * of every context receives the batch's wall time; with PSM_OPT_PROFILE 1 on ctxs[0], PSM_K_LRC / PSM_K_WMF of ctxs[0] count the
+ * batch's launches. */
+/* (below) The validity masks of the current maps as the last psm_lr_check, psm_post_process_batch or psm_upload_maps left them, to
+ * the caller's rows (stride 0: packed).  Needs a current mask.  Complete on return. */
+#define PSM_PP_LR_CHECK   1
+#define PSM_PP_FILL       2
+#define PSM_PP_WGT_MEDIAN 4
+int psm_post_process_batch(psm_ctx *const *ctxs, int n, int stages);
+int psm_download_valid(psm_ctx *ctx, uint8_t *lvalid, uint8_t *rvalid, size_t stride);
+
 /* The live post-filter of the reference: PP::processDM runs JointWMF::filter on both maps with the 8-bit colour image as
  * the feature (src/PP.cpp:402-424, include/JointWMF.h), which is what PostProcess_GPU / PostProcess_CPU compute
  * (src/DispEst.cpp:330-344).  Filters the context's device maps in place (lDisMap = JointWMF::filter(...)), the left map

@@ -26,6 +26,8 @@ PSM_FLAG_MATERIALISE_COSTS, PSM_FLAG_FGF_STORE, PSM_FLAG_STORE_FILTERED = 128, 4
 PSM_FLAG_TWO_PHASE_ON, PSM_FLAG_TWO_PHASE_OFF = 1048576, 2097152
 PSM_FLAG_WMF_DATAFLOW, PSM_FLAG_WMF_TWO_SWEEPS, PSM_FLAG_WMF_NO_CACHE = 4194304, 8388608, 16777216
 PSM_FLAG_F32_TOL = 33554432
+# psm_post_process_batch: the stages
+PSM_PP_LR_CHECK, PSM_PP_FILL, PSM_PP_WGT_MEDIAN = 1, 2, 4
 PSM_FLAG_FMA_SOLVE = 67108864
 # the score stage: sources, mask modes (include/StereoMatch.h), record flags
 PSM_SCORE_GIF, PSM_SCORE_SGM, PSM_SCORE_SGM_INT = 0, 1, 2
@@ -99,6 +101,8 @@ SYMBOLS = [
     ("psm_fill_invalid", _i, [_vp, _vp, _vp, _sz]),
     ("psm_wgt_median", _i, [_vp, _vp, _vp, _sz]),
     ("psm_wgt_median_stats", _i, [_vp, _vp, _vp]),
+    ("psm_post_process_batch", _i, [C.POINTER(_vp), _i, _i]),
+    ("psm_download_valid", _i, [_vp, _vp, _vp, _sz]),
     ("psm_joint_wmf", _i, [_vp, _i, C.c_float, _i, _i, _vp, _vp, _sz]),
     ("psm_joint_wmf_set_clusters", _i, [_vp, _i, _i, _vp, _vp]),
     ("psm_joint_wmf_clusters", _i, [_vp, _i, _pi, _vp, _vp, _pi]),

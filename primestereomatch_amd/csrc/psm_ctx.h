@@ -6,7 +6,8 @@
 //                       of the fused kernel runs, materialisation
 //   psm_api_select.cpp  DispSelect: maps, packed minima, row stripes and disparity shards
 //   psm_api_pp.cpp      post-processing: L-R check, invalid fill, weighted median (psm::WmState; its sweep schedule, block
-//                       layout and cache decision are the host-only psm_wm_sched.h)
+//                       layout and cache decision are the host-only psm_wm_sched.h), and the three of several contexts in
+//                       shared launches (psm_post_process_batch, psm::WmBatch)
 //   psm_api_batch.cpp   several Middlebury-size pairs per launch (psm_compute_batch); what every batch entry point shares: the
 //                       device table of the members' records (psm::DevTable), the join and fork of the members' streams, the
 //                       member checks
@@ -135,6 +136,17 @@ struct WmState {
     long long evals[2] = {0, 0};
 };
 
+// psm_post_process_batch (psm_api_pp.cpp; this context as the first of the call): the device table of the members' PpPair records,
+// and - the median being among the stages - the counters of all 2 n maps in one block, so that one copy kernel snapshots them all
+// into `pin`.  Every other buffer of the median stays the member's own (WmState).  Freed by wm_free alone.
+struct WmBatch {
+    DevTable tab;
+    int *cnt = nullptr;                            // [cap] x WM_NCNT counters, map 2 i + s: side s of member i
+    int *pin = nullptr;                            // page-locked snapshots of them: two slots of cap x WM_NCNT ints
+    size_t cap = 0;                                // maps
+    hipEvent_t ev[2] = {nullptr, nullptr};         // the snapshot into a slot has executed
+};
+
 // psm_score (psm_api_score.cpp): parameters, the dataset's truth (kept until replaced or cleared), and the stage's scratch -
 // display and error planes, counters, their page-locked slot - allocated on first use and given back by psm_release_scratch.
 struct ScoreState {
@@ -225,6 +237,7 @@ struct psm_ctx {
     uint8_t *pinned = nullptr;          // [2][H][W] page-locked bounce buffer for map / mask downloads (on first use)
     uint8_t *pinned2 = nullptr;         // second bounce buffer: psm_download_maps_async of frame i while frame i-1 is being read
     psm::WmState wm;
+    psm::WmBatch wmb;
     // psm_joint_wmf (psm_api_jwmf.cpp): one device block for both sides (psm::JwScratch), allocated on first use
     uint8_t *jw = nullptr;
     psm::JwClust jw_cl[2];

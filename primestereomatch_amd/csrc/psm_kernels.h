@@ -152,6 +152,19 @@ struct WmPair { WmSide s[2]; };
 void launch_wm_seed(hipStream_t s, const WmPair &p, int W, int H);
 void launch_wm_sweep(hipStream_t s, const WmPair &p, int W, int H, int maxDis, int sw, bool cached, bool tail);
 void launch_wm_weights(hipStream_t s, const float4 *g1, int W, int H, int right, const int *inv, const int *n_inv, int n, float *wts, int *slot_of);
+// A member of psm_post_process_batch as the _b entries of the kernels above find it in the batch's device table (the pair on a grid
+// axis of its own): the sweep state of its two maps - of which the L-R check and the fill read cur and valid alone - and the masks as
+// the L-R check writes them.  A side's cnt lies in the counter block of the batch's first context, the counters of all maps one
+// behind the other; wts of every side is set when the batch is cached.
+struct PpPair {
+    WmPair wm;
+    uint8_t *lv, *rv;
+};
+void launch_lr_check_b(hipStream_t s, const PpPair *tab, int n, int W, int H);
+void launch_fill_inv_b(hipStream_t s, const PpPair *tab, int n, int W, int H);
+void launch_wm_seed_b(hipStream_t s, const PpPair *tab, int n, int W, int H);
+void launch_wm_weights_b(hipStream_t s, const PpPair *tab, int n, int W, int H, int n_max);
+void launch_wm_sweep_b(hipStream_t s, const PpPair *tab, int n, int W, int H, int maxDis, int sw, bool cached, bool tail);
 
 // ---- Fast Guided Filter variant (psm_fgf.hip); sub = subsample rate, small planes are (H/sub) x (W/sub) ----
 // g1 -> subsampled guidance ism, its means msm and the inverse covariance planes v1 = {irr,irg,irb,igg}, v2 = {igb,ibb}

@@ -797,8 +797,8 @@ void launch_merge_batch(hipStream_t s, const PcPair *tab, int npairs, int W, int
 // ------------------------------------------------------------------------------------------
 // PP lrCheck (src/PP.cpp:17-50)
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_lr_check(const uint8_t *__restrict__ l, const uint8_t *__restrict__ r, int W, int H,
-                                                 uint8_t *__restrict__ lv, uint8_t *__restrict__ rv)
+__device__ __forceinline__ void lr_check_px(const uint8_t *__restrict__ l, const uint8_t *__restrict__ r, int W, uint8_t *__restrict__ lv,
+                                            uint8_t *__restrict__ rv)
 {
     int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= W) return;
@@ -812,6 +812,17 @@ __global__ __launch_bounds__(256) void k_lr_check(const uint8_t *__restrict__ l,
     lDep = lr[lLoc];
     rv[(size_t)y * W + x] = (rDep == lDep && rDep >= 2) ? 1 : 0;
 }
+__global__ __launch_bounds__(256) void k_lr_check(const uint8_t *__restrict__ l, const uint8_t *__restrict__ r, int W, int H,
+                                                 uint8_t *__restrict__ lv, uint8_t *__restrict__ rv)
+{
+    lr_check_px(l, r, W, lv, rv);
+}
+// ... of the pairs of a batch: the pair on blockIdx.z, its maps and masks from the device table (psm_post_process_batch)
+__global__ __launch_bounds__(256) void k_lr_check_b(const PpPair *__restrict__ tab, int W)
+{
+    const PpPair &p = tab[blockIdx.z];
+    lr_check_px(p.wm.s[0].cur, p.wm.s[1].cur, W, p.lv, p.rv);
+}
 
 // ------------------------------------------------------------------------------------------
 // PP fillInv (src/PP.cpp:52-143): every invalid pixel takes the smaller disparity of its nearest
@@ -822,13 +833,10 @@ __global__ __launch_bounds__(256) void k_lr_check(const uint8_t *__restrict__ l,
 // of the validity bytes (highest set bit below / lowest above the lane, a carry across the 64-pixel chunks), its value through a
 // lane read: no LDS scan, no barrier (the block scan of rounds 2 - 5 went through 2 x 8 x 16 barriers per row: 39 us a map at
 // 1080p).  The row is read once, 16 chunks' loads in flight at a time; the pass from the right works from LDS.
-__global__ __launch_bounds__(64) void k_fill_inv(uint8_t *__restrict__ dis0, const uint8_t *__restrict__ valid0, size_t side, int W)
-{
-    extern __shared__ short row[];        // [W] the pixel's value, -1: invalid | [W] value of the nearest valid pixel to the left, -1: none
+__device__ __forceinline__ void fill_inv_row(short *row, uint8_t *__restrict__ d, const uint8_t *__restrict__ v, int W)
+{   // row: [W] the pixel's value, -1: invalid | [W] value of the nearest valid pixel to the left, -1: none; d, v: the row's map and mask
     short *sv = row, *lval = row + W;
-    const int y = blockIdx.x, lane = threadIdx.x;
-    uint8_t *d = dis0 + blockIdx.y * side + (size_t)y * W;
-    const uint8_t *v = valid0 + blockIdx.y * side + (size_t)y * W;
+    const int lane = threadIdx.x;
     const unsigned long long below = (1ull << lane) - 1ull, above = lane == 63 ? 0ull : ~((2ull << lane) - 1ull);
     constexpr int NC = 16;
     int carry = -1;
@@ -871,11 +879,34 @@ __global__ __launch_bounds__(64) void k_fill_inv(uint8_t *__restrict__ dis0, con
         if (m) carry = __builtin_amdgcn_readlane(val, __builtin_ctzll(m));
     }
 }
+__global__ __launch_bounds__(64) void k_fill_inv(uint8_t *__restrict__ dis0, const uint8_t *__restrict__ valid0, size_t side, int W)
+{
+    extern __shared__ short row[];
+    const size_t at = blockIdx.y * side + (size_t)blockIdx.x * W;
+    fill_inv_row(row, dis0 + at, valid0 + at, W);
+}
+__global__ __launch_bounds__(64) void k_fill_inv_b(const PpPair *__restrict__ tab, int W)
+{
+    extern __shared__ short row[];
+    const WmSide &a = tab[blockIdx.z].wm.s[blockIdx.y];
+    const size_t at = (size_t)blockIdx.x * W;
+    fill_inv_row(row, a.cur + at, a.valid + at, W);
+}
 
 // both maps of a pair: dis / valid of the right map lie `side` bytes behind the left map's
 void launch_fill_inv(hipStream_t s, uint8_t *dis, const uint8_t *valid, size_t side, int W, int H)
 {
     hipLaunchKernelGGL(k_fill_inv, dim3(H, 2), dim3(64), 2 * (size_t)W * sizeof(short), s, dis, valid, side, W);
+}
+
+void launch_fill_inv_b(hipStream_t s, const PpPair *tab, int n, int W, int H)
+{
+    hipLaunchKernelGGL(k_fill_inv_b, dim3(H, 2, n), dim3(64), 2 * (size_t)W * sizeof(short), s, tab, W);
+}
+
+void launch_lr_check_b(hipStream_t s, const PpPair *tab, int n, int W, int H)
+{
+    hipLaunchKernelGGL(k_lr_check_b, dim3((W + 255) / 256, H, n), dim3(256), 0, s, tab, W);
 }
 
 void launch_lr_check(hipStream_t s, const uint8_t *l, const uint8_t *r, int W, int H, uint8_t *lv, uint8_t *rv)

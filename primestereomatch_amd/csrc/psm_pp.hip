@@ -256,9 +256,8 @@ __device__ __forceinline__ int wm_append(int *cnt, bool want)
 // wave), the input copy `orig` the later taps of a window are read from, and the per-pixel sweep state (stamp, the gather form's
 // byte maps) zeroed - round 6: one launch where seeds, copies and fills were eight.
 constexpr int WM_SEED_PER = 16;
-__global__ __launch_bounds__(256) void k_wm_seed(WmPair pr, int HW, int nb)
+__device__ __forceinline__ void wm_seed(const WmSide &a, int HW, int nb)
 {   // nb: length of the scratch planes (HW rounded up to whole blocks of 256 pixels)
-    const WmSide &a = pr.s[blockIdx.y];
     const int lane = threadIdx.x & 63;
     const int base = (blockIdx.x * blockDim.x + threadIdx.x) * WM_SEED_PER;
     typedef unsigned wm_u32 __attribute__((aligned(1)));
@@ -315,6 +314,9 @@ __global__ __launch_bounds__(256) void k_wm_seed(WmPair pr, int HW, int nb)
         a.inv[slot++] = base + k;
     }
 }
+__global__ __launch_bounds__(256) void k_wm_seed(WmPair pr, int HW, int nb) { wm_seed(pr.s[blockIdx.y], HW, nb); }
+// ... of the pairs of a batch: the pair on blockIdx.z, its record from the device table (psm_post_process_batch)
+__global__ __launch_bounds__(256) void k_wm_seed_b(const PpPair *__restrict__ tab, int HW, int nb) { wm_seed(tab[blockIdx.z].wm.s[blockIdx.y], HW, nb); }
 
 // One evaluation of f per LANE (round 3; round 2 spent a whole wave per pixel: every lane scanned all 361 taps for "its"
 // bins - 361 x 64 lane-steps for 722 useful additions).  A lane walks the 361 taps of its own pixel in window raster order:
@@ -348,8 +350,8 @@ __device__ __forceinline__ size_t wm_widx(int slot, int row, int j)
 }
 
 template <bool RIGHT>
-__global__ __launch_bounds__(256) void k_wm_weights(const float4 *__restrict__ g1, const int *__restrict__ inv, const int *n_inv,
-                                                   float4 *__restrict__ wts, int *__restrict__ slot_of, int W, int H)
+__device__ __forceinline__ void wm_weights(const float4 *__restrict__ g1, const int *__restrict__ inv, const int *n_inv,
+                                           float4 *__restrict__ wts, int *__restrict__ slot_of, int W, int H)
 {   // one thread per (window row, invalid pixel): a wave = 64 consecutive pixels of the list, one window row
     const int n = *n_inv;
     const long long nblk = (n + 63) / 64, total = nblk * WM_K * 64;
@@ -376,6 +378,19 @@ __global__ __launch_bounds__(256) void k_wm_weights(const float4 *__restrict__ g
 #pragma unroll
         for (int k = 0; k < WM_WROW / 4; ++k) wts[wm_widx(slot, r, k)] = make_float4(wk[4 * k], wk[4 * k + 1], wk[4 * k + 2], wk[4 * k + 3]);
     }
+}
+template <bool RIGHT>
+__global__ __launch_bounds__(256) void k_wm_weights(const float4 *__restrict__ g1, const int *__restrict__ inv, const int *n_inv,
+                                                   float4 *__restrict__ wts, int *__restrict__ slot_of, int W, int H)
+{
+    wm_weights<RIGHT>(g1, inv, n_inv, wts, slot_of, W, H);
+}
+// ... of every side of a batch that has a cache (blockIdx.y: the side, blockIdx.z: the pair); a side without invalid pixels returns at once
+__global__ __launch_bounds__(256) void k_wm_weights_b(const PpPair *__restrict__ tab, int W, int H)
+{
+    const WmSide &a = tab[blockIdx.z].wm.s[blockIdx.y];
+    if (blockIdx.y == 0) wm_weights<false>(a.g1, a.inv, a.cnt, (float4 *)a.wts, a.slot_of, W, H);
+    else wm_weights<true>(a.g1, a.inv, a.cnt, (float4 *)a.wts, a.slot_of, W, H);
 }
 
 template <bool RIGHT, bool CACHED>
@@ -561,10 +576,8 @@ __device__ __forceinline__ void wm_eval_lanes(float *hist, const uint8_t *cur, c
 
 // sweep `sw` of both maps (blockIdx.y); the cached form does not depend on the map (the weights kernel did)
 template <bool CACHED>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_wm_eval(WmPair pr, int sw, int W, int H, int maxDis)
+__device__ __forceinline__ void wm_eval_side(float *hist, const WmSide &a, int sw, int W, int H, int maxDis)
 {
-    extern __shared__ float hist[];
-    const WmSide &a = pr.s[blockIdx.y];
     const int *act = sw ? a.list[(sw + 1) & 1] : a.inv;
     if (CACHED || blockIdx.y == 0)
         wm_eval_lanes<false, CACHED>(hist, a.cur, a.orig, a.g1, act, a.cnt + 2 * sw, a.newv, a.chg, a.cnt + 2 * sw + 1, W, H, maxDis, (const float4 *)a.wts, a.slot_of,
@@ -572,6 +585,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
     else
         wm_eval_lanes<true, CACHED>(hist, a.cur, a.orig, a.g1, act, a.cnt + 2 * sw, a.newv, a.chg, a.cnt + 2 * sw + 1, W, H, maxDis, (const float4 *)a.wts, a.slot_of,
                                     a.cur, a.chgb, a.rowany, sw + 1);
+}
+template <bool CACHED>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_wm_eval(WmPair pr, int sw, int W, int H, int maxDis)
+{
+    extern __shared__ float hist[];
+    wm_eval_side<CACHED>(hist, pr.s[blockIdx.y], sw, W, H, maxDis);
+}
+template <bool CACHED>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_wm_eval_b(const PpPair *__restrict__ tab, int sw, int W, int H, int maxDis)
+{
+    extern __shared__ float hist[];
+    wm_eval_side<CACHED>(hist, tab[blockIdx.z].wm.s[blockIdx.y], sw, W, H, maxDis);
 }
 
 // Short active lists (the tail sweeps: a few hundred pixels whose evaluation latency is what the sweep costs): one WAVE per
@@ -730,9 +755,8 @@ __device__ __forceinline__ void wm_eval_wave(const uint8_t *cur, const uint8_t *
 }
 
 template <int NB, bool CACHED>
-__global__ __launch_bounds__(64) void k_wm_eval_w(WmPair pr, int sw, int W, int H, int maxDis, int force)
+__device__ __forceinline__ void wm_eval_w_side(const WmSide &a, int sw, int W, int H, int maxDis, int force)
 {
-    const WmSide &a = pr.s[blockIdx.y];
     const int *act = sw ? a.list[(sw + 1) & 1] : a.inv;
     uint8_t *const curw = force ? a.cur : nullptr;       // (force = the tail sweeps: evaluation and dependents in this one launch)
     if (CACHED || blockIdx.y == 0)
@@ -741,6 +765,16 @@ __global__ __launch_bounds__(64) void k_wm_eval_w(WmPair pr, int sw, int W, int 
     else
         wm_eval_wave<true, NB, CACHED>(a.cur, a.orig, a.g1, act, a.cnt + 2 * sw, a.newv, a.chg, a.cnt + 2 * sw + 1, W, H, maxDis, a.wts, a.slot_of, force, blockIdx.x, gridDim.x,
                                        curw, a.valid, a.stamp, sw + 1, a.list[sw & 1], a.cnt + 2 * (sw + 1));
+}
+template <int NB, bool CACHED>
+__global__ __launch_bounds__(64) void k_wm_eval_w(WmPair pr, int sw, int W, int H, int maxDis, int force)
+{
+    wm_eval_w_side<NB, CACHED>(pr.s[blockIdx.y], sw, W, H, maxDis, force);
+}
+template <int NB, bool CACHED>
+__global__ __launch_bounds__(64) void k_wm_eval_w_b(const PpPair *__restrict__ tab, int sw, int W, int H, int maxDis, int force)
+{
+    wm_eval_w_side<NB, CACHED>(tab[blockIdx.z].wm.s[blockIdx.y], sw, W, H, maxDis, force);
 }
 
 // Which pixels does the next sweep evaluate?  Every invalid pixel that has a pixel changed by this sweep among the EARLIER taps
@@ -754,9 +788,8 @@ __global__ __launch_bounds__(64) void k_wm_eval_w(WmPair pr, int sw, int W, int 
 // (measured at 1080p, both maps per launch: marks + gather pass ~0.07 ms whatever changed, the scatter pass ~12 ns per changed pixel)
 __device__ __forceinline__ bool wm_gather_form(int n_chg, int n_inv) { return n_inv >= 4096 && (long long)n_chg * 80 >= n_inv; }
 
-__global__ __launch_bounds__(256) void k_wm_gather(WmPair pr, int sw, int W, int H)
+__device__ __forceinline__ void wm_gather(const WmSide &a, int sw, int W, int H)
 {
-    const WmSide &a = pr.s[blockIdx.y];
     const int *__restrict__ inv = a.inv, *n_inv = a.cnt, *n_chg = a.cnt + 2 * sw + 1;
     const uint8_t *__restrict__ chgb = a.chgb, *__restrict__ rowany = a.rowany;
     const int mark = sw + 1;
@@ -781,6 +814,8 @@ __global__ __launch_bounds__(256) void k_wm_gather(WmPair pr, int sw, int W, int
         if (want) next[slot] = pix;
     }
 }
+__global__ __launch_bounds__(256) void k_wm_gather(WmPair pr, int sw, int W, int H) { wm_gather(pr.s[blockIdx.y], sw, W, H); }
+__global__ __launch_bounds__(256) void k_wm_gather_b(const PpPair *__restrict__ tab, int sw, int W, int H) { wm_gather(tab[blockIdx.z].wm.s[blockIdx.y], sw, W, H); }
 
 // the changed pixels take their new value; every invalid pixel LATER in raster order that has one of them in its window
 // is evaluated again in the next sweep (stamp: once)
@@ -826,11 +861,15 @@ __device__ __forceinline__ void wm_apply(uint8_t *__restrict__ cur, const uint8_
     }
 }
 
-__global__ __launch_bounds__(64) void k_wm_apply(WmPair pr, int sw, int W, int H, int force)
+__device__ __forceinline__ void wm_apply_side(const WmSide &a, int sw, int W, int H, int force)
 {
-    const WmSide &a = pr.s[blockIdx.y];
     wm_apply(a.cur, a.newv, a.valid, a.chg, a.cnt + 2 * sw + 1, a.cnt, a.stamp, sw + 1, a.list[sw & 1], a.cnt + 2 * (sw + 1), W, H, a.chgb, a.rowany, force,
              blockIdx.x, gridDim.x, a.cnt + 2 * sw);
+}
+__global__ __launch_bounds__(64) void k_wm_apply(WmPair pr, int sw, int W, int H, int force) { wm_apply_side(pr.s[blockIdx.y], sw, W, H, force); }
+__global__ __launch_bounds__(64) void k_wm_apply_b(const PpPair *__restrict__ tab, int sw, int W, int H, int force)
+{
+    wm_apply_side(tab[blockIdx.z].wm.s[blockIdx.y], sw, W, H, force);
 }
 
 // f(std::integral_constant<int, NB>) for nb = ceil(maxDis / 64) histogram bins per lane: the instantiations are NB 1..4 (D <= 256)
@@ -885,6 +924,55 @@ void launch_wm_sweep(hipStream_t s, const WmPair &p, int W, int H, int maxDis, i
     if (tail) return;               // (the forced wave form applied its changes and queued their dependents itself)
     hipLaunchKernelGGL(k_wm_apply, ga, dim3(64), 0, s, p, sw, W, H, force);
     hipLaunchKernelGGL(k_wm_gather, dim3(2048, 2), dim3(256), 0, s, p, sw, W, H);
+}
+
+// ---- The same launches for the n pairs of a device table (psm_post_process_batch).  No map depends on a grid's shape: every
+// kernel strides over its lists with gridDim.x.  A pair's share of grid.x shrinks as n grows, so that a launch stays at about what a
+// single pair's launch puts on the chip (the evaluations: resident workgroups; the wave form, apply and gather: their fixed grids)
+// and never falls below an eighth of it per pair - the floor keeps a long list beside empty ones from crawling.
+static int wm_share(int single, int n)
+{
+    const int floor_ = single / 8 > 1 ? single / 8 : 1;
+    const int x = (single + n - 1) / n;
+    return x > floor_ ? x : floor_;
+}
+
+void launch_wm_seed_b(hipStream_t s, const PpPair *tab, int n, int W, int H)
+{
+    const int HW = W * H, per_block = 256 * WM_SEED_PER;
+    hipLaunchKernelGGL(k_wm_seed_b, dim3((HW + per_block - 1) / per_block, 2, n), dim3(256), 0, s, tab, HW, (HW + 255) / 256 * 256);
+}
+
+// n_max: an upper bound of the invalid pixels of any side
+void launch_wm_weights_b(hipStream_t s, const PpPair *tab, int n, int W, int H, int n_max)
+{
+    const long long threads = (long long)((n_max + 63) / 64) * WM_K * 64;
+    const long long want = (threads + 255) / 256;
+    const int cap = wm_share(65536, n);
+    hipLaunchKernelGGL(k_wm_weights_b, dim3((unsigned)(want < cap ? (want > 0 ? want : 1) : cap), 2, n), dim3(256), 0, s, tab, W, H);
+}
+
+void launch_wm_sweep_b(hipStream_t s, const PpPair *tab, int n, int W, int H, int maxDis, int sw, bool cached, bool tail)
+{
+    const size_t lds = (size_t)maxDis * 64 * sizeof(float);
+    const PcDev dev = pc_dev();
+    const int per_cu = (int)(160 * 1024 / (lds > 16384 ? lds : 16384));
+    const dim3 ge(wm_share(dev.nxcd * dev.cus_per_xcd * (per_cu < 1 ? 1 : per_cu), n), 2, n);
+    const int force = tail ? 1 : 0;
+    if (!tail) {
+        if (cached) hipLaunchKernelGGL(k_wm_eval_b<true>, ge, dim3(64), lds, s, tab, sw, W, H, maxDis);
+        else hipLaunchKernelGGL(k_wm_eval_b<false>, ge, dim3(64), lds, s, tab, sw, W, H, maxDis);
+    }
+    const int nb = (maxDis + 63) / 64;
+    const dim3 gw(wm_share(8192, n), 2, n);
+    wm_with_nb(nb, [&](auto nbv) {
+        constexpr int NB = decltype(nbv)::value;
+        if (cached) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wm_eval_w_b<NB, true>), gw, dim3(64), 0, s, tab, sw, W, H, maxDis, force);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wm_eval_w_b<NB, false>), gw, dim3(64), 0, s, tab, sw, W, H, maxDis, force);
+    });
+    if (tail) return;
+    hipLaunchKernelGGL(k_wm_apply_b, dim3(wm_share(2048, n), 2, n), dim3(64), 0, s, tab, sw, W, H, force);
+    hipLaunchKernelGGL(k_wm_gather_b, dim3(wm_share(2048, n), 2, n), dim3(256), 0, s, tab, sw, W, H);
 }
 
 void launch_wgt_median(hipStream_t s, uint8_t *dis, const uint8_t *valid, const float4 *g1, int W, int H, int maxDis, int right,

@@ -7,6 +7,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace psm {
 
@@ -119,6 +120,80 @@ inline WmCachePlan wm_cache_plan(const int n0[2], size_t avail, unsigned flags)
     const size_t tot = need[0] + need[1];
     const bool none = (n0[0] < WM_LANE_MIN && n0[1] < WM_LANE_MIN) || tot * sizeof(float) > max_bytes || (flags & PSM_FLAG_WMF_NO_CACHE);
     return WmCachePlan{none ? 0 : tot, need[0]};
+}
+
+// ---- The maps of several pairs in shared launches (psm_post_process_batch, psm_api_pp_batch.cpp): m = 2 n maps, map 2 i + s being
+// side s of pair i; their counters lie one behind the other in one block (wm_counters(snap, map)), so one snapshot shows them all.
+// The rules per map are WmSched's - done, tail, the fixed point at the first sweep that changed nothing, sweeps and evals - and a
+// launch takes every map one way: a group is of the one-launch wave form only when EVERY map is tail or done, and the loop ends
+// when every map is done or the cap is reached.  With m = 2 it decides what WmSched decides, group for group
+// (tests/test_wm_batch_sched.py).  The driver's loop is WmSched's.
+struct WmBatchSched {
+    int cap;
+    int m;                              // maps
+    int sw = 0, unread = 0;
+    int upto[2] = {0, 0};
+    std::vector<char> done, tail;
+    std::vector<int> sweeps;            // -1: a map left to the dataflow form
+    std::vector<long long> evals;
+
+    WmBatchSched(int maps, unsigned flags)
+        : cap((flags & PSM_FLAG_WMF_TWO_SWEEPS) ? 2 : WM_SWEEP_CAP), m(maps), done(maps, 0), tail(maps, 0), sweeps(maps, -1), evals(maps, 0) {}
+    bool more() const { return sw < cap; }
+    bool all_done() const
+    {
+        for (int i = 0; i < m; ++i)
+            if (!done[i]) return false;
+        return true;
+    }
+    WmGroup next_group() const
+    {
+        bool short_lists = true;
+        for (int i = 0; i < m; ++i) short_lists = short_lists && (tail[i] || done[i]);
+        const int chk = short_lists ? 8 : 2;
+        return WmGroup{sw, sw + chk < cap ? sw + chk : cap, short_lists};
+    }
+    void launched(const WmGroup &g, int slot) { sw = g.end; upto[slot] = sw; ++unread; }
+    // snap: the counters of all m maps behind the group of `slot`; false when every map is finished or nothing more is queued
+    bool read(int slot, const int *snap)
+    {
+        const int seen = upto[slot];
+        for (int i = 0; i < m; ++i) {
+            if (done[i]) continue;
+            const int *cnt = wm_counters(snap, i);
+            long long ev = 0;
+            for (int k = 0; k < seen; ++k) {
+                ev += wm_active(cnt, k);
+                if (wm_changed(cnt, k) == 0) {
+                    done[i] = 1;
+                    sweeps[i] = k + 1;
+                    evals[i] = ev;
+                    break;
+                }
+            }
+            tail[i] = seen < cap && wm_next(cnt, seen - 1) < WM_LANE_MIN;
+        }
+        return --unread > 0 && !all_done();
+    }
+};
+
+// The cache decision of a batch is one for all its maps, since a launch takes every map one way: cached only if at least one of the
+// m sides has WM_LANE_MIN invalid pixels, the sum of all sides' needs stays within wm_cache_plan's bound and no flag forbids it -
+// then EVERY side gets its weights (need[i] floats: whole blocks of 64 pixels; a context's two sides lie one behind the other in its
+// own buffer).  The maps are the same either way.  Returns the floats of all sides, 0: no cache.
+inline size_t wm_side_need(int n0) { return (size_t)((n0 + 63) / 64 * 64) * WM_WPIX; }
+inline size_t wm_batch_cache_plan(const int *n0, int m, size_t avail, unsigned flags)
+{
+    size_t max_bytes = (size_t)12 << 30;
+    if (avail / 2 < max_bytes) max_bytes = avail / 2;
+    size_t tot = 0;
+    bool any = false;
+    for (int i = 0; i < m; ++i) {
+        tot += wm_side_need(n0[i]);
+        any = any || n0[i] >= WM_LANE_MIN;
+    }
+    const bool none = !any || tot * sizeof(float) > max_bytes || (flags & PSM_FLAG_WMF_NO_CACHE);
+    return none ? 0 : tot;
 }
 
 }  // namespace psm

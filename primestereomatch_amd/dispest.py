@@ -755,6 +755,23 @@ def joint_wmf_batch_device(des, radius: int = 0, sigma: float = 0.0, n_clusters:
                des[0]._h, "joint_wmf_batch")
 
 
+def post_process_batch(des, lr_check: bool = True, fill: bool = False, median: bool = False, download: bool = True):
+    """The named stages of PP::processDM's own sequence - LRCheck_GPU, FillInv_GPU, WgtMedian_GPU, in that order - of several DispEst
+    objects of one geometry in shared launches (psm_post_process_batch): each object's device maps and masks with its own pair, the
+    sweep chains of all maps side by side.  Every object afterwards behaves as after its own calls (wgt_median_stats() answers per
+    object); download: every object's lDisMap / rDisMap / lValid / rValid receive its results."""
+    des = list(des)
+    if not des:
+        return
+    stages = (capi.PSM_PP_LR_CHECK if lr_check else 0) | (capi.PSM_PP_FILL if fill else 0) | (capi.PSM_PP_WGT_MEDIAN if median else 0)
+    arr = (C.c_void_p * len(des))(*[d._h for d in des])
+    capi.check(des[0]._lib.psm_post_process_batch(arr, len(des), stages), des[0]._h, "post_process_batch")
+    if download:
+        for d in des:
+            d.download_maps()
+            d._ck(d._lib.psm_download_valid(d._h, _ptr(d.lValid), _ptr(d.rValid), d.wid), "post_process_batch")
+
+
 def score_batch(des, source: int = capi.PSM_SCORE_GIF):
     """Score_GPU of several DispEst objects of one geometry in one set of launches (psm_score_batch): each object's current result
     against its own truth -> the list of Score_GPU's dicts.  Every object afterwards behaves as after its own Score_GPU

@@ -63,13 +63,16 @@ def compute(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, error_t
 
 
 def compute_batch(pairs, maxDis=64, gts=None, masks=None, scale_factor=4, error_threshold=4, dtype="f32", post_process=True,
-                  joint_wmf=False, verbose=False, device_tail=False):
+                  joint_wmf=False, verbose=False, device_tail=False, process_dm=False):
     """compute() for a list of (l_bgr, r_bgr) uint8 pairs of one size in shared launches: the reference's loop over pairs and
     datasets (src/main.cpp:64-73, src/StereoMatch.cpp:528-609) on the live STEREO_GIF branch.  dispest.compute_batch (CostConst +
-    CostFilter + DispSelect of all pairs), then per object the L-R check when post_process, then dispest.joint_wmf_batch when
+    CostFilter + DispSelect of all pairs), then the L-R check of all pairs when post_process, then dispest.joint_wmf_batch when
     joint_wmf (the live processDM body on every pair's maps, the clustering chains of all images side by side).  gts / masks: one
     per pair (or None).  -> a list of compute's records; the stage times are each object's (a batch's wall time is charged to
-    every member).  device_tail: display maps and metric of all pairs from the device in one set of launches (dispest.score_batch)."""
+    every member).  device_tail: display maps and metric of all pairs from the device in one set of launches (dispest.score_batch).
+    process_dm: compute()'s - after the L-R check the rest of PP::processDM's plain sequence, fillInv and wgtMedian, of all pairs in
+    shared launches (dispest.post_process_batch; the sweep chains of all maps side by side); the maps before it stay in
+    lDisMap_raw / rDisMap_raw.  The L-R check of post_process goes through the same entry: the same bits."""
     if not pairs:
         return []
     frames = []
@@ -84,11 +87,13 @@ def compute_batch(pairs, maxDis=64, gts=None, masks=None, scale_factor=4, error_
         dispest.compute_batch(des)
         for d, out in zip(des, outs):
             d.download_maps()
-            if post_process:
-                d.LRCheck_GPU()
-                out["lValid"], out["rValid"] = d.lValid.copy(), d.rValid.copy()
-            if joint_wmf:
+            if joint_wmf or process_dm:
                 out["lDisMap_raw"], out["rDisMap_raw"] = d.lDisMap.copy(), d.rDisMap.copy()
+        if post_process or process_dm:
+            # (one call: the fill and the median leave the masks as the L-R check wrote them)
+            dispest.post_process_batch(des, lr_check=True, fill=process_dm, median=process_dm)
+            for d, out in zip(des, outs):
+                out["lValid"], out["rValid"] = d.lValid.copy(), d.rValid.copy()
         if joint_wmf:
             dispest.joint_wmf_batch(des)
         for d, out in zip(des, outs):
@@ -182,11 +187,14 @@ def write_ply(path, cloud):
 
 def _post_process_sgbm(des, outs, gts, masks, scale_factor, error_threshold, joint_wmf, device_tail):
     """The chain behind SGBMSelect_GPU on every object's device maps, and its keys of the record: lDisMap_pp and the metric on it."""
-    for d in des:
-        d.LRCheck_GPU()
-        if not joint_wmf:
-            d.FillInv_GPU()
-            d.WgtMedian_GPU()
+    if len(des) > 1:      # (several objects: the chain of all pairs in shared launches - the same bits)
+        dispest.post_process_batch(des, lr_check=True, fill=not joint_wmf, median=not joint_wmf)
+    else:
+        for d in des:
+            d.LRCheck_GPU()
+            if not joint_wmf:
+                d.FillInv_GPU()
+                d.WgtMedian_GPU()
     if joint_wmf and len(des) == 1:
         des[0].JointWMF_GPU()
     elif joint_wmf:

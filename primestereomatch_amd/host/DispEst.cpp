@@ -447,6 +447,26 @@ int DispEst::JointWMFBatch(DispEst *const *des, int n, int radius, float sigma, 
     return rc;
 }
 
+int DispEst::PostProcessBatch(DispEst *const *des, int n, int stages)
+{
+    if (!des || n < 1) return 1;
+    std::vector<psm_ctx *> cs;
+    for (int i = 0; i < n; ++i) {
+        if (!des[i] || des[i]->ctx.size() != 1) {
+            fprintf(stderr, "DispEst: PostProcessBatch runs on single-device objects only\n");
+            return 1;
+        }
+        cs.push_back(des[i]->ctx[0]);
+    }
+    const HipApi &api = hipUtil::api();
+    int rc = api.post_process_batch(cs.data(), n, stages);
+    for (int i = 0; i < n && !rc; ++i) {
+        rc |= api.download_maps(cs[i], des[i]->lDisMap.data, des[i]->rDisMap.data, des[i]->lDisMap.step);
+        rc |= api.download_valid(cs[i], des[i]->lValid.data, des[i]->rValid.data, des[i]->lValid.step);
+    }
+    return rc;
+}
+
 double DispEst::stageTimeUs(int stage) const
 {
     double us = 0;

@@ -187,6 +187,10 @@ public:
     // 0: the reference's radius, sigma, cluster count and iteration limit), each object's device maps with its own pair - after
     // computeBatch, say, with or without the L-R check between; every object's lDisMap / rDisMap receive its filtered maps.
     static int JointWMFBatch(DispEst *const *des, int n, int radius = 0, float sigma = 0, int n_clusters = 0, int max_iter = 0);
+    // ... and PP::processDM's own sequence: the stages named in `stages` (PSM_PP_LR_CHECK | PSM_PP_FILL | PSM_PP_WGT_MEDIAN, run in
+    // that order) of n single-device objects of one geometry in shared launches (psm_post_process_batch), the sweep chains of all
+    // maps side by side; every object's lDisMap / rDisMap / lValid / rValid receive its results.
+    static int PostProcessBatch(DispEst *const *des, int n, int stages);
 
     // psm_set_option on every device's context (PSM_OPT_FLAGS: e.g. PSM_FLAG_FMA_SOLVE - the maps of a reference binary built for an
     // FMA target -, PSM_OPT_SEG_ROWS, PSM_OPT_GATHER_STAGED, PSM_OPT_FRAMES_IN_FLIGHT ...; include/primesm_hip.h).  0 = ok.

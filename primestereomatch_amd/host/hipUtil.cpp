@@ -63,7 +63,8 @@ bool hipUtil::load(const char *path)
               bind(g_api.sgm_set_mode, "psm_sgm_set_mode") && bind(g_api.sgm_set_range, "psm_sgm_set_range") &&
               bind(g_api.sgm_set_census, "psm_sgm_set_census") && bind(g_api.sgm_select_maps, "psm_sgm_select_maps") &&
               bind(g_api.sgm_select_maps_batch, "psm_sgm_select_maps_batch") && bind(g_api.sgm_maps_time, "psm_sgm_maps_time") &&
-              bind(g_api.joint_wmf_batch, "psm_joint_wmf_batch") && bind(g_api.score_set_truth, "psm_score_set_truth") &&
+              bind(g_api.joint_wmf_batch, "psm_joint_wmf_batch") && bind(g_api.post_process_batch, "psm_post_process_batch") &&
+              bind(g_api.download_valid, "psm_download_valid") && bind(g_api.score_set_truth, "psm_score_set_truth") &&
               bind(g_api.score_set_params, "psm_score_set_params") && bind(g_api.score, "psm_score") &&
               bind(g_api.score_download, "psm_score_download") && bind(g_api.reproject_set_q, "psm_reproject_set_q") &&
               bind(g_api.reproject_set_range, "psm_reproject_set_range") && bind(g_api.reproject, "psm_reproject") &&

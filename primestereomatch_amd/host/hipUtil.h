@@ -64,6 +64,8 @@ struct HipApi {
     int (*sgm_select_maps_batch)(psm_ctx *const *, int) = nullptr;
     int (*sgm_maps_time)(psm_ctx *, double *) = nullptr;
     int (*joint_wmf_batch)(psm_ctx *const *, int, int, float, int, int) = nullptr;
+    int (*post_process_batch)(psm_ctx *const *, int, int) = nullptr;
+    int (*download_valid)(psm_ctx *, uint8_t *, uint8_t *, size_t) = nullptr;
     // score: display maps and the error metric against ground truth
     int (*score_set_truth)(psm_ctx *, const uint8_t *, const uint8_t *, size_t) = nullptr;
     int (*score_set_params)(psm_ctx *, int, int, int) = nullptr;
