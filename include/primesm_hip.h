@@ -749,7 +749,8 @@ int psm_score_time(psm_ctx *ctx, double *ms);
  * return it; missing only under PSM_DEPTH_USE_MASK: the left validity byte of the current L-R mask is 0.  PSM_DEPTH_SGM:
  * d = (double)v * 0.0625 of the int16 map the SGM sources of psm_score read (the plane of psm_score_upload_sgm_map while it is on,
  * else the last psm_sgm_compute*'s); missing: v == (min_disparity - 1) * 16, the invalid value of the range that map was
- * computed with (the hook plane: of the current psm_sgm_set_range setting).
+ * computed with (the hook plane: of the current psm_sgm_set_range setting).  While psm_wls_publish is on (and the hook plane
+ * off) both stages read the map of the last psm_wls_filter with the invalid value it was made with.
  * Arithmetic: fp64, every product and sum rounded on its own (no FMA), the terms added left to right, for i = 0..3:
  *   s_i = ((Q[i][0]*xf + Q[i][1]*yf) + Q[i][2]*d) + Q[i][3];   r = 1.0 / s_3;   p_i = s_i * r (i = 0..2)
  * - the reciprocal-then-multiply reading of OpenCV's Vec3d /= double.  Agreement with a live OpenCV is unpinned.
@@ -793,6 +794,66 @@ int psm_reproject_download_cloud(psm_ctx *ctx, void *records, uint32_t max_recor
 int psm_reproject_batch(psm_ctx *const *ctxs, int n, int source, int outputs, int flags, uint32_t *counts);
 /* Device ms of the launches of the last psm_reproject (a batch: on ctxs[0], for all pairs); needs PSM_OPT_PROFILE. */
 int psm_reproject_time(psm_ctx *ctx, double *ms);
+
+/* ---- WLS smoothing: the confidence-weighted, edge-aware global smoothing of a sub-pixel disparity map that users of
+ * cv::StereoSGBM apply at this point (cv::ximgproc::DisparityWLSFilter), by Min et al.'s Fast Global Smoother - separable
+ * tridiagonal solves along rows and columns, guided by the left image.  It fills the holes of the int16 map from
+ * their surroundings, keeps depth edges on image edges and keeps the sixteenths.  It follows no library's convention: the
+ * definition is tests/wls_model.py; the device equals it in every bit.  Agreement with a live OpenCV is unpinned.  An
+ * independent stage like psm_score: it reads the context's current result and writes planes of its own - it never writes the
+ * SGM map, the 8-bit maps or the masks. ----
+ * Inputs: an int16 map v[H][W] in 16ths with its invalid value inv, and a guide g[H][W][ch] of bytes - the left image exactly
+ * as psm_reproject takes the cloud's colours from it: the current pair's, float pairs quantised as the SGM stage reads them
+ * (saturate(rint(f * 255.0f))), or under PSM_WLS_SGM with a result of psm_sgm_compute_gray that call's left plane as one channel.
+ * Sources.  PSM_WLS_SGM: the int16 map of the last psm_sgm_compute* (the plane of psm_score_upload_sgm_map while it is on) with
+ * inv = (min_disparity - 1) * 16 of the range it belongs to - never the stage's own published result.  PSM_WLS_GIF: the current
+ * LEFT 8-bit map, v = byte * 16, inv = -16; nothing is missing, except under PSM_WLS_USE_MASK the pixels whose left validity
+ * byte is 0.
+ * Link indices: kh[y][x] = max over channels |g[y][x] - g[y][x+1]| (x < W-1), kv[y][x] the same between rows y and y+1; 0..255.
+ * Weight table: tab[k] = (float)exp(-(double)k / (double)sigma), k = 0..255, formed on the host with the C library's exp.
+ * Per-iteration lambda: lam_t = (float)((1.5 * (double)lambda * (double)4^(T-1-t)) / (double)(4^T - 1)), t = 0..T-1.
+ * Start: den = valid ? 1.0f : 0.0f, num = valid ? (float)v : 0.0f.
+ * Iterations: for t = 0..T-1, first every row, then every column, as one line of N pixels with link indices k[0..N-2].  All
+ * fp32, every operation rounded on its own (no FMA), 1.0f / m a correctly rounded division, subnormals kept; N = 1 is the identity:
+ *   lw[n] = lam_t * tab[k[n]]                 a[n] = n > 0   ? -lw[n-1] : 0
+ *                                             c[n] = n < N-1 ? -lw[n]   : 0
+ *   b[n] = (1 - a[n]) - c[n]
+ *   m = n ? b[n] - cp[n-1]*a[n] : b[0];       r = 1.0f / m;      cp[n] = c[n] * r
+ *   np[n] = (num[n] - np[n-1]*a[n]) * r       (n = 0: num[0] * r)        dp likewise from den
+ *   back:  u[N-1] = np[N-1];  u[n] = np[n] - cp[n]*u[n+1]                 likewise for den
+ * num and den are replaced by their u.  (m lies in [1, 1 + 2 lam_t]: r is always normal; the subnormals arise in np, dp and u.
+ * In fp32 that holds while 1.5 * lambda stays below 2^24; beyond it m can round to 0 next to a cut link, and the pixels the NaNs
+ * reach are void in the result.)
+ * End: q = num / den, one correctly rounded division.  A pixel is good if den >= 0x1p-64f and q is finite (below that mass it is
+ * connected to no valid pixel).  A good pixel gets min(max(rintf(q), inv + 1), 32767), every other pixel inv: the result has the
+ * conventions of the map it came from.  The float plane holds q for good pixels and the stored pattern 0x7FC00000 elsewhere. */
+enum { PSM_WLS_GIF = 0, PSM_WLS_SGM = 1 };                                /* sources (numbered as PSM_DEPTH_*) */
+enum { PSM_WLS_USE_MASK = 1 };                                            /* flags */
+/* lambda > 0, sigma > 0, both finite; iterations in [1, 4].  A new context has (8000, 1.5, 3); the parameters survive
+ * psm_release_scratch. */
+int psm_wls_set_params(psm_ctx *ctx, float lambda, float sigma, int iterations);
+/* The filter of `source` on the context's stream, in 1 + 2 T launches whatever the data: num, den and the link indices; per
+ * iteration one pass over the rows and one over the columns, the last of which forms the quotient.  Synchronous unless
+ * PSM_OPT_ASYNC: then psm_wls_wait waits for it (the downloads do so too).  The planes - 35 bytes per pixel - are allocated on
+ * first use and given back by psm_release_scratch.  Refused with nothing enqueued and the previous result intact: an unknown
+ * source or flag bit, a GIF source without current maps or with maps that cover a row stripe only, PSM_WLS_USE_MASK without a
+ * current mask or with the SGM source, the SGM source with neither a compute nor the hook plane, no current image pair (except
+ * under PSM_WLS_SGM after psm_sgm_compute_gray, whose left plane guides). */
+int psm_wls_filter(psm_ctx *ctx, int source, int flags);
+int psm_wls_wait(psm_ctx *ctx);
+/* The planes of the last psm_wls_filter; any pointer may be NULL.  disp: the filtered int16 map; q: the float plane; num, den:
+ * the working planes as the last pass left them (a debug view).  The float planes as H rows of W floats stride_bytes apart,
+ * disp as H rows of W int16 stride_bytes / 2 apart; stride_bytes 0: packed, else a multiple of 4 that is >= 4 W.  Synchronises. */
+int psm_wls_download(psm_ctx *ctx, int16_t *disp, float *q, float *num, float *den, size_t stride_bytes);
+/* The weight table the last psm_wls_filter read on the device. */
+int psm_wls_download_table(psm_ctx *ctx, float tab[256]);
+/* Device ms of the launches of the last psm_wls_filter; needs PSM_OPT_PROFILE. */
+int psm_wls_time(psm_ctx *ctx, double *ms);
+/* on != 0: from now on the SGM sources of psm_score, psm_score_batch, psm_reproject and psm_reproject_batch read the map and
+ * the invalid value of the last psm_wls_filter (whichever source it had) instead of the SGM stage's - the way to a dense cloud
+ * that keeps the sixteenths.  The hook plane of psm_score_upload_sgm_map wins while it is on.  Refused without a result.
+ * on == 0, or psm_release_scratch (which frees the planes): every call is again bit for bit what it is without this stage. */
+int psm_wls_publish(psm_ctx *ctx, int on);
 
 /* ---- debug / bench entry points (no counterpart in the reference) ---- */
 /* Test hook of the score stage: an int16 map (H rows of W values, pitch stride_bytes; 0: packed) that the SGM sources of

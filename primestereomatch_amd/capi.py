@@ -38,6 +38,10 @@ PSM_DEPTH_GIF, PSM_DEPTH_SGM = 0, 1
 PSM_DEPTH_XYZ, PSM_DEPTH_Z, PSM_DEPTH_CLOUD = 1, 2, 4
 PSM_DEPTH_USE_MASK = 1
 PSM_DEPTH_VOID = 0x7FC00000          # the bit pattern of a void pixel in the dense planes
+# the WLS smoothing stage: sources, flags
+PSM_WLS_GIF, PSM_WLS_SGM = 0, 1
+PSM_WLS_USE_MASK = 1
+PSM_WLS_VOID = 0x7FC00000            # the bit pattern of a void pixel in the float plane
 
 
 class Score(C.Structure):
@@ -166,6 +170,13 @@ SYMBOLS = [
     ("psm_reproject_download_cloud", _i, [_vp, _vp, C.c_uint32, _pu]),
     ("psm_reproject_batch", _i, [C.POINTER(_vp), _i, _i, _i, _i, _pu]),
     ("psm_reproject_time", _i, [_vp, _pd]),
+    ("psm_wls_set_params", _i, [_vp, C.c_float, C.c_float, _i]),
+    ("psm_wls_filter", _i, [_vp, _i, _i]),
+    ("psm_wls_wait", _i, [_vp]),
+    ("psm_wls_download", _i, [_vp, _vp, _vp, _vp, _vp, _sz]),
+    ("psm_wls_download_table", _i, [_vp, _vp]),
+    ("psm_wls_time", _i, [_vp, _pd]),
+    ("psm_wls_publish", _i, [_vp, _i]),
 ]
 
 _lib = None

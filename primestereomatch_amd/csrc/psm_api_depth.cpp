@@ -39,21 +39,6 @@ namespace {
 
 constexpr int DEPTH_OUTPUTS_ALL = PSM_DEPTH_XYZ | PSM_DEPTH_Z | PSM_DEPTH_CLOUD;
 
-// the left image the cloud's colours come from: the current pair's, or - an SGM source whose result psm_sgm_compute_gray made -
-// that call's left plane; img null: there is none.  slots: it lies in the image pair slots (the read mark applies)
-struct Colour {
-    const void *img;
-    int depth, ch;
-    bool slots;
-};
-Colour colour_of(const psm_ctx *c, int source)
-{
-    const SgmState &g = c->sgm;
-    if (source == PSM_DEPTH_SGM && g.have && g.res_ch == 1 && g.gray[0]) return Colour{g.gray[0], PSM_IMG_U8, 1, false};
-    if (c->pair.st.depth < 0) return Colour{nullptr, 0, 3, false};
-    return Colour{c->pair.raw[0], c->pair.st.depth, 3, true};
-}
-
 // what psm_reproject refuses about the call's own arguments (no context needed) ...
 int check_call(psm_ctx *e, const char *who, int source, int outputs, int flags)
 {
@@ -77,7 +62,7 @@ int check_ctx(psm_ctx *e, const psm_ctx *c, const char *who, int source, int out
     } else if (!sgm_source_exists(c)) {
         return fail(e, "%s: no SGM result (psm_sgm_compute) for an SGM source", who);
     }
-    if ((outputs & PSM_DEPTH_CLOUD) && !colour_of(c, source).img)
+    if ((outputs & PSM_DEPTH_CLOUD) && !colour_of(c, source == PSM_DEPTH_SGM).img)
         return fail(e, "%s: PSM_DEPTH_CLOUD without a current image pair (psm_upload_pair: the records take their colours from it)", who);
     return 0;
 }
@@ -103,7 +88,7 @@ int ensure_scratch(psm_ctx *c, int outputs)
 DpArgs depth_args(const psm_ctx *c, int source, int outputs, int flags)
 {
     const DepthState &q = c->depth;
-    const Colour col = colour_of(c, source);
+    const Colour col = colour_of(c, source == PSM_DEPTH_SGM);
     DpArgs a = {};
     a.map = c->maps;
     a.valid = (flags & PSM_DEPTH_USE_MASK) ? c->valid : nullptr;
@@ -197,7 +182,7 @@ int psm_reproject(psm_ctx *c, int source, int outputs, int flags, uint32_t *coun
     if (cloud) launch_dp_pack(c->stream, a, g);
     if (check_launch(c, "k_dp_count, k_dp_scan, k_dp_pack")) return 1;
     if (timed) PSM_HIP(c, hipEventRecord(q.ev[1], c->stream));
-    if (cloud && colour_of(c, source).slots && images_read(c, c->stream)) return 1;      // k_dp_pack read the pair's left image
+    if (cloud && colour_of(c, source == PSM_DEPTH_SGM).slots && images_read(c, c->stream)) return 1;      // k_dp_pack read the pair's left image
     PSM_HIP(c, hipMemcpyAsync(q.pin, q.cnt, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     PSM_HIP(c, hipEventRecord(q.ev_done, c->stream));
     reprojected(c, outputs, timed, c->opt_async != 0);
@@ -306,7 +291,7 @@ int psm_reproject_batch(psm_ctx *const *ctxs, int n, int source, int outputs, in
     // ---- every context is now where its own psm_reproject would have left it; only context 0 counts as timed ----
     for (int i = 0; i < n; ++i) {
         psm_ctx *c = ctxs[i];
-        if (cloud && colour_of(c, source).slots && images_read(c, s)) return member_failed(c0, who, i, c);
+        if (cloud && colour_of(c, source == PSM_DEPTH_SGM).slots && images_read(c, s)) return member_failed(c0, who, i, c);
         PSM_HIP(c0, hipMemcpyAsync(c->depth.pin, c->depth.cnt, sizeof(unsigned), hipMemcpyDeviceToHost, s));
         PSM_HIP(c0, hipEventRecord(c->depth.ev_done, s));
     }

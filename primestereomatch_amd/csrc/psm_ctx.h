@@ -20,6 +20,8 @@
 //                       results of several contexts in shared launches (psm_score_batch)
 //   psm_api_depth.cpp   from disparity to depth: cv::reprojectImageTo3D of the current result and the compacted point cloud
 //                       (psm_reproject), and of the results of several contexts in shared launches (psm_reproject_batch)
+//   psm_api_wls.cpp     edge-aware WLS smoothing of the sub-pixel int16 map (psm_wls_filter), and the switch that lets the SGM
+//                       sources of psm_score / psm_reproject read its result (psm_wls_publish)
 // Takes the place of the reference's oclUtil + CVC_cl / CVF_cl / DispSel_cl host wrappers
 // (src/oclUtil.cpp, src/CVC_cl.cpp, src/CVF_cl.cpp, src/DispSel_cl.cpp).
 // What a context knows about its volumes, results and image pairs between calls - psm::VolSide per side, psm::Results,
@@ -185,6 +187,28 @@ struct DepthState {
     DevTable tab;                                  // psm_reproject_batch (this context as the first of a batch): DpArgs records
 };
 
+// psm_wls_filter (psm_api_wls.cpp): parameters (they survive psm_release_scratch) and the stage's planes, allocated on first use
+// and given back by psm_release_scratch - 35 bytes per pixel: the working planes, the 12 bytes of the forward sweeps, the link
+// indices, the result.
+struct WlsState {
+    float lambda = 8000.0f, sigma = 1.5f;
+    int iters = 3;
+    float *work = nullptr;                         // [5][H][W]: num, den; cp, np, dp of a pass's forward sweep
+    uint8_t *links = nullptr;                      // [2][H][W]: kh, kv
+    int16_t *out = nullptr;                        // [H][W]: the filtered map
+    unsigned *q = nullptr;                         // [H][W]: the quotient's bit patterns
+    float *tab = nullptr;                          // [256] on the device; tab_sigma: the sigma it was formed with (0: none yet)
+    float tab_host[256] = {};                      // ... and the host's copy the upload reads
+    float tab_sigma = 0.0f;
+    hipEvent_t ev_done = nullptr;                  // behind the last launch (psm_wls_wait)
+    hipEvent_t ev[2] = {nullptr, nullptr};         // PSM_OPT_PROFILE: around the launches
+    bool have = false;                             // the planes hold the result of a filter run
+    int invalid = 0;                               // ... and its invalid value
+    bool pending = false;                          // an asynchronous run has not been waited for (psm_wls_wait)
+    bool timed = false;
+    bool publish = false;                          // psm_wls_publish: the SGM sources of psm_score / psm_reproject read `out`
+};
+
 // The image pair every frame starts with, and the second slot the next frame travels into (psm_upload_pair_async,
 // psm_upload_pair_rectified_async).  `st` is changed by its transitions (psm_state.h) alone, the rest by the functions declared
 // under "the image pair slots" below.
@@ -256,6 +280,7 @@ struct psm_ctx {
     psm::SgmState sgm;
     psm::ScoreState score;
     psm::DepthState depth;
+    psm::WlsState wls;
     uint8_t *p4[2] = {nullptr, nullptr};  // PSM_U8 only: {c0,c1,c2,grad} words
     // What stands for vol[side] (psm_state.h): costs that are a recipe, a filtered volume pending as packed minima or as FGF models.
     // The WTA consumes either form directly; any other reader makes the volume real first (materialize()).
@@ -456,13 +481,36 @@ void sgm_free(psm_ctx *c);                       // the stage's buffers and even
 void wm_free(psm_ctx *c, bool all);              // the weighted median's device scratch; all: its page-locked snapshots and events too
 // psm_api_score.cpp
 void score_free(psm_ctx *c, bool truth);         // the stage's scratch and events; truth: the uploaded truth, mask and hook map too
-// The int16 map the SGM sources of psm_score and psm_reproject read - the plane of psm_score_upload_sgm_map while it is on, else
-// the last psm_sgm_compute*'s - and the invalid value of the range it belongs to (the hook plane: the current setting's)
-inline const int16_t *sgm_source_map(const psm_ctx *c) { return c->score.hook_on ? c->score.hook : c->sgm.out; }
-inline int sgm_source_invalid(const psm_ctx *c) { return ((c->score.hook_on ? c->sgm.dmin : c->sgm.res_dmin) - 1) * 16; }
-inline bool sgm_source_exists(const psm_ctx *c) { return c->sgm.have || c->score.hook_on; }
+// The int16 map the SGM source of psm_wls_filter reads - the plane of psm_score_upload_sgm_map while it is on, else the last
+// psm_sgm_compute*'s - and the invalid value of the range it belongs to (the hook plane: the current setting's) ...
+inline const int16_t *sgm_stage_map(const psm_ctx *c) { return c->score.hook_on ? c->score.hook : c->sgm.out; }
+inline int sgm_stage_invalid(const psm_ctx *c) { return ((c->score.hook_on ? c->sgm.dmin : c->sgm.res_dmin) - 1) * 16; }
+inline bool sgm_stage_exists(const psm_ctx *c) { return c->sgm.have || c->score.hook_on; }
+// ... and the one the SGM sources of psm_score and psm_reproject read: the same, or - psm_wls_publish being on and no hook plane -
+// the result of the last psm_wls_filter with the invalid value it was made with
+inline bool wls_published(const psm_ctx *c) { return c->wls.publish && c->wls.have && !c->score.hook_on; }
+inline const int16_t *sgm_source_map(const psm_ctx *c) { return wls_published(c) ? c->wls.out : sgm_stage_map(c); }
+inline int sgm_source_invalid(const psm_ctx *c) { return wls_published(c) ? c->wls.invalid : sgm_stage_invalid(c); }
+inline bool sgm_source_exists(const psm_ctx *c) { return wls_published(c) || sgm_stage_exists(c); }
 // psm_api_depth.cpp
 void depth_free(psm_ctx *c);                     // the stage's scratch and events (its parameters stay)
+// The left image the colours of psm_reproject's cloud come from, and the guide of psm_wls_filter: the current pair's, or - an SGM
+// source whose result psm_sgm_compute_gray made - that call's left plane; img null: there is none.  slots: it lies in the image
+// pair slots (the read mark applies)
+struct Colour {
+    const void *img;
+    int depth, ch;
+    bool slots;
+};
+inline Colour colour_of(const psm_ctx *c, bool sgm_source)
+{
+    const SgmState &g = c->sgm;
+    if (sgm_source && g.have && g.res_ch == 1 && g.gray[0]) return Colour{g.gray[0], PSM_IMG_U8, 1, false};
+    if (c->pair.st.depth < 0) return Colour{nullptr, 0, 3, false};
+    return Colour{c->pair.raw[0], c->pair.st.depth, 3, true};
+}
+// psm_api_wls.cpp
+void wls_free(psm_ctx *c);                       // the stage's planes and events (its parameters stay); publishing is switched off
 // psm_api_select.cpp: copy_maps_out - two [H][W] planes on the device to the caller's rows
 int copy_maps_out(psm_ctx *c, const uint8_t *dev, uint8_t *lmap, uint8_t *rmap, size_t stride);
 

@@ -405,4 +405,34 @@ void launch_dp_count(hipStream_t s, const DpArgs &a, const DpGeom &g, const DpAr
 void launch_dp_scan(hipStream_t s, const DpArgs &a, const DpGeom &g, const DpArgs *tab = nullptr, int n = 1);    // k_dp_scan: tile_off, total
 void launch_dp_pack(hipStream_t s, const DpArgs &a, const DpGeom &g, const DpArgs *tab = nullptr, int n = 1);    // k_dp_pack: cloud
 
+// psm_wls.hip: edge-aware WLS smoothing of an int16 map in 16ths, Min et al.'s Fast Global Smoother (psm_wls_filter, psm_api_wls.cpp)
+enum { WLS_GIF = 0, WLS_SGM = 1 };                     // PSM_WLS_* (include/primesm_hip.h)
+constexpr int WLS_LINES = 64;                          // lines of a wave: one lane owns one line and walks it
+constexpr int WLS_STEPS = 64;                          // row pass: the steps of a tile that travels through LDS
+constexpr int WLS_PITCH = WLS_STEPS + 1;               // ... dwords between the lines of a tile in LDS: the transposed ds_read_b32 / ds_write_b32
+                                                       //     of a 32-lane half then touch 32 different banks ((a / 4) mod 32)
+constexpr int WLS_ROW_THREADS = 256;                   // ... threads of a workgroup: four waves move the tile, the first one walks it
+constexpr int WLS_CHUNK = 8;                           // steps whose loads - global in the column pass, LDS in the row pass - are issued ahead of the chain
+constexpr int WLS_TILE = 256;                          // k_wls_init: pixels (in raster order) of a workgroup
+constexpr unsigned WLS_VOID = 0x7FC00000u;             // what a void pixel holds in the float plane: stored, never computed
+struct WlsArgs {
+    const uint8_t *map;                // WLS_GIF: [H][W], the left 8-bit map
+    const uint8_t *valid;              // PSM_WLS_USE_MASK: [H][W], the left validity bytes; else null
+    const int16_t *d16;                // WLS_SGM: [H][W]
+    const void *img;                   // the guide: the left image of the colour pair
+    float *num, *den;                  // [H][W] each: the working planes
+    float *cp, *np, *dp;               // [H][W] each: what the forward sweep of a pass leaves for its back sweep
+    uint8_t *kh, *kv;                  // [H][W] each: the link indices to the right and downwards
+    const float *tab;                  // [256]: exp(-k / sigma)
+    int16_t *out;                      // [H][W]: the filtered map
+    unsigned *q;                       // [H][W]: the quotient's bit patterns
+    int W, H, source;
+    int invalid;                       // the invalid value of the source map, and of the result
+    int depth, ch;                     // of img: PSM_IMG_*, 3 or 1 channels
+};
+__host__ __device__ inline int wls_groups(int lines) { return (lines + WLS_LINES - 1) / WLS_LINES; }
+void launch_wls_init(hipStream_t s, const WlsArgs &a);                  // k_wls_init: num, den, kh, kv
+void launch_wls_rows(hipStream_t s, const WlsArgs &a, float lam);       // k_wls_rows: one pass over every row
+void launch_wls_cols(hipStream_t s, const WlsArgs &a, float lam, bool last);   // k_wls_cols: ... every column; last: and the quotient, out and q
+
 }  // namespace psm

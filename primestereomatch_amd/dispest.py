@@ -379,6 +379,53 @@ class DispEst:
         self._ck(self._lib.psm_reproject_time(self._h, C.byref(ms)), "reproject_time")
         return ms.value
 
+    # ---- WLS smoothing of the sub-pixel map (psm_wls_filter; the definition is tests/wls_model.py) ----
+    def setWLS(self, lam: float = 8000.0, sigma: float = 1.5, iterations: int = 3):
+        """psm_wls_set_params: lambda > 0, sigma > 0, iterations in 1..4 (a new object: 8000, 1.5, 3)."""
+        self._ck(self._lib.psm_wls_set_params(self._h, float(lam), float(sigma), int(iterations)), "setWLS")
+
+    def WLS_GPU(self, source: int = capi.PSM_WLS_SGM, use_mask: bool = False):
+        """psm_wls_filter: the confidence-weighted, edge-aware global smoothing (Fast Global Smoother) of the int16 map of the last
+        SGBM_GPU (capi.PSM_WLS_SGM) or of the current left 8-bit map times 16 (PSM_WLS_GIF; use_mask: pixels the current L-R mask
+        marks invalid are missing), guided by the left image: the holes are filled, the sixteenths stay.  Under PSM_OPT_ASYNC
+        wls_wait() waits for it.  wls_map() and wls_planes() download the results; wls_publish() hands the map to the SGM
+        sources of Score_GPU and Reproject_GPU."""
+        self._ck(self._lib.psm_wls_filter(self._h, int(source), capi.PSM_WLS_USE_MASK if use_mask else 0), "WLS_GPU")
+
+    def wls_wait(self):
+        """Wait for the WLS_GPU enqueued under PSM_OPT_ASYNC."""
+        self._ck(self._lib.psm_wls_wait(self._h), "wls_wait")
+
+    def wls_map(self):
+        """The filtered map of the last WLS_GPU: H x W int16 in 16ths, with the invalid value of the map it came from."""
+        disp = np.empty((self.hei, self.wid), np.int16)
+        self._ck(self._lib.psm_wls_download(self._h, _ptr(disp), None, None, None, 0), "wls_map")
+        return disp
+
+    def wls_planes(self):
+        """The float planes of the last WLS_GPU: (q, num, den), H x W float32 each - the quotient (void pixels hold the bit
+        pattern capi.PSM_WLS_VOID, a NaN) and the working planes as the last pass left them."""
+        q, num, den = (np.empty((self.hei, self.wid), np.float32) for _ in range(3))
+        self._ck(self._lib.psm_wls_download(self._h, None, _ptr(q), _ptr(num), _ptr(den), 0), "wls_planes")
+        return q, num, den
+
+    def wls_table(self):
+        """The 256 weights the last WLS_GPU read on the device."""
+        tab = np.empty(256, np.float32)
+        self._ck(self._lib.psm_wls_download_table(self._h, _ptr(tab)), "wls_table")
+        return tab
+
+    def wls_publish(self, on: bool = True):
+        """psm_wls_publish: while on, the SGM sources of Score_GPU / Reproject_GPU (and their batches) read the map of the last
+        WLS_GPU instead of the SGM stage's."""
+        self._ck(self._lib.psm_wls_publish(self._h, 1 if on else 0), "wls_publish")
+
+    def wls_time(self):
+        """Device ms of the launches of the last WLS_GPU; needs PSM_OPT_PROFILE."""
+        ms = C.c_double()
+        self._ck(self._lib.psm_wls_time(self._h, C.byref(ms)), "wls_time")
+        return ms.value
+
     # ---- extensions beyond the reference surface --------------------------------------------
     def LRCheck_GPU(self) -> int:
         """PP lrCheck (src/PP.cpp:17-50) on the device -> lValid / rValid."""

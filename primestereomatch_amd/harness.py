@@ -129,7 +129,7 @@ def compute_video(vFrame, rectification, maxDis=64, gt=None, mask=None, scale_fa
 
 
 def compute_sgbm(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, error_threshold=4, verbose=False, device_tail=False,
-                 post_process=False, joint_wmf=False, depth=False, **params):
+                 post_process=False, joint_wmf=False, depth=False, wls=None, **params):
     """One frame of STEREO_SGBM (src/StereoMatch.cpp:169-187, 275-309) on the device: l_bgr / r_bgr H x W x 3, uint8 or float32
     scaled by 1/255 (quantised on the device as lFrame.convertTo(lFrame, CV_8U, 255) does); params: DispEst.SGBM_GPU's, forwarded
     as they are - the reference's whole configuration is pre_filter_cap=63, speckle_window_size=100, speckle_range=32 (the
@@ -141,7 +141,11 @@ def compute_sgbm(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, er
     the GIF path on the device - LRCheck, FillInv, WgtMedian; joint_wmf: JointWMF in place of the latter two - and the record
     gains lDisMap_pp, the filtered left map, and (with gt) bp_percent_pp / avg_err_pp, the metric of compute() on it - from
     Score_GPU(PSM_SCORE_GIF) under device_tail.  The range must lie inside [0, maxDis).  Off, the default: no key is added.
-    depth: compute()'s, on the int16 map (PSM_DEPTH_SGM: sixteenths of a disparity, the invalid pixels missing)."""
+    depth: compute()'s, on the int16 map (PSM_DEPTH_SGM: sixteenths of a disparity, the invalid pixels missing).
+    wls: None, the default: nothing is added.  Else a dict of DispEst.setWLS's parameters ({}: lam 8000, sigma 1.5, iterations
+    3): the int16 map goes through the WLS smoothing on the device (DispEst.WLS_GPU) and is published, so that depth= gives the
+    cloud of the filtered map; the record gains wls16, the filtered map, and (with gt) bp_percent_wls - bp_percent_int's metric on
+    its rounded reading min((max(v, 0) + 8) >> 4, 255)."""
     out = {}
     lFrame, rFrame = np.ascontiguousarray(l_bgr), np.ascontiguousarray(r_bgr)
     with DispEst(lFrame, rFrame, maxDis, 8, True) as SMDE:
@@ -151,11 +155,24 @@ def compute_sgbm(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, er
         if params.get("speckle_window_size", 0) > 0:
             out["speckle_ms"] = SMDE.sgm_speckle_time()
         tail = _device_tail_sgbm([SMDE], [gt], [mask], scale_factor, error_threshold)[0] if device_tail else None
+        if wls is not None:
+            _wls(SMDE, out, wls, maxDis, gt, mask, scale_factor, error_threshold)
         _reproject(SMDE, out, depth, capi.PSM_DEPTH_SGM)
         if post_process or joint_wmf:
             SMDE.SGBMSelect_GPU()
             _post_process_sgbm([SMDE], [out], [gt], [mask], scale_factor, error_threshold, joint_wmf, device_tail)
     return _finish_sgbm(out, maxDis, gt, mask, scale_factor, error_threshold, verbose, tail)
+
+
+def _wls(SMDE, out, wls, maxDis, gt, mask, scale_factor, error_threshold):
+    """compute_sgbm's wls= option: the filtered map of the object's int16 map into the record, published to the SGM sources."""
+    SMDE.setWLS(**wls)
+    SMDE.WLS_GPU(capi.PSM_WLS_SGM)
+    SMDE.wls_publish(True)
+    w16 = out["wls16"] = SMDE.wls_map()
+    if gt is not None:
+        rounded = np.minimum((np.maximum(w16.astype(np.int32), 0) + 8) >> 4, 255)
+        out["bp_percent_wls"] = error_vs_ground_truth(rounded, gt, mask, maxDis, scale_factor, error_threshold)[0]
 
 
 def _reproject(SMDE, out, depth, source):

@@ -267,6 +267,29 @@ int DispEst::Reproject(int source, uint32_t *count, bool useMask, Mat *xyz, Mat 
     return 0;
 }
 
+int DispEst::setWLS(float lambda, float sigma, int iterations)
+{
+    if (ctx.empty()) return 1;
+    return hipUtil::api().wls_set_params(ctx[0], lambda, sigma, iterations);
+}
+
+int DispEst::WLS_GPU(int source, bool useMask, std::vector<int16_t> *disp16, Mat *q)
+{
+    if (ctx.empty()) return 1;
+    if (hipUtil::api().wls_filter(ctx[0], source, useMask ? PSM_WLS_USE_MASK : 0)) return 1;      // (several devices: ctx[0] holds the gathered maps)
+    if (disp16) {
+        disp16->resize((size_t)hei * wid);
+        if (hipUtil::api().wls_download(ctx[0], disp16->data(), nullptr, nullptr, nullptr, 0)) return 1;
+    }
+    if (q && (q->rows != hei || q->cols != wid || q->channels != 1 || q->depth != PSM_32F)) *q = Mat::zeros(hei, wid, 1, PSM_32F);
+    if (q && hipUtil::api().wls_download(ctx[0], nullptr, (float *)q->data, nullptr, nullptr, q->step)) return 1;
+    return 0;
+}
+
+int DispEst::WLSWait() { return ctx.empty() ? 1 : hipUtil::api().wls_wait(ctx[0]); }
+int DispEst::WLSPublish(bool on) { return ctx.empty() ? 1 : hipUtil::api().wls_publish(ctx[0], on ? 1 : 0); }
+int DispEst::wlsTime(double *ms) { return ctx.empty() ? 1 : hipUtil::api().wls_time(ctx[0], ms); }
+
 int DispEst::setSGBMParams(int blockSize, int P1, int P2, int uniquenessRatio, int disp12MaxDiff)
 {
     if (ctx.empty()) return 1;

@@ -162,6 +162,19 @@ public:
     int setReprojection(const double Q[16], int cropX = 0, int cropY = 0, float zMin = 0.f, float zMax = 0.f);
     int Reproject(int source, uint32_t *count, bool useMask = false, Mat *xyz = nullptr, Mat *z = nullptr);
     const std::vector<Point> &cloud() const { return cloud_; }
+    // WLS smoothing of the sub-pixel map on the device (psm_wls_filter): the confidence-weighted, edge-aware global smoothing users
+    // of cv::StereoSGBM apply behind it (cv::ximgproc::DisparityWLSFilter's kind, by the Fast Global Smoother), guided by the left
+    // image - the holes of the int16 map are filled from their surroundings, the sixteenths stay.  setWLS: lambda > 0, sigma > 0,
+    // iterations in 1..4 (a new object: 8000, 1.5, 3).  WLS_GPU: `source` PSM_WLS_SGM (the map of the last SGBM_GPU) or PSM_WLS_GIF
+    // (the current lDisMap times 16; useMask: without the pixels the L-R check rejected); disp16 (H x W int16, in 16ths) and q
+    // (H x W CV_32FC1, the unrounded quotient) receive the result if given.  WLSWait: behind a WLS_GPU under PSM_OPT_ASYNC.
+    // WLSPublish(true): Score and Reproject with an SGM source read the filtered map from now on - the way to a dense cloud that
+    // keeps the sixteenths.  wlsTime: device ms of the launches under PSM_OPT_PROFILE.
+    int setWLS(float lambda = 8000.f, float sigma = 1.5f, int iterations = 3);
+    int WLS_GPU(int source, bool useMask = false, std::vector<int16_t> *disp16 = nullptr, Mat *q = nullptr);
+    int WLSWait();
+    int WLSPublish(bool on);
+    int wlsTime(double *ms);
 
     // Frame loop (src/main.cpp:64-73) with the PCIe legs next to the kernels (single-device hosts): one call per frame -
     // CostConst (adopts the pair staged by the previous call), stages `next` pair (may be NULL at the end of the stream: its

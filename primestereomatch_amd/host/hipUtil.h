@@ -77,6 +77,13 @@ struct HipApi {
     int (*reproject)(psm_ctx *, int, int, int, uint32_t *) = nullptr;
     int (*reproject_download)(psm_ctx *, float *, float *, size_t) = nullptr;
     int (*reproject_download_cloud)(psm_ctx *, void *, uint32_t, uint32_t *) = nullptr;
+    // WLS smoothing of the sub-pixel map
+    int (*wls_set_params)(psm_ctx *, float, float, int) = nullptr;
+    int (*wls_filter)(psm_ctx *, int, int) = nullptr;
+    int (*wls_wait)(psm_ctx *) = nullptr;
+    int (*wls_download)(psm_ctx *, int16_t *, float *, float *, float *, size_t) = nullptr;
+    int (*wls_time)(psm_ctx *, double *) = nullptr;
+    int (*wls_publish)(psm_ctx *, int) = nullptr;
 };
 
 class hipUtil {

@@ -30,6 +30,10 @@
 // map - without the pixels the L-R check rejected; after pp, if given, all of it - is reprojected on the device (DispEst::Reproject) and the
 // coloured point cloud written to FILE as a binary little-endian PLY.  Without --q: a pinhole camera of focal length W pixels with the
 // principal point in the image centre and baseline 1 (depths in baselines)
+// --wls (anywhere on the line; with one of the sgbm words): the int16 map then goes through the WLS smoothing on the device
+// (DispEst::WLS_GPU: lambda 8000, sigma 1.5, 3 iterations) - the holes filled, the sixteenths kept; its device time is printed, the
+// filtered map dumped as <out>_sgbm_wls16.raw and, with gt.raw, scored as integer disparities beside the unfiltered map's figure;
+// with --ply a second cloud, that of the filtered map, goes to FILE with ".wls.ply" appended
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -75,10 +79,12 @@ int main(int argc, char **argv)
 {
     // the two named options are taken off the line first; the positional arguments keep their places
     const char *ply_path = nullptr, *q_text = nullptr;
+    bool wls = false;
     std::vector<char *> args;
     for (int i = 0; i < argc; ++i) {
         if (!strcmp(argv[i], "--ply") && i + 1 < argc) ply_path = argv[++i];
         else if (!strcmp(argv[i], "--q") && i + 1 < argc) q_text = argv[++i];
+        else if (!strcmp(argv[i], "--wls")) wls = true;
         else args.push_back(argv[i]);
     }
     argc = (int)args.size();
@@ -160,8 +166,8 @@ int main(int argc, char **argv)
         printf("%%BP = %.2f%% \t Avg Err = %.2f\n", psm::DispEst::scoreBP(rec), psm::DispEst::scoreAvgErr(rec));
         ok = dump(out + "_ldisp_disp.raw", disp.data, (size_t)W * H) && dump(out + "_edisp.raw", emap.data, (size_t)W * H);
     }
+    double Q[16] = {1, 0, 0, -0.5 * W, 0, 1, 0, -0.5 * H, 0, 0, 0, (double)W, 0, 0, 1, 0};
     if (ok && ply_path) {
-        double Q[16] = {1, 0, 0, -0.5 * W, 0, 1, 0, -0.5 * H, 0, 0, 0, (double)W, 0, 0, 1, 0};
         if (q_text) {
             const char *p = q_text;
             for (int i = 0; i < 16; ++i) {
@@ -244,6 +250,27 @@ int main(int argc, char **argv)
             if (SMDE.Score(PSM_SCORE_SGM, &rec, &disp, nullptr)) return 5;
             printf("%%BP = %.2f%% \t Avg Err = %.2f\n", psm::DispEst::scoreBP(rec), psm::DispEst::scoreAvgErr(rec));
             ok = dump(out + "_sgbm_disp.raw", disp.data, (size_t)W * H);
+        }
+        if (ok && wls) {          // the sub-pixel map through the WLS smoothing; published, the SGM sources of Score and Reproject read it
+            std::vector<int16_t> w16;
+            double wms = 0;
+            struct psm_score before, after;
+            if (gt_path && SMDE.Score(PSM_SCORE_SGM_INT, &before, nullptr, nullptr)) return 5;
+            if (SMDE.setWLS() || SMDE.WLS_GPU(PSM_WLS_SGM, false, &w16) || SMDE.wlsTime(&wms) || SMDE.WLSPublish(true)) return 5;
+            printf("WLS Time:\t %4.3f ms\n", wms);
+            ok = dump(out + "_sgbm_wls16.raw", (const unsigned char *)w16.data(), w16.size() * sizeof(int16_t));
+            if (ok && gt_path) {
+                if (SMDE.Score(PSM_SCORE_SGM_INT, &after, nullptr, nullptr)) return 5;
+                printf("SGBM integer disparities: %%BP = %.2f%%, WLS-filtered: %%BP = %.2f%%\n", psm::DispEst::scoreBP(before), psm::DispEst::scoreBP(after));
+            }
+            if (ok && ply_path) {
+                uint32_t count = 0;
+                const std::string path = std::string(ply_path) + ".wls.ply";
+                if (SMDE.setReprojection(Q) || SMDE.Reproject(PSM_DEPTH_SGM, &count)) return 5;
+                printf("Point cloud (WLS):\t %u of %d pixels kept -> %s\n", count, W * H, path.c_str());
+                ok = write_ply(path.c_str(), SMDE.cloud());
+            }
+            if (SMDE.WLSPublish(false)) return 5;
         }
         if (ok && sgbm_pp) {      // the stage's 8-bit maps through the post-processing chain of the GIF path, scored like its maps
             if (SMDE.SGBMSelect() || SMDE.LRCheck_GPU() || SMDE.FillInvalid_GPU() || SMDE.WgtMedian_GPU()) return 5;
