@@ -840,6 +840,17 @@ int psm_wls_set_params(psm_ctx *ctx, float lambda, float sigma, int iterations);
  * current mask or with the SGM source, the SGM source with neither a compute nor the hook plane, no current image pair (except
  * under PSM_WLS_SGM after psm_sgm_compute_gray, whose left plane guides). */
 int psm_wls_filter(psm_ctx *ctx, int source, int flags);
+/* psm_wls_filter of the n <= 4096 contexts ctxs[0..n) in one set of 1 + 2 T launches, the context on a grid axis of its own:
+ * the chains of different pairs are independent, so they run side by side.  source and flags apply to every context.  Same
+ * width, height, device and iterations on all (T is the batch's); each context uses its own lambda, sigma, map, guide and
+ * planes, and uploads its weight table only when its sigma changed.  The launches run on ctxs[0]'s stream, ordered as
+ * psm_score_batch's: behind every context's earlier work, ahead of its later work.  Synchronous unless ctxs[0] has
+ * PSM_OPT_ASYNC: then every context's psm_wls_wait collects.  Under PSM_OPT_PROFILE psm_wls_time of ctxs[0] is the batch's;
+ * the other contexts count as not timed.  Afterwards every context is exactly where its own psm_wls_filter would have left it
+ * (its planes, map, table and publishing switch).  Refused with nothing enqueued and every context's previous result intact,
+ * the message - on ctxs[0] - naming the context: what psm_wls_filter refuses, a NULL or repeated context, another width, height,
+ * device or iterations than context 0.  The table of the contexts' records belongs to ctxs[0] (psm_release_scratch frees it). */
+int psm_wls_filter_batch(psm_ctx *const *ctxs, int n, int source, int flags);
 int psm_wls_wait(psm_ctx *ctx);
 /* The planes of the last psm_wls_filter; any pointer may be NULL.  disp: the filtered int16 map; q: the float plane; num, den:
  * the working planes as the last pass left them (a debug view).  The float planes as H rows of W floats stride_bytes apart,

@@ -172,6 +172,7 @@ SYMBOLS = [
     ("psm_reproject_time", _i, [_vp, _pd]),
     ("psm_wls_set_params", _i, [_vp, C.c_float, C.c_float, _i]),
     ("psm_wls_filter", _i, [_vp, _i, _i]),
+    ("psm_wls_filter_batch", _i, [C.POINTER(_vp), _i, _i, _i]),
     ("psm_wls_wait", _i, [_vp]),
     ("psm_wls_download", _i, [_vp, _vp, _vp, _vp, _vp, _sz]),
     ("psm_wls_download_table", _i, [_vp, _vp]),

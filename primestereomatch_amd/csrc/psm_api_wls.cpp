@@ -5,10 +5,13 @@
 // are: it reads the context's current result - the int16 map of the SGM stage (or the hook plane), or the left 8-bit map and its
 // mask through psm::Results - and the left image of the pair, and writes its own planes (psm::WlsState).  psm_wls_publish lets the
 // SGM sources of psm_score and psm_reproject read its result instead of the SGM stage's.
+// psm_wls_filter_batch: the same launches for the maps of several contexts at once, the context on a grid axis of its own.
 #include "psm_ctx.h"
 #include "psm_wls_tab.h"
 
 #include <cmath>
+#include <cstdio>
+#include <vector>
 
 using namespace psm;
 
@@ -23,6 +26,7 @@ void wls_free(psm_ctx *c)
     (void)hipFree(w.q); w.q = nullptr;
     (void)hipFree(w.tab); w.tab = nullptr;
     w.tab_sigma = 0.0f;
+    table_free(w.pairs);
     for (hipEvent_t *e : {&w.ev_done, &w.ev[0], &w.ev[1]}) {
         if (*e) (void)hipEventDestroy(*e);
         *e = nullptr;
@@ -46,18 +50,18 @@ int check_call(psm_ctx *e, const char *who, int source, int flags)
     return 0;
 }
 
-// ... and about the context
-int check_ctx(psm_ctx *c, const char *who, int source, int flags)
+// ... and about one context; e: the context that receives the message (a batch: its first; who names the member)
+int check_ctx(psm_ctx *e, const psm_ctx *c, const char *who, int source, int flags)
 {
     if (source == PSM_WLS_GIF) {
-        if (!c->res.maps) return fail(c, "%s: no disparity maps computed (PSM_WLS_GIF)", who);
-        if (stripe_only(c)) return fail(c, "%s: the maps hold this context's row stripe only (gather the stripes first)", who);
-        if ((flags & PSM_WLS_USE_MASK) && !c->res.mask) return fail(c, "%s: PSM_WLS_USE_MASK without a current L-R mask (psm_lr_check)", who);
+        if (!c->res.maps) return fail(e, "%s: no disparity maps computed (PSM_WLS_GIF)", who);
+        if (stripe_only(c)) return fail(e, "%s: the maps hold this context's row stripe only (gather the stripes first)", who);
+        if ((flags & PSM_WLS_USE_MASK) && !c->res.mask) return fail(e, "%s: PSM_WLS_USE_MASK without a current L-R mask (psm_lr_check)", who);
     } else if (!sgm_stage_exists(c)) {
-        return fail(c, "%s: no SGM result (psm_sgm_compute) for the SGM source", who);
+        return fail(e, "%s: no SGM result (psm_sgm_compute) for the SGM source", who);
     }
     if (!colour_of(c, source == PSM_WLS_SGM).img)
-        return fail(c, "%s: no current image pair (psm_upload_pair: the left image guides the smoothing)", who);
+        return fail(e, "%s: no current image pair (psm_upload_pair: the left image guides the smoothing)", who);
     return 0;
 }
 
@@ -108,6 +112,81 @@ int result_ready(psm_ctx *c, const char *who)
     return 0;
 }
 
+// the member's weight table on the device is that of its sigma: uploaded on its own stream, only when sigma changed
+int table_current(psm_ctx *c)
+{
+    WlsState &w = c->wls;
+    if (w.tab_sigma == w.sigma) return 0;
+    // (the copy out of tab_host of an earlier run has executed: a pageable source is staged before the call returns)
+    wls_table(w.sigma, w.tab_host);
+    w.tab_sigma = 0.0f;
+    PSM_HIP(c, hipMemcpyAsync(w.tab, w.tab_host, sizeof w.tab_host, hipMemcpyHostToDevice, c->stream));
+    w.tab_sigma = w.sigma;
+    return 0;
+}
+
+// The host sequence of psm_wls_filter (its one context, the plain kernels with the record by value) and of psm_wls_filter_batch
+// (batch: the k_wls_*_b kernels over the device table of ctxs[0]), the arguments and every context checked: 1 + 2 T launches on
+// ctxs[0]'s stream.  T is ctxs[0]'s: the batch's.
+int wls_run(const char *who, psm_ctx *const *ctxs, int n, int source, int flags, bool batch)
+{
+    psm_ctx *c0 = ctxs[0];
+    if (bind(c0)) return 1;
+    hipStream_t s = c0->stream;
+    const bool timed = c0->opt_profile != 0;
+    const int T = c0->wls.iters;
+
+    // ---- buffers, events and the table's memory: before any launch ----
+    for (int i = 0; i < n; ++i)
+        if (ensure_buffers(ctxs[i])) return member_failed(c0, who, i, ctxs[i]);
+    if (batch_events(c0, ctxs, n)) return 1;
+    std::vector<WlsPair> tab((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        tab[i].a = wls_args(ctxs[i], source, flags);
+        for (int t = 0; t < T; ++t) tab[i].lam[t] = wls_lambda(ctxs[i]->wls.lambda, T, t);
+    }
+    bool fresh = false;
+    if (batch && table_reserve(c0, c0->wls.pairs, tab.data(), tab.size() * sizeof(WlsPair), &fresh)) return 1;
+    const WlsPair *dt = batch ? (const WlsPair *)c0->wls.pairs.dev : nullptr;
+
+    // ---- every context's earlier work (the map to filter, its weight table, a single psm_wls_filter) is ordered before the shared launches ----
+    for (int i = 0; i < n; ++i)
+        if (table_current(ctxs[i])) return member_failed(c0, who, i, ctxs[i]);
+    if (batch_join(c0, ctxs, n)) return 1;
+    if (fresh && table_upload(c0, c0->wls.pairs, tab.data(), tab.size() * sizeof(WlsPair))) return 1;
+
+    for (int i = 0; i < n; ++i) {
+        WlsState &w = ctxs[i]->wls;
+        w.have = w.pending = w.timed = false;   // (every check and allocation lies before this: the planes are about to be rewritten)
+    }
+    if (timed) PSM_HIP(c0, hipEventRecord(c0->wls.ev[0], s));
+    launch_wls_init(s, tab[0].a, dt, n);
+    for (int t = 0; t < T; ++t) {
+        launch_wls_rows(s, tab[0].a, tab[0].lam[t], t, dt, n);
+        launch_wls_cols(s, tab[0].a, tab[0].lam[t], t, t == T - 1, dt, n);
+    }
+    if (check_launch(c0, batch ? "k_wls_init_b, k_wls_rows_b, k_wls_cols_b" : "k_wls_init, k_wls_rows, k_wls_cols")) return 1;
+    if (timed) PSM_HIP(c0, hipEventRecord(c0->wls.ev[1], s));
+
+    // ---- every context is now where its own psm_wls_filter would have left it; only context 0 counts as timed ----
+    for (int i = 0; i < n; ++i) {
+        psm_ctx *c = ctxs[i];
+        if (colour_of(c, source == PSM_WLS_SGM).slots && images_read(c, s)) return member_failed(c0, who, i, c);   // k_wls_init read the pair's left image
+        PSM_HIP(c0, hipEventRecord(c->wls.ev_done, s));
+    }
+    if (batch_fork(c0, ctxs, n)) return 1;
+    for (int i = 0; i < n; ++i) {
+        WlsState &w = ctxs[i]->wls;
+        w.have = true;
+        w.invalid = tab[i].a.invalid;
+        w.timed = timed && i == 0;
+        w.pending = c0->opt_async != 0;
+    }
+    if (c0->opt_async) return 0;
+    PSM_HIP(c0, hipStreamSynchronize(s));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -129,38 +208,34 @@ int psm_wls_filter(psm_ctx *c, int source, int flags)
     const char *who = "psm_wls_filter";
     if (check_call(c, who, source, flags)) return 1;
     if (!c) return fail(nullptr, "%s: NULL context", who);
-    if (check_ctx(c, who, source, flags)) return 1;
-    if (bind(c)) return 1;
-    if (ensure_buffers(c)) return 1;
-    WlsState &w = c->wls;
-    if (w.tab_sigma != w.sigma) {
-        // (the copy out of tab_host of an earlier run has executed: a pageable source is staged before the call returns)
-        wls_table(w.sigma, w.tab_host);
-        w.tab_sigma = 0.0f;
-        PSM_HIP(c, hipMemcpyAsync(w.tab, w.tab_host, sizeof w.tab_host, hipMemcpyHostToDevice, c->stream));
-        w.tab_sigma = w.sigma;
+    if (check_ctx(c, c, who, source, flags)) return 1;
+    return wls_run(who, &c, 1, source, flags, false);
+}
+
+// The launches of psm_wls_filter with the context on a grid axis of its own.  Planes, table and parameters stay per context; the
+// kernels reach them through a device table ctxs[0] owns.  Every context ends where its own psm_wls_filter would have left it.
+int psm_wls_filter_batch(psm_ctx *const *ctxs, int n, int source, int flags)
+{
+    const char *who = "psm_wls_filter_batch";
+    psm_ctx *c0 = ctxs && n >= 1 ? ctxs[0] : nullptr;
+    if (check_call(c0, who, source, flags)) return 1;
+    if (!ctxs) return fail(nullptr, "%s: NULL ctxs", who);
+    if (n < 1) return fail(nullptr, "%s: n %d below 1", who, n);
+    if (!c0) return fail(nullptr, "%s: context 0 is NULL", who);
+    if (n > 4096) return fail(c0, "%s: %d contexts (at most 4096 per call)", who, n);
+    for (int i = 0; i < n; ++i) {
+        if (batch_member(c0, who, ctxs, i)) return 1;
+        const psm_ctx *c = ctxs[i];
+        if (c->W != c0->W || c->H != c0->H || c->device != c0->device)
+            return fail(c0, "%s: context %d has another width / height / device than context 0", who, i);
+        if (c->wls.iters != c0->wls.iters)
+            return fail(c0, "%s: context %d has iterations %d, context 0 has %d (the launches are the batch's; lambda and sigma may differ)", who, i,
+                        c->wls.iters, c0->wls.iters);
+        char member[64];
+        snprintf(member, sizeof member, "%s: context %d", who, i);
+        if (check_ctx(c0, c, member, source, flags)) return 1;
     }
-    const bool timed = c->opt_profile != 0;
-    const WlsArgs a = wls_args(c, source, flags);
-    w.have = w.pending = w.timed = false;       // (every check and allocation lies before this: the planes are about to be rewritten)
-    if (timed) PSM_HIP(c, hipEventRecord(w.ev[0], c->stream));
-    launch_wls_init(c->stream, a);
-    for (int t = 0; t < w.iters; ++t) {
-        const float lam = wls_lambda(w.lambda, w.iters, t);
-        launch_wls_rows(c->stream, a, lam);
-        launch_wls_cols(c->stream, a, lam, t == w.iters - 1);
-    }
-    if (check_launch(c, "k_wls_init, k_wls_rows, k_wls_cols")) return 1;
-    if (timed) PSM_HIP(c, hipEventRecord(w.ev[1], c->stream));
-    if (colour_of(c, source == PSM_WLS_SGM).slots && images_read(c, c->stream)) return 1;      // k_wls_init read the pair's left image
-    PSM_HIP(c, hipEventRecord(w.ev_done, c->stream));
-    w.have = true;
-    w.invalid = a.invalid;
-    w.timed = timed;
-    w.pending = c->opt_async != 0;
-    if (c->opt_async) return 0;
-    PSM_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return wls_run(who, ctxs, n, source, flags, true);
 }
 
 int psm_wls_wait(psm_ctx *c)

@@ -20,8 +20,9 @@
 //                       results of several contexts in shared launches (psm_score_batch)
 //   psm_api_depth.cpp   from disparity to depth: cv::reprojectImageTo3D of the current result and the compacted point cloud
 //                       (psm_reproject), and of the results of several contexts in shared launches (psm_reproject_batch)
-//   psm_api_wls.cpp     edge-aware WLS smoothing of the sub-pixel int16 map (psm_wls_filter), and the switch that lets the SGM
-//                       sources of psm_score / psm_reproject read its result (psm_wls_publish)
+//   psm_api_wls.cpp     edge-aware WLS smoothing of the sub-pixel int16 map (psm_wls_filter), of the maps of several contexts in
+//                       shared launches (psm_wls_filter_batch), and the switch that lets the SGM sources of psm_score /
+//                       psm_reproject read its result (psm_wls_publish)
 // Takes the place of the reference's oclUtil + CVC_cl / CVF_cl / DispSel_cl host wrappers
 // (src/oclUtil.cpp, src/CVC_cl.cpp, src/CVF_cl.cpp, src/DispSel_cl.cpp).
 // What a context knows about its volumes, results and image pairs between calls - psm::VolSide per side, psm::Results,
@@ -207,6 +208,7 @@ struct WlsState {
     bool pending = false;                          // an asynchronous run has not been waited for (psm_wls_wait)
     bool timed = false;
     bool publish = false;                          // psm_wls_publish: the SGM sources of psm_score / psm_reproject read `out`
+    DevTable pairs;                                // psm_wls_filter_batch (this context as the first of a batch): WlsPair records
 };
 
 // The image pair every frame starts with, and the second slot the next frame travels into (psm_upload_pair_async,

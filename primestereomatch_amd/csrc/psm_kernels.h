@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include "psm_live.h"
 #include "psm_wm_sched.h"
+#include "psm_wls_tab.h"
 
 namespace psm {
 
@@ -431,8 +432,16 @@ struct WlsArgs {
     int depth, ch;                     // of img: PSM_IMG_*, 3 or 1 channels
 };
 __host__ __device__ inline int wls_groups(int lines) { return (lines + WLS_LINES - 1) / WLS_LINES; }
-void launch_wls_init(hipStream_t s, const WlsArgs &a);                  // k_wls_init: num, den, kh, kv
-void launch_wls_rows(hipStream_t s, const WlsArgs &a, float lam);       // k_wls_rows: one pass over every row
-void launch_wls_cols(hipStream_t s, const WlsArgs &a, float lam, bool last);   // k_wls_cols: ... every column; last: and the quotient, out and q
+// A member of a batch (psm_wls_filter_batch): its record and the lambdas of its passes - lambda and sigma are the member's own, the
+// number of passes is the batch's.  The device table holds one per member, indexed with the member number (blockIdx.y).
+struct WlsPair {
+    WlsArgs a;
+    float lam[WLS_MAX_ITERS];          // wls_lambda(lambda, T, t), t < T; the rest 0
+};
+// tab == nullptr: the pair of `a` with the pass's `lam`; else the n members of the device table (grid y = member; of `a` only W and H
+// are read - they are the batch's - and the lambda of pass t is the member's lam[t])
+void launch_wls_init(hipStream_t s, const WlsArgs &a, const WlsPair *tab = nullptr, int n = 1);                  // k_wls_init: num, den, kh, kv
+void launch_wls_rows(hipStream_t s, const WlsArgs &a, float lam, int t, const WlsPair *tab = nullptr, int n = 1);   // k_wls_rows: pass t over every row
+void launch_wls_cols(hipStream_t s, const WlsArgs &a, float lam, int t, bool last, const WlsPair *tab = nullptr, int n = 1);   // k_wls_cols: ... every column; last: and the quotient, out and q
 
 }  // namespace psm

@@ -3,7 +3,8 @@
 // separable tridiagonal solves along rows and columns, guided by the left image.  It follows no library's convention: the
 // definition is tests/wls_model.py, the device equals it in every bit.  fp32, every operation rounded on its own
 // (the file is built without contraction), IEEE division, subnormals kept.
-// Launches, whatever the data - 1 + 2 T of them:
+// Launches, whatever the data - 1 + 2 T of them, for one pair or for the pairs of a batch (k_wls_*_b: the same device bodies, the
+// member on grid axis y, its record - pointers, table, the lambdas of its passes - in a device table):
 //   k_wls_init  one pixel per lane: num and den from the source map, the link indices kh and kv from the guide
 //   k_wls_rows  one pass over every row.  One lane owns one line and walks it, a wave holds WLS_LINES lines.  Lanes a row pitch
 //               apart would fetch a cache line per lane and step, so the WLS_LINES x WLS_STEPS tiles travel through LDS: the four
@@ -30,7 +31,19 @@ __device__ __forceinline__ void wls_forward(float am, float c, float v, float d,
     dp = __fmul_rn(__fsub_rn(d, __fmul_rn(dp, am)), r);
 }
 
-__global__ __launch_bounds__(WLS_TILE) void k_wls_init(WlsArgs a)
+// A member of a batch: its record of the device table, the pointers in it read as global ones (sgm_global, psm_kernels.h).  The
+// member index is the workgroup's grid y, so the record arrives through scalar loads ahead of the body.
+__device__ __forceinline__ WlsArgs wls_pair_args(const WlsPair *tab, unsigned pair)
+{
+    const WlsArgs &p = tab[pair].a;
+    WlsArgs a = p;
+    a.map = sgm_global(p.map); a.valid = sgm_global(p.valid); a.d16 = sgm_global(p.d16); a.img = sgm_global(p.img);
+    a.num = sgm_global(p.num); a.den = sgm_global(p.den); a.cp = sgm_global(p.cp); a.np = sgm_global(p.np); a.dp = sgm_global(p.dp);
+    a.kh = sgm_global(p.kh); a.kv = sgm_global(p.kv); a.tab = sgm_global(p.tab); a.out = sgm_global(p.out); a.q = sgm_global(p.q);
+    return a;
+}
+
+__device__ __forceinline__ void wls_init(WlsArgs a)
 {
     const size_t N = (size_t)a.W * a.H, i = (size_t)blockIdx.x * WLS_TILE + threadIdx.x;
     if (i >= N) return;
@@ -101,7 +114,7 @@ __device__ __forceinline__ void wls_tile_move(float (*sh)[WLS_LINES * WLS_PITCH]
     }
 }
 
-__global__ __launch_bounds__(WLS_ROW_THREADS) void k_wls_rows(WlsArgs a, float lam)
+__device__ __forceinline__ void wls_rows(WlsArgs a, float lam)
 {
     __shared__ float sh[3][WLS_LINES * WLS_PITCH];
     __shared__ float tab[256];
@@ -218,7 +231,7 @@ __device__ __forceinline__ void wls_cols_forward(const WlsArgs &a, const float *
 
 __device__ __forceinline__ bool wls_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
-__global__ __launch_bounds__(WLS_LINES) void k_wls_cols(WlsArgs a, float lam, int last)
+__device__ __forceinline__ void wls_cols(WlsArgs a, float lam, int last)
 {
     __shared__ float tab[256];
     const int W = a.W, H = a.H, x = blockIdx.x * WLS_LINES + threadIdx.x;
@@ -289,20 +302,37 @@ __global__ __launch_bounds__(WLS_LINES) void k_wls_cols(WlsArgs a, float lam, in
     }
 }
 
-void launch_wls_init(hipStream_t s, const WlsArgs &a)
+// The plain entries take the pair's record and the pass's lambda by value; the batch entries take the member's record from the device
+// table (grid y = member) and the lambda of pass t from it: every member has its own lambda and sigma.
+__global__ __launch_bounds__(WLS_TILE) void k_wls_init(WlsArgs a) { wls_init(a); }
+__global__ __launch_bounds__(WLS_TILE) void k_wls_init_b(const WlsPair *tab) { wls_init(wls_pair_args(tab, blockIdx.y)); }
+__global__ __launch_bounds__(WLS_ROW_THREADS) void k_wls_rows(WlsArgs a, float lam) { wls_rows(a, lam); }
+__global__ __launch_bounds__(WLS_ROW_THREADS) void k_wls_rows_b(const WlsPair *tab, int t) { wls_rows(wls_pair_args(tab, blockIdx.y), tab[blockIdx.y].lam[t]); }
+__global__ __launch_bounds__(WLS_LINES) void k_wls_cols(WlsArgs a, float lam, int last) { wls_cols(a, lam, last); }
+__global__ __launch_bounds__(WLS_LINES) void k_wls_cols_b(const WlsPair *tab, int t, int last)
+{
+    wls_cols(wls_pair_args(tab, blockIdx.y), tab[blockIdx.y].lam[t], last);
+}
+
+void launch_wls_init(hipStream_t s, const WlsArgs &a, const WlsPair *tab, int n)
 {
     const unsigned blocks = (unsigned)(((size_t)a.W * a.H + WLS_TILE - 1) / WLS_TILE);
-    hipLaunchKernelGGL(k_wls_init, dim3(blocks), dim3(WLS_TILE), 0, s, a);
+    if (tab) hipLaunchKernelGGL(k_wls_init_b, dim3(blocks, (unsigned)n), dim3(WLS_TILE), 0, s, tab);
+    else hipLaunchKernelGGL(k_wls_init, dim3(blocks), dim3(WLS_TILE), 0, s, a);
 }
 
-void launch_wls_rows(hipStream_t s, const WlsArgs &a, float lam)
+void launch_wls_rows(hipStream_t s, const WlsArgs &a, float lam, int t, const WlsPair *tab, int n)
 {
-    hipLaunchKernelGGL(k_wls_rows, dim3((unsigned)wls_groups(a.H)), dim3(WLS_ROW_THREADS), 0, s, a, lam);
+    const unsigned groups = (unsigned)wls_groups(a.H);
+    if (tab) hipLaunchKernelGGL(k_wls_rows_b, dim3(groups, (unsigned)n), dim3(WLS_ROW_THREADS), 0, s, tab, t);
+    else hipLaunchKernelGGL(k_wls_rows, dim3(groups), dim3(WLS_ROW_THREADS), 0, s, a, lam);
 }
 
-void launch_wls_cols(hipStream_t s, const WlsArgs &a, float lam, bool last)
+void launch_wls_cols(hipStream_t s, const WlsArgs &a, float lam, int t, bool last, const WlsPair *tab, int n)
 {
-    hipLaunchKernelGGL(k_wls_cols, dim3((unsigned)wls_groups(a.W)), dim3(WLS_LINES), 0, s, a, lam, last ? 1 : 0);
+    const unsigned groups = (unsigned)wls_groups(a.W);
+    if (tab) hipLaunchKernelGGL(k_wls_cols_b, dim3(groups, (unsigned)n), dim3(WLS_LINES), 0, s, tab, t, last ? 1 : 0);
+    else hipLaunchKernelGGL(k_wls_cols, dim3(groups), dim3(WLS_LINES), 0, s, a, lam, last ? 1 : 0);
 }
 
 }  // namespace psm

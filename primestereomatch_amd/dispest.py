@@ -848,6 +848,20 @@ def reproject_batch(des, source: int = capi.PSM_DEPTH_GIF, outputs: int = capi.P
     return None if des[0].options.get(capi.PSM_OPT_ASYNC) else [int(v) for v in counts]
 
 
+def wls_batch(des, source: int = capi.PSM_WLS_SGM, use_mask: bool = False):
+    """WLS_GPU of several DispEst objects of one geometry and one iteration count in one set of launches (psm_wls_filter_batch):
+    each object's map with its own guide, lambda and sigma (setWLS) -> the list of filtered H x W int16 maps.  Every object
+    afterwards behaves as after its own WLS_GPU (wls_map(), wls_planes(), wls_publish()); under PSM_OPT_ASYNC on des[0]: None,
+    every object's wls_wait() waits for it.  wls_time() of des[0] is the batch's (PSM_OPT_PROFILE)."""
+    des = list(des)
+    if not des:
+        return []
+    arr = (C.c_void_p * len(des))(*[d._h for d in des])
+    flags = capi.PSM_WLS_USE_MASK if use_mask else 0
+    capi.check(des[0]._lib.psm_wls_filter_batch(arr, len(des), int(source), flags), des[0]._h, "wls_batch")
+    return None if des[0].options.get(capi.PSM_OPT_ASYNC) else [d.wls_map() for d in des]
+
+
 def share_streams(des):
     """The DispEst objects of a batch run on one compute stream and one copy stream each way (psm_share_streams) - call once
     before a frame loop over batches."""
@@ -873,7 +887,7 @@ class FrameRing:
     """
 
     def __init__(self, l, r, d: int, frames: int = 2, *, dtype: str = "f32", device: int = 0, lr_check: bool = False,
-                 seg_rows: int = 0, truth=None, scale_factor: int = 4, error_threshold: int = 4, reproject: int = 0):
+                 seg_rows: int = 0, truth=None, scale_factor: int = 4, error_threshold: int = 4, reproject: int = 0, wls=None):
         """Every context is told PSM_OPT_FRAMES_IN_FLIGHT = frames: the planner of the fused launches then cuts them for a shared
         device (450 x 375 x 64: 0.207 ms per frame against 0.22-0.23 without the hint; no result changes).  seg_rows > 0:
         PSM_OPT_SEG_ROWS of every context on top of that (round 5's first finding - one segment per launch, seg_rows = image height
@@ -883,7 +897,10 @@ class FrameRing:
         reproject = outputs (capi.PSM_DEPTH_*): every frame's left map is reprojected on the device behind its last stage
         (Reproject_GPU, PSM_DEPTH_GIF; under lr_check with its mask) once setReprojection - or setRectification with a
         rectification that carries Q - has told the ring its Q; push / flush then return one more element: the cloud if the
-        outputs name it alone, else the dict {"xyz", "z", "cloud"} of what they name."""
+        outputs name it alone, else the dict {"xyz", "z", "cloud"} of what they name.
+        wls = a dict of DispEst.setWLS's parameters ({}: lam 8000, sigma 1.5, iterations 3): every frame's left map goes through the
+        WLS smoothing on the device behind its last stage (WLS_GPU, PSM_WLS_GIF; under lr_check with its mask); push / flush then
+        return one more element, the last: the filtered H x W int16 map in 16ths."""
         if frames < 1:
             raise ValueError("FrameRing: frames must be >= 1")
         self.ctx = [DispEst(l, r, d, dtype=dtype, device=device) for _ in range(frames)]
@@ -897,6 +914,10 @@ class FrameRing:
         self._lrc = lr_check
         self._score = truth is not None
         self._depth = int(reproject)
+        self._wls = wls is not None
+        if self._wls:
+            for c in self.ctx:
+                c.setWLS(**wls)
         if self._score:
             for c in self.ctx:
                 c.set_truth(truth[0], truth[1])
@@ -943,6 +964,8 @@ class FrameRing:
             c.Score_GPU(capi.PSM_SCORE_GIF)      # (behind the download's start: the copy of the maps does not wait for the score)
         if self._depth:
             c.Reproject_GPU(capi.PSM_DEPTH_GIF, self._depth, use_mask=self._lrc)
+        if self._wls:
+            c.WLS_GPU(capi.PSM_WLS_GIF, use_mask=self._lrc)
         self._busy[i] = True
         return out
 
@@ -957,6 +980,9 @@ class FrameRing:
             else:
                 xyz, z = c.reprojected()
                 out += ({"xyz": xyz, "z": z, "cloud": c.cloud() if self._depth & capi.PSM_DEPTH_CLOUD else None},)
+        if self._wls:
+            c.wls_wait()
+            out += (c.wls_map(),)
         return out
 
     def flush(self):

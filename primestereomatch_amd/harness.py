@@ -8,7 +8,7 @@ import numpy as np
 
 from . import capi
 from . import dispest
-from .dispest import DispEst, sgbm_batch, score_batch, sgbm_select_batch
+from .dispest import DispEst, reproject_batch, sgbm_batch, score_batch, sgbm_select_batch, wls_batch
 
 MASK_NONE, MASK_NONOCC, MASK_DISC = 0, 1, 2   # include/StereoMatch.h
 
@@ -187,6 +187,36 @@ def _reproject(SMDE, out, depth, source):
     out["cloud"] = SMDE.cloud()
 
 
+def _wls_batch(des, outs, wls, maxDis, gts, masks, scale_factor, error_threshold):
+    """compute_sgbm_batch's wls= option: _wls for every object, the smoothing of all maps in shared launches."""
+    for d in des:
+        d.setWLS(**wls)
+    maps = wls_batch(des, capi.PSM_WLS_SGM)
+    for i, (d, out, w16) in enumerate(zip(des, outs, maps)):
+        d.wls_publish(True)
+        out["wls16"] = w16
+        gt, mask = (gts[i] if gts else None), (masks[i] if masks else None)
+        if gt is not None:
+            rounded = np.minimum((np.maximum(w16.astype(np.int32), 0) + 8) >> 4, 255)
+            out["bp_percent_wls"] = error_vs_ground_truth(rounded, gt, mask, maxDis, scale_factor, error_threshold)[0]
+
+
+def _reproject_batch(des, outs, depth, source):
+    """compute_sgbm_batch's depth= option: _reproject for every object (depth: one setting for all, or a list with one per object),
+    the planes and clouds of all of them from shared launches."""
+    if depth is False or depth is None:
+        return
+    depths = list(depth) if isinstance(depth, (list, tuple)) else [depth] * len(des)
+    opts = [dp if isinstance(dp, dict) else {"Q": dp} for dp in depths]
+    for d, opt in zip(des, opts):
+        d.setReprojection(opt["Q"], opt.get("crop", (0, 0)), opt.get("z_range"))
+    use_mask = bool(opts[0].get("use_mask", False)) and source == capi.PSM_DEPTH_GIF
+    reproject_batch(des, source, capi.PSM_DEPTH_XYZ | capi.PSM_DEPTH_Z | capi.PSM_DEPTH_CLOUD, use_mask=use_mask)
+    for d, out in zip(des, outs):
+        out["xyz"], out["z"] = d.reprojected()
+        out["cloud"] = d.cloud()
+
+
 def write_ply(path, cloud):
     """A point cloud (capi.point_dtype() records: DispEst.cloud()) as a binary little-endian PLY file, vertices only: x, y, z as
     float, red, green, blue as uchar."""
@@ -230,12 +260,14 @@ def _post_process_sgbm(des, outs, gts, masks, scale_factor, error_threshold, joi
 
 
 def compute_sgbm_batch(pairs, maxDis=64, gts=None, masks=None, scale_factor=4, error_threshold=4, verbose=False, device_tail=False,
-                       post_process=False, joint_wmf=False, **params):
+                       post_process=False, joint_wmf=False, depth=False, wls=None, **params):
     """compute_sgbm for a list of (l_bgr, r_bgr) pairs of one size and depth in shared launches (dispest.sgbm_batch): the
     reference's loop over pairs and datasets (src/main.cpp:64-73, src/StereoMatch.cpp:528-609).  gts / masks: one per pair (or
     None).  -> a list of compute_sgbm's records; the times are the batch's divided by the number of pairs.  device_tail: display
     maps and both metrics of all pairs from the device (dispest.score_batch).  post_process / joint_wmf: compute_sgbm's, the maps of
-    all pairs from one launch (dispest.sgbm_select_batch)."""
+    all pairs from one launch (dispest.sgbm_select_batch).  wls / depth: compute_sgbm's, for every pair - the smoothing of all int16
+    maps in one set of launches (dispest.wls_batch), published, then with depth the planes and clouds of all pairs in one more
+    (dispest.reproject_batch, PSM_DEPTH_SGM); depth may be a list with one entry per pair.  The defaults add nothing."""
     pairs = [(np.ascontiguousarray(l), np.ascontiguousarray(r)) for l, r in pairs]
     if not pairs:
         return []
@@ -247,6 +279,9 @@ def compute_sgbm_batch(pairs, maxDis=64, gts=None, masks=None, scale_factor=4, e
         spk = des[0].sgm_speckle_time() / len(des) if params.get("speckle_window_size", 0) > 0 else None
         tails = _device_tail_sgbm(des, gts, masks, scale_factor, error_threshold) if device_tail else [None] * len(des)
         pps = [{} for _ in des]
+        if wls is not None:
+            _wls_batch(des, pps, wls, maxDis, gts, masks, scale_factor, error_threshold)
+        _reproject_batch(des, pps, depth, capi.PSM_DEPTH_SGM)
         if post_process or joint_wmf:
             sgbm_select_batch(des)
             _post_process_sgbm(des, pps, gts, masks, scale_factor, error_threshold, joint_wmf, device_tail)

@@ -490,6 +490,20 @@ int DispEst::PostProcessBatch(DispEst *const *des, int n, int stages)
     return rc;
 }
 
+int DispEst::WLSBatch(DispEst *const *des, int n, int source, int flags)
+{
+    if (!des || n < 1) return 1;
+    std::vector<psm_ctx *> cs;
+    for (int i = 0; i < n; ++i) {
+        if (!des[i] || des[i]->ctx.size() != 1) {
+            fprintf(stderr, "DispEst: WLSBatch runs on single-device objects only\n");
+            return 1;
+        }
+        cs.push_back(des[i]->ctx[0]);
+    }
+    return hipUtil::api().wls_filter_batch(cs.data(), n, source, flags);
+}
+
 double DispEst::stageTimeUs(int stage) const
 {
     double us = 0;

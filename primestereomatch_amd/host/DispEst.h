@@ -204,6 +204,11 @@ public:
     // that order) of n single-device objects of one geometry in shared launches (psm_post_process_batch), the sweep chains of all
     // maps side by side; every object's lDisMap / rDisMap / lValid / rValid receive its results.
     static int PostProcessBatch(DispEst *const *des, int n, int stages);
+    // ... and the WLS smoothing: WLS_GPU(source, flags & PSM_WLS_USE_MASK) of n single-device objects of one geometry and one
+    // iteration count in one set of launches (psm_wls_filter_batch), each object's map with its own guide, lambda and sigma.
+    // Every object is afterwards where its own WLS_GPU would have left it (WLSPublish, WLSWait under PSM_OPT_ASYNC on des[0]);
+    // wlsTime of des[0] reports the batch.
+    static int WLSBatch(DispEst *const *des, int n, int source = PSM_WLS_SGM, int flags = 0);
 
     // psm_set_option on every device's context (PSM_OPT_FLAGS: e.g. PSM_FLAG_FMA_SOLVE - the maps of a reference binary built for an
     // FMA target -, PSM_OPT_SEG_ROWS, PSM_OPT_GATHER_STAGED, PSM_OPT_FRAMES_IN_FLIGHT ...; include/primesm_hip.h).  0 = ok.

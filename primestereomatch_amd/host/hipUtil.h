@@ -80,6 +80,7 @@ struct HipApi {
     // WLS smoothing of the sub-pixel map
     int (*wls_set_params)(psm_ctx *, float, float, int) = nullptr;
     int (*wls_filter)(psm_ctx *, int, int) = nullptr;
+    int (*wls_filter_batch)(psm_ctx *const *, int, int, int) = nullptr;
     int (*wls_wait)(psm_ctx *) = nullptr;
     int (*wls_download)(psm_ctx *, int16_t *, float *, float *, float *, size_t) = nullptr;
     int (*wls_time)(psm_ctx *, double *) = nullptr;

@@ -10,8 +10,21 @@ JSON line per size and iteration count, and the same lines into profiles/wls_ben
                 ceiling if the bytes bind
   model_ms      the numpy model (tests/wls_model.py) on this machine's host, one thread; mean of --host-reps
 
+--batch: psm_wls_filter_batch instead - T = 3 and T = 1, 450 x 375 in batches of 1, 2, 4 and 8, 1280 x 720 of 1, 2 and 4,
+1920 x 1080 of 1 and 2, every member with a map of its own; the lines are appended to profiles/wls_bench.txt as a new block.
+
+  batch_ms_per_pair     device time of the 1 + 2 T launches of one psm_wls_filter_batch (PSM_OPT_PROFILE on its first context:
+                        k_wls_init_b, k_wls_rows_b, k_wls_cols_b) over the number of pairs; best of --reps
+  singles_ms_per_pair   the same number of psm_wls_filter calls one after the other: the sum of their kernels_ms over the number
+                        of pairs (the gaps between the calls are not in it); best of --reps
+  single_ms             the single call of context 0 alone: kernels_ms of the default mode, the figure to set against the
+                        parent commit's
+  batch_call_ms_per_pair, singles_call_ms_per_pair   the same two on the host clock, synchronous calls
+  ns_per_step           batch_ms (of the whole batch) over T * 2 * (W + H): what one step of the chain costs when n chains run
+                        side by side - constant over n while the chain binds, growing once the device is full
+
 The maps are random with 30 % missing, the guide is a smooth image with edges.  Usage: python scripts/wls_bench.py [--reps N]
-[--host-reps N] [--only WxH]"""
+[--host-reps N] [--only WxH] [--batch]"""
 import argparse
 import json
 import os
@@ -25,6 +38,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 SIZES = ((450, 375, 64), (1280, 720, 128), (1920, 1080, 256))
+BATCHES = {(450, 375): (1, 2, 4, 8), (1280, 720): (1, 2, 4), (1920, 1080): (1, 2)}
 
 
 def inputs(W, H, D, seed):
@@ -43,11 +57,60 @@ def bytes_per_pixel(T):
     return (2 + 3 + 8 + 2) + T * 2 * (9 + 12 + 12 + 8) + 6
 
 
+def batch_bench(a, emit):
+    import wls_model as M
+    import primestereomatch_amd as P
+    from primestereomatch_amd import capi
+    emit({"what": "wls_bench --batch", "reps": a.reps, "lambda": 8000.0, "sigma": 1.5})
+    for W, H, D in SIZES:
+        if a.only and a.only != f"{W}x{H}":
+            continue
+        ns = BATCHES[(W, H)]
+        pairs = [inputs(W, H, D, 1 + i) for i in range(max(ns))]
+        des = [P.DispEst(left, left, 16) for _, left in pairs]         # (the stage reads no volume: the contexts' own D is small)
+        try:
+            for de, (d16, _) in zip(des, pairs):
+                de.set_option(capi.PSM_OPT_PROFILE, 1)
+                de.upload_sgm_map(d16)
+            for T in (3, 1):
+                for de in des:
+                    de.setWLS(iterations=T)
+                models = [M.wls(d16, -16, left, iterations=T)["disp"] for d16, left in pairs[:2]]
+                for n in ns:
+                    maps = P.wls_batch(des[:n])                         # (first use: the planes, the table of the records)
+                    same = all(bool(np.array_equal(m, w)) for m, w in zip(maps, models))
+                    batch, batch_call, singles, singles_call, single = [], [], [], [], []
+                    for _ in range(a.reps):
+                        t0 = time.perf_counter()
+                        P.wls_batch(des[:n])
+                        batch_call.append((time.perf_counter() - t0) * 1e3)
+                        batch.append(des[0].wls_time())
+                    for _ in range(a.reps):
+                        t0 = time.perf_counter()
+                        for de in des[:n]:
+                            de.WLS_GPU(capi.PSM_WLS_SGM)
+                        singles_call.append((time.perf_counter() - t0) * 1e3)
+                        each = [de.wls_time() for de in des[:n]]
+                        singles.append(sum(each))
+                        single.append(each[0])
+                    ms = min(batch)
+                    emit({"size": f"{W}x{H}", "iterations": T, "n": n, "batch_ms_per_pair": round(ms / n, 4),
+                          "singles_ms_per_pair": round(min(singles) / n, 4), "single_ms": round(min(single), 4),
+                          "batch_call_ms_per_pair": round(min(batch_call) / n, 4),
+                          "singles_call_ms_per_pair": round(min(singles_call) / n, 4),
+                          "ns_per_step": round(ms * 1e6 / (T * 2 * (W + H)), 1),
+                          "gbps": round(n * bytes_per_pixel(T) * W * H / (ms * 1e-3) / 1e9, 1), "equals_model": same})
+        finally:
+            for de in des:
+                de.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--host-reps", type=int, default=2)
     ap.add_argument("--only", default="")
+    ap.add_argument("--batch", action="store_true")
     a = ap.parse_args()
     import wls_model as M
     import primestereomatch_amd as P
@@ -59,6 +122,11 @@ def main():
         print(line, flush=True)
         lines.append(line)
 
+    if a.batch:
+        batch_bench(a, emit)
+        with open(os.path.join(ROOT, "profiles", "wls_bench.txt"), "a") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     emit({"what": "wls_bench", "reps": a.reps, "lambda": 8000.0, "sigma": 1.5})
     for W, H, D in SIZES:
         if a.only and a.only != f"{W}x{H}":
