@@ -17,7 +17,16 @@ rectify_model.py for the rest - and keeps every value for the session, keyed by 
 Narrower than the calls allow: after psm_upload_volume of a few slices the shadow only knows that maps, mask and the filtered
 result are gone and lets nothing but new costs follow (a filter of the patched volume has no one-call CPU definition here);
 psm_download_volume is not read (both shapes have more than 16 slices; tests/test_gpu_parity.py and test_gpu_fuzz.py read
-volumes); a second filter of a filtered volume and a select of unfiltered costs are defined by the library but not generated."""
+volumes); a second filter of a filtered volume and a select of unfiltered costs are defined by the library but not generated.
+
+Two vocabularies.  generate(seed) deals the walks of SEEDS from OP_KINDS, as ever.  generate(seed, vocabulary="tail") deals the
+walks of TAIL_SEEDS from TAIL_KINDS: the WLS stage, the reprojection stage, psm_post_process_batch, the hook plane of
+psm_score_upload_sgm_map and psm_sgm_compute_gray, with the older calls their state depends on (pairs of every kind, the SGM
+stage, the guided-filter frame, the post-processing stages, psm_release_scratch, the score stage).  What decides which int16 map,
+which invalid value and which left image those stages read (psm_ctx.h: sgm_stage_map, sgm_source_map, colour_of) is stated once,
+in World._stage_map, _source_map and _guide.  Not in the tail vocabulary: row stripes and disparity shards (the new stages refuse
+stripe-only maps; test_gpu_wls.py and test_gpu_depth.py hold that refusal), psm_share_streams, the caller's map buffer,
+JointWMF, and asynchronous batches."""
 from __future__ import annotations
 
 import numpy as np
@@ -36,6 +45,26 @@ FLAGS_SAFE = (0, TWO_PHASE_ON, TWO_PHASE_OFF)                       # compatible
 FLAGS_ANY = FLAGS_SAFE + (MATERIALISE, STORE, STORE | MATERIALISE)
 MODES = ("sgbm", "hh", "3way", "hh4")
 STEPS = 40
+
+WLS_DEFAULT = (8000.0, 1.5, 3)                  # lambda, sigma, iterations of a new context
+# the parameters a wls_params op draws from: the defaults; a large lambda with a large sigma; a tiny sigma (most links are cut: void
+# pixels exist wherever a hole is walled in); then every other iteration count
+WLS_PARAMS = (WLS_DEFAULT, (4.0e6, 250.0, 3), (30.0, 0.02, 3), (8000.0, 1.5, 1), (500.0, 4.0, 2), (60.0, 0.02, 4), (4.0e6, 250.0, 2), (500.0, 4.0, 4))
+XYZ, Z, CLOUD = 1, 2, 4                          # PSM_DEPTH_*
+LR, FILL, WM = 1, 2, 4                           # PSM_PP_*
+PP_STAGES = (LR, LR | FILL, LR | FILL | WM, FILL)
+# what a reproject_q op draws from.  Q 0: the Q of cv::stereoRectify for two cameras whose principal points differ, with a crop; Q 1:
+# equal principal points (CALIB_ZERO_DISPARITY), so s_3 == 0 at disparity 0 and those pixels are void.  z-range 1 drops near and far.
+Q_CROPS = ((3, 2), (0, 0))
+Z_RANGES = ((0.0, float(np.finfo(np.float32).max)), (3600.0, 9000.0))
+
+
+def q_matrix(qi):
+    import depth_model as DM
+    P1 = [[700.0, 0, 30.0, 0], [0, 700.0, 20.0, 0], [0, 0, 1, 0]]
+    P2 = [[700.0, 0, 33.0 if qi == 0 else 30.0, -84000.0], [0, 700.0, 20.0, 0], [0, 0, 1, 0]]
+    return DM.q_from_projections(P1, P2)
+
 
 MAP_WRITERS = ("sgbm_select", "sgbm_select_batch", "upload_maps", "mapbuf", "gather", "merge")      # ... other than the filter
 JWMF_OPS = ("jwmf", "jwmf_batch")
@@ -87,6 +116,10 @@ class Data:
     def float_pair(self, k):
         """Pair k as the float images StereoMatch::compute hands over: byte * (1 / 255.0f)."""
         return tuple(a.astype(np.float32) * np.float32(1 / 255.0) for a in self.pairs[k])
+
+    def gray(self, k):
+        """The one-channel pair of an sgbm_gray op: the green planes of pair k."""
+        return tuple(np.ascontiguousarray(a[..., 1]) for a in self.pairs[k])
 
 
 def rand_maps(W, H, D, mseed):
@@ -169,7 +202,8 @@ class Refs:
         import sgm_census_model as CM
         import speckle_model as K
         kw = {"census": cost[1:]} if cost[0] == "census" else {"census": None, "pre_filter_cap": cost[1] if cost[0] == "bt" else 0}
-        ref = CM.sgm(*self.d.pairs[k], dmin, nd or self.d.D, mode=mode, **kw)
+        pair = self.d.gray(k[1]) if isinstance(k, tuple) else self.d.pairs[k]          # ("g", k): psm_sgm_compute_gray
+        ref = CM.sgm(*pair, dmin, nd or self.d.D, mode=mode, **kw)
         disp, sizes = ref["disp"], None
         if spk[0] > 0:
             disp, sizes = K.filter_speckles(ref["disp"], ref["invalid"], spk[0], 16 * spk[1])
@@ -198,6 +232,42 @@ class Refs:
     def _img(self, k):
         return self.d.pairs[k]
 
+    # the hook plane of psm_score_upload_sgm_map: rand_d16 with its invalid value re-mapped to the setting's at the upload
+    def _hook(self, mseed, inv):
+        m = rand_d16(self.d.W, self.d.H, self.d.D, mseed).copy()
+        m[m == -16] = inv
+        return {"d16": m}
+
+    # the left image as bytes: pair k, pair k as the quantised float pair, the left plane of a gray compute
+    def _guide(self, kind, k):
+        import depth_model as DM
+        if kind == "gray":
+            return self.d.gray(k)[0]
+        return DM.quantise(self.d.float_pair(k)[0]) if kind == "fpair" else self.d.pairs[k][0]
+
+    # the WLS stage: wls_model.wls's dict (plus "d16", the filtered map under the name the SGM sources read it by)
+    def _wls(self, src, inv, guide, par):
+        import wls_model as WM
+        if src[0] == "gif":
+            v, gif_inv = WM.gif_source(self(src[1])[0], self(src[2])[0] if src[2] is not None else None)
+            assert gif_inv == inv
+        else:
+            v = self(src[1])["d16"]
+        out = WM.wls(v, inv, self(guide), *par)
+        out["d16"] = out["disp"]
+        return out
+
+    # the reprojection stage: {"xyz", "z", "cloud"} of depth_model.reproject
+    def _depth(self, src, missing, qi, zi, colour):
+        import depth_model as DM
+        if src[0] == "gif":
+            d, miss = DM.gif_disparity(self(src[1])[0], self(missing)[0] if missing is not None else None)
+        else:
+            d16 = self(src[1])["d16"]
+            d, miss = d16.astype(np.float64) * 0.0625, d16 == missing
+        xyz, z, cloud = DM.reproject(d, miss, q_matrix(qi), Q_CROPS[qi], Z_RANGES[zi], self(colour))
+        return {"xyz": xyz, "z": z, "cloud": cloud}
+
 
 def sgm_range(sgm, D):
     """(dmin, number of disparities) an SGM result expression was computed with"""
@@ -223,9 +293,17 @@ class Ctx:
         self.sgm, self.range_set, self.sizes = None, (0, 0), None
         self.jw = [None, None]
         self.truth, self.score, self.pending = None, None, None
+        # the WLS stage: parameters, the result (("wls", source map, invalid value, guide, parameters)), the publish switch, an
+        # asynchronous run not yet waited for
+        self.wls_par, self.wls, self.wls_pub, self.wls_pending = WLS_DEFAULT, None, False, False
+        # the reprojection stage: Q with its crop and the z-range (indices; no Q in a new context), the result ((("depth", map,
+        # missing rule, Q, range, colour image), outputs)), an asynchronous count not yet collected
+        self.q, self.zr, self.depth, self.depth_pending = None, 0, None, False
+        self.hook = None                                # the hook plane: ("hook", mseed, the invalid value its holes were written with)
 
     def new_pair(self, k, fl):
-        """adopt_new_pair: nothing derived from the previous pair survives; the SGM and score stages keep their results"""
+        """adopt_new_pair: nothing derived from the previous pair survives; the SGM, score, WLS and reprojection stages keep their
+        results (the new left image guides and colours their later runs)"""
         self.pair = (k, fl)
         self.cost, self.filt, self.window = None, None, False
         self.maps, self.mask = None, None
@@ -367,8 +445,13 @@ class World:
         c.buf = to
 
     def op_release_scratch(self, ci):
+        """The SGM result, the score planes, the WLS planes with publishing and the reprojection planes go; parameters, Q, the
+        z-range, the truth and the hook plane (psm_api_core.cpp: score_free(c, false) keeps what psm_score_set_truth and
+        psm_score_upload_sgm_map uploaded) stay."""
         c = self._c(ci)
         c.sgm, c.sizes, c.score = None, None, None
+        c.wls, c.wls_pub, c.wls_pending = None, False, False
+        c.depth, c.depth_pending = None, False
 
     # post-processing
     def op_lr_check(self, ci):
@@ -449,7 +532,8 @@ class World:
     def _score_data(self, c, source):
         if source == GIF:
             return c.maps if c.whole_maps else None
-        return c.sgm
+        src = self._source_map(c)
+        return src[0] if src is not None else None
 
     def op_score(self, ci, source):
         c = self._c(ci)
@@ -527,10 +611,153 @@ class World:
         c = self._c(ci)
         c.write_maps(("gf", k, c.dtype))
 
+    # ---- which map, which invalid value, which left image (psm_ctx.h: sgm_stage_*, sgm_source_*, colour_of) ----
+    def _stage_map(self, c):
+        """What the SGM source of psm_wls_filter reads -> (expression, invalid value) or None.  The hook plane while it is on, with
+        the invalid value of the CURRENT psm_sgm_set_range setting; else the last compute's map with the invalid value of the range it
+        was computed with.  Never the WLS stage's own published result."""
+        if c.hook is not None:
+            return c.hook, (c.range_set[0] - 1) * 16
+        if c.sgm is not None:
+            return c.sgm, (sgm_range(c.sgm, self.D)[0] - 1) * 16
+        return None
+
+    def _source_map(self, c):
+        """What the SGM sources of psm_score and psm_reproject read: the same, or - publishing on, a WLS result there, no hook plane -
+        that result with the invalid value it was made with."""
+        if c.wls_pub and c.wls is not None and c.hook is None:
+            return c.wls, c.wls[2]
+        return self._stage_map(c)
+
+    def _guide(self, c, sgm_source):
+        """The left image that guides psm_wls_filter and colours the cloud: under an SGM source with a result of psm_sgm_compute_gray
+        that call's left plane (whichever map is read: the hook plane does not change it); else the current pair's, a float pair
+        quantised."""
+        if sgm_source and c.sgm is not None and isinstance(c.sgm[1], tuple):
+            return ("guide", "gray", c.sgm[1][1])
+        return ("guide", "fpair" if c.pair[1] else "pair", c.pair[0])
+
+    # the hook plane and the one-channel compute
+    def op_hook_map(self, ci, mseed):
+        c = self._c(ci)
+        c.hook = None if mseed is None else ("hook", mseed, (c.range_set[0] - 1) * 16)
+
+    def op_sgbm_gray(self, ci, k, cost, mode, dmin, nd, spk):
+        """psm_sgm_compute_gray on the green planes of pair k (the caller's memory: any pair, the staged colour pair is untouched)"""
+        c = self._c(ci)
+        c.range_set = (dmin, nd)
+        if c.striped:
+            return r"psm_sgm_compute_gray"
+        c.sgm = ("sgm", ("g", k), tuple(cost), mode, dmin, nd, tuple(spk))
+        if spk[0] > 0:
+            c.sizes = ("spk", c.sgm)
+
+    # the WLS stage.  source: "gif", "gifm" (PSM_WLS_USE_MASK), "sgm"
+    def _wls_expr(self, c, source):
+        if source == "sgm":
+            src = self._stage_map(c)
+            if src is None:
+                return None
+            return ("wls", ("d16", src[0]), src[1], self._guide(c, True), c.wls_par)
+        if not c.whole_maps or (source == "gifm" and c.mask is None):
+            return None
+        return ("wls", ("gif", c.maps, c.mask if source == "gifm" else None), -16, self._guide(c, False), c.wls_par)
+
+    def op_wls(self, ci, source, pending=False):
+        c = self._c(ci)
+        e = self._wls_expr(c, source)
+        if e is None:
+            return r"psm_wls_filter\b"
+        c.wls, c.wls_pending = e, pending
+
+    def op_wls_async(self, ci, source):
+        return self.op_wls(ci, source, pending=True)
+
+    def op_wls_wait(self, ci):
+        c = self._c(ci)
+        if not c.wls_pending:
+            return r"psm_wls_wait"
+        c.wls_pending = False
+
+    def op_wls_batch(self, cis, source):
+        cs = [self._c(i) for i in cis]
+        es = [self._wls_expr(c, source) for c in cs]
+        if any(e is None for e in es) or any(c.wls_par[2] != cs[0].wls_par[2] for c in cs):
+            return r"psm_wls_filter_batch"
+        for c, e in zip(cs, es):
+            c.wls, c.wls_pending = e, False
+
+    def op_wls_params(self, ci, lam, sigma, iterations):
+        self._c(ci).wls_par = (lam, sigma, iterations)
+
+    def op_wls_publish(self, ci, on):
+        c = self._c(ci)
+        if on and c.wls is None:
+            return r"psm_wls_publish"
+        c.wls_pub = bool(on)
+
+    # the reprojection stage.  source as above; outs: a non-empty subset of XYZ | Z | CLOUD
+    def _depth_expr(self, c, source):
+        if c.q is None:
+            return None
+        if source == "sgm":
+            src = self._source_map(c)
+            if src is None:
+                return None
+            return ("depth", ("d16", src[0]), src[1], c.q, c.zr, self._guide(c, True))
+        if not c.whole_maps or (source == "gifm" and c.mask is None):
+            return None
+        return ("depth", ("gif", c.maps), c.mask if source == "gifm" else None, c.q, c.zr, self._guide(c, False))
+
+    def op_reproject(self, ci, source, outs, pending=False):
+        c = self._c(ci)
+        e = self._depth_expr(c, source)
+        if e is None:
+            return r"psm_reproject\b"
+        c.depth, c.depth_pending = (e, outs), pending
+
+    def op_reproject_async(self, ci, source, outs):
+        return self.op_reproject(ci, source, outs, pending=True)
+
+    def op_reproject_wait(self, ci):
+        c = self._c(ci)
+        if not c.depth_pending:
+            return r"psm_reproject_wait"
+        c.depth_pending = False
+
+    def op_reproject_batch(self, cis, source, outs):
+        cs = [self._c(i) for i in cis]
+        es = [self._depth_expr(c, source) for c in cs]
+        if any(e is None for e in es):
+            return r"psm_reproject_batch"
+        for c, e in zip(cs, es):
+            c.depth, c.depth_pending = (e, outs), False
+
+    def op_reproject_q(self, ci, q, zr):
+        c = self._c(ci)
+        c.q, c.zr = q, zr
+
+    # psm_post_process_batch: the named stages in PP::processDM's order; every member ends where its own single calls leave it
+    def op_pp_batch(self, cis, stages):
+        cs = [self._c(i) for i in cis]
+        if any(not c.whole_maps or (not stages & LR and c.mask is None) or c.pair[1] != cs[0].pair[1] for c in cs):
+            return r"psm_post_process_batch"
+        for i in cis:
+            for bit, op in ((LR, self.op_lr_check), (FILL, self.op_fill_inv), (WM, self.op_wgt_median)):
+                if stages & bit:
+                    r = op(i)
+                    assert r is None, r
+
     # ---- readers: name -> the expression(s) the shadow says the context holds, or None when undefined ----
     def readers(self, ci):
         c = self._c(ci)
         out = {}
+        if c.wls is not None:
+            out["wls_planes"] = ("wls", c.wls)
+        if c.depth is not None:
+            out["reprojected"] = ("depth",) + c.depth
+            if c.depth[1] & CLOUD:
+                out["cloud"] = ("depth",) + c.depth
         if c.maps is not None:
             out["download_maps"] = ("gf_path", c.maps, c.maps_rows)
         if c.mask is not None and c.mask_fresh:
@@ -570,12 +797,12 @@ _WEIGHTS = _WEIGHTS / _WEIGHTS.sum()
 # ------------------------------------------------------------------------------------------------------------ the generator
 
 class Walk:
-    def __init__(self, seed, shape, dtype, steps):
-        self.seed, self.shape, self.dtype, self.steps = seed, shape, dtype, steps
+    def __init__(self, seed, shape, dtype, steps, vocabulary="default"):
+        self.seed, self.shape, self.dtype, self.steps, self.vocabulary = seed, shape, dtype, steps, vocabulary
 
     def log(self, upto=None):
         W, H, D = self.shape
-        head = f"walk {self.seed}: {W}x{H} D={D} {self.dtype}"
+        head = f"walk {self.seed}: {W}x{H} D={D} {self.dtype}" + ("" if self.vocabulary == "default" else f" ({self.vocabulary} vocabulary)")
         return "\n".join([head] + [f"  {i:3d} {s!r}" for i, s in enumerate(self.steps[:upto])])
 
 
@@ -715,9 +942,13 @@ _ELIGIBLE = {
 }
 
 
-def generate(seed, steps=STEPS) -> Walk:
+def generate(seed, steps=STEPS, vocabulary="default") -> Walk:
     """The walk of a seed: ops, each followed by one or two readers of another stage than the one just driven, and by one reader
-    on every context a batch op did not name.  The refusals are the shadow's; at most a quarter of the ops are refused."""
+    on every context a batch op did not name.  The refusals are the shadow's; at most a quarter of the ops are refused.
+    vocabulary "default": the ops of OP_KINDS, the walks of SEEDS; "tail": the ops of TAIL_KINDS, the walks of TAIL_SEEDS."""
+    if vocabulary == "tail":
+        return _generate_tail(seed, steps)
+    assert vocabulary == "default", vocabulary
     rng = np.random.default_rng([seed, 20240])
     shape = SHAPES[seed % 2]
     dtype = "u8" if (shape == SHAPES[0] and seed % 8 in (2, 6)) else "f32"
@@ -804,3 +1035,381 @@ def replay(walk: Walk):
 
 
 SEEDS = tuple(range(40))
+
+
+# ---------------------------------------------------------------------------------------------------- the tail vocabulary
+
+NEW_KINDS = ("wls", "wls_async", "wls_wait", "wls_batch", "wls_params", "wls_publish", "hook_map", "reproject", "reproject_async",
+             "reproject_wait", "reproject_batch", "reproject_q", "pp_batch", "sgbm_gray")
+NEW_READERS = ("wls_planes", "reprojected", "cloud")
+_OLDER = ("images", "images_async", "float", "frame", "frame_async", "cost_const", "cost_filter", "disp_select", "release_scratch",
+          "lr_check", "fill_inv", "wgt_median", "upload_maps", "sgbm", "sgbm_batch", "sgbm_select", "set_range", "set_truth", "score",
+          "score_async", "score_wait", "score_batch")
+TAIL_STAGE_OF = dict({k: STAGE_OF[k] for k in _OLDER}, wls="wls", wls_async="wls", wls_wait="wls", wls_batch="wls", wls_params="wls",
+                     wls_publish="wls", hook_map="score", reproject="depth", reproject_async="depth", reproject_wait="depth",
+                     reproject_batch="depth", reproject_q="depth", pp_batch="pp", sgbm_gray="sgm")
+TAIL_KINDS = tuple(TAIL_STAGE_OF)
+_TW = {"wls": 2.0, "reproject": 2.0, "wls_batch": 1.6, "reproject_batch": 1.6, "pp_batch": 1.8, "wls_publish": 1.6, "hook_map": 1.4,
+       "wls_params": 1.9, "wls_async": 1.2, "reproject_async": 1.2, "wls_wait": 0.9, "reproject_wait": 0.9, "sgbm_gray": 1.0,
+       "images": 0.6, "images_async": 0.5, "float": 0.6, "frame": 0.4, "frame_async": 0.4, "cost_const": 0.8, "cost_filter": 0.3,
+       "disp_select": 0.3, "release_scratch": 0.8, "lr_check": 0.9, "fill_inv": 0.5, "wgt_median": 0.5, "upload_maps": 0.9,
+       "sgbm": 1.0, "sgbm_batch": 0.6, "sgbm_select": 0.7, "set_range": 0.8, "set_truth": 0.5, "score": 1.2, "score_async": 0.5,
+       "score_wait": 0.3, "score_batch": 0.7, "reproject_q": 0.9}
+_TAIL_WEIGHTS = np.array([_TW[k] for k in TAIL_KINDS])
+_TAIL_WEIGHTS = _TAIL_WEIGHTS / _TAIL_WEIGHTS.sum()
+_SOURCES = ("gif", "gifm", "sgm")
+# the reader that sees what a carried-out op of the tail vocabulary wrote (read first, ahead of the readers of other stages)
+_OWN_READER = {"wls": ("wls_planes",), "wls_wait": ("wls_planes",), "wls_batch": ("wls_planes",), "reproject": ("reprojected", "cloud"),
+               "reproject_wait": ("reprojected", "cloud"), "reproject_batch": ("reprojected", "cloud"), "score": ("score_maps",),
+               "score_batch": ("score_maps",), "pp_batch": ("download_maps", "download_valid"), "sgbm_gray": ("sgm_disparity",)}
+
+
+def _a_source(rng, w, c, depth):
+    """mostly a source the call accepts in this state"""
+    ok = [s for s in _SOURCES if (w._depth_expr(c, s) if depth else w._wls_expr(c, s)) is not None]
+    if ok and rng.random() < 0.85:
+        return ok[int(rng.integers(0, len(ok)))]
+    return _SOURCES[int(rng.integers(0, 3))]
+
+
+def _wls_par(j):
+    lam, sigma, it = WLS_PARAMS[j]
+    return {"lam": lam, "sigma": sigma, "iterations": it}
+
+
+def _members(rng, w, free, ok):
+    """a batch's contexts: mostly a subset, in any order, of those among `free` that the call accepts"""
+    el = [i for i in free if ok(w.ctxs[i])]
+    pool = el if el and rng.random() < 0.85 else list(free)
+    return tuple(int(i) for i in rng.permutation(pool)[:int(rng.integers(1, len(pool) + 1))])
+
+
+def _propose_tail(rng, w: World, ci, free):
+    """One op of the tail vocabulary for context ci (a batch: among the contexts `free`).  -> (kind, ctx or contexts, args)"""
+    c = w.ctxs[ci]
+    D = w.D
+    u = rng.random()
+    if c.cost == "fresh":                             # a guided-filter frame runs on to its select
+        return ("cost_filter", ci, {})
+    if c.cost == "filt" and c.maps is None and u < 0.85:
+        return ("disp_select", ci, {})
+    if c.wls_pending and u < 0.5:
+        return ("wls_wait", ci, {})
+    if c.depth_pending and u < 0.5:
+        return ("reproject_wait", ci, {})
+    if c.pending is not None and u < 0.5:
+        return ("score_wait", ci, {})
+    kind = TAIL_KINDS[int(rng.choice(len(TAIL_KINDS), p=_TAIL_WEIGHTS))]
+    if kind in ("images", "images_async", "float"):
+        if kind == "float" and c.dtype != "f32":
+            kind = "images"
+        return (kind, ci, {"k": int(rng.integers(0, NPAIRS - 1))})
+    if kind in ("frame", "frame_async", "cost_const", "lr_check", "fill_inv", "wgt_median", "sgbm_select", "score_wait", "wls_wait",
+                "reproject_wait"):
+        return (kind, ci, {})
+    if kind == "cost_filter":
+        return (kind if c.cost is None else "cost_const", ci, {})
+    if kind == "disp_select":
+        return (kind, ci, {})
+    if kind == "release_scratch":
+        return (kind, ci, {}) if c.pending is None and c.staged is None else ("score_wait" if c.pending is not None else "cost_const", ci, {})
+    if kind == "upload_maps":
+        return (kind, ci, {"mseed": int(rng.integers(0, 1 << 16)), "masks": bool(rng.integers(0, 2))})
+    if kind == "sgbm":
+        return (kind, ci, _sgm_args(rng, D))
+    if kind == "sgbm_gray":
+        return (kind, ci, dict(_sgm_args(rng, D), k=int(rng.integers(0, NPAIRS))))
+    if kind == "set_range":
+        return (kind, ci, {"dmin": int(rng.integers(-4, 5)), "nd": int(rng.choice([0, 16, D + 8]))})
+    if kind == "set_truth":
+        return (kind, ci, {"t": int(rng.integers(0, 2))})
+    if kind in ("score", "score_async"):
+        if c.pending is not None:
+            return ("score_wait", ci, {})
+        return (kind, ci, {"source": int(rng.integers(0, 3))})
+    if kind in ("wls", "wls_async"):
+        return (kind, ci, {"source": _a_source(rng, w, c, False)})
+    if kind in ("reproject", "reproject_async"):
+        return (kind, ci, {"source": _a_source(rng, w, c, True), "outs": int(rng.integers(1, 8))})
+    if kind == "wls_params":
+        return (kind, ci, _wls_par(int(rng.integers(0, len(WLS_PARAMS)))))
+    if kind == "wls_publish":
+        return (kind, ci, {"on": bool(rng.random() < 0.7)})
+    if kind == "hook_map":
+        return (kind, ci, {"mseed": None if c.hook is not None and rng.random() < 0.4 else int(rng.integers(0, 1 << 16))})
+    if kind == "reproject_q":
+        return (kind, ci, {"q": int(rng.integers(0, 2)), "zr": int(rng.integers(0, 2))})
+    if kind == "sgbm_batch":
+        return (kind, _members(rng, w, free, lambda x: x.pair[1] == c.pair[1]), _sgm_args(rng, D))
+    if kind == "score_batch":
+        source = int(rng.integers(0, 3))
+        cis = _members(rng, w, free, lambda x: x.pending is None and w._score_data(x, source) is not None and x.truth == c.truth)
+        if any(w.ctxs[i].pending is not None for i in cis):
+            return ("score_wait", ci, {})
+        return (kind, cis, {"source": source})
+    if kind == "wls_batch":
+        source = _a_source(rng, w, c, False)
+        return (kind, _members(rng, w, free, lambda x: w._wls_expr(x, source) is not None and x.wls_par[2] == c.wls_par[2]), {"source": source})
+    if kind == "reproject_batch":
+        source = _a_source(rng, w, c, True)
+        return (kind, _members(rng, w, free, lambda x: w._depth_expr(x, source) is not None), {"source": source, "outs": int(rng.integers(1, 8))})
+    assert kind == "pp_batch", kind
+    stages = PP_STAGES[int(rng.integers(0, len(PP_STAGES)))]
+    return (kind, _members(rng, w, free, lambda x: x.whole_maps and (stages & LR or x.mask is not None) and x.pair[1] == c.pair[1]), {"stages": stages})
+
+
+# The interleavings tests/test_seq_model.py asks of the tail walks, as scripts: each yields the ops of one context (the batch
+# scripts: of all three) in order, reading the shadow as it stands when the op is due (H.w).  Ops of other contexts fall between.
+class _Holder:
+    w: World = None
+
+
+def _plain_sgm(dmin=0, nd=0):
+    return {"cost": ("sad",), "mode": "hh", "dmin": dmin, "nd": nd, "spk": (0, 0)}
+
+
+def _mseed(rng):
+    return int(rng.integers(0, 1 << 16))
+
+
+def _quiet(H, ci):
+    """ahead of a release_scratch: nothing staged, no record in flight (the shadow does not follow those through the release)"""
+    c = H.w.ctxs[ci]
+    if c.pending is not None:
+        yield ("score_wait", ci, {})
+    if c.staged is not None:
+        yield ("cost_const", ci, {})
+        yield ("cost_filter", ci, {})
+        yield ("disp_select", ci, {})
+
+
+def _score_sgm(H, ci, source):
+    if H.w.ctxs[ci].pending is not None:
+        yield ("score_wait", ci, {})
+    yield ("score", ci, {"source": source})
+
+
+def _m_hook_over_published(rng, H, ci):
+    if H.w.ctxs[ci].hook is not None:
+        yield ("hook_map", ci, {"mseed": None})
+    yield ("sgbm", ci, _sgm_args(rng, H.w.D))
+    yield ("wls", ci, {"source": "sgm"})
+    yield ("wls_publish", ci, {"on": True})
+    yield ("hook_map", ci, {"mseed": _mseed(rng)})
+    yield from _score_sgm(H, ci, SGM)
+    yield ("reproject", ci, {"source": "sgm", "outs": int(rng.integers(1, 8))})
+    yield ("hook_map", ci, {"mseed": None})
+    yield from _score_sgm(H, ci, SGM_INT)
+    yield ("reproject", ci, {"source": "sgm", "outs": int(rng.integers(1, 8)) | CLOUD})
+
+
+def _m_stale_invalid(rng, H, ci):
+    if H.w.ctxs[ci].hook is not None:
+        yield ("hook_map", ci, {"mseed": None})
+    yield ("sgbm", ci, _plain_sgm())
+    yield ("wls", ci, {"source": "sgm"})
+    yield ("wls_publish", ci, {"on": True})
+    yield ("sgbm", ci, dict(_sgm_args(rng, H.w.D), **dict(zip(("dmin", "nd"), ((2, H.w.D - 4), (-3, 16))[int(rng.integers(0, 2))]))))
+    yield ("reproject", ci, {"source": "sgm", "outs": XYZ | CLOUD})
+    yield from _score_sgm(H, ci, SGM)
+
+
+def _m_hook_invalid(rng, H, ci):
+    yield ("hook_map", ci, {"mseed": _mseed(rng)})
+    yield ("set_range", ci, {"dmin": 3, "nd": 0})
+    yield ("reproject", ci, {"source": "sgm", "outs": int(rng.integers(1, 8))})
+    yield ("wls", ci, {"source": "sgm"})
+    yield ("set_range", ci, {"dmin": -2, "nd": 0})
+    yield ("reproject", ci, {"source": "sgm", "outs": Z | CLOUD})
+
+
+def _m_rerun_after_release(rng, H, ci):
+    yield ("hook_map", ci, {"mseed": _mseed(rng)})
+    yield ("wls", ci, {"source": "sgm"})
+    yield ("wls_publish", ci, {"on": True})
+    yield ("reproject", ci, {"source": "sgm", "outs": int(rng.integers(1, 8))})
+    yield from _quiet(H, ci)
+    yield ("release_scratch", ci, {})
+    yield ("reproject", ci, {"source": "sgm", "outs": int(rng.integers(1, 8))})
+    yield ("wls", ci, {"source": "sgm"})
+
+
+def _m_table_reload(rng, H, ci):
+    a, b = ((0, 2), (1, 5), (4, 0), (2, 1), (3, 5), (6, 2), (7, 5))[int(rng.integers(0, 7))]          # two entries of WLS_PARAMS of different sigma
+    if H.w._stage_map(H.w.ctxs[ci]) is None:
+        yield ("hook_map", ci, {"mseed": _mseed(rng)})
+    yield ("wls_params", ci, _wls_par(a))
+    yield ("wls", ci, {"source": "sgm"})
+    yield ("wls_params", ci, _wls_par(b))
+    if rng.random() < 0.5:
+        yield ("wls", ci, {"source": "sgm"})
+        yield ("wls_params", ci, _wls_par(a))
+        yield ("wls", ci, {"source": "sgm"})
+        return
+    yield ("wls", ci, {"source": "sgm"})
+    yield ("hook_map", ci, {"mseed": _mseed(rng)})   # (the SGM source must outlive the release)
+    yield from _quiet(H, ci)
+    yield ("release_scratch", ci, {})
+    yield ("wls_params", ci, _wls_par(a))
+    yield ("wls", ci, {"source": "sgm"})
+
+
+def _a_new_pair(rng, H, ci):
+    c = H.w.ctxs[ci]
+    kinds = ["images", "frame"] + (["float"] if c.dtype == "f32" else [])
+    kind = kinds[int(rng.integers(0, len(kinds)))]
+    if kind == "frame":
+        return (kind, ci, {}) if c.pair != (RECT, False) else ("images", ci, {"k": 1})
+    k = int(rng.integers(0, NPAIRS - 1))
+    if (k, kind == "float") == c.pair:
+        k = (k + 1) % (NPAIRS - 1)
+    return (kind, ci, {"k": k})
+
+
+def _m_guide_follows_pair(rng, H, ci):
+    yield ("hook_map", ci, {"mseed": _mseed(rng)})
+    yield ("wls", ci, {"source": "sgm"})
+    yield ("reproject", ci, {"source": "sgm", "outs": CLOUD})
+    yield _a_new_pair(rng, H, ci)
+    yield ("wls", ci, {"source": "sgm"})
+    yield ("reproject", ci, {"source": "sgm", "outs": CLOUD | Z})
+
+
+def _m_staged_not_adopted(rng, H, ci):
+    yield ("hook_map", ci, {"mseed": _mseed(rng)})
+    yield ("wls_async", ci, {"source": "sgm"})
+    yield ("images_async", ci, {"k": (H.w.ctxs[ci].pair[0] + 1) % (NPAIRS - 1)})
+    yield ("wls_wait", ci, {})
+    yield ("reproject_async", ci, {"source": "sgm", "outs": CLOUD | int(rng.integers(0, 4))})
+    yield ("frame_async", ci, {}) if rng.random() < 0.5 else ("images_async", ci, {"k": (H.w.ctxs[ci].pair[0] + 2) % (NPAIRS - 1)})
+    yield ("reproject_wait", ci, {})
+
+
+def _m_gray_guide(rng, H, ci):
+    if H.w.ctxs[ci].hook is not None and rng.random() < 0.6:      # (with the hook plane on the gray plane guides all the same)
+        yield ("hook_map", ci, {"mseed": None})
+    yield ("sgbm_gray", ci, dict(_sgm_args(rng, H.w.D), k=int(rng.integers(0, NPAIRS))))
+    yield ("wls", ci, {"source": "sgm"})
+    yield ("reproject", ci, {"source": "sgm", "outs": CLOUD | int(rng.integers(0, 4))})
+    yield ("sgbm", ci, _sgm_args(rng, H.w.D))
+    yield ("wls", ci, {"source": "sgm"})
+    yield ("reproject", ci, {"source": "sgm", "outs": CLOUD})
+
+
+def _m_own_wls(rng, H, ci):
+    order = [int(i) for i in rng.permutation(NCTX)]
+    for i, j in zip(order, rng.permutation(3)):       # (entries 0 .. 2 of WLS_PARAMS: one iteration count, three lambdas and sigmas)
+        if H.w._stage_map(H.w.ctxs[i]) is None:
+            yield ("hook_map", i, {"mseed": _mseed(rng)})
+        yield ("wls_params", i, _wls_par(int(j)))
+    yield ("wls_batch", tuple(order), {"source": "sgm"})
+    yield ("wls_batch", (order[1], order[0]), {"source": "sgm"})
+    yield ("wls_params", order[0], _wls_par((int(rng.integers(0, 3)))))
+    yield ("wls_batch", (order[2], order[0], order[1]), {"source": "sgm"})
+
+
+def _m_own_depth_pp(rng, H, ci):
+    order = [int(i) for i in rng.permutation(NCTX)]
+    for i in order:
+        if H.w.ctxs[i].pair[1]:                       # (the members of a psm_post_process_batch hold pairs of one depth)
+            yield ("images", i, {"k": H.w.ctxs[i].pair[0]})
+        if not H.w.ctxs[i].whole_maps:
+            yield ("upload_maps", i, {"mseed": _mseed(rng), "masks": bool(rng.integers(0, 2))})
+    yield ("pp_batch", tuple(order), {"stages": LR | FILL})
+    yield ("reproject_batch", tuple(order), {"source": "gifm", "outs": int(rng.integers(1, 8))})
+    yield ("pp_batch", (order[2], order[0]), {"stages": PP_STAGES[int(rng.integers(0, 4))]})
+    yield ("reproject_batch", (order[1], order[2], order[0]), {"source": "gif", "outs": int(rng.integers(1, 8)) | CLOUD})
+
+
+def _m_batch_against_single(rng, H, ci):
+    if rng.random() < 0.5:
+        yield ("upload_maps", ci, {"mseed": _mseed(rng), "masks": bool(rng.integers(0, 2))})
+    else:
+        yield ("sgbm", ci, _plain_sgm())
+        yield ("sgbm_select", ci, {})
+    stages = PP_STAGES[int(rng.integers(0, 3))]
+    c = H.w.ctxs[ci]
+    others = [i for i in range(NCTX) if i != ci and H.w.ctxs[i].whole_maps and H.w.ctxs[i].pair[1] == c.pair[1]]
+    cis = [ci] + others[:int(rng.integers(0, 3))]
+    yield ("pp_batch", tuple(int(i) for i in rng.permutation(cis)), {"stages": stages})
+    yield ("pp_batch", (ci,), {"stages": LR})
+
+
+_MOTIFS = (_m_hook_over_published, _m_stale_invalid, _m_hook_invalid, _m_rerun_after_release, _m_table_reload, _m_guide_follows_pair,
+           _m_staged_not_adopted, _m_gray_guide, _m_own_wls, _m_own_depth_pp, _m_batch_against_single)
+_ALL_CTX = (_m_own_wls, _m_own_depth_pp, _m_batch_against_single)          # scripts whose batches name every context
+
+
+def _generate_tail(seed, steps) -> Walk:
+    """A walk of the tail vocabulary: four of the scripts above, one after the other, each on a context of its own choice, with
+    seeded ops of the other contexts between their steps and of any context between the scripts.  After every op that wrote a result
+    its own reader, then readers of other stages as in generate."""
+    rng = np.random.default_rng([seed, 20241])
+    shape = SHAPES[seed % 2]
+    dtype = "u8" if (shape == SHAPES[0] and seed % 6 == 4) else "f32"
+    H = _Holder()
+    H.w = World(shape, dtype)
+    out, count = [], {"ops": 0, "refused": 0}
+
+    def push(kind, ctx, args, forced=False):
+        w = H.w
+        named = (ctx,) if isinstance(ctx, int) else tuple(ctx)
+        st = Step(kind, ctx, args, window=any(w.ctxs[i].window for i in named))
+        trial = _copy(w)
+        st.refused = trial.apply(st)
+        if st.refused is not None:
+            if 4 * (count["refused"] + 1) > count["ops"] + 1:        # (keeps the share of refusals below a quarter at every prefix)
+                return
+            count["refused"] += 1
+        else:
+            H.w = w = trial
+        out.append(st)
+        count["ops"] += 1
+        if forced:
+            return
+        own = _OWN_READER.get(kind, ()) if st.refused is None else ()
+        for i in range(NCTX):
+            rd = w.readers(i)
+            first = [n for n in own if n in rd] if i in named else []
+            for n in first:
+                out.append(Step("read", i, {"what": n}))
+            rd = {n: v for n, v in rd.items() if n not in first}
+            if i in named:
+                rd = {n: v for n, v in rd.items() if v[0] != TAIL_STAGE_OF[kind]} or rd
+                take = min(len(rd), 1)
+            else:
+                take = min(len(rd), 1) if not isinstance(ctx, int) and rng.random() < 0.5 else 0
+            names = sorted(rd)
+            if take:
+                p = np.array([0.1 if n == "download_images" else 3.0 if n in NEW_READERS + ("score_maps", "download_valid") else 1.0 for n in names])
+                for j in rng.choice(len(names), size=take, replace=False, p=p / p.sum()):
+                    out.append(Step("read", i, {"what": names[int(j)]}))
+
+    for ci in range(NCTX):                            # every context starts with a Q; one with maps, one with a compute, one with a hook plane
+        push("reproject_q", ci, {"q": int(rng.integers(0, 2)), "zr": int(rng.integers(0, 2))}, forced=True)
+    for kind in ("cost_const", "cost_filter", "disp_select"):
+        push(kind, 0, {}, forced=True)
+    push("sgbm", 1, dict(_sgm_args(rng, shape[2]), dmin=0, nd=0))
+    push("hook_map", 2, {"mseed": _mseed(rng)})
+    steps += count["ops"]
+    scripts = [_MOTIFS[(4 * seed + 5 * j) % len(_MOTIFS)] for j in range(4)]
+    script, busy = None, ()
+    while count["ops"] < steps:
+        if script is None and scripts and rng.random() < 0.6:
+            m = scripts.pop(0)
+            ci = int(rng.integers(0, NCTX))
+            script, busy = m(rng, H, ci), (tuple(range(NCTX)) if m in _ALL_CTX else (ci,))
+        free = [i for i in range(NCTX) if i not in busy]
+        if script is not None and (not free or rng.random() < 0.7):
+            try:
+                push(*next(script))
+            except StopIteration:
+                script, busy = None, ()
+            continue
+        ci = int(free[int(rng.integers(0, len(free)))])
+        kind, ctx, args = _propose_tail(rng, H.w, ci, free)
+        push(kind, ctx, args)
+    return Walk(seed, shape, dtype, out, vocabulary="tail")
+
+
+TAIL_SEEDS = tuple(range(100, 124))

@@ -3,7 +3,10 @@ says a context holds between two calls; here its walks and a set of named interl
 call the bytes the context hands out - maps, masks, the SGM stage's planes, score planes and records, the staged pair, the
 JointWMF clustering - must equal what the CPU definitions give for the shadow's state.  Everything is bit for bit: there is no
 tolerance in this file.  A call the header says is refused must raise capi.PsmError naming the call, and the readers behind it
-must still see the state from before.
+must still see the state from before.  The walks of the tail vocabulary (test_tail_walk) do the same for the WLS stage, the
+reprojection stage, psm_post_process_batch, the hook plane and the gray compute: the int16 map and the float planes of
+psm_wls_download and the weight table as bit patterns, the dense planes of psm_reproject_download as bit patterns, the cloud's
+count and record bytes.
 
 One process, at most six contexts alive: three of the walk, one whose key plane serves as the caller's map buffer
 (psm_set_map_buffer wants device memory; the plane is never written, that context does not filter), two made and closed inside
@@ -144,6 +147,20 @@ class Rig:
             elif st.kind == "score_batch":
                 for i, rec in zip(st.ctx, dispest.score_batch(des, a["source"])):
                     self.check_record(rec, after.ctxs[i].score, ("score_batch", i))
+            elif st.kind == "wls_batch":
+                src, mask = self.wls_source(a["source"])
+                for i, m in zip(st.ctx, dispest.wls_batch(des, src, use_mask=mask)):
+                    assert same(m, self.R(after.ctxs[i].wls)["disp"]), ("wls_batch", i)
+            elif st.kind == "reproject_batch":
+                src, mask = self.depth_source(a["source"])
+                for i, n in zip(st.ctx, dispest.reproject_batch(des, src, a["outs"], use_mask=mask)):
+                    assert n == len(self.R(after.ctxs[i].depth[0])["cloud"]), ("reproject_batch", i, n)
+            elif st.kind == "pp_batch":
+                dispest.post_process_batch(des, bool(a["stages"] & S.LR), bool(a["stages"] & S.FILL), bool(a["stages"] & S.WM))
+                for i, d in zip(st.ctx, des):            # (the call's own downloads: psm_download_maps and psm_download_valid of every member)
+                    c = after.ctxs[i]
+                    assert same(d.lDisMap, self.R(c.maps)[0]) and same(d.rDisMap, self.R(c.maps)[1]), ("post_process_batch: maps", i)
+                    assert same(d.lValid, self.R(c.mask)[0]) and same(d.rValid, self.R(c.mask)[1]), ("post_process_batch: masks", i)
             else:
                 raise KeyError(st.kind)
             return
@@ -234,8 +251,88 @@ class Rig:
                 self.gather_into(de, a["k"], a["cut"])
         elif k == "merge":
             self.merge_into(de, a["k"], a["cut"])
+        elif k == "wls":
+            src, mask = self.wls_source(a["source"])
+            de.WLS_GPU(src, use_mask=mask)
+        elif k == "wls_async":
+            src, mask = self.wls_source(a["source"])
+            self.asynchronous(de, lambda: de.WLS_GPU(src, use_mask=mask))
+        elif k == "wls_wait":
+            de.wls_wait()
+        elif k == "wls_params":
+            de.setWLS(a["lam"], a["sigma"], a["iterations"])
+        elif k == "wls_publish":
+            de.wls_publish(a["on"])
+        elif k == "hook_map":
+            de.upload_sgm_map(None if a["mseed"] is None else self.R(c.hook)["d16"])
+        elif k == "reproject":
+            src, mask = self.depth_source(a["source"])
+            n = de.Reproject_GPU(src, a["outs"], use_mask=mask)
+            assert n == len(self.R(c.depth[0])["cloud"]), ("Reproject_GPU", n)
+        elif k == "reproject_async":
+            src, mask = self.depth_source(a["source"])
+            assert self.asynchronous(de, lambda: de.Reproject_GPU(src, a["outs"], use_mask=mask)) is None
+        elif k == "reproject_wait":
+            n = de.reproject_wait()
+            assert n == len(self.R(c.depth[0])["cloud"]), ("reproject_wait", n)
+        elif k == "reproject_q":
+            de.setReprojection(S.q_matrix(a["q"]), S.Q_CROPS[a["q"]], S.Z_RANGES[a["zr"]])
+        elif k == "sgbm_gray":
+            kw = self.sgbm_kw(a["cost"], a["mode"], a["dmin"], a["nd"], a["spk"])
+            assert same(de.SGBM_GPU(gray=self.data.gray(a["k"]), **kw), self.R(c.sgm)["d16"]), "SGBM_GPU(gray=...)"
         else:
             raise KeyError(k)
+
+    def wls_source(self, source):
+        return (self.capi.PSM_WLS_SGM if source == "sgm" else self.capi.PSM_WLS_GIF), source == "gifm"
+
+    def depth_source(self, source):
+        return (self.capi.PSM_DEPTH_SGM if source == "sgm" else self.capi.PSM_DEPTH_GIF), source == "gifm"
+
+    def asynchronous(self, de, call):
+        de.set_option(self.capi.PSM_OPT_ASYNC, 1)
+        try:
+            return call()
+        finally:
+            de.set_option(self.capi.PSM_OPT_ASYNC, 0)
+
+    def wls_is(self, de, expr, what=""):
+        """every plane of the WLS stage against the model: the int16 map; q, num, den and the table as bit patterns"""
+        m = self.R(expr)
+        q, num, den = de.wls_planes()
+        got = {"disp": de.wls_map(), "q": q, "num": num, "den": den, "tab": de.wls_table()}
+        assert got["disp"].dtype == np.int16
+        bad = [k for k in ("disp", "q", "num", "den", "tab")
+               if not np.array_equal(got[k] if k == "disp" else got[k].view(np.uint32), m[k] if k == "disp" else m[k].view(np.uint32))]
+        assert not bad, (what, bad, expr)
+
+    def depth_is(self, de, expr, outs, what=""):
+        """the planes of the reprojection stage that were among the outputs, and the cloud, against the model; the planes that were
+        not are refused, naming psm_reproject_download"""
+        import ctypes as C
+        capi = self.capi
+        m = self.R(expr)
+        de._depth_outputs = outs                          # (the wrapper sizes its arrays by the last Reproject_GPU it was asked for)
+        xyz, z = de.reprojected()
+        assert (xyz is not None) == bool(outs & S.XYZ) and (z is not None) == bool(outs & S.Z)
+        if xyz is not None:
+            assert np.array_equal(xyz.view(np.uint32), m["xyz"].view(np.uint32)), (what, "xyz", expr)
+        if z is not None:
+            assert np.array_equal(z.view(np.uint32), m["z"].view(np.uint32)), (what, "z", expr)
+        buf = np.empty((self.H, self.W, 3), np.float32)
+        for bit, args in ((S.XYZ, (buf.ctypes.data_as(C.c_void_p), None)), (S.Z, (None, buf.ctypes.data_as(C.c_void_p)))):
+            if not outs & bit:
+                assert de._lib.psm_reproject_download(de._h, *args, 0) != 0 and capi.last_error(de._h).startswith("psm_reproject_download"), (what, bit)
+        if outs & S.CLOUD:
+            self.cloud_is(de, expr, what)
+        else:
+            with pytest.raises(capi.PsmError, match="psm_reproject_download_cloud"):
+                de.cloud()
+
+    def cloud_is(self, de, expr, what=""):
+        m = self.R(expr)["cloud"]
+        got = de.cloud()
+        assert len(got) == len(m) and got.tobytes() == m.tobytes(), (what, "cloud", len(got), len(m), expr)
 
     def read(self, st, want):
         """A reader against the shadow.  -> None, or what differs."""
@@ -262,6 +359,15 @@ class Rig:
                 pairs = list(zip(de.score_maps(), (m["ldisp"], m["emap"])))
         elif what == "download_images":
             pairs = list(zip(de.download_images(), R(want[0])))
+        elif what == "wls_planes":
+            self.wls_is(de, want[0], what)
+            return None
+        elif what == "reprojected":
+            self.depth_is(de, want[0], want[1], what)
+            return None
+        elif what == "cloud":
+            self.cloud_is(de, want[0], what)
+            return None
         elif what == "jwmf_clusters":
             pairs = []
             for side, e in enumerate(want[0]):
@@ -280,8 +386,11 @@ class Rig:
 def test_walk(psm, oracle, seed):
     """One walk of tests/seq_model.py on real contexts, op by op.  On a mismatch the walk's log up to that step is the failure's
     message: a reproducible script."""
+    replay_on_the_device(psm, oracle, S.generate(seed), seed)
+
+
+def replay_on_the_device(psm, oracle, walk, seed):
     import copy
-    walk = S.generate(seed)
     with Rig(psm, oracle, walk.shape, walk.dtype, seed) as rig:
         before = S.World(walk.shape, walk.dtype)
         for i, st, after, want in S.replay(walk):
@@ -297,6 +406,13 @@ def test_walk(psm, oracle, seed):
             except BaseException as e:
                 raise AssertionError(f"step {i} ({st!r}): {type(e).__name__}: {str(e)[:600]}\n{walk.log(i + 1)}") from e
             before = copy.deepcopy(after)
+
+
+@pytest.mark.parametrize("seed", S.TAIL_SEEDS)
+def test_tail_walk(psm, oracle, seed):
+    """One walk of the tail vocabulary (the WLS stage, the reprojection stage, psm_post_process_batch, the hook plane, the gray
+    compute, between the older calls) on real contexts, op by op, as test_walk."""
+    replay_on_the_device(psm, oracle, S.generate(seed, vocabulary="tail"), seed)
 
 
 # ---------------------------------------------------------------------------------------------------------- named scenarios
@@ -603,3 +719,192 @@ def test_mask_lifetime(psm, oracle):
         # JointWMF filters in place and keeps the mask it found
         de.DispSelect_GPU(); de.LRCheck_GPU(); de.JointWMF_GPU(2); de.FillInv_GPU()
         rig.maps_are(de, ("fill", ("jw", gf, 0, 2), ("lr", gf)), what="fill behind JointWMF")
+
+
+def test_batch_tables_wls_reproject_and_pp(psm, oracle):
+    """The device tables of psm_wls_filter_batch, psm_reproject_batch and psm_post_process_batch, as test_batch_tables_sgm_and_score
+    for the older ones: three members; one gives back its scratch and gets new buffers; two in another order; a member that changed
+    lambda and sigma only; a member alone; the first context of one batch as the last of the next; and a member without an SGM result,
+    which makes the SGM-source batches refuse with every other member's planes still what they were."""
+    from primestereomatch_amd import dispest
+    capi = psm.capi
+    with Rig(psm, oracle, SHAPE_B, "f32", 109) as rig:
+        a, b, c = rig.des
+        R = rig.R
+        pars = [S.WLS_PARAMS[0], S.WLS_PARAMS[1], S.WLS_PARAMS[2]]          # one iteration count, three lambdas and sigmas
+        up = [("up", 20 + k) for k in range(3)]
+        sgm = [("sgm", k, ("sad",), "hh", 0, 0, (0, 0)) for k in range(3)]
+        maps = list(up)
+        for k, de in enumerate(rig.des):
+            de.setInputImages(*rig.data.pairs[k])
+            de.setReprojection(S.q_matrix(k % 2), S.Q_CROPS[k % 2], S.Z_RANGES[k % 2])
+            de.setWLS(*pars[k])
+            de.upload_maps(*S.rand_maps(rig.W, rig.H, rig.D, 20 + k)[:2])
+
+        def wls_e(k):
+            return ("wls", ("d16", sgm[k]), -16, ("guide", "pair", k), pars[k])
+
+        def depth_e(k, gif=False):
+            return ("depth", ("gif", maps[k]) if gif else ("d16", sgm[k]), None if gif else -16, k % 2, k % 2, ("guide", "pair", k))
+
+        def wls_run(ks):
+            for k, m in zip(ks, dispest.wls_batch([rig.des[k] for k in ks], capi.PSM_WLS_SGM)):
+                assert same(m, R(wls_e(k))["disp"]), ("wls_batch", ks, k)
+                rig.wls_is(rig.des[k], wls_e(k), ("wls_batch", ks, k))
+
+        def depth_run(ks, outs, gif=False):
+            counts = dispest.reproject_batch([rig.des[k] for k in ks], capi.PSM_DEPTH_GIF if gif else capi.PSM_DEPTH_SGM, outs)
+            for k, n in zip(ks, counts):
+                assert n == len(R(depth_e(k, gif))["cloud"]), ("reproject_batch", ks, k)
+                rig.depth_is(rig.des[k], depth_e(k, gif), outs, ("reproject_batch", ks, k))
+
+        def pp_run(ks, stages):
+            dispest.post_process_batch([rig.des[k] for k in ks], bool(stages & S.LR), bool(stages & S.FILL), bool(stages & S.WM))
+            for k in ks:
+                lr = ("lr", maps[k])
+                if stages & S.FILL:
+                    maps[k] = ("fill", maps[k], lr)
+                if stages & S.WM:
+                    maps[k] = ("wm", maps[k], lr, k)
+                rig.maps_are(rig.des[k], maps[k], what=("post_process_batch", ks, k))
+                if stages == S.LR:
+                    assert all(same(g, w) for g, w in zip(rig.des[k].download_valid(), R(lr))), ("post_process_batch", ks, k)
+
+        for de, m, e in zip(rig.des, dispest.sgbm_batch([a, b, c]), sgm):
+            assert same(m, R(e)["d16"])
+        wls_run((0, 1, 2)); depth_run((0, 1, 2), 7); pp_run((0, 1, 2), S.LR | S.FILL)
+        b.release_scratch()                                                  # b's planes of all three stages go; its maps stay
+        assert same(b.SGBM_GPU(), R(sgm[1])["d16"])
+        wls_run((2, 1)); depth_run((2, 1), S.CLOUD | S.Z); pp_run((2, 1), S.LR | S.FILL | S.WM)
+        rig.wls_is(a, wls_e(0), "a, not in the batch"); rig.depth_is(a, depth_e(0), 7, "a, not in the batch"); rig.maps_are(a, maps[0])
+        pars[1] = (123.0, 7.0, 3)                                            # lambda and sigma only: the entry's lambdas, b's weight table
+        b.setWLS(*pars[1])
+        wls_run((2, 1))
+        wls_run((1,)); depth_run((1,), S.XYZ, gif=True); pp_run((1,), S.LR)
+        wls_run((1, 2, 0)); depth_run((1, 2, 0), S.CLOUD, gif=True); pp_run((1, 2, 0), S.LR)      # a: first of the first batches, last here
+        b.release_scratch()
+        # (b's SGM result went with its scratch: the SGM-source batches must refuse it, naming the call)
+        with pytest.raises(capi.PsmError, match="psm_wls_filter_batch"):
+            dispest.wls_batch([c, b, a], capi.PSM_WLS_SGM)
+        with pytest.raises(capi.PsmError, match="psm_reproject_batch"):
+            dispest.reproject_batch([c, b, a], capi.PSM_DEPTH_SGM, 7)
+        for k in (0, 2):
+            rig.wls_is(rig.des[k], wls_e(k), "behind the refusals"); rig.depth_is(rig.des[k], depth_e(k, gif=True), S.CLOUD, "behind the refusals")
+        for call, fn in (("psm_wls_download", b.wls_map), ("psm_reproject_download_cloud", b.cloud)):
+            with pytest.raises(capi.PsmError, match=call):
+                fn()
+        wls_run((2, 0)); depth_run((0, 2), 7)
+
+
+def test_published_map_lifetime(psm, oracle):
+    """Which int16 map and which invalid value the SGM sources of psm_score and psm_reproject read (psm_ctx.h: sgm_stage_map,
+    wls_published, sgm_source_map, sgm_source_invalid), stepped through: hook plane on or off, publishing on or off, a compute or
+    none, psm_release_scratch.  At every stop the score record and planes of both SGM sources, the dense planes and the cloud."""
+    capi = psm.capi
+    with Rig(psm, oracle, SHAPE_A, "f32", 110, nctx=1) as rig:
+        de, R, D = rig.des[0], rig.R, rig.D
+        de.setReprojection(S.q_matrix(0), S.Q_CROPS[0], S.Z_RANGES[0])
+        de.set_truth(*rig.data.truths[0])
+        guide = ("guide", "pair", 0)
+        sgm0, sgm2 = ("sgm", 0, ("sad",), "hh", 0, 0, (0, 0)), ("sgm", 0, ("sad",), "hh", 2, D - 4, (0, 0))
+        hook = ("hook", 7, -16)
+
+        def stop(src, inv, where):
+            for source in (S.SGM, S.SGM_INT):
+                e = ("score", source, src, 0)
+                rig.check_record(de.Score_GPU(source), e, where)
+                ld, em = de.score_maps()
+                assert same(ld, R(e)["ldisp"]) and same(em, R(e)["emap"]), where
+            e = ("depth", ("d16", src), inv, 0, 0, guide)
+            assert de.Reproject_GPU(capi.PSM_DEPTH_SGM, 7) == len(R(e)["cloud"]), where
+            rig.depth_is(de, e, 7, where)
+
+        def wls(src, inv, where):
+            e = ("wls", ("d16", src), inv, guide, S.WLS_DEFAULT)
+            de.WLS_GPU(capi.PSM_WLS_SGM)
+            rig.wls_is(de, e, where)
+            return e
+
+        assert same(de.SGBM_GPU(), R(sgm0)["d16"])
+        stop(sgm0, -16, "a compute")
+        w0 = wls(sgm0, -16, "the filter of the compute's map")
+        stop(sgm0, -16, "a WLS result that is not published")
+        de.wls_publish(True)
+        stop(w0, -16, "published")
+        de.upload_sgm_map(R(hook)["d16"])
+        stop(hook, -16, "the hook plane wins over a published result")
+        w1 = wls(hook, -16, "the filter reads the hook plane")
+        stop(hook, -16, "... which still wins")
+        de._ck(de._lib.psm_sgm_set_range(de._h, 3, 0), "set_range")
+        stop(hook, 32, "the hook plane's invalid value is the current setting's")
+        de.upload_sgm_map(None)
+        stop(w1, -16, "the hook dropped: the published result with the invalid value it was made with")
+        assert same(de.SGBM_GPU(min_disparity=2, num_disparities=D - 4), R(sgm2)["d16"])
+        stop(w1, -16, "a compute with another min_disparity: the published map keeps its own invalid value")
+        w2 = wls(sgm2, 16, "published, the filter still reads the SGM stage's map, never its own")
+        stop(w2, 16, "the new result is the published one")
+        de.wls_publish(False)
+        stop(sgm2, 16, "publishing off: the compute's map with its range's invalid value")
+        de.wls_publish(True)
+        de.release_scratch()                                                 # the compute, the WLS planes and publishing go
+        for call, fn in (("psm_score", lambda: de.Score_GPU(S.SGM)), ("psm_reproject", lambda: de.Reproject_GPU(capi.PSM_DEPTH_SGM, 7)),
+                         ("psm_wls_filter", lambda: de.WLS_GPU(capi.PSM_WLS_SGM)), ("psm_wls_publish", lambda: de.wls_publish(True))):
+            with pytest.raises(capi.PsmError, match=call):
+                fn()
+        de.upload_sgm_map(R(hook)["d16"])
+        stop(hook, 16, "after the release: the hook plane alone, the setting is still (2, D - 4)")
+        de.upload_sgm_map(None)
+        assert same(de.SGBM_GPU(), R(sgm0)["d16"])
+        stop(sgm0, -16, "the release switched publishing off: the compute's map again")
+
+
+def test_guide_and_colours_follow_the_pair(psm, oracle):
+    """The left image that guides psm_wls_filter and colours the cloud (psm_ctx.h: colour_of) is the current pair's at the time of the
+    call - a u8 pair, a float pair quantised, a rectified frame; a staged pair counts from its adoption on - and under an SGM source
+    the left plane of a gray compute, whichever map is read."""
+    capi = psm.capi
+    with Rig(psm, oracle, SHAPE_A, "f32", 111, nctx=1) as rig:
+        de, R = rig.des[0], rig.R
+        de.setReprojection(S.q_matrix(0), S.Q_CROPS[0], S.Z_RANGES[0])
+        hook = ("hook", 9, -16)
+        de.upload_sgm_map(R(hook)["d16"])
+
+        def both(guide, where, src=hook):
+            we = ("wls", ("d16", src), -16, guide, S.WLS_DEFAULT)
+            de.WLS_GPU(capi.PSM_WLS_SGM)
+            rig.wls_is(de, we, where)
+            e = ("depth", ("d16", src), -16, 0, 0, guide)
+            assert de.Reproject_GPU(capi.PSM_DEPTH_SGM, S.CLOUD | S.Z) == len(R(e)["cloud"]), where
+            rig.depth_is(de, e, S.CLOUD | S.Z, where)
+            return we
+
+        both(("guide", "pair", 0), "the constructor's pair")
+        de.setInputImages(*rig.data.pairs[1])
+        both(("guide", "pair", 1), "a u8 pair")
+        de.setInputImages(*rig.data.float_pair(2))
+        both(("guide", "fpair", 2), "a float pair")
+        de.setInputFrame(rig.data.frame)
+        rect = both(("guide", "pair", S.RECT), "a rectified frame")
+        de.setInputImages_async(*rig.data.pairs[0])
+        both(("guide", "pair", S.RECT), "a staged pair is not the current one")
+        rig.asynchronous(de, lambda: de.WLS_GPU(capi.PSM_WLS_SGM))            # an asynchronous run, then a staged upload next to it
+        de.setInputImages_async(*rig.data.pairs[1])
+        de.wls_wait()
+        rig.wls_is(de, rect, "the asynchronous run read the frame, not the pair staged behind it")
+        assert rig.asynchronous(de, lambda: de.Reproject_GPU(capi.PSM_DEPTH_SGM, S.CLOUD)) is None
+        de.setInputImages_async(*rig.data.pairs[1])
+        e = ("depth", ("d16", hook), -16, 0, 0, ("guide", "pair", S.RECT))
+        assert de.reproject_wait() == len(R(e)["cloud"])
+        rig.cloud_is(de, e, "the asynchronous cloud took the frame's colours")
+        rig.frame(de)                                                        # CostConst adopts the staged pair
+        both(("guide", "pair", 1), "adopted")
+        gray = ("sgm", ("g", 2), ("sad",), "hh", 0, 0, (0, 0))
+        assert same(de.SGBM_GPU(gray=rig.data.gray(2)), R(gray)["d16"])
+        both(("guide", "gray", 2), "a gray compute: its left plane, though the hook plane is the map")
+        de.upload_sgm_map(None)
+        both(("guide", "gray", 2), "... and with its own map", src=gray)
+        de.WLS_GPU(capi.PSM_WLS_GIF)                                          # the GIF source keeps the pair
+        rig.wls_is(de, ("wls", ("gif", ("gf", 1, "f32"), None), -16, ("guide", "pair", 1), S.WLS_DEFAULT), "the GIF source")
+        colour = ("sgm", 1, ("sad",), "hh", 0, 0, (0, 0))
+        assert same(de.SGBM_GPU(), R(colour)["d16"])
+        both(("guide", "pair", 1), "a 3-channel compute brings the SGM source back to the pair", src=colour)
