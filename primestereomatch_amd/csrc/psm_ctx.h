@@ -5,9 +5,9 @@
 //   psm_api_filter.cpp  CostConst / CostFilter: which plane rows are current (ensure_planes), what is built lazily, which form
 //                       of the fused kernel runs, materialisation
 //   psm_api_select.cpp  DispSelect: maps, packed minima, row stripes and disparity shards
-//   psm_api_pp.cpp      post-processing: L-R check, invalid fill, weighted median (psm::WmState; its sweep schedule, block
-//                       layout and cache decision are the host-only psm_wm_sched.h), and the three of several contexts in
-//                       shared launches (psm_post_process_batch, psm::WmBatch)
+//   psm_api_pp.cpp      post-processing: L-R check, invalid fill, weighted median of one context or of several in shared
+//                       launches (psm_post_process_batch) - one launch sequence, pp_enqueue (psm::WmState, psm::WmBatch; the sweep
+//                       schedule, block layout and cache decision are the host-only psm_wm_sched.h)
 //   psm_api_batch.cpp   several Middlebury-size pairs per launch (psm_compute_batch); what every batch entry point shares: the
 //                       device table of the members' records (psm::DevTable), the join and fork of the members' streams, the
 //                       member checks
@@ -126,22 +126,21 @@ struct JwBatch {
     size_t cap = 0;                                // images
 };
 
-// psm_wgt_median (psm_api_pp.cpp): the scratch of its two forms, allocated on first use, and what the last call reports.  Freed by
-// wm_free alone.
+// The plain weighted median (pp_enqueue, psm_api_pp.cpp): a context's own scratch of the two forms, allocated on first use, and what
+// the last call reports.  Freed by wm_free alone.
 struct WmState {
     int *flow = nullptr;                           // the dataflow form: nxt[H][W+1], prog[H], err[1]
-    uint8_t *block = nullptr;                      // the sweep form: both sides' state and the per-sweep counters of both maps (wm_layout, psm_wm_sched.h)
+    uint8_t *block = nullptr;                      // the sweep form: both sides' state (wm_layout, psm_wm_sched.h)
     float *wts = nullptr;                          // ... the 19 x 19 window weights of every invalid pixel (formed once per call, read by every evaluation)
     size_t wts_n = 0;                              // floats
-    int *pin = nullptr;                            // page-locked snapshots of the counters (two slots: a group's counters are read while the next group runs)
-    hipEvent_t ev[2] = {nullptr, nullptr};         // ... the snapshot into a slot has executed
     int sweeps[2] = {0, 0};                        // last call: sweeps until the fixed point (-1: dataflow form), evaluations
     long long evals[2] = {0, 0};
 };
 
-// psm_post_process_batch (psm_api_pp.cpp; this context as the first of the call): the device table of the members' PpPair records,
-// and - the median being among the stages - the counters of all 2 n maps in one block, so that one copy kernel snapshots them all
-// into `pin`.  Every other buffer of the median stays the member's own (WmState).  Freed by wm_free alone.
+// The post-processing tail with this context as the first of the call (pp_enqueue; a single call's only one): the per-sweep counters
+// of all 2 n maps in one block, so that one fill clears and one copy kernel snapshots them all into `pin` (two slots: a group's
+// counters are read while the next group runs), and - n > 1 - the device table of the members' PpPair records.  Every other buffer
+// of the median stays the member's own (WmState).  Freed by wm_free alone.
 struct WmBatch {
     DevTable tab;
     int *cnt = nullptr;                            // [cap] x WM_NCNT counters, map 2 i + s: side s of member i
@@ -480,7 +479,7 @@ void jwmf_batch_free(psm_ctx *c);                // what the context holds as th
 // psm_api_sgm.cpp
 void sgm_free(psm_ctx *c);                       // the stage's buffers and events (its parameters stay)
 // psm_api_pp.cpp
-void wm_free(psm_ctx *c, bool all);              // the weighted median's device scratch; all: its page-locked snapshots and events too
+void wm_free(psm_ctx *c, bool all);              // the weighted median's scratch, counters, snapshots and table; all: its events too
 // psm_api_score.cpp
 void score_free(psm_ctx *c, bool truth);         // the stage's scratch and events; truth: the uploaded truth, mask and hook map too
 // The int16 map the SGM source of psm_wls_filter reads - the plane of psm_score_upload_sgm_map while it is on, else the last

@@ -124,12 +124,7 @@ void launch_wta(hipStream_t s, const float *vol, int W, int H, int d_begin, int 
 // min over nranks key planes -> map
 void launch_merge(hipStream_t s, const long long *keys_all, size_t rank_stride, int nranks, int n,
                   uint8_t *map);
-// left-right check on two maps
-void launch_lr_check(hipStream_t s, const uint8_t *l, const uint8_t *r, int W, int H, uint8_t *lv,
-                     uint8_t *rv);
-
-// fill invalid pixels of one map in place (valid: 0/1 per pixel)
-void launch_fill_inv(hipStream_t s, uint8_t *dis, const uint8_t *valid, size_t side, int W, int H);   // both maps: the right one `side` bytes behind
+// (the left-right check and the fill of invalid pixels: with the post-processing tail below, PpRecs)
 
 // weighted-median post-filter of one map, in place, with the reference's raster-order semantics (psm_pp.hip).
 // nxt: scratch of H*(W+1) ints, prog: H ints, err: 1 int (set to 1 if the dataflow watchdog fired)
@@ -150,22 +145,34 @@ struct WmSide {
     const float *wts;             // weight cache of this map (null: none, or an empty map)
 };
 struct WmPair { WmSide s[2]; };
-void launch_wm_seed(hipStream_t s, const WmPair &p, int W, int H);
-void launch_wm_sweep(hipStream_t s, const WmPair &p, int W, int H, int maxDis, int sw, bool cached, bool tail);
-void launch_wm_weights(hipStream_t s, const float4 *g1, int W, int H, int right, const int *inv, const int *n_inv, int n, float *wts, int *slot_of);
-// A member of psm_post_process_batch as the _b entries of the kernels above find it in the batch's device table (the pair on a grid
-// axis of its own): the sweep state of its two maps - of which the L-R check and the fill read cur and valid alone - and the masks as
-// the L-R check writes them.  A side's cnt lies in the counter block of the batch's first context, the counters of all maps one
-// behind the other; wts of every side is set when the batch is cached.
+// One pair of the post-processing tail (psm_lr_check, psm_fill_invalid, psm_wgt_median, psm_post_process_batch) as its kernels find
+// it, the pair on blockIdx.z and the side on blockIdx.y: the sweep state of its two maps - of which the L-R check and the fill read
+// cur and valid alone - and the masks as the L-R check writes them.  A side's cnt lies in the counter block of the call's first
+// context, the counters of all maps one behind the other; wts of every side is set when the call is cached.
 struct PpPair {
     WmPair wm;
     uint8_t *lv, *rv;
 };
-void launch_lr_check_b(hipStream_t s, const PpPair *tab, int n, int W, int H);
-void launch_fill_inv_b(hipStream_t s, const PpPair *tab, int n, int W, int H);
-void launch_wm_seed_b(hipStream_t s, const PpPair *tab, int n, int W, int H);
-void launch_wm_weights_b(hipStream_t s, const PpPair *tab, int n, int W, int H, int n_max);
-void launch_wm_sweep_b(hipStream_t s, const PpPair *tab, int n, int W, int H, int maxDis, int sw, bool cached, bool tail);
+// The n records of one call as the host filled them.  dev == nullptr (n == 1): the record travels by value in the kernarg (PpVal,
+// 256 bytes); else the kernels read the device table at dev.  Either way the index is uniform per workgroup: scalar loads ahead of
+// one body (pp_rec).  Every tail kernel is one template over the two sources.
+struct PpRecs { const PpPair *host, *dev; int n; };
+struct PpVal { PpPair r; };
+using PpTab = const PpPair *__restrict__;
+__device__ __forceinline__ const PpPair &pp_rec(const PpVal &v) { return v.r; }
+__device__ __forceinline__ const PpPair &pp_rec(const PpPair *tab) { return tab[blockIdx.z]; }
+// one launch of a tail kernel over either source (grid.z = q.n)
+template <typename... A>
+void pp_launch(hipStream_t st, void (*kv)(PpVal, A...), void (*kt)(const PpPair *, A...), dim3 grid, dim3 block, size_t lds, const PpRecs &q, A... rest)
+{
+    if (q.dev) hipLaunchKernelGGL(kt, grid, block, lds, st, q.dev, rest...);
+    else hipLaunchKernelGGL(kv, grid, block, lds, st, PpVal{q.host[0]}, rest...);
+}
+void launch_lr_check(hipStream_t s, const PpRecs &q, int W, int H);       // left-right check of the two maps of every pair -> lv, rv
+void launch_fill_inv(hipStream_t s, const PpRecs &q, int W, int H);       // fill of the invalid pixels of every map in place
+void launch_wm_seed(hipStream_t s, const PpRecs &q, int W, int H);        // (the counters of all maps are zero: the caller's memset)
+void launch_wm_weights(hipStream_t s, const PpRecs &q, int W, int H, int n_max);   // n_max: an upper bound of the invalid pixels of any side
+void launch_wm_sweep(hipStream_t s, const PpRecs &q, int W, int H, int maxDis, int sw, bool cached, bool tail);
 
 // ---- Fast Guided Filter variant (psm_fgf.hip); sub = subsample rate, small planes are (H/sub) x (W/sub) ----
 // g1 -> subsampled guidance ism, its means msm and the inverse covariance planes v1 = {irr,irg,irb,igg}, v2 = {igb,ibb}

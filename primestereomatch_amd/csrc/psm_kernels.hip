@@ -812,15 +812,11 @@ __device__ __forceinline__ void lr_check_px(const uint8_t *__restrict__ l, const
     lDep = lr[lLoc];
     rv[(size_t)y * W + x] = (rDep == lDep && rDep >= 2) ? 1 : 0;
 }
-__global__ __launch_bounds__(256) void k_lr_check(const uint8_t *__restrict__ l, const uint8_t *__restrict__ r, int W, int H,
-                                                 uint8_t *__restrict__ lv, uint8_t *__restrict__ rv)
+// the pair on blockIdx.z, its maps and masks from the record source S (psm_kernels.h, PpRecs): PpVal or PpTab
+template <typename S>
+__global__ __launch_bounds__(256) void k_lr_check(S src, int W)
 {
-    lr_check_px(l, r, W, lv, rv);
-}
-// ... of the pairs of a batch: the pair on blockIdx.z, its maps and masks from the device table (psm_post_process_batch)
-__global__ __launch_bounds__(256) void k_lr_check_b(const PpPair *__restrict__ tab, int W)
-{
-    const PpPair &p = tab[blockIdx.z];
+    const PpPair &p = pp_rec(src);
     lr_check_px(p.wm.s[0].cur, p.wm.s[1].cur, W, p.lv, p.rv);
 }
 
@@ -879,39 +875,23 @@ __device__ __forceinline__ void fill_inv_row(short *row, uint8_t *__restrict__ d
         if (m) carry = __builtin_amdgcn_readlane(val, __builtin_ctzll(m));
     }
 }
-__global__ __launch_bounds__(64) void k_fill_inv(uint8_t *__restrict__ dis0, const uint8_t *__restrict__ valid0, size_t side, int W)
+template <typename S>
+__global__ __launch_bounds__(64) void k_fill_inv(S src, int W)
 {
     extern __shared__ short row[];
-    const size_t at = blockIdx.y * side + (size_t)blockIdx.x * W;
-    fill_inv_row(row, dis0 + at, valid0 + at, W);
-}
-__global__ __launch_bounds__(64) void k_fill_inv_b(const PpPair *__restrict__ tab, int W)
-{
-    extern __shared__ short row[];
-    const WmSide &a = tab[blockIdx.z].wm.s[blockIdx.y];
+    const WmSide &a = pp_rec(src).wm.s[blockIdx.y];
     const size_t at = (size_t)blockIdx.x * W;
     fill_inv_row(row, a.cur + at, a.valid + at, W);
 }
 
-// both maps of a pair: dis / valid of the right map lie `side` bytes behind the left map's
-void launch_fill_inv(hipStream_t s, uint8_t *dis, const uint8_t *valid, size_t side, int W, int H)
+void launch_fill_inv(hipStream_t s, const PpRecs &q, int W, int H)
 {
-    hipLaunchKernelGGL(k_fill_inv, dim3(H, 2), dim3(64), 2 * (size_t)W * sizeof(short), s, dis, valid, side, W);
+    pp_launch(s, k_fill_inv<PpVal>, k_fill_inv<PpTab>, dim3(H, 2, q.n), dim3(64), 2 * (size_t)W * sizeof(short), q, W);
 }
 
-void launch_fill_inv_b(hipStream_t s, const PpPair *tab, int n, int W, int H)
+void launch_lr_check(hipStream_t s, const PpRecs &q, int W, int H)
 {
-    hipLaunchKernelGGL(k_fill_inv_b, dim3(H, 2, n), dim3(64), 2 * (size_t)W * sizeof(short), s, tab, W);
-}
-
-void launch_lr_check_b(hipStream_t s, const PpPair *tab, int n, int W, int H)
-{
-    hipLaunchKernelGGL(k_lr_check_b, dim3((W + 255) / 256, H, n), dim3(256), 0, s, tab, W);
-}
-
-void launch_lr_check(hipStream_t s, const uint8_t *l, const uint8_t *r, int W, int H, uint8_t *lv, uint8_t *rv)
-{
-    hipLaunchKernelGGL(k_lr_check, dim3((W + 255) / 256, H), dim3(256), 0, s, l, r, W, H, lv, rv);
+    pp_launch(s, k_lr_check<PpVal>, k_lr_check<PpTab>, dim3((W + 255) / 256, H, q.n), dim3(256), 0, q, W);
 }
 
 // ------------------------------------------------------------------------------------------

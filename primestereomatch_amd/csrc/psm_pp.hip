@@ -314,9 +314,11 @@ __device__ __forceinline__ void wm_seed(const WmSide &a, int HW, int nb)
         a.inv[slot++] = base + k;
     }
 }
-__global__ __launch_bounds__(256) void k_wm_seed(WmPair pr, int HW, int nb) { wm_seed(pr.s[blockIdx.y], HW, nb); }
-// ... of the pairs of a batch: the pair on blockIdx.z, its record from the device table (psm_post_process_batch)
-__global__ __launch_bounds__(256) void k_wm_seed_b(const PpPair *__restrict__ tab, int HW, int nb) { wm_seed(tab[blockIdx.z].wm.s[blockIdx.y], HW, nb); }
+// Every kernel of the sweep form is one body (wm_*) behind one entry k_wm_*<S> that has the side on blockIdx.y and the pair on
+// blockIdx.z and is templated over where the pair's record comes from (psm_kernels.h, PpRecs) - S = PpVal: the one pair of a call
+// by value in the kernarg; S = PpTab: the device table of a call of several.
+template <typename S> __device__ __forceinline__ const WmSide &wm_side(const S &src) { return pp_rec(src).wm.s[blockIdx.y]; }
+template <typename S> __global__ __launch_bounds__(256) void k_wm_seed(S src, int HW, int nb) { wm_seed(wm_side(src), HW, nb); }
 
 // One evaluation of f per LANE (round 3; round 2 spent a whole wave per pixel: every lane scanned all 361 taps for "its"
 // bins - 361 x 64 lane-steps for 722 useful additions).  A lane walks the 361 taps of its own pixel in window raster order:
@@ -379,16 +381,11 @@ __device__ __forceinline__ void wm_weights(const float4 *__restrict__ g1, const 
         for (int k = 0; k < WM_WROW / 4; ++k) wts[wm_widx(slot, r, k)] = make_float4(wk[4 * k], wk[4 * k + 1], wk[4 * k + 2], wk[4 * k + 3]);
     }
 }
-template <bool RIGHT>
-__global__ __launch_bounds__(256) void k_wm_weights(const float4 *__restrict__ g1, const int *__restrict__ inv, const int *n_inv,
-                                                   float4 *__restrict__ wts, int *__restrict__ slot_of, int W, int H)
+// ... of every side of a cached call in one launch; a side without invalid pixels returns at once
+template <typename S>
+__global__ __launch_bounds__(256) void k_wm_weights(S src, int W, int H)
 {
-    wm_weights<RIGHT>(g1, inv, n_inv, wts, slot_of, W, H);
-}
-// ... of every side of a batch that has a cache (blockIdx.y: the side, blockIdx.z: the pair); a side without invalid pixels returns at once
-__global__ __launch_bounds__(256) void k_wm_weights_b(const PpPair *__restrict__ tab, int W, int H)
-{
-    const WmSide &a = tab[blockIdx.z].wm.s[blockIdx.y];
+    const WmSide &a = wm_side(src);
     if (blockIdx.y == 0) wm_weights<false>(a.g1, a.inv, a.cnt, (float4 *)a.wts, a.slot_of, W, H);
     else wm_weights<true>(a.g1, a.inv, a.cnt, (float4 *)a.wts, a.slot_of, W, H);
 }
@@ -586,17 +583,11 @@ __device__ __forceinline__ void wm_eval_side(float *hist, const WmSide &a, int s
         wm_eval_lanes<true, CACHED>(hist, a.cur, a.orig, a.g1, act, a.cnt + 2 * sw, a.newv, a.chg, a.cnt + 2 * sw + 1, W, H, maxDis, (const float4 *)a.wts, a.slot_of,
                                     a.cur, a.chgb, a.rowany, sw + 1);
 }
-template <bool CACHED>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_wm_eval(WmPair pr, int sw, int W, int H, int maxDis)
+template <bool CACHED, typename S>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_wm_eval(S src, int sw, int W, int H, int maxDis)
 {
     extern __shared__ float hist[];
-    wm_eval_side<CACHED>(hist, pr.s[blockIdx.y], sw, W, H, maxDis);
-}
-template <bool CACHED>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_wm_eval_b(const PpPair *__restrict__ tab, int sw, int W, int H, int maxDis)
-{
-    extern __shared__ float hist[];
-    wm_eval_side<CACHED>(hist, tab[blockIdx.z].wm.s[blockIdx.y], sw, W, H, maxDis);
+    wm_eval_side<CACHED>(hist, wm_side(src), sw, W, H, maxDis);
 }
 
 // Short active lists (the tail sweeps: a few hundred pixels whose evaluation latency is what the sweep costs): one WAVE per
@@ -766,15 +757,10 @@ __device__ __forceinline__ void wm_eval_w_side(const WmSide &a, int sw, int W, i
         wm_eval_wave<true, NB, CACHED>(a.cur, a.orig, a.g1, act, a.cnt + 2 * sw, a.newv, a.chg, a.cnt + 2 * sw + 1, W, H, maxDis, a.wts, a.slot_of, force, blockIdx.x, gridDim.x,
                                        curw, a.valid, a.stamp, sw + 1, a.list[sw & 1], a.cnt + 2 * (sw + 1));
 }
-template <int NB, bool CACHED>
-__global__ __launch_bounds__(64) void k_wm_eval_w(WmPair pr, int sw, int W, int H, int maxDis, int force)
+template <int NB, bool CACHED, typename S>
+__global__ __launch_bounds__(64) void k_wm_eval_w(S src, int sw, int W, int H, int maxDis, int force)
 {
-    wm_eval_w_side<NB, CACHED>(pr.s[blockIdx.y], sw, W, H, maxDis, force);
-}
-template <int NB, bool CACHED>
-__global__ __launch_bounds__(64) void k_wm_eval_w_b(const PpPair *__restrict__ tab, int sw, int W, int H, int maxDis, int force)
-{
-    wm_eval_w_side<NB, CACHED>(tab[blockIdx.z].wm.s[blockIdx.y], sw, W, H, maxDis, force);
+    wm_eval_w_side<NB, CACHED>(wm_side(src), sw, W, H, maxDis, force);
 }
 
 // Which pixels does the next sweep evaluate?  Every invalid pixel that has a pixel changed by this sweep among the EARLIER taps
@@ -814,8 +800,7 @@ __device__ __forceinline__ void wm_gather(const WmSide &a, int sw, int W, int H)
         if (want) next[slot] = pix;
     }
 }
-__global__ __launch_bounds__(256) void k_wm_gather(WmPair pr, int sw, int W, int H) { wm_gather(pr.s[blockIdx.y], sw, W, H); }
-__global__ __launch_bounds__(256) void k_wm_gather_b(const PpPair *__restrict__ tab, int sw, int W, int H) { wm_gather(tab[blockIdx.z].wm.s[blockIdx.y], sw, W, H); }
+template <typename S> __global__ __launch_bounds__(256) void k_wm_gather(S src, int sw, int W, int H) { wm_gather(wm_side(src), sw, W, H); }
 
 // the changed pixels take their new value; every invalid pixel LATER in raster order that has one of them in its window
 // is evaluated again in the next sweep (stamp: once)
@@ -866,11 +851,7 @@ __device__ __forceinline__ void wm_apply_side(const WmSide &a, int sw, int W, in
     wm_apply(a.cur, a.newv, a.valid, a.chg, a.cnt + 2 * sw + 1, a.cnt, a.stamp, sw + 1, a.list[sw & 1], a.cnt + 2 * (sw + 1), W, H, a.chgb, a.rowany, force,
              blockIdx.x, gridDim.x, a.cnt + 2 * sw);
 }
-__global__ __launch_bounds__(64) void k_wm_apply(WmPair pr, int sw, int W, int H, int force) { wm_apply_side(pr.s[blockIdx.y], sw, W, H, force); }
-__global__ __launch_bounds__(64) void k_wm_apply_b(const PpPair *__restrict__ tab, int sw, int W, int H, int force)
-{
-    wm_apply_side(tab[blockIdx.z].wm.s[blockIdx.y], sw, W, H, force);
-}
+template <typename S> __global__ __launch_bounds__(64) void k_wm_apply(S src, int sw, int W, int H, int force) { wm_apply_side(wm_side(src), sw, W, H, force); }
 
 // f(std::integral_constant<int, NB>) for nb = ceil(maxDis / 64) histogram bins per lane: the instantiations are NB 1..4 (D <= 256)
 template <class F>
@@ -882,52 +863,8 @@ static void wm_with_nb(int nb, F f)
     else f(std::integral_constant<int, 4>{});
 }
 
-// the 19 x 19 weights of the n_inv invalid pixels of `inv` (n = an upper bound of *n_inv, for the grid) -> wts, slot_of
-void launch_wm_weights(hipStream_t s, const float4 *g1, int W, int H, int right, const int *inv, const int *n_inv, int n, float *wts, int *slot_of)
-{
-    const long long threads = (long long)((n + 63) / 64) * WM_K * 64;
-    const int blocks = (int)((threads + 255) / 256 < 65536 ? (threads + 255) / 256 : 65536);
-    if (right) hipLaunchKernelGGL(k_wm_weights<true>, dim3(blocks), dim3(256), 0, s, g1, inv, n_inv, (float4 *)wts, slot_of, W, H);
-    else hipLaunchKernelGGL(k_wm_weights<false>, dim3(blocks), dim3(256), 0, s, g1, inv, n_inv, (float4 *)wts, slot_of, W, H);
-}
-
-void launch_wm_seed(hipStream_t s, const WmPair &p, int W, int H)
-{   // (the counters of both maps are zero: the caller's memset)
-    const int HW = W * H, per_block = 256 * WM_SEED_PER;
-    hipLaunchKernelGGL(k_wm_seed, dim3((HW + per_block - 1) / per_block, 2), dim3(256), 0, s, p, HW, (HW + 255) / 256 * 256);
-}
-
-// sweep `sw` of both maps: evaluate the active lists -> changed pixels -> applied, dependents -> the next lists (WmSide)
-void launch_wm_sweep(hipStream_t s, const WmPair &p, int W, int H, int maxDis, int sw, bool cached, bool tail)
-{   // tail: the host has seen short lists going into this sweep on both maps - only the one-wave-per-pixel evaluation is launched
-    // (made to take whatever the lists turn out to be), and it applies its changes and queues their dependents itself: one launch
-    // instead of four.  cached: both maps have their weight cache (launch_wm_weights).
-    const dim3 ga(2048, 2);
-    // two waves per CU at D = 256 (64 KB of LDS each), up to ten at D <= 64; the grid strides over batches of 64 pixels
-    const size_t lds = (size_t)maxDis * 64 * sizeof(float);
-    const PcDev dev = pc_dev();
-    const int per_cu = (int)(160 * 1024 / (lds > 16384 ? lds : 16384));
-    const dim3 ge(dev.nxcd * dev.cus_per_xcd * (per_cu < 1 ? 1 : per_cu), 2);
-    const int force = tail ? 1 : 0;
-    if (!tail) {
-        if (cached) hipLaunchKernelGGL(k_wm_eval<true>, ge, dim3(64), lds, s, p, sw, W, H, maxDis);
-        else hipLaunchKernelGGL(k_wm_eval<false>, ge, dim3(64), lds, s, p, sw, W, H, maxDis);
-    }
-    // ... and the one-wave-per-pixel form for short lists (either kernel returns at once when a list is not its size)
-    const int nb = (maxDis + 63) / 64;
-    const dim3 gw(8192, 2);
-    wm_with_nb(nb, [&](auto nbv) {
-        constexpr int NB = decltype(nbv)::value;
-        if (cached) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wm_eval_w<NB, true>), gw, dim3(64), 0, s, p, sw, W, H, maxDis, force);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wm_eval_w<NB, false>), gw, dim3(64), 0, s, p, sw, W, H, maxDis, force);
-    });
-    if (tail) return;               // (the forced wave form applied its changes and queued their dependents itself)
-    hipLaunchKernelGGL(k_wm_apply, ga, dim3(64), 0, s, p, sw, W, H, force);
-    hipLaunchKernelGGL(k_wm_gather, dim3(2048, 2), dim3(256), 0, s, p, sw, W, H);
-}
-
-// ---- The same launches for the n pairs of a device table (psm_post_process_batch).  No map depends on a grid's shape: every
-// kernel strides over its lists with gridDim.x.  A pair's share of grid.x shrinks as n grows, so that a launch stays at about what a
+// ---- The launches of the sweep form for the q.n pairs of a call (q.n on grid.z).  No map depends on a grid's shape: every kernel
+// strides over its lists with gridDim.x.  A pair's share of grid.x shrinks as n grows, so that a launch stays at about what a
 // single pair's launch puts on the chip (the evaluations: resident workgroups; the wave form, apply and gather: their fixed grids)
 // and never falls below an eighth of it per pair - the floor keeps a long list beside empty ones from crawling.
 static int wm_share(int single, int n)
@@ -937,42 +874,48 @@ static int wm_share(int single, int n)
     return x > floor_ ? x : floor_;
 }
 
-void launch_wm_seed_b(hipStream_t s, const PpPair *tab, int n, int W, int H)
-{
+void launch_wm_seed(hipStream_t s, const PpRecs &q, int W, int H)
+{   // (the counters of all maps are zero: the caller's memset)
     const int HW = W * H, per_block = 256 * WM_SEED_PER;
-    hipLaunchKernelGGL(k_wm_seed_b, dim3((HW + per_block - 1) / per_block, 2, n), dim3(256), 0, s, tab, HW, (HW + 255) / 256 * 256);
+    pp_launch(s, k_wm_seed<PpVal>, k_wm_seed<PpTab>, dim3((HW + per_block - 1) / per_block, 2, q.n), dim3(256), 0, q, HW, (HW + 255) / 256 * 256);
 }
 
-// n_max: an upper bound of the invalid pixels of any side
-void launch_wm_weights_b(hipStream_t s, const PpPair *tab, int n, int W, int H, int n_max)
+// the 19 x 19 weights of the invalid pixels of every side -> its wts, slot_of; n_max: an upper bound of the invalid pixels of any side (for the grid)
+void launch_wm_weights(hipStream_t s, const PpRecs &q, int W, int H, int n_max)
 {
     const long long threads = (long long)((n_max + 63) / 64) * WM_K * 64;
     const long long want = (threads + 255) / 256;
-    const int cap = wm_share(65536, n);
-    hipLaunchKernelGGL(k_wm_weights_b, dim3((unsigned)(want < cap ? (want > 0 ? want : 1) : cap), 2, n), dim3(256), 0, s, tab, W, H);
+    const int cap = wm_share(65536, q.n);
+    pp_launch(s, k_wm_weights<PpVal>, k_wm_weights<PpTab>, dim3((unsigned)(want < cap ? (want > 0 ? want : 1) : cap), 2, q.n), dim3(256), 0, q, W, H);
 }
 
-void launch_wm_sweep_b(hipStream_t s, const PpPair *tab, int n, int W, int H, int maxDis, int sw, bool cached, bool tail)
-{
+// sweep `sw` of every map: evaluate the active lists -> changed pixels -> applied, dependents -> the next lists (WmSide)
+void launch_wm_sweep(hipStream_t s, const PpRecs &q, int W, int H, int maxDis, int sw, bool cached, bool tail)
+{   // tail: the host has seen short lists going into this sweep on every map - only the one-wave-per-pixel evaluation is launched
+    // (made to take whatever the lists turn out to be), and it applies its changes and queues their dependents itself: one launch
+    // instead of four.  cached: every map has its weight cache (launch_wm_weights).
+    const int n = q.n;
+    // two waves per CU at D = 256 (64 KB of LDS each), up to ten at D <= 64; the grid strides over batches of 64 pixels
     const size_t lds = (size_t)maxDis * 64 * sizeof(float);
     const PcDev dev = pc_dev();
     const int per_cu = (int)(160 * 1024 / (lds > 16384 ? lds : 16384));
     const dim3 ge(wm_share(dev.nxcd * dev.cus_per_xcd * (per_cu < 1 ? 1 : per_cu), n), 2, n);
     const int force = tail ? 1 : 0;
     if (!tail) {
-        if (cached) hipLaunchKernelGGL(k_wm_eval_b<true>, ge, dim3(64), lds, s, tab, sw, W, H, maxDis);
-        else hipLaunchKernelGGL(k_wm_eval_b<false>, ge, dim3(64), lds, s, tab, sw, W, H, maxDis);
+        if (cached) pp_launch(s, k_wm_eval<true, PpVal>, k_wm_eval<true, PpTab>, ge, dim3(64), lds, q, sw, W, H, maxDis);
+        else pp_launch(s, k_wm_eval<false, PpVal>, k_wm_eval<false, PpTab>, ge, dim3(64), lds, q, sw, W, H, maxDis);
     }
+    // ... and the one-wave-per-pixel form for short lists (either kernel returns at once when a list is not its size)
     const int nb = (maxDis + 63) / 64;
     const dim3 gw(wm_share(8192, n), 2, n);
     wm_with_nb(nb, [&](auto nbv) {
         constexpr int NB = decltype(nbv)::value;
-        if (cached) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wm_eval_w_b<NB, true>), gw, dim3(64), 0, s, tab, sw, W, H, maxDis, force);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wm_eval_w_b<NB, false>), gw, dim3(64), 0, s, tab, sw, W, H, maxDis, force);
+        if (cached) pp_launch(s, k_wm_eval_w<NB, true, PpVal>, k_wm_eval_w<NB, true, PpTab>, gw, dim3(64), 0, q, sw, W, H, maxDis, force);
+        else pp_launch(s, k_wm_eval_w<NB, false, PpVal>, k_wm_eval_w<NB, false, PpTab>, gw, dim3(64), 0, q, sw, W, H, maxDis, force);
     });
-    if (tail) return;
-    hipLaunchKernelGGL(k_wm_apply_b, dim3(wm_share(2048, n), 2, n), dim3(64), 0, s, tab, sw, W, H, force);
-    hipLaunchKernelGGL(k_wm_gather_b, dim3(wm_share(2048, n), 2, n), dim3(256), 0, s, tab, sw, W, H);
+    if (tail) return;               // (the forced wave form applied its changes and queued their dependents itself)
+    pp_launch(s, k_wm_apply<PpVal>, k_wm_apply<PpTab>, dim3(wm_share(2048, n), 2, n), dim3(64), 0, q, sw, W, H, force);
+    pp_launch(s, k_wm_gather<PpVal>, k_wm_gather<PpTab>, dim3(wm_share(2048, n), 2, n), dim3(256), 0, q, sw, W, H);
 }
 
 void launch_wgt_median(hipStream_t s, uint8_t *dis, const uint8_t *valid, const float4 *g1, int W, int H, int maxDis, int right,

@@ -1,7 +1,8 @@
-// psm_wm_sched.h - what the host driver of the plain weighted median (psm_wgt_median, psm_api_pp.cpp) decides
-// without the device: where the parts of the sweep block lie, what the per-sweep counters mean, how many sweeps the next group
-// holds and in which form, when a map is finished, and whether the call gets a weight cache.  Nothing of HIP in here: it compiles
-// with the host compiler alone (tests/test_wm_sched.py plays the device to it through tests/wm_sched_probe.cpp).
+// psm_wm_sched.h - what the host driver of the plain weighted median (pp_enqueue, psm_api_pp.cpp) decides without
+// the device, for the maps of one pair or of several: where the parts of a context's sweep block lie, what the per-sweep counters
+// mean, how many sweeps the next group holds and in which form, when a map is finished, and whether the call gets a weight cache.
+// Nothing of HIP in here: it compiles with the host compiler alone (tests/test_wm_sched.py and tests/test_wm_batch_sched.py play
+// the device to it through tests/wm_sched_probe.cpp).
 #pragma once
 #include "../../include/primesm_hip.h"
 
@@ -22,122 +23,52 @@ constexpr int WM_NCNT = 2 * (WM_SWEEP_CAP + 2);   // counters per map
 inline int wm_active(const int *cnt, int k) { return cnt[2 * k]; }
 inline int wm_changed(const int *cnt, int k) { return cnt[2 * k + 1]; }
 inline int wm_next(const int *cnt, int k) { return cnt[2 * k + 2]; }
-// ... of map s in a snapshot of the counter block (both maps, one behind the other)
+// ... of map s in a snapshot of the counter block (all maps of the call, one behind the other)
 inline const int *wm_counters(const int *snap, int s) { return snap + s * WM_NCNT; }
 
-// ---- The sweep block: byte offsets from its base.  Per side orig, newv, chgb, rowany (nb bytes each), then stamp, the two active
-// lists, the changed list, slot_of and the list of all invalid pixels (nb ints each), nb = W H rounded up to 256; the counters
-// of both maps follow the two sides (one fill, one snapshot).
-struct WmSideAt { size_t orig, newv, chgb, rowany, stamp, list[2], chg, slot_of, inv, cnt; };
+// ---- The sweep block of a context: byte offsets from its base.  Per side orig, newv, chgb, rowany (nb bytes each), then stamp, the two
+// active lists, the changed list, slot_of and the list of all invalid pixels (nb ints each), nb = W H rounded up to 256.  (The
+// counters are not in it: those of all maps of a call lie in one block of the call's first context, psm::WmBatch.)
+struct WmSideAt { size_t orig, newv, chgb, rowany, stamp, list[2], chg, slot_of, inv; };
 struct WmLayout {
     WmSideAt s[2];
-    size_t cnt;            // the counter block: WM_NCNT ints per map
     size_t bytes;          // to allocate
-    size_t snap;           // ints per counter snapshot (both maps)
 };
 inline WmLayout wm_layout(size_t HW)
 {
     const size_t nb = (HW + 255) / 256 * 256, per_side = 4 * nb + 6 * nb * sizeof(int);
     WmLayout l;
-    l.cnt = 2 * per_side;
-    l.snap = 2 * (size_t)WM_NCNT;
-    l.bytes = l.cnt + l.snap * sizeof(int);
+    l.bytes = 2 * per_side;
     for (int s = 0; s < 2; ++s) {
         const size_t b = s * per_side, ip = b + 4 * nb;
         auto ints = [&](int i) { return ip + i * nb * sizeof(int); };
-        l.s[s] = WmSideAt{b, b + nb, b + 2 * nb, b + 3 * nb, ints(0), {ints(1), ints(2)}, ints(3), ints(4), ints(5),
-                          l.cnt + s * WM_NCNT * sizeof(int)};
+        l.s[s] = WmSideAt{b, b + nb, b + 2 * nb, b + 3 * nb, ints(0), {ints(1), ints(2)}, ints(3), ints(4), ints(5)};
     }
     return l;
 }
 
-// ---- The schedule.  Sweeps are launched in groups; the host looks at a group's counters (did a sweep change nothing? how long
-// is the next list?) while the NEXT group is already queued - the device never idles behind a host round trip (~65 us of idle
-// per check, 0.7 ms of the 4.0 on the 1080p bench pair).  A group launched for a map that had already reached its fixed point is
-// a handful of launches over empty lists.  The driver's loop:
+// ---- The schedule of the m = 2 n maps of a call (n = 1: a single pair), map 2 i + s being side s of pair i; their counters lie one
+// behind the other in one block (wm_counters(snap, map)), so one snapshot shows them all.  Sweeps are launched in groups; the host
+// looks at a group's counters (did a sweep change nothing? how long is the next list?) while the NEXT group is already queued - the
+// device never idles behind a host round trip (~65 us of idle per check, 0.7 ms of the 4.0 on the 1080p bench pair).  A group
+// launched for a map that had already reached its fixed point is a handful of launches over empty lists.  A launch takes every
+// map one way: a group is of the one-launch wave form only when EVERY map is tail or done, and the loop ends when every map is
+// done or the cap is reached.  The driver's loop:
 //     launched(next_group(), 0);
 //     for (g = 0;; ++g) { if (more()) launched(next_group(), (g + 1) & 1);  if (!read(g & 1, snapshot of slot g & 1)) break; }
 struct WmGroup { int begin, end; bool short_lists; };      // sweeps [begin, end); short_lists: the one-launch wave form
 struct WmSched {
     int cap;                            // WM_SWEEP_CAP; 2 under PSM_FLAG_WMF_TWO_SWEEPS (test hook for the fall-back)
+    int m;                              // maps
     int sw = 0;                         // sweeps launched
     int unread = 0;                     // groups launched whose snapshot has not been read
-    bool done[2] = {false, false};      // the map has reached its fixed point
-    bool tail[2] = {false, false};      // the list going into the next sweep is short: one launch per sweep, more sweeps per check
     int upto[2] = {0, 0};               // sweeps covered by the snapshot in a slot
-    int sweeps[2] = {-1, -1};           // what psm_wgt_median_stats reports; as initialised: a map left to the dataflow form
-    long long evals[2] = {0, 0};
-
-    explicit WmSched(unsigned flags) : cap((flags & PSM_FLAG_WMF_TWO_SWEEPS) ? 2 : WM_SWEEP_CAP) {}
-    bool more() const { return sw < cap; }
-    // two sweeps per group while the lists are long (the host learns two groups late that they have become short, and a sweep
-    // launched the long way costs three launches more than it needs then), eight once they are short
-    WmGroup next_group() const
-    {
-        const bool short_lists = (tail[0] || done[0]) && (tail[1] || done[1]);
-        const int chk = short_lists ? 8 : 2;
-        return WmGroup{sw, sw + chk < cap ? sw + chk : cap, short_lists};
-    }
-    void launched(const WmGroup &g, int slot) { sw = g.end; upto[slot] = sw; ++unread; }
-    // the snapshot taken behind the group of `slot` has arrived: false when both maps are finished or nothing more is queued
-    bool read(int slot, const int *snap)
-    {
-        const int seen = upto[slot];
-        for (int s = 0; s < 2; ++s) {
-            if (done[s]) continue;
-            const int *cnt = wm_counters(snap, s);
-            long long ev = 0;
-            for (int k = 0; k < seen; ++k) {
-                ev += wm_active(cnt, k);
-                if (wm_changed(cnt, k) == 0) {      // sweep k changed nothing: fixed point
-                    done[s] = true;
-                    sweeps[s] = k + 1;
-                    evals[s] = ev;
-                    break;
-                }
-            }
-            tail[s] = seen < cap && wm_next(cnt, seen - 1) < WM_LANE_MIN;   // (what the group's last sweep left for the next one: wave form)
-        }
-        return --unread > 0 && !(done[0] && done[1]);
-    }
-};
-
-// ---- The weight cache: the 19 x 19 weights of an invalid pixel depend on the image only, and the sweeps evaluate it ~5 times.  For
-// sides with at least WM_LANE_MIN invalid pixels one pass forms them all (1.5 KB per invalid pixel); short lists form their weights
-// themselves, and a launch takes both maps one way.  n0: the invalid pixels of the two maps; avail: the bytes the device has free
-// plus what the context's cache holds already (SIZE_MAX: unknown).  At most 12 GB, and never more than half of avail: the volumes,
-// the spare volume and the FGF scratch of this or another context on the device are allocated on first use and must still fit.
-struct WmCachePlan {
-    size_t floats;         // of both sides; 0: no cache
-    size_t right;          // where the right side's weights begin (whole blocks of 64 pixels: the cache is laid out in such blocks)
-};
-inline WmCachePlan wm_cache_plan(const int n0[2], size_t avail, unsigned flags)
-{
-    size_t max_bytes = (size_t)12 << 30;
-    if (avail / 2 < max_bytes) max_bytes = avail / 2;
-    size_t need[2];
-    for (int s = 0; s < 2; ++s) need[s] = (size_t)((n0[s] + 63) / 64 * 64) * WM_WPIX;
-    const size_t tot = need[0] + need[1];
-    const bool none = (n0[0] < WM_LANE_MIN && n0[1] < WM_LANE_MIN) || tot * sizeof(float) > max_bytes || (flags & PSM_FLAG_WMF_NO_CACHE);
-    return WmCachePlan{none ? 0 : tot, need[0]};
-}
-
-// ---- The maps of several pairs in shared launches (psm_post_process_batch, psm_api_pp_batch.cpp): m = 2 n maps, map 2 i + s being
-// side s of pair i; their counters lie one behind the other in one block (wm_counters(snap, map)), so one snapshot shows them all.
-// The rules per map are WmSched's - done, tail, the fixed point at the first sweep that changed nothing, sweeps and evals - and a
-// launch takes every map one way: a group is of the one-launch wave form only when EVERY map is tail or done, and the loop ends
-// when every map is done or the cap is reached.  With m = 2 it decides what WmSched decides, group for group
-// (tests/test_wm_batch_sched.py).  The driver's loop is WmSched's.
-struct WmBatchSched {
-    int cap;
-    int m;                              // maps
-    int sw = 0, unread = 0;
-    int upto[2] = {0, 0};
-    std::vector<char> done, tail;
-    std::vector<int> sweeps;            // -1: a map left to the dataflow form
+    std::vector<char> done;             // the map has reached its fixed point
+    std::vector<char> tail;             // the list going into the next sweep is short: one launch per sweep, more sweeps per check
+    std::vector<int> sweeps;            // what psm_wgt_median_stats reports; as initialised (-1): a map left to the dataflow form
     std::vector<long long> evals;
 
-    WmBatchSched(int maps, unsigned flags)
+    WmSched(int maps, unsigned flags)
         : cap((flags & PSM_FLAG_WMF_TWO_SWEEPS) ? 2 : WM_SWEEP_CAP), m(maps), done(maps, 0), tail(maps, 0), sweeps(maps, -1), evals(maps, 0) {}
     bool more() const { return sw < cap; }
     bool all_done() const
@@ -146,6 +77,8 @@ struct WmBatchSched {
             if (!done[i]) return false;
         return true;
     }
+    // two sweeps per group while the lists are long (the host learns two groups late that they have become short, and a sweep
+    // launched the long way costs three launches more than it needs then), eight once they are short
     WmGroup next_group() const
     {
         bool short_lists = true;
@@ -164,25 +97,30 @@ struct WmBatchSched {
             long long ev = 0;
             for (int k = 0; k < seen; ++k) {
                 ev += wm_active(cnt, k);
-                if (wm_changed(cnt, k) == 0) {
+                if (wm_changed(cnt, k) == 0) {      // sweep k changed nothing: fixed point
                     done[i] = 1;
                     sweeps[i] = k + 1;
                     evals[i] = ev;
                     break;
                 }
             }
-            tail[i] = seen < cap && wm_next(cnt, seen - 1) < WM_LANE_MIN;
+            tail[i] = seen < cap && wm_next(cnt, seen - 1) < WM_LANE_MIN;   // (what the group's last sweep left for the next one: wave form)
         }
         return --unread > 0 && !all_done();
     }
 };
 
-// The cache decision of a batch is one for all its maps, since a launch takes every map one way: cached only if at least one of the
-// m sides has WM_LANE_MIN invalid pixels, the sum of all sides' needs stays within wm_cache_plan's bound and no flag forbids it -
-// then EVERY side gets its weights (need[i] floats: whole blocks of 64 pixels; a context's two sides lie one behind the other in its
-// own buffer).  The maps are the same either way.  Returns the floats of all sides, 0: no cache.
+// ---- The weight cache: the 19 x 19 weights of an invalid pixel depend on the image only, and the sweeps evaluate it ~5 times.  One
+// pass forms them all (1.5 KB per invalid pixel: wm_side_need floats per side, whole blocks of 64 pixels - the cache is laid out in
+// such blocks); short lists form their weights themselves.  The decision is one for all m maps of a call, since a launch takes
+// every map one way: cached only if at least one side has WM_LANE_MIN invalid pixels, the sum of all sides' needs stays within the
+// bound and no flag forbids it - then EVERY side gets its weights, a context's two sides one behind the other in its own buffer
+// (the right side's begin wm_side_need(n0[left]) floats into it).  n0: the invalid pixels of the m maps; avail: the bytes the device
+// has free plus what the contexts' caches hold already (SIZE_MAX: unknown).  At most 12 GB, and never more than half of avail: the
+// volumes, the spare volume and the FGF scratch of this or another context on the device are allocated on first use and must still
+// fit.  The maps are the same either way.  Returns the floats of all sides, 0: no cache.
 inline size_t wm_side_need(int n0) { return (size_t)((n0 + 63) / 64 * 64) * WM_WPIX; }
-inline size_t wm_batch_cache_plan(const int *n0, int m, size_t avail, unsigned flags)
+inline size_t wm_cache_plan(const int *n0, int m, size_t avail, unsigned flags)
 {
     size_t max_bytes = (size_t)12 << 30;
     if (avail / 2 < max_bytes) max_bytes = avail / 2;

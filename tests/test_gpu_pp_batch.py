@@ -1,7 +1,8 @@
 """-m gpu: PP::processDM's own sequence - lrCheck, fillInv, wgtMedian - of several contexts in shared launches
 (psm_post_process_batch, dispest.post_process_batch) against oracle.lr_check / fill_inv / wgt_median AND against the single calls on
 fresh contexts.  Every comparison is np.array_equal on all pixels of all members - maps and masks - without a tolerance.  Sweep and
-evaluation counts may differ from run to run: only their sanity is asserted (-1 or 1 .. 96; the dataflow form reports -1).
+evaluation counts may differ from run to run: only their sanity is asserted (-1 or 1 .. 96; the dataflow form reports -1) - but for
+a batch of one, which is the single calls' launch sequence and schedule and must report their sweeps.
 Inputs: tests/wmf_inputs.py.
 
 One case cannot be built as written: histogram word seams "D in {2, 64, 65, 129, 256} at 21 x 20" - a context takes no max_disp
@@ -113,9 +114,9 @@ def _same(got, want, what):
         assert np.array_equal(g, w), f"{what}: {name}: {int((g != w).sum())} pixels differ"
 
 
-def _batch(psm, expected, inps, D, stages, flags=0, label="", des=None, dataflow=False):
+def _batch(psm, expected, inps, D, stages, flags=0, label="", des=None, dataflow=False, equal_sweeps=False):
     """One psm_post_process_batch of `stages` on fresh contexts of the inputs (or on `des`): every member's maps and masks equal the
-    oracle's and the single calls'.  -> the sweeps per member."""
+    oracle's and the single calls'.  equal_sweeps: the sweeps the single calls report are the member's.  -> the sweeps per member."""
     from primestereomatch_amd import dispest
     own = des is None
     if own:
@@ -133,6 +134,9 @@ def _batch(psm, expected, inps, D, stages, flags=0, label="", des=None, dataflow
             if stages & MED:
                 _sane(sw, dataflow)
                 _sane(single_sweeps, dataflow)
+                if equal_sweeps:
+                    print(f"[pp-batch] {label} member {i}: sweeps {sw}, the single calls' {single_sweeps}")
+                    assert sw == single_sweeps, (label, i, sw, single_sweeps)
             sweeps.append(sw)
         print(f"[pp-batch] {label}: n = {len(des)}, stages {stages}, sweeps {sweeps}")
         return sweeps
@@ -148,6 +152,80 @@ def test_batch_sizes(psm, expected, n):
     inps = [G.random_case(64, 65, 64, G.FRACS[i % 3], 700 + i) for i in range(n)]
     _batch(psm, expected, inps, 64, ALL, label=f"sizes n={n}")
     _batch(psm, expected, inps, 64, MED, label=f"sizes n={n} (the masks of the inputs)")
+
+
+# ------------------------------------------------------------------------------------------ a batch of one (the record by value)
+
+@pytest.mark.parametrize("form", ["sweeps", "no_cache", "fallback", "dataflow"])
+def test_a_batch_of_one_in_every_form(psm, expected, form):
+    """n = 1 takes the single calls' path through the batch's entry - the record in the kernarg, no device table - in each form of
+    the median; its sweeps are the single calls', which follow the same schedule."""
+    inp = G.random_case(64, 65, 64, 1.0, 1300)
+    for stages in (ALL, MED):
+        sweeps = _batch(psm, expected, [inp], 64, stages, G.FORMS[form], label=f"one, {form}, stages {stages}", dataflow=form == "dataflow",
+                        equal_sweeps=True)
+        if form == "fallback":
+            assert sweeps == [[-1, -1]]                        # (all pixels invalid: no fixed point in two sweeps, both maps fall back)
+
+
+@pytest.mark.parametrize("counts", [(8192, 0), (0, 8192)])
+def test_a_batch_of_one_at_the_cache_threshold_beside_an_empty_side(psm, expected, counts):
+    """8192 invalid pixels on one side - the cache's threshold and the first list of the lane form - and none on the other, which
+    the one weights launch over both sides must skip."""
+    H, W, D = G.COUNTED_GEO
+    inp = G.counted_invalid(H, W, D, 11, counts[0], counts[1], map_seed=140)
+    for form in ("sweeps", "no_cache"):
+        sweeps = _batch(psm, expected, [inp], D, MED, G.FORMS[form], label=f"one, {counts}, {form}", equal_sweeps=True)
+        assert sweeps[0][counts.index(0)] == 1                 # (an empty list: its first sweep changes nothing)
+    _batch(psm, expected, [inp], D, FILL | MED, label=f"one, {counts}, fill + median", equal_sweeps=True)
+
+
+@pytest.mark.parametrize("W,H,D", [(9, 9, 9), (64, 9, 64), (65, 9, 65)])
+def test_a_batch_of_one_at_the_smallest_geometry_and_the_word_seam(psm, expected, W, H, D):
+    """The smallest image the median accepts, 9 x 9, and the 64-bin word seam of the wave form's histogram, D = 64 and 65.  9 x 9
+    with D = 64 cannot be built as written - a context takes no max_disp above its width (psm_create) - so 9 x 9 runs with D = 9 and
+    the seam on 9 rows of D columns."""
+    inp = G.random_case(W, H, D, 0.5, 1400 + D)
+    _batch(psm, expected, [inp], D, ALL, label=f"one, {W}x{H} D={D}", equal_sweeps=True)
+    _batch(psm, expected, [inp], D, MED, label=f"one, {W}x{H} D={D} (the masks of the input)", equal_sweeps=True)
+
+
+def test_the_counters_home_through_changing_roles(psm, expected):
+    """The counters, their snapshots and the events of every call lie with the call's first context.  One context runs the single
+    calls, heads a batch of three (which grows the block), runs the single calls again on fresh maps, gives its scratch back and runs
+    them once more, and is then a member of a batch another context heads - every step against the oracle.  (A batch of three takes
+    three contexts: the one followed here and two beside it.)"""
+    W, H, D = 64, 65, 64
+    inps = [G.random_case(W, H, D, G.FRACS[(i + 1) % 3], 1500 + i) for i in range(3)]
+    fresh = [G.random_case(W, H, D, G.FRACS[i % 3], 1600 + i) for i in range(3)]
+    des = [_context(psm, inp, D, masks=False) for inp in inps]
+    a = des[0]
+
+    def singles(inp, what):
+        a.upload_maps(inp.lmap, inp.rmap)
+        a.LRCheck_device()
+        a.FillInv_GPU()
+        a.WgtMedian_GPU()
+        _same(_results(a), expected(G.WmInput(inps[0].img, inp.lmap, inp.rmap, inp.lvalid, inp.rvalid, inp.pixels), D, ALL), what)
+        _sane(a.wgt_median_stats()[0])
+
+    def batch(order, maps, what):
+        members = []
+        for k in order:
+            des[k].upload_maps(maps[k].lmap, maps[k].rmap)
+            members.append(G.WmInput(inps[k].img, maps[k].lmap, maps[k].rmap, maps[k].lvalid, maps[k].rvalid, maps[k].pixels))
+        _batch(psm, expected, members, D, ALL, label=what, des=[des[k] for k in order])
+
+    try:
+        singles(inps[0], "the single calls on a new context")
+        batch([0, 1, 2], inps, "heading a batch of three")
+        singles(fresh[0], "the single calls after heading a batch")
+        a.release_scratch()
+        singles(fresh[1], "the single calls after psm_release_scratch")
+        batch([1, 0], fresh, "a member of another context's batch")
+        batch([0], inps, "a batch of one after all of them")
+    finally:
+        _close(des)
 
 
 # ------------------------------------------------------------------------------------------ mixed forms in one launch

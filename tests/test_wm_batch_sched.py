@@ -1,8 +1,8 @@
-"""What the host driver of the weighted median of several pairs (psm_post_process_batch) decides without the device
-(WmBatchSched, wm_batch_cache_plan in primestereomatch_amd/csrc/psm_wm_sched.h): the groups of sweeps of m = 2 n maps and their
-form, when a map is finished, which maps are left to the dataflow form, and the batch-wide cache decision.  tests/wm_batch_sched_probe.cpp
-plays the device to the schedule behind ctypes and is built here with the host compiler.  The rules are stated here a second
-time, in Python; with m = 2 the same tables also go through the single pair's WmSched, which must decide the same, group for group."""
+"""What the host driver of the weighted median decides without the device for the maps of several pairs (psm_post_process_batch;
+WmSched, wm_cache_plan in primestereomatch_amd/csrc/psm_wm_sched.h): the groups of sweeps of m = 2 n maps and their form, when a
+map is finished, which maps are left to the dataflow form, and the call-wide cache decision.  tests/wm_sched_probe.cpp plays the
+device to the schedule behind ctypes and is built here with the host compiler.  The rules are stated here a second time, in
+Python.  A single pair is the same schedule with m = 2: tests/test_wm_sched.py holds it against the single call's model."""
 import ctypes
 import os
 import subprocess
@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "wm_batch_sched_probe.cpp")
+SRC = os.path.join(HERE, "wm_sched_probe.cpp")
 TWO_SWEEPS, NO_CACHE = 8388608, 16777216          # PSM_FLAG_WMF_TWO_SWEEPS, PSM_FLAG_WMF_NO_CACHE (include/primesm_hip.h)
 CAP, LANE_MIN, WPIX = 96, 8192, 19 * 20
 NCNT = 2 * (CAP + 2)
@@ -21,12 +21,11 @@ SIZES = (2, 4, 6, 16)
 
 @pytest.fixture(scope="module")
 def probe(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("wm_batch_sched") / "wm_batch_sched_probe.so")
+    so = str(tmp_path_factory.mktemp("wm_batch_sched") / "wm_sched_probe.so")
     subprocess.run(["c++", "-std=c++17", "-O1", "-Wall", "-Werror", "-fPIC", "-shared", SRC, "-o", so], check=True)
     lib = ctypes.CDLL(so)
-    lib.wmb_probe_cache.restype = ctypes.c_ulonglong
-    lib.wmb_probe_cache_single.restype = ctypes.c_ulonglong
-    assert (lib.wmb_probe_ncnt(), lib.wmb_probe_cap(), lib.wmb_probe_lane_min(), lib.wmb_probe_wpix()) == (NCNT, CAP, LANE_MIN, WPIX)
+    lib.wm_probe_cache.restype = ctypes.c_ulonglong
+    assert (lib.wm_probe_ncnt(), lib.wm_probe_cap(), lib.wm_probe_lane_min(), lib.wm_probe_wpix()) == (NCNT, CAP, LANE_MIN, WPIX)
     return lib
 
 
@@ -84,7 +83,7 @@ def model_cache(n0, avail, flags):
 
 
 # ---- the header through the probe ----
-def probe_run(probe, table, flags, single=False):
+def probe_run(probe, table, flags):
     t = np.ascontiguousarray(table, dtype=np.int32)
     m = t.shape[0]
     assert t.shape == (m, NCNT)
@@ -93,11 +92,7 @@ def probe_run(probe, table, flags, single=False):
     ns = ctypes.c_int()
     done, tail, sweeps, evals = (ctypes.c_int * m)(), (ctypes.c_int * m)(), (ctypes.c_int * m)(), (ctypes.c_longlong * m)()
     tp = t.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-    if single:
-        assert m == 2
-        ng = probe.wmb_probe_run_single(tp, ctypes.c_uint(flags), groups, room, snaps, ctypes.byref(ns), done, tail, sweeps, evals)
-    else:
-        ng = probe.wmb_probe_run(tp, m, ctypes.c_uint(flags), groups, room, snaps, ctypes.byref(ns), done, tail, sweeps, evals)
+    ng = probe.wm_probe_run(tp, m, ctypes.c_uint(flags), groups, room, snaps, ctypes.byref(ns), done, tail, sweeps, evals)
     assert ng <= room and ns.value <= room
     return ([(groups[3 * i], groups[3 * i + 1], groups[3 * i + 2]) for i in range(ng)],
             [(snaps[2 * i], snaps[2 * i + 1]) for i in range(ns.value)], list(done), list(tail), list(sweeps), list(evals))
@@ -123,13 +118,10 @@ EMPTY = counters([0], [0])
 
 
 def both(probe, table, flags=0):
-    """The model, the batch schedule and - with two maps - the single pair's schedule: every group (begin, end, form), every
-    snapshot, done, tail, sweeps and evals equal."""
+    """The model and the schedule: every group (begin, end, form), every snapshot, done, tail, sweeps and evals equal."""
     want = model_run([list(map(int, t)) for t in table], flags)
     got = probe_run(probe, table, flags)
     assert got == want
-    if len(table) == 2:
-        assert probe_run(probe, table, flags, single=True) == got
     return got
 
 
@@ -233,11 +225,9 @@ def test_random_tables(probe, m):
 def cache(probe, n0, avail, flags=0):
     m = len(n0)
     need = (ctypes.c_ulonglong * m)()
-    got = probe.wmb_probe_cache((ctypes.c_int * m)(*n0), m, ctypes.c_ulonglong(avail), ctypes.c_uint(flags), need)
+    got = probe.wm_probe_cache((ctypes.c_int * m)(*n0), m, ctypes.c_ulonglong(avail), ctypes.c_uint(flags), need)
     assert got == model_cache(n0, avail, flags), (n0, avail, flags)
     assert list(need) == [(n + 63) // 64 * 64 * WPIX for n in n0]
-    if m == 2:
-        assert probe.wmb_probe_cache_single(n0[0], n0[1], ctypes.c_ulonglong(avail), ctypes.c_uint(flags)) == got
     return got
 
 
@@ -277,12 +267,11 @@ def test_cache_decision_at_the_seams(probe, m):
 
 
 def test_probe_as_a_program_under_sanitizers(tmp_path):
-    """The same probe source as a program of its own (its main walks seeded random tables of 2, 4, 6 and 16 maps through the schedule
-    - two maps through the single pair's as well - and the cache decision), built with the address and undefined-behaviour
-    sanitizers: it must report nothing."""
-    exe = str(tmp_path / "wm_batch_sched_probe")
+    """The same probe source as a program of its own (its main walks seeded random tables of 2, 4, 6 and 16 maps through the
+    schedule, the cache decision and the layout), built with the address and undefined-behaviour sanitizers: it must report nothing."""
+    exe = str(tmp_path / "wm_sched_probe")
     subprocess.run(["c++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-DWM_BATCH_SCHED_PROBE_MAIN", SRC, "-o", exe], check=True)
+                    "-DWM_SCHED_PROBE_MAIN", SRC, "-o", exe], check=True)
     r = subprocess.run([exe, "1500"], capture_output=True, text=True)
     assert r.returncode == 0 and r.stderr == "", r.stderr
     assert r.stdout.startswith("1500 tables")

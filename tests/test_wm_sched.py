@@ -2,7 +2,8 @@
 groups of sweeps and their form, when a map is finished, the weight cache, the layout of the sweep block), without a context or a
 device: tests/wm_sched_probe.cpp plays the device to the schedule behind ctypes and is built here with the host compiler - the
 header includes nothing of HIP.  The rules are stated here a second time, in Python, as psm_wgt_median had them in its body before
-the header existed; launches, snapshots and statistics must be equal."""
+the header existed, for the two maps of a single pair (the header's one schedule and one cache decision with m = 2; more maps:
+tests/test_wm_batch_sched.py); launches, snapshots and statistics must be equal."""
 import ctypes
 import os
 import subprocess
@@ -23,6 +24,7 @@ def probe(tmp_path_factory):
     so = str(tmp_path_factory.mktemp("wm_sched") / "wm_sched_probe.so")
     subprocess.run(["c++", "-std=c++17", "-O1", "-Wall", "-Werror", "-fPIC", "-shared", SRC, "-o", so], check=True)
     lib = ctypes.CDLL(so)
+    lib.wm_probe_cache.restype = ctypes.c_ulonglong
     assert (lib.wm_probe_ncnt(), lib.wm_probe_cap(), lib.wm_probe_lane_min(), lib.wm_probe_wpix()) == (NCNT, CAP, LANE_MIN, WPIX)
     return lib
 
@@ -80,9 +82,8 @@ def model_cache(n0, avail, flags):
 
 
 def model_layout(HW):
-    """-> ({name: (offset, bytes)} of every part of the block, bytes to allocate, ints per snapshot)."""
+    """-> ({name: (offset, bytes)} of every part of the block, bytes to allocate)."""
     nb = (HW + 255) // 256 * 256
-    ncnt = 2 * (96 + 2)
     per_side = 4 * nb + 6 * nb * 4
     parts = {}
     for s in range(2):
@@ -92,8 +93,7 @@ def model_layout(HW):
             parts[name, s] = (b + i * nb, nb)
         for i, name in enumerate(("stamp", "list0", "list1", "chg", "slot_of", "inv")):
             parts[name, s] = (ip + i * nb * 4, nb * 4)
-        parts["cnt", s] = (2 * per_side + s * ncnt * 4, ncnt * 4)
-    return parts, 2 * per_side + 2 * ncnt * 4, 2 * ncnt
+    return parts, 2 * per_side
 
 
 # ---- the header through the probe ----
@@ -101,13 +101,16 @@ def probe_run(probe, table, flags):
     t = np.ascontiguousarray(table, dtype=np.int32)
     assert t.shape == (2, NCNT)
     room = CAP + 8
-    launches, snaps = (ctypes.c_int * (2 * room))(), (ctypes.c_int * (2 * room))()
+    groups, snaps = (ctypes.c_int * (3 * room))(), (ctypes.c_int * (2 * room))()
     ns, sweeps, evals = ctypes.c_int(), (ctypes.c_int * 2)(), (ctypes.c_longlong * 2)()
-    nl = probe.wm_probe_run(t.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ctypes.c_uint(flags), launches, room, snaps, ctypes.byref(ns),
-                            sweeps, evals)
-    assert nl <= room and ns.value <= room
-    return ([(launches[2 * i], launches[2 * i + 1]) for i in range(nl)], [(snaps[2 * i], snaps[2 * i + 1]) for i in range(ns.value)],
-            list(sweeps), list(evals))
+    done, tail = (ctypes.c_int * 2)(), (ctypes.c_int * 2)()
+    ng = probe.wm_probe_run(t.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), 2, ctypes.c_uint(flags), groups, room, snaps, ctypes.byref(ns),
+                            done, tail, sweeps, evals)
+    assert ng <= room and ns.value <= room
+    assert [bool(d) for d in done] == [s > 0 for s in sweeps]
+    # (the probe reports groups {begin, end, form}: every sweep of a group is launched in the group's form)
+    launches = [(k, groups[3 * i + 2]) for i in range(ng) for k in range(groups[3 * i], groups[3 * i + 1])]
+    return launches, [(snaps[2 * i], snaps[2 * i + 1]) for i in range(ns.value)], list(sweeps), list(evals)
 
 
 def counters(active, changed):
@@ -218,10 +221,11 @@ def test_random_tables(probe):
 
 
 def cache(probe, n0, avail, flags=0):
-    out = (ctypes.c_ulonglong * 2)()
-    probe.wm_probe_cache(n0[0], n0[1], ctypes.c_ulonglong(avail), ctypes.c_uint(flags), out)
-    assert (out[0], out[1]) == model_cache(n0, avail, flags), (n0, avail, flags)
-    return out[0], out[1]
+    need = (ctypes.c_ulonglong * 2)()
+    floats = probe.wm_probe_cache((ctypes.c_int * 2)(*n0), 2, ctypes.c_ulonglong(avail), ctypes.c_uint(flags), need)
+    assert floats in (0, need[0] + need[1])
+    assert (floats, need[0]) == model_cache(n0, avail, flags), (n0, avail, flags)      # (the right side begins behind the left side's need)
+    return floats, need[0]
 
 
 def test_cache_decision(probe):
@@ -261,23 +265,23 @@ def test_cache_decision(probe):
 @pytest.mark.parametrize("W,H", [(9, 9), (111, 233), (1920, 1080)])
 def test_block_layout(probe, W, H):
     HW = W * H
-    out = (ctypes.c_ulonglong * 25)()
+    out = (ctypes.c_ulonglong * 21)()
     probe.wm_probe_layout(ctypes.c_ulonglong(HW), out)
-    names = ("orig", "newv", "chgb", "rowany", "stamp", "list0", "list1", "chg", "slot_of", "inv", "cnt")
-    parts, nbytes, snap = model_layout(HW)
-    got = {(n, s): out[11 * s + i] for s in range(2) for i, n in enumerate(names)}
+    names = ("orig", "newv", "chgb", "rowany", "stamp", "list0", "list1", "chg", "slot_of", "inv")
+    parts, nbytes = model_layout(HW)
+    got = {(n, s): out[10 * s + i] for s in range(2) for i, n in enumerate(names)}
     assert got == {k: off for k, (off, _) in parts.items()}
-    assert (out[22], out[23], out[24]) == (parts["cnt", 0][0], nbytes, snap)
-    # every part inside the allocation, none overlapping another; ints on int boundaries; the two maps' counters adjacent (one
-    # fill and one snapshot of `snap` ints take both)
+    assert out[20] == nbytes
+    # every part inside the allocation, none overlapping another; ints on int boundaries, every part on a 256-byte one (the seed
+    # writes 16 bytes per lane); the counters are no longer in the block (they lie with the call's first context)
     spans = sorted((got[k], got[k] + parts[k][1], k) for k in parts)
     assert spans[0][0] == 0 and spans[-1][1] == nbytes
     for (a0, a1, ka), (b0, b1, kb) in zip(spans, spans[1:]):
         assert a1 <= b0, (ka, kb)
     for (n, s), off in got.items():
-        assert parts[n, s][1] >= (HW if n in names[:4] else NCNT * 4 if n == "cnt" else HW * 4)
+        assert parts[n, s][1] >= (HW if n in names[:4] else HW * 4)
         assert n in names[:4] or off % 4 == 0
-    assert got["cnt", 1] == got["cnt", 0] + NCNT * 4 and snap == 2 * NCNT
+        assert off % 256 == 0
 
 
 def test_probe_as_a_program_under_sanitizers(tmp_path):
