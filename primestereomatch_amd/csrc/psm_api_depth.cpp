@@ -177,9 +177,10 @@ int psm_reproject(psm_ctx *c, int source, int outputs, int flags, uint32_t *coun
     forget(q);
     PSM_HIP(c, hipMemsetAsync(q.cnt, 0, sizeof(unsigned), c->stream));
     if (timed) PSM_HIP(c, hipEventRecord(q.ev[0], c->stream));
-    launch_dp_count(c->stream, a, g);
-    launch_dp_scan(c->stream, a, g);
-    if (cloud) launch_dp_pack(c->stream, a, g);
+    const Recs<DpArgs> one{&a, nullptr, 1};
+    launch_dp_count(c->stream, g, one);
+    launch_dp_scan(c->stream, g, one);
+    if (cloud) launch_dp_pack(c->stream, g, one);
     if (check_launch(c, "k_dp_count, k_dp_scan, k_dp_pack")) return 1;
     if (timed) PSM_HIP(c, hipEventRecord(q.ev[1], c->stream));
     if (cloud && colour_of(c, source == PSM_DEPTH_SGM).slots && images_read(c, c->stream)) return 1;      // k_dp_pack read the pair's left image
@@ -270,7 +271,7 @@ int psm_reproject_batch(psm_ctx *const *ctxs, int n, int source, int outputs, in
     for (int i = 0; i < n; ++i) tab[i] = depth_args(ctxs[i], source, outputs, flags);
     bool fresh = false;
     if (table_reserve(c0, t.tab, tab.data(), tab.size() * sizeof(DpArgs), &fresh)) return 1;
-    const DpArgs *dt = (const DpArgs *)t.tab.dev;
+    const Recs<DpArgs> recs{tab.data(), (const DpArgs *)t.tab.dev, n};
 
     // ---- every context's earlier work (the result to reproject, a single psm_reproject) is ordered before the shared launches ----
     if (batch_join(c0, ctxs, n)) return 1;
@@ -282,10 +283,10 @@ int psm_reproject_batch(psm_ctx *const *ctxs, int n, int source, int outputs, in
     }
     const DpGeom g{c0->W, c0->H, source};
     if (timed) PSM_HIP(c0, hipEventRecord(t.ev[0], s));
-    launch_dp_count(s, tab[0], g, dt, n);
-    launch_dp_scan(s, tab[0], g, dt, n);
-    if (cloud) launch_dp_pack(s, tab[0], g, dt, n);
-    if (check_launch(c0, "k_dp_count_b, k_dp_scan_b, k_dp_pack_b")) return 1;
+    launch_dp_count(s, g, recs);
+    launch_dp_scan(s, g, recs);
+    if (cloud) launch_dp_pack(s, g, recs);
+    if (check_launch(c0, "k_dp_count, k_dp_scan, k_dp_pack")) return 1;
     if (timed) PSM_HIP(c0, hipEventRecord(t.ev[1], s));
 
     // ---- every context is now where its own psm_reproject would have left it; only context 0 counts as timed ----

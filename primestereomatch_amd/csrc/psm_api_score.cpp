@@ -69,18 +69,17 @@ int ensure_scratch(psm_ctx *c)
     return 0;
 }
 
-// the context's buffers (ensure_scratch) as the kernels take them: an entry of a batch's table
+// the context's buffers (ensure_scratch) as the kernels take them: a single call's record, an entry of a batch's table
 ScPair score_pair(const psm_ctx *c)
 {
     const ScoreState &q = c->score;
     return ScPair{c->maps, sgm_source_map(c), q.have_truth ? q.gt : nullptr, use_mask(q) ? q.mask : nullptr, q.planes, q.cnt};
 }
 
-ScArgs score_args(const psm_ctx *c, const ScPair &p)
+ScArgs score_args(const psm_ctx *c)
 {
     const ScoreState &q = c->score;
     ScArgs a;
-    a.maps = p.maps; a.d16 = p.d16; a.gt = p.gt; a.mask = p.mask; a.planes = p.planes; a.cnt = p.cnt;
     a.W = c->W; a.H = c->H; a.D = c->D;
     a.scale = q.scale;
     a.thr = q.thr * (127 / c->D);
@@ -166,13 +165,15 @@ int psm_score(psm_ctx *c, int source, struct psm_score *out)
     if (ensure_scratch(c)) return 1;
     ScoreState &q = c->score;
     const bool timed = c->opt_profile != 0;
-    const ScArgs a = score_args(c, score_pair(c));
+    const ScArgs a = score_args(c);
+    const ScPair p = score_pair(c);
+    const Recs<ScPair> one{&p, nullptr, 1};
     q.source = -1;
     q.pending = q.timed = false;
     PSM_HIP(c, hipMemsetAsync(q.cnt, 0, sizeof(ScCnt), c->stream));
     if (timed) PSM_HIP(c, hipEventRecord(q.ev[0], c->stream));
-    if (source == PSM_SCORE_SGM) launch_sc_minmax(c->stream, a);
-    launch_sc_score(c->stream, source, a);
+    if (source == PSM_SCORE_SGM) launch_sc_minmax(c->stream, a, one);
+    launch_sc_score(c->stream, source, a, one);
     if (check_launch(c, "k_sc_minmax, k_sc_score")) return 1;
     if (timed) PSM_HIP(c, hipEventRecord(q.ev[1], c->stream));
     PSM_HIP(c, hipMemcpyAsync(q.pin, q.cnt, sizeof(ScCnt), hipMemcpyDeviceToHost, c->stream));
@@ -251,7 +252,7 @@ int psm_score_batch(psm_ctx *const *ctxs, int n, int source, struct psm_score *o
     for (int i = 0; i < n; ++i) tab[i] = score_pair(ctxs[i]);
     bool fresh = false;
     if (table_reserve(c0, t.tab, tab.data(), tab.size() * sizeof(ScPair), &fresh)) return 1;
-    const ScPair *dt = (const ScPair *)t.tab.dev;
+    const Recs<ScPair> recs{tab.data(), (const ScPair *)t.tab.dev, n};
 
     // ---- every context's earlier work (the result to score, a single psm_score) is ordered before the shared launches ----
     if (batch_join(c0, ctxs, n)) return 1;
@@ -263,11 +264,11 @@ int psm_score_batch(psm_ctx *const *ctxs, int n, int source, struct psm_score *o
         q.pending = q.timed = false;
         PSM_HIP(c0, hipMemsetAsync(q.cnt, 0, sizeof(ScCnt), s));
     }
-    const ScArgs a = score_args(c0, ScPair{nullptr, nullptr, q0.have_truth ? q0.gt : nullptr, use_mask(q0) ? q0.mask : nullptr, nullptr, nullptr});      // (the scalars; the pointers are the table's)
+    const ScArgs a = score_args(c0);
     if (timed) PSM_HIP(c0, hipEventRecord(t.ev[0], s));
-    if (source == PSM_SCORE_SGM) launch_sc_minmax(s, a, dt, n);
-    launch_sc_score(s, source, a, dt, n);
-    if (check_launch(c0, "k_sc_minmax_b, k_sc_score_b")) return 1;
+    if (source == PSM_SCORE_SGM) launch_sc_minmax(s, a, recs);
+    launch_sc_score(s, source, a, recs);
+    if (check_launch(c0, "k_sc_minmax, k_sc_score")) return 1;
     if (timed) PSM_HIP(c0, hipEventRecord(t.ev[1], s));
 
     // ---- every context is now where its own psm_score would have left it; only context 0 counts as timed ----

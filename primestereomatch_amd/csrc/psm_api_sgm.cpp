@@ -138,8 +138,8 @@ int ensure_buffers(psm_ctx *c)
     return 0;
 }
 
-// One pair's buffers (ensure_buffers) as the kernels take them: the record of a batch's device table, and what a single pair's
-// SgmArgs point to.  l, r: the staged pair, or psm_sgm_compute_gray's.
+// One pair's buffers (ensure_buffers) as the kernels take them: the record a single call passes by value and a batch's device table
+// holds.  l, r: the staged pair, or psm_sgm_compute_gray's.
 SgmPair pair_of(const psm_ctx *c, const void *l, const void *r)
 {
     const SgmState &g = c->sgm;
@@ -153,7 +153,7 @@ SgmPair pair_of(const psm_ctx *c, const void *l, const void *r)
     return p;
 }
 
-// the context's settings as the kernels take them; the pointers stay null: a single pair's are set by enqueue, a batch's are the table's
+// the context's settings as the kernels take them
 SgmArgs sgm_args(const psm_ctx *c, int depth, int ch, int p1, int p2)
 {
     const SgmState &g = c->sgm;
@@ -167,23 +167,22 @@ SgmArgs sgm_args(const psm_ctx *c, int depth, int ch, int p1, int p2)
     return a;
 }
 
-// the filter's settings as the kernels take them (the planes: the caller's)
+// the filter's settings as the kernels take them
 SpkArgs speckle_args(const psm_ctx *c, int new_val, int max_size, long long max_diff)
 {
     SpkArgs a;
-    a.map = nullptr; a.label = nullptr; a.size = nullptr;
     a.W = c->W; a.H = c->H;
     a.new_val = new_val; a.max_size = max_size;
     a.max_diff = (int)(max_diff > 65535 ? 65535 : max_diff);      // (two int16 values differ by 65535 at most)
     return a;
 }
 
-// The speckle filter in place on stream s - on the map of `a`, or on the `out` maps of the table's n pairs: four launches, nothing
-// read back.  timed: the event behind them is c's ev[4] (the one ahead is already recorded).
-int enqueue_speckle(psm_ctx *c, hipStream_t s, const SpkArgs &a, const SgmPair *tab, int n, bool timed)
+// The speckle filter in place on stream s - on the `out` maps of the pairs of q, with their planes: four launches, nothing read
+// back.  timed: the event behind them is c's ev[4] (the one ahead is already recorded).
+int enqueue_speckle(psm_ctx *c, hipStream_t s, const SpkArgs &a, const Recs<SgmPair> &q, bool timed)
 {
-    launch_speckle(s, a, tab, n);
-    if (check_launch(c, tab ? "k_spk_*_b" : "k_spk_*")) return 1;
+    launch_speckle(s, a, q);
+    if (check_launch(c, "k_spk_*")) return 1;
     if (timed) PSM_HIP(c, hipEventRecord(c->sgm.ev[4], s));
     return 0;
 }
@@ -216,10 +215,10 @@ void mark(SgmState &g, SgmCost kind, int ch, int dmin, int D, bool timed)
 }
 
 // The launches of a compute, for a single pair and for a batch alike: disp2 reset, the cost group, the mode's directions, select
-// and check, the speckle filter if it is on - on stream s, with c's settings, events (PSM_OPT_PROFILE) and error slot.  `one`:
-// the single pair's record; else the device table `tab` of n pairs, c being the batch's first context.  `a` brings the scalars.
-// What the two deliberately do differently:
-//   - a single pair resets disp2 with hipMemsetAsync, a batch with k_sgm_fill_b (one launch for the n planes);
+// and check, the speckle filter if it is on - on stream s, with c's settings, events (PSM_OPT_PROFILE) and error slot.  q:
+// the single pair's record (by value), or the n pairs of a batch's device table, c being the batch's first context.  `a` brings the
+// scalars.  What the two deliberately do differently:
+//   - a single pair resets disp2 with hipMemsetAsync, a batch with k_sgm_fill (one launch for the n planes);
 //   - a batch is bracketed by its first context's events only: that context alone counts as timed (psm_sgm_compute_batch);
 //   - psm_sgm_compute_gray comes with ch 1 in `a`, which has also resolved its P1 / P2 defaults (check_params);
 //   - a batch reports a member's allocation failure on its first context, as "...: context i: <the member's message>" - by its
@@ -227,46 +226,37 @@ void mark(SgmState &g, SgmCost kind, int ch, int dmin, int D, bool timed)
 // readers: the n contexts whose image slots the pairs are (null: psm_sgm_compute_gray's own planes) - behind the launches, outside
 // the brackets of psm_sgm_times, each records that its images have been read (the cost group reads them; the paths, the select
 // and the speckle filter read C, S and the maps).
-int enqueue(psm_ctx *c, hipStream_t s, SgmArgs a, const SgmPair *one, const SgmPair *tab, int n, psm_ctx *const *readers)
+int enqueue(psm_ctx *c, hipStream_t s, const SgmArgs &a, const Recs<SgmPair> &q, psm_ctx *const *readers)
 {
-    static const char *const cost_kernels[3][2] = {{"k_sgm_cost", "k_sgm_fill_b, k_sgm_cost_b"},
-                                                   {"k_sgm_prefilter, k_sgm_bt_*", "k_sgm_fill_b, k_sgm_prefilter_b, k_sgm_bt_*_b"},
-                                                   {"k_sgm_census, k_sgm_census_cost", "k_sgm_fill_b, k_sgm_census_b, k_sgm_census_cost_b"}};
+    static const char *const cost_kernels[3] = {"k_sgm_cost", "k_sgm_prefilter, k_sgm_bt_*", "k_sgm_census, k_sgm_census_cost"};
     SgmState &g = c->sgm;
     const SgmCost kind = cost_kind(g);
-    const bool timed = c->opt_profile != 0, batch = tab != nullptr;
-    if (one) {
-        a.img[0] = one->img[0]; a.img[1] = one->img[1];
-        a.C = one->C; a.S = one->S; a.disp2 = one->disp2; a.pre = one->pre; a.out = one->out;
-        a.pf[0] = one->pf[0]; a.pf[1] = one->pf[1];
-        a.Hs = (uint16_t *)a.S;                           // S is free until the first direction stores it (a batch: sgm_pair_args)
-    }
+    const bool timed = c->opt_profile != 0;
+    const int n = q.n;
     // disp2 starts every frame as "nothing lands here"
-    if (batch) launch_sgm_fill_batch(s, a, tab, n);
-    else PSM_HIP(c, hipMemsetAsync(a.disp2, 0xff, (size_t)a.W * a.H * sizeof(uint32_t), s));
+    if (q.dev) launch_sgm_fill_batch(s, a, q.dev, n);
+    else PSM_HIP(c, hipMemsetAsync(q.host[0].disp2, 0xff, (size_t)a.W * a.H * sizeof(uint32_t), s));
     if (timed) PSM_HIP(c, hipEventRecord(g.ev[0], s));
     switch (kind) {
-    case SgmCost::SAD: launch_sgm_cost(s, a, tab, n); break;
-    case SgmCost::BT: launch_sgm_cost_bt(s, a, tab, n); break;
-    case SgmCost::CENSUS: launch_sgm_cost_census(s, a, tab, n); break;
+    case SgmCost::SAD: launch_sgm_cost(s, a, q); break;
+    case SgmCost::BT: launch_sgm_cost_bt(s, a, q); break;
+    case SgmCost::CENSUS: launch_sgm_cost_census(s, a, q); break;
     }
-    if (check_launch(c, cost_kernels[(int)kind][batch])) return 1;
+    if (check_launch(c, cost_kernels[(int)kind])) return 1;
     if (timed) PSM_HIP(c, hipEventRecord(g.ev[1], s));
     // the directions of the mode in table order; the first launch stores S, so no sum of an earlier frame or mode survives
     for (int i = 0; i < SGM_MODE_NDIR[g.mode]; ++i) {
         const int *r = SGM_DIRS[SGM_MODE_DIRS[g.mode][i]];
-        launch_sgm_path(s, a, r[0], r[1], i == 0, tab, n);
+        launch_sgm_path(s, a, r[0], r[1], i == 0, q);
     }
-    if (check_launch(c, batch ? "k_sgm_path_b" : "k_sgm_path")) return 1;
+    if (check_launch(c, "k_sgm_path")) return 1;
     if (timed) PSM_HIP(c, hipEventRecord(g.ev[2], s));
-    launch_sgm_select(s, a, tab, n);
-    if (check_launch(c, batch ? "k_sgm_select_b" : "k_sgm_select")) return 1;
+    launch_sgm_select(s, a, q);
+    if (check_launch(c, "k_sgm_select")) return 1;
     if (timed) PSM_HIP(c, hipEventRecord(g.ev[3], s));
     if (g.spk_window > 0) {
         // filterSpeckles(disp, (minDisparity - 1) * 16, speckleWindowSize, 16 * speckleRange), as StereoSGBM ends
-        SpkArgs k = speckle_args(c, a.invalid, g.spk_window, 16ll * g.spk_range);
-        if (one) { k.map = one->out; k.label = one->spk_label; k.size = one->spk_size; }
-        if (enqueue_speckle(c, s, k, tab, n, timed)) return 1;
+        if (enqueue_speckle(c, s, speckle_args(c, a.invalid, g.spk_window, 16ll * g.spk_range), q, timed)) return 1;
     }
     for (int i = 0; readers && i < n; ++i)
         if (images_read(readers[i], s)) return member_failed(c, "the SGM stage", i, readers[i]);
@@ -302,7 +292,6 @@ SgmArgs maps_args(const psm_ctx *c)
 {
     const SgmState &g = c->sgm;
     SgmArgs a = {};
-    a.S = g.S;
     a.W = c->W; a.H = c->H; a.D = g.res_d; a.Dp = psm::sgm_dp(g.res_d);
     a.dmin = g.res_dmin;
     return a;
@@ -328,7 +317,7 @@ int compute_one(psm_ctx *c, const char *who, const void *l, const void *r, int d
     const SgmArgs a = sgm_args(c, depth, ch, p1, p2);
     const SgmPair p = pair_of(c, l, r);
     forget(g);
-    if (enqueue(c, c->stream, a, &p, nullptr, 1, slots ? &c : nullptr)) return 1;
+    if (enqueue(c, c->stream, a, Recs<SgmPair>{&p, nullptr, 1}, slots ? &c : nullptr)) return 1;
     mark(g, cost_kind(g), ch, a.dmin, a.D, c->opt_profile != 0);
     if (!c->opt_async) PSM_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
@@ -485,7 +474,7 @@ int psm_sgm_compute_batch(psm_ctx *const *ctxs, int n)
     // ---- the launches; then every context is where its own psm_sgm_compute would have left it - only context 0 counts as timed ----
     const SgmArgs a = sgm_args(c0, c0->pair.st.depth, 3, p1, p2);
     for (int i = 0; i < n; ++i) forget(ctxs[i]->sgm);
-    if (enqueue(c0, s, a, nullptr, (const SgmPair *)t.dev, n, ctxs)) return 1;
+    if (enqueue(c0, s, a, Recs<SgmPair>{tab.data(), (const SgmPair *)t.dev, n}, ctxs)) return 1;
     if (batch_fork(c0, ctxs, n)) return 1;
     for (int i = 0; i < n; ++i) mark(ctxs[i]->sgm, cost_kind(g0), 3, a.dmin, a.D, i == 0 && c0->opt_profile != 0);
     if (!c0->opt_async) PSM_HIP(c0, hipStreamSynchronize(s));
@@ -509,7 +498,8 @@ int psm_sgm_select_maps(psm_ctx *c, uint8_t *lmap, uint8_t *rmap, size_t stride)
     if (maps_writable(c)) return 1;
     g.maps_timed = false;
     if (timed) PSM_HIP(c, hipEventRecord(g.ev_maps[0], c->stream));
-    launch_sgm_maps(c->stream, maps_args(c), c->maps);
+    const SgmPair p = pair_of(c, nullptr, nullptr);
+    launch_sgm_maps(c->stream, maps_args(c), Recs<SgmPair>{&p, nullptr, 1});      // (pair_of: maps = c->maps)
     if (check_launch(c, "k_sgm_maps")) return 1;
     if (timed) PSM_HIP(c, hipEventRecord(g.ev_maps[1], c->stream));
     g.maps_timed = timed;
@@ -562,8 +552,8 @@ int psm_sgm_select_maps_batch(psm_ctx *const *ctxs, int n)
     // ---- the launch; then every context is where its own psm_sgm_select_maps would have left it - only context 0 counts as timed ----
     for (int i = 0; i < n; ++i) ctxs[i]->sgm.maps_timed = false;
     if (timed) PSM_HIP(c0, hipEventRecord(g0.ev_maps[0], s));
-    launch_sgm_maps(s, maps_args(c0), nullptr, (const SgmPair *)t.dev, n);
-    if (check_launch(c0, "k_sgm_maps_b")) return 1;
+    launch_sgm_maps(s, maps_args(c0), Recs<SgmPair>{tab.data(), (const SgmPair *)t.dev, n});
+    if (check_launch(c0, "k_sgm_maps")) return 1;
     if (timed) PSM_HIP(c0, hipEventRecord(g0.ev_maps[1], s));
     g0.maps_timed = timed;
     if (batch_fork(c0, ctxs, n)) return 1;
@@ -677,11 +667,11 @@ int psm_sgm_filter_speckles(psm_ctx *c, int16_t *disp, size_t stride_bytes, int 
     if (!rc && timed) rc = hipEventRecord(g.ev[5], c->stream) != hipSuccess ? fail(c, "psm_sgm_filter_speckles: hipEventRecord") : 0;
     if (!rc) rc = ensure_speckle_planes(c);
     if (!rc) {
-        SpkArgs a = speckle_args(c, new_val, max_speckle_size, max_diff);
-        a.map = map; a.label = g.spk_label; a.size = g.spk_size;
+        SgmPair p = {};
+        p.out = map; p.spk_label = g.spk_label; p.spk_size = g.spk_size;
         g.spk_have = false;
         g.spk_t0 = -1;
-        rc = enqueue_speckle(c, c->stream, a, nullptr, 1, timed);
+        rc = enqueue_speckle(c, c->stream, speckle_args(c, new_val, max_speckle_size, max_diff), Recs<SgmPair>{&p, nullptr, 1}, timed);
         if (!rc) {
             g.spk_have = true;
             g.spk_t0 = timed ? 5 : -1;

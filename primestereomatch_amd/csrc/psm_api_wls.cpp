@@ -125,8 +125,8 @@ int table_current(psm_ctx *c)
     return 0;
 }
 
-// The host sequence of psm_wls_filter (its one context, the plain kernels with the record by value) and of psm_wls_filter_batch
-// (batch: the k_wls_*_b kernels over the device table of ctxs[0]), the arguments and every context checked: 1 + 2 T launches on
+// The host sequence of psm_wls_filter (its one context, the record by value) and of psm_wls_filter_batch (batch: the same kernels
+// over the device table of ctxs[0]), the arguments and every context checked: 1 + 2 T launches on
 // ctxs[0]'s stream.  T is ctxs[0]'s: the batch's.
 int wls_run(const char *who, psm_ctx *const *ctxs, int n, int source, int flags, bool batch)
 {
@@ -147,7 +147,7 @@ int wls_run(const char *who, psm_ctx *const *ctxs, int n, int source, int flags,
     }
     bool fresh = false;
     if (batch && table_reserve(c0, c0->wls.pairs, tab.data(), tab.size() * sizeof(WlsPair), &fresh)) return 1;
-    const WlsPair *dt = batch ? (const WlsPair *)c0->wls.pairs.dev : nullptr;
+    const Recs<WlsPair> q{tab.data(), batch ? (const WlsPair *)c0->wls.pairs.dev : nullptr, n};
 
     // ---- every context's earlier work (the map to filter, its weight table, a single psm_wls_filter) is ordered before the shared launches ----
     for (int i = 0; i < n; ++i)
@@ -160,12 +160,12 @@ int wls_run(const char *who, psm_ctx *const *ctxs, int n, int source, int flags,
         w.have = w.pending = w.timed = false;   // (every check and allocation lies before this: the planes are about to be rewritten)
     }
     if (timed) PSM_HIP(c0, hipEventRecord(c0->wls.ev[0], s));
-    launch_wls_init(s, tab[0].a, dt, n);
+    launch_wls_init(s, q);
     for (int t = 0; t < T; ++t) {
-        launch_wls_rows(s, tab[0].a, tab[0].lam[t], t, dt, n);
-        launch_wls_cols(s, tab[0].a, tab[0].lam[t], t, t == T - 1, dt, n);
+        launch_wls_rows(s, q, t);
+        launch_wls_cols(s, q, t, t == T - 1);
     }
-    if (check_launch(c0, batch ? "k_wls_init_b, k_wls_rows_b, k_wls_cols_b" : "k_wls_init, k_wls_rows, k_wls_cols")) return 1;
+    if (check_launch(c0, "k_wls_init, k_wls_rows, k_wls_cols")) return 1;
     if (timed) PSM_HIP(c0, hipEventRecord(c0->wls.ev[1], s));
 
     // ---- every context is now where its own psm_wls_filter would have left it; only context 0 counts as timed ----

@@ -14,9 +14,12 @@
 
 namespace psm {
 
-__device__ __forceinline__ DpArgs dp_pair_args(const DpArgs *tab, unsigned pair)
+// The pair of a workgroup from either record source S (psm_kernels.h, Recs) - a single call's by value, or pair blockIdx.y of a batch's
+// device table - with its pointers read as global ones
+template <typename S>
+__device__ __forceinline__ DpArgs dp_pair(const S &src)
 {
-    const DpArgs &p = tab[pair];
+    const DpArgs &p = rec(src, blockIdx.y);
     DpArgs a = p;
     a.map = sgm_global(p.map); a.valid = sgm_global(p.valid); a.d16 = sgm_global(p.d16); a.img = sgm_global(p.img);
     a.xyz = sgm_global(p.xyz); a.z = sgm_global(p.z); a.cloud = sgm_global(p.cloud);
@@ -132,33 +135,26 @@ __device__ __forceinline__ void dp_pack(const DpArgs &a, const DpGeom &g)
     }
 }
 
-__global__ __launch_bounds__(DP_TILE) void k_dp_count(DpArgs a, DpGeom g) { dp_count(a, g); }
-__global__ __launch_bounds__(DP_TILE) void k_dp_count_b(const DpArgs *tab, DpGeom g) { dp_count(dp_pair_args(tab, blockIdx.y), g); }
-__global__ __launch_bounds__(DP_SCAN) void k_dp_scan(DpArgs a, DpGeom g) { dp_scan(a, g); }
-__global__ __launch_bounds__(DP_SCAN) void k_dp_scan_b(const DpArgs *tab, DpGeom g) { dp_scan(dp_pair_args(tab, blockIdx.y), g); }
-__global__ __launch_bounds__(DP_TILE) void k_dp_pack(DpArgs a, DpGeom g) { dp_pack(a, g); }
-__global__ __launch_bounds__(DP_TILE) void k_dp_pack_b(const DpArgs *tab, DpGeom g) { dp_pack(dp_pair_args(tab, blockIdx.y), g); }
+template <typename S> __global__ __launch_bounds__(DP_TILE) void k_dp_count(S src, DpGeom g) { dp_count(dp_pair(src), g); }
+template <typename S> __global__ __launch_bounds__(DP_SCAN) void k_dp_scan(S src, DpGeom g) { dp_scan(dp_pair(src), g); }
+template <typename S> __global__ __launch_bounds__(DP_TILE) void k_dp_pack(S src, DpGeom g) { dp_pack(dp_pair(src), g); }
 
-static void dp_launch(hipStream_t s, void (*k)(DpArgs, DpGeom), void (*kb)(const DpArgs *, DpGeom), unsigned blocks, unsigned threads,
-                      const DpArgs &a, const DpGeom &g, const DpArgs *tab, int n)
+using DpV = RecVal<DpArgs>;
+using DpT = RecTab<DpArgs>;
+
+void launch_dp_count(hipStream_t s, const DpGeom &g, const Recs<DpArgs> &q)
 {
-    if (tab) hipLaunchKernelGGL(kb, dim3(blocks, (unsigned)n), dim3(threads), 0, s, tab, g);
-    else hipLaunchKernelGGL(k, dim3(blocks), dim3(threads), 0, s, a, g);
+    rec_launch(s, k_dp_count<DpV>, k_dp_count<DpT>, dim3((unsigned)dp_tiles(g.W, g.H), (unsigned)q.n), dim3(DP_TILE), 0, q, g);
 }
 
-void launch_dp_count(hipStream_t s, const DpArgs &a, const DpGeom &g, const DpArgs *tab, int n)
+void launch_dp_scan(hipStream_t s, const DpGeom &g, const Recs<DpArgs> &q)
 {
-    dp_launch(s, k_dp_count, k_dp_count_b, (unsigned)dp_tiles(g.W, g.H), DP_TILE, a, g, tab, n);
+    rec_launch(s, k_dp_scan<DpV>, k_dp_scan<DpT>, dim3(1u, (unsigned)q.n), dim3(DP_SCAN), 0, q, g);
 }
 
-void launch_dp_scan(hipStream_t s, const DpArgs &a, const DpGeom &g, const DpArgs *tab, int n)
+void launch_dp_pack(hipStream_t s, const DpGeom &g, const Recs<DpArgs> &q)
 {
-    dp_launch(s, k_dp_scan, k_dp_scan_b, 1u, DP_SCAN, a, g, tab, n);
-}
-
-void launch_dp_pack(hipStream_t s, const DpArgs &a, const DpGeom &g, const DpArgs *tab, int n)
-{
-    dp_launch(s, k_dp_pack, k_dp_pack_b, (unsigned)dp_tiles(g.W, g.H), DP_TILE, a, g, tab, n);
+    rec_launch(s, k_dp_pack<DpV>, k_dp_pack<DpT>, dim3((unsigned)dp_tiles(g.W, g.H), (unsigned)q.n), dim3(DP_TILE), 0, q, g);
 }
 
 }  // namespace psm

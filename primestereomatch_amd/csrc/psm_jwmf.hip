@@ -14,9 +14,8 @@
 //
 // One launch sequence for a single pair and for several (psm_joint_wmf, psm_joint_wmf_batch): every kernel is one body (jw_*)
 // behind one entry k_jw_*<S>, which has the image to cluster (JwImg) or the map side (JwSide) on a grid axis of its own and is
-// templated over where the records come from - S = JwVal<R>: the at most two records of a single pair by value in the kernarg;
-// S = const R *: the device table of a batch.  The index is uniform per workgroup, so either way these are scalar loads ahead of
-// the same body.  All sums are exact integers: a body's result does not depend on the grid it runs in.
+// templated over where the records come from - S (psm_kernels.h, Recs) - JwVal<R>: the at most two records of a single pair by value in
+// the kernarg; RecTab<R>: the device table of a batch.  All sums are exact integers: a body's result does not depend on the grid it runs in.
 #include "psm_kernels.h"
 
 #include <algorithm>
@@ -50,13 +49,11 @@ __device__ __forceinline__ unsigned key_at(const void *img, int depth, size_t p)
 
 __device__ __forceinline__ void key_xyz(unsigned k, int &x, int &y, int &z) { x = (int)(k >> 12); y = (int)((k >> 6) & 63); z = (int)(k & 63); }
 
-// record i of either source (psm_kernels.h, JwRecs); its pointers are read as global ones (sgm_global)
-template <typename R> __device__ __forceinline__ const R &jw_rec(const R *tab, unsigned i) { return tab[i]; }
-template <typename R> __device__ __forceinline__ const R &jw_rec(const JwVal<R> &v, unsigned i) { return v.r[i]; }
+// the two record sources (psm_kernels.h, Recs) of the images and of the map sides; a record's pointers are read as global ones (sgm_global)
 using ImgV = JwVal<JwImg>;
-using ImgT = const JwImg *;
+using ImgT = RecTab<JwImg>;
 using SideV = JwVal<JwSide>;
-using SideT = const JwSide *;
+using SideT = RecTab<JwSide>;
 
 // presence of every key of one image: one bit per key in a 2^18-bit map
 __device__ __forceinline__ void jw_keys(const void *img, int depth, size_t HW, unsigned *bits)
@@ -70,14 +67,14 @@ __device__ __forceinline__ void jw_keys(const void *img, int depth, size_t HW, u
 
 template <typename S> __global__ void k_jw_keys(S src, int depth, size_t HW)
 {
-    const JwImg &r = jw_rec(src, blockIdx.y);
+    const JwImg &r = rec(src, blockIdx.y);
     jw_keys(sgm_global(r.img), depth, HW, sgm_global(r.bits));
 }
 
 // the key bitmap (what 0) or the key -> cluster table (what 1) of every image to zero, 16 bytes per lane
 template <typename S> __global__ void k_jw_clear(S src, int what)
 {
-    const JwImg &r = jw_rec(src, blockIdx.y);
+    const JwImg &r = rec(src, blockIdx.y);
     uint4 *p = what ? (uint4 *)sgm_global(r.lok) : (uint4 *)sgm_global(r.bits);
     const size_t n = (what ? (size_t)JW_KEYS : (size_t)JW_KEYS / 8) / 16;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = make_uint4(0, 0, 0, 0);
@@ -125,7 +122,7 @@ __device__ __forceinline__ void jw_compact(const unsigned *bits, unsigned *sampl
 
 template <typename S> __global__ void __launch_bounds__(1024) k_jw_compact(S src)
 {
-    const JwImg &r = jw_rec(src, blockIdx.x);
+    const JwImg &r = rec(src, blockIdx.x);
     jw_compact(sgm_global(r.bits), sgm_global(r.samples), sgm_global(r.state) + 3);
 }
 
@@ -143,7 +140,7 @@ __device__ __forceinline__ void jw_identity(const unsigned *samples, int n, floa
 // the images with at most n_clusters samples; such an image counts as converged from the start (the Lloyd entries skip it)
 template <typename S> __global__ void k_jw_identity(S src, int n_clusters)
 {
-    const JwImg &r = jw_rec(src, blockIdx.y);
+    const JwImg &r = rec(src, blockIdx.y);
     if (r.n > n_clusters) return;
     if (blockIdx.x == 0 && threadIdx.x == 0) sgm_global(r.state)[1] = 1;
     jw_identity(sgm_global(r.samples), r.n, sgm_global(r.centres), sgm_global(r.labels));
@@ -216,7 +213,7 @@ __device__ __forceinline__ void jw_seed(const unsigned *samples, int n, int nf, 
 // the start of the call)
 template <typename S> __global__ void __launch_bounds__(JW_SEED_THREADS) k_jw_seed(S src, int n_clusters, unsigned long long seed)
 {
-    const JwImg &r = jw_rec(src, blockIdx.x);
+    const JwImg &r = rec(src, blockIdx.x);
     if (r.n <= n_clusters) return;
     jw_seed(sgm_global(r.samples), r.n, r.nf, seed, sgm_global(r.centres), sgm_global(r.kt), sgm_global(r.d2t));
     int *labels = sgm_global(r.labels), *sums = sgm_global(r.sums);
@@ -263,7 +260,7 @@ __device__ __forceinline__ void jw_assign(const unsigned *samples, int n, int nf
 // the image on grid axis y, x sized for the largest image (an image's workgroups beyond its samples add nothing)
 template <typename S> __global__ void __launch_bounds__(256) k_jw_assign(S src)
 {
-    const JwImg &r = jw_rec(src, blockIdx.y);
+    const JwImg &r = rec(src, blockIdx.y);
     jw_assign(sgm_global(r.samples), r.n, r.nf, sgm_global(r.centres), sgm_global(r.labels), sgm_global(r.sums), sgm_global(r.state));
 }
 
@@ -291,7 +288,7 @@ __device__ __forceinline__ void jw_update(int nf, float *centres, int *sums, int
 
 template <typename S> __global__ void __launch_bounds__(256) k_jw_update(S src, int it)
 {
-    const JwImg &r = jw_rec(src, blockIdx.x);
+    const JwImg &r = rec(src, blockIdx.x);
     jw_update(r.nf, sgm_global(r.centres), sgm_global(r.sums), sgm_global(r.state), it);
 }
 
@@ -303,7 +300,7 @@ __device__ __forceinline__ void jw_lok(const unsigned *samples, int n, const int
 
 template <typename S> __global__ void k_jw_lok(S src)
 {
-    const JwImg &r = jw_rec(src, blockIdx.y);
+    const JwImg &r = rec(src, blockIdx.y);
     jw_lok(sgm_global(r.samples), r.n, sgm_global(r.labels), sgm_global(r.lok));
 }
 
@@ -315,12 +312,12 @@ __device__ __forceinline__ void jw_plane(const JwSide &s, int depth, size_t HW)
 }
 
 // a map side's record: of the device table, its pointers read as global ones (sgm_global, psm_kernels.h); of the kernarg, as it is
-__device__ __forceinline__ JwSide jw_side(const JwSide *tab, unsigned i)
+__device__ __forceinline__ JwSide jw_side(SideT tab, unsigned i)
 {
-    const JwSide &t = tab[i];
+    const JwSide &t = rec(tab, i);
     return JwSide{sgm_global(t.img), sgm_global(t.lok), sgm_global(t.F), sgm_global(t.din), sgm_global(t.wq), sgm_global(t.out)};
 }
-__device__ __forceinline__ const JwSide &jw_side(const SideV &v, unsigned i) { return v.r[i]; }
+__device__ __forceinline__ const JwSide &jw_side(const SideV &v, unsigned i) { return rec(v, i); }
 
 template <typename S> __global__ void k_jw_plane(S src, int depth, size_t HW) { jw_plane(jw_side(src, blockIdx.y), depth, HW); }
 
@@ -383,15 +380,6 @@ __device__ __forceinline__ void jw_median(const JwSide &s, int W, int H, int r)
 
 template <typename S> __global__ void __launch_bounds__(256) k_jw_median(S src, int W, int H, int r) { jw_median(jw_side(src, blockIdx.z), W, H, r); }
 
-// One launch of an entry over either record source (the caller sizes the record's grid axis with q.n): the device table, or - a
-// single pair - its records by value
-template <typename R, typename... A>
-void jw_launch(hipStream_t st, void (*kv)(JwVal<R>, A...), void (*kt)(const R *, A...), dim3 grid, dim3 block, const JwRecs<R> &q, A... rest)
-{
-    if (q.dev) hipLaunchKernelGGL(kt, grid, block, 0, st, q.dev, rest...);
-    else hipLaunchKernelGGL(kv, grid, block, 0, st, JwVal<R>{{q.host[0], q.host[q.n > 1]}}, rest...);
-}
-
 // grid x of the kernels that stride over the pixels of an image (keys, planes)
 unsigned pixel_blocks(size_t HW) { return (unsigned)std::min<size_t>(std::max<size_t>((HW + 255) / 256, 1), 2048); }
 
@@ -399,45 +387,45 @@ unsigned pixel_blocks(size_t HW) { return (unsigned)std::min<size_t>(std::max<si
 
 void launch_jw_keys(hipStream_t st, const JwRecs<JwImg> &im, int depth, size_t HW)
 {
-    jw_launch(st, k_jw_clear<ImgV>, k_jw_clear<ImgT>, dim3(JW_KEYS / 8 / 16 / 256, im.n), dim3(256), im, 0);
-    jw_launch(st, k_jw_keys<ImgV>, k_jw_keys<ImgT>, dim3(pixel_blocks(HW), im.n), dim3(256), im, depth, HW);
+    rec_launch(st, k_jw_clear<ImgV>, k_jw_clear<ImgT>, dim3(JW_KEYS / 8 / 16 / 256, im.n), dim3(256), 0, im, 0);
+    rec_launch(st, k_jw_keys<ImgV>, k_jw_keys<ImgT>, dim3(pixel_blocks(HW), im.n), dim3(256), 0, im, depth, HW);
 }
 
 void launch_jw_compact(hipStream_t st, const JwRecs<JwImg> &im)
 {
-    jw_launch(st, k_jw_compact<ImgV>, k_jw_compact<ImgT>, dim3(im.n), dim3(1024), im);
+    rec_launch(st, k_jw_compact<ImgV>, k_jw_compact<ImgT>, dim3(im.n), dim3(1024), 0, im);
 }
 
 void launch_jw_identity(hipStream_t st, const JwRecs<JwImg> &im, int n_clusters)
 {
-    jw_launch(st, k_jw_identity<ImgV>, k_jw_identity<ImgT>, dim3((n_clusters + 255) / 256, im.n), dim3(256), im, n_clusters);
+    rec_launch(st, k_jw_identity<ImgV>, k_jw_identity<ImgT>, dim3((n_clusters + 255) / 256, im.n), dim3(256), 0, im, n_clusters);
 }
 
 void launch_jw_seed(hipStream_t st, const JwRecs<JwImg> &im, int n_clusters, unsigned long long seed)
 {
-    jw_launch(st, k_jw_seed<ImgV>, k_jw_seed<ImgT>, dim3(im.n), dim3(JW_SEED_THREADS), im, n_clusters, seed);
+    rec_launch(st, k_jw_seed<ImgV>, k_jw_seed<ImgT>, dim3(im.n), dim3(JW_SEED_THREADS), 0, im, n_clusters, seed);
 }
 
 void launch_jw_lloyd(hipStream_t st, const JwRecs<JwImg> &im, int n_max, int it)
 {
-    jw_launch(st, k_jw_assign<ImgV>, k_jw_assign<ImgT>, dim3(std::min((n_max + 255) / 256, 512), im.n), dim3(256), im);
-    jw_launch(st, k_jw_update<ImgV>, k_jw_update<ImgT>, dim3(im.n), dim3(256), im, it);
+    rec_launch(st, k_jw_assign<ImgV>, k_jw_assign<ImgT>, dim3(std::min((n_max + 255) / 256, 512), im.n), dim3(256), 0, im);
+    rec_launch(st, k_jw_update<ImgV>, k_jw_update<ImgT>, dim3(im.n), dim3(256), 0, im, it);
 }
 
 void launch_jw_lok(hipStream_t st, const JwRecs<JwImg> &im, int n_max)
 {
-    jw_launch(st, k_jw_clear<ImgV>, k_jw_clear<ImgT>, dim3(64, im.n), dim3(256), im, 1);
-    jw_launch(st, k_jw_lok<ImgV>, k_jw_lok<ImgT>, dim3((n_max + 255) / 256, im.n), dim3(256), im);
+    rec_launch(st, k_jw_clear<ImgV>, k_jw_clear<ImgT>, dim3(64, im.n), dim3(256), 0, im, 1);
+    rec_launch(st, k_jw_lok<ImgV>, k_jw_lok<ImgT>, dim3((n_max + 255) / 256, im.n), dim3(256), 0, im);
 }
 
 void launch_jw_plane(hipStream_t st, const JwRecs<JwSide> &sides, int depth, size_t HW)
 {
-    jw_launch(st, k_jw_plane<SideV>, k_jw_plane<SideT>, dim3(pixel_blocks(HW), sides.n), dim3(256), sides, depth, HW);
+    rec_launch(st, k_jw_plane<SideV>, k_jw_plane<SideT>, dim3(pixel_blocks(HW), sides.n), dim3(256), 0, sides, depth, HW);
 }
 
 void launch_jw_median(hipStream_t st, const JwRecs<JwSide> &sides, int W, int H, int r)
 {
-    jw_launch(st, k_jw_median<SideV>, k_jw_median<SideT>, dim3((W + JW_TILE - 1) / JW_TILE, (H + JW_TILE - 1) / JW_TILE, sides.n), dim3(256), sides, W, H, r);
+    rec_launch(st, k_jw_median<SideV>, k_jw_median<SideT>, dim3((W + JW_TILE - 1) / JW_TILE, (H + JW_TILE - 1) / JW_TILE, sides.n), dim3(256), 0, sides, W, H, r);
 }
 
 }  // namespace psm

@@ -124,6 +124,51 @@ void launch_wta(hipStream_t s, const float *vol, int W, int H, int d_begin, int 
 // min over nranks key planes -> map
 void launch_merge(hipStream_t s, const long long *keys_all, size_t rank_stride, int nranks, int n,
                   uint8_t *map);
+// ---- record sources: what every stage with a batch entry (post-processing tail, JointWMF, SGM and speckle, score, depth, WLS) shares ----
+// The n records R of one launch as the host filled them, the record on a grid axis.  dev == nullptr: the records of a single call
+// travel by value in the kernarg (RecVal: one record; the two of JointWMF's single pair); else the kernels read the n records of the
+// device table at dev.  Either way the index is uniform per workgroup: scalar loads ahead of one body.  Every kernel of these stages
+// is one template over the two sources, S = RecVal<R, N> or RecTab<R>, and rec(src, i) is record i of either.
+template <typename R> struct Recs { const R *host, *dev; int n; };
+template <typename R, int N = 1> struct RecVal { R r[N]; };
+template <typename R> using RecTab = const R *;
+template <typename R> __device__ __forceinline__ const R &rec(const R *tab, unsigned i) { return tab[i]; }
+template <typename R, int N> __device__ __forceinline__ const R &rec(const RecVal<R, N> &v, unsigned i) { return v.r[N == 1 ? 0 : i]; }
+// A pointer a kernel reads from the table is a flat pointer to the compiler (one that arrives as a kernel argument is known to be
+// global): every access through it would become a flat_* instruction, which counts on vmcnt and lgkmcnt at once and makes the
+// body wait for everything in flight (k_sgm_path over the table with flat accesses: 0.44 ms for a batch of one Cones pair against
+// 0.38 ms).  Reading the record's slot as one that holds a global pointer gives the table instantiations the global_* instructions
+// of the by-value ones (a cast of the loaded value to global and back is folded away before it can tell anyone).
+template <typename T>
+__device__ __forceinline__ T *sgm_global(T *const &slot) { return (T *)*(__attribute__((address_space(1))) T *const *)(const void *)&slot; }
+// one launch of a kernel over either source: its two instantiations, the grid with q.n on the record's axis
+template <typename T> struct RecArg { using type = T; };
+template <typename R, int N, typename... A>
+void rec_launch(hipStream_t st, void (*kv)(RecVal<R, N>, A...), void (*kt)(const R *, A...), dim3 grid, dim3 block, size_t lds, const Recs<R> &q,
+                typename RecArg<A>::type... rest)
+{
+    if (q.dev) {
+        hipLaunchKernelGGL(kt, grid, block, lds, st, q.dev, rest...);
+        return;
+    }
+    RecVal<R, N> v;
+    for (int i = 0; i < N; ++i) v.r[i] = q.host[i < q.n ? i : q.n - 1];
+    hipLaunchKernelGGL(kv, grid, block, lds, st, v, rest...);
+}
+// ... of a kernel that takes the call's scalars H ahead of the source (SGM, speckle, score: the argument order of their earlier entries)
+template <typename H, typename R, int N, typename... A>
+void rec_launch(hipStream_t st, void (*kv)(H, RecVal<R, N>, A...), void (*kt)(H, const R *, A...), dim3 grid, dim3 block, size_t lds, const H &head,
+                const Recs<R> &q, typename RecArg<A>::type... rest)
+{
+    if (q.dev) {
+        hipLaunchKernelGGL(kt, grid, block, lds, st, head, q.dev, rest...);
+        return;
+    }
+    RecVal<R, N> v;
+    for (int i = 0; i < N; ++i) v.r[i] = q.host[i < q.n ? i : q.n - 1];
+    hipLaunchKernelGGL(kv, grid, block, lds, st, head, v, rest...);
+}
+
 // (the left-right check and the fill of invalid pixels: with the post-processing tail below, PpRecs)
 
 // weighted-median post-filter of one map, in place, with the reference's raster-order semantics (psm_pp.hip).
@@ -153,21 +198,10 @@ struct PpPair {
     WmPair wm;
     uint8_t *lv, *rv;
 };
-// The n records of one call as the host filled them.  dev == nullptr (n == 1): the record travels by value in the kernarg (PpVal,
-// 256 bytes); else the kernels read the device table at dev.  Either way the index is uniform per workgroup: scalar loads ahead of
-// one body (pp_rec).  Every tail kernel is one template over the two sources.
-struct PpRecs { const PpPair *host, *dev; int n; };
-struct PpVal { PpPair r; };
-using PpTab = const PpPair *__restrict__;
-__device__ __forceinline__ const PpPair &pp_rec(const PpVal &v) { return v.r; }
-__device__ __forceinline__ const PpPair &pp_rec(const PpPair *tab) { return tab[blockIdx.z]; }
-// one launch of a tail kernel over either source (grid.z = q.n)
-template <typename... A>
-void pp_launch(hipStream_t st, void (*kv)(PpVal, A...), void (*kt)(const PpPair *, A...), dim3 grid, dim3 block, size_t lds, const PpRecs &q, A... rest)
-{
-    if (q.dev) hipLaunchKernelGGL(kt, grid, block, lds, st, q.dev, rest...);
-    else hipLaunchKernelGGL(kv, grid, block, lds, st, PpVal{q.host[0]}, rest...);
-}
+// The records of one call (Recs above): a single pair travels by value (256 bytes of kernarg), several through the device table.
+using PpRecs = Recs<PpPair>;
+using PpVal = RecVal<PpPair>;
+using PpTab = const PpPair *__restrict__;      // (RecTab<PpPair> with the qualifier the tail's kernels were written and measured with)
 void launch_lr_check(hipStream_t s, const PpRecs &q, int W, int H);       // left-right check of the two maps of every pair -> lv, rv
 void launch_fill_inv(hipStream_t s, const PpRecs &q, int W, int H);       // fill of the invalid pixels of every map in place
 void launch_wm_seed(hipStream_t s, const PpRecs &q, int W, int H);        // (the counters of all maps are zero: the caller's memset)
@@ -223,11 +257,9 @@ struct JwImg {
     uint8_t *lok;
     int n, nf;                         // sample count and clusters: known once the samples have been counted
 };
-// The records (R: JwImg, JwSide) of one launch as the host filled them, the record on a grid axis.  dev == nullptr: the n <= 2 records
-// of a single pair travel by value in the kernarg (JwVal); else the kernels read the n records of the device table at dev and the
-// pointers in them as global ones (sgm_global below).  Either way the index is uniform per workgroup: scalar loads ahead of one body.
-template <typename R> struct JwRecs { const R *host, *dev; int n; };
-template <typename R> struct JwVal { R r[2]; };
+// The records (R: JwImg, JwSide) of one launch (Recs above): the n <= 2 records of a single pair travel by value
+template <typename R> using JwRecs = Recs<R>;
+template <typename R> using JwVal = RecVal<R, 2>;
 void launch_jw_keys(hipStream_t s, const JwRecs<JwImg> &im, int depth, size_t HW);           // clears the bitmaps first
 void launch_jw_compact(hipStream_t s, const JwRecs<JwImg> &im);
 void launch_jw_identity(hipStream_t s, const JwRecs<JwImg> &im, int n_clusters);             // the images with n <= n_clusters
@@ -253,43 +285,29 @@ struct RectArgs {
 void launch_rectify(hipStream_t s, const RectArgs &a);
 
 // psm_sgm.hip: semi-global matching over the staged pair (psm_sgm_compute, psm_api_sgm.cpp)
+// The scalars of one call - a single pair's or a batch's; the pair's buffers are its SgmPair
 struct SgmArgs {
-    const void *img[2];                // staged images: interleaved `ch` channels, PSM_IMG_U8 bytes or PSM_IMG_F32 floats
-    int depth, ch;
+    int depth, ch;                     // of the staged images: PSM_IMG_U8 bytes or PSM_IMG_F32 floats, interleaved `ch` channels
+    int W, H, D, Dp;                   // Dp: elements per pixel, sgm_dp(D)
+    int dmin, invalid;                 // psm_sgm_set_range: index k in [0, D) is the disparity dmin + k; invalid = (dmin - 1) * 16
+    int bs, P1, P2, u, m;
+    int ft;                            // the prefiltered Birchfield-Tomasi cost (launch_sgm_cost_bt only; psm_sgm_set_prefilter): max(pre_filter_cap, 15) | 1
+    int cw, chh;                       // the census cost (launch_sgm_cost_census only; psm_sgm_set_census): the window
+};
+// One pair's buffers: what a single call passes by value and what a batch's device table (psm_sgm_compute_batch) holds per pair,
+// indexed with the pair number (blockIdx.z).  The horizontal block sums Hs of the Birchfield-Tomasi cost, u16 [H][W][Dp], lie in
+// the memory of S (free until the first direction stores it).
+struct SgmPair {
+    const void *img[2];                // staged images
     uint16_t *C;                       // block costs [H][W][Dp]
     uint32_t *S;                       // summed path costs [H][W][Dp]
     uint32_t *disp2;                   // [H][W] packed minima (minS << KB | best index) landing on the right image's pixel, KB = sgm_kb(Dp); all ones: none
     int16_t *pre, *out;                // [H][W] d16 (or `invalid`: not unique) before the consistency test / the final map
-    int W, H, D, Dp;                   // Dp: elements per pixel, sgm_dp(D)
-    int dmin, invalid;                 // psm_sgm_set_range: index k in [0, D) is the disparity dmin + k; invalid = (dmin - 1) * 16
-    int bs, P1, P2, u, m;
-    // the prefiltered Birchfield-Tomasi cost (launch_sgm_cost_bt only; psm_sgm_set_prefilter)
-    uint8_t *pf[2];                    // prefiltered planes of both images, [H][W][2 ch] bytes: P_0 .. P_{ch-1}, Q_0 .. Q_{ch-1}
-    uint16_t *Hs;                      // horizontal block sums [H][W][Dp], in the memory of S (free until the first direction stores it)
-    int ft;                            // max(pre_filter_cap, 15) | 1
-    // the census cost (launch_sgm_cost_census only; psm_sgm_set_census): the window, and in the two pf slots the code planes of both
-    // images, [H][W] uint64 (the two costs exclude each other)
-    int cw, chh;
+    uint8_t *pf[2];                    // the prefiltered planes of both images, [H][W][2 ch] bytes: P_0 .. P_{ch-1}, Q_0 .. Q_{ch-1}; with the census
+                                       // cost the code planes, [H][W] uint64 (the two costs exclude each other); null with the SAD cost
+    unsigned *spk_label, *spk_size;    // the speckle filter's planes (SpkArgs below); null with the filter off
+    uint8_t *maps;                     // the map buffer [2][H][W] k_sgm_maps writes: the context's (psm_sgm_select_maps, _batch)
 };
-// Several pairs of one geometry per launch (psm_sgm_compute_batch): one pair's buffers, an entry of the device table the batched
-// entries index with the pair number (blockIdx.z).  The scalars of SgmArgs / SpkArgs are the batch's; the pointers come from here.
-struct SgmPair {
-    const void *img[2];
-    uint16_t *C;
-    uint32_t *S;
-    uint32_t *disp2;
-    int16_t *pre, *out;
-    uint8_t *pf[2];                    // null with the SAD cost; with the census cost the two code planes
-    unsigned *spk_label, *spk_size;    // null with the speckle filter off
-    uint8_t *maps;                     // the context's map buffer [2][H][W] (k_sgm_maps_b alone writes it: psm_sgm_select_maps_batch)
-};
-// A pointer a kernel reads from the table is a flat pointer to the compiler (one that arrives as a kernel argument is known to be
-// global): every access through it would become a flat_* instruction, which counts on vmcnt and lgkmcnt at once and makes the
-// body wait for everything in flight (k_sgm_path_b with flat accesses: 0.44 ms for a batch of one Cones pair against 0.38 ms).
-// Reading the table's slot as one that holds a global pointer gives the batched entries the global_* instructions of the
-// single-pair ones (a cast of the loaded value to global and back is folded away before it can tell anyone).
-template <typename T>
-__device__ __forceinline__ T *sgm_global(T *const &slot) { return (T *)*(__attribute__((address_space(1))) T *const *)(const void *)&slot; }
 // one pixel of a staged image as a dword of `ch` bytes (depth 0: bytes, PSM_IMG_U8); float images are quantised as lFrame.convertTo(lFrame, CV_8U, 255) does
 // (src/StereoMatch.cpp:174-177): saturate(rint(f * 255.0f)), ties to even
 __device__ __forceinline__ unsigned sgm_px(const void *img, int depth, int ch, size_t idx)
@@ -320,38 +338,30 @@ constexpr int SGM_CEN_TX = 32;         // k_sgm_census: the pixels of a workgrou
 constexpr int SGM_CEN_TY = 8;          // ... and rows
 constexpr int SGM_CEN_MAXW = 9;        // the widest census window (psm_sgm_set_census): 9 x 7 - 1 = 62 bits
 constexpr int SGM_CEN_MAXH = 7;
-// One launch of a kernel with its two entries, over either argument record R (SgmArgs, SpkArgs): the single-pair entry k with the
-// pair in `a`, or - tab given - the batched entry kb over the device table with gz as the grid's z extent
-template <typename R, typename... A>
-static void sgm_launch(hipStream_t s, void (*k)(R, A...), void (*kb)(R, const SgmPair *, A...), dim3 grid, dim3 block, const R &a,
-                       const SgmPair *tab, int gz, A... rest)
-{
-    if (tab) hipLaunchKernelGGL(kb, dim3(grid.x, grid.y, (unsigned)gz), block, 0, s, a, tab, rest...);
-    else hipLaunchKernelGGL(k, grid, block, 0, s, a, rest...);
-}
-// tab == nullptr: the pair whose pointers `a` holds; else the n pairs of the device table (the pointers of `a` unused, grid z = pair)
-void launch_sgm_cost(hipStream_t s, const SgmArgs &a, const SgmPair *tab = nullptr, int n = 1);
-void launch_sgm_cost_bt(hipStream_t s, const SgmArgs &a, const SgmPair *tab = nullptr, int n = 1);   // k_sgm_prefilter, k_sgm_bt_rows, k_sgm_bt_cols: the same C
-void launch_sgm_cost_census(hipStream_t s, const SgmArgs &a, const SgmPair *tab = nullptr, int n = 1);   // k_sgm_census, k_sgm_census_cost: the same C
-void launch_sgm_path(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first, const SgmPair *tab = nullptr, int n = 1);   // S = L_r (first) or S += L_r
-void launch_sgm_select(hipStream_t s, const SgmArgs &a, const SgmPair *tab = nullptr, int n = 1);   // k_sgm_select + k_sgm_check (disp2 all ones before)
+// q: the pair of a single call, or the n pairs of a batch's device table (grid z = pair)
+void launch_sgm_cost(hipStream_t s, const SgmArgs &a, const Recs<SgmPair> &q);
+void launch_sgm_cost_bt(hipStream_t s, const SgmArgs &a, const Recs<SgmPair> &q);       // k_sgm_prefilter, k_sgm_bt_rows, k_sgm_bt_cols: the same C
+void launch_sgm_cost_census(hipStream_t s, const SgmArgs &a, const Recs<SgmPair> &q);   // k_sgm_census, k_sgm_census_cost: the same C
+void launch_sgm_path(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first, const Recs<SgmPair> &q);   // S = L_r (first) or S += L_r
+void launch_sgm_select(hipStream_t s, const SgmArgs &a, const Recs<SgmPair> &q);        // k_sgm_select + k_sgm_check (disp2 all ones before)
 void launch_sgm_fill_batch(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n);   // disp2 of every pair all ones
-// k_sgm_maps: the 8-bit maps of both views from S into `maps` [2][H][W] (tab: into the pairs' `maps`); of `a` it reads S, W, H, D, Dp
-// and dmin >= 0, D <= 256.  One workgroup per row with sgm_maps_lds_bytes(W) of dynamic LDS, which must not exceed SGM_MAPS_LDS_MAX.
+// k_sgm_maps: the 8-bit maps of both views from S into every pair's `maps` [2][H][W]; of `a` it reads W, H, D, Dp and dmin >= 0,
+// D <= 256.  One workgroup per row with sgm_maps_lds_bytes(W) of dynamic LDS, which must not exceed
+// SGM_MAPS_LDS_MAX.
 constexpr size_t SGM_MAPS_LDS_MAX = 65536;
 size_t sgm_maps_lds_bytes(int W);
-void launch_sgm_maps(hipStream_t s, const SgmArgs &a, uint8_t *maps, const SgmPair *tab = nullptr, int n = 1);
+void launch_sgm_maps(hipStream_t s, const SgmArgs &a, const Recs<SgmPair> &q);
 
-// psm_speckle.hip: cv::filterSpeckles on an int16 map, in place (psm_sgm_set_speckle, psm_sgm_filter_speckles)
+// psm_speckle.hip: cv::filterSpeckles on an int16 map, in place (psm_sgm_set_speckle, psm_sgm_filter_speckles).  The planes are an
+// SgmPair's: out, the map [H][W], filtered in place; spk_label [H][W], union-find parents - a pixel index of the same component, <=
+// the pixel's own; all ones: a new_val pixel; spk_size [H][W], run lengths at run heads, then component sizes at roots, in the end
+// every pixel's component size
 struct SpkArgs {
-    int16_t *map;                      // [H][W], filtered in place
-    unsigned *label;                   // [H][W] union-find parents: a pixel index of the same component, <= the pixel's own; all ones: a new_val pixel
-    unsigned *size;                    // [H][W] run lengths at run heads, then component sizes at roots, in the end every pixel's component size
     int W, H;
     int new_val, max_size, max_diff;   // max_diff <= 65535
 };
-// k_spk_runs, k_spk_merge, k_spk_count, k_spk_apply; tab: as above - the maps are the pairs' `out`
-void launch_speckle(hipStream_t s, const SpkArgs &a, const SgmPair *tab = nullptr, int n = 1);
+// k_spk_runs, k_spk_merge, k_spk_count, k_spk_apply; q: as above
+void launch_speckle(hipStream_t s, const SpkArgs &a, const Recs<SgmPair> &q);
 
 // psm_score.hip: the display maps and the reference's error record of the current result (psm_score, psm_api_score.cpp)
 // The counters of one pair, zeroed on the stream ahead of the launches.  mn / mx hold the int16 map's minimum - 32767 (<= 0) and
@@ -363,27 +373,21 @@ struct ScCnt {
 };
 constexpr int SC_MN_BIAS = 32767, SC_MX_BIAS = 32768;
 enum { SC_GIF = 0, SC_SGM = 1, SC_SGM_INT = 2 };       // PSM_SCORE_* (include/primesm_hip.h)
-struct ScArgs {
+// One pair's pointers: a single call's by value, an entry of a batch's device table (psm_score_batch; blockIdx.y = pair)
+struct ScPair {
     const uint8_t *maps;               // SC_GIF: [2][H][W], the context's current maps
     const int16_t *d16;                // SC_SGM, SC_SGM_INT: [H][W], the map of the last compute
     const uint8_t *gt, *mask;          // [H][W] each; gt null: nothing is scored; mask null: step 5 of the metric is left out
     uint8_t *planes;                   // [3][H][W]: left display, right display (SC_GIF only), error plane
     ScCnt *cnt;
+};
+struct ScArgs {                        // the scalars of one call
     int W, H, D;
     int scale, thr;                    // scale_factor; error_threshold * unit: errors up to it count as none
     int disc;                          // PSM_MASK_DISC: mask values up to 254 count as 0
 };
-// Several pairs per launch (psm_score_batch): one pair's pointers, an entry of the device table the batched entries index with the
-// pair number (blockIdx.y); the scalars of ScArgs are the batch's.
-struct ScPair {
-    const uint8_t *maps;
-    const int16_t *d16;
-    const uint8_t *gt, *mask;
-    uint8_t *planes;
-    ScCnt *cnt;
-};
-void launch_sc_minmax(hipStream_t s, const ScArgs &a, const ScPair *tab = nullptr, int n = 1);   // k_sc_minmax: cnt->mn, cnt->mx of d16
-void launch_sc_score(hipStream_t s, int source, const ScArgs &a, const ScPair *tab = nullptr, int n = 1);   // k_sc_score<source>: planes, cnt->bad, cnt->sum
+void launch_sc_minmax(hipStream_t s, const ScArgs &a, const Recs<ScPair> &q);   // k_sc_minmax: cnt->mn, cnt->mx of d16
+void launch_sc_score(hipStream_t s, int source, const ScArgs &a, const Recs<ScPair> &q);   // k_sc_score<source>: planes, cnt->bad, cnt->sum
 
 // psm_depth.hip: cv::reprojectImageTo3D of the current result and the compacted point cloud (psm_reproject, psm_api_depth.cpp)
 enum { DP_GIF = 0, DP_SGM = 1 };                       // PSM_DEPTH_* (include/primesm_hip.h)
@@ -408,10 +412,9 @@ struct DpArgs {
     int depth, ch;                     // of img: PSM_IMG_*, 3 or 1 channels
 };
 struct DpGeom { int W, H, source; };
-// tab == nullptr: the pair of `a`; else the n pairs of the device table (`a` unused, grid y = pair)
-void launch_dp_count(hipStream_t s, const DpArgs &a, const DpGeom &g, const DpArgs *tab = nullptr, int n = 1);   // k_dp_count: dense planes, tile_cnt
-void launch_dp_scan(hipStream_t s, const DpArgs &a, const DpGeom &g, const DpArgs *tab = nullptr, int n = 1);    // k_dp_scan: tile_off, total
-void launch_dp_pack(hipStream_t s, const DpArgs &a, const DpGeom &g, const DpArgs *tab = nullptr, int n = 1);    // k_dp_pack: cloud
+void launch_dp_count(hipStream_t s, const DpGeom &g, const Recs<DpArgs> &q);   // k_dp_count: dense planes, tile_cnt
+void launch_dp_scan(hipStream_t s, const DpGeom &g, const Recs<DpArgs> &q);    // k_dp_scan: tile_off, total
+void launch_dp_pack(hipStream_t s, const DpGeom &g, const Recs<DpArgs> &q);    // k_dp_pack: cloud
 
 // psm_wls.hip: edge-aware WLS smoothing of an int16 map in 16ths, Min et al.'s Fast Global Smoother (psm_wls_filter, psm_api_wls.cpp)
 enum { WLS_GIF = 0, WLS_SGM = 1 };                     // PSM_WLS_* (include/primesm_hip.h)
@@ -439,16 +442,15 @@ struct WlsArgs {
     int depth, ch;                     // of img: PSM_IMG_*, 3 or 1 channels
 };
 __host__ __device__ inline int wls_groups(int lines) { return (lines + WLS_LINES - 1) / WLS_LINES; }
-// A member of a batch (psm_wls_filter_batch): its record and the lambdas of its passes - lambda and sigma are the member's own, the
-// number of passes is the batch's.  The device table holds one per member, indexed with the member number (blockIdx.y).
+// One call's record - psm_wls_filter's, or a member's of a batch (psm_wls_filter_batch) - and the lambdas of its passes: lambda and
+// sigma are the member's own, the number of passes is the batch's.  A single call passes it by value; a batch's device table holds
+// one per member, indexed with the member number (blockIdx.y).  W and H are the same in all records of a call.
 struct WlsPair {
     WlsArgs a;
     float lam[WLS_MAX_ITERS];          // wls_lambda(lambda, T, t), t < T; the rest 0
 };
-// tab == nullptr: the pair of `a` with the pass's `lam`; else the n members of the device table (grid y = member; of `a` only W and H
-// are read - they are the batch's - and the lambda of pass t is the member's lam[t])
-void launch_wls_init(hipStream_t s, const WlsArgs &a, const WlsPair *tab = nullptr, int n = 1);                  // k_wls_init: num, den, kh, kv
-void launch_wls_rows(hipStream_t s, const WlsArgs &a, float lam, int t, const WlsPair *tab = nullptr, int n = 1);   // k_wls_rows: pass t over every row
-void launch_wls_cols(hipStream_t s, const WlsArgs &a, float lam, int t, bool last, const WlsPair *tab = nullptr, int n = 1);   // k_wls_cols: ... every column; last: and the quotient, out and q
+void launch_wls_init(hipStream_t s, const Recs<WlsPair> &q);                   // k_wls_init: num, den, kh, kv
+void launch_wls_rows(hipStream_t s, const Recs<WlsPair> &q, int t);            // k_wls_rows: pass t over every row
+void launch_wls_cols(hipStream_t s, const Recs<WlsPair> &q, int t, bool last);   // k_wls_cols: ... every column; last: and the quotient, out and q
 
 }  // namespace psm

@@ -816,7 +816,7 @@ __device__ __forceinline__ void lr_check_px(const uint8_t *__restrict__ l, const
 template <typename S>
 __global__ __launch_bounds__(256) void k_lr_check(S src, int W)
 {
-    const PpPair &p = pp_rec(src);
+    const PpPair &p = rec(src, blockIdx.z);
     lr_check_px(p.wm.s[0].cur, p.wm.s[1].cur, W, p.lv, p.rv);
 }
 
@@ -879,19 +879,19 @@ template <typename S>
 __global__ __launch_bounds__(64) void k_fill_inv(S src, int W)
 {
     extern __shared__ short row[];
-    const WmSide &a = pp_rec(src).wm.s[blockIdx.y];
+    const WmSide &a = rec(src, blockIdx.z).wm.s[blockIdx.y];
     const size_t at = (size_t)blockIdx.x * W;
     fill_inv_row(row, a.cur + at, a.valid + at, W);
 }
 
 void launch_fill_inv(hipStream_t s, const PpRecs &q, int W, int H)
 {
-    pp_launch(s, k_fill_inv<PpVal>, k_fill_inv<PpTab>, dim3(H, 2, q.n), dim3(64), 2 * (size_t)W * sizeof(short), q, W);
+    rec_launch(s, k_fill_inv<PpVal>, k_fill_inv<PpTab>, dim3(H, 2, q.n), dim3(64), 2 * (size_t)W * sizeof(short), q, W);
 }
 
 void launch_lr_check(hipStream_t s, const PpRecs &q, int W, int H)
 {
-    pp_launch(s, k_lr_check<PpVal>, k_lr_check<PpTab>, dim3((W + 255) / 256, H, q.n), dim3(256), 0, q, W);
+    rec_launch(s, k_lr_check<PpVal>, k_lr_check<PpTab>, dim3((W + 255) / 256, H, q.n), dim3(256), 0, q, W);
 }
 
 // ------------------------------------------------------------------------------------------

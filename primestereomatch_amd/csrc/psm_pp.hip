@@ -315,9 +315,9 @@ __device__ __forceinline__ void wm_seed(const WmSide &a, int HW, int nb)
     }
 }
 // Every kernel of the sweep form is one body (wm_*) behind one entry k_wm_*<S> that has the side on blockIdx.y and the pair on
-// blockIdx.z and is templated over where the pair's record comes from (psm_kernels.h, PpRecs) - S = PpVal: the one pair of a call
+// blockIdx.z and is templated over where the pair's record comes from (psm_kernels.h, Recs) - S = PpVal: the one pair of a call
 // by value in the kernarg; S = PpTab: the device table of a call of several.
-template <typename S> __device__ __forceinline__ const WmSide &wm_side(const S &src) { return pp_rec(src).wm.s[blockIdx.y]; }
+template <typename S> __device__ __forceinline__ const WmSide &wm_side(const S &src) { return rec(src, blockIdx.z).wm.s[blockIdx.y]; }
 template <typename S> __global__ __launch_bounds__(256) void k_wm_seed(S src, int HW, int nb) { wm_seed(wm_side(src), HW, nb); }
 
 // One evaluation of f per LANE (round 3; round 2 spent a whole wave per pixel: every lane scanned all 361 taps for "its"
@@ -877,7 +877,7 @@ static int wm_share(int single, int n)
 void launch_wm_seed(hipStream_t s, const PpRecs &q, int W, int H)
 {   // (the counters of all maps are zero: the caller's memset)
     const int HW = W * H, per_block = 256 * WM_SEED_PER;
-    pp_launch(s, k_wm_seed<PpVal>, k_wm_seed<PpTab>, dim3((HW + per_block - 1) / per_block, 2, q.n), dim3(256), 0, q, HW, (HW + 255) / 256 * 256);
+    rec_launch(s, k_wm_seed<PpVal>, k_wm_seed<PpTab>, dim3((HW + per_block - 1) / per_block, 2, q.n), dim3(256), 0, q, HW, (HW + 255) / 256 * 256);
 }
 
 // the 19 x 19 weights of the invalid pixels of every side -> its wts, slot_of; n_max: an upper bound of the invalid pixels of any side (for the grid)
@@ -886,7 +886,7 @@ void launch_wm_weights(hipStream_t s, const PpRecs &q, int W, int H, int n_max)
     const long long threads = (long long)((n_max + 63) / 64) * WM_K * 64;
     const long long want = (threads + 255) / 256;
     const int cap = wm_share(65536, q.n);
-    pp_launch(s, k_wm_weights<PpVal>, k_wm_weights<PpTab>, dim3((unsigned)(want < cap ? (want > 0 ? want : 1) : cap), 2, q.n), dim3(256), 0, q, W, H);
+    rec_launch(s, k_wm_weights<PpVal>, k_wm_weights<PpTab>, dim3((unsigned)(want < cap ? (want > 0 ? want : 1) : cap), 2, q.n), dim3(256), 0, q, W, H);
 }
 
 // sweep `sw` of every map: evaluate the active lists -> changed pixels -> applied, dependents -> the next lists (WmSide)
@@ -902,20 +902,20 @@ void launch_wm_sweep(hipStream_t s, const PpRecs &q, int W, int H, int maxDis, i
     const dim3 ge(wm_share(dev.nxcd * dev.cus_per_xcd * (per_cu < 1 ? 1 : per_cu), n), 2, n);
     const int force = tail ? 1 : 0;
     if (!tail) {
-        if (cached) pp_launch(s, k_wm_eval<true, PpVal>, k_wm_eval<true, PpTab>, ge, dim3(64), lds, q, sw, W, H, maxDis);
-        else pp_launch(s, k_wm_eval<false, PpVal>, k_wm_eval<false, PpTab>, ge, dim3(64), lds, q, sw, W, H, maxDis);
+        if (cached) rec_launch(s, k_wm_eval<true, PpVal>, k_wm_eval<true, PpTab>, ge, dim3(64), lds, q, sw, W, H, maxDis);
+        else rec_launch(s, k_wm_eval<false, PpVal>, k_wm_eval<false, PpTab>, ge, dim3(64), lds, q, sw, W, H, maxDis);
     }
     // ... and the one-wave-per-pixel form for short lists (either kernel returns at once when a list is not its size)
     const int nb = (maxDis + 63) / 64;
     const dim3 gw(wm_share(8192, n), 2, n);
     wm_with_nb(nb, [&](auto nbv) {
         constexpr int NB = decltype(nbv)::value;
-        if (cached) pp_launch(s, k_wm_eval_w<NB, true, PpVal>, k_wm_eval_w<NB, true, PpTab>, gw, dim3(64), 0, q, sw, W, H, maxDis, force);
-        else pp_launch(s, k_wm_eval_w<NB, false, PpVal>, k_wm_eval_w<NB, false, PpTab>, gw, dim3(64), 0, q, sw, W, H, maxDis, force);
+        if (cached) rec_launch(s, k_wm_eval_w<NB, true, PpVal>, k_wm_eval_w<NB, true, PpTab>, gw, dim3(64), 0, q, sw, W, H, maxDis, force);
+        else rec_launch(s, k_wm_eval_w<NB, false, PpVal>, k_wm_eval_w<NB, false, PpTab>, gw, dim3(64), 0, q, sw, W, H, maxDis, force);
     });
     if (tail) return;               // (the forced wave form applied its changes and queued their dependents itself)
-    pp_launch(s, k_wm_apply<PpVal>, k_wm_apply<PpTab>, dim3(wm_share(2048, n), 2, n), dim3(64), 0, q, sw, W, H, force);
-    pp_launch(s, k_wm_gather<PpVal>, k_wm_gather<PpTab>, dim3(wm_share(2048, n), 2, n), dim3(256), 0, q, sw, W, H);
+    rec_launch(s, k_wm_apply<PpVal>, k_wm_apply<PpTab>, dim3(wm_share(2048, n), 2, n), dim3(64), 0, q, sw, W, H, force);
+    rec_launch(s, k_wm_gather<PpVal>, k_wm_gather<PpTab>, dim3(wm_share(2048, n), 2, n), dim3(256), 0, q, sw, W, H);
 }
 
 void launch_wgt_median(hipStream_t s, uint8_t *dis, const uint8_t *valid, const float4 *g1, int W, int H, int maxDis, int right,

@@ -36,16 +36,22 @@ __device__ __forceinline__ int sc_wave_sum(int v)
            __builtin_amdgcn_readlane(v, 63);
 }
 
-__device__ __forceinline__ ScArgs sc_pair_args(ScArgs a, const ScPair *tab, unsigned pair)
+// What a body takes: the call's scalars and the pointers of one pair, read as global ones, from either record source S
+// (psm_kernels.h, Recs) - a single call's pair by value, or pair blockIdx.y of a batch's device table
+struct ScRun : ScArgs, ScPair {};
+template <typename S>
+__device__ __forceinline__ ScRun sc_run(const S &src, const ScArgs &a, unsigned pair)
 {
-    const ScPair &p = tab[pair];
-    a.maps = sgm_global(p.maps); a.d16 = sgm_global(p.d16); a.gt = sgm_global(p.gt); a.mask = sgm_global(p.mask);
-    a.planes = sgm_global(p.planes); a.cnt = sgm_global(p.cnt);
-    return a;
+    const ScPair &p = rec(src, pair);
+    ScRun r;
+    static_cast<ScArgs &>(r) = a;
+    r.maps = sgm_global(p.maps); r.d16 = sgm_global(p.d16); r.gt = sgm_global(p.gt); r.mask = sgm_global(p.mask);
+    r.planes = sgm_global(p.planes); r.cnt = sgm_global(p.cnt);
+    return r;
 }
 
 // ---- k_sc_minmax: the map is one run of W H int16 values on an 8-byte boundary; a lane takes 4 of them per step ----
-__device__ __forceinline__ void sc_minmax(const ScArgs &a)
+__device__ __forceinline__ void sc_minmax(const ScRun &a)
 {
     const int n = a.W * a.H, n4 = n >> 2;
     int mn = 0x7fff, mx = -0x8000;
@@ -68,8 +74,7 @@ __device__ __forceinline__ void sc_minmax(const ScArgs &a)
     }
 }
 
-__global__ __launch_bounds__(256) void k_sc_minmax(ScArgs a) { sc_minmax(a); }
-__global__ __launch_bounds__(256) void k_sc_minmax_b(ScArgs a, const ScPair *tab) { sc_minmax(sc_pair_args(a, tab, blockIdx.y)); }
+template <typename S> __global__ __launch_bounds__(256) void k_sc_minmax(ScArgs a, S src) { sc_minmax(sc_run(src, a, blockIdx.y)); }
 
 // ---- k_sc_score ----
 // n (1..4) bytes at p as one dword, byte k the pixel x + k.  Rows are W bytes long, so p sits on no particular boundary: the whole
@@ -107,7 +112,7 @@ __device__ __forceinline__ unsigned sc_scale4(unsigned v, int scale)
 
 // One lane per 4 adjacent pixels of a row, ceil(W / 4) lanes per row, the rows one behind the other.
 template <int SRC>
-__device__ __forceinline__ void sc_score(const ScArgs &a)
+__device__ __forceinline__ void sc_score(const ScRun &a)
 {
     const int G = (a.W + 3) >> 2;
     const int t = blockIdx.x * 256 + threadIdx.x;
@@ -167,29 +172,24 @@ __device__ __forceinline__ void sc_score(const ScArgs &a)
     }
 }
 
-template <int SRC> __global__ __launch_bounds__(256) void k_sc_score(ScArgs a) { sc_score<SRC>(a); }
-template <int SRC> __global__ __launch_bounds__(256) void k_sc_score_b(ScArgs a, const ScPair *tab) { sc_score<SRC>(sc_pair_args(a, tab, blockIdx.y)); }
+template <int SRC, typename S> __global__ __launch_bounds__(256) void k_sc_score(ScArgs a, S src) { sc_score<SRC>(sc_run(src, a, blockIdx.y)); }
 
-static void sc_launch(hipStream_t s, void (*k)(ScArgs), void (*kb)(ScArgs, const ScPair *), unsigned blocks, const ScArgs &a,
-                      const ScPair *tab, int n)
-{
-    if (tab) hipLaunchKernelGGL(kb, dim3(blocks, (unsigned)n), dim3(256), 0, s, a, tab);
-    else hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, s, a);
-}
+using ScV = RecVal<ScPair>;
+using ScT = RecTab<ScPair>;
 
-void launch_sc_minmax(hipStream_t s, const ScArgs &a, const ScPair *tab, int n)
+void launch_sc_minmax(hipStream_t s, const ScArgs &a, const Recs<ScPair> &q)
 {
     const int n4 = (a.W * a.H) >> 2, blocks = (n4 + 255) / 256;
-    sc_launch(s, k_sc_minmax, k_sc_minmax_b, (unsigned)(blocks > 1024 ? 1024 : blocks), a, tab, n);      // (a lane of a large map takes several steps)
+    rec_launch(s, k_sc_minmax<ScV>, k_sc_minmax<ScT>, dim3((unsigned)(blocks > 1024 ? 1024 : blocks), (unsigned)q.n), dim3(256), 0, a, q);      // (a lane of a large map takes several steps)
 }
 
-void launch_sc_score(hipStream_t s, int source, const ScArgs &a, const ScPair *tab, int n)
+void launch_sc_score(hipStream_t s, int source, const ScArgs &a, const Recs<ScPair> &q)
 {
-    const unsigned blocks = (unsigned)((((a.W + 3) >> 2) * a.H + 255) / 256);
+    const dim3 grid((unsigned)((((a.W + 3) >> 2) * a.H + 255) / 256), (unsigned)q.n), block(256);
     switch (source) {
-    case SC_GIF: sc_launch(s, k_sc_score<SC_GIF>, k_sc_score_b<SC_GIF>, blocks, a, tab, n); break;
-    case SC_SGM: sc_launch(s, k_sc_score<SC_SGM>, k_sc_score_b<SC_SGM>, blocks, a, tab, n); break;
-    default: sc_launch(s, k_sc_score<SC_SGM_INT>, k_sc_score_b<SC_SGM_INT>, blocks, a, tab, n); break;
+    case SC_GIF: rec_launch(s, k_sc_score<SC_GIF, ScV>, k_sc_score<SC_GIF, ScT>, grid, block, 0, a, q); break;
+    case SC_SGM: rec_launch(s, k_sc_score<SC_SGM, ScV>, k_sc_score<SC_SGM, ScT>, grid, block, 0, a, q); break;
+    default: rec_launch(s, k_sc_score<SC_SGM_INT, ScV>, k_sc_score<SC_SGM_INT, ScT>, grid, block, 0, a, q); break;
     }
 }
 

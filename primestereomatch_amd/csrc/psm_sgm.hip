@@ -44,19 +44,29 @@ __device__ __forceinline__ int sgm_wave_min(int v)
 // (sgm_px, one pixel of a staged image as a dword of its bytes: psm_kernels.h - the reprojection stage's colours read it too)
 __device__ __forceinline__ int sgm_clamp(int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); }
 
-// Several pairs per launch (psm_sgm_compute_batch): every kernel below is one body (sgm_*) behind two entries.  k_sgm_* takes its
-// pair's pointers in SgmArgs, as ever; k_sgm_*_b has the pair on grid axis z and reads its pointers from the device table into
-// the same SgmArgs - the pair number is uniform per workgroup, so these are scalar loads ahead of an unchanged body.  All index
-// arithmetic stays inside a pair.
-__device__ __forceinline__ SgmArgs sgm_pair_args(SgmArgs a, const SgmPair *tab, unsigned pair)
+// Every kernel below is one body (sgm_*) behind an entry that is a template over the record source S (psm_kernels.h, Recs): the pair
+// of a single call by value, or pair blockIdx.z of a batch's device table (psm_sgm_compute_batch).  The entry assembles what the body
+// takes - the call's scalars and the pair's pointers, read as global ones; the pair number is uniform per workgroup, so these are
+// scalar loads ahead of an unchanged body.  All index arithmetic stays inside a pair.
+struct SgmRun : SgmArgs, SgmPair {
+    uint16_t *Hs;                      // horizontal block sums [H][W][Dp], in the memory of S (free until the first direction stores it)
+};
+template <typename S>
+__device__ __forceinline__ SgmRun sgm_run(const S &src, const SgmArgs &a, unsigned pair)
 {
-    const SgmPair &p = tab[pair];
-    a.img[0] = sgm_global(p.img[0]); a.img[1] = sgm_global(p.img[1]);
-    a.C = sgm_global(p.C); a.S = sgm_global(p.S); a.disp2 = sgm_global(p.disp2); a.pre = sgm_global(p.pre); a.out = sgm_global(p.out);
-    a.pf[0] = sgm_global(p.pf[0]); a.pf[1] = sgm_global(p.pf[1]);
-    a.Hs = (uint16_t *)a.S;
-    return a;
+    const SgmPair &p = rec(src, pair);
+    SgmRun r;
+    static_cast<SgmArgs &>(r) = a;
+    r.img[0] = sgm_global(p.img[0]); r.img[1] = sgm_global(p.img[1]);
+    r.C = sgm_global(p.C); r.S = sgm_global(p.S); r.disp2 = sgm_global(p.disp2); r.pre = sgm_global(p.pre); r.out = sgm_global(p.out);
+    r.pf[0] = sgm_global(p.pf[0]); r.pf[1] = sgm_global(p.pf[1]);
+    r.spk_label = r.spk_size = nullptr;                  // (the speckle filter's: psm_speckle.hip)
+    r.maps = sgm_global(p.maps);
+    r.Hs = (uint16_t *)r.S;
+    return r;
 }
+using SgmV = RecVal<SgmPair>;
+using SgmT = RecTab<SgmPair>;
 
 // One workgroup per SGM_TX pixels of one row, one thread per disparity.  The BS rows of both images the block needs go to LDS as
 // one dword per pixel (v_sad_u8 then takes the 1 or 3 channels of a tap in one instruction); a thread walks x with its d fixed:
@@ -65,7 +75,7 @@ __device__ __forceinline__ SgmArgs sgm_pair_args(SgmArgs a, const SgmPair *tab, 
 // WIDE (D > 256): 256 threads, a thread takes the disparities d, d + 256, ... in turn; the staged right span is NL + D - 1 columns
 // either way (static LDS: 29.7 KB at BS 7 when WIDE), and holds the clamped columns: a tap's index needs no clamp of its own.
 template <int BS, bool WIDE>
-__device__ __forceinline__ void sgm_cost(const SgmArgs &a)
+__device__ __forceinline__ void sgm_cost(const SgmRun &a)
 {
     constexpr int HALF = BS / 2, NL = SGM_TX + BS - 1, NR = NL + (WIDE ? SGM_DMAX : 256) - 1;
     __shared__ unsigned sl[BS][NL], sr[BS][NR];
@@ -109,9 +119,8 @@ __device__ __forceinline__ void sgm_cost(const SgmArgs &a)
     } while (WIDE && (d += 256) < a.Dp);
 }
 
-template <int BS, bool WIDE> __global__ __launch_bounds__(256) void k_sgm_cost(SgmArgs a) { sgm_cost<BS, WIDE>(a); }
-template <int BS, bool WIDE>
-__global__ __launch_bounds__(256) void k_sgm_cost_b(SgmArgs a, const SgmPair *tab) { sgm_cost<BS, WIDE>(sgm_pair_args(a, tab, blockIdx.z)); }
+template <int BS, bool WIDE, typename S>
+__global__ __launch_bounds__(256) void k_sgm_cost(SgmArgs a, S src) { sgm_cost<BS, WIDE>(sgm_run(src, a, blockIdx.z)); }
 
 // ---- the prefiltered Birchfield-Tomasi cost (psm_sgm_set_prefilter, tests/sgm_bt_model.py): the same C by three kernels -------
 //   k_sgm_prefilter  both images -> their 2 ch planes per pixel (x-Sobel clipped to [0, 2 ft], the intensity; ft in the border columns)
@@ -120,8 +129,8 @@ __global__ __launch_bounds__(256) void k_sgm_cost_b(SgmArgs a, const SgmPair *ta
 // Every c is evaluated once (the bs - 1 columns two neighbouring tiles of SGM_BT_TX columns share: twice): a Birchfield-Tomasi
 // tap is ~13 packed operations per pair of planes, not the one v_sad_u8 k_sgm_cost repeats per block row.
 
-// k_sgm_prefilter: one thread per pixel of one image (blockIdx.z; batched: z = 2 pair + side); a float image is quantised here, once
-__device__ __forceinline__ void sgm_prefilter(const SgmArgs &a, int side)
+// k_sgm_prefilter: one thread per pixel of one image (blockIdx.z = 2 pair + side); a float image is quantised here, once
+__device__ __forceinline__ void sgm_prefilter(const SgmRun &a, int side)
 {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= a.W) return;
@@ -149,8 +158,14 @@ __device__ __forceinline__ void sgm_prefilter(const SgmArgs &a, int side)
     }
 }
 
-__global__ __launch_bounds__(256) void k_sgm_prefilter(SgmArgs a) { sgm_prefilter(a, blockIdx.z); }
-__global__ __launch_bounds__(256) void k_sgm_prefilter_b(SgmArgs a, const SgmPair *tab) { sgm_prefilter(sgm_pair_args(a, tab, blockIdx.z >> 1), blockIdx.z & 1); }
+// (the side's planes go to slot 0 ahead of the body: an index that is known at compile time keeps the assembled record in registers)
+template <typename S>
+__global__ __launch_bounds__(256) void k_sgm_prefilter(SgmArgs a, S src)
+{
+    SgmRun r = sgm_run(src, a, blockIdx.z >> 1);
+    if (blockIdx.z & 1) { r.img[0] = r.img[1]; r.pf[0] = r.pf[1]; }
+    sgm_prefilter(r, 0);
+}
 
 // Two adjacent planes of a pixel travel as the two 16-bit lanes of a dword (planes 2p, 2p + 1: pair p), so that one packed
 // instruction (v_pk_sub_i16, v_pk_max_i16, v_pk_min_i16) serves both; every value is in [-255, 255].
@@ -183,7 +198,7 @@ __device__ __forceinline__ void sgm_bt_stage(const uint8_t *row, int W, int cx, 
 // i has shift 0 below ch (P), 2 from ch on (Q).  The sums go to Hs, or to C itself when BS is 1 (a 1 x 1 block has no vertical sum).
 // WIDE: as k_sgm_cost (static LDS: 46.5 KB at BS 7, NP 3).
 template <int BS, int NP, bool WIDE>
-__device__ __forceinline__ void sgm_bt_rows(const SgmArgs &a)
+__device__ __forceinline__ void sgm_bt_rows(const SgmRun &a)
 {
     uint16_t *const out = BS == 1 ? a.C : a.Hs;
     constexpr int HALF = BS / 2, NL = SGM_BT_TX + BS - 1, NR = NL + (WIDE ? SGM_DMAX : 256) - 1, NQ = 3 * NP;
@@ -233,16 +248,15 @@ __device__ __forceinline__ void sgm_bt_rows(const SgmArgs &a)
     } while (WIDE && (d += 256) < a.Dp);
 }
 
-template <int BS, int NP, bool WIDE> __global__ __launch_bounds__(256) void k_sgm_bt_rows(SgmArgs a) { sgm_bt_rows<BS, NP, WIDE>(a); }
-template <int BS, int NP, bool WIDE>
-__global__ __launch_bounds__(256) void k_sgm_bt_rows_b(SgmArgs a, const SgmPair *tab) { sgm_bt_rows<BS, NP, WIDE>(sgm_pair_args(a, tab, blockIdx.z)); }
+template <int BS, int NP, bool WIDE, typename S>
+__global__ __launch_bounds__(256) void k_sgm_bt_rows(SgmArgs a, S src) { sgm_bt_rows<BS, NP, WIDE>(sgm_run(src, a, blockIdx.z)); }
 
 // The vertical sum: a thread holds four adjacent disparities of one pixel column (8 bytes: Dp is a multiple of 4) and marches
 // down SGM_BT_YS rows; the last BS rows of Hs stay in registers, a step is one load, one add, one subtract and one store.  Two
 // 16-bit sums share a dword: every result is at most 65535 (psm_sgm_set_params), and the 32-bit arithmetic is exact modulo 2^32,
 // so no carry survives between the halves.  Only the BS - 1 rows two segments share are loaded twice.
 template <int BS>
-__device__ __forceinline__ void sgm_bt_cols(const SgmArgs &a)
+__device__ __forceinline__ void sgm_bt_cols(const SgmRun &a)
 {
     constexpr int HALF = BS / 2;
     const size_t rowq = (size_t)a.W * a.Dp / 4;           // uint2 per row
@@ -271,8 +285,7 @@ __device__ __forceinline__ void sgm_bt_cols(const SgmArgs &a)
     }
 }
 
-template <int BS> __global__ __launch_bounds__(256) void k_sgm_bt_cols(SgmArgs a) { sgm_bt_cols<BS>(a); }
-template <int BS> __global__ __launch_bounds__(256) void k_sgm_bt_cols_b(SgmArgs a, const SgmPair *tab) { sgm_bt_cols<BS>(sgm_pair_args(a, tab, blockIdx.z)); }
+template <int BS, typename S> __global__ __launch_bounds__(256) void k_sgm_bt_cols(SgmArgs a, S src) { sgm_bt_cols<BS>(sgm_run(src, a, blockIdx.z)); }
 
 // ---- the census cost (psm_sgm_set_census, tests/sgm_census_model.py): the same C by two kernels ---------------------------------
 //   k_sgm_census       both images -> their code planes T [H][W] uint64: bit i is "tap i of the win_w x win_h window is darker than
@@ -286,11 +299,11 @@ __device__ __forceinline__ unsigned sgm_gray(const void *img, int depth, int ch,
     return ch == 1 ? v : (1868u * (v & 255u) + 9617u * ((v >> 8) & 255u) + 4899u * (v >> 16) + 8192u) >> 14;
 }
 
-// One workgroup per tile of SGM_CEN_TX x SGM_CEN_TY pixels of one image (blockIdx.z; batched: z = 2 pair + side), one pixel per
+// One workgroup per tile of SGM_CEN_TX x SGM_CEN_TY pixels of one image (blockIdx.z = 2 pair + side), one pixel per
 // thread.  The tile's gray values with the window's halo go to LDS as bytes (a float image is quantised here, once); the clamp of
 // a tap is done there.  The two dwords of a code are built separately - a tap sets a bit of one of them - and leave as one 8-byte
 // store.
-__device__ __forceinline__ void sgm_census(const SgmArgs &a, int side)
+__device__ __forceinline__ void sgm_census(const SgmRun &a, int side)
 {
     constexpr int LW = SGM_CEN_TX + SGM_CEN_MAXW - 1, LH = SGM_CEN_TY + SGM_CEN_MAXH - 1;
     __shared__ uint8_t sg[LH * LW];
@@ -321,8 +334,8 @@ __device__ __forceinline__ void sgm_census(const SgmArgs &a, int side)
     ((uint2 *)(side ? a.pf[1] : a.pf[0]))[(size_t)y * a.W + x] = make_uint2(lo, hi);
 }
 
-__global__ __launch_bounds__(256) void k_sgm_census(SgmArgs a) { sgm_census(a, blockIdx.z); }
-__global__ __launch_bounds__(256) void k_sgm_census_b(SgmArgs a, const SgmPair *tab) { sgm_census(sgm_pair_args(a, tab, blockIdx.z >> 1), blockIdx.z & 1); }
+template <typename S>
+__global__ __launch_bounds__(256) void k_sgm_census(SgmArgs a, S src) { sgm_census(sgm_run(src, a, blockIdx.z >> 1), blockIdx.z & 1); }
 
 // k_sgm_cost's shape: one workgroup per SGM_TX pixels of one row, one thread per disparity; the BS rows of both code planes go to
 // LDS as 8-byte words, the left tap is a broadcast, the right taps of neighbouring lanes are neighbouring words; where k_sgm_cost
@@ -331,7 +344,7 @@ __global__ __launch_bounds__(256) void k_sgm_census_b(SgmArgs a, const SgmPair *
 // 256 and the right span is staged again for every pass: NL + 255 columns whatever D is (static LDS: 18.1 KB at BS 7, where one
 // span for all 1024 disparities would be 61.5 KB and leave a CU one workgroup).
 template <int BS>
-__device__ __forceinline__ void sgm_census_cost(const SgmArgs &a)
+__device__ __forceinline__ void sgm_census_cost(const SgmRun &a)
 {
     constexpr int HALF = BS / 2, NL = SGM_TX + BS - 1, NR = NL + 255;
     __shared__ uint2 sl[BS][NL], sr[BS][NR];
@@ -382,8 +395,7 @@ __device__ __forceinline__ void sgm_census_cost(const SgmArgs &a)
     }
 }
 
-template <int BS> __global__ __launch_bounds__(256) void k_sgm_census_cost(SgmArgs a) { sgm_census_cost<BS>(a); }
-template <int BS> __global__ __launch_bounds__(256) void k_sgm_census_cost_b(SgmArgs a, const SgmPair *tab) { sgm_census_cost<BS>(sgm_pair_args(a, tab, blockIdx.z)); }
+template <int BS, typename S> __global__ __launch_bounds__(256) void k_sgm_census_cost(SgmArgs a, S src) { sgm_census_cost<BS>(sgm_run(src, a, blockIdx.z)); }
 
 // NV adjacent disparities per lane: what a lane moves per pixel, and U, the steps of k_sgm_path whose loads are issued together.
 // NV U is constant from NV 4 on: the look-ahead of the wide forms (NV 8, 16: Dp up to 512, 1024) holds the 2 U (NV / 2 + NV) = 96
@@ -431,7 +443,7 @@ __host__ __device__ inline int sgm_npaths(int W, int H, int dy, int dx) { return
 // Within a direction every voxel lies on exactly one path and the launches of a frame follow each other on one stream: S is
 // updated with plain loads and stores, no atomics.
 template <int NV, bool FIRST, bool ALL>
-__device__ __forceinline__ void sgm_path(const SgmArgs &a, int dy, int dx)
+__device__ __forceinline__ void sgm_path(const SgmRun &a, int dy, int dx)
 {
     using CV = typename SgmVec<NV>::C;
     using SV = typename SgmVec<NV>::S;
@@ -509,17 +521,15 @@ __device__ __forceinline__ void sgm_path(const SgmArgs &a, int dy, int dx)
     run(cv[1], sv[1], i + U, std::false_type{});
 }
 
-template <int NV, bool FIRST, bool ALL>
-__global__ __launch_bounds__(256) void k_sgm_path(SgmArgs a, int dy, int dx) { sgm_path<NV, FIRST, ALL>(a, dy, dx); }
-// n x (H, W or W + H - 1) one-wave paths per launch: what hides a path's dependent chain is other pairs' waves on the same SIMD
-template <int NV, bool FIRST, bool ALL>
-__global__ __launch_bounds__(256) void k_sgm_path_b(SgmArgs a, const SgmPair *tab, int dy, int dx) { sgm_path<NV, FIRST, ALL>(sgm_pair_args(a, tab, blockIdx.z), dy, dx); }
+// a batch: n x (H, W or W + H - 1) one-wave paths per launch - what hides a path's dependent chain is other pairs' waves on the same SIMD
+template <int NV, bool FIRST, bool ALL, typename S>
+__global__ __launch_bounds__(256) void k_sgm_path(SgmArgs a, S src, int dy, int dx) { sgm_path<NV, FIRST, ALL>(sgm_run(src, a, blockIdx.z), dy, dx); }
 
 // One wave per pixel: the packed (S << KB | d) minimum over the wave is argmin with the lowest d on ties (S < 2^19: at most
 // 8 * 65535 = 524280, which tests/test_gpu_sgm_fuzz.py::test_saturating_pairs_reach_the_packing_bound reaches).  KB is 8 up to 256
 // disparities, 10 above (29 bits).  d is the index; the disparity is dmin + d in d16 and in the landing column.
 template <int NV>
-__device__ __forceinline__ void sgm_select(const SgmArgs &a)
+__device__ __forceinline__ void sgm_select(const SgmRun &a)
 {
     using SV = typename SgmVec<NV>::S;
     constexpr int KB = NV > 4 ? 10 : 8;                            // = sgm_kb(Dp): NV > 4 is Dp > 256
@@ -558,8 +568,7 @@ __device__ __forceinline__ void sgm_select(const SgmArgs &a)
     if (unique && xl >= 0 && xl < a.W) atomicMin(a.disp2 + (size_t)y * a.W + xl, (unsigned)kmin);
 }
 
-template <int NV> __global__ __launch_bounds__(256) void k_sgm_select(SgmArgs a) { sgm_select<NV>(a); }
-template <int NV> __global__ __launch_bounds__(256) void k_sgm_select_b(SgmArgs a, const SgmPair *tab) { sgm_select<NV>(sgm_pair_args(a, tab, blockIdx.z)); }
+template <int NV, typename S> __global__ __launch_bounds__(256) void k_sgm_select(SgmArgs a, S src) { sgm_select<NV>(sgm_run(src, a, blockIdx.z)); }
 
 // a packed minimum's disparity: dmin + its index bits (mask)
 __device__ __forceinline__ bool sgm_bad_probe(const unsigned *row, int W, int xq, int dq, int m, int dmin, unsigned mask)
@@ -571,7 +580,7 @@ __device__ __forceinline__ bool sgm_bad_probe(const unsigned *row, int W, int xq
     return (t < 0 ? -t : t) > m;
 }
 
-__device__ __forceinline__ void sgm_check(const SgmArgs &a)
+__device__ __forceinline__ void sgm_check(const SgmRun &a)
 {
     const int pix = blockIdx.x * 256 + threadIdx.x;
     if (pix >= a.W * a.H) return;
@@ -586,11 +595,10 @@ __device__ __forceinline__ void sgm_check(const SgmArgs &a)
     a.out[pix] = (int16_t)v;
 }
 
-__global__ __launch_bounds__(256) void k_sgm_check(SgmArgs a) { sgm_check(a); }
-__global__ __launch_bounds__(256) void k_sgm_check_b(SgmArgs a, const SgmPair *tab) { sgm_check(sgm_pair_args(a, tab, blockIdx.z)); }
+template <typename S> __global__ __launch_bounds__(256) void k_sgm_check(SgmArgs a, S src) { sgm_check(sgm_run(src, a, blockIdx.z)); }
 
 // disp2 of every pair of a batch: "nothing lands here" (the single pair's is a hipMemsetAsync)
-__global__ __launch_bounds__(256) void k_sgm_fill_b(SgmArgs a, const SgmPair *tab)
+__global__ __launch_bounds__(256) void k_sgm_fill(SgmArgs a, const SgmPair *tab)
 {
     const int pix = blockIdx.x * 256 + threadIdx.x;
     if (pix < a.W * a.H) sgm_global(tab[blockIdx.z].disp2)[pix] = 0xffffffffu;
@@ -598,7 +606,7 @@ __global__ __launch_bounds__(256) void k_sgm_fill_b(SgmArgs a, const SgmPair *ta
 
 void launch_sgm_fill_batch(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
 {
-    hipLaunchKernelGGL(k_sgm_fill_b, dim3((a.W * a.H + 255) / 256, 1, n), dim3(256), 0, s, a, tab);
+    hipLaunchKernelGGL(k_sgm_fill, dim3((a.W * a.H + 255) / 256, 1, n), dim3(256), 0, s, a, tab);
 }
 
 // one thread per disparity up to 256 of them; above, 256 threads that each take every 256th (the WIDE forms)
@@ -621,40 +629,48 @@ static void sgm_with_bs(int bs, bool wide, F f)
     }
 }
 
-void launch_sgm_cost(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
+// one launch over the pairs of q (psm_kernels.h, rec_launch): the pairs - times `per`, the images of a pair - on grid axis z
+template <typename... A>
+static void sgm_launch(hipStream_t s, void (*kv)(SgmArgs, SgmV, A...), void (*kt)(SgmArgs, SgmT, A...), dim3 grid, dim3 block, const SgmArgs &a,
+                       const Recs<SgmPair> &q, int per, A... rest)
+{
+    rec_launch(s, kv, kt, dim3(grid.x, grid.y, (unsigned)(per * q.n)), block, 0, a, q, rest...);
+}
+
+void launch_sgm_cost(hipStream_t s, const SgmArgs &a, const Recs<SgmPair> &q)
 {
     const dim3 grid((a.W + SGM_TX - 1) / SGM_TX, a.H), block(sgm_cost_threads(a.D));
     sgm_with_bs(a.bs, a.D > 256, [&](auto bs, auto wide) {
         constexpr int BS = decltype(bs)::value;
         constexpr bool WIDE = decltype(wide)::value;
-        sgm_launch(s, k_sgm_cost<BS, WIDE>, k_sgm_cost_b<BS, WIDE>, grid, block, a, tab, n);
+        sgm_launch(s, k_sgm_cost<BS, WIDE, SgmV>, k_sgm_cost<BS, WIDE, SgmT>, grid, block, a, q, 1);
     });
 }
 
-void launch_sgm_cost_bt(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
+void launch_sgm_cost_bt(hipStream_t s, const SgmArgs &a, const Recs<SgmPair> &q)
 {
-    sgm_launch(s, k_sgm_prefilter, k_sgm_prefilter_b, dim3((a.W + 255) / 256, a.H, 2), dim3(256), a, tab, 2 * n);
+    sgm_launch(s, k_sgm_prefilter<SgmV>, k_sgm_prefilter<SgmT>, dim3((a.W + 255) / 256, a.H), dim3(256), a, q, 2);
     const dim3 grid((a.W + SGM_BT_TX - 1) / SGM_BT_TX, a.H), block(sgm_cost_threads(a.D));
     sgm_with_bs(a.bs, a.D > 256, [&](auto bs, auto wide) {
         constexpr int BS = decltype(bs)::value;
         constexpr bool WIDE = decltype(wide)::value;
-        if (a.ch == 1) sgm_launch(s, k_sgm_bt_rows<BS, 1, WIDE>, k_sgm_bt_rows_b<BS, 1, WIDE>, grid, block, a, tab, n);
-        else sgm_launch(s, k_sgm_bt_rows<BS, 3, WIDE>, k_sgm_bt_rows_b<BS, 3, WIDE>, grid, block, a, tab, n);
+        if (a.ch == 1) sgm_launch(s, k_sgm_bt_rows<BS, 1, WIDE, SgmV>, k_sgm_bt_rows<BS, 1, WIDE, SgmT>, grid, block, a, q, 1);
+        else sgm_launch(s, k_sgm_bt_rows<BS, 3, WIDE, SgmV>, k_sgm_bt_rows<BS, 3, WIDE, SgmT>, grid, block, a, q, 1);
         if constexpr (BS > 1) {
             const size_t rowq = (size_t)a.W * a.Dp / 4;
-            sgm_launch(s, k_sgm_bt_cols<BS>, k_sgm_bt_cols_b<BS>, dim3((unsigned)((rowq + 255) / 256), (a.H + SGM_BT_YS - 1) / SGM_BT_YS), dim3(256), a, tab, n);
+            sgm_launch(s, k_sgm_bt_cols<BS, SgmV>, k_sgm_bt_cols<BS, SgmT>, dim3((unsigned)((rowq + 255) / 256), (a.H + SGM_BT_YS - 1) / SGM_BT_YS), dim3(256), a, q, 1);
         }
     });
 }
 
-void launch_sgm_cost_census(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
+void launch_sgm_cost_census(hipStream_t s, const SgmArgs &a, const Recs<SgmPair> &q)
 {
-    sgm_launch(s, k_sgm_census, k_sgm_census_b, dim3((a.W + SGM_CEN_TX - 1) / SGM_CEN_TX, (a.H + SGM_CEN_TY - 1) / SGM_CEN_TY, 2),
-               dim3(SGM_CEN_TX * SGM_CEN_TY), a, tab, 2 * n);
+    sgm_launch(s, k_sgm_census<SgmV>, k_sgm_census<SgmT>, dim3((a.W + SGM_CEN_TX - 1) / SGM_CEN_TX, (a.H + SGM_CEN_TY - 1) / SGM_CEN_TY),
+               dim3(SGM_CEN_TX * SGM_CEN_TY), a, q, 2);
     const dim3 grid((a.W + SGM_TX - 1) / SGM_TX, a.H), block(sgm_cost_threads(a.D));
     sgm_with_bs(a.bs, false, [&](auto bs, auto) {              // (one form whatever D is: the passes are the kernel's own)
         constexpr int BS = decltype(bs)::value;
-        sgm_launch(s, k_sgm_census_cost<BS>, k_sgm_census_cost_b<BS>, grid, block, a, tab, n);
+        sgm_launch(s, k_sgm_census_cost<BS, SgmV>, k_sgm_census_cost<BS, SgmT>, grid, block, a, q, 1);
     });
 }
 
@@ -669,27 +685,27 @@ static void sgm_with_nv(int Dp, F f)
     else f(std::integral_constant<int, 16>{});
 }
 
-void launch_sgm_path(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first, const SgmPair *tab, int n)
+void launch_sgm_path(hipStream_t s, const SgmArgs &a, int dy, int dx, bool first, const Recs<SgmPair> &q)
 {
     const dim3 grid((sgm_npaths(a.W, a.H, dy, dx) + 3) / 4), block(256);
     sgm_with_nv(a.Dp, [&](auto nv) {
         constexpr int NV = decltype(nv)::value;
         const bool all = a.Dp == 64 * NV;
-        if (first && all) sgm_launch(s, k_sgm_path<NV, true, true>, k_sgm_path_b<NV, true, true>, grid, block, a, tab, n, dy, dx);
-        else if (first) sgm_launch(s, k_sgm_path<NV, true, false>, k_sgm_path_b<NV, true, false>, grid, block, a, tab, n, dy, dx);
-        else if (all) sgm_launch(s, k_sgm_path<NV, false, true>, k_sgm_path_b<NV, false, true>, grid, block, a, tab, n, dy, dx);
-        else sgm_launch(s, k_sgm_path<NV, false, false>, k_sgm_path_b<NV, false, false>, grid, block, a, tab, n, dy, dx);
+        if (first && all) sgm_launch(s, k_sgm_path<NV, true, true, SgmV>, k_sgm_path<NV, true, true, SgmT>, grid, block, a, q, 1, dy, dx);
+        else if (first) sgm_launch(s, k_sgm_path<NV, true, false, SgmV>, k_sgm_path<NV, true, false, SgmT>, grid, block, a, q, 1, dy, dx);
+        else if (all) sgm_launch(s, k_sgm_path<NV, false, true, SgmV>, k_sgm_path<NV, false, true, SgmT>, grid, block, a, q, 1, dy, dx);
+        else sgm_launch(s, k_sgm_path<NV, false, false, SgmV>, k_sgm_path<NV, false, false, SgmT>, grid, block, a, q, 1, dy, dx);
     });
 }
 
-void launch_sgm_select(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int n)
+void launch_sgm_select(hipStream_t s, const SgmArgs &a, const Recs<SgmPair> &q)
 {
     const int HW = a.W * a.H;
     sgm_with_nv(a.Dp, [&](auto nv) {
         constexpr int NV = decltype(nv)::value;
-        sgm_launch(s, k_sgm_select<NV>, k_sgm_select_b<NV>, dim3((HW + 3) / 4), dim3(256), a, tab, n);
+        sgm_launch(s, k_sgm_select<NV, SgmV>, k_sgm_select<NV, SgmT>, dim3((HW + 3) / 4), dim3(256), a, q, 1);
     });
-    sgm_launch(s, k_sgm_check, k_sgm_check_b, dim3((HW + 255) / 256), dim3(256), a, tab, n);
+    sgm_launch(s, k_sgm_check<SgmV>, k_sgm_check<SgmT>, dim3((HW + 255) / 256), dim3(256), a, q, 1);
 }
 
 // ---- the 8-bit maps of both views from S (psm_sgm_select_maps, tests/sgm_maps_model.py) -----------------------------------------
@@ -709,7 +725,7 @@ void launch_sgm_select(hipStream_t s, const SgmArgs &a, const SgmPair *tab, int 
 constexpr int SGM_MAPS_WAVES = 8, SGM_MAPS_U = 4;
 
 template <int NV>
-__device__ __forceinline__ void sgm_maps(const SgmArgs &a, uint8_t *maps)
+__device__ __forceinline__ void sgm_maps(const SgmRun &a, uint8_t *maps)
 {
     extern __shared__ unsigned sgm_maps_lds[];
     unsigned *rkey = sgm_maps_lds;                                 // [W] the right view's packed minima
@@ -758,24 +774,23 @@ __device__ __forceinline__ void sgm_maps(const SgmArgs &a, uint8_t *maps)
     }
 }
 
-template <int NV> __global__ __launch_bounds__(SGM_MAPS_WAVES * 64) void k_sgm_maps(SgmArgs a, uint8_t *maps) { sgm_maps<NV>(a, maps); }
-template <int NV>
-__global__ __launch_bounds__(SGM_MAPS_WAVES * 64) void k_sgm_maps_b(SgmArgs a, const SgmPair *tab)
+template <int NV, typename S>
+__global__ __launch_bounds__(SGM_MAPS_WAVES * 64) void k_sgm_maps(SgmArgs a, S src)
 {
-    sgm_maps<NV>(sgm_pair_args(a, tab, blockIdx.z), sgm_global(tab[blockIdx.z].maps));
+    const SgmRun r = sgm_run(src, a, blockIdx.z);
+    sgm_maps<NV>(r, r.maps);
 }
 
 size_t sgm_maps_lds_bytes(int W) { return (size_t)W * 5; }
 
-// one workgroup per image row (a batch: the pair on grid axis z)
-void launch_sgm_maps(hipStream_t s, const SgmArgs &a, uint8_t *maps, const SgmPair *tab, int n)
+// one workgroup per image row, the pair on grid axis z
+void launch_sgm_maps(hipStream_t s, const SgmArgs &a, const Recs<SgmPair> &q)
 {
     const dim3 block(SGM_MAPS_WAVES * 64);
     const size_t lds = sgm_maps_lds_bytes(a.W);
     auto go = [&](auto nv) {
         constexpr int NV = decltype(nv)::value;
-        if (tab) hipLaunchKernelGGL(k_sgm_maps_b<NV>, dim3(a.H, 1, n), block, lds, s, a, tab);
-        else hipLaunchKernelGGL(k_sgm_maps<NV>, dim3(a.H), block, lds, s, a, maps);
+        rec_launch(s, k_sgm_maps<NV, SgmV>, k_sgm_maps<NV, SgmT>, dim3(a.H, 1, q.n), block, lds, a, q);
     };
     if (a.Dp <= 64) go(std::integral_constant<int, 1>{});
     else if (a.Dp <= 128) go(std::integral_constant<int, 2>{});

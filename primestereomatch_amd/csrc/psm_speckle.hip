@@ -52,11 +52,18 @@ __device__ __forceinline__ void spk_union(unsigned *label, unsigned a, unsigned 
     }
 }
 
+// What a body takes: the call's scalars and the planes of one pair - map [H][W], filtered in place; label and size as psm_kernels.h
+// has them (SgmPair's out, spk_label, spk_size)
+struct SpkRun : SpkArgs {
+    int16_t *map;
+    unsigned *label, *size;
+};
+
 // One wave per row, 64 pixels at a time.  A pixel starts a run if it is a vertex and does not connect to its left neighbour; the
 // ballot of the starts and a bit scan give every lane its run's first pixel, a run that began in an earlier piece is carried in
 // `carry`.  The last pixel of a run writes the run's length to size[head].  All horizontal structure is flat before the first
 // atomic is issued.
-__device__ __forceinline__ void spk_runs(const SpkArgs &a)
+__device__ __forceinline__ void spk_runs(const SpkRun &a)
 {
     const int lane = threadIdx.x & 63;
     const int y = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -87,7 +94,7 @@ __device__ __forceinline__ void spk_runs(const SpkArgs &a)
 
 // One thread per pixel below the first row: its edge to the pixel above.  Skipped when the left neighbour is in the same run, has
 // an edge of its own to the pixel above it and that pixel is in the same run as ours above: the edge would join the same two runs.
-__device__ __forceinline__ void spk_merge(const SpkArgs &a)
+__device__ __forceinline__ void spk_merge(const SpkRun &a)
 {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y + 1;
     if (x >= a.W) return;
@@ -104,7 +111,7 @@ __device__ __forceinline__ void spk_merge(const SpkArgs &a)
 // One thread per pixel, run heads act.  After k_spk_merge the labels are final (a launch of its own on the same stream), so find
 // gives the true root; writing it back only shortens chains other threads walk (either value leads to the same root).  Only roots
 // receive adds and only heads that are no roots read their own size: a size is an exact integer sum, whatever the arrival order.
-__device__ __forceinline__ void spk_count(const SpkArgs &a)
+__device__ __forceinline__ void spk_count(const SpkRun &a)
 {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= a.W) return;
@@ -120,7 +127,7 @@ __device__ __forceinline__ void spk_count(const SpkArgs &a)
 
 // One thread per pixel.  size[p] is rewritten in place with the size of p's component: the only entries other threads read here
 // are those of roots, and a root writes the value it already holds.
-__device__ __forceinline__ void spk_apply(const SpkArgs &a)
+__device__ __forceinline__ void spk_apply(const SpkRun &a)
 {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= a.W) return;
@@ -134,31 +141,33 @@ __device__ __forceinline__ void spk_apply(const SpkArgs &a)
     a.size[p] = s;
 }
 
-// Every kernel is its body behind two entries: the map of `a`, or - several maps of one size per launch (psm_sgm_compute_batch) -
-// the planes of pair blockIdx.z of the device table, read into the same SpkArgs (uniform per workgroup).  Labels and sizes are
-// pixel indices within a pair's own planes.
-__device__ __forceinline__ SpkArgs spk_pair_args(SpkArgs a, const SgmPair *tab, unsigned pair)
+// Every kernel is its body behind an entry that is a template over the record source S (psm_kernels.h, Recs): the pair of a single
+// call by value, or - several maps of one size per launch (psm_sgm_compute_batch) - pair blockIdx.z of the device table; its planes
+// are read as global pointers (uniform per workgroup).  Labels and sizes are pixel indices within a pair's own planes.
+template <typename S>
+__device__ __forceinline__ SpkRun spk_run(const S &src, const SpkArgs &a, unsigned pair)
 {
-    const SgmPair &p = tab[pair];
-    a.map = sgm_global(p.out); a.label = sgm_global(p.spk_label); a.size = sgm_global(p.spk_size);
-    return a;
+    const SgmPair &p = rec(src, pair);
+    SpkRun r;
+    static_cast<SpkArgs &>(r) = a;
+    r.map = sgm_global(p.out); r.label = sgm_global(p.spk_label); r.size = sgm_global(p.spk_size);
+    return r;
 }
-__global__ __launch_bounds__(256) void k_spk_runs(SpkArgs a) { spk_runs(a); }
-__global__ __launch_bounds__(256) void k_spk_merge(SpkArgs a) { spk_merge(a); }
-__global__ __launch_bounds__(256) void k_spk_count(SpkArgs a) { spk_count(a); }
-__global__ __launch_bounds__(256) void k_spk_apply(SpkArgs a) { spk_apply(a); }
-__global__ __launch_bounds__(256) void k_spk_runs_b(SpkArgs a, const SgmPair *tab) { spk_runs(spk_pair_args(a, tab, blockIdx.z)); }
-__global__ __launch_bounds__(256) void k_spk_merge_b(SpkArgs a, const SgmPair *tab) { spk_merge(spk_pair_args(a, tab, blockIdx.z)); }
-__global__ __launch_bounds__(256) void k_spk_count_b(SpkArgs a, const SgmPair *tab) { spk_count(spk_pair_args(a, tab, blockIdx.z)); }
-__global__ __launch_bounds__(256) void k_spk_apply_b(SpkArgs a, const SgmPair *tab) { spk_apply(spk_pair_args(a, tab, blockIdx.z)); }
+template <typename S> __global__ __launch_bounds__(256) void k_spk_runs(SpkArgs a, S src) { spk_runs(spk_run(src, a, blockIdx.z)); }
+template <typename S> __global__ __launch_bounds__(256) void k_spk_merge(SpkArgs a, S src) { spk_merge(spk_run(src, a, blockIdx.z)); }
+template <typename S> __global__ __launch_bounds__(256) void k_spk_count(SpkArgs a, S src) { spk_count(spk_run(src, a, blockIdx.z)); }
+template <typename S> __global__ __launch_bounds__(256) void k_spk_apply(SpkArgs a, S src) { spk_apply(spk_run(src, a, blockIdx.z)); }
 
-void launch_speckle(hipStream_t s, const SpkArgs &a, const SgmPair *tab, int n)
+void launch_speckle(hipStream_t s, const SpkArgs &a, const Recs<SgmPair> &q)
 {
-    const dim3 block(256), rows((a.W + 255) / 256, a.H);
-    sgm_launch(s, k_spk_runs, k_spk_runs_b, dim3((a.H + 3) / 4), block, a, tab, n);
-    if (a.H > 1) sgm_launch(s, k_spk_merge, k_spk_merge_b, dim3(rows.x, a.H - 1), block, a, tab, n);
-    sgm_launch(s, k_spk_count, k_spk_count_b, rows, block, a, tab, n);
-    sgm_launch(s, k_spk_apply, k_spk_apply_b, rows, block, a, tab, n);
+    using V = RecVal<SgmPair>;
+    using T = RecTab<SgmPair>;
+    const unsigned n = (unsigned)q.n;
+    const dim3 block(256), rows((a.W + 255) / 256, a.H, n);
+    rec_launch(s, k_spk_runs<V>, k_spk_runs<T>, dim3((a.H + 3) / 4, 1, n), block, 0, a, q);
+    if (a.H > 1) rec_launch(s, k_spk_merge<V>, k_spk_merge<T>, dim3(rows.x, a.H - 1, n), block, 0, a, q);
+    rec_launch(s, k_spk_count<V>, k_spk_count<T>, rows, block, 0, a, q);
+    rec_launch(s, k_spk_apply<V>, k_spk_apply<T>, rows, block, 0, a, q);
 }
 
 }  // namespace psm

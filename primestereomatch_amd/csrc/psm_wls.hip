@@ -3,8 +3,8 @@
 // separable tridiagonal solves along rows and columns, guided by the left image.  It follows no library's convention: the
 // definition is tests/wls_model.py, the device equals it in every bit.  fp32, every operation rounded on its own
 // (the file is built without contraction), IEEE division, subnormals kept.
-// Launches, whatever the data - 1 + 2 T of them, for one pair or for the pairs of a batch (k_wls_*_b: the same device bodies, the
-// member on grid axis y, its record - pointers, table, the lambdas of its passes - in a device table):
+// Launches, whatever the data - 1 + 2 T of them, for one pair or for the pairs of a batch (the same kernels, the member on grid
+// axis y, its record - pointers, table, the lambdas of its passes - by value or in a device table):
 //   k_wls_init  one pixel per lane: num and den from the source map, the link indices kh and kv from the guide
 //   k_wls_rows  one pass over every row.  One lane owns one line and walks it, a wave holds WLS_LINES lines.  Lanes a row pitch
 //               apart would fetch a cache line per lane and step, so the WLS_LINES x WLS_STEPS tiles travel through LDS: the four
@@ -31,11 +31,13 @@ __device__ __forceinline__ void wls_forward(float am, float c, float v, float d,
     dp = __fmul_rn(__fsub_rn(d, __fmul_rn(dp, am)), r);
 }
 
-// A member of a batch: its record of the device table, the pointers in it read as global ones (sgm_global, psm_kernels.h).  The
-// member index is the workgroup's grid y, so the record arrives through scalar loads ahead of the body.
-__device__ __forceinline__ WlsArgs wls_pair_args(const WlsPair *tab, unsigned pair)
+// The record of a workgroup from either source S (psm_kernels.h, Recs) - a single call's by value, or member blockIdx.y of a batch's
+// device table - with the pointers in it read as global ones.  The index is uniform, so the record arrives through scalar loads
+// ahead of the body.
+template <typename S>
+__device__ __forceinline__ WlsArgs wls_pair(const S &src)
 {
-    const WlsArgs &p = tab[pair].a;
+    const WlsArgs &p = rec(src, blockIdx.y).a;
     WlsArgs a = p;
     a.map = sgm_global(p.map); a.valid = sgm_global(p.valid); a.d16 = sgm_global(p.d16); a.img = sgm_global(p.img);
     a.num = sgm_global(p.num); a.den = sgm_global(p.den); a.cp = sgm_global(p.cp); a.np = sgm_global(p.np); a.dp = sgm_global(p.dp);
@@ -302,37 +304,31 @@ __device__ __forceinline__ void wls_cols(WlsArgs a, float lam, int last)
     }
 }
 
-// The plain entries take the pair's record and the pass's lambda by value; the batch entries take the member's record from the device
-// table (grid y = member) and the lambda of pass t from it: every member has its own lambda and sigma.
-__global__ __launch_bounds__(WLS_TILE) void k_wls_init(WlsArgs a) { wls_init(a); }
-__global__ __launch_bounds__(WLS_TILE) void k_wls_init_b(const WlsPair *tab) { wls_init(wls_pair_args(tab, blockIdx.y)); }
-__global__ __launch_bounds__(WLS_ROW_THREADS) void k_wls_rows(WlsArgs a, float lam) { wls_rows(a, lam); }
-__global__ __launch_bounds__(WLS_ROW_THREADS) void k_wls_rows_b(const WlsPair *tab, int t) { wls_rows(wls_pair_args(tab, blockIdx.y), tab[blockIdx.y].lam[t]); }
-__global__ __launch_bounds__(WLS_LINES) void k_wls_cols(WlsArgs a, float lam, int last) { wls_cols(a, lam, last); }
-__global__ __launch_bounds__(WLS_LINES) void k_wls_cols_b(const WlsPair *tab, int t, int last)
-{
-    wls_cols(wls_pair_args(tab, blockIdx.y), tab[blockIdx.y].lam[t], last);
-}
+// The lambda of pass t is the record's own lam[t]: every member of a batch has its own lambda and sigma.
+template <typename S> __global__ __launch_bounds__(WLS_TILE) void k_wls_init(S src) { wls_init(wls_pair(src)); }
+template <typename S>
+__global__ __launch_bounds__(WLS_ROW_THREADS) void k_wls_rows(S src, int t) { wls_rows(wls_pair(src), rec(src, blockIdx.y).lam[t]); }
+template <typename S>
+__global__ __launch_bounds__(WLS_LINES) void k_wls_cols(S src, int t, int last) { wls_cols(wls_pair(src), rec(src, blockIdx.y).lam[t], last); }
 
-void launch_wls_init(hipStream_t s, const WlsArgs &a, const WlsPair *tab, int n)
+using WlsV = RecVal<WlsPair>;
+using WlsT = RecTab<WlsPair>;
+
+void launch_wls_init(hipStream_t s, const Recs<WlsPair> &q)
 {
+    const WlsArgs &a = q.host[0].a;
     const unsigned blocks = (unsigned)(((size_t)a.W * a.H + WLS_TILE - 1) / WLS_TILE);
-    if (tab) hipLaunchKernelGGL(k_wls_init_b, dim3(blocks, (unsigned)n), dim3(WLS_TILE), 0, s, tab);
-    else hipLaunchKernelGGL(k_wls_init, dim3(blocks), dim3(WLS_TILE), 0, s, a);
+    rec_launch(s, k_wls_init<WlsV>, k_wls_init<WlsT>, dim3(blocks, (unsigned)q.n), dim3(WLS_TILE), 0, q);
 }
 
-void launch_wls_rows(hipStream_t s, const WlsArgs &a, float lam, int t, const WlsPair *tab, int n)
+void launch_wls_rows(hipStream_t s, const Recs<WlsPair> &q, int t)
 {
-    const unsigned groups = (unsigned)wls_groups(a.H);
-    if (tab) hipLaunchKernelGGL(k_wls_rows_b, dim3(groups, (unsigned)n), dim3(WLS_ROW_THREADS), 0, s, tab, t);
-    else hipLaunchKernelGGL(k_wls_rows, dim3(groups), dim3(WLS_ROW_THREADS), 0, s, a, lam);
+    rec_launch(s, k_wls_rows<WlsV>, k_wls_rows<WlsT>, dim3((unsigned)wls_groups(q.host[0].a.H), (unsigned)q.n), dim3(WLS_ROW_THREADS), 0, q, t);
 }
 
-void launch_wls_cols(hipStream_t s, const WlsArgs &a, float lam, int t, bool last, const WlsPair *tab, int n)
+void launch_wls_cols(hipStream_t s, const Recs<WlsPair> &q, int t, bool last)
 {
-    const unsigned groups = (unsigned)wls_groups(a.W);
-    if (tab) hipLaunchKernelGGL(k_wls_cols_b, dim3(groups, (unsigned)n), dim3(WLS_LINES), 0, s, tab, t, last ? 1 : 0);
-    else hipLaunchKernelGGL(k_wls_cols, dim3(groups), dim3(WLS_LINES), 0, s, a, lam, last ? 1 : 0);
+    rec_launch(s, k_wls_cols<WlsV>, k_wls_cols<WlsT>, dim3((unsigned)wls_groups(q.host[0].a.W), (unsigned)q.n), dim3(WLS_LINES), 0, q, t, last ? 1 : 0);
 }
 
 }  // namespace psm

@@ -14,7 +14,8 @@ JSON line per size and iteration count, and the same lines into profiles/wls_ben
 1920 x 1080 of 1 and 2, every member with a map of its own; the lines are appended to profiles/wls_bench.txt as a new block.
 
   batch_ms_per_pair     device time of the 1 + 2 T launches of one psm_wls_filter_batch (PSM_OPT_PROFILE on its first context:
-                        k_wls_init_b, k_wls_rows_b, k_wls_cols_b) over the number of pairs; best of --reps
+                        the instantiations of k_wls_init, k_wls_rows, k_wls_cols over the device table - k_wls_*_b in the blocks
+                        recorded before they were templates) over the number of pairs; best of --reps
   singles_ms_per_pair   the same number of psm_wls_filter calls one after the other: the sum of their kernels_ms over the number
                         of pairs (the gaps between the calls are not in it); best of --reps
   single_ms             the single call of context 0 alone: kernels_ms of the default mode, the figure to set against the

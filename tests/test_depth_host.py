@@ -30,9 +30,17 @@ def test_library_exports_the_symbols(built):
     out = subprocess.run(["nm", "-D", "--defined-only", built.LIB_PATH], capture_output=True, text=True, check=True).stdout
     for name in NAMES:
         assert re.search(rf"\bT {name}\b", out), name
+    # the stage's own device code: every kernel is a template over the record source, and both instantiations - the record by
+    # value (RecVal<DpArgs, 1>) and the device table (const DpArgs *) - are in the symbol table and in the code object
     blob = open(built.LIB_PATH, "rb").read()
-    for kernel in ("k_dp_count", "k_dp_scan", "k_dp_pack", "k_dp_count_b", "k_dp_scan_b", "k_dp_pack_b"):      # the stage's own device code
-        assert kernel.encode() in blob, kernel
+    for kernel in ("k_dp_count", "k_dp_scan", "k_dp_pack"):
+        stem = rf"_ZN3psm{len(kernel)}{kernel}I"
+        by_value = re.search(rf"\bV ({stem}NS_6RecValINS_6DpArgsELi1EEEEEv\w+)$", out, re.M)
+        table = re.search(rf"\bV ({stem}PKNS_6DpArgsEEEv\w+)$", out, re.M)
+        assert by_value and table, kernel
+        assert by_value.group(1) != table.group(1)
+        for sym in (by_value.group(1), table.group(1)):
+            assert (sym + ".kd").encode() in blob, sym
 
 
 def test_capi_declares_them_and_the_record(built):

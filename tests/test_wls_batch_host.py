@@ -27,9 +27,17 @@ def built():
 def test_library_exports_the_symbol_and_holds_the_kernels(built):
     out = subprocess.run(["nm", "-D", "--defined-only", built.LIB_PATH], capture_output=True, text=True, check=True).stdout
     assert re.search(rf"\bT {NAME}\b", out)
+    # every kernel is a template over the record source: both instantiations - the record by value (RecVal<WlsPair, 1>, the single
+    # call) and the device table (const WlsPair *, the batch) - are in the symbol table and in the code object
     blob = open(built.LIB_PATH, "rb").read()
-    for kernel in ("k_wls_init_b", "k_wls_rows_b", "k_wls_cols_b"):
-        assert kernel.encode() in blob, kernel
+    for kernel in ("k_wls_init", "k_wls_rows", "k_wls_cols"):
+        stem = rf"_ZN3psm{len(kernel)}{kernel}I"
+        by_value = re.search(rf"\bV ({stem}NS_6RecValINS_7WlsPairELi1EEEEEv\w+)$", out, re.M)
+        table = re.search(rf"\bV ({stem}PKNS_7WlsPairEEEv\w+)$", out, re.M)
+        assert by_value and table, kernel
+        assert by_value.group(1) != table.group(1)
+        for sym in (by_value.group(1), table.group(1)):
+            assert (sym + ".kd").encode() in blob, sym
 
 
 def test_capi_declares_it(built):
@@ -123,7 +131,7 @@ def test_the_header_and_the_documents_carry_the_call():
     text = open(os.path.join(ROOT, "include", "primesm_hip.h")).read()
     assert re.search(r"int psm_wls_filter_batch\(psm_ctx \*const \*ctxs, int n, int source, int flags\);", text)
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
-    for phrase in (NAME, "k_wls_init_b", "k_wls_rows_b", "k_wls_cols_b", "WlsPair"):
+    for phrase in (NAME, "k_wls_init", "k_wls_rows", "k_wls_cols", "WlsPair", "Recs<WlsPair>"):
         assert phrase in design, phrase
     assert NAME in open(os.path.join(ROOT, "README.md")).read()
     assert NAME in open(os.path.join(ROOT, "INTEGRATION.md")).read()
