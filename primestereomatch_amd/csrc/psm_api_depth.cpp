@@ -3,7 +3,8 @@
 // coloured point cloud.  Kernels: psm_depth.hip.  The definition is tests/depth_model.py / DESIGN.md 12.  An independent stage, as
 // psm_score is: it reads the context's current result - the left map and its mask through psm::Results, the int16 map the SGM
 // sources of psm_score read - and the left image of the pair, and writes its own planes (psm::DepthState).
-// psm_reproject_batch: the same launches for the results of several contexts at once, the context on a grid axis of its own.
+// psm_reproject_batch: the same launches for the results of several contexts at once, the context on a grid axis of its own.  Both
+// entries check their arguments and enqueue through reproject_run.
 #include "psm_ctx.h"
 
 #include <cmath>
@@ -24,13 +25,12 @@ void depth_free(psm_ctx *c)
     (void)hipFree(q.cnt); q.cnt = nullptr;
     if (q.pin) (void)hipHostFree(q.pin);
     q.pin = nullptr;
-    for (hipEvent_t *e : {&q.ev_done, &q.ev[0], &q.ev[1]}) {
-        if (*e) (void)hipEventDestroy(*e);
-        *e = nullptr;
-    }
+    if (q.ev_done) (void)hipEventDestroy(q.ev_done);
+    q.ev_done = nullptr;
+    bracket_free(q.prof);
     table_free(q.tab);
     q.outputs = 0;
-    q.pending = q.timed = false;
+    q.pending = false;
 }
 
 }  // namespace psm
@@ -78,10 +78,7 @@ int ensure_scratch(psm_ctx *c, int outputs)
     if (!q.cnt) PSM_HIP(c, hipMalloc((void **)&q.cnt, sizeof(unsigned)));
     if (!q.pin) PSM_HIP(c, hipHostMalloc((void **)&q.pin, sizeof(unsigned), hipHostMallocDefault));
     if (!q.ev_done) PSM_HIP(c, hipEventCreateWithFlags(&q.ev_done, hipEventDisableTiming));
-    if (c->opt_profile)
-        for (hipEvent_t &e : q.ev)
-            if (!e) PSM_HIP(c, hipEventCreate(&e));
-    return 0;
+    return bracket_events(c, q.prof);
 }
 
 // the context's buffers (ensure_scratch) and parameters as the kernels take them: the kernel argument, or an entry of a batch's table
@@ -108,27 +105,66 @@ DpArgs depth_args(const psm_ctx *c, int source, int outputs, int flags)
     return a;
 }
 
-// ahead of the launches a context forgets its previous result (every check and allocation lies before this) ...
-void forget(DepthState &q)
-{
-    q.outputs = 0;
-    q.pending = q.timed = false;
-}
-
-// ... and behind them it holds the result of these outputs
-void reprojected(psm_ctx *c, int outputs, bool timed, bool pending)
-{
-    DepthState &q = c->depth;
-    q.outputs = outputs;
-    q.timed = timed;
-    q.pending = pending;
-}
-
 // the count of the last run, its copy having executed
 int count_of(psm_ctx *c, uint32_t *count)
 {
     PSM_HIP(c, hipEventSynchronize(c->depth.ev_done));
     *count = *c->depth.pin;
+    return 0;
+}
+
+// The host sequence of psm_reproject (its one context, the record by value) and of psm_reproject_batch (batch: the same kernels
+// over the device table of ctxs[0]), the arguments and every context checked: two or three launches on ctxs[0]'s stream.  Every
+// context ends where its own psm_reproject would have left it, its count in its page-locked slot unless the call is asynchronous.
+int reproject_run(const char *who, psm_ctx *const *ctxs, int n, int source, int outputs, int flags, bool batch)
+{
+    psm_ctx *c0 = ctxs[0];
+    if (bind(c0)) return 1;
+    hipStream_t s = c0->stream;
+    DepthState &t = c0->depth;
+    const bool cloud = (outputs & PSM_DEPTH_CLOUD) != 0;
+
+    // ---- buffers, events and the table's memory: before any launch ----
+    for (int i = 0; i < n; ++i)
+        if (ensure_scratch(ctxs[i], outputs)) return member_failed(c0, who, i, ctxs[i]);
+    if (batch_events(c0, ctxs, n)) return 1;
+    std::vector<DpArgs> tab((size_t)n);
+    for (int i = 0; i < n; ++i) tab[i] = depth_args(ctxs[i], source, outputs, flags);
+    bool fresh = false;
+    if (batch && table_reserve(c0, t.tab, tab.data(), tab.size() * sizeof(DpArgs), &fresh)) return 1;
+    const Recs<DpArgs> recs{tab.data(), batch ? (const DpArgs *)t.tab.dev : nullptr, n};
+
+    // ---- every context's earlier work (the result to reproject, a single psm_reproject) is ordered before the shared launches ----
+    if (batch_join(c0, ctxs, n)) return 1;
+    if (fresh && table_upload(c0, t.tab, tab.data(), tab.size() * sizeof(DpArgs))) return 1;
+
+    for (int i = 0; i < n; ++i) {
+        DepthState &q = ctxs[i]->depth;
+        q.outputs = 0;                          // (every check and allocation lies before this: the planes are about to be rewritten)
+        q.pending = q.prof.timed = false;
+        PSM_HIP(c0, hipMemsetAsync(q.cnt, 0, sizeof(unsigned), s));
+    }
+    const DpGeom g{c0->W, c0->H, source};
+    if (bracket_open(c0, t.prof, s)) return 1;
+    launch_dp_count(s, g, recs);
+    launch_dp_scan(s, g, recs);
+    if (cloud) launch_dp_pack(s, g, recs);
+    if (check_launch(c0, "k_dp_count, k_dp_scan, k_dp_pack")) return 1;
+    if (bracket_close(c0, t.prof, s)) return 1;
+
+    // ---- every context is now where its own psm_reproject would have left it; only context 0 counts as timed ----
+    for (int i = 0; i < n; ++i) {
+        psm_ctx *c = ctxs[i];
+        if (cloud && colour_of(c, source == PSM_DEPTH_SGM).slots && images_read(c, s)) return member_failed(c0, who, i, c);   // k_dp_pack read the pair's left image
+        PSM_HIP(c0, hipMemcpyAsync(c->depth.pin, c->depth.cnt, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        PSM_HIP(c0, hipEventRecord(c->depth.ev_done, s));
+    }
+    if (batch_fork(c0, ctxs, n)) return 1;
+    for (int i = 0; i < n; ++i) {
+        ctxs[i]->depth.outputs = outputs;
+        ctxs[i]->depth.pending = c0->opt_async != 0;
+    }
+    if (!c0->opt_async) PSM_HIP(c0, hipStreamSynchronize(s));
     return 0;
 }
 
@@ -168,28 +204,8 @@ int psm_reproject(psm_ctx *c, int source, int outputs, int flags, uint32_t *coun
     if (!c) return fail(nullptr, "%s: NULL context", who);
     if (check_ctx(c, c, who, source, outputs, flags)) return 1;
     if (!count && !c->opt_async) return fail(c, "%s: NULL count (only PSM_OPT_ASYNC leaves it to psm_reproject_wait)", who);
-    if (bind(c)) return 1;
-    if (ensure_scratch(c, outputs)) return 1;
-    DepthState &q = c->depth;
-    const bool timed = c->opt_profile != 0, cloud = (outputs & PSM_DEPTH_CLOUD) != 0;
-    const DpArgs a = depth_args(c, source, outputs, flags);
-    const DpGeom g{c->W, c->H, source};
-    forget(q);
-    PSM_HIP(c, hipMemsetAsync(q.cnt, 0, sizeof(unsigned), c->stream));
-    if (timed) PSM_HIP(c, hipEventRecord(q.ev[0], c->stream));
-    const Recs<DpArgs> one{&a, nullptr, 1};
-    launch_dp_count(c->stream, g, one);
-    launch_dp_scan(c->stream, g, one);
-    if (cloud) launch_dp_pack(c->stream, g, one);
-    if (check_launch(c, "k_dp_count, k_dp_scan, k_dp_pack")) return 1;
-    if (timed) PSM_HIP(c, hipEventRecord(q.ev[1], c->stream));
-    if (cloud && colour_of(c, source == PSM_DEPTH_SGM).slots && images_read(c, c->stream)) return 1;      // k_dp_pack read the pair's left image
-    PSM_HIP(c, hipMemcpyAsync(q.pin, q.cnt, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-    PSM_HIP(c, hipEventRecord(q.ev_done, c->stream));
-    reprojected(c, outputs, timed, c->opt_async != 0);
-    if (c->opt_async) return 0;
-    PSM_HIP(c, hipStreamSynchronize(c->stream));
-    *count = *q.pin;
+    if (reproject_run(who, &c, 1, source, outputs, flags, false)) return 1;
+    if (!c->opt_async) *count = *c->depth.pin;
     return 0;
 }
 
@@ -239,8 +255,8 @@ int psm_reproject_download_cloud(psm_ctx *c, void *records, uint32_t max_records
     return 0;
 }
 
-// The launches of psm_reproject with the context on a grid axis of its own.  Buffers and parameters stay per context; the kernels
-// reach them through a device table ctxs[0] owns.  Every context ends where its own psm_reproject would have left it.
+// The launches of psm_reproject with the context on a grid axis of its own (reproject_run).  Buffers and parameters stay per
+// context; the kernels reach them through a device table ctxs[0] owns.
 int psm_reproject_batch(psm_ctx *const *ctxs, int n, int source, int outputs, int flags, uint32_t *counts)
 {
     const char *who = "psm_reproject_batch";
@@ -258,63 +274,15 @@ int psm_reproject_batch(psm_ctx *const *ctxs, int n, int source, int outputs, in
         snprintf(member, sizeof member, "%s: context %d", who, i);
         if (check_ctx(c0, c, member, source, outputs, flags)) return 1;
     }
-    if (bind(c0)) return 1;
-    hipStream_t s = c0->stream;
-    const bool timed = c0->opt_profile != 0, cloud = (outputs & PSM_DEPTH_CLOUD) != 0;
-
-    // ---- buffers, events and the table's memory: before any launch ----
-    for (int i = 0; i < n; ++i)
-        if (ensure_scratch(ctxs[i], outputs)) return member_failed(c0, who, i, ctxs[i]);
-    if (batch_events(c0, ctxs, n)) return 1;
-    DepthState &t = c0->depth;
-    std::vector<DpArgs> tab((size_t)n);
-    for (int i = 0; i < n; ++i) tab[i] = depth_args(ctxs[i], source, outputs, flags);
-    bool fresh = false;
-    if (table_reserve(c0, t.tab, tab.data(), tab.size() * sizeof(DpArgs), &fresh)) return 1;
-    const Recs<DpArgs> recs{tab.data(), (const DpArgs *)t.tab.dev, n};
-
-    // ---- every context's earlier work (the result to reproject, a single psm_reproject) is ordered before the shared launches ----
-    if (batch_join(c0, ctxs, n)) return 1;
-    if (fresh && table_upload(c0, t.tab, tab.data(), tab.size() * sizeof(DpArgs))) return 1;
-
-    for (int i = 0; i < n; ++i) {
-        forget(ctxs[i]->depth);
-        PSM_HIP(c0, hipMemsetAsync(ctxs[i]->depth.cnt, 0, sizeof(unsigned), s));
-    }
-    const DpGeom g{c0->W, c0->H, source};
-    if (timed) PSM_HIP(c0, hipEventRecord(t.ev[0], s));
-    launch_dp_count(s, g, recs);
-    launch_dp_scan(s, g, recs);
-    if (cloud) launch_dp_pack(s, g, recs);
-    if (check_launch(c0, "k_dp_count, k_dp_scan, k_dp_pack")) return 1;
-    if (timed) PSM_HIP(c0, hipEventRecord(t.ev[1], s));
-
-    // ---- every context is now where its own psm_reproject would have left it; only context 0 counts as timed ----
-    for (int i = 0; i < n; ++i) {
-        psm_ctx *c = ctxs[i];
-        if (cloud && colour_of(c, source == PSM_DEPTH_SGM).slots && images_read(c, s)) return member_failed(c0, who, i, c);
-        PSM_HIP(c0, hipMemcpyAsync(c->depth.pin, c->depth.cnt, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        PSM_HIP(c0, hipEventRecord(c->depth.ev_done, s));
-    }
-    if (batch_fork(c0, ctxs, n)) return 1;
-    for (int i = 0; i < n; ++i) reprojected(ctxs[i], outputs, timed && i == 0, c0->opt_async != 0);
-    if (c0->opt_async) return 0;
-    PSM_HIP(c0, hipStreamSynchronize(s));
-    for (int i = 0; i < n; ++i) counts[i] = *ctxs[i]->depth.pin;
+    if (reproject_run(who, ctxs, n, source, outputs, flags, true)) return 1;
+    for (int i = 0; i < n && !c0->opt_async; ++i) counts[i] = *ctxs[i]->depth.pin;
     return 0;
 }
 
 int psm_reproject_time(psm_ctx *c, double *ms)
 {
     if (!c) return fail(nullptr, "psm_reproject_time: NULL context");
-    if (!ms) return fail(c, "psm_reproject_time: NULL pointer");
-    if (!c->depth.outputs || !c->depth.timed) return fail(c, "psm_reproject_time: the last psm_reproject was not timed (PSM_OPT_PROFILE)");
-    if (bind(c)) return 1;
-    PSM_HIP(c, hipEventSynchronize(c->depth.ev[1]));
-    float t = 0.f;
-    PSM_HIP(c, hipEventElapsedTime(&t, c->depth.ev[0], c->depth.ev[1]));
-    *ms = t;
-    return 0;
+    return bracket_ms(c, c->depth.prof, c->depth.outputs != 0, "psm_reproject_time", "the last psm_reproject was not timed (PSM_OPT_PROFILE)", ms);
 }
 
 }  // extern "C"

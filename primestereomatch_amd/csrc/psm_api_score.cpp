@@ -2,7 +2,8 @@
 // (src/StereoMatch.cpp:181-185, 248-249) and the error metric against ground truth (:275-309) - on the device, behind the C ABI.
 // Kernels: psm_score.hip.  The definition is tests/score_model.py / DESIGN.md 11.  An independent stage: it reads the context's
 // current result - the maps through psm::Results, the int16 map of the SGM stage - and writes its own planes (psm::ScoreState).
-// psm_score_batch: the same launches for the results of several contexts at once, the context on a grid axis of its own.
+// psm_score_batch: the same launches for the results of several contexts at once, the context on a grid axis of its own.  Both
+// entries check their arguments and enqueue through score_run.
 #include "psm_ctx.h"
 
 #include <cstdio>
@@ -19,13 +20,12 @@ void score_free(psm_ctx *c, bool truth)
     (void)hipFree(q.cnt); q.cnt = nullptr;
     if (q.pin) (void)hipHostFree(q.pin);
     q.pin = nullptr;
-    for (hipEvent_t *e : {&q.ev_done, &q.ev[0], &q.ev[1]}) {
-        if (*e) (void)hipEventDestroy(*e);
-        *e = nullptr;
-    }
+    if (q.ev_done) (void)hipEventDestroy(q.ev_done);
+    q.ev_done = nullptr;
+    bracket_free(q.prof);
     table_free(q.tab);
     q.source = -1;
-    q.pending = q.timed = false;
+    q.pending = false;
     if (truth) {
         (void)hipFree(q.gt); q.gt = nullptr;
         (void)hipFree(q.mask); q.mask = nullptr;
@@ -63,10 +63,7 @@ int ensure_scratch(psm_ctx *c)
     if (!q.cnt) PSM_HIP(c, hipMalloc((void **)&q.cnt, sizeof(ScCnt)));
     if (!q.pin) PSM_HIP(c, hipHostMalloc((void **)&q.pin, sizeof(ScCnt), hipHostMallocDefault));
     if (!q.ev_done) PSM_HIP(c, hipEventCreateWithFlags(&q.ev_done, hipEventDisableTiming));
-    if (c->opt_profile)
-        for (hipEvent_t &e : q.ev)
-            if (!e) PSM_HIP(c, hipEventCreate(&e));
-    return 0;
+    return bracket_events(c, q.prof);
 }
 
 // the context's buffers (ensure_scratch) as the kernels take them: a single call's record, an entry of a batch's table
@@ -101,14 +98,58 @@ void fill_record(const psm_ctx *c, struct psm_score *out)
     out->flags = mm && out->min_val == out->max_val ? PSM_SCORE_FLAT : 0u;
 }
 
-// what a finished enqueue leaves in the context
-void scored(psm_ctx *c, int source, bool timed, bool pending)
+// The host sequence of psm_score (its one context, the record by value) and of psm_score_batch (batch: the same kernels over the
+// device table of ctxs[0]), the arguments and every context checked: one or two launches on ctxs[0]'s stream.  Every context ends
+// where its own psm_score would have left it, its counters in its page-locked slot (fill_record) unless the call is asynchronous.
+int score_run(const char *who, psm_ctx *const *ctxs, int n, int source, bool batch)
 {
-    ScoreState &q = c->score;
-    q.source = source;
-    q.unit = 127 / c->D;
-    q.timed = timed;
-    q.pending = pending;
+    psm_ctx *c0 = ctxs[0];
+    if (bind(c0)) return 1;
+    hipStream_t s = c0->stream;
+    ScoreState &t = c0->score;
+
+    // ---- buffers, events and the table's memory: before any launch ----
+    for (int i = 0; i < n; ++i)
+        if (ensure_scratch(ctxs[i])) return member_failed(c0, who, i, ctxs[i]);
+    if (batch_events(c0, ctxs, n)) return 1;
+    std::vector<ScPair> tab((size_t)n);
+    for (int i = 0; i < n; ++i) tab[i] = score_pair(ctxs[i]);
+    bool fresh = false;
+    if (batch && table_reserve(c0, t.tab, tab.data(), tab.size() * sizeof(ScPair), &fresh)) return 1;
+    const Recs<ScPair> recs{tab.data(), batch ? (const ScPair *)t.tab.dev : nullptr, n};
+
+    // ---- every context's earlier work (the result to score, a single psm_score) is ordered before the shared launches ----
+    if (batch_join(c0, ctxs, n)) return 1;
+    if (fresh && table_upload(c0, t.tab, tab.data(), tab.size() * sizeof(ScPair))) return 1;
+
+    for (int i = 0; i < n; ++i) {
+        ScoreState &q = ctxs[i]->score;
+        q.source = -1;                          // (every check and allocation lies before this: the planes are about to be rewritten)
+        q.pending = q.prof.timed = false;
+        PSM_HIP(c0, hipMemsetAsync(q.cnt, 0, sizeof(ScCnt), s));
+    }
+    const ScArgs a = score_args(c0);
+    if (bracket_open(c0, t.prof, s)) return 1;
+    if (source == PSM_SCORE_SGM) launch_sc_minmax(s, a, recs);
+    launch_sc_score(s, source, a, recs);
+    if (check_launch(c0, "k_sc_minmax, k_sc_score")) return 1;
+    if (bracket_close(c0, t.prof, s)) return 1;
+
+    // ---- every context is now where its own psm_score would have left it; only context 0 counts as timed ----
+    for (int i = 0; i < n; ++i) {
+        ScoreState &q = ctxs[i]->score;
+        PSM_HIP(c0, hipMemcpyAsync(q.pin, q.cnt, sizeof(ScCnt), hipMemcpyDeviceToHost, s));
+        PSM_HIP(c0, hipEventRecord(q.ev_done, s));
+    }
+    if (batch_fork(c0, ctxs, n)) return 1;
+    for (int i = 0; i < n; ++i) {
+        ScoreState &q = ctxs[i]->score;
+        q.source = source;
+        q.unit = 127 / ctxs[i]->D;
+        q.pending = c0->opt_async != 0;
+    }
+    if (!c0->opt_async) PSM_HIP(c0, hipStreamSynchronize(s));
+    return 0;
 }
 
 }  // namespace
@@ -161,27 +202,8 @@ int psm_score(psm_ctx *c, int source, struct psm_score *out)
     if (!c) return fail(nullptr, "psm_score: NULL context");
     if (check_source(c, c, "psm_score", source)) return 1;
     if (!out && !c->opt_async) return fail(c, "psm_score: NULL record (only PSM_OPT_ASYNC leaves it to psm_score_wait)");
-    if (bind(c)) return 1;
-    if (ensure_scratch(c)) return 1;
-    ScoreState &q = c->score;
-    const bool timed = c->opt_profile != 0;
-    const ScArgs a = score_args(c);
-    const ScPair p = score_pair(c);
-    const Recs<ScPair> one{&p, nullptr, 1};
-    q.source = -1;
-    q.pending = q.timed = false;
-    PSM_HIP(c, hipMemsetAsync(q.cnt, 0, sizeof(ScCnt), c->stream));
-    if (timed) PSM_HIP(c, hipEventRecord(q.ev[0], c->stream));
-    if (source == PSM_SCORE_SGM) launch_sc_minmax(c->stream, a, one);
-    launch_sc_score(c->stream, source, a, one);
-    if (check_launch(c, "k_sc_minmax, k_sc_score")) return 1;
-    if (timed) PSM_HIP(c, hipEventRecord(q.ev[1], c->stream));
-    PSM_HIP(c, hipMemcpyAsync(q.pin, q.cnt, sizeof(ScCnt), hipMemcpyDeviceToHost, c->stream));
-    PSM_HIP(c, hipEventRecord(q.ev_done, c->stream));
-    scored(c, source, timed, c->opt_async != 0);
-    if (c->opt_async) return 0;
-    PSM_HIP(c, hipStreamSynchronize(c->stream));
-    fill_record(c, out);
+    if (score_run("psm_score", &c, 1, source, false)) return 1;
+    if (!c->opt_async) fill_record(c, out);
     return 0;
 }
 
@@ -211,8 +233,8 @@ int psm_score_download(psm_ctx *c, uint8_t *ldisp, uint8_t *rdisp, uint8_t *emap
     return copy_maps_out(c, q.planes + 2 * HW, emap, nullptr, stride);
 }
 
-// The launches of psm_score with the context on a grid axis of its own.  Buffers stay per context; the kernels reach them through a
-// device table ctxs[0] owns.  Every context ends where its own psm_score would have left it.
+// The launches of psm_score with the context on a grid axis of its own (score_run).  Buffers stay per context; the kernels reach
+// them through a device table ctxs[0] owns.
 int psm_score_batch(psm_ctx *const *ctxs, int n, int source, struct psm_score *outs)
 {
     const char *who = "psm_score_batch";
@@ -239,63 +261,15 @@ int psm_score_batch(psm_ctx *const *ctxs, int n, int source, struct psm_score *o
             return fail(c0, "%s: context %d has %s mask, context 0 has %s (on all contexts or on none)", who, i, use_mask(q) ? "a" : "no",
                         use_mask(q0) ? "one" : "none");
     }
-    if (bind(c0)) return 1;
-    hipStream_t s = c0->stream;
-    const bool timed = c0->opt_profile != 0;
-
-    // ---- buffers, events and the table's memory: before any launch ----
-    for (int i = 0; i < n; ++i)
-        if (ensure_scratch(ctxs[i])) return member_failed(c0, who, i, ctxs[i]);
-    if (batch_events(c0, ctxs, n)) return 1;
-    ScoreState &t = c0->score;
-    std::vector<ScPair> tab((size_t)n);
-    for (int i = 0; i < n; ++i) tab[i] = score_pair(ctxs[i]);
-    bool fresh = false;
-    if (table_reserve(c0, t.tab, tab.data(), tab.size() * sizeof(ScPair), &fresh)) return 1;
-    const Recs<ScPair> recs{tab.data(), (const ScPair *)t.tab.dev, n};
-
-    // ---- every context's earlier work (the result to score, a single psm_score) is ordered before the shared launches ----
-    if (batch_join(c0, ctxs, n)) return 1;
-    if (fresh && table_upload(c0, t.tab, tab.data(), tab.size() * sizeof(ScPair))) return 1;
-
-    for (int i = 0; i < n; ++i) {
-        ScoreState &q = ctxs[i]->score;
-        q.source = -1;
-        q.pending = q.timed = false;
-        PSM_HIP(c0, hipMemsetAsync(q.cnt, 0, sizeof(ScCnt), s));
-    }
-    const ScArgs a = score_args(c0);
-    if (timed) PSM_HIP(c0, hipEventRecord(t.ev[0], s));
-    if (source == PSM_SCORE_SGM) launch_sc_minmax(s, a, recs);
-    launch_sc_score(s, source, a, recs);
-    if (check_launch(c0, "k_sc_minmax, k_sc_score")) return 1;
-    if (timed) PSM_HIP(c0, hipEventRecord(t.ev[1], s));
-
-    // ---- every context is now where its own psm_score would have left it; only context 0 counts as timed ----
-    for (int i = 0; i < n; ++i) {
-        ScoreState &q = ctxs[i]->score;
-        PSM_HIP(c0, hipMemcpyAsync(q.pin, q.cnt, sizeof(ScCnt), hipMemcpyDeviceToHost, s));
-        PSM_HIP(c0, hipEventRecord(q.ev_done, s));
-    }
-    if (batch_fork(c0, ctxs, n)) return 1;
-    for (int i = 0; i < n; ++i) scored(ctxs[i], source, timed && i == 0, c0->opt_async != 0);
-    if (c0->opt_async) return 0;
-    PSM_HIP(c0, hipStreamSynchronize(s));
-    for (int i = 0; i < n; ++i) fill_record(ctxs[i], &outs[i]);
+    if (score_run(who, ctxs, n, source, true)) return 1;
+    for (int i = 0; i < n && !c0->opt_async; ++i) fill_record(ctxs[i], &outs[i]);
     return 0;
 }
 
 int psm_score_time(psm_ctx *c, double *ms)
 {
     if (!c) return fail(nullptr, "psm_score_time: NULL context");
-    if (!ms) return fail(c, "psm_score_time: NULL pointer");
-    if (c->score.source < 0 || !c->score.timed) return fail(c, "psm_score_time: the last psm_score was not timed (PSM_OPT_PROFILE)");
-    if (bind(c)) return 1;
-    PSM_HIP(c, hipEventSynchronize(c->score.ev[1]));
-    float t = 0.f;
-    PSM_HIP(c, hipEventElapsedTime(&t, c->score.ev[0], c->score.ev[1]));
-    *ms = t;
-    return 0;
+    return bracket_ms(c, c->score.prof, c->score.source >= 0, "psm_score_time", "the last psm_score was not timed (PSM_OPT_PROFILE)", ms);
 }
 
 int psm_score_upload_sgm_map(psm_ctx *c, const int16_t *disp, size_t stride_bytes)

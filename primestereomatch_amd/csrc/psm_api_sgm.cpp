@@ -12,7 +12,8 @@
 // from S, so that the post-processing and score stages run behind it (tests/sgm_maps_model.py).
 // Single pairs and batches share the launch sequence (enqueue), the record of a pair's buffers (pair_of), the name of the pixel
 // cost (cost_kind) and what a context forgets ahead of the launches and holds behind them (forget, mark); the entry points keep
-// what differs - argument checks, the gray upload, a batch's cross-context checks, stream ordering and table.
+// what differs - argument checks, the gray upload, a batch's cross-context checks, stream ordering and table.  The map select's
+// two entries keep their checks and share the whole sequence (maps_run).
 #include "psm_ctx.h"
 
 #include <cstdio>
@@ -39,8 +40,8 @@ void sgm_free(psm_ctx *c)
     g.cen_have = false;
     for (hipEvent_t &e : g.ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     table_free(g.tab);
-    for (hipEvent_t &e : g.ev_maps) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    g.have = g.timed = g.spk_have = g.maps_timed = false;
+    bracket_free(g.maps);
+    g.have = g.timed = g.spk_have = false;
     g.spk_t0 = -1;
     g.vol_dp = g.res_d = g.res_dmin = g.res_ch = 0;
 }
@@ -306,6 +307,42 @@ void maps_selected(psm_ctx *c)
     maps_written(c->res);
 }
 
+// The host sequence of psm_sgm_select_maps (its one context, the record by value) and of psm_sgm_select_maps_batch (batch: the same
+// kernel over the device table of ctxs[0]), every context checked: one launch on ctxs[0]'s stream.  Every context ends where its
+// own psm_sgm_select_maps would have left it.  The single entry has its copy_maps_out behind this function, which is why the
+// closing synchronisation is the entries'.
+int maps_run(psm_ctx *const *ctxs, int n, bool batch)
+{
+    psm_ctx *c0 = ctxs[0];
+    if (bind(c0)) return 1;
+    hipStream_t s = c0->stream;
+    SgmState &g0 = c0->sgm;
+
+    // ---- events and the table's memory: before anything is ordered or launched ----
+    if (batch_events(c0, ctxs, n)) return 1;
+    if (bracket_events(c0, g0.maps)) return 1;
+    const std::vector<SgmPair> tab = pairs_of(ctxs, n);      // (pair_of: maps = c->maps)
+    bool fresh = false;
+    if (batch && table_reserve(c0, g0.tab, tab.data(), tab.size() * sizeof(SgmPair), &fresh)) return 1;
+    const Recs<SgmPair> recs{tab.data(), batch ? (const SgmPair *)g0.tab.dev : nullptr, n};
+
+    // ---- every context's earlier work (its compute, downloads of its maps) is ordered before the shared launch ----
+    for (int i = 0; i < n; ++i)
+        if (ctxs[i]->ev_down) PSM_HIP(c0, hipStreamWaitEvent(s, ctxs[i]->ev_down, 0));       // (maps_writable, for the stream that writes)
+    if (batch_join(c0, ctxs, n)) return 1;
+    if (fresh && table_upload(c0, g0.tab, tab.data(), tab.size() * sizeof(SgmPair))) return 1;
+
+    // ---- the launch; then every context is where its own psm_sgm_select_maps would have left it - only context 0 counts as timed ----
+    for (int i = 0; i < n; ++i) ctxs[i]->sgm.maps.timed = false;
+    if (bracket_open(c0, g0.maps, s)) return 1;
+    launch_sgm_maps(s, maps_args(c0), recs);
+    if (check_launch(c0, "k_sgm_maps")) return 1;
+    if (bracket_close(c0, g0.maps, s)) return 1;
+    if (batch_fork(c0, ctxs, n)) return 1;
+    for (int i = 0; i < n; ++i) maps_selected(ctxs[i]);
+    return 0;
+}
+
 // a single pair of `ch` channels through the stage on the context's stream (psm_sgm_compute: the context's image slots;
 // psm_sgm_compute_gray: planes of its own)
 int compute_one(psm_ctx *c, const char *who, const void *l, const void *r, int depth, int ch, bool slots)
@@ -489,27 +526,13 @@ int psm_sgm_select_maps(psm_ctx *c, uint8_t *lmap, uint8_t *rmap, size_t stride)
     if (!c) return fail(nullptr, "%s: NULL context", who);
     if (check_maps(c, c, who)) return 1;
     if (stride != 0 && stride < (size_t)c->W) return fail(c, "%s: stride %zu < width %d", who, stride, c->W);
-    if (bind(c)) return 1;
-    SgmState &g = c->sgm;
-    const bool timed = c->opt_profile != 0;
-    if (timed)
-        for (hipEvent_t &e : g.ev_maps)
-            if (!e) PSM_HIP(c, hipEventCreate(&e));
-    if (maps_writable(c)) return 1;
-    g.maps_timed = false;
-    if (timed) PSM_HIP(c, hipEventRecord(g.ev_maps[0], c->stream));
-    const SgmPair p = pair_of(c, nullptr, nullptr);
-    launch_sgm_maps(c->stream, maps_args(c), Recs<SgmPair>{&p, nullptr, 1});      // (pair_of: maps = c->maps)
-    if (check_launch(c, "k_sgm_maps")) return 1;
-    if (timed) PSM_HIP(c, hipEventRecord(g.ev_maps[1], c->stream));
-    g.maps_timed = timed;
-    maps_selected(c);
+    if (maps_run(&c, 1, false)) return 1;
     if (copy_maps_out(c, c->maps, lmap, rmap, stride)) return 1;
     if (!c->opt_async) PSM_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 
-// ... of the n contexts ctxs[0..n) in one launch on ctxs[0]'s stream, ordered as psm_sgm_compute_batch's
+// ... of the n contexts ctxs[0..n) in one launch on ctxs[0]'s stream (maps_run), ordered as psm_sgm_compute_batch's
 int psm_sgm_select_maps_batch(psm_ctx *const *ctxs, int n)
 {
     const char *who = "psm_sgm_select_maps_batch";
@@ -528,51 +551,15 @@ int psm_sgm_select_maps_batch(psm_ctx *const *ctxs, int n)
             return fail(c0, "%s: the result of context %d has another disparity range (min %d, %d disparities) than context 0's (min %d, %d)", who, i,
                         c->sgm.res_dmin, c->sgm.res_d, c0->sgm.res_dmin, c0->sgm.res_d);
     }
-    if (bind(c0)) return 1;
-    hipStream_t s = c0->stream;
-    SgmState &g0 = c0->sgm;
-    DevTable &t = g0.tab;
-    const bool timed = c0->opt_profile != 0;
-
-    // ---- events and the table's memory: before anything is ordered or launched ----
-    if (batch_events(c0, ctxs, n)) return 1;
-    if (timed)
-        for (hipEvent_t &e : g0.ev_maps)
-            if (!e) PSM_HIP(c0, hipEventCreate(&e));
-    const std::vector<SgmPair> tab = pairs_of(ctxs, n);
-    bool fresh = false;
-    if (table_reserve(c0, t, tab.data(), tab.size() * sizeof(SgmPair), &fresh)) return 1;
-
-    // ---- every context's earlier work (its compute, downloads of its maps) is ordered before the shared launch ----
-    for (int i = 0; i < n; ++i)
-        if (ctxs[i]->ev_down) PSM_HIP(c0, hipStreamWaitEvent(s, ctxs[i]->ev_down, 0));       // (maps_writable, for the stream that writes)
-    if (batch_join(c0, ctxs, n)) return 1;
-    if (fresh && table_upload(c0, t, tab.data(), tab.size() * sizeof(SgmPair))) return 1;
-
-    // ---- the launch; then every context is where its own psm_sgm_select_maps would have left it - only context 0 counts as timed ----
-    for (int i = 0; i < n; ++i) ctxs[i]->sgm.maps_timed = false;
-    if (timed) PSM_HIP(c0, hipEventRecord(g0.ev_maps[0], s));
-    launch_sgm_maps(s, maps_args(c0), Recs<SgmPair>{tab.data(), (const SgmPair *)t.dev, n});
-    if (check_launch(c0, "k_sgm_maps")) return 1;
-    if (timed) PSM_HIP(c0, hipEventRecord(g0.ev_maps[1], s));
-    g0.maps_timed = timed;
-    if (batch_fork(c0, ctxs, n)) return 1;
-    for (int i = 0; i < n; ++i) maps_selected(ctxs[i]);
-    if (!c0->opt_async) PSM_HIP(c0, hipStreamSynchronize(s));
+    if (maps_run(ctxs, n, true)) return 1;
+    if (!c0->opt_async) PSM_HIP(c0, hipStreamSynchronize(c0->stream));
     return 0;
 }
 
 int psm_sgm_maps_time(psm_ctx *c, double *ms)
 {
     if (!c) return fail(nullptr, "psm_sgm_maps_time: NULL context");
-    if (!ms) return fail(c, "psm_sgm_maps_time: NULL pointer");
-    if (!c->sgm.maps_timed) return fail(c, "psm_sgm_maps_time: the last psm_sgm_select_maps was not timed (PSM_OPT_PROFILE), or there is none");
-    if (bind(c)) return 1;
-    PSM_HIP(c, hipEventSynchronize(c->sgm.ev_maps[1]));
-    float t = 0.f;
-    PSM_HIP(c, hipEventElapsedTime(&t, c->sgm.ev_maps[0], c->sgm.ev_maps[1]));
-    *ms = t;
-    return 0;
+    return bracket_ms(c, c->sgm.maps, true, "psm_sgm_maps_time", "the last psm_sgm_select_maps was not timed (PSM_OPT_PROFILE), or there is none", ms);
 }
 
 int psm_sgm_download_disparity(psm_ctx *c, int16_t *disp, size_t stride_bytes)

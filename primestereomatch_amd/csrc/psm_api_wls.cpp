@@ -27,11 +27,10 @@ void wls_free(psm_ctx *c)
     (void)hipFree(w.tab); w.tab = nullptr;
     w.tab_sigma = 0.0f;
     table_free(w.pairs);
-    for (hipEvent_t *e : {&w.ev_done, &w.ev[0], &w.ev[1]}) {
-        if (*e) (void)hipEventDestroy(*e);
-        *e = nullptr;
-    }
-    w.have = w.pending = w.timed = w.publish = false;
+    if (w.ev_done) (void)hipEventDestroy(w.ev_done);
+    w.ev_done = nullptr;
+    bracket_free(w.prof);
+    w.have = w.pending = w.publish = false;
 }
 
 }  // namespace psm
@@ -75,10 +74,7 @@ int ensure_buffers(psm_ctx *c)
     if (!w.q) PSM_HIP(c, hipMalloc((void **)&w.q, HW * sizeof(unsigned)));
     if (!w.tab) PSM_HIP(c, hipMalloc((void **)&w.tab, WLS_TAB * sizeof(float)));
     if (!w.ev_done) PSM_HIP(c, hipEventCreateWithFlags(&w.ev_done, hipEventDisableTiming));
-    if (c->opt_profile)
-        for (hipEvent_t &e : w.ev)
-            if (!e) PSM_HIP(c, hipEventCreate(&e));
-    return 0;
+    return bracket_events(c, w.prof);
 }
 
 WlsArgs wls_args(const psm_ctx *c, int source, int flags)
@@ -133,7 +129,6 @@ int wls_run(const char *who, psm_ctx *const *ctxs, int n, int source, int flags,
     psm_ctx *c0 = ctxs[0];
     if (bind(c0)) return 1;
     hipStream_t s = c0->stream;
-    const bool timed = c0->opt_profile != 0;
     const int T = c0->wls.iters;
 
     // ---- buffers, events and the table's memory: before any launch ----
@@ -157,16 +152,16 @@ int wls_run(const char *who, psm_ctx *const *ctxs, int n, int source, int flags,
 
     for (int i = 0; i < n; ++i) {
         WlsState &w = ctxs[i]->wls;
-        w.have = w.pending = w.timed = false;   // (every check and allocation lies before this: the planes are about to be rewritten)
+        w.have = w.pending = w.prof.timed = false;   // (every check and allocation lies before this: the planes are about to be rewritten)
     }
-    if (timed) PSM_HIP(c0, hipEventRecord(c0->wls.ev[0], s));
+    if (bracket_open(c0, c0->wls.prof, s)) return 1;
     launch_wls_init(s, q);
     for (int t = 0; t < T; ++t) {
         launch_wls_rows(s, q, t);
         launch_wls_cols(s, q, t, t == T - 1);
     }
     if (check_launch(c0, "k_wls_init, k_wls_rows, k_wls_cols")) return 1;
-    if (timed) PSM_HIP(c0, hipEventRecord(c0->wls.ev[1], s));
+    if (bracket_close(c0, c0->wls.prof, s)) return 1;
 
     // ---- every context is now where its own psm_wls_filter would have left it; only context 0 counts as timed ----
     for (int i = 0; i < n; ++i) {
@@ -179,11 +174,9 @@ int wls_run(const char *who, psm_ctx *const *ctxs, int n, int source, int flags,
         WlsState &w = ctxs[i]->wls;
         w.have = true;
         w.invalid = tab[i].a.invalid;
-        w.timed = timed && i == 0;
         w.pending = c0->opt_async != 0;
     }
-    if (c0->opt_async) return 0;
-    PSM_HIP(c0, hipStreamSynchronize(s));
+    if (!c0->opt_async) PSM_HIP(c0, hipStreamSynchronize(s));
     return 0;
 }
 
@@ -274,14 +267,7 @@ int psm_wls_download_table(psm_ctx *c, float tab[256])
 int psm_wls_time(psm_ctx *c, double *ms)
 {
     if (!c) return fail(nullptr, "psm_wls_time: NULL context");
-    if (!ms) return fail(c, "psm_wls_time: NULL pointer");
-    if (!c->wls.have || !c->wls.timed) return fail(c, "psm_wls_time: the last psm_wls_filter was not timed (PSM_OPT_PROFILE)");
-    if (bind(c)) return 1;
-    PSM_HIP(c, hipEventSynchronize(c->wls.ev[1]));
-    float t = 0.f;
-    PSM_HIP(c, hipEventElapsedTime(&t, c->wls.ev[0], c->wls.ev[1]));
-    *ms = t;
-    return 0;
+    return bracket_ms(c, c->wls.prof, c->wls.have, "psm_wls_time", "the last psm_wls_filter was not timed (PSM_OPT_PROFILE)", ms);
 }
 
 int psm_wls_publish(psm_ctx *c, int on)

@@ -15,14 +15,17 @@
 //                       maps of several contexts in shared launches (psm_joint_wmf_batch)
 //   psm_api_rectify.cpp video mode: remap + crop of the camera frame into the staged image slot (psm_upload_pair_rectified)
 //   psm_api_sgm.cpp     semi-global matching over the staged pair, the reference's STEREO_SGBM branch (psm_sgm_compute), and
-//                       over the pairs of several contexts in shared launches (psm_sgm_compute_batch)
+//                       over the pairs of several contexts in shared launches (psm_sgm_compute_batch) - one launch sequence,
+//                       enqueue; the 8-bit maps of both views from its S (psm_sgm_select_maps, _batch) - one sequence, maps_run
 //   psm_api_score.cpp   display maps and the error metric against ground truth of the current result (psm_score), and of the
-//                       results of several contexts in shared launches (psm_score_batch)
+//                       results of several contexts in shared launches (psm_score_batch) - one sequence, score_run
 //   psm_api_depth.cpp   from disparity to depth: cv::reprojectImageTo3D of the current result and the compacted point cloud
-//                       (psm_reproject), and of the results of several contexts in shared launches (psm_reproject_batch)
+//                       (psm_reproject), and of the results of several contexts in shared launches (psm_reproject_batch) - one
+//                       sequence, reproject_run
 //   psm_api_wls.cpp     edge-aware WLS smoothing of the sub-pixel int16 map (psm_wls_filter), of the maps of several contexts in
-//                       shared launches (psm_wls_filter_batch), and the switch that lets the SGM sources of psm_score /
-//                       psm_reproject read its result (psm_wls_publish)
+//                       shared launches (psm_wls_filter_batch) - one sequence, wls_run - and the switch that lets the SGM sources
+//                       of psm_score / psm_reproject read its result (psm_wls_publish)
+// The last four bracket their launches for PSM_OPT_PROFILE with one psm::Bracket each (bracket_* below).
 // Takes the place of the reference's oclUtil + CVC_cl / CVF_cl / DispSel_cl host wrappers
 // (src/oclUtil.cpp, src/CVC_cl.cpp, src/CVF_cl.cpp, src/DispSel_cl.cpp).
 // What a context knows about its volumes, results and image pairs between calls - psm::VolSide per side, psm::Results,
@@ -64,6 +67,14 @@ struct DevTable {
     hipEvent_t ev[2] = {nullptr, nullptr};         // the copy out of a slot has executed (the host may refill it)
 };
 
+// PSM_OPT_PROFILE around one launch sequence - score_run, reproject_run, maps_run, wls_run: two events on its stream, and whether
+// the last sequence recorded them (a batch records its first context's alone: only that context counts as timed).  Written by the
+// bracket_* functions below alone, but for the `timed = false` of a sequence's forget step.
+struct Bracket {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool timed = false;
+};
+
 // psm_sgm_compute (psm_api_sgm.cpp): parameters, the stage's own device buffers (allocated on first use, reused from frame to
 // frame) and the events of psm_sgm_times.  Nothing else in the context reads or writes any of it.
 struct SgmState {
@@ -96,9 +107,7 @@ struct SgmState {
     uint64_t *cen[2] = {nullptr, nullptr};         // the code planes of both images, [H][W]
     bool cen_have = false;                         // the last compute wrote them
     DevTable tab;                                  // psm_sgm_compute_batch, psm_sgm_select_maps_batch (this context as the first): SgmPair records
-    // psm_sgm_select_maps: the events around its launch (PSM_OPT_PROFILE), and whether the last call recorded them (psm_sgm_maps_time)
-    hipEvent_t ev_maps[2] = {nullptr, nullptr};
-    bool maps_timed = false;
+    Bracket maps;                                  // psm_sgm_select_maps: around its launch (psm_sgm_maps_time)
 };
 
 // JointWMF (psm_api_jwmf.cpp): what a side's clustering of the current pair is.  Written by its three transitions alone; each makes
@@ -160,11 +169,10 @@ struct ScoreState {
     uint8_t *planes = nullptr;                     // [3][H][W]: left display, right display, error plane
     ScCnt *cnt = nullptr, *pin = nullptr;          // the counters and the page-locked slot their copy lands in
     hipEvent_t ev_done = nullptr;                  // ... that copy has executed
-    hipEvent_t ev[2] = {nullptr, nullptr};         // PSM_OPT_PROFILE: around the launches
+    Bracket prof;                                  // PSM_OPT_PROFILE: around the launches
     int source = -1;                               // of the last psm_score (-1: none: the planes hold nothing)
     int unit = 0;                                  // ... and its 127 / max_disp
     bool pending = false;                          // a record is on its way to `pin` (psm_score_wait)
-    bool timed = false;
     DevTable tab;                                  // psm_score_batch (this context as the first of a batch): ScPair records
 };
 
@@ -180,10 +188,9 @@ struct DepthState {
     unsigned *tiles = nullptr;                     // [2][dp_tiles]: counts, offsets
     unsigned *cnt = nullptr, *pin = nullptr;       // the count and the page-locked slot its copy lands in
     hipEvent_t ev_done = nullptr;                  // ... that copy has executed
-    hipEvent_t ev[2] = {nullptr, nullptr};         // PSM_OPT_PROFILE: around the launches
+    Bracket prof;                                  // PSM_OPT_PROFILE: around the launches
     int outputs = 0;                               // of the last psm_reproject (0: none: the planes hold nothing)
     bool pending = false;                          // a count is on its way to `pin` (psm_reproject_wait)
-    bool timed = false;
     DevTable tab;                                  // psm_reproject_batch (this context as the first of a batch): DpArgs records
 };
 
@@ -201,11 +208,10 @@ struct WlsState {
     float tab_host[256] = {};                      // ... and the host's copy the upload reads
     float tab_sigma = 0.0f;
     hipEvent_t ev_done = nullptr;                  // behind the last launch (psm_wls_wait)
-    hipEvent_t ev[2] = {nullptr, nullptr};         // PSM_OPT_PROFILE: around the launches
+    Bracket prof;                                  // PSM_OPT_PROFILE: around the launches
     bool have = false;                             // the planes hold the result of a filter run
     int invalid = 0;                               // ... and its invalid value
     bool pending = false;                          // an asynchronous run has not been waited for (psm_wls_wait)
-    bool timed = false;
     bool publish = false;                          // psm_wls_publish: the SGM sources of psm_score / psm_reproject read `out`
     DevTable pairs;                                // psm_wls_filter_batch (this context as the first of a batch): WlsPair records
 };
@@ -346,6 +352,49 @@ inline int maps_writable(psm_ctx *c)
 {
     if (c->ev_down) PSM_HIP(c, hipStreamWaitEvent(c->stream, c->ev_down, 0));
     return 0;
+}
+
+// The profile bracket of a launch sequence (psm::Bracket).  events: before anything is ordered or launched, its events exist while
+// PSM_OPT_PROFILE is set; open / close: around the launches on stream s - c is the context whose option decides, a batch's first;
+// ms: what the stage's _time getter answers - `have`: the result the bracket belongs to still exists, `not_timed`: the getter's
+// refusal; free: with the stage's scratch.
+inline int bracket_events(psm_ctx *c, Bracket &b)
+{
+    if (c->opt_profile)
+        for (hipEvent_t &e : b.ev)
+            if (!e) PSM_HIP(c, hipEventCreate(&e));
+    return 0;
+}
+inline int bracket_open(psm_ctx *c, Bracket &b, hipStream_t s)
+{
+    b.timed = false;
+    if (c->opt_profile) PSM_HIP(c, hipEventRecord(b.ev[0], s));
+    return 0;
+}
+inline int bracket_close(psm_ctx *c, Bracket &b, hipStream_t s)
+{
+    if (c->opt_profile) PSM_HIP(c, hipEventRecord(b.ev[1], s));
+    b.timed = c->opt_profile != 0;
+    return 0;
+}
+inline int bracket_ms(psm_ctx *c, const Bracket &b, bool have, const char *who, const char *not_timed, double *ms)
+{
+    if (!ms) return fail(c, "%s: NULL pointer", who);
+    if (!have || !b.timed) return fail(c, "%s: %s", who, not_timed);
+    if (bind(c)) return 1;
+    PSM_HIP(c, hipEventSynchronize(b.ev[1]));
+    float t = 0.f;
+    PSM_HIP(c, hipEventElapsedTime(&t, b.ev[0], b.ev[1]));
+    *ms = t;
+    return 0;
+}
+inline void bracket_free(Bracket &b)
+{
+    for (hipEvent_t &e : b.ev) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    b.timed = false;
 }
 
 // RAII bracket of one kernel launch with hipEvents on the launch stream (PSM_OPT_PROFILE 1); s: that stream if it is not the

@@ -1,7 +1,7 @@
-"""-m gpu: a batch of ONE against the single call, stage by stage - SGM with the speckle filter on, score, depth, WLS.  The two
-reach their pair's record through different sources (psm_kernels.h, Recs: the single call passes it by value in the kernarg, the
-batch - of one too - reads the device table), launch by launch the same kernels: every output must be equal in every bit, and
-equal to the stage's numpy model.  No tolerance anywhere in this file.
+"""-m gpu: a batch of ONE against the single call, stage by stage - SGM with the speckle filter on, its map select, score, depth,
+WLS.  The two reach their pair's record through different sources (psm_kernels.h, Recs: the single call passes it by value in the
+kernarg, the batch - of one too - reads the device table), launch by launch the same kernels: every output must be equal in every
+bit, and equal to the stage's numpy model.  No tolerance anywhere in this file.
 
 Shapes: the smallest image a context takes, 8 x 8, and 65 x 9 - one row past the 64-line group of the WLS passes, and inside one
 256-pixel tile of the depth, WLS and score kernels at 8 x 8 but across three of them at 65 x 9.  SGM runs them with 2 and 9
@@ -14,6 +14,7 @@ import pytest
 import depth_model as DM
 import score_model as SM
 import sgm_bt_model as B
+import sgm_maps_model as MM
 import sgm_model as M
 import speckle_model as K
 import wls_model as WM
@@ -72,6 +73,23 @@ def test_sgm_with_the_speckle_filter(psm, W, H, D, cap):
                 pb = member.sgm_prefiltered(side)
                 assert np.array_equal(pb, one.sgm_prefiltered(side)) and np.array_equal(pb, ref["planes"][side])
     assert W == 8 or (want != ref["disp"]).sum() > 50                            # at 65 x 9 the filter removes speckles (8 x 8 x 2 is one component)
+
+
+@pytest.mark.parametrize("W,H,D", SHAPES)
+def test_sgm_map_select(psm, W, H, D):
+    from primestereomatch_amd import dispest
+    l, r = rnd(30 + W).integers(0, 256, (2, H, W, 3), dtype=np.uint8)            # unrelated images: the winners vary from pixel to pixel
+    want = MM.maps(M.sgm(l, r, D)["S"], 0, D)                                    # the model's maps of the model's S
+    # the batch runs on a context of its own that never saw a single call: maps it did not write could not come out equal
+    with psm.DispEst(l, r, D) as one, psm.DispEst(l, r, D) as member:
+        one.SGBM_GPU()
+        dispest.sgbm_batch([member])
+        single = [m.copy() for m in one.SGBMSelect_GPU()]
+        dispest.sgbm_select_batch([member])
+        batch = member.download_maps()
+        for b, s, w in zip(batch, single, want):
+            assert b.dtype == np.uint8 and np.array_equal(b, s) and np.array_equal(b, w)
+    assert all(len(np.unique(w)) == D for w in want)                             # every disparity of the range wins somewhere
 
 
 @pytest.mark.parametrize("W,H,D", SHAPES)
