@@ -179,8 +179,7 @@ extern "C" int psm_compute_batch(psm_ctx *const *ctxs, int n)
     bool fresh = false;
     if (table_reserve(c0, c0->batch_tab, tab.data(), tab.size() * sizeof(PcPair), &fresh)) return 1;
     if (fresh && table_upload(c0, c0->batch_tab, tab.data(), tab.size() * sizeof(PcPair))) return 1;
-    const PcPair *dt = (const PcPair *)c0->batch_tab.dev;
-    const PcPairs P = {dt, n, {}};
+    const Recs<PcPair> q = {tab.data(), (const PcPair *)c0->batch_tab.dev, n};
 
     const int depth = c0->pair.st.depth;
     const size_t row = (size_t)W * 3 * (depth == PSM_IMG_F32 ? 4 : 1);
@@ -191,18 +190,19 @@ extern "C" int psm_compute_batch(psm_ctx *const *ctxs, int n)
         // ---- CostConst: CVC::preprocess of every image (the cost volumes stay virtual) - float mode: inside the guidance launch ----
         if (u8) {
             Prof p(c0, PSM_K_PREP);
-            launch_prep_batch(s, dt, n, row, depth == PSM_IMG_F32, W, H, u8);
+            launch_prep(s, q, row, depth == PSM_IMG_F32, W, 0, H, false);
+            launch_prep(s, q, row, depth == PSM_IMG_F32, W, 0, H, true);
         }
         t1 = now_us();
         // ---- CostFilter: guidance of every image, the fused select kernel over every pair, the reduction ----
         {
             Prof p(c0, PSM_K_GUIDE);
-            launch_guidance(s, P, W, H, 0, H, false, u8 ? 0 : (depth == PSM_IMG_F32 ? 2 : 1), row);
+            launch_guidance(s, q, W, H, 0, H, false, u8 ? 0 : (depth == PSM_IMG_F32 ? 2 : 1), row);
         }
-        if (enqueue_select(c0, P, sp)) return 1;
+        if (enqueue_select(c0, q, sp)) return 1;
         if (sp.two_phase && whole) {
             Prof p(c0, PSM_K_MERGE);
-            launch_merge_batch(s, dt, n, W, H);
+            launch_merge_batch(s, q, W, H);
         }
         return check_launch(c0, "batch (prep, guidance, fused select filter, reduction)");
     };
@@ -210,7 +210,7 @@ extern "C" int psm_compute_batch(psm_ctx *const *ctxs, int n)
     if (c0->opt_graph && c0->opt_profile == 0) {
         // One graph per frame: the kernels read every pair through the device table (whose ADDRESS is all the graph holds), so the
         // captured launches stay valid while the batch size, the geometry and the options do - also across new image pairs.
-        const long long sig[8] = {n, (long long)(size_t)dt, c0->march.flags, c0->march.seg_rows, depth, Dloc, c0->d0, (long long)W << 32 | H};
+        const long long sig[8] = {n, (long long)(size_t)q.dev, c0->march.flags, c0->march.seg_rows, depth, Dloc, c0->d0, (long long)W << 32 | H};
         if (!c0->batch_graph || memcmp(sig, c0->graph_sig, sizeof sig) != 0) {
             if (c0->batch_graph) { (void)hipGraphExecDestroy(c0->batch_graph); c0->batch_graph = nullptr; }
             hipGraph_t g = nullptr;

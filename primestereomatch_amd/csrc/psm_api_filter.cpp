@@ -107,32 +107,27 @@ int ensure_planes(psm_ctx *c, Rows g1_need, Rows guid_need)
     if (!need_g1 && !need_guid) return 0;
     const bool f32_img = c->pair.st.depth == PSM_IMG_F32;
     const size_t row = (size_t)c->W * 3 * (f32_img ? 4 : 1);
+    const PcPair pair = pc_pair(c);
+    const Recs<PcPair> q = {&pair, nullptr, 1};
     if (need_g1 && need_guid && c->dtype == PSM_F32) {
         {
             Prof p(c, PSM_K_GUIDE);
-            launch_guidance(c->stream, PcPairs{nullptr, 1, pc_pair(c)}, c->W, c->H, g1_need.y0, g1_need.y1, fma_solve(c), f32_img ? 2 : 1, row);
+            launch_guidance(c->stream, q, c->W, c->H, g1_need.y0, g1_need.y1, fma_solve(c), f32_img ? 2 : 1, row);
         }
         if (check_launch(c, "prep + guidance") || images_read(c, c->stream)) return 1;
         guid_need = g1_need;
     } else {
         if (need_g1) {
-            const int ya = g1_need.y0, rows = g1_need.y1 - ya;
-            const size_t o = (size_t)ya * c->W;
-            {   // both images in one launch
+            for (int u8 = 0; u8 < (c->dtype == PSM_U8 ? 2 : 1); ++u8) {   // both images per launch: g1, then the byte planes of an 8-bit context
                 Prof p(c, PSM_K_PREP);
-                launch_prep(c->stream, (const char *)c->pair.raw[0] + ya * row, row, f32_img, c->W, rows, c->g[0].g1 + o,
-                            (const char *)c->pair.raw[1] + ya * row, c->g[1].g1 + o);
-            }
-            for (int s = 0; s < 2 && c->dtype == PSM_U8; ++s) {
-                Prof p(c, PSM_K_PREP);
-                launch_prep_u8(c->stream, (const uint8_t *)c->pair.raw[s] + ya * row, row, c->W, rows, c->p4[s] + 4 * o, c->g[s].g1 + o);
+                launch_prep(c->stream, q, row, f32_img, c->W, g1_need.y0, g1_need.y1, u8 != 0);
             }
             if (check_launch(c, "prep") || images_read(c, c->stream)) return 1;
         }
         if (need_guid) {
             {
                 Prof p(c, PSM_K_GUIDE);
-                launch_guidance(c->stream, PcPairs{nullptr, 1, pc_pair(c)}, c->W, c->H, guid_need.y0, guid_need.y1, fma_solve(c));
+                launch_guidance(c->stream, q, c->W, c->H, guid_need.y0, guid_need.y1, fma_solve(c));
             }
             if (check_launch(c, "guidance")) return 1;
         }
@@ -165,24 +160,24 @@ SelPlan select_plan(const psm_ctx *c, int npairs, bool batch)
     return sp;
 }
 
-// Plane form (all slices, or every S-th) -> reduction -> key form (the others) for the pairs P on c's stream, with c's brackets
+// Plane form (all slices, or every S-th) -> reduction -> key form (the others) for the pairs q on c's stream, with c's brackets
 // and launch stamps.  Every pair's scratch holds sp.scratch_bytes.
-int enqueue_select(psm_ctx *c, const PcPairs &P, const SelPlan &sp)
+int enqueue_select(psm_ctx *c, const Recs<PcPair> &q, const SelPlan &sp)
 {
     const bool u8 = c->dtype == PSM_U8;
     {
         Prof p(c, PSM_K_CVF_F);
-        launch_cvf_select2(c->stream, c->march, P, u8, c->W, c->H, sp.n1, c->d0, next_pc_stamp(c), sp.two_phase ? 1 : 0, sp.S);
+        launch_cvf_select2(c->stream, c->march, q, u8, c->W, c->H, sp.n1, c->d0, next_pc_stamp(c), sp.two_phase ? 1 : 0, sp.S);
     }
     // (a single context's maps may still be the source of the last frame's download; a batch waited for its contexts' before the table)
-    if (sp.maps && !P.tab && maps_writable(c)) return 1;
+    if (sp.maps && !q.dev && maps_writable(c)) return 1;
     {
         Prof p(c, PSM_K_WTA);
-        launch_chunk_min2sides(c->stream, c->march, P, c->W, c->H, sp.n1, sp.maps, c->d0, sp.two_phase ? 1 : 0, sp.S);
+        launch_chunk_min2sides(c->stream, c->march, q, c->W, c->H, sp.n1, sp.maps, c->d0, sp.two_phase ? 1 : 0, sp.S);
     }
     if (sp.n2 > 0) {
         Prof p(c, PSM_K_CVF_F);
-        launch_cvf_select_keys2(c->stream, c->march, P, u8, c->W, c->H, sp.n2, c->d0, next_pc_stamp(c), 2, sp.S);
+        launch_cvf_select_keys2(c->stream, c->march, q, u8, c->W, c->H, sp.n2, c->d0, next_pc_stamp(c), 2, sp.S);
     }
     return 0;
 }
@@ -275,7 +270,10 @@ int filter_side_select(psm_ctx *c, int side)
     }
     {
         Prof p(c, PSM_K_WTA);
-        launch_chunk_min(c->stream, c->march, W, H, c->Dloc, c->gf_scratch, c->keys_cur + side * (size_t)W * H, nullptr);
+        PcPair one = {};                 // the one volume's planes and keys
+        one.scratch = c->gf_scratch;
+        one.keys = c->keys_cur + side * (size_t)W * H;
+        launch_chunk_min(c->stream, c->march, Recs<PcPair>{&one, nullptr, 1}, W, H, c->Dloc);
     }
     filtered_to_keys(c->vside[side]);
     return check_launch(c, "cvf (fused, select mode)");
@@ -335,7 +333,8 @@ int filter_both(psm_ctx *c)
     if (ensure_planes(c, need.g1, need.guid)) return 1;
     const SelPlan sp = select_plan(c, 1, false);
     if (ensure_gf_scratch(c, sp.scratch_bytes)) return 1;
-    if (enqueue_select(c, PcPairs{nullptr, 1, pc_pair(c)}, sp)) return 1;
+    const PcPair pair = pc_pair(c);
+    if (enqueue_select(c, Recs<PcPair>{&pair, nullptr, 1}, sp)) return 1;
     for (VolSide &v : c->vside) filtered_to_keys(v);
     filtered(c->res, stripe_rows(c), sp.maps ? c->maps : nullptr);
     return check_launch(c, sp.two_phase ? "cvf (fused, select mode, two phases, both volumes)" : "cvf (fused, select mode, both volumes)");

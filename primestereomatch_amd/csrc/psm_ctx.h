@@ -497,7 +497,7 @@ struct SelPlan {
     size_t scratch_bytes;   // chunk planes per pair (both volumes)
 };
 SelPlan select_plan(const psm_ctx *c, int npairs, bool batch);
-int enqueue_select(psm_ctx *c, const PcPairs &P, const SelPlan &sp);
+int enqueue_select(psm_ctx *c, const Recs<PcPair> &q, const SelPlan &sp);
 // PSM_FLAG_FMA_SOLVE applies to float mode only (8-bit contexts never carry the bit: psm_set_option)
 inline bool fma_solve(const psm_ctx *c) { return c->dtype == PSM_F32 && (c->march.flags & PSM_FLAG_FMA_SOLVE) != 0; }
 // psm_create_shard_strided: the slices of such a context exist in the select forms of the fused kernel only

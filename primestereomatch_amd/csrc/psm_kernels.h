@@ -36,7 +36,7 @@ struct March {       // geometry of the marching kernels
 
 // ---- batched launches: B stereo pairs of one geometry share every launch of the default path (psm_compute_batch; the
 // reference's use on Middlebury-size data is a loop over pairs, src/main.cpp:64-73) ----
-struct PcPair {                  // one pair's buffers: an entry of a batch's device table the kernels index with the pair number
+struct PcPair {                  // one pair's buffers: what a single call passes by value, an entry of a batch's device table (Recs below)
     const void *raw[2];          // staged interleaved images (left, right)
     Guidance g[2];
     uint8_t *p4[2];              // 8-bit char mode: {c0,c1,c2,grad} byte planes (else null)
@@ -44,87 +44,8 @@ struct PcPair {                  // one pair's buffers: an entry of a batch's de
     long long *keys;             // [2][H][W] packed minima
     uint8_t *maps;               // [2][H][W]
 };
-// The pairs one launch of the select path covers: the single pair `one` (tab == nullptr, n == 1; its pointers go into the
-// kernels' arguments), or the n pairs of the device table `tab` (psm_compute_batch; blockIdx.z = pair, `one` unused)
-struct PcPairs {
-    const PcPair *tab;
-    int n;
-    PcPair one;
-};
-void launch_prep_batch(hipStream_t s, const PcPair *tab, int npairs, size_t pitch, int depth_f32, int W, int H, bool u8_planes);
-void launch_merge_batch(hipStream_t s, const PcPair *tab, int npairs, int W, int H);   // keys -> maps of every pair
-
-// device <-> page-locked host copy as a kernel (both pointers 16-byte aligned)
-void launch_copy_bytes(hipStream_t s, void *dst, const void *src, size_t bytes);
-// biased-exponent range of n floats: out[0] = max, out[1] = min over the non-zero values (initialise out to {0, 255})
-void launch_range_f32(hipStream_t s, const float *p, size_t n, unsigned *out);
-// image -> g1 (planarise, scale, gray, x-gradient).  src: device copy of the interleaved image.
-void launch_prep(hipStream_t s, const void *src, size_t pitch, int depth_f32, int W, int H, float4 *g1, const void *src1 = nullptr,
-                 float4 *g11 = nullptr);
-// g1 -> g2,g3,g4 of both images of every pair in P, one launch ([ybeg, yend): rows of g2..g4 to produce, yend <= ybeg: all).
-// fma: PSM_FLAG_FMA_SOLVE - minors and DET in their fused forms.  src 1 / 2: image preparation (launch_prep) in the same launch
-// from the pairs' staged 8-bit / float images (raw, row pitch `pitch`) - the g1 rows [ybeg, yend) are written from them
-void launch_guidance(hipStream_t s, const PcPairs &P, int W, int H, int ybeg, int yend, bool fma, int src = 0, size_t pitch = 0);
-// cost volume slices [d_begin, d_begin+Dloc) of one side.  base: g1 of the side's own image.
-void launch_cvc(hipStream_t s, const float4 *g1_base, const float4 *g1_other, float *vol, int W, int H,
-                int d_begin, int Dloc, int right, int ybeg, int yend);
-// Stage A of the guided filter alone (the debug entry psm_filter_stage_a; tests compare (a0,a1,a2,b) with the oracle's
-// intermediates).  variant 0 = marching, 1 = direct per-voxel.  [ybeg, yend): output rows of this launch (the arithmetic
-// always refers to the full H-row planes).  Stage B alone exists in the direct formulation only (cross-check).
-void launch_cvf_a(hipStream_t s, int variant, March m, const float *vol, float4 *ab, Guidance g, int W,
-                  int H, int Dloc, int ybeg, int yend);
-void launch_cvf_b_direct(hipStream_t s, const float4 *ab, float *vol, Guidance g, int W, int H, int Dloc);
-// fused stage A+B: vin -> vout (distinct buffers), output rows [ybeg, yend) within [4, H-3)
-// cvc_mode 0: read the cost slices from vin; 1/2: build the left/right costs on the fly from the g1 planes
-void launch_cvf_fused(hipStream_t s, March m, const float *vin, float *vout, Guidance g, int W, int H, int Dloc,
-                      int ybeg, int yend, const float4 *g1_other, int d_begin, int cvc_mode, unsigned long long *ts = nullptr);
-// The same kernel with the winner-takes-all fused in ("select" forms): the filtered volume is never written.
-//   plane form: per pixel the running minimum over chunks of DC slices in scratch planes -> launch_chunk_min* -> packed WTA keys
-//   key form:   64-bit atomicMin on a key plane that already holds good bounds (second phase of the two-phase selection)
-struct PcDev { int nxcd = 0, cus_per_xcd = 0; };
-PcDev pc_dev();                                                  // of the device the calling thread is bound to
-enum { PC_STORE = 0, PC_PLANES = 1, PC_KEYS = 2, PC_BOTH = 4 };  // forms of pc_plan (PC_BOTH: both volumes per launch)
-struct PcPlan {
-    int ngroups, nsegs, seg_rows, DC, nchunks, nbmax, nxcd;
-    int cols;                                                    // output columns per column group (107; 50 in the narrow layout; 96 storing form)
-    bool narrow;                                                 // two-wave workgroups (one producer + one consumer wave)
-    size_t rec_per_chunk;                                        // records per chunk plane
-    int rec_bytes;                                               // bytes per record (costs + disparities)
-    size_t scratch_bytes() const { return rec_per_chunk * (size_t)nchunks * rec_bytes; }
-};
-PcPlan pc_plan(int W, int rows, int Dloc, int seg_rows_opt, int form, int batch = 1, int inflight = 1);   // batch: pairs per launch (psm_compute_batch); inflight: March::inflight
-// pc_plan of the two-volume select launches (form PC_PLANES / PC_KEYS) of npairs pairs; batch: the pairs of psm_compute_batch
-PcPlan pc_plan_select(March m, int W, int H, int Dloc, int form, int npairs, bool batch);
-int pc_seed_stride(int W, int rows, bool u8);                     // S of the two-phase selection: every S-th slice seeds the key plane (rows: of the stripe being filtered)
-// ts (may be NULL): slot of this launch in a buffer of 3 x PC_TS_SLOTS 64-bit words {first workgroup start | last workgroup
-// end | form} in ticks of the device's constant-rate clock (PSM_OPT_PROFILE 2, psm_filter_launch_times)
-constexpr int PC_TS_SLOTS = 4096;
-// one volume per launch (costs read from vin, cvc_mode 0, or built on the fly, 1 / 2; p4_*: 8-bit char mode)
-void launch_cvf_select(hipStream_t s, March m, const float *vin, Guidance g, int W, int H, int Dloc, const float4 *g1_other,
-                       int d_begin, int cvc_mode, void *scratch, unsigned long long *ts = nullptr, const uint8_t *p4_own = nullptr,
-                       const uint8_t *p4_other = nullptr);
-void launch_chunk_min(hipStream_t s, March m, int W, int H, int Dloc, void *scratch, long long *keys, uint8_t *map);
-// both volumes of every pair in P per launch (costs on the fly; u8: 8-bit char mode): the left volume is filtered with the guidance
-// g[0] of the left image, the right one with g[1]; keys / maps: [2][H][W] per pair; grid z = pair (a single pair: 1).  Dloc slices,
-// which ones: (sel, step) - 0: all, 1: every step-th, 2: the others.
-// ... plane form: chunk planes in each pair's scratch (2 x pc_plan_select(..., PC_PLANES, ...).scratch_bytes())
-void launch_cvf_select2(hipStream_t s, March m, const PcPairs &P, bool u8, int W, int H, int Dloc, int d_begin, unsigned long long *ts,
-                        int sel, int step);
-// ... their reduction to each pair's keys; to_maps: the maps as well
-// d_begin, (sel, step): as given to launch_cvf_select2 - chunks it did not walk (psm_live.h) are not read
-void launch_chunk_min2sides(hipStream_t s, March m, const PcPairs &P, int W, int H, int Dloc, bool to_maps, int d_begin, int sel, int step);
-// ... key form: continues from the minima each pair's keys hold (the second phase of the two-phase selection)
-void launch_cvf_select_keys2(hipStream_t s, March m, const PcPairs &P, bool u8, int W, int H, int Dloc, int d_begin,
-                             unsigned long long *ts, int sel, int step);
-// plain 8x8 box filter of every slice (the north-star kernel in isolation)
-void launch_box8(hipStream_t s, int variant, March m, const float *vol, float *out, int W, int H, int Dloc);
-// WTA over local slices -> packed keys (keys != NULL) and/or final map (map != NULL)
-void launch_wta(hipStream_t s, const float *vol, int W, int H, int d_begin, int Dloc, long long *keys,
-                uint8_t *map);
-// min over nranks key planes -> map
-void launch_merge(hipStream_t s, const long long *keys_all, size_t rank_stride, int nranks, int n,
-                  uint8_t *map);
-// ---- record sources: what every stage with a batch entry (post-processing tail, JointWMF, SGM and speckle, score, depth, WLS) shares ----
+// ---- record sources: what every stage with a batch entry (the default path - prep, guidance, fused select filter, reduction -,
+// post-processing tail, JointWMF, SGM and speckle, score, depth, WLS) shares ----
 // The n records R of one launch as the host filled them, the record on a grid axis.  dev == nullptr: the records of a single call
 // travel by value in the kernarg (RecVal: one record; the two of JointWMF's single pair); else the kernels read the n records of the
 // device table at dev.  Either way the index is uniform per workgroup: scalar loads ahead of one body.  Every kernel of these stages
@@ -169,6 +90,83 @@ void rec_launch(hipStream_t st, void (*kv)(H, RecVal<R, N>, A...), void (*kt)(H,
     hipLaunchKernelGGL(kv, grid, block, lds, st, head, v, rest...);
 }
 
+// the default path's two sources: its kernels are templates over S = PcVal (120 bytes of kernarg) or PcTab
+using PcVal = RecVal<PcPair>;
+using PcTab = RecTab<PcPair>;
+void launch_merge_batch(hipStream_t s, const Recs<PcPair> &q, int W, int H);   // keys -> maps of every pair of a batch's table
+
+// device <-> page-locked host copy as a kernel (both pointers 16-byte aligned)
+void launch_copy_bytes(hipStream_t s, void *dst, const void *src, size_t bytes);
+// biased-exponent range of n floats: out[0] = max, out[1] = min over the non-zero values (initialise out to {0, 255})
+void launch_range_f32(hipStream_t s, const float *p, size_t n, unsigned *out);
+// staged images (raw, row pitch `pitch`) -> rows [y0, y1) of g1 (planarise, scale, gray, x-gradient) of both images of every pair in
+// q, one launch.  u8_planes: the launch of 8-bit char mode instead - the {c0,c1,c2,grad} byte planes p4, the same word also into
+// g1[..].w (bit pattern) of the image's g1 plane: after the launch that writes g1
+void launch_prep(hipStream_t s, const Recs<PcPair> &q, size_t pitch, int depth_f32, int W, int y0, int y1, bool u8_planes);
+// g1 -> g2,g3,g4 of both images of every pair in q, one launch ([ybeg, yend): rows of g2..g4 to produce, yend <= ybeg: all).
+// fma: PSM_FLAG_FMA_SOLVE - minors and DET in their fused forms.  src 1 / 2: image preparation (launch_prep) in the same launch
+// from the pairs' staged 8-bit / float images (raw, row pitch `pitch`) - the g1 rows [ybeg, yend) are written from them
+void launch_guidance(hipStream_t s, const Recs<PcPair> &q, int W, int H, int ybeg, int yend, bool fma, int src = 0, size_t pitch = 0);
+// cost volume slices [d_begin, d_begin+Dloc) of one side.  base: g1 of the side's own image.
+void launch_cvc(hipStream_t s, const float4 *g1_base, const float4 *g1_other, float *vol, int W, int H,
+                int d_begin, int Dloc, int right, int ybeg, int yend);
+// Stage A of the guided filter alone (the debug entry psm_filter_stage_a; tests compare (a0,a1,a2,b) with the oracle's
+// intermediates).  variant 0 = marching, 1 = direct per-voxel.  [ybeg, yend): output rows of this launch (the arithmetic
+// always refers to the full H-row planes).  Stage B alone exists in the direct formulation only (cross-check).
+void launch_cvf_a(hipStream_t s, int variant, March m, const float *vol, float4 *ab, Guidance g, int W,
+                  int H, int Dloc, int ybeg, int yend);
+void launch_cvf_b_direct(hipStream_t s, const float4 *ab, float *vol, Guidance g, int W, int H, int Dloc);
+// fused stage A+B: vin -> vout (distinct buffers), output rows [ybeg, yend) within [4, H-3)
+// cvc_mode 0: read the cost slices from vin; 1/2: build the left/right costs on the fly from the g1 planes
+void launch_cvf_fused(hipStream_t s, March m, const float *vin, float *vout, Guidance g, int W, int H, int Dloc,
+                      int ybeg, int yend, const float4 *g1_other, int d_begin, int cvc_mode, unsigned long long *ts = nullptr);
+// The same kernel with the winner-takes-all fused in ("select" forms): the filtered volume is never written.
+//   plane form: per pixel the running minimum over chunks of DC slices in scratch planes -> launch_chunk_min* -> packed WTA keys
+//   key form:   64-bit atomicMin on a key plane that already holds good bounds (second phase of the two-phase selection)
+struct PcDev { int nxcd = 0, cus_per_xcd = 0; };
+PcDev pc_dev();                                                  // of the device the calling thread is bound to
+enum { PC_STORE = 0, PC_PLANES = 1, PC_KEYS = 2, PC_BOTH = 4 };  // forms of pc_plan (PC_BOTH: both volumes per launch)
+struct PcPlan {
+    int ngroups, nsegs, seg_rows, DC, nchunks, nbmax, nxcd;
+    int cols;                                                    // output columns per column group (107; 50 in the narrow layout; 96 storing form)
+    bool narrow;                                                 // two-wave workgroups (one producer + one consumer wave)
+    size_t rec_per_chunk;                                        // records per chunk plane
+    int rec_bytes;                                               // bytes per record (costs + disparities)
+    size_t scratch_bytes() const { return rec_per_chunk * (size_t)nchunks * rec_bytes; }
+};
+PcPlan pc_plan(int W, int rows, int Dloc, int seg_rows_opt, int form, int batch = 1, int inflight = 1);   // batch: pairs per launch (psm_compute_batch); inflight: March::inflight
+// pc_plan of the two-volume select launches (form PC_PLANES / PC_KEYS) of npairs pairs; batch: the pairs of psm_compute_batch
+PcPlan pc_plan_select(March m, int W, int H, int Dloc, int form, int npairs, bool batch);
+int pc_seed_stride(int W, int rows, bool u8);                     // S of the two-phase selection: every S-th slice seeds the key plane (rows: of the stripe being filtered)
+// ts (may be NULL): slot of this launch in a buffer of 3 x PC_TS_SLOTS 64-bit words {first workgroup start | last workgroup
+// end | form} in ticks of the device's constant-rate clock (PSM_OPT_PROFILE 2, psm_filter_launch_times)
+constexpr int PC_TS_SLOTS = 4096;
+// one volume per launch (costs read from vin, cvc_mode 0, or built on the fly, 1 / 2; p4_*: 8-bit char mode)
+void launch_cvf_select(hipStream_t s, March m, const float *vin, Guidance g, int W, int H, int Dloc, const float4 *g1_other,
+                       int d_begin, int cvc_mode, void *scratch, unsigned long long *ts = nullptr, const uint8_t *p4_own = nullptr,
+                       const uint8_t *p4_other = nullptr);
+// ... its reduction: the chunk planes in q's scratch -> q's keys (one volume's: [H][W])
+void launch_chunk_min(hipStream_t s, March m, const Recs<PcPair> &q, int W, int H, int Dloc);
+// both volumes of every pair in q per launch (costs on the fly; u8: 8-bit char mode): the left volume is filtered with the guidance
+// g[0] of the left image, the right one with g[1]; keys / maps: [2][H][W] per pair; grid z = pair (a single pair: 1).  Dloc slices,
+// which ones: (sel, step) - 0: all, 1: every step-th, 2: the others.
+// ... plane form: chunk planes in each pair's scratch (2 x pc_plan_select(..., PC_PLANES, ...).scratch_bytes())
+void launch_cvf_select2(hipStream_t s, March m, const Recs<PcPair> &q, bool u8, int W, int H, int Dloc, int d_begin, unsigned long long *ts,
+                        int sel, int step);
+// ... their reduction to each pair's keys; to_maps: the maps as well
+// d_begin, (sel, step): as given to launch_cvf_select2 - chunks it did not walk (psm_live.h) are not read
+void launch_chunk_min2sides(hipStream_t s, March m, const Recs<PcPair> &q, int W, int H, int Dloc, bool to_maps, int d_begin, int sel, int step);
+// ... key form: continues from the minima each pair's keys hold (the second phase of the two-phase selection)
+void launch_cvf_select_keys2(hipStream_t s, March m, const Recs<PcPair> &q, bool u8, int W, int H, int Dloc, int d_begin,
+                             unsigned long long *ts, int sel, int step);
+// plain 8x8 box filter of every slice (the north-star kernel in isolation)
+void launch_box8(hipStream_t s, int variant, March m, const float *vol, float *out, int W, int H, int Dloc);
+// WTA over local slices -> packed keys (keys != NULL) and/or final map (map != NULL)
+void launch_wta(hipStream_t s, const float *vol, int W, int H, int d_begin, int Dloc, long long *keys,
+                uint8_t *map);
+// min over nranks key planes -> map
+void launch_merge(hipStream_t s, const long long *keys_all, size_t rank_stride, int nranks, int n,
+                  uint8_t *map);
 // (the left-right check and the fill of invalid pixels: with the post-processing tail below, PpRecs)
 
 // weighted-median post-filter of one map, in place, with the reference's raster-order semantics (psm_pp.hip).
@@ -224,9 +222,7 @@ bool fgf_can_fuse_wta(int W);
 void launch_fgf_apply_wta(hipStream_t s, const float4 *g1, int W, int H, int Dloc, int d_begin, int sub, const float4 *mab,
                           long long *keys);
 
-// ---- 8-bit char mode ----
-// ({c0,c1,c2,grad} byte planes; the same word also into g1[..].w - bit pattern - of the image's g1 plane: launch_prep first)
-void launch_prep_u8(hipStream_t s, const uint8_t *src, size_t pitch, int W, int H, uint8_t *planes4, float4 *g1);
+// ---- 8-bit char mode ----  (the {c0,c1,c2,grad} byte planes: launch_prep)
 void launch_cvc_u8(hipStream_t s, const uint8_t *base4, const uint8_t *other4, uint8_t *vol, int W, int H,
                    int d_begin, int Dloc, int right);
 void launch_u8_to_f32(hipStream_t s, const uint8_t *src, float *dst, size_t n);

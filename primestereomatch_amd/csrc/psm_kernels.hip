@@ -46,29 +46,21 @@ __device__ __forceinline__ void load_px(const void *src, size_t pitch, int y, in
     }
 }
 
-template <bool F32>
-__global__ __launch_bounds__(256) void k_prep(const void *src, size_t pitch, int W, int H, float4 *g1, const void *src1, float4 *g11,
-                                             const PcPair *__restrict__ tab)
+// row y0 + blockIdx.y of image z & 1 of pair z >> 1 of the record source S (psm_kernels.h, Recs): PcVal or PcTab
+template <bool F32, typename S>
+__global__ __launch_bounds__(256) void k_prep(S src, size_t pitch, int W, int y0)
 {
-    int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (tab) { src = tab[blockIdx.z >> 1].raw[blockIdx.z & 1]; g1 = tab[blockIdx.z >> 1].g[blockIdx.z & 1].g1; }   // batch: image z & 1 of pair z >> 1
-    else if (blockIdx.z == 1) { src = src1; g1 = g11; }    // second image of a two-image launch
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = y0 + blockIdx.y, img = blockIdx.z & 1;
+    const PcPair &p = rec(src, blockIdx.z >> 1);
+    const void *raw = sgm_global(p.raw[img]);
+    float4 *g1 = sgm_global(p.g[img].g1);
     if (x >= W) return;
     float c0, c1, c2, l0, l1, l2, r0, r1, r2;
-    load_px<F32>(src, pitch, y, x, c0, c1, c2);
-    load_px<F32>(src, pitch, y, r101(x - 1, W), l0, l1, l2);
-    load_px<F32>(src, pitch, y, r101(x + 1, W), r0, r1, r2);
+    load_px<F32>(raw, pitch, y, x, c0, c1, c2);
+    load_px<F32>(raw, pitch, y, r101(x - 1, W), l0, l1, l2);
+    load_px<F32>(raw, pitch, y, r101(x + 1, W), r0, r1, r2);
     float grd = __fsub_rn(gray_of(r0, r1, r2), gray_of(l0, l1, l2));
     g1[(size_t)y * W + x] = make_float4(c0, c1, c2, grd);
-}
-
-void launch_prep(hipStream_t s, const void *src, size_t pitch, int depth_f32, int W, int H, float4 *g1, const void *src1, float4 *g11)
-{   // src1 != NULL: both images in one launch
-    dim3 grid((W + 255) / 256, H, src1 ? 2 : 1);
-    if (depth_f32)
-        hipLaunchKernelGGL(k_prep<true>, grid, dim3(256), 0, s, src, pitch, W, H, g1, src1, g11, (const PcPair *)nullptr);
-    else
-        hipLaunchKernelGGL(k_prep<false>, grid, dim3(256), 0, s, src, pitch, W, H, g1, src1, g11, (const PcPair *)nullptr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -178,19 +170,18 @@ __device__ __forceinline__ void guide_finish(const float *m, float4 &g2, float4 
 // (u8: (float)b * (1/255.0f) as load_px; float: as it is), and wave 0 also forms gray and the x-gradient from its lane neighbours
 // (the lanes of a wave hold consecutive columns, reflected at the image border exactly as r101 asks) and writes the g1 rows the
 // workgroup owns: one launch instead of k_prep + k_guide_march, and g1 is written once instead of written and read back.
-template <int SRC>
-__global__ __launch_bounds__(192) void k_guide_march(const float4 *g1, int W, int H, int nstrips, int seg_rows,
-                                                    float4 *g2, float4 *g3, float2 *g4, Guidance second, int ybeg, int yend,
-                                                    const PcPair *__restrict__ tab, int fma, const void *raw0, const void *raw1, size_t pitch)
+// Image y & 1 of pair y >> 1 of the record source S.
+template <int SRC, typename S>
+__global__ __launch_bounds__(192) void k_guide_march(S src, int W, int H, int nstrips, int seg_rows, int ybeg, int yend, int fma, size_t pitch)
 {
     __shared__ float ms[2][4][9][64];            // [batch parity][row of the batch][channel][lane]
-    const void *raw = raw0;
-    float4 *g1w = const_cast<float4 *>(g1);      // SRC != 0: g1 is an OUTPUT
-    if (tab) {   // batch: image y & 1 of pair y >> 1
-        const Guidance gg = tab[blockIdx.y >> 1].g[blockIdx.y & 1];
-        g1 = gg.g1; g1w = gg.g1; g2 = gg.g2; g3 = gg.g3; g4 = gg.g4;
-        raw = tab[blockIdx.y >> 1].raw[blockIdx.y & 1];
-    } else if (blockIdx.y == 1) { g1 = second.g1; g1w = second.g1; g2 = second.g2; g3 = second.g3; g4 = second.g4; raw = raw1; }   // second image of a two-image launch
+    const PcPair &p = rec(src, blockIdx.y >> 1);
+    const Guidance &gg = p.g[blockIdx.y & 1];
+    const void *const raw = sgm_global(p.raw[blockIdx.y & 1]);
+    float4 *const g1w = sgm_global(gg.g1);       // SRC != 0: g1 is an OUTPUT
+    const float4 *const g1 = g1w;
+    float4 *const g2 = sgm_global(gg.g2), *const g3 = sgm_global(gg.g3);
+    float2 *const g4 = sgm_global(gg.g4);
     const int strip = blockIdx.x % nstrips, seg = blockIdx.x / nstrips;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int x0 = strip * 56;
@@ -264,25 +255,25 @@ __global__ __launch_bounds__(192) void k_guide_march(const float4 *g1, int W, in
     }
 }
 
-void launch_guidance(hipStream_t s, const PcPairs &P, int W, int H, int ybeg, int yend, bool fma, int src, size_t pitch)
+void launch_guidance(hipStream_t s, const Recs<PcPair> &q, int W, int H, int ybeg, int yend, bool fma, int src, size_t pitch)
 {   // [ybeg, yend): the rows of g2..g4 to produce - a row stripe of the filter needs its own rows + 4 either side.  src != 0:
     // CVC::preprocess in the same launch - the images are read from the staged interleaved copies, and the g1 rows [ybeg, yend)
-    // are WRITTEN.  A single pair passes its planes and images in the arguments; a table is read by the kernel (blockIdx.y = image)
+    // are WRITTEN.  grid y = 2 x pair + image
     if (yend <= ybeg) { ybeg = 0; yend = H; }
     const int rows = yend - ybeg;
     // one workgroup of three waves per (strip, segment); segments as short as still fill ~2 workgroups per SIMD-quad of the
     // chip in one resident round (8..64 rows each: 7 halo rows per segment)
     const int nstrips = (W + 55) / 56;
     const PcDev dev = pc_dev();
-    const int wgs = std::max(1, 6 * dev.nxcd * dev.cus_per_xcd / (2 * P.n));   // per image (87 VGPRs, 18 KB of LDS: ~6 resident workgroups per CU)
+    const int wgs = std::max(1, 6 * dev.nxcd * dev.cus_per_xcd / (2 * q.n));   // per image (87 VGPRs, 18 KB of LDS: ~6 resident workgroups per CU)
     int seg_rows = 8;
     while (seg_rows < 64 && nstrips * ((rows + seg_rows - 1) / seg_rows) > wgs) ++seg_rows;
     const int nsegs = (rows + seg_rows - 1) / seg_rows;
-    const Guidance gl = P.tab ? Guidance{} : P.one.g[0], gr = P.tab ? Guidance{} : P.one.g[1];
-    const bool raw = !P.tab && src != 0;
-    hipLaunchKernelGGL(src == 1 ? k_guide_march<1> : (src == 2 ? k_guide_march<2> : k_guide_march<0>), dim3(nstrips * nsegs, 2 * P.n),
-                       dim3(192), 0, s, (const float4 *)gl.g1, W, H, nstrips, seg_rows, gl.g2, gl.g3, gl.g4, gr, ybeg, yend, P.tab,
-                       fma ? 1 : 0, raw ? P.one.raw[0] : nullptr, raw ? P.one.raw[1] : nullptr, pitch);
+    const dim3 grid(nstrips * nsegs, 2 * q.n);
+    auto go = [&](auto kv, auto kt) { rec_launch(s, kv, kt, grid, dim3(192), 0, q, W, H, nstrips, seg_rows, ybeg, yend, fma ? 1 : 0, pitch); };
+    if (src == 1) go(k_guide_march<1, PcVal>, k_guide_march<1, PcTab>);
+    else if (src == 2) go(k_guide_march<2, PcVal>, k_guide_march<2, PcTab>);
+    else go(k_guide_march<0, PcVal>, k_guide_march<0, PcTab>);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -788,10 +779,10 @@ __global__ __launch_bounds__(256) void k_merge_batch(const PcPair *__restrict__ 
     if (i >= n) return;
     tab[blockIdx.y].maps[i] = (uint8_t)((unsigned long long)tab[blockIdx.y].keys[i] & 0xffull);
 }
-void launch_merge_batch(hipStream_t s, const PcPair *tab, int npairs, int W, int H)
-{
+void launch_merge_batch(hipStream_t s, const Recs<PcPair> &q, int W, int H)
+{   // (only a batch merges here: the kernel reads the table)
     const int n = 2 * W * H;
-    hipLaunchKernelGGL(k_merge_batch, dim3((n + 255) / 256, npairs), dim3(256), 0, s, tab, n);
+    hipLaunchKernelGGL(k_merge_batch, dim3((n + 255) / 256, q.n), dim3(256), 0, s, q.dev, n);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -903,15 +894,17 @@ __device__ __forceinline__ int gray_u8(const uint8_t *p)
 }
 
 // planes4[y][x] = {c0, c1, c2, grad} as one 32-bit word per pixel
-__global__ __launch_bounds__(256) void k_prep_u8(const uint8_t *src, size_t pitch, int W, int H, uchar4 *out, const PcPair *__restrict__ tab, float4 *g1)
+// (the pair and the row as k_prep finds them)
+template <typename S>
+__global__ __launch_bounds__(256) void k_prep_u8(S src, size_t pitch, int W, int y0)
 {
-    int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (tab) {
-        src = (const uint8_t *)tab[blockIdx.z >> 1].raw[blockIdx.z & 1]; out = (uchar4 *)tab[blockIdx.z >> 1].p4[blockIdx.z & 1];
-        g1 = tab[blockIdx.z >> 1].g[blockIdx.z & 1].g1;
-    }
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = y0 + blockIdx.y, img = blockIdx.z & 1;
+    const PcPair &pp = rec(src, blockIdx.z >> 1);
+    const uint8_t *raw = (const uint8_t *)sgm_global(pp.raw[img]);
+    uchar4 *out = (uchar4 *)sgm_global(pp.p4[img]);
+    float4 *g1 = sgm_global(pp.g[img].g1);
     if (x >= W) return;
-    const uint8_t *row = src + (size_t)y * pitch;
+    const uint8_t *row = raw + (size_t)y * pitch;
     const uint8_t *p = row + 3 * x;
     int g = gray_u8(row + 3 * r101(x + 1, W)) - gray_u8(row + 3 * r101(x - 1, W));
     g = g < 0 ? 0 : (g > 255 ? 255 : g);
@@ -921,19 +914,12 @@ __global__ __launch_bounds__(256) void k_prep_u8(const uint8_t *src, size_t pitc
     // float gradient - the pixel's four bytes ride in that slot (bit pattern), which saves them a load instruction per step
     reinterpret_cast<uchar4 *>(&g1[(size_t)y * W + x])[3] = w;
 }
-void launch_prep_u8(hipStream_t s, const uint8_t *src, size_t pitch, int W, int H, uint8_t *planes4, float4 *g1)
+void launch_prep(hipStream_t s, const Recs<PcPair> &q, size_t pitch, int depth_f32, int W, int y0, int y1, bool u8_planes)
 {
-    hipLaunchKernelGGL(k_prep_u8, dim3((W + 255) / 256, H), dim3(256), 0, s, src, pitch, W, H, (uchar4 *)planes4, (const PcPair *)nullptr, g1);
-}
-void launch_prep_batch(hipStream_t s, const PcPair *tab, int npairs, size_t pitch, int depth_f32, int W, int H, bool u8_planes)
-{
-    const dim3 grid((W + 255) / 256, H, 2 * npairs);
-    if (depth_f32)
-        hipLaunchKernelGGL(k_prep<true>, grid, dim3(256), 0, s, (const void *)nullptr, pitch, W, H, (float4 *)nullptr, (const void *)nullptr, (float4 *)nullptr, tab);
-    else
-        hipLaunchKernelGGL(k_prep<false>, grid, dim3(256), 0, s, (const void *)nullptr, pitch, W, H, (float4 *)nullptr, (const void *)nullptr, (float4 *)nullptr, tab);
-    if (u8_planes)
-        hipLaunchKernelGGL(k_prep_u8, grid, dim3(256), 0, s, (const uint8_t *)nullptr, pitch, W, H, (uchar4 *)nullptr, tab, (float4 *)nullptr);
+    const dim3 grid((W + 255) / 256, y1 - y0, 2 * q.n), block(256);
+    if (u8_planes) rec_launch(s, k_prep_u8<PcVal>, k_prep_u8<PcTab>, grid, block, 0, q, pitch, W, y0);
+    else if (depth_f32) rec_launch(s, k_prep<true, PcVal>, k_prep<true, PcTab>, grid, block, 0, q, pitch, W, y0);
+    else rec_launch(s, k_prep<false, PcVal>, k_prep<false, PcTab>, grid, block, 0, q, pitch, W, y0);
 }
 
 __device__ __forceinline__ uint8_t cost_u8(int clr3, int grd)

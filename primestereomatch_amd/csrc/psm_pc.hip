@@ -646,31 +646,26 @@ void k_cvf_pc(
 // chunk planes -> packed WTA key and / or final map per pixel (minimum over the chunks; pack_key_f32 makes the signed
 // 64-bit minimum select (min cost, then lowest d) exactly as the sequential loop of src/DispSel.cpp:96-104).
 // One thread per record (pair, batch, column) = four rows of one column, as the select kernel wrote them.
-__global__ __launch_bounds__(256) void k_chunk_min(const float4 *kcost, const unsigned *kdisp, int nchunks, int npairs,
-                                                  int nbmax, int ngroups, int seg_rows, int W, int H, long long *keys,
-                                                  uint8_t *map, const float4 *__restrict__ kcost1, const unsigned *__restrict__ kdisp1,
-                                                  int ybeg, int yend, const PcPair *__restrict__ batch, int to_maps, int cols,
-                                                  PcLive lv)
+// The pair (blockIdx.z) comes from the record source S (psm_kernels.h, Recs): its scratch holds, per side (blockIdx.y, as in the
+// select kernel), the float4 cost records of all chunks, then their uchar4 disparity records - 20 bytes a record.
+template <typename S>
+__global__ __launch_bounds__(256) void k_chunk_min(S src, int nchunks, int npairs, int nbmax, int ngroups, int seg_rows, int W, int H,
+                                                  int ybeg, int yend, int to_maps, int cols, PcLive lv)
 {   // cols: output columns per (column group) of the layout the select kernel ran with (107 / 50)
     // lv: the select launch's item table - the chunks it walked for each column group; the others' records were never written
-    // (blockIdx.y = side, as in the select kernel)
-    if (batch) {             // batched launch: blockIdx.z = pair, planes / keys / maps from the table
-        const PcPair pp = batch[blockIdx.z];
-        const size_t rec_total = (size_t)npairs * nbmax * cols * nchunks;
-        kcost = (const float4 *)pp.scratch;
-        kdisp = (const unsigned *)(kcost + rec_total);
-        kcost1 = (const float4 *)((const char *)pp.scratch + rec_total * 20);
-        kdisp1 = (const unsigned *)(kcost1 + rec_total);
-        keys = pp.keys;
-        map = to_maps ? pp.maps : nullptr;
-    }
-    if (blockIdx.y == 1) {   // second volume of a two-side launch: its own planes, keys / map one image further
-        kcost = kcost1;
-        kdisp = kdisp1;
+    const PcPair &pp = rec(src, blockIdx.z);
+    const size_t nrec = (size_t)npairs * nbmax * cols;          // records per chunk plane
+    const size_t rec_total = nrec * nchunks;
+    // (a side's offsets are selected, not multiplied by blockIdx.y: the 64-bit scalar multiplies of every wave measured 0.2 - 0.5 us
+    // at 450 x 375, profiles/default_path_records_speed.txt)
+    const float4 *kcost = (const float4 *)((const char *)sgm_global(pp.scratch) + (blockIdx.y == 1 ? rec_total * 20 : 0));
+    const unsigned *kdisp = (const unsigned *)(kcost + rec_total);
+    long long *keys = sgm_global(pp.keys);
+    uint8_t *map = to_maps ? sgm_global(pp.maps) : nullptr;
+    if (blockIdx.y == 1) {   // the second volume: its keys / map lie one image further
         if (keys) keys += (size_t)W * H;
         if (map) map += (size_t)W * H;
     }
-    const size_t nrec = (size_t)npairs * nbmax * cols;          // records per chunk plane
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= nrec) return;
     const int col = (int)(idx % cols);
@@ -968,15 +963,12 @@ static int pc_var(March m, bool u8)
     return u8 ? 0 : (m.flags & PSM_FLAG_FMA_SOLVE) ? 2 : (m.flags & PSM_FLAG_F32_TOL) ? 1 : 0;
 }
 
-// The one launch of k_chunk_min: `sides` volumes (chunk planes in `scratch`, or from the table `tab`) of `npairs` pairs.
-static void pc_chunk_min(hipStream_t s, March m, const PcPlan &pl, int W, int H, int sides, int npairs, void *scratch,
-                         long long *keys, uint8_t *map, const PcLive &lv, const PcPair *tab = nullptr, bool to_maps = false)
+// The one launch of k_chunk_min: `sides` volumes of every pair in q (chunk planes as pc_planes lays them out in the pair's scratch).
+static void pc_chunk_min(hipStream_t s, March m, const PcPlan &pl, int W, int H, int sides, const Recs<PcPair> &q, const PcLive &lv, bool to_maps)
 {
-    const PcSide p0 = scratch ? pc_planes(pl, scratch, 0) : PcSide{}, p1 = scratch && sides == 2 ? pc_planes(pl, scratch, 1) : PcSide{};
-    hipLaunchKernelGGL(k_chunk_min, dim3((unsigned)((pl.rec_per_chunk + 255) / 256), sides, npairs), dim3(256), 0, s,
-                       (const float4 *)p0.kcost, (const unsigned *)p0.kdisp, pl.nchunks, pl.ngroups * pl.nsegs, pl.nbmax, pl.ngroups,
-                       pl.seg_rows, W, H, keys, map, (const float4 *)p1.kcost, (const unsigned *)p1.kdisp, m.y0(H), m.y1(H), tab,
-                       to_maps ? 1 : 0, pl.cols, lv);
+    rec_launch(s, k_chunk_min<PcVal>, k_chunk_min<PcTab>, dim3((unsigned)((pl.rec_per_chunk + 255) / 256), sides, q.n),
+               dim3(256), 0, q, pl.nchunks, pl.ngroups * pl.nsegs, pl.nbmax, pl.ngroups, pl.seg_rows, W, H, m.y0(H), m.y1(H), to_maps ? 1 : 0,
+               pl.cols, lv);
 }
 
 // Storing form (MODE 0): vin (or, cvc_mode 1 / 2, the costs built on the fly) -> vout, one slice per workgroup.
@@ -1009,10 +1001,10 @@ void launch_cvf_select(hipStream_t s, March m, const float *vin, Guidance gd, in
     pc_launch(s, pl, dim3(pc_blocks(pl, lv)), a, {PC_PLANES, cvc, u8, (m.flags & PSM_FLAG_FMA_SOLVE) ? 2 : 0, false, false, false});
 }
 
-void launch_chunk_min(hipStream_t s, March m, int W, int H, int Dloc, void *scratch, long long *keys, uint8_t *map)
+void launch_chunk_min(hipStream_t s, March m, const Recs<PcPair> &q, int W, int H, int Dloc)
 {
     const PcPlan pl = pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_PLANES);
-    pc_chunk_min(s, m, pl, W, H, 1, 1, scratch, keys, map, pc_live(W, pl.cols, pl.ngroups, Dloc, pl.DC, true, PcOwn{}));
+    pc_chunk_min(s, m, pl, W, H, 1, q, pc_live(W, pl.cols, pl.ngroups, Dloc, pl.DC, true, PcOwn{}), false);
 }
 
 // pc_plan of the two-volume select launches.  A single context plans the rows of its stripe together with the frames other contexts
@@ -1025,16 +1017,16 @@ PcPlan pc_plan_select(March m, int W, int H, int Dloc, int form, int npairs, boo
     return pc_plan(W, m.rows(H), Dloc, m.seg_rows, form | PC_BOTH, npairs, batch ? 1 : m.inflight);
 }
 
-// The arguments of a two-volume select launch (form PC_PLANES / PC_KEYS) for the pairs P, costs built on the fly: left volume =
-// (g[0], other g[1].g1), right = (g[1], other g[0].g1).  A single pair passes its planes here - 8-bit mode: the byte planes
-// {c0,c1,c2,grad} of the left / right image as vin / vout; the minima: chunk planes in its scratch, or its keys -, the batched forms
-// read every pointer of a pair from the table.
-static PcArgs pc_args2(March m, const PcPlan &pl, int form, const PcPairs &P, bool u8, int W, int H, int Dloc, int d_begin, PcSel sel,
+// The arguments of a two-volume select launch (form PC_PLANES / PC_KEYS) for the pairs q, costs built on the fly: left volume =
+// (g[0], other g[1].g1), right = (g[1], other g[0].g1).  A single pair (q.host[0]) passes its planes here - 8-bit mode: the byte
+// planes {c0,c1,c2,grad} of the left / right image as vin / vout; the minima: chunk planes in its scratch, or its keys -, the batched
+// forms read every pointer of a pair from the table q.dev.
+static PcArgs pc_args2(March m, const PcPlan &pl, int form, const Recs<PcPair> &q, bool u8, int W, int H, int Dloc, int d_begin, PcSel sel,
                        unsigned long long *ts)
 {
-    PcArgs a = {nullptr, nullptr, W, H, Dloc, m.y0(H), m.y1(H), d_begin, {}, sel, ts, P.tab};
-    if (P.tab) return a;
-    const PcPair &p = P.one;
+    PcArgs a = {nullptr, nullptr, W, H, Dloc, m.y0(H), m.y1(H), d_begin, {}, sel, ts, q.dev};
+    if (q.dev) return a;
+    const PcPair &p = q.host[0];
     if (u8) { a.vin = (const float *)p.p4[0]; a.vout = (float *)p.p4[1]; }
     for (int v = 0; v < 2; ++v) {
         const PcSide k = form == PC_PLANES ? pc_planes(pl, p.scratch, v) : PcSide{};
@@ -1044,32 +1036,31 @@ static PcArgs pc_args2(March m, const PcPlan &pl, int form, const PcPairs &P, bo
     return a;
 }
 
-void launch_cvf_select2(hipStream_t s, March m, const PcPairs &P, bool u8, int W, int H, int Dloc, int d_begin, unsigned long long *ts,
+void launch_cvf_select2(hipStream_t s, March m, const Recs<PcPair> &q, bool u8, int W, int H, int Dloc, int d_begin, unsigned long long *ts,
                         int sel, int step)
 {
-    const PcPlan pl = pc_plan_select(m, W, H, Dloc, PC_PLANES, P.n, P.tab != nullptr);
+    const PcPlan pl = pc_plan_select(m, W, H, Dloc, PC_PLANES, q.n, q.dev != nullptr);
     const PcLive lv = pc_live(W, pl.cols, pl.ngroups, Dloc, pl.DC, true, pc_own(m, d_begin, sel, step));
-    const unsigned long long rec_total = P.tab ? (unsigned long long)pl.rec_per_chunk * pl.nchunks : 0;   // (read by the batched form only)
-    const PcArgs a = pc_args2(m, pl, PC_PLANES, P, u8, W, H, Dloc, d_begin, PcSel{sel, step, pl.nxcd, 0, rec_total, m.dstep, lv}, ts);
-    pc_launch(s, pl, dim3(pc_blocks(pl, lv), 2, P.n), a, {PC_PLANES, 3, u8, pc_var(m, u8), P.tab != nullptr, pl.narrow, false});
+    const unsigned long long rec_total = q.dev ? (unsigned long long)pl.rec_per_chunk * pl.nchunks : 0;   // (read by the batched form only)
+    const PcArgs a = pc_args2(m, pl, PC_PLANES, q, u8, W, H, Dloc, d_begin, PcSel{sel, step, pl.nxcd, 0, rec_total, m.dstep, lv}, ts);
+    pc_launch(s, pl, dim3(pc_blocks(pl, lv), 2, q.n), a, {PC_PLANES, 3, u8, pc_var(m, u8), q.dev != nullptr, pl.narrow, false});
 }
 
-void launch_chunk_min2sides(hipStream_t s, March m, const PcPairs &P, int W, int H, int Dloc, bool to_maps, int d_begin, int sel, int step)
+void launch_chunk_min2sides(hipStream_t s, March m, const Recs<PcPair> &q, int W, int H, int Dloc, bool to_maps, int d_begin, int sel, int step)
 {
-    const PcPlan pl = pc_plan_select(m, W, H, Dloc, PC_PLANES, P.n, P.tab != nullptr);
+    const PcPlan pl = pc_plan_select(m, W, H, Dloc, PC_PLANES, q.n, q.dev != nullptr);
     const PcLive lv = pc_live(W, pl.cols, pl.ngroups, Dloc, pl.DC, true, pc_own(m, d_begin, sel, step));    // the select launch's own table
-    if (P.tab) pc_chunk_min(s, m, pl, W, H, 2, P.n, nullptr, nullptr, nullptr, lv, P.tab, to_maps);
-    else pc_chunk_min(s, m, pl, W, H, 2, 1, P.one.scratch, P.one.keys, to_maps ? P.one.maps : nullptr, lv);
+    pc_chunk_min(s, m, pl, W, H, 2, q, lv, to_maps);
 }
 
-void launch_cvf_select_keys2(hipStream_t s, March m, const PcPairs &P, bool u8, int W, int H, int Dloc, int d_begin,
+void launch_cvf_select_keys2(hipStream_t s, March m, const Recs<PcPair> &q, bool u8, int W, int H, int Dloc, int d_begin,
                              unsigned long long *ts, int sel, int step)
 {
-    const PcPlan pl = pc_plan_select(m, W, H, Dloc, PC_KEYS, P.n, P.tab != nullptr);
+    const PcPlan pl = pc_plan_select(m, W, H, Dloc, PC_KEYS, q.n, q.dev != nullptr);
     const PcLive lv = pc_live(W, pl.cols, pl.ngroups, Dloc, 1, false, pc_own(m, d_begin, sel, step));
-    const PcArgs a = pc_args2(m, pl, PC_KEYS, P, u8, W, H, Dloc, d_begin,
+    const PcArgs a = pc_args2(m, pl, PC_KEYS, q, u8, W, H, Dloc, d_begin,
                               PcSel{sel, step, pl.nxcd, PSM_KNOB("PSM_PC_SPREAD", PC_KEY_SPREAD), 0, m.dstep, lv}, ts);
-    pc_launch(s, pl, dim3(pc_blocks(pl, lv), 2, P.n), a, {PC_KEYS, 3, u8, pc_var(m, u8), P.tab != nullptr, pl.narrow, false});
+    pc_launch(s, pl, dim3(pc_blocks(pl, lv), 2, q.n), a, {PC_KEYS, 3, u8, pc_var(m, u8), q.dev != nullptr, pl.narrow, false});
 }
 
 }  // namespace psm

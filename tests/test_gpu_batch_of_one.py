@@ -1,11 +1,13 @@
-"""-m gpu: a batch of ONE against the single call, stage by stage - SGM with the speckle filter on, its map select, score, depth,
-WLS.  The two reach their pair's record through different sources (psm_kernels.h, Recs: the single call passes it by value in the
-kernarg, the batch - of one too - reads the device table), launch by launch the same kernels: every output must be equal in every
-bit, and equal to the stage's numpy model.  No tolerance anywhere in this file.
+"""-m gpu: a batch of ONE against the single call, stage by stage - the default path (prep, guidance, fused select filter,
+reduction), SGM with the speckle filter on, its map select, score, depth, WLS.  The two reach their pair's record through different
+sources (psm_kernels.h, Recs: the single call passes it by value in the kernarg, the batch - of one too - reads the device table),
+launch by launch the same kernels: every output must be equal in every bit, and equal to the stage's numpy model (the default
+path: the CPU oracle).  No tolerance anywhere in this file.
 
 Shapes: the smallest image a context takes, 8 x 8, and 65 x 9 - one row past the 64-line group of the WLS passes, and inside one
 256-pixel tile of the depth, WLS and score kernels at 8 x 8 but across three of them at 65 x 9.  SGM runs them with 2 and 9
-disparities: a context takes no max_disp above its width (psm_create), and the stage needs two."""
+disparities: a context takes no max_disp above its width (psm_create), and the stage needs two.  The default path has shapes of
+its own (DEFAULT_SHAPES)."""
 import os
 
 import numpy as np
@@ -45,6 +47,103 @@ def cal():
 
 def rnd(seed):
     return np.random.default_rng(seed)
+
+
+# ---- the default path: psm_cost_construct + psm_cost_filter + psm_disp_select against psm_compute_batch ----
+# 8 x 8 x 8: the smallest context - one guidance strip, one column group, one partial 4-row record of the reduction; 57 x 9: two
+# 56-column guidance strips, H no multiple of 4; 108 x 9 x 12: the narrow layout's three 50-column groups.  (With 2 disparities an
+# 8 x 8 map would be constant, and a constant map cannot tell a wrong pointer.)
+DEFAULT_SHAPES = ((8, 8, 8), (57, 9, 8), (108, 9, 12))
+SEEDS = (1, 2, 3)
+TWO_PHASE_ON, MATERIALISE_COSTS = 1048576, 128           # PSM_FLAG_* (include/primesm_hip.h)
+_default_refs = {}
+
+
+def default_refs(oracle, W, H, D, dtype):
+    """the pairs of SEEDS and the oracle's maps of each: computed once per shape and mode, shared by the tests below, never written to"""
+    key = (W, H, D, dtype)
+    if key not in _default_refs:
+        from primestereomatch_amd import synth
+        pairs = [synth.make_pair(W, H, D, seed)[:2] for seed in SEEDS]
+        pipe = oracle.pipeline_u8 if dtype == "u8" else oracle.pipeline_f32
+        maps = []
+        for l, r in pairs:
+            ref = pipe(l, r, D, threads=2)
+            maps.append((ref["ldisp"], ref["rdisp"]))
+            for m in maps[-1]:
+                m.setflags(write=False)
+                assert len(np.unique(m)) >= 2, "a constant map cannot tell a wrong pointer"
+        _default_refs[key] = (pairs, maps)
+    return _default_refs[key]
+
+
+def guidance(de):
+    """all 14 planes of both images, as bit patterns (an 8-bit context keeps a pixel's bytes in GrdX's slot: not a number)"""
+    return [de.download_guidance(side).view(np.uint32).copy() for side in (0, 1)]
+
+
+def same(a, b):
+    return all(x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x, y) for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("flags", (0, TWO_PHASE_ON))
+@pytest.mark.parametrize("dtype", ("f32", "u8"))
+@pytest.mark.parametrize("W,H,D", DEFAULT_SHAPES)
+def test_default_path(psm, oracle, W, H, D, dtype, flags):
+    from primestereomatch_amd.dispest import compute_batch
+    capi = psm.capi
+    pairs, want = default_refs(oracle, W, H, D, dtype)
+    single = []                                                                  # per pair: (maps, guidance) of the three single calls
+    # the batches run on contexts of their own that never saw a single call: outputs they did not write could not come out equal
+    with psm.DispEst(*pairs[0], D, dtype=dtype) as one:
+        one.set_option(capi.PSM_OPT_FLAGS, flags)
+        for (l, r), w in zip(pairs, want):
+            one.setInputImages(l, r)
+            one.CostConst_GPU(); one.CostFilter_GPU(); one.DispSelect_GPU()
+            single.append(((one.lDisMap.copy(), one.rDisMap.copy()), guidance(one)))
+            assert same(single[-1][0], w)
+    members = [psm.DispEst(l, r, D, dtype=dtype) for l, r in pairs]
+    try:
+        for de in members:
+            de.set_option(capi.PSM_OPT_FLAGS, flags)
+        compute_batch(members[:1])                                               # a batch of one reads the device table
+        assert same(members[0].download_maps(), single[0][0]) and same(members[0].download_maps(), want[0])
+        assert same(guidance(members[0]), single[0][1])
+        compute_batch(members)                                                   # the three pairs in one set of launches
+        for de, (maps, planes), w in zip(members, single, want):
+            assert same(de.download_maps(), maps) and same(de.download_maps(), w)
+            assert same(guidance(de), planes)
+    finally:
+        for de in members:
+            de.close()
+
+
+def test_one_volume_reduction(psm, oracle):
+    """psm_cost_filter_side over a materialised volume: the one-volume plane form and the reduction of ONE side (grid y = 1), whose
+    record carries the context's scratch and the side's half of the key planes"""
+    W, H, D = 57, 9, 8
+    pairs, want = default_refs(oracle, W, H, D, "f32")
+    with psm.DispEst(*pairs[0], D) as de:
+        de.set_option(psm.capi.PSM_OPT_FLAGS, MATERIALISE_COSTS)
+        de.CostConst_GPU()
+        de.CostFilter_side(0); de.CostFilter_side(1)
+        de.DispSelect_GPU()
+        assert same((de.lDisMap, de.rDisMap), want[0])
+
+
+def test_prep_of_a_row_stripe(psm, oracle):
+    """an 8-bit context prepares the rows of its stripe only (k_prep, k_prep_u8: the first row is an argument), then the whole image"""
+    W, H, D = 57, 40, 8
+    pairs, want = default_refs(oracle, W, H, D, "u8")
+    with psm.DispEst(*pairs[0], D, dtype="u8") as de:
+        de.set_rows(11, 23)
+        de.CostConst_GPU(); de.CostFilter_GPU(); de.DispSelect_device()
+        assert same([m[11:23] for m in de.download_maps()], [m[11:23] for m in want[0]])
+        de.set_rows(0, 0)
+        for k in (0, 1):                                                         # whole-image frames, of this pair and of a new one
+            de.setInputImages(*pairs[k])
+            de.CostConst_GPU(); de.CostFilter_GPU(); de.DispSelect_GPU()
+            assert same((de.lDisMap, de.rDisMap), want[k])
 
 
 @pytest.mark.parametrize("cap", (0, 63))

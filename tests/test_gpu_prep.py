@@ -82,7 +82,9 @@ def test_merged_launch_on_row_stripes_and_a_second_pair(psm, oracle):
 def test_a_float_frame_launches_no_preparation_kernel(psm):
     from primestereomatch_amd import capi, synth
     l, r, _ = synth.make_pair(320, 200, 48, seed=1)
-    for dtype, nprep in (("f32", 0), ("u8", 3)):            # 8-bit contexts keep k_prep (+ k_prep_u8 per image: their byte planes)
+    # 8-bit contexts keep k_prep and k_prep_u8 (their byte planes), each ONE launch over both images - as a batch always ran them;
+    # k_prep_u8 used to be launched once per image, which made three
+    for dtype, nprep in (("f32", 0), ("u8", 2)):
         with psm.DispEst(l, r, 48, dtype=dtype) as de:
             de.CostConst_GPU(); de.CostFilter_GPU(); de.DispSelect_GPU()
             de.set_option(capi.PSM_OPT_PROFILE, 1)
