@@ -866,6 +866,42 @@ int psm_wls_time(psm_ctx *ctx, double *ms);
  * on == 0, or psm_release_scratch (which frees the planes): every call is again bit for bit what it is without this stage. */
 int psm_wls_publish(psm_ctx *ctx, int on);
 
+/* ---- the guided-filter path over a one-channel pair ----
+ * Cost build, guided-filter aggregation and winner-takes-all of a monochrome pair in one call: what FastGuidedFilter's dispatch on
+ * I.channels() intends (src/fastguidedfilter.cpp:38-49,89-119) - the one-channel reading of GuidedFilter_cv (src/CVF.cpp:72-165) over
+ * costs that are myCostGrd (src/CVC.cpp:18-39) with the colour sum over one channel and the x-gradient of the plane itself.  Four box
+ * filters per voxel instead of eight, no 3 x 3 solve.  The definition, which the device equals in every bit, is
+ * tests/gray_model.py: per side, with I the side's own plane, mI = box(I), inv = 1 / (box(I I) - mI mI + 1e-4f);
+ * per slice p: a = inv (box(I p) - mI box(p)), b = box(p) - a mI, q = box(b) + box(a) I; fp32 operations rounded one by one, box =
+ * cv::boxFilter(Size(8,8)) in this library's order; selection d = 1 .. max_disp - 1, strict <, default 0.
+ * l, r: host planes, H rows of W one-channel pixels stride_bytes apart (0: packed) - bytes (depth PSM_IMG_U8, scaled by 1/255.0f
+ * as psm_upload_pair scales) or floats (PSM_IMG_F32, used as they are).  The staged colour pair and its slots are untouched.  The
+ * maps go to the context's map buffer and - lmap / rmap, either may be NULL - to H rows of W bytes map_stride apart (0: packed).
+ * Afterwards the context is exactly where psm_sgm_select_maps leaves it: whole-image maps are current, there is no mask; volumes,
+ * minima and anything pending of the colour path are untouched, so psm_lr_check, psm_fill_invalid, psm_score(PSM_SCORE_GIF),
+ * psm_download_maps* and psm_reproject work behind it as they do there.  On the context's stream; synchronous on return unless
+ * PSM_OPT_ASYNC is set (the upload of the planes always completes before the call returns).  The PSM_FLAG_* values of the float
+ * path are ignored: there is one arithmetic.  No volume is ever held: the stage's buffers - 8 bytes per pixel for the pair, 16 per
+ * pixel and side of guidance, 16 per pixel of minima and a scratch of at most 32 slices' {a, b} of both sides (at most 1 GiB,
+ * whatever max_disp is) - are allocated on first use and given back by psm_release_scratch and psm_destroy.
+ * Refused - psm_last_error names the call, nothing has been enqueued, the previous maps are still current - for a NULL context
+ * (psm_last_error(NULL)), NULL planes, an unknown depth, a stride below a row, a map_stride below W, a PSM_U8 context, a disparity
+ * shard, a row stripe in force (psm_set_rows).
+ * Out of scope: batches, FrameRing, the Fast Guided Filter variant, 8-bit mode, rectified upload, and the tail stages that read
+ * the image - psm_wgt_median, psm_joint_wmf, the guide of psm_wls_filter and the colours of psm_reproject's cloud keep reading
+ * the staged colour pair.  psm_upload_pair* keep refusing 1 channel. */
+int psm_gray_compute(psm_ctx *ctx, const void *l, const void *r, size_t stride_bytes, int depth, uint8_t *lmap, uint8_t *rmap,
+                     size_t map_stride);
+/* Device ms of the launches of the last psm_gray_compute (guidance, every chunk, the maps); needs PSM_OPT_PROFILE. */
+int psm_gray_time(psm_ctx *ctx, double *ms);
+/* Test hooks on the pair of the last psm_gray_compute (refused before any, and after psm_release_scratch).
+ * psm_gray_guidance: planes receives [4][H][W] floats of `side`: I, G, mI, inv.
+ * psm_gray_volume: the slices [d0, d1) of `side` through the storing instantiation of the same kernels (slice 0 included, which
+ * the selection never computes): q receives [d1-d0][H][W] floats, ab - may be NULL - [d1-d0][2][H][W]: the planes a and b of
+ * every slice.  The chunks of the walk begin at d0.  Keys and maps are not touched.  Both synchronise. */
+int psm_gray_guidance(psm_ctx *ctx, int side, float *planes);
+int psm_gray_volume(psm_ctx *ctx, int side, int d0, int d1, float *q, float *ab);
+
 /* ---- debug / bench entry points (no counterpart in the reference) ---- */
 /* Test hook of the score stage: an int16 map (H rows of W values, pitch stride_bytes; 0: packed) that the SGM sources of
  * psm_score read from now on instead of the map of the last psm_sgm_compute - maps no compute would produce.  Kept in a plane

@@ -178,6 +178,10 @@ SYMBOLS = [
     ("psm_wls_download_table", _i, [_vp, _vp]),
     ("psm_wls_time", _i, [_vp, _pd]),
     ("psm_wls_publish", _i, [_vp, _i]),
+    ("psm_gray_compute", _i, [_vp, _vp, _vp, _sz, _i, _vp, _vp, _sz]),
+    ("psm_gray_time", _i, [_vp, _pd]),
+    ("psm_gray_guidance", _i, [_vp, _i, _vp]),
+    ("psm_gray_volume", _i, [_vp, _i, _i, _i, _vp, _vp]),
 ]
 
 _lib = None

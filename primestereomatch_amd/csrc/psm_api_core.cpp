@@ -115,6 +115,7 @@ void free_all(psm_ctx *c)
     score_free(c, true);
     depth_free(c);
     wls_free(c);
+    gray_free(c);
     (void)hipFree(c->fvol);
     (void)hipFree(c->spare);
     (void)hipFree(c->ab);
@@ -494,6 +495,7 @@ int psm_release_scratch(psm_ctx *c)
     score_free(c, false);
     depth_free(c);
     wls_free(c);
+    gray_free(c);
     for (int k = 0; k < 2; ++k)
         if (c->xfer_pin[k]) { (void)hipHostFree(c->xfer_pin[k]); c->xfer_pin[k] = nullptr; c->xfer_pin_bytes[k] = 0; }
     (void)hipGetLastError();

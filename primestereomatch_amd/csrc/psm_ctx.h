@@ -22,6 +22,8 @@
 //   psm_api_depth.cpp   from disparity to depth: cv::reprojectImageTo3D of the current result and the compacted point cloud
 //                       (psm_reproject), and of the results of several contexts in shared launches (psm_reproject_batch) - one
 //                       sequence, reproject_run
+//   psm_api_gray.cpp    the guided-filter path over a one-channel pair: one-channel fused filter and selection of host planes
+//                       (psm_gray_compute), its test hooks and timer (psm::GrayState)
 //   psm_api_wls.cpp     edge-aware WLS smoothing of the sub-pixel int16 map (psm_wls_filter), of the maps of several contexts in
 //                       shared launches (psm_wls_filter_batch) - one sequence, wls_run - and the switch that lets the SGM sources
 //                       of psm_score / psm_reproject read its result (psm_wls_publish)
@@ -216,6 +218,19 @@ struct WlsState {
     DevTable pairs;                                // psm_wls_filter_batch (this context as the first of a batch): WlsPair records
 };
 
+// psm_gray_compute (psm_api_gray.cpp): the stage's own device buffers - the pair's planes, 16 bytes of guidance per pixel and side,
+// the chunk scratch, the key plane - allocated on first use and given back by gray_free alone.  Nothing else in the context reads
+// or writes any of it; the stage meets the rest in the map buffer and psm::Results only.
+struct GrayState {
+    void *raw[2] = {nullptr, nullptr};             // the pair's planes [H][W], room for floats
+    float2 *ig[2] = {nullptr, nullptr};            // {I, G}
+    float2 *mv[2] = {nullptr, nullptr};            // {mI, 1 / (var + eps)}
+    float2 *ab = nullptr;                          // [2][gray_plan().dc][H][W] {a, b} of one chunk of slices
+    long long *keys = nullptr;                     // [2][H][W]: this stage's packed minima (ctx->keys belongs to the colour path)
+    int depth = -1;                                // PSM_IMG_* of the last call's pair, which the planes hold; -1: none
+    Bracket prof;                                  // PSM_OPT_PROFILE: around the launches (psm_gray_time)
+};
+
 // The image pair every frame starts with, and the second slot the next frame travels into (psm_upload_pair_async,
 // psm_upload_pair_rectified_async).  `st` is changed by its transitions (psm_state.h) alone, the rest by the functions declared
 // under "the image pair slots" below.
@@ -288,6 +303,7 @@ struct psm_ctx {
     psm::ScoreState score;
     psm::DepthState depth;
     psm::WlsState wls;
+    psm::GrayState gray;
     uint8_t *p4[2] = {nullptr, nullptr};  // PSM_U8 only: {c0,c1,c2,grad} words
     // What stands for vol[side] (psm_state.h): costs that are a recipe, a filtered volume pending as packed minima or as FGF models.
     // The WTA consumes either form directly; any other reader makes the volume real first (materialize()).
@@ -561,6 +577,8 @@ inline Colour colour_of(const psm_ctx *c, bool sgm_source)
 }
 // psm_api_wls.cpp
 void wls_free(psm_ctx *c);                       // the stage's planes and events (its parameters stay); publishing is switched off
+// psm_api_gray.cpp
+void gray_free(psm_ctx *c);                      // the stage's buffers and events: no pair of a psm_gray_compute is left
 // psm_api_select.cpp: copy_maps_out - two [H][W] planes on the device to the caller's rows
 int copy_maps_out(psm_ctx *c, const uint8_t *dev, uint8_t *lmap, uint8_t *rmap, size_t stride);
 

@@ -449,4 +449,22 @@ void launch_wls_init(hipStream_t s, const Recs<WlsPair> &q);                   /
 void launch_wls_rows(hipStream_t s, const Recs<WlsPair> &q, int t);            // k_wls_rows: pass t over every row
 void launch_wls_cols(hipStream_t s, const Recs<WlsPair> &q, int t, bool last);   // k_wls_cols: ... every column; last: and the quotient, out and q
 
+// psm_gray.hip: the one-channel guided filter over a one-channel pair (psm_gray_compute, psm_api_gray.cpp)
+constexpr int GRAY_COLS = 56;                          // output columns of a wave's strip
+constexpr int GRAY_DC_MAX = 32;                        // slices of a chunk at most
+constexpr size_t GRAY_SCRATCH_MAX = (size_t)1 << 30;   // bytes of the chunk scratch at most (but four slices always fit)
+struct GrayPair {
+    const void *raw[2];                // the pair's planes [H][W]: bytes (PSM_IMG_U8) or floats (PSM_IMG_F32)
+    float2 *ig[2];                     // [H][W] {I, G}: the plane and its x-gradient
+    float2 *mv[2];                     // [H][W] {mI, 1 / (var + eps)}
+    float2 *ab;                        // the chunk scratch [2][dc][H][W] {a, b}
+    long long *keys;                   // [2][H][W] packed minima of this stage (not the colour path's)
+};
+struct GrayPlan { int nstrips, nsegs, seg_rows, dc; };   // strips of GRAY_COLS columns, segments of seg_rows rows, slices per chunk
+GrayPlan gray_plan(int W, int H, int D);                // for the device the calling thread is bound to (pc_dev)
+void launch_gray_prep(hipStream_t s, const GrayPair &p, const GrayPlan &g, int W, int H, bool f32);   // k_gray_prep: ig, mv of both sides; keys = no candidate
+// k_gray_ab, k_gray_q over the slices [dbeg, dend) (at most g.dc) of the sides [side0, side0 + nsides): minima into p.keys, or -
+// qvol != null, nsides 1: the storing form - q into qvol [dend - dbeg][H][W]; {a, b} of the slices are in p.ab either way
+void launch_gray_chunk(hipStream_t s, const GrayPair &p, const GrayPlan &g, int W, int H, int side0, int nsides, int dbeg, int dend, float *qvol);
+
 }  // namespace psm

@@ -45,7 +45,19 @@ class DispEst:
             raise ValueError("DE: Error - Left & Right images are of different types.")
         if l.ndim != 3 or l.shape[2] != 3:
             raise ValueError("DispEst: images must be H x W x 3")
-        self.hei, self.wid = int(l.shape[0]), int(l.shape[1])
+        self._create(int(l.shape[0]), int(l.shape[1]), d, t, dtype, device, d_range, d_stride)
+        self.setInputImages(l, r)
+
+    @classmethod
+    def blank(cls, hei: int, wid: int, d: int, t: int = 8, *, dtype: str = "f32", device: int = 0, d_range=None, d_stride=None):
+        """A DispEst of the given size without an image pair: what Gray_GPU and SGBM_GPU(gray=...) need, which bring their own
+        one-channel planes.  Every method that reads the staged colour pair is refused until setInputImages has run."""
+        self = cls.__new__(cls)
+        self._create(int(hei), int(wid), d, t, dtype, device, d_range, d_stride)
+        return self
+
+    def _create(self, hei, wid, d, t, dtype, device, d_range, d_stride):
+        self.hei, self.wid = hei, wid
         self.maxDis = int(d)
         self.threads = int(t)
         self.useOCL = True
@@ -71,7 +83,6 @@ class DispEst:
         self.rDisMap = np.zeros((self.hei, self.wid), np.uint8)
         self.lValid = np.zeros((self.hei, self.wid), np.uint8)
         self.rValid = np.zeros((self.hei, self.wid), np.uint8)
-        self.setInputImages(l, r)
 
     # ---- lifetime -------------------------------------------------------------------------
     def close(self):
@@ -250,6 +261,51 @@ class DispEst:
             return self.lDisMap, self.rDisMap
         self._ck(self._lib.psm_sgm_select_maps(self._h, None, None, 0), "SGBMSelect_GPU")
         return None
+
+    # ---- the guided-filter path over a one-channel pair (psm_gray_compute) --------------------------
+    def Gray_GPU(self, gl, gr, download: bool = True):
+        """Cost build, one-channel guided filter and winner-takes-all of the monochrome pair (gl, gr) - two H x W planes, uint8 or
+        float32 (uint8 is scaled by 1/255 as setInputImages scales) - in one call; the definition is tests/gray_model.py.  The maps
+        land in the object's device maps, where LRCheck_GPU, FillInv_GPU, Score_GPU(PSM_SCORE_GIF), Reproject_GPU and
+        download_maps() find them; the staged colour pair, the volumes and whatever CostFilter_GPU left pending are untouched.
+        -> (lDisMap, rDisMap); download=False: the maps stay on the device, None."""
+        gl, gr = np.asarray(gl), np.asarray(gr)
+        if gl.shape != (self.hei, self.wid) or gr.shape != gl.shape or gl.dtype != gr.dtype:
+            raise ValueError("Gray_GPU: gl, gr must be two H x W planes of one type and of the size DispEst was built for")
+        if gl.dtype == np.uint8:
+            depth = capi.PSM_IMG_U8
+        elif gl.dtype == np.float32:
+            depth = capi.PSM_IMG_F32
+        else:
+            raise ValueError("Gray_GPU: planes must be uint8 or float32")
+        if gl.strides[1] != gl.itemsize or gr.strides != gl.strides or gl.strides[0] < self.wid * gl.itemsize:
+            gl, gr = np.ascontiguousarray(gl), np.ascontiguousarray(gr)      # (rows with a pitch go as they are)
+        lm, rm = (_ptr(self.lDisMap), _ptr(self.rDisMap)) if download else (None, None)
+        self._ck(self._lib.psm_gray_compute(self._h, _ptr(gl), _ptr(gr), gl.strides[0], depth, lm, rm, self.wid if download else 0),
+                 "Gray_GPU")
+        return (self.lDisMap, self.rDisMap) if download else None
+
+    def gray_guidance(self, side: int):
+        """Test hook: [4][H][W] float32 - I, G, mI, inv - of `side` of the last Gray_GPU's pair."""
+        planes = np.empty((4, self.hei, self.wid), np.float32)
+        self._ck(self._lib.psm_gray_guidance(self._h, int(side), _ptr(planes)), "gray_guidance")
+        return planes
+
+    def gray_volume(self, side: int, d0: int = 0, d1: int | None = None, want_ab: bool = False):
+        """Test hook: the filtered slices [d0, d1) of `side` of the last Gray_GPU's pair through the storing form of its kernels:
+        q [d1-d0][H][W] float32, and - want_ab - ab [d1-d0][2][H][W], the planes a and b of every slice."""
+        d1 = self.maxDis if d1 is None else int(d1)
+        n = max(d1 - int(d0), 0)
+        q = np.empty((n, self.hei, self.wid), np.float32)
+        ab = np.empty((n, 2, self.hei, self.wid), np.float32) if want_ab else None
+        self._ck(self._lib.psm_gray_volume(self._h, int(side), int(d0), d1, _ptr(q), _ptr(ab)), "gray_volume")
+        return (q, ab) if want_ab else q
+
+    def gray_time(self):
+        """Device ms of the launches of the last Gray_GPU; needs PSM_OPT_PROFILE."""
+        ms = C.c_double()
+        self._ck(self._lib.psm_gray_time(self._h, C.byref(ms)), "gray_time")
+        return ms.value
 
     def sgm_maps_time(self):
         """Device ms of the launch of the last SGBMSelect_GPU (sgbm_select_batch: of all pairs, on its first object); needs

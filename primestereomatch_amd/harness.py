@@ -164,6 +164,33 @@ def compute_sgbm(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, er
     return _finish_sgbm(out, maxDis, gt, mask, scale_factor, error_threshold, verbose, tail)
 
 
+def compute_gray(gl, gr, maxDis=64, gt=None, mask=None, scale_factor=4, error_threshold=4, lr_check=True, fill=False,
+                 device_tail=False, verbose=False):
+    """One frame of STEREO_GIF for a monochrome pair: gl / gr are H x W planes, uint8 or float32 scaled by 1/255, and go through
+    the one-channel guided filter in one call (DispEst.Gray_GPU; no colour pair is staged).  lr_check: the L-R check behind it
+    (lValid / rValid); fill: fillInv after it - the selected maps then stay in lDisMap_raw / rDisMap_raw.  The tail stages that
+    read the image (wgtMedian, JointWMF) need a colour pair and are not offered.  device_tail: compute()'s.
+    -> compute()'s record with gray_ms, the device time of the call; of the stage times cvf_ms repeats it, the others are 0."""
+    out = {}
+    gl, gr = np.asarray(gl), np.asarray(gr)
+    with DispEst.blank(gl.shape[0], gl.shape[1], maxDis) as SMDE:
+        SMDE.set_option(capi.PSM_OPT_PROFILE, 1)
+        SMDE.Gray_GPU(gl, gr)
+        out["gray_ms"] = SMDE.gray_time()
+        if lr_check or fill:
+            SMDE.LRCheck_GPU()
+            out["lValid"], out["rValid"] = SMDE.lValid.copy(), SMDE.rValid.copy()
+        if fill:
+            out["lDisMap_raw"], out["rDisMap_raw"] = SMDE.lDisMap.copy(), SMDE.rDisMap.copy()
+            SMDE.FillInv_GPU()
+        out["lDisMap"], out["rDisMap"] = SMDE.lDisMap.copy(), SMDE.rDisMap.copy()
+        tail = _device_tail([SMDE], [gt], [mask], scale_factor, error_threshold, capi.PSM_SCORE_GIF)[0] if device_tail else None
+    for k in ("cvc_ms", "cvf_ms", "dispsel_ms", "pp_ms"):
+        out[k] = 0.0
+    out["cvf_ms"] = out["gray_ms"]
+    return _finish(out, maxDis, gt, mask, scale_factor, error_threshold, verbose, tail)
+
+
 def _wls(SMDE, out, wls, maxDis, gt, mask, scale_factor, error_threshold):
     """compute_sgbm's wls= option: the filtered map of the object's int16 map into the record, published to the SGM sources."""
     SMDE.setWLS(**wls)

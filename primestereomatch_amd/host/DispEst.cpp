@@ -321,6 +321,27 @@ int DispEst::sgbmMapsTime(double *ms)
     return hipUtil::api().sgm_maps_time(ctx[0], ms);
 }
 
+int DispEst::Gray_GPU(const Mat &gl, const Mat &gr)
+{
+    if (ctx.size() != 1) {
+        fprintf(stderr, "DispEst: Gray_GPU runs on single-device objects only\n");
+        return 1;
+    }
+    if (gl.channels != 1 || gr.channels != 1 || gl.rows != hei || gl.cols != wid || gr.rows != hei || gr.cols != wid || gl.depth != gr.depth ||
+        gl.step != gr.step) {
+        fprintf(stderr, "DispEst: Gray_GPU wants two one-channel Mats of the object's size, of one depth and step\n");
+        return 1;
+    }
+    return hipUtil::api().gray_compute(ctx[0], gl.data, gr.data, gl.step, gl.depth == PSM_32F ? PSM_IMG_F32 : PSM_IMG_U8, lDisMap.data,
+                                       rDisMap.data, lDisMap.step);
+}
+
+int DispEst::grayTime(double *ms)
+{
+    if (ctx.empty()) return 1;
+    return hipUtil::api().gray_time(ctx[0], ms);
+}
+
 int DispEst::setSGBMSpeckle(int speckleWindowSize, int speckleRange)
 {
     if (ctx.empty()) return 1;

@@ -138,6 +138,14 @@ public:
     // stages' volumes are untouched.  sgbmMapsTime: device ms of the launch under PSM_OPT_PROFILE.
     int SGBMSelect();
     int sgbmMapsTime(double *ms);
+    // The GIF stages for a monochrome pair in one call (psm_gray_compute): gl, gr are H x W one-channel Mats of the object's size,
+    // CV_8U or CV_32F (scaled by 1/255.0f already) - cost build, the one-channel guided filter (FastGuidedFilter's dispatch on
+    // I.channels(), src/fastguidedfilter.cpp:38-49) and the selection; lDisMap / rDisMap are filled and become the object's device
+    // maps, so LRCheck_GPU, FillInvalid_GPU and Score(PSM_SCORE_GIF) run behind it.  The pair of setInputImages, the volumes and
+    // whatever CostFilter_GPU left pending are untouched (an object built for mono frames alone is given blank colour Mats).
+    // Single-device objects only.  grayTime: device ms of the call under PSM_OPT_PROFILE.
+    int Gray_GPU(const Mat &gl, const Mat &gr);
+    int grayTime(double *ms);
 
     // The steps of StereoMatch::compute behind the maps, on the device (psm_score): setGroundTruth uploads the dataset's ground truth
     // and (mask non-NULL) error mask once, H x W CV_8UC1 each; setScoreParams: scale_factor, error_threshold, PSM_MASK_NONE / NONOCC /

@@ -85,6 +85,9 @@ struct HipApi {
     int (*wls_download)(psm_ctx *, int16_t *, float *, float *, float *, size_t) = nullptr;
     int (*wls_time)(psm_ctx *, double *) = nullptr;
     int (*wls_publish)(psm_ctx *, int) = nullptr;
+    // the guided-filter path over a one-channel pair
+    int (*gray_compute)(psm_ctx *, const void *, const void *, size_t, int, uint8_t *, uint8_t *, size_t) = nullptr;
+    int (*gray_time)(psm_ctx *, double *) = nullptr;
 };
 
 class hipUtil {
