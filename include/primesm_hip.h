@@ -887,11 +887,26 @@ int psm_wls_publish(psm_ctx *ctx, int on);
  * Refused - psm_last_error names the call, nothing has been enqueued, the previous maps are still current - for a NULL context
  * (psm_last_error(NULL)), NULL planes, an unknown depth, a stride below a row, a map_stride below W, a PSM_U8 context, a disparity
  * shard, a row stripe in force (psm_set_rows).
- * Out of scope: batches, FrameRing, the Fast Guided Filter variant, 8-bit mode, rectified upload, and the tail stages that read
+ * Out of scope: FrameRing, the Fast Guided Filter variant, 8-bit mode, rectified upload, and the tail stages that read
  * the image - psm_wgt_median, psm_joint_wmf, the guide of psm_wls_filter and the colours of psm_reproject's cloud keep reading
  * the staged colour pair.  psm_upload_pair* keep refusing 1 channel. */
 int psm_gray_compute(psm_ctx *ctx, const void *l, const void *r, size_t stride_bytes, int depth, uint8_t *lmap, uint8_t *rmap,
                      size_t map_stride);
+/* psm_gray_compute of the pairs of n contexts (1 <= n <= 4096) in one set of launches, the pair on a grid axis: 2 + 2 per chunk of
+ * 32 slices whatever n is (the reference's use on small data is a loop over pairs, src/main.cpp:64-73).  The contexts share width,
+ * height, max_disp, device and options, as psm_compute_batch requires; member i takes its own planes ls[i], rs[i]; depth and
+ * stride_bytes are the call's.  lmaps / rmaps may be NULL, and so may any entry; else entry i receives member i's map, H rows of W
+ * bytes map_stride apart.  The launches run on ctxs[0]'s stream, ordered after everything queued on the members' streams and before
+ * anything queued on them later; synchronous on return unless ctxs[0] has PSM_OPT_ASYNC; every host plane has been read before the
+ * call returns.  Afterwards every member is exactly where its own psm_gray_compute would have left it - maps, state and the bits
+ * of both; the test hooks work on each.  Buffers stay per member; ctxs[0] owns a device table of the members' pointers.
+ * psm_gray_time on ctxs[0] gives the batch's device ms; the other members count as not timed.
+ * Refused before anything is enqueued on any member - every member's earlier maps stay current, psm_last_error(ctxs[0]) names the
+ * call and the member's index (psm_last_error(NULL) for NULL ctxs, n < 1 and a NULL ctxs[0]) - for n out of range, a NULL member,
+ * the same context twice, a member whose geometry, device or options differ from ctxs[0]'s, and per member or for the call what
+ * psm_gray_compute refuses. */
+int psm_gray_compute_batch(psm_ctx *const *ctxs, int n, const void *const *ls, const void *const *rs, size_t stride_bytes, int depth,
+                           uint8_t *const *lmaps, uint8_t *const *rmaps, size_t map_stride);
 /* Device ms of the launches of the last psm_gray_compute (guidance, every chunk, the maps); needs PSM_OPT_PROFILE. */
 int psm_gray_time(psm_ctx *ctx, double *ms);
 /* Test hooks on the pair of the last psm_gray_compute (refused before any, and after psm_release_scratch).

@@ -179,6 +179,7 @@ SYMBOLS = [
     ("psm_wls_time", _i, [_vp, _pd]),
     ("psm_wls_publish", _i, [_vp, _i]),
     ("psm_gray_compute", _i, [_vp, _vp, _vp, _sz, _i, _vp, _vp, _sz]),
+    ("psm_gray_compute_batch", _i, [C.POINTER(_vp), _i, C.POINTER(_vp), C.POINTER(_vp), _sz, _i, C.POINTER(_vp), C.POINTER(_vp), _sz]),
     ("psm_gray_time", _i, [_vp, _pd]),
     ("psm_gray_guidance", _i, [_vp, _i, _vp]),
     ("psm_gray_volume", _i, [_vp, _i, _i, _i, _vp, _vp]),

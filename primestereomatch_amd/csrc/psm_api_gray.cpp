@@ -6,10 +6,13 @@
 // L-R check, the fill, psm_score, the downloads and psm_reproject run behind it.  The image pair slots, the volume sides and the
 // packed minima of the colour path never see it.
 // No volume exists: per chunk of gray_plan().dc slices k_gray_ab leaves {a, b} in the chunk scratch and k_gray_q folds q into the
-// stage's key plane; launch_merge turns the keys into the maps.  The test hooks run the storing form of the same kernels.
+// stage's key plane; k_gray_merge turns the keys into the maps.  The test hooks run the storing form of the same kernels.
+// psm_gray_compute_batch: the same launches for the pairs of several contexts at once, the pair on a grid axis - one host sequence,
+// gray_run, of which the single call is the n = 1 with the record by value.
 #include "psm_ctx.h"
 
 #include <algorithm>
+#include <cstdio>
 #include <vector>
 
 using namespace psm;
@@ -26,6 +29,7 @@ void gray_free(psm_ctx *c)
     }
     (void)hipFree(g.ab); g.ab = nullptr;
     (void)hipFree(g.keys); g.keys = nullptr;
+    table_free(g.pairs);
     bracket_free(g.prof);
     g.depth = -1;
 }
@@ -34,12 +38,13 @@ void gray_free(psm_ctx *c)
 
 namespace {
 
-// what a context must be for the stage; who: the call
-int check_ctx(psm_ctx *c, const char *who)
+// what a context must be for the stage; who: the call; e: the context that receives the message (a batch: its first; who names the
+// member)
+int check_ctx(psm_ctx *e, const psm_ctx *c, const char *who)
 {
-    if (c->dtype == PSM_U8) return fail(c, "%s: an 8-bit context (PSM_U8): the one-channel filter is a float-mode stage", who);
-    if (c->Dloc != c->D || strided(c)) return fail(c, "%s: a disparity shard holds part of the range (the stage selects over every disparity)", who);
-    if (c->march.yend > c->march.ybeg) return fail(c, "%s: a row stripe is in force (psm_set_rows): the maps are whole-image maps", who);
+    if (c->dtype == PSM_U8) return fail(e, "%s: an 8-bit context (PSM_U8): the one-channel filter is a float-mode stage", who);
+    if (c->Dloc != c->D || strided(c)) return fail(e, "%s: a disparity shard holds part of the range (the stage selects over every disparity)", who);
+    if (c->march.yend > c->march.ybeg) return fail(e, "%s: a row stripe is in force (psm_set_rows): the maps are whole-image maps", who);
     return 0;
 }
 
@@ -60,13 +65,88 @@ int ensure_buffers(psm_ctx *c, const GrayPlan &pl)
 GrayPair pair_of(const psm_ctx *c)
 {
     const GrayState &g = c->gray;
-    return GrayPair{{g.raw[0], g.raw[1]}, {g.ig[0], g.ig[1]}, {g.mv[0], g.mv[1]}, g.ab, g.keys};
+    return GrayPair{{g.raw[0], g.raw[1]}, {g.ig[0], g.ig[1]}, {g.mv[0], g.mv[1]}, g.ab, g.keys, c->maps};
+}
+
+// The host sequence of psm_gray_compute (its one context, the record by value) and of psm_gray_compute_batch (batch: the same
+// kernels over the device table of ctxs[0]), the arguments and every context checked: 2 + 2 ceil((D - 1) / dc) launches on ctxs[0]'s
+// stream whatever n is.  ls, rs, lmaps, rmaps: per member (the map arrays, or an entry, may be null).
+int gray_run(const char *who, psm_ctx *const *ctxs, int n, const void *const *ls, const void *const *rs, size_t stride_bytes, int depth,
+             uint8_t *const *lmaps, uint8_t *const *rmaps, size_t map_stride, bool batch)
+{
+    psm_ctx *c0 = ctxs[0];
+    if (bind(c0)) return 1;
+    hipStream_t s = c0->stream;
+    const int W = c0->W, H = c0->H, D = c0->D;
+    const size_t row = (size_t)W * (depth == PSM_IMG_F32 ? sizeof(float) : 1);
+    const GrayPlan pl = gray_plan(W, H, D, n);
+
+    // ---- buffers, events and the table's memory: before anything is ordered or launched ----
+    for (int i = 0; i < n; ++i)
+        if (ensure_buffers(ctxs[i], pl)) return member_failed(c0, who, i, ctxs[i]);
+    if (bracket_events(c0, c0->gray.prof) || batch_events(c0, ctxs, n)) return 1;
+    std::vector<GrayPair> tab((size_t)n);
+    for (int i = 0; i < n; ++i) tab[i] = pair_of(ctxs[i]);
+    bool fresh = false;
+    if (batch && table_reserve(c0, c0->gray.pairs, tab.data(), tab.size() * sizeof(GrayPair), &fresh)) return 1;
+    const Recs<GrayPair> q{tab.data(), batch ? (const GrayPair *)c0->gray.pairs.dev : nullptr, n};
+
+    // ---- the pairs, each on its member's stream: the planes of an earlier call are gone from here on ----
+    for (int i = 0; i < n; ++i) {
+        GrayState &g = ctxs[i]->gray;
+        g.depth = -1;
+        g.prof.timed = false;
+    }
+    for (int i = 0; i < n; ++i) {
+        psm_ctx *c = ctxs[i];
+        const void *src[2] = {ls[i], rs[i]};
+        for (int k = 0; k < 2; ++k)
+            if (h2d_rows(c, c->gray.raw[k], src[k], row, stride_bytes, H)) return member_failed(c0, who, i, c);
+    }
+    for (int i = 0; i < n; ++i) PSM_HIP(c0, hipStreamSynchronize(ctxs[i]->stream));      // the copies read caller memory (psm_upload_pair)
+
+    // ---- every member's earlier work (a download of its maps, the copy of its pair) is ordered before the shared launches ----
+    for (int i = 0; i < n; ++i) {
+        psm_ctx *c = ctxs[i];
+        hipStream_t own = c->stream;
+        c->stream = s;                       // (maps_writable makes `s` wait for the member's download)
+        const int bad = maps_writable(c);
+        c->stream = own;
+        if (bad) return member_failed(c0, who, i, c);
+    }
+    if (batch_join(c0, ctxs, n)) return 1;
+    if (fresh && table_upload(c0, c0->gray.pairs, tab.data(), tab.size() * sizeof(GrayPair))) return 1;
+
+    // ---- the launches: guidance and empty keys, the chunks of the slices 1 .. D - 1 (d = 0 is never a candidate), the maps ----
+    if (bracket_open(c0, c0->gray.prof, s)) return 1;
+    launch_gray_prep(s, q, pl, W, H, depth == PSM_IMG_F32);
+    if (check_launch(c0, "k_gray_prep")) return 1;
+    for (int d = 1; d < D; d += pl.dc) launch_gray_chunk(s, q, pl, W, H, d, std::min(D, d + pl.dc));
+    if (check_launch(c0, "k_gray_ab, k_gray_q")) return 1;
+    launch_gray_merge(s, q, W, H);
+    if (check_launch(c0, "k_gray_merge")) return 1;
+    if (bracket_close(c0, c0->gray.prof, s)) return 1;
+
+    // ---- every context is where psm_sgm_select_maps leaves it: whole-image maps, no mask, no early map; the volume sides, the
+    // packed minima and whatever the colour path has pending are not touched.  Only context 0 counts as timed ----
+    for (int i = 0; i < n; ++i) {
+        psm_ctx *c = ctxs[i];
+        c->gray.depth = depth;
+        forget_early(c->res);
+        cover(c->res, whole_image(c));
+        maps_written(c->res);
+    }
+    if (batch_fork(c0, ctxs, n)) return 1;
+    for (int i = 0; i < n; ++i)
+        if (copy_maps_out(ctxs[i], ctxs[i]->maps, lmaps ? lmaps[i] : nullptr, rmaps ? rmaps[i] : nullptr, map_stride)) return member_failed(c0, who, i, ctxs[i]);
+    if (!c0->opt_async) PSM_HIP(c0, hipStreamSynchronize(s));
+    return 0;
 }
 
 // the hooks: the planes of a psm_gray_compute must exist
 int check_hook(psm_ctx *c, const char *who, int side)
 {
-    if (check_ctx(c, who)) return 1;
+    if (check_ctx(c, c, who)) return 1;
     if (c->gray.depth < 0) return fail(c, "%s: no pair (psm_gray_compute; psm_release_scratch gives it back)", who);
     if (side != PSM_LEFT && side != PSM_RIGHT) return fail(c, "%s: bad side %d", who, side);
     return 0;
@@ -80,48 +160,47 @@ int psm_gray_compute(psm_ctx *c, const void *l, const void *r, size_t stride_byt
 {
     const char *who = "psm_gray_compute";
     if (!c) return fail(nullptr, "%s: NULL context", who);
-    if (check_ctx(c, who)) return 1;
+    if (check_ctx(c, c, who)) return 1;
     if (!l || !r) return fail(c, "%s: NULL image", who);
     if (depth != PSM_IMG_U8 && depth != PSM_IMG_F32) return fail(c, "%s: unknown depth %d", who, depth);
     const size_t row = (size_t)c->W * (depth == PSM_IMG_F32 ? sizeof(float) : 1);
     if (stride_bytes == 0) stride_bytes = row;
     if (stride_bytes < row) return fail(c, "%s: stride %zu < row size %zu", who, stride_bytes, row);
     if (map_stride != 0 && map_stride < (size_t)c->W) return fail(c, "%s: map stride %zu < width %d", who, map_stride, c->W);
-    if (bind(c)) return 1;
-    GrayState &g = c->gray;
-    const GrayPlan pl = gray_plan(c->W, c->H, c->D);
-    if (ensure_buffers(c, pl) || bracket_events(c, g.prof)) return 1;
+    return gray_run(who, &c, 1, &l, &r, stride_bytes, depth, &lmap, &rmap, map_stride, false);
+}
 
-    // ---- the pair: the planes of an earlier call are gone from here on ----
-    g.depth = -1;
-    g.prof.timed = false;
-    const void *src[2] = {l, r};
-    for (int s = 0; s < 2; ++s)
-        if (h2d_rows(c, g.raw[s], src[s], row, stride_bytes, c->H)) return 1;
-    PSM_HIP(c, hipStreamSynchronize(c->stream));      // the copy reads caller memory (psm_upload_pair)
-
-    // ---- the launches: guidance and empty keys, the chunks of the slices 1 .. D - 1 (d = 0 is never a candidate), the maps ----
-    if (maps_writable(c)) return 1;
-    const GrayPair p = pair_of(c);
-    const size_t HW = (size_t)c->W * c->H;
-    if (bracket_open(c, g.prof, c->stream)) return 1;
-    launch_gray_prep(c->stream, p, pl, c->W, c->H, depth == PSM_IMG_F32);
-    if (check_launch(c, "k_gray_prep")) return 1;
-    for (int d = 1; d < c->D; d += pl.dc) launch_gray_chunk(c->stream, p, pl, c->W, c->H, 0, 2, d, std::min(c->D, d + pl.dc), nullptr);
-    if (check_launch(c, "k_gray_ab, k_gray_q")) return 1;
-    launch_merge(c->stream, g.keys, 2 * HW, 1, (int)(2 * HW), c->maps);
-    if (check_launch(c, "k_merge")) return 1;
-    if (bracket_close(c, g.prof, c->stream)) return 1;
-
-    // ---- the context is where psm_sgm_select_maps leaves it: whole-image maps, no mask, no early map; the volume sides, the
-    // packed minima and whatever the colour path has pending are not touched ----
-    g.depth = depth;
-    forget_early(c->res);
-    cover(c->res, whole_image(c));
-    maps_written(c->res);
-    if (copy_maps_out(c, c->maps, lmap, rmap, map_stride)) return 1;
-    if (!c->opt_async) PSM_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
+// The launches of psm_gray_compute with the pair on a grid axis.  Planes, chunk scratch and keys stay per context; the kernels
+// reach them through a device table ctxs[0] owns.  Every context ends where its own psm_gray_compute would have left it.
+int psm_gray_compute_batch(psm_ctx *const *ctxs, int n, const void *const *ls, const void *const *rs, size_t stride_bytes, int depth,
+                           uint8_t *const *lmaps, uint8_t *const *rmaps, size_t map_stride)
+{
+    const char *who = "psm_gray_compute_batch";
+    if (!ctxs) return fail(nullptr, "%s: NULL ctxs", who);
+    if (n < 1) return fail(nullptr, "%s: n %d below 1", who, n);
+    psm_ctx *c0 = ctxs[0];
+    if (!c0) return fail(nullptr, "%s: context 0 is NULL", who);
+    if (n > 4096) return fail(c0, "%s: %d contexts (at most 4096 per call)", who, n);
+    for (int i = 0; i < n; ++i) {
+        if (batch_member(c0, who, ctxs, i)) return 1;
+        const psm_ctx *c = ctxs[i];
+        char member[64];
+        snprintf(member, sizeof member, "%s: context %d", who, i);
+        if (check_ctx(c0, c, member)) return 1;
+        if (c->W != c0->W || c->H != c0->H || c->D != c0->D || c->d0 != c0->d0 || c->d1 != c0->d1 || c->dtype != c0->dtype || c->device != c0->device)
+            return fail(c0, "%s: context %d has another geometry / type / device than context 0", who, i);
+        if (c->march.flags != c0->march.flags || c->march.seg_rows != c0->march.seg_rows || c->march.dstep != c0->march.dstep)
+            return fail(c0, "%s: context %d has other options than context 0", who, i);
+    }
+    if (!ls || !rs) return fail(c0, "%s: NULL image arrays", who);
+    for (int i = 0; i < n; ++i)
+        if (!ls[i] || !rs[i]) return fail(c0, "%s: context %d: NULL image", who, i);
+    if (depth != PSM_IMG_U8 && depth != PSM_IMG_F32) return fail(c0, "%s: unknown depth %d", who, depth);
+    const size_t row = (size_t)c0->W * (depth == PSM_IMG_F32 ? sizeof(float) : 1);
+    if (stride_bytes == 0) stride_bytes = row;
+    if (stride_bytes < row) return fail(c0, "%s: stride %zu < row size %zu", who, stride_bytes, row);
+    if (map_stride != 0 && map_stride < (size_t)c0->W) return fail(c0, "%s: map stride %zu < width %d", who, map_stride, c0->W);
+    return gray_run(who, ctxs, n, ls, rs, stride_bytes, depth, lmaps, rmaps, map_stride, true);
 }
 
 int psm_gray_guidance(psm_ctx *c, int side, float *planes)
@@ -162,7 +241,7 @@ int psm_gray_volume(psm_ctx *c, int side, int d0, int d1, float *q, float *ab)
     for (int d = d0; d < d1 && !rc; d += pl.dc) {
         const int e = std::min(d1, d + pl.dc);
         const size_t n = (size_t)(e - d) * HW;
-        launch_gray_chunk(c->stream, p, pl, c->W, c->H, side, 1, d, e, qdev);
+        launch_gray_chunk_store(c->stream, p, pl, c->W, c->H, side, d, e, qdev);
         rc = check_launch(c, "k_gray_ab, k_gray_q");
         if (!rc && hipMemcpyAsync(q + (size_t)(d - d0) * HW, qdev, n * sizeof(float), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
             rc = fail(c, "%s: hipMemcpyAsync", who);

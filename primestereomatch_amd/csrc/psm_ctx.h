@@ -23,7 +23,8 @@
 //                       (psm_reproject), and of the results of several contexts in shared launches (psm_reproject_batch) - one
 //                       sequence, reproject_run
 //   psm_api_gray.cpp    the guided-filter path over a one-channel pair: one-channel fused filter and selection of host planes
-//                       (psm_gray_compute), its test hooks and timer (psm::GrayState)
+//                       (psm_gray_compute), of the pairs of several contexts in shared launches (psm_gray_compute_batch) - one
+//                       sequence, gray_run -, its test hooks and timer (psm::GrayState)
 //   psm_api_wls.cpp     edge-aware WLS smoothing of the sub-pixel int16 map (psm_wls_filter), of the maps of several contexts in
 //                       shared launches (psm_wls_filter_batch) - one sequence, wls_run - and the switch that lets the SGM sources
 //                       of psm_score / psm_reproject read its result (psm_wls_publish)
@@ -229,6 +230,7 @@ struct GrayState {
     long long *keys = nullptr;                     // [2][H][W]: this stage's packed minima (ctx->keys belongs to the colour path)
     int depth = -1;                                // PSM_IMG_* of the last call's pair, which the planes hold; -1: none
     Bracket prof;                                  // PSM_OPT_PROFILE: around the launches (psm_gray_time)
+    DevTable pairs;                                // psm_gray_compute_batch (this context as the first of a batch): GrayPair records
 };
 
 // The image pair every frame starts with, and the second slot the next frame travels into (psm_upload_pair_async,

@@ -453,18 +453,23 @@ void launch_wls_cols(hipStream_t s, const Recs<WlsPair> &q, int t, bool last);  
 constexpr int GRAY_COLS = 56;                          // output columns of a wave's strip
 constexpr int GRAY_DC_MAX = 32;                        // slices of a chunk at most
 constexpr size_t GRAY_SCRATCH_MAX = (size_t)1 << 30;   // bytes of the chunk scratch at most (but four slices always fit)
-struct GrayPair {
+struct GrayPair {                                      // one pair's buffers: a single call's by value, an entry of a batch's device table (psm_gray_compute_batch)
     const void *raw[2];                // the pair's planes [H][W]: bytes (PSM_IMG_U8) or floats (PSM_IMG_F32)
     float2 *ig[2];                     // [H][W] {I, G}: the plane and its x-gradient
     float2 *mv[2];                     // [H][W] {mI, 1 / (var + eps)}
     float2 *ab;                        // the chunk scratch [2][dc][H][W] {a, b}
     long long *keys;                   // [2][H][W] packed minima of this stage (not the colour path's)
+    uint8_t *maps;                     // [2][H][W]: the context's map buffer (k_gray_merge)
 };
 struct GrayPlan { int nstrips, nsegs, seg_rows, dc; };   // strips of GRAY_COLS columns, segments of seg_rows rows, slices per chunk
-GrayPlan gray_plan(int W, int H, int D);                // for the device the calling thread is bound to (pc_dev)
-void launch_gray_prep(hipStream_t s, const GrayPair &p, const GrayPlan &g, int W, int H, bool f32);   // k_gray_prep: ig, mv of both sides; keys = no candidate
-// k_gray_ab, k_gray_q over the slices [dbeg, dend) (at most g.dc) of the sides [side0, side0 + nsides): minima into p.keys, or -
-// qvol != null, nsides 1: the storing form - q into qvol [dend - dbeg][H][W]; {a, b} of the slices are in p.ab either way
-void launch_gray_chunk(hipStream_t s, const GrayPair &p, const GrayPlan &g, int W, int H, int side0, int nsides, int dbeg, int dend, float *qvol);
+// for the device the calling thread is bound to (pc_dev); n: the pairs that share every launch - seg_rows alone depends on it
+GrayPlan gray_plan(int W, int H, int D, int n = 1);
+// q: the pair of a single call, or the n pairs of a batch's device table (grid z = pair; k_gray_ab, k_gray_q: pair * 2 + side)
+void launch_gray_prep(hipStream_t s, const Recs<GrayPair> &q, const GrayPlan &g, int W, int H, bool f32);   // k_gray_prep: ig, mv of both sides; keys = no candidate
+// k_gray_ab, k_gray_q over the slices [dbeg, dend) (at most g.dc) of both sides of every pair: {a, b} into each pair's ab, minima into its keys
+void launch_gray_chunk(hipStream_t s, const Recs<GrayPair> &q, const GrayPlan &g, int W, int H, int dbeg, int dend);
+// ... the storing form (the test hooks'), one side of one pair by value: q into qvol [dend - dbeg][H][W]; {a, b} of the slices are in p.ab
+void launch_gray_chunk_store(hipStream_t s, const GrayPair &p, const GrayPlan &g, int W, int H, int side, int dbeg, int dend, float *qvol);
+void launch_gray_merge(hipStream_t s, const Recs<GrayPair> &q, int W, int H);   // k_gray_merge: keys -> maps of every pair
 
 }  // namespace psm

@@ -918,6 +918,40 @@ def wls_batch(des, source: int = capi.PSM_WLS_SGM, use_mask: bool = False):
     return None if des[0].options.get(capi.PSM_OPT_ASYNC) else [d.wls_map() for d in des]
 
 
+def gray_batch(des, gls=(), grs=(), download: bool = True):
+    """Gray_GPU of several DispEst objects of one geometry in one set of launches (psm_gray_compute_batch): object i takes the
+    monochrome pair (gls[i], grs[i]) - H x W planes, all uint8 or all float32.  Every object afterwards behaves as after its own
+    Gray_GPU (LRCheck_GPU, Score_GPU(PSM_SCORE_GIF), download_maps(), the gray_* hooks).  -> the list of (lDisMap, rDisMap) of the
+    objects; download=False: the maps stay on the device, a list of None.  gray_time() of des[0] is the batch's
+    (PSM_OPT_PROFILE)."""
+    des, gls, grs = list(des), [np.asarray(g) for g in gls], [np.asarray(g) for g in grs]
+    if len(gls) != len(des) or len(grs) != len(des):
+        raise ValueError("gray_batch: one (gl, gr) pair per object")
+    if not des:
+        return []
+    shape, dtype = (des[0].hei, des[0].wid), gls[0].dtype
+    if dtype == np.uint8:
+        depth = capi.PSM_IMG_U8
+    elif dtype == np.float32:
+        depth = capi.PSM_IMG_F32
+    else:
+        raise ValueError("gray_batch: planes must be uint8 or float32")
+    if any(g.shape != shape or g.dtype != dtype for g in gls + grs):
+        raise ValueError("gray_batch: every plane must be H x W, of one type and of the size the objects were built for")
+    row = shape[1] * gls[0].itemsize
+    if any(g.strides != gls[0].strides for g in gls + grs) or gls[0].strides[1] != gls[0].itemsize or gls[0].strides[0] < row:
+        gls, grs = [np.ascontiguousarray(g) for g in gls], [np.ascontiguousarray(g) for g in grs]      # (one pitch for the call)
+    n = len(des)
+    arr = (C.c_void_p * n)(*[d._h for d in des])
+    ls = (C.c_void_p * n)(*[g.ctypes.data for g in gls])
+    rs = (C.c_void_p * n)(*[g.ctypes.data for g in grs])
+    lm = (C.c_void_p * n)(*[d.lDisMap.ctypes.data for d in des]) if download else None
+    rm = (C.c_void_p * n)(*[d.rDisMap.ctypes.data for d in des]) if download else None
+    capi.check(des[0]._lib.psm_gray_compute_batch(arr, n, ls, rs, gls[0].strides[0], depth, lm, rm, shape[1] if download else 0),
+               des[0]._h, "gray_batch")
+    return [(d.lDisMap, d.rDisMap) if download else None for d in des]
+
+
 def share_streams(des):
     """The DispEst objects of a batch run on one compute stream and one copy stream each way (psm_share_streams) - call once
     before a frame loop over batches."""

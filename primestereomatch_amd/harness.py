@@ -191,6 +191,47 @@ def compute_gray(gl, gr, maxDis=64, gt=None, mask=None, scale_factor=4, error_th
     return _finish(out, maxDis, gt, mask, scale_factor, error_threshold, verbose, tail)
 
 
+def compute_gray_batch(pairs, maxDis=64, gts=None, masks=None, scale_factor=4, error_threshold=4, lr_check=True, fill=False,
+                       device_tail=False, verbose=False):
+    """compute_gray for a list of (gl, gr) monochrome pairs of one size and one depth (all uint8, or all float32) in shared
+    launches (dispest.gray_batch): the reference's loop over pairs and datasets (src/main.cpp:64-73).  gts / masks: one per pair (or
+    None).  lr_check / fill: compute_gray's, the stages of all pairs in shared launches (dispest.post_process_batch); device_tail:
+    display maps and metrics of all pairs from the device (dispest.score_batch).
+    -> a list of compute_gray's records; gray_ms is the batch's device time divided by the number of pairs."""
+    pairs = [(np.asarray(gl), np.asarray(gr)) for gl, gr in pairs]
+    if not pairs:
+        return []
+    hei, wid = pairs[0][0].shape
+    des = [DispEst.blank(hei, wid, maxDis) for _ in pairs]
+    outs = [{} for _ in pairs]
+    try:
+        des[0].set_option(capi.PSM_OPT_PROFILE, 1)
+        dispest.gray_batch(des, [p[0] for p in pairs], [p[1] for p in pairs])
+        ms = des[0].gray_time() / len(des)
+        if lr_check or fill:
+            dispest.post_process_batch(des, lr_check=True)
+            for d, out in zip(des, outs):
+                out["lValid"], out["rValid"] = d.lValid.copy(), d.rValid.copy()
+        if fill:
+            for d, out in zip(des, outs):
+                out["lDisMap_raw"], out["rDisMap_raw"] = d.lDisMap.copy(), d.rDisMap.copy()
+            dispest.post_process_batch(des, lr_check=False, fill=True)
+        for d, out in zip(des, outs):
+            out["lDisMap"], out["rDisMap"] = d.lDisMap.copy(), d.rDisMap.copy()
+        tails = _device_tail(des, gts, masks, scale_factor, error_threshold, capi.PSM_SCORE_GIF) if device_tail else [None] * len(des)
+    finally:
+        for d in des:
+            d.close()
+    for i, out in enumerate(outs):
+        out["gray_ms"] = ms
+        for k in ("cvc_ms", "dispsel_ms", "pp_ms"):
+            out[k] = 0.0
+        out["cvf_ms"] = ms
+        outs[i] = _finish(out, maxDis, gts[i] if gts else None, masks[i] if masks else None, scale_factor, error_threshold, verbose,
+                          tails[i])
+    return outs
+
+
 def _wls(SMDE, out, wls, maxDis, gt, mask, scale_factor, error_threshold):
     """compute_sgbm's wls= option: the filtered map of the object's int16 map into the record, published to the SGM sources."""
     SMDE.setWLS(**wls)

@@ -525,6 +525,34 @@ int DispEst::WLSBatch(DispEst *const *des, int n, int source, int flags)
     return hipUtil::api().wls_filter_batch(cs.data(), n, source, flags);
 }
 
+int DispEst::GrayBatch(DispEst *const *des, int n, const Mat *gls, const Mat *grs)
+{
+    if (!des || n < 1 || !gls || !grs) return 1;
+    std::vector<psm_ctx *> cs;
+    std::vector<const void *> ls, rs;
+    std::vector<uint8_t *> lm, rm;
+    for (int i = 0; i < n; ++i) {
+        if (!des[i] || des[i]->ctx.size() != 1) {
+            fprintf(stderr, "DispEst: GrayBatch runs on single-device objects only\n");
+            return 1;
+        }
+        const DispEst &d = *des[i];
+        for (const Mat *m : {&gls[i], &grs[i]})
+            if (m->channels != 1 || m->rows != d.hei || m->cols != d.wid || m->depth != gls[0].depth || m->step != gls[0].step) {
+                fprintf(stderr, "DispEst: GrayBatch wants one-channel Mats of the objects' size, of one depth and step\n");
+                return 1;
+            }
+        if (d.lDisMap.step != des[0]->lDisMap.step || d.rDisMap.step != des[0]->lDisMap.step) return 1;
+        cs.push_back(d.ctx[0]);
+        ls.push_back(gls[i].data);
+        rs.push_back(grs[i].data);
+        lm.push_back(d.lDisMap.data);
+        rm.push_back(d.rDisMap.data);
+    }
+    return hipUtil::api().gray_compute_batch(cs.data(), n, ls.data(), rs.data(), gls[0].step, gls[0].depth == PSM_32F ? PSM_IMG_F32 : PSM_IMG_U8,
+                                             lm.data(), rm.data(), des[0]->lDisMap.step);
+}
+
 double DispEst::stageTimeUs(int stage) const
 {
     double us = 0;

@@ -217,6 +217,11 @@ public:
     // Every object is afterwards where its own WLS_GPU would have left it (WLSPublish, WLSWait under PSM_OPT_ASYNC on des[0]);
     // wlsTime of des[0] reports the batch.
     static int WLSBatch(DispEst *const *des, int n, int source = PSM_WLS_SGM, int flags = 0);
+    // ... and the monochrome path: Gray_GPU(gls[i], grs[i]) of n single-device objects of one geometry in one set of launches
+    // (psm_gray_compute_batch); the 2 n Mats are one-channel, of the objects' size and of one depth and step.  Every object's
+    // lDisMap / rDisMap are filled and it is afterwards where its own Gray_GPU would have left it; grayTime of des[0] reports the
+    // batch.
+    static int GrayBatch(DispEst *const *des, int n, const Mat *gls, const Mat *grs);
 
     // psm_set_option on every device's context (PSM_OPT_FLAGS: e.g. PSM_FLAG_FMA_SOLVE - the maps of a reference binary built for an
     // FMA target -, PSM_OPT_SEG_ROWS, PSM_OPT_GATHER_STAGED, PSM_OPT_FRAMES_IN_FLIGHT ...; include/primesm_hip.h).  0 = ok.

@@ -87,6 +87,8 @@ struct HipApi {
     int (*wls_publish)(psm_ctx *, int) = nullptr;
     // the guided-filter path over a one-channel pair
     int (*gray_compute)(psm_ctx *, const void *, const void *, size_t, int, uint8_t *, uint8_t *, size_t) = nullptr;
+    int (*gray_compute_batch)(psm_ctx *const *, int, const void *const *, const void *const *, size_t, int, uint8_t *const *, uint8_t *const *,
+                              size_t) = nullptr;
     int (*gray_time)(psm_ctx *, double *) = nullptr;
 };
 

@@ -11,10 +11,22 @@ the two paths; reported are the best and the median of
                  call completes first, lies outside - as the upload of the colour pair lies outside the colour figure)
   gray_call_ms   device events on the stream around the whole call, upload included
   colour_ms      device events on the stream around construct + filter + select of the tripled pair, maps left on the device
-and gray_ms over colour_ms (best over best).  The maps of the gray call are left on the device too."""
+and gray_ms over colour_ms (best over best).  The maps of the gray call are left on the device too.
+
+--batch: psm_gray_compute_batch beside a loop of single calls instead.  Per configuration (default: cones, and 720p with a batch of
+4 alone) and per batch size 1 / 2 / 4 / 8, device ms per pair (psm_gray_time of the batch's first context over n) beside the per-pair
+device ms of a loop of 8 psm_gray_compute calls on 8 contexts (the sum of their psm_gray_time over 8), and the single call's device
+ms at all three configurations.  Every build of the library measured - this tree's, and with --parent-lib another build's (the
+parent commit's, which has no batch: its loop of single calls and its single calls alone) - runs in child processes of its own,
+through ctypes on the few symbols both builds have, --rounds times in alternation; a child warms up, then repeats --runs times.
+Reported per build: the best and the median over all of its repeats, and the spread of its rounds' bests (max - min).  The block
+is printed as JSON lines and, with --out, appended to that file."""
 import argparse
+import ctypes as C
+import functools
 import json
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -83,13 +95,138 @@ def bench(torch, name, warmup, runs):
     return rec
 
 
+# ---- --batch -------------------------------------------------------------------------------------------------------------
+BATCH_SIZES = (1, 2, 4, 8)
+LOOP = 8
+
+
+def _bind(path):
+    vp, i, sz = C.c_void_p, C.c_int, C.c_size_t
+    lib = C.CDLL(path)
+    for name, args in (("psm_create", [C.POINTER(vp), i, i, i, i, i]), ("psm_set_option", [vp, i, i]), ("psm_synchronize", [vp]),
+                       ("psm_gray_compute", [vp, vp, vp, sz, i, vp, vp, sz]), ("psm_gray_time", [vp, C.POINTER(C.c_double)])):
+        getattr(lib, name).argtypes, getattr(lib, name).restype = args, i
+    lib.psm_destroy.argtypes, lib.psm_destroy.restype = [vp], None
+    lib.psm_last_error.argtypes, lib.psm_last_error.restype = [vp], C.c_char_p
+    if hasattr(lib, "psm_gray_compute_batch"):
+        pp = C.POINTER(vp)
+        lib.psm_gray_compute_batch.argtypes, lib.psm_gray_compute_batch.restype = [pp, i, pp, pp, sz, i, pp, pp, sz], i
+    return lib
+
+
+def worker(path, names, warmup, runs):
+    """one build of the library in this process: {key: [ms per pair, one per repeat]}"""
+    lib = _bind(path)
+    out = {}
+
+    def ck(rc, h=None):
+        if rc:
+            raise SystemExit("gray_bench worker: " + (lib.psm_last_error(h) or b"?").decode())
+
+    def time_of(h):
+        ms = C.c_double()
+        ck(lib.psm_gray_time(h, C.byref(ms)), h)
+        return ms.value
+
+    for name in names:
+        W, H, D = CONFIGS[name]
+        gl, gr = the_planes(name)
+        planes = [(np.ascontiguousarray(np.roll(gl, k, axis=0)), np.ascontiguousarray(np.roll(gr, k, axis=0))) for k in range(LOOP)]
+        nctx = LOOP if name != "1080p" else 1
+        hs = []
+        for _ in range(nctx):
+            h = C.c_void_p()
+            ck(lib.psm_create(C.byref(h), W, H, D, 0, 0))
+            ck(lib.psm_set_option(h, 2, 1), h)                                # PSM_OPT_PROFILE
+            hs.append(h)
+
+        def single(k):
+            l, r = planes[k]
+            ck(lib.psm_gray_compute(hs[k], l.ctypes.data, r.ctypes.data, 0, 0, None, None, 0), hs[k])
+            return time_of(hs[k])
+
+        def batch(n):
+            arr = (C.c_void_p * n)(*[h.value for h in hs[:n]])
+            ls = (C.c_void_p * n)(*[p[0].ctypes.data for p in planes[:n]])
+            rs = (C.c_void_p * n)(*[p[1].ctypes.data for p in planes[:n]])
+            ck(lib.psm_gray_compute_batch(arr, n, ls, rs, 0, 0, None, None, 0), hs[0])
+            return time_of(hs[0]) / n
+
+        sizes = [n for n in BATCH_SIZES if hasattr(lib, "psm_gray_compute_batch") and (name == "cones" or (name == "720p" and n == 4))]
+        def loop():
+            return sum(single(k) for k in range(LOOP)) / LOOP
+
+        # two phases, each warmed up by itself, the forms of a phase alternating: the single calls, the same sequence in every
+        # build (what follows a batch is not what follows a single call) - then, in a build that has it, the batches beside the loop
+        phases = [{f"{name}.single": lambda: single(0)}]
+        if nctx == LOOP:
+            phases[0][f"{name}.loop{LOOP}"] = loop
+        if sizes:
+            phases.append({f"{name}.loop{LOOP}_beside_batches": loop})
+            for n in sizes:
+                phases[1][f"{name}.batch{n}"] = functools.partial(batch, n)
+        for runs_of in phases:
+            for _ in range(warmup):
+                for f in runs_of.values():
+                    f()
+            res = {k: [] for k in runs_of}
+            for _ in range(runs):
+                for k, f in runs_of.items():
+                    res[k].append(f())
+            out.update(res)
+        for h in hs:
+            lib.psm_destroy(h)
+    return out
+
+
+def batch_bench(a):
+    from primestereomatch_amd import capi
+    builds = [("this", capi.LIB_PATH)] + ([("parent", os.path.abspath(a.parent_lib))] if a.parent_lib else [])
+    names = a.config or ["cones", "720p", "1080p"]
+    rounds = {tag: [] for tag, _ in builds}
+    for _ in range(a.rounds):
+        for tag, path in builds:
+            cmd = [sys.executable, os.path.abspath(__file__), "--worker", path, "--warmup", str(a.warmup), "--runs", str(a.runs)]
+            for n in names:
+                cmd += ["--config", n]
+            p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+            if p.returncode != 0:
+                raise SystemExit(f"gray_bench: the child of build '{tag}' ended with {p.returncode}: {p.stderr[-2000:]}")
+            rounds[tag].append(json.loads(p.stdout.strip().splitlines()[-1]))
+    lines = [json.dumps({"block": "batch", "unit": "device ms per pair", "rounds": a.rounds, "warmup": a.warmup, "runs": a.runs,
+                         "builds": [t for t, _ in builds], "loop": LOOP})]
+    for tag, _ in builds:
+        for key in rounds[tag][0]:
+            per_round = [r[key] for r in rounds[tag]]
+            allv = [v for r in per_round for v in r]
+            bests = [min(r) for r in per_round]
+            name, form = key.split(".")
+            lines.append(json.dumps({"build": tag, "config": name, "size": "x".join(map(str, CONFIGS[name])), "form": form,
+                                     "best": round(min(allv), 4), "median": round(float(np.median(allv)), 4),
+                                     "spread_of_round_bests": round(max(bests) - min(bests), 4), "worst": round(max(allv), 4)}))
+    for line in lines:
+        print(line, flush=True)
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--batch", action="store_true", help="psm_gray_compute_batch beside a loop of single calls")
+    ap.add_argument("--parent-lib", help="--batch: another build of libprimesm_hip.so to measure in alternation (single calls only)")
+    ap.add_argument("--rounds", type=int, default=2, help="--batch: child processes per build")
+    ap.add_argument("--worker", help=argparse.SUPPRESS)
     ap.add_argument("--config", action="append", choices=sorted(CONFIGS), help="default: all three")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--runs", type=int, default=20)
     ap.add_argument("--out", help="append the JSON lines to this file")
     a = ap.parse_args()
+    if a.worker:
+        print(json.dumps(worker(a.worker, a.config or ["cones"], a.warmup, a.runs)), flush=True)
+        return
+    if a.batch:
+        return batch_bench(a)
     import torch
     from primestereomatch_amd import capi
     capi.load()
