@@ -828,7 +828,41 @@ int psm_reproject_time(psm_ctx *ctx, double *ms);
  * connected to no valid pixel).  A good pixel gets min(max(rintf(q), inv + 1), 32767), every other pixel inv: the result has the
  * conventions of the map it came from.  The float plane holds q for good pixels and the stored pattern 0x7FC00000 elsewhere. */
 enum { PSM_WLS_GIF = 0, PSM_WLS_SGM = 1 };                                /* sources (numbered as PSM_DEPTH_*) */
-enum { PSM_WLS_USE_MASK = 1 };                                            /* flags */
+enum { PSM_WLS_USE_MASK = 1, PSM_WLS_CONFIDENCE = 2 };                    /* flags */
+enum { PSM_WLS_CONF_LR = 1, PSM_WLS_CONF_VAR = 2 };                       /* terms of the graded confidence */
+/* PSM_WLS_CONFIDENCE (the SGM source only): the start is graded - den = (float)conf, num = (float)conf * (float)v, one exact
+ * multiply - with a confidence byte per pixel from the left-right consistency of the SGM stage's summed costs S and from the
+ * variance of the map around the pixel; everything behind the start is unchanged.  The definition is tests/wls_conf_model.py,
+ * all integer; the device equals it in every bit.  (A confidence of 255 everywhere is not the unflagged start bit for bit: a
+ * call without the flag is the stage as it ever was.)
+ *   right16[y][xr]  the right view's map in 16ths from the S [H][W][D] of the last psm_sgm_compute* with its range (dmin, D): the
+ *                   smallest (S[y][xr + dmin + k][k], k) over the k in [0, D) with 0 <= xr + dmin + k < W, the lowest k on ties;
+ *                   xl = xr + dmin + k, S0 that minimum; inner = 0 < k < D-1 and xl-1 >= 0 and xl+1 < W; Sm = S[y][xl-1][k-1],
+ *                   Sp = S[y][xl+1][k+1]; den = max(Sm + Sp - 2 S0, 1), sub = floor(((Sm - Sp) 16 + den) / (2 den)); the value is
+ *                   (dmin + k) 16 + (inner ? sub : 0); a column without a candidate gets rinv = (dmin - 1) 16.
+ *   L-R term        0 where v == inv; else xq = x - ((v + 8) >> 4), arithmetic; 0 if xq is outside [0, W) or right16[y][xq] ==
+ *                   rinv; else 255 - min((|v - right16[y][xq]| 255) / lr_thresh, 255), the quotient floored.
+ *   variance term   over the (2 radius + 1)^2 window, pixels outside the image and invalid ones contributing nothing: n the
+ *                   count, s the sum of v, ss the sum of v^2, t = floor((255 (n ss - s^2)) / (n^2 << var_shift)); 255 - min(t, 255)
+ *                   where the centre is valid, 0 elsewhere (var_shift 8: one step per square pixel of disparity variance).
+ *   conf            floor((c_var c_lr + 127) / 255), a term that is switched off counting as 255, an invalid pixel 0.
+ * Out of scope: a confidence for the GIF source, a speckle or uniqueness pass on the right map, a confidence supplied by the
+ * host; agreement with a live OpenCV stays unpinned, like the rest of the stage.
+ * psm_wls_set_confidence: terms in {1, 2, 3}, lr_thresh in [1, 32767], radius in [1, 4], var_shift in [0, 16].  A new context has
+ * (PSM_WLS_CONF_LR | PSM_WLS_CONF_VAR, 24, 2, 8); the parameters survive psm_release_scratch.
+ * Under the flag psm_wls_filter and psm_wls_filter_batch launch k_sgm_right16 (if a member has the L-R term; members without it
+ * take no part) and k_wls_conf ahead of their 1 + 2 T launches; a batch uses every member's own terms and parameters.  The two
+ * planes - 3 more bytes per pixel - are allocated on first use and given back by psm_release_scratch.  Refused ahead of the first
+ * launch, the previous result intact (a batch: naming the member): the flag with PSM_WLS_GIF; the L-R term while the plane of
+ * psm_score_upload_sgm_map is on (S does not belong to it) or without the S of a psm_sgm_compute* of this context (never
+ * computed, or released), or with a range or width k_sgm_right16 cannot serve.  The variance term alone needs only the map. */
+int psm_wls_set_confidence(psm_ctx *ctx, int terms, int lr_thresh, int radius, int var_shift);
+/* The confidence bytes and the right map of the last psm_wls_filter; either pointer may be NULL.  conf as H rows of W bytes
+ * conf_stride apart, right16 as H rows of W int16 right_stride_bytes apart (0: packed; right_stride_bytes even).  Refused after
+ * a call without PSM_WLS_CONFIDENCE, and right16 after one without the L-R term.  Synchronises. */
+int psm_wls_download_confidence(psm_ctx *ctx, uint8_t *conf, size_t conf_stride, int16_t *right16, size_t right_stride_bytes);
+/* Device ms of the two launches PSM_WLS_CONFIDENCE adds (they lie inside psm_wls_time's bracket too); needs PSM_OPT_PROFILE. */
+int psm_wls_conf_time(psm_ctx *ctx, double *ms);
 /* lambda > 0, sigma > 0, both finite; iterations in [1, 4].  A new context has (8000, 1.5, 3); the parameters survive
  * psm_release_scratch. */
 int psm_wls_set_params(psm_ctx *ctx, float lambda, float sigma, int iterations);

@@ -40,7 +40,8 @@ PSM_DEPTH_USE_MASK = 1
 PSM_DEPTH_VOID = 0x7FC00000          # the bit pattern of a void pixel in the dense planes
 # the WLS smoothing stage: sources, flags
 PSM_WLS_GIF, PSM_WLS_SGM = 0, 1
-PSM_WLS_USE_MASK = 1
+PSM_WLS_USE_MASK, PSM_WLS_CONFIDENCE = 1, 2
+PSM_WLS_CONF_LR, PSM_WLS_CONF_VAR = 1, 2   # the terms of the graded confidence (psm_wls_set_confidence)
 PSM_WLS_VOID = 0x7FC00000            # the bit pattern of a void pixel in the float plane
 
 
@@ -178,6 +179,9 @@ SYMBOLS = [
     ("psm_wls_download_table", _i, [_vp, _vp]),
     ("psm_wls_time", _i, [_vp, _pd]),
     ("psm_wls_publish", _i, [_vp, _i]),
+    ("psm_wls_set_confidence", _i, [_vp, _i, _i, _i, _i]),
+    ("psm_wls_download_confidence", _i, [_vp, _vp, _sz, _vp, _sz]),
+    ("psm_wls_conf_time", _i, [_vp, _pd]),
     ("psm_gray_compute", _i, [_vp, _vp, _vp, _sz, _i, _vp, _vp, _sz]),
     ("psm_gray_compute_batch", _i, [C.POINTER(_vp), _i, C.POINTER(_vp), C.POINTER(_vp), _sz, _i, C.POINTER(_vp), C.POINTER(_vp), _sz]),
     ("psm_gray_time", _i, [_vp, _pd]),

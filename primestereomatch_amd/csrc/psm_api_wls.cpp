@@ -6,9 +6,12 @@
 // mask through psm::Results - and the left image of the pair, and writes its own planes (psm::WlsState).  psm_wls_publish lets the
 // SGM sources of psm_score and psm_reproject read its result instead of the SGM stage's.
 // psm_wls_filter_batch: the same launches for the maps of several contexts at once, the context on a grid axis of its own.
+// PSM_WLS_CONFIDENCE (psm_wls_set_confidence; tests/wls_conf_model.py): wls_run puts k_sgm_right16 and k_wls_conf ahead of them and
+// the solve starts with a graded confidence instead of one bit per pixel.
 #include "psm_ctx.h"
 #include "psm_wls_tab.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <vector>
@@ -30,6 +33,10 @@ void wls_free(psm_ctx *c)
     if (w.ev_done) (void)hipEventDestroy(w.ev_done);
     w.ev_done = nullptr;
     bracket_free(w.prof);
+    (void)hipFree(w.conf); w.conf = nullptr;
+    (void)hipFree(w.r16); w.r16 = nullptr;
+    bracket_free(w.conf_prof);
+    w.have_conf = 0;
     w.have = w.pending = w.publish = false;
 }
 
@@ -37,7 +44,7 @@ void wls_free(psm_ctx *c)
 
 namespace {
 
-constexpr int WLS_FLAGS_ALL = PSM_WLS_USE_MASK;
+constexpr int WLS_FLAGS_ALL = PSM_WLS_USE_MASK | PSM_WLS_CONFIDENCE;
 
 // what psm_wls_filter refuses about the call's own arguments (no context needed) ...
 int check_call(psm_ctx *e, const char *who, int source, int flags)
@@ -46,6 +53,18 @@ int check_call(psm_ctx *e, const char *who, int source, int flags)
     if (flags & ~WLS_FLAGS_ALL) return fail(e, "%s: unknown flag bits 0x%x", who, flags & ~WLS_FLAGS_ALL);
     if ((flags & PSM_WLS_USE_MASK) && source != PSM_WLS_GIF)
         return fail(e, "%s: PSM_WLS_USE_MASK with the SGM source (the L-R mask belongs to the 8-bit maps)", who);
+    if ((flags & PSM_WLS_CONFIDENCE) && source != PSM_WLS_SGM)
+        return fail(e, "%s: flag bits 0x%x (PSM_WLS_CONFIDENCE) with the GIF source (the confidence is made of the SGM stage's map and costs)", who,
+                    PSM_WLS_CONFIDENCE);
+    return 0;
+}
+
+int check_conf_params(psm_ctx *e, const char *who, int terms, int lr_thresh, int radius, int var_shift)
+{
+    if (terms < 1 || terms > (PSM_WLS_CONF_LR | PSM_WLS_CONF_VAR)) return fail(e, "%s: terms %d not in {1: PSM_WLS_CONF_LR, 2: PSM_WLS_CONF_VAR, 3: both}", who, terms);
+    if (lr_thresh < 1 || lr_thresh > 32767) return fail(e, "%s: lr_thresh %d outside [1, 32767]", who, lr_thresh);
+    if (radius < 1 || radius > WLS_CONF_RMAX) return fail(e, "%s: radius %d outside [1, %d]", who, radius, WLS_CONF_RMAX);
+    if (var_shift < 0 || var_shift > 16) return fail(e, "%s: var_shift %d outside [0, 16]", who, var_shift);
     return 0;
 }
 
@@ -61,10 +80,24 @@ int check_ctx(psm_ctx *e, const psm_ctx *c, const char *who, int source, int fla
     }
     if (!colour_of(c, source == PSM_WLS_SGM).img)
         return fail(e, "%s: no current image pair (psm_upload_pair: the left image guides the smoothing)", who);
+    if ((flags & PSM_WLS_CONFIDENCE) && (c->wls.conf_terms & PSM_WLS_CONF_LR)) {
+        // the L-R term reads the S the map was selected from: the last psm_sgm_compute*'s of this context, with that result's range
+        // (with the hook plane off, sgm_stage_exists above has answered for a compute that never ran or was released: S lives and
+        // dies with the map)
+        const SgmState &g = c->sgm;
+        if (c->score.hook_on)
+            return fail(e, "%s: flag bits 0x%x (PSM_WLS_CONFIDENCE): the L-R term while the plane of psm_score_upload_sgm_map is on (the summed costs do not belong to it)",
+                        who, PSM_WLS_CONFIDENCE);
+        if (g.res_d < 1 || g.res_d > SGM_DMAX || g.res_dmin < -SGM_DMAX || g.res_dmin > SGM_DMAX)
+            return fail(e, "%s: the result's range (min_disparity %d, %d disparities) is outside what k_sgm_right16 serves", who, g.res_dmin, g.res_d);
+        if ((size_t)c->W * sizeof(unsigned) > WLS_R16_LDS_MAX)
+            return fail(e, "%s: width %d: a row's keys (%zu bytes) exceed the %zu bytes of LDS a workgroup takes", who, c->W, (size_t)c->W * sizeof(unsigned),
+                        WLS_R16_LDS_MAX);
+    }
     return 0;
 }
 
-int ensure_buffers(psm_ctx *c)
+int ensure_buffers(psm_ctx *c, int flags)
 {
     WlsState &w = c->wls;
     const size_t HW = (size_t)c->W * c->H;
@@ -74,6 +107,11 @@ int ensure_buffers(psm_ctx *c)
     if (!w.q) PSM_HIP(c, hipMalloc((void **)&w.q, HW * sizeof(unsigned)));
     if (!w.tab) PSM_HIP(c, hipMalloc((void **)&w.tab, WLS_TAB * sizeof(float)));
     if (!w.ev_done) PSM_HIP(c, hipEventCreateWithFlags(&w.ev_done, hipEventDisableTiming));
+    if (flags & PSM_WLS_CONFIDENCE) {
+        if (!w.conf) PSM_HIP(c, hipMalloc((void **)&w.conf, HW));
+        if (!w.r16) PSM_HIP(c, hipMalloc((void **)&w.r16, HW * sizeof(int16_t)));
+        if (bracket_events(c, w.conf_prof)) return 1;
+    }
     return bracket_events(c, w.prof);
 }
 
@@ -96,7 +134,23 @@ WlsArgs wls_args(const psm_ctx *c, int source, int flags)
     a.W = c->W; a.H = c->H; a.source = source;
     a.invalid = source == PSM_WLS_GIF ? -16 : sgm_stage_invalid(c);
     a.depth = col.depth; a.ch = col.ch;
+    a.conf = (flags & PSM_WLS_CONFIDENCE) ? w.conf : nullptr;
     return a;
+}
+
+// the member's own terms and parameters, and - the L-R term - the S of its SGM result with that result's range
+WlsConf wls_conf_args(const psm_ctx *c, int flags)
+{
+    WlsConf k = {};
+    if (!(flags & PSM_WLS_CONFIDENCE)) return k;
+    const WlsState &w = c->wls;
+    k.r16 = w.r16; k.conf = w.conf;
+    k.terms = w.conf_terms; k.thresh = w.conf_thresh; k.radius = w.conf_radius; k.shift = w.conf_shift;
+    if (k.terms & PSM_WLS_CONF_LR) {
+        k.S = c->sgm.S;
+        k.D = c->sgm.res_d; k.Dp = sgm_dp(c->sgm.res_d); k.dmin = c->sgm.res_dmin;
+    }
+    return k;
 }
 
 // the planes of the last run, complete: an asynchronous run is waited for on the way
@@ -133,11 +187,12 @@ int wls_run(const char *who, psm_ctx *const *ctxs, int n, int source, int flags,
 
     // ---- buffers, events and the table's memory: before any launch ----
     for (int i = 0; i < n; ++i)
-        if (ensure_buffers(ctxs[i])) return member_failed(c0, who, i, ctxs[i]);
+        if (ensure_buffers(ctxs[i], flags)) return member_failed(c0, who, i, ctxs[i]);
     if (batch_events(c0, ctxs, n)) return 1;
     std::vector<WlsPair> tab((size_t)n);
     for (int i = 0; i < n; ++i) {
         tab[i].a = wls_args(ctxs[i], source, flags);
+        tab[i].c = wls_conf_args(ctxs[i], flags);
         for (int t = 0; t < T; ++t) tab[i].lam[t] = wls_lambda(ctxs[i]->wls.lambda, T, t);
     }
     bool fresh = false;
@@ -152,15 +207,23 @@ int wls_run(const char *who, psm_ctx *const *ctxs, int n, int source, int flags,
 
     for (int i = 0; i < n; ++i) {
         WlsState &w = ctxs[i]->wls;
-        w.have = w.pending = w.prof.timed = false;   // (every check and allocation lies before this: the planes are about to be rewritten)
+        w.have = w.pending = w.prof.timed = w.conf_prof.timed = false;   // (every check and allocation lies before this: the planes are about to be rewritten)
     }
     if (bracket_open(c0, c0->wls.prof, s)) return 1;
+    if (flags & PSM_WLS_CONFIDENCE) {                // the confidence bytes of every member, from its map and - the L-R term - its S
+        int dp_max = 0;
+        for (const WlsPair &p : tab) dp_max = std::max(dp_max, p.c.Dp);
+        if (bracket_open(c0, c0->wls.conf_prof, s)) return 1;
+        if (dp_max) launch_sgm_right16(s, q, dp_max);
+        launch_wls_conf(s, q);
+        if (bracket_close(c0, c0->wls.conf_prof, s)) return 1;
+    }
     launch_wls_init(s, q);
     for (int t = 0; t < T; ++t) {
         launch_wls_rows(s, q, t);
         launch_wls_cols(s, q, t, t == T - 1);
     }
-    if (check_launch(c0, "k_wls_init, k_wls_rows, k_wls_cols")) return 1;
+    if (check_launch(c0, "k_sgm_right16, k_wls_conf, k_wls_init, k_wls_rows, k_wls_cols")) return 1;
     if (bracket_close(c0, c0->wls.prof, s)) return 1;
 
     // ---- every context is now where its own psm_wls_filter would have left it; only context 0 counts as timed ----
@@ -174,6 +237,7 @@ int wls_run(const char *who, psm_ctx *const *ctxs, int n, int source, int flags,
         WlsState &w = ctxs[i]->wls;
         w.have = true;
         w.invalid = tab[i].a.invalid;
+        w.have_conf = tab[i].c.terms;
         w.pending = c0->opt_async != 0;
     }
     if (!c0->opt_async) PSM_HIP(c0, hipStreamSynchronize(s));
@@ -193,6 +257,17 @@ int psm_wls_set_params(psm_ctx *c, float lambda, float sigma, int iterations)
     c->wls.lambda = lambda;
     c->wls.sigma = sigma;
     c->wls.iters = iterations;
+    return 0;
+}
+
+int psm_wls_set_confidence(psm_ctx *c, int terms, int lr_thresh, int radius, int var_shift)
+{
+    if (check_conf_params(c, "psm_wls_set_confidence", terms, lr_thresh, radius, var_shift)) return 1;
+    if (!c) return fail(nullptr, "psm_wls_set_confidence: NULL context");
+    c->wls.conf_terms = terms;
+    c->wls.conf_thresh = lr_thresh;
+    c->wls.conf_radius = radius;
+    c->wls.conf_shift = var_shift;
     return 0;
 }
 
@@ -254,6 +329,31 @@ int psm_wls_download(psm_ctx *c, int16_t *disp, float *q, float *num, float *den
     if (num && d2h_rows(c, num, w.work, row, stride_bytes, c->H)) return 1;
     if (den && d2h_rows(c, den, w.work + HW, row, stride_bytes, c->H)) return 1;
     return 0;
+}
+
+int psm_wls_download_confidence(psm_ctx *c, uint8_t *conf, size_t conf_stride, int16_t *right16, size_t right_stride_bytes)
+{
+    const char *who = "psm_wls_download_confidence";
+    if (!c) return fail(nullptr, "%s: NULL context", who);
+    const size_t row = (size_t)c->W;
+    if (conf_stride == 0) conf_stride = row;
+    if (right_stride_bytes == 0) right_stride_bytes = 2 * row;
+    if (conf_stride < row) return fail(c, "%s: conf_stride %zu below the row size %zu", who, conf_stride, row);
+    if (right_stride_bytes < 2 * row || right_stride_bytes % 2) return fail(c, "%s: right_stride_bytes %zu: a multiple of 2, at least the row size %zu", who, right_stride_bytes, 2 * row);
+    if (result_ready(c, who)) return 1;
+    const WlsState &w = c->wls;
+    if (!w.have_conf) return fail(c, "%s: the last psm_wls_filter ran without PSM_WLS_CONFIDENCE", who);
+    if (right16 && !(w.have_conf & PSM_WLS_CONF_LR)) return fail(c, "%s: the last psm_wls_filter ran without the L-R term: there is no right map", who);
+    if (conf && d2h_rows(c, conf, w.conf, row, conf_stride, c->H)) return 1;
+    if (right16 && d2h_rows(c, right16, w.r16, 2 * row, right_stride_bytes, c->H)) return 1;
+    return 0;
+}
+
+int psm_wls_conf_time(psm_ctx *c, double *ms)
+{
+    if (!c) return fail(nullptr, "psm_wls_conf_time: NULL context");
+    return bracket_ms(c, c->wls.conf_prof, c->wls.have && c->wls.have_conf, "psm_wls_conf_time",
+                      "the last psm_wls_filter was not timed (PSM_OPT_PROFILE) or ran without PSM_WLS_CONFIDENCE", ms);
 }
 
 int psm_wls_download_table(psm_ctx *c, float tab[256])

@@ -199,7 +199,7 @@ struct DepthState {
 
 // psm_wls_filter (psm_api_wls.cpp): parameters (they survive psm_release_scratch) and the stage's planes, allocated on first use
 // and given back by psm_release_scratch - 35 bytes per pixel: the working planes, the 12 bytes of the forward sweeps, the link
-// indices, the result.
+// indices, the result - and 3 more under PSM_WLS_CONFIDENCE.
 struct WlsState {
     float lambda = 8000.0f, sigma = 1.5f;
     int iters = 3;
@@ -217,6 +217,13 @@ struct WlsState {
     bool pending = false;                          // an asynchronous run has not been waited for (psm_wls_wait)
     bool publish = false;                          // psm_wls_publish: the SGM sources of psm_score / psm_reproject read `out`
     DevTable pairs;                                // psm_wls_filter_batch (this context as the first of a batch): WlsPair records
+    // PSM_WLS_CONFIDENCE (psm_wls_set_confidence: the parameters survive psm_release_scratch too): 3 more bytes per pixel,
+    // allocated when first used
+    int conf_terms = PSM_WLS_CONF_LR | PSM_WLS_CONF_VAR, conf_thresh = 24, conf_radius = 2, conf_shift = 8;
+    uint8_t *conf = nullptr;                       // [H][W]: the confidence bytes
+    int16_t *r16 = nullptr;                        // [H][W]: the right view's map in 16ths
+    int have_conf = 0;                             // the terms the last run's planes were made with (0: it had no flag)
+    Bracket conf_prof;                             // PSM_OPT_PROFILE: around the two launches ahead of k_wls_init (psm_wls_conf_time)
 };
 
 // psm_gray_compute (psm_api_gray.cpp): the stage's own device buffers - the pair's planes, 16 bytes of guidance per pixel and side,

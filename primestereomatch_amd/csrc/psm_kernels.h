@@ -436,6 +436,22 @@ struct WlsArgs {
     int W, H, source;
     int invalid;                       // the invalid value of the source map, and of the result
     int depth, ch;                     // of img: PSM_IMG_*, 3 or 1 channels
+    const uint8_t *conf;               // PSM_WLS_CONFIDENCE: [H][W], the confidence bytes k_wls_conf wrote - num = conf * v, den = conf; else null
+};
+// PSM_WLS_CONFIDENCE (tests/wls_conf_model.py): what the two launches ahead of k_wls_init read of a member - its own terms and
+// parameters, and, with the L-R term, the S of its SGM result with the range that result has.  terms 0: the call has no flag.
+enum { WLS_CONF_LR = 1, WLS_CONF_VAR = 2 };            // PSM_WLS_CONF_* (include/primesm_hip.h)
+constexpr int WLS_CONF_RMAX = 4;                       // the widest radius of the variance window
+constexpr int WLS_CONF_TX = 64, WLS_CONF_TY = 4;       // k_wls_conf: the pixels of a workgroup's tile - a wave per row, the lane as x: every LDS
+                                                       // instruction of a wave reads 64 consecutive dwords, whatever the pitch
+constexpr int WLS_R16_WAVES = 8;                       // k_sgm_right16: waves of a row's workgroup
+constexpr size_t WLS_R16_LDS_MAX = 65536;              // ... whose W keys of 4 bytes must fit
+struct WlsConf {
+    const uint32_t *S;                 // [H][W][Dp]: the summed path costs of the member's SGM result (L-R term only)
+    int16_t *r16;                      // [H][W]: the right view's map in 16ths, k_sgm_right16's
+    uint8_t *conf;                     // [H][W]: the confidence bytes, k_wls_conf's
+    int terms, thresh, radius, shift;
+    int D, Dp, dmin;                   // of S
 };
 __host__ __device__ inline int wls_groups(int lines) { return (lines + WLS_LINES - 1) / WLS_LINES; }
 // One call's record - psm_wls_filter's, or a member's of a batch (psm_wls_filter_batch) - and the lambdas of its passes: lambda and
@@ -444,8 +460,13 @@ __host__ __device__ inline int wls_groups(int lines) { return (lines + WLS_LINES
 struct WlsPair {
     WlsArgs a;
     float lam[WLS_MAX_ITERS];          // wls_lambda(lambda, T, t), t < T; the rest 0
+    WlsConf c;                         // PSM_WLS_CONFIDENCE; else zeros
 };
-void launch_wls_init(hipStream_t s, const Recs<WlsPair> &q);                   // k_wls_init: num, den, kh, kv
+// k_sgm_right16: r16 of every member with the L-R term (the others' workgroups return at once); one workgroup per image row with
+// 4 W bytes of dynamic LDS (<= WLS_R16_LDS_MAX); dp_max: the largest Dp among those members (the per-lane count of the launch)
+void launch_sgm_right16(hipStream_t s, const Recs<WlsPair> &q, int dp_max);
+void launch_wls_conf(hipStream_t s, const Recs<WlsPair> &q);                   // k_wls_conf: conf from the source map and r16
+void launch_wls_init(hipStream_t s, const Recs<WlsPair> &q);                   // k_wls_init: num, den, kh, kv; a.conf of q.host[0] non-null: the weighted start
 void launch_wls_rows(hipStream_t s, const Recs<WlsPair> &q, int t);            // k_wls_rows: pass t over every row
 void launch_wls_cols(hipStream_t s, const Recs<WlsPair> &q, int t, bool last);   // k_wls_cols: ... every column; last: and the quotient, out and q
 

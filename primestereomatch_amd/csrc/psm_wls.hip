@@ -13,6 +13,8 @@
 //               cp, np, dp in the scratch planes, the back sweep takes the tiles in reverse and writes num and den
 //   k_wls_cols  one pass over every column: the lane is x, so its walk is coalesced as it stands; the loads of WLS_CHUNK steps are
 //               in flight ahead of the chain.  The last one forms the quotient, the int16 map and the float plane in its back sweep
+// Under PSM_WLS_CONFIDENCE two launches lie ahead of them - k_sgm_right16, k_wls_conf (below: the graded confidence of
+// tests/wls_conf_model.py) - and k_wls_init starts with num = conf * v, den = conf.
 // No atomics, no workgroup waits for another (the order between the launches is the stream's), no scratch memory.  The chain of a
 // step - multiply, subtract, divide, multiply - is the definition's and is not reordered.
 #include "psm_kernels.h"
@@ -42,9 +44,143 @@ __device__ __forceinline__ WlsArgs wls_pair(const S &src)
     a.map = sgm_global(p.map); a.valid = sgm_global(p.valid); a.d16 = sgm_global(p.d16); a.img = sgm_global(p.img);
     a.num = sgm_global(p.num); a.den = sgm_global(p.den); a.cp = sgm_global(p.cp); a.np = sgm_global(p.np); a.dp = sgm_global(p.dp);
     a.kh = sgm_global(p.kh); a.kv = sgm_global(p.kv); a.tab = sgm_global(p.tab); a.out = sgm_global(p.out); a.q = sgm_global(p.q);
+    a.conf = sgm_global(p.conf);
     return a;
 }
+template <typename S>
+__device__ __forceinline__ WlsConf wls_conf_of(const S &src)
+{
+    const WlsConf &p = rec(src, blockIdx.y).c;
+    WlsConf c = p;
+    c.S = sgm_global(p.S); c.r16 = sgm_global(p.r16); c.conf = sgm_global(p.conf);
+    return c;
+}
 
+// ---- PSM_WLS_CONFIDENCE: the two launches ahead of k_wls_init (tests/wls_conf_model.py) -----------------------------
+//   k_sgm_right16  the right view's sub-pixel map in 16ths from S, built the way k_sgm_maps is (psm_sgm.hip): a workgroup owns one
+//                  image row and holds the row's W right keys in LDS, all ones to begin with; S is read once, a pixel's
+//                  disparities across the lanes of a wave (lane l holds the indices l, l + 64, ..: the 64 lanes of one LDS
+//                  instruction go to 64 consecutive slots), and every lane takes the LDS minimum of (S << 10 | k) - 29 bits, as
+//                  S < 2^19: never the all-ones start - into slot x - dmin - k.  The body has no branch: what takes no part (a lane
+//                  past D, a landing column left OR right of the image - dmin may be negative -, a pixel past the row's end) loads
+//                  a clamped address and brings the all-ones key to a mirrored, clamped slot inside the row.  After the barrier a
+//                  thread takes right pixels: the neighbours Sm, Sp on the candidate's diagonal by two gathered loads of the row
+//                  just read (L2), the sub-pixel step with k_sgm_select's expressions, one coalesced int16 store.
+//   k_wls_conf     the confidence byte of every pixel: a tile of the int16 map with a halo of WLS_CONF_RMAX goes through LDS as
+//                  dwords (an invalid or outside pixel as WLS_NONE); a wave is one row of the tile with the lane as x, so every
+//                  LDS read of a wave is of 64 consecutive dwords.  Window sums in 64-bit integers, one 64-bit division per pixel.
+// No atomics on global memory, no workgroup waits for another, no scratch memory.
+constexpr int WLS_NONE = (int)0x80000000;
+
+template <int NV>
+__device__ __forceinline__ void sgm_right16(const WlsConf &c, int W, int y)
+{
+    extern __shared__ unsigned wls_r16_keys[];                     // [W] the right view's packed minima
+    constexpr int U = NV > 4 ? 2 : 4;                              // pixels whose loads are issued ahead of their minima
+    constexpr int T = WLS_R16_WAVES * 64;
+    unsigned *rkey = wls_r16_keys;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = threadIdx.x; i < W; i += T) rkey[i] = 0xffffffffu;
+    __syncthreads();
+    const unsigned *Srow = c.S + (size_t)y * W * c.Dp;
+    for (int x0 = wave; x0 < W; x0 += WLS_R16_WAVES * U) {         // (wave-uniform)
+        unsigned s[U][NV];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const unsigned *Sp = Srow + (size_t)min(x0 + u * WLS_R16_WAVES, W - 1) * c.Dp;
+#pragma unroll
+            for (int j = 0; j < NV; ++j) s[u][j] = Sp[min(j * 64 + lane, c.Dp - 1)];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int x = x0 + u * WLS_R16_WAVES;
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                const int k = j * 64 + lane;
+                const bool real = k < c.D && x < W;                // (the padding elements of Dp take no part)
+                const unsigned key = (s[u][j] << 10) | (unsigned)k;
+                const int xr = x - c.dmin - k;                     // the landing column: on either side of the image with dmin < 0
+                const int xm = xr < 0 ? -xr - 1 : (xr >= W ? 2 * W - 1 - xr : xr);
+                atomicMin(rkey + min(max(xm, 0), W - 1), real && xr >= 0 && xr < W ? key : 0xffffffffu);
+            }
+        }
+    }
+    __syncthreads();
+    int16_t *out = c.r16 + (size_t)y * W;
+    const int rinv = (c.dmin - 1) * 16;
+    for (int i = threadIdx.x; i < W; i += T) {
+        const unsigned key = rkey[i];
+        const bool none = key == 0xffffffffu;
+        const int k = (int)(key & 1023u), s0 = (int)(key >> 10), xl = i + c.dmin + k;
+        const bool inner = k > 0 && k < c.D - 1 && xl - 1 >= 0 && xl + 1 < W;
+        const int km = min(max(k - 1, 0), c.D - 1), kp = min(k + 1, c.D - 1);
+        const int sm = (int)Srow[(size_t)min(max(xl - 1, 0), W - 1) * c.Dp + km];
+        const int sp = (int)Srow[(size_t)min(max(xl + 1, 0), W - 1) * c.Dp + kp];
+        const int den = max(sm + sp - 2 * s0, 1);
+        const int num = (sm - sp) * 16 + den, dd = 2 * den;
+        int q = num / dd;
+        if (num % dd != 0 && num < 0) --q;                         // floor
+        out[i] = (int16_t)(none ? rinv : (c.dmin + k) * 16 + (inner ? q : 0));
+    }
+}
+
+template <int NV, typename S>
+__global__ __launch_bounds__(WLS_R16_WAVES * 64) void k_sgm_right16(S src)
+{
+    const WlsConf c = wls_conf_of(src);
+    if (!(c.terms & WLS_CONF_LR)) return;                          // (uniform: a member without the L-R term takes no part)
+    sgm_right16<NV>(c, rec(src, blockIdx.y).a.W, blockIdx.x);
+}
+
+__device__ __forceinline__ void wls_conf(const WlsArgs &a, const WlsConf &c)
+{
+    constexpr int R = WLS_CONF_RMAX, LW = WLS_CONF_TX + 2 * R, LH = WLS_CONF_TY + 2 * R;
+    __shared__ int tile[LH * LW];
+    const int W = a.W, H = a.H, tx = (W + WLS_CONF_TX - 1) / WLS_CONF_TX;
+    const int y0 = (int)(blockIdx.x / tx) * WLS_CONF_TY, x0 = (int)(blockIdx.x % tx) * WLS_CONF_TX;
+    for (int e = threadIdx.x; e < LH * LW; e += WLS_CONF_TX * WLS_CONF_TY) {
+        const int gy = y0 - R + e / LW, gx = x0 - R + e % LW;
+        const bool inside = gy >= 0 && gy < H && gx >= 0 && gx < W;
+        const int v = a.d16[(size_t)min(max(gy, 0), H - 1) * W + min(max(gx, 0), W - 1)];
+        tile[e] = inside && v != a.invalid ? v : WLS_NONE;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, row = threadIdx.x >> 6, x = x0 + lane, y = y0 + row;
+    if (x >= W || y >= H) return;
+    const int *centre = tile + (row + R) * LW + lane + R;
+    const int v = *centre;
+    const bool valid = v != WLS_NONE;
+    unsigned cvar = 255, clr = 255;
+    if (c.terms & WLS_CONF_VAR) {                                  // (uniform)
+        unsigned n = 0;
+        int s = 0;                                                 // |s| <= 81 * 2^15
+        unsigned long long ss = 0;                                 // <= 81 * 2^30
+        for (int dy = -c.radius; dy <= c.radius; ++dy)
+            for (int dx = -c.radius; dx <= c.radius; ++dx) {
+                const int t = centre[dy * LW + dx];
+                const bool ok = t != WLS_NONE;
+                n += ok ? 1u : 0u;
+                s += ok ? t : 0;
+                ss += ok ? (unsigned)(t * t) : 0u;
+            }
+        const unsigned long long m = (unsigned long long)n * ss - (unsigned long long)((long long)s * s);   // n ss >= s^2 (Cauchy-Schwarz)
+        const unsigned long long den = max((unsigned long long)(n * n) << c.shift, 1ull);                   // (n = 0: the centre is invalid)
+        cvar = 255u - (unsigned)min(255ull * m / den, 255ull);
+    }
+    if (c.terms & WLS_CONF_LR) {
+        const int vv = valid ? v : 0, xq = x - ((vv + 8) >> 4);
+        const int r = c.r16[(size_t)y * W + min(max(xq, 0), W - 1)];
+        const bool ok = xq >= 0 && xq < W && r != (c.dmin - 1) * 16;
+        clr = ok ? 255u - min((unsigned)abs(vv - r) * 255u / (unsigned)c.thresh, 255u) : 0u;
+    }
+    c.conf[(size_t)y * W + x] = (uint8_t)(valid ? (cvar * clr + 127u) / 255u : 0u);
+}
+
+template <typename S> __global__ __launch_bounds__(WLS_CONF_TX * WLS_CONF_TY) void k_wls_conf(S src) { wls_conf(wls_pair(src), wls_conf_of(src)); }
+
+// CONF (PSM_WLS_CONFIDENCE, the SGM source): the start is weighted with the bytes of k_wls_conf, which are 0 in the invalid pixels -
+// den = (float)conf, num = (float)conf * (float)v, one exact multiply.  The instantiation without it is the stage's as it ever was.
+template <bool CONF>
 __device__ __forceinline__ void wls_init(WlsArgs a)
 {
     const size_t N = (size_t)a.W * a.H, i = (size_t)blockIdx.x * WLS_TILE + threadIdx.x;
@@ -59,8 +195,14 @@ __device__ __forceinline__ void wls_init(WlsArgs a)
         v = a.d16[i];
         valid = v != a.invalid;
     }
-    a.num[i] = valid ? (float)v : 0.0f;
-    a.den[i] = valid ? 1.0f : 0.0f;
+    if (CONF) {
+        const float c = (float)a.conf[i];
+        a.num[i] = __fmul_rn(c, (float)v);
+        a.den[i] = c;
+    } else {
+        a.num[i] = valid ? (float)v : 0.0f;
+        a.den[i] = valid ? 1.0f : 0.0f;
+    }
     const unsigned g = sgm_px(a.img, a.depth, a.ch, i);
     const unsigned gr = x < a.W - 1 ? sgm_px(a.img, a.depth, a.ch, i + 1) : g;
     const unsigned gd = y < a.H - 1 ? sgm_px(a.img, a.depth, a.ch, i + a.W) : g;
@@ -305,7 +447,8 @@ __device__ __forceinline__ void wls_cols(WlsArgs a, float lam, int last)
 }
 
 // The lambda of pass t is the record's own lam[t]: every member of a batch has its own lambda and sigma.
-template <typename S> __global__ __launch_bounds__(WLS_TILE) void k_wls_init(S src) { wls_init(wls_pair(src)); }
+template <typename S> __global__ __launch_bounds__(WLS_TILE) void k_wls_init(S src) { wls_init<false>(wls_pair(src)); }
+template <typename S> __global__ __launch_bounds__(WLS_TILE) void k_wls_init_conf(S src) { wls_init<true>(wls_pair(src)); }
 template <typename S>
 __global__ __launch_bounds__(WLS_ROW_THREADS) void k_wls_rows(S src, int t) { wls_rows(wls_pair(src), rec(src, blockIdx.y).lam[t]); }
 template <typename S>
@@ -318,7 +461,31 @@ void launch_wls_init(hipStream_t s, const Recs<WlsPair> &q)
 {
     const WlsArgs &a = q.host[0].a;
     const unsigned blocks = (unsigned)(((size_t)a.W * a.H + WLS_TILE - 1) / WLS_TILE);
-    rec_launch(s, k_wls_init<WlsV>, k_wls_init<WlsT>, dim3(blocks, (unsigned)q.n), dim3(WLS_TILE), 0, q);
+    if (a.conf) rec_launch(s, k_wls_init_conf<WlsV>, k_wls_init_conf<WlsT>, dim3(blocks, (unsigned)q.n), dim3(WLS_TILE), 0, q);
+    else rec_launch(s, k_wls_init<WlsV>, k_wls_init<WlsT>, dim3(blocks, (unsigned)q.n), dim3(WLS_TILE), 0, q);
+}
+
+void launch_sgm_right16(hipStream_t s, const Recs<WlsPair> &q, int dp_max)
+{
+    const WlsArgs &a = q.host[0].a;
+    const dim3 grid((unsigned)a.H, (unsigned)q.n), block(WLS_R16_WAVES * 64);
+    const size_t lds = (size_t)a.W * sizeof(unsigned);
+    auto go = [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        rec_launch(s, k_sgm_right16<NV, WlsV>, k_sgm_right16<NV, WlsT>, grid, block, lds, q);
+    };
+    if (dp_max <= 64) go(std::integral_constant<int, 1>{});
+    else if (dp_max <= 128) go(std::integral_constant<int, 2>{});
+    else if (dp_max <= 256) go(std::integral_constant<int, 4>{});
+    else if (dp_max <= 512) go(std::integral_constant<int, 8>{});
+    else go(std::integral_constant<int, 16>{});
+}
+
+void launch_wls_conf(hipStream_t s, const Recs<WlsPair> &q)
+{
+    const WlsArgs &a = q.host[0].a;
+    const unsigned tiles = (unsigned)((a.W + WLS_CONF_TX - 1) / WLS_CONF_TX) * (unsigned)((a.H + WLS_CONF_TY - 1) / WLS_CONF_TY);
+    rec_launch(s, k_wls_conf<WlsV>, k_wls_conf<WlsT>, dim3(tiles, (unsigned)q.n), dim3(WLS_CONF_TX * WLS_CONF_TY), 0, q);
 }
 
 void launch_wls_rows(hipStream_t s, const Recs<WlsPair> &q, int t)

@@ -440,13 +440,40 @@ class DispEst:
         """psm_wls_set_params: lambda > 0, sigma > 0, iterations in 1..4 (a new object: 8000, 1.5, 3)."""
         self._ck(self._lib.psm_wls_set_params(self._h, float(lam), float(sigma), int(iterations)), "setWLS")
 
-    def WLS_GPU(self, source: int = capi.PSM_WLS_SGM, use_mask: bool = False):
+    def setWLSConfidence(self, terms: int = capi.PSM_WLS_CONF_LR | capi.PSM_WLS_CONF_VAR, lr_thresh: int = 24, radius: int = 2,
+                         var_shift: int = 8):
+        """psm_wls_set_confidence: the terms (capi.PSM_WLS_CONF_LR | PSM_WLS_CONF_VAR) and parameters of the graded confidence
+        WLS_GPU(confidence=...) starts with - lr_thresh in 1..32767 (16ths), radius in 1..4, var_shift in 0..16."""
+        self._ck(self._lib.psm_wls_set_confidence(self._h, int(terms), int(lr_thresh), int(radius), int(var_shift)), "setWLSConfidence")
+
+    def WLS_GPU(self, source: int = capi.PSM_WLS_SGM, use_mask: bool = False, confidence=None):
         """psm_wls_filter: the confidence-weighted, edge-aware global smoothing (Fast Global Smoother) of the int16 map of the last
         SGBM_GPU (capi.PSM_WLS_SGM) or of the current left 8-bit map times 16 (PSM_WLS_GIF; use_mask: pixels the current L-R mask
         marks invalid are missing), guided by the left image: the holes are filled, the sixteenths stay.  Under PSM_OPT_ASYNC
         wls_wait() waits for it.  wls_map() and wls_planes() download the results; wls_publish() hands the map to the SGM
-        sources of Score_GPU and Reproject_GPU."""
-        self._ck(self._lib.psm_wls_filter(self._h, int(source), capi.PSM_WLS_USE_MASK if use_mask else 0), "WLS_GPU")
+        sources of Score_GPU and Reproject_GPU.
+        confidence: None, the default: every valid pixel starts with the weight 1.  Else a dict of setWLSConfidence's parameters
+        ({}: both terms, 24, 2, 8; PSM_WLS_SGM only): they are set, and the solve starts with the graded confidence of
+        tests/wls_conf_model.py (PSM_WLS_CONFIDENCE) - download_wls_confidence() gives its planes."""
+        flags = capi.PSM_WLS_USE_MASK if use_mask else 0
+        if confidence is not None:
+            self.setWLSConfidence(**confidence)
+            flags |= capi.PSM_WLS_CONFIDENCE
+        self._ck(self._lib.psm_wls_filter(self._h, int(source), flags), "WLS_GPU")
+
+    def download_wls_confidence(self, right: bool = True):
+        """The planes of the last WLS_GPU(confidence=...): (conf H x W uint8, right16 H x W int16 - the right view's map in 16ths;
+        None with right=False, which a run without the L-R term needs)."""
+        conf = np.empty((self.hei, self.wid), np.uint8)
+        r16 = np.empty((self.hei, self.wid), np.int16) if right else None
+        self._ck(self._lib.psm_wls_download_confidence(self._h, _ptr(conf), 0, _ptr(r16) if right else None, 0), "download_wls_confidence")
+        return conf, r16
+
+    def wls_conf_time(self):
+        """Device ms of the two launches the confidence adds to the last WLS_GPU; needs PSM_OPT_PROFILE."""
+        ms = C.c_double()
+        self._ck(self._lib.psm_wls_conf_time(self._h, C.byref(ms)), "wls_conf_time")
+        return ms.value
 
     def wls_wait(self):
         """Wait for the WLS_GPU enqueued under PSM_OPT_ASYNC."""
@@ -904,16 +931,24 @@ def reproject_batch(des, source: int = capi.PSM_DEPTH_GIF, outputs: int = capi.P
     return None if des[0].options.get(capi.PSM_OPT_ASYNC) else [int(v) for v in counts]
 
 
-def wls_batch(des, source: int = capi.PSM_WLS_SGM, use_mask: bool = False):
+def wls_batch(des, source: int = capi.PSM_WLS_SGM, use_mask: bool = False, confidence=None):
     """WLS_GPU of several DispEst objects of one geometry and one iteration count in one set of launches (psm_wls_filter_batch):
     each object's map with its own guide, lambda and sigma (setWLS) -> the list of filtered H x W int16 maps.  Every object
     afterwards behaves as after its own WLS_GPU (wls_map(), wls_planes(), wls_publish()); under PSM_OPT_ASYNC on des[0]: None,
-    every object's wls_wait() waits for it.  wls_time() of des[0] is the batch's (PSM_OPT_PROFILE)."""
+    every object's wls_wait() waits for it.  wls_time() of des[0] is the batch's (PSM_OPT_PROFILE).  confidence: WLS_GPU's - one
+    dict for every object, or a sequence of one dict per object (the terms and parameters may differ between them)."""
     des = list(des)
     if not des:
         return []
     arr = (C.c_void_p * len(des))(*[d._h for d in des])
     flags = capi.PSM_WLS_USE_MASK if use_mask else 0
+    if confidence is not None:
+        per = [confidence] * len(des) if isinstance(confidence, dict) else list(confidence)
+        if len(per) != len(des):
+            raise ValueError(f"wls_batch: {len(per)} confidence dicts for {len(des)} objects")
+        for d, k in zip(des, per):
+            d.setWLSConfidence(**k)
+        flags |= capi.PSM_WLS_CONFIDENCE
     capi.check(des[0]._lib.psm_wls_filter_batch(arr, len(des), int(source), flags), des[0]._h, "wls_batch")
     return None if des[0].options.get(capi.PSM_OPT_ASYNC) else [d.wls_map() for d in des]
 
@@ -990,7 +1025,8 @@ class FrameRing:
         outputs name it alone, else the dict {"xyz", "z", "cloud"} of what they name.
         wls = a dict of DispEst.setWLS's parameters ({}: lam 8000, sigma 1.5, iterations 3): every frame's left map goes through the
         WLS smoothing on the device behind its last stage (WLS_GPU, PSM_WLS_GIF; under lr_check with its mask); push / flush then
-        return one more element, the last: the filtered H x W int16 map in 16ths."""
+        return one more element, the last: the filtered H x W int16 map in 16ths.  (The dict's key "confidence", WLS_GPU's option, is
+        passed through with it - and refused by the library, whose confidence belongs to the SGM source.)"""
         if frames < 1:
             raise ValueError("FrameRing: frames must be >= 1")
         self.ctx = [DispEst(l, r, d, dtype=dtype, device=device) for _ in range(frames)]
@@ -1005,9 +1041,10 @@ class FrameRing:
         self._score = truth is not None
         self._depth = int(reproject)
         self._wls = wls is not None
+        self._wls_conf = wls.get("confidence") if self._wls else None
         if self._wls:
             for c in self.ctx:
-                c.setWLS(**wls)
+                c.setWLS(**{k: v for k, v in wls.items() if k != "confidence"})
         if self._score:
             for c in self.ctx:
                 c.set_truth(truth[0], truth[1])
@@ -1055,7 +1092,7 @@ class FrameRing:
         if self._depth:
             c.Reproject_GPU(capi.PSM_DEPTH_GIF, self._depth, use_mask=self._lrc)
         if self._wls:
-            c.WLS_GPU(capi.PSM_WLS_GIF, use_mask=self._lrc)
+            c.WLS_GPU(capi.PSM_WLS_GIF, use_mask=self._lrc, confidence=self._wls_conf)
         self._busy[i] = True
         return out
 

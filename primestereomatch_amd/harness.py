@@ -145,7 +145,9 @@ def compute_sgbm(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, er
     wls: None, the default: nothing is added.  Else a dict of DispEst.setWLS's parameters ({}: lam 8000, sigma 1.5, iterations
     3): the int16 map goes through the WLS smoothing on the device (DispEst.WLS_GPU) and is published, so that depth= gives the
     cloud of the filtered map; the record gains wls16, the filtered map, and (with gt) bp_percent_wls - bp_percent_int's metric on
-    its rounded reading min((max(v, 0) + 8) >> 4, 255)."""
+    its rounded reading min((max(v, 0) + 8) >> 4, 255).  The key "confidence" of the dict is not setWLS's: a dict of
+    DispEst.setWLSConfidence's parameters ({}: both terms, 24, 2, 8) - the solve then starts with the graded confidence
+    (PSM_WLS_CONFIDENCE: the L-R consistency of the stage's summed costs and the variance of the map around the pixel)."""
     out = {}
     lFrame, rFrame = np.ascontiguousarray(l_bgr), np.ascontiguousarray(r_bgr)
     with DispEst(lFrame, rFrame, maxDis, 8, True) as SMDE:
@@ -232,10 +234,20 @@ def compute_gray_batch(pairs, maxDis=64, gts=None, masks=None, scale_factor=4, e
     return outs
 
 
+def _wls_split(wls):
+    """the wls= dict -> (setWLS's parameters, the "confidence" dict or None)"""
+    params = {k: v for k, v in wls.items() if k != "confidence"}
+    return params, wls.get("confidence")
+
+
 def _wls(SMDE, out, wls, maxDis, gt, mask, scale_factor, error_threshold):
     """compute_sgbm's wls= option: the filtered map of the object's int16 map into the record, published to the SGM sources."""
-    SMDE.setWLS(**wls)
-    SMDE.WLS_GPU(capi.PSM_WLS_SGM)
+    params, conf = _wls_split(wls)
+    SMDE.setWLS(**params)
+    if conf is None:
+        SMDE.WLS_GPU(capi.PSM_WLS_SGM)
+    else:
+        SMDE.WLS_GPU(capi.PSM_WLS_SGM, confidence=conf)
     SMDE.wls_publish(True)
     w16 = out["wls16"] = SMDE.wls_map()
     if gt is not None:
@@ -257,9 +269,10 @@ def _reproject(SMDE, out, depth, source):
 
 def _wls_batch(des, outs, wls, maxDis, gts, masks, scale_factor, error_threshold):
     """compute_sgbm_batch's wls= option: _wls for every object, the smoothing of all maps in shared launches."""
+    params, conf = _wls_split(wls)
     for d in des:
-        d.setWLS(**wls)
-    maps = wls_batch(des, capi.PSM_WLS_SGM)
+        d.setWLS(**params)
+    maps = wls_batch(des, capi.PSM_WLS_SGM) if conf is None else wls_batch(des, capi.PSM_WLS_SGM, confidence=conf)
     for i, (d, out, w16) in enumerate(zip(des, outs, maps)):
         d.wls_publish(True)
         out["wls16"] = w16

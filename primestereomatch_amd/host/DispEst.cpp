@@ -273,10 +273,26 @@ int DispEst::setWLS(float lambda, float sigma, int iterations)
     return hipUtil::api().wls_set_params(ctx[0], lambda, sigma, iterations);
 }
 
-int DispEst::WLS_GPU(int source, bool useMask, std::vector<int16_t> *disp16, Mat *q)
+int DispEst::setWLSConfidence(int terms, int lrThresh, int radius, int varShift)
 {
     if (ctx.empty()) return 1;
-    if (hipUtil::api().wls_filter(ctx[0], source, useMask ? PSM_WLS_USE_MASK : 0)) return 1;      // (several devices: ctx[0] holds the gathered maps)
+    return hipUtil::api().wls_set_confidence(ctx[0], terms, lrThresh, radius, varShift);
+}
+
+int DispEst::wlsConfidence(std::vector<uint8_t> *conf, std::vector<int16_t> *right16)
+{
+    if (ctx.empty()) return 1;
+    if (conf) conf->resize((size_t)hei * wid);
+    if (right16) right16->resize((size_t)hei * wid);
+    return hipUtil::api().wls_download_confidence(ctx[0], conf ? conf->data() : nullptr, 0, right16 ? right16->data() : nullptr, 0);
+}
+
+int DispEst::wlsConfTime(double *ms) { return ctx.empty() ? 1 : hipUtil::api().wls_conf_time(ctx[0], ms); }
+
+int DispEst::WLS_GPU(int source, bool useMask, std::vector<int16_t> *disp16, Mat *q, bool confidence)
+{
+    if (ctx.empty()) return 1;
+    if (hipUtil::api().wls_filter(ctx[0], source, (useMask ? PSM_WLS_USE_MASK : 0) | (confidence ? PSM_WLS_CONFIDENCE : 0))) return 1;      // (several devices: ctx[0] holds the gathered maps)
     if (disp16) {
         disp16->resize((size_t)hei * wid);
         if (hipUtil::api().wls_download(ctx[0], disp16->data(), nullptr, nullptr, nullptr, 0)) return 1;

@@ -179,7 +179,15 @@ public:
     // WLSPublish(true): Score and Reproject with an SGM source read the filtered map from now on - the way to a dense cloud that
     // keeps the sixteenths.  wlsTime: device ms of the launches under PSM_OPT_PROFILE.
     int setWLS(float lambda = 8000.f, float sigma = 1.5f, int iterations = 3);
-    int WLS_GPU(int source, bool useMask = false, std::vector<int16_t> *disp16 = nullptr, Mat *q = nullptr);
+    int WLS_GPU(int source, bool useMask = false, std::vector<int16_t> *disp16 = nullptr, Mat *q = nullptr, bool confidence = false);
+    // The graded confidence (PSM_WLS_CONFIDENCE, PSM_WLS_SGM only; the definition is tests/wls_conf_model.py): with `confidence` WLS_GPU
+    // - and WLSBatch with the flag - starts the solve with a confidence byte per pixel from the L-R consistency of the SGM stage's
+    // summed costs and the variance of the map around the pixel.  setWLSConfidence: terms PSM_WLS_CONF_LR | PSM_WLS_CONF_VAR,
+    // lr_thresh in 1..32767 (16ths), radius in 1..4, var_shift in 0..16 (a new object: both, 24, 2, 8).  wlsConfidence: the planes
+    // of the last such run (either may be null; right16 needs the L-R term).  wlsConfTime: device ms of the two launches it adds.
+    int setWLSConfidence(int terms = PSM_WLS_CONF_LR | PSM_WLS_CONF_VAR, int lrThresh = 24, int radius = 2, int varShift = 8);
+    int wlsConfidence(std::vector<uint8_t> *conf, std::vector<int16_t> *right16);
+    int wlsConfTime(double *ms);
     int WLSWait();
     int WLSPublish(bool on);
     int wlsTime(double *ms);

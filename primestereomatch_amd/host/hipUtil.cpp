@@ -71,6 +71,8 @@ bool hipUtil::load(const char *path)
               bind(g_api.reproject_download, "psm_reproject_download") && bind(g_api.reproject_download_cloud, "psm_reproject_download_cloud") &&
               bind(g_api.wls_set_params, "psm_wls_set_params") && bind(g_api.wls_filter, "psm_wls_filter") && bind(g_api.wls_wait, "psm_wls_wait") &&
               bind(g_api.wls_download, "psm_wls_download") && bind(g_api.wls_time, "psm_wls_time") && bind(g_api.wls_publish, "psm_wls_publish") &&
+              bind(g_api.wls_set_confidence, "psm_wls_set_confidence") && bind(g_api.wls_download_confidence, "psm_wls_download_confidence") &&
+              bind(g_api.wls_conf_time, "psm_wls_conf_time") &&
               bind(g_api.wls_filter_batch, "psm_wls_filter_batch") && bind(g_api.gray_compute, "psm_gray_compute") &&
               bind(g_api.gray_compute_batch, "psm_gray_compute_batch") && bind(g_api.gray_time, "psm_gray_time");
     if (!ok) {

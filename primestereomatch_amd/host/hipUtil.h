@@ -85,6 +85,9 @@ struct HipApi {
     int (*wls_download)(psm_ctx *, int16_t *, float *, float *, float *, size_t) = nullptr;
     int (*wls_time)(psm_ctx *, double *) = nullptr;
     int (*wls_publish)(psm_ctx *, int) = nullptr;
+    int (*wls_set_confidence)(psm_ctx *, int, int, int, int) = nullptr;
+    int (*wls_download_confidence)(psm_ctx *, uint8_t *, size_t, int16_t *, size_t) = nullptr;
+    int (*wls_conf_time)(psm_ctx *, double *) = nullptr;
     // the guided-filter path over a one-channel pair
     int (*gray_compute)(psm_ctx *, const void *, const void *, size_t, int, uint8_t *, uint8_t *, size_t) = nullptr;
     int (*gray_compute_batch)(psm_ctx *const *, int, const void *const *, const void *const *, size_t, int, uint8_t *const *, uint8_t *const *,

@@ -34,6 +34,8 @@
 // (DispEst::WLS_GPU: lambda 8000, sigma 1.5, 3 iterations) - the holes filled, the sixteenths kept; its device time is printed, the
 // filtered map dumped as <out>_sgbm_wls16.raw and, with gt.raw, scored as integer disparities beside the unfiltered map's figure;
 // with --ply a second cloud, that of the filtered map, goes to FILE with ".wls.ply" appended
+// --wls-conf: --wls with the graded confidence (PSM_WLS_CONFIDENCE: both terms, lr_thresh 24, radius 2, var_shift 8) at the start of the
+// solve; the device time of the two launches it adds is printed too
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -79,12 +81,13 @@ int main(int argc, char **argv)
 {
     // the two named options are taken off the line first; the positional arguments keep their places
     const char *ply_path = nullptr, *q_text = nullptr;
-    bool wls = false;
+    bool wls = false, wls_conf = false;
     std::vector<char *> args;
     for (int i = 0; i < argc; ++i) {
         if (!strcmp(argv[i], "--ply") && i + 1 < argc) ply_path = argv[++i];
         else if (!strcmp(argv[i], "--q") && i + 1 < argc) q_text = argv[++i];
         else if (!strcmp(argv[i], "--wls")) wls = true;
+        else if (!strcmp(argv[i], "--wls-conf")) wls = wls_conf = true;
         else args.push_back(argv[i]);
     }
     argc = (int)args.size();
@@ -256,8 +259,15 @@ int main(int argc, char **argv)
             double wms = 0;
             struct psm_score before, after;
             if (gt_path && SMDE.Score(PSM_SCORE_SGM_INT, &before, nullptr, nullptr)) return 5;
-            if (SMDE.setWLS() || SMDE.WLS_GPU(PSM_WLS_SGM, false, &w16) || SMDE.wlsTime(&wms) || SMDE.WLSPublish(true)) return 5;
+            if (SMDE.setWLS() || SMDE.setWLSConfidence() || SMDE.WLS_GPU(PSM_WLS_SGM, false, &w16, nullptr, wls_conf) || SMDE.wlsTime(&wms) ||
+                SMDE.WLSPublish(true))
+                return 5;
             printf("WLS Time:\t %4.3f ms\n", wms);
+            if (wls_conf) {
+                double cms = 0;
+                if (SMDE.wlsConfTime(&cms)) return 5;
+                printf("... of which the graded confidence:\t %4.3f ms\n", cms);
+            }
             ok = dump(out + "_sgbm_wls16.raw", (const unsigned char *)w16.data(), w16.size() * sizeof(int16_t));
             if (ok && gt_path) {
                 if (SMDE.Score(PSM_SCORE_SGM_INT, &after, nullptr, nullptr)) return 5;

@@ -24,8 +24,22 @@ JSON line per size and iteration count, and the same lines into profiles/wls_ben
   ns_per_step           batch_ms (of the whole batch) over T * 2 * (W + H): what one step of the chain costs when n chains run
                         side by side - constant over n while the chain binds, growing once the device is full
 
+--conf: PSM_WLS_CONFIDENCE - the two launches the graded confidence adds (k_sgm_right16, k_wls_conf), on the SGM stage's own result
+of a synthetic pair (synth.make_pair) at 450 x 375 x 64, 1280 x 720 x 128 and 1920 x 1080 x 256; the lines are appended to
+profiles/wls_bench.txt as a new block.  All device ms between events (PSM_OPT_PROFILE), best of --reps.
+
+  conf_ms_both, conf_ms_lr, conf_ms_var   psm_wls_conf_time with both terms (k_sgm_right16 + k_wls_conf), with the L-R term alone
+                        (k_sgm_right16 + k_wls_conf without its window), with the variance term alone (k_wls_conf alone, without
+                        its gather of right16)
+  sgm_maps_ms           k_sgm_maps of the same S in the same session (psm_sgm_maps_time): it reads S once and scatters the same
+                        keys, so it is the yardstick of k_sgm_right16; right16_over_maps = (conf_ms_both - conf_ms_var) / sgm_maps_ms
+                        bounds the ratio from above (the difference also holds k_wls_conf's gather of right16)
+  s_floor_ms            S read once at the 6.29 TB/s copy ceiling of profiles/sgm_bench.txt
+  flagged_ms, unflagged_ms   psm_wls_time of the whole call with and without the flag (T = 3)
+  equals_model          450 x 375 only: disp, conf and right16 equal tests/wls_conf_model.py
+
 The maps are random with 30 % missing, the guide is a smooth image with edges.  Usage: python scripts/wls_bench.py [--reps N]
-[--host-reps N] [--only WxH] [--batch]"""
+[--host-reps N] [--only WxH] [--batch | --conf]"""
 import argparse
 import json
 import os
@@ -106,12 +120,56 @@ def batch_bench(a, emit):
                 de.close()
 
 
+def conf_bench(a, emit):
+    import wls_conf_model as CM
+    import primestereomatch_amd as P
+    from primestereomatch_amd import capi, synth
+    emit({"what": "wls_bench --conf", "reps": a.reps, "lambda": 8000.0, "sigma": 1.5, "iterations": 3, **CM.DEFAULTS})
+    for W, H, D in SIZES:
+        if a.only and a.only != f"{W}x{H}":
+            continue
+        l, r, _ = synth.make_pair(W, H, D, seed=0)
+        with P.DispEst(l, r, D) as de:
+            de.set_option(capi.PSM_OPT_PROFILE, 1)
+            m16 = de.SGBM_GPU()
+            de.setWLS()
+
+            def best(conf, what):
+                t = []
+                for _ in range(a.reps + 1):                             # (the first run allocates)
+                    de.WLS_GPU(capi.PSM_WLS_SGM, confidence=conf)
+                    t.append(what())
+                return min(t[1:])
+
+            both = best({}, de.wls_conf_time)
+            flagged = best({}, de.wls_time)
+            same = None
+            if (W, H) == (450, 375):
+                import depth_model as DM
+                got = {"disp": de.wls_map()}
+                got["conf"], got["right16"] = de.download_wls_confidence()
+                model = CM.wls(m16, -16, DM.quantise(l), S=de.sgm_costs()[1], dmin=0)
+                same = all(bool(np.array_equal(got[k], model[k])) for k in got)
+            lr = best({"terms": capi.PSM_WLS_CONF_LR}, de.wls_conf_time)
+            var = best({"terms": capi.PSM_WLS_CONF_VAR}, de.wls_conf_time)
+            unflagged = best(None, de.wls_time)
+            maps = []
+            for _ in range(a.reps):
+                de.SGBMSelect_GPU(download=False)
+                maps.append(de.sgm_maps_time())
+            floor = W * H * D * 4 / 6.29e12 * 1e3
+            emit({"size": f"{W}x{H}x{D}", "conf_ms_both": round(both, 4), "conf_ms_lr": round(lr, 4), "conf_ms_var": round(var, 4),
+                  "sgm_maps_ms": round(min(maps), 4), "right16_over_maps": round((both - var) / min(maps), 2), "s_floor_ms": round(floor, 4),
+                  "flagged_ms": round(flagged, 4), "unflagged_ms": round(unflagged, 4), "void_in": int((m16 == -16).sum()), "equals_model": same})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--host-reps", type=int, default=2)
     ap.add_argument("--only", default="")
     ap.add_argument("--batch", action="store_true")
+    ap.add_argument("--conf", action="store_true")
     a = ap.parse_args()
     import wls_model as M
     import primestereomatch_amd as P
@@ -123,8 +181,8 @@ def main():
         print(line, flush=True)
         lines.append(line)
 
-    if a.batch:
-        batch_bench(a, emit)
+    if a.batch or a.conf:
+        (conf_bench if a.conf else batch_bench)(a, emit)
         with open(os.path.join(ROOT, "profiles", "wls_bench.txt"), "a") as f:
             f.write("\n".join(lines) + "\n")
         return
