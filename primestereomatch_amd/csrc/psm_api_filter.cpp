@@ -186,6 +186,16 @@ int enqueue_select(psm_ctx *c, const Recs<PcPair> &q, const SelPlan &sp)
 
 namespace {
 
+// The context's pair as a one-volume launch of the fused filter and its reduction see it: `side` first - its guidance and byte
+// planes in [0], the other image's in [1] -, its chunk planes at the start of the scratch, its own key plane.
+PcPair pc_pair_side(const psm_ctx *c, int side)
+{
+    PcPair p = pc_pair(c);
+    if (side) { std::swap(p.g[0], p.g[1]); std::swap(p.p4[0], p.p4[1]); }
+    if (p.keys) p.keys += side * (size_t)c->W * c->H;
+    return p;
+}
+
 // the recipe carried out: the unfiltered costs of `side` written to vol[side]
 int build_costs(psm_ctx *c, int side)
 {
@@ -222,9 +232,10 @@ int filter_stored(psm_ctx *c, int side)
     if (!lazy && ensure_spare(c)) return 1;
     const float *in = lazy ? nullptr : u8 ? c->fvol : (const float *)c->vol[side];
     float *out = lazy ? (float *)c->vol[side] : c->spare;
+    const PcPair one = pc_pair_side(c, side);
     {
         Prof p(c, PSM_K_CVF_F);
-        launch_cvf_fused(c->stream, c->march, in, out, c->g[side], c->W, c->H, c->Dloc, 0, c->H, c->g[1 - side].g1, c->d0, lazy ? 1 + side : 0,
+        launch_cvf_fused(c->stream, c->march, Recs<PcPair>{&one, nullptr, 1}, in, out, c->W, c->H, c->Dloc, 0, c->H, c->d0, lazy ? 1 + side : 0,
                          next_pc_stamp(c));
     }
     if (u8) launch_f32_to_u8(c->stream, out, (uint8_t *)c->vol[side], (size_t)c->W * c->H * c->Dloc);   // q8 = sat_u8(rintf(q * 255))
@@ -263,17 +274,16 @@ int filter_side_select(psm_ctx *c, int side)
     const bool lazy = costs_lazy(c->vside[side]), sel8 = c->dtype == PSM_U8;
     const PcPlan pl = pc_plan(W, c->march.rows(H), c->Dloc, c->march.seg_rows, PC_PLANES);
     if (ensure_gf_scratch(c, pl.scratch_bytes())) return 1;
+    const PcPair one = pc_pair_side(c, side);      // (after the scratch exists: the record carries it)
+    const Recs<PcPair> q = {&one, nullptr, 1};
     {
         Prof p(c, PSM_K_CVF_F);
-        launch_cvf_select(c->stream, c->march, lazy ? nullptr : (const float *)c->vol[side], c->g[side], W, H, c->Dloc, c->g[1 - side].g1,
-                          c->d0, lazy ? 1 + side : 0, c->gf_scratch, next_pc_stamp(c), sel8 ? c->p4[side] : nullptr, sel8 ? c->p4[1 - side] : nullptr);
+        launch_cvf_select(c->stream, c->march, q, lazy ? nullptr : (const float *)c->vol[side], sel8, W, H, c->Dloc, c->d0, lazy ? 1 + side : 0,
+                          next_pc_stamp(c));
     }
     {
         Prof p(c, PSM_K_WTA);
-        PcPair one = {};                 // the one volume's planes and keys
-        one.scratch = c->gf_scratch;
-        one.keys = c->keys_cur + side * (size_t)W * H;
-        launch_chunk_min(c->stream, c->march, Recs<PcPair>{&one, nullptr, 1}, W, H, c->Dloc);
+        launch_chunk_min(c->stream, c->march, q, W, H, c->Dloc);
     }
     filtered_to_keys(c->vside[side]);
     return check_launch(c, "cvf (fused, select mode)");

@@ -43,7 +43,7 @@ struct PcPair {                  // one pair's buffers: what a single call passe
     void *scratch;               // chunk planes of the select kernel (both sides)
     long long *keys;             // [2][H][W] packed minima
     uint8_t *maps;               // [2][H][W]
-};
+};                               // (a one-volume launch of the fused filter and its reduction: that volume's side in [0], its keys [H][W])
 // ---- record sources: what every stage with a batch entry (the default path - prep, guidance, fused select filter, reduction -,
 // post-processing tail, JointWMF, SGM and speckle, score, depth, WLS) shares ----
 // The n records R of one launch as the host filled them, the record on a grid axis.  dev == nullptr: the records of a single call
@@ -118,8 +118,10 @@ void launch_cvf_a(hipStream_t s, int variant, March m, const float *vol, float4 
 void launch_cvf_b_direct(hipStream_t s, const float4 *ab, float *vol, Guidance g, int W, int H, int Dloc);
 // fused stage A+B: vin -> vout (distinct buffers), output rows [ybeg, yend) within [4, H-3)
 // cvc_mode 0: read the cost slices from vin; 1/2: build the left/right costs on the fly from the g1 planes
-void launch_cvf_fused(hipStream_t s, March m, const float *vin, float *vout, Guidance g, int W, int H, int Dloc,
-                      int ybeg, int yend, const float4 *g1_other, int d_begin, int cvc_mode, unsigned long long *ts = nullptr);
+// One volume per launch: q is one record (by value, q.dev == nullptr) that carries the volume's own side FIRST - g[0] its
+// guidance, g[1].g1 the other image; likewise launch_cvf_select below.
+void launch_cvf_fused(hipStream_t s, March m, const Recs<PcPair> &q, const float *vin, float *vout, int W, int H, int Dloc,
+                      int ybeg, int yend, int d_begin, int cvc_mode, unsigned long long *ts = nullptr);
 // The same kernel with the winner-takes-all fused in ("select" forms): the filtered volume is never written.
 //   plane form: per pixel the running minimum over chunks of DC slices in scratch planes -> launch_chunk_min* -> packed WTA keys
 //   key form:   64-bit atomicMin on a key plane that already holds good bounds (second phase of the two-phase selection)
@@ -141,11 +143,11 @@ int pc_seed_stride(int W, int rows, bool u8);                     // S of the tw
 // ts (may be NULL): slot of this launch in a buffer of 3 x PC_TS_SLOTS 64-bit words {first workgroup start | last workgroup
 // end | form} in ticks of the device's constant-rate clock (PSM_OPT_PROFILE 2, psm_filter_launch_times)
 constexpr int PC_TS_SLOTS = 4096;
-// one volume per launch (costs read from vin, cvc_mode 0, or built on the fly, 1 / 2; p4_*: 8-bit char mode)
-void launch_cvf_select(hipStream_t s, March m, const float *vin, Guidance g, int W, int H, int Dloc, const float4 *g1_other,
-                       int d_begin, int cvc_mode, void *scratch, unsigned long long *ts = nullptr, const uint8_t *p4_own = nullptr,
-                       const uint8_t *p4_other = nullptr);
-// ... its reduction: the chunk planes in q's scratch -> q's keys (one volume's: [H][W])
+// one volume per launch (costs read from vin, cvc_mode 0, or built on the fly, 1 / 2; u8: 8-bit char mode): the first side of q's
+// one record - its byte planes p4[0] against p4[1], its chunk planes at the start of the record's scratch
+void launch_cvf_select(hipStream_t s, March m, const Recs<PcPair> &q, const float *vin, bool u8, int W, int H, int Dloc, int d_begin,
+                       int cvc_mode, unsigned long long *ts = nullptr);
+// ... its reduction, over the same record: the chunk planes in q's scratch -> q's keys (one volume's: [H][W])
 void launch_chunk_min(hipStream_t s, March m, const Recs<PcPair> &q, int W, int H, int Dloc);
 // both volumes of every pair in q per launch (costs on the fly; u8: 8-bit char mode): the left volume is filtered with the guidance
 // g[0] of the left image, the right one with g[1]; keys / maps: [2][H][W] per pair; grid z = pair (a single pair: 1).  Dloc slices,

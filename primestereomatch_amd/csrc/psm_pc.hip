@@ -33,6 +33,8 @@
 //   work granularity, shortest tail), no reduction kernel afterwards.
 // d = 0 is never a candidate, NaN never wins, the lowest d wins ties (src/DispSel.cpp:91-105): slices are visited in
 // ascending d with strict '<' inside a chunk, and k_chunk_min takes the signed minimum of pack_key_f32 across chunks.
+// Both kernels are templates over the record source (psm_kernels.h, Recs): a workgroup finds the planes of its pair - guidance,
+// byte planes, chunk planes, keys - in the pair's PcPair record, by value in the kernarg or in a batch's device table.
 #include "psm_kernels.h"
 #include "psm_cost.h"
 #include "psm_dev.h"
@@ -108,16 +110,6 @@ __device__ __forceinline__ float3 pc_load3(__amdgpu_buffer_rsrc_t r, int voff, i
     return make_float3(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z));
 }
 
-// Second set of plane pointers for CVC == 3: one launch filters BOTH volumes (blockIdx.y = side; side 0 = left volume with
-// the kernel's own arguments, side 1 = right volume with these) - twice the workgroups per launch, half the launches.
-struct PcSide {
-    const float4 *G1, *G2, *G3;
-    const float2 *G4;
-    const float4 *Gother;
-    float *kcost;
-    unsigned *kdisp;
-};
-
 // Which local slices a launch covers (Dloc = their number): sel 0 all (index i = local slice i); sel 1 every step-th slice
 // (i -> i * step); sel 2 the others (i -> (i / (step-1)) * step + i % (step-1) + 1).  Two-phase selection: a first launch
 // reduces every step-th slice to the key plane, a MODE 2 launch then runs the rest against that plane - its consumer lanes
@@ -149,7 +141,7 @@ struct PcSel {
     int sel, step;
     int nxcd;      // XCDs of the device (blocks are dispatched round-robin over them)
     int spread;    // key form: dispatch a group's live slices in `spread` interleaved passes (0 / 1: ascending; pc_spread)
-    unsigned long long rec_total;   // BATCH launches: float4 cost records per side in a pair's scratch (the disparities follow them)
+    unsigned long long rec_total;   // plane form: float4 cost records per side in a pair's scratch (the disparities follow them)
     int dstep;     // global disparity of local slice i: d_begin + i * dstep (1: a contiguous range; psm_create_shard_strided: the rank count)
     PcLive live;
 };
@@ -172,55 +164,48 @@ __device__ __forceinline__ int pc_spread(const PcSel &o, int n, int i)      // d
     return i;
 }
 
+// S - the record source (psm_kernels.h, Recs): blockIdx.z = stereo pair, and every plane pointer of the pair comes from its
+// PcPair record rec(src, blockIdx.z) - the single pair's by value in the kernarg (PcVal), a batch's from the device table (PcTab,
+// psm_compute_batch: B Middlebury-size pairs fill the chip for many rounds of workgroups instead of 1.7).  Uniform either way:
+// scalar loads ahead of the first barrier.  CVC = 3: one launch filters BOTH volumes, blockIdx.y = side - the left volume with
+// the guidance g[0] against g[1].g1, the right one with g[1] against g[0].g1, minima in the side's half of the scratch / of the
+// keys.  CVC 0 - 2: one volume, and the record carries that volume's side FIRST (g[0] its guidance, g[1].g1 the other image,
+// p4 likewise, its chunk planes at the start of the scratch): the launchers' callers build it so.
+// `vin` / `vout` stay arguments: the cost volume of CVC = 0 and the filtered volume of MODE 0.
 // CVC = 0: the cost slice is read from `vin`.  CVC = 1 (left volume) / 2 (right volume): the cost volume is never
 // materialised - the producer waves evaluate myCostGrd (src/CVC.cpp:18-39) for their input column on the fly from the
 // two g1 planes (`G1` = this side's image, `Gother` = the other one), exactly as k_cvc does.
 // U8 (8-bit char mode, select mode with costs on the fly only): the producer waves build the 8-bit matching cost of
-// assets/cvc.cl:279-301 (oracle: cost_u8) from the {c0,c1,c2,grad} byte planes handed over in `vin` (this side) and `vout`
-// (other side) and filter cost * (1/255.0f); the consumer waves re-quantise q8 = sat_u8(rintf(q * 255)) before the
+// assets/cvc.cl:279-301 (oracle: cost_u8) from the {c0,c1,c2,grad} byte planes p4[0] and p4[1] of the record (carried on in
+// `vin` and `vout`) and filter cost * (1/255.0f); the consumer waves re-quantise q8 = sat_u8(rintf(q * 255)) before the
 // strict-'<' selection (assets/dispsel.cl:41-62 with the initial minimum above 255) - the build-defined 8-bit contract
 // of oracle/psm_oracle.h, in one pass and without an 8-bit volume in memory.
-// BATCH (psm_compute_batch): blockIdx.z = stereo pair; every plane pointer of the pair comes from the device table `batch`
-// (uniform: scalar loads), so B Middlebury-size pairs fill the chip for many rounds of workgroups instead of 1.7.
 // VAR - the two opt-in arithmetic variants of float mode (0: the canon, bit-exact against the oracle):
 //   1 (PSM_FLAG_F32_TOL): level 1 of the horizontal trees of both roles in fp32 (psm_dev.h: hsum8<true>) - within the 1e-4
 //     BASELINE.json states for float mode, not the oracle's bits;
 //   2 (PSM_FLAG_FMA_SOLVE): the 3x3 solve as an FMA target compiles it (psm_dev.h: solve_ab<true>; minors / DET from
 //     k_guide_march in their fused forms) - the oracle's reading PSMO_VAR_FMA_SOLVE, bit for bit.
-template <bool VEC4, int CVC, int MODE, bool U8 = false, bool BATCH = false, int VAR = 0, bool NARROW = false>
+template <bool VEC4, int CVC, int MODE, typename S, bool U8 = false, int VAR = 0, bool NARROW = false>
 __global__ __launch_bounds__(64 * (PcLayout<MODE, NARROW>::NA + PcLayout<MODE, NARROW>::NB))
 __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 4 : 1, MODE == 2 ? 4 : 8)))   // the key form capped at 128 VGPRs = four workgroups per CU
-void k_cvf_pc(
-    const float *__restrict__ vin, float *__restrict__ vout, const float4 *__restrict__ G1a, const float4 *__restrict__ G2a,
-    const float4 *__restrict__ G3a, const float2 *__restrict__ G4a, int W, int H, int Dloc, int ngroups, int nsegs, int seg_rows,
-    int ybeg, int yend, const float4 *__restrict__ Gothera, int d_begin, int DC, float *__restrict__ kcosta, unsigned *__restrict__ kdispa, int nbmax,
-    PcSide side1, PcSel dyn, unsigned long long *__restrict__ ts, const PcPair *__restrict__ batch)
+void k_cvf_pc(S src, const float *__restrict__ vin, float *__restrict__ vout, int W, int H, int Dloc, int ngroups, int nsegs, int seg_rows,
+              int ybeg, int yend, int d_begin, int DC, int nbmax, PcSel dyn, unsigned long long *__restrict__ ts)
 {
-    constexpr bool TOL = VAR == 1, FMA = VAR == 2;
-    static_assert(VAR >= 0 && VAR <= 2 && !(TOL && (U8 || MODE == 0)) && !(FMA && (U8 || BATCH)), "tolerance form: float select forms; FMA solve: float mode, single pair");
-    if constexpr (BATCH) {
-        static_assert(CVC == 3 && MODE != 0, "batched launches: both volumes per launch, select forms");
-        const PcPair pp = batch[blockIdx.z];
-        G1a = pp.g[0].g1; G2a = pp.g[0].g2; G3a = pp.g[0].g3; G4a = pp.g[0].g4; Gothera = pp.g[1].g1;
-        side1.G1 = pp.g[1].g1; side1.G2 = pp.g[1].g2; side1.G3 = pp.g[1].g3; side1.G4 = pp.g[1].g4; side1.Gother = pp.g[0].g1;
-        if (U8) { vin = (const float *)pp.p4[0]; vout = (float *)pp.p4[1]; }
-        if (MODE == 1) {     // minima planes: [side][costs | disparities] in the pair's scratch
-            kcosta = (float *)pp.scratch;
-            kdispa = (unsigned *)(kcosta + 4 * dyn.rec_total);
-            side1.kcost = (float *)((char *)pp.scratch + dyn.rec_total * 20);
-            side1.kdisp = (unsigned *)(side1.kcost + 4 * dyn.rec_total);
-        } else {             // key planes
-            kcosta = (float *)pp.keys;
-            side1.kcost = (float *)(pp.keys + (size_t)W * H);
-        }
-    }
+    constexpr bool TOL = VAR == 1, FMA = VAR == 2, TABLE = std::is_pointer<S>::value;
+    static_assert(VAR >= 0 && VAR <= 2 && !(TOL && (U8 || MODE == 0)) && !(FMA && (U8 || TABLE)), "tolerance form: float select forms; FMA solve: float mode, single pair");
+    static_assert(!TABLE || (CVC == 3 && MODE != 0), "batched launches: both volumes per launch, select forms");
     const bool right = CVC == 2 || (CVC == 3 && blockIdx.y == 1);      // buildCV_right arithmetic (uniform)
-    const bool s1 = CVC == 3 && blockIdx.y == 1;
-    const float4 *const G1 = s1 ? side1.G1 : G1a, *const G2 = s1 ? side1.G2 : G2a, *const G3 = s1 ? side1.G3 : G3a;
-    const float2 *const G4 = s1 ? side1.G4 : G4a;
-    const float4 *const Gother = s1 ? side1.Gother : Gothera;
-    float *const kcost = s1 ? side1.kcost : kcosta;
-    unsigned *const kdisp = s1 ? side1.kdisp : kdispa;
+    const bool s1 = CVC == 3 && blockIdx.y == 1;                        // (a one-volume launch: its side comes first in the record)
+    const PcPair &pp = rec(src, blockIdx.z);
+    const float4 *const G1 = s1 ? pp.g[1].g1 : pp.g[0].g1, *const G2 = s1 ? pp.g[1].g2 : pp.g[0].g2, *const G3 = s1 ? pp.g[1].g3 : pp.g[0].g3;
+    const float2 *const G4 = s1 ? pp.g[1].g4 : pp.g[0].g4;
+    const float4 *const Gother = s1 ? pp.g[0].g1 : pp.g[1].g1;
+    if (U8) { vin = (const float *)pp.p4[0]; vout = (float *)pp.p4[1]; }
+    // the side's minima: chunk planes [side][costs | disparities] in the pair's scratch (MODE 1), or its key plane (MODE 2, handed on
+    // as `kcost`).  (The side's offset is selected, not multiplied by blockIdx.y: see k_chunk_min.)
+    float *const kcost = MODE == 1 ? (float *)((char *)pp.scratch + (s1 ? dyn.rec_total * 20 : 0))
+                       : MODE == 2 ? (float *)(pp.keys + (s1 ? (size_t)W * H : 0)) : nullptr;
+    unsigned *const kdisp = MODE == 1 ? (unsigned *)(kcost + 4 * dyn.rec_total) : nullptr;
     static_assert(!NARROW || (MODE != 0 && CVC == 3), "the narrow layout exists for the two-volume select forms");
     using L = PcLayout<MODE, NARROW>;
     constexpr int PC_NA = L::NA, PC_NB = L::NB, PC_OUT_A = L::OUT_A, PC_OUT_B = L::OUT_B, PC_COLS = L::COLS;
@@ -492,7 +477,7 @@ void k_cvf_pc(
     }
         float4 kq = make_float4(__builtin_inff(), __builtin_inff(), __builtin_inff(), __builtin_inff());   // running minima of the current batch
         unsigned kd4 = 0;                                                                                  // and their disparities
-        // MODE 2: the volume's key plane (handed over in the kcost argument), current keys of this lane's pixel one batch ahead
+        // MODE 2: the volume's key plane (carried in `kcost`), current keys of this lane's pixel one batch ahead
         long long *const keyp = reinterpret_cast<long long *>(kcost);
         const __amdgpu_buffer_rsrc_t rKy = pc_rsrc(MODE == 2 ? (const void *)keyp : (const void *)G1, (unsigned)HW * 8u);
         long long kcur[4] = {0, 0, 0, 0};
@@ -893,21 +878,20 @@ static int pc_blocks(const PcPlan &pl, const PcLive &lv)
 
 // The arguments of one k_cvf_pc launch, gathered by its launcher (pc_launch passes them on).
 struct PcArgs {
-    const float *vin;                // CVC 0: the cost volume; 8-bit mode: byte planes of the left image (read by the right volume)
-    float *vout;                     // MODE 0: the filtered volume; 8-bit mode: byte planes of the right image (read by the left volume)
+    Recs<PcPair> q;                  // the pairs (grid z): every plane pointer of a launch comes from their records
+    const float *vin;                // CVC 0: the cost volume
+    float *vout;                     // MODE 0: the filtered volume
     int W, H, Dloc, ybeg, yend, d_begin;
-    PcSide side[2];                  // side[0]: the launch's (left) volume; side[1]: the right one of a two-volume launch
     PcSel sel;
     unsigned long long *ts;
-    const PcPair *batch;             // BATCH: the pairs' table (the sides' planes come from it)
 };
 
-// Which k_cvf_pc runs a launch: its template arguments as runtime values.
+// Which k_cvf_pc runs a launch: its template arguments as runtime values (the record source: PcArgs::q).
 struct PcForm {
     int mode, cvc;
     bool u8;
     int var;
-    bool batch, narrow, vec4;
+    bool narrow, vec4;
 };
 
 template <int V> using pc_int = std::integral_constant<int, V>;
@@ -919,42 +903,36 @@ template <class Fn> static void pc_pick_bool(bool b, Fn &&fn) { if (b) fn(std::t
 //   storing form:            VEC4 x CVC 0-2 x {canon, FMA solve}
 //   one-volume plane form:   CVC 0-2 x {canon, FMA solve}, CVC 1-2 x 8-bit
 //   two-volume select forms: planes / keys x wide / narrow x {8-bit, canon, tolerance, FMA solve}; batched: {8-bit, canon}
+// all over the single pair's record by value (PcVal) but the batched ones, which read the device table a.q.dev (PcTab).  (Not
+// rec_launch: that instantiates a kernel over both sources, and most of these forms exist over one.)
 static void pc_launch(hipStream_t s, const PcPlan &pl, dim3 grid, const PcArgs &a, const PcForm &f)
 {
     using F = std::false_type;
     using T = std::true_type;
     const bool planes = f.mode == PC_PLANES;     // (DC and nbmax mean something to the plane form only)
-    const PcSide &s0 = a.side[0];
     if (grid.x == 0) return;                     // (no live item: a launch of d = 0 alone)
-    auto go = [&](auto V4, auto CV, auto MD, auto U, auto BT, auto VR, auto NW) {
+    const PcVal val = {{a.q.host[0]}};
+    const PcTab tab = a.q.dev;
+    auto go = [&](auto V4, auto CV, auto MD, auto src, auto U, auto VR, auto NW) {
         using L = PcLayout<MD, NW>;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cvf_pc<V4, CV, MD, U, BT, VR, NW>), grid, dim3(64 * (L::NA + L::NB)), 0, s, a.vin, a.vout,
-                           s0.G1, s0.G2, s0.G3, s0.G4, a.W, a.H, a.Dloc, pl.ngroups, pl.nsegs, pl.seg_rows, a.ybeg, a.yend, s0.Gother,
-                           a.d_begin, planes ? pl.DC : 1, s0.kcost, s0.kdisp, planes ? pl.nbmax : 0, a.side[1], a.sel, a.ts, a.batch);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cvf_pc<V4, CV, MD, decltype(src), U, VR, NW>), grid, dim3(64 * (L::NA + L::NB)), 0, s, src, a.vin,
+                           a.vout, a.W, a.H, a.Dloc, pl.ngroups, pl.nsegs, pl.seg_rows, a.ybeg, a.yend, a.d_begin, planes ? pl.DC : 1,
+                           planes ? pl.nbmax : 0, a.sel, a.ts);
     };
     if (f.mode == PC_STORE)
         pc_pick_bool(f.vec4, [&](auto V4) { pc_pick<0, 1, 2>(f.cvc, [&](auto CV) {
-            pc_pick<0, 2>(f.var, [&](auto VR) { go(V4, CV, pc_int<0>{}, F{}, F{}, VR, F{}); }); }); });
+            pc_pick<0, 2>(f.var, [&](auto VR) { go(V4, CV, pc_int<0>{}, val, F{}, VR, F{}); }); }); });
     else if (f.cvc != 3)
         pc_pick<0, 1, 2>(f.cvc, [&](auto CV) {
-            if constexpr (CV != 0) if (f.u8) return go(F{}, CV, pc_int<1>{}, T{}, F{}, pc_int<0>{}, F{});
-            pc_pick<0, 2>(f.var, [&](auto VR) { go(F{}, CV, pc_int<1>{}, F{}, F{}, VR, F{}); });
+            if constexpr (CV != 0) if (f.u8) return go(F{}, CV, pc_int<1>{}, val, T{}, pc_int<0>{}, F{});
+            pc_pick<0, 2>(f.var, [&](auto VR) { go(F{}, CV, pc_int<1>{}, val, F{}, VR, F{}); });
         });
     else
         pc_pick<1, 2>(f.mode, [&](auto MD) { pc_pick_bool(f.narrow, [&](auto NW) {
-            if (f.u8) pc_pick_bool(f.batch, [&](auto BT) { go(F{}, pc_int<3>{}, MD, T{}, BT, pc_int<0>{}, NW); });
-            else if (f.batch) go(F{}, pc_int<3>{}, MD, F{}, T{}, pc_int<0>{}, NW);
-            else pc_pick<0, 1, 2>(f.var, [&](auto VR) { go(F{}, pc_int<3>{}, MD, F{}, F{}, VR, NW); });
+            if (tab) pc_pick_bool(f.u8, [&](auto U) { go(F{}, pc_int<3>{}, MD, tab, U, pc_int<0>{}, NW); });
+            else if (f.u8) go(F{}, pc_int<3>{}, MD, val, T{}, pc_int<0>{}, NW);
+            else pc_pick<0, 1, 2>(f.var, [&](auto VR) { go(F{}, pc_int<3>{}, MD, val, F{}, VR, NW); });
         }); });
-}
-
-// Chunk planes of volume v in `scratch` (pl.scratch_bytes() per volume): float4 cost records, then uchar4 disparity records.
-static PcSide pc_planes(const PcPlan &pl, void *scratch, int v)
-{
-    PcSide p = {};
-    p.kcost = (float *)((char *)scratch + v * pl.scratch_bytes());
-    p.kdisp = (unsigned *)(p.kcost + 4 * pl.rec_per_chunk * pl.nchunks);
-    return p;
 }
 
 // float mode's arithmetic variant of a two-volume launch (8-bit mode: the canon)
@@ -963,7 +941,8 @@ static int pc_var(March m, bool u8)
     return u8 ? 0 : (m.flags & PSM_FLAG_FMA_SOLVE) ? 2 : (m.flags & PSM_FLAG_F32_TOL) ? 1 : 0;
 }
 
-// The one launch of k_chunk_min: `sides` volumes of every pair in q (chunk planes as pc_planes lays them out in the pair's scratch).
+// The one launch of k_chunk_min: `sides` volumes of every pair in q (a volume's chunk planes: pl.scratch_bytes() of the pair's
+// scratch - float4 cost records, then uchar4 disparity records -, the left volume's first).
 static void pc_chunk_min(hipStream_t s, March m, const PcPlan &pl, int W, int H, int sides, const Recs<PcPair> &q, const PcLive &lv, bool to_maps)
 {
     rec_launch(s, k_chunk_min<PcVal>, k_chunk_min<PcTab>, dim3((unsigned)((pl.rec_per_chunk + 255) / 256), sides, q.n),
@@ -971,34 +950,30 @@ static void pc_chunk_min(hipStream_t s, March m, const PcPlan &pl, int W, int H,
                pl.cols, lv);
 }
 
-// Storing form (MODE 0): vin (or, cvc_mode 1 / 2, the costs built on the fly) -> vout, one slice per workgroup.
-void launch_cvf_fused(hipStream_t s, March m, const float *vin, float *vout, Guidance gd, int W, int H, int Dloc,
-                      int ybeg, int yend, const float4 *g1_other, int d_begin, int cvc_mode, unsigned long long *ts)
+// Storing form (MODE 0), one volume - the first side of the record q.host[0]: vin (or, cvc_mode 1 / 2, the costs built on the fly)
+// -> vout, one slice per workgroup.
+void launch_cvf_fused(hipStream_t s, March m, const Recs<PcPair> &q, const float *vin, float *vout, int W, int H, int Dloc,
+                      int ybeg, int yend, int d_begin, int cvc_mode, unsigned long long *ts)
 {
     if (yend <= ybeg) return;
     const PcPlan pl = pc_plan(W, yend - ybeg, Dloc, m.seg_rows, PC_STORE);
     const PcLive lv = pc_live(W, pl.cols, pl.ngroups, Dloc, 1, false, PcOwn{});      // (the stored volume is complete)
-    PcArgs a = {vin, vout, W, H, Dloc, ybeg, yend, d_begin, {}, PcSel{0, 1, pl.nxcd, 0, 0, 1, lv}, ts, nullptr};
-    a.side[0] = PcSide{gd.g1, gd.g2, gd.g3, gd.g4, g1_other, nullptr, nullptr};
+    const PcArgs a = {q, vin, vout, W, H, Dloc, ybeg, yend, d_begin, PcSel{0, 1, pl.nxcd, 0, 0, 1, lv}, ts};
     const int cvc = cvc_mode == 1 || cvc_mode == 2 ? cvc_mode : 0;
-    pc_launch(s, pl, dim3(pc_blocks(pl, lv)), a, {PC_STORE, cvc, false, (m.flags & PSM_FLAG_FMA_SOLVE) ? 2 : 0, false, false, (W & 3) == 0});
+    pc_launch(s, pl, dim3(pc_blocks(pl, lv)), a, {PC_STORE, cvc, false, (m.flags & PSM_FLAG_FMA_SOLVE) ? 2 : 0, false, (W & 3) == 0});
 }
 
-// Select form with chunk planes (MODE 1), one volume: costs read from vin (cvc_mode 0) or built on the fly (1 / 2; p4_own !=
-// NULL: 8-bit char mode).  scratch: pc_plan(..., PC_PLANES).scratch_bytes().
-void launch_cvf_select(hipStream_t s, March m, const float *vin, Guidance gd, int W, int H, int Dloc, const float4 *g1_other,
-                       int d_begin, int cvc_mode, void *scratch, unsigned long long *ts, const uint8_t *p4_own, const uint8_t *p4_other)
+// Select form with chunk planes (MODE 1), one volume - the first side of the record q.host[0], whose scratch holds
+// pc_plan(..., PC_PLANES).scratch_bytes(): costs read from vin (cvc_mode 0) or built on the fly (1 / 2; u8: 8-bit char mode).
+void launch_cvf_select(hipStream_t s, March m, const Recs<PcPair> &q, const float *vin, bool u8, int W, int H, int Dloc, int d_begin,
+                       int cvc_mode, unsigned long long *ts)
 {
     const PcPlan pl = pc_plan(W, m.rows(H), Dloc, m.seg_rows, PC_PLANES);
     const int cvc = cvc_mode == 1 || cvc_mode == 2 ? cvc_mode : 0;
-    const bool u8 = p4_own && cvc != 0;
     const PcLive lv = pc_live(W, pl.cols, pl.ngroups, Dloc, pl.DC, true, PcOwn{});    // (one volume per launch: every chunk walked, as before)
-    PcArgs a = {u8 ? (const float *)p4_own : vin, u8 ? (float *)const_cast<uint8_t *>(p4_other) : nullptr, W, H, Dloc, m.y0(H), m.y1(H),
-                d_begin, {}, PcSel{0, 1, pl.nxcd, 0, 0, 1, lv}, ts, nullptr};
-    const PcSide k = pc_planes(pl, scratch, 0);
-    a.side[0] = PcSide{gd.g1, gd.g2, gd.g3, gd.g4, g1_other, k.kcost, k.kdisp};
+    const PcArgs a = {q, vin, nullptr, W, H, Dloc, m.y0(H), m.y1(H), d_begin, PcSel{0, 1, pl.nxcd, 0, pl.rec_per_chunk * pl.nchunks, 1, lv}, ts};
     // (one volume per launch: the canon and the FMA reading; no tolerance form)
-    pc_launch(s, pl, dim3(pc_blocks(pl, lv)), a, {PC_PLANES, cvc, u8, (m.flags & PSM_FLAG_FMA_SOLVE) ? 2 : 0, false, false, false});
+    pc_launch(s, pl, dim3(pc_blocks(pl, lv)), a, {PC_PLANES, cvc, u8 && cvc != 0, (m.flags & PSM_FLAG_FMA_SOLVE) ? 2 : 0, false, false});
 }
 
 void launch_chunk_min(hipStream_t s, March m, const Recs<PcPair> &q, int W, int H, int Dloc)
@@ -1017,33 +992,16 @@ PcPlan pc_plan_select(March m, int W, int H, int Dloc, int form, int npairs, boo
     return pc_plan(W, m.rows(H), Dloc, m.seg_rows, form | PC_BOTH, npairs, batch ? 1 : m.inflight);
 }
 
-// The arguments of a two-volume select launch (form PC_PLANES / PC_KEYS) for the pairs q, costs built on the fly: left volume =
-// (g[0], other g[1].g1), right = (g[1], other g[0].g1).  A single pair (q.host[0]) passes its planes here - 8-bit mode: the byte
-// planes {c0,c1,c2,grad} of the left / right image as vin / vout; the minima: chunk planes in its scratch, or its keys -, the batched
-// forms read every pointer of a pair from the table q.dev.
-static PcArgs pc_args2(March m, const PcPlan &pl, int form, const Recs<PcPair> &q, bool u8, int W, int H, int Dloc, int d_begin, PcSel sel,
-                       unsigned long long *ts)
-{
-    PcArgs a = {nullptr, nullptr, W, H, Dloc, m.y0(H), m.y1(H), d_begin, {}, sel, ts, q.dev};
-    if (q.dev) return a;
-    const PcPair &p = q.host[0];
-    if (u8) { a.vin = (const float *)p.p4[0]; a.vout = (float *)p.p4[1]; }
-    for (int v = 0; v < 2; ++v) {
-        const PcSide k = form == PC_PLANES ? pc_planes(pl, p.scratch, v) : PcSide{};
-        a.side[v] = PcSide{p.g[v].g1, p.g[v].g2, p.g[v].g3, p.g[v].g4, p.g[v ^ 1].g1, k.kcost, k.kdisp};
-        if (form == PC_KEYS) a.side[v].kcost = (float *)(p.keys + v * (size_t)W * H);
-    }
-    return a;
-}
-
+// The two-volume select launches for the pairs q, costs built on the fly: left volume = (g[0], other g[1].g1), right = (g[1], other
+// g[0].g1); 8-bit mode: the byte planes p4 of the left / right image; the minima: chunk planes in each pair's scratch, or its keys.
 void launch_cvf_select2(hipStream_t s, March m, const Recs<PcPair> &q, bool u8, int W, int H, int Dloc, int d_begin, unsigned long long *ts,
                         int sel, int step)
 {
     const PcPlan pl = pc_plan_select(m, W, H, Dloc, PC_PLANES, q.n, q.dev != nullptr);
     const PcLive lv = pc_live(W, pl.cols, pl.ngroups, Dloc, pl.DC, true, pc_own(m, d_begin, sel, step));
-    const unsigned long long rec_total = q.dev ? (unsigned long long)pl.rec_per_chunk * pl.nchunks : 0;   // (read by the batched form only)
-    const PcArgs a = pc_args2(m, pl, PC_PLANES, q, u8, W, H, Dloc, d_begin, PcSel{sel, step, pl.nxcd, 0, rec_total, m.dstep, lv}, ts);
-    pc_launch(s, pl, dim3(pc_blocks(pl, lv), 2, q.n), a, {PC_PLANES, 3, u8, pc_var(m, u8), q.dev != nullptr, pl.narrow, false});
+    const PcArgs a = {q, nullptr, nullptr, W, H, Dloc, m.y0(H), m.y1(H), d_begin,
+                      PcSel{sel, step, pl.nxcd, 0, pl.rec_per_chunk * pl.nchunks, m.dstep, lv}, ts};
+    pc_launch(s, pl, dim3(pc_blocks(pl, lv), 2, q.n), a, {PC_PLANES, 3, u8, pc_var(m, u8), pl.narrow, false});
 }
 
 void launch_chunk_min2sides(hipStream_t s, March m, const Recs<PcPair> &q, int W, int H, int Dloc, bool to_maps, int d_begin, int sel, int step)
@@ -1058,9 +1016,9 @@ void launch_cvf_select_keys2(hipStream_t s, March m, const Recs<PcPair> &q, bool
 {
     const PcPlan pl = pc_plan_select(m, W, H, Dloc, PC_KEYS, q.n, q.dev != nullptr);
     const PcLive lv = pc_live(W, pl.cols, pl.ngroups, Dloc, 1, false, pc_own(m, d_begin, sel, step));
-    const PcArgs a = pc_args2(m, pl, PC_KEYS, q, u8, W, H, Dloc, d_begin,
-                              PcSel{sel, step, pl.nxcd, PSM_KNOB("PSM_PC_SPREAD", PC_KEY_SPREAD), 0, m.dstep, lv}, ts);
-    pc_launch(s, pl, dim3(pc_blocks(pl, lv), 2, q.n), a, {PC_KEYS, 3, u8, pc_var(m, u8), q.dev != nullptr, pl.narrow, false});
+    const PcArgs a = {q, nullptr, nullptr, W, H, Dloc, m.y0(H), m.y1(H), d_begin,
+                      PcSel{sel, step, pl.nxcd, PSM_KNOB("PSM_PC_SPREAD", PC_KEY_SPREAD), 0, m.dstep, lv}, ts};
+    pc_launch(s, pl, dim3(pc_blocks(pl, lv), 2, q.n), a, {PC_KEYS, 3, u8, pc_var(m, u8), pl.narrow, false});
 }
 
 }  // namespace psm

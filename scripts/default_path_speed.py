@@ -1,4 +1,5 @@
-"""Speed of the default path, a parent checkout against this tree (profiles/default_path_records_speed.txt).
+"""Speed of the default path, a parent checkout against this tree (profiles/default_path_records_speed.txt,
+profiles/fused_filter_records_speed.txt).
 
   python scripts/default_path_speed.py run PARENT TREE OUTDIR [session]   alternating processes parent, tree, tree, parent, ... five
                                                                           each, every process under its own time limit; stops at the
@@ -9,6 +10,8 @@
 One process runs ROOT/bench.py (--gpus 1 --steps 20 --warmup 5) at c2, c1, c3, c4 and c2 --batch 8 and keeps ms_per_step, and at the
 same sizes takes the device time per frame of the kernel classes PSM_K_PREP, PSM_K_GUIDE, PSM_K_WTA and PSM_K_CVF_F under
 PSM_OPT_PROFILE 1 (20 frames after 3): the totals are dominated by the fused filter and would hide a change in the small kernels.
+The forms of the fused filter that bench.py does not run - one volume per launch, the storing form - give their PSM_K_CVF_F per frame
+at 450 x 375 x 64 and 1920 x 1080 x 64 (10 frames after 3).
 The bar: every median of the tree inside the parent's own min .. max of that quantity in that session."""
 import contextlib
 import io
@@ -22,6 +25,7 @@ import sys
 CONFIGS = (("c2", 1), ("c1", 1), ("c3", 1), ("c4", 1), ("c2", 8))
 CLASSES = ("PSM_K_PREP", "PSM_K_GUIDE", "PSM_K_WTA", "PSM_K_CVF_F")
 STEPS, WARMUP, FRAMES, N_EACH, LIMIT_S = 20, 5, 20, 5, 240
+FORM_SHAPES, FORM_FRAMES = ((450, 375, 64), (1920, 1080, 64)), 10
 
 
 def name(cfg, batch):
@@ -78,6 +82,33 @@ def classes(P, shape, dtype, batch):
             d.close()
 
 
+def forms(P, shape):
+    """PSM_K_CVF_F per frame of the fused filter's forms that bench.py does not run: one volume per launch (CostFilter_side 0, 1)
+    and the storing form (the default path under PSM_FLAG_STORE_FILTERED)."""
+    from primestereomatch_amd import capi, synth
+    W, H, D = shape
+    out = {}
+    with P.DispEst(*synth.make_pair(W, H, D, seed=0)[:2], D) as de:
+        def sides():
+            de.CostConst_GPU(); de.CostFilter_side(0); de.CostFilter_side(1)
+
+        def stored():
+            de.CostConst_GPU(); de.CostFilter_GPU()
+        de.set_option(capi.PSM_OPT_PROFILE, 1)
+        for form, frame, flags in (("one volume per launch", sides, 0), ("storing form", stored, capi.PSM_FLAG_STORE_FILTERED)):
+            de.set_option(capi.PSM_OPT_FLAGS, flags)
+            for _ in range(3):
+                frame()
+            de.synchronize()
+            de.reset_kernel_times()
+            for _ in range(FORM_FRAMES):
+                frame()
+            de.synchronize()
+            ms, n = de.kernel_time_ms(capi.PSM_K_CVF_F)
+            out[form] = {"PSM_K_CVF_F": {"ms_per_frame": round(ms / FORM_FRAMES, 5), "launches_per_frame": n / FORM_FRAMES}}
+    return out
+
+
 def one(root, label, out):
     root = os.path.abspath(root)
     sys.path.insert(0, root)
@@ -88,6 +119,9 @@ def one(root, label, out):
     for cfg, batch in CONFIGS:
         res["bench_ms_per_step"][name(cfg, batch)] = bench(root, cfg, batch)
         res["classes"][name(cfg, batch)] = classes(P, shapes[cfg][:3], "u8" if cfg.startswith("c1") else "f32", batch)
+    for shape in FORM_SHAPES:
+        for form, v in forms(P, shape).items():
+            res["classes"]["%d x %d x %d, %s" % (*shape, form)] = v
     line = json.dumps(res)
     print(line, flush=True)
     with open(out, "w") as f:

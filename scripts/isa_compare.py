@@ -6,7 +6,8 @@
     python scripts/isa_compare.py --focus k_prep,k_guide_march,k_chunk_min parent_FILE.s tree_FILE.s [more pairs ...]
 
 Every kernel of the tree is matched with the parent's kernel of the same demangled name; a focus kernel whose signature changed is
-matched with the parent's kernel of the same name and template head (its "role").  Per kernel: VGPRs, SGPRs, scratch, LDS,
+matched with the parent's kernel of the same name and template head (its "role": the leading non-type template arguments), a
+k_cvf_pc instantiation with the parent's of the same form and source (pair_key).  Per kernel: VGPRs, SGPRs, scratch, LDS,
 occupancy, the memory instructions by address space, and a verdict - identical / same sequence / same vector+memory+LDS multiset /
 DIFFERS with the counts that changed."""
 import argparse
@@ -72,26 +73,48 @@ def verdict(a, b):
         return "same instruction sequence, operands differ (registers / kernarg offsets)"
     ca = collections.Counter(m for m in ma if not is_scalar(m))
     cb = collections.Counter(m for m in mb if not is_scalar(m))
-    if ca == cb:
-        return "same VALU/memory/LDS instruction multiset; scalar set-up / order differs (%d -> %d instr)" % (len(a), len(b))
+    same = ca == cb
     ca, cb = collections.Counter(ma), collections.Counter(mb)
     d = ", ".join("%s %d -> %d" % (k, ca[k], cb[k]) for k in sorted(set(ca) | set(cb)) if ca[k] != cb[k])
+    if same:
+        return "same VALU/memory/LDS instruction multiset; scalar set-up / order differs (%d -> %d instr)%s" % (len(a), len(b), ": " + d if d else "")
     return "DIFFERS (%d -> %d instr): %s" % (len(a), len(b), d)
+
+
+def template_head(dem):
+    """(kernel name, its template arguments) of a demangled name"""
+    m = re.match(r"^(?:void )?(?:psm::)?(\w+)(?:<([^()]*?)>)?\(", dem)
+    if not m:
+        return dem, []
+    return m.group(1), [a.strip() for a in re.split(r",\s*(?![^<]*>)", m.group(2) or "") if a.strip()]
 
 
 def role(dem):
     """name + leading non-type template arguments: k_prep<true, ...> -> k_prep<true>"""
-    m = re.match(r"^(?:void )?(?:psm::)?(\w+)(?:<([^()]*?)>)?\(", dem)
-    if not m:
-        return dem
-    args = [a.strip() for a in re.split(r",\s*(?![^<]*>)", m.group(2) or "") if a.strip()]
+    name, args = template_head(dem)
     lead = []
     for a in args:
         if re.match(r"^(true|false|\(?\w*\)?-?\d+)$", a):
             lead.append(a)
         else:
             break
-    return m.group(1) + ("<" + ", ".join(lead) + ">" if lead else "")
+    return name + ("<" + ", ".join(lead) + ">" if lead else "")
+
+
+def pair_key(dem):
+    """What pairs a tree kernel with the parent's across a signature change: its role - and for k_cvf_pc the whole instantiation,
+    whose record source S took the place of a flag further back: <VEC4, CVC, MODE, U8, BATCH, VAR, NARROW> with BATCH = false is
+    <VEC4, CVC, MODE, S, U8, VAR, NARROW> over the pair by value, BATCH = true the one over the table."""
+    name, args = template_head(dem)
+    if name != "k_cvf_pc" or len(args) != 7:
+        return role(dem)
+    if source_of(dem):
+        v4, cvc, mode, _, u8, var, narrow = args
+        src = source_of(dem)
+    else:
+        v4, cvc, mode, u8, batch, var, narrow = args
+        src = "table" if batch == "true" else "value"
+    return "k_cvf_pc<%s> [%s]" % (", ".join((v4, cvc, mode, u8, var, narrow)), src)
 
 
 def source_of(dem):
@@ -121,7 +144,7 @@ def main():
         print("== %s -> %s: %d -> %d kernels ==" % (pf.split("/")[-1], tf.split("/")[-1], len(P), len(T)))
         by_role = collections.defaultdict(list)
         for n in P:
-            by_role[role(dp[n])].append(n)
+            by_role[pair_key(dp[n])].append(n)
         gone = set(P) - set(T)
         for n in sorted(T, key=lambda k: dt[k]):
             short = re.sub(r"^void ", "", dt[n]).split("(")[0]
@@ -134,19 +157,21 @@ def main():
                     print("    " + line(T[n][1], mem_mix(T[n][0])))
                     print("    " + v + ("".join(" | " + c for c in chg)))
                 continue
-            r = role(dt[n])
-            if not any(r == f or r.startswith(f + "<") for f in focus) or r not in by_role:
+            r, key = role(dt[n]), pair_key(dt[n])
+            if not any(r == f or r.startswith(f + "<") for f in focus) or key not in by_role:
                 print(short)
                 print("    " + line(T[n][1], mem_mix(T[n][0])))
                 print("    NEW: no kernel of this name in the parent")
                 counts["new"] += 1
                 continue
-            for pn in by_role[r]:
+            for pn in by_role[key]:
                 gone.discard(pn)
-                print("%s [%s]   against the parent's %s" % (r, source_of(dt[n]), role(dp[pn])))
+                print("%s   against the parent's %s" % (key if key != r else "%s [%s]" % (r, source_of(dt[n])),
+                                                        re.sub(r"^void (psm::)?", "", dp[pn]).split("(")[0] if key != r else role(dp[pn])))
                 print("    parent: " + line(P[pn][1], mem_mix(P[pn][0])))
                 print("    tree:   " + line(T[n][1], mem_mix(T[n][0])))
-                print("    " + verdict(P[pn][0], T[n][0]))
+                chg = ["%s %d -> %d" % (k, P[pn][1][k], T[n][1][k]) for k in sorted(T[n][1]) if P[pn][1].get(k) != T[n][1][k]]
+                print("    " + verdict(P[pn][0], T[n][0]) + "".join(" | " + c for c in chg))
                 counts["focus"] += 1
         for n in sorted(gone):
             print("GONE: " + re.sub(r"^void ", "", dp[n]).split("(")[0])

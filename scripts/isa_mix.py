@@ -26,12 +26,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "primestereomatch_amd", "csrc", "psm_pc.hip")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize"]
-# template arguments <VEC4, CVC, MODE, U8, BATCH, VAR, NARROW>
-KERNELS = {"planes_f32": "k_cvf_pcILb0ELi3ELi1ELb0ELb0ELi0ELb0EEE", "keys_f32": "k_cvf_pcILb0ELi3ELi2ELb0ELb0ELi0ELb0EEE",
-           "planes_u8": "k_cvf_pcILb0ELi3ELi1ELb1ELb0ELi0ELb0EEE", "keys_u8": "k_cvf_pcILb0ELi3ELi2ELb1ELb0ELi0ELb0EEE",
-           "planes_f32_fma": "k_cvf_pcILb0ELi3ELi1ELb0ELb0ELi2ELb0EEE", "keys_f32_fma": "k_cvf_pcILb0ELi3ELi2ELb0ELb0ELi2ELb0EEE",
-           "planes_f32_narrow": "k_cvf_pcILb0ELi3ELi1ELb0ELb0ELi0ELb1EEE", "keys_f32_narrow": "k_cvf_pcILb0ELi3ELi2ELb0ELb0ELi0ELb1EEE",
-           "planes_u8_narrow": "k_cvf_pcILb0ELi3ELi1ELb1ELb0ELi0ELb1EEE", "keys_u8_narrow": "k_cvf_pcILb0ELi3ELi2ELb1ELb0ELi0ELb1EEE"}
+# template arguments <VEC4, CVC, MODE, S, U8, VAR, NARROW>; S: the single pair's record by value, psm::RecVal<psm::PcPair, 1>
+VAL = "NS_6RecValINS_6PcPairELi1EEE"
+KERNELS = {name: "k_cvf_pcILb0ELi3ELi%dE%sLb%dELi%dELb%dEEE" % (mode, VAL, u8, var, narrow)
+           for name, mode, u8, var, narrow in (
+               ("planes_f32", 1, 0, 0, 0), ("keys_f32", 2, 0, 0, 0), ("planes_u8", 1, 1, 0, 0), ("keys_u8", 2, 1, 0, 0),
+               ("planes_f32_fma", 1, 0, 2, 0), ("keys_f32_fma", 2, 0, 2, 0), ("planes_f32_narrow", 1, 0, 0, 1),
+               ("keys_f32_narrow", 2, 0, 0, 1), ("planes_u8_narrow", 1, 1, 0, 1), ("keys_u8_narrow", 2, 1, 0, 1))}
 
 
 def classify(op, rest):

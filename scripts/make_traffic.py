@@ -62,8 +62,11 @@ def main():
         prev = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
     for cfg, dt, pre in cases:
         u8 = "true" if dt == "u8" else "false"
-        # (the sixth template argument was a bool before round 5's VAR, and round 5 added the layout argument NARROW: all spellings)
-        ks = {"planes": rf"k_cvf_pc<false, 3, 1, {u8}, false, (false|0)(, (false|true))?>", "keys": rf"k_cvf_pc<false, 3, 2, {u8}, false, (false|0)(, (false|true))?>"}
+        # The single pair's canon instantiations, in every spelling a session's summaries may hold: <VEC4, CVC, MODE, U8, BATCH, VAR,
+        # NARROW> (the sixth argument was a bool before round 5's VAR, and round 5 added the layout argument NARROW), and since the
+        # record source S took BATCH's place <VEC4, CVC, MODE, S, U8, VAR, NARROW> with S = RecVal<PcPair, 1>
+        tail = rf"({u8}, false, (false|0)(, (false|true))?|(psm::)?RecVal<(psm::)?PcPair, 1>, {u8}, 0, (false|true))>"
+        ks = {"planes": r"k_cvf_pc<false, 3, 1, " + tail, "keys": r"k_cvf_pc<false, 3, 2, " + tail}
         key = f"{cfg}:{dt}:k_cvf_fused"
         try:
             parts, insts = {}, {}

@@ -124,6 +124,16 @@ def test_planner_counts_live_items_at_1080p_256(lib):
     assert s["live_l"] == s["live_r"] == s["all"] == s["slices_l"] == s["ngroups"] * 256
 
 
+def test_layouts_of_the_side_order_shapes(lib):
+    """The shapes of tests/test_gpu_parity.py::test_right_side_first as the planner cuts their two-volume plane launch: one wide
+    column group; the narrow layout with three groups; the wide layout with two groups and more than one chunk, whatever the
+    device (DC <= 16 < 20 slices)."""
+    a, b, c = items(lib, 61, 21, 4, PLANES), items(lib, 120, 24, 9, PLANES), items(lib, 200, 33, 20, PLANES)
+    assert (a["cols"], a["ngroups"]) == (107, 1)
+    assert (b["cols"], b["ngroups"]) == (50, 3)
+    assert (c["cols"], c["ngroups"]) == (107, 2) and c["DC"] < 20
+
+
 @pytest.mark.parametrize("W", [150, 200, 300, 450, 1920])
 @pytest.mark.parametrize("d_begin,dstep,nsl_all", [(0, 1, 128), (96, 1, 32), (1, 4, 32), (0, 4, 32), (200, 1, 56), (0, 1, 1)])
 def test_enumerated_items_are_the_live_slices(lib, W, d_begin, dstep, nsl_all):

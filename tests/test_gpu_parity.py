@@ -641,6 +641,61 @@ def test_per_side_calls_equal_whole_stage_calls(psm, oracle):
             s.close()
 
 
+@pytest.fixture(scope="module")
+def side_order_refs(oracle):
+    """Per shape, computed once: a pair of unrelated images, one uploaded cost volume per side (unrelated too), and what the
+    oracle makes of them."""
+    cache = {}
+
+    def get(W, H, D):
+        if (W, H, D) not in cache:
+            l, r = rand_pair(H, W, 31)
+            rng = np.random.default_rng(32)
+            vols = [(rng.random((D, H, W), dtype=np.float32) * 2.7).astype(np.float32) for _ in range(2)]
+            up = {}
+            for side, img in enumerate((l, r)):
+                rgb, mean, var = oracle.cvf_preprocess(oracle.u8_to_f32(img))
+                q = np.stack([oracle.guided_filter(rgb, mean, var, vols[side][d]) for d in range(D)])
+                up["lr"[side] + "vol"], up["lr"[side] + "disp"] = q, oracle.wta(q)
+            cache[(W, H, D)] = {"l": l, "r": r, "vols": vols, "up": up,
+                                "f32": oracle.pipeline_f32(l, r, D, threads=4, want_volumes=True),
+                                "u8": oracle.pipeline_u8(l, r, D, threads=4, want_volumes=True)}
+        return cache[(W, H, D)]
+    return get
+
+
+@pytest.mark.parametrize("form", ["fly", "uploaded", "stored", "stored_uploaded", "u8", "both", "both_u8"])
+@pytest.mark.parametrize("W,H,D", [(61, 21, 4), (120, 24, 9), (200, 33, 20)])
+def test_right_side_first(psm, oracle, side_order_refs, W, H, D, form):
+    """One volume per launch, the RIGHT side before the left: each launch of the fused filter and its reduction must find its own
+    side's guidance, the other image, its byte planes, its chunk planes and its half of the keys.  Unrelated left / right images
+    (and uploaded volumes), so a launch that takes the other side's planes cannot pass.  Forms: float with costs on the fly,
+    float over uploaded volumes, the storing form (8192) over both, 8-bit mode; `both*`: the two-volume default path (control).
+    Shapes (tests/test_border_skip.py::test_layouts_of_the_side_order_shapes): one wide column group; narrow, three groups; wide,
+    two groups and several chunks.  Maps and volumes bit for bit against the oracle."""
+    from primestereomatch_amd import capi
+    R = side_order_refs(W, H, D)
+    u8, uploaded = form.endswith("u8"), form.endswith("uploaded")
+    ref = R["up"] if uploaded else R["u8" if u8 else "f32"]
+    with psm.DispEst(R["l"], R["r"], D, dtype="u8" if u8 else "f32") as de:
+        de.set_option(capi.PSM_OPT_FLAGS, capi.PSM_FLAG_STORE_FILTERED if form.startswith("stored") else 0)
+        if uploaded:
+            de.upload_volume(0, R["vols"][0])
+            de.upload_volume(1, R["vols"][1])
+        else:
+            de.CostConst_GPU()
+        if form.startswith("both"):
+            de.CostFilter_GPU()
+            de.DispSelect_GPU()
+        else:
+            for side in (1, 0):
+                de.CostFilter_side(side)
+                de.DispSelect_partial_side(side)
+            de.DispSelect_merge_ctx([de])
+        assert np.array_equal(de.lDisMap, ref["ldisp"]) and np.array_equal(de.rDisMap, ref["rdisp"])
+        assert np.array_equal(de.download_volume(0), ref["lvol"]) and np.array_equal(de.download_volume(1), ref["rvol"])
+
+
 @pytest.mark.parametrize("W,H,D,dtype,flags", [(260, 40, 200, "f32", 0), (260, 40, 200, "f32", 2097152), (230, 70, 37, "f32", 1048576),
                                                (260, 40, 200, "u8", 0), (214, 33, 19, "u8", 1048576), (108, 90, 2, "f32", 1048576),
                                                (108, 20, 7, "f32", 1048576)])
