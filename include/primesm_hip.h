@@ -921,7 +921,7 @@ int psm_wls_publish(psm_ctx *ctx, int on);
  * Refused - psm_last_error names the call, nothing has been enqueued, the previous maps are still current - for a NULL context
  * (psm_last_error(NULL)), NULL planes, an unknown depth, a stride below a row, a map_stride below W, a PSM_U8 context, a disparity
  * shard, a row stripe in force (psm_set_rows).
- * Out of scope: FrameRing, the Fast Guided Filter variant, 8-bit mode, rectified upload, and the tail stages that read
+ * Out of scope: FrameRing, 8-bit mode, rectified upload, and the tail stages that read
  * the image - psm_wgt_median, psm_joint_wmf, the guide of psm_wls_filter and the colours of psm_reproject's cloud keep reading
  * the staged colour pair.  psm_upload_pair* keep refusing 1 channel. */
 int psm_gray_compute(psm_ctx *ctx, const void *l, const void *r, size_t stride_bytes, int depth, uint8_t *lmap, uint8_t *rmap,
@@ -941,7 +941,30 @@ int psm_gray_compute(psm_ctx *ctx, const void *l, const void *r, size_t stride_b
  * psm_gray_compute refuses. */
 int psm_gray_compute_batch(psm_ctx *const *ctxs, int n, const void *const *ls, const void *const *rs, size_t stride_bytes, int depth,
                            uint8_t *const *lmaps, uint8_t *const *rmaps, size_t map_stride);
-/* Device ms of the launches of the last psm_gray_compute (guidance, every chunk, the maps); needs PSM_OPT_PROFILE. */
+/* psm_gray_compute with the Fast Guided Filter in place of the full-resolution one: FastGuidedFilterMono
+ * (src/fastguidedfilter.cpp:89-119), the one-channel half of the reference's FastGuidedFilter(I, 8, 1e-4, subsample_rate)
+ * (src/DispEst.cpp:281-296), as psm_cost_filter_fgf is its colour half.  The definition, which the device equals in every bit, is
+ * tests/gray_fgf_model.py: with s = subsample_rate in {2, 4, 8}, k = 2 (8 / s) + 1, nn = cv::resize(INTER_NN) to
+ * H / s x W / s, blur = cv::blur(Size(k, k)), up = cv::resize(INTER_LINEAR) back to H x W as psm_cost_filter_fgf has them: per side
+ * Is = nn(I), mI = blur(Is), den = (blur(Is Is) - mI mI) + 1e-4f; per slice ps = nn(cost), a = (blur(Is ps) - mI blur(ps)) / den (the
+ * reference's per-voxel quotient), b = blur(ps) - a mI, q = up(blur(a)) I + up(blur(b)); costs and selection are psm_gray_compute's.
+ * The cost is formed at the sampled pixels only; the stage's scratch is two chunks of at most 32 slices' {a, b} of both sides at the
+ * subsampled size, whatever max_disp is.  Arguments, state afterwards, stream and timer (psm_gray_time) are psm_gray_compute's;
+ * so are the refusals, plus a subsample_rate outside {2, 4, 8} and a W / s or H / s not above 8 / s (psm_cost_filter_fgf's bound).
+ * psm_gray_compute_fgf_batch is to it what psm_gray_compute_batch is to psm_gray_compute: 2 + 3 launches per chunk whatever n is.
+ * The hooks of one form are refused after a call of the other form: the planes belong to the last call of the stage.
+ * psm_gray_fgf_guidance: planes receives [3][H / s][W / s] floats of `side`: Is, mI, den.
+ * psm_gray_fgf_volume: the slices [d0, d1) of `side` through the storing instantiation of the same kernels: q receives
+ * [d1-d0][H][W] floats, model - may be NULL - [d1-d0][4][H / s][W / s]: a, b, blur(a), blur(b) of every slice.  The chunks of the
+ * walk begin at d0.  Keys and maps are not touched.  Both synchronise. */
+int psm_gray_compute_fgf(psm_ctx *ctx, const void *l, const void *r, size_t stride_bytes, int depth, int subsample_rate, uint8_t *lmap,
+                         uint8_t *rmap, size_t map_stride);
+int psm_gray_compute_fgf_batch(psm_ctx *const *ctxs, int n, const void *const *ls, const void *const *rs, size_t stride_bytes, int depth,
+                               int subsample_rate, uint8_t *const *lmaps, uint8_t *const *rmaps, size_t map_stride);
+int psm_gray_fgf_guidance(psm_ctx *ctx, int side, float *planes);
+int psm_gray_fgf_volume(psm_ctx *ctx, int side, int d0, int d1, float *q, float *model);
+/* Device ms of the launches of the last psm_gray_compute or psm_gray_compute_fgf (guidance, every chunk, the maps); needs
+ * PSM_OPT_PROFILE. */
 int psm_gray_time(psm_ctx *ctx, double *ms);
 /* Test hooks on the pair of the last psm_gray_compute (refused before any, and after psm_release_scratch).
  * psm_gray_guidance: planes receives [4][H][W] floats of `side`: I, G, mI, inv.

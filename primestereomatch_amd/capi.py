@@ -184,6 +184,10 @@ SYMBOLS = [
     ("psm_wls_conf_time", _i, [_vp, _pd]),
     ("psm_gray_compute", _i, [_vp, _vp, _vp, _sz, _i, _vp, _vp, _sz]),
     ("psm_gray_compute_batch", _i, [C.POINTER(_vp), _i, C.POINTER(_vp), C.POINTER(_vp), _sz, _i, C.POINTER(_vp), C.POINTER(_vp), _sz]),
+    ("psm_gray_compute_fgf", _i, [_vp, _vp, _vp, _sz, _i, _i, _vp, _vp, _sz]),
+    ("psm_gray_compute_fgf_batch", _i, [C.POINTER(_vp), _i, C.POINTER(_vp), C.POINTER(_vp), _sz, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _sz]),
+    ("psm_gray_fgf_guidance", _i, [_vp, _i, _vp]),
+    ("psm_gray_fgf_volume", _i, [_vp, _i, _i, _i, _vp, _vp]),
     ("psm_gray_time", _i, [_vp, _pd]),
     ("psm_gray_guidance", _i, [_vp, _i, _vp]),
     ("psm_gray_volume", _i, [_vp, _i, _i, _i, _vp, _vp]),

@@ -9,6 +9,9 @@
 // stage's key plane; k_gray_merge turns the keys into the maps.  The test hooks run the storing form of the same kernels.
 // psm_gray_compute_batch: the same launches for the pairs of several contexts at once, the pair on a grid axis - one host sequence,
 // gray_run, of which the single call is the n = 1 with the record by value.
+// psm_gray_compute_fgf / _batch: the same sequence with a subsample rate - FastGuidedFilterMono (src/fastguidedfilter.cpp:89-119;
+// psm_gray_fgf.hip, tests/gray_fgf_model.py): its prep launch, per chunk model, smooth and apply + select on planes
+// of the subsampled size, the same key plane, merge, state and timer.  Rate 0 is psm_gray_compute.
 #include "psm_ctx.h"
 
 #include <algorithm>
@@ -29,6 +32,11 @@ void gray_free(psm_ctx *c)
     }
     (void)hipFree(g.ab); g.ab = nullptr;
     (void)hipFree(g.keys); g.keys = nullptr;
+    for (int s = 0; s < 2; ++s) { (void)hipFree(g.fsm[s]); g.fsm[s] = nullptr; }
+    (void)hipFree(g.fab); g.fab = nullptr;
+    (void)hipFree(g.fmab); g.fmab = nullptr;
+    g.fsm_cap = g.fab_cap = 0;
+    g.rate = 0;
     table_free(g.pairs);
     bracket_free(g.prof);
     g.depth = -1;
@@ -48,31 +56,51 @@ int check_ctx(psm_ctx *e, const psm_ctx *c, const char *who)
     return 0;
 }
 
-int ensure_buffers(psm_ctx *c, const GrayPlan &pl)
+// fp: the plan of a psm_gray_compute_fgf, which needs the subsampled planes in place of mv and ab; null: psm_gray_compute
+int ensure_buffers(psm_ctx *c, const GrayPlan &pl, const GrayFgfPlan *fp)
 {
     GrayState &g = c->gray;
     const size_t HW = (size_t)c->W * c->H;
     for (int s = 0; s < 2; ++s) {
         if (!g.raw[s]) PSM_HIP(c, hipMalloc(&g.raw[s], HW * sizeof(float)));
         if (!g.ig[s]) PSM_HIP(c, hipMalloc((void **)&g.ig[s], HW * sizeof(float2)));
-        if (!g.mv[s]) PSM_HIP(c, hipMalloc((void **)&g.mv[s], HW * sizeof(float2)));
+        if (!fp && !g.mv[s]) PSM_HIP(c, hipMalloc((void **)&g.mv[s], HW * sizeof(float2)));
     }
-    if (!g.ab) PSM_HIP(c, hipMalloc((void **)&g.ab, 2 * (size_t)pl.dc * HW * sizeof(float2)));
+    if (!fp && !g.ab) PSM_HIP(c, hipMalloc((void **)&g.ab, 2 * (size_t)pl.dc * HW * sizeof(float2)));
     if (!g.keys) PSM_HIP(c, hipMalloc((void **)&g.keys, 2 * HW * sizeof(long long)));
+    if (!fp) return 0;
+    const size_t n = (size_t)fp->ws * fp->hs, nab = 2 * (size_t)fp->dc * n;
+    if (g.fsm_cap < n) {      // (a lower rate than any before: hipFree waits for whatever still reads the planes)
+        g.depth = -1;
+        for (int s = 0; s < 2; ++s) { (void)hipFree(g.fsm[s]); g.fsm[s] = nullptr; }
+        g.fsm_cap = 0;
+        for (int s = 0; s < 2; ++s) PSM_HIP(c, hipMalloc((void **)&g.fsm[s], n * sizeof(float4)));
+        g.fsm_cap = n;
+    }
+    if (g.fab_cap < nab) {
+        g.depth = -1;
+        (void)hipFree(g.fab); g.fab = nullptr;
+        (void)hipFree(g.fmab); g.fmab = nullptr;
+        g.fab_cap = 0;
+        PSM_HIP(c, hipMalloc((void **)&g.fab, nab * sizeof(float2)));
+        PSM_HIP(c, hipMalloc((void **)&g.fmab, nab * sizeof(float2)));
+        g.fab_cap = nab;
+    }
     return 0;
 }
 
 GrayPair pair_of(const psm_ctx *c)
 {
     const GrayState &g = c->gray;
-    return GrayPair{{g.raw[0], g.raw[1]}, {g.ig[0], g.ig[1]}, {g.mv[0], g.mv[1]}, g.ab, g.keys, c->maps};
+    return GrayPair{{g.raw[0], g.raw[1]}, {g.ig[0], g.ig[1]}, {g.mv[0], g.mv[1]}, g.ab, g.keys, c->maps, {g.fsm[0], g.fsm[1]}, g.fab, g.fmab};
 }
 
 // The host sequence of psm_gray_compute (its one context, the record by value) and of psm_gray_compute_batch (batch: the same
 // kernels over the device table of ctxs[0]), the arguments and every context checked: 2 + 2 ceil((D - 1) / dc) launches on ctxs[0]'s
 // stream whatever n is.  ls, rs, lmaps, rmaps: per member (the map arrays, or an entry, may be null).
+// rate: 0, or the subsample rate of psm_gray_compute_fgf / _batch (checked): 2 + 3 ceil((D - 1) / dc) launches.
 int gray_run(const char *who, psm_ctx *const *ctxs, int n, const void *const *ls, const void *const *rs, size_t stride_bytes, int depth,
-             uint8_t *const *lmaps, uint8_t *const *rmaps, size_t map_stride, bool batch)
+             uint8_t *const *lmaps, uint8_t *const *rmaps, size_t map_stride, bool batch, int rate)
 {
     psm_ctx *c0 = ctxs[0];
     if (bind(c0)) return 1;
@@ -80,10 +108,11 @@ int gray_run(const char *who, psm_ctx *const *ctxs, int n, const void *const *ls
     const int W = c0->W, H = c0->H, D = c0->D;
     const size_t row = (size_t)W * (depth == PSM_IMG_F32 ? sizeof(float) : 1);
     const GrayPlan pl = gray_plan(W, H, D, n);
+    const GrayFgfPlan fp = rate ? gray_fgf_plan(W, H, D, rate, n) : GrayFgfPlan{};
 
     // ---- buffers, events and the table's memory: before anything is ordered or launched ----
     for (int i = 0; i < n; ++i)
-        if (ensure_buffers(ctxs[i], pl)) return member_failed(c0, who, i, ctxs[i]);
+        if (ensure_buffers(ctxs[i], pl, rate ? &fp : nullptr)) return member_failed(c0, who, i, ctxs[i]);
     if (bracket_events(c0, c0->gray.prof) || batch_events(c0, ctxs, n)) return 1;
     std::vector<GrayPair> tab((size_t)n);
     for (int i = 0; i < n; ++i) tab[i] = pair_of(ctxs[i]);
@@ -119,10 +148,17 @@ int gray_run(const char *who, psm_ctx *const *ctxs, int n, const void *const *ls
 
     // ---- the launches: guidance and empty keys, the chunks of the slices 1 .. D - 1 (d = 0 is never a candidate), the maps ----
     if (bracket_open(c0, c0->gray.prof, s)) return 1;
-    launch_gray_prep(s, q, pl, W, H, depth == PSM_IMG_F32);
-    if (check_launch(c0, "k_gray_prep")) return 1;
-    for (int d = 1; d < D; d += pl.dc) launch_gray_chunk(s, q, pl, W, H, d, std::min(D, d + pl.dc));
-    if (check_launch(c0, "k_gray_ab, k_gray_q")) return 1;
+    if (rate) {
+        launch_grayf_prep(s, q, fp, W, H, depth == PSM_IMG_F32);
+        if (check_launch(c0, "k_grayf_prep")) return 1;
+        for (int d = 1; d < D; d += fp.dc) launch_grayf_chunk(s, q, fp, W, H, d, std::min(D, d + fp.dc));
+        if (check_launch(c0, "k_grayf_model, k_grayf_smooth, k_grayf_apply")) return 1;
+    } else {
+        launch_gray_prep(s, q, pl, W, H, depth == PSM_IMG_F32);
+        if (check_launch(c0, "k_gray_prep")) return 1;
+        for (int d = 1; d < D; d += pl.dc) launch_gray_chunk(s, q, pl, W, H, d, std::min(D, d + pl.dc));
+        if (check_launch(c0, "k_gray_ab, k_gray_q")) return 1;
+    }
     launch_gray_merge(s, q, W, H);
     if (check_launch(c0, "k_gray_merge")) return 1;
     if (bracket_close(c0, c0->gray.prof, s)) return 1;
@@ -132,6 +168,7 @@ int gray_run(const char *who, psm_ctx *const *ctxs, int n, const void *const *ls
     for (int i = 0; i < n; ++i) {
         psm_ctx *c = ctxs[i];
         c->gray.depth = depth;
+        c->gray.rate = rate;
         forget_early(c->res);
         cover(c->res, whole_image(c));
         maps_written(c->res);
@@ -143,39 +180,41 @@ int gray_run(const char *who, psm_ctx *const *ctxs, int n, const void *const *ls
     return 0;
 }
 
-// the hooks: the planes of a psm_gray_compute must exist
-int check_hook(psm_ctx *c, const char *who, int side)
+// the hooks: the planes of a psm_gray_compute (fgf: of a psm_gray_compute_fgf) must exist
+int check_hook(psm_ctx *c, const char *who, int side, bool fgf = false)
 {
     if (check_ctx(c, c, who)) return 1;
-    if (c->gray.depth < 0) return fail(c, "%s: no pair (psm_gray_compute; psm_release_scratch gives it back)", who);
+    if (c->gray.depth < 0) return fail(c, "%s: no pair (%s; psm_release_scratch gives it back)", who, fgf ? "psm_gray_compute_fgf" : "psm_gray_compute");
+    if (fgf != (c->gray.rate != 0))
+        return fail(c, "%s: the planes belong to %s (the last call of the stage)", who, c->gray.rate ? "psm_gray_compute_fgf" : "psm_gray_compute");
     if (side != PSM_LEFT && side != PSM_RIGHT) return fail(c, "%s: bad side %d", who, side);
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int psm_gray_compute(psm_ctx *c, const void *l, const void *r, size_t stride_bytes, int depth, uint8_t *lmap, uint8_t *rmap, size_t map_stride)
+// what both single entries check of the call's arguments; *stride_bytes 0 becomes the packed row
+int check_call(psm_ctx *c, const char *who, const void *l, const void *r, size_t *stride_bytes, int depth, size_t map_stride)
 {
-    const char *who = "psm_gray_compute";
-    if (!c) return fail(nullptr, "%s: NULL context", who);
-    if (check_ctx(c, c, who)) return 1;
     if (!l || !r) return fail(c, "%s: NULL image", who);
     if (depth != PSM_IMG_U8 && depth != PSM_IMG_F32) return fail(c, "%s: unknown depth %d", who, depth);
     const size_t row = (size_t)c->W * (depth == PSM_IMG_F32 ? sizeof(float) : 1);
-    if (stride_bytes == 0) stride_bytes = row;
-    if (stride_bytes < row) return fail(c, "%s: stride %zu < row size %zu", who, stride_bytes, row);
+    if (*stride_bytes == 0) *stride_bytes = row;
+    if (*stride_bytes < row) return fail(c, "%s: stride %zu < row size %zu", who, *stride_bytes, row);
     if (map_stride != 0 && map_stride < (size_t)c->W) return fail(c, "%s: map stride %zu < width %d", who, map_stride, c->W);
-    return gray_run(who, &c, 1, &l, &r, stride_bytes, depth, &lmap, &rmap, map_stride, false);
+    return 0;
 }
 
-// The launches of psm_gray_compute with the pair on a grid axis.  Planes, chunk scratch and keys stay per context; the kernels
-// reach them through a device table ctxs[0] owns.  Every context ends where its own psm_gray_compute would have left it.
-int psm_gray_compute_batch(psm_ctx *const *ctxs, int n, const void *const *ls, const void *const *rs, size_t stride_bytes, int depth,
-                           uint8_t *const *lmaps, uint8_t *const *rmaps, size_t map_stride)
+// the rate of psm_gray_compute_fgf / _batch on a context of c's size: psm_cost_filter_fgf's bounds
+int check_rate(psm_ctx *c, const char *who, int rate)
 {
-    const char *who = "psm_gray_compute_batch";
+    if (rate != 2 && rate != 4 && rate != 8) return fail(c, "%s: subsample_rate %d not in {2,4,8}", who, rate);
+    if (c->W / rate <= 8 / rate || c->H / rate <= 8 / rate) return fail(c, "%s: %dx%d too small for subsample_rate %d", who, c->W, c->H, rate);
+    return 0;
+}
+
+// the batch entries' checks: the members, then the call's arguments; rate: of psm_gray_compute_fgf_batch, else null
+int check_batch(const char *who, psm_ctx *const *ctxs, int n, const void *const *ls, const void *const *rs, size_t *stride_bytes, int depth,
+                size_t map_stride, const int *rate)
+{
     if (!ctxs) return fail(nullptr, "%s: NULL ctxs", who);
     if (n < 1) return fail(nullptr, "%s: n %d below 1", who, n);
     psm_ctx *c0 = ctxs[0];
@@ -197,10 +236,50 @@ int psm_gray_compute_batch(psm_ctx *const *ctxs, int n, const void *const *ls, c
         if (!ls[i] || !rs[i]) return fail(c0, "%s: context %d: NULL image", who, i);
     if (depth != PSM_IMG_U8 && depth != PSM_IMG_F32) return fail(c0, "%s: unknown depth %d", who, depth);
     const size_t row = (size_t)c0->W * (depth == PSM_IMG_F32 ? sizeof(float) : 1);
-    if (stride_bytes == 0) stride_bytes = row;
-    if (stride_bytes < row) return fail(c0, "%s: stride %zu < row size %zu", who, stride_bytes, row);
+    if (*stride_bytes == 0) *stride_bytes = row;
+    if (*stride_bytes < row) return fail(c0, "%s: stride %zu < row size %zu", who, *stride_bytes, row);
     if (map_stride != 0 && map_stride < (size_t)c0->W) return fail(c0, "%s: map stride %zu < width %d", who, map_stride, c0->W);
-    return gray_run(who, ctxs, n, ls, rs, stride_bytes, depth, lmaps, rmaps, map_stride, true);
+    return rate ? check_rate(c0, who, *rate) : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int psm_gray_compute(psm_ctx *c, const void *l, const void *r, size_t stride_bytes, int depth, uint8_t *lmap, uint8_t *rmap, size_t map_stride)
+{
+    const char *who = "psm_gray_compute";
+    if (!c) return fail(nullptr, "%s: NULL context", who);
+    if (check_ctx(c, c, who) || check_call(c, who, l, r, &stride_bytes, depth, map_stride)) return 1;
+    return gray_run(who, &c, 1, &l, &r, stride_bytes, depth, &lmap, &rmap, map_stride, false, 0);
+}
+
+// psm_gray_compute with FastGuidedFilterMono in place of the full-resolution filter: the same sequence with the rate
+int psm_gray_compute_fgf(psm_ctx *c, const void *l, const void *r, size_t stride_bytes, int depth, int subsample_rate, uint8_t *lmap, uint8_t *rmap,
+                         size_t map_stride)
+{
+    const char *who = "psm_gray_compute_fgf";
+    if (!c) return fail(nullptr, "%s: NULL context", who);
+    if (check_ctx(c, c, who) || check_call(c, who, l, r, &stride_bytes, depth, map_stride) || check_rate(c, who, subsample_rate)) return 1;
+    return gray_run(who, &c, 1, &l, &r, stride_bytes, depth, &lmap, &rmap, map_stride, false, subsample_rate);
+}
+
+// The launches of psm_gray_compute with the pair on a grid axis.  Planes, chunk scratch and keys stay per context; the kernels
+// reach them through a device table ctxs[0] owns.  Every context ends where its own psm_gray_compute would have left it.
+int psm_gray_compute_batch(psm_ctx *const *ctxs, int n, const void *const *ls, const void *const *rs, size_t stride_bytes, int depth,
+                           uint8_t *const *lmaps, uint8_t *const *rmaps, size_t map_stride)
+{
+    const char *who = "psm_gray_compute_batch";
+    if (check_batch(who, ctxs, n, ls, rs, &stride_bytes, depth, map_stride, nullptr)) return 1;
+    return gray_run(who, ctxs, n, ls, rs, stride_bytes, depth, lmaps, rmaps, map_stride, true, 0);
+}
+
+int psm_gray_compute_fgf_batch(psm_ctx *const *ctxs, int n, const void *const *ls, const void *const *rs, size_t stride_bytes, int depth,
+                               int subsample_rate, uint8_t *const *lmaps, uint8_t *const *rmaps, size_t map_stride)
+{
+    const char *who = "psm_gray_compute_fgf_batch";
+    if (check_batch(who, ctxs, n, ls, rs, &stride_bytes, depth, map_stride, &subsample_rate)) return 1;
+    return gray_run(who, ctxs, n, ls, rs, stride_bytes, depth, lmaps, rmaps, map_stride, true, subsample_rate);
 }
 
 int psm_gray_guidance(psm_ctx *c, int side, float *planes)
@@ -258,10 +337,65 @@ int psm_gray_volume(psm_ctx *c, int side, int d0, int d1, float *q, float *ab)
     return rc;
 }
 
+int psm_gray_fgf_guidance(psm_ctx *c, int side, float *planes)
+{
+    const char *who = "psm_gray_fgf_guidance";
+    if (!c) return fail(nullptr, "%s: NULL context", who);
+    if (check_hook(c, who, side, true)) return 1;
+    if (!planes) return fail(c, "%s: NULL buffer", who);
+    if (bind(c)) return 1;
+    const size_t n = (size_t)(c->W / c->gray.rate) * (c->H / c->gray.rate);
+    std::vector<float4> sm(n);
+    PSM_HIP(c, hipMemcpyAsync(sm.data(), c->gray.fsm[side], n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    PSM_HIP(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < n; ++i) {
+        planes[i] = sm[i].x; planes[n + i] = sm[i].y; planes[2 * n + i] = sm[i].z;
+    }
+    return 0;
+}
+
+int psm_gray_fgf_volume(psm_ctx *c, int side, int d0, int d1, float *q, float *model)
+{
+    const char *who = "psm_gray_fgf_volume";
+    if (!c) return fail(nullptr, "%s: NULL context", who);
+    if (check_hook(c, who, side, true)) return 1;
+    if (d0 < 0 || d1 > c->D || d0 >= d1) return fail(c, "%s: slices [%d,%d) not inside [0,%d)", who, d0, d1, c->D);
+    if (!q) return fail(c, "%s: NULL buffer", who);
+    if (bind(c)) return 1;
+    const GrayFgfPlan fp = gray_fgf_plan(c->W, c->H, c->D, c->gray.rate);
+    const GrayPair p = pair_of(c);
+    const size_t HW = (size_t)c->W * c->H, n = (size_t)fp.ws * fp.hs;
+    float *qdev = nullptr;
+    PSM_HIP(c, hipMalloc((void **)&qdev, (size_t)fp.dc * HW * sizeof(float)));
+    std::vector<float2> abh(model ? (size_t)fp.dc * n : 0), mabh(abh.size());
+    int rc = 0;
+    // chunk by chunk through the storing form; the chunks begin at d0
+    for (int d = d0; d < d1 && !rc; d += fp.dc) {
+        const int e = std::min(d1, d + fp.dc);
+        const size_t nq = (size_t)(e - d) * HW, nm = (size_t)(e - d) * n, off = (size_t)side * fp.dc * n;
+        launch_grayf_chunk_store(c->stream, p, fp, c->W, c->H, side, d, e, qdev);
+        rc = check_launch(c, "k_grayf_model, k_grayf_smooth, k_grayf_apply");
+        if (!rc && hipMemcpyAsync(q + (size_t)(d - d0) * HW, qdev, nq * sizeof(float), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+            rc = fail(c, "%s: hipMemcpyAsync", who);
+        if (!rc && model && (hipMemcpyAsync(abh.data(), c->gray.fab + off, nm * sizeof(float2), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                             hipMemcpyAsync(mabh.data(), c->gray.fmab + off, nm * sizeof(float2), hipMemcpyDeviceToHost, c->stream) != hipSuccess))
+            rc = fail(c, "%s: hipMemcpyAsync", who);
+        if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(c, "%s: hipStreamSynchronize", who);
+        for (size_t i = 0; model && !rc && i < nm; ++i) {      // [slice][4][hs][ws]: a, b, blur(a), blur(b)
+            const size_t z = i / n, px = i - z * n;
+            float *dst = model + ((size_t)(d - d0) + z) * 4 * n;
+            dst[px] = abh[i].x; dst[n + px] = abh[i].y;
+            dst[2 * n + px] = mabh[i].x; dst[3 * n + px] = mabh[i].y;
+        }
+    }
+    (void)hipFree(qdev);
+    return rc;
+}
+
 int psm_gray_time(psm_ctx *c, double *ms)
 {
     if (!c) return fail(nullptr, "psm_gray_time: NULL context");
-    return bracket_ms(c, c->gray.prof, c->gray.depth >= 0, "psm_gray_time", "the last psm_gray_compute was not timed (PSM_OPT_PROFILE), or there is none", ms);
+    return bracket_ms(c, c->gray.prof, c->gray.depth >= 0, "psm_gray_time", "the last psm_gray_compute / psm_gray_compute_fgf was not timed (PSM_OPT_PROFILE), or there is none", ms);
 }
 
 }  // extern "C"

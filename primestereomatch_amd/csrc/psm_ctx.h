@@ -236,6 +236,11 @@ struct GrayState {
     float2 *ab = nullptr;                          // [2][gray_plan().dc][H][W] {a, b} of one chunk of slices
     long long *keys = nullptr;                     // [2][H][W]: this stage's packed minima (ctx->keys belongs to the colour path)
     int depth = -1;                                // PSM_IMG_* of the last call's pair, which the planes hold; -1: none
+    // psm_gray_compute_fgf: the subsampled planes, allocated on its first use and grown when a call needs more (a lower rate)
+    float4 *fsm[2] = {nullptr, nullptr};           // [hs][ws] {Is, mI, den, 0}
+    float2 *fab = nullptr, *fmab = nullptr;        // [2][gray_fgf_plan().dc][hs][ws] {a, b} and {blur(a), blur(b)} of one chunk of slices
+    size_t fsm_cap = 0, fab_cap = 0;               // elements of each fsm plane; of fab and of fmab
+    int rate = 0;                                  // the call the planes belong to: 0 psm_gray_compute, else the rate of psm_gray_compute_fgf
     Bracket prof;                                  // PSM_OPT_PROFILE: around the launches (psm_gray_time)
     DevTable pairs;                                // psm_gray_compute_batch (this context as the first of a batch): GrayPair records
 };

@@ -483,6 +483,10 @@ struct GrayPair {                                      // one pair's buffers: a 
     float2 *ab;                        // the chunk scratch [2][dc][H][W] {a, b}
     long long *keys;                   // [2][H][W] packed minima of this stage (not the colour path's)
     uint8_t *maps;                     // [2][H][W]: the context's map buffer (k_gray_merge)
+    // psm_gray_compute_fgf (psm_gray_fgf.hip) alone; hs = H / s, ws = W / s
+    float4 *fsm[2];                    // [hs][ws] {Is, mI, den, 0}: the subsampled guidance
+    float2 *fab;                       // the chunk scratch [2][dc][hs][ws] {a, b}
+    float2 *fmab;                      // ... and [2][dc][hs][ws] {blur(a), blur(b)}
 };
 struct GrayPlan { int nstrips, nsegs, seg_rows, dc; };   // strips of GRAY_COLS columns, segments of seg_rows rows, slices per chunk
 // for the device the calling thread is bound to (pc_dev); n: the pairs that share every launch - seg_rows alone depends on it
@@ -494,5 +498,16 @@ void launch_gray_chunk(hipStream_t s, const Recs<GrayPair> &q, const GrayPlan &g
 // ... the storing form (the test hooks'), one side of one pair by value: q into qvol [dend - dbeg][H][W]; {a, b} of the slices are in p.ab
 void launch_gray_chunk_store(hipStream_t s, const GrayPair &p, const GrayPlan &g, int W, int H, int side, int dbeg, int dend, float *qvol);
 void launch_gray_merge(hipStream_t s, const Recs<GrayPair> &q, int W, int H);   // k_gray_merge: keys -> maps of every pair
+
+// psm_gray_fgf.hip: FastGuidedFilterMono over a one-channel pair (psm_gray_compute_fgf, psm_api_gray.cpp)
+struct GrayFgfPlan { int sub, k, ws, hs, nstrips, nsegs, seg, dc; };   // rate, taps, subsampled size; strips of 64 - 2 (k / 2) columns, segments of seg rows, slices per chunk
+// n: the pairs that share every launch - seg alone depends on it (and on D)
+GrayFgfPlan gray_fgf_plan(int W, int H, int D, int sub, int n = 1);
+// k_grayf_prep: ig and fsm of both sides of every pair; keys = no candidate
+void launch_grayf_prep(hipStream_t s, const Recs<GrayPair> &q, const GrayFgfPlan &g, int W, int H, bool f32);
+// k_grayf_model, k_grayf_smooth, k_grayf_apply over the slices [dbeg, dend) (at most g.dc) of both sides of every pair: minima into its keys
+void launch_grayf_chunk(hipStream_t s, const Recs<GrayPair> &q, const GrayFgfPlan &g, int W, int H, int dbeg, int dend);
+// ... the storing form (the test hooks'), one side of one pair by value: q into qvol [dend - dbeg][H][W]; the model planes of the slices are in p.fab, p.fmab
+void launch_grayf_chunk_store(hipStream_t s, const GrayPair &p, const GrayFgfPlan &g, int W, int H, int side, int dbeg, int dend, float *qvol);
 
 }  // namespace psm

@@ -27,6 +27,7 @@ def _ptr(a):
 
 class DispEst:
     _sgm_d = 0                               # the disparities of the last SGBM_GPU (0: none yet - maxDis)
+    _gray_rate = 0                               # the subsample rate of the last Gray_GPU / gray_batch (0: the full-resolution filter)
     _sgm_ch = 3                                  # the channels of the pair the last SGBM_GPU ran on (1: its gray= pair)
 
     def __init__(self, l, r, d: int, t: int = 8, ocl: bool = True, *, dtype: str = "f32",
@@ -263,11 +264,13 @@ class DispEst:
         return None
 
     # ---- the guided-filter path over a one-channel pair (psm_gray_compute) --------------------------
-    def Gray_GPU(self, gl, gr, download: bool = True):
+    def Gray_GPU(self, gl, gr, download: bool = True, subsample_rate: int = 0):
         """Cost build, one-channel guided filter and winner-takes-all of the monochrome pair (gl, gr) - two H x W planes, uint8 or
         float32 (uint8 is scaled by 1/255 as setInputImages scales) - in one call; the definition is tests/gray_model.py.  The maps
         land in the object's device maps, where LRCheck_GPU, FillInv_GPU, Score_GPU(PSM_SCORE_GIF), Reproject_GPU and
         download_maps() find them; the staged colour pair, the volumes and whatever CostFilter_GPU left pending are untouched.
+        subsample_rate 2, 4 or 8: the Fast Guided Filter in place of the full-resolution one (psm_gray_compute_fgf,
+        FastGuidedFilterMono; the definition is tests/gray_fgf_model.py); 0: every bit as without the argument.
         -> (lDisMap, rDisMap); download=False: the maps stay on the device, None."""
         gl, gr = np.asarray(gl), np.asarray(gr)
         if gl.shape != (self.hei, self.wid) or gr.shape != gl.shape or gl.dtype != gr.dtype:
@@ -281,8 +284,13 @@ class DispEst:
         if gl.strides[1] != gl.itemsize or gr.strides != gl.strides or gl.strides[0] < self.wid * gl.itemsize:
             gl, gr = np.ascontiguousarray(gl), np.ascontiguousarray(gr)      # (rows with a pitch go as they are)
         lm, rm = (_ptr(self.lDisMap), _ptr(self.rDisMap)) if download else (None, None)
-        self._ck(self._lib.psm_gray_compute(self._h, _ptr(gl), _ptr(gr), gl.strides[0], depth, lm, rm, self.wid if download else 0),
-                 "Gray_GPU")
+        if subsample_rate:
+            self._ck(self._lib.psm_gray_compute_fgf(self._h, _ptr(gl), _ptr(gr), gl.strides[0], depth, int(subsample_rate), lm, rm,
+                                                    self.wid if download else 0), "Gray_GPU")
+        else:
+            self._ck(self._lib.psm_gray_compute(self._h, _ptr(gl), _ptr(gr), gl.strides[0], depth, lm, rm, self.wid if download else 0),
+                     "Gray_GPU")
+        self._gray_rate = int(subsample_rate)
         return (self.lDisMap, self.rDisMap) if download else None
 
     def gray_guidance(self, side: int):
@@ -300,6 +308,24 @@ class DispEst:
         ab = np.empty((n, 2, self.hei, self.wid), np.float32) if want_ab else None
         self._ck(self._lib.psm_gray_volume(self._h, int(side), int(d0), d1, _ptr(q), _ptr(ab)), "gray_volume")
         return (q, ab) if want_ab else q
+
+    def gray_fgf_guidance(self, side: int):
+        """Test hook: [3][H/s][W/s] float32 - Is, mI, den - of `side` of the last Gray_GPU(subsample_rate=s)'s pair."""
+        s = self._gray_rate or 1
+        planes = np.empty((3, self.hei // s, self.wid // s), np.float32)
+        self._ck(self._lib.psm_gray_fgf_guidance(self._h, int(side), _ptr(planes)), "gray_fgf_guidance")
+        return planes
+
+    def gray_fgf_volume(self, side: int, d0: int = 0, d1: int | None = None, want_model: bool = False):
+        """Test hook: the filtered slices [d0, d1) of `side` of the last Gray_GPU(subsample_rate=s)'s pair through the storing form
+        of its kernels: q [d1-d0][H][W] float32, and - want_model - [d1-d0][4][H/s][W/s]: a, b, blur(a), blur(b) of every slice."""
+        s = self._gray_rate or 1
+        d1 = self.maxDis if d1 is None else int(d1)
+        n = max(d1 - int(d0), 0)
+        q = np.empty((n, self.hei, self.wid), np.float32)
+        model = np.empty((n, 4, self.hei // s, self.wid // s), np.float32) if want_model else None
+        self._ck(self._lib.psm_gray_fgf_volume(self._h, int(side), int(d0), d1, _ptr(q), _ptr(model)), "gray_fgf_volume")
+        return (q, model) if want_model else q
 
     def gray_time(self):
         """Device ms of the launches of the last Gray_GPU; needs PSM_OPT_PROFILE."""
@@ -953,12 +979,12 @@ def wls_batch(des, source: int = capi.PSM_WLS_SGM, use_mask: bool = False, confi
     return None if des[0].options.get(capi.PSM_OPT_ASYNC) else [d.wls_map() for d in des]
 
 
-def gray_batch(des, gls=(), grs=(), download: bool = True):
+def gray_batch(des, gls=(), grs=(), download: bool = True, subsample_rate: int = 0):
     """Gray_GPU of several DispEst objects of one geometry in one set of launches (psm_gray_compute_batch): object i takes the
     monochrome pair (gls[i], grs[i]) - H x W planes, all uint8 or all float32.  Every object afterwards behaves as after its own
     Gray_GPU (LRCheck_GPU, Score_GPU(PSM_SCORE_GIF), download_maps(), the gray_* hooks).  -> the list of (lDisMap, rDisMap) of the
     objects; download=False: the maps stay on the device, a list of None.  gray_time() of des[0] is the batch's
-    (PSM_OPT_PROFILE)."""
+    (PSM_OPT_PROFILE).  subsample_rate 2, 4 or 8: Gray_GPU(subsample_rate=...) of every object (psm_gray_compute_fgf_batch)."""
     des, gls, grs = list(des), [np.asarray(g) for g in gls], [np.asarray(g) for g in grs]
     if len(gls) != len(des) or len(grs) != len(des):
         raise ValueError("gray_batch: one (gl, gr) pair per object")
@@ -982,8 +1008,14 @@ def gray_batch(des, gls=(), grs=(), download: bool = True):
     rs = (C.c_void_p * n)(*[g.ctypes.data for g in grs])
     lm = (C.c_void_p * n)(*[d.lDisMap.ctypes.data for d in des]) if download else None
     rm = (C.c_void_p * n)(*[d.rDisMap.ctypes.data for d in des]) if download else None
-    capi.check(des[0]._lib.psm_gray_compute_batch(arr, n, ls, rs, gls[0].strides[0], depth, lm, rm, shape[1] if download else 0),
-               des[0]._h, "gray_batch")
+    if subsample_rate:
+        capi.check(des[0]._lib.psm_gray_compute_fgf_batch(arr, n, ls, rs, gls[0].strides[0], depth, int(subsample_rate), lm, rm,
+                                                          shape[1] if download else 0), des[0]._h, "gray_batch")
+    else:
+        capi.check(des[0]._lib.psm_gray_compute_batch(arr, n, ls, rs, gls[0].strides[0], depth, lm, rm, shape[1] if download else 0),
+                   des[0]._h, "gray_batch")
+    for d in des:
+        d._gray_rate = int(subsample_rate)
     return [(d.lDisMap, d.rDisMap) if download else None for d in des]
 
 

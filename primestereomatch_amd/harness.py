@@ -167,17 +167,18 @@ def compute_sgbm(l_bgr, r_bgr, maxDis=64, gt=None, mask=None, scale_factor=4, er
 
 
 def compute_gray(gl, gr, maxDis=64, gt=None, mask=None, scale_factor=4, error_threshold=4, lr_check=True, fill=False,
-                 device_tail=False, verbose=False):
+                 device_tail=False, verbose=False, subsample_rate=0):
     """One frame of STEREO_GIF for a monochrome pair: gl / gr are H x W planes, uint8 or float32 scaled by 1/255, and go through
     the one-channel guided filter in one call (DispEst.Gray_GPU; no colour pair is staged).  lr_check: the L-R check behind it
     (lValid / rValid); fill: fillInv after it - the selected maps then stay in lDisMap_raw / rDisMap_raw.  The tail stages that
-    read the image (wgtMedian, JointWMF) need a colour pair and are not offered.  device_tail: compute()'s.
+    read the image (wgtMedian, JointWMF) need a colour pair and are not offered.  device_tail: compute()'s.  subsample_rate 2, 4
+    or 8: the Fast Guided Filter (FastGuidedFilterMono) in place of the full-resolution filter.
     -> compute()'s record with gray_ms, the device time of the call; of the stage times cvf_ms repeats it, the others are 0."""
     out = {}
     gl, gr = np.asarray(gl), np.asarray(gr)
     with DispEst.blank(gl.shape[0], gl.shape[1], maxDis) as SMDE:
         SMDE.set_option(capi.PSM_OPT_PROFILE, 1)
-        SMDE.Gray_GPU(gl, gr)
+        SMDE.Gray_GPU(gl, gr, subsample_rate=subsample_rate)
         out["gray_ms"] = SMDE.gray_time()
         if lr_check or fill:
             SMDE.LRCheck_GPU()
@@ -194,11 +195,11 @@ def compute_gray(gl, gr, maxDis=64, gt=None, mask=None, scale_factor=4, error_th
 
 
 def compute_gray_batch(pairs, maxDis=64, gts=None, masks=None, scale_factor=4, error_threshold=4, lr_check=True, fill=False,
-                       device_tail=False, verbose=False):
+                       device_tail=False, verbose=False, subsample_rate=0):
     """compute_gray for a list of (gl, gr) monochrome pairs of one size and one depth (all uint8, or all float32) in shared
     launches (dispest.gray_batch): the reference's loop over pairs and datasets (src/main.cpp:64-73).  gts / masks: one per pair (or
     None).  lr_check / fill: compute_gray's, the stages of all pairs in shared launches (dispest.post_process_batch); device_tail:
-    display maps and metrics of all pairs from the device (dispest.score_batch).
+    display maps and metrics of all pairs from the device (dispest.score_batch); subsample_rate: compute_gray's.
     -> a list of compute_gray's records; gray_ms is the batch's device time divided by the number of pairs."""
     pairs = [(np.asarray(gl), np.asarray(gr)) for gl, gr in pairs]
     if not pairs:
@@ -208,7 +209,7 @@ def compute_gray_batch(pairs, maxDis=64, gts=None, masks=None, scale_factor=4, e
     outs = [{} for _ in pairs]
     try:
         des[0].set_option(capi.PSM_OPT_PROFILE, 1)
-        dispest.gray_batch(des, [p[0] for p in pairs], [p[1] for p in pairs])
+        dispest.gray_batch(des, [p[0] for p in pairs], [p[1] for p in pairs], subsample_rate=subsample_rate)
         ms = des[0].gray_time() / len(des)
         if lr_check or fill:
             dispest.post_process_batch(des, lr_check=True)

@@ -337,19 +337,32 @@ int DispEst::sgbmMapsTime(double *ms)
     return hipUtil::api().sgm_maps_time(ctx[0], ms);
 }
 
-int DispEst::Gray_GPU(const Mat &gl, const Mat &gr)
+int DispEst::grayRun(const Mat &gl, const Mat &gr, int rate)
 {
+    const char *who = rate ? "GrayFGF_GPU" : "Gray_GPU";
     if (ctx.size() != 1) {
-        fprintf(stderr, "DispEst: Gray_GPU runs on single-device objects only\n");
+        fprintf(stderr, "DispEst: %s runs on single-device objects only\n", who);
         return 1;
     }
     if (gl.channels != 1 || gr.channels != 1 || gl.rows != hei || gl.cols != wid || gr.rows != hei || gr.cols != wid || gl.depth != gr.depth ||
         gl.step != gr.step) {
-        fprintf(stderr, "DispEst: Gray_GPU wants two one-channel Mats of the object's size, of one depth and step\n");
+        fprintf(stderr, "DispEst: %s wants two one-channel Mats of the object's size, of one depth and step\n", who);
         return 1;
     }
-    return hipUtil::api().gray_compute(ctx[0], gl.data, gr.data, gl.step, gl.depth == PSM_32F ? PSM_IMG_F32 : PSM_IMG_U8, lDisMap.data,
-                                       rDisMap.data, lDisMap.step);
+    const int depth = gl.depth == PSM_32F ? PSM_IMG_F32 : PSM_IMG_U8;
+    if (rate) return hipUtil::api().gray_compute_fgf(ctx[0], gl.data, gr.data, gl.step, depth, rate, lDisMap.data, rDisMap.data, lDisMap.step);
+    return hipUtil::api().gray_compute(ctx[0], gl.data, gr.data, gl.step, depth, lDisMap.data, rDisMap.data, lDisMap.step);
+}
+
+int DispEst::Gray_GPU(const Mat &gl, const Mat &gr) { return grayRun(gl, gr, 0); }
+
+int DispEst::GrayFGF_GPU(const Mat &gl, const Mat &gr)
+{
+    if (subsample_rate != 2 && subsample_rate != 4 && subsample_rate != 8) {
+        fprintf(stderr, "DispEst: GrayFGF_GPU: subsample_rate %u not in {2,4,8}\n", subsample_rate);
+        return 1;
+    }
+    return grayRun(gl, gr, (int)subsample_rate);
 }
 
 int DispEst::grayTime(double *ms)
@@ -541,7 +554,20 @@ int DispEst::WLSBatch(DispEst *const *des, int n, int source, int flags)
     return hipUtil::api().wls_filter_batch(cs.data(), n, source, flags);
 }
 
-int DispEst::GrayBatch(DispEst *const *des, int n, const Mat *gls, const Mat *grs)
+int DispEst::GrayBatch(DispEst *const *des, int n, const Mat *gls, const Mat *grs) { return grayBatchRun(des, n, gls, grs, 0, "GrayBatch"); }
+
+int DispEst::GrayFGFBatch(DispEst *const *des, int n, const Mat *gls, const Mat *grs)
+{
+    if (!des || n < 1 || !des[0]) return 1;
+    const unsigned int s = des[0]->subsample_rate;
+    if (s != 2 && s != 4 && s != 8) {
+        fprintf(stderr, "DispEst: GrayFGFBatch: subsample_rate %u not in {2,4,8}\n", s);
+        return 1;
+    }
+    return grayBatchRun(des, n, gls, grs, (int)s, "GrayFGFBatch");
+}
+
+int DispEst::grayBatchRun(DispEst *const *des, int n, const Mat *gls, const Mat *grs, int rate, const char *who)
 {
     if (!des || n < 1 || !gls || !grs) return 1;
     std::vector<psm_ctx *> cs;
@@ -549,13 +575,13 @@ int DispEst::GrayBatch(DispEst *const *des, int n, const Mat *gls, const Mat *gr
     std::vector<uint8_t *> lm, rm;
     for (int i = 0; i < n; ++i) {
         if (!des[i] || des[i]->ctx.size() != 1) {
-            fprintf(stderr, "DispEst: GrayBatch runs on single-device objects only\n");
+            fprintf(stderr, "DispEst: %s runs on single-device objects only\n", who);
             return 1;
         }
         const DispEst &d = *des[i];
         for (const Mat *m : {&gls[i], &grs[i]})
             if (m->channels != 1 || m->rows != d.hei || m->cols != d.wid || m->depth != gls[0].depth || m->step != gls[0].step) {
-                fprintf(stderr, "DispEst: GrayBatch wants one-channel Mats of the objects' size, of one depth and step\n");
+                fprintf(stderr, "DispEst: %s wants one-channel Mats of the objects' size, of one depth and step\n", who);
                 return 1;
             }
         if (d.lDisMap.step != des[0]->lDisMap.step || d.rDisMap.step != des[0]->lDisMap.step) return 1;
@@ -565,8 +591,11 @@ int DispEst::GrayBatch(DispEst *const *des, int n, const Mat *gls, const Mat *gr
         lm.push_back(d.lDisMap.data);
         rm.push_back(d.rDisMap.data);
     }
-    return hipUtil::api().gray_compute_batch(cs.data(), n, ls.data(), rs.data(), gls[0].step, gls[0].depth == PSM_32F ? PSM_IMG_F32 : PSM_IMG_U8,
-                                             lm.data(), rm.data(), des[0]->lDisMap.step);
+    const int depth = gls[0].depth == PSM_32F ? PSM_IMG_F32 : PSM_IMG_U8;
+    if (rate)
+        return hipUtil::api().gray_compute_fgf_batch(cs.data(), n, ls.data(), rs.data(), gls[0].step, depth, rate, lm.data(), rm.data(),
+                                                     des[0]->lDisMap.step);
+    return hipUtil::api().gray_compute_batch(cs.data(), n, ls.data(), rs.data(), gls[0].step, depth, lm.data(), rm.data(), des[0]->lDisMap.step);
 }
 
 double DispEst::stageTimeUs(int stage) const

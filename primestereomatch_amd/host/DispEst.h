@@ -146,6 +146,10 @@ public:
     // Single-device objects only.  grayTime: device ms of the call under PSM_OPT_PROFILE.
     int Gray_GPU(const Mat &gl, const Mat &gr);
     int grayTime(double *ms);
+    // ... with the Fast Guided Filter in place of the full-resolution one (psm_gray_compute_fgf: FastGuidedFilterMono,
+    // src/fastguidedfilter.cpp:89-119), s = subsample_rate (setSubsampleRate: 2, 4 or 8) - to Gray_GPU what CostFilter_FGF_GPU is to
+    // CostFilter_GPU.  Everything else is Gray_GPU's.
+    int GrayFGF_GPU(const Mat &gl, const Mat &gr);
 
     // The steps of StereoMatch::compute behind the maps, on the device (psm_score): setGroundTruth uploads the dataset's ground truth
     // and (mask non-NULL) error mask once, H x W CV_8UC1 each; setScoreParams: scale_factor, error_threshold, PSM_MASK_NONE / NONOCC /
@@ -230,6 +234,8 @@ public:
     // lDisMap / rDisMap are filled and it is afterwards where its own Gray_GPU would have left it; grayTime of des[0] reports the
     // batch.
     static int GrayBatch(DispEst *const *des, int n, const Mat *gls, const Mat *grs);
+    // ... GrayFGF_GPU of the n objects (psm_gray_compute_fgf_batch), at the subsample_rate of des[0]
+    static int GrayFGFBatch(DispEst *const *des, int n, const Mat *gls, const Mat *grs);
 
     // psm_set_option on every device's context (PSM_OPT_FLAGS: e.g. PSM_FLAG_FMA_SOLVE - the maps of a reference binary built for an
     // FMA target -, PSM_OPT_SEG_ROWS, PSM_OPT_GATHER_STAGED, PSM_OPT_FRAMES_IN_FLIGHT ...; include/primesm_hip.h).  0 = ok.
@@ -244,6 +250,8 @@ private:
     int hei, wid, maxDis, threads;
     bool useOCL;
     unsigned int subsample_rate = 4;
+    int grayRun(const Mat &gl, const Mat &gr, int rate);      // Gray_GPU (rate 0) and GrayFGF_GPU
+    static int grayBatchRun(DispEst *const *des, int n, const Mat *gls, const Mat *grs, int rate, const char *who);
     std::vector<psm_ctx *> ctx;  // one per device (row stripes of ceil(H / ndev) rows)
     std::vector<int> y0s, y1s;   // their stripes
     int rect_src_w = 0, rect_src_h = 0;   // setRectification: the eye images' size

@@ -74,7 +74,8 @@ bool hipUtil::load(const char *path)
               bind(g_api.wls_set_confidence, "psm_wls_set_confidence") && bind(g_api.wls_download_confidence, "psm_wls_download_confidence") &&
               bind(g_api.wls_conf_time, "psm_wls_conf_time") &&
               bind(g_api.wls_filter_batch, "psm_wls_filter_batch") && bind(g_api.gray_compute, "psm_gray_compute") &&
-              bind(g_api.gray_compute_batch, "psm_gray_compute_batch") && bind(g_api.gray_time, "psm_gray_time");
+              bind(g_api.gray_compute_batch, "psm_gray_compute_batch") && bind(g_api.gray_time, "psm_gray_time") &&
+              bind(g_api.gray_compute_fgf, "psm_gray_compute_fgf") && bind(g_api.gray_compute_fgf_batch, "psm_gray_compute_fgf_batch");
     if (!ok) {
         fprintf(stderr, "%s\n", g_error.c_str());
         dlclose(g_handle);

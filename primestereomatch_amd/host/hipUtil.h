@@ -93,6 +93,9 @@ struct HipApi {
     int (*gray_compute_batch)(psm_ctx *const *, int, const void *const *, const void *const *, size_t, int, uint8_t *const *, uint8_t *const *,
                               size_t) = nullptr;
     int (*gray_time)(psm_ctx *, double *) = nullptr;
+    int (*gray_compute_fgf)(psm_ctx *, const void *, const void *, size_t, int, int, uint8_t *, uint8_t *, size_t) = nullptr;
+    int (*gray_compute_fgf_batch)(psm_ctx *const *, int, const void *const *, const void *const *, size_t, int, int, uint8_t *const *,
+                                  uint8_t *const *, size_t) = nullptr;
 };
 
 class hipUtil {

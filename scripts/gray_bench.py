@@ -20,7 +20,16 @@ ms at all three configurations.  Every build of the library measured - this tree
 parent commit's, which has no batch: its loop of single calls and its single calls alone) - runs in child processes of its own,
 through ctypes on the few symbols both builds have, --rounds times in alternation; a child warms up, then repeats --runs times.
 Reported per build: the best and the median over all of its repeats, and the spread of its rounds' bests (max - min).  The block
-is printed as JSON lines and, with --out, appended to that file."""
+is printed as JSON lines and, with --out, appended to that file.
+
+--fgf S: psm_gray_compute_fgf at subsample rate S (2, 4 or 8) instead.  Per configuration, in one process and one session, --warmup
+rounds, then --runs rounds that alternate three paths; reported are the best and the median of
+  fgf_ms         psm_gray_time of psm_gray_compute_fgf: device events around its launches
+  colour_fgf_ms  device events on the stream around the unchanged colour FGF path - psm_cost_construct + psm_cost_filter_fgf +
+                 psm_disp_select - on the tripled plane: the only fast mode a mono user had before, and the yardstick
+  gray_ms        psm_gray_time of psm_gray_compute, the full-resolution one-channel filter
+and fgf_ms over colour_fgf_ms (best over best).  Then, at 450 x 375 x 64, psm_gray_compute_fgf_batch: device ms per pair in
+batches of 2 / 4 / 8 (psm_gray_time of the first context over n) beside a loop of 8 single calls on 8 contexts, alternating."""
 import argparse
 import ctypes as C
 import functools
@@ -92,6 +101,100 @@ def bench(torch, name, warmup, runs):
         rec[key] = {"best": round(min(v), 4), "median": round(float(np.median(v)), 4)}
     rec["gray_over_colour"] = round(min(g_ms) / min(c_ms), 4)
     rec["maps_differ_percent"] = round(100.0 * float(np.mean(gmaps[0] != cmaps[0])), 2)      # two different filters: for scale only
+    return rec
+
+
+# ---- --fgf ---------------------------------------------------------------------------------------------------------------
+def fgf_bench(torch, name, s, warmup, runs):
+    import primestereomatch_amd as P
+    from primestereomatch_amd import capi
+    W, H, D = CONFIGS[name]
+    gl, gr = the_planes(name)
+    l3, r3 = (np.ascontiguousarray(np.repeat(g[:, :, None], 3, axis=2)) for g in (gl, gr))
+    stream = torch.cuda.Stream()
+    with P.DispEst.blank(H, W, D) as df, P.DispEst.blank(H, W, D) as dg, P.DispEst(l3, r3, D) as dc:
+        for d in (df, dg, dc):
+            d.set_stream(stream.cuda_stream)
+            d.set_option(capi.PSM_OPT_ASYNC, 1)
+        df.set_option(capi.PSM_OPT_PROFILE, 1)
+        dg.set_option(capi.PSM_OPT_PROFILE, 1)
+        dc.setSubsampleRate(s)
+
+        def colour():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            dc.CostConst_GPU()
+            dc.CostFilter_FGF_GPU()
+            dc._ck(dc._lib.psm_disp_select(dc._h, None, None, 0), "disp_select")
+            b.record(stream)
+            b.synchronize()
+            return a.elapsed_time(b)
+
+        def fgf():
+            df.Gray_GPU(gl, gr, download=False, subsample_rate=s)
+            return df.gray_time()
+
+        def gray():
+            dg.Gray_GPU(gl, gr, download=False)
+            return dg.gray_time()
+
+        paths = {"fgf_ms": fgf, "colour_fgf_ms": colour, "gray_ms": gray}
+        for _ in range(warmup):
+            for f in paths.values():
+                f()
+        res = {k: [] for k in paths}
+        for _ in range(runs):
+            for k, f in paths.items():
+                res[k].append(f())
+        fmaps = [m.copy() for m in df.download_maps()]
+        cmaps = [m.copy() for m in dc.download_maps()]
+    rec = {"config": name, "size": f"{W}x{H}x{D}", "fgf": s, "warmup": warmup, "runs": runs}
+    for key, v in res.items():
+        rec[key] = {"best": round(min(v), 4), "median": round(float(np.median(v)), 4)}
+    rec["fgf_over_colour_fgf"] = round(min(res["fgf_ms"]) / min(res["colour_fgf_ms"]), 4)
+    rec["maps_differ_percent"] = round(100.0 * float(np.mean(fmaps[0] != cmaps[0])), 2)      # one plane against three equal ones: for scale only
+    return rec
+
+
+def fgf_batch_bench(name, s, warmup, runs):
+    """ms per pair: batches of 2 / 4 / 8 beside a loop of LOOP single calls, alternating"""
+    import primestereomatch_amd as P
+    from primestereomatch_amd import capi
+    W, H, D = CONFIGS[name]
+    gl, gr = the_planes(name)
+    planes = [(np.ascontiguousarray(np.roll(gl, k, axis=0)), np.ascontiguousarray(np.roll(gr, k, axis=0))) for k in range(LOOP)]
+    des = [P.DispEst.blank(H, W, D) for _ in range(LOOP)]
+    try:
+        for d in des:
+            d.set_option(capi.PSM_OPT_PROFILE, 1)
+
+        def loop():
+            ms = 0.0
+            for d, (l, r) in zip(des, planes):
+                d.Gray_GPU(l, r, download=False, subsample_rate=s)
+                ms += d.gray_time()
+            return ms / LOOP
+
+        def batch(n):
+            P.gray_batch(des[:n], [p[0] for p in planes[:n]], [p[1] for p in planes[:n]], download=False, subsample_rate=s)
+            return des[0].gray_time() / n
+
+        forms = {f"loop{LOOP}": loop}
+        for n in (2, 4, 8):
+            forms[f"batch{n}"] = functools.partial(batch, n)
+        for _ in range(warmup):
+            for f in forms.values():
+                f()
+        res = {k: [] for k in forms}
+        for _ in range(runs):
+            for k, f in forms.items():
+                res[k].append(f())
+    finally:
+        for d in des:
+            d.close()
+    rec = {"block": "fgf batch", "unit": "device ms per pair", "config": name, "size": f"{W}x{H}x{D}", "fgf": s, "warmup": warmup, "runs": runs}
+    for k, v in res.items():
+        rec[k] = {"best": round(min(v), 4), "median": round(float(np.median(v)), 4)}
     return rec
 
 
@@ -214,6 +317,7 @@ def batch_bench(a):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--batch", action="store_true", help="psm_gray_compute_batch beside a loop of single calls")
+    ap.add_argument("--fgf", type=int, choices=(2, 4, 8), help="psm_gray_compute_fgf at this rate beside the colour FGF path and psm_gray_compute")
     ap.add_argument("--parent-lib", help="--batch: another build of libprimesm_hip.so to measure in alternation (single calls only)")
     ap.add_argument("--rounds", type=int, default=2, help="--batch: child processes per build")
     ap.add_argument("--worker", help=argparse.SUPPRESS)
@@ -232,8 +336,14 @@ def main():
     capi.load()
     if capi.device_count() < 1 or not torch.cuda.is_available():
         raise SystemExit("gray_bench: no HIP device visible (there is no CPU path to time)")
-    for name in a.config or ["cones", "720p", "1080p"]:
-        line = json.dumps(bench(torch, name, a.warmup, a.runs))
+    names = a.config or ["cones", "720p", "1080p"]
+    if a.fgf:
+        lines = (json.dumps(fgf_bench(torch, name, a.fgf, a.warmup, a.runs)) for name in names)
+        if "cones" in names:
+            lines = list(lines) + [json.dumps(fgf_batch_bench("cones", a.fgf, a.warmup, a.runs))]
+    else:
+        lines = (json.dumps(bench(torch, name, a.warmup, a.runs)) for name in names)
+    for line in lines:
         print(line, flush=True)
         if a.out:
             with open(a.out, "a") as f:
