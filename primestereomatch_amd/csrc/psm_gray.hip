@@ -222,7 +222,8 @@ __device__ __forceinline__ void gray_q_step(const GrayQIn<NS> &in, const GrayPos
     const int step = i + K;
     const bool st = step >= 7 && step < pos.n && pos.ovalid;
     const unsigned o = (unsigned)(pos.ybase + step - 3) * (unsigned)W + (unsigned)pos.xo;      // (used under st alone)
-    long long best = 0x7fffffffffffffffll;
+    float bq = __builtin_inff();
+    int bd = 0;
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
         const float ma = box_out(vstep<K>(t[s][0], hsum8(in.ab[s][K].x, i1, i2, i4)));
@@ -231,12 +232,18 @@ __device__ __forceinline__ void gray_q_step(const GrayQIn<NS> &in, const GrayPos
         if (STORE) {
             if (st && live[s]) qout[s][o] = q;
         } else {
-            // d = 0 is never a candidate (src/DispSel.cpp:96); ascending slots: the lower disparity wins an exact tie by its key
-            const long long key = pack_key_f32(q, d[s]);
-            if (live[s] && d[s] > 0 && key < best) best = key;
+            // d = 0 is never a candidate (src/DispSel.cpp:96); ascending slots, strict <: the lower disparity keeps an exact tie.
+            // The wave's slices meet as floats, not as keys: a NaN q fails the compare whatever its sign, so it never wins - as a
+            // key, a NaN with the sign bit set (an input 0xFFC00000 carried through, or the device's own 0 * inf) sorts below
+            // every finite cost.  What reaches the key plane is never a NaN: (+inf, 0) where no slice was a candidate.
+            // (Two selects, no branch: && here became a scalar branch per slice and cost 4 % of the call.)
+            const bool take = (q < bq) & live[s] & (d[s] > 0);
+            bq = take ? q : bq;
+            bd = take ? d[s] : bd;
         }
     }
     if (!STORE && st) {
+        const long long best = pack_key_f32(bq, bd);      // across waves and chunks the key's low word lets the lower d win a tie
         if (best < keys[o]) (void)__hip_atomic_fetch_min(keys + o, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
